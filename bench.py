@@ -1,6 +1,6 @@
 """bench.py -- images/sec of the Faster R-CNN R50-FPN 800x1344 bf16 inference hot path on N MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--batch B]
+    python bench.py --gpus N --steps K --warmup W [--batch B] [--dump-outputs DIR] [--full]
 
 --gpus is authoritative.  Under a launcher (WORLD_SIZE in the environment, e.g. python -m torch.distributed.run --nnodes=1
 --nproc-per-node N ... bench.py --gpus N ...) WORLD_SIZE must equal N, else the run stops with exit code 2.  Without a launcher
@@ -13,7 +13,9 @@ class-wise NMS + packing) over one batch of synthetic COCO-shaped images already
 followed, when N > 1, by the single all_gather of the padded detections.  Images are
 sharded across ranks (weak scaling: B images per GPU); value = N*B*K / max-over-ranks time.
 
-The JSON line also carries
+A plain run sets up, runs W warmup steps and the K timed steps, and prints the line; --dump-outputs DIR writes what the last timed step
+returned (write_outputs) before the line is printed.  Everything else the line can carry is measured only with --full; without it those
+fields are null.  With --full the JSON line also carries
   roofline     -- the DOMINANT conv kernel by time (md_conv2d_last_kernel attributes every launch; each is bracketed by
                   HIP events on the launch stream) against the roofline that binds its launches in aggregate
                   (algorithmic flops / 2.5 PFLOP/s dense bf16 or algorithmic bytes / 8 TB/s), its PMC traffic from
@@ -21,6 +23,7 @@ The JSON line also carries
                   (incl. frac_of_layerwise_roofline = sum of per-launch max(flops/peak, bytes/peak) / measured time).
   cpu_baseline -- the oracle's plain fp32 torch-CPU restatement of the same graph (oracle/nets.py) timed on this
                   host's cores on a bounded sample (rank 0, N=1 only).
+  from_uint8, two_streams, one_stream, mask_paste, nms_prefix, host_enqueue_ms_single_step -- see main().
 The batch is resident in HBM in the model's input layout (zero-bordered 4-channel NHWC for the fused stem) before the timed
 region; --from-uint8 also times md_image_preprocess from a resident uint8 batch.
 """
@@ -71,6 +74,11 @@ def parse_args(argv=None):
                          "single-stream pass AFTER the timed region (a launch's duration under overlap includes the other stream's share of the CUs)")
     ap.add_argument("--no-zero-operands", action="store_true",
                     help="skip the zero-operand replay of the dominant kernel (roofline.zero_operands)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: roofline (incl. --dump-convs, --bracket), cpu_baseline, "
+                         "from_uint8, two_streams, one_stream, mask_paste, nms_prefix, host_enqueue_ms_single_step")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step as DIR/<name>.npy (write_outputs)")
     return ap.parse_args(argv)
 
 
@@ -152,7 +160,7 @@ def make_step(model_forward, images, use_dist, gatherer=None, preprocess=None):
         x = images if preprocess is None else preprocess()
         out = model_forward(x)
         if not use_dist:
-            pending["out"] = (out[0], out[1])
+            pending["out"] = tuple(out)
             return pending["out"]
         prev = pending["h"]
         pending["h"] = gatherer(out)
@@ -198,6 +206,34 @@ def run_timed(step, finish, steps, warmup, use_dist, sync, barrier, all_reduce_m
     if use_dist:
         dt = all_reduce_max(dt)
     return dt
+
+
+OUTPUT_NAMES = ("dets", "count", "masks")   # the detectors' forward() outputs, in order
+DUMP_LIMIT_BYTES = 64 * 10**6   # all .npy files of one run, headers included
+
+
+def write_outputs(out_dir, outputs, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: each output of the last timed step as <out_dir>/<name>.npy -- floating outputs as float32 (float64 stays float64),
+    integer ones as float64 (exact).  All files together stay within `limit` bytes: an output larger than its share is written as a fixed
+    sample of its flattened elements (sorted distinct indices from default_rng(0), the same for the same shape), so that two builds run
+    with the same arguments can be compared element for element."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    outs = [(OUTPUT_NAMES[i] if i < len(OUTPUT_NAMES) else f"out{i}", t) for i, t in enumerate(outputs) if t is not None]
+    left = limit
+    for k, (name, t) in enumerate(sorted(outs, key=lambda o: o[1].numel())):   # small outputs first: they are never sampled
+        td = torch.float32 if t.is_floating_point() and t.dtype != torch.float64 else torch.float64
+        a = t.detach()
+        cap = max(left // (len(outs) - k) - 256, 0) // td.itemsize   # 256: room for the .npy header
+        if a.numel() > cap:
+            idx = np.unique(np.random.default_rng(0).integers(0, a.numel(), cap))
+            a = a.reshape(-1)[torch.from_numpy(idx).to(a.device)]
+        arr = a.to(td).cpu().numpy()
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, arr)
+        left -= os.path.getsize(path)
 
 
 def kernel_source_hash():
@@ -272,6 +308,12 @@ def main(argv=None):
     args = parse_args(argv)
     if args.gpus < 1:
         sys.stderr.write("bench.py: --gpus must be >= 1\n")
+        return 2
+    if args.steps < 1:
+        sys.stderr.write("bench.py: --steps must be >= 1\n")
+        return 2
+    if args.dump_convs and not args.full:
+        sys.stderr.write("bench.py: --dump-convs needs --full (the per-launch table comes from the roofline instrumentation)\n")
         return 2
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and (args.gpus > 1 or args.spawn):
@@ -488,8 +530,8 @@ def main(argv=None):
 
         args.no_roofline = True
         captured = CapturedStep(lambda xx: tuple(model.forward(xx))[:2], images)
-        step, finish = (lambda: captured(images)), (lambda: None)   # noqa: E731
-    instrument = not args.no_roofline
+        step, finish = (lambda: captured(images)), (lambda: captured.static_out)   # noqa: E731
+    instrument = args.full and not args.no_roofline
     if splitter is not None and instrument and (args.bracket != "dominant" or args.dump_convs or args.warmup < 1):
         raise SystemExit("bench.py: with --streams > 1 the roofline pass is --bracket dominant, --warmup >= 1, no --dump-convs (use --streams 1 for those)")
     survey = []            # records of ONE fully bracketed step (the last warmup step): the whole-set table in --bracket dominant
@@ -526,6 +568,8 @@ def main(argv=None):
     dt = run_timed(step, finish, args.steps, args.warmup, use_dist, torch.cuda.synchronize,
                    lambda: dist.barrier(device_ids=[local_rank]), all_reduce_max, before_timed, on_warmup)
     instrument_off()
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, finish())   # before anything below runs the model again
     one_stream = None
     if instrument and splitter is not None and survey:
         # two streams: the dominant kernel's launches are bracketed in a serialized pass of the same steps on ONE stream, outside `dt`
@@ -547,16 +591,19 @@ def main(argv=None):
     host_enqueue_ms = None if HOST_ENQUEUE["s"] is None else HOST_ENQUEUE["s"] / max(args.steps, 1) * 1e3
     # ... and of ONE step enqueued into an empty queue (device idle before, no synchronisation until the host is done): the pure cost of
     # Python + ctypes + launches, free of any back-pressure of a full queue that the in-run figure may contain
-    torch.cuda.synchronize()
-    t_h0 = time.perf_counter()
-    step()
-    host_single_ms = (time.perf_counter() - t_h0) * 1e3
-    finish()
-    torch.cuda.synchronize()
+    host_single_ms = None
+    if args.full:
+        torch.cuda.synchronize()
+        t_h0 = time.perf_counter()
+        step()
+        host_single_ms = (time.perf_counter() - t_h0) * 1e3
+        finish()
+        torch.cuda.synchronize()
 
     # the end-to-end figure from a resident uint8 batch (md_image_preprocess inside the step), next to the resident-layout one
     from_u8 = None
-    if not args.from_uint8 and not args.no_from_uint8 and not args.graph and rank == 0 and not use_dist and hasattr(nn_ops, "image_preprocess"):
+    if (args.full and not args.from_uint8 and not args.no_from_uint8 and not args.graph and rank == 0 and not use_dist
+            and hasattr(nn_ops, "image_preprocess")):
         u8, mat = make_u8()
         step2, finish2 = make_step(forward, images, False, None, lambda: (u8, mat))
         k2 = max(2, min(args.steps, 5))
@@ -569,8 +616,8 @@ def main(argv=None):
     # the same steps with the batch as two halves on two HIP streams (graphs.SplitForward), when the config runs on one: a secondary figure --
     # `value` stays the one-stream run whose launches the roofline block brackets
     two_streams = None
-    if (splitter is None and n_streams == 1 and B % 2 == 0 and hasattr(model, "forward_split") and rank == 0 and not use_dist and not args.graph
-            and not args.no_from_uint8 and images_u8 is None):
+    if (args.full and splitter is None and n_streams == 1 and B % 2 == 0 and hasattr(model, "forward_split") and rank == 0 and not use_dist
+            and not args.graph and not args.no_from_uint8 and images_u8 is None):
         from minddet_amd.graphs import SplitForward
 
         sp2 = SplitForward(model, 2)
@@ -728,7 +775,7 @@ def main(argv=None):
 
     # Mask R-CNN: the pasting launch on its own (HBM-write-bound: H * W / 8 bytes per detection slot), from the last step's outputs
     mask_paste = None
-    if rank == 0 and hasattr(model, "mask_head") and not args.graph:
+    if args.full and rank == 0 and hasattr(model, "mask_head") and not args.graph:
         from minddet_amd import det_ops
 
         out_m = model.forward(images, paste=False)
@@ -747,7 +794,7 @@ def main(argv=None):
 
     is_frcnn = type(model).__name__ == "FasterRCNN"
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and is_frcnn:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and is_frcnn:
         from oracle import nets
 
         try:
@@ -783,7 +830,7 @@ def main(argv=None):
             # host time per step spent ENQUEUING (Python + ctypes + launches) in the timed region, before the closing device sync: well
             # under ms_per_step = the device is the bottleneck and N Python ranks on one node are not launch-bound
             "host_enqueue_ms_per_step": None if host_enqueue_ms is None else round(host_enqueue_ms, 3),
-            "host_enqueue_ms_single_step": round(host_single_ms, 3),
+            "host_enqueue_ms_single_step": None if host_single_ms is None else round(host_single_ms, 3),
             "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
             "config": {"workload": wl, "batch_per_gpu": B, "streams": n_streams,
@@ -792,7 +839,7 @@ def main(argv=None):
             "roofline": roofline, "cpu_baseline": cpu_baseline, "from_uint8": from_u8, "two_streams": two_streams, "one_stream": one_stream, "mask_paste": mask_paste,
             # images (over every step of this run) whose class-wise NMS saw a FULL top-nms_pre prefix and fewer than max_det
             # survivors: only those can differ from the NMS over every candidate (DESIGN.md "pre-NMS prefix"); read after timing
-            "nms_prefix": None if not hasattr(model, "prefix_status") else {
+            "nms_prefix": None if not (args.full and hasattr(model, "prefix_status")) else {
                 "nms_pre": getattr(getattr(model, "roi_head", model), "nms_pre", None), "image_slots_flagged": model.prefix_status.flagged()},
             "lib": os.path.relpath(_lib.LIB_PATH, ROOT),
         }

@@ -152,6 +152,40 @@ def test_gpus_flag_is_authoritative():
     assert r.returncode == 2
 
 
+def test_bench_refuses_zero_steps_and_dump_convs_without_full():
+    """both refused before any GPU call: a run of 0 timed steps has no ms_per_step, and the per-launch table needs --full's instrumentation"""
+    r = _run_bench(["--steps", "0"])
+    assert r.returncode == 2 and "--steps" in r.stderr and "{" not in r.stdout
+    r = _run_bench(["--steps", "1", "--dump-convs", "convs.json"])
+    assert r.returncode == 2 and "--full" in r.stderr and "{" not in r.stdout
+
+
+def test_write_outputs_dtypes_and_size_cap(tmp_path):
+    """--dump-outputs: floating outputs as float32, integer outputs as float64 with their values intact; past the size cap an output is
+    written as a fixed sample of its elements -- the same sample for the same shape, and all files together within the cap"""
+    import numpy as np
+
+    import bench
+
+    dets = torch.randn((3, 5, 6)).to(torch.bfloat16)
+    count = torch.tensor([5, 0, 2], dtype=torch.int32)
+    masks = torch.rand((3, 5, 100, 100))
+    bench.write_outputs(str(tmp_path / "a"), (dets, count, masks))
+    d, c, m = (np.load(tmp_path / "a" / f"{n}.npy") for n in ("dets", "count", "masks"))
+    assert d.dtype == np.float32 and np.array_equal(d, dets.float().numpy())
+    assert c.dtype == np.float64 and c.tolist() == [5, 0, 2]
+    assert m.dtype == np.float32 and np.array_equal(m, masks.numpy())
+    limit = 40_000
+    masks2 = masks + 1
+    bench.write_outputs(str(tmp_path / "b"), (dets, count, masks), limit=limit)
+    bench.write_outputs(str(tmp_path / "c"), (dets, count, masks2), limit=limit)
+    files = sorted(os.listdir(tmp_path / "b"))
+    assert files == ["count.npy", "dets.npy", "masks.npy"] and sum(os.path.getsize(tmp_path / "b" / f) for f in files) <= limit
+    mb, mc = np.load(tmp_path / "b" / "masks.npy"), np.load(tmp_path / "c" / "masks.npy")
+    assert mb.ndim == 1 and 1000 < mb.size < masks.numel() and np.array_equal(mc, mb + 1)
+    assert np.isin(mb, masks.numpy().ravel()).all() and np.array_equal(np.load(tmp_path / "b" / "dets.npy"), d)
+
+
 def test_launcher_relays_exactly_one_line(tmp_path, monkeypatch):
     """launch_ranks with a stand-in child: N processes get RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 and rank 0's line is
     relayed once; a rank that fails, or a line with the wrong n_gpus, is an error."""

@@ -8,10 +8,10 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 ROOT=$(pwd)
 run_cfg() {  # name config batch
-  python bench.py --config $2 --batch $3 --steps 10 --warmup 3 --no-cpu-baseline --bracket all --dump-convs $OUT/$1_conv_layers.json > $OUT/$1_bench.json 2> $OUT/$1_bench.err
+  python bench.py --full --config $2 --batch $3 --steps 10 --warmup 3 --no-cpu-baseline --bracket all --dump-convs $OUT/$1_conv_layers.json > $OUT/$1_bench.json 2> $OUT/$1_bench.err
   tail -c 600 $OUT/$1_bench.json; echo
 }
-python bench.py --steps 20 --warmup 5 > $OUT/frcnn_bench.json 2> $OUT/frcnn_bench.err
+python bench.py --full --steps 20 --warmup 5 > $OUT/frcnn_bench.json 2> $OUT/frcnn_bench.err
 tail -c 1500 $OUT/frcnn_bench.json; echo
 run_cfg frcnn_all configs/faster_rcnn/faster_rcnn_r50_fpn.py 120
 run_cfg yolov5s configs/yolov5/yolov5s.py 32

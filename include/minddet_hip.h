@@ -154,17 +154,16 @@ typedef struct md_conv2d_attrs {
     int32_t kh, kw, stride, pad; /* square stride / symmetric zero padding */
     int32_t relu;                /* activation: 0 none; 1 ReLU applied after bias (+ residual);
                                     2 SiLU applied after bias, BEFORE the residual add (x + act(conv(x))) */
-    int32_t variant;             /* 0 = auto (default: cost model in csrc/conv.hip).  Pins a kernel for A/B measurements:
-                                    1 register-staged 128x128, 2 / 20 LDS-DMA 128x128 with two / one staging buffer,
-                                    11 / 27 halo-reuse kernel with 128- / 64-cout tiles,
+    int32_t variant;             /* 0 = auto (default: cost model in csrc/conv.hip).  Pins a kernel for A/B measurements and tests
+                                    (enum ConvVariant in csrc/conv.hip has the full table): 1 register-staged 128x128, 2 / 20 LDS-DMA
+                                    128x128 with two / one staging buffer, 11 / 27 halo-reuse kernel with 128- / 64-cout tiles,
                                     15 / 22 256x256 ping-pong kernel (32x32x16 / 16x16x32 MFMA), 32 its persistent form, 36 / 37 / 38 its
                                     HALO form for 3x3 layers (16x16-pixel tiles, the halo staged once per channel chunk; 38 persistent);
-                                    30 weight-stationary pointwise kernel; 31 / 33 / 35 = auto without the pointwise / persistent /
-                                    HALO kernel, 34 = auto with the HALO form wherever it applies, 39 / 40 = auto with the HALO form also for / instead of
-                                    the persistent form where its tiles fit (A/B records in profiles/r03_pp_halo_step_ab.txt); a variant whose
-                                    preconditions do not hold falls back to the generic kernel.  17-19 and 25 (timing /
-                                    stamp diagnostics that do NOT compute the convolution) exist only in the MD_DIAG build
-                                    used by tools/ (libminddet_hip_diag.so); this library rejects them with MD_ERR_ARG. */
+                                    30 weight-stationary pointwise kernel; 33 / 35 = auto without the persistent / HALO form, 34 = auto
+                                    with the HALO form wherever it applies; a variant whose preconditions do not hold falls back as the
+                                    table says.  17-19, 25 and 26 (timing / stamp diagnostics that do NOT compute the convolution) exist
+                                    only in the MD_DIAG build used by tools/ (libminddet_hip_diag.so).  Every other code, and a
+                                    diagnostic code in this library, is MD_ERR_ARG. */
     /* generalised addressing, used when adv != 0 (all zero = plain conv).  The op then computes, for
      * ho < sub_h, wo < sub_w:  y[n, ho*out_stride + out_off_y, wo*out_stride + out_off_x, c_off + c] =
      * act(bias[c] + sum x[n, ho*stride - pad_top + kh, wo*stride - pad_left + kw, ci] * w[c,kh,kw,ci]), c < cout.
@@ -199,6 +198,37 @@ int md_conv2d(MD_AOT_ARGS);
 /* tile of output channels the dispatcher uses for a given Cout (32, 64 or 128): the packer
  * pads Cout up to a multiple of it.  Pure function, callable without a GPU. */
 int md_conv2d_cout_tile(int cout);
+/* One kernel launch of a conv-family call as the dispatcher plans it (md_conv_plan): the kernel template (family) and its template
+ * arguments, the images it covers, grid, workgroup and dynamic LDS. */
+enum {
+    MD_CONV_FAMILY_IGEMM = 1,     /* conv_igemm_kernel<.., MODE, GEN, DUAL> */
+    MD_CONV_FAMILY_PINGPONG = 2,  /* conv_pingpong_kernel<ABL, MF, GEN, HEAD, PERS, HALO> */
+    MD_CONV_FAMILY_STREAM = 3,    /* conv1x1_stream_kernel<K, CB, SILU, RES, NW> */
+    MD_CONV_FAMILY_HALO = 4       /* conv3x3_halo_kernel<CT, ONE_HALO> */
+};
+typedef struct md_conv_launch {
+    int32_t family;              /* MD_CONV_FAMILY_* */
+    int32_t kernel_id;           /* MD_CONV_KERNEL_* (what md_conv2d_last_kernel reports after the launch) */
+    int32_t ct, pt;              /* cout x pixel tile */
+    int32_t mode;                /* IGEMM: 0 register-staged, 1 LDS-DMA generic K walk, 2 LDS-DMA Cin % 64 == 0 */
+    int32_t gen;                 /* IGEMM / PINGPONG epilogue: 1 general, 0 plain ReLU or none, 2 plain SiLU */
+    int32_t dual;                /* IGEMM: K over two inputs (md_conv1x1_dual) */
+    int32_t mf;                  /* PINGPONG: 0 = 32x32x16 MFMA, 1 = 16x16x32 */
+    int32_t head, pers, halo;    /* PINGPONG: fused 1x1 head, persistent form, HALO form */
+    int32_t abl;                 /* PINGPONG: timing ablation (diagnostic build only; 0) */
+    int32_t k, cb, nw, res, silu;/* STREAM */
+    int32_t one_halo;            /* HALO */
+    int32_t single_buf;          /* IGEMM: one LDS staging buffer */
+    int32_t sub;                 /* md_conv2d_head without the fused kernel: 0 = the conv into a temporary, 1 = the 1x1 head on it */
+    int32_t n0, nn;              /* the images [n0, n0 + nn) of the call */
+    int32_t block, lds;          /* threads per workgroup, dynamic LDS bytes */
+    int64_t grid;                /* workgroups */
+} md_conv_launch;
+/* The launches op ("md_conv2d", "md_conv2d_head" or "md_conv1x1_dual") makes for these arguments (stream omitted): the op's own
+ * argument checks and dispatcher, without a device call and without dereferencing a tensor pointer (callable without a GPU).  Returns
+ * the op's rc; writes the first min(cap, *n) records to out and sets *n to the number of launches. */
+int md_conv_plan(const char *op, int nparam, void **params, int *ndims, int64_t **shapes, const char **dtypes, void *extra,
+                 md_conv_launch *out, int cap, int *n);
 
 /* ONE 1x1 GEMM over the K-concatenation of two inputs: y = act(W . [x_a ; x_b sampled with stride_b] + bias [+ residual]).
  * Replaces, in the first block of a ResNet stage (centernet/src/resnet.py:139-178 with `downsample`; _make_layer :214-224),

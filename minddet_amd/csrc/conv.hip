@@ -529,62 +529,6 @@ __global__ __launch_bounds__(NT, NT == 256 ? 3 : 2) void conv_igemm_kernel(ConvA
     }
 }
 
-template <int NT, int WC, int WP, int FC, int FP, int MODE>
-static int launch_conv(ConvArgs &a, hipStream_t s) {
-    const bool cat_only = a.adv && a.os == 1 && !a.oy && !a.ox && a.Ho == a.Hf && a.Wo == a.Wf;
-    const bool plain = MODE == 2 && (!a.adv || cat_only) && !a.res_up;
-    constexpr int CT = WC * FC * 32, PT = WP * FP * 32;
-    ++g_launch_count;
-    g_last_kernel = MODE == 1 ? MD_CONV_KERNEL_IGEMM_GENERIC_K : (CT == 128 && PT == 128 ? MD_CONV_KERNEL_IGEMM_128 :
-                    (CT < 128 ? MD_CONV_KERNEL_IGEMM_SMALL_COUT : MD_CONV_KERNEL_OTHER));
-    a.n_ctiles = (a.Cout + CT - 1) / CT;
-    a.n_ptiles = (a.M + PT - 1) / PT;
-    // one staging buffer is enough when the whole K fits one tile (1x1 convs on 64 channels): more
-    // workgroups per CU for the HBM-bound layers
-    if (MODE == 0) a.single_buf = 0;
-    const int nbuf = a.Kpad / BK > 1 && !a.single_buf ? 2 : 1;
-    const int tile_bytes = (CT + PT) * ROWB * nbuf;
-    constexpr int ep_bytes = PT * (CT * 2 + 16);
-    a.bias_lds_off = tile_bytes > ep_bytes ? tile_bytes : ep_bytes;
-    const int lds = a.bias_lds_off + CT * 4;
-    a.pt_per_xcd = (a.n_ptiles + 7) / 8;
-    const long long blocks = (long long)a.n_ctiles * a.pt_per_xcd * 8;
-    if (blocks > 0x7fffffffLL) return MD_ERR_SIZE;
-    constexpr bool HAS_PLAIN = MODE == 2;
-    auto k = conv_igemm_kernel<NT, WC, WP, FC, FP, MODE, 1>;
-    if (plain) k = a.relu == 2 ? conv_igemm_kernel<NT, WC, WP, FC, FP, MODE, HAS_PLAIN ? 2 : 1> : conv_igemm_kernel<NT, WC, WP, FC, FP, MODE, HAS_PLAIN ? 0 : 1>;
-    if (lds > 64 * 1024 && ensure_dyn_lds((const void *)k, lds) != MD_OK) return MD_ERR_HIP;
-    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(NT), lds, s, a);
-    return hipGetLastError() == hipSuccess ? MD_OK : MD_ERR_HIP;
-}
-
-
-static int launch_conv_dual_pingpong(ConvArgs &a, hipStream_t s);   // defined behind the ping-pong kernel
-
-// 128 x 128 single-buffer kernel on the K-concatenation of two inputs (md_conv1x1_dual)
-static int launch_conv_dual(ConvArgs &a, hipStream_t s, const Tune &tn) {
-    // long-K, MFMA-bound forms (768 -> 1024, 1536 -> 2048 of the ResNet-50 stages 3 / 4): the 256x256 ping-pong kernel reading its K tiles
-    // past nk_a from the second tensor
-    if (a.Cout % 256 == 0 && a.Kpad >= tn.dual_pp_min_k && !a.res && (long long)(a.M + 255) / 256 * (a.Cout / 256) >= 256)
-        return launch_conv_dual_pingpong(a, s);
-    constexpr int CT = 128, PT = 128;
-    ++g_launch_count;
-    g_last_kernel = MD_CONV_KERNEL_IGEMM_128;
-    a.n_ctiles = (a.Cout + CT - 1) / CT;
-    a.n_ptiles = (a.M + PT - 1) / PT;
-    a.single_buf = 1;
-    const int tile_bytes = (CT + PT) * ROWB;
-    constexpr int ep_bytes = PT * (CT * 2 + 16);
-    a.bias_lds_off = tile_bytes > ep_bytes ? tile_bytes : ep_bytes;
-    const int lds = a.bias_lds_off + CT * 4;
-    a.pt_per_xcd = (a.n_ptiles + 7) / 8;
-    const long long blocks = (long long)a.n_ctiles * a.pt_per_xcd * 8;
-    if (blocks > 0x7fffffffLL) return MD_ERR_SIZE;
-    auto k = conv_igemm_kernel<256, 2, 2, 2, 2, 2, 0, 1>;
-    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(256), lds, s, a);
-    return hipGetLastError() == hipSuccess ? MD_OK : MD_ERR_HIP;
-}
-
 // ------------------------------------------------------------------------------------------------------------
 // conv1x1_stream_kernel -- pointwise conv (1x1 / stride 1 / pad 0) with K = Cin <= 512, WEIGHT-STATIONARY.
 //
@@ -829,51 +773,6 @@ __global__ __launch_bounds__(NW * 64, 2) void conv1x1_stream_kernel(ConvArgs a, 
     }
 }
 
-// dispatch + launch of conv1x1_stream_kernel; MD_ERR_UNSUPPORTED_STREAM when the layer is not one it takes
-#define MD_ERR_UNSUPPORTED_STREAM 101
-template <int K, int CB, int NW = 4>
-static int launch_conv1x1_stream_t(ConvArgs &a, hipStream_t s, const Tune &tn) {
-    constexpr int NR = K == 512 ? (NW == 8 ? 3 : 2) : (K == 128 ? 4 : 3);
-    constexpr int CT = NW * CB * 32;
-    const int lds = NR * 32 * K * 2 + NW * (32 * CB * 64) + CT * 4;
-    a.n_ctiles = a.Cout / CT;
-    a.n_ptiles = (a.M + 31) / 32;
-    const long long slots = 256LL * tn.stream_wgs_per_cu * 4 / NW * tn.stream_rounds;   // resident workgroups (two 4-wave ones per CU) x rounds
-    a.tune = tn.stream_cache_bits;
-    long long tpw = ((long long)a.n_ptiles * a.n_ctiles + slots - 1) / slots;
-    if (tpw < 4) tpw = 4;
-    const long long n_chunks = (a.n_ptiles + tpw - 1) / tpw;
-    const long long chunks_per_xcd = (n_chunks + 7) / 8;
-    const long long blocks = chunks_per_xcd * 8 * a.n_ctiles;
-    if (blocks > 0x7fffffffLL) return MD_ERR_SIZE;
-    auto k = a.res ? (a.relu == 2 ? conv1x1_stream_kernel<K, CB, true, 1, NW> : conv1x1_stream_kernel<K, CB, false, 1, NW>)
-                   : (a.relu == 2 ? conv1x1_stream_kernel<K, CB, true, 0, NW> : conv1x1_stream_kernel<K, CB, false, 0, NW>);
-    if (a.res_up) k = conv1x1_stream_kernel<K, CB, false, 2, NW>;
-    if (ensure_dyn_lds((const void *)k, lds) != MD_OK) return MD_ERR_HIP;
-    ++g_launch_count;
-    g_last_kernel = MD_CONV_KERNEL_STREAM_1X1;
-    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(NW * 64), lds, s, a, (int)tpw, (int)n_chunks, (int)chunks_per_xcd);
-    return hipGetLastError() == hipSuccess ? MD_OK : MD_ERR_HIP;
-}
-
-static bool stream1x1_takes(const ConvArgs &a) {
-    const bool cat_only = !a.adv || (a.os == 1 && a.oy == 0 && a.ox == 0 && a.Ho == a.Hf && a.Wo == a.Wf);
-    if (!a.pointwise || !cat_only || a.Kpad != a.Cin || a.x_bytes == 0) return false;
-    // upsampled residual (the FPN lateral convs): plain output, no SiLU, residual tensor inside the 32-bit offset reach
-    if (a.res_up && (a.adv || a.relu == 2 || (long long)a.N * ((a.Ho + 1) / 2) * ((a.Wo + 1) / 2) * a.Cout * 2 >= 0x7fff0000LL)) return false;
-    if (a.Cin != 128 && a.Cin != 256 && a.Cin != 512) return false;
-    return a.Cout % 128 == 0;
-}
-
-static int launch_conv1x1_stream(ConvArgs &a, hipStream_t s, const Tune &tn) {
-    if (!stream1x1_takes(a)) return MD_ERR_UNSUPPORTED_STREAM;
-    const bool wide = a.Cout % 256 == 0;
-    if (a.Cin == 128) return wide ? launch_conv1x1_stream_t<128, 2>(a, s, tn) : launch_conv1x1_stream_t<128, 1>(a, s, tn);
-    if (a.Cin == 256) return wide ? launch_conv1x1_stream_t<256, 2>(a, s, tn) : launch_conv1x1_stream_t<256, 1>(a, s, tn);
-    // K = 512: 256 couts per (8-wave) workgroup where Cout allows, so that an activation tile is staged once per 256 couts
-    if (wide && !tn.stream_narrow) return launch_conv1x1_stream_t<512, 1, 8>(a, s, tn);
-    return launch_conv1x1_stream_t<512, 1>(a, s, tn);
-}
 
 // ------------------------------------------------------------------------------------------------------------
 // 3x3 / stride 1 / pad 1 convolution with HALO REUSE.
@@ -1080,24 +979,6 @@ __global__ __launch_bounds__(256, CT == 64 ? 4 : 2) void conv3x3_halo_kernel(Con
     }
 }
 
-template <int CT, bool ONE_HALO>
-static int launch_conv3x3_halo(ConvArgs &a, hipStream_t s) {
-    ++g_launch_count;
-    g_last_kernel = MD_CONV_KERNEL_HALO;
-    const int tiles_x = (a.W + HT_W - 1) / HT_W, tiles_y = (a.H + HT_H - 1) / HT_H;
-    a.n_ctiles = (a.Cout + CT - 1) / CT;
-    a.n_ptiles = a.N * tiles_x * tiles_y;
-    a.pt_per_xcd = (a.n_ptiles + 7) / 8;
-    const long long blocks = (long long)a.n_ctiles * a.pt_per_xcd * 8;
-    if (blocks > 0x7fffffffLL) return MD_ERR_SIZE;
-    const int stage = 2 * CT * ROWB + (ONE_HALO ? 1 : 2) * HALO_BYTES;
-    const int ep = HT_H * HT_W * (CT * 2 + 16) + CT * 4;  // epilogue image + bias copy
-    const int lds = stage > ep ? stage : ep;
-    auto k = conv3x3_halo_kernel<CT, ONE_HALO>;
-    if (ensure_dyn_lds((const void *)k, lds) != MD_OK) return MD_ERR_HIP;
-    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(256), lds, s, a, tiles_x, tiles_y);
-    return hipGetLastError() == hipSuccess ? MD_OK : MD_ERR_HIP;
-}
 
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1780,11 +1661,6 @@ static long long pingpong_halo_tiles_per_image(int H, int W, int *tiles_y, int *
     if (tiles_strip) *tiles_strip = ts;
     return (long long)ty * ((W + 15) / 16) + ts;
 }
-static void pingpong_halo_tiles(ConvArgs &a) {
-    a.tiles_x = (a.W + 15) / 16;
-    a.n_ptiles = (int)(a.N * pingpong_halo_tiles_per_image(a.H, a.W, &a.tiles_y, &a.tiles_strip));
-    a.pt_per_xcd = (a.n_ptiles + 7) / 8;
-}
 // Preconditions of the HALO form (checked by the dispatcher besides the ping-pong kernel's own): 3x3 / stride 1 / pad 1 with korder-1 weights.
 static bool pingpong_halo_takes(const ConvArgs &a) {
     return a.kh == 3 && a.kw == 3 && a.stride == 1 && a.pad_top == 1 && a.pad_left == 1 && a.korder == 1 && a.Cin % 64 == 0 && a.Ho == a.H &&
@@ -1792,123 +1668,315 @@ static bool pingpong_halo_takes(const ConvArgs &a) {
            (long long)(15 * a.W + 32) * a.Ctot * 2 < 0x7fffffffLL;   // the persistent form's 32-bit store offsets inside a tile
 }
 
-template <int MF, bool HALO>
-static int launch_conv_pingpong_head_mf(ConvArgs &a, hipStream_t s, long long blocks, int lds) {
-    auto k = conv_pingpong_kernel<0, MF, 0, true, false, HALO>;
-    if (ensure_dyn_lds((const void *)k, lds) != MD_OK) return MD_ERR_HIP;
-    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(512), lds, s, a);
-    return hipGetLastError() == hipSuccess ? MD_OK : MD_ERR_HIP;
-}
-
-static int launch_conv_pingpong_head(ConvArgs &a, hipStream_t s, bool halo) {
-    ++g_launch_count;
-    g_last_kernel = MD_CONV_KERNEL_PINGPONG;
-    a.n_ctiles = 1;
-    a.n_ptiles = (a.M + 255) / 256;
-    a.pt_per_xcd = (a.n_ptiles + 7) / 8;
-    if (halo) pingpong_halo_tiles(a);
-    const long long blocks = (long long)a.pt_per_xcd * 8;
-    if (blocks > 0x7fffffffLL) return MD_ERR_SIZE;
-    if (halo) return pingpong_wants_16x16(a) ? launch_conv_pingpong_head_mf<1, true>(a, s, blocks, HB_LDS_HEAD) : launch_conv_pingpong_head_mf<0, true>(a, s, blocks, HB_LDS_HEAD);
-    const int lds = 256 * (256 * 2 + 16) + 256 * 4 + 16 * 256 * 2;  // epilogue image + bias + head weights
-    return pingpong_wants_16x16(a) ? launch_conv_pingpong_head_mf<1, false>(a, s, blocks, lds) : launch_conv_pingpong_head_mf<0, false>(a, s, blocks, lds);
-}
-
-// the persistent form: one workgroup per CU, S = 32 / n_ctiles workgroups per (XCD, cout tile) stride through the XCD's pixel range
-template <int MF, bool HALO = false>
-static int launch_conv_pingpong_pers(ConvArgs &a, hipStream_t s) {
-    ++g_launch_count;
-    g_last_kernel = MD_CONV_KERNEL_PINGPONG;
-    a.n_ctiles = a.Cout / 256;
-    a.n_ptiles = (a.M + 255) / 256;
-    a.pt_per_xcd = (a.n_ptiles + 7) / 8;
-    if (HALO) pingpong_halo_tiles(a);
-    const int lds = HALO ? HB_LDS : 8 * 128 * ROWB + 256 * 4 + 8 * 2560;   // staging buffers + bias + eight wave-private slabs (HALO: in halo buffer 1)
-    auto k = a.relu == 2 ? conv_pingpong_kernel<0, MF, 2, false, true, HALO> : conv_pingpong_kernel<0, MF, 0, false, true, HALO>;
-    if (ensure_dyn_lds((const void *)k, lds) != MD_OK) return MD_ERR_HIP;
-    hipLaunchKernelGGL(k, dim3(256), dim3(512), lds, s, a);
-    return hipGetLastError() == hipSuccess ? MD_OK : MD_ERR_HIP;
-}
-
-static int launch_conv_dual_pingpong(ConvArgs &a, hipStream_t s) {
-    ++g_launch_count;
-    g_last_kernel = MD_CONV_KERNEL_PINGPONG;
-    a.n_ctiles = a.Cout / 256;
-    a.n_ptiles = (a.M + 255) / 256;
-    a.pt_per_xcd = (a.n_ptiles + 7) / 8;
-    const long long blocks = (long long)a.n_ctiles * a.pt_per_xcd * 8;
-    if (blocks > 0x7fffffffLL) return MD_ERR_SIZE;
-    const int lds = 256 * (256 * 2 + 16) + 256 * 4;
-    auto k = conv_pingpong_kernel<0, 0, 0>;
-    if (ensure_dyn_lds((const void *)k, lds) != MD_OK) return MD_ERR_HIP;
-    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(512), lds, s, a);
-    return hipGetLastError() == hipSuccess ? MD_OK : MD_ERR_HIP;
-}
-
-// plain (one tile per workgroup) HALO form: GEN 0 / 2 epilogues, optional residual with the output's layout or a channel slice
-template <int MF>
-static int launch_conv_pingpong_halo(ConvArgs &a, hipStream_t s) {
-    ++g_launch_count;
-    g_last_kernel = MD_CONV_KERNEL_PINGPONG;
-    a.n_ctiles = a.Cout / 256;
-    pingpong_halo_tiles(a);
-    const long long blocks = (long long)a.n_ctiles * a.pt_per_xcd * 8;
-    if (blocks > 0x7fffffffLL) return MD_ERR_SIZE;
-    auto k = a.relu == 2 ? conv_pingpong_kernel<0, MF, 2, false, false, true> : conv_pingpong_kernel<0, MF, 0, false, false, true>;
-    if (ensure_dyn_lds((const void *)k, HB_LDS) != MD_OK) return MD_ERR_HIP;
-    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(512), HB_LDS, s, a);
-    return hipGetLastError() == hipSuccess ? MD_OK : MD_ERR_HIP;
-}
-
 // (r04: conv_w128_kernel -- this tile on four waves with a 128 x 128 register tile each -- was built, bit-identical, and measured: it ties
 // this kernel on dense data and loses 4-35 % on zero operands; profiles/r04_w128_experiment.txt, git history has the source.)
-template <int ABL = 0, int MF = 0>
-static int launch_conv_pingpong(ConvArgs &a, hipStream_t s) {
-    ++g_launch_count;
-    g_last_kernel = MD_CONV_KERNEL_PINGPONG;
-    a.n_ctiles = a.Cout / 256;
-    a.n_ptiles = (a.M + 255) / 256;
-    a.pt_per_xcd = (a.n_ptiles + 7) / 8;
-    const long long blocks = (long long)a.n_ctiles * a.pt_per_xcd * 8;
-    if (blocks > 0x7fffffffLL) return MD_ERR_SIZE;
-    const int lds = 256 * (256 * 2 + 16) + 256 * 4;  // 136,192 B: the epilogue image (>= the 128 KiB of staging buffers) + bias
-    constexpr bool HAS_PLAIN = ABL == 0 || (ABL == 4 && MF == 0);
-    const bool cat_only = a.adv && a.os == 1 && !a.oy && !a.ox && a.Ho == a.Hf && a.Wo == a.Wf;
-    const bool plain = HAS_PLAIN && (!a.adv || cat_only) && !a.res_up;
-    auto k = conv_pingpong_kernel<ABL, MF, 1>;
-    if (plain) k = a.relu == 2 ? conv_pingpong_kernel<ABL, MF, HAS_PLAIN ? 2 : 1> : conv_pingpong_kernel<ABL, MF, HAS_PLAIN ? 0 : 1>;
-    if (ensure_dyn_lds((const void *)k, lds) != MD_OK) return MD_ERR_HIP;
-    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(512), lds, s, a);
-    return hipGetLastError() == hipSuccess ? MD_OK : MD_ERR_HIP;
-}
 
-}  // namespace md
+// Dispatcher: validate -> plan -> launch.  The plan (conv_plan_*) is a pure host function of the validated call: no HIP call, no heap, no
+// global; it maps (ConvArgs, variant, head?, Tune) to md_conv_launch records (kernel instantiation, images, grid, block, LDS).  The launch
+// derives the kernel arguments with the same conv_geometry.  md_conv_plan exports the plan, so that a CPU test reads which kernel each layer gets.
+// ------------------------------------------------------------------------------------------------------------
 
-using namespace md;
-
-// Required weight padding for a given Cout (the tile the dispatcher will pick): exported so the
-// host packer pads consistently.
-extern "C" int md_conv2d_last_kernel(void) { return g_last_kernel; }
-extern "C" long long md_conv2d_launch_count(void) { return g_launch_count; }
-namespace md {
-void md_note_conv_kernel(int id) { g_last_kernel = id; ++g_launch_count; }
-}
-
-extern "C" int md_conv2d_cout_tile(int cout) { return cout > 64 ? 128 : (cout > 32 ? 64 : 32); }
-
-struct HeadArgs {   // the fused RPN head: y2 has 16 channels, y is not written
-    const uint16_t *w2;
-    const float *b2;
-    uint16_t *y2;
+// md_conv2d_attrs.variant.  0 picks by the cost model; the others pin a kernel for A/B measurements and tests and fall back as noted where
+// their kernel does not apply ("generic" = the 128x128 / small-cout conv_igemm_kernel).  Any other code is MD_ERR_ARG; so are the MD_DIAG
+// codes (timing ablations and stamps that do not compute the convolution) in the product library.
+enum ConvVariant {
+    V_AUTO = 0,
+    V_IGEMM_REG = 1,        // generic kernel, register-staged (MODE 0, 64-bit addressing)
+    V_IGEMM_DBUF = 2,       // generic kernel, LDS-DMA, two staging buffers
+    V_HALO128 = 11,         // conv3x3_halo_kernel with 128-cout tiles; else as 2
+    V_PP = 15,              // ping-pong kernel, 32x32x16 MFMA; else as 2
+    V_DIAG_NOSTAGE = 17,    // MD_DIAG: ping-pong without in-loop staging; else as 2
+    V_DIAG_NOSTORE = 18,    // MD_DIAG: ping-pong without output stores; else as 2
+    V_DIAG_PP_STAMPS = 19,  // MD_DIAG: ping-pong with cycle stamps; else as 2
+    V_IGEMM_SBUF = 20,      // generic kernel, LDS-DMA, one staging buffer
+    V_PP16 = 22,            // ping-pong kernel, 16x16x32 MFMA; else as 2
+    V_DIAG_IGEMM_STAMPS = 25,  // MD_DIAG: 20 with cycle stamps
+    V_DIAG_PP16_STAMPS = 26,   // MD_DIAG: 22 with cycle stamps; else as 2
+    V_HALO64 = 27,          // conv3x3_halo_kernel with 64-cout tiles; else as 2
+    V_STREAM = 30,          // conv1x1_stream_kernel; else auto
+    V_PERS = 32,            // the persistent ping-pong form; else auto without the first 64-cout halo rule
+    V_NO_PERS = 33,         // auto without the persistent form
+    V_HALO_ALL = 34,        // auto with the HALO ping-pong form wherever it applies
+    V_NO_HALO = 35,         // auto without the HALO ping-pong form
+    V_PP_HALO = 36,         // HALO ping-pong form, 32x32x16 MFMA; else the ping-pong kernel; else the generic kernel, one staging buffer
+    V_PP16_HALO = 37,       // the same on 16x16x32 MFMA
+    V_PP_PERS_HALO = 38,    // the persistent HALO form; else as 37
 };
+static bool variant_diag(int v) { return (v >= V_DIAG_NOSTAGE && v <= V_DIAG_PP_STAMPS) || v == V_DIAG_IGEMM_STAMPS || v == V_DIAG_PP16_STAMPS; }
+static bool variant_known(int v) {
+    return variant_diag(v) ? kDiag : (v >= V_AUTO && v <= V_IGEMM_DBUF) || v == V_HALO128 || v == V_PP || v == V_IGEMM_SBUF || v == V_PP16 ||
+                                     v == V_HALO64 || v == V_STREAM || (v >= V_PERS && v <= V_PP_PERS_HALO);
+}
+
 #ifdef MD_DIAG
 static unsigned long long *g_stamp_buf = nullptr;
-// device buffer (>= 8 * 16 * 8 bytes) that receives the cycle stamps of the variant 19 / 25 launches
-extern "C" int md_diag_set_stamp_buffer(void *p) { g_stamp_buf = (unsigned long long *)p; return MD_OK; }
 #endif
-#define MD_ERR_UNSUPPORTED_INTERNAL 100  // conv2d_entry with a head on a layer the fused kernel does not take
 
-static int conv2d_entry(MD_AOT_ARGS, const HeadArgs *head) {
+// A validated call, before its batch is sliced: ConvArgs with N = the whole batch (M and the DMA byte counts are per slice).
+struct ConvCall {
+    ConvArgs a;                      // a.x2 != null: md_conv1x1_dual
+    int variant;
+    Tune tn;
+    bool empty;                      // no output pixels: nothing to launch
+    long long per;                   // images per launch: the batch, or the image chunks of a batch past the chunk limit
+    long long x_img, x2_img, r_img, y_img;   // elements per image of x, x2, the residual and y
+    long long x_off, w_bytes;        // x_c_off (x_bytes counts from the slice's first channel); the weights' bytes
+};
+
+// The images [n0, n0 + nn) of a call.  DMA byte counts of 0 = not inside the 32-bit LDS-DMA offsets (out-of-range marker 2^31).
+static ConvArgs conv_slice(const ConvCall &c, long long n0, long long nn) {
+    ConvArgs a = c.a;
+    a.N = (int)nn; a.M = (int)(nn * a.Ho * a.Wo);
+    a.x += n0 * c.x_img;
+    if (a.x2) a.x2 += n0 * c.x2_img;
+    if (a.res) a.res += n0 * c.r_img;
+    a.y += n0 * c.y_img;
+    if (a.y2) a.y2 += n0 * a.Ho * a.Wo * 16;
+    const long long x_bytes = nn * c.x_img * 2 - c.x_off * 2;
+    const bool dma_ok = x_bytes < 0x7fff0000LL && c.w_bytes < 0x7fff0000LL;
+    a.x_bytes = (unsigned)(dma_ok ? x_bytes : 0);
+    a.w_bytes = (unsigned)(dma_ok ? c.w_bytes : 0);
+    a.x2_bytes = (unsigned)(nn * c.x2_img * 2);
+    return a;
+}
+
+// Grid, block, LDS and kernel id of the kernel chosen in r, and the kernel arguments that go with them: a's tile counts (ConvArgs) and the
+// arguments behind it (xarg: conv1x1_stream_kernel's tpw, n_chunks, chunks_per_xcd; conv3x3_halo_kernel's tiles_x, tiles_y).
+static int conv_geometry(ConvArgs &a, const Tune &tn, md_conv_launch &r, int xarg[3]) {
+    long long blocks = 0;   // (0: one workgroup per cout tile x pixel tile, below)
+    r.block = 256;
+    switch (r.family) {
+    case MD_CONV_FAMILY_IGEMM: {
+        r.kernel_id = r.mode == 1 ? MD_CONV_KERNEL_IGEMM_GENERIC_K : (r.ct == 128 ? MD_CONV_KERNEL_IGEMM_128 : MD_CONV_KERNEL_IGEMM_SMALL_COUT);
+        const int CT = r.ct, PT = r.pt = CT == 128 ? 128 : 256;   // 4 waves: 2 x 2 of 64 x 64, or 1 x 4 of CT x 64
+        a.single_buf = r.single_buf;
+        a.n_ctiles = (a.Cout + CT - 1) / CT; a.n_ptiles = (a.M + PT - 1) / PT;
+        const int tile_bytes = (CT + PT) * ROWB * (a.Kpad / BK > 1 && !r.single_buf ? 2 : 1), ep_bytes = PT * (CT * 2 + 16);
+        a.bias_lds_off = tile_bytes > ep_bytes ? tile_bytes : ep_bytes;
+        r.lds = a.bias_lds_off + CT * 4;
+        break;
+    }
+    case MD_CONV_FAMILY_PINGPONG:
+        r.kernel_id = MD_CONV_KERNEL_PINGPONG; r.ct = r.pt = 256; r.block = 512;
+        a.n_ctiles = r.head ? 1 : a.Cout / 256; a.n_ptiles = (a.M + 255) / 256;
+        if (r.halo) {   // the HALO form's tile map
+            a.tiles_x = (a.W + 15) / 16;
+            a.n_ptiles = (int)(a.N * pingpong_halo_tiles_per_image(a.H, a.W, &a.tiles_y, &a.tiles_strip));
+        }
+        // persistent form: one workgroup per CU, S = 32 / n_ctiles workgroups per (XCD, cout tile) stride through the XCD's pixel range
+        if (r.pers) blocks = 256;
+        // one tile per workgroup: 136,192 B = the epilogue image (>= the 128 KiB of staging buffers) + bias (+ the head's weights); persistent:
+        // staging buffers + bias + eight wave-private slabs (HALO: in halo buffer 1)
+        r.lds = r.halo ? (r.head ? HB_LDS_HEAD : HB_LDS) : r.pers ? 8 * 128 * ROWB + 256 * 4 + 8 * 2560 : 256 * (256 * 2 + 16) + 256 * 4 + r.head * 16 * 256 * 2;
+        break;
+    case MD_CONV_FAMILY_STREAM: {
+        r.kernel_id = MD_CONV_KERNEL_STREAM_1X1; r.ct = r.nw * r.cb * 32; r.pt = 32; r.block = r.nw * 64;
+        const int NR = r.k == 512 ? (r.nw == 8 ? 3 : 2) : (r.k == 128 ? 4 : 3);
+        r.lds = NR * 32 * r.k * 2 + r.nw * (32 * r.cb * 64) + r.ct * 4;
+        a.n_ctiles = a.Cout / r.ct; a.n_ptiles = (a.M + 31) / 32;
+        a.tune = tn.stream_cache_bits;
+        const long long slots = 256LL * tn.stream_wgs_per_cu * 4 / r.nw * tn.stream_rounds;   // resident workgroups (two 4-wave ones per CU) x rounds
+        long long tpw = ((long long)a.n_ptiles * a.n_ctiles + slots - 1) / slots;
+        if (tpw < 4) tpw = 4;
+        const long long n_chunks = (a.n_ptiles + tpw - 1) / tpw, chunks_per_xcd = (n_chunks + 7) / 8;
+        xarg[0] = (int)tpw; xarg[1] = (int)n_chunks; xarg[2] = (int)chunks_per_xcd;
+        blocks = chunks_per_xcd * 8 * a.n_ctiles;
+        break;
+    }
+    case MD_CONV_FAMILY_HALO: {
+        r.kernel_id = MD_CONV_KERNEL_HALO; r.pt = HT_H * HT_W; r.one_halo = r.ct == 64;
+        xarg[0] = (a.W + HT_W - 1) / HT_W; xarg[1] = (a.H + HT_H - 1) / HT_H;
+        a.n_ctiles = (a.Cout + r.ct - 1) / r.ct; a.n_ptiles = a.N * xarg[0] * xarg[1];
+        const int stage = 2 * r.ct * ROWB + (r.one_halo ? 1 : 2) * HALO_BYTES, ep = HT_H * HT_W * (r.ct * 2 + 16) + r.ct * 4;  // ep: image + bias
+        r.lds = stage > ep ? stage : ep;
+        break;
+    }
+    }
+    if (r.family != MD_CONV_FAMILY_STREAM) {   // pixel tiles dealt out per XCD (8), every cout tile of a pixel tile on one XCD
+        a.pt_per_xcd = (a.n_ptiles + 7) / 8;
+        if (!blocks) blocks = (long long)a.n_ctiles * a.pt_per_xcd * 8;
+    }
+    if (blocks > 0x7fffffffLL) return MD_ERR_SIZE;
+    r.grid = blocks;
+    return MD_OK;
+}
+
+static md_conv_launch igemm_launch(const ConvArgs &a, int mode, int ct, bool plain_out, bool dual = false) {
+    md_conv_launch r = {};
+    r.family = MD_CONV_FAMILY_IGEMM; r.mode = mode; r.ct = ct; r.dual = r.single_buf = dual;
+    r.gen = mode == 2 && plain_out && !a.res_up ? (a.relu == 2 ? 2 : 0) : 1;   // GEN 0 / 2 exist for MODE 2 only
+    return r;
+}
+static md_conv_launch pingpong_launch(const ConvArgs &a, int mf, bool pers, bool halo, bool plain_out, bool head = false, int abl = 0) {
+    md_conv_launch r = {};
+    r.family = MD_CONV_FAMILY_PINGPONG; r.mf = mf; r.pers = pers; r.halo = halo; r.head = head; r.abl = abl;
+    // the persistent, HALO and head forms are GEN 0 / 2 only (the head: ReLU, GEN 0); the timing ablations have the plain epilogues on
+    // ABL 4 / 32x32x16 only
+    const bool has_plain = abl == 0 || (abl == 4 && mf == 0);
+    r.gen = pers || halo || (has_plain && plain_out && !a.res_up) ? (a.relu == 2 ? 2 : 0) : 1;
+    return r;
+}
+static md_conv_launch halo3x3_launch(int ct) { md_conv_launch r = {}; r.family = MD_CONV_FAMILY_HALO; r.ct = ct; return r; }
+
+static bool stream1x1_takes(const ConvArgs &a, bool plain_out) {
+    if (!a.pointwise || !plain_out || a.Kpad != a.Cin || a.x_bytes == 0) return false;
+    // upsampled residual (the FPN lateral convs): plain output, no SiLU, residual tensor inside the 32-bit offset reach
+    if (a.res_up && (a.adv || a.relu == 2 || (long long)a.N * ((a.Ho + 1) / 2) * ((a.Wo + 1) / 2) * a.Cout * 2 >= 0x7fff0000LL)) return false;
+    return (a.Cin == 128 || a.Cin == 256 || a.Cin == 512) && a.Cout % 128 == 0;
+}
+static md_conv_launch stream_launch(const ConvArgs &a, const Tune &tn) {
+    md_conv_launch r = {};
+    const bool wide = a.Cout % 256 == 0;
+    r.family = MD_CONV_FAMILY_STREAM; r.k = a.Cin; r.cb = wide && a.Cin != 512 ? 2 : 1;
+    // K = 512: 256 couts per (8-wave) workgroup where Cout allows, so that an activation tile is staged once per 256 couts
+    r.nw = a.Cin == 512 && wide && !tn.stream_narrow ? 8 : 4;
+    r.res = a.res_up ? 2 : (a.res ? 1 : 0); r.silu = a.relu == 2 && !a.res_up;
+    return r;
+}
+
+// The kernel choice of one md_conv2d launch (a: one slice of the validated call).  head: the fused RPN head form (the caller has checked
+// conv_head_fuses).
+static md_conv_launch conv_choose(const ConvArgs &a, int variant, const Tune &tn, bool head) {
+    // md_conv1x1_dual: the 128 x 128 single-buffer kernel on the K-concatenation of two inputs, or for the long-K, MFMA-bound forms
+    // (768 -> 1024, 1536 -> 2048 of the ResNet-50 stages 3 / 4) the 256x256 ping-pong kernel reading its K tiles past nk_a from the second tensor
+    if (a.x2 && a.Cout % 256 == 0 && a.Kpad >= tn.dual_pp_min_k && !a.res && (long long)(a.M + 255) / 256 * (a.Cout / 256) >= 256)
+        return pingpong_launch(a, 0, false, false, true);
+    if (a.x2) return igemm_launch(a, 2, 128, true, true);
+    const bool dma_ok = a.w_bytes != 0;
+    const long long M = a.M;
+    const int ctile = md_conv2d_cout_tile(a.Cout);
+    const bool fast = a.Cin % 64 == 0 && a.kh * a.kw <= 32;  // MODE 2 preconditions (then Kpad == Kreal)
+    // Output addressing.  plain_out: the output is the whole tensor or a channel range of it (offset = m * Ctot + c_off + c) -- what the
+    // GEN 0 / 2 epilogues, conv1x1_stream_kernel and the persistent / HALO ping-pong forms address.
+    const bool plain_out = !a.adv || (a.os == 1 && a.oy == 0 && a.ox == 0 && a.Ho == a.Hf && a.Wo == a.Wf);
+    // conv3x3_halo_kernel in addition takes its input window at a.pad on both axes (not pad_top / pad_left) and reads a residual at stride
+    // Rs or Cout, not at the output's offsets: an adv call qualifies with symmetric pads and no residual or a channel-slice one
+    const bool plain_out_halo = plain_out && (!a.adv || (a.pad_top == a.pad && a.pad_left == a.pad && (!a.res || a.Rs)));
+    const bool no_pers = variant == V_NO_PERS, force_halo = variant == V_HALO_ALL, no_halo = variant == V_NO_HALO;
+    if (no_pers || force_halo || no_halo) variant = V_AUTO;
+    // weight-stationary streaming kernel for pointwise layers with K <= 512 (variant 30 forces it where it applies)
+    // auto: where it measured faster than the 128x128 kernel INSIDE the Faster R-CNN step (r02 tools/stream_insitu_tune.py, batch 60;
+    // a replay loop on one layer flatters it: the activation tensor then survives in the Infinity Cache between launches):
+    // 256->1024 + residual -0.40 ms/step (5 launches), 512->256 -0.12, 512->2048 + residual -0.09; 128->512 + residual +0.15 (stays on
+    // the 128x128 kernel); the 128-cout forms lose 2-15 % -- and every workgroup gets at least 8 tiles to stream past its weights
+    if (!head && dma_ok && stream1x1_takes(a, plain_out) &&
+        (variant == V_STREAM || (variant == V_AUTO && a.Cout % 256 == 0 && a.Cin != 128 && (M + 31) / 32 * (a.Cout / (a.Cin == 512 ? 128 : 256)) >= 4096)))
+        return stream_launch(a, tn);
+    if (variant == V_STREAM) variant = V_AUTO;
+    // 3x3 / stride 1 / pad 1 with korder-1 weights: halo-reuse kernel (variant 11)
+    const bool halo_ok = dma_ok && !a.adv && a.korder == 1 && a.kh == 3 && a.kw == 3 && a.stride == 1 && a.pad == 1 &&
+                         a.Cin % 64 == 0 && ctile == 128;
+    // MFMA-bound layers (K >= 1024, Cout a multiple of 256): the 256x256 ping-pong kernel (measured r01, tools/conv_ab.py:
+    // +17 % over the halo kernel on 3x3 256->256, +75 % on the 12544->1024 FC; loses on the HBM-bound K < 1024 layers)
+    // and it needs enough 256x256 tiles to fill whole rounds of the 256 CUs (one workgroup per CU, ~1.2x the per-CU rate
+    // of four resident 128x128 workgroups; a partial last round costs a full tile time there, a large fraction of a round
+    // on the 128x128 kernel -- see below).  Unit: one 128x128 tile at the full-CU 128x128 rate.
+    const long long pp_blocks = (M + 255) / 256 * (a.Cout / 256), sb_blocks = (M + 127) / 128 * ((a.Cout + 127) / 128);
+    const double t_pp = (double)((pp_blocks + 255) / 256) * (4.0 / 1.2);
+    // a partial last round is expensive on the single-buffer kernel: the few workgroups left run alone on their CUs, nobody hides
+    // their DMA latency (~1.3 us per K tile).  Measured r01, batch 32: 256->256 3x3 @50x84 = 2.05 rounds: 194 us vs ping-pong
+    // (3 rounds) 176 us; 1024->256 1x1 @50x84: 107 vs 98 us -> a partial round costs 0.6-1.0 of a full one.
+    const double sb_part = 2.5 + 1.5 * ((double)(sb_blocks % 1024) / 1024.0), sb_lone = 0.0726 * (double)(a.Kpad / BK);
+    const double t_sb = (double)(sb_blocks / 1024) * 4.0 + (sb_blocks % 1024 ? (sb_part > sb_lone ? sb_part : sb_lone) : 0.0);
+    const bool pp_ok = fast && dma_ok && a.Cout % 256 == 0 && a.Kpad >= 1024 && pp_blocks >= 128 && t_pp <= t_sb;
+    // HALO form of the ping-pong kernel (3x3 / s1 / p1, korder-1 weights): 16 x 16-pixel tiles, the 18 x 18 halo staged once per channel
+    // chunk instead of the B tile once per tap.  Auto where the 2-D tiles cover the image with little waste and the layer is long enough
+    // for the energy per K tile to matter (r03 tools/pp_halo_ab.py)
+    const long long halo_tiles = (long long)a.N * pingpong_halo_tiles_per_image(a.H, a.W, nullptr, nullptr);
+    const bool halo_ok_pp = fast && dma_ok && pingpong_halo_takes(a) && plain_out && a.Cout % 256 == 0;
+    // r03 tools/pp_halo_ab.py (batch 60, same box, interleaved, bit-identical; with the conflict-free lane -> pixel map): on 200x336 (0.2 % idle
+    // tile pixels) the fused-head form gains 10.3 %, the persistent form 3.4 %, the one-tile form 8.5 % (= the persistent HALO form); on
+    // 100x168 (9 % idle) the head form +3.7 %, the persistent form -3 %; on 50x84 (22 % idle) everything loses 8-14 %.  In the step
+    // (profiles/r03_pp_halo_step_ab.txt): head form -0.59 ms, persistent P2 form another -0.40 ms -> auto for the head form from 90 % tile
+    // efficiency, for the persistent form from 99 %
+    const double halo_eff = (double)M / (double)(halo_tiles * 256);
+    const bool halo_pp = halo_ok_pp && (force_halo || (!no_halo && ((head && halo_eff >= 0.90) || halo_eff >= 0.99)));
+    if (head) return pingpong_launch(a, pingpong_wants_16x16(a), false, halo_pp, plain_out, true);
+    // 3x3 layers on <= 256 channels: the 64-cout halo-reuse kernel at four workgroups per CU beats the 128x128 kernel wherever
+    // the ping-pong kernel does not apply, and beats the ping-pong kernel when its 256x256 tiles fill the last of several rounds
+    // badly (r01 tools/conv_ab_yolo.py, batch 32: 128->128 @80x80 +11 %, 256->256 @20x20 +16 %, 256->256 @80x80 (3.1 rounds) +8 %;
+    // one-round grids and K = 4608 layers stay where they were -- except Cout not a multiple of 128, where the 128x128 kernel pads:
+    // 512->320 @40x40 +23 %, tools/dispatch_audit.py)
+    const long long pp_rounds = (pp_blocks + 255) / 256;
+    const bool pp_ragged = pp_rounds >= 2 && (double)pp_blocks < 0.85 * (double)(pp_rounds * 256);
+    // ... provided its 8x16-pixel tiles cover the image without much waste (100x168: 8 % idle lanes and the 128x128 kernel is 3 %
+    // ahead), or the whole grid is resident at once anyway (<= 1024 workgroups: latency-bound, the halo kernel's shorter chain wins)
+    const long long h_tiles = (long long)a.N * ((a.H + HT_H - 1) / HT_H) * ((a.W + HT_W - 1) / HT_W);
+    const bool halo_fits = (double)a.H * a.W * a.N >= 0.95 * (double)(h_tiles * HT_H * HT_W) || h_tiles * (a.Cout / 64) <= 1024;
+    // 64-cout tiles of the halo kernel (a channel-concat output is fine: the kernel stores with the output tensor's channel stride;
+    // sub-pixel addressing is not)
+    const bool halo64_ok = dma_ok && plain_out_halo && a.korder == 1 && a.kh == 3 && a.kw == 3 && a.stride == 1 && a.pad == 1 &&
+                           a.Cin % 64 == 0 && a.Cout % 64 == 0 && !a.res_up && a.Ho == a.H && a.Wo == a.W;   // (so is the padded Cout)
+    if (variant == V_AUTO && halo64_ok && (a.Cin <= 256 || (a.Cin <= 512 && a.Cout % 128 != 0)) && (!pp_ok || pp_ragged) && halo_fits)
+        return halo3x3_launch(64);
+    // the persistent form of the ping-pong kernel (no residual, plain / concat output, the cout tiles divide a 32-CU XCD, more than one
+    // round of tiles): auto for the long-K layers (r02 tools/pp_pers_ab.py, batch 60, bit-identical: 3x3 256->256 +3.2...4.4 %, 3x3 512->512
+    // +4.2 %; the K = 1024 1x1 layers lose 4-5 %: behind a tile's prologue DMAs sit the previous tile's stores, and the loop's first counted
+    // wait then covers their write latency -- 1 / 16 of such a tile's K loop)
+    const bool pers_ok = fast && dma_ok && a.Cout % 256 == 0 && !a.res && !a.res_up && plain_out && 32 % (a.Cout / 256) == 0 && pp_blocks > 256;
+    const bool pers_halo = halo_ok_pp && !a.res && 32 % (a.Cout / 256) == 0 && halo_tiles * (a.Cout / 256) > 256;   // the persistent HALO form fits
+    if (pers_ok && (variant == V_PERS || (variant == V_AUTO && !no_pers && pp_ok && a.Kpad >= tn.pers_min_k))) {
+        // (persistent + HALO exists on the 16x16x32 MFMA shape only: the 32x32x16 instantiation needs 258 registers)
+        if (halo_pp && pers_halo) return pingpong_launch(a, 1, true, true, plain_out);
+        return pingpong_launch(a, pingpong_wants_16x16(a), true, false, plain_out);
+    }
+    if (variant == V_PERS) variant = V_AUTO;
+    if (variant == V_AUTO && pp_ok) return pingpong_launch(a, pingpong_wants_16x16(a), false, halo_pp, plain_out);
+    if (variant == V_HALO128 && halo_ok && !a.res_up) return halo3x3_launch(128);  // superseded by the paths around it
+    if (halo64_ok && (variant == V_HALO64 || (variant == V_AUTO && ctile == 64))) return halo3x3_launch(64);  // auto for Cout <= 64
+    const bool pp_fits = fast && dma_ok && a.Cout % 256 == 0;
+    if (pp_fits && variant == V_PP_PERS_HALO && pers_halo) return pingpong_launch(a, 1, true, true, plain_out);
+    if (pp_fits && (variant == V_PP_HALO || variant == V_PP16_HALO || variant == V_PP_PERS_HALO))
+        return pingpong_launch(a, variant != V_PP_HALO, false, halo_ok_pp, plain_out);
+    if (pp_fits && (variant == V_PP || variant == V_PP16)) return pingpong_launch(a, variant == V_PP16, false, false, plain_out);
+    if (kDiag && pp_fits && (variant == V_DIAG_PP16_STAMPS || (variant >= V_DIAG_NOSTAGE && variant <= V_DIAG_PP_STAMPS)))
+        return pingpong_launch(a, variant == V_DIAG_PP16_STAMPS, false, false, plain_out, false,
+                               variant == V_DIAG_NOSTAGE ? 1 : (variant == V_DIAG_NOSTORE ? 2 : 4));
+    md_conv_launch r = igemm_launch(a, variant == V_IGEMM_REG ? 0 : (fast ? 2 : 1), ctile, plain_out);
+    // one LDS staging buffer by default: measured r01 (tools/conv_ab.py), 4 resident workgroups per CU with a serial
+    // DMA -> MFMA loop beat 2 double-buffered ones on every benchmark layer (+8...43 %); the codes that predate that default (2 and the
+    // fall-backs of 11 / 15 / 22 / 27 and the MD_DIAG ping-pong codes) keep the double buffer, the register-staged MODE 0 has no DMA
+    // (r03: the first A/Bs of 34 / 35 ran their fall-back on the double-buffered loop and read 1.5 ms per step too slow)
+    if (variant == V_AUTO)
+        // a grid of fewer than two workgroups per CU with a long K loop: nobody else hides the DMA latency, stage the next tile
+        // while this one is multiplied (512->512 @20x20, batch 32: +11 %)
+        r.single_buf = !(ctile == 128 && sb_blocks <= 512 && a.Kpad / BK >= 4);
+    else
+        r.single_buf = r.mode != 0 && (variant == V_IGEMM_SBUF || variant >= V_PP_HALO);
+    return r;
+}
+
+// The fused RPN head applies (to one slice of the call)
+static bool conv_head_fuses(const ConvArgs &a) {
+    const bool fast = a.Cin % 64 == 0 && a.kh * a.kw <= 32;
+    return fast && a.w_bytes != 0 && a.Cout == 256 && !a.adv && !a.res && a.relu == 1 && (long long)(a.M + 255) / 256 >= 64;
+}
+
+struct ConvPlan {
+    md_conv_launch *out; int first, cap, n;   // records [first, first + cap) go to out; n counts them all
+    bool two_launch;         // md_conv2d_head through a temporary
+};
+
+// every launch of one call: one per image slice
+static int plan_call(const ConvCall &c, bool head, int sub, ConvPlan &p) {
+    for (long long n0 = 0; n0 < c.a.N && !c.empty; n0 += c.per) {
+        const long long nn = c.a.N - n0 < c.per ? c.a.N - n0 : c.per;
+        ConvArgs a = conv_slice(c, n0, nn);
+        const int variant = a.w_bytes ? c.variant : V_IGEMM_REG;   // offsets past the 32-bit LDS-DMA reach: the register-staged kernel
+        if (a.korder != 0 && (a.korder != 1 || variant == V_IGEMM_REG || a.Cin % 64 || a.kh * a.kw > 32)) return MD_ERR_ARG;
+        md_conv_launch r = conv_choose(a, variant, c.tn, head);
+        r.sub = sub; r.n0 = (int)n0; r.nn = (int)nn;
+        int xarg[3];
+        if (const int rc = conv_geometry(a, c.tn, r, xarg)) return rc;
+        if (p.n >= p.first && p.n - p.first < p.cap) p.out[p.n - p.first] = r;
+        ++p.n;
+    }
+    return MD_OK;
+}
+
+// ---- validate: the argument checks of each op, filling a ConvCall
+
+static int validate_conv2d(int nparam, void **params, int *ndims, int64_t **shapes, const char **dtypes, const void *extra, ConvCall &c) {
     if (nparam != 5) return MD_ERR_NPARAM;
     if (!params || !extra || !params[1] || !params[2]) return MD_ERR_ARG;  // x / y may be null for an empty batch
     if (!dtype_is(dtypes, 0, "bfloat16") || !dtype_is(dtypes, 1, "bfloat16") || !dtype_is(dtypes, 2, "float32") ||
@@ -1917,40 +1985,20 @@ static int conv2d_entry(MD_AOT_ARGS, const HeadArgs *head) {
     if (!ndims || !shapes || ndims[0] != 4 || ndims[1] != 2 || ndims[4] != 4) return MD_ERR_ARG;
     const md_conv2d_attrs *at = (const md_conv2d_attrs *)extra;
     if (at->reserved0 != 0) return MD_ERR_ARG;
-    const Tune tn = resolve_tune(&at->tune);
-    const long long chunk_limit = tn.chunk_limit;   // per call (md_conv_tune.chunk_limit)
+    c = ConvCall{};
+    c.tn = resolve_tune(&at->tune);
     // The LDS-DMA kernels address the activation tensor with 32-bit byte offsets.  A batch whose input (or output /
     // residual, which the kernels address with 64-bit math but the same image split applies to) exceeds 2 GiB is run
     // as consecutive image chunks on the same stream: every tensor of the call is sliced along N.
-    {
-        const long long n_img = shapes[0][0];
-        const long long x_img = shapes[0][1] * shapes[0][2] * shapes[0][3] * 2;
-        if (n_img > 1 && x_img > 0 && x_img < chunk_limit && n_img * x_img >= chunk_limit && shapes[4][0] == n_img &&
-            (!params[3] || (ndims[3] == 4 && shapes[3][0] == n_img))) {
-            const long long per_max = chunk_limit / x_img;                 // images a chunk may hold (>= 1)
-            const long long n_chunks = (n_img + per_max - 1) / per_max;
-            const long long per = (n_img + n_chunks - 1) / n_chunks;          // even split: no tiny last chunk
-            const long long y_img = shapes[4][1] * shapes[4][2] * shapes[4][3] * 2;
-            const long long r_img = params[3] ? shapes[3][1] * shapes[3][2] * shapes[3][3] * 2 : 0;
-            for (long long n0 = 0; n0 < n_img; n0 += per) {
-                const long long nn = n_img - n0 < per ? n_img - n0 : per;
-                int64_t sx[4] = {nn, shapes[0][1], shapes[0][2], shapes[0][3]};
-                int64_t sy[4] = {nn, shapes[4][1], shapes[4][2], shapes[4][3]};
-                int64_t sr[4] = {nn, 0, 0, 0};
-                if (params[3]) { sr[1] = shapes[3][1]; sr[2] = shapes[3][2]; sr[3] = shapes[3][3]; }
-                int64_t *sh2[5] = {sx, shapes[1], shapes[2], params[3] ? sr : shapes[3], sy};
-                void *p2[5] = {(char *)params[0] + n0 * x_img, params[1], params[2],
-                               params[3] ? (void *)((char *)params[3] + n0 * r_img) : nullptr, (char *)params[4] + n0 * y_img};
-                HeadArgs h2;
-                if (head) { h2 = *head; h2.y2 += n0 * shapes[4][1] * shapes[4][2] * 16; }
-                const int rc = conv2d_entry(nparam, p2, ndims, sh2, dtypes, stream, extra, head ? &h2 : nullptr);
-                if (rc != MD_OK) return rc;
-            }
-            return MD_OK;
-        }
+    const long long n_img = shapes[0][0], x_img = shapes[0][1] * shapes[0][2] * shapes[0][3] * 2;
+    c.per = n_img;
+    if (n_img > 1 && x_img > 0 && x_img < c.tn.chunk_limit && n_img * x_img >= c.tn.chunk_limit && shapes[4][0] == n_img &&
+        (!params[3] || (ndims[3] == 4 && shapes[3][0] == n_img))) {
+        const long long per_max = c.tn.chunk_limit / x_img;          // images a chunk may hold (>= 1)
+        const long long n_chunks = (n_img + per_max - 1) / per_max;
+        c.per = (n_img + n_chunks - 1) / n_chunks;                    // even split: no tiny last chunk
     }
-    int variant_override = -1;
-    ConvArgs a = {};   // (x2 == null: not a dual launch)
+    ConvArgs &a = c.a;   // (x2 == null: not a dual launch)
     a.x = (const uint16_t *)params[0];
     a.w = (const uint16_t *)params[1];
     a.bias = (const float *)params[2];
@@ -1964,6 +2012,7 @@ static int conv2d_entry(MD_AOT_ARGS, const HeadArgs *head) {
         if (at->x_c_off < 0 || at->x_c_off % 8 || at->x_cin % 8 || at->x_c_off + at->x_cin > a.Xs) return MD_ERR_ARG;
         a.Cin = at->x_cin;
         if (a.x) a.x += at->x_c_off;
+        c.x_off = at->x_c_off;
     } else if (at->x_c_off != 0) return MD_ERR_ARG;
     a.Hf = (int)shapes[4][1]; a.Wf = (int)shapes[4][2]; a.Ctot = (int)shapes[4][3];
     a.kh = at->kh; a.kw = at->kw; a.stride = at->stride; a.pad = at->pad; a.relu = at->relu;
@@ -1971,21 +2020,13 @@ static int conv2d_entry(MD_AOT_ARGS, const HeadArgs *head) {
     a.adv = at->adv != 0;
     a.korder = at->korder;
     a.res_up = at->res_upsample != 0 && params[3] != nullptr;
-    // one LDS staging buffer by default: measured r01 (tools/conv_ab.py), 4 resident workgroups per CU with a serial
-    // DMA -> MFMA loop beat 2 double-buffered ones on every benchmark layer (+8...43 %); variant 2 keeps the double buffer
-    // (every "auto, except ..." code counts as auto here: r03's first A/Bs of 34 / 35 / 39 / 40 ran their arm on the double-buffered loop
-    // and read 1.5 ms per step too slow)
-    a.single_buf = at->variant == 0 || at->variant == 20 || at->variant == 25 || (at->variant >= 30 && at->variant <= 40);
-    a.stamp = 0; a.dbg = nullptr;
-    if ((at->variant >= 17 && at->variant <= 19) || at->variant == 25 || at->variant == 26) {
-        // timing ablations / stamp builds: wrong results by construction, so not part of the product library
-        if (!kDiag) return MD_ERR_ARG;
+    if (!variant_known(at->variant)) return MD_ERR_ARG;
+    c.variant = at->variant;
 #ifdef MD_DIAG
-        a.stamp = at->variant == 25; a.dbg = g_stamp_buf;
+    a.stamp = at->variant == V_DIAG_IGEMM_STAMPS;
+    if (variant_diag(at->variant)) a.dbg = g_stamp_buf;
 #endif
-    }
-    if (at->variant == 25) variant_override = 2;
-    if (at->variant == 20) variant_override = 2;
+    if (c.variant == V_DIAG_IGEMM_STAMPS) c.variant = V_IGEMM_SBUF;
     if (a.res_up && a.adv) return MD_ERR_ARG;
     if (!a.adv) {
         a.Ho = a.Hf; a.Wo = a.Wf; a.Cout = a.Ctot;
@@ -2019,212 +2060,21 @@ static int conv2d_entry(MD_AOT_ARGS, const HeadArgs *head) {
     if (a.res_up && (ndims[3] != 4 || shapes[3][0] != a.N || shapes[3][1] != (a.Ho + 1) / 2 || shapes[3][2] != (a.Wo + 1) / 2 ||
                      shapes[3][3] != a.Cout))
         return MD_ERR_ARG;
-    const long long M = (long long)a.N * a.Ho * a.Wo;
-    if (M <= 0) return MD_OK;
+    c.empty = (long long)a.N * a.Ho * a.Wo <= 0;
+    if (c.empty) return MD_OK;
     if (!params[0] || !params[4]) return MD_ERR_ARG;
-    if (M > 0x7fffffffLL || (long long)a.N * a.H * a.W > 0x7fffffffLL / 2 || a.H > 32000 || a.W > 32000)
-        return MD_ERR_SIZE;
-    a.M = (int)M;
+    // (per chunk: the first chunk is the largest)
+    if (c.per * a.Ho * a.Wo > 0x7fffffffLL || c.per * a.H * a.W > 0x7fffffffLL / 2 || a.H > 32000 || a.W > 32000) return MD_ERR_SIZE;
     a.cpt = a.Cin / 8;
     a.pointwise = a.kh == 1 && a.kw == 1 && a.stride == 1 && a.pad_top == 0 && a.pad_left == 0 && a.H == a.Ho && a.W == a.Wo;
-    hipStream_t s = (hipStream_t)stream;
-    // variant: 0 = auto (cost model below); 1 = register-staged 128x128; 2 = LDS-DMA 128x128 with two staging buffers;
-    // 11 = 128-cout halo kernel; 15 / 22 = ping-pong kernel (32x32x16 / 16x16x32 MFMA);
-    // 20 = LDS-DMA 128x128 with one staging buffer; 27 = 64-cout halo kernel; 30 = conv1x1_stream_kernel where it applies,
-    // 31 = auto without it; 17-19 / 25 = timing ablations / stamps, MD_DIAG
-    // builds only (the product library answers MD_ERR_ARG)
-    int variant = variant_override >= 0 ? variant_override : at->variant;
-    const long long x_bytes = (long long)a.N * a.H * a.W * a.Xs * 2 - (at->x_cin > 0 ? at->x_c_off * 2 : 0), w_bytes = (long long)cout_pad * a.Kpad * 2;
-    const bool dma_ok = x_bytes < 0x7fff0000LL && w_bytes < 0x7fff0000LL;  // 32-bit DMA offsets, out-of-range marker 2^31
-    a.x_bytes = (unsigned)(dma_ok ? x_bytes : 0);
-    a.w_bytes = (unsigned)(dma_ok ? w_bytes : 0);
-    if (!dma_ok) variant = 1;
-    if (a.korder != 0 && (a.korder != 1 || variant == 1 || a.Cin % 64 || a.kh * a.kw > 32)) return MD_ERR_ARG;
-    // weight-stationary streaming kernel for pointwise layers with K <= 512 (variant 30 forces it where it applies)
-    // auto: where it measured faster than the 128x128 kernel INSIDE the Faster R-CNN step (r02 tools/stream_insitu_tune.py, batch 60;
-    // a replay loop on one layer flatters it: the activation tensor then survives in the Infinity Cache between launches):
-    // 256->1024 + residual -0.40 ms/step (5 launches), 512->256 -0.12, 512->2048 + residual -0.09; 128->512 + residual +0.15 (stays on
-    // the 128x128 kernel); the 128-cout forms lose 2-15 % -- and every workgroup gets at least 8 tiles to stream past its weights
-    const bool no_stream = variant == 31;   // 31 = the dispatcher's choice without conv1x1_stream_kernel (A/B)
-    const bool no_pers = variant == 33;     // 33 = the dispatcher's choice without the persistent form of the ping-pong kernel (A/B)
-    const bool force_halo = variant == 34;  // 34 = the dispatcher's choice, with the HALO form of the ping-pong kernel wherever it applies
-    const bool no_halo = variant == 35;     // 35 = the dispatcher's choice without the HALO form (A/B)
-    const bool halo_fit = variant == 39;    // 39 = auto, with the HALO form also for the persistent / one-tile forms where the tiles fit the image (A/B)
-    const bool halo_not_pers = variant == 40;   // 40 = auto, but layers the persistent form would take run on the one-tile HALO form where the tiles fit (A/B)
-    if (no_stream || no_pers || force_halo || no_halo || halo_fit || halo_not_pers) variant = 0;
-    const bool stream_auto = variant == 0 && !no_stream && !head && dma_ok && stream1x1_takes(a) && a.Cout % 256 == 0 && a.Cin != 128 &&
-                             (M + 31) / 32 * (a.Cout / (a.Cin == 512 ? 128 : 256)) >= 4096;
-    if ((variant == 30 || stream_auto) && !head) {
-        const int rc = dma_ok ? launch_conv1x1_stream(a, s, tn) : MD_ERR_UNSUPPORTED_STREAM;
-        if (rc != MD_ERR_UNSUPPORTED_STREAM) return rc;
-        variant = 0;
-    }
-    const bool fast = a.Cin % 64 == 0 && a.kh * a.kw <= 32;  // MODE 2 preconditions (then Kpad == Kreal)
-    // 3x3 / stride 1 / pad 1 with korder-1 weights: halo-reuse kernel (variant 0 auto or 11 forced)
-    const bool halo_ok = dma_ok && !a.adv && a.korder == 1 && a.kh == 3 && a.kw == 3 && a.stride == 1 && a.pad == 1 &&
-                         a.Cin % 64 == 0 && ctile == 128;
-    // MFMA-bound layers (K >= 1024, Cout a multiple of 256): the 256x256 ping-pong kernel (measured r01, tools/conv_ab.py:
-    // +17 % over the halo kernel on 3x3 256->256, +75 % on the 12544->1024 FC; loses on the HBM-bound K < 1024 layers)
-    // and it needs enough 256x256 tiles to fill whole rounds of the 256 CUs (one workgroup per CU, ~1.2x the per-CU rate
-    // of four resident 128x128 workgroups; a partial last round costs a full tile time there, a large fraction of a round
-    // on the 128x128 kernel -- see below).  Unit: one 128x128 tile at the full-CU 128x128 rate.
-    const long long pp_blocks = (M + 255) / 256 * (a.Cout / 256), sb_blocks = (M + 127) / 128 * ((a.Cout + 127) / 128);
-    const double t_pp = (double)((pp_blocks + 255) / 256) * (4.0 / 1.2);
-    const double sb_last = (double)(sb_blocks % 1024) / 1024.0;
-    // a partial last round is expensive on the single-buffer kernel: the few workgroups left run alone on their CUs, nobody hides
-    // their DMA latency (~1.3 us per K tile).  Measured r01, batch 32: 256->256 3x3 @50x84 = 2.05 rounds: 194 us vs ping-pong
-    // (3 rounds) 176 us; 1024->256 1x1 @50x84: 107 vs 98 us -> a partial round costs 0.6-1.0 of a full one.
-    const double sb_part = 2.5 + 1.5 * sb_last, sb_lone = 0.0726 * (double)(a.Kpad / BK);
-    const double t_sb = (double)(sb_blocks / 1024) * 4.0 + (sb_blocks % 1024 ? (sb_part > sb_lone ? sb_part : sb_lone) : 0.0);
-    const bool pp_ok = fast && dma_ok && a.Cout % 256 == 0 && a.Kpad >= 1024 && pp_blocks >= 128 && t_pp <= t_sb;
-    // HALO form of the ping-pong kernel (3x3 / s1 / p1, korder-1 weights): 16 x 16-pixel tiles, the 18 x 18 halo staged once per channel
-    // chunk instead of the B tile once per tap.  Auto where the 2-D tiles cover the image with little waste and the layer is long enough
-    // for the energy per K tile to matter (r03 tools/pp_halo_ab.py)
-    const long long halo_tiles = (long long)a.N * pingpong_halo_tiles_per_image(a.H, a.W, nullptr, nullptr);
-    const bool halo_plain_out = !a.adv || (a.os == 1 && a.oy == 0 && a.ox == 0 && a.Ho == a.Hf && a.Wo == a.Wf);
-    const bool halo_ok_pp = fast && dma_ok && pingpong_halo_takes(a) && halo_plain_out && a.Cout % 256 == 0;
-    // r03 tools/pp_halo_ab.py (batch 60, same box, interleaved, bit-identical; with the conflict-free lane -> pixel map): on 200x336 (0.2 % idle
-    // tile pixels) the fused-head form gains 10.3 %, the persistent form 3.4 %, the one-tile form 8.5 % (= the persistent HALO form); on
-    // 100x168 (9 % idle) the head form +3.7 %, the persistent form -3 %; on 50x84 (22 % idle) everything loses 8-14 %.  In the step
-    // (profiles/r03_pp_halo_step_ab.txt): head form -0.59 ms, persistent P2 form another -0.40 ms -> auto for the head form from 90 % tile
-    // efficiency, for the persistent form from 99 %
-    const double halo_eff = (double)M / (double)(halo_tiles * 256);
-    const bool halo_auto = halo_ok_pp && !no_halo && ((head != nullptr && halo_eff >= 0.90) || (!halo_not_pers && halo_eff >= 0.99));
-    const bool halo_pp = halo_ok_pp && (force_halo || halo_auto || (halo_fit && halo_eff >= 0.99));
-    if (head) {
-        if (!(fast && dma_ok && a.Cout == 256 && !a.adv && !a.res && a.relu == 1 && pp_blocks >= 64)) return MD_ERR_UNSUPPORTED_INTERNAL;
-        a.w2 = head->w2; a.b2 = head->b2; a.y2 = head->y2;
-        return launch_conv_pingpong_head(a, s, halo_pp);
-    }
-    // 3x3 layers on <= 256 channels: the 64-cout halo-reuse kernel at four workgroups per CU beats the 128x128 kernel wherever
-    // the ping-pong kernel does not apply, and beats the ping-pong kernel when its 256x256 tiles fill the last of several rounds
-    // badly (r01 tools/conv_ab_yolo.py, batch 32: 128->128 @80x80 +11 %, 256->256 @20x20 +16 %, 256->256 @80x80 (3.1 rounds) +8 %;
-    // one-round grids and K = 4608 layers stay where they were -- except Cout not a multiple of 128, where the 128x128 kernel pads:
-    // 512->320 @40x40 +23 %, tools/dispatch_audit.py)
-    const long long pp_rounds = (pp_blocks + 255) / 256;
-    const bool pp_ragged = pp_rounds >= 2 && (double)pp_blocks < 0.85 * (double)(pp_rounds * 256);
-    // ... provided its 8x16-pixel tiles cover the image without much waste (100x168: 8 % idle lanes and the 128x128 kernel is 3 %
-    // ahead), or the whole grid is resident at once anyway (<= 1024 workgroups: latency-bound, the halo kernel's shorter chain wins)
-    const long long h_tiles = (long long)a.N * ((a.H + HT_H - 1) / HT_H) * ((a.W + HT_W - 1) / HT_W);
-    const bool halo_fits = (double)a.H * a.W * a.N >= 0.95 * (double)(h_tiles * HT_H * HT_W) || h_tiles * (a.Cout / 64) <= 1024;
-    const bool cat_only_h = !a.adv || (a.os == 1 && a.oy == 0 && a.ox == 0 && a.Ho == a.Hf && a.Wo == a.Wf && a.pad_top == a.pad &&
-                                       a.pad_left == a.pad && (!a.res || a.Rs));
-    const bool halo64_first = variant == 0 && !head && dma_ok && cat_only_h && a.korder == 1 && a.kh == 3 && a.kw == 3 && a.stride == 1 &&
-                              a.pad == 1 && a.Cin % 64 == 0 && (a.Cin <= 256 || (a.Cin <= 512 && a.Cout % 128 != 0)) && a.Cout % 64 == 0 &&
-                              cout_pad % 64 == 0 && !a.res_up &&
-                              a.Ho == a.H && a.Wo == a.W && (!pp_ok || pp_ragged) && halo_fits;
-    if (halo64_first) return launch_conv3x3_halo<64, true>(a, s);
-    // the persistent form of the ping-pong kernel (no residual, plain / concat output, the cout tiles divide a 32-CU XCD, more than one
-    // round of tiles): auto for the long-K layers (r02 tools/pp_pers_ab.py, batch 60, bit-identical: 3x3 256->256 +3.2...4.4 %, 3x3 512->512
-    // +4.2 %; the K = 1024 1x1 layers lose 4-5 %: behind a tile's prologue DMAs sit the previous tile's stores, and the loop's first counted
-    // wait then covers their write latency -- 1 / 16 of such a tile's K loop); variant 32 forces it, 33 = auto without it
-    {
-        const bool cat_only_p = !a.adv || (a.os == 1 && a.oy == 0 && a.ox == 0 && a.Ho == a.Hf && a.Wo == a.Wf);
-        const bool pers_ok = fast && dma_ok && a.Cout % 256 == 0 && !a.res && !a.res_up && cat_only_p && 32 % (a.Cout / 256) == 0 && pp_blocks > 256;
-        const bool pers_auto = variant == 0 && !no_pers && pp_ok && pers_ok && a.Kpad >= tn.pers_min_k &&
-                               !(halo_not_pers && halo_ok_pp && (double)M >= 0.99 * (double)(halo_tiles * 256));
-        if ((variant == 32 || pers_auto) && pers_ok) {
-            // (persistent + HALO exists on the 16x16x32 MFMA shape only: the 32x32x16 instantiation needs 258 registers)
-            if (halo_pp && 32 % (a.Cout / 256) == 0 && halo_tiles * (a.Cout / 256) > 256) return launch_conv_pingpong_pers<1, true>(a, s);
-            return pingpong_wants_16x16(a) ? launch_conv_pingpong_pers<1>(a, s) : launch_conv_pingpong_pers<0>(a, s);
-        }
-        if (variant == 32) variant = 0;
-    }
-    if (variant == 0 && pp_ok && (halo_pp || (halo_not_pers && halo_ok_pp && (double)M >= 0.99 * (double)(halo_tiles * 256)))) return pingpong_wants_16x16(a) ? launch_conv_pingpong_halo<1>(a, s) : launch_conv_pingpong_halo<0>(a, s);
-    if (variant == 0 && pp_ok) return pingpong_wants_16x16(a) ? launch_conv_pingpong<0, 1>(a, s) : launch_conv_pingpong<0>(a, s);
-    if (halo_ok && !a.res_up && variant == 11) return launch_conv3x3_halo<128, false>(a, s);  // superseded by the paths around it
-    // 64-cout tiles of the halo kernel at four workgroups per CU (variant 27; auto for Cout <= 64)
-    // (a channel-concat output is fine: the kernel stores with the output tensor's channel stride; sub-pixel addressing is not)
-    const bool cat_only = !a.adv || (a.os == 1 && a.oy == 0 && a.ox == 0 && a.Ho == a.Hf && a.Wo == a.Wf && a.pad_top == a.pad &&
-                                     a.pad_left == a.pad && (!a.res || a.Rs));
-    const bool halo64_ok = dma_ok && cat_only && a.korder == 1 && a.kh == 3 && a.kw == 3 && a.stride == 1 && a.pad == 1 &&
-                           a.Cin % 64 == 0 && a.Cout % 64 == 0 && cout_pad % 64 == 0 && !a.res_up && a.Ho == a.H && a.Wo == a.W;
-    if (halo64_ok && (variant == 27 || (variant == 0 && ctile == 64))) return launch_conv3x3_halo<64, true>(a, s);
-    if (variant == 11) variant = 2;
-    // 36 / 37: the HALO form pinned (32x32x16 / 16x16x32 MFMA), 38: its persistent form; where it does not apply: the plain ping-pong kernel
-    if ((variant == 36 || variant == 37 || variant == 38) && fast && dma_ok && a.Cout % 256 == 0) {
-        const bool gen_plain = (!a.adv || halo_plain_out) && !a.res_up;
-        if (halo_ok_pp && gen_plain) {
-            if (variant == 38 && !a.res && 32 % (a.Cout / 256) == 0 && halo_tiles * (a.Cout / 256) > 256) return launch_conv_pingpong_pers<1, true>(a, s);
-            return variant == 36 ? launch_conv_pingpong_halo<0>(a, s) : launch_conv_pingpong_halo<1>(a, s);
-        }
-        return variant == 36 ? launch_conv_pingpong<0>(a, s) : launch_conv_pingpong<0, 1>(a, s);
-    }
-    if (variant == 15 && fast && dma_ok && a.Cout % 256 == 0) return launch_conv_pingpong<0>(a, s);  // 256x256 ping-pong, 8 waves
-    if (variant == 22 && fast && dma_ok && a.Cout % 256 == 0) return launch_conv_pingpong<0, 1>(a, s);  // same, 16x16x32 MFMA
-#ifdef MD_DIAG
-    if (variant == 26 && fast && dma_ok && a.Cout % 256 == 0) return launch_conv_pingpong<4, 1>(a, s);   // stamps, 16x16x32 MFMA
-    if (variant >= 17 && variant <= 19 && fast && dma_ok && a.Cout % 256 == 0)                       // timing ablations
-        return variant == 17 ? launch_conv_pingpong<1>(a, s) : (variant == 18 ? launch_conv_pingpong<2>(a, s) : launch_conv_pingpong<4>(a, s));
-#endif
-    if (ctile != 128) {
-        if (variant == 1) return ctile == 64 ? launch_conv<256, 1, 4, 2, 2, 0>(a, s) : launch_conv<256, 1, 4, 1, 2, 0>(a, s);
-        if (fast) return ctile == 64 ? launch_conv<256, 1, 4, 2, 2, 2>(a, s) : launch_conv<256, 1, 4, 1, 2, 2>(a, s);
-        return ctile == 64 ? launch_conv<256, 1, 4, 2, 2, 1>(a, s) : launch_conv<256, 1, 4, 1, 2, 1>(a, s);
-    }
-    // a grid of fewer than two workgroups per CU with a long K loop: nobody else hides the DMA latency, stage the next tile
-    // while this one is multiplied (512->512 @20x20, batch 32: +11 %)
-    if (variant == 0 && sb_blocks <= 512 && a.Kpad / BK >= 4) a.single_buf = 0;
-    if (variant == 1) return launch_conv<256, 2, 2, 2, 2, 0>(a, s);               // register-staged, 64-bit addressing
-    return fast ? launch_conv<256, 2, 2, 2, 2, 2>(a, s) : launch_conv<256, 2, 2, 2, 2, 1>(a, s);
+    c.x_img = (long long)a.H * a.W * a.Xs; c.y_img = (long long)a.Hf * a.Wf * a.Ctot; c.w_bytes = (long long)cout_pad * a.Kpad * 2;
+    c.r_img = params[3] ? shapes[3][1] * shapes[3][2] * shapes[3][3] : 0;
+    return MD_OK;
 }
 
-extern "C" int md_conv2d(MD_AOT_ARGS) { return conv2d_entry(nparam, params, ndims, shapes, dtypes, stream, extra, nullptr); }
-
-// conv (Cout = 256, ReLU) followed by a 1x1 head with <= 16 output channels, in one launch where the ping-pong kernel
-// applies (the 256-channel intermediate then never leaves the CU); otherwise the two convolutions run back to back
-// through a stream-ordered temporary (or the caller's workspace).  The RPN head of the two-stage detectors: 3x3 conv +
-// ReLU -> [objectness | deltas].
-extern "C" int md_conv2d_head(MD_AOT_ARGS) {
-    // in: x[N,H,W,Cin], w[256,Kpad], bias[256], w2[32,256] (rows >= c2 zero), bias2[32] ; out: y2[N,Ho,Wo,16] ; [workspace]
-    if (nparam != 6 && nparam != 7) return MD_ERR_NPARAM;
-    if (!params || !extra || !ndims || !shapes || !params[3] || !params[4]) return MD_ERR_ARG;
-    if (!dtype_is(dtypes, 3, "bfloat16") || !dtype_is(dtypes, 4, "float32") || !dtype_is(dtypes, 5, "bfloat16")) return MD_ERR_ARG;
-    if (ndims[0] != 4 || ndims[1] != 2 || ndims[3] != 2 || ndims[5] != 4) return MD_ERR_ARG;
-    if (shapes[1][0] != 256 || shapes[3][0] < 16 || shapes[3][1] != 256 || numel(ndims, shapes, 4) < 16 || shapes[5][3] != 16 ||
-        shapes[5][0] != shapes[0][0])
-        return MD_ERR_ARG;
-    const md_conv2d_attrs *at = (const md_conv2d_attrs *)extra;
-    if (at->adv || at->relu != 1 || at->res_upsample) return MD_ERR_ARG;
-    const int64_t N = shapes[5][0], Ho = shapes[5][1], Wo = shapes[5][2];
-    if (N * Ho * Wo == 0) return MD_OK;
-    if (!params[0] || !params[5]) return MD_ERR_ARG;
-    // the conv as md_conv2d sees it: residual NULL, output [N,Ho,Wo,256] (never written by the fused kernel)
-    int64_t sy[4] = {N, Ho, Wo, 256}, snull[1] = {0};
-    int nd5[5] = {ndims[0], ndims[1], ndims[2], 0, 4};
-    int64_t *sh5[5] = {shapes[0], shapes[1], shapes[2], snull, sy};
-    const char *dt5[5] = {dtypes[0], dtypes[1], dtypes[2], nullptr, "bfloat16"};
-    HeadArgs head = {(const uint16_t *)params[3], (const float *)params[4], (uint16_t *)params[5]};
-    void *p5[5] = {params[0], params[1], params[2], nullptr, params[5] /* placeholder, not written */};
-    int rc = conv2d_entry(5, p5, nd5, sh5, dt5, stream, extra, &head);
-    if (rc != MD_ERR_UNSUPPORTED_INTERNAL) return rc;
-    // two launches through a temporary [N,Ho,Wo,256]
-    Scratch tmp;
-    const size_t bytes = (size_t)(N * Ho * Wo) * 256 * 2;
-    rc = tmp.acquire(bytes, nparam, params, ndims, shapes, 6, (hipStream_t)stream);
-    if (rc != MD_OK) return rc;
-    p5[4] = tmp.ptr;
-    rc = conv2d_entry(5, p5, nd5, sh5, dt5, stream, extra, nullptr);
-    if (rc != MD_OK) return rc;
-    md_conv2d_attrs a1 = {};
-    a1.kh = a1.kw = 1; a1.stride = 1; a1.pad = 0; a1.relu = 0; a1.variant = at->variant < 15 ? at->variant : 0;
-    a1.tune = at->tune;
-    int64_t sw2[2] = {shapes[3][0], 256}, sb2[1] = {shapes[3][0]};
-    int nd1[5] = {4, 2, 1, 0, 4};
-    int64_t *sh1[5] = {sy, sw2, sb2, snull, shapes[5]};
-    const char *dt1[5] = {"bfloat16", "bfloat16", "float32", nullptr, "bfloat16"};
-    void *p1[5] = {tmp.ptr, params[3], params[4], nullptr, params[5]};
-    return conv2d_entry(5, p1, nd1, sh1, dt1, stream, &a1, nullptr);
-}
-
-// y = act(W . [x_a ; x_b sampled with stride] + bias [+ residual]): ONE 1x1 GEMM over the K-concatenation of two inputs.
-// The use: the first block of a ResNet stage (centernet/src/resnet.py:139-178 with `downsample`, built by _make_layer :214-224):
-// out = relu(bn3(conv3(t2)) + bn_d(conv_d(x))) -- conv3 is 1x1 on the block's own feature map, conv_d a 1x1 conv with the block's stride
-// on its input.  [W3 | Wd] . [t2 ; x_strided] + (b3 + bd) is the same sum in one accumulator: no downsample launch, no Cout-channel
-// residual tensor written and re-read.  (One bf16 rounding instead of the three of the layer-by-layer path.)
 // in : x_a[N,Ho,Wo,Ca] bf16 (Ca % 64 == 0), x_b[N,Hb,Wb,Cb] bf16 (Cb % 64 == 0, Ho == (Hb-1)/stride_b + 1), w[Cout_pad, Ca + Cb] bf16,
 //      bias[Cout_pad] f32, residual[N,Ho,Wo,Cout] bf16 | NULL ; out y[N,Ho,Wo,Cout] bf16 (Cout > 64).  extra: md_conv1x1_dual_attrs
-extern "C" int md_conv1x1_dual(MD_AOT_ARGS) {
+static int validate_dual(int nparam, void **params, int *ndims, int64_t **shapes, const char **dtypes, const void *extra, ConvCall &c) {
     if (nparam != 6) return MD_ERR_NPARAM;
     if (!params || !extra || !ndims || !shapes || !params[2] || !params[3]) return MD_ERR_ARG;
     if (!dtype_is(dtypes, 0, "bfloat16") || !dtype_is(dtypes, 1, "bfloat16") || !dtype_is(dtypes, 2, "bfloat16") ||
@@ -2241,32 +2091,212 @@ extern "C" int md_conv1x1_dual(MD_AOT_ARGS) {
     const int64_t cout_pad = (Cout + 127) / 128 * 128;
     if (shapes[2][0] != cout_pad || shapes[2][1] != Ca + Cb || numel(ndims, shapes, 3) != cout_pad) return MD_ERR_ARG;
     if (params[4] && (ndims[4] != 4 || numel(ndims, shapes, 4) != N * Ho * Wo * Cout)) return MD_ERR_ARG;
-    if (N * Ho * Wo == 0) return MD_OK;
+    c = ConvCall{};
+    c.empty = N * Ho * Wo == 0;
+    if (c.empty) return MD_OK;
     if (!params[0] || !params[1] || !params[5]) return MD_ERR_ARG;
     if (Hb > 32000 || Wb > 32000) return MD_ERR_SIZE;
-    const long long xa_img = Ho * Wo * Ca * 2, xb_img = Hb * Wb * Cb * 2, w_bytes = cout_pad * (Ca + Cb) * 2;
+    const long long xa_img = Ho * Wo * Ca * 2, xb_img = Hb * Wb * Cb * 2;
     const long long big = xa_img > xb_img ? xa_img : xb_img;
-    if (big >= 0x7fff0000LL || w_bytes >= 0x7fff0000LL) return MD_ERR_SIZE;
-    const Tune tn = resolve_tune(&at->tune);
-    const long long lim = tn.chunk_limit > big ? tn.chunk_limit : big;
-    const long long per = lim / big < N ? lim / big : N;     // images per launch: both inputs stay inside the DMA reach
-    for (long long n0 = 0; n0 < N; n0 += per) {
-        const long long nn = N - n0 < per ? N - n0 : per;
-        ConvArgs a = {};
-        a.x = (const uint16_t *)params[0] + n0 * Ho * Wo * Ca;
-        a.x2 = (const uint16_t *)params[1] + n0 * Hb * Wb * Cb;
-        a.w = (const uint16_t *)params[2]; a.bias = (const float *)params[3];
-        a.res = params[4] ? (const uint16_t *)params[4] + n0 * Ho * Wo * Cout : nullptr;
-        a.y = (uint16_t *)params[5] + n0 * Ho * Wo * Cout;
-        a.N = (int)nn; a.H = (int)Ho; a.W = (int)Wo; a.Cin = (int)Ca; a.Xs = (int)Ca; a.Cout = (int)Cout; a.Ho = (int)Ho; a.Wo = (int)Wo;
-        a.kh = a.kw = 1; a.stride = 1; a.pad = 0; a.relu = at->relu;
-        a.Kpad = (int)(Ca + Cb); a.Kreal = a.Kpad; a.cpt = (int)(Ca / 8);
-        a.M = (int)(nn * Ho * Wo);
-        a.x_bytes = (unsigned)(nn * xa_img); a.w_bytes = (unsigned)w_bytes; a.x2_bytes = (unsigned)(nn * xb_img);
-        a.Hf = (int)Ho; a.Wf = (int)Wo; a.Ctot = (int)Cout; a.os = 1; a.pointwise = 1;
-        a.H2 = (int)Hb; a.W2 = (int)Wb; a.Xs2 = (int)Cb; a.stride2 = at->stride_b; a.nk_a = (int)(Ca / 64);
-        const int rc = launch_conv_dual(a, (hipStream_t)stream, tn);
+    c.w_bytes = cout_pad * (Ca + Cb) * 2;
+    if (big >= 0x7fff0000LL || c.w_bytes >= 0x7fff0000LL) return MD_ERR_SIZE;
+    c.tn = resolve_tune(&at->tune);
+    const long long lim = c.tn.chunk_limit > big ? c.tn.chunk_limit : big;
+    c.per = lim / big < N ? lim / big : N;     // images per launch: both inputs stay inside the DMA reach
+    ConvArgs &a = c.a;
+    a.x = (const uint16_t *)params[0]; a.x2 = (const uint16_t *)params[1]; a.w = (const uint16_t *)params[2]; a.bias = (const float *)params[3];
+    a.res = (const uint16_t *)params[4]; a.y = (uint16_t *)params[5];
+    a.N = (int)N; a.H = (int)Ho; a.W = (int)Wo; a.Cin = (int)Ca; a.Xs = (int)Ca; a.Cout = (int)Cout; a.Ho = (int)Ho; a.Wo = (int)Wo;
+    a.kh = a.kw = 1; a.stride = 1; a.pad = 0; a.relu = at->relu;
+    a.Kpad = (int)(Ca + Cb); a.Kreal = a.Kpad; a.cpt = (int)(Ca / 8);
+    a.Hf = (int)Ho; a.Wf = (int)Wo; a.Ctot = (int)Cout; a.os = 1; a.pointwise = 1;
+    a.H2 = (int)Hb; a.W2 = (int)Wb; a.Xs2 = (int)Cb; a.stride2 = at->stride_b; a.nk_a = (int)(Ca / 64);
+    c.x_img = Ho * Wo * Ca; c.x2_img = Hb * Wb * Cb; c.r_img = c.y_img = Ho * Wo * Cout;
+    return MD_OK;
+}
+
+// md_conv2d_head as two md_conv2d calls: c[0] the conv -- residual NULL, output [N,Ho,Wo,256] (never written by the fused kernel; in the
+// two-launch form the temporary, for which y2 stands in here) -- and c[1] the 1x1 head on that temporary (the two-launch form; its
+// validation result in rc1)
+static int validate_head(int nparam, void **params, int *ndims, int64_t **shapes, const char **dtypes, const void *extra, ConvCall *c, int &rc1) {
+    // in: x[N,H,W,Cin], w[256,Kpad], bias[256], w2[32,256] (rows >= c2 zero), bias2[32] ; out: y2[N,Ho,Wo,16] ; [workspace]
+    if (nparam != 6 && nparam != 7) return MD_ERR_NPARAM;
+    if (!params || !extra || !ndims || !shapes || !params[3] || !params[4]) return MD_ERR_ARG;
+    if (!dtype_is(dtypes, 3, "bfloat16") || !dtype_is(dtypes, 4, "float32") || !dtype_is(dtypes, 5, "bfloat16")) return MD_ERR_ARG;
+    if (ndims[0] != 4 || ndims[1] != 2 || ndims[3] != 2 || ndims[5] != 4) return MD_ERR_ARG;
+    if (shapes[1][0] != 256 || shapes[3][0] < 16 || shapes[3][1] != 256 || numel(ndims, shapes, 4) < 16 || shapes[5][3] != 16 ||
+        shapes[5][0] != shapes[0][0])
+        return MD_ERR_ARG;
+    const md_conv2d_attrs *at = (const md_conv2d_attrs *)extra;
+    if (at->adv || at->relu != 1 || at->res_upsample) return MD_ERR_ARG;
+    const int64_t N = shapes[5][0], Ho = shapes[5][1], Wo = shapes[5][2];
+    c[0] = ConvCall{}; c[0].empty = N * Ho * Wo == 0;
+    if (c[0].empty) return MD_OK;
+    if (!params[0] || !params[5]) return MD_ERR_ARG;
+    int64_t sy[4] = {N, Ho, Wo, 256}, snull[1] = {0}, sw2[2] = {shapes[3][0], 256}, sb2[1] = {shapes[3][0]};
+    int nd0[5] = {ndims[0], ndims[1], ndims[2], 0, 4}, nd1[5] = {4, 2, 1, 0, 4};
+    int64_t *sh0[5] = {shapes[0], shapes[1], shapes[2], snull, sy}, *sh1[5] = {sy, sw2, sb2, snull, shapes[5]};
+    const char *dt0[5] = {dtypes ? dtypes[0] : nullptr, dtypes ? dtypes[1] : nullptr, dtypes ? dtypes[2] : nullptr, nullptr, "bfloat16"};
+    const char *dt1[5] = {"bfloat16", "bfloat16", "float32", nullptr, "bfloat16"};
+    void *p0[5] = {params[0], params[1], params[2], nullptr, params[5]}, *p1[5] = {params[5], params[3], params[4], nullptr, params[5]};
+    md_conv2d_attrs a1 = {};
+    a1.kh = a1.kw = 1; a1.stride = 1; a1.pad = 0; a1.relu = 0; a1.variant = at->variant < 15 ? at->variant : 0;
+    a1.tune = at->tune;
+    rc1 = validate_conv2d(5, p1, nd1, sh1, dt1, &a1, c[1]);
+    if (const int rc = validate_conv2d(5, p0, nd0, sh0, dt0, extra, c[0])) return rc;
+    c[0].a.w2 = (const uint16_t *)params[3]; c[0].a.b2 = (const float *)params[4]; c[0].a.y2 = (uint16_t *)params[5];
+    return MD_OK;
+}
+
+enum ConvOp { OP_CONV2D, OP_HEAD, OP_DUAL };
+
+// validate + plan of one op.  c[1]: md_conv2d_head's 1x1 head when the fused kernel does not apply (records with sub = 1).
+static int conv_op_plan(ConvOp op, int nparam, void **params, int *ndims, int64_t **shapes, const char **dtypes, const void *extra,
+                        ConvCall *c, ConvPlan &p) {
+    p.n = 0;
+    p.two_launch = false;
+    if (op != OP_HEAD) {
+        const int rc = op == OP_DUAL ? validate_dual(nparam, params, ndims, shapes, dtypes, extra, c[0])
+                                     : validate_conv2d(nparam, params, ndims, shapes, dtypes, extra, c[0]);
+        return rc ? rc : plan_call(c[0], false, 0, p);
+    }
+    // conv (Cout = 256, ReLU) followed by a 1x1 head with <= 16 output channels, in one launch where the ping-pong kernel
+    // applies (the 256-channel intermediate then never leaves the CU); otherwise the two convolutions run back to back
+    // through a stream-ordered temporary (or the caller's workspace)
+    int rc1 = MD_OK;
+    if (const int rc = validate_head(nparam, params, ndims, shapes, dtypes, extra, c, rc1)) return rc;
+    bool fuses = true;
+    for (long long n0 = 0; n0 < c[0].a.N && !c[0].empty; n0 += c[0].per)
+        fuses = fuses && conv_head_fuses(conv_slice(c[0], n0, c[0].a.N - n0 < c[0].per ? c[0].a.N - n0 : c[0].per));
+    if (fuses) return plan_call(c[0], true, 0, p);
+    p.two_launch = true;
+    if (const int rc = plan_call(c[0], false, 0, p)) return rc;
+    return rc1 ? rc1 : plan_call(c[1], false, 1, p);
+}
+
+// ---- launch: the template instance of a record
+
+template <int WC, int FC>   // 4 waves, 128 pixels: WC x FC x 32 couts
+static const void *igemm_kernel(const md_conv_launch &r) {
+    constexpr int WP = 4 / WC;
+    if (r.mode != 2) return r.mode ? (const void *)conv_igemm_kernel<256, WC, WP, FC, 2, 1, 1> : (const void *)conv_igemm_kernel<256, WC, WP, FC, 2, 0, 1>;
+    if (r.gen == 0) return (const void *)conv_igemm_kernel<256, WC, WP, FC, 2, 2, 0>;
+    if (r.gen == 2) return (const void *)conv_igemm_kernel<256, WC, WP, FC, 2, 2, 2>;
+    return (const void *)conv_igemm_kernel<256, WC, WP, FC, 2, 2, 1>;
+}
+template <int MF>
+static const void *pingpong_kernel(const md_conv_launch &r) {
+    const bool silu = r.gen == 2;
+    if (r.head) return r.halo ? (const void *)conv_pingpong_kernel<0, MF, 0, true, false, true> : (const void *)conv_pingpong_kernel<0, MF, 0, true>;
+    if (r.halo) return silu ? (const void *)conv_pingpong_kernel<0, MF, 2, false, false, true> : (const void *)conv_pingpong_kernel<0, MF, 0, false, false, true>;
+    if (r.pers) return silu ? (const void *)conv_pingpong_kernel<0, MF, 2, false, true> : (const void *)conv_pingpong_kernel<0, MF, 0, false, true>;
+    return silu ? (const void *)conv_pingpong_kernel<0, MF, 2> : (r.gen == 0 ? (const void *)conv_pingpong_kernel<0, MF, 0> : (const void *)conv_pingpong_kernel<0, MF, 1>);
+}
+template <int K, int CB, int NW = 4>
+static const void *stream_kernel(const md_conv_launch &r) {
+    if (r.res == 2) return (const void *)conv1x1_stream_kernel<K, CB, false, 2, NW>;
+    if (r.res == 1) return r.silu ? (const void *)conv1x1_stream_kernel<K, CB, true, 1, NW> : (const void *)conv1x1_stream_kernel<K, CB, false, 1, NW>;
+    return r.silu ? (const void *)conv1x1_stream_kernel<K, CB, true, 0, NW> : (const void *)conv1x1_stream_kernel<K, CB, false, 0, NW>;
+}
+
+static int conv_launch(md_conv_launch r, const ConvCall &c, hipStream_t s) {
+    ConvArgs a = conv_slice(c, r.n0, r.nn);
+    int xarg[3] = {0, 0, 0};
+    conv_geometry(a, c.tn, r, xarg);   // the kernel arguments the plan derived r from (it has checked the grid)
+    const void *k = (const void *)conv3x3_halo_kernel<128, false>;   // (MD_CONV_FAMILY_HALO with CT 128; the one-halo CT 64 form below)
+    switch (r.family) {
+    case MD_CONV_FAMILY_IGEMM:
+        k = r.dual ? (const void *)conv_igemm_kernel<256, 2, 2, 2, 2, 2, 0, 1>
+                   : (r.ct == 128 ? igemm_kernel<2, 2>(r) : (r.ct == 64 ? igemm_kernel<1, 2>(r) : igemm_kernel<1, 1>(r)));
+        break;
+    case MD_CONV_FAMILY_PINGPONG:
+        if (r.pers && r.halo) k = r.gen == 2 ? (const void *)conv_pingpong_kernel<0, 1, 2, false, true, true> : (const void *)conv_pingpong_kernel<0, 1, 0, false, true, true>;
+#ifdef MD_DIAG
+        else if (r.abl == 1) k = (const void *)conv_pingpong_kernel<1, 0, 1>;
+        else if (r.abl == 2) k = (const void *)conv_pingpong_kernel<2, 0, 1>;
+        else if (r.abl == 4 && r.mf) k = (const void *)conv_pingpong_kernel<4, 1, 1>;
+        else if (r.abl == 4) k = r.gen == 2 ? (const void *)conv_pingpong_kernel<4, 0, 2> : (r.gen == 0 ? (const void *)conv_pingpong_kernel<4, 0, 0> : (const void *)conv_pingpong_kernel<4, 0, 1>);
+#endif
+        else k = r.mf ? pingpong_kernel<1>(r) : pingpong_kernel<0>(r);
+        break;
+    case MD_CONV_FAMILY_STREAM:
+        k = r.k == 128 ? (r.cb == 2 ? stream_kernel<128, 2>(r) : stream_kernel<128, 1>(r))
+                       : r.k == 256 ? (r.cb == 2 ? stream_kernel<256, 2>(r) : stream_kernel<256, 1>(r)) : (r.nw == 8 ? stream_kernel<512, 1, 8>(r) : stream_kernel<512, 1>(r));
+        break;
+    case MD_CONV_FAMILY_HALO:
+        if (r.one_halo) k = (const void *)conv3x3_halo_kernel<64, true>;
+        break;
+    }
+    // the dynamic-LDS attribute only above the 64 KiB a launch gets without it (before, the stream / halo / ping-pong launchers set it for
+    // every launch: each call costs a hipGetDevice and a cache probe on the host)
+    if (r.lds > 64 * 1024 && ensure_dyn_lds(k, r.lds) != MD_OK) return MD_ERR_HIP;
+    g_last_kernel = r.kernel_id;
+    ++g_launch_count;
+    void *args[4] = {&a, &xarg[0], &xarg[1], &xarg[2]};   // conv1x1_stream_kernel takes three ints after ConvArgs, conv3x3_halo_kernel two
+    (void)hipLaunchKernel(k, dim3((unsigned)r.grid), dim3(r.block), args, r.lds, s);
+    return hipGetLastError() == hipSuccess ? MD_OK : MD_ERR_HIP;
+}
+
+static int conv_op(ConvOp op, MD_AOT_ARGS) {
+    ConvCall c[2];
+    md_conv_launch rec[16];
+    ConvPlan p = {rec, 0, 16, 0, false};
+    Scratch tmp;
+    // (a call of more than 16 launches -- image chunks under a lowered chunk_limit -- is planned again for each further 16: the plan keeps
+    // no state and allocates nothing)
+    for (int total = 1; p.first < total; p.first += p.cap) {
+        int rc = conv_op_plan(op, nparam, params, ndims, shapes, dtypes, extra, c, p);
         if (rc != MD_OK) return rc;
+        total = p.n;
+        if (p.two_launch) {   // md_conv2d_head's two launches through a temporary [N,Ho,Wo,256]
+            if (!tmp.ptr && (rc = tmp.acquire((size_t)c[0].a.N * c[0].a.Ho * c[0].a.Wo * 256 * 2, nparam, params, ndims, shapes, 6,
+                                              (hipStream_t)stream)) != MD_OK)
+                return rc;
+            c[0].a.y = (uint16_t *)tmp.ptr; c[1].a.x = (const uint16_t *)tmp.ptr;
+        }
+        for (int i = 0; i < p.cap && p.first + i < total; ++i)
+            if ((rc = conv_launch(rec[i], c[rec[i].sub], (hipStream_t)stream)) != MD_OK) return rc;
     }
     return MD_OK;
 }
+
+void md_note_conv_kernel(int id) { g_last_kernel = id; ++g_launch_count; }
+
+}  // namespace md
+
+using namespace md;
+
+extern "C" int md_conv2d_last_kernel(void) { return g_last_kernel; }
+extern "C" long long md_conv2d_launch_count(void) { return g_launch_count; }
+
+// Required weight padding for a given Cout (the tile the dispatcher will pick): exported so the
+// host packer pads consistently.
+extern "C" int md_conv2d_cout_tile(int cout) { return cout > 64 ? 128 : (cout > 32 ? 64 : 32); }
+
+#ifdef MD_DIAG
+// device buffer (>= 8 * 16 * 8 bytes) that receives the cycle stamps of the variant 19 / 25 launches
+extern "C" int md_diag_set_stamp_buffer(void *p) { g_stamp_buf = (unsigned long long *)p; return MD_OK; }
+#endif
+
+extern "C" int md_conv_plan(const char *op, int nparam, void **params, int *ndims, int64_t **shapes, const char **dtypes, void *extra,
+                            md_conv_launch *out, int cap, int *n) {
+    if (!op || !n || cap < 0 || (cap > 0 && !out)) return MD_ERR_ARG;
+    const ConvOp o = !strcmp(op, "md_conv2d") ? OP_CONV2D : !strcmp(op, "md_conv2d_head") ? OP_HEAD : OP_DUAL;
+    if (o == OP_DUAL && strcmp(op, "md_conv1x1_dual")) return MD_ERR_ARG;
+    ConvCall c[2]; ConvPlan p = {out, 0, cap, 0, false};
+    const int rc = conv_op_plan(o, nparam, params, ndims, shapes, dtypes, extra, c, p);
+    *n = p.n;
+    return rc;
+}
+
+extern "C" int md_conv2d(MD_AOT_ARGS) { return conv_op(OP_CONV2D, nparam, params, ndims, shapes, dtypes, stream, extra); }
+
+// The RPN head of the two-stage detectors: 3x3 conv + ReLU -> [objectness | deltas] (see conv_op_plan).
+extern "C" int md_conv2d_head(MD_AOT_ARGS) { return conv_op(OP_HEAD, nparam, params, ndims, shapes, dtypes, stream, extra); }
+
+// y = act(W . [x_a ; x_b sampled with stride] + bias [+ residual]): ONE 1x1 GEMM over the K-concatenation of two inputs.
+// The use: the first block of a ResNet stage (centernet/src/resnet.py:139-178 with `downsample`, built by _make_layer :214-224):
+// out = relu(bn3(conv3(t2)) + bn_d(conv_d(x))) -- conv3 is 1x1 on the block's own feature map, conv_d a 1x1 conv with the block's stride
+// on its input.  [W3 | Wd] . [t2 ; x_strided] + (b3 + bd) is the same sum in one accumulator: no downsample launch, no Cout-channel
+// residual tensor written and re-read.  (One bf16 rounding instead of the three of the layer-by-layer path.)
+extern "C" int md_conv1x1_dual(MD_AOT_ARGS) { return conv_op(OP_DUAL, nparam, params, ndims, shapes, dtypes, stream, extra); }

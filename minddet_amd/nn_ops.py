@@ -104,7 +104,6 @@ import os as _os
 # A/B knobs (tools): MD_DUAL_PP_MIN_K = concatenated K from which md_conv1x1_dual runs on the ping-pong kernel, MD_PERS_MIN_K = K from
 # which the persistent ping-pong form is the dispatcher's choice.  They travel in every call's attribute struct (md_conv_tune).
 TUNE = ConvTune(dual_pp_min_k=int(_os.environ.get("MD_DUAL_PP_MIN_K", "0")), pers_min_k=int(_os.environ.get("MD_PERS_MIN_K", "0")))
-CONV_VARIANT = int(_os.environ.get("MD_CONV_VARIANT", "0"))  # 0 auto; other values force a kernel variant (A/B measurements, see md_conv2d_attrs; 31 = auto without conv1x1_stream_kernel)
 
 
 def conv2d(x, pc, residual=None, relu=None, out=None, variant=None, c_off=0, res_upsample=False, x_c_off=None, res_c_off=None, tune=None):
@@ -119,7 +118,7 @@ def conv2d(x, pc, residual=None, relu=None, out=None, variant=None, c_off=0, res
     if out is None:
         out = torch.empty((n, ho, wo, pc.cout), dtype=torch.bfloat16, device=x.device)
     attrs = _ConvAttrs(pc.kh, pc.kw, pc.stride, pc.pad, int(pc.relu if relu is None else relu),
-                       int(CONV_VARIANT if variant is None else variant))
+                       int(variant or 0))
     attrs.korder = getattr(pc, "korder", 0)
     attrs.tune = TUNE if tune is None else tune
     attrs.res_upsample = int(bool(res_upsample))
@@ -143,7 +142,7 @@ def conv2d_head(x, pc, pc2, variant=None, tune=None):
         raise _lib.MindDetHipError("conv2d_head: needs a 256-channel conv followed by a 1x1 conv with 16 (padded) output channels")
     ho, wo = conv_out_hw(h, w, pc)
     y2 = torch.empty((n, ho, wo, 16), dtype=torch.bfloat16, device=x.device)
-    attrs = _ConvAttrs(pc.kh, pc.kw, pc.stride, pc.pad, 1, int(CONV_VARIANT if variant is None else variant))
+    attrs = _ConvAttrs(pc.kh, pc.kw, pc.stride, pc.pad, 1, int(variant or 0))
     attrs.korder = getattr(pc, "korder", 0)
     attrs.tune = TUNE if tune is None else tune
     _lib.call("md_conv2d_head", [x, pc.w, pc.bias, pc2.w, pc2.bias, y2], extra=attrs)
@@ -318,7 +317,7 @@ def conv_transpose2d(x, pct, out=None, c_off=0):
     if out is None:
         out = torch.empty((n, h * s, w * s, c_out), dtype=torch.bfloat16, device=x.device)
     for pc, m in pct.subs:
-        attrs = _ConvAttrs(pc.kh, pc.kw, 1, 0, int(pct.relu), int(CONV_VARIANT))
+        attrs = _ConvAttrs(pc.kh, pc.kw, 1, 0, int(pct.relu), 0)
         attrs.adv, attrs.pad_top, attrs.pad_left, attrs.sub_h, attrs.sub_w = 1, m["pad_top"], m["pad_left"], h, w
         attrs.out_stride, attrs.out_off_y, attrs.out_off_x, attrs.c_off, attrs.cout = s, m["py"], m["px"], int(c_off), pc.cout
         attrs.korder = getattr(pc, "korder", 0)

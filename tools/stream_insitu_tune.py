@@ -41,7 +41,7 @@ def run():
     torch.cuda.synchronize()
     return e0.elapsed_time(e1) / STEPS
 
-SETTINGS = [("default r1 w2 t6", (1, 2, 6), None), ("off (v31)", (1, 2, 6), 31), ("r2", (2, 2, 6), None), ("r4", (4, 2, 6), None),
+SETTINGS = [("default r1 w2 t6", (1, 2, 6), None), ("r2", (2, 2, 6), None), ("r4", (4, 2, 6), None),
             ("w3", (1, 3, 6), None), ("w3 r2", (2, 3, 6), None), ("t7 x nt", (1, 2, 7), None), ("t2 st cached", (1, 2, 2), None),
             ("t0 all cached", (1, 2, 0), None), ("t4 res cached", (1, 2, 4), None)]
 for fam in [(128, 512), (256, 1024), (512, 256), (512, 2048)]:

@@ -283,6 +283,31 @@ typedef struct md_c3_pair_attrs {
 } md_c3_pair_attrs;
 int md_c3_pair(MD_AOT_ARGS);
 
+/* A block-diagonal (grouped) conv with many narrow groups in ONE launch.  Replaces the last conv of every SepHead branch of CenterPoint's
+ * CenterHead (centerpoint/det3d_ms/models/bbox_heads/center_head.py:28-99, built per task at :152-166, run by `construct` at :193-200):
+ * 3x3 conv 64 -> c (+ bias; hm bias init -2.19) on the branch's own 64-channel slice of the shared intermediate -- 36 convs with c in
+ * {1, 2, 3} for the nuScenes model.  Group g computes, for every pixel and c < cout[g]:
+ *   y[n, h, w, y_off[g] + c] = act(bias[w_row[g] + c] + sum_{tap, ci} x[n, h + ky - k/2, w + kx - k/2, x_c_off + 64 g + ci] * w[w_row[g] + c, tap * 64 + ci])
+ * (stride 1, zero padding k / 2, bf16 operands, fp32 accumulation, one rounding to bf16).
+ * in : x[N,H,W,C] bf16 (C % 8 == 0), w[R, k*k*64] bf16 (K order (tap, ci); BN and a conv bias in front of it folded exactly as
+ *      md_conv2d's packer folds them; group g's rows are [w_row[g], w_row[g] + cout[g])), bias[R] f32
+ * out: y[N,H,W,Cy] bf16 (Cy % 8 == 0).  Output channels that no group covers are LEFT UNTOUCHED (the call writes only
+ *      [y_off[g], y_off[g] + cout[g]) of each group).  y must not overlap x; two groups must not share an output channel.
+ * extra: md_conv2d_grouped_attrs (required).  Every argument is checked before any device call (MD_ERR_ARG). */
+#define MD_GROUPED_MAX_GROUPS 64
+typedef struct md_conv2d_grouped_attrs {
+    int32_t k;          /* 1 or 3 (square kernel, stride 1, pad k / 2) */
+    int32_t relu;       /* 0 none, 1 ReLU after the bias (as md_conv2d_attrs.relu; SiLU is not offered) */
+    int32_t groups;     /* G, 1 .. MD_GROUPED_MAX_GROUPS */
+    int32_t cin_g;      /* input channels per group: must be 64 */
+    int32_t x_c_off;    /* group g reads channels [x_c_off + 64 g, + 64) of x (multiple of 8; x_c_off + 64 G <= C) */
+    int32_t reserved0;  /* must be 0 */
+    int32_t cout[MD_GROUPED_MAX_GROUPS];   /* output channels of group g: 1 .. 16 */
+    int32_t y_off[MD_GROUPED_MAX_GROUPS];  /* first output channel of group g in y (any value; y_off + cout <= Cy) */
+    int32_t w_row[MD_GROUPED_MAX_GROUPS];  /* first row of group g in w and bias (w_row + cout <= R) */
+} md_conv2d_grouped_attrs;
+int md_conv2d_grouped(MD_AOT_ARGS);
+
 /* Which kernel the dispatcher launched for the calling host thread's most recent md_conv2d (0 before any call, or when
  * the call returned without launching).  Diagnostic only: lets bench.py attribute per-launch HIP-event timings. */
 enum {
@@ -295,11 +320,12 @@ enum {
     MD_CONV_KERNEL_OTHER = 6,           /* A/B variants */
     MD_CONV_KERNEL_BOTTLENECK = 7,      /* bottleneck64_kernel (md_bottleneck) */
     MD_CONV_KERNEL_STREAM_1X1 = 8,      /* conv1x1_stream_kernel: weight-stationary pointwise layers, K <= 512 */
-    MD_CONV_KERNEL_C3_PAIR = 9          /* c3pair_kernel (md_c3_pair) */
+    MD_CONV_KERNEL_C3_PAIR = 9,         /* c3pair_kernel (md_c3_pair) */
+    MD_CONV_KERNEL_GROUPED = 10         /* grouped_conv_kernel (md_conv2d_grouped) */
 };
 int md_conv2d_last_kernel(void);
 /* Running count of the kernels the calling host thread's conv-family calls (md_conv2d, md_conv2d_head, md_conv1x1_dual,
- * md_bottleneck) have launched: a call on a batch past the chunk limit launches once per image chunk.  Diagnostic only:
+ * md_bottleneck, md_c3_pair, md_conv2d_grouped) have launched: a call on a batch past the chunk limit launches once per image chunk.  Diagnostic only:
  * bench.py divides a call's algorithmic work and bracketed time by its launches. */
 long long md_conv2d_launch_count(void);
 

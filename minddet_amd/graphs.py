@@ -830,6 +830,171 @@ class RPN:
         return out
 
 
+# ----------------------------------------------------------------------------- CenterPoint head + detector
+SEPHEAD_GROUPED = os.environ.get("MD_SEPHEAD_GROUPED", "1") != "0"   # A/B knob: 0 = 36 md_conv2d launches for the SepHead final convs
+SEPHEAD_ORDER = ("reg", "height", "dim", "rot", "vel", "hm")         # the dict order of SepHead.construct (center_head.py:85-93)
+
+
+@HEADS.register_module
+class CenterHead:
+    """centerpoint/det3d_ms/models/bbox_heads/center_head.py:103-200: shared 3x3 conv (in_channels -> share_conv_channel, bias, BN,
+    ReLU), then per task a SepHead (:28-99) with one branch per head of common_heads + hm: 3x3 conv 64 -> 64 + bias + BN(eps 1e-5) +
+    ReLU, 3x3 conv 64 -> c + bias (hm bias init_bias).  The per-branch ConvModules (self.tasks[t][head] = (c1, c2)) are the source of
+    truth; fuse() rebuilds the fast form from them, three launches: the shared conv, ONE md_conv2d 64 -> 36 x 64 for every branch's
+    first conv, ONE md_conv2d_grouped for every branch's last conv into one head tensor [B, H, W, roundup(sum c, 8)] that holds task
+    t's heads in SEPHEAD_ORDER from channel task_base[t] (channels past sum c are not written).  MD_SEPHEAD_GROUPED=0 runs the last
+    convs as one md_conv2d per branch instead, into [B, H, W, 8 x branches] with branch i at channel 8 i (A/B)."""
+
+    def __init__(self, in_channels=384, tasks=(), common_heads=None, share_conv_channel=64, num_hm_conv=2, init_bias=-2.19, seed=7,
+                 dataset="nuscenes", weight=0.25, code_weights=None, logger=None, dcn_head=False):
+        if dcn_head:
+            raise ValueError("CenterHead: dcn_head is not supported")
+        if share_conv_channel != 64 or num_hm_conv != 2:
+            raise ValueError("CenterHead: the fast form needs share_conv_channel=64 and two convs per SepHead branch (num_hm_conv=2)")
+        common_heads = dict(common_heads or {})
+        init = ParamInit(seed)
+        self.in_channels, self.share = int(in_channels), int(share_conv_channel)
+        self.num_classes = [int(t.get("num_class", len(t["class_names"]))) for t in tasks]
+        self.class_names = [list(t["class_names"]) for t in tasks]
+        self.shared_conv = ConvModule(init, self.in_channels, self.share, 3, 1, 1, bn=True, relu=True, bias=True)
+        self.tasks = []
+        for nc in self.num_classes:
+            heads = dict(common_heads)
+            heads["hm"] = (nc, num_hm_conv)
+            order = [h for h in SEPHEAD_ORDER if h in heads] + [h for h in heads if h not in SEPHEAD_ORDER]
+            sep = {}
+            for h in order:
+                c = int(heads[h][0])
+                if int(heads[h][1]) != 2:
+                    raise ValueError(f"CenterHead: head {h!r} has {heads[h][1]} convs; the fast form needs 2")
+                c1 = ConvModule(init, self.share, self.share, 3, 1, 1, bn=True, relu=True, bias=True)
+                c2 = ConvModule(init, self.share, c, 3, 1, 1, bn=False, relu=False, bias=True,
+                                bias_value=init_bias if h == "hm" else None)
+                sep[h] = (c1, c2)
+            self.tasks.append(sep)
+        # channel layout of the head tensor: task t's heads side by side from task_base[t]
+        self.offsets, base = [], 0
+        for sep in self.tasks:
+            off = {}
+            for h, (_, c2) in sep.items():
+                off[h] = base
+                base += c2.cout
+            self.offsets.append(off)
+        self.head_channels = base
+        self.task_base = [min(o.values()) for o in self.offsets]
+        self._dev = None
+
+    def branches(self):
+        return [(t, h, c1, c2) for t, sep in enumerate(self.tasks) for h, (c1, c2) in sep.items()]
+
+    def conv_modules(self):
+        return [self.shared_conv] + [m for _, _, c1, c2 in self.branches() for m in (c1, c2)]
+
+    def fuse(self):
+        """(Re)build the fast form from the per-branch ConvModules on the head's device (call after the weights change; .to() calls it)."""
+        if self._dev is None:
+            return self
+        br = self.branches()
+        self._first = merged_conv([c1 for _, _, c1, _ in br], self._dev)
+        self._second = nn_ops.pack_conv2d_grouped([(c2.weight, c2.bias, None) for _, _, _, c2 in br],
+                                                  y_offs=[self.offsets[t][h] for t, h, _, _ in br]).to(self._dev)
+        for _, _, _, c2 in br:           # the per-branch last convs packed alone: the A/B path
+            c2.to(self._dev)
+        return self
+
+    def to(self, device):
+        self._dev = device
+        self.shared_conv.to(device)
+        return self.fuse()
+
+    def task_offsets(self, grouped=None):
+        """per task {head: first channel} in the head tensor __call__ returns (grouped None: the SEPHEAD_GROUPED setting)"""
+        if grouped if grouped is not None else SEPHEAD_GROUPED:
+            return [dict(o) for o in self.offsets]
+        out, i = [], 0
+        for sep in self.tasks:
+            out.append({h: 8 * (i + j) for j, h in enumerate(sep)})
+            i += len(sep)
+        return out
+
+    def __call__(self, x, grouped=None):
+        """x [B, H, W, in_channels] bf16 -> (head, shared): the head tensor (layout: task_offsets()) and the shared conv's output
+        [B, H, W, 64] (construct's (ret_dicts, x), center_head.py:193-200)."""
+        sh = self.shared_conv(x)
+        mid = nn_ops.conv2d(sh, self._first)                                    # [B, H, W, 64 x branches]
+        B, H, W, _ = sh.shape
+        if grouped if grouped is not None else SEPHEAD_GROUPED:
+            head = torch.empty((B, H, W, (self.head_channels + 7) // 8 * 8), dtype=torch.bfloat16, device=x.device)
+            nn_ops.conv2d_grouped(mid, self._second, head)
+        else:
+            br = self.branches()
+            head = torch.empty((B, H, W, 8 * len(br)), dtype=torch.bfloat16, device=x.device)
+            for i, (_, _, _, c2) in enumerate(br):
+                nn_ops.conv2d(mid, c2.packed, out=head, c_off=8 * i, x_c_off=64 * i)
+        return head, sh
+
+
+@DETECTORS.register_module
+class PointPillars:
+    """det3d's PointPillars detector with a CenterHead (centerpoint/det3d_ms/models/detectors/point_pillars.py; the nuScenes
+    CenterPoint-PP config): neck (graphs.RPN) -> bbox_head (CenterHead) -> one CenterHeadPost per task -> the task merge of
+    tools_ms/eval.py:84-111.  The pillar encoder (reader) and the scatter (backbone) are out of scope: forward() takes the scattered
+    pseudo-image [B, H, W, 64] bf16."""
+
+    def __init__(self, neck, bbox_head, reader=None, backbone=None, train_cfg=None, test_cfg=None, pretrained=None, seed=7):
+        if reader is not None or backbone is not None:
+            raise ValueError("PointPillars: the pillar encoder (`reader`) and the scatter (`backbone`) are not part of this build; "
+                             "drop them from the config and feed the scattered pseudo-image [B, H, W, 64] bf16 to forward()")
+        _split_forward_of(self, test_cfg)
+        self.neck = build_neck(dict(neck, seed=seed) if isinstance(neck, dict) and "seed" not in neck else neck)
+        self.bbox_head = build_head(dict(bbox_head, seed=seed + 1) if isinstance(bbox_head, dict) and "seed" not in bbox_head else bbox_head)
+        self.test_cfg = test_cfg
+        self.max_per_task = int(test_cfg["nms"]["nms_post_max_size"])
+
+    def to(self, device):
+        self.neck.to(device)
+        self.bbox_head.to(device)
+        _packs_rebuilt(self)
+        return self
+
+    def forward(self, pseudo_image, return_aux=False):
+        """pseudo_image [B, H, W, 64] bf16 -> (dets [B, tasks x nms_post_max_size, 11] f32, count [B] i32): per row the 9 box values
+        (x, y, z, dx, dy, dz, vx, vy, rot), score, label over all tasks; rows past count are zero."""
+        feat = self.neck(pseudo_image)
+        head, shared = self.bbox_head(feat)
+        posts = [det_ops.CenterHeadPost(off, nc, self.test_cfg)
+                 for off, nc in zip(self.bbox_head.task_offsets(), self.bbox_head.num_classes)]
+        outs = [post(head) for post in posts]
+        dets, count = merge_center_tasks(outs, self.bbox_head.num_classes, self.max_per_task)
+        if return_aux:
+            return (dets, count), dict(neck=feat, head=head, shared=shared, tasks=outs)
+        return dets, count
+
+    __call__ = forward
+
+
+def merge_center_tasks(outs, num_classes, max_per_task):
+    """The task merge of tools_ms/eval.py:84-111 on the device: per sample and task the first size rows, size = the rows among the first
+    count whose score is > 0; tasks concatenated in order, each label shifted by the summed num_class of the earlier tasks.
+    outs: per task (boxes [B, k, 9], scores [B, k], labels [B, k], count [B]) -> (dets [B, T x max_per_task, 11] f32, count [B] i32)."""
+    B, dev, m = outs[0][1].shape[0], outs[0][1].device, int(max_per_task)
+    T = len(outs)
+    rows = torch.zeros((B, T * m + 1, 11), dtype=torch.float32, device=dev)      # the last row takes the rows that are dropped
+    j = torch.arange(m, device=dev).view(1, m)
+    base = torch.zeros((B, 1), dtype=torch.int64, device=dev)
+    flag = 0
+    for (boxes, scores, labels, count), nc in zip(outs, num_classes):
+        sc = scores[:, :m]
+        size = ((j < count.view(B, 1).long()) & (sc > 0)).sum(1, keepdim=True)
+        r = torch.cat([boxes[:, :m], sc.unsqueeze(2), (labels[:, :m] + flag).to(torch.float32).unsqueeze(2)], 2)
+        dst = torch.where(j < size, base + j, torch.full_like(j, T * m))
+        rows.scatter_(1, dst.unsqueeze(2).expand(B, m, 11), r)
+        base = base + size
+        flag += int(nc)
+    rows[:, T * m] = 0
+    return rows[:, :T * m].contiguous(), base.view(B).to(torch.int32)
+
+
 # ----------------------------------------------------------------------------- YOLOv5 (build-authored; parity unpinned)
 SPPF_FUSED = os.environ.get("MD_SPPF_FUSED", "1") != "0"    # A/B knob: 0 = three md_maxpool2d launches + four concat copies per SPPF block
 C3_PAIR_FUSED = os.environ.get("MD_C3_PAIR", "1") != "0"   # A/B knob (tools/ab_env_bench.sh): 0 = two md_conv2d launches per C3 bottleneck

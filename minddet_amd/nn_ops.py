@@ -547,3 +547,66 @@ def image_preprocess(img_u8, mat, mean, std, out_hw, stem_layout=True):
     norm = torch.tensor(list(mean) + list(std), dtype=torch.float32, device=img_u8.device)
     _lib.call("md_image_preprocess", [img_u8, mat, norm, out], extra=_PreAttrs(ho, wo, lo, hi))
     return out
+
+
+# ----------------------------------------------------------------------------- grouped conv (csrc/grouped.hip)
+GROUPED_MAX_GROUPS = 64
+
+
+class _GroupedAttrs(ctypes.Structure):
+    _fields_ = [("k", ctypes.c_int32), ("relu", ctypes.c_int32), ("groups", ctypes.c_int32), ("cin_g", ctypes.c_int32),
+                ("x_c_off", ctypes.c_int32), ("reserved0", ctypes.c_int32), ("cout", ctypes.c_int32 * GROUPED_MAX_GROUPS),
+                ("y_off", ctypes.c_int32 * GROUPED_MAX_GROUPS), ("w_row", ctypes.c_int32 * GROUPED_MAX_GROUPS)]
+
+
+class PackedGrouped:
+    """The folded weights of G narrow convs on consecutive 64-channel input slices as md_conv2d_grouped consumes them: one [R, k*k*64]
+    bf16 buffer (group g's rows from w_row[g], K order (tap, ci)), bias [R] f32, and each group's output channel offset."""
+
+    def __init__(self, w, bias, k, couts, w_rows, y_offs, relu):
+        self.w, self.bias, self.k, self.relu = w, bias, k, relu
+        self.couts, self.w_rows, self.y_offs = list(couts), list(w_rows), list(y_offs)
+        self.groups, self.cin_g = len(self.couts), 64
+
+    def to(self, device):
+        self.w, self.bias = self.w.to(device), self.bias.to(device)
+        return self
+
+    def flops(self, n, h, w):
+        """2 N H W sum_g cout_g cin_g k^2 (the useful work; the kernel pads each group's couts to a 16-row MFMA tile)"""
+        return 2 * n * h * w * sum(self.couts) * self.cin_g * self.k * self.k
+
+    def attrs(self, x_c_off=0):
+        at = _GroupedAttrs(self.k, int(self.relu), self.groups, self.cin_g, int(x_c_off), 0)
+        for g in range(self.groups):
+            at.cout[g], at.y_off[g], at.w_row[g] = self.couts[g], self.y_offs[g], self.w_rows[g]
+        return at
+
+
+def pack_conv2d_grouped(convs, y_offs=None, relu=False):
+    """convs: one (weight [c, 64, k, k], bias [c] or None, bn (gamma, beta, mean, var, eps) or None) per group, in input-slice order;
+    every group has the same k (1 or 3) and 1 <= c <= 16.  BN and a conv bias in front of it are folded as pack_conv folds them.
+    y_offs: each group's first output channel (default: the groups' outputs side by side from channel 0)."""
+    if not 1 <= len(convs) <= GROUPED_MAX_GROUPS:
+        raise _lib.MindDetHipError(f"pack_conv2d_grouped: 1..{GROUPED_MAX_GROUPS} groups, got {len(convs)}")
+    k = convs[0][0].shape[2]
+    ws, bs, couts = [], [], []
+    for weight, bias, bn in convs:
+        c, cin, kh, kw = weight.shape
+        if cin != 64 or kh != k or kw != k or k not in (1, 3) or not 1 <= c <= 16:
+            raise _lib.MindDetHipError(f"pack_conv2d_grouped: every group is a [1..16, 64, k, k] conv with one k in (1, 3), got {tuple(weight.shape)}")
+        pc = pack_conv(weight, bias=bias, bn=bn, pad=k // 2, korder=0)   # the folding and the (tap, ci) K order of md_conv2d
+        ws.append(pc.w[:c, :k * k * 64])
+        bs.append(pc.bias[:c])
+        couts.append(c)
+    w_rows = [sum(couts[:g]) for g in range(len(couts))]
+    if y_offs is None:
+        y_offs = w_rows
+    return PackedGrouped(torch.cat(ws).contiguous(), torch.cat(bs).contiguous(), k, couts, w_rows, y_offs, int(bool(relu)))
+
+
+def conv2d_grouped(x, pk, out, x_c_off=0):
+    """Group g reads channels [x_c_off + 64 g, + 64) of x [N,H,W,C] and writes its pk.couts[g] channels at pk.y_offs[g] of out
+    [N,H,W,Cy] (one md_conv2d_grouped launch; channels no group covers are left as they are)."""
+    _lib.call("md_conv2d_grouped", [x, pk.w, pk.bias, out], extra=pk.attrs(x_c_off))
+    return out

@@ -358,3 +358,59 @@ def load_rpn(model, params, prefix="neck.", naming="auto", strict=True):
         if all(v is not None for v in vals):
             m.bn = (vals[0], vals[1], vals[2], vals[3], m.bn[4])
     return sorted(k for k in params if k not in used)
+
+
+def _center_head_slots(head, prefix):
+    """(module, key prefix of its conv, key prefix of its BN or None) for every conv of graphs.CenterHead under the reference's cell
+    names (center_head.py:131-141: shared_conv = SequentialCell[Conv, BN, ReLU] -> 0, 1; :28-77: SepHead branch `head` of task t =
+    SequentialCell[Conv, BN, ReLU, Conv] -> tasks.t.head.0, .1, .3)."""
+    slots = [(head.shared_conv, f"{prefix}shared_conv.0", f"{prefix}shared_conv.1")]
+    for t, h, c1, c2 in head.branches():
+        slots.append((c1, f"{prefix}tasks.{t}.{h}.0", f"{prefix}tasks.{t}.{h}.1"))
+        slots.append((c2, f"{prefix}tasks.{t}.{h}.3", None))
+    return slots
+
+
+def center_head_state(head, prefix="bbox_head.", naming="ms"):
+    """graphs.CenterHead parameters under the reference's names (MindSpore, or the det3d torch original with naming='torch')."""
+    bn_names = ("gamma", "beta", "moving_mean", "moving_variance") if naming == "ms" else ("weight", "bias", "running_mean", "running_var")
+    out = {}
+    for m, conv, bn in _center_head_slots(head, prefix):
+        out[conv + ".weight"], out[conv + ".bias"] = m.weight, m.bias
+        if bn is not None:
+            for n, v in zip(bn_names, m.bn[:4]):
+                out[f"{bn}.{n}"] = v
+    return {k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)) for k, v in out.items()}
+
+
+def load_center_head(head, params, prefix="bbox_head.", naming="auto", strict=True):
+    """Write a CenterPoint checkpoint's bbox_head into a graphs.CenterHead; returns the unused keys.  naming 'torch' goes through
+    `torch_to_ms_generic` first; call head.to(device) (or the detector's .to) afterwards to fold, fuse and pack."""
+    if naming == "auto":
+        naming = "torch" if any(k.endswith("running_var") for k in params) else "ms"
+    if naming == "torch":
+        kmap = torch_to_ms_generic(params.keys())
+        params = {kmap[k]: v for k, v in params.items() if k in kmap}
+    used = set()
+
+    def get(key, like):
+        if key not in params:
+            if strict:
+                raise KeyError(f"checkpoint has no {key!r}")
+            return None
+        a = np.asarray(params[key])
+        if tuple(a.shape) != tuple(like.shape):
+            raise ValueError(f"{key}: checkpoint shape {tuple(a.shape)} != model shape {tuple(like.shape)}")
+        used.add(key)
+        return torch.from_numpy(a.astype(np.float32))
+
+    for m, conv, bn in _center_head_slots(head, prefix):
+        for attr in ("weight", "bias"):
+            v = get(f"{conv}.{attr}", getattr(m, attr))
+            if v is not None:
+                setattr(m, attr, v)
+        if bn is not None:
+            vals = [get(f"{bn}.{n}", m.bn[i]) for i, n in enumerate(("gamma", "beta", "moving_mean", "moving_variance"))]
+            if all(v is not None for v in vals):
+                m.bn = (vals[0], vals[1], vals[2], vals[3], m.bn[4])
+    return sorted(k for k in params if k not in used)

@@ -532,13 +532,20 @@ int md_delta2bbox(MD_AOT_ARGS);
 typedef struct md_topk_attrs {
     int32_t k;        /* <= 4096 */
     float min_score;  /* only scores > min_score are selectable; -FLT_MAX to disable */
-    int32_t max_segment; /* upper bound of the segment lengths if the caller knows it (seg_off lives on the
-                            device); > 32768 switches to the multi-workgroup select. 0 = unknown */
+    int32_t max_segment; /* the longest segment if the caller knows it (seg_off lives on the device); picks the
+                            form: > 32768 (and L <= 65535) the multi-workgroup select, 1..30000 the LDS-staged one,
+                            else (0 = unknown) one workgroup per segment.  A hint, not a promise: a segment longer
+                            than max_segment is still selected exactly, by the slower global-memory passes */
 } md_topk_attrs;
 /* in scores[T] f32, seg_off[L+1] i32 ; out values[L,k] f32 (padded -FLT_MAX), indices[L,k] i32
  * (relative to the segment, padded 0), count[L] i32 ; optional workspace
- * (L*(2048*4+4) rounded up to 256, + L*8192*8 bytes) for the multi-workgroup path. */
+ * (L*(2048*4+4) rounded up to 256, + L*8192*8 bytes) for the multi-workgroup path.
+ * Order: descending, ties to the lower index; -0.0 and +0.0 are one value (a -0.0 is returned as +0.0).
+ * NaN scores have no specified order. */
 int md_topk_segmented(MD_AOT_ARGS);
+/* Diagnostic: the form the calling thread's last md_topk_segmented call launched -- 0 none (an error or L == 0),
+ * 1 one workgroup per segment, 2 LDS-staged, 3 multi-workgroup. */
+int md_topk_last_path(void);
 
 /* ------------------------------------------------------------------------------------------
  * RoIAlign over an FPN pyramid (absent from the reference, SURVEY a12: torchvision semantics)

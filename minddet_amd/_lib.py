@@ -57,6 +57,7 @@ def exported_symbols():
     txt = open(hdr).read()
     names = re.findall(r"^\s*int\s+(\w+)\s*\(MD_AOT_ARGS\)\s*;", txt, flags=re.M)
     names += re.findall(r"^\s*const char \*(\w+)\s*\(void\)\s*;", txt, flags=re.M)
+    names += re.findall(r"^\s*int\s+(\w+)\s*\(void\)\s*;", txt, flags=re.M)
     return names
 
 

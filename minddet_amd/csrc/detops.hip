@@ -204,9 +204,11 @@ __global__ void delta2bbox_kernel(const float *__restrict__ rois, const float *_
 }
 
 // ------------------------------------------------------------------------------------------ segmented top-k
-// order-preserving map float -> uint (ascending)
+// order-preserving map float -> uint (ascending).  -0.0 is folded onto +0.0 first: the two are IEEE-equal, so they must share a key (a tie
+// then goes to the lower index, and -0.0 is not > a min_score of +0.0 nor +0.0 > a min_score of -0.0); funord() returns +0.0 for both
 __device__ __forceinline__ unsigned ford(float f) {
-    const unsigned u = __float_as_uint(f);
+    unsigned u = __float_as_uint(f);
+    u = u == 0x80000000u ? 0u : u;
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 __device__ __forceinline__ float funord(unsigned o) {
@@ -601,7 +603,8 @@ __global__ __launch_bounds__(TOPK_THREADS) void topk_segmented_lds_kernel(const 
 //    candidates (bin >= b1) as 64-bit keys (~ordinal << 32 | index) to the segment's candidate list.
 // D: one workgroup per segment sorts the (few thousand) candidates in LDS: ascending key order ==
 //    descending score, ascending index -> exact stable top-k.  If the candidate list overflowed (extreme
-//    ties) the segment falls back to the single-workgroup select above.
+//    ties), or the segment is longer than the max_segment that sized the chunk grid of A and C (its tail was
+//    never histogrammed nor compacted), the segment falls back to the single-workgroup select above.
 constexpr int TK_BINS = 2048;
 constexpr int TK_CHUNK = 8192;
 constexpr int TK_CAP = 8192;
@@ -712,11 +715,11 @@ __global__ __launch_bounds__(TOPK_THREADS) void topk_final_kernel(const float *_
                                                                   const unsigned *__restrict__ cand_cnt,
                                                                   const unsigned long long *__restrict__ cand,
                                                                   float *__restrict__ out_val, int *__restrict__ out_idx,
-                                                                  int *__restrict__ out_cnt) {
+                                                                  int *__restrict__ out_cnt, int max_segment) {
     __shared__ unsigned long long keys[TK_CAP];
     const int seg = blockIdx.x, tid = threadIdx.x;
     const unsigned nc = cand_cnt[seg];
-    if (nc > (unsigned)TK_CAP) {  // block-uniform
+    if (nc > (unsigned)TK_CAP || seg_off[seg + 1] - seg_off[seg] > max_segment) {  // block-uniform
         topk_block_select(scores, seg_off, seg, k, min_score, out_val, out_idx, out_cnt, keys);
         return;
     }
@@ -1432,8 +1435,14 @@ extern "C" int md_delta2bbox(MD_AOT_ARGS) {
     return MD_OK;
 }
 
+// which form the calling host thread's last md_topk_segmented call launched (md_topk_last_path): 0 none, 1 single workgroup,
+// 2 LDS-staged, 3 multi-workgroup.  Lets a test assert the path it meant to reach.
+static thread_local int g_topk_last_path = 0;
+extern "C" int md_topk_last_path(void) { return g_topk_last_path; }
+
 extern "C" int md_topk_segmented(MD_AOT_ARGS) {
     // in: scores[T] f32, seg_off[L+1] i32 ; out: values[L,k] f32, indices[L,k] i32, count[L] i32
+    g_topk_last_path = 0;
     if (nparam != 5 && nparam != 6) return MD_ERR_NPARAM;
     if (!params || !extra) return MD_ERR_ARG;
     if (!dtype_is(dtypes, 0, "float32") || !dtype_is(dtypes, 1, "int32") || !dtype_is(dtypes, 2, "float32") ||
@@ -1464,17 +1473,20 @@ extern "C" int md_topk_segmented(MD_AOT_ARGS) {
                            (const int *)params[1], at->k, at->min_score, ghist, cand_cnt, cand);
         hipLaunchKernelGGL(topk_final_kernel, dim3((unsigned)L), dim3(TOPK_THREADS), 0, s, (const float *)params[0],
                            (const int *)params[1], at->k, at->min_score, cand_cnt, cand, (float *)params[2],
-                           (int *)params[3], (int *)params[4]);
+                           (int *)params[3], (int *)params[4], at->max_segment);
+        g_topk_last_path = 3;
     } else if (at->max_segment > 0 && at->max_segment <= TOPK_LDS_MAX_N) {
         const int cap = at->max_segment;
         const int lds = (int)align_up((size_t)cap * 4, 16);
         if (ensure_dyn_lds((const void *)topk_segmented_lds_kernel, lds) != MD_OK) return MD_ERR_HIP;
         hipLaunchKernelGGL(topk_segmented_lds_kernel, dim3((unsigned)L), dim3(TOPK_THREADS), lds, s, (const float *)params[0],
                            (const int *)params[1], at->k, at->min_score, (float *)params[2], (int *)params[3], (int *)params[4], cap);
+        g_topk_last_path = 2;
     } else {
         hipLaunchKernelGGL(topk_segmented_kernel, dim3((unsigned)L), dim3(TOPK_THREADS), 0, s, (const float *)params[0],
                            (const int *)params[1], at->k, at->min_score, (float *)params[2], (int *)params[3],
                            (int *)params[4]);
+        g_topk_last_path = 1;
     }
     MD_HIP_TRY(hipGetLastError());
     return MD_OK;

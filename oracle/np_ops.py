@@ -510,12 +510,18 @@ def fpn_level_log2(rois, k_min=2, k_max=5, canonical=224.0, canonical_level=4):
     return np.clip(lvl, k_min, k_max).astype(np.int32)
 
 
-def roi_align_fast(feat, rois, out_size, spatial_scale, sampling_ratio=2, aligned=True, chunk=64):
+def roi_align_fast(feat, rois, out_size, spatial_scale, sampling_ratio=2, aligned=True, chunk=64, acc_dtype=np.float32,
+                   return_tap_max=False):
     """Vectorised twin of roi_align (same float32 arithmetic per element, different summation grouping
-    is avoided: taps are accumulated in the same (iy, ix) order)."""
+    is avoided: taps are accumulated in the same (iy, ix) order).
+    acc_dtype=np.float64: the high-precision reference.  Sample coordinates, the floor / clamp / out-of-range decisions and the
+    four bilinear weights stay in fp32, exactly as the kernels compute them; only the weighted taps are summed (and divided by
+    g*g) in float64.  return_tap_max: also return M [R,C,P,P], the largest |feature| among the taps of each bin's in-range
+    samples (0 where no sample is in range), the scale of a bin's accumulation error."""
     C, H, W = feat.shape
     R, P, g = rois.shape[0], out_size, sampling_ratio
-    out = np.zeros((R, C, P, P), np.float32)
+    out = np.zeros((R, C, P, P), acc_dtype)
+    tmax = np.zeros((R, C, P, P), np.float32) if return_tap_max else None
     off = np.float32(0.5 if aligned else 0.0)
     f = np.ascontiguousarray(feat.transpose(1, 2, 0))  # [H,W,C]
     for r0 in range(0, R, chunk):
@@ -530,7 +536,8 @@ def roi_align_fast(feat, rois, out_size, spatial_scale, sampling_ratio=2, aligne
             rw, rh = np.maximum(rw, np.float32(1)), np.maximum(rh, np.float32(1))
         bw, bh = rw / np.float32(P), rh / np.float32(P)
         pidx = np.arange(P, dtype=np.float32)
-        acc = np.zeros((n, P, P, C), np.float32)
+        acc = np.zeros((n, P, P, C), acc_dtype)
+        mx = np.zeros((n, P, P, C), np.float32)
         for iy in range(g):
             y = y1[:, None] + pidx[None, :] * bh[:, None] + (np.float32(iy) + np.float32(0.5)) * bh[:, None] / np.float32(g)
             for ix in range(g):
@@ -547,11 +554,20 @@ def roi_align_fast(feat, rois, out_size, spatial_scale, sampling_ratio=2, aligne
                 xx = np.where(xcl, x_lo.astype(np.float32), xx)
                 ly, lx = yy - y_lo.astype(np.float32), xx - x_lo.astype(np.float32)
                 hy, hx = np.float32(1) - ly, np.float32(1) - lx
-                v = ((hy * hx)[..., None] * f[y_lo, x_lo] + (hy * lx)[..., None] * f[y_lo, x_hi] +
-                     (ly * hx)[..., None] * f[y_hi, x_lo] + (ly * lx)[..., None] * f[y_hi, x_hi])
-                acc += np.where(oob[..., None], np.float32(0), v)
-        out[r0:r0 + n] = (acc / np.float32(g * g)).transpose(0, 3, 1, 2)
-    return out
+                taps = (f[y_lo, x_lo], f[y_lo, x_hi], f[y_hi, x_lo], f[y_hi, x_hi])
+                wts = ((hy * hx)[..., None], (hy * lx)[..., None], (ly * hx)[..., None], (ly * lx)[..., None])
+                if acc_dtype == np.float32:
+                    v = wts[0] * taps[0] + wts[1] * taps[1] + wts[2] * taps[2] + wts[3] * taps[3]
+                else:
+                    v = sum(w.astype(acc_dtype) * t.astype(acc_dtype) for w, t in zip(wts, taps))
+                acc += np.where(oob[..., None], 0, v).astype(acc_dtype)
+                if return_tap_max:
+                    m = np.maximum(np.maximum(np.abs(taps[0]), np.abs(taps[1])), np.maximum(np.abs(taps[2]), np.abs(taps[3])))
+                    mx = np.maximum(mx, np.where(oob[..., None], np.float32(0), m))
+        out[r0:r0 + n] = (acc / acc_dtype(g * g)).transpose(0, 3, 1, 2)
+        if return_tap_max:
+            tmax[r0:r0 + n] = mx.transpose(0, 3, 1, 2)
+    return (out, tmax) if return_tap_max else out
 
 
 # ----------------------------------------------------------------------------- CenterPoint head

@@ -24,6 +24,15 @@ def test_library_exports_every_declared_symbol():
     assert b"gfx950" in lib.md_version()
 
 
+def test_topk_last_path_is_exported_and_reset_by_a_call():
+    """md_topk_last_path (the top-k form the calling thread's last md_topk_segmented call launched; test_topk_gpu.py asserts it) is
+    declared and exported, and a call that launches nothing -- a wrong parameter count, checked before any device work -- reports 0"""
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    assert "md_topk_last_path" in _lib.exported_symbols()
+    assert lib.md_topk_segmented(1, None, None, None, None, None, None) == 1
+    assert lib.md_topk_last_path() == 0
+
+
 def test_reference_symbol_names_are_kept():
     # the names the reference's ops.Custom strings bind (iou_gpu.py:18,33,53,72)
     for n in ["BoxesIouBevGpu", "BoxesOverlapBevGpu", "NmsGpu", "NmsNormalGpu"]:

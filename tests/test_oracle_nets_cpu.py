@@ -36,6 +36,29 @@ def test_roi_align_fast_equals_loop():
     assert (z == 0).all()
 
 
+def test_roi_align_float64_reference_equals_loop():
+    """The float64-accumulating reference (acc_dtype=np.float64: fp32 coordinates / decisions / weights, float64 sums) agrees with the
+    fp32 loop form to fp32 summation error, over sampling 1-3, both `aligned` settings and RoIs inside, across and outside the map,
+    sub-pixel, zero-size and inverted; its tap maximum bounds every output"""
+    rng = np.random.default_rng(1)
+    feat = rng.normal(0, 1, (5, 12, 17)).astype(np.float32)
+    rois = np.array([[2, 3, 50, 40], [-10, -10, 20, 20], [60, 40, 90, 70], [0, 0, 67, 47], [5, 5, 5.5, 5.5], [-30, 8, -6, 30],
+                     [20, 20, 20, 20], [30, 30, 22, 25], [1.25, 2.5, 4.75, 3.0]], np.float32)
+    for g in (1, 2, 3):
+        for aligned in (True, False):
+            a = np_ops.roi_align(feat, rois, 7, 0.25, g, aligned)
+            b, m = np_ops.roi_align_fast(feat, rois, 7, 0.25, g, aligned, chunk=4, acc_dtype=np.float64, return_tap_max=True)
+            assert b.dtype == np.float64 and m.shape == b.shape
+            np.testing.assert_allclose(b, a, rtol=0, atol=1e-5)
+            assert (np.abs(b) <= m + 1e-12).all()
+            assert (b[5] == 0).all() and (m[5] == 0).all()   # wholly left of x = -1: no sample in range
+    # the sums really are float64: a sum of fp32 products that fp32 rounds away (2^10 + 2^-20) survives
+    f2 = np.full((1, 4, 4), 2.0 ** -20, np.float32)
+    f2[0, 1, 1] = 2.0 ** 10
+    c = np_ops.roi_align_fast(f2, np.array([[0.5, 0.5, 2.5, 2.5]], np.float32), 1, 1.0, 2, True, acc_dtype=np.float64)
+    assert c[0, 0, 0, 0] == (2.0 ** 10 + 3 * 2.0 ** -20) / 4
+
+
 def test_tiny_faster_rcnn_oracle_runs():
     cfg = Config.fromfile("configs/faster_rcnn/faster_rcnn_tiny.py")
     m = build_detector(cfg.model, cfg.train_cfg, cfg.test_cfg)

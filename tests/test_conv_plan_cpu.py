@@ -10,52 +10,9 @@ import subprocess
 import pytest
 
 from minddet_amd import _lib, nn_ops
+from tests.conv_contract import HALO, IGEMM, PINGPONG, STREAM, _struct, kernel_name, plan
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-IGEMM, PINGPONG, STREAM, HALO = 1, 2, 3, 4
-
-
-class Launch(ctypes.Structure):   # md_conv_launch (include/minddet_hip.h)
-    _fields_ = [(n, ctypes.c_int32) for n in (
-        "family", "kernel_id", "ct", "pt", "mode", "gen", "dual", "mf", "head", "pers", "halo", "abl", "k", "cb", "nw", "res", "silu",
-        "one_halo", "single_buf", "sub", "n0", "nn", "block", "lds")] + [("grid", ctypes.c_int64)]
-
-
-def kernel_name(r):
-    """the demangled template instance a record names (as a kernel trace prints it)"""
-    b = lambda v: "true" if v else "false"
-    if r.family == IGEMM:
-        wc, fc = (2, 2) if r.ct == 128 else (1, 2 if r.ct == 64 else 1)
-        return f"conv_igemm_kernel<256, {wc}, {4 // wc}, {fc}, 2, {r.mode}, {r.gen}, {r.dual}>"
-    if r.family == PINGPONG:
-        return f"conv_pingpong_kernel<{r.abl}, {r.mf}, {r.gen}, {b(r.head)}, {b(r.pers)}, {b(r.halo)}>"
-    if r.family == STREAM:
-        return f"conv1x1_stream_kernel<{r.k}, {r.cb}, {b(r.silu)}, {r.res}, {r.nw}>"
-    assert r.family == HALO
-    return f"conv3x3_halo_kernel<{r.ct}, {b(r.one_halo)}>"
-
-
-def _struct(cls, d):
-    s = cls()
-    for k, v in d.items():
-        setattr(s, k, _struct(type(getattr(s, k)), v) if isinstance(v, dict) else v)
-    return s
-
-
-def plan(op, shapes, attrs, dtypes=None, lib_path=None):
-    """-> (rc, [Launch]).  Tensor pointers are fake non-null addresses: the plan never dereferences them."""
-    lib = ctypes.CDLL(lib_path or _lib.LIB_PATH)
-    n = len(shapes)
-    params = (ctypes.c_void_p * n)(*[None if s is None else 0x100000 * (i + 1) for i, s in enumerate(shapes)])
-    ndims = (ctypes.c_int * n)(*[0 if s is None else len(s) for s in shapes])
-    bufs = [(ctypes.c_int64 * max(len(s or []), 1))(*(s or [0])) for s in shapes]
-    shp = (ctypes.POINTER(ctypes.c_int64) * n)(*[ctypes.cast(b_, ctypes.POINTER(ctypes.c_int64)) for b_ in bufs])
-    dts = (ctypes.c_char_p * n)(*[None if d is None else d.encode() for d in (dtypes or [None] * n)])
-    cnt = ctypes.c_int(0)
-    out = (Launch * 64)()
-    rc = lib.md_conv_plan(op.encode(), n, params, ndims, shp, dts, ctypes.byref(attrs), out, 64, ctypes.byref(cnt))
-    assert cnt.value <= 64
-    return rc, [out[i] for i in range(cnt.value)]
 
 
 def conv(x, cout, k=3, stride=1, pad=None, relu=1, variant=0, korder=None, res=False, tune=None, res_up=False, lib_path=None, **adv):

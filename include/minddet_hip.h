@@ -654,7 +654,9 @@ typedef struct md_yolo_attrs {
 } md_yolo_attrs;
 /* in head[B,H,W,Cp] bf16 ; out boxes[B,out_total,4] f32 (x1,y1,x2,y2), scores[B,out_total] f32 = obj*max_cls
  * (-FLT_MAX if obj <= conf_thres or score <= conf_thres), labels[B,out_total] i32 ; only rows
- * [out_offset, out_offset + H*W*A) are written */
+ * [out_offset, out_offset + H*W*A) are written.  label = the arg-max of the bf16 class logits (unclamped), the first index on
+ * ties, and max_cls = sigmoid(logit[label]): the arg-max of the exact class probabilities, also where the fp32 sigmoid saturates
+ * (>= 16.75 -> 1.0) or underflows (< -87) -- md_yolov8_decode's rule. */
 int md_yolo_decode(MD_AOT_ARGS);
 
 #ifdef __cplusplus

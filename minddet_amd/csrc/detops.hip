@@ -1134,9 +1134,10 @@ __global__ void centerpoint_decode_kernel(const uint16_t *__restrict__ head, CpA
 struct YoloArgs { int H, W, Cp, nc, A; float stride, aw[3], ah[3], thr; int off, total; };
 // Head rows are staged through LDS with coalesced 16-B loads (cells consecutive cells x Cp channels; rows padded by one dword so
 // that the per-(cell, anchor) scalar reads that follow spread over the banks): r01 the direct 2-byte global reads at a 170-B lane
-// stride made this kernel 24 % of the YOLOv5s step.  The class arg-max runs on the logits (sigmoid is monotonic; logits are
-// clamped to the range where the fp32 sigmoid still separates values, so saturated ties resolve to the first index as they
-// would after the sigmoid) and only the winner is passed through the sigmoid.
+// stride made this kernel 24 % of the YOLOv5s step.  The class arg-max runs on the unclamped bf16 logits, first index on ties (the
+// float64 sigmoid is strictly increasing, so this is the arg-max of the exact class probabilities; the fp32 sigmoid saturates to
+// 1.0 from 16.75 up and underflows below -87, where an arg-max taken after it, or on clamped logits, would pick the first of the
+// saturated classes instead), and only the winner is passed through the sigmoid -- as yolov8_decode_kernel does.
 __device__ __forceinline__ void stage_head_rows(const uint16_t *__restrict__ head, unsigned *sm, long long cell0, long long cells_total,
                                                 int cells, int Cp) {
     const int chunks = Cp / 8, rowdw = Cp / 2 + 1;
@@ -1150,8 +1151,6 @@ __device__ __forceinline__ void stage_head_rows(const uint16_t *__restrict__ hea
     }
     __syncthreads();
 }
-__device__ __forceinline__ float logit_key(float v) { return fminf(fmaxf(v, -87.f), 16.f); }
-
 __global__ __launch_bounds__(256) void yolo_decode_kernel(const uint16_t *__restrict__ head, YoloArgs a, int B, int cells,
                                                           float *__restrict__ boxes, float *__restrict__ scores, int *__restrict__ labels) {
     extern __shared__ unsigned ysm[];
@@ -1169,13 +1168,13 @@ __global__ __launch_bounds__(256) void yolo_decode_kernel(const uint16_t *__rest
     const float sx = sg(rbf2f(h[0])), sy = sg(rbf2f(h[1])), sw = sg(rbf2f(h[2])), sh = sg(rbf2f(h[3])), obj = sg(rbf2f(h[4]));
     const float cx = (sx * 2.f - 0.5f + (float)gx) * a.stride, cy = (sy * 2.f - 0.5f + (float)gy) * a.stride;
     const float w = (sw * 2.f) * (sw * 2.f) * a.aw[an], hh = (sh * 2.f) * (sh * 2.f) * a.ah[an];
-    float best = -FLT_MAX, best_v = 0.f;
+    float best = -FLT_MAX;
     int lab = 0;
     for (int k = 0; k < a.nc; ++k) {
-        const float v = rbf2f(h[5 + k]), key = logit_key(v);
-        if (key > best) { best = key; best_v = v; lab = k; }
+        const float v = rbf2f(h[5 + k]);
+        if (v > best) { best = v; lab = k; }
     }
-    const float conf = obj * sg(best_v);
+    const float conf = obj * sg(best);
     const size_t o = (size_t)b * a.total + a.off + (size_t)loc * a.A + an;
     *reinterpret_cast<float4 *>(boxes + o * 4) = make_float4(cx - w / 2, cy - hh / 2, cx + w / 2, cy + hh / 2);
     scores[o] = (obj > a.thr && conf > a.thr) ? conf : -FLT_MAX;

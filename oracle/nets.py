@@ -375,19 +375,22 @@ def yolov5_heads(m, x, quant=False):
 
 
 def yolo_decode_np(head_nhwc, nc, na, stride, anchors, conf_thres):
-    """head [B,H,W,C>=na*(5+nc)] float32 -> boxes [B,HWA,4], scores [B,HWA] (-inf where rejected), labels."""
+    """head [B,H,W,C>=na*(5+nc)] float32 -> boxes [B,HWA,4], scores [B,HWA] (-inf where rejected), labels.  label = the arg-max
+    of the class LOGITS (first index on ties), score = obj * sigmoid(max logit): the arg-max of float32-rounded sigmoids would tie
+    saturated classes (sigmoid(x) rounds to 1.0 from x = 16.75 up) and pick the first of them."""
     B, H, W, _ = head_nhwc.shape
     h = head_nhwc[..., :na * (5 + nc)].reshape(B, H, W, na, 5 + nc).astype(np.float32)
-    s = (1.0 / (1.0 + np.exp(-h.astype(np.float64)))).astype(np.float32)
+    sig = lambda t: (1.0 / (1.0 + np.exp(-t.astype(np.float64)))).astype(np.float32)
+    s = sig(h)
     gy, gx = np.meshgrid(np.arange(H, dtype=np.float32), np.arange(W, dtype=np.float32), indexing="ij")
     cx = (s[..., 0] * 2 - 0.5 + gx[None, :, :, None]) * np.float32(stride)
     cy = (s[..., 1] * 2 - 0.5 + gy[None, :, :, None]) * np.float32(stride)
     an = np.asarray(anchors, np.float32).reshape(na, 2)
     w = (s[..., 2] * 2) ** 2 * an[None, None, None, :, 0]
     hh = (s[..., 3] * 2) ** 2 * an[None, None, None, :, 1]
-    obj, cls = s[..., 4], s[..., 5:]
-    best, lab = cls.max(-1), cls.argmax(-1)
-    conf = obj * best
+    obj, logits = s[..., 4], h[..., 5:]
+    lab = logits.argmax(-1)
+    conf = obj * sig(logits.max(-1))
     ok = (obj > np.float32(conf_thres)) & (conf > np.float32(conf_thres))
     boxes = np.stack([cx - w / 2, cy - hh / 2, cx + w / 2, cy + hh / 2], -1).reshape(B, -1, 4).astype(np.float32)
     return boxes, np.where(ok, conf, -np.inf).reshape(B, -1).astype(np.float32), lab.reshape(B, -1).astype(np.int32)

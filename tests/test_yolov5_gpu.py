@@ -43,7 +43,7 @@ def test_yolov5s_end_to_end():
         both = np.isfinite(s_d) & np.isfinite(s_o)
         assert (np.isfinite(s_d) != np.isfinite(s_o)).mean() < 1e-3
         np.testing.assert_allclose(s_d[both], s_o[both], rtol=3e-6, atol=1e-7)
-        assert (ld[:, off:off + n][both] == l_o[both]).mean() > 0.999
+        np.testing.assert_array_equal(ld[:, off:off + n], l_o)   # arg-max of the same bf16 logits, first index on ties: exact
         off += n
     # select + class-aware NMS + packing from the DEVICE scores/boxes/labels: exact
     d = dets.cpu().numpy()

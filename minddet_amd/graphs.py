@@ -62,9 +62,10 @@ class SplitForward:
             return p[0] if prepare is None else prepare(*p)
 
         cur = torch.cuda.current_stream(dev)
-        # the model's pack generation is part of the key: .to() after a weight reload drops the lazily built packs (fused blocks, merged
-        # convs), and the pass that rebuilds them must again be a single-stream one (r03 ADVICE: part 1 would read them unsynchronised)
-        key = (getattr(self.model, "_pack_gen", 0), step, prepare is not None) + tuple(ins[0].shape[1:])
+        # the pack generation is part of the key: any .to() (after a weight reload, of the model or of one of its parts) makes new packs and
+        # empties the device constants, and the pass that builds those again must be a single-stream one (r03 ADVICE: part 1 would read
+        # them unsynchronised)
+        key = (Module.generation, step, prepare is not None) + tuple(ins[0].shape[1:])
         if key not in self._primed:
             self.model.forward(part(0), **kw)
             self._primed.add(key)
@@ -88,12 +89,6 @@ def _split_forward_of(model, test_cfg):
     """test_cfg.streams (default 1) -> model.streams and model.forward_split (== model.forward for one stream)"""
     model.streams = int((test_cfg or {}).get("streams", 1))
     model.forward_split = SplitForward(model, model.streams)
-    model._pack_gen = 0
-
-
-def _packs_rebuilt(model):
-    """called by every detector's .to(): the packed weights (and with them every lazily derived pack) are new objects from here on"""
-    model._pack_gen = getattr(model, "_pack_gen", 0) + 1
 
 
 class ParamInit:
@@ -116,7 +111,54 @@ class ParamInit:
         return torch.from_numpy(self.rng.normal(0, std, c).astype(np.float32))
 
 
-class ConvModule:
+class Module:
+    """Life cycle of everything that holds parameters or sub-modules.  A class names its direct sub-modules in `children()`; a class
+    without any is a leaf and packs its own parameters in `_derive`.  `to(device)` is the one place packs are made: it packs the
+    children, then `_derive(device)` builds every pack that is derived from theirs (fused blocks, merged convs, stem forms) into plain
+    attributes -- so the call that repacks a conv also rebuilds what was made from it -- empties the device constants and advances
+    the process-wide pack generation SplitForward keys its priming pass on."""
+    generation = 0
+
+    def children(self):
+        return []
+
+    def modules(self):
+        """the leaves under this module, in children order"""
+        ch = self.children()
+        return [m for c in ch for m in c.modules()] if ch else [self]
+
+    conv_modules = modules
+
+    def to(self, device):
+        for c in self.children():
+            c.to(device)
+        self._derive(device)
+        self._consts = {}
+        Module.generation += 1
+        return self
+
+    def _derive(self, device):
+        pass
+
+    def const(self, key, build):
+        """a shape-dependent device constant (anchors, segment tables, a side stream): built on first use, dropped by to()"""
+        if key not in self._consts:
+            self._consts[key] = build()
+        return self._consts[key]
+
+
+def _segments(B, n, device):
+    """[0, n, 2 n, ..., B n] int32: the segment table of B equal segments (det_ops.topk_segmented)"""
+    return torch.arange(0, (B + 1) * n, n, dtype=torch.int32, device=device)
+
+
+def _image_hw(images):
+    """(H, W) of the images in a batch; in the stem layout (nn_ops.to_stem_layout) the border is not image"""
+    border = nn_ops.STEM_PAD_LO + nn_ops.STEM_PAD_HI if images.shape[3] == 4 else 0
+    return images.shape[1] - border, images.shape[2] - border
+
+
+class ConvModule(Module):
     """Conv2d [+ BatchNorm2d(eval)] [+ ReLU] -> one md_conv2d call."""
 
     def __init__(self, init, cin, cout, k, stride=1, pad=0, bn=True, relu=True, bias=False, bn_eps=1e-5, std=None,
@@ -130,10 +172,9 @@ class ConvModule:
         self.bias = init.bias(cout, bias_value) if bias else None
         self.packed = None
 
-    def to(self, device):
+    def _derive(self, device):
         self.packed = nn_ops.pack_conv(self.weight, bias=self.bias, bn=self.bn, stride=self.stride, pad=self.pad,
                                        relu=self.act).to(device)
-        return self
 
     def __call__(self, x, residual=None, out=None, c_off=0, x_c_off=None, res_c_off=None):
         return nn_ops.conv2d(x, self.packed, residual=residual, out=out, c_off=c_off, x_c_off=x_c_off, res_c_off=res_c_off)
@@ -156,7 +197,7 @@ def merged_conv(mods, device):
 
 
 # ----------------------------------------------------------------------------- ResNet (centernet/src/resnet.py)
-class BasicBlock:
+class BasicBlock(Module):
     """centernet/src/resnet.py:109-136"""
     expansion = 1
 
@@ -165,7 +206,7 @@ class BasicBlock:
         self.conv2 = ConvModule(init, planes, planes, 3, 1, 1, relu=True)  # ReLU applied after the residual add
         self.downsample = downsample
 
-    def modules(self):
+    def children(self):
         return [self.conv1, self.conv2] + ([self.downsample] if self.downsample else [])
 
     def __call__(self, x):
@@ -174,7 +215,7 @@ class BasicBlock:
         return self.conv2(out, residual=residual)
 
 
-class Bottleneck:
+class Bottleneck(Module):
     """centernet/src/resnet.py:139-178 (stride on the 3x3 conv)"""
     expansion = 4
 
@@ -183,34 +224,32 @@ class Bottleneck:
         self.conv2 = ConvModule(init, planes, planes, 3, stride, 1)
         self.conv3 = ConvModule(init, planes, planes * 4, 1, relu=True)  # ReLU after the residual add
         self.downsample = downsample
-        self._fused = False
-        self._dual = False
+        self._fused = self._dual = None   # the md_bottleneck / md_conv1x1_dual packs (None: the kernel does not take this block)
 
-    def modules(self):
+    def children(self):
         return [self.conv1, self.conv2, self.conv3] + ([self.downsample] if self.downsample else [])
 
+    def _derive(self, device):
+        # (PackedDual and PackedBottleneck.b12 hold their own copies of the conv packs' numbers)
+        pd = self.downsample.packed if self.downsample is not None else None
+        self._fused = nn_ops.pack_bottleneck(self.conv1.packed, self.conv2.packed, self.conv3.packed, pd)
+        self._dual = nn_ops.pack_dual(self.conv3.packed, pd) if pd is not None else None
+
     def __call__(self, x):
-        if FUSE_BLOCKS:
-            if self._fused is False:   # packed on first use (the convs are packed by ResNet.to)
-                self._fused = nn_ops.pack_bottleneck(self.conv1.packed, self.conv2.packed, self.conv3.packed,
-                                                     self.downsample.packed if self.downsample is not None else None)
-            if self._fused is not None:
-                # one launch for the whole block (md_bottleneck): x is read once, the 64-channel intermediates stay in LDS, and the
-                # first block's 1x1 downsample conv is computed from the same x tile
-                res = self.downsample(x) if (self.downsample is not None and self._fused.wd is None) else None
-                return nn_ops.bottleneck(x, self._fused, residual=res)
-        if FUSE_DUAL and self.downsample is not None:
+        if FUSE_BLOCKS and self._fused is not None:
+            # one launch for the whole block (md_bottleneck): x is read once, the 64-channel intermediates stay in LDS, and the
+            # first block's 1x1 downsample conv is computed from the same x tile
+            res = self.downsample(x) if (self.downsample is not None and self._fused.wd is None) else None
+            return nn_ops.bottleneck(x, self._fused, residual=res)
+        if FUSE_DUAL and self._dual is not None:
             # first block of a stage: conv3 and the (strided) 1x1 downsample conv as ONE GEMM over [t2 ; x] (md_conv1x1_dual)
-            if self._dual is False:
-                self._dual = nn_ops.pack_dual(self.conv3.packed, self.downsample.packed)
-            if self._dual is not None:
-                return nn_ops.conv1x1_dual(self.conv2(self.conv1(x)), x, self._dual)
+            return nn_ops.conv1x1_dual(self.conv2(self.conv1(x)), x, self._dual)
         residual = self.downsample(x) if self.downsample is not None else x
         return self.conv3(self.conv2(self.conv1(x)), residual=residual)
 
 
 @BACKBONES.register_module
-class ResNet:
+class ResNet(Module):
     """centernet/src/resnet.py:181-252: 7x7/2 stem + BN + ReLU, zero-pad + MaxPool(3,2), 4 stages;
     returns (C2, C3, C4, C5).  depth 18/34 -> BasicBlock, 50/101 -> Bottleneck."""
     SETTINGS = {18: (BasicBlock, [2, 2, 2, 2]), 34: (BasicBlock, [3, 4, 6, 3]), 50: (Bottleneck, [3, 4, 6, 3]),
@@ -237,26 +276,13 @@ class ResNet:
             layers.append(block(init, self.inplanes, planes))
         return layers
 
-    def modules(self):
-        out = [self.conv1]
-        for st in self.stages:
-            for b in st:
-                out += b.modules()
-        return out
+    def children(self):
+        return [self.conv1] + [b for st in self.stages for b in st]
 
-    def to(self, device):
-        for m in self.modules():
-            m.to(device)
-        # the fused-block / dual-GEMM packs are derived from the conv packs just rebuilt (PackedDual and PackedBottleneck.b12 hold their own
-        # copies): drop them, or a forward pass after a weight change + .to() would keep running the old weights in those launches
-        for st in self.stages:
-            for b in st:
-                if isinstance(b, Bottleneck):
-                    b._fused = b._dual = False
+    def _derive(self, device):
         self.stem = None
         if self.conv1.cout == 64 and self.conv1.relu:  # the fused conv + BN + ReLU + maxpool kernel (md_stem_pool)
             self.stem = nn_ops.pack_stem(self.conv1.weight, bn=self.conv1.bn, bias=self.conv1.bias).to(device)
-        return self
 
     def __call__(self, x):
         """x: [N,H,W,8] bf16 NHWC (3 real channels), or the same batch already in the stem layout
@@ -278,7 +304,7 @@ class ResNet:
 
 # ----------------------------------------------------------------------------- FPN / RPN / RoI head (build-authored)
 @NECKS.register_module
-class FPN:
+class FPN(Module):
     """Lin et al. 2017: 1x1 laterals, top-down nearest upsample + add, 3x3 output convs, extra level by
     stride-2 subsampling (max_pool k=1 s=2) of the last output.  parity unpinned."""
 
@@ -289,13 +315,8 @@ class FPN:
                        for _ in in_channels]
         self.num_outs = num_outs
 
-    def modules(self):
+    def children(self):
         return self.lateral + self.output
-
-    def to(self, device):
-        for m in self.modules():
-            m.to(device)
-        return self
 
     def __call__(self, feats):
         # top-down path: lateral_i + nearest_up(merged_{i+1}).  When the pyramid halves exactly the add is fused into
@@ -316,7 +337,7 @@ class FPN:
 
 
 @HEADS.register_module
-class RPNHead:
+class RPNHead(Module):
     """Shared 3x3 conv + ReLU, then one fused 1x1 conv producing [A objectness | 4A deltas] channels.
     Proposal generation: per level top-k (nms_pre) on the logits, delta2bbox + clip, NMS (iou_thr),
     per image top-`max_per_img` across levels.  parity unpinned (absent from the reference)."""
@@ -329,34 +350,25 @@ class RPNHead:
         self.out = ConvModule(init, feat_channels, 5 * self.A, 1, bn=False, relu=False, bias=True, std=0.01)
         self.strides, self.scale, self.ratios = tuple(strides), scale, tuple(ratios)
         self.nms_pre, self.max_per_img, self.nms_thr = nms_pre, max_per_img, nms_thr
-        self._cache = {}
-        self._side = None
 
-    def modules(self):
+    def children(self):
         return [self.conv, self.out]
 
-    def to(self, device):
-        for m in self.modules():
-            m.to(device)
-        return self
-
     def _static(self, feats, img_hw):
-        B = feats[0].shape[0]
+        B, dev = feats[0].shape[0], feats[0].device
         sizes = tuple((f.shape[1], f.shape[2]) for f in feats)
-        key = (B, sizes, img_hw)
-        if key not in self._cache:
-            dev = feats[0].device
+
+        def build():
             anchors = det_ops.fpn_anchors(sizes, self.strides, self.scale, self.ratios, device=dev)
             per, offs, o = [], [], 0
             for (h, w) in sizes:
                 n = h * w * self.A
                 per.append(anchors[o:o + n])
-                offs.append(torch.arange(0, (B + 1) * n, n, dtype=torch.int32, device=dev))
+                offs.append(_segments(B, n, dev))
                 o += n
-            L, k = len(sizes), self.nms_pre
-            self._cache[key] = dict(anchors=per, seg=offs,
-                                    merged_seg=torch.arange(0, (B + 1) * L * k, L * k, dtype=torch.int32, device=dev))
-        return self._cache[key]
+            return dict(anchors=per, seg=offs, merged_seg=_segments(B, len(sizes) * self.nms_pre, dev))
+
+        return self.const((B, sizes, img_hw), build)
 
     def __call__(self, feats, img_hw):
         st = self._static(feats, img_hw)
@@ -369,14 +381,13 @@ class RPNHead:
         # RPN_OVERLAP: the per-level selection (slice, top-k, decode: small latency-bound launches) runs on a side stream behind the
         # level's conv while the main stream goes on with the next level's conv; the streams join before the NMS
         main = torch.cuda.current_stream(dev) if RPN_OVERLAP else None
-        if RPN_OVERLAP and self._side is None:
-            self._side = torch.cuda.Stream(dev)
+        side = self.const("side", lambda: torch.cuda.Stream(dev)) if RPN_OVERLAP else None
         keep_alive = []
         if RPN_OVERLAP:
             # written on the side stream, allocated on the main one: the caching allocator must not hand their memory to a
             # main-stream allocation while side-stream work may still touch it, whatever happens to the Python references
             for t in (boxes, scores, counts):
-                t.record_stream(self._side)
+                t.record_stream(side)
         try:
             for l, f in enumerate(feats):
                 if RPN_FUSED_HEAD and self.conv.cout == 256 and self.out.packed.cout == 16 and self.conv.relu:
@@ -393,17 +404,17 @@ class RPNHead:
                     keep_alive.append((logits, idx, cnt))
 
                 if RPN_OVERLAP:
-                    head.record_stream(self._side)
+                    head.record_stream(side)
                     ev = torch.cuda.Event()
                     ev.record(main)
-                    with torch.cuda.stream(self._side):
-                        self._side.wait_event(ev)
+                    with torch.cuda.stream(side):
+                        side.wait_event(ev)
                         select()
                 else:
                     select()
         finally:
             if RPN_OVERLAP:
-                main.wait_stream(self._side)   # always joined, also when a level's selection raised
+                main.wait_stream(side)   # always joined, also when a level's selection raised
         keep, _, _ = det_ops.nms_aligned(boxes.view(L * B, k, 4), self.nms_thr, mode=det_ops.NMS_MODE_STRICT,
                                          count=counts.view(-1))
         mboxes, mscores = det_ops.rpn_merge(boxes, scores, keep.view(L, B, k))
@@ -414,7 +425,7 @@ class RPNHead:
 
 
 @ROI_HEAD.register_module
-class StandardRoIHead:
+class StandardRoIHead(Module):
     """RoIAlign 7x7 over P2..P5 -> FC 1024 -> FC 1024 -> fused [cls (nc+1) | reg (4 nc)] FC, softmax,
     class-specific delta2bbox, score threshold, class-wise NMS, top max_per_img.  parity unpinned."""
 
@@ -439,19 +450,13 @@ class StandardRoIHead:
         self.fc_out.weight[:num_classes + 1] *= 20.0
         self.strides, self.sampling = tuple(featmap_strides), sampling_ratio
         self.score_thr, self.nms_thr, self.max_per_img, self.nms_pre = score_thr, nms_thr, max_per_img, nms_pre
-        self._cache = {}
         # nms_pre: the class-wise NMS runs on the top-nms_pre (roi, class) candidates of an image instead of on all of them (the
         # public definition: every candidate above score_thr).  The cut is result-identical whenever the prefix yields max_per_img
         # survivors or was not full; the one other case raises a sticky per-image flag on the device (DESIGN.md "pre-NMS prefix")
         self.prefix_status = det_ops.PrefixStatus()
 
-    def modules(self):
+    def children(self):
         return [self.fc1, self.fc2, self.fc_out]
-
-    def to(self, device):
-        for m in self.modules():
-            m.to(device)
-        return self
 
     def __call__(self, feats, rois, roi_cnt, img_hw):
         B = feats[0].shape[0]
@@ -464,10 +469,8 @@ class StandardRoIHead:
         x = nn_ops.linear(x, self.fc2.packed)
         cls_reg = nn_ops.linear(x, self.fc_out.packed)
         cand = det_ops.rcnn_scores(cls_reg, roi_cnt, self.nc, self.score_thr)
-        key = (B, post)
-        if key not in self._cache:
-            self._cache[key] = torch.arange(0, (B + 1) * post * self.nc, post * self.nc, dtype=torch.int32, device=dev)
-        sv, si, sc = det_ops.topk_segmented(cand, self._cache[key], self.nms_pre, max_segment=post * self.nc)
+        seg = self.const((B, post), lambda: _segments(B, post * self.nc, dev))
+        sv, si, sc = det_ops.topk_segmented(cand, seg, self.nms_pre, max_segment=post * self.nc)
         boxes, labels = det_ops.rcnn_decode_selected(cls_reg, rois, si, sc, self.nc, self.reg_offset, img_hw)
         keep, kidx, num = det_ops.nms_aligned(boxes, self.nms_thr, mode=det_ops.NMS_MODE_STRICT, count=sc, group=labels,
                                               max_output=self.max_per_img)
@@ -478,7 +481,7 @@ class StandardRoIHead:
 
 
 @DETECTORS.register_module
-class FasterRCNN:
+class FasterRCNN(Module):
     """Two-stage detector: backbone -> neck -> rpn_head -> roi_head.  `forward(images)` takes
     [B,H,W,8] bf16 NHWC (RGB in channels 0..2, 5 zero channels) and returns (dets [B,max_det,6], count [B])."""
 
@@ -492,14 +495,8 @@ class FasterRCNN:
         self.test_cfg = test_cfg
         _split_forward_of(self, test_cfg)
 
-    def to(self, device):
-        for m in (self.backbone, self.neck, self.rpn_head, self.roi_head):
-            m.to(device)
-        _packs_rebuilt(self)
-        return self
-
-    def conv_modules(self):
-        return self.backbone.modules() + self.neck.modules() + self.rpn_head.modules() + self.roi_head.modules()
+    def children(self):
+        return [self.backbone, self.neck, self.rpn_head, self.roi_head]
 
     @property
     def prefix_status(self):
@@ -510,9 +507,7 @@ class FasterRCNN:
         return self.neck(self.backbone(images))
 
     def forward(self, images, return_aux=False):
-        img_hw = (images.shape[1], images.shape[2])
-        if images.shape[3] == 4:  # stem layout (nn_ops.to_stem_layout): the border is not image
-            img_hw = (img_hw[0] - nn_ops.STEM_PAD_LO - nn_ops.STEM_PAD_HI, img_hw[1] - nn_ops.STEM_PAD_LO - nn_ops.STEM_PAD_HI)
+        img_hw = _image_hw(images)
         feats = self.extract_feat(images)
         rois, roi_scores, roi_cnt, aux_rpn = self.rpn_head(feats, img_hw)
         dets, count, aux_roi = self.roi_head(feats, rois, roi_cnt, img_hw)
@@ -561,7 +556,7 @@ class FasterRCNN:
 
 
 # ----------------------------------------------------------------------------- CenterNet (reference-present graph)
-class DeconvModule:
+class DeconvModule(Module):
     """Conv2dTranspose [+ BatchNorm2d] [+ ReLU] -> s*s sub-pixel md_conv2d launches (nn_ops.pack_conv_transpose)."""
 
     def __init__(self, init, cin, cout, k, stride, pad, bn=True, relu=True, bn_eps=1e-5):
@@ -571,17 +566,16 @@ class DeconvModule:
         self.bn = init.bn(cout, bn_eps) if bn else None
         self.packed = None
 
-    def to(self, device):
+    def _derive(self, device):
         self.packed = nn_ops.pack_conv_transpose(self.weight_t, bn=self.bn, stride=self.stride, pad=self.pad,
                                                  relu=self.relu).to(device)
-        return self
 
     def __call__(self, x, out=None, c_off=0):
         return nn_ops.conv_transpose2d(x, self.packed, out=out, c_off=c_off)
 
 
 @ROI_HEAD.register_module
-class FCNMaskHead:
+class FCNMaskHead(Module):
     """Mask R-CNN mask branch (He et al. 2017, FPN variant): RoIAlign 14x14 over P2..P5 on the final detections -> 4 x
     [3x3 conv 256 + ReLU] -> Conv2dTranspose 2x2 s2 + ReLU -> 1x1 conv to num_classes -> the detection's own class channel,
     sigmoid: [B, max_det, 28, 28].  Absent from the reference (Mask R-CNN is a README bullet): parity unpinned."""
@@ -599,13 +593,8 @@ class FCNMaskHead:
         self.logits = ConvModule(init, conv_channels, num_classes, 1, bn=False, relu=False, bias=True, std=0.05)
         self.strides, self.sampling = tuple(featmap_strides), sampling_ratio
 
-    def modules(self):
+    def children(self):
         return self.convs + [self.upsample, self.logits]
-
-    def to(self, device):
-        for m in self.modules():
-            m.to(device)
-        return self
 
     def __call__(self, feats, dets):
         B, D = dets.shape[0], dets.shape[1]
@@ -631,23 +620,15 @@ class MaskRCNN(FasterRCNN):
         self.paste = bool(tc.get("paste_masks", False))
         self.mask_thr = float(tc.get("mask_thr_binary", 0.5))
 
-    def to(self, device):
-        super().to(device)
-        self.mask_head.to(device)
-        return self
-
-    def conv_modules(self):
-        return super().conv_modules() + self.mask_head.modules()
+    def children(self):
+        return super().children() + [self.mask_head]
 
     def forward(self, images, return_aux=False, paste=None):
         dets, count, aux = FasterRCNN.forward(self, images, return_aux=True)
         masks, aux_mask = self.mask_head(aux["feats"], dets)
         out = (dets, count, masks)
         if self.paste if paste is None else paste:
-            img_hw = (images.shape[1], images.shape[2])
-            if images.shape[3] == 4:  # stem layout: the border is not image
-                img_hw = (img_hw[0] - nn_ops.STEM_PAD_LO - nn_ops.STEM_PAD_HI, img_hw[1] - nn_ops.STEM_PAD_LO - nn_ops.STEM_PAD_HI)
-            out = out + (det_ops.paste_masks(masks, dets, img_hw, self.mask_thr, bits=True),)
+            out = out + (det_ops.paste_masks(masks, dets, _image_hw(images), self.mask_thr, bits=True),)
         if return_aux:
             aux["mask"] = aux_mask
             return out + (aux,)
@@ -656,7 +637,7 @@ class MaskRCNN(FasterRCNN):
     __call__ = forward
 
 
-class DeformConvModule:
+class DeformConvModule(Module):
     """ModulatedDeformConv2d (DCNv2) + BatchNorm2d + ReLU -- centernet/src/resnet.py:24-106, used by the CenterNet neck
     (centernet_det.py:123-160): offset conv (3*k*k channels, has_bias) -> md_deform_cols -> 1x1 md_conv2d over the columns.
     The reference zero-initialises the offset conv; here it gets a small random init so that random-weight runs and tests
@@ -672,12 +653,11 @@ class DeformConvModule:
         self.offset_bias = torch.from_numpy(init.rng.normal(0.0, 0.1, (3 * k * k,)).astype(np.float32))
         self.packed = self.packed_offset = None
 
-    def to(self, device):
+    def _derive(self, device):
         self.packed = nn_ops.pack_conv(self.weight, bias=self.bias, bn=self.bn, stride=self.stride, pad=self.pad, relu=self.act,
                                        korder=0).to(device)
         self.packed_offset = nn_ops.pack_conv(self.offset_weight, bias=self.offset_bias, stride=self.stride, pad=self.pad,
                                               relu=False).to(device)
-        return self
 
     def __call__(self, x):
         return nn_ops.deform_conv2d(x, self.packed_offset, self.packed)
@@ -687,7 +667,7 @@ class DeformConvModule:
 
 
 @DETECTORS.register_module
-class CenterNet:
+class CenterNet(Module):
     """centernet/src/centernet_det.py:79-174 (GatherDetectionFeatureCell) + :374-399 (CenterNetDetEval):
     ResNet-18 -> 3 x [3x3 conv + BN + ReLU, Conv2dTranspose 4x4 s2 p1 + BN + ReLU] (512->256->128->64)
     -> hm / wh / reg heads (3x3 conv 64 + ReLU, 1x1 conv; hm bias -2.19, :29-69) -> sigmoid+clip ->
@@ -726,7 +706,7 @@ class CenterNet:
         self.decode = det_ops.DetectionDecode(reg_offset=True, K=K)
 
     def fuse_heads(self):
-        """(Re)build the fused head convs from self.heads -- call after the per-head weights change (weights.py)."""
+        """(Re)build the fused head convs' weights from self.heads (to() calls it: they are packed like any other conv)."""
         hc = self.head_conv
         self.head1.weight = torch.cat([self.heads[n][0].weight for n in ("hm", "wh", "reg")], 0)
         self.head1.bias = torch.cat([self.heads[n][0].bias for n in ("hm", "wh", "reg")], 0)
@@ -740,14 +720,12 @@ class CenterNet:
             o += c2.cout
         self.head2.weight, self.head2.bias = w2, b2
 
-    def conv_modules(self):
-        return self.backbone.modules() + self.neck + [self.head1, self.head2]
+    def children(self):
+        return [self.backbone] + self.neck + [self.head1, self.head2]
 
     def to(self, device):
-        for m in self.conv_modules():
-            m.to(device)
-        _packs_rebuilt(self)
-        return self
+        self.fuse_heads()   # head1 / head2 are children whose weights derive from self.heads: refreshed before they are packed
+        return super().to(device)
 
     def features(self, images):
         x = self.backbone(images)[-1]
@@ -772,7 +750,7 @@ class CenterNet:
 
 # ----------------------------------------------------------------------------- CenterPoint RPN neck
 @NECKS.register_module
-class RPN:
+class RPN(Module):
     """centerpoint/det3d_ms/models/necks/rpn.py:9-154: per stage [Pad1 + Conv3x3(stride) + BN(eps 1e-3) + ReLU]
     + n x [Conv3x3 + BN + ReLU]; deblocks = Conv2dTranspose(k=s, stride s) or strided Conv2d(k, stride k)
     + BN + ReLU; channel concat -> [B, H/ds, W/ds, sum(us_num_filters)].  The concat is free: every deblock
@@ -801,13 +779,8 @@ class RPN:
                     self.deblocks.append(ConvModule(init, cin, cout, k, k, 0, bn_eps=eps))
         self.out_channels = sum(us_num_filters)
 
-    def modules(self):
+    def children(self):
         return [m for b in self.blocks for m in b] + self.deblocks
-
-    def to(self, device):
-        for m in self.modules():
-            m.to(device)
-        return self
 
     def __call__(self, x):
         out, c_off = None, 0
@@ -836,11 +809,11 @@ SEPHEAD_ORDER = ("reg", "height", "dim", "rot", "vel", "hm")         # the dict 
 
 
 @HEADS.register_module
-class CenterHead:
+class CenterHead(Module):
     """centerpoint/det3d_ms/models/bbox_heads/center_head.py:103-200: shared 3x3 conv (in_channels -> share_conv_channel, bias, BN,
     ReLU), then per task a SepHead (:28-99) with one branch per head of common_heads + hm: 3x3 conv 64 -> 64 + bias + BN(eps 1e-5) +
     ReLU, 3x3 conv 64 -> c + bias (hm bias init_bias).  The per-branch ConvModules (self.tasks[t][head] = (c1, c2)) are the source of
-    truth; fuse() rebuilds the fast form from them, three launches: the shared conv, ONE md_conv2d 64 -> 36 x 64 for every branch's
+    truth; to() rebuilds the fast form from them, three launches: the shared conv, ONE md_conv2d 64 -> 36 x 64 for every branch's
     first conv, ONE md_conv2d_grouped for every branch's last conv into one head tensor [B, H, W, roundup(sum c, 8)] that holds task
     t's heads in SEPHEAD_ORDER from channel task_base[t] (channels past sum c are not written).  MD_SEPHEAD_GROUPED=0 runs the last
     convs as one md_conv2d per branch instead, into [B, H, W, 8 x branches] with branch i at channel 8 i (A/B)."""
@@ -882,30 +855,20 @@ class CenterHead:
             self.offsets.append(off)
         self.head_channels = base
         self.task_base = [min(o.values()) for o in self.offsets]
-        self._dev = None
 
     def branches(self):
         return [(t, h, c1, c2) for t, sep in enumerate(self.tasks) for h, (c1, c2) in sep.items()]
 
-    def conv_modules(self):
-        return [self.shared_conv] + [m for _, _, c1, c2 in self.branches() for m in (c1, c2)]
+    def children(self):
+        """the convs that are packed alone: the shared conv and every branch's last conv (the A/B path).  The branches' first convs only
+        run merged (_derive); branches() lists both."""
+        return [self.shared_conv] + [c2 for _, _, _, c2 in self.branches()]
 
-    def fuse(self):
-        """(Re)build the fast form from the per-branch ConvModules on the head's device (call after the weights change; .to() calls it)."""
-        if self._dev is None:
-            return self
+    def _derive(self, device):
         br = self.branches()
-        self._first = merged_conv([c1 for _, _, c1, _ in br], self._dev)
+        self._first = merged_conv([c1 for _, _, c1, _ in br], device)
         self._second = nn_ops.pack_conv2d_grouped([(c2.weight, c2.bias, None) for _, _, _, c2 in br],
-                                                  y_offs=[self.offsets[t][h] for t, h, _, _ in br]).to(self._dev)
-        for _, _, _, c2 in br:           # the per-branch last convs packed alone: the A/B path
-            c2.to(self._dev)
-        return self
-
-    def to(self, device):
-        self._dev = device
-        self.shared_conv.to(device)
-        return self.fuse()
+                                                  y_offs=[self.offsets[t][h] for t, h, _, _ in br]).to(device)
 
     def task_offsets(self, grouped=None):
         """per task {head: first channel} in the head tensor __call__ returns (grouped None: the SEPHEAD_GROUPED setting)"""
@@ -935,7 +898,7 @@ class CenterHead:
 
 
 @DETECTORS.register_module
-class PointPillars:
+class PointPillars(Module):
     """det3d's PointPillars detector with a CenterHead (centerpoint/det3d_ms/models/detectors/point_pillars.py; the nuScenes
     CenterPoint-PP config): neck (graphs.RPN) -> bbox_head (CenterHead) -> one CenterHeadPost per task -> the task merge of
     tools_ms/eval.py:84-111.  The pillar encoder (reader) and the scatter (backbone) are out of scope: forward() takes the scattered
@@ -951,11 +914,8 @@ class PointPillars:
         self.test_cfg = test_cfg
         self.max_per_task = int(test_cfg["nms"]["nms_post_max_size"])
 
-    def to(self, device):
-        self.neck.to(device)
-        self.bbox_head.to(device)
-        _packs_rebuilt(self)
-        return self
+    def children(self):
+        return [self.neck, self.bbox_head]
 
     def forward(self, pseudo_image, return_aux=False):
         """pseudo_image [B, H, W, 64] bf16 -> (dets [B, tasks x nms_post_max_size, 11] f32, count [B] i32): per row the 9 box values
@@ -1004,7 +964,7 @@ def _yconv(init, cin, cout, k=1, s=1, p=None):
     return ConvModule(init, cin, cout, k, s, k // 2 if p is None else p, bn=True, bn_eps=1e-3, act="silu")
 
 
-class C3:
+class C3(Module):
     """CSP bottleneck with 3 convs: cv3(concat(m(cv1(x)), cv2(x))), m = n x [x (+) cv2_3x3(cv1_1x1(x))]."""
 
     def __init__(self, init, c1, c2, n=1, shortcut=True):
@@ -1012,11 +972,14 @@ class C3:
         self.cv1, self.cv2, self.cv3 = _yconv(init, c1, c_), _yconv(init, c1, c_), _yconv(init, 2 * c_, c2)
         self.m = [(_yconv(init, c_, c_, 1), _yconv(init, c_, c_, 3)) for _ in range(n)]
         self.shortcut, self.c_ = shortcut, c_
-        self._cv12 = None
-        self._pairs = None   # md_c3_pair packs of self.m (False: this width is not fused)
 
-    def modules(self):
+    def children(self):
         return [self.cv1, self.cv2, self.cv3] + [m for pair in self.m for m in pair]
+
+    def _derive(self, device):
+        self._cv12 = merged_conv([self.cv1, self.cv2], device)
+        pk = [nn_ops.pack_c3_pair(a.packed, b.packed) for a, b in self.m]
+        self._pairs = pk if all(p is not None for p in pk) else None   # md_c3_pair packs of self.m (None: this width is not fused)
 
     def __call__(self, x, x_c_off=None, out=None, c_off=0):
         """No copies: one launch computes [cv1(x) | cv2(x)] into the concat buffer; every bottleneck then updates channels [0, c_).
@@ -1024,14 +987,8 @@ class C3:
         place (a tile's halo pixels are other tiles' outputs), so the blocks alternate between two concat buffers and the last one
         carries the cv2(x) half along when it ends in the second.  Other widths: two launches per bottleneck, in place (the 1x1 reads the
         slice, the 3x3 adds the slice as residual and writes it back: each element is read and written by the same thread)."""
-        n, h, w, _ = x.shape
-        if self._cv12 is None:
-            self._cv12 = merged_conv([self.cv1, self.cv2], x.device)
         cat = nn_ops.conv2d(x, self._cv12, x_c_off=x_c_off)
-        if self._pairs is None:
-            pk = [nn_ops.pack_c3_pair(a.packed, b.packed) for a, b in self.m] if C3_PAIR_FUSED else [None]
-            self._pairs = pk if all(p is not None for p in pk) else False
-        if self._pairs:
+        if C3_PAIR_FUSED and self._pairs is not None:
             bufs = (cat, torch.empty_like(cat))   # block i reads bufs[i % 2], writes bufs[(i + 1) % 2]; cv2(x) sits in bufs[0]
             npairs = len(self._pairs)
             for i, pk in enumerate(self._pairs):
@@ -1047,12 +1004,12 @@ class C3:
         return self.cv3(cat, out=out, c_off=c_off)
 
 
-class SPPF:
+class SPPF(Module):
     def __init__(self, init, c1, c2, k=5):
         c_ = c1 // 2
         self.cv1, self.cv2, self.k, self.c_ = _yconv(init, c1, c_), _yconv(init, 4 * c_, c2), k, c_
 
-    def modules(self):
+    def children(self):
         return [self.cv1, self.cv2]
 
     def __call__(self, x, out=None, c_off=0):
@@ -1071,8 +1028,42 @@ class SPPF:
         return self.cv2(cat, out=out, c_off=c_off)
 
 
+class _YOLO(Module):
+    """What YOLOv5 and YOLOv8 share: the stem conv `b0` with its stem-layout form, and everything behind the decode."""
+
+    def _derive(self, device):
+        # the 3-channel stride-2 stem conv on the 4-channel stem layout (md_stem_conv) when the batch arrives in it
+        self.stem = nn_ops.pack_stem_conv(self.b0.weight, bn=self.b0.bn, bias=self.b0.bias, act=self.b0.act)
+        if self.stem is not None:
+            self.stem.to(device)
+
+    def _stem(self, x):
+        """x: [N,H,W,8] bf16 NHWC (3 real channels), or the batch in the stem layout ([N,H+16,W+16,4], nn_ops.to_stem_layout)."""
+        if x.shape[3] != 4:
+            return self.b0(x)
+        if self.stem is None:
+            raise nn_ops._lib.MindDetHipError("stem-layout input needs a 6x6 / 3x3 stride-2 stem conv with 32 or 64 output channels")
+        return nn_ops.stem_conv(x, self.stem)
+
+    def _detections(self, heads, boxes, scores, labels, return_aux):
+        """decoded candidates [B, total, ...] -> per image the top nms_pre, class-aware NMS, (dets [B,max_det,6], count [B])"""
+        B, total = scores.shape
+        seg = self.const((B, total), lambda: _segments(B, total, scores.device))
+        sv, si, sc = det_ops.topk_segmented(scores, seg, self.nms_pre, max_segment=total)
+        sb = det_ops.gather_rows(boxes, si, sc)
+        sl = torch.gather(labels, 1, si.long())
+        keep, kidx, num = det_ops.nms_aligned(sb, self.iou_thres, mode=det_ops.NMS_MODE_STRICT, count=sc, group=sl,
+                                              max_output=self.max_det)
+        dets, count = det_ops.pack_detections(sb, sv, sl, kidx, num, self.max_det, sel_cnt=sc,
+                                              status=self.prefix_status.tensor(B, scores.device))
+        if return_aux:
+            return dets, count, dict(heads=heads, boxes=boxes, scores=scores, labels=labels, sel_idx=si, sel_cnt=sc,
+                                     sel_boxes=sb, sel_labels=sl, keep=keep)
+        return dets, count
+
+
 @DETECTORS.register_module
-class YOLOv5:
+class YOLOv5(_YOLO):
     """YOLOv5 (Ultralytics v6/v7 layout): CSPDarknet backbone + PANet head + Detect, single-label decode and
     class-aware NMS (conf 0.25 / IoU 0.45 / max_det 300 by default).  depth_multiple/width_multiple 0.33/0.5 = yolov5s."""
     ANCHORS = ((10, 13, 16, 30, 33, 23), (30, 61, 62, 45, 59, 119), (116, 90, 156, 198, 373, 326))
@@ -1109,35 +1100,14 @@ class YOLOv5:
         self.conf_thres, self.iou_thres, self.max_det, self.nms_pre = conf_thres, iou_thres, max_det, nms_pre
         self.prefix_status = det_ops.PrefixStatus()   # sticky flags of the top-nms_pre cut (see StandardRoIHead)
         self.c = (c256, c512)
-        self._seg = {}
 
-    def conv_modules(self):
-        out = [self.b0, self.b1, self.b3, self.b5, self.b7, self.h10, self.h14, self.h18, self.h21] + self.detect
-        for blk in (self.b2, self.b4, self.b6, self.b8, self.b9, self.h13, self.h17, self.h20, self.h23):
-            out += blk.modules()
-        return out
-
-    def to(self, device):
-        for m in self.conv_modules():
-            m.to(device)
-        for blk in (self.b2, self.b4, self.b6, self.b8, self.h13, self.h17, self.h20, self.h23):
-            blk._cv12 = blk._pairs = None     # merged / fused packs are derived copies: rebuilt from the (possibly re-loaded) weights on next use
-        _packs_rebuilt(self)
-        # the 3-channel stride-2 stem conv on the 4-channel stem layout (md_stem_conv) when the batch arrives in it
-        self.stem = nn_ops.pack_stem_conv(self.b0.weight, bn=self.b0.bn, bias=self.b0.bias, act=self.b0.act)
-        if self.stem is not None:
-            self.stem.to(device)
-        return self
+    def children(self):
+        return ([self.b0, self.b1, self.b3, self.b5, self.b7, self.h10, self.h14, self.h18, self.h21] + self.detect +
+                [self.b2, self.b4, self.b6, self.b8, self.b9, self.h13, self.h17, self.h20, self.h23])
 
     def features(self, x):
-        """x: [N,H,W,8] bf16 NHWC (3 real channels), or the batch in the stem layout ([N,H+16,W+16,4], nn_ops.to_stem_layout)."""
-        if x.shape[3] == 4:
-            if self.stem is None:
-                raise nn_ops._lib.MindDetHipError("stem-layout input needs a 6x6 / 3x3 stride-2 stem conv with 32 or 64 output channels")
-            x = nn_ops.stem_conv(x, self.stem)
-        else:
-            x = self.b0(x)
-        x = self.b3(self.b2(self.b1(x)))
+        """x: see _stem"""
+        x = self.b3(self.b2(self.b1(self._stem(x))))
         # p3 / p4 are produced straight into the second half of the PAN concat buffers that consume them later
         # ([upsampled top | skip]); the next backbone conv reads them as a channel slice
         n, h, w, _ = x.shape
@@ -1181,24 +1151,13 @@ class YOLOv5:
         for h, s, anc in zip(heads, self.strides, self.ANCHORS):
             det_ops.yolo_decode(h, boxes, scores, labels, self.nc, self.na, s, anc, self.conf_thres, off, total)
             off += h.shape[1] * h.shape[2] * self.na
-        if (B, total) not in self._seg:
-            self._seg[(B, total)] = torch.arange(0, (B + 1) * total, total, dtype=torch.int32, device=dev)
-        sv, si, sc = det_ops.topk_segmented(scores, self._seg[(B, total)], self.nms_pre, max_segment=total)
-        sb = det_ops.gather_rows(boxes, si, sc)
-        sl = torch.gather(labels, 1, si.long())
-        keep, kidx, num = det_ops.nms_aligned(sb, self.iou_thres, mode=det_ops.NMS_MODE_STRICT, count=sc, group=sl,
-                                              max_output=self.max_det)
-        dets, count = det_ops.pack_detections(sb, sv, sl, kidx, num, self.max_det, sel_cnt=sc, status=self.prefix_status.tensor(B, dev))
-        if return_aux:
-            return dets, count, dict(heads=heads, boxes=boxes, scores=scores, labels=labels, sel_idx=si, sel_cnt=sc,
-                                     sel_boxes=sb, sel_labels=sl, keep=keep)
-        return dets, count
+        return self._detections(heads, boxes, scores, labels, return_aux)
 
     __call__ = forward
 
 
 # ----------------------------------------------------------------------------- YOLOv8 (BASELINE configs[3]; parity unpinned)
-class C2f:
+class C2f(Module):
     """Ultralytics C2f: cv2(concat(y0, y1, m1(y1), m2(m1(y1)), ...)) with (y0, y1) = chunk(cv1(x), 2) and m = n x
     [x (+) 3x3(3x3(x))].  cv1 is stored as its two output halves (cv1a, cv1b: the same arithmetic as one 2c-channel 1x1
     conv followed by chunk), so that y0 is written straight into the concat buffer and y1 is a compact tensor."""
@@ -1209,18 +1168,18 @@ class C2f:
         self.cv1a, self.cv1b = _yconv(init, c1, c, 1), _yconv(init, c1, c, 1)
         self.cv2 = _yconv(init, (2 + n) * c, c2, 1)
         self.m = [(_yconv(init, c, c, 3), _yconv(init, c, c, 3)) for _ in range(n)]
-        self._cv1 = None
 
-    def modules(self):
+    def children(self):
         return [self.cv1a, self.cv1b, self.cv2] + [m for pair in self.m for m in pair]
+
+    def _derive(self, device):
+        self._cv1 = merged_conv([self.cv1a, self.cv1b], device)
 
     def __call__(self, x, x_c_off=None, out=None, c_off=0):
         """No copies: one launch writes (y0 | y1) = cv1(x) into channels [0, 2c) of the concat buffer; bottleneck i reads its
         input (and its shortcut) as channels [(1+i)c, (2+i)c) of that buffer and writes [(2+i)c, (3+i)c)."""
         n, h, w, _ = x.shape
         c = self.c
-        if self._cv1 is None:
-            self._cv1 = merged_conv([self.cv1a, self.cv1b], x.device)
         cat = torch.empty((n, h, w, (2 + self.n) * c), dtype=torch.bfloat16, device=x.device)
         nn_ops.conv2d(x, self._cv1, out=cat, c_off=0, x_c_off=x_c_off)
         for i, (a, b) in enumerate(self.m):
@@ -1233,7 +1192,7 @@ class C2f:
 
 
 @DETECTORS.register_module
-class YOLOv8:
+class YOLOv8(_YOLO):
     """YOLOv8 (Ultralytics v8.0 yolov8.yaml): CSP backbone with C2f blocks + SPPF, PAN head, anchor-free Detect with DFL
     (reg_max 16); decode + class-aware NMS (conf 0.25 / IoU 0.7 / max_det 300).  depth / width / max_channels 1.0 / 1.0 / 512
     = yolov8l."""
@@ -1274,40 +1233,19 @@ class YOLOv8:
         self.strides = (8, 16, 32)
         self.conf_thres, self.iou_thres, self.max_det, self.nms_pre = conf_thres, iou_thres, max_det, nms_pre
         self.prefix_status = det_ops.PrefixStatus()   # sticky flags of the top-nms_pre cut (see StandardRoIHead)
-        self._seg = {}
-        self._stem2 = {}
-        _packs_rebuilt(self)
 
-    def conv_modules(self):
-        out = [self.b0, self.b1, self.b3, self.b5, self.b7, self.h16, self.h19]
-        for blk in (self.b2, self.b4, self.b6, self.b8, self.b9, self.h12, self.h15, self.h18, self.h21):
-            out += blk.modules()
-        for br in self.box + self.cls:
-            out += br
-        return out
+    def children(self):
+        return ([self.b0, self.b1, self.b3, self.b5, self.b7, self.h16, self.h19] +
+                [self.b2, self.b4, self.b6, self.b8, self.b9, self.h12, self.h15, self.h18, self.h21] +
+                [m for br in self.box + self.cls for m in br])
 
-    def to(self, device):
-        for m in self.conv_modules():
-            m.to(device)
-        for blk in (self.b2, self.b4, self.b6, self.b8, self.h12, self.h15, self.h18, self.h21):
-            blk._cv1 = None      # merged packs are derived copies: rebuilt from the (possibly re-loaded) weights on next use
-        self._stem2 = {}
-        _packs_rebuilt(self)
-        # the 3-channel stride-2 stem conv on the 4-channel stem layout (md_stem_conv) when the batch arrives in it
-        self.stem = nn_ops.pack_stem_conv(self.b0.weight, bn=self.b0.bn, bias=self.b0.bias, act=self.b0.act)
-        if self.stem is not None:
-            self.stem.to(device)
-        return self
+    def _derive(self, device):
+        super()._derive(device)
+        self._stem2 = [merged_conv([bx[0], cl[0]], device) for bx, cl in zip(self.box, self.cls)]   # a level's two branch stems read f once
 
     def features(self, x):
-        """x: [N,H,W,8] bf16 NHWC (3 real channels), or the batch in the stem layout ([N,H+16,W+16,4], nn_ops.to_stem_layout)."""
-        if x.shape[3] == 4:
-            if self.stem is None:
-                raise nn_ops._lib.MindDetHipError("stem-layout input needs a 6x6 / 3x3 stride-2 stem conv with 32 or 64 output channels")
-            x = nn_ops.stem_conv(x, self.stem)
-        else:
-            x = self.b0(x)
-        x = self.b3(self.b2(self.b1(x)))
+        """x: see _stem"""
+        x = self.b3(self.b2(self.b1(self._stem(x))))
         # p3 / p4 are produced straight into the PAN concat buffers that consume them later ([upsampled top | skip]); the next
         # backbone conv reads them as a channel slice
         n, h, w, _ = x.shape
@@ -1338,15 +1276,12 @@ class YOLOv8:
         self.h19(o4, out=cat21, c_off=0)
         o5 = self.h21(cat21)
         heads = []
-        for f, bx, cl in zip((o3, o4, o5), self.box, self.cls):
+        for f, bx, cl, stem2 in zip((o3, o4, o5), self.box, self.cls, self._stem2):
             n, h, w, _ = f.shape
             # (the two branch convs write every channel unless the class count needed padding to a multiple of 8: only then a zero fill)
             full = self.head_c == 4 * self.reg_max + cl[2].cout
             head = (torch.empty if full else torch.zeros)((n, h, w, self.head_c), dtype=torch.bfloat16, device=f.device)
-            key = id(bx[0])
-            if key not in self._stem2:                                      # the two branch stems read f once: one launch
-                self._stem2[key] = merged_conv([bx[0], cl[0]], f.device)
-            t = nn_ops.conv2d(f, self._stem2[key])
+            t = nn_ops.conv2d(f, stem2)                                     # the two branch stems: one launch
             bx[2](bx[1](t, x_c_off=0), out=head, c_off=0)                   # 4 * reg_max distribution logits
             cl[2](cl[1](t, x_c_off=bx[0].cout), out=head, c_off=4 * self.reg_max)   # class logits
             heads.append(head)
@@ -1363,17 +1298,7 @@ class YOLOv8:
         for h, s in zip(heads, self.strides):
             det_ops.yolov8_decode(h, boxes, scores, labels, self.nc, self.reg_max, s, self.conf_thres, off, total)
             off += h.shape[1] * h.shape[2]
-        if (B, total) not in self._seg:
-            self._seg[(B, total)] = torch.arange(0, (B + 1) * total, total, dtype=torch.int32, device=dev)
-        sv, si, sc = det_ops.topk_segmented(scores, self._seg[(B, total)], self.nms_pre, max_segment=total)
-        sb = det_ops.gather_rows(boxes, si, sc)
-        sl = torch.gather(labels, 1, si.long())
-        keep, kidx, num = det_ops.nms_aligned(sb, self.iou_thres, mode=det_ops.NMS_MODE_STRICT, count=sc, group=sl, max_output=self.max_det)
-        dets, count = det_ops.pack_detections(sb, sv, sl, kidx, num, self.max_det, sel_cnt=sc, status=self.prefix_status.tensor(B, dev))
-        if return_aux:
-            return dets, count, dict(heads=heads, boxes=boxes, scores=scores, labels=labels, sel_idx=si, sel_cnt=sc, sel_boxes=sb,
-                                     sel_labels=sl, keep=keep)
-        return dets, count
+        return self._detections(heads, boxes, scores, labels, return_aux)
 
     __call__ = forward
 

@@ -40,7 +40,18 @@ def _round_up(x, m):
 KORDER_DEFAULT = 0  # K order for multi-tap convs with Cin % 64 == 0 (see md_conv2d_attrs.korder)
 
 
-class PackedConv:
+ACT_CODES = {None: 0, False: 0, True: 1, "relu": 1, "silu": 2, 0: 0, 1: 1, 2: 2}  # md_conv2d_attrs.relu / md_stem_conv act codes
+
+
+class _PackedWB:
+    """A pack whose device operands are one weight blob `w` and one `bias`."""
+
+    def to(self, device):
+        self.w, self.bias = self.w.to(device), self.bias.to(device)
+        return self
+
+
+class PackedConv(_PackedWB):
     """Folded conv weights in the kernel's layout + the static attributes of the layer."""
 
     def __init__(self, w, bias, cin, cout, kh, kw, stride, pad, relu):
@@ -48,29 +59,30 @@ class PackedConv:
         self.cin, self.cout, self.kh, self.kw = cin, cout, kh, kw
         self.stride, self.pad, self.relu = stride, pad, relu
 
-    def to(self, device):
-        self.w, self.bias = self.w.to(device), self.bias.to(device)
-        return self
-
     def flops(self, n, ho, wo):
         return 2 * n * ho * wo * self.cout * self.cin_real * self.kh * self.kw
 
     cin_real = 0
 
 
+def _fold_bn(weight, bias, bn):
+    """Conv weight [Cout,...] + optional conv bias + eval BatchNorm (gamma, beta, mean, var, eps) or None -> (w', b') in fp32.
+    The one fold of the package: md_conv2d and the stem kernels must see the same numbers."""
+    weight = weight.detach().to(torch.float32)
+    if bn is None:
+        return weight, (bias.detach().to(torch.float32) if bias is not None else torch.zeros(weight.shape[0]))
+    gamma, beta, mean, var, eps = bn
+    scale = gamma.to(torch.float32) / torch.sqrt(var.to(torch.float32) + eps)
+    b = beta.to(torch.float32) - mean.to(torch.float32) * scale
+    if bias is not None:
+        b = b + bias.to(torch.float32) * scale
+    return weight * scale.view(-1, 1, 1, 1), b
+
+
 def pack_conv(weight, bias=None, bn=None, stride=1, pad=0, relu=False, cin_pad_to=8, cout_pad_to=8, korder=None):
     """weight [Cout,Cin,kh,kw] fp32 (torch, any device). bn = (gamma, beta, mean, var, eps) or None."""
-    weight = weight.detach().to(torch.float32)
     cout, cin, kh, kw = weight.shape
-    if bn is not None:
-        gamma, beta, mean, var, eps = bn
-        scale = gamma.to(torch.float32) / torch.sqrt(var.to(torch.float32) + eps)
-        weight = weight * scale.view(-1, 1, 1, 1)
-        b = beta.to(torch.float32) - mean.to(torch.float32) * scale
-        if bias is not None:
-            b = b + bias.to(torch.float32) * scale
-    else:
-        b = bias.detach().to(torch.float32) if bias is not None else torch.zeros(cout)
+    weight, b = _fold_bn(weight, bias, bn)
     cin_p = _round_up(cin, cin_pad_to)
     cout_o = _round_up(cout, cout_pad_to)           # channels the output tensor carries
     cout_p = _round_up(cout_o, cout_tile(cout_o))    # rows of the packed weight
@@ -89,8 +101,7 @@ def pack_conv(weight, bias=None, bn=None, stride=1, pad=0, relu=False, cin_pad_t
     wk[:, :k_real] = wp.reshape(cout_p, k_real)
     bp = torch.zeros((cout_p,), dtype=torch.float32, device=weight.device)
     bp[:cout] = b.to(weight.device)
-    act = {None: 0, False: 0, True: 1, "relu": 1, "silu": 2, 0: 0, 1: 1, 2: 2}[relu]  # md_conv2d_attrs.relu codes
-    pc = PackedConv(wk.to(torch.bfloat16).contiguous(), bp.contiguous(), cin_p, cout_o, kh, kw, stride, pad, act)
+    pc = PackedConv(wk.to(torch.bfloat16).contiguous(), bp.contiguous(), cin_p, cout_o, kh, kw, stride, pad, ACT_CODES[relu])
     pc.cin_real = cin
     pc.korder = korder
     return pc
@@ -414,30 +425,17 @@ def upsample2x(src, dst=None, c0=0, src_c0=0, width=None):
 STEM_PAD_LO, STEM_PAD_HI = 7, 9
 
 
-class PackedStem:
+class PackedStem(_PackedWB):
     def __init__(self, w, bias):
         self.w, self.bias = w, bias
-
-    def to(self, device):
-        self.w, self.bias = self.w.to(device), self.bias.to(device)
-        return self
 
 
 def pack_stem(weight, bn=None, bias=None):
     """weight [64,3,7,7] fp32 (+ eval BatchNorm) -> md_stem_pool operands: w [64, 224] bf16 with K = (ky, kx 0..7, c 0..3)."""
-    weight = weight.detach().to(torch.float32)
     cout, cin, kh, kw = weight.shape
     if (cout, kh, kw) != (64, 7, 7) or cin > 3:
         raise _lib.MindDetHipError("pack_stem: expects a [64, <=3, 7, 7] stem convolution")
-    if bn is not None:
-        gamma, beta, mean, var, eps = bn
-        scale = gamma.to(torch.float32) / torch.sqrt(var.to(torch.float32) + eps)
-        weight = weight * scale.view(-1, 1, 1, 1)
-        b = beta.to(torch.float32) - mean.to(torch.float32) * scale
-        if bias is not None:
-            b = b + bias.to(torch.float32) * scale
-    else:
-        b = bias.detach().to(torch.float32) if bias is not None else torch.zeros(cout)
+    weight, b = _fold_bn(weight, bias, bn)
     wp = torch.zeros((64, 7, 8, 4), dtype=torch.float32)
     wp[:, :, :7, :cin] = weight.permute(0, 2, 3, 1)
     return PackedStem(wp.reshape(64, 224).to(torch.bfloat16).contiguous(), b.contiguous())
@@ -447,37 +445,23 @@ class _StemConvAttrs(ctypes.Structure):
     _fields_ = [("kh", ctypes.c_int32), ("act", ctypes.c_int32)]
 
 
-class PackedStemConv:
+class PackedStemConv(_PackedWB):
     def __init__(self, w, bias, kh, act, cout):
         self.w, self.bias, self.kh, self.act, self.cout = w, bias, kh, act, cout
-
-    def to(self, device):
-        self.w, self.bias = self.w.to(device), self.bias.to(device)
-        return self
 
 
 def pack_stem_conv(weight, bn=None, bias=None, act=None):
     """weight [Cout, <=3, k, k] fp32 (+ eval BatchNorm) of a stride-2 stem conv with k = 6 (pad 2) or k = 3 (pad 1), Cout 32 or 64
     -> md_stem_conv operands, or None when the layer is not one it takes.  K = (ky, kx', c 0..3): k = 6 -> kx' = kx + 1 in 0..7,
     k = 3 -> kx' = kx in 0..3."""
-    weight = weight.detach().to(torch.float32)
     cout, cin, kh, kw = weight.shape
     if kh != kw or kh not in (6, 3) or cin > 3 or cout not in (32, 64):
         return None
-    if bn is not None:
-        gamma, beta, mean, var, eps = bn
-        scale = gamma.to(torch.float32) / torch.sqrt(var.to(torch.float32) + eps)
-        weight = weight * scale.view(-1, 1, 1, 1)
-        b = beta.to(torch.float32) - mean.to(torch.float32) * scale
-        if bias is not None:
-            b = b + bias.to(torch.float32) * scale
-    else:
-        b = bias.detach().to(torch.float32) if bias is not None else torch.zeros(cout)
+    weight, b = _fold_bn(weight, bias, bn)
     kx, x0 = (8, 1) if kh == 6 else (4, 0)
     wp = torch.zeros((cout, kh, kx, 4), dtype=torch.float32)
     wp[:, :, x0:x0 + kw, :cin] = weight.permute(0, 2, 3, 1)
-    code = {None: 0, False: 0, True: 1, "relu": 1, "silu": 2, 0: 0, 1: 1, 2: 2}[act]
-    return PackedStemConv(wp.reshape(cout, kh * kx * 4).to(torch.bfloat16).contiguous(), b.contiguous(), kh, code, cout)
+    return PackedStemConv(wp.reshape(cout, kh * kx * 4).to(torch.bfloat16).contiguous(), b.contiguous(), kh, ACT_CODES[act], cout)
 
 
 def stem_conv(x4, ps):
@@ -559,7 +543,7 @@ class _GroupedAttrs(ctypes.Structure):
                 ("y_off", ctypes.c_int32 * GROUPED_MAX_GROUPS), ("w_row", ctypes.c_int32 * GROUPED_MAX_GROUPS)]
 
 
-class PackedGrouped:
+class PackedGrouped(_PackedWB):
     """The folded weights of G narrow convs on consecutive 64-channel input slices as md_conv2d_grouped consumes them: one [R, k*k*64]
     bf16 buffer (group g's rows from w_row[g], K order (tap, ci)), bias [R] f32, and each group's output channel offset."""
 
@@ -567,10 +551,6 @@ class PackedGrouped:
         self.w, self.bias, self.k, self.relu = w, bias, k, relu
         self.couts, self.w_rows, self.y_offs = list(couts), list(w_rows), list(y_offs)
         self.groups, self.cin_g = len(self.couts), 64
-
-    def to(self, device):
-        self.w, self.bias = self.w.to(device), self.bias.to(device)
-        return self
 
     def flops(self, n, h, w):
         """2 N H W sum_g cout_g cin_g k^2 (the useful work; the kernel pads each group's couts to a 16-row MFMA tile)"""

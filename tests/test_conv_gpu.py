@@ -428,7 +428,7 @@ def test_resnet_with_fused_blocks_equals_layer_by_layer():
     try:
         graphs.FUSE_BLOCKS = graphs.FUSE_DUAL = True
         fused = bb(xb)
-        assert all(b._fused is not None for b in bb.stages[0]) and all(b._fused in (None, False) for st in bb.stages[1:] for b in st)
+        assert all(b._fused is not None for b in bb.stages[0]) and all(b._fused is None for st in bb.stages[1:] for b in st)
         assert all(st[0]._dual is not None for st in bb.stages[1:])
         graphs.FUSE_BLOCKS = graphs.FUSE_DUAL = False
         plain = bb(xb)

@@ -51,10 +51,10 @@ def test_split_forward_is_bit_identical_tiny(cfgp, hw):
 
 @pytest.mark.parametrize("cfgp,hw", [("configs/faster_rcnn/faster_rcnn_tiny.py", (128, 192)), ("configs/yolov8/yolov8_tiny.py", (128, 160))])
 def test_split_forward_after_weight_reload(cfgp, hw):
-    """r03 ADVICE: .to() after a weight change drops the lazily built packs (fused blocks, merged convs); the pass that rebuilds them must be a
-    single-stream one again -- the priming key carries the model's pack generation"""
+    """r03 ADVICE: .to() after a weight change makes new packs (fused blocks, merged convs included) and drops the device constants; the pass
+    that builds those again must be a single-stream one -- the priming key carries the pack generation"""
     from minddet.models import Config, build_detector
-    from minddet_amd.graphs import SplitForward
+    from minddet_amd.graphs import Module, SplitForward
 
     cfg = Config.fromfile(cfgp)
     m = build_detector(cfg.model, cfg.train_cfg, cfg.test_cfg).to(DEV)
@@ -62,11 +62,11 @@ def test_split_forward_after_weight_reload(cfgp, hw):
     sp = SplitForward(m, 2)
     before = sp(x)
     torch.cuda.synchronize()
-    gen0, n_primed = m._pack_gen, len(sp._primed)
+    gen0, n_primed = Module.generation, len(sp._primed)
     for mod in m.conv_modules():          # new weights in every conv
         mod.weight = mod.weight * 0.5 + 0.01
     m.to(DEV)
-    assert m._pack_gen == gen0 + 1
+    assert Module.generation != gen0
     out = sp(x)                            # must prime again (new key), then fork
     torch.cuda.synchronize()
     assert len(sp._primed) == n_primed + 1

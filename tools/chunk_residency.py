@@ -12,7 +12,7 @@ N = int(sys.argv[1]) if len(sys.argv) > 1 else 60
 dev = "cuda:0"
 net = graphs.ResNet(50).to(dev)
 x = nn_ops.to_stem_layout(synthetic_images(N, 800, 1344, device=dev))
-net(x[:2])   # packs the fused blocks
+net(x[:2])   # warm-up
 torch.cuda.synchronize()
 
 

@@ -31,6 +31,19 @@
  *   - return 0 on success; non-zero on failure (iou-bev-nms-org.cpp:238,282): 1 = wrong
  *     nparam, 2 = bad dtype/shape, 3 = HIP runtime error, 4 = unsupported size.  No
  *     exceptions, no stdout, no exit().
+ *   - argument checks (one layer for every op, md::Args in csrc/aot.h).  They COMPLETE before the op makes any device or runtime
+ *     call, so a refused call has touched nothing, and they read host memory only (never through a pointer of params[]):
+ *       nparam comes first: outside the op's set -> 1, whatever else is wrong with the call;
+ *       then, all -> 2: params == NULL; extra == NULL where the op says "required"; for every operand that is not optional:
+ *       ndims == NULL, shapes == NULL, shapes[i] == NULL, a rank or extent other than the op documents, a dtypes[i] other than
+ *       documented; then the op's own attribute checks;
+ *       then -> 4, the size limits the op documents; a call with defects of both kinds returns 2 or 4, 2 where the defect is one
+ *       of the descriptor checks above.
+ *     dtypes may be NULL and so may any dtypes[i]: an undescribed dtype passes.  An operand documented "or NULL" / "may be NULL"
+ *     is optional: with params[i] == NULL nothing else about it is looked at.  The five reference-ABI ops below also accept
+ *     shapes[i] == NULL for thresh and for their outputs (shapes a caller does not describe are not checked).  With work to
+ *     do, the data pointer of every non-empty required operand must be non-NULL (2); a call without work (an empty batch)
+ *     returns 0 whatever the pointers are.
  *   - re-entrant; safe to call from several host threads on different streams.  Process-lifetime
  *     data: per-thread diagnostics counters (md_conv2d_last_kernel / md_conv2d_launch_count), a
  *     "LDS size attribute set" cache per kernel and device, and the scratch pool above -- each
@@ -269,12 +282,16 @@ int md_bottleneck(MD_AOT_ARGS);
 
 /* The Bottleneck of a YOLOv5 C3 block (build-authored model of BASELINE configs[1]; the reference names the family only,
  * README.md:5-14) in ONE launch:  y[.., y_c_off : +C] = x[.., x_c_off : +C] (if shortcut) + silu(conv3x3(silu(conv1x1(x[.., x_c_off : +C])))),
- * C = 64 or 128 channels in and out, BN folded, stride 1 / pad 1; the C-channel intermediate stays in LDS.  Same arithmetic as the two
+ * C = 32, 64 or 128 channels in and out, BN folded, stride 1 / pad 1; the C-channel intermediate stays in LDS.  Same arithmetic as the two
  * md_conv2d launches it replaces (bf16 operands, fp32 accumulation in the same K order, the intermediate and the pre-shortcut value
  * rounded to bf16): bit-identical to them.  With pass_through the next C channels of x are copied to the next C channels of y (the
  * cv2(x) half of the C3 concat buffer travels with the result).  x and y must not overlap: MD_ERR_ARG.
- * in : x[N,H,W,XC] bf16, w1[C,C] bf16, b12[2C] f32 (conv1's biases, then conv2's), w2[C,9C] bf16 (md_conv2d's korder-1 layout:
- *      K = (ci / 64) * 576 + tap * 64 + ci % 64);  out: y[N,H,W,YC] bf16.   extra: md_c3_pair_attrs (required). */
+ * in : x[N,H,W,XC] bf16, w1[C, roundup(C, 64)] bf16, b12[2C] f32 (conv1's biases, then conv2's), w2[C, roundup(9C, 64)] bf16 -- the
+ *      weights as md_conv2d packs them (K zero-padded to a multiple of 64):
+ *        C = 32 : w1[32, 64],   w2[32, 320],   korder 0: K = tap * 32 + ci;
+ *        C = 64 : w1[64, 64],   w2[64, 576],   K = tap * 64 + ci (korder 0 and 1 coincide);
+ *        C = 128: w1[128, 128], w2[128, 1152], korder 1: K = (ci / 64) * 576 + tap * 64 + ci % 64;
+ *      out: y[N,H,W,YC] bf16.   extra: md_c3_pair_attrs (required). */
 typedef struct md_c3_pair_attrs {
     int32_t x_c_off;       /* first channel of x the pair reads (multiple of 8) */
     int32_t y_c_off;       /* first channel of y it writes (multiple of 8) */

@@ -6,6 +6,8 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <initializer_list>
+
 #include "../../include/minddet_hip.h"
 
 #define MD_HIP_TRY(expr)                       \
@@ -51,24 +53,86 @@
 
 namespace md {
 
-static inline bool dtype_is(const char **dtypes, int i, const char *want) {
-    // dtypes may be NULL when the caller (e.g. a plain C test) does not describe tensors.
-    if (!dtypes || !dtypes[i]) return true;
-    return strcmp(dtypes[i], want) == 0;
-}
+// Args: the one argument-check layer of every AOT entry point (the rule is stated once, in include/minddet_hip.h "Conventions").
+// A view over (nparam, params, ndims, shapes, dtypes) that is built, filled with the op's operands and asked for rc() BEFORE the
+// entry point makes any device or runtime call.  The first failure latches its code; every accessor is safe whatever the caller passed:
+// d() / numel() answer -1 for an operand that tensor() / optional() did not accept, and never index past ndims[i].
+constexpr int ANY = -1;   // tensor(i, dtype, ANY): any rank
+constexpr const char *F32 = "float32", *BF16 = "bfloat16", *I32 = "int32", *I64 = "int64", *U8 = "uint8";
+struct Args {
+    int nparam; void **params; int *ndims; int64_t **shapes; const char **dtypes;
+    int err = MD_OK;
+    unsigned ok = 0;      // bit i: operand i is described (ndims[i], shapes[i]) and was accepted
 
-static inline int64_t dim(int *ndims, int64_t **shapes, int i, int d) {
-    if (!ndims || !shapes || !shapes[i]) return -1;
-    if (d < 0) d += ndims[i];
-    if (d < 0 || d >= ndims[i]) return -1;
-    return shapes[i][d];
-}
+    // nparam in [lo, hi] (hi - lo trailing operands, e.g. the workspace, may be left out) and a params array
+    Args(int np, void **p, int *nd, int64_t **sh, const char **dt, int lo, int hi) : nparam(np), params(p), ndims(nd), shapes(sh), dtypes(dt) {
+        if (np < lo || np > hi) err = MD_ERR_NPARAM;
+        else if (!p) err = MD_ERR_ARG;
+    }
+    int rc() const { return err; }
+    bool require(bool cond, int code = MD_ERR_ARG) {
+        if (!cond && !err) err = code;
+        return cond;
+    }
+    // the op's attribute struct; an op that requires it reads this pointer only after rc() == 0
+    template <typename T> const T *attrs(const void *extra) { require(extra != nullptr); return (const T *)extra; }
+    // required operand i: described, of rank in [rank, rank_hi] (ANY = not looked at), of dtype `dt` where the caller names one
+    // (dtypes == NULL or dtypes[i] == NULL passes, dt == nullptr = not looked at)
+    bool tensor(int i, const char *dt, int rank = ANY, int rank_hi = ANY) {
+        if (err) return false;
+        if (i < 0 || i >= nparam || i >= 32 || !ndims || !shapes || !shapes[i] || ndims[i] < 0) return require(false);
+        if (rank != ANY && (ndims[i] < rank || ndims[i] > (rank_hi == ANY ? rank : rank_hi))) return require(false);
+        if (dt && dtypes && dtypes[i] && strcmp(dtypes[i], dt) != 0) return require(false);
+        ok |= 1u << i;
+        return true;
+    }
+    // operand of the five reference-ABI ops whose shape the caller may leave out (shapes[i] == NULL: numel(i) is then -1)
+    bool loose(int i, const char *dt) {
+        const bool described = i >= 0 && i < nparam && ndims && shapes && shapes[i];
+        if (described) return tensor(i, dt);
+        return require(i >= 0 && i < nparam && !(dt && dtypes && dtypes[i] && strcmp(dtypes[i], dt) != 0));
+    }
+    // operand whose pointer may be NULL (or that lies past nparam): then nothing else is looked at
+    bool optional(int i, const char *dt, int rank = ANY, int rank_hi = ANY) { return !given(i) || tensor(i, dt, rank, rank_hi); }
+    bool given(int i) const { return !err && i >= 0 && i < nparam && params[i] != nullptr; }
+    int rank(int i) const { return i >= 0 && i < 32 && (ok >> i & 1) ? ndims[i] : -1; }
+    // extent k of operand i; k < 0 counts from the last
+    int64_t d(int i, int k) const {
+        const int nd = rank(i);
+        if (k < 0) k += nd;
+        return k >= 0 && k < nd ? shapes[i][k] : -1;
+    }
+    int64_t numel(int i) const { return rank(i) < 0 ? -1 : prod(i); }
+    // bytes of the caller's workspace operand, -1 when it is absent (the scratch pool then serves) or not described
+    int64_t workspace(int i) const { return i < nparam && params[i] && ndims && shapes && shapes[i] ? prod(i) : -1; }
+    int64_t prod(int i) const {
+        int64_t n = 1;
+        for (int k = 0; k < ndims[i]; ++k) n *= shapes[i][k];
+        return n;
+    }
+    // operands i, j agree in rank and every extent
+    bool same_shape(int i, int j) const {
+        bool same = rank(i) >= 0 && rank(i) == rank(j);
+        for (int k = 0; same && k < rank(i); ++k) same = shapes[i][k] == shapes[j][k];
+        return same;
+    }
+    template <typename T> T *ptr(int i) const { return i >= 0 && i < nparam && !err ? (T *)params[i] : nullptr; }
+    // the data pointers an op with non-zero work dereferences: non-NULL, except for an operand described as empty
+    bool have(std::initializer_list<int> idx) {
+        for (int i : idx)
+            if (!given(i) && numel(i) != 0) return require(false);
+        return !err;
+    }
+};
+#define MD_ARGS nparam, params, ndims, shapes, dtypes
 
-static inline int64_t numel(int *ndims, int64_t **shapes, int i) {
-    if (!ndims || !shapes || !shapes[i]) return -1;
-    int64_t n = 1;
-    for (int d = 0; d < ndims[i]; ++d) n *= shapes[i][d];
-    return n;
+static inline bool fits_i32(long long x) { return x <= 0x7fffffffLL; }
+// the one launch epilogue: the launches of the call were accepted by the runtime
+static inline int launched() { return hipGetLastError() == hipSuccess ? MD_OK : MD_ERR_HIP; }
+// grid of a 1-D grid-stride kernel over `total` elements, 256 per workgroup, at most `cap` workgroups
+static inline unsigned grid1d(size_t total, size_t cap = 16384) {
+    const size_t b = (total + 255) / 256;
+    return (unsigned)(b > cap ? cap : (b == 0 ? 1 : b));
 }
 
 // pool buffers grow in 1 MiB steps, doubling: few regrowths even when the first calls are small
@@ -138,14 +202,13 @@ struct Scratch {
     void *ptr = nullptr;
     bool owned = false;     // true: more than 64 (device, stream) pairs are live -- a one-call stream-ordered allocation
     hipStream_t stream = nullptr;
-    int acquire(size_t bytes, int nparam, void **params, int *ndims, int64_t **shapes, int ws_index,
-                hipStream_t s) {
+    int acquire(size_t bytes, const Args &a, int ws_index, hipStream_t s) {
         stream = s;
         if (bytes == 0) bytes = 16;
-        if (ws_index < nparam && params[ws_index]) {
-            int64_t have = numel(ndims, shapes, ws_index);
+        if (ws_index < a.nparam && a.params[ws_index]) {
+            int64_t have = a.workspace(ws_index);
             if (have >= 0 && (size_t)have < bytes) return MD_ERR_SIZE;
-            ptr = params[ws_index];
+            ptr = a.params[ws_index];
             owned = false;
             return MD_OK;
         }

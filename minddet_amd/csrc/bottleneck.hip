@@ -554,29 +554,22 @@ extern "C" int md_diag_set_bn_stamp_buffer(void *p) { g_bn_stamp_buf = (unsigned
 // residual source: wd given (Cin == 64, residual NULL) -> the downsample conv wd . x + bd computed in the launch; residual given ->
 // that tensor; neither (Cin == 256) -> x itself.
 extern "C" int md_bottleneck(MD_AOT_ARGS) {
-    if (nparam != 10) return MD_ERR_NPARAM;
-    if (!params || !ndims || !shapes) return MD_ERR_ARG;
-    for (int i : {0, 1, 3, 4, 9})
-        if (!dtype_is(dtypes, i, "bfloat16")) return MD_ERR_ARG;
-    for (int i : {2, 5})
-        if (!dtype_is(dtypes, i, "float32")) return MD_ERR_ARG;
-    if (params[6] && !dtype_is(dtypes, 6, "bfloat16")) return MD_ERR_ARG;
-    if (ndims[0] != 4 || ndims[9] != 4 || ndims[1] != 2 || ndims[3] != 2 || ndims[4] != 2) return MD_ERR_ARG;
-    const int64_t N = shapes[0][0], H = shapes[0][1], W = shapes[0][2], Cin = shapes[0][3];
-    if ((Cin != 64 && Cin != 256) || shapes[1][0] != 64 || shapes[1][1] != Cin || shapes[3][0] != 64 || shapes[3][1] != 576 ||
-        shapes[4][0] != 256 || shapes[4][1] != 64 || numel(ndims, shapes, 2) != 128 || numel(ndims, shapes, 5) < 256)
-        return MD_ERR_ARG;
-    if (shapes[9][0] != N || shapes[9][1] != H || shapes[9][2] != W || shapes[9][3] != 256) return MD_ERR_ARG;
-    if (params[7]) {   // fused downsample conv
-        if (params[6] || !params[8] || Cin != 64 || !dtype_is(dtypes, 7, "bfloat16") || !dtype_is(dtypes, 8, "float32") || ndims[7] != 2 ||
-            shapes[7][0] != 256 || shapes[7][1] != 64 || numel(ndims, shapes, 8) < 256)
-            return MD_ERR_ARG;
-    } else if (params[6]) {
-        if (ndims[6] != 4 || numel(ndims, shapes, 6) != N * H * W * 256) return MD_ERR_ARG;
-    } else if (Cin != 256) return MD_ERR_ARG;
+    Args g(MD_ARGS, 10, 10);
+    g.tensor(0, BF16, 4); g.tensor(1, BF16, 2); g.tensor(2, F32); g.tensor(3, BF16, 2); g.tensor(4, BF16, 2); g.tensor(5, F32);
+    g.optional(6, BF16, 4); g.tensor(9, BF16, 4);
+    const int64_t N = g.d(0, 0), H = g.d(0, 1), W = g.d(0, 2), Cin = g.d(0, 3);
+    g.require((Cin == 64 || Cin == 256) && g.d(1, 0) == 64 && g.d(1, 1) == Cin && g.d(3, 0) == 64 && g.d(3, 1) == 576 &&
+              g.d(4, 0) == 256 && g.d(4, 1) == 64 && g.numel(2) == 128 && g.numel(5) >= 256);
+    g.require(g.d(9, 0) == N && g.d(9, 1) == H && g.d(9, 2) == W && g.d(9, 3) == 256);
+    if (g.given(7)) {   // fused downsample conv
+        g.tensor(7, BF16, 2); g.tensor(8, F32);
+        g.require(!g.given(6) && g.given(8) && Cin == 64 && g.d(7, 0) == 256 && g.d(7, 1) == 64 && g.numel(8) >= 256);
+    } else if (g.given(6)) {
+        g.require(g.numel(6) == N * H * W * 256);
+    } else g.require(Cin == 256);
+    if (int rc = g.rc()) return rc;
     if (N * H * W == 0) return MD_OK;
-    for (int i : {0, 1, 2, 3, 4, 5, 9})
-        if (!params[i]) return MD_ERR_ARG;
+    if (!g.have({0, 1, 2, 3, 4, 5, 9})) return MD_ERR_ARG;
     if (H > 32000 || W > 32000) return MD_ERR_SIZE;
     const long long x_img = H * W * Cin * 2;
     if (x_img >= 0x7fff0000LL) return MD_ERR_SIZE;
@@ -618,6 +611,5 @@ extern "C" int md_bottleneck(MD_AOT_ARGS) {
         hipLaunchKernelGGL(k, dim3((unsigned)(a.pt_per_xcd * 8)), dim3(512), bn_lds, (hipStream_t)stream, a);
         md_note_conv_kernel(MD_CONV_KERNEL_BOTTLENECK);
     }
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+    return launched();
 }

@@ -536,24 +536,20 @@ extern "C" int md_diag_set_c3_stamp_buffer(void *p) { g_c3_stamp_buf = (unsigned
 // out: y[N,H,W,YC] bf16 -- another buffer than x (a workgroup's halo pixels are other workgroups' outputs)
 // extra: md_c3_pair_attrs (required)
 extern "C" int md_c3_pair(MD_AOT_ARGS) {
-    if (nparam != 5) return MD_ERR_NPARAM;
-    if (!params || !ndims || !shapes || !extra) return MD_ERR_ARG;
-    for (int i : {0, 1, 3, 4})
-        if (!dtype_is(dtypes, i, "bfloat16")) return MD_ERR_ARG;
-    if (!dtype_is(dtypes, 2, "float32")) return MD_ERR_ARG;
-    if (ndims[0] != 4 || ndims[4] != 4 || ndims[1] != 2 || ndims[3] != 2) return MD_ERR_ARG;
-    const md_c3_pair_attrs *at = (const md_c3_pair_attrs *)extra;
-    const int64_t N = shapes[0][0], H = shapes[0][1], W = shapes[0][2], XC = shapes[0][3], YC = shapes[4][3];
-    const int64_t C = shapes[1][0];
+    Args g(MD_ARGS, 5, 5);
+    const md_c3_pair_attrs *at = g.attrs<md_c3_pair_attrs>(extra);
+    g.tensor(0, BF16, 4); g.tensor(1, BF16, 2); g.tensor(2, F32); g.tensor(3, BF16, 2); g.tensor(4, BF16, 4);
+    const int64_t N = g.d(0, 0), H = g.d(0, 1), W = g.d(0, 2), XC = g.d(0, 3), YC = g.d(4, 3);
+    const int64_t C = g.d(1, 0);
     const int64_t k1 = (C + 63) / 64 * 64, k2 = (9 * C + 63) / 64 * 64;   // md_conv2d pads the packed K to a multiple of 64
-    if ((C != 32 && C != 64 && C != 128) || shapes[1][1] != k1 || shapes[3][0] != C || shapes[3][1] != k2 || numel(ndims, shapes, 2) != 2 * C) return MD_ERR_ARG;
-    if (shapes[4][0] != N || shapes[4][1] != H || shapes[4][2] != W) return MD_ERR_ARG;
+    g.require((C == 32 || C == 64 || C == 128) && g.d(1, 1) == k1 && g.d(3, 0) == C && g.d(3, 1) == k2 && g.numel(2) == 2 * C);
+    g.require(g.d(4, 0) == N && g.d(4, 1) == H && g.d(4, 2) == W);
+    if (int rc = g.rc()) return rc;
     const int64_t span = at->pass_through ? 2 * C : C;
     if (at->x_c_off < 0 || at->y_c_off < 0 || at->x_c_off % 8 || at->y_c_off % 8 || XC % 8 || YC % 8 || at->x_c_off + span > XC || at->y_c_off + span > YC)
         return MD_ERR_ARG;
     if (N * H * W == 0) return MD_OK;
-    for (int i = 0; i < 5; ++i)
-        if (!params[i]) return MD_ERR_ARG;
+    if (!g.have({0, 1, 2, 3, 4})) return MD_ERR_ARG;
     {   // x and y must not overlap (see above)
         const char *xb = (const char *)params[0], *yb = (const char *)params[4];
         const long long xn = N * H * W * XC * 2, yn = N * H * W * YC * 2;
@@ -568,7 +564,7 @@ extern "C" int md_c3_pair(MD_AOT_ARGS) {
     a.x_off = at->x_c_off; a.y_off = at->y_c_off; a.shortcut = at->shortcut ? 1 : 0; a.pass = at->pass_through ? 1 : 0;
     a.tiles_x = (int)((W + CP_TW - 1) / CP_TW); a.tiles_y = (int)((H + CP_TH - 1) / CP_TH);
     const long long n_tiles = N * a.tiles_x * a.tiles_y;
-    if (n_tiles > 0x7fffffffLL / 8) return MD_ERR_SIZE;
+    if (!fits_i32(n_tiles * 8)) return MD_ERR_SIZE;
     a.n_tiles = (int)n_tiles;
     a.pt_per_xcd = (a.n_tiles + 7) / 8;
     a.x_bytes = (unsigned)(N * H * W * XC * 2);
@@ -583,6 +579,5 @@ extern "C" int md_c3_pair(MD_AOT_ARGS) {
     if (ensure_dyn_lds((const void *)k, lds) != MD_OK) return MD_ERR_HIP;
     hipLaunchKernelGGL(k, dim3((unsigned)(a.pt_per_xcd * 8)), dim3(C == 32 ? 256 : 512), lds, (hipStream_t)stream, a);
     md_note_conv_kernel(MD_CONV_KERNEL_C3_PAIR);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+    return launched();
 }

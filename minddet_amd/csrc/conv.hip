@@ -1977,23 +1977,22 @@ static int plan_call(const ConvCall &c, bool head, int sub, ConvPlan &p) {
 // ---- validate: the argument checks of each op, filling a ConvCall
 
 static int validate_conv2d(int nparam, void **params, int *ndims, int64_t **shapes, const char **dtypes, const void *extra, ConvCall &c) {
-    if (nparam != 5) return MD_ERR_NPARAM;
-    if (!params || !extra || !params[1] || !params[2]) return MD_ERR_ARG;  // x / y may be null for an empty batch
-    if (!dtype_is(dtypes, 0, "bfloat16") || !dtype_is(dtypes, 1, "bfloat16") || !dtype_is(dtypes, 2, "float32") ||
-        !dtype_is(dtypes, 4, "bfloat16"))
-        return MD_ERR_ARG;
-    if (!ndims || !shapes || ndims[0] != 4 || ndims[1] != 2 || ndims[4] != 4) return MD_ERR_ARG;
-    const md_conv2d_attrs *at = (const md_conv2d_attrs *)extra;
+    // in: x[N,H,W,Cin] bf16, w[Cout_pad,Kpad] bf16, bias[Cout_pad] f32, residual bf16 (rank 4) | NULL ; out: y[N,Ho,Wo,Cout] bf16
+    Args g(MD_ARGS, 5, 5);
+    const md_conv2d_attrs *at = g.attrs<md_conv2d_attrs>(extra);
+    g.tensor(0, BF16, 4); g.tensor(1, BF16, 2); g.tensor(2, F32); g.optional(3, BF16, 4); g.tensor(4, BF16, 4);
+    g.require(g.given(1) && g.given(2));  // x / y may be null for an empty batch
+    if (int rc = g.rc()) return rc;
     if (at->reserved0 != 0) return MD_ERR_ARG;
     c = ConvCall{};
     c.tn = resolve_tune(&at->tune);
     // The LDS-DMA kernels address the activation tensor with 32-bit byte offsets.  A batch whose input (or output /
     // residual, which the kernels address with 64-bit math but the same image split applies to) exceeds 2 GiB is run
     // as consecutive image chunks on the same stream: every tensor of the call is sliced along N.
-    const long long n_img = shapes[0][0], x_img = shapes[0][1] * shapes[0][2] * shapes[0][3] * 2;
+    const long long n_img = g.d(0, 0), x_img = g.d(0, 1) * g.d(0, 2) * g.d(0, 3) * 2;
     c.per = n_img;
-    if (n_img > 1 && x_img > 0 && x_img < c.tn.chunk_limit && n_img * x_img >= c.tn.chunk_limit && shapes[4][0] == n_img &&
-        (!params[3] || (ndims[3] == 4 && shapes[3][0] == n_img))) {
+    if (n_img > 1 && x_img > 0 && x_img < c.tn.chunk_limit && n_img * x_img >= c.tn.chunk_limit && g.d(4, 0) == n_img &&
+        (!params[3] || g.d(3, 0) == n_img)) {
         const long long per_max = c.tn.chunk_limit / x_img;          // images a chunk may hold (>= 1)
         const long long n_chunks = (n_img + per_max - 1) / per_max;
         c.per = (n_img + n_chunks - 1) / n_chunks;                    // even split: no tiny last chunk
@@ -2004,7 +2003,7 @@ static int validate_conv2d(int nparam, void **params, int *ndims, int64_t **shap
     a.bias = (const float *)params[2];
     a.res = (const uint16_t *)params[3];
     a.y = (uint16_t *)params[4];
-    a.N = (int)shapes[0][0]; a.H = (int)shapes[0][1]; a.W = (int)shapes[0][2]; a.Cin = (int)shapes[0][3];
+    a.N = (int)g.d(0, 0); a.H = (int)g.d(0, 1); a.W = (int)g.d(0, 2); a.Cin = (int)g.d(0, 3);
     // channel-slice operands: x = channels [x_c_off, x_c_off + x_cin) of the [N,H,W,Xs] tensor; residual = channels
     // [res_c_off, res_c_off + Cout) of a [N,Ho,Wo,Rs] tensor (res_slice)
     a.Xs = a.Cin; a.Rs = 0;
@@ -2014,7 +2013,7 @@ static int validate_conv2d(int nparam, void **params, int *ndims, int64_t **shap
         if (a.x) a.x += at->x_c_off;
         c.x_off = at->x_c_off;
     } else if (at->x_c_off != 0) return MD_ERR_ARG;
-    a.Hf = (int)shapes[4][1]; a.Wf = (int)shapes[4][2]; a.Ctot = (int)shapes[4][3];
+    a.Hf = (int)g.d(4, 1); a.Wf = (int)g.d(4, 2); a.Ctot = (int)g.d(4, 3);
     a.kh = at->kh; a.kw = at->kw; a.stride = at->stride; a.pad = at->pad; a.relu = at->relu;
     if (a.kh < 1 || a.kw < 1 || a.stride < 1 || a.pad < 0 || a.relu < 0 || a.relu > 2) return MD_ERR_ARG;
     a.adv = at->adv != 0;
@@ -2042,59 +2041,57 @@ static int validate_conv2d(int nparam, void **params, int *ndims, int64_t **shap
         // every written element must lie inside the output tensor
         if ((a.Ho - 1) * a.os + a.oy >= a.Hf || (a.Wo - 1) * a.os + a.ox >= a.Wf || a.c_off + a.Cout > a.Ctot) return MD_ERR_ARG;
     }
-    if (a.Cin % 8 || a.Cout % 8 || a.Ctot % 8 || shapes[4][0] != a.N) return MD_ERR_ARG;
+    if (a.Cin % 8 || a.Cout % 8 || a.Ctot % 8 || g.d(4, 0) != a.N) return MD_ERR_ARG;
     a.Kreal = a.kh * a.kw * a.Cin;
-    a.Kpad = (int)shapes[1][1];
+    a.Kpad = (int)g.d(1, 1);
     const int ctile = md_conv2d_cout_tile(a.Cout);
     const int cout_pad = (a.Cout + ctile - 1) / ctile * ctile;
-    if (a.Kpad % BK || a.Kpad < a.Kreal || shapes[1][0] != cout_pad) return MD_ERR_ARG;
-    if (numel(ndims, shapes, 2) != cout_pad) return MD_ERR_ARG;
+    if (a.Kpad % BK || a.Kpad < a.Kreal || g.d(1, 0) != cout_pad) return MD_ERR_ARG;
+    if (g.numel(2) != cout_pad) return MD_ERR_ARG;
     if (at->res_slice) {
-        if (!params[3] || a.res_up || ndims[3] != 4 || shapes[3][0] != a.N || shapes[3][1] != a.Ho || shapes[3][2] != a.Wo ||
+        if (!params[3] || a.res_up || g.d(3, 0) != a.N || g.d(3, 1) != a.Ho || g.d(3, 2) != a.Wo ||
             a.os != 1 || a.oy || a.ox || a.Ho != a.Hf || a.Wo != a.Wf || at->res_c_off < 0 || at->res_c_off % 8 ||
-            at->res_c_off + a.Cout > shapes[3][3])
+            at->res_c_off + a.Cout > g.d(3, 3))
             return MD_ERR_ARG;
-        a.Rs = (int)shapes[3][3];
+        a.Rs = (int)g.d(3, 3);
         a.res += at->res_c_off;
-    } else if (params[3] && !a.res_up && (ndims[3] != 4 || numel(ndims, shapes, 3) != numel(ndims, shapes, 4))) return MD_ERR_ARG;
-    if (a.res_up && (ndims[3] != 4 || shapes[3][0] != a.N || shapes[3][1] != (a.Ho + 1) / 2 || shapes[3][2] != (a.Wo + 1) / 2 ||
-                     shapes[3][3] != a.Cout))
+    } else if (params[3] && !a.res_up && g.numel(3) != g.numel(4)) return MD_ERR_ARG;
+    if (a.res_up && (g.d(3, 0) != a.N || g.d(3, 1) != (a.Ho + 1) / 2 || g.d(3, 2) != (a.Wo + 1) / 2 ||
+                     g.d(3, 3) != a.Cout))
         return MD_ERR_ARG;
     c.empty = (long long)a.N * a.Ho * a.Wo <= 0;
     if (c.empty) return MD_OK;
-    if (!params[0] || !params[4]) return MD_ERR_ARG;
+    if (!g.have({0, 4})) return MD_ERR_ARG;
     // (per chunk: the first chunk is the largest)
-    if (c.per * a.Ho * a.Wo > 0x7fffffffLL || c.per * a.H * a.W > 0x7fffffffLL / 2 || a.H > 32000 || a.W > 32000) return MD_ERR_SIZE;
+    if (!fits_i32(c.per * a.Ho * a.Wo) || !fits_i32(c.per * a.H * a.W * 2) || a.H > 32000 || a.W > 32000) return MD_ERR_SIZE;
     a.cpt = a.Cin / 8;
     a.pointwise = a.kh == 1 && a.kw == 1 && a.stride == 1 && a.pad_top == 0 && a.pad_left == 0 && a.H == a.Ho && a.W == a.Wo;
     c.x_img = (long long)a.H * a.W * a.Xs; c.y_img = (long long)a.Hf * a.Wf * a.Ctot; c.w_bytes = (long long)cout_pad * a.Kpad * 2;
-    c.r_img = params[3] ? shapes[3][1] * shapes[3][2] * shapes[3][3] : 0;
+    c.r_img = params[3] ? g.d(3, 1) * g.d(3, 2) * g.d(3, 3) : 0;
     return MD_OK;
 }
 
 // in : x_a[N,Ho,Wo,Ca] bf16 (Ca % 64 == 0), x_b[N,Hb,Wb,Cb] bf16 (Cb % 64 == 0, Ho == (Hb-1)/stride_b + 1), w[Cout_pad, Ca + Cb] bf16,
 //      bias[Cout_pad] f32, residual[N,Ho,Wo,Cout] bf16 | NULL ; out y[N,Ho,Wo,Cout] bf16 (Cout > 64).  extra: md_conv1x1_dual_attrs
 static int validate_dual(int nparam, void **params, int *ndims, int64_t **shapes, const char **dtypes, const void *extra, ConvCall &c) {
-    if (nparam != 6) return MD_ERR_NPARAM;
-    if (!params || !extra || !ndims || !shapes || !params[2] || !params[3]) return MD_ERR_ARG;
-    if (!dtype_is(dtypes, 0, "bfloat16") || !dtype_is(dtypes, 1, "bfloat16") || !dtype_is(dtypes, 2, "bfloat16") ||
-        !dtype_is(dtypes, 3, "float32") || !dtype_is(dtypes, 5, "bfloat16") || (params[4] && !dtype_is(dtypes, 4, "bfloat16")))
-        return MD_ERR_ARG;
-    if (ndims[0] != 4 || ndims[1] != 4 || ndims[2] != 2 || ndims[5] != 4) return MD_ERR_ARG;
-    const md_conv1x1_dual_attrs *at = (const md_conv1x1_dual_attrs *)extra;
-    const int64_t N = shapes[0][0], Ho = shapes[0][1], Wo = shapes[0][2], Ca = shapes[0][3];
-    const int64_t Hb = shapes[1][1], Wb = shapes[1][2], Cb = shapes[1][3], Cout = shapes[5][3];
+    Args g(MD_ARGS, 6, 6);
+    const md_conv1x1_dual_attrs *at = g.attrs<md_conv1x1_dual_attrs>(extra);
+    g.tensor(0, BF16, 4); g.tensor(1, BF16, 4); g.tensor(2, BF16, 2); g.tensor(3, F32); g.optional(4, BF16, 4); g.tensor(5, BF16, 4);
+    g.require(g.given(2) && g.given(3));
+    if (int rc = g.rc()) return rc;
+    const int64_t N = g.d(0, 0), Ho = g.d(0, 1), Wo = g.d(0, 2), Ca = g.d(0, 3);
+    const int64_t Hb = g.d(1, 1), Wb = g.d(1, 2), Cb = g.d(1, 3), Cout = g.d(5, 3);
     if (at->stride_b < 1 || at->relu < 0 || at->relu > 1 || Ca % 64 || Cb % 64 || Ca < 64 || Cb < 64 || Cout % 8 || Cout <= 64) return MD_ERR_ARG;
-    if (shapes[1][0] != N || shapes[5][0] != N || shapes[5][1] != Ho || shapes[5][2] != Wo || Hb < 1 || Wb < 1 ||
+    if (g.d(1, 0) != N || g.d(5, 0) != N || g.d(5, 1) != Ho || g.d(5, 2) != Wo || Hb < 1 || Wb < 1 ||
         Ho != (Hb - 1) / at->stride_b + 1 || Wo != (Wb - 1) / at->stride_b + 1)
         return MD_ERR_ARG;
     const int64_t cout_pad = (Cout + 127) / 128 * 128;
-    if (shapes[2][0] != cout_pad || shapes[2][1] != Ca + Cb || numel(ndims, shapes, 3) != cout_pad) return MD_ERR_ARG;
-    if (params[4] && (ndims[4] != 4 || numel(ndims, shapes, 4) != N * Ho * Wo * Cout)) return MD_ERR_ARG;
+    if (g.d(2, 0) != cout_pad || g.d(2, 1) != Ca + Cb || g.numel(3) != cout_pad) return MD_ERR_ARG;
+    if (params[4] && g.numel(4) != N * Ho * Wo * Cout) return MD_ERR_ARG;
     c = ConvCall{};
     c.empty = N * Ho * Wo == 0;
     if (c.empty) return MD_OK;
-    if (!params[0] || !params[1] || !params[5]) return MD_ERR_ARG;
+    if (!g.have({0, 1, 5})) return MD_ERR_ARG;
     if (Hb > 32000 || Wb > 32000) return MD_ERR_SIZE;
     const long long xa_img = Ho * Wo * Ca * 2, xb_img = Hb * Wb * Cb * 2;
     const long long big = xa_img > xb_img ? xa_img : xb_img;
@@ -2120,22 +2117,21 @@ static int validate_dual(int nparam, void **params, int *ndims, int64_t **shapes
 // validation result in rc1)
 static int validate_head(int nparam, void **params, int *ndims, int64_t **shapes, const char **dtypes, const void *extra, ConvCall *c, int &rc1) {
     // in: x[N,H,W,Cin], w[256,Kpad], bias[256], w2[32,256] (rows >= c2 zero), bias2[32] ; out: y2[N,Ho,Wo,16] ; [workspace]
-    if (nparam != 6 && nparam != 7) return MD_ERR_NPARAM;
-    if (!params || !extra || !ndims || !shapes || !params[3] || !params[4]) return MD_ERR_ARG;
-    if (!dtype_is(dtypes, 3, "bfloat16") || !dtype_is(dtypes, 4, "float32") || !dtype_is(dtypes, 5, "bfloat16")) return MD_ERR_ARG;
-    if (ndims[0] != 4 || ndims[1] != 2 || ndims[3] != 2 || ndims[5] != 4) return MD_ERR_ARG;
-    if (shapes[1][0] != 256 || shapes[3][0] < 16 || shapes[3][1] != 256 || numel(ndims, shapes, 4) < 16 || shapes[5][3] != 16 ||
-        shapes[5][0] != shapes[0][0])
-        return MD_ERR_ARG;
-    const md_conv2d_attrs *at = (const md_conv2d_attrs *)extra;
+    Args g(MD_ARGS, 6, 7);
+    const md_conv2d_attrs *at = g.attrs<md_conv2d_attrs>(extra);
+    // (x, w and bias get their dtype check from the md_conv2d validation of the first conv below)
+    g.tensor(0, nullptr, 4); g.tensor(1, nullptr, 2); g.tensor(2, nullptr); g.tensor(3, BF16, 2); g.tensor(4, F32); g.tensor(5, BF16, 4);
+    g.require(g.given(3) && g.given(4));
+    g.require(g.d(1, 0) == 256 && g.d(3, 0) >= 16 && g.d(3, 1) == 256 && g.numel(4) >= 16 && g.d(5, 3) == 16 && g.d(5, 0) == g.d(0, 0));
+    if (int rc = g.rc()) return rc;
     if (at->adv || at->relu != 1 || at->res_upsample) return MD_ERR_ARG;
-    const int64_t N = shapes[5][0], Ho = shapes[5][1], Wo = shapes[5][2];
+    const int64_t N = g.d(5, 0), Ho = g.d(5, 1), Wo = g.d(5, 2);
     c[0] = ConvCall{}; c[0].empty = N * Ho * Wo == 0;
     if (c[0].empty) return MD_OK;
-    if (!params[0] || !params[5]) return MD_ERR_ARG;
-    int64_t sy[4] = {N, Ho, Wo, 256}, snull[1] = {0}, sw2[2] = {shapes[3][0], 256}, sb2[1] = {shapes[3][0]};
-    int nd0[5] = {ndims[0], ndims[1], ndims[2], 0, 4}, nd1[5] = {4, 2, 1, 0, 4};
-    int64_t *sh0[5] = {shapes[0], shapes[1], shapes[2], snull, sy}, *sh1[5] = {sy, sw2, sb2, snull, shapes[5]};
+    if (!g.have({0, 5})) return MD_ERR_ARG;
+    int64_t sy[4] = {N, Ho, Wo, 256}, snull[1] = {0}, sw2[2] = {g.d(3, 0), 256}, sb2[1] = {g.d(3, 0)};
+    int nd0[5] = {g.rank(0), g.rank(1), g.rank(2), 0, 4}, nd1[5] = {4, 2, 1, 0, 4};
+    int64_t *sh0[5] = {g.shapes[0], g.shapes[1], g.shapes[2], snull, sy}, *sh1[5] = {sy, sw2, sb2, snull, g.shapes[5]};
     const char *dt0[5] = {dtypes ? dtypes[0] : nullptr, dtypes ? dtypes[1] : nullptr, dtypes ? dtypes[2] : nullptr, nullptr, "bfloat16"};
     const char *dt1[5] = {"bfloat16", "bfloat16", "float32", nullptr, "bfloat16"};
     void *p0[5] = {params[0], params[1], params[2], nullptr, params[5]}, *p1[5] = {params[5], params[3], params[4], nullptr, params[5]};
@@ -2249,7 +2245,7 @@ static int conv_op(ConvOp op, MD_AOT_ARGS) {
         if (rc != MD_OK) return rc;
         total = p.n;
         if (p.two_launch) {   // md_conv2d_head's two launches through a temporary [N,Ho,Wo,256]
-            if (!tmp.ptr && (rc = tmp.acquire((size_t)c[0].a.N * c[0].a.Ho * c[0].a.Wo * 256 * 2, nparam, params, ndims, shapes, 6,
+            if (!tmp.ptr && (rc = tmp.acquire((size_t)c[0].a.N * c[0].a.Ho * c[0].a.Wo * 256 * 2, Args(MD_ARGS, 6, 7), 6,
                                               (hipStream_t)stream)) != MD_OK)
                 return rc;
             c[0].a.y = (uint16_t *)tmp.ptr; c[1].a.x = (const uint16_t *)tmp.ptr;

@@ -82,25 +82,25 @@ using namespace md;
 
 extern "C" int md_deform_cols(MD_AOT_ARGS) {
     // in: x[N,H,W,C] bf16, off[N,Ho,Wo,Coff >= 3*kh*kw] bf16 ; out: cols[N,Ho,Wo,kh*kw*C] bf16 ; extra: md_pool_attrs (k,stride,pad)
-    if (nparam != 3) return MD_ERR_NPARAM;
-    if (!params || !extra || !ndims || !shapes || ndims[0] != 4 || ndims[1] != 4 || ndims[2] != 4) return MD_ERR_ARG;
-    if (!dtype_is(dtypes, 0, "bfloat16") || !dtype_is(dtypes, 1, "bfloat16") || !dtype_is(dtypes, 2, "bfloat16")) return MD_ERR_ARG;
-    const md_pool_attrs *at = (const md_pool_attrs *)extra;
+    Args g(MD_ARGS, 3, 3);
+    const md_pool_attrs *at = g.attrs<md_pool_attrs>(extra);
+    g.tensor(0, BF16, 4); g.tensor(1, BF16, 4); g.tensor(2, BF16, 4);
+    if (int rc = g.rc()) return rc;
     DcnArgs a;
-    a.N = (int)shapes[0][0]; a.H = (int)shapes[0][1]; a.W = (int)shapes[0][2]; a.C = (int)shapes[0][3];
-    a.Ho = (int)shapes[1][1]; a.Wo = (int)shapes[1][2]; a.Coff = (int)shapes[1][3];
+    a.N = (int)g.d(0, 0); a.H = (int)g.d(0, 1); a.W = (int)g.d(0, 2); a.C = (int)g.d(0, 3);
+    a.Ho = (int)g.d(1, 1); a.Wo = (int)g.d(1, 2); a.Coff = (int)g.d(1, 3);
     a.kh = a.kw = at->k; a.stride = at->stride; a.pad = at->pad;
     if (a.kh < 1 || a.kh > 7 || a.stride < 1 || a.pad < 0 || a.C % 8) return MD_ERR_ARG;
     const int T = a.kh * a.kw;
-    if (a.Coff < 3 * T || shapes[1][0] != a.N || a.Ho != (a.H + 2 * a.pad - a.kh) / a.stride + 1 ||
+    if (a.Coff < 3 * T || g.d(1, 0) != a.N || a.Ho != (a.H + 2 * a.pad - a.kh) / a.stride + 1 ||
         a.Wo != (a.W + 2 * a.pad - a.kw) / a.stride + 1)
         return MD_ERR_ARG;
-    if (shapes[2][0] != a.N || shapes[2][1] != a.Ho || shapes[2][2] != a.Wo || shapes[2][3] != (int64_t)T * a.C) return MD_ERR_ARG;
+    if (g.d(2, 0) != a.N || g.d(2, 1) != a.Ho || g.d(2, 2) != a.Wo || g.d(2, 3) != (int64_t)T * a.C) return MD_ERR_ARG;
     const size_t total = (size_t)a.N * a.Ho * a.Wo * T * (a.C / 8);
     if (total == 0) return MD_OK;
-    if (!params[0] || !params[1] || !params[2]) return MD_ERR_ARG;
+    if (!g.have({0, 1, 2})) return MD_ERR_ARG;
     a.x = (const uint16_t *)params[0]; a.off = (const uint16_t *)params[1]; a.cols = (uint16_t *)params[2];
     const size_t nb = (total + 255) / 256;
     hipLaunchKernelGGL(deform_cols_kernel, dim3((unsigned)(nb < 0x7fffffffull ? nb : 0x7fffffffull)), dim3(256), 0, (hipStream_t)stream, a, total);
-    return hipGetLastError() == hipSuccess ? MD_OK : MD_ERR_HIP;
+    return launched();
 }

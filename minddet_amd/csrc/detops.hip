@@ -26,11 +26,6 @@
 
 namespace md {
 
-static inline unsigned grid1d(size_t total, int bs = 256) {
-    size_t b = (total + bs - 1) / bs;
-    return (unsigned)(b > 16384 ? 16384 : (b == 0 ? 1 : b));
-}
-
 // ------------------------------------------------------------------------------------------ anchors
 // 2-D FPN anchors: out[(loc * A + a), 4] = shift(x,y) + base[level][a]; locations row-major.
 struct FpnLevel { int H, W, stride; int64_t offset; };  // offset in anchors
@@ -314,7 +309,6 @@ __device__ __forceinline__ void topk_blocked_stages(unsigned long long (&v)[16],
     for (int rb = 3; rb >= 0; --rb) {
         const int stride = 1 << (SHIFT + rb);
         if (stride < size) {
-            constexpr int dummy = 0; (void)dummy;
 #pragma unroll
             for (int j = 0; j < 16; ++j) {
                 if ((j & (1 << rb)) == 0) {
@@ -1277,9 +1271,11 @@ extern "C" int md_diag_set_topk_stamp_buffer(void *p) {
 #endif
 
 extern "C" int md_anchors_fpn(MD_AOT_ARGS) {
-    if (nparam != 1) return MD_ERR_NPARAM;
-    if (!params || !extra || !dtype_is(dtypes, 0, "float32")) return MD_ERR_ARG;
-    const md_fpn_anchor_attrs *at = (const md_fpn_anchor_attrs *)extra;
+    // out: anchors[sum_l H_l*W_l*A, 4] f32.  extra: md_fpn_anchor_attrs (required)
+    Args g(MD_ARGS, 1, 1);
+    const md_fpn_anchor_attrs *at = g.attrs<md_fpn_anchor_attrs>(extra);
+    g.tensor(0, F32);
+    if (int rc = g.rc()) return rc;
     if (at->num_levels < 1 || at->num_levels > 8 || at->num_ratios < 1 || at->num_ratios > 16) return MD_ERR_ARG;
     FpnArgs a;
     a.L = at->num_levels;
@@ -1299,18 +1295,20 @@ extern "C" int md_anchors_fpn(MD_AOT_ARGS) {
             a.base[l][r][2] = 0.5f * ws;  a.base[l][r][3] = 0.5f * hs;
         }
     }
-    if (numel(ndims, shapes, 0) != off * 4) return MD_ERR_ARG;
+    if (g.numel(0) != off * 4) return MD_ERR_ARG;
     if (off == 0) return MD_OK;
+    if (!g.have({0})) return MD_ERR_ARG;
     hipLaunchKernelGGL(anchors_fpn_kernel, dim3(grid1d((size_t)off)), dim3(256), 0, (hipStream_t)stream, a,
                        (float4 *)params[0], (size_t)off);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+    return launched();
 }
 
 extern "C" int md_anchors_3d_stride(MD_AOT_ARGS) {
-    if (nparam != 1) return MD_ERR_NPARAM;
-    if (!params || !extra || !dtype_is(dtypes, 0, "float32")) return MD_ERR_ARG;
-    const md_anchor3d_attrs *at = (const md_anchor3d_attrs *)extra;
+    // out: anchors[1,H,W,1,R,7] f32 (or [1,H,W,slots_total,7]).  extra: md_anchor3d_attrs (required)
+    Args g(MD_ARGS, 1, 1);
+    const md_anchor3d_attrs *at = g.attrs<md_anchor3d_attrs>(extra);
+    g.tensor(0, F32);
+    if (int rc = g.rc()) return rc;
     if (at->feat_h < 2 || at->feat_w < 2 || at->num_rot < 1 || at->num_rot > 8) return MD_ERR_ARG;
     Anchor3dArgs a;
     a.H = at->feat_h; a.W = at->feat_w; a.R = at->num_rot;
@@ -1331,17 +1329,18 @@ extern "C" int md_anchors_3d_stride(MD_AOT_ARGS) {
     a.slots = at->slots_total > 0 ? at->slots_total : a.R;
     a.slot_off = at->slots_total > 0 ? at->slot_off : 0;
     if (a.slot_off < 0 || a.slot_off + a.R > a.slots) return MD_ERR_ARG;
-    if (numel(ndims, shapes, 0) != (int64_t)a.H * a.W * a.slots * 7) return MD_ERR_ARG;
+    if (g.numel(0) != (int64_t)a.H * a.W * a.slots * 7 || !g.have({0})) return MD_ERR_ARG;
     hipLaunchKernelGGL(anchors_3d_stride_kernel, dim3(grid1d((size_t)total)), dim3(256), 0, (hipStream_t)stream, a,
                        (float *)params[0]);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+    return launched();
 }
 
 extern "C" int md_anchors_3d_range(MD_AOT_ARGS) {
-    if (nparam != 1) return MD_ERR_NPARAM;
-    if (!params || !extra || !dtype_is(dtypes, 0, "float32")) return MD_ERR_ARG;
-    const md_anchor3d_range_attrs *at = (const md_anchor3d_range_attrs *)extra;
+    // out: anchors[D,H,W,S,R,7] f32 (or [D,H,W,slots_total,7]).  extra: md_anchor3d_range_attrs (required)
+    Args g(MD_ARGS, 1, 1);
+    const md_anchor3d_range_attrs *at = g.attrs<md_anchor3d_range_attrs>(extra);
+    g.tensor(0, F32);
+    if (int rc = g.rc()) return rc;
     if (at->feat_d < 1 || at->feat_h < 1 || at->feat_w < 1 || at->num_sizes < 1 || at->num_sizes > 4 || at->num_rot < 1 ||
         at->num_rot > 8 || (at->linspace_mode != 0 && at->linspace_mode != 1))
         return MD_ERR_ARG;
@@ -1362,29 +1361,25 @@ extern "C" int md_anchors_3d_range(MD_AOT_ARGS) {
     a.slot_off = at->slots_total > 0 ? at->slot_off : 0;
     if (a.slot_off < 0 || a.slot_off + per > a.slots) return MD_ERR_ARG;
     const int64_t locs = (int64_t)a.D * a.H * a.W;
-    if (numel(ndims, shapes, 0) != locs * a.slots * 7) return MD_ERR_ARG;
-    if (!params[0]) return MD_ERR_ARG;
+    if (g.numel(0) != locs * a.slots * 7 || !g.have({0})) return MD_ERR_ARG;
     hipLaunchKernelGGL(anchors_3d_range_kernel, dim3(grid1d((size_t)locs * per)), dim3(256), 0, (hipStream_t)stream, a, (float *)params[0]);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+    return launched();
 }
 
 extern "C" int md_anchor_mask(MD_AOT_ARGS) {
     // in: coors[V,3] i32 (z,y,x), anchors_bv[N,4] f32 ; out: area[N] f32, mask[N] u8 ; ws: ny*nx i32
-    if (nparam != 4 && nparam != 5) return MD_ERR_NPARAM;
-    if (!params || !extra) return MD_ERR_ARG;
-    if (!dtype_is(dtypes, 0, "int32") || !dtype_is(dtypes, 1, "float32") || !dtype_is(dtypes, 2, "float32") ||
-        !dtype_is(dtypes, 3, "uint8"))
-        return MD_ERR_ARG;
-    const md_anchor_mask_attrs *at = (const md_anchor_mask_attrs *)extra;
-    const int64_t nv = dim(ndims, shapes, 0, 0), n = dim(ndims, shapes, 1, 0);
-    if (nv < 0 || n < 0 || dim(ndims, shapes, 0, 1) != 3 || dim(ndims, shapes, 1, 1) != 4) return MD_ERR_ARG;
+    Args a(MD_ARGS, 4, 5);
+    const md_anchor_mask_attrs *at = a.attrs<md_anchor_mask_attrs>(extra);
+    a.tensor(0, I32, 2); a.tensor(1, F32, 2); a.tensor(2, F32); a.tensor(3, U8);
+    const int64_t nv = a.d(0, 0), n = a.d(1, 0);
+    a.require(nv >= 0 && n >= 0 && a.d(0, 1) == 3 && a.d(1, 1) == 4 && a.numel(2) >= n && a.numel(3) >= n);
+    if (int rc = a.rc()) return rc;
     const int nx = at->grid_x, ny = at->grid_y;
     if (nx < 1 || ny < 1 || (int64_t)nx * ny > (1 << 28)) return MD_ERR_SIZE;
+    if ((nv > 0 && !a.have({0})) || (n > 0 && !a.have({1, 2, 3}))) return MD_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     Scratch ws;
-    int rc = ws.acquire((size_t)nx * ny * 4, nparam, params, ndims, shapes, 4, s);
-    if (rc) return rc;
+    if (int rc = ws.acquire((size_t)nx * ny * 4, a, 4, s)) return rc;
     int *dense = (int *)ws.ptr;
     MD_HIP_TRY(hipMemsetAsync(dense, 0, (size_t)nx * ny * 4, s));
     if (nv > 0)
@@ -1396,42 +1391,40 @@ extern "C" int md_anchor_mask(MD_AOT_ARGS) {
         hipLaunchKernelGGL(amask_area_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dense,
                            (const float *)params[1], (int)n, nx, ny, at->voxel_x, at->voxel_y, at->offset_x,
                            at->offset_y, at->area_threshold, (float *)params[2], (unsigned char *)params[3]);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+    return launched();
 }
 
 extern "C" int md_second_box_decode(MD_AOT_ARGS) {
     // in: encodings[..., 7] f32, anchors[A,7] f32 (broadcast over leading dims: row i uses anchor i % A) ; out: boxes
-    if (nparam != 3) return MD_ERR_NPARAM;
-    if (!params) return MD_ERR_ARG;
-    for (int i = 0; i < 3; ++i)
-        if (!dtype_is(dtypes, i, "float32")) return MD_ERR_ARG;
-    const int64_t tot = numel(ndims, shapes, 0), ta = numel(ndims, shapes, 1);
-    if (tot < 0 || ta <= 0 || tot % 7 || ta % 7 || numel(ndims, shapes, 2) != tot || (tot / 7) % (ta / 7)) return MD_ERR_ARG;
+    Args a(MD_ARGS, 3, 3);
+    a.tensor(0, F32); a.tensor(1, F32); a.tensor(2, F32);
+    const int64_t tot = a.numel(0), ta = a.numel(1);
+    if (int rc = a.rc()) return rc;
+    if (tot < 0 || ta <= 0 || tot % 7 || ta % 7 || a.numel(2) != tot || (tot / 7) % (ta / 7)) return MD_ERR_ARG;
     if (tot == 0) return MD_OK;
+    if (!a.have({0, 1, 2})) return MD_ERR_ARG;
     hipLaunchKernelGGL(second_box_decode_kernel, dim3(grid1d((size_t)tot / 7)), dim3(256), 0, (hipStream_t)stream,
                        (const float *)params[0], (const float *)params[1], (size_t)tot / 7, (size_t)ta / 7,
                        (float *)params[2]);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+    return launched();
 }
 
 extern "C" int md_delta2bbox(MD_AOT_ARGS) {
-    if (nparam != 3) return MD_ERR_NPARAM;
-    if (!params || !extra) return MD_ERR_ARG;
-    for (int i = 0; i < 3; ++i)
-        if (!dtype_is(dtypes, i, "float32")) return MD_ERR_ARG;
-    const int64_t tot = numel(ndims, shapes, 0);
-    if (tot < 0 || tot % 4 || numel(ndims, shapes, 1) != tot || numel(ndims, shapes, 2) != tot) return MD_ERR_ARG;
-    const md_delta2bbox_attrs *at = (const md_delta2bbox_attrs *)extra;
+    // in: rois[n,4] f32, deltas[n,4] f32 ; out: boxes[n,4] f32.  extra: md_delta2bbox_attrs (required)
+    Args g(MD_ARGS, 3, 3);
+    const md_delta2bbox_attrs *at = g.attrs<md_delta2bbox_attrs>(extra);
+    g.tensor(0, F32); g.tensor(1, F32); g.tensor(2, F32);
+    const int64_t tot = g.numel(0);
+    g.require(tot >= 0 && tot % 4 == 0 && g.numel(1) == tot && g.numel(2) == tot);
+    if (int rc = g.rc()) return rc;
     DeltaArgs a;
     for (int i = 0; i < 4; ++i) { a.mean[i] = at->means[i]; a.stdv[i] = at->stds[i]; }
     a.max_ratio = at->max_ratio; a.clip_w = at->clip_w; a.clip_h = at->clip_h; a.do_clip = at->clip_w > 0 && at->clip_h > 0;
     if (tot == 0) return MD_OK;
+    if (!g.have({0, 1, 2})) return MD_ERR_ARG;
     hipLaunchKernelGGL(delta2bbox_kernel, dim3(grid1d((size_t)tot / 4)), dim3(256), 0, (hipStream_t)stream,
                        (const float *)params[0], (const float *)params[1], (size_t)tot / 4, a, (float *)params[2]);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+    return launched();
 }
 
 // which form the calling host thread's last md_topk_segmented call launched (md_topk_last_path): 0 none, 1 single workgroup,
@@ -1442,26 +1435,23 @@ extern "C" int md_topk_last_path(void) { return g_topk_last_path; }
 extern "C" int md_topk_segmented(MD_AOT_ARGS) {
     // in: scores[T] f32, seg_off[L+1] i32 ; out: values[L,k] f32, indices[L,k] i32, count[L] i32
     g_topk_last_path = 0;
-    if (nparam != 5 && nparam != 6) return MD_ERR_NPARAM;
-    if (!params || !extra) return MD_ERR_ARG;
-    if (!dtype_is(dtypes, 0, "float32") || !dtype_is(dtypes, 1, "int32") || !dtype_is(dtypes, 2, "float32") ||
-        !dtype_is(dtypes, 3, "int32") || !dtype_is(dtypes, 4, "int32"))
-        return MD_ERR_ARG;
-    const md_topk_attrs *at = (const md_topk_attrs *)extra;
-    const int64_t L = numel(ndims, shapes, 1) - 1;
+    Args a(MD_ARGS, 5, 6);
+    const md_topk_attrs *at = a.attrs<md_topk_attrs>(extra);
+    a.tensor(0, F32); a.tensor(1, I32); a.tensor(2, F32); a.tensor(3, I32); a.tensor(4, I32);
+    const int64_t L = a.numel(1) - 1;
+    if (int rc = a.rc()) return rc;
     if (L < 0 || at->k < 1) return MD_ERR_ARG;
     if (at->k > TOPK_MAXK) return MD_ERR_SIZE;
-    if (numel(ndims, shapes, 2) != L * at->k || numel(ndims, shapes, 3) != L * at->k || numel(ndims, shapes, 4) != L)
-        return MD_ERR_ARG;
+    if (a.numel(2) != L * at->k || a.numel(3) != L * at->k || a.numel(4) != L) return MD_ERR_ARG;
     if (L == 0) return MD_OK;
+    if (!a.have({0, 1, 2, 3, 4})) return MD_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     // (r03: lowering the threshold to one 8192-score chunk -- the 32-image YOLO batches, 25 200 / 8 400 scores per image, run the single-workgroup
     // form for 110 / 86 us -- measured no gain: three launches + a memset cost what the idle CUs cost)
     if (at->max_segment > 4 * TK_CHUNK && at->k <= TK_CAP / 2 && L <= 65535) {
         const size_t hist_bytes = align_up((size_t)L * TK_BINS * 4 + (size_t)L * 4, 256);
         Scratch ws;
-        int rc = ws.acquire(hist_bytes + (size_t)L * TK_CAP * 8, nparam, params, ndims, shapes, 5, s);
-        if (rc) return rc;
+        if (int rc = ws.acquire(hist_bytes + (size_t)L * TK_CAP * 8, a, 5, s)) return rc;
         unsigned *ghist = (unsigned *)ws.ptr, *cand_cnt = ghist + (size_t)L * TK_BINS;
         unsigned long long *cand = (unsigned long long *)((char *)ws.ptr + hist_bytes);
         MD_HIP_TRY(hipMemsetAsync(ws.ptr, 0, hist_bytes, s));
@@ -1487,21 +1477,22 @@ extern "C" int md_topk_segmented(MD_AOT_ARGS) {
                            (int *)params[4]);
         g_topk_last_path = 1;
     }
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+    return launched();
 }
 
 extern "C" int md_roi_align(MD_AOT_ARGS) {
     // in: rois[R,5] f32, feat_0..feat_{L-1} [N,H,W,C] bf16 ; out: pooled[R,P,P,C] bf16, level[R] i32 (may be NULL ptr)
-    if (!params || !extra) return MD_ERR_ARG;
+    // extra: md_roi_align_attrs (required): its num_levels gives the parameter count, 1 + L + 2
     const md_roi_align_attrs *at = (const md_roi_align_attrs *)extra;
-    const int L = at->num_levels;
-    if (L < 1 || L > 6) return MD_ERR_ARG;
-    if (nparam != 1 + L + 2) return MD_ERR_NPARAM;
-    if (!dtype_is(dtypes, 0, "float32") || !dtype_is(dtypes, 1 + L, "bfloat16") || !dtype_is(dtypes, 2 + L, "int32"))
-        return MD_ERR_ARG;
-    const int64_t R = dim(ndims, shapes, 0, 0);
-    if (R < 0 || dim(ndims, shapes, 0, 1) != 5) return MD_ERR_ARG;
+    const int L = at && at->num_levels >= 1 && at->num_levels <= 6 ? at->num_levels : 0;
+    Args g(MD_ARGS, L ? 1 + L + 2 : 3, L ? 1 + L + 2 : 9);
+    g.require(L != 0);
+    g.tensor(0, F32, 2);
+    for (int l = 0; l < L; ++l) g.tensor(1 + l, BF16, 4);
+    g.tensor(1 + L, BF16); g.optional(2 + L, I32);
+    const int64_t R = g.d(0, 0);
+    g.require(R >= 0 && g.d(0, 1) == 5 && (!g.given(2 + L) || g.numel(2 + L) >= R));
+    if (int rc = g.rc()) return rc;
     RoiArgs a;
     a.L = L; a.P = at->pooled; a.sampling = at->sampling_ratio; a.aligned = at->aligned;
     a.k_min = at->k_min; a.canonical_level = at->canonical_level; a.canonical_scale = at->canonical_scale;
@@ -1512,16 +1503,17 @@ extern "C" int md_roi_align(MD_AOT_ARGS) {
     }
     a.C = 0; a.N = 0;
     for (int l = 0; l < L; ++l) {
-        if (!dtype_is(dtypes, 1 + l, "bfloat16") || ndims[1 + l] != 4) return MD_ERR_ARG;
-        a.lv[l].feat = (const uint16_t *)params[1 + l];
-        a.lv[l].H = (int)shapes[1 + l][1]; a.lv[l].W = (int)shapes[1 + l][2];
+        a.lv[l].feat = g.ptr<const uint16_t>(1 + l);
+        a.lv[l].H = (int)g.d(1 + l, 1); a.lv[l].W = (int)g.d(1 + l, 2);
         a.lv[l].scale = at->spatial_scale[l];
-        if (l == 0) { a.C = (int)shapes[1][3]; a.N = (int)shapes[1][0]; }
-        else if (shapes[1 + l][3] != a.C || shapes[1 + l][0] != a.N) return MD_ERR_ARG;
+        if (l == 0) { a.C = (int)g.d(1, 3); a.N = (int)g.d(1, 0); }
+        else if (g.d(1 + l, 3) != a.C || g.d(1 + l, 0) != a.N) return MD_ERR_ARG;
     }
     if (a.C % 8) return MD_ERR_ARG;
-    if (numel(ndims, shapes, 1 + L) != R * a.P * a.P * a.C) return MD_ERR_ARG;
+    if (g.numel(1 + L) != R * a.P * a.P * a.C) return MD_ERR_ARG;
     if (R == 0) return MD_OK;
+    for (int i = 0; i < 2 + L; ++i)
+        if (!g.have({i})) return MD_ERR_ARG;
     const size_t total = (size_t)R * a.P * a.P * (a.C / 8);
     if (a.C % 32 == 0)
         hipLaunchKernelGGL(roi_align_c32_kernel, dim3(grid1d(total / 4)), dim3(256), 0, (hipStream_t)stream, a,
@@ -1529,77 +1521,76 @@ extern "C" int md_roi_align(MD_AOT_ARGS) {
     else
         hipLaunchKernelGGL(roi_align_kernel, dim3(grid1d(total)), dim3(256), 0, (hipStream_t)stream, a,
                            (const float *)params[0], (int)R, (uint16_t *)params[1 + L], (int *)params[2 + L]);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+    return launched();
 }
 
 extern "C" int md_heat_nms(MD_AOT_ARGS) {
     // in: heat[B,C,H,W] f32 ; out: same shape
-    if (nparam != 2) return MD_ERR_NPARAM;
-    if (!params || !ndims || ndims[0] != 4 || !dtype_is(dtypes, 0, "float32") || !dtype_is(dtypes, 1, "float32")) return MD_ERR_ARG;
-    if (numel(ndims, shapes, 1) != numel(ndims, shapes, 0)) return MD_ERR_ARG;
-    const size_t planes = (size_t)shapes[0][0] * shapes[0][1];
-    const int H = (int)shapes[0][2], W = (int)shapes[0][3];
+    Args a(MD_ARGS, 2, 2);
+    a.tensor(0, F32, 4); a.tensor(1, F32);
+    a.require(a.numel(1) == a.numel(0));
+    if (int rc = a.rc()) return rc;
+    const size_t planes = (size_t)a.d(0, 0) * a.d(0, 1);
+    const int H = (int)a.d(0, 2), W = (int)a.d(0, 3);
     if (planes * H * W == 0) return MD_OK;
+    if (!a.have({0, 1})) return MD_ERR_ARG;
     hipLaunchKernelGGL(heat_nms_kernel, dim3(grid1d(planes * H * W)), dim3(256), 0, (hipStream_t)stream,
                        (const float *)params[0], (float *)params[1], H, W, planes);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+    return launched();
 }
 
 extern "C" int md_heat_peaks(MD_AOT_ARGS) {
     // in: head[B,H,W,Cp] bf16 ; out: heat[B,nc,H,W] f32 (sigmoid + clip, zeroed where not a 3x3 maximum), hm[B,nc,H,W] f32 | NULL
-    if (nparam != 3) return MD_ERR_NPARAM;
-    if (!params || !extra || !ndims || !shapes || ndims[0] != 4 || !dtype_is(dtypes, 0, "bfloat16") || !dtype_is(dtypes, 1, "float32") ||
-        !dtype_is(dtypes, 2, "float32"))
-        return MD_ERR_ARG;
-    const md_heat_peaks_attrs *at = (const md_heat_peaks_attrs *)extra;
+    Args g(MD_ARGS, 3, 3);
+    const md_heat_peaks_attrs *at = g.attrs<md_heat_peaks_attrs>(extra);
+    g.tensor(0, BF16, 4); g.tensor(1, F32); g.optional(2, F32);
+    if (int rc = g.rc()) return rc;
     PeakArgs a;
-    const int64_t B = shapes[0][0];
-    a.H = (int)shapes[0][1]; a.W = (int)shapes[0][2]; a.Cp = (int)shapes[0][3];
+    const int64_t B = g.d(0, 0);
+    a.H = (int)g.d(0, 1); a.W = (int)g.d(0, 2); a.Cp = (int)g.d(0, 3);
     a.c0 = at->c0; a.nc = at->num_classes; a.lo = at->lo; a.hi = at->hi;
     if (a.Cp % 8 || a.c0 < 0 || a.c0 % 8 || a.nc < 1 || a.c0 + (a.nc + 7) / 8 * 8 > a.Cp) return MD_ERR_ARG;
-    if (numel(ndims, shapes, 1) != B * a.nc * a.H * a.W || (params[2] && numel(ndims, shapes, 2) != B * a.nc * a.H * a.W)) return MD_ERR_ARG;
+    if (g.numel(1) != B * a.nc * a.H * a.W || (g.given(2) && g.numel(2) != B * a.nc * a.H * a.W)) return MD_ERR_ARG;
     if (B * a.H * a.W == 0) return MD_OK;
-    if (!params[0] || !params[1]) return MD_ERR_ARG;
+    if (!g.have({0, 1})) return MD_ERR_ARG;
     const long long tiles = (long long)((a.H + PK_TH - 1) / PK_TH) * ((a.W + PK_TW - 1) / PK_TW);
-    if (tiles > 0x7fffffffLL || B > 65535 || (a.nc + PK_C - 1) / PK_C > 65535) return MD_ERR_SIZE;
+    if (!fits_i32(tiles) || B > 65535 || (a.nc + PK_C - 1) / PK_C > 65535) return MD_ERR_SIZE;
     hipLaunchKernelGGL(heat_peaks_kernel, dim3((unsigned)tiles, (a.nc + PK_C - 1) / PK_C, (unsigned)B), dim3(256), 0, (hipStream_t)stream,
                        (const uint16_t *)params[0], a, (float *)params[1], (float *)params[2]);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+    return launched();
 }
 
 extern "C" int md_centernet_assemble(MD_AOT_ARGS) {
     // in: top_score[B,K] f32, top_ind2[B,K] i32, cls_inds[B,C,K] i32, wh[B,2,H,W] f32, reg[B,2,H,W] f32 | NULL
     // out: det[B,K,6] f32, inds[B,K] i32, cls[B,K] i32
-    if (nparam != 8) return MD_ERR_NPARAM;
-    if (!params || !ndims || ndims[0] != 2 || ndims[2] != 3 || ndims[3] != 4) return MD_ERR_ARG;
-    const int B = (int)shapes[0][0], K = (int)shapes[0][1], C = (int)shapes[2][1];
-    const int H = (int)shapes[3][2], W = (int)shapes[3][3];
-    if (shapes[2][2] != K || shapes[2][0] != B || shapes[3][0] != B || shapes[3][1] != 2) return MD_ERR_ARG;
-    if (numel(ndims, shapes, 5) != (int64_t)B * K * 6) return MD_ERR_ARG;
+    Args a(MD_ARGS, 8, 8);
+    a.tensor(0, F32, 2); a.tensor(1, I32); a.tensor(2, I32, 3); a.tensor(3, F32, 4); a.optional(4, F32);
+    a.tensor(5, F32); a.tensor(6, I32); a.tensor(7, I32);
+    const int B = (int)a.d(0, 0), K = (int)a.d(0, 1), C = (int)a.d(2, 1);
+    const int H = (int)a.d(3, 2), W = (int)a.d(3, 3);
+    a.require(a.d(2, 2) == K && a.d(2, 0) == B && a.d(3, 0) == B && a.d(3, 1) == 2 && a.numel(5) == (int64_t)B * K * 6);
+    a.require(a.numel(1) >= (int64_t)B * K && a.numel(6) >= (int64_t)B * K && a.numel(7) >= (int64_t)B * K &&
+              (!a.given(4) || a.numel(4) >= a.numel(3)));
+    if (int rc = a.rc()) return rc;
     if (B * K == 0) return MD_OK;
+    if (!a.have({0, 1, 2, 3, 5, 6, 7})) return MD_ERR_ARG;
     hipLaunchKernelGGL(centernet_assemble_kernel, dim3((B * K + 255) / 256), dim3(256), 0, (hipStream_t)stream,
                        (const float *)params[0], (const int *)params[1], (const int *)params[2], (const float *)params[3],
                        (const float *)params[4], B, C, K, H, W, (float *)params[5], (int *)params[6], (int *)params[7]);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+    return launched();
 }
 
 extern "C" int md_centerpoint_decode(MD_AOT_ARGS) {
     // in: head[B,H,W,C] bf16 ; out: scores[B,HW] f32, labels[B,HW] i32, boxes[B,HW,9] f32, nms_boxes[B,HW,7] f32
-    if (nparam != 5) return MD_ERR_NPARAM;
-    if (!params || !extra || !ndims || ndims[0] != 4) return MD_ERR_ARG;
-    if (!dtype_is(dtypes, 0, "bfloat16") || !dtype_is(dtypes, 1, "float32") || !dtype_is(dtypes, 2, "int32") ||
-        !dtype_is(dtypes, 3, "float32") || !dtype_is(dtypes, 4, "float32"))
-        return MD_ERR_ARG;
-    const md_centerpoint_attrs *at = (const md_centerpoint_attrs *)extra;
+    Args g(MD_ARGS, 5, 5);
+    const md_centerpoint_attrs *at = g.attrs<md_centerpoint_attrs>(extra);
+    g.tensor(0, BF16, 4); g.tensor(1, F32); g.tensor(2, I32); g.tensor(3, F32); g.tensor(4, F32);
+    if (int rc = g.rc()) return rc;
     CpArgs a;
     a.o_reg = at->off_reg; a.o_height = at->off_height; a.o_dim = at->off_dim; a.o_rot = at->off_rot;
     a.o_vel = at->off_vel; a.o_hm = at->off_hm; a.ncls = at->num_classes;
-    const int B = (int)shapes[0][0];
-    a.H = (int)shapes[0][1]; a.W = (int)shapes[0][2]; a.C = (int)shapes[0][3];
+    const int B = (int)g.d(0, 0);
+    a.H = (int)g.d(0, 1); a.W = (int)g.d(0, 2); a.C = (int)g.d(0, 3);
     if (a.ncls < 1 || a.o_hm + a.ncls > a.C || a.o_reg + 2 > a.C || a.o_dim + 3 > a.C || a.o_rot + 2 > a.C ||
         a.o_height + 1 > a.C || a.o_vel + 2 > a.C)
         return MD_ERR_ARG;
@@ -1607,39 +1598,34 @@ extern "C" int md_centerpoint_decode(MD_AOT_ARGS) {
     a.px = at->pc_range[0]; a.py = at->pc_range[1];
     for (int i = 0; i < 3; ++i) { a.rmin[i] = at->post_center_range[i]; a.rmax[i] = at->post_center_range[3 + i]; }
     const int64_t total = (int64_t)B * a.H * a.W;
-    if (numel(ndims, shapes, 1) != total || numel(ndims, shapes, 2) != total || numel(ndims, shapes, 3) != total * 9 ||
-        numel(ndims, shapes, 4) != total * 7)
-        return MD_ERR_ARG;
+    if (g.numel(1) != total || g.numel(2) != total || g.numel(3) != total * 9 || g.numel(4) != total * 7) return MD_ERR_ARG;
     if (total == 0) return MD_OK;
-    if (total > 0x7fffffffLL) return MD_ERR_SIZE;
+    if (!fits_i32(total)) return MD_ERR_SIZE;
+    if (!g.have({0, 1, 2, 3, 4})) return MD_ERR_ARG;
     hipLaunchKernelGGL(centerpoint_decode_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        (const uint16_t *)params[0], a, (int)total, (float *)params[1], (int *)params[2], (float *)params[3],
                        (float *)params[4]);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+    return launched();
 }
 
 extern "C" int md_yolo_decode(MD_AOT_ARGS) {
-    if (nparam != 4) return MD_ERR_NPARAM;
-    if (!params || !extra || !ndims || ndims[0] != 4) return MD_ERR_ARG;
-    if (!dtype_is(dtypes, 0, "bfloat16") || !dtype_is(dtypes, 1, "float32") || !dtype_is(dtypes, 2, "float32") ||
-        !dtype_is(dtypes, 3, "int32"))
-        return MD_ERR_ARG;
-    const md_yolo_attrs *at = (const md_yolo_attrs *)extra;
+    // in: head[B,H,W,Cp] bf16 ; out: boxes[B,out_total,4] f32, scores[B,out_total] f32, labels[B,out_total] i32.  extra: md_yolo_attrs
+    Args g(MD_ARGS, 4, 4);
+    const md_yolo_attrs *at = g.attrs<md_yolo_attrs>(extra);
+    g.tensor(0, BF16, 4); g.tensor(1, F32); g.tensor(2, F32); g.tensor(3, I32);
+    if (int rc = g.rc()) return rc;
     YoloArgs a;
-    const int B = (int)shapes[0][0];
-    a.H = (int)shapes[0][1]; a.W = (int)shapes[0][2]; a.Cp = (int)shapes[0][3];
+    const int B = (int)g.d(0, 0);
+    a.H = (int)g.d(0, 1); a.W = (int)g.d(0, 2); a.Cp = (int)g.d(0, 3);
     a.nc = at->num_classes; a.A = at->num_anchors; a.stride = at->stride; a.thr = at->conf_thres;
     a.off = at->out_offset; a.total = at->out_total;
     if (a.A < 1 || a.A > 3 || a.nc < 1 || a.A * (5 + a.nc) > a.Cp) return MD_ERR_ARG;
     for (int i = 0; i < a.A; ++i) { a.aw[i] = at->anchors[2 * i]; a.ah[i] = at->anchors[2 * i + 1]; }
     const int64_t per = (int64_t)a.H * a.W * a.A;
     if (a.off < 0 || a.off + per > a.total) return MD_ERR_ARG;
-    if (numel(ndims, shapes, 1) != (int64_t)B * a.total * 4 || numel(ndims, shapes, 2) != (int64_t)B * a.total ||
-        numel(ndims, shapes, 3) != (int64_t)B * a.total)
-        return MD_ERR_ARG;
+    if (g.numel(1) != (int64_t)B * a.total * 4 || g.numel(2) != (int64_t)B * a.total || g.numel(3) != (int64_t)B * a.total) return MD_ERR_ARG;
     if (B * per == 0) return MD_OK;
-    if (a.Cp % 8) return MD_ERR_ARG;
+    if (a.Cp % 8 || !g.have({0, 1, 2, 3})) return MD_ERR_ARG;
     // cells per 256-thread workgroup: A threads per cell, rows of Cp/2 + 1 dwords in at most 60 KiB of LDS
     int cells = 256 / a.A;
     if (cells > 64) cells = 64;
@@ -1650,79 +1636,76 @@ extern "C" int md_yolo_decode(MD_AOT_ARGS) {
     hipLaunchKernelGGL(yolo_decode_kernel, dim3((unsigned)((cells_total + cells - 1) / cells)), dim3(256), (size_t)cells * rowb,
                        (hipStream_t)stream, (const uint16_t *)params[0], a, B, cells, (float *)params[1], (float *)params[2],
                        (int *)params[3]);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+    return launched();
 }
 
 extern "C" int md_standup_boxes(MD_AOT_ARGS) {
     // in: boxes[N, S] f32 (S = 5: x,y,dx,dy,r ; S = 7: x,y,z,dx,dy,dz,r) ; out: standup[N,4] f32
-    if (nparam != 2) return MD_ERR_NPARAM;
-    if (!params || !ndims || ndims[0] != 2 || !dtype_is(dtypes, 0, "float32") || !dtype_is(dtypes, 1, "float32")) return MD_ERR_ARG;
-    const int64_t n = shapes[0][0];
-    const int S = (int)shapes[0][1];
-    if ((S != 5 && S != 7) || numel(ndims, shapes, 1) != n * 4) return MD_ERR_ARG;
+    Args a(MD_ARGS, 2, 2);
+    a.tensor(0, F32, 2); a.tensor(1, F32);
+    const int64_t n = a.d(0, 0);
+    const int S = (int)a.d(0, 1);
+    a.require((S == 5 || S == 7) && a.numel(1) == n * 4);
+    if (int rc = a.rc()) return rc;
     if (n == 0) return MD_OK;
-    if (n > 0x7fffffffLL) return MD_ERR_SIZE;
+    if (!fits_i32(n)) return MD_ERR_SIZE;
+    if (!a.have({0, 1})) return MD_ERR_ARG;
     if (S == 5)
         hipLaunchKernelGGL(standup_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                            (const float *)params[0], (int)n, 5, 0, 1, 2, 3, 4, (float *)params[1]);
     else
         hipLaunchKernelGGL(standup_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                            (const float *)params[0], (int)n, 7, 0, 1, 3, 4, 6, (float *)params[1]);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+    return launched();
 }
 
 extern "C" int md_gather_rows(MD_AOT_ARGS) {
     // in: src[B,n,W] f32, idx[B,k] i32, cnt[B] i32 or NULL ; out: out[B,k,W] f32
-    if (nparam != 4) return MD_ERR_NPARAM;
-    if (!params || !ndims || ndims[0] != 3 || ndims[1] != 2) return MD_ERR_ARG;
-    if (!dtype_is(dtypes, 0, "float32") || !dtype_is(dtypes, 1, "int32") || !dtype_is(dtypes, 2, "int32") ||
-        !dtype_is(dtypes, 3, "float32"))
-        return MD_ERR_ARG;
-    const int B = (int)shapes[0][0], n = (int)shapes[0][1], W = (int)shapes[0][2], k = (int)shapes[1][1];
-    if (shapes[1][0] != B || numel(ndims, shapes, 3) != (int64_t)B * k * W) return MD_ERR_ARG;
+    Args a(MD_ARGS, 4, 4);
+    a.tensor(0, F32, 3); a.tensor(1, I32, 2); a.optional(2, I32); a.tensor(3, F32);
+    const int B = (int)a.d(0, 0), n = (int)a.d(0, 1), W = (int)a.d(0, 2), k = (int)a.d(1, 1);
+    a.require(a.d(1, 0) == B && a.numel(3) == (int64_t)B * k * W && (!a.given(2) || a.numel(2) >= B));
+    if (int rc = a.rc()) return rc;
     if ((int64_t)B * k * W == 0) return MD_OK;
+    if (!a.have({0, 1, 3})) return MD_ERR_ARG;
     hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)(((int64_t)B * k * W + 255) / 256)), dim3(256), 0,
                        (hipStream_t)stream, (const float *)params[0], (const int *)params[1], (const int *)params[2], B, n, k,
                        W, (float *)params[3]);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+    return launched();
 }
 
 extern "C" int md_sigmoid_clip(MD_AOT_ARGS) {
-    if (nparam != 2) return MD_ERR_NPARAM;
-    if (!params || !dtype_is(dtypes, 0, "float32") || !dtype_is(dtypes, 1, "float32")) return MD_ERR_ARG;
-    const int64_t n = numel(ndims, shapes, 0);
-    if (n < 0 || numel(ndims, shapes, 1) != n) return MD_ERR_ARG;
+    // in: x f32 (any shape) ; out: y f32, as many elements.  extra: md_clip_attrs (NULL -> 1e-4, 1 - 1e-4)
+    Args a(MD_ARGS, 2, 2);
+    a.tensor(0, F32); a.tensor(1, F32);
+    const int64_t n = a.numel(0);
+    a.require(n >= 0 && a.numel(1) == n);
+    if (int rc = a.rc()) return rc;
     float lo = 1e-4f, hi = 1.0f - 1e-4f;
     if (extra) { lo = ((const md_clip_attrs *)extra)->lo; hi = ((const md_clip_attrs *)extra)->hi; }
     if (n == 0) return MD_OK;
+    if (!a.have({0, 1})) return MD_ERR_ARG;
     hipLaunchKernelGGL(sigmoid_clip_kernel, dim3(grid1d((size_t)n)), dim3(256), 0, (hipStream_t)stream,
                        (const float *)params[0], (float *)params[1], (size_t)n, lo, hi);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+    return launched();
 }
 
 extern "C" int md_yolov8_decode(MD_AOT_ARGS) {
     // in: head[B,H,W,Cp >= 4*reg_max + nc] bf16 ; out: boxes[B,total,4] f32, scores[B,total] f32, labels[B,total] i32
-    if (nparam != 4) return MD_ERR_NPARAM;
-    if (!params || !extra || !ndims || !shapes || ndims[0] != 4) return MD_ERR_ARG;
-    if (!dtype_is(dtypes, 0, "bfloat16") || !dtype_is(dtypes, 1, "float32") || !dtype_is(dtypes, 2, "float32") || !dtype_is(dtypes, 3, "int32"))
-        return MD_ERR_ARG;
-    const md_yolov8_attrs *at = (const md_yolov8_attrs *)extra;
+    Args g(MD_ARGS, 4, 4);
+    const md_yolov8_attrs *at = g.attrs<md_yolov8_attrs>(extra);
+    g.tensor(0, BF16, 4); g.tensor(1, F32); g.tensor(2, F32); g.tensor(3, I32);
+    if (int rc = g.rc()) return rc;
     Yolo8Args a;
-    const int B = (int)shapes[0][0];
-    a.H = (int)shapes[0][1]; a.W = (int)shapes[0][2]; a.Cp = (int)shapes[0][3];
+    const int B = (int)g.d(0, 0);
+    a.H = (int)g.d(0, 1); a.W = (int)g.d(0, 2); a.Cp = (int)g.d(0, 3);
     a.nc = at->num_classes; a.R = at->reg_max; a.stride = at->stride; a.thr = at->conf_thres; a.off = at->out_offset; a.total = at->out_total;
     const int per = a.H * a.W;
     if (a.nc < 1 || a.R < 1 || a.R > 64 || 4 * a.R + a.nc > a.Cp || a.off < 0 || a.off + per > a.total) return MD_ERR_ARG;
-    if (numel(ndims, shapes, 1) != (int64_t)B * a.total * 4 || numel(ndims, shapes, 2) != (int64_t)B * a.total ||
-        numel(ndims, shapes, 3) != (int64_t)B * a.total)
-        return MD_ERR_ARG;
+    if (g.numel(1) != (int64_t)B * a.total * 4 || g.numel(2) != (int64_t)B * a.total || g.numel(3) != (int64_t)B * a.total) return MD_ERR_ARG;
     if ((int64_t)B * per == 0) return MD_OK;
-    if ((int64_t)B * per > 0x7fffffffLL) return MD_ERR_SIZE;
-    if (a.Cp % 8) return MD_ERR_ARG;
+    if (!fits_i32((int64_t)B * per)) return MD_ERR_SIZE;
+    if (a.Cp % 8 || !g.have({0, 1, 2, 3})) return MD_ERR_ARG;
     int cells = 128;                                  // one thread per cell; rows of Cp/2 + 1 dwords in at most 60 KiB of LDS
     const int rowb = (a.Cp / 2 + 1) * 4;
     if (cells * rowb > 60 * 1024) cells = 60 * 1024 / rowb;
@@ -1731,7 +1714,6 @@ extern "C" int md_yolov8_decode(MD_AOT_ARGS) {
     hipLaunchKernelGGL(yolov8_decode_kernel, dim3((unsigned)((cells_total + cells - 1) / cells)), dim3(256), (size_t)cells * rowb,
                        (hipStream_t)stream, (const uint16_t *)params[0], a, B, cells, (float *)params[1], (float *)params[2],
                        (int *)params[3]);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+    return launched();
 }
 

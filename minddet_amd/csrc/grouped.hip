@@ -157,26 +157,21 @@ using namespace md;
 // in : x[N,H,W,C] bf16, w[R, k*k*64] bf16, bias[R] f32 ; out: y[N,H,W,Cy] bf16.  extra: md_conv2d_grouped_attrs (required).
 // Every check precedes the first device call.
 extern "C" int md_conv2d_grouped(MD_AOT_ARGS) {
-    if (nparam != 4) return MD_ERR_NPARAM;
-    if (!params || !ndims || !shapes || !extra) return MD_ERR_ARG;
-    const md_conv2d_grouped_attrs *at = (const md_conv2d_grouped_attrs *)extra;
+    Args g(MD_ARGS, 4, 4);
+    const md_conv2d_grouped_attrs *at = g.attrs<md_conv2d_grouped_attrs>(extra);
+    g.tensor(0, BF16, 4); g.tensor(1, BF16, 2); g.tensor(2, F32, 1); g.tensor(3, BF16, 4);
+    if (int rc = g.rc()) return rc;
     if (at->reserved0 != 0) return MD_ERR_ARG;
     if (at->k != 1 && at->k != 3) return MD_ERR_ARG;
     if (at->relu != 0 && at->relu != 1) return MD_ERR_ARG;
     if (at->cin_g != 64) return MD_ERR_ARG;
     const int G = at->groups;
     if (G < 1 || G > MD_GROUPED_MAX_GROUPS) return MD_ERR_ARG;
-    for (int i : {0, 1, 3})
-        if (!dtype_is(dtypes, i, "bfloat16")) return MD_ERR_ARG;
-    if (!dtype_is(dtypes, 2, "float32")) return MD_ERR_ARG;
-    if (ndims[0] != 4 || ndims[1] != 2 || ndims[2] != 1 || ndims[3] != 4) return MD_ERR_ARG;
-    for (int i = 0; i < 4; ++i)
-        if (!shapes[i]) return MD_ERR_ARG;
-    const int64_t N = shapes[0][0], H = shapes[0][1], W = shapes[0][2], C = shapes[0][3];
-    const int64_t R = shapes[1][0], Cy = shapes[3][3];
+    const int64_t N = g.d(0, 0), H = g.d(0, 1), W = g.d(0, 2), C = g.d(0, 3);
+    const int64_t R = g.d(1, 0), Cy = g.d(3, 3);
     if (N < 0 || H < 0 || W < 0 || C % 8 || Cy % 8 || Cy <= 0) return MD_ERR_ARG;
-    if (shapes[1][1] != (int64_t)at->k * at->k * 64 || shapes[2][0] != R) return MD_ERR_ARG;
-    if (shapes[3][0] != N || shapes[3][1] != H || shapes[3][2] != W) return MD_ERR_ARG;
+    if (g.d(1, 1) != (int64_t)at->k * at->k * 64 || g.d(2, 0) != R) return MD_ERR_ARG;
+    if (g.d(3, 0) != N || g.d(3, 1) != H || g.d(3, 2) != W) return MD_ERR_ARG;
     if (at->x_c_off < 0 || at->x_c_off % 8 || at->x_c_off + (int64_t)G * 64 > C) return MD_ERR_ARG;
     for (int g = 0; g < G; ++g) {
         const int co = at->cout[g], yo = at->y_off[g], wr = at->w_row[g];
@@ -185,8 +180,7 @@ extern "C" int md_conv2d_grouped(MD_AOT_ARGS) {
             if (yo < at->y_off[h] + at->cout[h] && at->y_off[h] < yo + co) return MD_ERR_ARG;
     }
     if (N * H * W == 0) return MD_OK;
-    for (int i = 0; i < 4; ++i)
-        if (!params[i]) return MD_ERR_ARG;
+    if (!g.have({0, 1, 2, 3})) return MD_ERR_ARG;
     {   // y must not overlap x (a workgroup's halo pixels are other workgroups' outputs)
         const char *xb = (const char *)params[0], *yb = (const char *)params[3];
         const long long xn = N * H * W * C * 2, yn = N * H * W * Cy * 2;
@@ -199,7 +193,7 @@ extern "C" int md_conv2d_grouped(MD_AOT_ARGS) {
     a.x_c_off = at->x_c_off; a.relu = at->relu;
     a.tiles_x = (int)((W + GC_TW - 1) / GC_TW); a.tiles_y = (int)((H + GC_TH - 1) / GC_TH);
     const long long n_work = N * a.tiles_x * a.tiles_y * (long long)G;
-    if (n_work > 0x7fffffffLL / 2) return MD_ERR_SIZE;
+    if (!fits_i32(n_work * 2)) return MD_ERR_SIZE;
     a.n_work = (int)n_work;
     a.work_per_xcd = (a.n_work + 7) / 8;
     for (int g = 0; g < MD_GROUPED_MAX_GROUPS; ++g) {
@@ -212,6 +206,5 @@ extern "C" int md_conv2d_grouped(MD_AOT_ARGS) {
     if (ensure_dyn_lds((const void *)k, lds) != MD_OK) return MD_ERR_HIP;
     hipLaunchKernelGGL(k, dim3((unsigned)a.work_per_xcd * 8u), dim3(GC_THREADS), lds, (hipStream_t)stream, a);
     md_note_conv_kernel(MD_CONV_KERNEL_GROUPED);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+    return launched();
 }

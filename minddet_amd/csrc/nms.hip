@@ -547,111 +547,95 @@ using namespace md;
 extern "C" const char *md_version(void) { return "minddet_hip 0.1 gfx950"; }
 extern "C" int md_scratch_release(void) { return md::pool_release(); }
 
-static int check_boxes7(int nparam, int want, void **params, int *ndims, int64_t **shapes, const char **dtypes,
-                        int64_t &n) {
-    if (nparam != want && nparam != want + 1) return MD_ERR_NPARAM;
-    if (!params || !dtype_is(dtypes, 0, "float32")) return MD_ERR_ARG;
-    n = dim(ndims, shapes, 0, 0);
-    if (n < 0 || dim(ndims, shapes, 0, 1) != 7) return MD_ERR_ARG;
-    if (n > (1 << 16)) return MD_ERR_SIZE;
-    return MD_OK;
-}
-
-// outputs of the keep-list NMS ops: keep[>= n] and num[>= 1] (the kernels zero keep[0..n) and write num[0] whatever the
-// caller's out_shape lambdas said), no NULL operand when there is work.  Shapes a caller does not describe are not checked.
-static int check_keep_outputs(void **params, int *ndims, int64_t **shapes, int64_t n) {
-    const int64_t keep_n = numel(ndims, shapes, 2), num_n = numel(ndims, shapes, 3);
-    if ((keep_n >= 0 && keep_n < n) || (num_n >= 0 && num_n < 1)) return MD_ERR_ARG;
-    if (!params[3]) return MD_ERR_ARG;
-    if (n > 0 && (!params[0] || !params[1] || !params[2])) return MD_ERR_ARG;
-    return MD_OK;
+// The keep-list NMS ops of the reference ABI.  in: boxes[N,7] f32 (N <= 65536), thresh f32 ; out: keep[>= N] KeepT, num[>= 1] i32
+// (the kernels zero keep[0..N) and write num[0] whatever the caller's out_shape lambdas said) ; [workspace].  Shapes of thresh, keep
+// and num that a caller does not describe are not checked.  Returns the checked view; n = N.
+static Args keep_nms_args(int nparam, void **params, int *ndims, int64_t **shapes, const char **dtypes, const char *keep_dtype, int64_t &n) {
+    Args a(MD_ARGS, 4, 5);
+    a.tensor(0, F32, 2);
+    n = a.d(0, 0);
+    a.require(n >= 0 && a.d(0, 1) == 7);
+    a.require(n <= (1 << 16), MD_ERR_SIZE);
+    a.loose(1, F32); a.loose(2, keep_dtype); a.loose(3, I32);
+    a.require((a.numel(2) < 0 || a.numel(2) >= n) && (a.numel(3) < 0 || a.numel(3) >= 1));
+    a.have({3});
+    if (n > 0) a.have({0, 1, 2});
+    return a;
 }
 
 template <int MODE, typename KeepT>
 static int rot_nms_impl(MD_AOT_ARGS, const char *keep_dtype) {
     int64_t n;
-    int rc = check_boxes7(nparam, 4, params, ndims, shapes, dtypes, n);
-    if (rc) return rc;
-    if (!dtype_is(dtypes, 1, "float32") || !dtype_is(dtypes, 2, keep_dtype) || !dtype_is(dtypes, 3, "int32"))
-        return MD_ERR_ARG;
-    rc = check_keep_outputs(params, ndims, shapes, n);
-    if (rc) return rc;
+    Args a = keep_nms_args(MD_ARGS, keep_dtype, n);
+    if (int rc = a.rc()) return rc;
     hipStream_t s = (hipStream_t)stream;
-    KeepT *keep = (KeepT *)params[2];
-    int *num = (int *)params[3];
+    KeepT *keep = a.ptr<KeepT>(2);
+    int *num = a.ptr<int>(3);
     if (n == 0) return hipMemsetAsync(num, 0, sizeof(int), s) == hipSuccess ? MD_OK : MD_ERR_HIP;
     const int cb = (int)((n + TILE - 1) / TILE);
     const size_t rec_bytes = align_up((size_t)n * ROT_REC * 4, 256);
     const size_t mask_bytes = (size_t)n * cb * 8;
     Scratch ws;
-    rc = ws.acquire(rec_bytes + mask_bytes, nparam, params, ndims, shapes, 4, s);
-    if (rc) return rc;
+    if (int rc = ws.acquire(rec_bytes + mask_bytes, a, 4, s)) return rc;
     float *rec = (float *)ws.ptr;
     unsigned long long *mask = (unsigned long long *)((char *)ws.ptr + rec_bytes);
-    hipLaunchKernelGGL(rot_prep_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (const float *)params[0], (int)n, rec);
+    hipLaunchKernelGGL(rot_prep_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a.ptr<const float>(0), (int)n, rec);
     hipLaunchKernelGGL((nms_rot_mask_kernel<MODE>), dim3(cb * (cb + 1) / 2), dim3(256), 0, s, rec, (int)n,
-                       (const float *)params[1], mask, cb);
+                       a.ptr<const float>(1), mask, cb);
     hipLaunchKernelGGL((nms_scan_kernel<KeepT>), dim3(1), dim3(256), scan_lds(cb), s, mask, (const int *)nullptr,
                        (int)n, cb, MODE == 1 ? rec + 14 : (const float *)nullptr, ROT_REC, 0, keep, num,
                        (unsigned char *)nullptr);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+    return launched();
 }
 
 extern "C" int NmsGpu(MD_AOT_ARGS) {
-    return rot_nms_impl<0, long long>(nparam, params, ndims, shapes, dtypes, stream, extra, "int64");
+    return rot_nms_impl<0, long long>(nparam, params, ndims, shapes, dtypes, stream, extra, I64);
 }
 
 extern "C" int boxes_iou_nms_gpu(MD_AOT_ARGS) {
-    return rot_nms_impl<1, int>(nparam, params, ndims, shapes, dtypes, stream, extra, "int32");
+    return rot_nms_impl<1, int>(nparam, params, ndims, shapes, dtypes, stream, extra, I32);
 }
 
 extern "C" int NmsNormalGpu(MD_AOT_ARGS) {
     int64_t n;
-    int rc = check_boxes7(nparam, 4, params, ndims, shapes, dtypes, n);
-    if (rc) return rc;
-    if (!dtype_is(dtypes, 1, "float32") || !dtype_is(dtypes, 2, "int64") || !dtype_is(dtypes, 3, "int32"))
-        return MD_ERR_ARG;
-    rc = check_keep_outputs(params, ndims, shapes, n);
-    if (rc) return rc;
+    Args a = keep_nms_args(MD_ARGS, I64, n);
+    if (int rc = a.rc()) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (n == 0) return hipMemsetAsync(params[3], 0, sizeof(int), s) == hipSuccess ? MD_OK : MD_ERR_HIP;
     const int cb = (int)((n + TILE - 1) / TILE);
     Scratch ws;
-    rc = ws.acquire((size_t)n * cb * 8, nparam, params, ndims, shapes, 4, s);
-    if (rc) return rc;
+    if (int rc = ws.acquire((size_t)n * cb * 8, a, 4, s)) return rc;
     unsigned long long *mask = (unsigned long long *)ws.ptr;
-    hipLaunchKernelGGL(nms_normal7_mask_kernel, dim3(cb * (cb + 1) / 2), dim3(256), 0, s, (const float *)params[0],
-                       (int)n, (const float *)params[1], mask, cb);
+    hipLaunchKernelGGL(nms_normal7_mask_kernel, dim3(cb * (cb + 1) / 2), dim3(256), 0, s, a.ptr<const float>(0),
+                       (int)n, a.ptr<const float>(1), mask, cb);
     hipLaunchKernelGGL((nms_scan_kernel<long long>), dim3(1), dim3(256), scan_lds(cb), s, mask, (const int *)nullptr,
-                       (int)n, cb, (const float *)nullptr, 0, 0, (long long *)params[2], (int *)params[3],
+                       (int)n, cb, (const float *)nullptr, 0, 0, a.ptr<long long>(2), a.ptr<int>(3),
                        (unsigned char *)nullptr);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+    return launched();
 }
 
+// in: boxes_a[M,7] f32, boxes_b[N,7] f32 ; out: iou / overlap [M,N] f32 (its shape may be left out) ; [workspace]
 template <int IOU>
 static int rot_matrix_impl(MD_AOT_ARGS) {
-    if (nparam != 3 && nparam != 4) return MD_ERR_NPARAM;
-    if (!params || !dtype_is(dtypes, 0, "float32") || !dtype_is(dtypes, 1, "float32") || !dtype_is(dtypes, 2, "float32"))
-        return MD_ERR_ARG;
-    const int64_t na = dim(ndims, shapes, 0, 0), nb = dim(ndims, shapes, 1, 0);
-    if (na < 0 || nb < 0 || dim(ndims, shapes, 0, 1) != 7 || dim(ndims, shapes, 1, 1) != 7) return MD_ERR_ARG;
+    Args a(MD_ARGS, 3, 4);
+    a.tensor(0, F32, 2); a.tensor(1, F32, 2); a.loose(2, F32);
+    const int64_t na = a.d(0, 0), nb = a.d(1, 0);
+    a.require(na >= 0 && nb >= 0 && a.d(0, 1) == 7 && a.d(1, 1) == 7);
+    if (int rc = a.rc()) return rc;
     if (na == 0 || nb == 0) return MD_OK;
     if (na > (1 << 24) || nb > (1 << 24)) return MD_ERR_SIZE;
+    if (!a.have({0, 1, 2})) return MD_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     const size_t ra = align_up((size_t)na * ROT_REC * 4, 256), rbb = (size_t)nb * ROT_REC * 4;
     Scratch ws;
-    int rc = ws.acquire(ra + rbb, nparam, params, ndims, shapes, 3, s);
-    if (rc) return rc;
+    if (int rc = ws.acquire(ra + rbb, a, 3, s)) return rc;
     float *rec_a = (float *)ws.ptr, *rec_b = (float *)((char *)ws.ptr + ra);
-    hipLaunchKernelGGL(rot_prep_kernel, dim3((na + 255) / 256), dim3(256), 0, s, (const float *)params[0], (int)na, rec_a);
-    hipLaunchKernelGGL(rot_prep_kernel, dim3((nb + 255) / 256), dim3(256), 0, s, (const float *)params[1], (int)nb, rec_b);
+    hipLaunchKernelGGL(rot_prep_kernel, dim3((na + 255) / 256), dim3(256), 0, s, a.ptr<const float>(0), (int)na, rec_a);
+    hipLaunchKernelGGL(rot_prep_kernel, dim3((nb + 255) / 256), dim3(256), 0, s, a.ptr<const float>(1), (int)nb, rec_b);
     const size_t total = (size_t)na * nb;
     hipLaunchKernelGGL((rot_pair_matrix_kernel<IOU>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, rec_a,
-                       (int)na, rec_b, (int)nb, (float *)params[2]);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+                       (int)na, rec_b, (int)nb, a.ptr<float>(2));
+    return launched();
 }
 
 extern "C" int BoxesIouBevGpu(MD_AOT_ARGS) {
@@ -661,55 +645,62 @@ extern "C" int BoxesOverlapBevGpu(MD_AOT_ARGS) {
     return rot_matrix_impl<0>(nparam, params, ndims, shapes, dtypes, stream, extra);
 }
 
+// in: boxes[N,W] f32, query[K,W] f32 ; out: [N,K] f32 -- the operands of md_iou_aligned (W = 4) and md_rotate_iou_eval (W = 5)
+static Args pair_matrix_args(int nparam, void **params, int *ndims, int64_t **shapes, const char **dtypes, int width, int64_t &n, int64_t &k) {
+    Args a(MD_ARGS, 3, 3);
+    a.tensor(0, F32, 2); a.tensor(1, F32, 2); a.tensor(2, F32);
+    n = a.d(0, 0); k = a.d(1, 0);
+    a.require(n >= 0 && k >= 0 && a.d(0, 1) == width && a.d(1, 1) == width && a.numel(2) >= n * k);
+    return a;
+}
+
 extern "C" int md_iou_aligned(MD_AOT_ARGS) {
-    if (nparam != 3) return MD_ERR_NPARAM;
-    if (!params || !dtype_is(dtypes, 0, "float32") || !dtype_is(dtypes, 1, "float32") || !dtype_is(dtypes, 2, "float32"))
-        return MD_ERR_ARG;
-    const int64_t n = dim(ndims, shapes, 0, 0), k = dim(ndims, shapes, 1, 0);
-    if (n < 0 || k < 0 || dim(ndims, shapes, 0, 1) != 4 || dim(ndims, shapes, 1, 1) != 4) return MD_ERR_ARG;
+    // extra: md_iou_attrs (NULL -> eps 0)
+    int64_t n, k;
+    Args a = pair_matrix_args(MD_ARGS, 4, n, k);
+    if (int rc = a.rc()) return rc;
     if (n == 0 || k == 0) return MD_OK;
+    if (!a.have({0, 1, 2})) return MD_ERR_ARG;
     const float eps = extra ? ((const md_iou_attrs *)extra)->eps : 0.f;
     const size_t total = (size_t)n * k;
     hipLaunchKernelGGL(iou_aligned_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const float *)params[0], (int)n, (const float *)params[1], (int)k, eps, (float *)params[2]);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+                       a.ptr<const float>(0), (int)n, a.ptr<const float>(1), (int)k, eps, a.ptr<float>(2));
+    return launched();
 }
 
 extern "C" int md_rotate_iou_eval(MD_AOT_ARGS) {
-    // in: boxes[N,5] f32, query[K,5] f32 ; out: iou[N,K] f32.  extra: md_rotate_iou_attrs (NULL -> criterion -1)
-    if (nparam != 3) return MD_ERR_NPARAM;
-    if (!params || !dtype_is(dtypes, 0, "float32") || !dtype_is(dtypes, 1, "float32") || !dtype_is(dtypes, 2, "float32"))
-        return MD_ERR_ARG;
-    const int64_t n = dim(ndims, shapes, 0, 0), k = dim(ndims, shapes, 1, 0);
-    if (n < 0 || k < 0 || dim(ndims, shapes, 0, 1) != 5 || dim(ndims, shapes, 1, 1) != 5) return MD_ERR_ARG;
+    // extra: md_rotate_iou_attrs (NULL -> criterion -1)
+    int64_t n, k;
+    Args a = pair_matrix_args(MD_ARGS, 5, n, k);
+    if (int rc = a.rc()) return rc;
     if (n == 0 || k == 0) return MD_OK;
     if (n > (1 << 24) || k > (1 << 24)) return MD_ERR_SIZE;
+    if (!a.have({0, 1, 2})) return MD_ERR_ARG;
     const int criterion = extra ? ((const md_rotate_iou_attrs *)extra)->criterion : -1;
     const size_t total = (size_t)n * k;
     hipLaunchKernelGGL(rotate_iou_eval_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const float *)params[0], (int)n, (const float *)params[1], (int)k, criterion, (float *)params[2]);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+                       a.ptr<const float>(0), (int)n, a.ptr<const float>(1), (int)k, criterion, a.ptr<float>(2));
+    return launched();
 }
 
 extern "C" int md_nms_aligned(MD_AOT_ARGS) {
-    if (nparam != 6 && nparam != 7) return MD_ERR_NPARAM;
-    if (!params || !extra) return MD_ERR_ARG;  // params[0] may be a null pointer for an empty tensor
-    if (!dtype_is(dtypes, 0, "float32") || !dtype_is(dtypes, 1, "int32") || !dtype_is(dtypes, 2, "int32") ||
-        !dtype_is(dtypes, 3, "uint8") || !dtype_is(dtypes, 4, "int32") || !dtype_is(dtypes, 5, "int32"))
-        return MD_ERR_ARG;
-    const int nd = ndims ? ndims[0] : -1;
-    if (nd != 2 && nd != 3) return MD_ERR_ARG;
-    const int64_t B = nd == 3 ? shapes[0][0] : 1, n = shapes[0][nd - 2];
-    if (shapes[0][nd - 1] != 4 || B < 0 || n < 0) return MD_ERR_ARG;
-    if (n > (1 << 16) || B > 65535) return MD_ERR_SIZE;
-    const md_nms_attrs *at = (const md_nms_attrs *)extra;
+    // in: boxes[B,N,4] f32 (or [N,4]), count[B] i32 | NULL, group[B,N] i32 | NULL ; out: keep_mask[B,N] u8, keep_idx[B,N] i32, num[B] i32 ;
+    // [workspace].  extra: md_nms_attrs (required)
+    Args a(MD_ARGS, 6, 7);
+    const md_nms_attrs *at = a.attrs<md_nms_attrs>(extra);
+    a.tensor(0, F32, 2, 3);   // (the pointer may be null for an empty tensor)
+    a.optional(1, I32); a.optional(2, I32); a.tensor(3, U8); a.tensor(4, I32); a.tensor(5, I32);
+    const int64_t B = a.rank(0) == 3 ? a.d(0, 0) : 1, n = a.d(0, -2);
+    a.require(a.d(0, -1) == 4 && B >= 0 && n >= 0);
+    a.require(n <= (1 << 16) && B <= 65535, MD_ERR_SIZE);
+    a.require((!a.given(1) || a.numel(1) >= B) && (!a.given(2) || a.numel(2) >= B * n) && a.numel(3) >= B * n && a.numel(4) >= B * n && a.numel(5) >= B);
+    if (int rc = a.rc()) return rc;
     if (at->mode < 0 || at->mode > 2) return MD_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     if (B == 0) return MD_OK;
+    if (!a.have({5})) return MD_ERR_ARG;
     if (n == 0) return hipMemsetAsync(params[5], 0, sizeof(int) * B, s) == hipSuccess ? MD_OK : MD_ERR_HIP;
-    if (!params[0]) return MD_ERR_ARG;
+    if (!a.have({0, 3, 4})) return MD_ERR_ARG;
     const int cb = (int)((n + TILE - 1) / TILE);
     const size_t mask_bytes = (size_t)B * n * cb * 8;
     // Quota prefix pass.  With an output quota (max_output > 0) the scan stops at the quota-th kept box, and a box is suppressed by
@@ -723,11 +714,11 @@ extern "C" int md_nms_aligned(MD_AOT_ARGS) {
     const bool two_level = at->max_output > 0 && n >= 2 * (int64_t)P;
     const size_t flag_bytes = two_level ? align_up((size_t)B * 4, 256) : 0;
     Scratch ws;
-    int rc = ws.acquire(mask_bytes + flag_bytes, nparam, params, ndims, shapes, 6, s);
+    int rc = ws.acquire(mask_bytes + flag_bytes, a, 6, s);
     bool tl = two_level;
     if (rc == MD_ERR_SIZE && two_level) {   // a caller workspace sized for the mask only: single full pass
         tl = false;
-        rc = ws.acquire(mask_bytes, nparam, params, ndims, shapes, 6, s);
+        rc = ws.acquire(mask_bytes, a, 6, s);
     }
     if (rc) return rc;
     unsigned long long *mask = (unsigned long long *)ws.ptr;
@@ -748,54 +739,49 @@ extern "C" int md_nms_aligned(MD_AOT_ARGS) {
     hipLaunchKernelGGL((nms_scan_kernel<int>), dim3((unsigned)B), dim3(256), scan_lds(cb), s, mask,
                        (const int *)params[1], (int)n, cb, (const float *)nullptr, 0, at->max_output, (int *)params[4],
                        (int *)params[5], (unsigned char *)params[3], 0x7fffffff, (const int *)need_full, (int *)nullptr);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+    return launched();
 }
 
 extern "C" int md_soft_nms(MD_AOT_ARGS) {
     // in: boxes[L,N,4] f32 (or [N,4]), scores[L,N] f32, count[L] i32 | NULL ; out: scores_out[L,N] f32 (0 = removed),
     //     order[L,N] i32 (selection order, leading num valid), num[L] i32.  extra: md_soft_nms_attrs
-    if (nparam != 6) return MD_ERR_NPARAM;
-    if (!params || !extra || !ndims) return MD_ERR_ARG;
-    if (!dtype_is(dtypes, 0, "float32") || !dtype_is(dtypes, 1, "float32") || !dtype_is(dtypes, 2, "int32") ||
-        !dtype_is(dtypes, 3, "float32") || !dtype_is(dtypes, 4, "int32") || !dtype_is(dtypes, 5, "int32"))
-        return MD_ERR_ARG;
-    const int nd = ndims[0];
-    if (nd != 2 && nd != 3) return MD_ERR_ARG;
-    const int64_t L = nd == 3 ? shapes[0][0] : 1, n = shapes[0][nd - 2];
-    if (shapes[0][nd - 1] != 4 || numel(ndims, shapes, 1) != L * n || numel(ndims, shapes, 3) != L * n ||
-        numel(ndims, shapes, 4) != L * n || numel(ndims, shapes, 5) != L)
-        return MD_ERR_ARG;
-    if (n > 1024) return MD_ERR_SIZE;
-    const md_soft_nms_attrs *at = (const md_soft_nms_attrs *)extra;
+    Args a(MD_ARGS, 6, 6);
+    const md_soft_nms_attrs *at = a.attrs<md_soft_nms_attrs>(extra);
+    a.tensor(0, F32, 2, 3); a.tensor(1, F32); a.optional(2, I32); a.tensor(3, F32); a.tensor(4, I32); a.tensor(5, I32);
+    const int64_t L = a.rank(0) == 3 ? a.d(0, 0) : 1, n = a.d(0, -2);
+    a.require(a.d(0, -1) == 4 && a.numel(1) == L * n && a.numel(3) == L * n && a.numel(4) == L * n && a.numel(5) == L &&
+              (!a.given(2) || a.numel(2) >= L));
+    a.require(n <= 1024, MD_ERR_SIZE);
+    if (int rc = a.rc()) return rc;
     if (at->method < 1 || at->method > 3 || !(at->sigma > 0.f)) return MD_ERR_ARG;
     if (L == 0) return MD_OK;
-    hipLaunchKernelGGL(soft_nms_kernel, dim3((unsigned)L), dim3(64), 0, (hipStream_t)stream, (const float *)params[0],
-                       (const float *)params[1], (const int *)params[2], (int)n, at->sigma, at->Nt, at->threshold, at->method,
-                       (float *)params[3], (int *)params[4], (int *)params[5]);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+    if (!a.have({3, 4, 5}) || (n > 0 && !a.have({0, 1}))) return MD_ERR_ARG;
+    hipLaunchKernelGGL(soft_nms_kernel, dim3((unsigned)L), dim3(64), 0, (hipStream_t)stream, a.ptr<const float>(0),
+                       a.ptr<const float>(1), a.ptr<const int>(2), (int)n, at->sigma, at->Nt, at->threshold, at->method,
+                       a.ptr<float>(3), a.ptr<int>(4), a.ptr<int>(5));
+    return launched();
 }
 
 extern "C" int md_circle_nms(MD_AOT_ARGS) {
-    if (nparam != 5 && nparam != 6) return MD_ERR_NPARAM;
-    if (!params || !dtype_is(dtypes, 0, "float32") || !dtype_is(dtypes, 1, "float32") || !dtype_is(dtypes, 2, "uint8") ||
-        !dtype_is(dtypes, 3, "int32") || !dtype_is(dtypes, 4, "int32"))
-        return MD_ERR_ARG;
-    const int64_t n = dim(ndims, shapes, 0, 0);
-    if (n < 0 || dim(ndims, shapes, 0, 1) != 2) return MD_ERR_ARG;
-    if (n > (1 << 16)) return MD_ERR_SIZE;
+    // in: xy[N,2] f32 sorted by score, thresh[1] f32 ; out: keep_mask[N] u8, keep_idx[N] i32, num[1] i32 ; [workspace]
+    Args a(MD_ARGS, 5, 6);
+    a.tensor(0, F32, 2); a.tensor(1, F32); a.tensor(2, U8); a.tensor(3, I32); a.tensor(4, I32);
+    const int64_t n = a.d(0, 0);
+    a.require(n >= 0 && a.d(0, 1) == 2);
+    a.require(n <= (1 << 16), MD_ERR_SIZE);
+    a.require(a.numel(1) >= 1 && a.numel(2) >= n && a.numel(3) >= n && a.numel(4) >= 1);
+    if (int rc = a.rc()) return rc;
     hipStream_t s = (hipStream_t)stream;
+    if (!a.have({4})) return MD_ERR_ARG;
     if (n == 0) return hipMemsetAsync(params[4], 0, sizeof(int), s) == hipSuccess ? MD_OK : MD_ERR_HIP;
+    if (!a.have({0, 1, 2, 3})) return MD_ERR_ARG;
     const int cb = (int)((n + TILE - 1) / TILE);
     Scratch ws;
-    int rc = ws.acquire((size_t)n * cb * 8, nparam, params, ndims, shapes, 5, s);
-    if (rc) return rc;
+    if (int rc = ws.acquire((size_t)n * cb * 8, a, 5, s)) return rc;
     unsigned long long *mask = (unsigned long long *)ws.ptr;
-    hipLaunchKernelGGL(circle_mask_kernel, dim3(cb * (cb + 1) / 2), dim3(256), 0, s, (const float *)params[0], (int)n,
-                       (const float *)params[1], mask, cb);
+    hipLaunchKernelGGL(circle_mask_kernel, dim3(cb * (cb + 1) / 2), dim3(256), 0, s, a.ptr<const float>(0), (int)n,
+                       a.ptr<const float>(1), mask, cb);
     hipLaunchKernelGGL((nms_scan_kernel<int>), dim3(1), dim3(256), scan_lds(cb), s, mask, (const int *)nullptr, (int)n,
-                       cb, (const float *)nullptr, 0, 0, (int *)params[3], (int *)params[4], (unsigned char *)params[2]);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+                       cb, (const float *)nullptr, 0, 0, a.ptr<int>(3), a.ptr<int>(4), a.ptr<unsigned char>(2));
+    return launched();
 }

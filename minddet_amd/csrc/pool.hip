@@ -204,32 +204,30 @@ __global__ __launch_bounds__(256) void sppf_pool_kernel(uint16_t *__restrict__ b
     }
 }
 
-static inline unsigned grid_for(size_t total) {
-    size_t b = (total + 255) / 256;
-    return (unsigned)(b > 8192 ? 8192 : (b == 0 ? 1 : b));
-}
+constexpr size_t POOL_GRID_CAP = 8192;   // workgroups of the grid-stride kernels of this file (md::grid1d)
 
 }  // namespace md
 
 using namespace md;
 
+// in: x[N,H,W,C] bf16 ; out: y[N,Ho,Wo,C] bf16.  extra: md_pool_attrs (required)
 extern "C" int md_maxpool2d(MD_AOT_ARGS) {
-    if (nparam != 2) return MD_ERR_NPARAM;
-    if (!params || !extra || !ndims || !shapes || ndims[0] != 4 || ndims[1] != 4) return MD_ERR_ARG;
-    if (!dtype_is(dtypes, 0, "bfloat16") || !dtype_is(dtypes, 1, "bfloat16")) return MD_ERR_ARG;
-    const md_pool_attrs *at = (const md_pool_attrs *)extra;
-    const int N = (int)shapes[0][0], H = (int)shapes[0][1], W = (int)shapes[0][2], C = (int)shapes[0][3];
-    const int Ho = (int)shapes[1][1], Wo = (int)shapes[1][2];
-    if (C % 8 || shapes[1][3] != C || shapes[1][0] != N || at->k < 1 || at->stride < 1 || at->pad < 0) return MD_ERR_ARG;
+    Args a(MD_ARGS, 2, 2);
+    const md_pool_attrs *at = a.attrs<md_pool_attrs>(extra);
+    a.tensor(0, BF16, 4); a.tensor(1, BF16, 4);
+    if (int rc = a.rc()) return rc;
+    const int N = (int)a.d(0, 0), H = (int)a.d(0, 1), W = (int)a.d(0, 2), C = (int)a.d(0, 3);
+    const int Ho = (int)a.d(1, 1), Wo = (int)a.d(1, 2);
+    if (C % 8 || a.d(1, 3) != C || a.d(1, 0) != N || at->k < 1 || at->stride < 1 || at->pad < 0) return MD_ERR_ARG;
     if (Ho != (H + 2 * at->pad - at->k) / at->stride + 1 || Wo != (W + 2 * at->pad - at->k) / at->stride + 1)
         return MD_ERR_ARG;
     const size_t total = (size_t)N * Ho * Wo * (C / 8);
     if (total == 0) return MD_OK;
-    hipLaunchKernelGGL(maxpool_nhwc_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
+    if (!a.have({0, 1})) return MD_ERR_ARG;
+    hipLaunchKernelGGL(maxpool_nhwc_kernel, dim3(grid1d(total, POOL_GRID_CAP)), dim3(256), 0, (hipStream_t)stream,
                        (const uint16_t *)params[0], (uint16_t *)params[1], N, H, W, C, Ho, Wo, at->k, at->stride, at->pad,
                        at->zero_pad);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+    return launched();
 }
 
 // channel groups (of 8 channels) per workgroup that md_sppf_pool would use for an H x W map with C channels, 0 = does not fit LDS
@@ -243,97 +241,97 @@ extern "C" int md_sppf_pool_groups(int H, int W, int C) {
 
 // in/out: buf[N,H,W,Ctot] bf16, Ctot >= 4 C: reads channels [0, C), writes [C, 4C).   extra: md_sppf_attrs {C, k}
 extern "C" int md_sppf_pool(MD_AOT_ARGS) {
-    if (nparam != 1) return MD_ERR_NPARAM;
-    if (!params || !extra || !ndims || !shapes || ndims[0] != 4 || !dtype_is(dtypes, 0, "bfloat16")) return MD_ERR_ARG;
-    const md_sppf_attrs *at = (const md_sppf_attrs *)extra;
-    const long long N = shapes[0][0], H = shapes[0][1], W = shapes[0][2], Ctot = shapes[0][3];
+    Args a(MD_ARGS, 1, 1);
+    const md_sppf_attrs *at = a.attrs<md_sppf_attrs>(extra);
+    a.tensor(0, BF16, 4);
+    if (int rc = a.rc()) return rc;
+    const long long N = a.d(0, 0), H = a.d(0, 1), W = a.d(0, 2), Ctot = a.d(0, 3);
     const int C = at->channels, k = at->k;
     if (C < 8 || C % 8 || Ctot % 8 || Ctot < 4LL * C || k < 1 || k % 2 == 0) return MD_ERR_ARG;
     if (N * H * W == 0) return MD_OK;
-    if (!params[0]) return MD_ERR_ARG;
+    if (!a.have({0})) return MD_ERR_ARG;
     if (H > 4096 || W > 4096) return MD_ERR_SIZE;
     const int cc = md_sppf_pool_groups((int)H, (int)W, C);
-    if (cc == 0 || N * (C / 8 / cc) > 0x7fffffffLL) return MD_ERR_SIZE;
+    if (cc == 0 || !fits_i32(N * (C / 8 / cc))) return MD_ERR_SIZE;
     const int lds = (int)(H * W * cc * 64);
     if (ensure_dyn_lds((const void *)sppf_pool_kernel, lds) != MD_OK) return MD_ERR_HIP;
     hipLaunchKernelGGL(sppf_pool_kernel, dim3((unsigned)(N * (C / 8 / cc))), dim3(256), lds, (hipStream_t)stream, (uint16_t *)params[0], (int)H, (int)W, C,
                        (int)Ctot, k / 2, cc);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+    return launched();
 }
 
+// in: lateral[N,H,W,C] bf16, top[N,Ht,Wt,C] bf16 ; out: y[N,H,W,C] bf16
 extern "C" int md_upsample_add(MD_AOT_ARGS) {
-    if (nparam != 3) return MD_ERR_NPARAM;
-    if (!params || !ndims || !shapes || ndims[0] != 4 || ndims[1] != 4 || ndims[2] != 4) return MD_ERR_ARG;
-    for (int i = 0; i < 3; ++i)
-        if (!dtype_is(dtypes, i, "bfloat16")) return MD_ERR_ARG;
-    const int N = (int)shapes[0][0], H = (int)shapes[0][1], W = (int)shapes[0][2], C = (int)shapes[0][3];
-    const int Ht = (int)shapes[1][1], Wt = (int)shapes[1][2];
-    if (C % 8 || shapes[1][0] != N || shapes[1][3] != C || Ht < 1 || Wt < 1) return MD_ERR_ARG;
-    for (int d = 0; d < 4; ++d)
-        if (shapes[2][d] != shapes[0][d]) return MD_ERR_ARG;
+    Args a(MD_ARGS, 3, 3);
+    a.tensor(0, BF16, 4); a.tensor(1, BF16, 4); a.tensor(2, BF16, 4);
+    const int N = (int)a.d(0, 0), H = (int)a.d(0, 1), W = (int)a.d(0, 2), C = (int)a.d(0, 3);
+    const int Ht = (int)a.d(1, 1), Wt = (int)a.d(1, 2);
+    a.require(C % 8 == 0 && a.d(1, 0) == N && a.d(1, 3) == C && Ht >= 1 && Wt >= 1 && a.same_shape(2, 0));
+    if (int rc = a.rc()) return rc;
     const size_t total = (size_t)N * H * W * (C / 8);
     if (total == 0) return MD_OK;
-    hipLaunchKernelGGL(upsample_add_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
+    if (!a.have({0, 1, 2})) return MD_ERR_ARG;
+    hipLaunchKernelGGL(upsample_add_kernel, dim3(grid1d(total, POOL_GRID_CAP)), dim3(256), 0, (hipStream_t)stream,
                        (const uint16_t *)params[0], (const uint16_t *)params[1], (uint16_t *)params[2], N, H, W, C, Ht, Wt);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+    return launched();
 }
 
 extern "C" int md_nhwc_to_nchw_f32(MD_AOT_ARGS) {
     // in x[N,H,W,C] bf16 ; out y[N,width,H,W] f32 = x[..., c0:c0+width] transposed.  extra: md_slice_attrs
-    if (nparam != 2) return MD_ERR_NPARAM;
-    if (!params || !extra || !ndims || !shapes || ndims[0] != 4 || ndims[1] != 4) return MD_ERR_ARG;
-    if (!dtype_is(dtypes, 0, "bfloat16") || !dtype_is(dtypes, 1, "float32")) return MD_ERR_ARG;
-    const md_slice_attrs *at = (const md_slice_attrs *)extra;
-    const int N = (int)shapes[0][0], H = (int)shapes[0][1], W = (int)shapes[0][2], C = (int)shapes[0][3];
+    Args a(MD_ARGS, 2, 2);
+    const md_slice_attrs *at = a.attrs<md_slice_attrs>(extra);
+    a.tensor(0, BF16, 4); a.tensor(1, F32, 4);
+    if (int rc = a.rc()) return rc;
+    const int N = (int)a.d(0, 0), H = (int)a.d(0, 1), W = (int)a.d(0, 2), C = (int)a.d(0, 3);
     if (at->c0 < 0 || at->width < 1 || at->c0 + at->width > C) return MD_ERR_ARG;
-    if (shapes[1][0] != N || shapes[1][1] != at->width || shapes[1][2] != H || shapes[1][3] != W) return MD_ERR_ARG;
+    if (a.d(1, 0) != N || a.d(1, 1) != at->width || a.d(1, 2) != H || a.d(1, 3) != W) return MD_ERR_ARG;
     if ((size_t)N * H * W == 0) return MD_OK;
+    if (!a.have({0, 1})) return MD_ERR_ARG;
     if (N > 65535) return MD_ERR_SIZE;
     const int HW = H * W;
     hipLaunchKernelGGL(nhwc_to_nchw_f32_kernel, dim3((HW + 63) / 64, (at->width + 63) / 64, N), dim3(256), 0,
                        (hipStream_t)stream, (const uint16_t *)params[0], (float *)params[1], HW, C, at->c0, at->width);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+    return launched();
 }
 
+// in: src[N,H,W,Cs] bf16 ; out: dst[N,up*H,up*W,Ctot] bf16
 static int slice_write_impl(MD_AOT_ARGS, int up) {
-    if (nparam != 2) return MD_ERR_NPARAM;
-    if (!params || !extra || !ndims || !shapes || ndims[0] != 4 || ndims[1] != 4) return MD_ERR_ARG;
-    if (!dtype_is(dtypes, 0, "bfloat16") || !dtype_is(dtypes, 1, "bfloat16")) return MD_ERR_ARG;
+    Args a(MD_ARGS, 2, 2);
     // md_concat_copy: md_slice_attrs {c0, width}; md_upsample2x: md_upsample2x_attrs {c0, width, src_c0} (the source may be a channel slice)
-    const md_upsample2x_attrs *at = (const md_upsample2x_attrs *)extra;
+    const md_upsample2x_attrs *at = a.attrs<md_upsample2x_attrs>(extra);
+    a.tensor(0, BF16, 4); a.tensor(1, BF16, 4);
+    if (int rc = a.rc()) return rc;
     const int sc0 = up == 2 ? at->src_c0 : 0;
-    const int N = (int)shapes[0][0], Hs = (int)shapes[0][1], Ws = (int)shapes[0][2], Cs = (int)shapes[0][3];
+    const int N = (int)a.d(0, 0), Hs = (int)a.d(0, 1), Ws = (int)a.d(0, 2), Cs = (int)a.d(0, 3);
     const int C = up == 2 ? at->width : Cs;
-    const int H = (int)shapes[1][1], W = (int)shapes[1][2], Ctot = (int)shapes[1][3];
-    if (shapes[1][0] != N || H != Hs * up || W != Ws * up || C < 8 || C % 8 || Cs % 8 || Ctot % 8 || at->c0 % 8 || at->c0 < 0 || sc0 % 8 || sc0 < 0 ||
+    const int H = (int)a.d(1, 1), W = (int)a.d(1, 2), Ctot = (int)a.d(1, 3);
+    if (a.d(1, 0) != N || H != Hs * up || W != Ws * up || C < 8 || C % 8 || Cs % 8 || Ctot % 8 || at->c0 % 8 || at->c0 < 0 || sc0 % 8 || sc0 < 0 ||
         at->width != C || at->c0 + C > Ctot || sc0 + C > Cs)
         return MD_ERR_ARG;
     const size_t total = (size_t)N * H * W * (C / 8);
     if (total == 0) return MD_OK;
-    hipLaunchKernelGGL(slice_write_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
+    if (!a.have({0, 1})) return MD_ERR_ARG;
+    hipLaunchKernelGGL(slice_write_kernel, dim3(grid1d(total, POOL_GRID_CAP)), dim3(256), 0, (hipStream_t)stream,
                        (const uint16_t *)params[0], (uint16_t *)params[1], N, H, W, C, Ctot, at->c0, up, Cs, sc0);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+    return launched();
 }
 extern "C" int md_concat_copy(MD_AOT_ARGS) { return slice_write_impl(nparam, params, ndims, shapes, dtypes, stream, extra, 1); }
 extern "C" int md_upsample2x(MD_AOT_ARGS) { return slice_write_impl(nparam, params, ndims, shapes, dtypes, stream, extra, 2); }
 
+// in: x[..., C] bf16 ; out: y[..., width] f32.  extra: md_slice_attrs (required)
 extern "C" int md_slice_cast(MD_AOT_ARGS) {
-    if (nparam != 2) return MD_ERR_NPARAM;
-    if (!params || !extra || !ndims || !shapes || ndims[0] < 1 || ndims[1] < 1) return MD_ERR_ARG;
-    if (!dtype_is(dtypes, 0, "bfloat16") || !dtype_is(dtypes, 1, "float32")) return MD_ERR_ARG;
-    const md_slice_attrs *at = (const md_slice_attrs *)extra;
-    const int C = (int)shapes[0][ndims[0] - 1];
-    const int64_t tot = numel(ndims, shapes, 0);
+    Args a(MD_ARGS, 2, 2);
+    const md_slice_attrs *at = a.attrs<md_slice_attrs>(extra);
+    a.tensor(0, BF16, 1, 32); a.tensor(1, F32, 1, 32);
+    if (int rc = a.rc()) return rc;
+    const int C = (int)a.d(0, -1);
+    const int64_t tot = a.numel(0);
     if (C <= 0 || at->c0 < 0 || at->width < 1 || at->c0 + at->width > C) return MD_ERR_ARG;
     const size_t M = (size_t)(tot / C);
-    if (numel(ndims, shapes, 1) != (int64_t)(M * at->width)) return MD_ERR_ARG;
+    if (a.numel(1) != (int64_t)(M * at->width)) return MD_ERR_ARG;
     if (M == 0) return MD_OK;
-    hipLaunchKernelGGL(slice_cast_kernel, dim3(grid_for(M * at->width)), dim3(256), 0, (hipStream_t)stream,
+    if (!a.have({0, 1})) return MD_ERR_ARG;
+    hipLaunchKernelGGL(slice_cast_kernel, dim3(grid1d(M * at->width, POOL_GRID_CAP)), dim3(256), 0, (hipStream_t)stream,
                        (const uint16_t *)params[0], (float *)params[1], M, C, at->c0, at->width);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+    return launched();
 }

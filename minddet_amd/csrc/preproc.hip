@@ -71,28 +71,25 @@ using namespace md;
 
 extern "C" int md_image_preprocess(MD_AOT_ARGS) {
     // in: img[N,Hs,Ws,3] uint8, mat[N,6] f32 (output pixel -> source pixel), norm[6] f32 (mean, std) ;
-    // out: y[N,Ho + 2*? ...] bf16 -- extra: md_preprocess_attrs {out_h, out_w, pad_lo, pad_hi}
-    if (nparam != 4) return MD_ERR_NPARAM;
-    if (!params || !extra || !ndims || !shapes || ndims[0] != 4 || ndims[1] != 2 || ndims[3] != 4) return MD_ERR_ARG;
-    if (!dtype_is(dtypes, 0, "uint8") || !dtype_is(dtypes, 1, "float32") || !dtype_is(dtypes, 2, "float32") ||
-        !dtype_is(dtypes, 3, "bfloat16"))
-        return MD_ERR_ARG;
-    const md_preprocess_attrs *at = (const md_preprocess_attrs *)extra;
+    // out: y[N, pad_lo + out_h + pad_hi, pad_lo + out_w + pad_hi, C = 4 | 8] bf16 -- extra: md_preprocess_attrs {out_h, out_w, pad_lo, pad_hi}
+    Args g(MD_ARGS, 4, 4);
+    const md_preprocess_attrs *at = g.attrs<md_preprocess_attrs>(extra);
+    g.tensor(0, U8, 4); g.tensor(1, F32, 2); g.tensor(2, F32); g.tensor(3, BF16, 4);
+    if (int rc = g.rc()) return rc;
     PreArgs a;
-    a.N = (int)shapes[0][0]; a.Hs = (int)shapes[0][1]; a.Ws = (int)shapes[0][2];
+    a.N = (int)g.d(0, 0); a.Hs = (int)g.d(0, 1); a.Ws = (int)g.d(0, 2);
     a.Ho = at->out_h; a.Wo = at->out_w; a.pad_lo = at->pad_lo;
-    a.Hp = (int)shapes[3][1]; a.Wp = (int)shapes[3][2]; a.C = (int)shapes[3][3];
-    if (shapes[0][3] != 3 || shapes[1][0] != a.N || shapes[1][1] != 6 || numel(ndims, shapes, 2) != 6 || shapes[3][0] != a.N)
-        return MD_ERR_ARG;
+    a.Hp = (int)g.d(3, 1); a.Wp = (int)g.d(3, 2); a.C = (int)g.d(3, 3);
+    if (g.d(0, 3) != 3 || g.d(1, 0) != a.N || g.d(1, 1) != 6 || g.numel(2) != 6 || g.d(3, 0) != a.N) return MD_ERR_ARG;
     if ((a.C != 4 && a.C != 8) || a.Ho < 1 || a.Wo < 1 || a.pad_lo < 0 || at->pad_hi < 0 || a.Hp != a.Ho + a.pad_lo + at->pad_hi ||
         a.Wp != a.Wo + a.pad_lo + at->pad_hi)
         return MD_ERR_ARG;
     const size_t total = (size_t)a.N * a.Hp * a.Wp;
     if (total == 0) return MD_OK;
-    if (!params[0] || !params[1] || !params[2] || !params[3]) return MD_ERR_ARG;
+    if (!g.have({0, 1, 2, 3})) return MD_ERR_ARG;
     a.img = (const uint8_t *)params[0]; a.mat = (const float *)params[1]; a.norm = (const float *)params[2];
     a.out = (uint16_t *)params[3];
     const size_t nb = (total + 255) / 256;
     hipLaunchKernelGGL(image_preprocess_kernel, dim3((unsigned)(nb < 0x7fffffffull ? nb : 0x7fffffffull)), dim3(256), 0, (hipStream_t)stream, a, total);
-    return hipGetLastError() == hipSuccess ? MD_OK : MD_ERR_HIP;
+    return launched();
 }

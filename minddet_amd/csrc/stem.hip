@@ -205,22 +205,19 @@ extern "C" int md_stem_layout_pad(int which) { return which == 0 ? ST_PAD_LO : S
 extern "C" int md_stem_pool(MD_AOT_ARGS) {
     // in: x[N, H+16, W+16, 4] bf16 (zero border 7 / 9, channel 3 zero), w[64, 224] bf16 (K = ky, kx 0..7, c 0..3; kx 7 and c 3
     //     zero), bias[64] f32 ; out: y[N, H/4, W/4, 64] bf16.  H % 16 == 0, W % 64 == 0.
-    if (nparam != 4) return MD_ERR_NPARAM;
-    if (!params || !ndims || !shapes || !params[1] || !params[2]) return MD_ERR_ARG;
-    if (!dtype_is(dtypes, 0, "bfloat16") || !dtype_is(dtypes, 1, "bfloat16") || !dtype_is(dtypes, 2, "float32") ||
-        !dtype_is(dtypes, 3, "bfloat16"))
-        return MD_ERR_ARG;
-    if (ndims[0] != 4 || ndims[1] != 2 || ndims[3] != 4) return MD_ERR_ARG;
-    if (shapes[0][3] != 4 || shapes[1][0] != 64 || shapes[1][1] != ST_K || numel(ndims, shapes, 2) != 64 || shapes[3][3] != 64)
-        return MD_ERR_ARG;
+    Args g(MD_ARGS, 4, 4);
+    g.tensor(0, BF16, 4); g.tensor(1, BF16, 2); g.tensor(2, F32); g.tensor(3, BF16, 4);
+    g.require(g.given(1) && g.given(2));   // (x / y may be null for an empty batch)
+    g.require(g.d(0, 3) == 4 && g.d(1, 0) == 64 && g.d(1, 1) == ST_K && g.numel(2) == 64 && g.d(3, 3) == 64);
+    if (int rc = g.rc()) return rc;
     StemArgs a;
-    a.N = (int)shapes[0][0]; a.Hp = (int)shapes[0][1]; a.Wp = (int)shapes[0][2];
+    a.N = (int)g.d(0, 0); a.Hp = (int)g.d(0, 1); a.Wp = (int)g.d(0, 2);
     const int H = a.Hp - ST_PAD_LO - ST_PAD_HI, W = a.Wp - ST_PAD_LO - ST_PAD_HI;
     if (H <= 0 || W <= 0 || H % (4 * ST_TPH) || W % (4 * ST_TPW)) return MD_ERR_ARG;
     a.Hq = H / 4; a.Wq = W / 4;
-    if (shapes[3][0] != a.N || shapes[3][1] != a.Hq || shapes[3][2] != a.Wq) return MD_ERR_ARG;
+    if (g.d(3, 0) != a.N || g.d(3, 1) != a.Hq || g.d(3, 2) != a.Wq) return MD_ERR_ARG;
     if (a.N == 0) return MD_OK;
-    if (!params[0] || !params[3]) return MD_ERR_ARG;
+    if (!g.have({0, 3})) return MD_ERR_ARG;
     const long long x_bytes = (long long)a.N * a.Hp * a.Wp * 8;
     if (x_bytes >= 0x7fff0000LL) return MD_ERR_SIZE;
     a.x = (const uint16_t *)params[0]; a.w = (const uint16_t *)params[1]; a.bias = (const float *)params[2];
@@ -228,10 +225,10 @@ extern "C" int md_stem_pool(MD_AOT_ARGS) {
     a.x_bytes = (unsigned)x_bytes;
     a.tiles_x = a.Wq / ST_TPW; a.tiles_y = a.Hq / ST_TPH;
     const long long n_tiles = (long long)a.N * a.tiles_x * a.tiles_y;
-    if (n_tiles > 0x7fffffffLL) return MD_ERR_SIZE;
+    if (!fits_i32(n_tiles)) return MD_ERR_SIZE;
     a.n_tiles = (int)n_tiles;
     if (ensure_dyn_lds((const void *)stem_pool_kernel, ST_LDS) != MD_OK) return MD_ERR_HIP;
     const int grid = a.n_tiles < 256 * 2 ? a.n_tiles : 256 * 2;  // persistent: two workgroups per CU
     hipLaunchKernelGGL(stem_pool_kernel, dim3((unsigned)grid), dim3(256), ST_LDS, (hipStream_t)stream, a);
-    return hipGetLastError() == hipSuccess ? MD_OK : MD_ERR_HIP;
+    return launched();
 }

@@ -157,7 +157,7 @@ static int launch_stem_conv(StemConvArgs &a, hipStream_t s) {
     if (lds > 64 * 1024 && ensure_dyn_lds((const void *)k, lds) != MD_OK) return MD_ERR_HIP;
     const int grid = a.n_tiles < 256 * 3 ? a.n_tiles : 256 * 3;   // persistent: up to three workgroups per CU
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(256), lds, s, a);
-    return hipGetLastError() == hipSuccess ? MD_OK : MD_ERR_HIP;
+    return launched();
 }
 
 }  // namespace md
@@ -168,25 +168,22 @@ using namespace md;
 //      kh = 6: kx' = kx + 1 in 0..7 (columns 0 and 7 zero), kh = 3: kx' = kx in 0..3 (column 3 zero); c = 3 zero; bias[COUT] f32
 // out: y[N, H/2, W/2, COUT] bf16, COUT = 32 or 64.   H % 16 == 0, W % 64 == 0.   extra: md_stem_conv_attrs {kh (6 | 3), act}
 extern "C" int md_stem_conv(MD_AOT_ARGS) {
-    if (nparam != 4) return MD_ERR_NPARAM;
-    if (!params || !extra || !ndims || !shapes || !params[1] || !params[2]) return MD_ERR_ARG;
-    if (!dtype_is(dtypes, 0, "bfloat16") || !dtype_is(dtypes, 1, "bfloat16") || !dtype_is(dtypes, 2, "float32") ||
-        !dtype_is(dtypes, 3, "bfloat16"))
-        return MD_ERR_ARG;
-    if (ndims[0] != 4 || ndims[1] != 2 || ndims[3] != 4) return MD_ERR_ARG;
-    const md_stem_conv_attrs *at = (const md_stem_conv_attrs *)extra;
+    Args g(MD_ARGS, 4, 4);
+    const md_stem_conv_attrs *at = g.attrs<md_stem_conv_attrs>(extra);
+    g.tensor(0, BF16, 4); g.tensor(1, BF16, 2); g.tensor(2, F32); g.tensor(3, BF16, 4);
+    g.require(g.given(1) && g.given(2));   // (x / y may be null for an empty batch)
+    if (int rc = g.rc()) return rc;
     if ((at->kh != 6 && at->kh != 3) || at->act < 0 || at->act > 2) return MD_ERR_ARG;
-    const int64_t cout = shapes[3][3], ktot = at->kh == 6 ? 192 : 48;
-    if ((cout != 32 && cout != 64) || shapes[0][3] != 4 || shapes[1][0] != cout || shapes[1][1] != ktot || numel(ndims, shapes, 2) != cout)
-        return MD_ERR_ARG;
+    const int64_t cout = g.d(3, 3), ktot = at->kh == 6 ? 192 : 48;
+    if ((cout != 32 && cout != 64) || g.d(0, 3) != 4 || g.d(1, 0) != cout || g.d(1, 1) != ktot || g.numel(2) != cout) return MD_ERR_ARG;
     StemConvArgs a;
-    a.N = (int)shapes[0][0]; a.Hp = (int)shapes[0][1]; a.Wp = (int)shapes[0][2];
+    a.N = (int)g.d(0, 0); a.Hp = (int)g.d(0, 1); a.Wp = (int)g.d(0, 2);
     const int H = a.Hp - 16, W = a.Wp - 16;
     if (H <= 0 || W <= 0 || H % (2 * SC_TH) || W % (2 * SC_TW)) return MD_ERR_ARG;
     a.Ho = H / 2; a.Wo = W / 2;
-    if (shapes[3][0] != a.N || shapes[3][1] != a.Ho || shapes[3][2] != a.Wo) return MD_ERR_ARG;
+    if (g.d(3, 0) != a.N || g.d(3, 1) != a.Ho || g.d(3, 2) != a.Wo) return MD_ERR_ARG;
     if (a.N == 0) return MD_OK;
-    if (!params[0] || !params[3]) return MD_ERR_ARG;
+    if (!g.have({0, 3})) return MD_ERR_ARG;
     const long long x_bytes = (long long)a.N * a.Hp * a.Wp * 8;
     if (x_bytes >= 0x7fff0000LL) return MD_ERR_SIZE;
     a.x = (const uint16_t *)params[0]; a.w = (const uint16_t *)params[1]; a.bias = (const float *)params[2];
@@ -195,7 +192,7 @@ extern "C" int md_stem_conv(MD_AOT_ARGS) {
     a.act = at->act;
     a.tiles_x = a.Wo / SC_TW; a.tiles_y = a.Ho / SC_TH;
     const long long n_tiles = (long long)a.N * a.tiles_x * a.tiles_y;
-    if (n_tiles > 0x7fffffffLL) return MD_ERR_SIZE;
+    if (!fits_i32(n_tiles)) return MD_ERR_SIZE;
     a.n_tiles = (int)n_tiles;
     hipStream_t s = (hipStream_t)stream;
     if (at->kh == 6) return cout == 32 ? launch_stem_conv<6, 32>(a, s) : launch_stem_conv<6, 64>(a, s);

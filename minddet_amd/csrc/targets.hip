@@ -125,26 +125,22 @@ using namespace md;
 extern "C" int md_assign_targets(MD_AOT_ARGS) {
     // in : anchors[A,7] f32, gt[G,7] f32, gt_cls[G] i32, matched_thr[A] f32, unmatched_thr[A] f32, mask[A] u8 | NULL
     // out: labels[A] i32, bbox_targets[A,7] f32, bbox_outside_weights[A] f32, gt_ids[A] i32 ; [workspace >= 4*G bytes]
-    if (nparam != 10 && nparam != 11) return MD_ERR_NPARAM;
-    if (!params || !ndims || !shapes) return MD_ERR_ARG;
-    if (!dtype_is(dtypes, 0, "float32") || !dtype_is(dtypes, 3, "float32") || !dtype_is(dtypes, 4, "float32") ||
-        !dtype_is(dtypes, 6, "int32") || !dtype_is(dtypes, 7, "float32") || !dtype_is(dtypes, 8, "float32") || !dtype_is(dtypes, 9, "int32"))
-        return MD_ERR_ARG;
-    const int64_t A = dim(ndims, shapes, 0, 0), G = params[1] ? dim(ndims, shapes, 1, 0) : 0;
-    if (A < 0 || G < 0 || dim(ndims, shapes, 0, 1) != 7 || (G > 0 && dim(ndims, shapes, 1, 1) != 7)) return MD_ERR_ARG;
-    if (numel(ndims, shapes, 3) != A || numel(ndims, shapes, 4) != A || numel(ndims, shapes, 6) != A || numel(ndims, shapes, 7) != A * 7 ||
-        numel(ndims, shapes, 8) != A || numel(ndims, shapes, 9) != A || (G > 0 && numel(ndims, shapes, 2) != G))
-        return MD_ERR_ARG;
-    if (params[5] && (!dtype_is(dtypes, 5, "uint8") || numel(ndims, shapes, 5) != A)) return MD_ERR_ARG;
-    if (G > 0 && (!dtype_is(dtypes, 1, "float32") || !dtype_is(dtypes, 2, "int32"))) return MD_ERR_ARG;
+    // (gt / gt_cls: NULL pointers, or G = 0, for an image without ground truth)
+    Args a(MD_ARGS, 10, 11);
+    a.tensor(0, F32, 2); a.optional(1, nullptr, 1, 32); a.tensor(3, F32); a.tensor(4, F32); a.optional(5, U8);
+    a.tensor(6, I32); a.tensor(7, F32); a.tensor(8, F32); a.tensor(9, I32);
+    const int64_t A = a.d(0, 0), G = a.given(1) ? a.d(1, 0) : 0;
+    if (G > 0) { a.tensor(1, F32, 2); a.tensor(2, I32); }
+    a.require(A >= 0 && G >= 0 && a.d(0, 1) == 7 && (G == 0 || a.d(1, 1) == 7));
+    a.require(a.numel(3) == A && a.numel(4) == A && a.numel(6) == A && a.numel(7) == A * 7 && a.numel(8) == A && a.numel(9) == A &&
+              (G == 0 || a.numel(2) == G) && (!a.given(5) || a.numel(5) == A));
+    if (int rc = a.rc()) return rc;
     if (A == 0) return MD_OK;
     if (A > 0x7fffff00LL || G > TG_MAX_GT) return MD_ERR_SIZE;
-    if (!params[0] || !params[3] || !params[4] || !params[6] || !params[7] || !params[8] || !params[9] || (G > 0 && (!params[1] || !params[2])))
-        return MD_ERR_ARG;
+    if (!a.have({0, 3, 4, 6, 7, 8, 9}) || (G > 0 && !a.have({1, 2}))) return MD_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     Scratch ws;
-    const int rc = ws.acquire((size_t)(G > 0 ? G : 1) * 4, nparam, params, ndims, shapes, 10, s);
-    if (rc != MD_OK) return rc;
+    if (int rc = ws.acquire((size_t)(G > 0 ? G : 1) * 4, a, 10, s)) return rc;
     unsigned *colmax = (unsigned *)ws.ptr;
     const unsigned blocks = (unsigned)((A + 255) / 256);
     if (G > 0) {
@@ -155,6 +151,5 @@ extern "C" int md_assign_targets(MD_AOT_ARGS) {
     hipLaunchKernelGGL(target_assign_kernel, dim3(blocks), dim3(256), 0, s, (const float *)params[0], (int)A, (const float *)params[1], (int)G,
                        (const int *)params[2], (const float *)params[3], (const float *)params[4], (const uint8_t *)params[5], colmax,
                        (int *)params[6], (float *)params[7], (float *)params[8], (int *)params[9]);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+    return launched();
 }

@@ -200,129 +200,118 @@ using namespace md;
 
 extern "C" int md_rpn_decode(MD_AOT_ARGS) {
     // in: head[B,H,W,Cp] bf16, anchors[HWA,4] f32, idx[B,k] i32, cnt[B] i32 ; out: boxes[B,k,4] f32, scores[B,k] f32
-    if (nparam != 6) return MD_ERR_NPARAM;
-    if (!params || !extra || !ndims || ndims[0] != 4 || ndims[2] != 2) return MD_ERR_ARG;
-    if (!dtype_is(dtypes, 0, "bfloat16") || !dtype_is(dtypes, 1, "float32") || !dtype_is(dtypes, 2, "int32") ||
-        !dtype_is(dtypes, 3, "int32") || !dtype_is(dtypes, 4, "float32") || !dtype_is(dtypes, 5, "float32"))
-        return MD_ERR_ARG;
-    const md_rpn_decode_attrs *at = (const md_rpn_decode_attrs *)extra;
-    const int B = (int)shapes[0][0], HW = (int)(shapes[0][1] * shapes[0][2]), Cp = (int)shapes[0][3];
-    const int k = (int)shapes[2][1], A = at->num_anchors;
-    if (shapes[2][0] != B || A < 1 || 5 * A > Cp || numel(ndims, shapes, 1) != (int64_t)HW * A * 4) return MD_ERR_ARG;
-    if (numel(ndims, shapes, 4) != (int64_t)B * k * 4 || numel(ndims, shapes, 5) != (int64_t)B * k) return MD_ERR_ARG;
+    Args a(MD_ARGS, 6, 6);
+    const md_rpn_decode_attrs *at = a.attrs<md_rpn_decode_attrs>(extra);
+    a.tensor(0, BF16, 4); a.tensor(1, F32); a.tensor(2, I32, 2); a.tensor(3, I32); a.tensor(4, F32); a.tensor(5, F32);
+    if (int rc = a.rc()) return rc;
+    const int B = (int)a.d(0, 0), HW = (int)(a.d(0, 1) * a.d(0, 2)), Cp = (int)a.d(0, 3);
+    const int k = (int)a.d(2, 1), A = at->num_anchors;
+    if (a.d(2, 0) != B || A < 1 || 5 * A > Cp || a.numel(1) != (int64_t)HW * A * 4) return MD_ERR_ARG;
+    if (a.numel(4) != (int64_t)B * k * 4 || a.numel(5) != (int64_t)B * k || a.numel(3) < B) return MD_ERR_ARG;
     if (B * k == 0) return MD_OK;
+    if (!a.have({0, 1, 2, 3, 4, 5})) return MD_ERR_ARG;
     DecodeP p;
     fill_decode(p, at->decode);
     hipLaunchKernelGGL(rpn_decode_kernel, dim3((B * k + 255) / 256), dim3(256), 0, (hipStream_t)stream,
                        (const uint16_t *)params[0], (const float *)params[1], (const int *)params[2], (const int *)params[3],
                        B, k, HW, A, Cp, p, (float *)params[4], (float *)params[5]);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+    return launched();
 }
 
 extern "C" int md_rpn_merge(MD_AOT_ARGS) {
     // in: boxes[L,B,k,4] f32, scores[L,B,k] f32, keep[L,B,k] u8 ; out: mboxes[B,L*k,4] f32, mscores[B,L*k] f32
-    if (nparam != 5) return MD_ERR_NPARAM;
-    if (!params || !ndims || ndims[1] != 3) return MD_ERR_ARG;
-    if (!dtype_is(dtypes, 0, "float32") || !dtype_is(dtypes, 1, "float32") || !dtype_is(dtypes, 2, "uint8") ||
-        !dtype_is(dtypes, 3, "float32") || !dtype_is(dtypes, 4, "float32"))
-        return MD_ERR_ARG;
-    const int L = (int)shapes[1][0], B = (int)shapes[1][1], k = (int)shapes[1][2];
+    Args a(MD_ARGS, 5, 5);
+    a.tensor(0, F32); a.tensor(1, F32, 3); a.tensor(2, U8); a.tensor(3, F32); a.tensor(4, F32);
+    const int L = (int)a.d(1, 0), B = (int)a.d(1, 1), k = (int)a.d(1, 2);
     const int64_t tot = (int64_t)L * B * k;
-    if (numel(ndims, shapes, 0) != tot * 4 || numel(ndims, shapes, 2) != tot || numel(ndims, shapes, 3) != tot * 4 ||
-        numel(ndims, shapes, 4) != tot)
-        return MD_ERR_ARG;
+    a.require(a.numel(0) == tot * 4 && a.numel(2) == tot && a.numel(3) == tot * 4 && a.numel(4) == tot);
+    if (int rc = a.rc()) return rc;
     if (tot == 0) return MD_OK;
+    if (!a.have({0, 1, 2, 3, 4})) return MD_ERR_ARG;
     hipLaunchKernelGGL(rpn_merge_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        (const float *)params[0], (const float *)params[1], (const unsigned char *)params[2], L, B, k,
                        (float *)params[3], (float *)params[4]);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+    return launched();
 }
 
 extern "C" int md_make_rois(MD_AOT_ARGS) {
     // in: mboxes[B,P,4] f32, topv[B,post] f32, topi[B,post] i32, cnt[B] i32 ; out: rois[B*post,5] f32, scores[B*post] f32
-    if (nparam != 6) return MD_ERR_NPARAM;
-    if (!params || !ndims || ndims[0] != 3 || ndims[1] != 2) return MD_ERR_ARG;
-    if (!dtype_is(dtypes, 0, "float32") || !dtype_is(dtypes, 1, "float32") || !dtype_is(dtypes, 2, "int32") ||
-        !dtype_is(dtypes, 3, "int32") || !dtype_is(dtypes, 4, "float32") || !dtype_is(dtypes, 5, "float32"))
-        return MD_ERR_ARG;
-    const int B = (int)shapes[0][0], per = (int)shapes[0][1], post = (int)shapes[1][1];
-    if (shapes[1][0] != B || numel(ndims, shapes, 4) != (int64_t)B * post * 5 || numel(ndims, shapes, 5) != (int64_t)B * post)
-        return MD_ERR_ARG;
+    Args a(MD_ARGS, 6, 6);
+    a.tensor(0, F32, 3); a.tensor(1, F32, 2); a.tensor(2, I32); a.tensor(3, I32); a.tensor(4, F32); a.tensor(5, F32);
+    const int B = (int)a.d(0, 0), per = (int)a.d(0, 1), post = (int)a.d(1, 1);
+    a.require(a.d(1, 0) == B && a.numel(4) == (int64_t)B * post * 5 && a.numel(5) == (int64_t)B * post);
+    a.require(a.numel(0) >= (int64_t)B * per * 4 && a.numel(2) >= (int64_t)B * post && a.numel(3) >= B);
+    if (int rc = a.rc()) return rc;
     if (B * post == 0) return MD_OK;
+    if (!a.have({0, 1, 2, 3, 4, 5})) return MD_ERR_ARG;
     hipLaunchKernelGGL(make_rois_kernel, dim3((B * post + 255) / 256), dim3(256), 0, (hipStream_t)stream,
                        (const float *)params[0], (const float *)params[1], (const int *)params[2], (const int *)params[3],
                        B, post, per, (float *)params[4], (float *)params[5]);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+    return launched();
 }
 
 extern "C" int md_rcnn_scores(MD_AOT_ARGS) {
     // in: cls_reg[R,Cp] bf16, roi_cnt[B] i32 ; out: cand[B, post*nc] f32
-    if (nparam != 3) return MD_ERR_NPARAM;
-    if (!params || !extra || !ndims || ndims[0] != 2) return MD_ERR_ARG;
-    if (!dtype_is(dtypes, 0, "bfloat16") || !dtype_is(dtypes, 1, "int32") || !dtype_is(dtypes, 2, "float32")) return MD_ERR_ARG;
-    const md_rcnn_attrs *at = (const md_rcnn_attrs *)extra;
-    const int R = (int)shapes[0][0], Cp = (int)shapes[0][1];
-    const int B = (int)numel(ndims, shapes, 1);
+    Args a(MD_ARGS, 3, 3);
+    const md_rcnn_attrs *at = a.attrs<md_rcnn_attrs>(extra);
+    a.tensor(0, BF16, 2); a.tensor(1, I32); a.tensor(2, F32);
+    if (int rc = a.rc()) return rc;
+    const int R = (int)a.d(0, 0), Cp = (int)a.d(0, 1);
+    const int B = (int)a.numel(1);
     if (B < 1 || R % B || at->num_classes < 1 || at->num_classes > 127 || at->num_classes + 1 > Cp) return MD_ERR_ARG;
-    if (numel(ndims, shapes, 2) != (int64_t)R * at->num_classes) return MD_ERR_ARG;
+    if (a.numel(2) != (int64_t)R * at->num_classes) return MD_ERR_ARG;
     if (R == 0) return MD_OK;
+    if (!a.have({0, 1, 2})) return MD_ERR_ARG;
     hipLaunchKernelGGL(rcnn_scores_kernel, dim3((R + 3) / 4), dim3(256), 0, (hipStream_t)stream,
                        (const uint16_t *)params[0], (const int *)params[1], R, R / B, at->num_classes, Cp, at->score_thr,
                        (float *)params[2]);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+    return launched();
 }
 
 extern "C" int md_rcnn_decode_selected(MD_AOT_ARGS) {
     // in: cls_reg[R,Cp] bf16, rois[R,5] f32, sel_idx[B,npre] i32, sel_cnt[B] i32 ; out: boxes[B,npre,4] f32, labels[B,npre] i32
-    if (nparam != 6) return MD_ERR_NPARAM;
-    if (!params || !extra || !ndims || ndims[0] != 2 || ndims[2] != 2) return MD_ERR_ARG;
-    if (!dtype_is(dtypes, 0, "bfloat16") || !dtype_is(dtypes, 1, "float32") || !dtype_is(dtypes, 2, "int32") ||
-        !dtype_is(dtypes, 3, "int32") || !dtype_is(dtypes, 4, "float32") || !dtype_is(dtypes, 5, "int32"))
-        return MD_ERR_ARG;
-    const md_rcnn_attrs *at = (const md_rcnn_attrs *)extra;
-    const int R = (int)shapes[0][0], Cp = (int)shapes[0][1], B = (int)shapes[2][0], npre = (int)shapes[2][1];
+    Args a(MD_ARGS, 6, 6);
+    const md_rcnn_attrs *at = a.attrs<md_rcnn_attrs>(extra);
+    a.tensor(0, BF16, 2); a.tensor(1, F32); a.tensor(2, I32, 2); a.tensor(3, I32); a.tensor(4, F32); a.tensor(5, I32);
+    if (int rc = a.rc()) return rc;
+    const int R = (int)a.d(0, 0), Cp = (int)a.d(0, 1), B = (int)a.d(2, 0), npre = (int)a.d(2, 1);
     if (B < 1 || R % B || at->reg_offset + 4 * at->num_classes > Cp) return MD_ERR_ARG;
-    if (numel(ndims, shapes, 4) != (int64_t)B * npre * 4 || numel(ndims, shapes, 5) != (int64_t)B * npre) return MD_ERR_ARG;
+    if (a.numel(4) != (int64_t)B * npre * 4 || a.numel(5) != (int64_t)B * npre || a.numel(1) < (int64_t)R * 5 || a.numel(3) < B) return MD_ERR_ARG;
     if (B * npre == 0) return MD_OK;
+    if (!a.have({0, 1, 2, 3, 4, 5})) return MD_ERR_ARG;
     DecodeP p;
     fill_decode(p, at->decode);
     hipLaunchKernelGGL(rcnn_decode_selected_kernel, dim3((B * npre + 255) / 256), dim3(256), 0, (hipStream_t)stream,
                        (const uint16_t *)params[0], (const float *)params[1], (const int *)params[2], (const int *)params[3],
                        B, npre, R / B, at->num_classes, Cp, at->reg_offset, p, (float *)params[4], (int *)params[5]);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+    return launched();
 }
 
 extern "C" int md_pack_detections(MD_AOT_ARGS) {
     // in: boxes[B,npre,4] f32, scores[B,npre] f32, labels[B,npre] i32, keep_idx[B,npre] i32, num[B] i32 [, sel_cnt[B] i32]
     // out: dets[B,max_det,6] f32, count[B] i32 [, status[B] i32 (in/out: bit 0 OR-ed in)]
-    if (nparam != 7 && nparam != 9) return MD_ERR_NPARAM;
+    Args a(MD_ARGS, 7, 9);
+    a.require(nparam != 8, MD_ERR_NPARAM);
     const int o = nparam == 9 ? 6 : 5;   // index of dets
-    if (!params || !ndims || ndims[1] != 2 || ndims[o] != 3) return MD_ERR_ARG;
-    if (!dtype_is(dtypes, 0, "float32") || !dtype_is(dtypes, 1, "float32") || !dtype_is(dtypes, 2, "int32") ||
-        !dtype_is(dtypes, 3, "int32") || !dtype_is(dtypes, 4, "int32") || !dtype_is(dtypes, o, "float32") ||
-        !dtype_is(dtypes, o + 1, "int32"))
-        return MD_ERR_ARG;
-    const int B = (int)shapes[1][0], npre = (int)shapes[1][1], max_det = (int)shapes[o][1];
-    if (shapes[o][0] != B || shapes[o][2] != 6) return MD_ERR_ARG;
-    const int *sel_cnt = nullptr;
-    int *status = nullptr;
+    a.tensor(0, F32); a.tensor(1, F32, 2); a.tensor(2, I32); a.tensor(3, I32); a.tensor(4, I32); a.tensor(o, F32, 3); a.tensor(o + 1, I32);
+    const int B = (int)a.d(1, 0), npre = (int)a.d(1, 1), max_det = (int)a.d(o, 1);
+    a.require(a.d(o, 0) == B && a.d(o, 2) == 6);
+    a.require(a.numel(0) >= (int64_t)B * npre * 4 && a.numel(2) >= (int64_t)B * npre && a.numel(3) >= (int64_t)B * npre && a.numel(4) >= B &&
+              a.numel(o + 1) >= B);
     if (nparam == 9) {
-        if (!dtype_is(dtypes, 5, "int32") || !dtype_is(dtypes, 8, "int32") || numel(ndims, shapes, 5) != B || numel(ndims, shapes, 8) != B ||
-            (B > 0 && (!params[5] || !params[8])))
-            return MD_ERR_ARG;
-        sel_cnt = (const int *)params[5]; status = (int *)params[8];
+        a.tensor(5, I32); a.tensor(8, I32);
+        a.require(a.numel(5) == B && a.numel(8) == B);
+        if (B > 0) a.have({5, 8});
     }
+    if (int rc = a.rc()) return rc;
+    const int *sel_cnt = nparam == 9 ? a.ptr<const int>(5) : nullptr;
+    int *status = nparam == 9 ? a.ptr<int>(8) : nullptr;
     if (B * max_det == 0) return MD_OK;
+    if (!a.have({0, 1, 2, 3, 4, o, o + 1})) return MD_ERR_ARG;
     hipLaunchKernelGGL(pack_dets_kernel, dim3((B * max_det + 255) / 256), dim3(256), 0, (hipStream_t)stream,
                        (const float *)params[0], (const float *)params[1], (const int *)params[2], (const int *)params[3],
                        (const int *)params[4], B, npre, max_det, (float *)params[o], (int *)params[o + 1], sel_cnt, status);
-    MD_HIP_TRY(hipGetLastError());
-    return MD_OK;
+    return launched();
 }
 
 // ------------------------------------------------------------------------------------------ Mask R-CNN mask select
@@ -349,19 +338,20 @@ __global__ void mask_select_kernel(const uint16_t *__restrict__ logits, const fl
 
 extern "C" int md_mask_select(MD_AOT_ARGS) {
     // in: logits[R,S,S,Cpad] bf16, dets[R,6] f32 ; out: masks[R,S,S] f32 ; extra: int32 num_classes
-    if (nparam != 3) return MD_ERR_NPARAM;
-    if (!params || !extra || !ndims || !shapes || ndims[0] != 4) return MD_ERR_ARG;
-    if (!md::dtype_is(dtypes, 0, "bfloat16") || !md::dtype_is(dtypes, 1, "float32") || !md::dtype_is(dtypes, 2, "float32")) return MD_ERR_ARG;
-    const int64_t R = shapes[0][0], S = shapes[0][1], C = shapes[0][3];
-    const int nc = *(const int32_t *)extra;
-    if (shapes[0][2] != S || nc < 1 || nc > C || md::numel(ndims, shapes, 1) != R * 6 || md::numel(ndims, shapes, 2) != R * S * S) return MD_ERR_ARG;
+    md::Args a(MD_ARGS, 3, 3);
+    const int32_t *num_classes = a.attrs<int32_t>(extra);
+    a.tensor(0, md::BF16, 4); a.tensor(1, md::F32); a.tensor(2, md::F32);
+    if (int rc = a.rc()) return rc;
+    const int64_t R = a.d(0, 0), S = a.d(0, 1), C = a.d(0, 3);
+    const int nc = *num_classes;
+    if (a.d(0, 2) != S || nc < 1 || nc > C || a.numel(1) != R * 6 || a.numel(2) != R * S * S) return MD_ERR_ARG;
     if (R * S * S == 0) return MD_OK;
-    if (!params[0] || !params[1] || !params[2]) return MD_ERR_ARG;
+    if (!a.have({0, 1, 2})) return MD_ERR_ARG;
     const size_t total = (size_t)R * S * S;
     const size_t nb = (total + 255) / 256;
     hipLaunchKernelGGL(md::mask_select_kernel, dim3((unsigned)(nb < 65535u * 64 ? nb : 65535u * 64)), dim3(256), 0, (hipStream_t)stream,
                        (const uint16_t *)params[0], (const float *)params[1], (int)R, (int)(S * S), (int)C, nc, (float *)params[2]);
-    return hipGetLastError() == hipSuccess ? MD_OK : MD_ERR_HIP;
+    return md::launched();
 }
 
 
@@ -444,23 +434,22 @@ __global__ __launch_bounds__(256) void paste_masks_kernel(PasteArgs a) {
 
 extern "C" int md_paste_masks(MD_AOT_ARGS) {
     // in: masks[R,S,S] f32, dets[R,6] f32 ; out: bits != 0: words[R,H,ceil(W/32)] i32 (bit j of word k = pixel 32 k + j), else mask[R,H,W] u8
-    if (nparam != 3) return MD_ERR_NPARAM;
-    if (!params || !extra || !ndims || !shapes || ndims[0] != 3 || ndims[2] != 3) return MD_ERR_ARG;
-    const md_paste_attrs *at = (const md_paste_attrs *)extra;
-    if (!md::dtype_is(dtypes, 0, "float32") || !md::dtype_is(dtypes, 1, "float32") || !md::dtype_is(dtypes, 2, at->bits ? "int32" : "uint8"))
-        return MD_ERR_ARG;
-    const int64_t R = shapes[0][0], S = shapes[0][1], H = at->img_h, W = at->img_w;
-    if (shapes[0][2] != S || S < 1 || S > 1024 || H < 1 || W < 1 || H > 32768 || W > 32768 || md::numel(ndims, shapes, 1) != R * 6) return MD_ERR_ARG;
+    md::Args g(MD_ARGS, 3, 3);
+    const md_paste_attrs *at = g.attrs<md_paste_attrs>(extra);
+    g.tensor(0, md::F32, 3); g.tensor(1, md::F32); g.tensor(2, at && at->bits ? md::I32 : md::U8, 3);
+    if (int rc = g.rc()) return rc;
+    const int64_t R = g.d(0, 0), S = g.d(0, 1), H = at->img_h, W = at->img_w;
+    if (g.d(0, 2) != S || S < 1 || S > 1024 || H < 1 || W < 1 || H > 32768 || W > 32768 || g.numel(1) != R * 6) return MD_ERR_ARG;
     const int64_t Ww = at->bits ? (W + 31) / 32 : (W + 3) / 4;
-    if (shapes[2][0] != R || shapes[2][1] != H || shapes[2][2] != (at->bits ? Ww : W)) return MD_ERR_ARG;
+    if (g.d(2, 0) != R || g.d(2, 1) != H || g.d(2, 2) != (at->bits ? Ww : W)) return MD_ERR_ARG;
     if (R == 0) return MD_OK;
-    if (!params[0] || !params[1] || !params[2]) return MD_ERR_ARG;
+    if (!g.have({0, 1, 2})) return MD_ERR_ARG;
     // the kernel's grid-stride index is 32-bit: e += grid * 256 must not wrap below `total` (r03 ADVICE: it would restart the loop and never end)
-    if (R > 0x7fffffffLL / 6 || (long long)R * H * Ww > 0xffffffffLL - 256LL * 64 * 256) return MD_ERR_SIZE;
+    if (!md::fits_i32(R * 6) || (long long)R * H * Ww > 0xffffffffLL - 256LL * 64 * 256) return MD_ERR_SIZE;
     md::PasteArgs a = {(const float *)params[0], (const float *)params[1], params[2], (int)R, (int)S, (int)H, (int)W, (int)Ww, at->threshold};
     const size_t total = (size_t)R * H * Ww, nb = (total + 255) / 256;
     const unsigned grid = (unsigned)(nb < 256u * 64 ? nb : 256u * 64);   // grid-stride: 64 blocks per CU
     if (at->bits) hipLaunchKernelGGL(md::paste_masks_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(md::paste_masks_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
-    return hipGetLastError() == hipSuccess ? MD_OK : MD_ERR_HIP;
+    return md::launched();
 }

@@ -983,7 +983,8 @@ class C3(Module):
 
     def __call__(self, x, x_c_off=None, out=None, c_off=0):
         """No copies: one launch computes [cv1(x) | cv2(x)] into the concat buffer; every bottleneck then updates channels [0, c_).
-        With 64 or 128 channels a bottleneck is ONE md_c3_pair launch (its 1x1 output stays in LDS; bit-identical): it cannot run in
+        With 32, 64 or 128 channels a bottleneck is ONE md_c3_pair launch (its 1x1 output stays in LDS; bit-identical; weights as
+        md_conv2d packs them: w1[C, roundup(C, 64)], w2[C, roundup(9 C, 64)], korder 0 for C = 32, korder 1 for C = 64 (where the two coincide) and 128): it cannot run in
         place (a tile's halo pixels are other tiles' outputs), so the blocks alternate between two concat buffers and the last one
         carries the cv2(x) half along when it ends in the second.  Other widths: two launches per bottleneck, in place (the 1x1 reads the
         slice, the 3x3 adds the slice as residual and writes it back: each element is read and written by the same thread)."""

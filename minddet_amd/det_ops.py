@@ -18,6 +18,7 @@ synchronises.  There is no CPU path.
 import ctypes
 import math
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -873,3 +874,91 @@ class _Yolo8Attrs(ctypes.Structure):
 def yolov8_decode(head, boxes, scores, labels, num_classes, reg_max, stride, conf_thres, out_offset, out_total):
     _lib.call("md_yolov8_decode", [head, boxes, scores, labels],
               extra=_Yolo8Attrs(int(num_classes), int(reg_max), float(stride), float(conf_thres), int(out_offset), int(out_total)))
+
+
+# ----------------------------------------------------------------------------- point-cloud front end (csrc/pillars.hip)
+class _VoxelizeAttrs(ctypes.Structure):
+    _fields_ = [("voxel_size", ctypes.c_float * 3), ("range", ctypes.c_float * 6), ("max_points", ctypes.c_int32),
+                ("max_voxels", ctypes.c_int32)]
+
+
+class _PillarEncodeAttrs(ctypes.Structure):
+    _fields_ = [("vx", ctypes.c_float), ("vy", ctypes.c_float), ("x_offset", ctypes.c_float), ("y_offset", ctypes.c_float),
+                ("with_distance", ctypes.c_int32), ("virtual_points", ctypes.c_int32)]
+
+
+def voxel_grid(voxel_size, pc_range):
+    """cells per axis (x, y, z) as the reference computes them: round((max - min) / voxel_size) in fp32 (point_cloud_ops.py:24-27)"""
+    vs, r = np.asarray(voxel_size, np.float32), np.asarray(pc_range, np.float32)
+    return tuple(int(v) for v in np.round((r[3:] - r[:3]) / vs).astype(np.int32))
+
+
+def voxelize_workspace_bytes(N, B, cells, max_voxels):
+    """bytes of scratch md_voxelize takes for N points, B samples of `cells` cells (include/minddet_hip_points.h)"""
+    up = lambda n: (n + 63) // 64 * 64
+    nb = (max(N, B * max_voxels) + 1023) // 1024
+    return 4 * (2 * up(B * cells) + 2 * up(N) + up(N + 1) + up(B * max_voxels) + up(B * max_voxels + 1) + up(nb + 1))
+
+
+def voxelize(points, offsets, voxel_size, pc_range, max_points, max_voxels):
+    """points [N, F] f32 (F = 4 or 5; B samples back to back), offsets [B + 1] i32 on the device ->
+    (voxels [B, max_voxels, max_points, F] f32, coors [B, max_voxels, 4] i32 (b, z, y, x), num_points [B, max_voxels] i32,
+    voxel_num [B] i32): points_to_voxel(reverse_index=True) per sample, bit for bit (md_voxelize; no host round trip)."""
+    if points.dim() != 2 or points.shape[1] not in (4, 5):
+        raise ValueError(f"voxelize: points are [N, 4] or [N, 5], got {tuple(points.shape)}")
+    points = _f32c(points)
+    dev, (N, F), B = points.device, points.shape, offsets.numel() - 1
+    max_points, max_voxels = int(max_points), int(max_voxels)
+    at = _VoxelizeAttrs((ctypes.c_float * 3)(*[float(v) for v in voxel_size]), (ctypes.c_float * 6)(*[float(v) for v in pc_range]),
+                        max_points, max_voxels)
+    gx, gy, gz = voxel_grid(voxel_size, pc_range)
+    voxels = torch.empty((B, max_voxels, max_points, F), dtype=torch.float32, device=dev)
+    coors = torch.empty((B, max_voxels, 4), dtype=torch.int32, device=dev)
+    num_points = torch.empty((B, max_voxels), dtype=torch.int32, device=dev)
+    voxel_num = torch.empty((B,), dtype=torch.int32, device=dev)
+    ws = torch.empty((voxelize_workspace_bytes(N, B, gx * gy * gz, max_voxels),), dtype=torch.uint8, device=dev)
+    _lib.call("md_voxelize", [points, offsets, voxels, coors, num_points, voxel_num, ws], extra=at)
+    return voxels, coors, num_points, voxel_num
+
+
+class PackedPFN:
+    """The PFN layers as md_pillar_encode takes them: per layer the Dense weight with the BatchNorm folded in (fp32)."""
+
+    def __init__(self, w1, b1, w2=None, b2=None):
+        self.w1, self.b1, self.w2, self.b2 = w1, b1, w2, b2
+
+    def to(self, device):
+        self.w1, self.b1 = self.w1.to(device), self.b1.to(device)
+        if self.w2 is not None:
+            self.w2, self.b2 = self.w2.to(device), self.b2.to(device)
+        return self
+
+
+def pack_pfn(layers):
+    """layers: one (weight [units, in] f32, (gamma, beta, mean, var, eps)) per PFN layer -> PackedPFN.  The fold, in fp32:
+    scale = gamma / sqrt(var + eps); w = weight * scale per output row; b = beta - mean * scale.  One layer [64, F + 5] or two layers
+    [32, F + 5] and [64, 64]; anything else raises ValueError."""
+    if len(layers) not in (1, 2):
+        raise ValueError(f"pack_pfn: one or two PFN layers are supported, got {len(layers)}")
+    out = []
+    for weight, (gamma, beta, mean, var, eps) in layers:
+        weight = torch.as_tensor(weight, dtype=torch.float32)
+        scale = torch.as_tensor(gamma, dtype=torch.float32) / torch.sqrt(torch.as_tensor(var, dtype=torch.float32) + float(eps))
+        out += [(weight * scale[:, None]).contiguous(), (torch.as_tensor(beta, dtype=torch.float32)
+                                                        - torch.as_tensor(mean, dtype=torch.float32) * scale).contiguous()]
+    want = [(64,)] if len(layers) == 1 else [(32,), (64, 64)]
+    if out[0].shape[0] != want[0][0] or out[0].shape[1] not in (9, 10) or (len(layers) == 2 and tuple(out[2].shape) != want[1]):
+        raise ValueError(f"pack_pfn: supported are num_filters (64,) and (64, 64) on 4 or 5 point features, got weights "
+                         f"{[tuple(w.shape) for w in out[0::2]]}")
+    return PackedPFN(*out)
+
+
+def pillar_encode(voxels, num_points, coors, voxel_num, pfn, hw, vx, vy, x_offset, y_offset, out=None):
+    """PillarFeatureNet + PointPillarsScatter (md_pillar_encode): the outputs of voxelize and a PackedPFN -> the pseudo-image
+    [B, H, W, 64] bf16 (NHWC), zero where no pillar is."""
+    B = voxels.shape[0]
+    H, W = int(hw[0]), int(hw[1])
+    canvas = out if out is not None else torch.empty((B, H, W, 64), dtype=torch.bfloat16, device=voxels.device)
+    at = _PillarEncodeAttrs(float(vx), float(vy), float(x_offset), float(y_offset), 0, 0)
+    _lib.call("md_pillar_encode", [voxels, num_points, coors, voxel_num, pfn.w1, pfn.b1, pfn.w2, pfn.b2, canvas], extra=at)
+    return canvas

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import det_ops, nn_ops
-from .registry import BACKBONES, DETECTORS, HEADS, NECKS, ROI_HEAD, build_backbone, build_head, build_neck, build_roi_head
+from .registry import BACKBONES, DETECTORS, HEADS, NECKS, READERS, ROI_HEAD, build_backbone, build_head, build_neck, build_roi_head
 
 
 # per-level proposal selection (slice, top-k, decode) on a side HIP stream behind the level's conv, joined before the NMS: +0.4 % on
@@ -953,6 +953,116 @@ def merge_center_tasks(outs, num_classes, max_per_task):
         flag += int(nc)
     rows[:, T * m] = 0
     return rows[:, :T * m].contiguous(), base.view(B).to(torch.int32)
+
+
+# ----------------------------------------------------------------------------- point-cloud front end (csrc/pillars.hip)
+@READERS.register_module
+class PillarFeatureNet(Module):
+    """centerpoint/det3d_ms/models/readers/pillar_encoder.py:70-199: the decoration of every point with its offsets from the voxel's
+    mean and from the pillar centre, then the PFN layers (:18-67) -- Dense without bias + BatchNorm(eps 1e-3) + ReLU + max over the
+    voxel's rows, a non-last layer (units = filters / 2) concatenating the maximum to every row.  Parameters in the reference's layout
+    (`layers[i] = (weight [units, in], (gamma, beta, mean, var, eps))`); to() folds them (det_ops.pack_pfn).  The net only runs fused
+    with the scatter: PointPillarsScatter.__call__ makes the one md_pillar_encode launch."""
+
+    def __init__(self, num_input_features=4, num_filters=(64,), with_distance=False, voxel_size=(0.2, 0.2, 4),
+                 pc_range=(0, -40, -3, 70.4, 40, 1), norm_cfg=None, virtual=False, seed=7):
+        num_filters = [int(c) for c in num_filters]
+        if with_distance or virtual:
+            raise ValueError("PillarFeatureNet: with_distance=True and virtual=True are not built")
+        if int(num_input_features) not in (4, 5) or num_filters not in ([64], [64, 64]):
+            raise ValueError(f"PillarFeatureNet: built for 4 or 5 point features and num_filters (64,) or (64, 64), got "
+                             f"num_input_features={num_input_features}, num_filters={tuple(num_filters)}")
+        eps = (norm_cfg or {}).get("eps", 1e-3)
+        if eps != 1e-3:
+            raise ValueError("PillarFeatureNet: the reference's PFN layers use BatchNorm eps 1e-3 whatever norm_cfg says")
+        init = ParamInit(seed)
+        self.num_input_features, self.num_filters = int(num_input_features), num_filters
+        self.vx, self.vy = float(voxel_size[0]), float(voxel_size[1])
+        self.x_offset, self.y_offset = self.vx / 2 + float(pc_range[0]), self.vy / 2 + float(pc_range[1])
+        self.layers = []
+        cin = self.num_input_features + 5
+        for i, c in enumerate(num_filters):
+            units = c if i == len(num_filters) - 1 else c // 2
+            w = init.conv(units, cin, 1, std=math.sqrt(2.0 / cin)).reshape(units, cin)
+            gamma, beta, mean, var, _ = init.bn(units, eps)
+            beta = init.bias(units, std=0.1)               # both signs: where the shift is positive the padded rows win the maximum
+            self.layers.append((w, (gamma, beta, mean, var, eps)))
+            cin = 2 * units
+        self.out_channels = num_filters[-1]
+
+    def _derive(self, device):
+        self.packed = det_ops.pack_pfn(self.layers).to(device)
+
+
+@BACKBONES.register_module
+class PointPillarsScatter(Module):
+    """pillar_encoder.py:202-228: the voxel features scattered to the dense BEV canvas.  Here the canvas is written by the same launch
+    that computes the features, in the NHWC layout the neck reads (the reference's transpose to NCHW is not needed)."""
+
+    def __init__(self, num_input_features=64, norm_cfg=None, name="PointPillarsScatter", ds_factor=1, **kwargs):
+        if int(ds_factor) != 1 or int(num_input_features) != 64:
+            raise ValueError(f"PointPillarsScatter: built for ds_factor=1 and 64 channels, got ds_factor={ds_factor}, "
+                             f"num_input_features={num_input_features}")
+        self.nchannels = 64
+
+    def __call__(self, reader, voxels, coors, num_points, voxel_num, hw):
+        """md_voxelize's outputs -> pseudo-image [B, H, W, 64] bf16"""
+        return det_ops.pillar_encode(voxels, num_points, coors, voxel_num, reader.packed, hw, reader.vx, reader.vy, reader.x_offset,
+                                     reader.y_offset)
+
+
+@DETECTORS.register_module
+class PillarDetector(Module):
+    """CenterPoint-PP from raw points (det3d's PointPillars detector with its reader and backbone,
+    centerpoint/det3d_ms/models/detectors/point_pillars.py): voxel generator (md_voxelize) -> PillarFeatureNet + PointPillarsScatter
+    (md_pillar_encode) -> graphs.PointPillars (neck, bbox_head, post-processing, unchanged).  Everything stays on the device: the
+    outputs have fixed capacity and no size is read back."""
+
+    def __init__(self, reader, backbone, neck, bbox_head, voxel_generator, train_cfg=None, test_cfg=None, pretrained=None, seed=7):
+        from .registry import build
+        self.reader = build(dict(reader, seed=seed + 2) if isinstance(reader, dict) and "seed" not in reader else reader, READERS)
+        self.backbone = build_backbone(backbone)
+        self.detector = PointPillars(neck, bbox_head, train_cfg=train_cfg, test_cfg=test_cfg, pretrained=pretrained, seed=seed)
+        vg = dict(voxel_generator)
+        self.pc_range = tuple(float(v) for v in vg["range"])
+        self.voxel_size = tuple(float(v) for v in vg["voxel_size"])
+        self.max_points, self.max_voxels = int(vg["max_points_in_voxel"]), int(vg["max_voxel_num"])
+        gx, gy, gz = det_ops.voxel_grid(self.voxel_size, self.pc_range)
+        if gz != 1:
+            raise ValueError(f"PillarDetector: pillars span the whole z range (one cell), the voxel generator gives {gz}")
+        self.grid_hw = (gy, gx)
+        if (self.reader.vx, self.reader.vy) != self.voxel_size[:2] or self.reader.num_filters[-1] != self.backbone.nchannels:
+            raise ValueError("PillarDetector: the reader's voxel_size / width do not match the voxel generator / the backbone")
+
+    def children(self):
+        return [self.reader, self.backbone, self.detector]
+
+    @property
+    def neck(self):
+        return self.detector.neck
+
+    @property
+    def bbox_head(self):
+        return self.detector.bbox_head
+
+    def pseudo_image(self, points, offsets):
+        """points [N, F] f32, offsets [B + 1] i32 -> (canvas [B, H, W, 64] bf16, (voxels, coors, num_points, voxel_num))"""
+        vox = det_ops.voxelize(points, offsets, self.voxel_size, self.pc_range, self.max_points, self.max_voxels)
+        voxels, coors, num_points, voxel_num = vox
+        return self.backbone(self.reader, voxels, coors, num_points, voxel_num, self.grid_hw), vox
+
+    def forward(self, points, offsets, return_aux=False):
+        """points [N, F] f32: the B samples' points back to back; offsets [B + 1] i32 (device) ->
+        (dets [B, tasks x nms_post_max_size, 11] f32, count [B] i32) as PointPillars.forward"""
+        if points.shape[1] != self.reader.num_input_features:
+            raise ValueError(f"PillarDetector: the reader takes {self.reader.num_input_features} point features, got {points.shape[1]}")
+        canvas, (voxels, coors, num_points, voxel_num) = self.pseudo_image(points, offsets)
+        if return_aux:
+            out, aux = self.detector.forward(canvas, return_aux=True)
+            return out, dict(aux, voxels=voxels, coors=coors, num_points=num_points, voxel_num=voxel_num, pseudo_image=canvas)
+        return self.detector.forward(canvas)
+
+    __call__ = forward
 
 
 # ----------------------------------------------------------------------------- YOLOv5 (build-authored; parity unpinned)

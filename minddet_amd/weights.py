@@ -414,3 +414,52 @@ def load_center_head(head, params, prefix="bbox_head.", naming="auto", strict=Tr
             if all(v is not None for v in vals):
                 m.bn = (vals[0], vals[1], vals[2], vals[3], m.bn[4])
     return sorted(k for k in params if k not in used)
+
+
+_READER_BN = ("gamma", "beta", "moving_mean", "moving_variance")
+
+
+def reader_state(reader, prefix="reader.", naming="ms"):
+    """graphs.PillarFeatureNet parameters under the reference's names (pillar_encoder.py:40-43,118: pfn_layers.i.linear.weight,
+    pfn_layers.i.norm.*), MindSpore or the det3d torch original (naming='torch')."""
+    bn_names = _READER_BN if naming == "ms" else ("weight", "bias", "running_mean", "running_var")
+    out = {}
+    for i, (w, bn) in enumerate(reader.layers):
+        out[f"{prefix}pfn_layers.{i}.linear.weight"] = w
+        for n, v in zip(bn_names, bn[:4]):
+            out[f"{prefix}pfn_layers.{i}.norm.{n}"] = v
+    return {k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)) for k, v in out.items()}
+
+
+def load_reader(reader, params, prefix="reader.", naming="auto", strict=True):
+    """Write a checkpoint's pillar feature net into a graphs.PillarFeatureNet; returns the unused keys.  The moving statistics are
+    accepted as `moving_mean` / `moving_variance` and as `mean` / `variance`, the names the reference's BatchNorm2dMasked gives its
+    parameters (custom_bn.py:27-36).  naming 'torch' goes through `torch_to_ms_generic` first; call .to(device) afterwards to fold."""
+    if naming == "auto":
+        naming = "torch" if any(k.endswith("running_var") for k in params) else "ms"
+    if naming == "torch":
+        kmap = torch_to_ms_generic(params.keys())
+        params = {kmap[k]: v for k, v in params.items() if k in kmap}
+    used = set()
+
+    def get(keys, like):
+        key = next((k for k in keys if k in params), None)
+        if key is None:
+            if strict:
+                raise KeyError(f"checkpoint has no {keys[0]!r}")
+            return None
+        a = np.asarray(params[key])
+        if tuple(a.shape) != tuple(like.shape):
+            raise ValueError(f"{key}: checkpoint shape {tuple(a.shape)} != model shape {tuple(like.shape)}")
+        used.add(key)
+        return torch.from_numpy(a.astype(np.float32))
+
+    for i, (w, bn) in enumerate(reader.layers):
+        p = f"{prefix}pfn_layers.{i}."
+        nw = get([p + "linear.weight"], w)
+        alt = {"moving_mean": "mean", "moving_variance": "variance"}
+        vals = [get([p + "norm." + n] + ([p + "norm." + alt[n]] if n in alt else []), bn[j]) for j, n in enumerate(_READER_BN)]
+        if all(v is not None for v in vals):
+            bn = (vals[0], vals[1], vals[2], vals[3], bn[4])
+        reader.layers[i] = (nw if nw is not None else w, bn)
+    return sorted(k for k in params if k not in used)

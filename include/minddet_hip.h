@@ -354,13 +354,22 @@ typedef struct md_pool_attrs {
     int32_t zero_pad; /* 1: out-of-image taps count as 0 (explicit zero Pad + MaxPool2d,
                          centernet/src/resnet.py:199-204); 0: ignored (-inf padding) */
 } md_pool_attrs;
-/* in x[N,H,W,C] bf16 ; out y[N,Ho,Wo,C] bf16.  extra: md_pool_attrs (required). */
+/* in x[N,H,W,C] bf16 ; out y[N,Ho,Wo,C] bf16.  extra: md_pool_attrs (required).
+ * y = the maximum over the window's in-image taps (and 0, under zero_pad, when the window reaches past the image); a window with no
+ * in-image tap at all (possible only with pad >= k) gives 0.  The result is one of the compared values, exact as a NUMBER; which of
+ * two equal values is kept is unspecified, so a maximum of zero may come out as -0 or +0 whatever the signs of the zeros in the window
+ * (today: the first of equal taps in row-major order; under zero_pad the padding's +0 loses to an in-image -0).  Infinities and
+ * denormals compare as numbers.  NaN inputs are unspecified: a NaN tap may or may not reach the output. */
 int md_maxpool2d(MD_AOT_ARGS);
 
 /* The pooling chain of an SPPF block (build-authored YOLOv5 / YOLOv8 models; SURVEY 0.2: the reference names the families only) in ONE
  * launch, in place on the block's concat buffer: with x = buf[.., 0:C],
  *   buf[.., C:2C] = mp(x), buf[.., 2C:3C] = mp(mp(x)), buf[.., 3C:4C] = mp(mp(mp(x))),  mp = max-pool k x k, stride 1, pad k/2, out-of-image
- * taps ignored (torch semantics) -- bit-identical to three md_maxpool2d(zero_pad = 0) launches + the copies into the buffer.
+ * taps ignored (torch semantics) -- equal AS NUMBERS to three md_maxpool2d(zero_pad = 0) launches + the copies into the buffer, and
+ * bit-identical to them wherever no window holds zeros of both signs: this kernel orders +0 above -0 and returns +0 for such a window,
+ * md_maxpool2d keeps the first of equal taps and may return -0.  The sign of a zero maximum is unspecified for both (-0 == +0), and so
+ * are NaN inputs (here a NaN orders by its bit pattern: above +inf when positive, below -inf when negative; md_maxpool2d takes the
+ * later tap whenever one of the two is NaN).  Channels [0, C) and [4C, Ctot) are not written.
  * in/out: buf[N,H,W,Ctot] bf16 (Ctot >= 4 C, both multiples of 8).  extra: md_sppf_attrs (required).
  * MD_ERR_SIZE when an image's working set does not fit LDS (md_sppf_pool_groups(H, W, C) == 0): run the three pools instead. */
 typedef struct md_sppf_attrs {
@@ -456,7 +465,12 @@ typedef struct md_stem_conv_attrs {
 int md_stem_conv(MD_AOT_ARGS);
 int md_stem_layout_pad(int which);
 
-/* FPN top-down step: in lateral[N,H,W,C], top[N,Ht,Wt,C] bf16 ; out y = lateral + nearest_up(top). */
+/* FPN top-down step: in lateral[N,H,W,C], top[N,Ht,Wt,C] bf16 ; out y[N,H,W,C] bf16,
+ *   y[n,h,w,c] = bf16_rne(float(lateral[n,h,w,c]) + float(top[n, (h * Ht) / H, (w * Wt) / W, c]))   (integer division)
+ * -- one fp32 add, one round-to-nearest-even to bf16; overflow goes to +-inf, results below 2^-126 are bf16 denormals (gradual
+ * underflow, not flushed).  The integer index formula IS the contract: it equals torch's F.interpolate(mode="nearest", size=(H, W)) for
+ * every exact halving (all FPN levels of configs/), but F.interpolate computes the index with a float scale and lands one row / column
+ * off for some sizes that do not divide (first: 44 <- 26, 46 <- 14, 82 <- 2). */
 int md_upsample_add(MD_AOT_ARGS);
 typedef struct md_slice_attrs {
     int32_t c0, width;
@@ -615,7 +629,8 @@ int md_rpn_decode(MD_AOT_ARGS);
  * (score -FLT_MAX where suppressed) */
 int md_rpn_merge(MD_AOT_ARGS);
 /* in mboxes[B,P,4] f32, topv[B,post] f32, topi[B,post] i32, cnt[B] i32 ;
- * out rois[B*post,5] f32 (batch_idx,x1,y1,x2,y2; zero box past cnt), roi_scores[B*post] f32 */
+ * out rois[B*post,5] f32 (batch_idx,x1,y1,x2,y2; zero box past cnt), roi_scores[B*post] f32 (0 past cnt).  Slots of topv / topi past
+ * cnt are not read. */
 int md_make_rois(MD_AOT_ARGS);
 typedef struct md_rcnn_attrs {
     int32_t num_classes;  /* nc foreground classes; logits [0,nc] with background LAST */

@@ -22,7 +22,8 @@ __device__ __forceinline__ unsigned pf2bf(float f) {
     u += 0x7fffu + ((u >> 16) & 1u);
     return u >> 16;
 }
-// max of two packed bf16 pairs (compare as floats; -0/+0 and NaN corner cases follow fmaxf)
+// max of two packed bf16 pairs (compared as floats; of equal values -- -0 and +0 among them -- the first, a, is kept; when either is
+// NaN, b is taken: minddet_hip.h leaves both cases unspecified)
 __device__ __forceinline__ unsigned max_bf16x2(unsigned a, unsigned b) {
     const float alo = pbf2f(a & 0xffffu), blo = pbf2f(b & 0xffffu);
     const float ahi = pbf2f(a >> 16), bhi = pbf2f(b >> 16);
@@ -68,7 +69,8 @@ __global__ void maxpool_nhwc_kernel(const uint16_t *__restrict__ x, uint16_t *__
     }
 }
 
-// y[n,h,w,:] = lateral[n,h,w,:] + top[n, floor(h*Ht/H), floor(w*Wt/W), :]   (nearest, F.interpolate(size=))
+// y[n,h,w,:] = lateral[n,h,w,:] + top[n, floor(h*Ht/H), floor(w*Wt/W), :]   (nearest; the integer formula is the contract: it is
+// F.interpolate(size=) for exact halvings, not for every size pair -- minddet_hip.h)
 __global__ void upsample_add_kernel(const uint16_t *__restrict__ lat, const uint16_t *__restrict__ top,
                                     uint16_t *__restrict__ y, int N, int H, int W, int C, int Ht, int Wt) {
     const int cv = C / 8;

@@ -1127,7 +1127,7 @@ class SPPF(Module):
         n, h, w, _ = x.shape
         cat = torch.empty((n, h, w, 4 * self.c_), dtype=torch.bfloat16, device=x.device)
         if SPPF_FUSED and nn_ops.sppf_pool_fits(h, w, self.c_):
-            # cv1 writes the first slice of the concat buffer; ONE launch fills the other three (md_sppf_pool; bit-identical)
+            # cv1 writes the first slice of the concat buffer; ONE launch fills the other three (md_sppf_pool; equal as numbers, a zero maximum may differ in sign)
             self.cv1(x, out=cat, c_off=0)
             nn_ops.sppf_pool(cat, self.c_, self.k)
             return self.cv2(cat, out=out, c_off=c_off)

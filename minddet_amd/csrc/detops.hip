@@ -21,6 +21,7 @@
 #include <float.h>
 
 #include "aot.h"
+#include "box_codec.h"
 
 #pragma clang fp contract(off)
 
@@ -163,15 +164,7 @@ __global__ void amask_area_kernel(const int *__restrict__ dense, const float *__
 __global__ void second_box_decode_kernel(const float *__restrict__ enc, const float *__restrict__ anc, size_t n,
                                          size_t n_anchor, float *__restrict__ out) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const float *t = enc + i * 7, *a = anc + (i % n_anchor) * 7;
-        const float xa = a[0], ya = a[1], wa = a[3], la = a[4], ha = a[5], ra = a[6];
-        const float za = a[2] + ha / 2;
-        const float diagonal = sqrtf(la * la + wa * wa);
-        const float xg = t[0] * diagonal + xa, yg = t[1] * diagonal + ya, zg = t[2] * ha + za;
-        const float lg = expf(t[4]) * la, wg = expf(t[3]) * wa, hg = expf(t[5]) * ha;
-        const float rg = t[6] + ra;
-        float *o = out + i * 7;
-        o[0] = xg; o[1] = yg; o[2] = zg - hg / 2; o[3] = wg; o[4] = lg; o[5] = hg; o[6] = rg;
+        second_box_decode_one(enc + i * 7, anc + (i % n_anchor) * 7, out + i * 7);
     }
 }
 
@@ -1220,26 +1213,13 @@ __global__ __launch_bounds__(256) void yolov8_decode_kernel(const uint16_t *__re
     labels[o] = lab;
 }
 
-// rotated BEV box (x, y, dx, dy, r) -> axis-aligned "standup" box of its 4 corners:
-// pointpillars/src/core/box_np_ops.py:316-341 (center_to_corner_box2d, origin 0.5, corners @ [[c,-s],[s,c]])
-// + :172-177 (corner_to_standup_nd); call site pointpillars/src/predict.py:61-78.
+// rotated BEV boxes -> standup boxes (box_codec.h: standup_one)
 __global__ void standup_kernel(const float *__restrict__ boxes, int n, int stride, int ix, int iy, int idx_, int idy, int ir,
                                float *__restrict__ out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float *b = boxes + (size_t)i * stride;
-    const float cx = b[ix], cy = b[iy], dx = b[idx_], dy = b[idy], r = b[ir];
-    const float s = sinf(r), c = cosf(r);
-    const float nx[4] = {-0.5f, -0.5f, 0.5f, 0.5f}, ny[4] = {-0.5f, 0.5f, 0.5f, -0.5f};
-    float x0 = 0, x1 = 0, y0 = 0, y1 = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const float px = dx * nx[k], py = dy * ny[k];
-        const float qx = px * c + py * s + cx, qy = -px * s + py * c + cy;
-        if (k == 0) { x0 = x1 = qx; y0 = y1 = qy; }
-        else { x0 = fminf(x0, qx); x1 = fmaxf(x1, qx); y0 = fminf(y0, qy); y1 = fmaxf(y1, qy); }
-    }
-    *reinterpret_cast<float4 *>(out + (size_t)i * 4) = make_float4(x0, y0, x1, y1);
+    *reinterpret_cast<float4 *>(out + (size_t)i * 4) = standup_one(b[ix], b[iy], b[idx_], b[idy], b[ir]);
 }
 
 // out[b, j, :] = src[b, idx[b, j], :] for j < cnt[b] (zero rows past cnt); W floats per row

@@ -381,6 +381,16 @@ def anchors_mask(coors, grid_size_xy, anchors_bv, voxel_size, pc_range, area_thr
     return area, mask.bool()
 
 
+def rbbox2d_to_near_bbox(rbboxes):
+    """pointpillars/src/core/box_np_ops.py:180-192: rotated BEV boxes [N,5] (x, y, dx, dy, r) -> the nearest axis-aligned boxes
+    [N,4] (xmin, ymin, xmax, ymax): dx and dy change places where the rotation, folded into [-pi/2, pi/2), is beyond pi/4."""
+    r = _f32c(rbboxes)
+    rot = r[:, 4]
+    folded = (rot - torch.floor(rot / math.pi + 0.5) * math.pi).abs()
+    dims = torch.where((folded > math.pi / 4).unsqueeze(1), r[:, [3, 2]], r[:, 2:4])
+    return torch.cat([r[:, :2] - dims / 2, r[:, :2] + dims / 2], 1).contiguous()
+
+
 def second_box_decode(box_encodings, anchors):
     enc, anc = _f32c(box_encodings), _f32c(anchors).reshape(-1, 7)
     out = torch.empty_like(enc)
@@ -700,6 +710,86 @@ def pp_get_selected_data(total_scores, box_preds, anchors_mask, cfg):
     n = num[0]
     ki = kidx[0].long()
     return sel[ki], vals[0][ki], top_labels[idx[0].long()][ki], n
+
+
+class _PPHeadAttrs(ctypes.Structure):
+    _fields_ = [("off_cls", ctypes.c_int32), ("off_box", ctypes.c_int32), ("off_dir", ctypes.c_int32), ("num_anchors", ctypes.c_int32),
+                ("num_classes", ctypes.c_int32), ("score_mode", ctypes.c_int32), ("self_train", ctypes.c_int32)]
+
+
+def pp_scores(head, off_cls, num_anchors, num_classes, mask=None):
+    """head [B,H,W,C] bf16 (the merged head tensor), mask [B,N] bool / uint8 or None -> (scores [B,N] f32, labels [B,N] i32),
+    N = H W num_anchors: per anchor the maximum of the class sigmoids and the first class that attains it, -1 where the mask is 0
+    (md_pp_scores, include/minddet_hip_pp.h)."""
+    B, H, W, _ = head.shape
+    n = H * W * int(num_anchors)
+    scores = torch.empty((B, n), dtype=torch.float32, device=head.device)
+    labels = torch.empty((B, n), dtype=torch.int32, device=head.device)
+    if mask is not None:
+        mask = mask.to(device=head.device, dtype=torch.uint8).reshape(B, n).contiguous()
+    _lib.call("md_pp_scores", [head, mask, scores, labels], extra=_PPHeadAttrs(int(off_cls), 0, -1, int(num_anchors), int(num_classes), 0, 1))
+    return scores, labels
+
+
+def pp_decode_selected(head, anchors, idx, cnt, sel_scores, labels, off_box, off_dir, num_anchors, self_train=True, with_boxes=False):
+    """The selected anchors' boxes (md_pp_decode_selected): idx [B,k] i32, cnt [B] i32, sel_scores [B,k] f32 from the top-k, labels
+    [B,N] i32 from pp_scores -> (dets [B,k,9] = x, y, z, w, l, h, rot, score, label; standup [B,k,4]; dir_labels [B,k] i32
+    [, boxes [B,k,7] before the direction fix]); rows past cnt are zero.  off_dir None / -1: no direction classifier."""
+    B, k = idx.shape
+    dev = head.device
+    dets = torch.empty((B, k, 9), dtype=torch.float32, device=dev)
+    standup = torch.empty((B, k, 4), dtype=torch.float32, device=dev)
+    dirs = torch.empty((B, k), dtype=torch.int32, device=dev)
+    boxes = torch.empty((B, k, 7), dtype=torch.float32, device=dev) if with_boxes else None
+    at = _PPHeadAttrs(0, int(off_box), -1 if off_dir is None else int(off_dir), int(num_anchors), 1, 0, int(bool(self_train)))
+    _lib.call("md_pp_decode_selected", [head, _f32c(anchors).reshape(-1, 7), idx, cnt, sel_scores, labels, dets, standup, dirs, boxes],
+              extra=at)
+    return (dets, standup, dirs, boxes) if with_boxes else (dets, standup, dirs)
+
+
+class PPHeadPost:
+    """Post-processing of the anchor-based PointPillars head for a whole batch, five launches and no host read:
+    PointPillarsNet.post_processing (pointpillars/src/pointpillars.py:767-800) + _get_selected_data (predict.py:43-98) + the
+    direction fix (predict.py:222-236).  pp_scores over every anchor -> one segmented top-k (nms_pre_max_size per sample, score
+    threshold as `>=`) -> pp_decode_selected on the selected anchors only -> NMS on the standup boxes (nms_jit convention, as
+    pp_get_selected_data) -> the first nms_post_max_size survivors.
+    cfg: num_anchors, num_classes, off_cls, off_box, off_dir (None: no direction classifier), nms_pre_max_size, nms_post_max_size,
+    nms_score_threshold, nms_iou_threshold [, use_self_train (default True; False is not built)]."""
+
+    def __init__(self, cfg):
+        self.cfg = dict(cfg)
+        c = self.cfg
+        self.A, self.K = int(c["num_anchors"]), int(c["num_classes"])
+        self.off_cls, self.off_box, self.off_dir = int(c["off_cls"]), int(c["off_box"]), c.get("off_dir")
+        self.pre, self.post = int(c["nms_pre_max_size"]), int(c["nms_post_max_size"])
+        self.score_thr, self.iou_thr = float(c["nms_score_threshold"]), float(c["nms_iou_threshold"])
+        self.self_train = bool(c.get("use_self_train", True))
+        if not self.self_train:
+            raise ValueError("PPHeadPost: use_self_train=False (the limit_period direction form, pointpillars.py:637-649) is not built")
+
+    def __call__(self, head, anchors, mask=None, segments=None, return_aux=False):
+        """head [B,H,W,C] bf16, anchors [N,7] f32, mask [B,N] or None -> (dets [B, nms_post_max_size, 9] f32, count [B] i32);
+        rows past count are zero.  segments: the [B + 1] int32 table 0, N, 2 N, ... (built when not given)."""
+        B, H, W, _ = head.shape
+        n = H * W * self.A
+        dev = head.device
+        scores, labels = pp_scores(head, self.off_cls, self.A, self.K, mask)
+        if segments is None:
+            segments = torch.arange(0, (B + 1) * n, n, dtype=torch.int32, device=dev)
+        k = min(self.pre, n)
+        vals, idx, cnt = topk_segmented(scores, segments, k, min_score=_just_below(self.score_thr) if self.score_thr > 0 else None,
+                                        max_segment=n)
+        out = pp_decode_selected(head, anchors, idx, cnt, vals, labels, self.off_box, self.off_dir, self.A, with_boxes=return_aux)
+        sel, standup, dirs = out[:3]
+        keep_mask, kidx, num = nms_aligned(standup, self.iou_thr, 0.0, NMS_MODE_JIT, count=cnt, max_output=self.post)
+        ki = kidx[:, :self.post]
+        if k < self.post:
+            ki = torch.nn.functional.pad(ki, (0, self.post - k))
+        dets = gather_rows(sel, ki.contiguous(), num)
+        if return_aux:
+            return (dets, num), dict(scores=scores, labels=labels, topk_values=vals, topk_idx=idx, topk_cnt=cnt, selected=sel,
+                                     standup=standup, dir_labels=dirs, boxes=out[3], keep_mask=keep_mask, keep_idx=kidx)
+        return dets, num
 
 
 # ----------------------------------------------------------------------------- CenterNet post-process (post_process.py)

@@ -758,15 +758,17 @@ class RPN(Module):
 
     def __init__(self, layer_nums=(3, 5, 5), ds_layer_strides=(2, 2, 2), ds_num_filters=(64, 128, 256),
                  us_layer_strides=(0.5, 1, 2), us_num_filters=(128, 128, 128), num_input_features=64, norm_cfg=None,
-                 seed=7, **kwargs):
+                 seed=7, inner_norm_eps=None, **kwargs):
+        # inner_norm_eps: per block the BatchNorm eps of the n convs behind the block's first one, None (entry or whole argument) = eps
         init = ParamInit(seed)
         eps = (norm_cfg or {}).get("eps", 1e-3)
+        inner = [eps if e is None else float(e) for e in (inner_norm_eps or [None] * len(layer_nums))]
         self.blocks, self.deblocks = [], []
         cin = num_input_features
         self.up_start = len(layer_nums) - len(us_layer_strides)
         for i, n in enumerate(layer_nums):
             blk = [ConvModule(init, cin, ds_num_filters[i], 3, ds_layer_strides[i], 1, bn_eps=eps)]
-            blk += [ConvModule(init, ds_num_filters[i], ds_num_filters[i], 3, 1, 1, bn_eps=eps) for _ in range(n)]
+            blk += [ConvModule(init, ds_num_filters[i], ds_num_filters[i], 3, 1, 1, bn_eps=inner[i]) for _ in range(n)]
             self.blocks.append(blk)
             cin = ds_num_filters[i]
             if i - self.up_start >= 0:
@@ -1063,6 +1065,149 @@ class PillarDetector(Module):
         return self.detector.forward(canvas)
 
     __call__ = forward
+
+
+# ----------------------------------------------------------------------------- PointPillars, anchor-based (KITTI)
+class PPAnchorHead(Module):
+    """conv_cls / conv_box / conv_dir_cls of the KITTI RPN (pointpillars/src/pointpillars.py:562-578): three 1x1 convs with bias, no
+    BatchNorm, no activation, on the neck's concatenated features.  The three ConvModules are the source of truth; to() builds ONE
+    md_conv2d launch from them (merged_conv) whose output [B, H, W, roundup(A K + 7 A + 2 A, 8)] bf16 holds the three side by side:
+    the head tensor md_pp_scores and md_pp_decode_selected read in place (head_offsets())."""
+
+    def __init__(self, init, in_channels, num_anchors, num_classes, use_direction_classifier=True):
+        self.A, self.K = int(num_anchors), int(num_classes)
+        kw = dict(bn=False, relu=False, bias=True)
+        self.conv_cls = ConvModule(init, in_channels, self.A * self.K, 1, **kw)
+        self.conv_box = ConvModule(init, in_channels, self.A * 7, 1, **kw)
+        self.conv_dir_cls = ConvModule(init, in_channels, self.A * 2, 1, **kw) if use_direction_classifier else None
+        self.head_channels = sum(m.cout for m in self.children())
+
+    def children(self):
+        return [m for m in (self.conv_cls, self.conv_box, self.conv_dir_cls) if m is not None]
+
+    def _derive(self, device):
+        self._merged = merged_conv(self.children(), device)
+
+    def head_offsets(self):
+        """first channel of each conv's outputs in the head tensor; dir_cls None without a direction classifier"""
+        return dict(cls=0, box=self.conv_cls.cout, dir_cls=self.conv_cls.cout + self.conv_box.cout if self.conv_dir_cls is not None else None)
+
+    def __call__(self, x):
+        return nn_ops.conv2d(x, self._merged)
+
+
+@DETECTORS.register_module(name="PointPillarsKITTI")
+class PointPillarsNet(Module):
+    """Registered as "PointPillarsKITTI" (a config's `type`); the class keeps the reference's name.  The reference's KITTI PointPillars from the scattered pseudo-image on (pointpillars/src/pointpillars.py:655-800, inference):
+    the RPN of :367-621 -- graphs.RPN with block1's inner BatchNorms at the framework's default eps 1e-5 (:470), every other one at
+    1e-3 -- the three 1x1 heads as one launch (PPAnchorHead) and det_ops.PPHeadPost on the head tensor.  The anchors come from the
+    config's anchor generators (det_ops.generate_anchors at the feature-map size) and are a device constant.
+    Not built (ValueError): this model's reader and scatter (its PillarFeatureNet has a tenth point feature, the z offset from the
+    pillar centre, and an fp16 Dense, which md_pillar_encode does not compute), use_bev=True, encode_background_as_zeros=False,
+    use_self_train=False."""
+
+    def __init__(self, rpn, voxel_generator, anchor_generators, num_class=1, use_direction_classifier=True,
+                 encode_background_as_zeros=True, use_sigmoid_score=True, use_bev=False, use_self_train=True, anchor_area_threshold=1,
+                 voxel_feature_extractor=None, middle_feature_extractor=None, class_names=None, train_cfg=None, test_cfg=None,
+                 pretrained=None, seed=7):
+        if voxel_feature_extractor is not None or middle_feature_extractor is not None:
+            raise ValueError("PointPillarsNet: the pillar feature net and the scatter of this model are not part of this build (its "
+                             "reader has a tenth point feature and an fp16 Dense); drop `voxel_feature_extractor` / "
+                             "`middle_feature_extractor` from the config and feed the scattered pseudo-image [B, H, W, 64] bf16 to forward()")
+        if use_bev:
+            raise ValueError("PointPillarsNet: use_bev=True (the BEV extractor branch of the RPN) is not built")
+        if not encode_background_as_zeros or not use_sigmoid_score:
+            raise ValueError("PointPillarsNet: only encode_background_as_zeros=True with sigmoid scores is built")
+        if not use_self_train:
+            raise ValueError("PointPillarsNet: use_self_train=False (the limit_period direction form) is not built")
+        if not test_cfg:
+            raise ValueError("PointPillarsNet: test_cfg with nms_pre_max_size, nms_post_max_size, nms_score_threshold and "
+                             "nms_iou_threshold is required")
+        _split_forward_of(self, test_cfg)
+        rpn, vg = dict(rpn), dict(voxel_generator)
+        strides, ups = [int(s) for s in rpn.get("layer_strides", (2, 2, 2))], [int(s) for s in rpn.get("upsample_strides", (1, 2, 4))]
+        if len(strides) != 3 or len(ups) != 3 or any(int(np.prod(strides[:i + 1])) * ups[0] != strides[0] * ups[i] for i in range(3)):
+            raise ValueError(f"PointPillarsNet: the three deblocks must reach one size, got layer_strides {strides}, upsample_strides {ups}")
+        self.in_channels = int(rpn.get("num_input_filters", 64))
+        self.neck = RPN(layer_nums=rpn.get("layer_nums", (3, 5, 5)), ds_layer_strides=strides,
+                        ds_num_filters=rpn.get("num_filters", (64, 128, 256)), us_layer_strides=ups,
+                        us_num_filters=rpn.get("num_upsample_filters", (128, 128, 128)), num_input_features=self.in_channels,
+                        norm_cfg=dict(eps=1e-3), inner_norm_eps=(1e-5, None, None), seed=seed)
+        self.generators = [g if isinstance(g, det_ops.AnchorGeneratorStride) else
+                           det_ops.AnchorGeneratorStride(sizes=g["sizes"], anchor_strides=g["strides"], anchor_offsets=g["offsets"],
+                                                         rotations=g["rotations"], match_threshold=g.get("matched_threshold", -1),
+                                                         unmatch_threshold=g.get("unmatched_threshold", -1),
+                                                         anchor_range=vg["point_cloud_range"]) for g in anchor_generators]
+        self.num_class = int(num_class)
+        self.num_anchors = sum(g.num_anchors_per_localization for g in self.generators)
+        self.bbox_head = PPAnchorHead(ParamInit(seed + 1), self.neck.out_channels, self.num_anchors, self.num_class,
+                                      use_direction_classifier)
+        self.pc_range = tuple(float(v) for v in vg["point_cloud_range"])
+        self.voxel_size = tuple(float(v) for v in vg["voxel_size"])
+        gx, gy, _ = det_ops.voxel_grid(self.voxel_size, self.pc_range)
+        self.grid_hw = (gy, gx)                                              # the pseudo-image
+        # block1's first conv (3x3, pad 1, stride s) gives (n - 1) // s + 1 cells, its deblock multiplies by the upsample stride
+        self.feature_hw = (((gy - 1) // strides[0] + 1) * ups[0], ((gx - 1) // strides[0] + 1) * ups[0])
+        self.anchor_area_threshold = float(anchor_area_threshold)
+        self.class_names = list(class_names) if class_names is not None else None
+        self.test_cfg = dict(test_cfg)
+        off = self.bbox_head.head_offsets()
+        self.post = det_ops.PPHeadPost(dict(num_anchors=self.num_anchors, num_classes=self.num_class, off_cls=off["cls"], off_box=off["box"],
+                                            off_dir=off["dir_cls"], use_self_train=use_self_train,
+                                            **{k: self.test_cfg[k] for k in ("nms_pre_max_size", "nms_post_max_size", "nms_score_threshold",
+                                                                             "nms_iou_threshold")}))
+
+    def children(self):
+        return [self.neck, self.bbox_head]
+
+    def head_offsets(self):
+        return self.bbox_head.head_offsets()
+
+    def to(self, device):
+        super().to(device)
+        fh, fw = self.feature_hw
+        self.anchors = det_ops.generate_anchors(self.generators, (1, fh, fw), device=device)["anchors"].reshape(-1, 7)
+        self.anchors_bv = det_ops.rbbox2d_to_near_bbox(self.anchors[:, [0, 1, 3, 4, 6]])
+        return self
+
+    def anchors_mask_from_coors(self, coors, voxel_num=None):
+        """coors [B, MV, 4] i32 (b, z, y, x: md_voxelize's output) or a list of per-sample [V, 3] (z, y, x), voxel_num [B] (rows that
+        count; None = all) -> the anchors mask [B, N] uint8: det_ops.anchors_mask per sample with anchor_area_threshold, as
+        data/preprocess.py:211-225 does.  Pre-processing: reads voxel_num on the host."""
+        nums = None if voxel_num is None else [int(v) for v in voxel_num.tolist()]
+        rows = []
+        for b in range(len(coors)):
+            c = coors[b][:, -3:] if nums is None else coors[b][:nums[b], -3:]
+            _, m = det_ops.anchors_mask(c.contiguous(), (self.grid_hw[1], self.grid_hw[0]), self.anchors_bv, self.voxel_size, self.pc_range,
+                                        self.anchor_area_threshold)
+            rows.append(m.to(torch.uint8))
+        return torch.stack(rows)
+
+    def forward(self, pseudo_image, anchors_mask=None, return_aux=False):
+        """pseudo_image [B, H, W, 64] bf16, anchors_mask [B, N] or None (all valid) -> (dets [B, nms_post_max_size, 9] f32 = x, y, z,
+        w, l, h, rot, score, label; count [B] i32); rows past count are zero.  Nothing is read back to the host."""
+        if isinstance(pseudo_image, (tuple, list)):       # (pseudo_image, anchors_mask): the form forward_streams hands to SplitForward
+            pseudo_image, anchors_mask = pseudo_image
+        if tuple(pseudo_image.shape[1:]) != (self.grid_hw[0], self.grid_hw[1], self.in_channels):
+            raise ValueError(f"PointPillarsNet: the pseudo-image is [B, {self.grid_hw[0]}, {self.grid_hw[1]}, {self.in_channels}], got "
+                             f"{tuple(pseudo_image.shape)}")
+        feat = self.neck(pseudo_image)
+        head = self.bbox_head(feat)
+        B = head.shape[0]
+        n = self.anchors.shape[0]
+        seg = self.const(("segments", B), lambda: _segments(B, n, head.device))
+        if return_aux:
+            out, aux = self.post(head, self.anchors, anchors_mask, segments=seg, return_aux=True)
+            return out, dict(aux, neck=feat, head=head)
+        return self.post(head, self.anchors, anchors_mask, segments=seg)
+
+    __call__ = forward
+
+    def forward_streams(self, pseudo_image, anchors_mask=None):
+        """forward() through test_cfg.streams HIP streams (SplitForward): the mask is split with the batch"""
+        if anchors_mask is None:
+            return self.forward_split(pseudo_image)
+        return self.forward_split((pseudo_image, anchors_mask), prepare=lambda p, m: (p, m))
 
 
 # ----------------------------------------------------------------------------- YOLOv5 (build-authored; parity unpinned)

@@ -34,14 +34,18 @@ class Registry:
     def __repr__(self):
         return f"<{self._kind} registry: {', '.join(sorted(self._table)) or 'empty'}>"
 
-    def register_module(self, cls):
-        """class decorator; the class is registered under its own name and returned unchanged"""
+    def register_module(self, cls=None, name=None):
+        """class decorator; the class is registered under its own name -- or, as `@REG.register_module(name="...")`, under `name` --
+        and returned unchanged"""
+        if cls is None:
+            return lambda c: self.register_module(c, name=name)
         if not inspect.isclass(cls):
             raise TypeError(f"{self._kind} registry: only classes can be registered, got an object of type {type(cls).__name__}")
-        known = self._table.get(cls.__name__)
+        key = cls.__name__ if name is None else str(name)
+        known = self._table.get(key)
         if known is not None:
-            raise KeyError(f"{self._kind} registry: the name {cls.__name__!r} is taken by {known.__module__}.{known.__qualname__}")
-        self._table[cls.__name__] = cls
+            raise KeyError(f"{self._kind} registry: the name {key!r} is taken by {known.__module__}.{known.__qualname__}")
+        self._table[key] = cls
         return cls
 
 

@@ -463,3 +463,88 @@ def load_reader(reader, params, prefix="reader.", naming="auto", strict=True):
             bn = (vals[0], vals[1], vals[2], vals[3], bn[4])
         reader.layers[i] = (nw if nw is not None else w, bn)
     return sorted(k for k in params if k not in used)
+
+
+# ----------------------------------------------------------------------------- PointPillars, anchor-based (KITTI)
+_PP_BN = ("gamma", "beta", "moving_mean", "moving_variance")
+
+
+def _pointpillars_slots(model, prefix):
+    """(module, parameter attribute, key, transposed) for every tensor of graphs.PointPillarsNet under the reference's cell names
+    (pointpillars/src/pointpillars.py:445-578): block{i} = SequentialCell[Conv, BN, ReLU, (Conv, BN, ReLU) x n] -> conv at 3 j, BN at
+    3 j + 1; deconv{i} = SequentialCell[Conv2dTranspose, BN, ReLU] -> 0 and 1; conv_cls / conv_box / conv_dir_cls with bias.  A BN
+    entry has attribute ('bn', index).  The stride-1 deblock runs as a 1x1 conv here: its Conv2dTranspose weight [Cin, Cout, 1, 1] is
+    that conv's weight with the first two axes exchanged (`transposed`)."""
+    slots = []
+
+    def conv_bn(m, conv, bn, deblock=False):
+        if hasattr(m, "weight_t"):
+            slots.append((m, "weight_t", conv + ".weight", False))
+        else:
+            slots.append((m, "weight", conv + ".weight", deblock))
+        for i, n in enumerate(_PP_BN):
+            slots.append((m, ("bn", i), f"{bn}.{n}", False))
+
+    for i, blk in enumerate(model.neck.blocks):
+        for j, m in enumerate(blk):
+            conv_bn(m, f"{prefix}block{i + 1}.{3 * j}", f"{prefix}block{i + 1}.{3 * j + 1}")
+    for i, m in enumerate(model.neck.deblocks):
+        conv_bn(m, f"{prefix}deconv{i + 1}.0", f"{prefix}deconv{i + 1}.1", deblock=True)
+    for name in ("conv_cls", "conv_box", "conv_dir_cls"):
+        m = getattr(model.bbox_head, name)
+        if m is not None:
+            slots += [(m, "weight", f"{prefix}{name}.weight", False), (m, "bias", f"{prefix}{name}.bias", False)]
+    return slots
+
+
+def pointpillars_state(model, prefix="rpn.", naming="ms"):
+    """graphs.PointPillarsNet parameters under the reference's names (`rpn.block1.0.weight`, `rpn.block1.1.gamma`, ...,
+    `rpn.deconv3.0.weight`, `rpn.conv_cls.weight`, `rpn.conv_cls.bias`, ...), MindSpore or, with naming='torch', the BatchNorm
+    names of a torch state dict (weight, bias, running_mean, running_var)."""
+    t_names = dict(zip(_PP_BN, ("weight", "bias", "running_mean", "running_var")))
+    out = {}
+    for m, attr, key, transposed in _pointpillars_slots(model, prefix):
+        if isinstance(attr, tuple):
+            v = m.bn[attr[1]]
+            if naming != "ms":
+                head, leaf = key.rsplit(".", 1)
+                key = f"{head}.{t_names[leaf]}"
+        else:
+            v = getattr(m, attr)
+            v = v.permute(1, 0, 2, 3) if transposed else v
+        out[key] = np.ascontiguousarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v))
+    return out
+
+
+def load_pointpillars(model, params, prefix="rpn.", naming="auto", strict=True):
+    """Write a PointPillars checkpoint (the names of pointpillars_state; a training checkpoint's `network.network.` / `optimizer.`
+    prefixes are stripped as the reference's get_params_for_net does) into a graphs.PointPillarsNet; returns the unused keys.  naming
+    'torch' goes through `torch_to_ms_generic` first; call model.to(device) afterwards to fold, merge and pack.  No checkpoint of this
+    model ships with the reference: only the round trip is tested, parity with real weights is unpinned."""
+    if any(k.startswith(("network.network.", "optimizer.")) for k in params):
+        params = strip_net_prefix(params)
+    if naming == "auto":
+        naming = "torch" if any(k.endswith("running_var") for k in params) else "ms"
+    if naming == "torch":
+        kmap = torch_to_ms_generic(params.keys())
+        params = {kmap[k]: v for k, v in params.items() if k in kmap}
+    used = set()
+    for m, attr, key, transposed in _pointpillars_slots(model, prefix):
+        like = m.bn[attr[1]] if isinstance(attr, tuple) else getattr(m, attr)
+        if key not in params:
+            if strict:
+                raise KeyError(f"checkpoint has no {key!r}")
+            continue
+        a = torch.from_numpy(np.asarray(params[key]).astype(np.float32))
+        if transposed and a.dim() == 4:
+            a = a.permute(1, 0, 2, 3).contiguous()
+        if tuple(a.shape) != tuple(like.shape):
+            raise ValueError(f"{key}: checkpoint shape {tuple(np.asarray(params[key]).shape)} does not fit the model's {tuple(like.shape)}")
+        used.add(key)
+        if isinstance(attr, tuple):
+            bn = list(m.bn)
+            bn[attr[1]] = a
+            m.bn = tuple(bn)
+        else:
+            setattr(m, attr, a)
+    return sorted(k for k in params if k not in used)

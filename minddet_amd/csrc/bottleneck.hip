@@ -32,18 +32,9 @@
 #include <stdlib.h>
 
 #include "aot.h"
+#include "device.h"
 
 namespace md {
-
-typedef __attribute__((ext_vector_type(8))) short bn_bf16x8;
-typedef __attribute__((ext_vector_type(16))) float bn_f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned int bn_u32x4;
-typedef float bn_f32x2 __attribute__((ext_vector_type(2)));
-// LDS accesses below use BUILTIN vector types only: hipcc's waitcnt pass puts s_waitcnt vmcnt(0) in front of an LDS access without type-based
-// alias info (HIP's float4 / uint2 structs) while LDS-DMAs are pending -- r02: that drained the W2-tap / W3 DMAs in front of the T1 / T2
-// epilogues instead of letting the epilogue math run under their latency
-typedef float bn_f32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((ext_vector_type(2))) unsigned int bn_u32x2;
 
 struct BottleneckArgs {
     const uint16_t *x;    // [N,H,W,Cin]
@@ -65,18 +56,6 @@ constexpr int BN_TH = 8, BN_TW = 16, BN_HW = BN_TW + 2, BN_HALO = (BN_TH + 2) * 
 constexpr int BN_ROWB = 128;
 constexpr int BN_A = 0, BN_B = 32768, BN_C = 57344, BN_D = 65536, BN_LDS = 81920;
 constexpr int BN_ES = 144;  // transpose image row stride (64 channels * 2 B + 16)
-
-__device__ __forceinline__ unsigned bn_pk_bf16(float lo, float hi) {
-    unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-    return r;
-}
-__device__ __forceinline__ unsigned bn_pk_relu(unsigned v) {
-    unsigned r;
-    asm("v_pk_max_i16 %0, %1, 0" : "=v"(r) : "v"(v));
-    return r;
-}
-__device__ __forceinline__ int bn_swz(int row, int chunk) { return row * BN_ROWB + ((chunk ^ ((row >> 1) & 7)) << 4); }
 
 // MD_DIAG build (tools/bottleneck_stamps.py): cycle stamps of one mid-grid workgroup, written to a buffer of their own
 #ifdef MD_DIAG
@@ -133,11 +112,11 @@ __global__ __launch_bounds__(512, 4) void bottleneck64_kernel(BottleneckArgs a) 
 #endif
     BN_STAMP(0);
 
-    __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void *)a.x, 0, a.x_bytes, 0x00020000);
-    __amdgpu_buffer_rsrc_t rs_w1 = __builtin_amdgcn_make_buffer_rsrc((void *)a.w1, 0, a.w1_bytes, 0x00020000);
-    __amdgpu_buffer_rsrc_t rs_w2 = __builtin_amdgcn_make_buffer_rsrc((void *)a.w2, 0, 64 * 576 * 2, 0x00020000);
-    __amdgpu_buffer_rsrc_t rs_w3 = __builtin_amdgcn_make_buffer_rsrc((void *)a.w3, 0, 256 * 64 * 2, 0x00020000);
-    __amdgpu_buffer_rsrc_t rs_wd = __builtin_amdgcn_make_buffer_rsrc((void *)(MODE == 2 ? a.wd : a.w3), 0, 256 * 64 * 2, 0x00020000);
+    __amdgpu_buffer_rsrc_t rs_x = srd(a.x, a.x_bytes);
+    __amdgpu_buffer_rsrc_t rs_w1 = srd(a.w1, a.w1_bytes);
+    __amdgpu_buffer_rsrc_t rs_w2 = srd(a.w2, 64 * 576 * 2);
+    __amdgpu_buffer_rsrc_t rs_w3 = srd(a.w3, 256 * 64 * 2);
+    __amdgpu_buffer_rsrc_t rs_wd = srd(MODE == 2 ? a.wd : a.w3, 256 * 64 * 2);
 
     // ---- staging maps.  One wave instruction = 8 rows x 128 B; lane -> (row = 8 * piece + lane / 8, physical chunk = lane & 7).
     // 64-row weight tiles = 8 pieces: wave w stages piece w.  x halo = 24 pieces: wave w stages pieces w, w + 8, w + 16.
@@ -177,17 +156,17 @@ __global__ __launch_bounds__(512, 4) void bottleneck64_kernel(BottleneckArgs a) 
     // ---- phase A: T1 = relu(W1 . x + b1) on the 192 halo rows = 2 cout x 6 row fragments of 32 x 32: wave (wc, wq) owns row
     // fragments wq and, for wq < 2, wq + 4
     const bool two = wq < 2;
-    bn_f32x16 acc1[2];
+    f32x16 acc1[2];
     // phase C ownership: wave (wc, wq) = output quarters 2 wc + {0, 1} x pixels 32 wq .. + 31.  This lane's four 16-B pieces of a quarter
     // (the read-out of the wave's 16-pixel slab, twice): piece i = h * 2 + it -> pixel 32 wq + 16 h + 8 it + lane / 8, 16-B chunk lane & 7
-    bn_u32x4 rres[MODE == 2 ? 1 : 2][MODE == 2 ? 1 : 4];
+    u32x4 rres[MODE == 2 ? 1 : 2][MODE == 2 ? 1 : 4];
     int res_lds[4] = {0, 0, 0, 0};   // IDENT: where that piece of the residual sits in an x chunk (halo row of the centre pixel, swizzled chunk)
     if constexpr (MODE == 0) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int p = 32 * wq + 8 * i + (lane >> 3), cc = lane & 7;
             const int r = ((p >> 4) + 1) * BN_HW + (p & 15) + 1;
-            res_lds[i] = bn_swz(r, cc);
+            res_lds[i] = swz128(r, cc);
         }
     }
     dma_chunk_a(0, 0);
@@ -214,27 +193,27 @@ __global__ __launch_bounds__(512, 4) void bottleneck64_kernel(BottleneckArgs a) 
         if constexpr (MODE == 2) {   // the downsample conv on the centre pixels (kt == 0 is the only chunk)
             const int pc_ = 32 * wq + hp_now();
             const int rc = ((pc_ >> 4) + 1) * BN_HW + (pc_ & 15) + 1;   // halo row of this lane's centre pixel
-            bn_bf16x8 fx[4];
+            bf16x8 fx[4];
 #pragma unroll
-            for (int kk = 0; kk < 4; ++kk) fx[kk] = *reinterpret_cast<const bn_bf16x8 *>(Xt + bn_swz(rc, 2 * kk + lh));
+            for (int kk = 0; kk < 4; ++kk) fx[kk] = *reinterpret_cast<const bf16x8 *>(Xt + swz128(rc, 2 * kk + lh));
 #pragma unroll
             // (the row expressions are written out in place: a hoisted `row0 = 64 q + 32 wc` cost this instantiation 9 spilled registers, and
             // with scratch in use the kernel ran 7 % slower -- r03, found by bisecting against the round-2 source)
             for (int q = 0; q < 4; ++q) {   // the (quarter, cout fragment) tiles this wave owns again in phase C: M2_SLAB: cout rows
                                             // 64 (2 wc + q / 2) + 32 (q & 1) .., else 64 q + 32 wc ..
-                bn_f32x16 accd;
+                f32x16 accd;
 #pragma unroll
                 for (int e = 0; e < 16; ++e) accd[e] = 0.f;
 #pragma unroll
                 for (int kk = 0; kk < 4; ++kk) {
-                    const bn_bf16x8 fa = *reinterpret_cast<const bn_bf16x8 *>(smem + BN_B + bn_swz((M2_SLAB ? 64 * (2 * wc + (q >> 1)) + 32 * (q & 1) : 64 * q + 32 * wc) + lr, 2 * kk + lh));
+                    const bf16x8 fa = *reinterpret_cast<const bf16x8 *>(smem + BN_B + swz128((M2_SLAB ? 64 * (2 * wc + (q >> 1)) + 32 * (q & 1) : 64 * q + 32 * wc) + lr, 2 * kk + lh));
                     accd = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fx[kk], accd, 0, 0, 0);
                 }
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    const bn_f32x4 bv = *reinterpret_cast<const bn_f32x4 *>(bias12 + 128 + (M2_SLAB ? 64 * (2 * wc + (q >> 1)) + 32 * (q & 1) : 64 * q + 32 * wc) + 8 * g + 4 * lh);
-                    resd[q][2 * g + 0] = bn_pk_bf16(accd[4 * g + 0] + bv.x, accd[4 * g + 1] + bv.y);
-                    resd[q][2 * g + 1] = bn_pk_bf16(accd[4 * g + 2] + bv.z, accd[4 * g + 3] + bv.w);
+                    const f32x4 bv = *reinterpret_cast<const f32x4 *>(bias12 + 128 + (M2_SLAB ? 64 * (2 * wc + (q >> 1)) + 32 * (q & 1) : 64 * q + 32 * wc) + 8 * g + 4 * lh);
+                    resd[q][2 * g + 0] = pk_bf16(accd[4 * g + 0] + bv.x, accd[4 * g + 1] + bv.y);
+                    resd[q][2 * g + 1] = pk_bf16(accd[4 * g + 2] + bv.z, accd[4 * g + 3] + bv.w);
                 }
                 __builtin_amdgcn_sched_barrier(0);   // keeps hipcc from hoisting all four quarters' fragment reads (register budget)
             }
@@ -247,11 +226,11 @@ __global__ __launch_bounds__(512, 4) void bottleneck64_kernel(BottleneckArgs a) 
         }
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
-            const bn_bf16x8 fa = *reinterpret_cast<const bn_bf16x8 *>(Wt + bn_swz(32 * wc + lr, 2 * kk + lh));
-            const bn_bf16x8 fb0 = *reinterpret_cast<const bn_bf16x8 *>(Xt + bn_swz(32 * wq + lr, 2 * kk + lh));
+            const bf16x8 fa = *reinterpret_cast<const bf16x8 *>(Wt + swz128(32 * wc + lr, 2 * kk + lh));
+            const bf16x8 fb0 = *reinterpret_cast<const bf16x8 *>(Xt + swz128(32 * wq + lr, 2 * kk + lh));
             acc1[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fb0, acc1[0], 0, 0, 0);
             if (two) {
-                const bn_bf16x8 fb1 = *reinterpret_cast<const bn_bf16x8 *>(Xt + bn_swz(32 * (wq + 4) + lr, 2 * kk + lh));
+                const bf16x8 fb1 = *reinterpret_cast<const bf16x8 *>(Xt + swz128(32 * (wq + 4) + lr, 2 * kk + lh));
                 acc1[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fb1, acc1[1], 0, 0, 0);
             }
         }
@@ -260,7 +239,7 @@ __global__ __launch_bounds__(512, 4) void bottleneck64_kernel(BottleneckArgs a) 
             for (int q = 0; q < 4; ++q)
                 if (q == kt && (q >> 1) == wc) {
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) rres[q & 1][i] = *reinterpret_cast<const bn_u32x4 *>(Xt + res_lds[i]);
+                    for (int i = 0; i < 4; ++i) rres[q & 1][i] = *reinterpret_cast<const u32x4 *>(Xt + res_lds[i]);
                 }
         }
         BN_BAR_RAW();   // every wave has finished reading this buffer
@@ -290,12 +269,12 @@ __global__ __launch_bounds__(512, 4) void bottleneck64_kernel(BottleneckArgs a) 
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int c_local = 32 * wc + 8 * g + 4 * lh;
-                const bn_f32x4 bv = *reinterpret_cast<const bn_f32x4 *>(bias12 + c_local);
-                bn_u32x2 pk;
-                pk.x = bn_pk_relu(bn_pk_bf16(acc1[j][4 * g + 0] + bv.x, acc1[j][4 * g + 1] + bv.y));
-                pk.y = bn_pk_relu(bn_pk_bf16(acc1[j][4 * g + 2] + bv.z, acc1[j][4 * g + 3] + bv.w));
+                const f32x4 bv = *reinterpret_cast<const f32x4 *>(bias12 + c_local);
+                u32x2 pk;
+                pk.x = pk_relu_bf16(pk_bf16(acc1[j][4 * g + 0] + bv.x, acc1[j][4 * g + 1] + bv.y));
+                pk.y = pk_relu_bf16(pk_bf16(acc1[j][4 * g + 2] + bv.z, acc1[j][4 * g + 3] + bv.w));
                 if (!ok) pk.x = pk.y = 0u;
-                *reinterpret_cast<bn_u32x2 *>(T1 + r * BN_ROWB + (((4 * wc + g) ^ ((r >> 1) & 7)) << 4) + 8 * lh) = pk;
+                *reinterpret_cast<u32x2 *>(T1 + r * BN_ROWB + (((4 * wc + g) ^ ((r >> 1) & 7)) << 4) + 8 * lh) = pk;
             }
         }
     }
@@ -304,7 +283,7 @@ __global__ __launch_bounds__(512, 4) void bottleneck64_kernel(BottleneckArgs a) 
     BN_STAMP(3);
 
     // ---- phase B: T2 = relu(conv3x3(T1) + b2) = 2 cout x 4 pixel fragments: wave (wc, wq) owns couts 32 wc.., pixels 32 wq..
-    bn_f32x16 acc2;
+    f32x16 acc2;
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc2[e] = 0.f;
     const int pB = 32 * wq + hp_now();
@@ -315,11 +294,11 @@ __global__ __launch_bounds__(512, 4) void bottleneck64_kernel(BottleneckArgs a) 
         const char *T1 = smem + BN_B;
         const int r = r0 + (t / 3) * BN_HW + (t % 3);
         const int sw = (r >> 1) & 7;
-        bn_bf16x8 tfa[4], tfb[4];
+        bf16x8 tfa[4], tfb[4];
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
-            tfb[kk] = *reinterpret_cast<const bn_bf16x8 *>(T1 + r * BN_ROWB + (((2 * kk + lh) ^ sw) << 4));
-            tfa[kk] = *reinterpret_cast<const bn_bf16x8 *>(Wt + bn_swz(32 * wc + lr, 2 * kk + lh));
+            tfb[kk] = *reinterpret_cast<const bf16x8 *>(T1 + r * BN_ROWB + (((2 * kk + lh) ^ sw) << 4));
+            tfa[kk] = *reinterpret_cast<const bf16x8 *>(Wt + swz128(32 * wc + lr, 2 * kk + lh));
         }
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tfa[kk], tfb[kk], acc2, 0, 0, 0);
@@ -337,9 +316,9 @@ __global__ __launch_bounds__(512, 4) void bottleneck64_kernel(BottleneckArgs a) 
     BN_STAMP(5);
 #pragma unroll
     for (int t = 5; t < 9; ++t) tap_mfma(t, smem + BN_A + (t - 5) * 8192);
-    bn_f32x4 bv2[4];
+    f32x4 bv2[4];
 #pragma unroll
-    for (int g = 0; g < 4; ++g) bv2[g] = *reinterpret_cast<const bn_f32x4 *>(bias12 + 64 + 32 * wc + 8 * g + 4 * lh);
+    for (int g = 0; g < 4; ++g) bv2[g] = *reinterpret_cast<const f32x4 *>(bias12 + 64 + 32 * wc + 8 * g + 4 * lh);
     __syncthreads();   // every wave is done with T1, the tap buffers and b2
     BN_STAMP(6);
     // W3 (256 x 64) -> region A: 32 pieces, wave w stages pieces w + 8j
@@ -353,10 +332,10 @@ __global__ __launch_bounds__(512, 4) void bottleneck64_kernel(BottleneckArgs a) 
         char *T2 = smem + BN_D;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            bn_u32x2 pk;
-            pk.x = bn_pk_relu(bn_pk_bf16(acc2[4 * g + 0] + bv2[g].x, acc2[4 * g + 1] + bv2[g].y));
-            pk.y = bn_pk_relu(bn_pk_bf16(acc2[4 * g + 2] + bv2[g].z, acc2[4 * g + 3] + bv2[g].w));
-            *reinterpret_cast<bn_u32x2 *>(T2 + (32 * wq + lr) * BN_ROWB + (((4 * wc + g) ^ ((lr >> 1) & 7)) << 4) + 8 * lh) = pk;   // row = lane
+            u32x2 pk;
+            pk.x = pk_relu_bf16(pk_bf16(acc2[4 * g + 0] + bv2[g].x, acc2[4 * g + 1] + bv2[g].y));
+            pk.y = pk_relu_bf16(pk_bf16(acc2[4 * g + 2] + bv2[g].z, acc2[4 * g + 3] + bv2[g].w));
+            *reinterpret_cast<u32x2 *>(T2 + (32 * wq + lr) * BN_ROWB + (((4 * wc + g) ^ ((lr >> 1) & 7)) << 4) + 8 * lh) = pk;   // row = lane
         }
     }
     if constexpr (MODE == 2 && !M2_SLAB) {
@@ -381,40 +360,37 @@ __global__ __launch_bounds__(512, 4) void bottleneck64_kernel(BottleneckArgs a) 
         const int pE = 32 * wq + hp_now();   // the pixel of accumulator column lr
         // the pixel operand (T2 fragments) is the same for all four quarters: read once; the weight fragments of quarter q + 1 are
         // requested before quarter q's epilogue (W3 is read-only in this phase: no hazard with the image barriers)
-        bn_bf16x8 fbc[4], fac[2][4];
+        bf16x8 fbc[4], fac[2][4];
     #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
-            fbc[kk] = *reinterpret_cast<const bn_bf16x8 *>(smem + BN_D + bn_swz(32 * wq + lr, 2 * kk + lh));
-            fac[0][kk] = *reinterpret_cast<const bn_bf16x8 *>(smem + BN_A + bn_swz(32 * wc + lr, 2 * kk + lh));
+            fbc[kk] = *reinterpret_cast<const bf16x8 *>(smem + BN_D + swz128(32 * wq + lr, 2 * kk + lh));
+            fac[0][kk] = *reinterpret_cast<const bf16x8 *>(smem + BN_A + swz128(32 * wc + lr, 2 * kk + lh));
         }
     #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            bn_f32x16 acc3;
+            f32x16 acc3;
     #pragma unroll
             for (int e = 0; e < 16; ++e) acc3[e] = 0.f;
     #pragma unroll
             for (int kk = 0; kk < 4; ++kk) {
-                if (q + 1 < 4) fac[(q + 1) & 1][kk] = *reinterpret_cast<const bn_bf16x8 *>(smem + BN_A + bn_swz(64 * (q + 1) + 32 * wc + lr, 2 * kk + lh));
+                if (q + 1 < 4) fac[(q + 1) & 1][kk] = *reinterpret_cast<const bf16x8 *>(smem + BN_A + swz128(64 * (q + 1) + 32 * wc + lr, 2 * kk + lh));
                 acc3 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fac[q & 1][kk], fbc[kk], acc3, 0, 0, 0);
             }
             if (q == 1) BN_STAMP(13);
     #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int c_local = 32 * wc + 8 * g + 4 * lh;
-                const bn_f32x4 bv = *reinterpret_cast<const bn_f32x4 *>(bias3 + 64 * q + c_local);
-                bn_u32x2 pk;
-                pk.x = bn_pk_bf16(acc3[4 * g + 0] + bv.x, acc3[4 * g + 1] + bv.y);
-                pk.y = bn_pk_bf16(acc3[4 * g + 2] + bv.z, acc3[4 * g + 3] + bv.w);
+                const f32x4 bv = *reinterpret_cast<const f32x4 *>(bias3 + 64 * q + c_local);
+                u32x2 pk;
+                pk.x = pk_bf16(acc3[4 * g + 0] + bv.x, acc3[4 * g + 1] + bv.y);
+                pk.y = pk_bf16(acc3[4 * g + 2] + bv.z, acc3[4 * g + 3] + bv.w);
                 if constexpr (MODE == 2) {   // + bf16(Wd . x + bd), ReLU: the final value goes into the image
                     const unsigned r0_ = resd[q][2 * g], r1_ = resd[q][2 * g + 1];
-                    const bn_f32x2 s0 = (bn_f32x2){__uint_as_float(pk.x << 16), __uint_as_float(pk.x & 0xffff0000u)} +
-                                        (bn_f32x2){__uint_as_float(r0_ << 16), __uint_as_float(r0_ & 0xffff0000u)};
-                    const bn_f32x2 s1 = (bn_f32x2){__uint_as_float(pk.y << 16), __uint_as_float(pk.y & 0xffff0000u)} +
-                                        (bn_f32x2){__uint_as_float(r1_ << 16), __uint_as_float(r1_ & 0xffff0000u)};
-                    pk.x = bn_pk_relu(bn_pk_bf16(s0.x, s0.y));
-                    pk.y = bn_pk_relu(bn_pk_bf16(s1.x, s1.y));
+                    const f32x2 s0 = bf2f_pair(pk.x) + bf2f_pair(r0_), s1 = bf2f_pair(pk.y) + bf2f_pair(r1_);
+                    pk.x = pk_relu_bf16(pk_bf16(s0.x, s0.y));
+                    pk.y = pk_relu_bf16(pk_bf16(s1.x, s1.y));
                 }
-                *reinterpret_cast<bn_u32x2 *>(E + pE * BN_ES + c_local * 2) = pk;
+                *reinterpret_cast<u32x2 *>(E + pE * BN_ES + c_local * 2) = pk;
             }
             BN_BAR_RAW();   // raw barriers in this loop: __syncthreads() would wait for the previous quarter's stores to COMPLETE (vmcnt 0)
             if (q == 1) BN_STAMP(14);
@@ -422,8 +398,8 @@ __global__ __launch_bounds__(512, 4) void bottleneck64_kernel(BottleneckArgs a) 
             for (int it = 0; it < 2; ++it) {
                 if (g_off[it] < 0) continue;
                 const int e = tid + 512 * it;
-                bn_u32x4 v = *reinterpret_cast<const bn_u32x4 *>(E + (e >> 3) * BN_ES + (e & 7) * 16);
-                __builtin_nontemporal_store(v, reinterpret_cast<bn_u32x4 *>(a.y + g_off[it] + 64 * q));
+                u32x4 v = *reinterpret_cast<const u32x4 *>(E + (e >> 3) * BN_ES + (e & 7) * 16);
+                __builtin_nontemporal_store(v, reinterpret_cast<u32x4 *>(a.y + g_off[it] + 64 * q));
             }
             if (q == 1) BN_STAMP(15);
             BN_BAR_RAW();      // the image is rewritten by the next quarter
@@ -442,7 +418,7 @@ __global__ __launch_bounds__(512, 4) void bottleneck64_kernel(BottleneckArgs a) 
         }
         const long long pix00 = ((long long)n * a.H + y0) * a.W + x0;
         const long long y_rem = ((long long)a.N * a.H * a.W - pix00) * 512;
-        __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc((void *)(a.y + pix00 * 256), 0, (int)(y_rem > 0x7fffffffLL ? 0x7fffffffLL : y_rem), 0x00020000);
+        __amdgpu_buffer_rsrc_t rs_y = srd(a.y + pix00 * 256, (int)(y_rem > 0x7fffffffLL ? 0x7fffffffLL : y_rem));
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         BN_STAMP(7);
@@ -451,17 +427,17 @@ __global__ __launch_bounds__(512, 4) void bottleneck64_kernel(BottleneckArgs a) 
         const float *bias3 = reinterpret_cast<const float *>(smem + BN_C);
         char *slab = smem + BN_B + wave * 2560;   // 16 pixels x 64 channels, 144-B rows (region B: T1 is consumed)
         if constexpr (MODE == 1) {   // a separate residual tensor: all 8 pieces requested now, behind every DMA of the tile
-            __amdgpu_buffer_rsrc_t rs_r = __builtin_amdgcn_make_buffer_rsrc((void *)(a.res + pix00 * 256), 0, (int)(y_rem > 0x7fffffffLL ? 0x7fffffffLL : y_rem), 0x00020000);
+            __amdgpu_buffer_rsrc_t rs_r = srd(a.res + pix00 * 256, (int)(y_rem > 0x7fffffffLL ? 0x7fffffffLL : y_rem));
     #pragma unroll
             for (int q2 = 0; q2 < 2; ++q2)
     #pragma unroll
                 for (int i = 0; i < 4; ++i)
-                    rres[q2][i] = __builtin_bit_cast(bn_u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_r, (int)y_off[i], (2 * wc + q2) * 128, 2));
+                    rres[q2][i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_r, (int)y_off[i], (2 * wc + q2) * 128, 2));
         }
         // the pixel operand (T2 fragments) is the same for both quarters: read once
-        bn_bf16x8 fbc[4];
+        bf16x8 fbc[4];
     #pragma unroll
-        for (int kk = 0; kk < 4; ++kk) fbc[kk] = *reinterpret_cast<const bn_bf16x8 *>(smem + BN_D + bn_swz(32 * wq + lr, 2 * kk + lh));
+        for (int kk = 0; kk < 4; ++kk) fbc[kk] = *reinterpret_cast<const bf16x8 *>(smem + BN_D + swz128(32 * wq + lr, 2 * kk + lh));
     #pragma unroll
         for (int q2 = 0; q2 < 2; ++q2) {
             const int q = 2 * wc + q2;   // output channels 64 q .. 64 q + 63
@@ -470,27 +446,24 @@ __global__ __launch_bounds__(512, 4) void bottleneck64_kernel(BottleneckArgs a) 
             unsigned pkv[2][8];
     #pragma unroll
             for (int f = 0; f < 2; ++f) {
-                bn_f32x16 acc3;
+                f32x16 acc3;
     #pragma unroll
                 for (int e = 0; e < 16; ++e) acc3[e] = 0.f;
     #pragma unroll
                 for (int kk = 0; kk < 4; ++kk) {
-                    const bn_bf16x8 fa = *reinterpret_cast<const bn_bf16x8 *>(smem + BN_A + bn_swz(64 * q + 32 * f + lr, 2 * kk + lh));
+                    const bf16x8 fa = *reinterpret_cast<const bf16x8 *>(smem + BN_A + swz128(64 * q + 32 * f + lr, 2 * kk + lh));
                     acc3 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fbc[kk], acc3, 0, 0, 0);
                 }
     #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    const bn_f32x4 bv = *reinterpret_cast<const bn_f32x4 *>(bias3 + 64 * q + 32 * f + 8 * g + 4 * lh);
-                    unsigned p0 = bn_pk_bf16(acc3[4 * g + 0] + bv.x, acc3[4 * g + 1] + bv.y);
-                    unsigned p1 = bn_pk_bf16(acc3[4 * g + 2] + bv.z, acc3[4 * g + 3] + bv.w);
+                    const f32x4 bv = *reinterpret_cast<const f32x4 *>(bias3 + 64 * q + 32 * f + 8 * g + 4 * lh);
+                    unsigned p0 = pk_bf16(acc3[4 * g + 0] + bv.x, acc3[4 * g + 1] + bv.y);
+                    unsigned p1 = pk_bf16(acc3[4 * g + 2] + bv.z, acc3[4 * g + 3] + bv.w);
                     if constexpr (MODE == 2) {
                         const unsigned r0_ = resd[q2 * 2 + f][2 * g], r1_ = resd[q2 * 2 + f][2 * g + 1];
-                        const bn_f32x2 s0 = (bn_f32x2){__uint_as_float(p0 << 16), __uint_as_float(p0 & 0xffff0000u)} +
-                                            (bn_f32x2){__uint_as_float(r0_ << 16), __uint_as_float(r0_ & 0xffff0000u)};
-                        const bn_f32x2 s1 = (bn_f32x2){__uint_as_float(p1 << 16), __uint_as_float(p1 & 0xffff0000u)} +
-                                            (bn_f32x2){__uint_as_float(r1_ << 16), __uint_as_float(r1_ & 0xffff0000u)};
-                        p0 = bn_pk_relu(bn_pk_bf16(s0.x, s0.y));
-                        p1 = bn_pk_relu(bn_pk_bf16(s1.x, s1.y));
+                        const f32x2 s0 = bf2f_pair(p0) + bf2f_pair(r0_), s1 = bf2f_pair(p1) + bf2f_pair(r1_);
+                        p0 = pk_relu_bf16(pk_bf16(s0.x, s0.y));
+                        p1 = pk_relu_bf16(pk_bf16(s1.x, s1.y));
                     }
                     pkv[f][2 * g] = p0; pkv[f][2 * g + 1] = p1;
                 }
@@ -505,7 +478,7 @@ __global__ __launch_bounds__(512, 4) void bottleneck64_kernel(BottleneckArgs a) 
                     for (int f = 0; f < 2; ++f)
     #pragma unroll
                         for (int g = 0; g < 4; ++g)
-                            *reinterpret_cast<bn_u32x2 *>(slab + (hp & 15) * BN_ES + f * 64 + 16 * g + 8 * lh) = (bn_u32x2){pkv[f][2 * g], pkv[f][2 * g + 1]};
+                            *reinterpret_cast<u32x2 *>(slab + (hp & 15) * BN_ES + f * 64 + 16 * g + 8 * lh) = (u32x2){pkv[f][2 * g], pkv[f][2 * g + 1]};
                 }
                 // The slab is read back by OTHER lanes of the wave, in another vector type: without a compiler-level ordering point hipcc
                 // duplicated the read-out into the lanes that skip the write block and ran it FIRST (stale rows in exactly those lanes' pieces;
@@ -513,17 +486,9 @@ __global__ __launch_bounds__(512, 4) void bottleneck64_kernel(BottleneckArgs a) 
                 MD_WAVE_LDS_ORDER();
     #pragma unroll
                 for (int it = 0; it < 2; ++it) {
-                    bn_u32x4 v = *reinterpret_cast<const bn_u32x4 *>(slab + (8 * it + (lane >> 3)) * BN_ES + (lane & 7) * 16);
-                    if constexpr (MODE != 2) {
-                        const bn_u32x4 rv = rres[q2][h * 2 + it];
-    #pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            const bn_f32x2 sum = (bn_f32x2){__uint_as_float(v[k] << 16), __uint_as_float(v[k] & 0xffff0000u)} +
-                                                 (bn_f32x2){__uint_as_float(rv[k] << 16), __uint_as_float(rv[k] & 0xffff0000u)};
-                            v[k] = bn_pk_relu(bn_pk_bf16(sum.x, sum.y));
-                        }
-                    }
-                    MD_BUFFER_STORE_B128(v, rs_y, y_off[h * 2 + it], q * 128, 2);   // (store + guard: aot.h)
+                    u32x4 v = *reinterpret_cast<const u32x4 *>(slab + (8 * it + (lane >> 3)) * BN_ES + (lane & 7) * 16);
+                    if constexpr (MODE != 2) MD_ADD_BF16X8(v, rres[q2][h * 2 + it], true);
+                    MD_BUFFER_STORE_B128(v, rs_y, y_off[h * 2 + it], q * 128, 2);   // (store + guard: device.h)
                 }
                 MD_WAVE_LDS_ORDER();   // ... and the next half's writes stay behind this half's reads
             }

@@ -1,10 +1,38 @@
-// box_codec.h -- the per-box device arithmetic that more than one translation unit runs: second_box_decode and the standup box.
-// detops.hip (md_second_box_decode, md_standup_boxes) and pphead.hip (md_pp_decode_selected) call these two functions and nothing
-// else for that arithmetic, so the fused PointPillars decode agrees with the stand-alone operators bit for bit.
+// box_codec.h -- the per-box device arithmetic that more than one translation unit runs: second_box_decode, the standup box and the
+// delta-to-box decode.  detops.hip (md_second_box_decode, md_standup_boxes) and pphead.hip (md_pp_decode_selected) call the first two
+// and nothing else for that arithmetic, so the fused PointPillars decode agrees with the stand-alone operators bit for bit;
+// detops.hip (md_delta2bbox) and twostage.hip (the RPN and R-CNN decodes) call the third.
 #pragma once
 #include <hip/hip_runtime.h>
 
-// every product below is rounded before it is added (no fused multiply-add), as in detops.hip: part of the arithmetic both units share
+namespace md {
+
+// delta2bbox (the public mmdet definition): deltas (dx, dy, dw, dh), denormalised by p.mean / p.stdv, applied to the box r = (x1, y1, x2,
+// y2); dw, dh clamped to +-p.max_ratio.  clip_box then clamps the result to [0, w] x [0, h]; WHETHER to clip is the caller's decision and
+// stays at the call: md_delta2bbox clips when clip_w > 0 && clip_h > 0 (its do_clip), the two-stage decodes when p.clip_w > 0.
+// These two functions stand ABOVE the contraction pragma below and so takes the mode of the unit that includes it: detops.hip switches
+// contraction off first (every product rounded, as its float64-judged contract says), twostage.hip keeps the compiler's fused
+// multiply-adds.  Both are what the two units computed when each had its own copy.
+struct DecodeP { float mean[4], stdv[4]; float max_ratio, clip_w, clip_h; };
+__device__ __forceinline__ float4 delta2bbox_one(float4 r, float dx, float dy, float dw, float dh, const DecodeP &p) {
+    dx = dx * p.stdv[0] + p.mean[0]; dy = dy * p.stdv[1] + p.mean[1];
+    dw = dw * p.stdv[2] + p.mean[2]; dh = dh * p.stdv[3] + p.mean[3];
+    dw = fminf(fmaxf(dw, -p.max_ratio), p.max_ratio);
+    dh = fminf(fmaxf(dh, -p.max_ratio), p.max_ratio);
+    const float px = (r.x + r.z) * 0.5f, py = (r.y + r.w) * 0.5f, pw = r.z - r.x, ph = r.w - r.y;
+    const float gw = pw * expf(dw), gh = ph * expf(dh);
+    const float gx = px + pw * dx, gy = py + ph * dy;
+    return make_float4(gx - gw * 0.5f, gy - gh * 0.5f, gx + gw * 0.5f, gy + gh * 0.5f);
+}
+__device__ __forceinline__ float4 clip_box(float4 b, float w, float h) {
+    const float x1 = fminf(fmaxf(b.x, 0.f), w), x2 = fminf(fmaxf(b.z, 0.f), w);
+    const float y1 = fminf(fmaxf(b.y, 0.f), h), y2 = fminf(fmaxf(b.w, 0.f), h);
+    return make_float4(x1, y1, x2, y2);
+}
+
+}  // namespace md
+
+// every product below is rounded before it is added (no fused multiply-add), as in detops.hip: part of the arithmetic the units share
 #pragma clang fp contract(off)
 
 namespace md {

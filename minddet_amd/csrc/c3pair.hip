@@ -25,15 +25,9 @@
 #include <stdint.h>
 
 #include "aot.h"
+#include "device.h"
 
 namespace md {
-
-typedef __attribute__((ext_vector_type(8))) short cp_bf16x8;
-typedef __attribute__((ext_vector_type(16))) float cp_f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned int cp_u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int cp_u32x2;
-typedef float cp_f32x2 __attribute__((ext_vector_type(2)));
-typedef float cp_f32x4 __attribute__((ext_vector_type(4)));   // (LDS accesses use builtin vector types only: see bottleneck.hip)
 
 struct C3PairArgs {
     const uint16_t *x;    // [N,H,W,XC]; the pair reads channels [x_off, x_off + C) (+ the next C when `pass`)
@@ -49,14 +43,6 @@ struct C3PairArgs {
 };
 
 constexpr int CP_TH = 8, CP_TW = 16, CP_HW = CP_TW + 2, CP_HALO = (CP_TH + 2) * CP_HW, CP_ROWS = 192;
-
-__device__ __forceinline__ unsigned cp_pk_bf16(float lo, float hi) {
-    unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-    return r;
-}
-// the SiLU of md_conv2d's epilogues (conv.hip: hardware reciprocal)
-__device__ __forceinline__ float cp_silu(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
 
 // MD_DIAG build (tools/c3pair_stamps.py): cycle stamps of one mid-grid workgroup
 #ifdef MD_DIAG
@@ -104,7 +90,6 @@ template <int C>
 __device__ __forceinline__ int cp_key(int row) { return C == 64 ? ((row >> 1) & 7) : (row & 15); }
 template <int C>
 __device__ __forceinline__ int cp_swz(int row, int chunk) { return row * (2 * C) + ((chunk ^ cp_key<C>(row)) << 4); }
-__device__ __forceinline__ int cp_wswz(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }   // sub-units: 128-B rows
 
 template <int C>
 __device__ __forceinline__ void c3pair_body(const C3PairArgs &a) {
@@ -129,9 +114,9 @@ __device__ __forceinline__ void c3pair_body(const C3PairArgs &a) {
 #endif
     CP_STAMP(0);
 
-    __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void *)a.x, 0, a.x_bytes, 0x00020000);
-    __amdgpu_buffer_rsrc_t rs_w1 = __builtin_amdgcn_make_buffer_rsrc((void *)a.w1, 0, C * C * 2, 0x00020000);
-    __amdgpu_buffer_rsrc_t rs_w2 = __builtin_amdgcn_make_buffer_rsrc((void *)a.w2, 0, C * 9 * C * 2, 0x00020000);
+    __amdgpu_buffer_rsrc_t rs_x = srd(a.x, a.x_bytes);
+    __amdgpu_buffer_rsrc_t rs_w1 = srd(a.w1, C * C * 2);
+    __amdgpu_buffer_rsrc_t rs_w2 = srd(a.w2, C * 9 * C * 2);
 
     // ---- staging maps.  x halo tile: one wave instruction = 1024 B = 1024 / ROWB rows; wave w stages pieces w, w + 8, ...
     unsigned h_off[G::XPW];
@@ -181,12 +166,12 @@ __device__ __forceinline__ void c3pair_body(const C3PairArgs &a) {
     if (tid < 2 * C) bias12[tid] = b12_early;
 
     char *T = smem + G::T_OFF;
-    cp_f32x16 acc1[G::NFA];
+    f32x16 acc1[G::NFA];
 #pragma unroll
     for (int j = 0; j < G::NFA; ++j)
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc1[j][e] = 0.f;
-    cp_f32x16 acc2[G::NFB];
+    f32x16 acc2[G::NFB];
 #pragma unroll
     for (int j = 0; j < G::NFB; ++j)
 #pragma unroll
@@ -201,15 +186,15 @@ __device__ __forceinline__ void c3pair_body(const C3PairArgs &a) {
     // the image: out-of-range offset = read as zero / store dropped by the hardware, no divergent branch).  The shortcut values and the
     // pass-through channels are requested three sub-units before the end of phase B (their latency runs under its last MFMAs; earlier
     // they would only hold registers)
-    __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc((void *)a.y, 0, a.y_bytes, 0x00020000);
+    __amdgpu_buffer_rsrc_t rs_y = srd(a.y, a.y_bytes);
     auto piece_off = [&](int it, int cstride, int c0) __attribute__((always_inline)) {
         const int e = tid + 512 * it, p = e / G::NCH, cc = e % G::NCH;
         const int yy = y0 + (p >> 4), xx = x0 + (p & 15);
         return (yy < a.H && xx < a.W) ? (unsigned)((((n * a.H + yy) * a.W + xx) * cstride + c0 + cc * 8) * 2) : OOR;
     };
-    cp_u32x4 rres[G::EP_ITERS], pval[G::EP_ITERS];
+    u32x4 rres[G::EP_ITERS], pval[G::EP_ITERS];
 #pragma unroll
-    for (int it = 0; it < G::EP_ITERS; ++it) rres[it] = pval[it] = (cp_u32x4){0u, 0u, 0u, 0u};
+    for (int it = 0; it < G::EP_ITERS; ++it) rres[it] = pval[it] = (u32x4){0u, 0u, 0u, 0u};
 
 #pragma unroll
     for (int g = 0; g < G::NG; ++g) {
@@ -230,12 +215,12 @@ __device__ __forceinline__ void c3pair_body(const C3PairArgs &a) {
                 // ---- phase A, K chunk q: T1 accumulators of halo-row fragments wq, wq + NWQ, ...
 #pragma unroll
                 for (int kk = 0; kk < 4; ++kk) {
-                    const cp_bf16x8 fa = *reinterpret_cast<const cp_bf16x8 *>(Wt + cp_wswz(32 * wc + lr, 2 * kk + lh));
+                    const bf16x8 fa = *reinterpret_cast<const bf16x8 *>(Wt + swz128(32 * wc + lr, 2 * kk + lh));
 #pragma unroll
                     for (int j = 0; j < G::NFA; ++j) {
                         const int f = wq + G::NWQ * j;
                         if (f < 6) {
-                            const cp_bf16x8 fb = *reinterpret_cast<const cp_bf16x8 *>(T + cp_swz<C>(32 * f + lr, 8 * q + 2 * kk + lh));
+                            const bf16x8 fb = *reinterpret_cast<const bf16x8 *>(T + cp_swz<C>(32 * f + lr, 8 * q + 2 * kk + lh));
                             acc1[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fb, acc1[j], 0, 0, 0);
                         }
                     }
@@ -257,12 +242,12 @@ __device__ __forceinline__ void c3pair_body(const C3PairArgs &a) {
 #pragma unroll
                             for (int gg = 0; gg < 4; ++gg) {
                                 const int c_local = 32 * wc + 8 * gg + 4 * lh;
-                                const cp_f32x4 bv = *reinterpret_cast<const cp_f32x4 *>(bias12 + c_local);
-                                cp_u32x2 pk;
-                                pk.x = cp_pk_bf16(cp_silu(acc1[j][4 * gg + 0] + bv.x), cp_silu(acc1[j][4 * gg + 1] + bv.y));
-                                pk.y = cp_pk_bf16(cp_silu(acc1[j][4 * gg + 2] + bv.z), cp_silu(acc1[j][4 * gg + 3] + bv.w));
+                                const f32x4 bv = *reinterpret_cast<const f32x4 *>(bias12 + c_local);
+                                u32x2 pk;
+                                pk.x = pk_bf16(silu(acc1[j][4 * gg + 0] + bv.x), silu(acc1[j][4 * gg + 1] + bv.y));
+                                pk.y = pk_bf16(silu(acc1[j][4 * gg + 2] + bv.z), silu(acc1[j][4 * gg + 3] + bv.w));
                                 if (!ok) pk.x = pk.y = 0u;
-                                if (r < G::BIAS_ROW) *reinterpret_cast<cp_u32x2 *>(T + r * G::ROWB + (((4 * wc + gg) ^ cp_key<C>(r)) << 4) + 8 * lh) = pk;
+                                if (r < G::BIAS_ROW) *reinterpret_cast<u32x2 *>(T + r * G::ROWB + (((4 * wc + gg) ^ cp_key<C>(r)) << 4) + 8 * lh) = pk;
                             }
                         }
                     }
@@ -281,10 +266,10 @@ __device__ __forceinline__ void c3pair_body(const C3PairArgs &a) {
                 const int shift = (t / 3) * CP_HW + (t % 3);
 #pragma unroll
                 for (int kk = 0; kk < 4; ++kk) {
-                    const cp_bf16x8 fa = *reinterpret_cast<const cp_bf16x8 *>(Wt + cp_wswz(32 * wc + lr, 2 * kk + lh));
+                    const bf16x8 fa = *reinterpret_cast<const bf16x8 *>(Wt + swz128(32 * wc + lr, 2 * kk + lh));
 #pragma unroll
                     for (int j = 0; j < G::NFB; ++j) {
-                        const cp_bf16x8 fb = *reinterpret_cast<const cp_bf16x8 *>(T + cp_swz<C>(r0[j] + shift, 8 * ch + 2 * kk + lh));
+                        const bf16x8 fb = *reinterpret_cast<const bf16x8 *>(T + cp_swz<C>(r0[j] + shift, 8 * ch + 2 * kk + lh));
                         acc2[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fb, acc2[j], 0, 0, 0);
                     }
                 }
@@ -292,8 +277,8 @@ __device__ __forceinline__ void c3pair_body(const C3PairArgs &a) {
 #pragma unroll
                     for (int it = 0; it < G::EP_ITERS; ++it) {
                         const unsigned xo = piece_off(it, a.XC, a.x_off);
-                        if (a.shortcut) rres[it] = __builtin_bit_cast(cp_u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_x, (int)xo, 0, 0));
-                        if (a.pass) pval[it] = __builtin_bit_cast(cp_u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_x, (int)xo, C * 2, 0));
+                        if (a.shortcut) rres[it] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_x, (int)xo, 0, 0));
+                        if (a.pass) pval[it] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_x, (int)xo, C * 2, 0));
                     }
                 }
             }
@@ -302,9 +287,9 @@ __device__ __forceinline__ void c3pair_body(const C3PairArgs &a) {
 
     CP_STAMP(5);
     // ---- epilogue: bias, SiLU -> bf16 image [pixel][cout] over T, then 16-B pieces (+ shortcut) to y
-    cp_f32x4 bv2[4];
+    f32x4 bv2[4];
 #pragma unroll
-    for (int g = 0; g < 4; ++g) bv2[g] = *reinterpret_cast<const cp_f32x4 *>(bias12 + C + 32 * wc + 8 * g + 4 * lh);
+    for (int g = 0; g < 4; ++g) bv2[g] = *reinterpret_cast<const f32x4 *>(bias12 + C + 32 * wc + 8 * g + 4 * lh);
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();   // every wave is done with T1 (and has b2 in registers)
@@ -317,10 +302,10 @@ __device__ __forceinline__ void c3pair_body(const C3PairArgs &a) {
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             const int c_local = 32 * wc + 8 * g + 4 * lh;
-            cp_u32x2 pk;
-            pk.x = cp_pk_bf16(cp_silu(acc2[j][4 * g + 0] + bv2[g].x), cp_silu(acc2[j][4 * g + 1] + bv2[g].y));
-            pk.y = cp_pk_bf16(cp_silu(acc2[j][4 * g + 2] + bv2[g].z), cp_silu(acc2[j][4 * g + 3] + bv2[g].w));
-            *reinterpret_cast<cp_u32x2 *>(E + p_local * G::ES + c_local * 2) = pk;
+            u32x2 pk;
+            pk.x = pk_bf16(silu(acc2[j][4 * g + 0] + bv2[g].x), silu(acc2[j][4 * g + 1] + bv2[g].y));
+            pk.y = pk_bf16(silu(acc2[j][4 * g + 2] + bv2[g].z), silu(acc2[j][4 * g + 3] + bv2[g].w));
+            *reinterpret_cast<u32x2 *>(E + p_local * G::ES + c_local * 2) = pk;
         }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -331,18 +316,10 @@ __device__ __forceinline__ void c3pair_body(const C3PairArgs &a) {
 #pragma unroll
     for (int it = 0; it < G::EP_ITERS; ++it) {
         const int e = tid + 512 * it, p = e / G::NCH, cc = e % G::NCH;
-        cp_u32x4 v = *reinterpret_cast<const cp_u32x4 *>(E + p * G::ES + cc * 16);
-        if (a.shortcut) {
-            const cp_u32x4 rv = rres[it];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const cp_f32x2 sum = (cp_f32x2){__uint_as_float(v[k] << 16), __uint_as_float(v[k] & 0xffff0000u)} +
-                                     (cp_f32x2){__uint_as_float(rv[k] << 16), __uint_as_float(rv[k] & 0xffff0000u)};
-                v[k] = cp_pk_bf16(sum.x, sum.y);
-            }
-        }
+        u32x4 v = *reinterpret_cast<const u32x4 *>(E + p * G::ES + cc * 16);
+        if (a.shortcut) MD_ADD_BF16X8(v, rres[it], false);
         const unsigned yo = piece_off(it, a.YC, a.y_off);
-        MD_BUFFER_STORE_B128(v, rs_y, yo, 0, 0);   // (store + hazard guard: aot.h)
+        MD_BUFFER_STORE_B128(v, rs_y, yo, 0, 0);   // (store + hazard guard: device.h)
         if (a.pass) MD_BUFFER_STORE_B128(pval[it], rs_y, yo, C * 2, 0);
     }
 #ifdef MD_DIAG
@@ -377,8 +354,8 @@ __global__ __launch_bounds__(256, 4) void c3pair32_kernel(C3PairArgs a) {
     if (pt >= a.n_tiles) return;
     const int tx = pt % a.tiles_x, ty = (pt / a.tiles_x) % a.tiles_y, n = pt / (a.tiles_x * a.tiles_y);
     const int y0 = ty * CP_TH, x0 = tx * CP_TW;
-    __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void *)a.x, 0, a.x_bytes, 0x00020000);
-    __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc((void *)a.y, 0, a.y_bytes, 0x00020000);
+    __amdgpu_buffer_rsrc_t rs_x = srd(a.x, a.x_bytes);
+    __amdgpu_buffer_rsrc_t rs_y = srd(a.y, a.y_bytes);
 
     // x halo tile by LDS-DMA: one wave instruction = 16 rows x 64 B; 12 pieces, wave w stages pieces w, w + 4, w + 8
 #pragma unroll
@@ -396,16 +373,16 @@ __global__ __launch_bounds__(256, 4) void c3pair32_kernel(C3PairArgs a) {
     {
         if (tid < 128) {
             const int row = tid >> 2, ch = tid & 3;
-            const cp_u32x4 v = *reinterpret_cast<const cp_u32x4 *>(a.w1 + row * a.w1_ld + ch * 8);
-            *reinterpret_cast<cp_u32x4 *>(smem + C32_W1 + row * C32_W1ROW + ch * 16) = v;
+            const u32x4 v = *reinterpret_cast<const u32x4 *>(a.w1 + row * a.w1_ld + ch * 8);
+            *reinterpret_cast<u32x4 *>(smem + C32_W1 + row * C32_W1ROW + ch * 16) = v;
         }
 #pragma unroll
         for (int it = 0; it < 5; ++it) {
             const int e = tid + 256 * it;
             if (e < 32 * 36) {
                 const int row = e / 36, ch = e - row * 36;
-                const cp_u32x4 v = *reinterpret_cast<const cp_u32x4 *>(a.w2 + row * a.w2_ld + ch * 8);
-                *reinterpret_cast<cp_u32x4 *>(smem + C32_W2 + row * C32_W2ROW + ch * 16) = v;
+                const u32x4 v = *reinterpret_cast<const u32x4 *>(a.w2 + row * a.w2_ld + ch * 8);
+                *reinterpret_cast<u32x4 *>(smem + C32_W2 + row * C32_W2ROW + ch * 16) = v;
             }
         }
         if (tid < 64) reinterpret_cast<float *>(smem + C32_BIAS)[tid] = a.b12[tid];
@@ -416,19 +393,19 @@ __global__ __launch_bounds__(256, 4) void c3pair32_kernel(C3PairArgs a) {
     __syncthreads();
 
     // ---- phase A: T1 rows of fragments wave, wave + 4
-    cp_f32x16 acc1[2];
+    f32x16 acc1[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc1[j][e] = 0.f;
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
-        const cp_bf16x8 fa = *reinterpret_cast<const cp_bf16x8 *>(smem + C32_W1 + lr * C32_W1ROW + (2 * kk + lh) * 16);
+        const bf16x8 fa = *reinterpret_cast<const bf16x8 *>(smem + C32_W1 + lr * C32_W1ROW + (2 * kk + lh) * 16);
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int f = wave + 4 * j;
             if (f < 6) {
-                const cp_bf16x8 fb = *reinterpret_cast<const cp_bf16x8 *>(T + c32_swz(32 * f + lr, 2 * kk + lh));
+                const bf16x8 fb = *reinterpret_cast<const bf16x8 *>(T + c32_swz(32 * f + lr, 2 * kk + lh));
                 acc1[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fb, acc1[j], 0, 0, 0);
             }
         }
@@ -443,12 +420,12 @@ __global__ __launch_bounds__(256, 4) void c3pair32_kernel(C3PairArgs a) {
             const bool ok = r < CP_HALO && (unsigned)(y0 - 1 + hy) < (unsigned)a.H && (unsigned)(x0 - 1 + hx) < (unsigned)a.W;
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                const cp_f32x4 bv = *reinterpret_cast<const cp_f32x4 *>(bias12 + 8 * g + 4 * lh);
-                cp_u32x2 pk;
-                pk.x = cp_pk_bf16(cp_silu(acc1[j][4 * g + 0] + bv.x), cp_silu(acc1[j][4 * g + 1] + bv.y));
-                pk.y = cp_pk_bf16(cp_silu(acc1[j][4 * g + 2] + bv.z), cp_silu(acc1[j][4 * g + 3] + bv.w));
+                const f32x4 bv = *reinterpret_cast<const f32x4 *>(bias12 + 8 * g + 4 * lh);
+                u32x2 pk;
+                pk.x = pk_bf16(silu(acc1[j][4 * g + 0] + bv.x), silu(acc1[j][4 * g + 1] + bv.y));
+                pk.y = pk_bf16(silu(acc1[j][4 * g + 2] + bv.z), silu(acc1[j][4 * g + 3] + bv.w));
                 if (!ok) pk.x = pk.y = 0u;
-                *reinterpret_cast<cp_u32x2 *>(T + r * C32_TROW + ((g ^ ((r >> 2) & 3)) << 4) + 8 * lh) = pk;
+                *reinterpret_cast<u32x2 *>(T + r * C32_TROW + ((g ^ ((r >> 2) & 3)) << 4) + 8 * lh) = pk;
             }
         }
     }
@@ -458,18 +435,18 @@ __global__ __launch_bounds__(256, 4) void c3pair32_kernel(C3PairArgs a) {
         const int yy = y0 + (p >> 4), xx = x0 + (p & 15);
         return (yy < a.H && xx < a.W) ? (unsigned)((((n * a.H + yy) * a.W + xx) * cstride + c0 + cc * 8) * 2) : OOR;
     };
-    cp_u32x4 rres[2], pval[2];
+    u32x4 rres[2], pval[2];
 #pragma unroll
     for (int it = 0; it < 2; ++it) {
-        rres[it] = pval[it] = (cp_u32x4){0u, 0u, 0u, 0u};
+        rres[it] = pval[it] = (u32x4){0u, 0u, 0u, 0u};
         const unsigned xo = piece_off(it, a.XC, a.x_off);
-        if (a.shortcut) rres[it] = __builtin_bit_cast(cp_u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_x, (int)xo, 0, 0));
-        if (a.pass) pval[it] = __builtin_bit_cast(cp_u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_x, (int)xo, 64, 0));
+        if (a.shortcut) rres[it] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_x, (int)xo, 0, 0));
+        if (a.pass) pval[it] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_x, (int)xo, 64, 0));
     }
     __syncthreads();   // T1 complete
 
     // ---- phase B: pixel fragment = wave
-    cp_f32x16 acc2;
+    f32x16 acc2;
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc2[e] = 0.f;
     const int pB = 32 * wave + hp;
@@ -479,37 +456,29 @@ __global__ __launch_bounds__(256, 4) void c3pair32_kernel(C3PairArgs a) {
         const int r = r0 + (t / 3) * CP_HW + (t % 3);
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
-            const cp_bf16x8 fa = *reinterpret_cast<const cp_bf16x8 *>(smem + C32_W2 + lr * C32_W2ROW + t * 64 + (2 * kk + lh) * 16);
-            const cp_bf16x8 fb = *reinterpret_cast<const cp_bf16x8 *>(T + c32_swz(r, 2 * kk + lh));
+            const bf16x8 fa = *reinterpret_cast<const bf16x8 *>(smem + C32_W2 + lr * C32_W2ROW + t * 64 + (2 * kk + lh) * 16);
+            const bf16x8 fb = *reinterpret_cast<const bf16x8 *>(T + c32_swz(r, 2 * kk + lh));
             acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fb, acc2, 0, 0, 0);
         }
     }
-    cp_f32x4 bv2[4];
+    f32x4 bv2[4];
 #pragma unroll
-    for (int g = 0; g < 4; ++g) bv2[g] = *reinterpret_cast<const cp_f32x4 *>(bias12 + 32 + 8 * g + 4 * lh);
+    for (int g = 0; g < 4; ++g) bv2[g] = *reinterpret_cast<const f32x4 *>(bias12 + 32 + 8 * g + 4 * lh);
     __syncthreads();   // every wave is done with T1
     char *E = smem + C32_T;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-        cp_u32x2 pk;
-        pk.x = cp_pk_bf16(cp_silu(acc2[4 * g + 0] + bv2[g].x), cp_silu(acc2[4 * g + 1] + bv2[g].y));
-        pk.y = cp_pk_bf16(cp_silu(acc2[4 * g + 2] + bv2[g].z), cp_silu(acc2[4 * g + 3] + bv2[g].w));
-        *reinterpret_cast<cp_u32x2 *>(E + pB * C32_ES + (8 * g + 4 * lh) * 2) = pk;
+        u32x2 pk;
+        pk.x = pk_bf16(silu(acc2[4 * g + 0] + bv2[g].x), silu(acc2[4 * g + 1] + bv2[g].y));
+        pk.y = pk_bf16(silu(acc2[4 * g + 2] + bv2[g].z), silu(acc2[4 * g + 3] + bv2[g].w));
+        *reinterpret_cast<u32x2 *>(E + pB * C32_ES + (8 * g + 4 * lh) * 2) = pk;
     }
     __syncthreads();
 #pragma unroll
     for (int it = 0; it < 2; ++it) {
         const int e = tid + 256 * it, p = e >> 2, cc = e & 3;
-        cp_u32x4 v = *reinterpret_cast<const cp_u32x4 *>(E + p * C32_ES + cc * 16);
-        if (a.shortcut) {
-            const cp_u32x4 rv = rres[it];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const cp_f32x2 sum = (cp_f32x2){__uint_as_float(v[k] << 16), __uint_as_float(v[k] & 0xffff0000u)} +
-                                     (cp_f32x2){__uint_as_float(rv[k] << 16), __uint_as_float(rv[k] & 0xffff0000u)};
-                v[k] = cp_pk_bf16(sum.x, sum.y);
-            }
-        }
+        u32x4 v = *reinterpret_cast<const u32x4 *>(E + p * C32_ES + cc * 16);
+        if (a.shortcut) MD_ADD_BF16X8(v, rres[it], false);
         const unsigned yo = piece_off(it, a.YC, a.y_off);
         MD_BUFFER_STORE_B128(v, rs_y, yo, 0, 0);
         if (a.pass) MD_BUFFER_STORE_B128(pval[it], rs_y, yo, 64, 0);

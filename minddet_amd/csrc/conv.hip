@@ -28,12 +28,13 @@
 //   conv3x3_halo_kernel   3x3 / s1 layers with Cout <= 64: the 10 x 18 halo staged once per 64-channel chunk.
 // Common: v_mfma_f32_32x32x16_bf16; LDS tiles [row][64 k] bf16 (128-B rows) with the 16-B chunk index XOR-swizzled by
 // (row>>1)&7 (applied to the DMA's SOURCE chunk and to the ds_read_b128 fragment reads: conflict free); epilogue = bias
-// from LDS (requested at kernel start) -> packed adds -> v_cvt_pk_bf16_f32 -> packed ReLU -> LDS transpose -> +residual
+// from LDS (requested at kernel start) -> packed adds -> pk_bf16 -> packed ReLU -> LDS transpose -> +residual
 // -> non-temporal 16-B stores.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "aot.h"
+#include "device.h"
 
 namespace md {
 
@@ -46,12 +47,6 @@ constexpr bool kDiag = true;
 #else
 constexpr bool kDiag = false;
 #endif
-
-typedef __attribute__((ext_vector_type(8))) short bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 
 struct ConvArgs {
     const uint16_t *x;      // [N,H,W,Cin]
@@ -97,38 +92,8 @@ struct ConvArgs {
                             // slice of a wider [N,Ho,Wo,Rs] tensor, a.res pointing at its first channel)
 };
 
-__device__ __forceinline__ float bf2f(uint16_t v) { return __uint_as_float((unsigned)v << 16); }
-__device__ __forceinline__ uint16_t f2bf(float f) {
-    // round-to-nearest-even; NaN stays NaN (quiet)
-    unsigned u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-
-// two fp32 -> packed bf16 (round-to-nearest-even) in ONE instruction (gfx950 v_cvt_pk_bf16_f32).  r01 stamps: the software
-// rounding (9 VALU per value, 64 values per lane) made the epilogue VALU-bound at four workgroups per CU.
-__device__ __forceinline__ unsigned pk_bf16(float lo, float hi) {
-    unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-    return r;
-}
-
-__device__ __forceinline__ unsigned pk_relu_bf16(unsigned v) {  // max(x, 0) on a packed bf16 pair: as signed 16-bit integers
-    unsigned r;
-    asm("v_pk_max_i16 %0, %1, 0" : "=v"(r) : "v"(v));
-    return r;
-}
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// SiLU with the hardware reciprocal (v_rcp_f32, 1 ulp) instead of an IEEE division (v_div_scale / fmas / fixup: ~10 VALU per
-// value, 64 values per lane in an epilogue that is VALU-bound at four workgroups per CU); the result is rounded to bf16.
-__device__ __forceinline__ float silu(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
-
 constexpr int BK = 64;
 constexpr int ROWB = BK * 2;  // bytes per LDS tile row
-
-__device__ __forceinline__ int swz(int row, int chunk) { return row * ROWB + ((chunk ^ ((row >> 1) & 7)) << 4); }
 
 // id of the kernel the dispatcher chose for this host thread's last md_conv2d call (md_conv2d_last_kernel): lets a
 // profiler-less caller (bench.py) attribute per-launch timings to kernels
@@ -275,23 +240,23 @@ __global__ __launch_bounds__(NT, NT == 256 ? 3 : 2) void conv_igemm_kernel(ConvA
     auto store_tile = [&](int buf) {
         char *A = smem + buf * TILE_BYTES, *B = A + CT * ROWB;
 #pragma unroll
-        for (int i = 0; i < A_ROWS; ++i) *reinterpret_cast<u32x4 *>(A + swz(row0 + RPP * i, tid & 7)) = ra[GLDS ? 0 : i];
+        for (int i = 0; i < A_ROWS; ++i) *reinterpret_cast<u32x4 *>(A + swz128(row0 + RPP * i, tid & 7)) = ra[GLDS ? 0 : i];
 #pragma unroll
-        for (int i = 0; i < B_ROWS; ++i) *reinterpret_cast<u32x4 *>(B + swz(row0 + RPP * i, tid & 7)) = rb[GLDS ? 0 : i];
+        for (int i = 0; i < B_ROWS; ++i) *reinterpret_cast<u32x4 *>(B + swz128(row0 + RPP * i, tid & 7)) = rb[GLDS ? 0 : i];
     };
     // ---- staging, LDS-DMA path: one wave instruction fills 8 rows x 128 B = 1 KiB, destination lane-linear
     __amdgpu_buffer_rsrc_t rs_w, rs_x;
     int a_off0 = 0;
     if constexpr (GLDS) {
-        rs_w = __builtin_amdgcn_make_buffer_rsrc((void *)a.w, 0, a.w_bytes, 0x00020000);
-        rs_x = __builtin_amdgcn_make_buffer_rsrc((void *)a.x, 0, a.x_bytes, 0x00020000);
+        rs_w = srd(a.w, a.w_bytes);
+        rs_x = srd(a.x, a.x_bytes);
         a_off0 = ((cout0 + row0) * a.Kpad + chunk * 8) * 2;
     }
     const int wrow = wave * 8;  // first row of this wave's 8-row group inside a staging pass
     __amdgpu_buffer_rsrc_t rs_x2 = rs_x;
     unsigned p_base2[DUAL ? B_ROWS : 1];
     if constexpr (DUAL != 0) {
-        rs_x2 = __builtin_amdgcn_make_buffer_rsrc((void *)a.x2, 0, a.x2_bytes, 0x00020000);
+        rs_x2 = srd(a.x2, a.x2_bytes);
 #pragma unroll
         for (int i = 0; i < B_ROWS; ++i) {
             const int m = pix0 + row0 + RPP * i;
@@ -364,8 +329,8 @@ __global__ __launch_bounds__(NT, NT == 256 ? 3 : 2) void conv_igemm_kernel(ConvA
     int fa_off[BK / 16], fb_off[BK / 16];
 #pragma unroll
     for (int kk = 0; kk < BK / 16; ++kk) {
-        fa_off[kk] = swz(wc * FC * 32 + lr, kk * 2 + lh);
-        fb_off[kk] = CT * ROWB + swz(wp * FP * 32 + lr, kk * 2 + lh);
+        fa_off[kk] = swz128(wc * FC * 32 + lr, kk * 2 + lh);
+        fb_off[kk] = CT * ROWB + swz128(wp * FP * 32 + lr, kk * 2 + lh);
     }
     auto compute_tile32 = [&](int buf) {
         const char *T = smem + buf * TILE_BYTES;
@@ -506,16 +471,7 @@ __global__ __launch_bounds__(NT, NT == 256 ? 3 : 2) void conv_igemm_kernel(ConvA
         if (m >= a.M || c >= a.Cout) continue;
         u32x4 v = *reinterpret_cast<const u32x4 *>(E + p_local * EP_STRIDE + cc * 16);
         const size_t off = out_offset(m, c);
-        if (a.res) {
-            const u32x4 rv = rres[it];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const f32x2 sum = (f32x2){__uint_as_float(v[k] << 16), __uint_as_float(v[k] & 0xffff0000u)} +
-                                  (f32x2){__uint_as_float(rv[k] << 16), __uint_as_float(rv[k] & 0xffff0000u)};
-                v[k] = pk_bf16(sum.x, sum.y);
-                if (a.relu == 1) v[k] = pk_relu_bf16(v[k]);
-            }
-        }
+        if (a.res) MD_ADD_BF16X8(v, rres[it], a.relu == 1);
         __builtin_nontemporal_store(v, reinterpret_cast<u32x4 *>(a.y + off));
     }
     if (kDiag && a.stamp && a.dbg && blockIdx.x == gridDim.x / 2) {
@@ -621,17 +577,17 @@ __global__ __launch_bounds__(NW * 64, 2) void conv1x1_stream_kernel(ConvArgs a, 
     auto x_desc = [&](int t) {
         const long long b = (long long)(t0 + t) * PT * a.Xs * 2;
         const long long rem = t < nt ? (long long)a.x_bytes - b : 0;
-        return __builtin_amdgcn_make_buffer_rsrc((void *)((const char *)a.x + (t < nt ? b : 0)), 0, clip(rem), 0x00020000);
+        return srd((const char *)a.x + (t < nt ? b : 0), clip(rem));
     };
     auto r_desc = [&](int t) {
         const long long m0 = t < nt ? (long long)(t0 + t) * PT : 0;
         const long long rem = t < nt ? ((long long)a.M - m0) * r_stride * 2 - r_c0 * 2 : 0;
-        return __builtin_amdgcn_make_buffer_rsrc((void *)(a.res + m0 * r_stride + r_c0), 0, clip(rem), 0x00020000);
+        return srd(a.res + m0 * r_stride + r_c0, clip(rem));
     };
     auto y_desc = [&](int t) {
         const long long m0 = (long long)(t0 + t) * PT;
         const long long rem = ((long long)a.M - m0) * a.Ctot * 2 - y_c0 * 2;
-        return __builtin_amdgcn_make_buffer_rsrc((void *)(a.y + m0 * a.Ctot + y_c0), 0, clip(rem), 0x00020000);
+        return srd(a.y + m0 * a.Ctot + y_c0, clip(rem));
     };
     auto dma_x = [&](int t, int slot) {
         __amdgpu_buffer_rsrc_t rs = x_desc(t);
@@ -659,7 +615,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv1x1_stream_kernel(ConvArgs a, 
     }
     auto dma_res_up = [&](bool live) {   // requests the residual rows of the NEXT tile in sequence (tiles are consecutive)
         const long long tot = (long long)a.N * Hr * Wr * a.Cout * 2;
-        __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)a.res, 0, live ? clip(tot) : 0, 0x00020000);
+        __amdgpu_buffer_rsrc_t rs = srd(a.res, live ? clip(tot) : 0);
 #pragma unroll
         for (int i = 0; i < NE; ++i) {
             const int lc = (lane % CPP) ^ (((i * RPE + lane / CPP) >> ESH) & (CPP - 1));
@@ -746,10 +702,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv1x1_stream_kernel(ConvArgs a, 
                 u32x2 *cell = reinterpret_cast<u32x2 *>(E + lr * EROW + (((4 * b + g) ^ eswz) << 4) + 8 * lh);
                 if constexpr (RES != 0) {
                     const u32x2 rv = *cell;
-                    const f32x2 a01 = (f32x2){__uint_as_float(pk.x << 16), __uint_as_float(pk.x & 0xffff0000u)} +
-                                      (f32x2){__uint_as_float(rv.x << 16), __uint_as_float(rv.x & 0xffff0000u)};
-                    const f32x2 a23 = (f32x2){__uint_as_float(pk.y << 16), __uint_as_float(pk.y & 0xffff0000u)} +
-                                      (f32x2){__uint_as_float(rv.y << 16), __uint_as_float(rv.y & 0xffff0000u)};
+                    const f32x2 a01 = bf2f_pair(pk.x) + bf2f_pair(rv.x), a23 = bf2f_pair(pk.y) + bf2f_pair(rv.y);
                     pk.x = pk_bf16(a01.x, a01.y);
                     pk.y = pk_bf16(a23.x, a23.y);
                 }
@@ -814,8 +767,8 @@ __global__ __launch_bounds__(256, CT == 64 ? 4 : 2) void conv3x3_halo_kernel(Con
     const int y0 = ty * HT_H, x0 = tx * HT_W;
     const float bias_early = tid < CT ? a.bias[cout0 + tid] : 0.f;  // parked in LDS for the epilogue (see conv_igemm_kernel)
 
-    __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void *)a.w, 0, a.w_bytes, 0x00020000);
-    __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void *)a.x, 0, a.x_bytes, 0x00020000);
+    __amdgpu_buffer_rsrc_t rs_w = srd(a.w, a.w_bytes);
+    __amdgpu_buffer_rsrc_t rs_x = srd(a.x, a.x_bytes);
 
     // weight staging: thread -> rows row0 + 32 i, logical chunk `chunk` (as in conv_igemm_kernel)
     const int row0 = tid >> 3;
@@ -858,7 +811,7 @@ __global__ __launch_bounds__(256, CT == 64 ? 4 : 2) void conv3x3_halo_kernel(Con
     const int lr = lane & 31, lh = lane >> 5;
     int fa_off[BK / 16];
 #pragma unroll
-    for (int kk = 0; kk < BK / 16; ++kk) fa_off[kk] = swz(wc * 64 + lr, kk * 2 + lh);
+    for (int kk = 0; kk < BK / 16; ++kk) fa_off[kk] = swz128(wc * 64 + lr, kk * 2 + lh);
     // lane -> pixel of a 32-pixel fragment (= two 16-pixel tile rows, 18 halo rows apart): ds_read_b128 is served in the lane groups
     // {0-3, 12-15, 20-27} {4-11, 16-19, 28-31} (+32), 16 lanes x 16 B = all 64 banks per pass.  With pixel = lane a group straddles the two
     // tile rows and two of its halo rows coincide mod 16 (a 2-way conflict on every tap: SQ_LDS_BANK_CONFLICT 1.3 x the LDS-busy cycles,
@@ -965,16 +918,7 @@ __global__ __launch_bounds__(256, CT == 64 ? 4 : 2) void conv3x3_halo_kernel(Con
         if (off < 0) continue;
         off += a.c_off;
         u32x4 v = *reinterpret_cast<const u32x4 *>(E + p_local * EP_STRIDE + cc * 16);
-        if (a.res) {
-            const u32x4 rv = rres[it];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const f32x2 sum = (f32x2){__uint_as_float(v[k] << 16), __uint_as_float(v[k] & 0xffff0000u)} +
-                                  (f32x2){__uint_as_float(rv[k] << 16), __uint_as_float(rv[k] & 0xffff0000u)};
-                v[k] = pk_bf16(sum.x, sum.y);
-                if (a.relu == 1) v[k] = pk_relu_bf16(v[k]);
-            }
-        }
+        if (a.res) MD_ADD_BF16X8(v, rres[it], a.relu == 1);
         __builtin_nontemporal_store(v, reinterpret_cast<u32x4 *>(a.y + off));
     }
 }
@@ -1059,9 +1003,9 @@ __global__ __launch_bounds__(512, 2) void conv_pingpong_kernel(ConvArgs a) {
     const float bias_early = tid < CT ? a.bias[cout0 + tid] : 0.f;
     float *bias_lds = reinterpret_cast<float *>(smem + (HALO ? HB_BIAS : (PERS ? 8 * 128 * ROWB : PT * EP_STRIDE)));   // PERS: right behind the 128 KiB of staging buffers
 
-    __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void *)a.w, 0, a.w_bytes, 0x00020000);
-    __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void *)a.x, 0, a.x_bytes, 0x00020000);
-    __amdgpu_buffer_rsrc_t rs_x2 = __builtin_amdgcn_make_buffer_rsrc((void *)(a.x2 ? a.x2 : a.x), 0, a.x2 ? a.x2_bytes : 0u, 0x00020000);
+    __amdgpu_buffer_rsrc_t rs_w = srd(a.w, a.w_bytes);
+    __amdgpu_buffer_rsrc_t rs_x = srd(a.x, a.x_bytes);
+    __amdgpu_buffer_rsrc_t rs_x2 = srd(a.x2 ? a.x2 : a.x, a.x2 ? a.x2_bytes : 0u);
 
     // ---- staging map: one wave instruction = 8 rows x 128 B; a half tile = 2 instructions per wave (rows srow, srow+64)
     const int srow = wave * 8 + (lane >> 3);
@@ -1234,8 +1178,8 @@ __global__ __launch_bounds__(512, 2) void conv_pingpong_kernel(ConvArgs a) {
     int fa_off[4], fb_off[4];  // per k-step fragment offsets inside a half tile (MF 1 uses two: K 32 per step)
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
-        fa_off[kk] = MF ? swz(wr * 64 + l16, (kk & 1) * 4 + lq) : swz(wr * 64 + lr, kk * 2 + lh);
-        fb_off[kk] = MF ? swz(wc * 32 + l16, (kk & 1) * 4 + lq) : swz(wc * 32 + lr, kk * 2 + lh);
+        fa_off[kk] = MF ? swz128(wr * 64 + l16, (kk & 1) * 4 + lq) : swz128(wr * 64 + lr, kk * 2 + lh);
+        fb_off[kk] = MF ? swz128(wc * 32 + l16, (kk & 1) * 4 + lq) : swz128(wc * 32 + lr, kk * 2 + lh);
     }
     // HALO: the lane's k-chunk bits in address position
     const int hkq = MF ? (lq << 4) : (lh << 4);
@@ -1295,7 +1239,7 @@ __global__ __launch_bounds__(512, 2) void conv_pingpong_kernel(ConvArgs a) {
     // 16-B chunk), logical chunk = physical ^ row so that the 16 rows of an A-fragment read fall on 16 different slots
     constexpr int W2_OFF = HALO ? HB_W2 : PT * EP_STRIDE + CT * 4;
     if constexpr (HEAD) {
-        __amdgpu_buffer_rsrc_t rs_w2 = __builtin_amdgcn_make_buffer_rsrc((void *)a.w2, 0, 16 * 256 * 2, 0x00020000);
+        __amdgpu_buffer_rsrc_t rs_w2 = srd(a.w2, 16 * 256 * 2);
         const int i = wave * 64 + lane, row = i >> 5, phys = i & 31;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w2, (lds_void *)(smem + W2_OFF + wave * 1024), 16, row * 512 + ((phys ^ row) & 31) * 16, 0, 0, 0);
     }
@@ -1427,8 +1371,7 @@ __global__ __launch_bounds__(512, 2) void conv_pingpong_kernel(ConvArgs a) {
         // next tile's loop, behind that tile's opening barrier)
         char *slab = smem + (HALO ? HB0_OFF + HB_BYTES : 8 * 128 * ROWB + CT * 4) + wave * 2560;
         const long long rem = ((long long)a.M - pix_cur) * a.Ctot * 2 - (a.c_off + cout0) * 2;
-        __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc((void *)(a.y + (size_t)pix_cur * a.Ctot + a.c_off + cout0), 0,
-                                                                        (int)(rem > 0x7fffffffLL ? 0x7fffffffLL : rem), 0x00020000);
+        __amdgpu_buffer_rsrc_t rs_y = srd(a.y + (size_t)pix_cur * a.Ctot + a.c_off + cout0, (int)(rem > 0x7fffffffLL ? 0x7fffffffLL : rem));
         // a slab holds 16 pixels x 64 output channels (144-B rows): its read-out is 8 lanes per pixel = one whole 128-B line per pixel and
         // store instruction.  (32 x 32 slabs stored 64-B half lines: rocprofv3 FETCH_SIZE showed 15 % more HBM reads -- the L2 fills a
         // partially written line first.)
@@ -1619,16 +1562,7 @@ __global__ __launch_bounds__(512, 2) void conv_pingpong_kernel(ConvArgs a) {
         const int m = tile_pixel(p_local), c = cout0 + cc * 8;
         if (m >= a.M) continue;
         u32x4 v = *reinterpret_cast<const u32x4 *>(E + p_local * EP_STRIDE + cc * 16);
-        if (a.res) {
-            const u32x4 rv = rres[it];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const f32x2 sum = (f32x2){__uint_as_float(v[k] << 16), __uint_as_float(v[k] & 0xffff0000u)} +
-                                  (f32x2){__uint_as_float(rv[k] << 16), __uint_as_float(rv[k] & 0xffff0000u)};
-                v[k] = pk_bf16(sum.x, sum.y);
-                if (a.relu == 1) v[k] = pk_relu_bf16(v[k]);
-            }
-        }
+        if (a.res) MD_ADD_BF16X8(v, rres[it], a.relu == 1);
         if (ABL == 2 && v[0] != 0x12345u) continue;
         __builtin_nontemporal_store(v, reinterpret_cast<u32x4 *>(a.y + out_offset(m, c)));
     }

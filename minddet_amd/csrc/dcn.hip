@@ -13,18 +13,9 @@
 #include <stdint.h>
 
 #include "aot.h"
+#include "device.h"
 
 namespace md {
-
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float dbf2f(uint16_t v) { return __uint_as_float((unsigned)v << 16); }
-__device__ __forceinline__ unsigned dpk_bf16(float lo, float hi) {
-    unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-    return r;
-}
 
 struct DcnArgs {
     const uint16_t *x;    // [N,H,W,C]
@@ -45,8 +36,8 @@ __global__ __launch_bounds__(256) void deform_cols_kernel(DcnArgs a, size_t tota
         const int ho = (int)((pix / a.Wo) % a.Ho);
         const int n = (int)(pix / ((size_t)a.Wo * a.Ho));
         const uint16_t *o = a.off + pix * a.Coff;
-        const float dy = dbf2f(o[2 * k]), dx = dbf2f(o[2 * k + 1]);
-        const float m = 1.0f / (1.0f + __expf(-dbf2f(o[2 * T + k])));
+        const float dy = bf2f(o[2 * k]), dx = bf2f(o[2 * k + 1]);
+        const float m = 1.0f / (1.0f + __expf(-bf2f(o[2 * T + k])));
         const float y = (float)(ho * a.stride - a.pad + k / a.kw) + dy;
         const float x = (float)(wo * a.stride - a.pad + k % a.kw) + dx;
         float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -63,15 +54,16 @@ __global__ __launch_bounds__(256) void deform_cols_kernel(DcnArgs a, size_t tota
                     const u32x4 v = *reinterpret_cast<const u32x4 *>(base + ((size_t)yy * a.W + xx) * a.C);
 #pragma unroll
                     for (int d = 0; d < 4; ++d) {
-                        acc[2 * d] += w * __uint_as_float(v[d] << 16);
-                        acc[2 * d + 1] += w * __uint_as_float(v[d] & 0xffff0000u);
+                        const f32x2 pr = bf2f_pair(v[d]);
+                        acc[2 * d] += w * pr.x;
+                        acc[2 * d + 1] += w * pr.y;
                     }
                 }
             }
         }
         u32x4 outv;
 #pragma unroll
-        for (int d = 0; d < 4; ++d) outv[d] = dpk_bf16(acc[2 * d] * m, acc[2 * d + 1] * m);
+        for (int d = 0; d < 4; ++d) outv[d] = pk_bf16(acc[2 * d] * m, acc[2 * d + 1] * m);
         *reinterpret_cast<u32x4 *>(a.cols + (pix * T + k) * a.C + c8 * 8) = outv;
     }
 }

@@ -21,9 +21,11 @@
 #include <float.h>
 
 #include "aot.h"
-#include "box_codec.h"
+#include "device.h"
 
+// every product and sum below rounds on its own; set before box_codec.h, whose delta2bbox_one takes the including unit's mode
 #pragma clang fp contract(off)
+#include "box_codec.h"
 
 namespace md {
 
@@ -168,26 +170,16 @@ __global__ void second_box_decode_kernel(const float *__restrict__ enc, const fl
     }
 }
 
-struct DeltaArgs { float mean[4], stdv[4]; float max_ratio; float clip_w, clip_h; int do_clip; };
+struct DeltaArgs { DecodeP c; int do_clip; };
 // rois[n,4], deltas[n,4] (optionally gathered: idx[n] selects rows of rois_src/deltas_src)
 __global__ void delta2bbox_kernel(const float *__restrict__ rois, const float *__restrict__ deltas, size_t n,
                                   DeltaArgs a, float *__restrict__ out) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const float4 r = *reinterpret_cast<const float4 *>(rois + i * 4);
-        const float4 d0 = *reinterpret_cast<const float4 *>(deltas + i * 4);
-        const float dx = d0.x * a.stdv[0] + a.mean[0], dy = d0.y * a.stdv[1] + a.mean[1];
-        float dw = d0.z * a.stdv[2] + a.mean[2], dh = d0.w * a.stdv[3] + a.mean[3];
-        dw = fminf(fmaxf(dw, -a.max_ratio), a.max_ratio);
-        dh = fminf(fmaxf(dh, -a.max_ratio), a.max_ratio);
-        const float px = (r.x + r.z) * 0.5f, py = (r.y + r.w) * 0.5f, pw = r.z - r.x, ph = r.w - r.y;
-        const float gw = pw * expf(dw), gh = ph * expf(dh);
-        const float gx = px + pw * dx, gy = py + ph * dy;
-        float x1 = gx - gw * 0.5f, y1 = gy - gh * 0.5f, x2 = gx + gw * 0.5f, y2 = gy + gh * 0.5f;
-        if (a.do_clip) {
-            x1 = fminf(fmaxf(x1, 0.f), a.clip_w); x2 = fminf(fmaxf(x2, 0.f), a.clip_w);
-            y1 = fminf(fmaxf(y1, 0.f), a.clip_h); y2 = fminf(fmaxf(y2, 0.f), a.clip_h);
-        }
-        *reinterpret_cast<float4 *>(out + i * 4) = make_float4(x1, y1, x2, y2);
+        const float4 d = *reinterpret_cast<const float4 *>(deltas + i * 4);
+        float4 o = delta2bbox_one(r, d.x, d.y, d.z, d.w, a.c);
+        if (a.do_clip) o = clip_box(o, a.c.clip_w, a.c.clip_h);
+        *reinterpret_cast<float4 *>(out + i * 4) = o;
     }
 }
 
@@ -756,21 +748,7 @@ __device__ __forceinline__ int roi_fpn_level(const RoiArgs &a, const float *roi)
     for (int j = 0; j < 5; ++j) lvl += (j < a.L - 1 && area >= a.lvl_thr[j]) ? 1 : 0;
     return lvl;
 }
-__device__ __forceinline__ float rbf2f(unsigned v16) { return __uint_as_float(v16 << 16); }
-__device__ __forceinline__ unsigned rf2bf(float f) {
-    unsigned u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40;
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return u >> 16;
-}
 // rois [R,5] = (batch_idx, x1,y1,x2,y2) f32 ; out [R,P,P,C] bf16 ; one thread = 8 channels of one bin
-// two fp32 -> packed bf16, round-to-nearest-even, one instruction (gfx950)
-__device__ __forceinline__ unsigned rpk_bf16(float lo, float hi) {
-    unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-    return r;
-}
-
 __global__ void roi_align_kernel(RoiArgs a, const float *__restrict__ rois, int R, uint16_t *__restrict__ out,
                                  int *__restrict__ out_level) {
     const int cv = a.C / 8;
@@ -814,19 +792,19 @@ __global__ void roi_align_kernel(RoiArgs a, const float *__restrict__ rois, int 
                 const unsigned q3[4] = {v3.x, v3.y, v3.z, v3.w}, q4[4] = {v4.x, v4.y, v4.z, v4.w};
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    acc[2 * q] += w1 * rbf2f(q1[q] & 0xffffu) + w2 * rbf2f(q2[q] & 0xffffu) + w3 * rbf2f(q3[q] & 0xffffu) +
-                                  w4 * rbf2f(q4[q] & 0xffffu);
-                    acc[2 * q + 1] += w1 * rbf2f(q1[q] >> 16) + w2 * rbf2f(q2[q] >> 16) + w3 * rbf2f(q3[q] >> 16) +
-                                      w4 * rbf2f(q4[q] >> 16);
+                    acc[2 * q] += w1 * bf2f(q1[q] & 0xffffu) + w2 * bf2f(q2[q] & 0xffffu) + w3 * bf2f(q3[q] & 0xffffu) +
+                                  w4 * bf2f(q4[q] & 0xffffu);
+                    acc[2 * q + 1] += w1 * bf2f(q1[q] >> 16) + w2 * bf2f(q2[q] >> 16) + w3 * bf2f(q3[q] >> 16) +
+                                      w4 * bf2f(q4[q] >> 16);
                 }
             }
         }
         const float inv = 1.f / (float)(g * g);
         uint4 o;
-        o.x = rpk_bf16(acc[0] * inv, acc[1] * inv);
-        o.y = rpk_bf16(acc[2] * inv, acc[3] * inv);
-        o.z = rpk_bf16(acc[4] * inv, acc[5] * inv);
-        o.w = rpk_bf16(acc[6] * inv, acc[7] * inv);
+        o.x = pk_bf16(acc[0] * inv, acc[1] * inv);
+        o.y = pk_bf16(acc[2] * inv, acc[3] * inv);
+        o.z = pk_bf16(acc[4] * inv, acc[5] * inv);
+        o.w = pk_bf16(acc[6] * inv, acc[7] * inv);
         *reinterpret_cast<uint4 *>(out + e * 8) = o;
     }
 }
@@ -834,8 +812,6 @@ __global__ void roi_align_kernel(RoiArgs a, const float *__restrict__ rois, int 
 // 32 channels per thread (C % 32 == 0): the RoI / bin / tap arithmetic is paid once per 64 B instead of once per 16 B, and
 // the accumulation runs on channel PAIRS (v_pk_fma_f32).  Same sampling arithmetic as roi_align_kernel; the 16 tap terms of
 // a bin are fused-multiply-added one by one (different fp32 rounding than the 4-term sums there, same bf16 tolerance).  r01: the 16-B kernel was VALU-bound.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(256) void roi_align_c32_kernel(RoiArgs a, const float *__restrict__ rois, int R, uint16_t *__restrict__ out,
                                                             int *__restrict__ out_level) {
     const int cv = a.C / 32;
@@ -914,7 +890,7 @@ __global__ __launch_bounds__(256) void roi_align_c32_kernel(RoiArgs a, const flo
                         const unsigned wd[4] = {v[q].x, v[q].y, v[q].z, v[q].w};
 #pragma unroll
                         for (int d = 0; d < 4; ++d) {
-                            const f32x2 pr = (f32x2){__uint_as_float(wd[d] << 16), __uint_as_float(wd[d] & 0xffff0000u)};
+                            const f32x2 pr = bf2f_pair(wd[d]);
                             acc[q * 4 + d] = __builtin_elementwise_fma(w2, pr, acc[q * 4 + d]);
                         }
                     }
@@ -945,7 +921,7 @@ __global__ __launch_bounds__(256) void roi_align_c32_kernel(RoiArgs a, const flo
                         const unsigned wd[4] = {v[q].x, v[q].y, v[q].z, v[q].w};
 #pragma unroll
                         for (int d = 0; d < 4; ++d) {
-                            const f32x2 pr = (f32x2){__uint_as_float(wd[d] << 16), __uint_as_float(wd[d] & 0xffff0000u)};
+                            const f32x2 pr = bf2f_pair(wd[d]);
                             acc[q * 4 + d] = __builtin_elementwise_fma(w2, pr, acc[q * 4 + d]);
                         }
                     }
@@ -957,12 +933,12 @@ __global__ __launch_bounds__(256) void roi_align_c32_kernel(RoiArgs a, const flo
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             uint4 o;
-            o.x = rpk_bf16(acc[q * 4 + 0].x * inv, acc[q * 4 + 0].y * inv);
-            o.y = rpk_bf16(acc[q * 4 + 1].x * inv, acc[q * 4 + 1].y * inv);
-            o.z = rpk_bf16(acc[q * 4 + 2].x * inv, acc[q * 4 + 2].y * inv);
-            o.w = rpk_bf16(acc[q * 4 + 3].x * inv, acc[q * 4 + 3].y * inv);
+            o.x = pk_bf16(acc[q * 4 + 0].x * inv, acc[q * 4 + 0].y * inv);
+            o.y = pk_bf16(acc[q * 4 + 1].x * inv, acc[q * 4 + 1].y * inv);
+            o.z = pk_bf16(acc[q * 4 + 2].x * inv, acc[q * 4 + 2].y * inv);
+            o.w = pk_bf16(acc[q * 4 + 3].x * inv, acc[q * 4 + 3].y * inv);
             // non-temporal: the 3 GB pooled tensor is not read again by this kernel and should not push feature-map lines out of L2
-            __builtin_nontemporal_store((u32x4_t){o.x, o.y, o.z, o.w}, reinterpret_cast<u32x4_t *>(dst + q * cv));
+            __builtin_nontemporal_store((u32x4){o.x, o.y, o.z, o.w}, reinterpret_cast<u32x4 *>(dst + q * cv));
         }
     }
 }
@@ -1016,7 +992,7 @@ __global__ __launch_bounds__(256) void heat_peaks_kernel(const uint16_t *__restr
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 const float xin = __uint_as_float(k & 1 ? (w[k >> 1] & 0xffff0000u) : (w[k >> 1] << 16));
-                const float sg = 1.0f / (1.0f + expf(-xin));
+                const float sg = sigmoid(xin);
                 v[k] = fminf(fmaxf(sg, a.lo), a.hi);
             }
         }
@@ -1088,15 +1064,15 @@ __global__ void centerpoint_decode_kernel(const uint16_t *__restrict__ head, CpA
     float best = -FLT_MAX;
     int lab = 0;
     for (int c = 0; c < a.ncls; ++c) {  // ArgMaxWithValue: first maximum wins
-        const float v = 1.0f / (1.0f + expf(-rbf2f(h[a.o_hm + c])));
+        const float v = sigmoid(bf2f(h[a.o_hm + c]));
         if (v > best) { best = v; lab = c; }
     }
-    const float xs = ((float)x + rbf2f(h[a.o_reg])) * a.osf * a.vx + a.px;
-    const float ys = ((float)y + rbf2f(h[a.o_reg + 1])) * a.osf * a.vy + a.py;
-    const float zs = rbf2f(h[a.o_height]);
-    const float d0 = expf(rbf2f(h[a.o_dim])), d1 = expf(rbf2f(h[a.o_dim + 1])), d2 = expf(rbf2f(h[a.o_dim + 2]));
-    const float rot = atan2f(rbf2f(h[a.o_rot]), rbf2f(h[a.o_rot + 1]));
-    const float v0 = a.o_vel >= 0 ? rbf2f(h[a.o_vel]) : 0.f, v1 = a.o_vel >= 0 ? rbf2f(h[a.o_vel + 1]) : 0.f;
+    const float xs = ((float)x + bf2f(h[a.o_reg])) * a.osf * a.vx + a.px;
+    const float ys = ((float)y + bf2f(h[a.o_reg + 1])) * a.osf * a.vy + a.py;
+    const float zs = bf2f(h[a.o_height]);
+    const float d0 = expf(bf2f(h[a.o_dim])), d1 = expf(bf2f(h[a.o_dim + 1])), d2 = expf(bf2f(h[a.o_dim + 2]));
+    const float rot = atan2f(bf2f(h[a.o_rot]), bf2f(h[a.o_rot + 1]));
+    const float v0 = a.o_vel >= 0 ? bf2f(h[a.o_vel]) : 0.f, v1 = a.o_vel >= 0 ? bf2f(h[a.o_vel + 1]) : 0.f;
     const bool in_range = xs >= a.rmin[0] && ys >= a.rmin[1] && zs >= a.rmin[2] && xs <= a.rmax[0] && ys <= a.rmax[1] && zs <= a.rmax[2];
     const bool ok = best > a.score_thr && in_range;
     float *b = boxes + (size_t)e * 9;
@@ -1151,17 +1127,16 @@ __global__ __launch_bounds__(256) void yolo_decode_kernel(const uint16_t *__rest
     const int b = (int)(cell / (a.H * a.W)), loc = (int)(cell - (long long)b * a.H * a.W);
     const int gx = loc % a.W, gy = loc / a.W;
     const uint16_t *h = reinterpret_cast<const uint16_t *>(ysm + c * (a.Cp / 2 + 1)) + an * (5 + a.nc);
-    auto sg = [](float v) { return 1.0f / (1.0f + expf(-v)); };
-    const float sx = sg(rbf2f(h[0])), sy = sg(rbf2f(h[1])), sw = sg(rbf2f(h[2])), sh = sg(rbf2f(h[3])), obj = sg(rbf2f(h[4]));
+    const float sx = sigmoid(bf2f(h[0])), sy = sigmoid(bf2f(h[1])), sw = sigmoid(bf2f(h[2])), sh = sigmoid(bf2f(h[3])), obj = sigmoid(bf2f(h[4]));
     const float cx = (sx * 2.f - 0.5f + (float)gx) * a.stride, cy = (sy * 2.f - 0.5f + (float)gy) * a.stride;
     const float w = (sw * 2.f) * (sw * 2.f) * a.aw[an], hh = (sh * 2.f) * (sh * 2.f) * a.ah[an];
     float best = -FLT_MAX;
     int lab = 0;
     for (int k = 0; k < a.nc; ++k) {
-        const float v = rbf2f(h[5 + k]);
+        const float v = bf2f(h[5 + k]);
         if (v > best) { best = v; lab = k; }
     }
-    const float conf = obj * sg(best);
+    const float conf = obj * sigmoid(best);
     const size_t o = (size_t)b * a.total + a.off + (size_t)loc * a.A + an;
     *reinterpret_cast<float4 *>(boxes + o * 4) = make_float4(cx - w / 2, cy - hh / 2, cx + w / 2, cy + hh / 2);
     scores[o] = (obj > a.thr && conf > a.thr) ? conf : -FLT_MAX;
@@ -1189,10 +1164,10 @@ __global__ __launch_bounds__(256) void yolov8_decode_kernel(const uint16_t *__re
 #pragma unroll
     for (int sd = 0; sd < 4; ++sd) {
         float mx = -FLT_MAX;
-        for (int i = 0; i < a.R; ++i) mx = fmaxf(mx, rbf2f(h[sd * a.R + i]));
+        for (int i = 0; i < a.R; ++i) mx = fmaxf(mx, bf2f(h[sd * a.R + i]));
         float den = 0.f, num = 0.f;
         for (int i = 0; i < a.R; ++i) {
-            const float p = expf(rbf2f(h[sd * a.R + i]) - mx);
+            const float p = expf(bf2f(h[sd * a.R + i]) - mx);
             den += p;
             num += p * (float)i;
         }
@@ -1202,10 +1177,10 @@ __global__ __launch_bounds__(256) void yolov8_decode_kernel(const uint16_t *__re
     float best = -FLT_MAX;
     int lab = 0;
     for (int c = 0; c < a.nc; ++c) {
-        const float v = rbf2f(h[4 * a.R + c]);
+        const float v = bf2f(h[4 * a.R + c]);
         if (v > best) { best = v; lab = c; }
     }
-    const float conf = 1.0f / (1.0f + expf(-best));  // sigmoid is monotonic: arg-max on the logits
+    const float conf = sigmoid(best);  // sigmoid is monotonic: arg-max on the logits
     const size_t o = (size_t)b * a.total + a.off + loc;
     *reinterpret_cast<float4 *>(boxes + o * 4) =
         make_float4((ax - d[0]) * a.stride, (ay - d[1]) * a.stride, (ax + d[2]) * a.stride, (ay + d[3]) * a.stride);
@@ -1235,7 +1210,7 @@ __global__ void gather_rows_kernel(const float *__restrict__ src, const int *__r
 
 __global__ void sigmoid_clip_kernel(const float *__restrict__ x, float *__restrict__ y, size_t n, float lo, float hi) {
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
-        const float s = 1.0f / (1.0f + expf(-x[e]));
+        const float s = sigmoid(x[e]);
         y[e] = fminf(fmaxf(s, lo), hi);
     }
 }
@@ -1398,8 +1373,8 @@ extern "C" int md_delta2bbox(MD_AOT_ARGS) {
     g.require(tot >= 0 && tot % 4 == 0 && g.numel(1) == tot && g.numel(2) == tot);
     if (int rc = g.rc()) return rc;
     DeltaArgs a;
-    for (int i = 0; i < 4; ++i) { a.mean[i] = at->means[i]; a.stdv[i] = at->stds[i]; }
-    a.max_ratio = at->max_ratio; a.clip_w = at->clip_w; a.clip_h = at->clip_h; a.do_clip = at->clip_w > 0 && at->clip_h > 0;
+    for (int i = 0; i < 4; ++i) { a.c.mean[i] = at->means[i]; a.c.stdv[i] = at->stds[i]; }
+    a.c.max_ratio = at->max_ratio; a.c.clip_w = at->clip_w; a.c.clip_h = at->clip_h; a.do_clip = at->clip_w > 0 && at->clip_h > 0;
     if (tot == 0) return MD_OK;
     if (!g.have({0, 1, 2})) return MD_ERR_ARG;
     hipLaunchKernelGGL(delta2bbox_kernel, dim3(grid1d((size_t)tot / 4)), dim3(256), 0, (hipStream_t)stream,

@@ -25,12 +25,9 @@
 #include <stdint.h>
 
 #include "aot.h"
+#include "device.h"
 
 namespace md {
-
-typedef __attribute__((ext_vector_type(8))) short gc_bf16x8;
-typedef __attribute__((ext_vector_type(4))) float gc_f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int gc_u32x4;
 
 constexpr int GC_TH = 8, GC_TW = 32, GC_THREADS = 256;
 
@@ -44,12 +41,6 @@ struct GroupedArgs {
     int tiles_x, tiles_y, n_work, work_per_xcd;
     int cout[MD_GROUPED_MAX_GROUPS], y_off[MD_GROUPED_MAX_GROUPS], w_row[MD_GROUPED_MAX_GROUPS];
 };
-
-__device__ __forceinline__ uint16_t gc_f32_to_bf16(float f) {   // round to nearest even (finite inputs), as md_conv2d's epilogue
-    uint32_t u = __float_as_uint(f);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
 
 template <int KS>
 __global__ __launch_bounds__(GC_THREADS, 3) void grouped_conv_kernel(GroupedArgs a) {
@@ -73,27 +64,27 @@ __global__ __launch_bounds__(GC_THREADS, 3) void grouped_conv_kernel(GroupedArgs
     // ---- halo tile -> LDS (all loads issued before the first LDS write)
     const size_t img = (size_t)n * a.H * a.W;
     const int c0 = a.x_c_off + g * 64;
-    gc_u32x4 v[LOADS];
+    u32x4 v[LOADS];
 #pragma unroll
     for (int i = 0; i < LOADS; ++i) {
         const int p = tid + i * GC_THREADS;
         const int q = p >> 3, c = p & 7;
         const int yy = y0 - HALO + q / LW, xx = x0 - HALO + q % LW;
-        v[i] = gc_u32x4{0u, 0u, 0u, 0u};
+        v[i] = u32x4{0u, 0u, 0u, 0u};
         if (p < PIECES && yy >= 0 && yy < a.H && xx >= 0 && xx < a.W)
-            v[i] = *(const gc_u32x4 *)(a.x + (img + (size_t)yy * a.W + xx) * a.C + c0 + c * 8);
+            v[i] = *(const u32x4 *)(a.x + (img + (size_t)yy * a.W + xx) * a.C + c0 + c * 8);
     }
     // ---- the group's weights -> registers: lane l holds A[row l & 15][k = 32 s + 8 (l >> 4) .. +7], zero for rows >= cout
     constexpr int KW = KS * KS * 64;
     const int row = lane & 15, kq = lane >> 4;
-    gc_bf16x8 wf[KSTEPS];
+    bf16x8 wf[KSTEPS];
     {
         const bool live = row < cout;
         const uint16_t *wr = a.w + (size_t)(a.w_row[g] + (live ? row : 0)) * KW + kq * 8;
 #pragma unroll
         for (int s = 0; s < KSTEPS; ++s) {
-            gc_bf16x8 t = *(const gc_bf16x8 *)(wr + s * 32);
-            wf[s] = live ? t : gc_bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+            bf16x8 t = *(const bf16x8 *)(wr + s * 32);
+            wf[s] = live ? t : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
         }
     }
 #pragma unroll
@@ -101,15 +92,15 @@ __global__ __launch_bounds__(GC_THREADS, 3) void grouped_conv_kernel(GroupedArgs
         const int p = tid + i * GC_THREADS;
         if (p < PIECES) {
             const int q = p >> 3, c = p & 7;
-            *(gc_u32x4 *)(gc_lds + q * 128 + ((c ^ (q & 7)) << 4)) = v[i];
+            *(u32x4 *)(gc_lds + q * 128 + ((c ^ (q & 7)) << 4)) = v[i];
         }
     }
     __syncthreads();
 
     // ---- MFMA: wave w computes output rows 2w, 2w + 1, column blocks 0-15 and 16-31 of each
-    gc_f32x4 acc[4];
+    f32x4 acc[4];
 #pragma unroll
-    for (int b = 0; b < 4; ++b) acc[b] = gc_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int b = 0; b < 4; ++b) acc[b] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int s = 0; s < KSTEPS; ++s) {
         const int tap = s >> 1, ky = tap / KS, kx = tap % KS;
@@ -118,7 +109,7 @@ __global__ __launch_bounds__(GC_THREADS, 3) void grouped_conv_kernel(GroupedArgs
         for (int b = 0; b < 4; ++b) {
             const int r = wave * 2 + (b >> 1), col = (b & 1) * 16 + row;
             const int q = (r + ky) * LW + col + kx;
-            const gc_bf16x8 bf = *(const gc_bf16x8 *)(gc_lds + q * 128 + ((piece ^ (q & 7)) << 4));
+            const bf16x8 bf = *(const bf16x8 *)(gc_lds + q * 128 + ((piece ^ (q & 7)) << 4));
             acc[b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[s], bf, acc[b], 0, 0, 0);
         }
     }
@@ -141,7 +132,7 @@ __global__ __launch_bounds__(GC_THREADS, 3) void grouped_conv_kernel(GroupedArgs
                 const int c = kq * 4 + j;
                 float f = acc[b][j] + bs[j];
                 if (a.relu) f = fmaxf(f, 0.f);
-                if (c < cout) yp[c] = gc_f32_to_bf16(f);
+                if (c < cout) yp[c] = f2bf_finite(f);
             }
         }
     }

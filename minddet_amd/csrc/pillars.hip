@@ -26,6 +26,7 @@
 
 #include "../../include/minddet_hip_points.h"
 #include "aot.h"
+#include "device.h"
 
 namespace md {
 
@@ -240,12 +241,6 @@ struct EncArgs {
     float vx, vy, x_off, y_off;
 };
 
-__device__ __forceinline__ uint16_t pe_f32_to_bf16(float f) {   // round to nearest even (the inputs are finite and >= 0)
-    uint32_t u = __float_as_uint(f);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-
 template <int F, bool TWO>
 __global__ __launch_bounds__(PE_WAVES * 64, 2) void pillar_encode_kernel(EncArgs a) {
     constexpr int K = F + 5;
@@ -327,7 +322,7 @@ __global__ __launch_bounds__(PE_WAVES * 64, 2) void pillar_encode_kernel(EncArgs
         if (TWO) best = fmaxf(best, __shfl_xor(best, 32, 64));
         if (n < a.MP) best = fmaxf(best, pad1);             // the padded rows take part in the maximum
         if (!TWO) {
-            *dst = pe_f32_to_bf16(best);
+            *dst = f2bf_finite(best);
             continue;
         }
         if (lane < 32) x1[(PE_MAX_POINTS + 1) * 32 + lane] = best;
@@ -361,7 +356,7 @@ __global__ __launch_bounds__(PE_WAVES * 64, 2) void pillar_encode_kernel(EncArgs
             }
             best2 = fmaxf(best2, fmaxf(__fadd_rn(__fadd_rn(acc, tail), sh2), 0.f));
         }
-        *dst = pe_f32_to_bf16(best2);
+        *dst = f2bf_finite(best2);
     }
 }
 

@@ -10,23 +10,15 @@
 #include <stdint.h>
 
 #include "aot.h"
+#include "device.h"
 
 namespace md {
 
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-
-__device__ __forceinline__ float pbf2f(unsigned v16) { return __uint_as_float(v16 << 16); }
-__device__ __forceinline__ unsigned pf2bf(float f) {
-    unsigned u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40;
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return u >> 16;
-}
 // max of two packed bf16 pairs (compared as floats; of equal values -- -0 and +0 among them -- the first, a, is kept; when either is
 // NaN, b is taken: minddet_hip.h leaves both cases unspecified)
 __device__ __forceinline__ unsigned max_bf16x2(unsigned a, unsigned b) {
-    const float alo = pbf2f(a & 0xffffu), blo = pbf2f(b & 0xffffu);
-    const float ahi = pbf2f(a >> 16), bhi = pbf2f(b >> 16);
+    const float alo = bf2f(a & 0xffffu), blo = bf2f(b & 0xffffu);
+    const float ahi = bf2f(a >> 16), bhi = bf2f(b >> 16);
     const unsigned lo = alo >= blo ? (a & 0xffffu) : (b & 0xffffu);
     const unsigned hi = ahi >= bhi ? (a >> 16) : (b >> 16);
     return lo | (hi << 16);
@@ -87,9 +79,9 @@ __global__ void upsample_add_kernel(const uint16_t *__restrict__ lat, const uint
         u32x4 o;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const float lo = pbf2f(a[q] & 0xffffu) + pbf2f(b[q] & 0xffffu);
-            const float hi = pbf2f(a[q] >> 16) + pbf2f(b[q] >> 16);
-            asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(o[q]) : "v"(lo), "v"(hi));  // RNE pack, one instruction
+            const float lo = bf2f(a[q] & 0xffffu) + bf2f(b[q] & 0xffffu);
+            const float hi = bf2f(a[q] >> 16) + bf2f(b[q] >> 16);
+            o[q] = pk_bf16(lo, hi);
         }
         *reinterpret_cast<u32x4 *>(y + e * 8) = o;
     }
@@ -102,7 +94,7 @@ __global__ void slice_cast_kernel(const uint16_t *__restrict__ in, float *__rest
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
         const size_t m = e / cw;
         const int j = (int)(e % cw);
-        out[e] = pbf2f(in[m * C + c0 + j]);
+        out[e] = bf2f(in[m * C + c0 + j]);
     }
 }
 
@@ -115,7 +107,7 @@ __global__ __launch_bounds__(256) void nhwc_to_nchw_f32_kernel(const uint16_t *_
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
     for (int r = ty; r < 64; r += 4) {   // r: pixel within tile, tx: channel
         const int p = p0 + r, j = j0 + tx;
-        tile[r][tx] = (p < HW && j < cw) ? pbf2f(in[((size_t)n * HW + p) * C + c0 + j]) : 0.f;
+        tile[r][tx] = (p < HW && j < cw) ? bf2f(in[((size_t)n * HW + p) * C + c0 + j]) : 0.f;
     }
     __syncthreads();
     for (int r = ty; r < 64; r += 4) {   // r: channel within tile, tx: pixel
@@ -150,13 +142,12 @@ __global__ void slice_write_kernel(const uint16_t *__restrict__ src, uint16_t *_
 // holds one image x CC 16-B channel groups in LDS: x, then the three row maxima, then the column maxima of those go out.  bf16 values are
 // mapped to order-preserving 16-bit keys (negative: all bits flipped, else the sign bit set) so that a max is one v_pk_max_u16 per pair.
 // Replaces three md_maxpool2d launches (25 global loads per output each) and four concat copies: 103 -> 22 us on YOLOv5s' 32 x 20 x 20 x 256.
-typedef unsigned short sp_u16x8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ unsigned sp_key(unsigned v) { return v ^ ((((v >> 15) & 0x00010001u) * 0x7fffu) | 0x80008000u); }
 __device__ __forceinline__ unsigned sp_unkey(unsigned k) { return k ^ ((((~k >> 15) & 0x00010001u) * 0x7fffu) | 0x80008000u); }
 // (whole-vector form: an element-by-element loop over u32x4 with a 2 x u16 bit cast per element was compiled into ONE v_pk_max_u16 whose
 // result was broadcast to all four dwords -- hipcc 7.2, found by the bit-compare test)
 __device__ __forceinline__ u32x4 sp_max(u32x4 a, u32x4 b) {
-    return __builtin_bit_cast(u32x4, __builtin_elementwise_max(__builtin_bit_cast(sp_u16x8, a), __builtin_bit_cast(sp_u16x8, b)));
+    return __builtin_bit_cast(u32x4, __builtin_elementwise_max(__builtin_bit_cast(u16x8, a), __builtin_bit_cast(u16x8, b)));
 }
 
 __global__ __launch_bounds__(256) void sppf_pool_kernel(uint16_t *__restrict__ buf, int H, int W, int C, int Ctot, int R, int CC) {

@@ -9,15 +9,13 @@
 #include <stdint.h>
 
 #include "aot.h"
+#include "device.h"
 #include "box_codec.h"
 #include "../../include/minddet_hip_pp.h"
 
 #pragma clang fp contract(off)
 
 namespace md {
-
-__device__ __forceinline__ float pp_bf16(uint32_t bits) { return __uint_as_float(bits << 16); }
-__device__ __forceinline__ float pp_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 struct PPScoreArgs {
     const uint16_t *head;
@@ -31,7 +29,7 @@ struct PPScoreArgs {
 // running (maximum, first index that attains it) over the classes in order
 #define PP_TAKE(BITS, KI)                              \
     do {                                               \
-        const float s__ = pp_sigmoid(pp_bf16(BITS));   \
+        const float s__ = sigmoid(bf2f(BITS));         \
         if ((KI) == 0 || s__ > best) { best = s__; lab = (KI); } \
     } while (0)
 
@@ -84,12 +82,12 @@ __global__ __launch_bounds__(256) void pp_decode_selected_kernel(PPDecodeArgs g)
         const uint16_t *p = g.head + ((size_t)b * (size_t)(g.N / g.A) + (size_t)cell) * (size_t)g.C;
         float t[7];
 #pragma unroll
-        for (int q = 0; q < 7; ++q) t[q] = pp_bf16(p[g.off_box + a * 7 + q]);
+        for (int q = 0; q < 7; ++q) t[q] = bf2f(p[g.off_box + a * 7 + q]);
         second_box_decode_one(t, g.anchors + (size_t)n * 7, raw);
         st = standup_one(raw[0], raw[1], raw[3], raw[4], raw[6]);
         float rot = raw[6];
         if (g.off_dir >= 0) {
-            const float d0 = pp_bf16(p[g.off_dir + a * 2]), d1 = pp_bf16(p[g.off_dir + a * 2 + 1]);
+            const float d0 = bf2f(p[g.off_dir + a * 2]), d1 = bf2f(p[g.off_dir + a * 2 + 1]);
             dir = d1 > d0 ? 1 : 0;
             if ((rot > 0.f) != (dir != 0)) rot = rot + 3.14159265358979323846f;
         }

@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include "aot.h"
+#include "device.h"
 
 namespace md {
 
@@ -22,12 +23,6 @@ struct PreArgs {
     uint16_t *out;        // [N,Hp,Wp,C] bf16, C = 4 or 8, image area at (pad_lo, pad_lo), everything else zero
     int N, Hs, Ws, Ho, Wo, Hp, Wp, C, pad_lo;
 };
-
-__device__ __forceinline__ unsigned ppk_bf16(float lo, float hi) {
-    unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-    return r;
-}
 
 // one lane = one output pixel of the PADDED tensor (8 or 16 bytes), so the zero border is written by the same pass
 __global__ __launch_bounds__(256) void image_preprocess_kernel(PreArgs a, size_t total) {
@@ -59,7 +54,7 @@ __global__ __launch_bounds__(256) void image_preprocess_kernel(PreArgs a, size_t
             for (int c = 0; c < 3; ++c) v[c] = (v[c] * (1.0f / 255.0f) - a.norm[c]) / a.norm[3 + c];
         }
         uint16_t *dst = a.out + e * a.C;
-        const uint2 lo = make_uint2(ppk_bf16(v[0], v[1]), ppk_bf16(v[2], 0.f));
+        const uint2 lo = make_uint2(pk_bf16(v[0], v[1]), pk_bf16(v[2], 0.f));
         *reinterpret_cast<uint2 *>(dst) = lo;
         if (a.C == 8) *reinterpret_cast<uint2 *>(dst + 4) = make_uint2(0u, 0u);
     }

@@ -23,12 +23,9 @@
 #include <stdint.h>
 
 #include "aot.h"
+#include "device.h"
 
 namespace md {
-
-typedef __attribute__((ext_vector_type(8))) short bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 
 constexpr int ST_PAD_LO = 7, ST_PAD_HI = 9;               // image border (pixels) in the input layout
 constexpr int ST_TPH = 4, ST_TPW = 16;                    // pooled pixels per workgroup
@@ -55,19 +52,6 @@ struct StemArgs {
     int tiles_x, tiles_y, n_tiles;
     unsigned x_bytes;
 };
-
-__device__ __forceinline__ uint16_t st_f2bf(float f) {
-    unsigned u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-
-__device__ __forceinline__ unsigned st_pk_bf16(float lo, float hi) {  // RNE, one instruction (gfx950)
-    unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-    return r;
-}
 
 __device__ __forceinline__ unsigned pk_max_u16(unsigned x, unsigned y) {
     unsigned r;
@@ -106,7 +90,7 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(StemArgs a) {
         t_off[f] = q < ST_NPX ? q * ST_TROW : -1;
         q_rc[f] = (cyl << 8) | cxl;
     }
-    __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void *)a.x, 0, a.x_bytes, 0x00020000);
+    __amdgpu_buffer_rsrc_t rs_x = srd(a.x, a.x_bytes);
     // patch DMA: wave w issues pieces w, w+4, ...; lane -> 16-B chunk i = piece * 64 + lane = (row, chunk in row)
     auto dma_patch = [&](int t) {
         const int tx = t % a.tiles_x, ty = (t / a.tiles_x) % a.tiles_y, n = t / (a.tiles_x * a.tiles_y);
@@ -159,8 +143,8 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(StemArgs a) {
                 float v0 = fmaxf(acc[f][4 * g + 0] + bv[g].x, 0.f), v1 = fmaxf(acc[f][4 * g + 1] + bv[g].y, 0.f);
                 float v2 = fmaxf(acc[f][4 * g + 2] + bv[g].z, 0.f), v3 = fmaxf(acc[f][4 * g + 3] + bv[g].w, 0.f);
                 uint2 pk;
-                pk.x = st_pk_bf16(v0, v1);
-                pk.y = st_pk_bf16(v2, v3);
+                pk.x = pk_bf16(v0, v1);
+                pk.y = pk_bf16(v2, v3);
                 if (pad) pk = make_uint2(0u, 0u);
                 *reinterpret_cast<uint2 *>(tile + t_off[f] + (wc * 32 + 8 * g + 4 * lh) * 2) = pk;
             }

@@ -21,14 +21,9 @@
 #include <stdint.h>
 
 #include "aot.h"
+#include "device.h"
 
 namespace md {
-
-typedef __attribute__((ext_vector_type(8))) short sc_bf16x8;
-typedef __attribute__((ext_vector_type(16))) float sc_f32x16;
-typedef __attribute__((ext_vector_type(4))) float sc_f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int sc_u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int sc_u32x2;
 
 constexpr int SC_TH = 8, SC_TW = 32;            // output pixels per workgroup: fragment f = tile row f, lane = column
 constexpr int SC_PW = 72, SC_ROWB = SC_PW * 8;  // patch row: 72 pixels x 4 channels x 2 B = 576 B
@@ -42,13 +37,6 @@ struct StemConvArgs {
     int tiles_x, tiles_y, n_tiles;
     unsigned x_bytes;
 };
-
-__device__ __forceinline__ unsigned sc_pk_bf16(float lo, float hi) {
-    unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-    return r;
-}
-__device__ __forceinline__ float sc_silu(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }   // as conv.hip
 
 // KH 6: the 6x6 / pad 2 window as 6 rows x 8 columns starting at padded (2 oy + 5, 2 ox + 4); KH 3: 3x3 / pad 1 as 3 rows x 4 columns
 // starting at padded (2 oy + 6, 2 ox + 6)
@@ -70,14 +58,14 @@ __global__ __launch_bounds__(256, 2) void stem_conv_kernel(StemConvArgs a) {
     const int wc = wave / WPN, wp = wave % WPN;
     const int lr = lane & 31, lh = lane >> 5;
 
-    sc_bf16x8 fa[KSTEPS];
+    bf16x8 fa[KSTEPS];
 #pragma unroll
-    for (int s = 0; s < KSTEPS; ++s) fa[s] = *reinterpret_cast<const sc_bf16x8 *>(a.w + (size_t)(wc * 32 + lr) * KTOT + s * 16 + lh * 8);
-    sc_f32x4 bv[4];
+    for (int s = 0; s < KSTEPS; ++s) fa[s] = *reinterpret_cast<const bf16x8 *>(a.w + (size_t)(wc * 32 + lr) * KTOT + s * 16 + lh * 8);
+    f32x4 bv[4];
 #pragma unroll
-    for (int g = 0; g < 4; ++g) bv[g] = *reinterpret_cast<const sc_f32x4 *>(a.bias + wc * 32 + 8 * g + 4 * lh);
+    for (int g = 0; g < 4; ++g) bv[g] = *reinterpret_cast<const f32x4 *>(a.bias + wc * 32 + 8 * g + 4 * lh);
 
-    __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void *)a.x, 0, a.x_bytes, 0x00020000);
+    __amdgpu_buffer_rsrc_t rs_x = srd(a.x, a.x_bytes);
     auto dma_patch = [&](int t) {
         const int tx = t % a.tiles_x, ty = (t / a.tiles_x) % a.tiles_y, n = t / (a.tiles_x * a.tiles_y);
         const int base = ((n * a.Hp + 2 * ty * SC_TH + ROW0) * a.Wp + 2 * tx * SC_TW + COL0) * 8;
@@ -101,7 +89,7 @@ __global__ __launch_bounds__(256, 2) void stem_conv_kernel(StemConvArgs a) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();   // patch landed; the previous tile's read-out is done
 
-        sc_f32x16 acc[NF];
+        f32x16 acc[NF];
 #pragma unroll
         for (int f = 0; f < NF; ++f)
 #pragma unroll
@@ -112,7 +100,7 @@ __global__ __launch_bounds__(256, 2) void stem_conv_kernel(StemConvArgs a) {
 #pragma unroll
             for (int f = 0; f < NF; ++f) {
                 const int cy = wp * NF + f;   // tile row of this fragment
-                const sc_bf16x8 fb = *reinterpret_cast<const sc_bf16x8 *>(patch + ((2 * cy + ky) * SC_PW + 2 * lr + kx0 + 2 * lh) * 8);
+                const bf16x8 fb = *reinterpret_cast<const bf16x8 *>(patch + ((2 * cy + ky) * SC_PW + 2 * lr + kx0 + 2 * lh) * 8);
                 acc[f] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s], fb, acc[f], 0, 0, 0);
             }
         }
@@ -126,12 +114,12 @@ __global__ __launch_bounds__(256, 2) void stem_conv_kernel(StemConvArgs a) {
             for (int g = 0; g < 4; ++g) {
                 float v0 = acc[f][4 * g + 0] + bv[g].x, v1 = acc[f][4 * g + 1] + bv[g].y;
                 float v2 = acc[f][4 * g + 2] + bv[g].z, v3 = acc[f][4 * g + 3] + bv[g].w;
-                if (a.act == 2) { v0 = sc_silu(v0); v1 = sc_silu(v1); v2 = sc_silu(v2); v3 = sc_silu(v3); }
+                if (a.act == 2) { v0 = silu(v0); v1 = silu(v1); v2 = silu(v2); v3 = silu(v3); }
                 else if (a.act == 1) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); v2 = fmaxf(v2, 0.f); v3 = fmaxf(v3, 0.f); }
-                sc_u32x2 pk;
-                pk.x = sc_pk_bf16(v0, v1);
-                pk.y = sc_pk_bf16(v2, v3);
-                *reinterpret_cast<sc_u32x2 *>(tile + q * TROW + (wc * 32 + 8 * g + 4 * lh) * 2) = pk;
+                u32x2 pk;
+                pk.x = pk_bf16(v0, v1);
+                pk.y = pk_bf16(v2, v3);
+                *reinterpret_cast<u32x2 *>(tile + q * TROW + (wc * 32 + 8 * g + 4 * lh) * 2) = pk;
             }
         }
         __syncthreads();
@@ -139,9 +127,9 @@ __global__ __launch_bounds__(256, 2) void stem_conv_kernel(StemConvArgs a) {
 #pragma unroll
         for (int it = 0; it < SC_TH * SC_TW * CPP / 256; ++it) {
             const int e = tid + 256 * it, q = e / CPP, cc = e % CPP;
-            const sc_u32x4 v = *reinterpret_cast<const sc_u32x4 *>(tile + q * TROW + cc * 16);
+            const u32x4 v = *reinterpret_cast<const u32x4 *>(tile + q * TROW + cc * 16);
             const int oy = ty * SC_TH + (q >> 5), ox = tx * SC_TW + (q & 31);
-            __builtin_nontemporal_store(v, reinterpret_cast<sc_u32x4 *>(a.y + (((size_t)n * a.Ho + oy) * a.Wo + ox) * COUT + cc * 8));
+            __builtin_nontemporal_store(v, reinterpret_cast<u32x4 *>(a.y + (((size_t)n * a.Ho + oy) * a.Wo + ox) * COUT + cc * 8));
         }
     }
 }

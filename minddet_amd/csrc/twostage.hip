@@ -15,32 +15,15 @@
 #include <float.h>
 
 #include "aot.h"
+#include "device.h"
+#include "box_codec.h"   // delta2bbox_one: under this unit's default contraction (fused multiply-adds)
 
 namespace md {
 
-__device__ __forceinline__ float tbf2f(unsigned v16) { return __uint_as_float(v16 << 16); }
-
-static inline unsigned tgrid(size_t total) {
-    size_t b = (total + 255) / 256;
-    return (unsigned)(b > 16384 ? 16384 : (b == 0 ? 1 : b));
-}
-
-struct DecodeP { float mean[4], stdv[4]; float max_ratio, clip_w, clip_h; };
-
+// delta2bbox of this path: clipped to the image when the host left a clip width (fill_decode: only when both extents are positive)
 __device__ __forceinline__ float4 decode_box(float4 r, float dx, float dy, float dw, float dh, const DecodeP &p) {
-    dx = dx * p.stdv[0] + p.mean[0]; dy = dy * p.stdv[1] + p.mean[1];
-    dw = dw * p.stdv[2] + p.mean[2]; dh = dh * p.stdv[3] + p.mean[3];
-    dw = fminf(fmaxf(dw, -p.max_ratio), p.max_ratio);
-    dh = fminf(fmaxf(dh, -p.max_ratio), p.max_ratio);
-    const float px = (r.x + r.z) * 0.5f, py = (r.y + r.w) * 0.5f, pw = r.z - r.x, ph = r.w - r.y;
-    const float gw = pw * expf(dw), gh = ph * expf(dh);
-    const float gx = px + pw * dx, gy = py + ph * dy;
-    float x1 = gx - gw * 0.5f, y1 = gy - gh * 0.5f, x2 = gx + gw * 0.5f, y2 = gy + gh * 0.5f;
-    if (p.clip_w > 0.f) {
-        x1 = fminf(fmaxf(x1, 0.f), p.clip_w); x2 = fminf(fmaxf(x2, 0.f), p.clip_w);
-        y1 = fminf(fmaxf(y1, 0.f), p.clip_h); y2 = fminf(fmaxf(y2, 0.f), p.clip_h);
-    }
-    return make_float4(x1, y1, x2, y2);
+    const float4 o = delta2bbox_one(r, dx, dy, dw, dh, p);
+    return p.clip_w > 0.f ? clip_box(o, p.clip_w, p.clip_h) : o;
 }
 
 // head [B, HW, Cp] bf16: channels [0,A) objectness logits, [A, 5A) deltas (anchor-major: a*4+j).
@@ -57,10 +40,10 @@ __global__ void rpn_decode_kernel(const uint16_t *__restrict__ head, const float
         const int id = idx[e];
         const int loc = id / A, a = id % A;
         const uint16_t *h = head + ((size_t)b * HW + loc) * Cp;
-        const float logit = tbf2f(h[a]);
+        const float logit = bf2f(h[a]);
         const float4 an = *reinterpret_cast<const float4 *>(anchors + (size_t)id * 4);
-        o = decode_box(an, tbf2f(h[A + a * 4]), tbf2f(h[A + a * 4 + 1]), tbf2f(h[A + a * 4 + 2]), tbf2f(h[A + a * 4 + 3]), p);
-        s = 1.0f / (1.0f + expf(-logit));
+        o = decode_box(an, bf2f(h[A + a * 4]), bf2f(h[A + a * 4 + 1]), bf2f(h[A + a * 4 + 2]), bf2f(h[A + a * 4 + 3]), p);
+        s = sigmoid(logit);
     }
     *reinterpret_cast<float4 *>(boxes + (size_t)e * 4) = o;
     scores[e] = s;
@@ -113,7 +96,7 @@ __global__ __launch_bounds__(256) void rcnn_scores_kernel(const uint16_t *__rest
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
         const int c = lane + 64 * t;
-        v[t] = c <= nc ? tbf2f(h[c]) : -FLT_MAX;
+        v[t] = c <= nc ? bf2f(h[c]) : -FLT_MAX;
         m = fmaxf(m, v[t]);
     }
     for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
@@ -151,7 +134,7 @@ __global__ void rcnn_decode_selected_kernel(const uint16_t *__restrict__ cls_reg
         const int r = b * post + j;
         const float *roi = rois + (size_t)r * 5;
         const uint16_t *h = cls_reg + (size_t)r * Cp + reg0 + c * 4;
-        o = decode_box(make_float4(roi[1], roi[2], roi[3], roi[4]), tbf2f(h[0]), tbf2f(h[1]), tbf2f(h[2]), tbf2f(h[3]), p);
+        o = decode_box(make_float4(roi[1], roi[2], roi[3], roi[4]), bf2f(h[0]), bf2f(h[1]), bf2f(h[2]), bf2f(h[3]), p);
         lab = c;
     }
     *reinterpret_cast<float4 *>(boxes + (size_t)e * 4) = o;
@@ -328,8 +311,8 @@ __global__ void mask_select_kernel(const uint16_t *__restrict__ logits, const fl
         const int label = (int)dets[(size_t)r * 6 + 5];
         float v = 0.f;
         if (score > 0.f && label >= 0 && label < nc) {
-            const float x = __uint_as_float((unsigned)logits[e * C + label] << 16);
-            v = 1.0f / (1.0f + expf(-x));
+            const float x = bf2f(logits[e * C + label]);
+            v = sigmoid(x);
         }
         out[e] = v;
     }

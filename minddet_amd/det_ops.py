@@ -399,11 +399,7 @@ def second_box_decode(box_encodings, anchors):
 
 
 def delta2bbox(rois, deltas, means=(0, 0, 0, 0), stds=(1, 1, 1, 1), max_shape=None, wh_ratio_clip=16 / 1000):
-    at = _DeltaAttrs()
-    for i in range(4):
-        at.means[i], at.stds[i] = float(means[i]), float(stds[i])
-    at.max_ratio = abs(math.log(wh_ratio_clip))
-    at.clip_h, at.clip_w = (float(max_shape[0]), float(max_shape[1])) if max_shape is not None else (0.0, 0.0)
+    at = _decode_attrs(means, stds, max_shape, wh_ratio_clip)
     rois, deltas = _f32c(rois), _f32c(deltas)
     out = torch.empty_like(rois)
     _lib.call("md_delta2bbox", [rois, deltas, out], extra=at)
@@ -678,8 +674,6 @@ class CenterHeadPost:
 # ----------------------------------------------------------------------------- PointPillars host post-process
 def _just_below(x):
     """Largest float32 strictly below x: `score >= x` (predict.py:30) expressed as `score > just_below(x)`."""
-    import numpy as np
-
     return float(np.nextafter(np.float32(x), np.float32(-np.inf)))
 
 
@@ -812,8 +806,6 @@ def soft_nms(boxes, scores, count=None, sigma=0.5, Nt=0.5, threshold=0.001, meth
 def get_affine_transform(center, scale, output_size, inv=True):
     """centernet/src/image.py (get_affine_transform with rot = 0): the 2x3 matrix cv2.getAffineTransform returns for
     the three reference points, solved here in float64 (cv2 is not a dependency)."""
-    import numpy as np
-
     scale = np.array([scale, scale], np.float32) if np.isscalar(scale) else np.asarray(scale, np.float32)
     src_w, dst_w, dst_h = scale[0], output_size[0], output_size[1]
     center = np.asarray(center, np.float32)

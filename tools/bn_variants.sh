@@ -14,7 +14,7 @@ FLAGS="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wall -Wno-unused-function -fn
 python3 - "$SRC/bottleneck.hip" "$OUT" <<'EOF'
 import sys
 src, out = sys.argv[1], sys.argv[2]
-s = open(src).read().replace('#include "aot.h"', '#include "../../aot.h"')
+s = open(src).read().replace('#include "aot.h"', '#include "../../aot.h"').replace('#include "device.h"', '#include "../../device.h"')
 MAP = "return (int)(((0x73261540u >> ((l >> 2) * 4)) & 7u) << 2) | (l & 3);"
 assert s.count(MAP) == 1
 variants = {

@@ -25,6 +25,9 @@ RPN_OVERLAP = os.environ.get("MD_RPN_OVERLAP", "1") == "1"
 FUSE_BLOCKS = os.environ.get("MD_FUSE_BLOCKS", "1") == "1"
 # first block of the later stages: conv3 + the strided 1x1 downsample conv as one K-concatenated GEMM (md_conv1x1_dual; MD_FUSE_DUAL=0: two launches)
 FUSE_DUAL = os.environ.get("MD_FUSE_DUAL", "1") == "1"
+# identity-block boundaries of ResNet stage 2 (128 mid / 512 block channels): conv3 + residual of block b and conv1 of block b + 1 as ONE
+# md_pw_chain launch -- the 512-channel tensor is written once and not read back (bit-identical; MD_PW_CHAIN=0: two md_conv2d launches)
+PW_CHAIN = os.environ.get("MD_PW_CHAIN", "1") == "1"
 RPN_FUSED_HEAD = os.environ.get("MD_RPN_FUSED", "1") == "1"  # 0: two md_conv2d launches per level (A/B)
 
 
@@ -235,17 +238,23 @@ class Bottleneck(Module):
         self._fused = nn_ops.pack_bottleneck(self.conv1.packed, self.conv2.packed, self.conv3.packed, pd)
         self._dual = nn_ops.pack_dual(self.conv3.packed, pd) if pd is not None else None
 
-    def __call__(self, x):
-        if FUSE_BLOCKS and self._fused is not None:
-            # one launch for the whole block (md_bottleneck): x is read once, the 64-channel intermediates stay in LDS, and the
-            # first block's 1x1 downsample conv is computed from the same x tile
-            res = self.downsample(x) if (self.downsample is not None and self._fused.wd is None) else None
-            return nn_ops.bottleneck(x, self._fused, residual=res)
-        if FUSE_DUAL and self._dual is not None:
-            # first block of a stage: conv3 and the (strided) 1x1 downsample conv as ONE GEMM over [t2 ; x] (md_conv1x1_dual)
-            return nn_ops.conv1x1_dual(self.conv2(self.conv1(x)), x, self._dual)
+    def __call__(self, x, t1=None, chain=None):
+        """t1: conv1(x), where the block in front has computed it in its tail; chain: the md_pw_chain pack of (this conv3, the next block's
+        conv1) -- the call then returns (y, the next block's t1).  Both are for identity blocks on the layer-by-layer path only."""
+        if t1 is None and chain is None:
+            if FUSE_BLOCKS and self._fused is not None:
+                # one launch for the whole block (md_bottleneck): x is read once, the 64-channel intermediates stay in LDS, and the
+                # first block's 1x1 downsample conv is computed from the same x tile
+                res = self.downsample(x) if (self.downsample is not None and self._fused.wd is None) else None
+                return nn_ops.bottleneck(x, self._fused, residual=res)
+            if FUSE_DUAL and self._dual is not None:
+                # first block of a stage: conv3 and the (strided) 1x1 downsample conv as ONE GEMM over [t2 ; x] (md_conv1x1_dual)
+                return nn_ops.conv1x1_dual(self.conv2(self.conv1(x)), x, self._dual)
         residual = self.downsample(x) if self.downsample is not None else x
-        return self.conv3(self.conv2(self.conv1(x)), residual=residual)
+        t2 = self.conv2(self.conv1(x) if t1 is None else t1)
+        if chain is not None:
+            return nn_ops.pw_chain(t2, residual, chain)
+        return self.conv3(t2, residual=residual)
 
 
 @BACKBONES.register_module
@@ -283,6 +292,16 @@ class ResNet(Module):
         self.stem = None
         if self.conv1.cout == 64 and self.conv1.relu:  # the fused conv + BN + ReLU + maxpool kernel (md_stem_pool)
             self.stem = nn_ops.pack_stem(self.conv1.weight, bn=self.conv1.bn, bias=self.conv1.bias).to(device)
+        # md_pw_chain packs, keyed by (stage, block): the tail of identity block b with the head of block b + 1 (they hold the blocks'
+        # own pack tensors, so ResNet.to() is the call that makes them)
+        self._chains = {}
+        if self.block is Bottleneck:
+            for si, st in enumerate(self.stages):
+                for bi in range(1, len(st) - 1):
+                    if st[bi].downsample is None and st[bi + 1].downsample is None and st[bi]._fused is None and st[bi + 1]._fused is None:
+                        pk = nn_ops.pack_pw_chain(st[bi].conv3.packed, st[bi + 1].conv1.packed)
+                        if pk is not None:
+                            self._chains[(si, bi)] = pk
 
     def __call__(self, x):
         """x: [N,H,W,8] bf16 NHWC (3 real channels), or the same batch already in the stem layout
@@ -295,9 +314,16 @@ class ResNet(Module):
             x = self.conv1(x)
             x = nn_ops.maxpool2d(x, 3, 2, 1, zero_pad=True)
         outs = []
-        for st in self.stages:
-            for b in st:
-                x = b(x)
+        for si, st in enumerate(self.stages):
+            t1 = None
+            for bi, b in enumerate(st):
+                chain = self._chains.get((si, bi)) if PW_CHAIN else None
+                if chain is not None:
+                    x, t1 = b(x, t1=t1, chain=chain)      # ... and conv1 of block bi + 1
+                elif t1 is not None:
+                    x, t1 = b(x, t1=t1), None
+                else:
+                    x = b(x)
             outs.append(x)
         return tuple(outs)
 

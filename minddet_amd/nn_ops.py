@@ -285,6 +285,40 @@ def conv1x1_dual(xa, xb, pk, out=None, tune=None):
     return out
 
 
+class PackedPwChain:
+    """conv3 of one identity bottleneck block and conv1 of the block behind it, as md_pw_chain consumes them (the conv packs' own tensors)."""
+
+    def __init__(self, pc3, pc1):
+        self.w3, self.b3, self.w1, self.b1 = pc3.w, pc3.bias, pc1.w, pc1.bias
+        self.cin_real = pc3.cin_real
+
+    def flops_bytes(self, n, h, w):
+        """algorithmic flops and bytes of the pair as ONE op: t2 and the residual read, y and t1 written"""
+        px = n * h * w
+        return 2.0 * px * (512 * 128 + 128 * 512), 2.0 * (px * (128 + 512 + 512 + 128) + self.w3.numel() + self.w1.numel())
+
+
+def pack_pw_chain(pc3, pc1):
+    """-> PackedPwChain when (conv 1x1 128 -> 512 + residual + ReLU, then conv 1x1 512 -> 128 + ReLU) is the pair md_pw_chain computes in
+    one launch (the identity-block boundaries of ResNet-50 / 101 stage 2), else None"""
+    def plain1x1(pc, cin, cout):
+        return (pc.kh == 1 and pc.kw == 1 and pc.stride == 1 and pc.pad == 0 and pc.relu == 1 and pc.cin == cin and pc.cout == cout and
+                tuple(pc.w.shape) == (cout, cin) and tuple(pc.bias.shape) == (cout,))
+    return PackedPwChain(pc3, pc1) if plain1x1(pc3, 128, 512) and plain1x1(pc1, 512, 128) else None
+
+
+def pw_chain(t2, res, pk):
+    """(y, t1) = (relu(conv3(t2) + res), relu(conv1(y))) in one md_pw_chain launch: t2 [N,H,W,128], res [N,H,W,512] -> y [N,H,W,512],
+    t1 [N,H,W,128]; bit-identical to conv2d(t2, conv3, residual=res) followed by conv2d(y, conv1)."""
+    n, h, w, c = t2.shape
+    if c != 128 or tuple(res.shape) != (n, h, w, 512):
+        raise _lib.MindDetHipError(f"pw_chain: inputs are {tuple(t2.shape)} / {tuple(res.shape)}, need [N,H,W,128] / [N,H,W,512]")
+    y = torch.empty((n, h, w, 512), dtype=torch.bfloat16, device=t2.device)
+    t1 = torch.empty((n, h, w, 128), dtype=torch.bfloat16, device=t2.device)
+    _lib.call("md_pw_chain", [t2, res, pk.w3, pk.b3, pk.w1, pk.b1, y, t1])
+    return y, t1
+
+
 class PackedConvT:
     """A transposed conv as s*s sub-pixel convs on the MFMA kernel (one launch per output parity)."""
 

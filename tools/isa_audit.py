@@ -42,13 +42,15 @@ HOT = {
     "md::c3pair32_kernel": 0,
     "md::c3pair64_kernel": 2,
     "md::c3pair128_kernel": 3,
+    # pwchain: every per-tile decision is a scalar select of a descriptor (empty past the workgroup's range), none is a branch
+    "md::pw_chain_kernel": 0,
 }
 
 
 def compile_isa(src):
     os.makedirs(OUT, exist_ok=True)
     dst = os.path.join(OUT, os.path.basename(src)[:-4] + ".s")
-    deps = [src] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [os.path.join(ROOT, "include", "minddet_hip.h")]
+    deps = [src] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [os.path.join(ROOT, "include", "minddet_hip.h"), os.path.join(ROOT, "include", "minddet_hip_chain.h")]
     if not os.path.exists(dst) or os.path.getmtime(dst) < max(os.path.getmtime(d) for d in deps):
         subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + ["-o", dst, src], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     return dst
@@ -142,7 +144,7 @@ def audit_file(spath):
     return res
 
 
-def audit(files=("bottleneck.hip", "c3pair.hip", "conv.hip", "stem.hip", "stemconv.hip", "detops.hip", "twostage.hip", "nms.hip", "pool.hip", "preproc.hip", "dcn.hip", "targets.hip")):
+def audit(files=("bottleneck.hip", "c3pair.hip", "pwchain.hip", "conv.hip", "stem.hip", "stemconv.hip", "detops.hip", "twostage.hip", "nms.hip", "pool.hip", "preproc.hip", "dcn.hip", "targets.hip")):
     """-> (rows, violations): rows = [(demangled name, stats)], violations = [str]"""
     rows, bad = [], []
     for f in files:

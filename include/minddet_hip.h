@@ -83,17 +83,42 @@ int md_scratch_release(void);
 int BoxesIouBevGpu(MD_AOT_ARGS);
 /* in: boxes_a[M,7] f32, boxes_b[N,7] f32 ; out: overlap[M,N] f32.  iou3d_nms_kernel.cu:236-249 */
 int BoxesOverlapBevGpu(MD_AOT_ARGS);
+/* Rules shared by every greedy NMS op of this header (NmsGpu, NmsNormalGpu, boxes_iou_nms_gpu, md_nms_aligned, md_circle_nms;
+ * tests/nms_contract.py states them in float64 and tests/test_nms_lists_gpu.py holds the kernels to them):
+ *   - greedy over the list order (= descending score): a box is dropped iff an earlier KEPT box suppresses it; a dropped box
+ *     suppresses nothing.
+ *   - tie operator: each op below names it (`>`, `>=` or `<=`) against float32(thresh); a quantity exactly equal to the
+ *     threshold is decided by that operator alone.
+ *   - NaN rule: an IoU (or distance) that IS NaN compares false in both directions: such a pair never suppresses, under every
+ *     operator.  Whether a NaN coordinate makes the quantity NaN differs per op:
+ *       md_nms_aligned modes 0 and 1, boxes_iou_nms_gpu, md_circle_nms: the quotient (distance) is unclamped and NaN; a box
+ *         with a NaN coordinate is kept and drops nothing.
+ *       md_nms_aligned mode 2: fmaxf(NaN union, 1e-8) is 1e-8, and min / max are the reference's ternaries (a > b ? b : a;
+ *         md_nms_aligned only), which keep or drop a NaN edge by operand order: ovr = inter / 1e-8 or 0.  A box with NaN x1 or
+ *         y1 suppresses what its remaining extent overlaps, a box with NaN x2 or y2 is suppressed by what overlaps it; an
+ *         all-NaN box has inter 0 and is inert.
+ *       NmsNormalGpu: fmaxf / fminf drop a NaN edge, so along an axis with a NaN centre or size the box takes the other box's
+ *         extent; with a NaN dx or dy the NaN union also clamps to 1e-8 and iou = inter / 1e-8.  Such a box suppresses, and is
+ *         suppressed by, whatever its remaining extent overlaps (an all-NaN first row drops every later box).
+ *       NmsGpu: every comparison of the clipping is false, the overlap is 0 and the IoU 0 / 1e-8 = 0: kept, drops nothing.
+ *   - count clamp (md_nms_aligned, md_soft_nms): a list's length is min(count[b], N); boxes past it
+ *     are never kept and suppress nothing; their keep_mask is 0.
+ *   - dead-area rule: only boxes_iou_nms_gpu has one (a box with dx * dy == 0 in fp32 is never kept and never suppresses).  The
+ *     other ops keep a zero-area box unless a kept box suppresses it: NmsGpu and NmsNormalGpu see IoU 0 / 1e-8 = 0 between two
+ *     all-zero rows and keep every one of them; md_nms_aligned per mode, see there.
+ *   - keep lists ascend; entries past num are 0. */
 /* in: boxes[N,7] f32 (sorted by score, descending), thresh[1] f32 ;
- * out: keep[N] i64 (leading num valid, rest 0), num[1] i32.  Suppress iff IoU > thresh,
- * IoU = overlap / fmaxf(sa+sb-overlap, 1e-8).  iou3d_nms_kernel.cu:267-311 + :491-546 */
+ * out: keep[N] i64 (leading num valid, rest 0), num[1] i32.  Suppress iff IoU > thresh (a tie is kept),
+ * IoU = overlap / fmaxf(sa+sb-overlap, 1e-8).  No dead-area rule.  iou3d_nms_kernel.cu:267-311 + :491-546 */
 int NmsGpu(MD_AOT_ARGS);
-/* same I/O; axis-aligned IoU of the (x,y,dx,dy) footprint.  iou3d_nms_kernel.cu:314-372,548-601 */
+/* same I/O and operator (> thresh, union clamped at 1e-8, no dead-area rule); axis-aligned IoU of the (x -+ dx/2, y -+ dy/2)
+ * footprint.  iou3d_nms_kernel.cu:314-372,548-601 */
 int NmsNormalGpu(MD_AOT_ARGS);
 /* Device twin of the reference's CPU operator boxes_iou_nms_cpu (iou-bev-nms-org.cpp:237-283,
  * Python side nms_cpu.py:10-27): in: boxes[N,7] f32, thresh[1] f32 ; out: keep[N] i32,
- * num[1] i32.  Suppress iff ovr >= thresh with ovr = overlap/(sa+sb-overlap) (no eps);
- * zero-area boxes are dropped up front.  N comes from shapes[0][0] (the reference hard-codes
- * 1000, :244). */
+ * num[1] i32.  Suppress iff ovr >= thresh (a tie is dropped) with ovr = overlap/(sa+sb-overlap) (no eps: 0/0 = NaN never
+ * suppresses); dead-area rule: boxes with dx * dy == 0 are dropped up front and suppress nothing.  N comes from shapes[0][0]
+ * (the reference hard-codes 1000, :244). */
 int boxes_iou_nms_gpu(MD_AOT_ARGS);
 
 /* ------------------------------------------------------------------------------------------
@@ -116,17 +141,20 @@ int md_rotate_iou_eval(MD_AOT_ARGS);
 typedef struct md_nms_attrs {
     float iou_threshold;
     float eps;         /* mode 0 only */
-    int32_t mode;      /* 0 nms_jit (>= thr, eps)       pointpillars/src/core/nms.py:85-112
-                          1 apply_nms (+1 px, > thr)     pointpillars/src/core/nms.py:7-41
-                          2 strict > thr, fmaxf(union,1e-8) (iou_normal on corner boxes) */
+    int32_t mode;      /* 0 nms_jit (>= thr: a tie is dropped, eps)       pointpillars/src/core/nms.py:85-112
+                          1 apply_nms (+1 px, > thr: a tie is kept)        pointpillars/src/core/nms.py:7-41
+                          2 strict > thr (a tie is kept), fmaxf(union,1e-8) (iou_normal on corner boxes) */
     int32_t max_output; /* <=0: no cap; else keep only the first max_output survivors */
 } md_nms_attrs;
 /* Greedy NMS over B independent lists of corner boxes already sorted by descending score.
- * in : boxes[B,N,4] f32 (or [N,4]), count[B] i32 (valid leading boxes per list; may be a
+ * in : boxes[B,N,4] f32 (or [N,4]), count[B] i32 (valid leading boxes per list, clamped to [0, N]; may be a
  *      NULL pointer = all N), group[B,N] i32 (class / task key: boxes with different keys
  *      never suppress each other; may be a NULL pointer)
  * out: keep_mask[B,N] u8, keep_idx[B,N] i32 (leading num valid, rest 0), num[B] i32
- * extra: md_nms_attrs (required). */
+ * extra: md_nms_attrs (required).  With max_output = q > 0 the list is cut right after its q-th kept box.  No dead-area rule: a
+ * zero-area box is kept unless a kept box suppresses it, and whether coincident ones do follows from the mode: mode 0 with
+ * eps 0 sees 0/0 = NaN and mode 2 sees 0 / 1e-8 = 0 (all kept); mode 1 (+1 pixel), and mode 0 with eps > 0, give such a box a
+ * positive area, coincident ones have ovr 1 and only the first is kept.  NaN rule above. */
 int md_nms_aligned(MD_AOT_ARGS);
 
 typedef struct md_soft_nms_attrs {
@@ -136,12 +164,16 @@ typedef struct md_soft_nms_attrs {
 /* Soft-NMS (Bodla et al. 2017; call site centernet/src/post_process.py:45-52 -- the Cython module is not vendored in
  * the reference, parity unpinned).  in boxes[L,N,4] f32, scores[L,N] f32, count[L] i32 or NULL (N <= 1024) ;
  * out scores_out[L,N] f32 (decayed score of each surviving box at its ORIGINAL position, 0 = removed),
- * order[L,N] i32 (survivors in selection order, leading num valid), num[L] i32 */
+ * order[L,N] i32 (survivors in selection order, leading num valid, rest 0), num[L] i32.
+ * Each round selects the live box of the highest score (a tie goes to the lowest index), multiplies the score of every other
+ * live box that overlaps it (+1 pixel extents, both > 0) by the method's weight -- methods 1 and 3 act iff overlap > Nt -- and
+ * drops a box whose score thereby falls below `threshold` (<: a score equal to it stays; a box that is never decayed is never
+ * dropped, whatever its score).  count clamp as above; boxes past it read 0 in scores_out. */
 int md_soft_nms(MD_AOT_ARGS);
 
 /* circle_nms (centerpoint/det3d_ms/core/utils/circle_nms_jit.py:6-36):
  * in xy[N,2] f32 sorted by score desc, thresh[1] f32 ; out keep_mask[N] u8, keep_idx[N] i32,
- * num[1] i32.  Suppress iff squared centre distance <= thresh. */
+ * num[1] i32.  Suppress iff squared centre distance <= thresh (a distance exactly equal to it suppresses; NaN does not). */
 int md_circle_nms(MD_AOT_ARGS);
 
 /* ------------------------------------------------------------------------------------------

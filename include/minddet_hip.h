@@ -457,7 +457,10 @@ int md_assign_targets(MD_AOT_ARGS);
  * in : img[N,Hs,Ws,3] uint8 ; mat[N,6] f32 = per image the 2x3 matrix mapping OUTPUT pixel (x, y) to SOURCE pixel
  *      (sx = m0 x + m1 y + m2, sy = m3 x + m4 y + m5) ; norm[6] f32 = mean[3], std[3] of the 0..1 image
  * out: y[N, pad_lo + out_h + pad_hi, pad_lo + out_w + pad_hi, C] bf16, C = 4 (stem layout: pad_lo 7, pad_hi 9) or 8
- *      (pad 0); channels 3.. and the border are zero.
+ *      (pad 0; any pad_lo, pad_hi >= 0 is accepted with either C); channels 3.. and the border are exactly +0.
+ * Sampling: the source is extended by zeros; a position in (-1, 0) or (Ws - 1, Ws) keeps its in-image column with its partial
+ * weight (likewise rows).  A position outside the open range (-1, Ws) x (-1, Hs) -- huge, infinite and NaN positions included --
+ * touches no pixel and gives the black level (0 - mean) / std; it is never converted to an integer.
  * fp32 interpolation (cv2's 1/32-pixel fixed point is not reproduced; cv2 is absent here: parity unpinned). */
 typedef struct md_preprocess_attrs {
     int32_t out_h, out_w, pad_lo, pad_hi;
@@ -469,7 +472,12 @@ int md_image_preprocess(MD_AOT_ARGS);
  * in  x[N,H,W,C] bf16 ; off[N,Ho,Wo,Coff >= 3*k*k] bf16 = the offset conv's output in the wrapper's own channel order
  *     (tap t = ky*k + kx: channel 2t = dy, 2t+1 = dx; channel 2*k*k + t = mask logit)
  * out cols[N,Ho,Wo,k*k*C] bf16, cols[.., t*C + c] = sigmoid(mask_t) * bilinear(x[.., c]; ho*s - p + ky + dy_t, wo*s - p + kx + dx_t),
- *     zero outside the image.  extra: md_pool_attrs (k, stride, pad).
+ *     zero outside the image.  extra: md_pool_attrs (k, stride, pad), k in 1..7.
+ *     The coordinate is the fp32 sum of the integer tap position and the bf16 offset.  A coordinate in (-1, 0) or (H - 1, H) keeps
+ *     its in-image row with its partial weight (likewise columns); the range test is strict: a tap samples only for -1 < y < H and
+ *     -1 < x < W, and every other tap -- at exactly -1, H or W, huge, infinite or NaN offsets included -- gives +0 columns.
+ *     sigmoid is 1.0f / (1.0f + __expf(-logit)): exactly 1/2 at 0, 1 from 18 up and at +inf, 0 from -89 down and at -inf; a NaN
+ *     logit gives NaN columns (also on a tap outside the range).  The product is rounded to bf16 once, after the mask.
  * Step 2 is md_conv2d with kh = kw = 1 on `cols` and the layer's [Cout][k*k*C] weights (K order (tap, channel) = the packed
  * 3x3 layout).  The arithmetic of the MindSpore primitive is not in the reference: published DCNv2 definition, parity unpinned. */
 int md_deform_cols(MD_AOT_ARGS);

@@ -46,6 +46,7 @@ namespace md {
 // alias info (HIP's float4 / uint2 structs) while LDS-DMAs are pending -- r02: that drained the W2-tap / W3 DMAs of bottleneck64_kernel in
 // front of the T1 / T2 epilogues instead of letting the epilogue math run under their latency
 typedef __attribute__((ext_vector_type(8))) short bf16x8;
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;   // the A / B fragment of the f16 MFMAs (ppreader.hip)
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(2))) float f32x2;

@@ -1044,3 +1044,62 @@ def pillar_encode(voxels, num_points, coors, voxel_num, pfn, hw, vx, vy, x_offse
     at = _PillarEncodeAttrs(float(vx), float(vy), float(x_offset), float(y_offset), 0, 0)
     _lib.call("md_pillar_encode", [voxels, num_points, coors, voxel_num, pfn.w1, pfn.b1, pfn.w2, pfn.b2, canvas], extra=at)
     return canvas
+
+
+# ----------------------------------------------------------------------------- KITTI PointPillars front end (csrc/ppreader.hip)
+class _PPPillarEncodeAttrs(ctypes.Structure):
+    _fields_ = [("vx", ctypes.c_float), ("vy", ctypes.c_float), ("vz", ctypes.c_float), ("x_offset", ctypes.c_float),
+                ("y_offset", ctypes.c_float), ("z_offset", ctypes.c_float), ("with_distance", ctypes.c_int32), ("reserved0", ctypes.c_int32)]
+
+
+class PackedPPReader:
+    """The KITTI reader's one PFN layer as md_pp_pillar_encode takes it: the RAW Dense weight [64, K] (the op rounds it to fp16 as the
+    reference's to_float(float16) does, so the BatchNorm must not be folded into it) and the BatchNorm as scale, shift [64] in fp32."""
+
+    def __init__(self, w, scale, shift):
+        self.w, self.scale, self.shift = w, scale, shift
+
+    def to(self, device):
+        self.w, self.scale, self.shift = self.w.to(device), self.scale.to(device), self.shift.to(device)
+        return self
+
+
+def pack_pp_pfn(layers):
+    """layers: [(weight [64, K] f32, (gamma, beta, mean, var, eps))], K = 10 or 11 -> PackedPPReader.  In fp32:
+    scale = gamma / sqrt(var + eps), shift = beta - mean * scale; the weight is kept as it is."""
+    if len(layers) != 1:
+        raise ValueError(f"pack_pp_pfn: the KITTI reader is built with one PFN layer, got {len(layers)}")
+    weight, (gamma, beta, mean, var, eps) = layers[0]
+    weight = torch.as_tensor(weight, dtype=torch.float32).contiguous()
+    if weight.dim() != 2 or weight.shape[0] != 64 or weight.shape[1] not in (10, 11):
+        raise ValueError(f"pack_pp_pfn: the Dense weight is [64, 10] or [64, 11] (with_distance), got {tuple(weight.shape)}")
+    scale = torch.as_tensor(gamma, dtype=torch.float32) / torch.sqrt(torch.as_tensor(var, dtype=torch.float32) + float(eps))
+    shift = torch.as_tensor(beta, dtype=torch.float32) - torch.as_tensor(mean, dtype=torch.float32) * scale
+    return PackedPPReader(weight, scale.contiguous(), shift.contiguous())
+
+
+def pp_pillar_encode(voxels, num_points, coors, voxel_num, pfn, hw, voxel_size, offsets, out=None):
+    """The KITTI model's PillarFeatureNet + PointPillarsScatter (md_pp_pillar_encode): the outputs of voxelize ([.., 4] points) and a
+    PackedPPReader -> the pseudo-image [B, H, W, 64] bf16 (NHWC), zero where no pillar is.  voxel_size = (vx, vy, vz), offsets =
+    (x, y, z): the centre of cell 0 per axis.  with_distance follows the weight's width."""
+    B = voxels.shape[0]
+    H, W = int(hw[0]), int(hw[1])
+    canvas = out if out is not None else torch.empty((B, H, W, 64), dtype=torch.bfloat16, device=voxels.device)
+    at = _PPPillarEncodeAttrs(*[float(v) for v in voxel_size[:3]], *[float(v) for v in offsets[:3]], int(pfn.w.shape[1] == 11), 0)
+    _lib.call("md_pp_pillar_encode", [voxels, num_points, coors, voxel_num, pfn.w, pfn.scale, pfn.shift, canvas], extra=at)
+    return canvas
+
+
+def anchors_mask_batched(coors, voxel_num, grid_size_xy, anchors_bv, voxel_size, pc_range, area_threshold, with_area=False):
+    """preprocess.py:211-225 for the batch (md_pp_anchor_mask): coors [B, MV, 4] i32 (b, z, y, x) and voxel_num [B] i32 as voxelize
+    leaves them -> mask [B, N] uint8 (, area [B, N] f32): row b is anchors_mask(coors[b, :voxel_num[b], 1:]) bit for bit, with
+    voxel_num read on the device."""
+    at = _AnchorMaskAttrs(int(grid_size_xy[0]), int(grid_size_xy[1]), float(voxel_size[0]), float(voxel_size[1]),
+                          float(pc_range[0]), float(pc_range[1]), float(area_threshold))
+    bv = _f32c(anchors_bv)
+    B, dev = coors.shape[0], bv.device
+    mask = torch.empty((B, bv.shape[0]), dtype=torch.uint8, device=dev)
+    area = torch.empty((B, bv.shape[0]), dtype=torch.float32, device=dev) if with_area else None
+    ws = torch.empty((max(B, 1) * at.grid_x * at.grid_y * 4,), dtype=torch.uint8, device=dev)
+    _lib.call("md_pp_anchor_mask", [coors, voxel_num, bv, mask, area, ws], extra=at)
+    return (mask, area) if with_area else mask

@@ -1128,8 +1128,9 @@ class PointPillarsNet(Module):
     the RPN of :367-621 -- graphs.RPN with block1's inner BatchNorms at the framework's default eps 1e-5 (:470), every other one at
     1e-3 -- the three 1x1 heads as one launch (PPAnchorHead) and det_ops.PPHeadPost on the head tensor.  The anchors come from the
     config's anchor generators (det_ops.generate_anchors at the feature-map size) and are a device constant.
-    Not built (ValueError): this model's reader and scatter (its PillarFeatureNet has a tenth point feature, the z offset from the
-    pillar centre, and an fp16 Dense, which md_pillar_encode does not compute), use_bev=True, encode_background_as_zeros=False,
+    This type starts at the pseudo-image and refuses `voxel_feature_extractor` / `middle_feature_extractor` (ValueError): the model's
+    reader and scatter (a tenth point feature, the z offset from the pillar centre, and an fp16 Dense: md_pp_pillar_encode) belong to
+    graphs.PointPillarsKITTIPoints, which wraps this class.  Not built: use_bev=True, encode_background_as_zeros=False,
     use_self_train=False."""
 
     def __init__(self, rpn, voxel_generator, anchor_generators, num_class=1, use_direction_classifier=True,
@@ -1137,9 +1138,9 @@ class PointPillarsNet(Module):
                  voxel_feature_extractor=None, middle_feature_extractor=None, class_names=None, train_cfg=None, test_cfg=None,
                  pretrained=None, seed=7):
         if voxel_feature_extractor is not None or middle_feature_extractor is not None:
-            raise ValueError("PointPillarsNet: the pillar feature net and the scatter of this model are not part of this build (its "
-                             "reader has a tenth point feature and an fp16 Dense); drop `voxel_feature_extractor` / "
-                             "`middle_feature_extractor` from the config and feed the scattered pseudo-image [B, H, W, 64] bf16 to forward()")
+            raise ValueError("PointPillarsNet: this type starts at the scattered pseudo-image [B, H, W, 64] bf16; a config with "
+                             "`voxel_feature_extractor` / `middle_feature_extractor` is built by type \"PointPillarsKITTIPoints\", which "
+                             "runs the reader (a tenth point feature and an fp16 Dense: md_pp_pillar_encode) from raw points")
         if use_bev:
             raise ValueError("PointPillarsNet: use_bev=True (the BEV extractor branch of the RPN) is not built")
         if not encode_background_as_zeros or not use_sigmoid_score:
@@ -1234,6 +1235,111 @@ class PointPillarsNet(Module):
         if anchors_mask is None:
             return self.forward_split(pseudo_image)
         return self.forward_split((pseudo_image, anchors_mask), prepare=lambda p, m: (p, m))
+
+
+# ----------------------------------------------------------------------------- PointPillars (KITTI) from raw points (csrc/ppreader.hip)
+@READERS.register_module
+class PPPillarFeatureNet(Module):
+    """The KITTI model's PillarFeatureNet (pointpillars/src/pointpillars.py:226-317) with its one PFNLayer (:180-223): every point
+    decorated with its offsets from the voxel's mean and from the pillar centre in x, y AND z (ten features, eleven with_distance),
+    then Dense without bias under to_float(float16) + BatchNorm(eps 1e-3) + ReLU + max over the voxel's rows.  Parameters in the
+    reference's layout (`layers[0] = (weight [64, K], (gamma, beta, mean, var, 1e-3))`); to() keeps the raw weight and folds the
+    BatchNorm into scale / shift (det_ops.pack_pp_pfn).  The net only runs fused with the scatter, as one md_pp_pillar_encode launch."""
+
+    def __init__(self, num_input_features=4, use_norm=True, num_filters=(64,), with_distance=False, voxel_size=(0.16, 0.16, 4),
+                 pc_range=(0, -39.68, -3, 69.12, 39.68, 1), seed=7):
+        num_filters = [int(c) for c in num_filters]
+        if not use_norm:
+            raise ValueError("PPPillarFeatureNet: use_norm=False (a Dense with bias and no BatchNorm) is not built")
+        if num_filters != [64]:
+            raise ValueError(f"PPPillarFeatureNet: built for one PFN layer, num_filters (64,), got {tuple(num_filters)}")
+        if int(num_input_features) != 4:
+            raise ValueError(f"PPPillarFeatureNet: built for 4 point features (x, y, z, r), got {num_input_features}")
+        init = ParamInit(seed)
+        self.num_input_features, self.num_filters, self.with_distance = 4, num_filters, bool(with_distance)
+        self.voxel_size = tuple(float(v) for v in voxel_size[:3])
+        self.offsets = tuple(float(v) / 2 + float(lo) for v, lo in zip(voxel_size[:3], pc_range[:3]))
+        K = 10 + int(self.with_distance)
+        w = init.conv(64, K, 1, std=math.sqrt(2.0 / K)).reshape(64, K)
+        gamma, _, mean, var, _ = init.bn(64, 1e-3)
+        gamma = torch.from_numpy(init.rng.uniform(0.5, 1.5, 64).astype(np.float32))
+        beta = init.bias(64, std=0.1)                      # both signs: where the shift is positive the padded rows win the maximum
+        self.layers = [(w, (gamma, beta, mean, var, 1e-3))]
+        self.out_channels = 64
+
+    def _derive(self, device):
+        self.packed = det_ops.pack_pp_pfn(self.layers).to(device)
+
+
+@DETECTORS.register_module(name="PointPillarsKITTIPoints")
+class PointPillarsKITTIPoints(Module):
+    """The KITTI PointPillars from raw points, built from the reference's config keys: voxel generator (md_voxelize) ->
+    PillarFeatureNet + PointPillarsScatter (md_pp_pillar_encode) -> the anchor mask of the batch (md_pp_anchor_mask) -> an unchanged
+    graphs.PointPillarsNet, i.e. PointPillarsNet.construct(voxels, num_points, coors, anchors, anchors_mask)
+    (pointpillars/src/pointpillars.py:728-739) with the data pipeline's voxeliser and mask in front.  Everything stays on the device:
+    the outputs have fixed capacity and no size is read back."""
+
+    def __init__(self, voxel_generator, voxel_feature_extractor=None, middle_feature_extractor=None, num_point_features=4, use_norm=True,
+                 seed=7, **kwargs):
+        vg = dict(voxel_generator)
+        self.inner = PointPillarsNet(voxel_generator=vg, seed=seed, **kwargs)
+        vfe = dict(voxel_feature_extractor or {})
+        unknown = set(vfe) - {"num_filters", "with_distance", "type"} | set(dict(middle_feature_extractor or {})) - {"type"}
+        if unknown:
+            raise ValueError(f"PointPillarsKITTIPoints: options that are not built: {sorted(unknown)}")
+        self.max_points, self.max_voxels = int(vg["max_number_of_points_per_voxel"]), int(vg["max_number_of_voxels"])
+        if self.max_points > 32:
+            raise ValueError(f"PointPillarsKITTIPoints: at most 32 points per voxel are built, got {self.max_points}")
+        self.pc_range, self.voxel_size = self.inner.pc_range, self.inner.voxel_size
+        gx, gy, gz = det_ops.voxel_grid(self.voxel_size, self.pc_range)
+        if gz != 1:
+            raise ValueError(f"PointPillarsKITTIPoints: pillars span the whole z range (one cell), the voxel generator gives {gz}")
+        self.grid_hw = self.inner.grid_hw
+        self.reader = PPPillarFeatureNet(num_input_features=num_point_features, use_norm=use_norm, num_filters=vfe.get("num_filters", (64,)),
+                                         with_distance=vfe.get("with_distance", False), voxel_size=self.voxel_size,
+                                         pc_range=self.pc_range, seed=seed + 2)
+        if self.reader.out_channels != self.inner.in_channels:
+            raise ValueError("PointPillarsKITTIPoints: the reader's width does not match rpn.num_input_filters")
+        self.test_cfg, self.class_names = self.inner.test_cfg, self.inner.class_names
+
+    def children(self):
+        return [self.reader, self.inner]
+
+    @property
+    def neck(self):
+        return self.inner.neck
+
+    @property
+    def bbox_head(self):
+        return self.inner.bbox_head
+
+    def front_end(self, points, offsets):
+        """points [N, 4] f32, offsets [B + 1] i32 -> (canvas [B, H, W, 64] bf16, anchors mask [B, N_anchors] u8, md_voxelize's outputs)"""
+        vox = det_ops.voxelize(points, offsets, self.voxel_size, self.pc_range, self.max_points, self.max_voxels)
+        voxels, coors, num_points, voxel_num = vox
+        canvas = det_ops.pp_pillar_encode(voxels, num_points, coors, voxel_num, self.reader.packed, self.grid_hw, self.reader.voxel_size,
+                                          self.reader.offsets)
+        mask = det_ops.anchors_mask_batched(coors, voxel_num, (self.grid_hw[1], self.grid_hw[0]), self.inner.anchors_bv, self.voxel_size,
+                                            self.pc_range, self.inner.anchor_area_threshold)
+        return canvas, mask, vox
+
+    def forward(self, points, offsets, return_aux=False):
+        """points [N, 4] f32: the B samples' points back to back; offsets [B + 1] i32 (device) -> (dets [B, nms_post_max_size, 9] f32,
+        count [B] i32) as PointPillarsNet.forward.  With test_cfg.streams > 1 the front end runs once for the batch and the inner
+        model's forward_streams takes the canvas and the mask."""
+        if points.dim() != 2 or points.shape[1] != self.reader.num_input_features:
+            raise ValueError(f"PointPillarsKITTIPoints: the reader takes [N, {self.reader.num_input_features}] points, got "
+                             f"{tuple(points.shape)}")
+        canvas, mask, (voxels, coors, num_points, voxel_num) = self.front_end(points, offsets)
+        if return_aux:
+            out, aux = self.inner.forward(canvas, mask, return_aux=True)
+            return out, dict(aux, voxels=voxels, coors=coors, num_points=num_points, voxel_num=voxel_num, pseudo_image=canvas,
+                             anchors_mask=mask)
+        if self.inner.streams > 1:
+            return self.inner.forward_streams(canvas, mask)
+        return self.inner.forward(canvas, mask)
+
+    __call__ = forward
 
 
 # ----------------------------------------------------------------------------- YOLOv5 (build-authored; parity unpinned)

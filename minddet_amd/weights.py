@@ -548,3 +548,20 @@ def load_pointpillars(model, params, prefix="rpn.", naming="auto", strict=True):
         else:
             setattr(m, attr, a)
     return sorted(k for k in params if k not in used)
+
+
+def pointpillars_points_state(model, naming="ms"):
+    """graphs.PointPillarsKITTIPoints parameters under the reference's names: the reader as `voxel_feature_extractor.pfn_layers.0.linear.
+    weight` / `.norm.*` (pointpillars/src/pointpillars.py:695, 180-200) and the rest as pointpillars_state gives it (`rpn.*`)."""
+    return dict(reader_state(model.reader, prefix="voxel_feature_extractor.", naming=naming), **pointpillars_state(model.inner, naming=naming))
+
+
+def load_pointpillars_points(model, params, naming="auto", strict=True):
+    """Write a PointPillars checkpoint into a graphs.PointPillarsKITTIPoints: load_reader under the prefix `voxel_feature_extractor.` and
+    load_pointpillars under `rpn.`; returns the keys neither used.  Call model.to(device) afterwards.  As for load_pointpillars, only
+    the round trip is tested."""
+    if any(k.startswith(("network.network.", "optimizer.")) for k in params):
+        params = strip_net_prefix(params)
+    unused_r = load_reader(model.reader, params, prefix="voxel_feature_extractor.", naming=naming, strict=strict)
+    unused_m = load_pointpillars(model.inner, params, naming=naming, strict=strict)
+    return sorted(set(unused_r) & set(unused_m))

@@ -1,9 +1,15 @@
 // box_codec.h -- the per-box device arithmetic that more than one translation unit runs: second_box_decode, the standup box and the
 // delta-to-box decode.  detops.hip (md_second_box_decode, md_standup_boxes) and pphead.hip (md_pp_decode_selected) call the first two
 // and nothing else for that arithmetic, so the fused PointPillars decode agrees with the stand-alone operators bit for bit;
-// detops.hip (md_delta2bbox) and twostage.hip (the RPN and R-CNN decodes) call the third.
+// detops.hip (md_delta2bbox) and twostage.hip (the RPN and R-CNN decodes) call the third.  The CenterPoint cell arithmetic
+// (cp_score_one, cp_box_one) is shared the same way by detops.hip (md_centerpoint_decode) and cphead.hip (md_cp_scores,
+// md_cp_decode_selected).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <float.h>
+#include <stdint.h>
+
+#include "device.h"
 
 namespace md {
 
@@ -64,6 +70,40 @@ __device__ __forceinline__ float4 standup_one(float cx, float cy, float dx, floa
         else { x0 = fminf(x0, qx); x1 = fmaxf(x1, qx); y0 = fminf(y0, qy); y1 = fmaxf(y1, qy); }
     }
     return make_float4(x0, y0, x1, y1);
+}
+
+// CenterPoint head, one BEV cell of one task (center_head.py:297-334 predict, :408-423 the score / range mask).  h: the cell's
+// channels (bf16 bits; global memory or LDS), t: the task's first channels, g: the geometry of the test config.
+struct CpTask { int o_reg, o_height, o_dim, o_rot, o_vel, o_hm, ncls; };
+struct CpGeom { float score_thr, osf, vx, vy, px, py; float rmin[3], rmax[3]; };
+
+// -> the cell's score: the first maximum of sigmoid(hm_c) where it is > score_thr and the centre lies inside post_center_range, else
+// -1.  lab = the class of that maximum (whatever the mask says), c = the centre (xs, ys, zs).
+__device__ __forceinline__ float cp_score_one(const uint16_t *h, const CpTask &t, const CpGeom &g, int x, int y, int &lab, float *c) {
+    float best = -FLT_MAX;
+    lab = 0;
+    for (int k = 0; k < t.ncls; ++k) {  // ArgMaxWithValue: first maximum wins
+        const float v = sigmoid(bf2f(h[t.o_hm + k]));
+        if (v > best) { best = v; lab = k; }
+    }
+    const float xs = ((float)x + bf2f(h[t.o_reg])) * g.osf * g.vx + g.px;
+    const float ys = ((float)y + bf2f(h[t.o_reg + 1])) * g.osf * g.vy + g.py;
+    const float zs = bf2f(h[t.o_height]);
+    const bool in_range = xs >= g.rmin[0] && ys >= g.rmin[1] && zs >= g.rmin[2] && xs <= g.rmax[0] && ys <= g.rmax[1] && zs <= g.rmax[2];
+    const bool ok = best > g.score_thr && in_range;
+    c[0] = xs; c[1] = ys; c[2] = zs;
+    return ok ? best : -1.f;
+}
+
+// the box of a cell that passed the mask: b = (x, y, z, dx, dy, dz, vx, vy, rot), nb = the NMS operand (x, y, z, dy, dx, dz,
+// -rot - pi/2: center_head.py:426-430)
+__device__ __forceinline__ void cp_box_one(const uint16_t *h, const CpTask &t, const float *c, float *b, float *nb) {
+    const float d0 = expf(bf2f(h[t.o_dim])), d1 = expf(bf2f(h[t.o_dim + 1])), d2 = expf(bf2f(h[t.o_dim + 2]));
+    const float rot = atan2f(bf2f(h[t.o_rot]), bf2f(h[t.o_rot + 1]));
+    const float v0 = t.o_vel >= 0 ? bf2f(h[t.o_vel]) : 0.f, v1 = t.o_vel >= 0 ? bf2f(h[t.o_vel + 1]) : 0.f;
+    b[0] = c[0]; b[1] = c[1]; b[2] = c[2]; b[3] = d0; b[4] = d1; b[5] = d2; b[6] = v0; b[7] = v1; b[8] = rot;
+    const float r2 = -rot - 1.5707963267948966f;
+    nb[0] = c[0]; nb[1] = c[1]; nb[2] = c[2]; nb[3] = d1; nb[4] = d0; nb[5] = d2; nb[6] = r2;
 }
 
 }  // namespace md

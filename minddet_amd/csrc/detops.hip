@@ -1048,11 +1048,11 @@ __global__ void centernet_assemble_kernel(const float *__restrict__ top_score, c
 // voxel + pc_range; score/range mask -> score = label = -1, box = 0; heading flipped for the NMS operator
 // (box[:, -1] = -rot - pi/2, :426) and dims swapped in the NMS copy (:430).
 struct CpArgs {
-    int o_reg, o_height, o_dim, o_rot, o_vel, o_hm, ncls, C;
-    int H, W;
-    float score_thr, osf, vx, vy, px, py;
-    float rmin[3], rmax[3];
+    CpTask t;
+    CpGeom g;
+    int C, H, W;
 };
+// the per-cell arithmetic: box_codec.h (cp_score_one, cp_box_one), shared with cphead.hip
 __global__ void centerpoint_decode_kernel(const uint16_t *__restrict__ head, CpArgs a, int total,
                                           float *__restrict__ scores, int *__restrict__ labels,
                                           float *__restrict__ boxes, float *__restrict__ nms_boxes) {
@@ -1061,27 +1061,19 @@ __global__ void centerpoint_decode_kernel(const uint16_t *__restrict__ head, CpA
     const int loc = e % (a.H * a.W);
     const int y = loc / a.W, x = loc % a.W;
     const uint16_t *h = head + (size_t)e * a.C;
-    float best = -FLT_MAX;
-    int lab = 0;
-    for (int c = 0; c < a.ncls; ++c) {  // ArgMaxWithValue: first maximum wins
-        const float v = sigmoid(bf2f(h[a.o_hm + c]));
-        if (v > best) { best = v; lab = c; }
-    }
-    const float xs = ((float)x + bf2f(h[a.o_reg])) * a.osf * a.vx + a.px;
-    const float ys = ((float)y + bf2f(h[a.o_reg + 1])) * a.osf * a.vy + a.py;
-    const float zs = bf2f(h[a.o_height]);
-    const float d0 = expf(bf2f(h[a.o_dim])), d1 = expf(bf2f(h[a.o_dim + 1])), d2 = expf(bf2f(h[a.o_dim + 2]));
-    const float rot = atan2f(bf2f(h[a.o_rot]), bf2f(h[a.o_rot + 1]));
-    const float v0 = a.o_vel >= 0 ? bf2f(h[a.o_vel]) : 0.f, v1 = a.o_vel >= 0 ? bf2f(h[a.o_vel + 1]) : 0.f;
-    const bool in_range = xs >= a.rmin[0] && ys >= a.rmin[1] && zs >= a.rmin[2] && xs <= a.rmax[0] && ys <= a.rmax[1] && zs <= a.rmax[2];
-    const bool ok = best > a.score_thr && in_range;
+    int lab;
+    float c[3];
+    const float sc = cp_score_one(h, a.t, a.g, x, y, lab, c);
     float *b = boxes + (size_t)e * 9;
     float *nb = nms_boxes + (size_t)e * 7;
-    if (ok) {
-        b[0] = xs; b[1] = ys; b[2] = zs; b[3] = d0; b[4] = d1; b[5] = d2; b[6] = v0; b[7] = v1; b[8] = rot;
-        const float r2 = -rot - 1.5707963267948966f;
-        nb[0] = xs; nb[1] = ys; nb[2] = zs; nb[3] = d1; nb[4] = d0; nb[5] = d2; nb[6] = r2;
-        scores[e] = best; labels[e] = lab;
+    if (sc != -1.f) {
+        float bb[9], nn[7];
+        cp_box_one(h, a.t, c, bb, nn);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) b[k] = bb[k];
+#pragma unroll
+        for (int k = 0; k < 7; ++k) nb[k] = nn[k];
+        scores[e] = sc; labels[e] = lab;
     } else {
 #pragma unroll
         for (int k = 0; k < 9; ++k) b[k] = 0.f;
@@ -1542,16 +1534,16 @@ extern "C" int md_centerpoint_decode(MD_AOT_ARGS) {
     g.tensor(0, BF16, 4); g.tensor(1, F32); g.tensor(2, I32); g.tensor(3, F32); g.tensor(4, F32);
     if (int rc = g.rc()) return rc;
     CpArgs a;
-    a.o_reg = at->off_reg; a.o_height = at->off_height; a.o_dim = at->off_dim; a.o_rot = at->off_rot;
-    a.o_vel = at->off_vel; a.o_hm = at->off_hm; a.ncls = at->num_classes;
+    a.t.o_reg = at->off_reg; a.t.o_height = at->off_height; a.t.o_dim = at->off_dim; a.t.o_rot = at->off_rot;
+    a.t.o_vel = at->off_vel; a.t.o_hm = at->off_hm; a.t.ncls = at->num_classes;
     const int B = (int)g.d(0, 0);
     a.H = (int)g.d(0, 1); a.W = (int)g.d(0, 2); a.C = (int)g.d(0, 3);
-    if (a.ncls < 1 || a.o_hm + a.ncls > a.C || a.o_reg + 2 > a.C || a.o_dim + 3 > a.C || a.o_rot + 2 > a.C ||
-        a.o_height + 1 > a.C || a.o_vel + 2 > a.C)
+    if (a.t.ncls < 1 || a.t.o_hm + a.t.ncls > a.C || a.t.o_reg + 2 > a.C || a.t.o_dim + 3 > a.C || a.t.o_rot + 2 > a.C ||
+        a.t.o_height + 1 > a.C || a.t.o_vel + 2 > a.C)
         return MD_ERR_ARG;
-    a.score_thr = at->score_threshold; a.osf = at->out_size_factor; a.vx = at->voxel_size[0]; a.vy = at->voxel_size[1];
-    a.px = at->pc_range[0]; a.py = at->pc_range[1];
-    for (int i = 0; i < 3; ++i) { a.rmin[i] = at->post_center_range[i]; a.rmax[i] = at->post_center_range[3 + i]; }
+    a.g.score_thr = at->score_threshold; a.g.osf = at->out_size_factor; a.g.vx = at->voxel_size[0]; a.g.vy = at->voxel_size[1];
+    a.g.px = at->pc_range[0]; a.g.py = at->pc_range[1];
+    for (int i = 0; i < 3; ++i) { a.g.rmin[i] = at->post_center_range[i]; a.g.rmax[i] = at->post_center_range[3 + i]; }
     const int64_t total = (int64_t)B * a.H * a.W;
     if (g.numel(1) != total || g.numel(2) != total || g.numel(3) != total * 9 || g.numel(4) != total * 7) return MD_ERR_ARG;
     if (total == 0) return MD_OK;

@@ -26,6 +26,7 @@
 
 #include "aot.h"
 #include "rot_geom.h"
+#include "../../include/minddet_hip_cp.h"
 
 #pragma clang fp contract(off)
 
@@ -45,6 +46,24 @@ __global__ void rot_prep_kernel(const float *__restrict__ boxes, int n, float *_
     for (int k = 0; k < ROT_REC; ++k) rec[(size_t)i * ROT_REC + k] = r[k];
 }
 
+// the records of L lists in one launch (md_nms_rotated): grid.y = list; rows at or past the list's count are neither read nor written
+__global__ void rot_prep_batched_kernel(const float *__restrict__ boxes_all, const int *__restrict__ count, int n_max,
+                                        float *__restrict__ rec_all) {
+    const int list = blockIdx.y;
+    const int n = count ? min(count[list], n_max) : n_max;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *boxes = boxes_all + ((size_t)list * n_max + i) * 7;
+    float r[ROT_REC];
+    float b[7];
+#pragma unroll
+    for (int k = 0; k < 7; ++k) b[k] = boxes[k];
+    rot_make_record(b, r);
+    float *rec = rec_all + ((size_t)list * n_max + i) * ROT_REC;
+#pragma unroll
+    for (int k = 0; k < ROT_REC; ++k) rec[k] = r[k];
+}
+
 // linear upper-triangular tile id -> (row block, col block)
 __device__ __forceinline__ void tri_tile(int t, int cb, int &rb, int &cbk) {
     int r = 0;
@@ -55,14 +74,11 @@ __device__ __forceinline__ void tri_tile(int t, int cb, int &rb, int &cbk) {
 
 // MODE 0: IoU = so / fmaxf(sa+sb-so, 1e-8), suppress iff >  thr   (NmsGpu)
 // MODE 1: ovr = so / (sa+sb-so),            suppress iff >= thr   (boxes_iou_nms_cpu)
+// One 64 x 64 tile (row block rb, column block cbk) of one list's suppression mask: the one statement of the per-pair predicate, for
+// the single-list kernel and the batched one below.  rec / mask: the list's own; n: its valid rows; cb: words per mask row.
 template <int MODE>
-__global__ __launch_bounds__(256) void nms_rot_mask_kernel(const float *__restrict__ rec, int n,
-                                                            const float *__restrict__ thr_p,
-                                                            unsigned long long *__restrict__ mask, int cb) {
-    __shared__ float row_rec[TILE * ROT_REC];
-    __shared__ float poly[3 * ROT_PTS * 256];
-    int rb, cbk;
-    tri_tile(blockIdx.x, cb, rb, cbk);
+__device__ __forceinline__ void rot_mask_tile(const float *__restrict__ rec, int n, float thr, unsigned long long *__restrict__ mask,
+                                              int cb, int rb, int cbk, float *row_rec, float *poly) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     for (int e = tid; e < TILE * ROT_REC; e += 256) {
         const int g = rb * TILE + e / ROT_REC;
@@ -72,7 +88,6 @@ __global__ __launch_bounds__(256) void nms_rot_mask_kernel(const float *__restri
     float col[ROT_REC];
 #pragma unroll
     for (int k = 0; k < ROT_REC; ++k) col[k] = gc < n ? rec[(size_t)gc * ROT_REC + k] : 0.f;
-    const float thr = *thr_p;
     __syncthreads();
     float *scratch = poly + tid;
     for (int rr = wave * 16; rr < wave * 16 + 16; ++rr) {
@@ -93,6 +108,35 @@ __global__ __launch_bounds__(256) void nms_rot_mask_kernel(const float *__restri
         const unsigned long long w = __ballot(pred);
         if (lane == 0) mask[(size_t)gr * cb + cbk] = w;
     }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void nms_rot_mask_kernel(const float *__restrict__ rec, int n,
+                                                            const float *__restrict__ thr_p,
+                                                            unsigned long long *__restrict__ mask, int cb) {
+    __shared__ float row_rec[TILE * ROT_REC];
+    __shared__ float poly[3 * ROT_PTS * 256];
+    int rb, cbk;
+    tri_tile(blockIdx.x, cb, rb, cbk);
+    rot_mask_tile<MODE>(rec, n, *thr_p, mask, cb, rb, cbk, row_rec, poly);
+}
+
+// L lists in one launch (md_nms_rotated): grid.y = list, grid.x = the upper-triangular tiles of the full cb x cb grid.  A tile whose
+// row or column block lies at or past the list's own ceil(n / 64) returns at once: a short list costs its own tiles only.
+template <int MODE>
+__global__ __launch_bounds__(256) void nms_rot_mask_batched_kernel(const float *__restrict__ rec_all, const int *__restrict__ count,
+                                                                    int n_max, float thr,
+                                                                    unsigned long long *__restrict__ mask_all, int cb) {
+    __shared__ float row_rec[TILE * ROT_REC];
+    __shared__ float poly[3 * ROT_PTS * 256];
+    const int list = blockIdx.y;
+    const int n = count ? min(count[list], n_max) : n_max;
+    const int nb = (n + TILE - 1) / TILE;
+    int rb, cbk;
+    tri_tile(blockIdx.x, cb, rb, cbk);
+    if (rb >= nb || cbk >= nb) return;  // block-uniform
+    rot_mask_tile<MODE>(rec_all + (size_t)list * n_max * ROT_REC, n, thr, mask_all + (size_t)list * n_max * cb, cb, rb, cbk, row_rec,
+                        poly);
 }
 
 // ------------------------------------------------------------------ axis-aligned variants
@@ -312,8 +356,8 @@ __device__ __forceinline__ unsigned long long wave_or64(unsigned long long v) {
 }
 
 // One workgroup per list.  mask rows are valid for column blocks >= the row's block.
-// dead_area: optional per-box area array (stride in floats) -- boxes with area == 0 are
-// removed up front without suppressing anything (iou-bev-nms-org.cpp:250-256).
+// dead_area: optional per-box area array (stride in floats; dead_list_stride floats from one list's to the next's) -- boxes with
+// area == 0 are removed up front without suppressing anything (iou-bev-nms-org.cpp:250-256).
 template <typename KeepT>
 __global__ __launch_bounds__(256) void nms_scan_kernel(const unsigned long long *__restrict__ mask_all,
                                                         const int *__restrict__ count, int n_max, int cb,
@@ -322,7 +366,7 @@ __global__ __launch_bounds__(256) void nms_scan_kernel(const unsigned long long 
                                                         int *__restrict__ num_all,
                                                         unsigned char *__restrict__ keepmask_all, int n_limit = 0x7fffffff,
                                                         const int *__restrict__ gate = nullptr,
-                                                        int *__restrict__ need_full = nullptr) {
+                                                        int *__restrict__ need_full = nullptr, size_t dead_list_stride = 0) {
     // n_limit / gate / need_full: the quota prefix pass of md_nms_aligned (see there).  A prefix pass looks at the first n_limit
     // boxes only and raises need_full[list] when they did not fill the quota although the list goes on.
     // The removed-bits of a column block are taken when the scan REACHES the block: the OR over the rows kept so far of their words for
@@ -354,7 +398,7 @@ __global__ __launch_bounds__(256) void nms_scan_kernel(const unsigned long long 
         bool dead = r >= n;
         if (wave == 0 && r < n) {   // requested together with the kept rows' words below
             diag = mask[(size_t)r * cb + blk];
-            if (dead_area && dead_area[(size_t)r * dead_stride] == 0.f) dead = true;
+            if (dead_area && dead_area[(size_t)list * dead_list_stride + (size_t)r * dead_stride] == 0.f) dead = true;
         }
         unsigned long long v = 0ull;
         for (int k = tid; k < total; k += 256) {
@@ -611,6 +655,43 @@ extern "C" int NmsNormalGpu(MD_AOT_ARGS) {
     hipLaunchKernelGGL((nms_scan_kernel<long long>), dim3(1), dim3(256), scan_lds(cb), s, mask, (const int *)nullptr,
                        (int)n, cb, (const float *)nullptr, 0, 0, a.ptr<long long>(2), a.ptr<int>(3),
                        (unsigned char *)nullptr);
+    return launched();
+}
+
+// include/minddet_hip_cp.h.  in: boxes[L,N,7] f32 (or [N,7]), count[L] i32 | NULL ; out: keep_idx[L,N] i32, num[L] i32 ; [workspace].
+// extra: md_nms_rotated_attrs (required)
+extern "C" int md_nms_rotated(MD_AOT_ARGS) {
+    Args a(MD_ARGS, 4, 5);
+    const md_nms_rotated_attrs *at = a.attrs<md_nms_rotated_attrs>(extra);
+    a.tensor(0, F32, 2, 3);
+    a.optional(1, I32, 1); a.tensor(2, I32, 1, 2); a.tensor(3, I32, 1);
+    const int64_t L = a.rank(0) == 3 ? a.d(0, 0) : 1, n = a.d(0, -2);
+    a.require(a.d(0, -1) == 7 && L >= 0 && n >= 0);
+    a.require(n <= (1 << 16) && L <= 65535, MD_ERR_SIZE);
+    a.require((!a.given(1) || a.numel(1) == L) && a.numel(2) == L * n && a.numel(3) == L);
+    if (int rc = a.rc()) return rc;
+    if (at->mode < 0 || at->mode > 1 || at->max_output < 0) return MD_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    if (L == 0) return MD_OK;
+    if (!a.have({3})) return MD_ERR_ARG;
+    if (n == 0) return hipMemsetAsync(params[3], 0, sizeof(int) * L, s) == hipSuccess ? MD_OK : MD_ERR_HIP;
+    if (!a.have({0, 2})) return MD_ERR_ARG;
+    const int cb = (int)((n + TILE - 1) / TILE);
+    const size_t mask_bytes = (size_t)L * n * cb * 8, rec_bytes = (size_t)L * n * ROT_REC * 4;
+    Scratch ws;
+    if (int rc = ws.acquire(mask_bytes + rec_bytes, a, 4, s)) return rc;
+    unsigned long long *mask = (unsigned long long *)ws.ptr;     // (the 8-byte words first: rec_bytes is a multiple of 4 only)
+    float *rec = (float *)((char *)ws.ptr + mask_bytes);
+    const int *count = a.given(1) ? a.ptr<const int>(1) : nullptr;
+    hipLaunchKernelGGL(rot_prep_batched_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)L), dim3(256), 0, s,
+                       a.ptr<const float>(0), count, (int)n, rec);
+    auto mk = at->mode == 0 ? nms_rot_mask_batched_kernel<0> : nms_rot_mask_batched_kernel<1>;
+    hipLaunchKernelGGL(mk, dim3(cb * (cb + 1) / 2, (unsigned)L), dim3(256), 0, s, (const float *)rec, count, (int)n,
+                       at->iou_threshold, mask, cb);
+    hipLaunchKernelGGL((nms_scan_kernel<int>), dim3((unsigned)L), dim3(256), scan_lds(cb), s, (const unsigned long long *)mask, count,
+                       (int)n, cb, at->mode == 1 ? (const float *)(rec + 14) : (const float *)nullptr, ROT_REC, at->max_output,
+                       a.ptr<int>(2), a.ptr<int>(3), (unsigned char *)nullptr, 0x7fffffff, (const int *)nullptr, (int *)nullptr,
+                       (size_t)n * ROT_REC);
     return launched();
 }
 

@@ -671,6 +671,140 @@ class CenterHeadPost:
         return out
 
 
+class _NmsRotatedAttrs(ctypes.Structure):
+    _fields_ = [("iou_threshold", ctypes.c_float), ("mode", ctypes.c_int32), ("max_output", ctypes.c_int32)]
+
+
+NMS_ROT_GPU = 0       # NmsGpu: suppress iff so / max(sa + sb - so, 1e-8) > thr
+NMS_ROT_CPU = 1       # boxes_iou_nms_cpu: suppress iff so / (sa + sb - so) >= thr; zero-area boxes are dropped up front
+
+
+def nms_rotated(boxes, thresh, mode, count=None, max_output=0, workspace=None):
+    """Greedy rotated-BEV NMS over score-sorted boxes [N,7] or L lists [L,N,7] in one call (md_nms_rotated, include/minddet_hip_cp.h);
+    count [L] int32: the valid leading rows per list (None: all).  Returns (keep_idx i32 zero-padded, num i32 [L])."""
+    b = _f32c(boxes)
+    batched = b.dim() == 3
+    L, n = (b.shape[0], b.shape[1]) if batched else (1, b.shape[0])
+    dev = b.device
+    idx = torch.empty((L, n) if batched else (n,), dtype=torch.int32, device=dev)
+    num = torch.empty((L,), dtype=torch.int32, device=dev)
+    if count is not None:
+        count = count.to(device=dev, dtype=torch.int32).reshape(L).contiguous()
+    params = [b, count, idx, num]
+    if workspace is None and L * n > 0:
+        # record + mask scratch from torch's caching allocator (never blocks), as nms_aligned does
+        workspace = torch.empty((L * n * (20 * 4 + (n + 63) // 64 * 8),), dtype=torch.uint8, device=dev)
+    if workspace is not None:
+        params.append(workspace)
+    _lib.call("md_nms_rotated", params, extra=_NmsRotatedAttrs(float(thresh), int(mode), int(max_output)))
+    return idx, num
+
+
+CP_MAX_TASKS = 8
+
+
+class _CPTaskAttrs(ctypes.Structure):
+    _fields_ = [("off_reg", ctypes.c_int32), ("off_height", ctypes.c_int32), ("off_dim", ctypes.c_int32), ("off_rot", ctypes.c_int32),
+                ("off_vel", ctypes.c_int32), ("off_hm", ctypes.c_int32), ("num_classes", ctypes.c_int32), ("class_base", ctypes.c_int32)]
+
+
+class _CPHeadAttrs(ctypes.Structure):
+    _fields_ = [("num_tasks", ctypes.c_int32), ("task", _CPTaskAttrs * CP_MAX_TASKS), ("score_threshold", ctypes.c_float),
+                ("out_size_factor", ctypes.c_float), ("voxel_size", ctypes.c_float * 2), ("pc_range", ctypes.c_float * 2),
+                ("post_center_range", ctypes.c_float * 6), ("max_per_task", ctypes.c_int32)]
+
+
+def cp_head_attrs(task_offsets, num_classes, test_cfg):
+    """md_cp_head_attrs of a CenterHead (per task {head: first channel}, per task num_class) under a test config"""
+    if not 1 <= len(task_offsets) <= CP_MAX_TASKS or len(task_offsets) != len(num_classes):
+        raise ValueError(f"cp_head_attrs: 1 .. {CP_MAX_TASKS} tasks, one num_class each; got {len(task_offsets)} / {len(num_classes)}")
+    at = _CPHeadAttrs()
+    at.num_tasks = len(task_offsets)
+    base = 0
+    for t, (off, nc) in enumerate(zip(task_offsets, num_classes)):
+        a = at.task[t]
+        a.off_reg, a.off_height, a.off_dim, a.off_rot = int(off["reg"]), int(off["height"]), int(off["dim"]), int(off["rot"])
+        a.off_vel, a.off_hm, a.num_classes, a.class_base = int(off.get("vel", -1)), int(off["hm"]), int(nc), base
+        base += int(nc)
+    at.score_threshold, at.out_size_factor = float(test_cfg["score_threshold"]), float(test_cfg["out_size_factor"])
+    for i in range(2):
+        at.voxel_size[i], at.pc_range[i] = float(test_cfg["voxel_size"][i]), float(test_cfg["pc_range"][i])
+    for i in range(6):
+        at.post_center_range[i] = float(test_cfg["post_center_limit_range"][i])
+    at.max_per_task = int(test_cfg["nms"]["nms_post_max_size"])
+    return at
+
+
+def cp_scores(head, at):
+    """head [B,H,W,C] bf16 -> scores [B,T,H W] f32: per cell and task the first maximum of the class sigmoids, -1 where the score or
+    the range mask fails (md_cp_scores)"""
+    B, H, W, _ = head.shape
+    scores = torch.empty((B, at.num_tasks, H * W), dtype=torch.float32, device=head.device)
+    _lib.call("md_cp_scores", [head, scores], extra=at)
+    return scores
+
+
+def cp_decode_selected(head, idx, cnt, at):
+    """idx [B,T,k] i32 (cell per selected row), cnt [B,T] i32 -> (boxes [B,T,k,9], nms_boxes [B,T,k,7], labels [B,T,k] i32); rows past
+    cnt are zero (md_cp_decode_selected)"""
+    B, T, k = idx.shape
+    dev = head.device
+    boxes = torch.empty((B, T, k, 9), dtype=torch.float32, device=dev)
+    nms_boxes = torch.empty((B, T, k, 7), dtype=torch.float32, device=dev)
+    labels = torch.empty((B, T, k), dtype=torch.int32, device=dev)
+    _lib.call("md_cp_decode_selected", [head, idx, cnt, boxes, nms_boxes, labels], extra=at)
+    return boxes, nms_boxes, labels
+
+
+def cp_pack(boxes, sel_scores, labels, keep_idx, num, cnt, at):
+    """-> (dets [B, T max_per_task, 11] f32, count [B] i32): per task the first min(num, cnt, max_per_task) kept rows whose score is
+    > 0, tasks in order, label + class_base (md_cp_pack = graphs.merge_center_tasks on the per-task outputs)"""
+    B, T, _ = sel_scores.shape
+    dets = torch.empty((B, T * int(at.max_per_task), 11), dtype=torch.float32, device=boxes.device)
+    count = torch.empty((B,), dtype=torch.int32, device=boxes.device)
+    _lib.call("md_cp_pack", [boxes, sel_scores, labels, keep_idx, num, cnt, dets, count], extra=at)
+    return dets, count
+
+
+class CenterHeadPostBatched:
+    """CenterHead.predict + post_processing (center_head.py:273-463) and the task merge of tools_ms/eval.py:84-111 for every task and
+    every sample of the batch, seven launches and no host read: cp_scores over every cell -> one segmented top-k (B T segments,
+    nms_pre_max_size each, the masked cells' -1 excluded) -> cp_decode_selected on the selected cells only -> nms_rotated (the
+    boxes_iou_nms_cpu rule, count-aware, quota nms_post_max_size: three launches) -> cp_pack.  The result equals CenterHeadPost per
+    task + graphs.merge_center_tasks bit for bit."""
+
+    def __init__(self, task_offsets, num_classes, test_cfg):
+        self.cfg = test_cfg
+        self.at = cp_head_attrs(task_offsets, num_classes, test_cfg)
+        self.T = len(num_classes)
+        self.pre, self.post = int(test_cfg["nms"]["nms_pre_max_size"]), int(test_cfg["nms"]["nms_post_max_size"])
+        self.iou_thr = float(test_cfg["nms"]["nms_iou_threshold"])
+        self._segments = {}
+
+    def segments(self, B, n, device):
+        """the [B T + 1] int32 table 0, n, 2 n, ... of the top-k: a device constant per batch shape, built on first use"""
+        key = (int(B), int(n), str(device))
+        if key not in self._segments:
+            self._segments[key] = torch.arange(0, (B * self.T + 1) * n, n, dtype=torch.int32, device=device)
+        return self._segments[key]
+
+    def __call__(self, head, return_aux=False):
+        """head [B,H,W,C] bf16 -> (dets [B, T nms_post_max_size, 11] f32, count [B] i32); rows past count are zero"""
+        B, H, W, _ = head.shape
+        n, T = H * W, self.T
+        scores = cp_scores(head, self.at)
+        k = min(self.pre, n)
+        vals, idx, cnt = topk_segmented(scores, self.segments(B, n, head.device), k, min_score=-1.0, max_segment=n)
+        vals, idx, cnt = vals.view(B, T, k), idx.view(B, T, k), cnt.view(B, T)
+        boxes, nms_boxes, labels = cp_decode_selected(head, idx, cnt, self.at)
+        keep, num = nms_rotated(nms_boxes.view(B * T, k, 7), self.iou_thr, NMS_ROT_CPU, count=cnt, max_output=self.post)
+        dets, count = cp_pack(boxes, vals, labels, keep.view(B, T, k), num.view(B, T), cnt, self.at)
+        if return_aux:
+            return (dets, count), dict(scores=scores, topk_values=vals, topk_idx=idx, topk_cnt=cnt, boxes=boxes, nms_boxes=nms_boxes,
+                                       labels=labels, keep_idx=keep.view(B, T, k), num=num.view(B, T))
+        return dets, count
+
+
 # ----------------------------------------------------------------------------- PointPillars host post-process
 def _just_below(x):
     """Largest float32 strictly below x: `score >= x` (predict.py:30) expressed as `score > just_below(x)`."""

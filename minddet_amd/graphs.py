@@ -834,6 +834,9 @@ class RPN(Module):
 # ----------------------------------------------------------------------------- CenterPoint head + detector
 SEPHEAD_GROUPED = os.environ.get("MD_SEPHEAD_GROUPED", "1") != "0"   # A/B knob: 0 = 36 md_conv2d launches for the SepHead final convs
 SEPHEAD_ORDER = ("reg", "height", "dim", "rot", "vel", "hm")         # the dict order of SepHead.construct (center_head.py:85-93)
+# post-processing of every task and sample as ONE chain of seven launches (det_ops.CenterHeadPostBatched; bit-identical): MD_CP_POST=1.
+# The default stays one CenterHeadPost per task + merge_center_tasks: the production-replay tests pin that pass's operator set
+CP_POST = os.environ.get("MD_CP_POST", "0") == "1"
 
 
 @HEADS.register_module
@@ -929,10 +932,12 @@ class CenterHead(Module):
 class PointPillars(Module):
     """det3d's PointPillars detector with a CenterHead (centerpoint/det3d_ms/models/detectors/point_pillars.py; the nuScenes
     CenterPoint-PP config): neck (graphs.RPN) -> bbox_head (CenterHead) -> one CenterHeadPost per task -> the task merge of
-    tools_ms/eval.py:84-111.  The pillar encoder (reader) and the scatter (backbone) are out of scope: forward() takes the scattered
-    pseudo-image [B, H, W, 64] bf16."""
+    tools_ms/eval.py:84-111 (merge_center_tasks); cp_post=True (default: the MD_CP_POST setting) and return_aux=False: the
+    post-processing of every task and the merge as one chain (det_ops.CenterHeadPostBatched), the same result.  The pillar encoder (reader) and the scatter
+    (backbone) are out of scope: forward() takes the scattered pseudo-image [B, H, W, 64] bf16."""
 
-    def __init__(self, neck, bbox_head, reader=None, backbone=None, train_cfg=None, test_cfg=None, pretrained=None, seed=7):
+    def __init__(self, neck, bbox_head, reader=None, backbone=None, train_cfg=None, test_cfg=None, pretrained=None, seed=7,
+                 cp_post=None):
         if reader is not None or backbone is not None:
             raise ValueError("PointPillars: the pillar encoder (`reader`) and the scatter (`backbone`) are not part of this build; "
                              "drop them from the config and feed the scattered pseudo-image [B, H, W, 64] bf16 to forward()")
@@ -941,15 +946,24 @@ class PointPillars(Module):
         self.bbox_head = build_head(dict(bbox_head, seed=seed + 1) if isinstance(bbox_head, dict) and "seed" not in bbox_head else bbox_head)
         self.test_cfg = test_cfg
         self.max_per_task = int(test_cfg["nms"]["nms_post_max_size"])
+        self.cp_post = CP_POST if cp_post is None else bool(cp_post)
+        self._post_batched = None
 
     def children(self):
         return [self.neck, self.bbox_head]
+
+    def post_batched(self):
+        if self._post_batched is None:
+            self._post_batched = det_ops.CenterHeadPostBatched(self.bbox_head.task_offsets(), self.bbox_head.num_classes, self.test_cfg)
+        return self._post_batched
 
     def forward(self, pseudo_image, return_aux=False):
         """pseudo_image [B, H, W, 64] bf16 -> (dets [B, tasks x nms_post_max_size, 11] f32, count [B] i32): per row the 9 box values
         (x, y, z, dx, dy, dz, vx, vy, rot), score, label over all tasks; rows past count are zero."""
         feat = self.neck(pseudo_image)
         head, shared = self.bbox_head(feat)
+        if self.cp_post and not return_aux:
+            return self.post_batched()(head)
         posts = [det_ops.CenterHeadPost(off, nc, self.test_cfg)
                  for off, nc in zip(self.bbox_head.task_offsets(), self.bbox_head.num_classes)]
         outs = [post(head) for post in posts]

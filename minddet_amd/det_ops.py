@@ -11,6 +11,8 @@ read the same (paths relative to /root/reference/minddet/models):
   iou_jit                 pointpillars/src/core/box_np_ops.py:639-679
   nms_jit / apply_nms     pointpillars/src/core/nms.py:7-41,85-112     (via nms_aligned)
   circle_nms              centerpoint/det3d_ms/core/utils/circle_nms_jit.py:6-36
+  cp_assign_targets, CenterPointTargets
+                          centerpoint/det3d_ms/datasets/pipelines/preprocess.py:285-521 (AssignLabel, for a batch)
 
 All tensors are torch CUDA tensors; work is enqueued on the current stream; nothing here
 synchronises.  There is no CPU path.
@@ -1237,3 +1239,77 @@ def anchors_mask_batched(coors, voxel_num, grid_size_xy, anchors_bv, voxel_size,
     ws = torch.empty((max(B, 1) * at.grid_x * at.grid_y * 4,), dtype=torch.uint8, device=dev)
     _lib.call("md_pp_anchor_mask", [coors, voxel_num, bv, mask, area, ws], extra=at)
     return (mask, area) if with_area else mask
+
+
+# ----------------------------------------------------------------------------- CenterPoint training targets (csrc/cptargets.hip)
+class _CPTargetsAttrs(ctypes.Structure):
+    _fields_ = [("num_tasks", ctypes.c_int32), ("num_classes", ctypes.c_int32 * 8), ("voxel_size", ctypes.c_float * 2),
+                ("pc_range", ctypes.c_float * 2), ("out_size_factor", ctypes.c_int32), ("gaussian_overlap", ctypes.c_float),
+                ("min_radius", ctypes.c_int32)]
+
+
+def _task_num_classes(tasks):
+    """per task num_class, from the config's task dicts (or plain integers)"""
+    return [int(t if isinstance(t, int) else t["num_class"]) for t in tasks]
+
+
+def cp_assign_targets(gt_boxes, gt_classes, *, tasks, voxel_size, pc_range, out_size_factor, gaussian_overlap, min_radius, max_objs,
+                      feature_map_size, out=None):
+    """AssignLabel.__call__ (preprocess.py:297-521) for a batch on the device (md_cp_assign_targets, include/minddet_hip_cptargets.h):
+    gt_boxes [B,G,9] f32 (x, y, z, w, l, h, vx, vy, rot), gt_classes [B,G] (global 1-based class; 0 or an id past the last class: a
+    padding row), G <= max_objs -> dict with the reference's keys: hm [B,T,C,H,W] f32, anno_box [B,T,M,10] f32, ind [B,T,M] i32,
+    mask [B,T,M] u8, cat [B,T,M] i32, gt_boxes_and_cls [B,M,10] f32.  feature_map_size = (W, H) as in the reference; every element
+    of every output is written by the op, so `out` (a dict of such tensors from an earlier call) can be reused without clearing."""
+    ncs = _task_num_classes(tasks)
+    if not 1 <= len(ncs) <= CP_MAX_TASKS:
+        raise ValueError(f"cp_assign_targets: 1 .. {CP_MAX_TASKS} tasks, got {len(ncs)}")
+    at = _CPTargetsAttrs()
+    at.num_tasks = len(ncs)
+    for t, nc in enumerate(ncs):
+        at.num_classes[t] = nc
+    for i in range(2):
+        at.voxel_size[i], at.pc_range[i] = float(voxel_size[i]), float(pc_range[i])
+    at.out_size_factor, at.gaussian_overlap, at.min_radius = int(out_size_factor), float(gaussian_overlap), int(min_radius)
+    g = _f32c(gt_boxes)
+    dev = g.device
+    cls = gt_classes.to(device=dev, dtype=torch.int32).contiguous()
+    B, G = g.shape[0], g.shape[1]
+    T, C, M = len(ncs), max(ncs), int(max_objs)
+    W, H = int(feature_map_size[0]), int(feature_map_size[1])
+    want = dict(hm=((B, T, C, H, W), torch.float32), anno_box=((B, T, M, 10), torch.float32), ind=((B, T, M), torch.int32),
+                mask=((B, T, M), torch.uint8), cat=((B, T, M), torch.int32), gt_boxes_and_cls=((B, M, 10), torch.float32))
+    if out is None:
+        out = {k: torch.empty(shp, dtype=dt, device=dev) for k, (shp, dt) in want.items()}
+    for k, (shp, dt) in want.items():
+        if tuple(out[k].shape) != shp or out[k].dtype != dt:
+            raise ValueError(f"cp_assign_targets: out[{k!r}] has to be {dt} of shape {shp}")
+    ws = torch.empty((max(B * T * (G + 1), 1) * 16,), dtype=torch.uint8, device=dev)
+    _lib.call("md_cp_assign_targets", [g, cls, out["hm"], out["anno_box"], out["ind"], out["mask"], out["cat"], out["gt_boxes_and_cls"], ws],
+              extra=at)
+    return out
+
+
+class CenterPointTargets:
+    """The AssignLabel step of a config: train_cfg["assigner"] (target_assigner.tasks, out_size_factor, gaussian_overlap, max_objs,
+    min_radius -- the reference's key names) plus the voxel generator's range and voxel size.  __call__(gt_boxes [B,G,9],
+    gt_classes [B,G]) -> the dict of cp_assign_targets."""
+
+    def __init__(self, assigner, voxel_generator):
+        self.tasks = [dict(t) for t in assigner["target_assigner"]["tasks"]]
+        self.out_size_factor = int(assigner["out_size_factor"])
+        self.gaussian_overlap = float(assigner["gaussian_overlap"])
+        self.max_objs, self.min_radius = int(assigner["max_objs"]), int(assigner["min_radius"])
+        rg, vs = voxel_generator["range"], voxel_generator["voxel_size"]
+        self.pc_range, self.voxel_size = (float(rg[0]), float(rg[1])), (float(vs[0]), float(vs[1]))
+        # grid_size = round((range[3:] - range[:3]) / voxel_size), feature_map_size = grid_size[:2] // out_size_factor (preprocess.py:313-318)
+        grid = [int(np.round((np.float32(rg[3 + i]) - np.float32(rg[i])) / np.float32(vs[i]))) for i in range(2)]
+        self.feature_map_size = (grid[0] // self.out_size_factor, grid[1] // self.out_size_factor)
+
+    @classmethod
+    def from_config(cls, cfg):
+        return cls(cfg.train_cfg["assigner"], cfg.model["voxel_generator"])
+
+    def __call__(self, gt_boxes, gt_classes):
+        return cp_assign_targets(gt_boxes, gt_classes, tasks=self.tasks, voxel_size=self.voxel_size, pc_range=self.pc_range,
+                                 out_size_factor=self.out_size_factor, gaussian_overlap=self.gaussian_overlap, min_radius=self.min_radius,
+                                 max_objs=self.max_objs, feature_map_size=self.feature_map_size)

@@ -2,7 +2,8 @@
 # net and the scatter of the reference model in front of the neck and the centre-based head of centerpoint_pp_nusc.py.
 # forward(points [N, 5] f32, offsets [B + 1] i32) -> (dets, count); the whole path runs on the device.
 # This is centerpoint_pp_nusc_points.py plus the training-target assigner of the reference's training configuration (AssignLabel:
-# Gaussian overlap 0.1, at most 500 objects per sample, radius at least 2 cells), which det_ops.CenterPointTargets builds on the device.
+# Gaussian overlap 0.1, at most 500 objects per sample, radius at least 2 cells), which det_ops.CenterPointTargets builds on the device,
+# and the loss settings of its CenterHead (train_cfg["loss"]), which det_ops.CenterPointLoss reads.
 
 tasks = [
     dict(num_class=1, class_names=["car"]),
@@ -49,6 +50,9 @@ train_cfg = dict(
         max_objs=500,
         min_radius=2,
     ),
+    # CenterHead.loss: the loc-loss weight and one weight per anno_box column (reg 2, height, dim 3, vel 2, rot 2), the reference
+    # configuration's values; det_ops.CenterPointLoss.from_config reads them
+    loss=dict(weight=0.25, code_weights=[1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 0.2, 0.2, 1.0, 1.0]),
 )
 
 voxel_size = [0.2, 0.2]

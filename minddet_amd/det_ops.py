@@ -13,6 +13,9 @@ read the same (paths relative to /root/reference/minddet/models):
   circle_nms              centerpoint/det3d_ms/core/utils/circle_nms_jit.py:6-36
   cp_assign_targets, CenterPointTargets
                           centerpoint/det3d_ms/datasets/pipelines/preprocess.py:285-521 (AssignLabel, for a batch)
+  cp_loss, CenterPointLoss, center_point_loss
+                          centerpoint/det3d_ms/models/bbox_heads/center_head.py:208-271 (CenterHead.loss) with
+                          centerpoint/det3d_ms/models/losses/centernet_loss.py:22-82 (FastFocalLoss, RegLoss)
 
 All tensors are torch CUDA tensors; work is enqueued on the current stream; nothing here
 synchronises.  There is no CPU path.
@@ -1313,3 +1316,113 @@ class CenterPointTargets:
         return cp_assign_targets(gt_boxes, gt_classes, tasks=self.tasks, voxel_size=self.voxel_size, pc_range=self.pc_range,
                                  out_size_factor=self.out_size_factor, gaussian_overlap=self.gaussian_overlap, min_radius=self.min_radius,
                                  max_objs=self.max_objs, feature_map_size=self.feature_map_size)
+
+
+# ----------------------------------------------------------------------------- CenterPoint training loss (csrc/cploss.hip)
+CP_LOSS_STRIP = 64      # MD_CP_LOSS_STRIP: cells per workgroup of the dense pass (the workspace formula)
+
+
+class _CPLossAttrs(ctypes.Structure):
+    _fields_ = [("num_tasks", ctypes.c_int32), ("task", _CPTaskAttrs * CP_MAX_TASKS), ("weight", ctypes.c_float),
+                ("code_weights", ctypes.c_float * 10)]
+
+
+def cp_loss_attrs(task_offsets, num_classes, weight, code_weights):
+    """md_cp_loss_attrs of a CenterHead (per task {head: first channel}, per task num_class), the loc-loss weight and the code weights
+    in the order of anno_box (reg 2, height 1, dim 3, vel 2, rot 2; 8 values for heads without vel: the last two are then unused)"""
+    if not 1 <= len(task_offsets) <= CP_MAX_TASKS or len(task_offsets) != len(num_classes):
+        raise ValueError(f"cp_loss_attrs: 1 .. {CP_MAX_TASKS} tasks, one num_class each; got {len(task_offsets)} / {len(num_classes)}")
+    cw = [float(v) for v in code_weights]
+    if len(cw) not in (8, 10) or (len(cw) == 8 and any("vel" in off for off in task_offsets)):
+        raise ValueError(f"cp_loss_attrs: 10 code weights (8 for heads without vel), got {len(cw)}")
+    at = _CPLossAttrs()
+    at.num_tasks = len(task_offsets)
+    for t, (off, nc) in enumerate(zip(task_offsets, num_classes)):
+        a = at.task[t]
+        a.off_reg, a.off_height, a.off_dim, a.off_rot = int(off["reg"]), int(off["height"]), int(off["dim"]), int(off["rot"])
+        a.off_vel, a.off_hm, a.num_classes, a.class_base = int(off.get("vel", -1)), int(off["hm"]), int(nc), 0
+    at.weight = float(weight)
+    for j, v in enumerate(cw):
+        at.code_weights[j] = v
+    return at
+
+
+def cp_loss_workspace_bytes(B, T, H, W):
+    return 8 * B * T * (12 + (H * W + CP_LOSS_STRIP - 1) // CP_LOSS_STRIP)
+
+
+def cp_loss(head, targets, at, grad=False, out=None):
+    """CenterHead.loss (center_head.py:208-271, FastFocalLoss + RegLoss per task) on the device (md_cp_loss / md_cp_loss_grad,
+    include/minddet_hip_cploss.h): head [B,H,W,Cp] bf16 raw logits in the layout of CenterHead.task_offsets(), targets = the dict of
+    cp_assign_targets (hm, anno_box, ind, mask, cat) -> dict with total [1] f32, parts [T,12] f32 (per task hm_loss, loc_loss,
+    box_loss[10]), num_pos [T] f32 and, with grad=True, grad [B,H,W,Cp] f32 = d total / d head.  Every element of every output is
+    written, so `out` (such a dict from an earlier call) can be reused without clearing.  A slot whose ind or cat is out of range is
+    skipped as if masked."""
+    if head.dtype != torch.bfloat16 or head.dim() != 4:
+        raise ValueError("cp_loss: head has to be [B,H,W,Cp] bfloat16")
+    head = head.contiguous()
+    dev = head.device
+    B, H, W, _ = head.shape
+    T = int(at.num_tasks)
+    want = dict(total=((1,), torch.float32), parts=((T, 12), torch.float32), num_pos=((T,), torch.float32))
+    if grad:
+        want["grad"] = (tuple(head.shape), torch.float32)
+    if out is None:
+        out = {k: torch.empty(shp, dtype=dt, device=dev) for k, (shp, dt) in want.items()}
+    for k, (shp, dt) in want.items():
+        if tuple(out[k].shape) != shp or out[k].dtype != dt:
+            raise ValueError(f"cp_loss: out[{k!r}] has to be {dt} of shape {shp}")
+    ws = torch.empty((cp_loss_workspace_bytes(B, T, H, W),), dtype=torch.uint8, device=dev)
+    ops = [head, targets["hm"], targets["anno_box"], targets["ind"], targets["mask"], targets["cat"], out["parts"], out["num_pos"],
+           out["total"]]
+    if grad:
+        _lib.call("md_cp_loss_grad", ops + [out["grad"], ws], extra=at)
+    else:
+        _lib.call("md_cp_loss", ops + [ws], extra=at)
+    return out
+
+
+class CenterPointLoss:
+    """The loss of a CenterHead: its channel layout plus the loc-loss weight and the code weights (the reference's CenterHead
+    arguments `weight` and `code_weights`).  __call__(head, targets, grad=False) -> the dict of cp_loss."""
+
+    def __init__(self, task_offsets, num_classes, weight=0.25, code_weights=(1.0,) * 10):
+        self.weight, self.code_weights = float(weight), [float(v) for v in code_weights]
+        self.num_classes = [int(n) for n in num_classes]
+        self.at = cp_loss_attrs(task_offsets, self.num_classes, self.weight, self.code_weights)
+
+    @classmethod
+    def from_head(cls, center_head, weight=None, code_weights=None):
+        """weight / code_weights None: the values the head was built with"""
+        weight = center_head.weight if weight is None else weight
+        code_weights = center_head.code_weights if code_weights is None else code_weights
+        return cls(center_head.task_offsets(), center_head.num_classes, weight, code_weights)
+
+    @classmethod
+    def from_config(cls, cfg, center_head):
+        loss = cfg.train_cfg["loss"]
+        return cls.from_head(center_head, loss["weight"], loss["code_weights"])
+
+    def __call__(self, head, targets, grad=False, out=None):
+        return cp_loss(head, targets, self.at, grad=grad, out=out)
+
+
+class _CenterPointLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, head, targets, loss):
+        out = cp_loss(head.detach(), targets, loss.at, grad=True)
+        ctx.save_for_backward(out["grad"])
+        ctx.head_dtype = head.dtype
+        ctx.mark_non_differentiable(out["parts"], out["num_pos"])
+        return out["total"], out["parts"], out["num_pos"]
+
+    @staticmethod
+    def backward(ctx, g_total, g_parts, g_num_pos):
+        (grad,) = ctx.saved_tensors
+        return (g_total.to(torch.float32) * grad).to(ctx.head_dtype), None, None
+
+
+def center_point_loss(head, targets, loss):
+    """differentiable form: -> (total [1] f32, parts [T,12], num_pos [T]); the forward runs md_cp_loss_grad once, the backward returns
+    grad_output x (d total / d head) in the head's dtype.  parts and num_pos carry no gradient."""
+    return _CenterPointLossFn.apply(head, targets, loss)

@@ -860,6 +860,10 @@ class CenterHead(Module):
         self.in_channels, self.share = int(in_channels), int(share_conv_channel)
         self.num_classes = [int(t.get("num_class", len(t["class_names"]))) for t in tasks]
         self.class_names = [list(t["class_names"]) for t in tasks]
+        # the loss settings of center_head.py:124-125: the loc-loss weight and one weight per anno_box column (default: all 1)
+        self.weight = float(weight)
+        self.code_weights = [float(v) for v in code_weights] if code_weights else [1.0] * (10 if "vel" in common_heads else 8)
+        self._loss = None
         self.shared_conv = ConvModule(init, self.in_channels, self.share, 3, 1, 1, bn=True, relu=True, bias=True)
         self.tasks = []
         for nc in self.num_classes:
@@ -927,6 +931,18 @@ class CenterHead(Module):
                 nn_ops.conv2d(mid, c2.packed, out=head, c_off=8 * i, x_c_off=64 * i)
         return head, sh
 
+    def loss(self, example, head, grad=False):
+        """center_head.py:208-271 on the head tensor of __call__ (raw logits in the layout of task_offsets(); the per-branch A/B layout
+        of MD_SEPHEAD_GROUPED=0 is 8 channels per branch wide, which at six tasks is past the operator's 160 channels):
+        example = the dict of det_ops.cp_assign_targets -> the dict of det_ops.cp_loss (total, parts, num_pos[, grad]); the
+        differentiable form is det_ops.center_point_loss(head, example, self.loss_op())."""
+        return self.loss_op()(head, example, grad=grad)
+
+    def loss_op(self):
+        if self._loss is None:
+            self._loss = det_ops.CenterPointLoss.from_head(self)
+        return self._loss
+
 
 @DETECTORS.register_module
 class PointPillars(Module):
@@ -973,6 +989,12 @@ class PointPillars(Module):
         return dets, count
 
     __call__ = forward
+
+    def loss(self, pseudo_image, example, grad=False):
+        """the neck and the head, then CenterHead.loss on the head tensor: example = the dict of det_ops.cp_assign_targets -> the dict of
+        det_ops.cp_loss (grad=True: with d total / d head, the first gradient of a training step)"""
+        head, _ = self.bbox_head(self.neck(pseudo_image))
+        return self.bbox_head.loss(example, head, grad=grad)
 
 
 def merge_center_tasks(outs, num_classes, max_per_task):

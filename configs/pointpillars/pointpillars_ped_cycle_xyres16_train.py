@@ -1,0 +1,59 @@
+# Anchor-based PointPillars for the KITTI Cyclist and Pedestrian classes on 0.16 m pillars, from raw points, with the training settings of the
+# reference model's ped_cycle_xyres16 configuration: this is pointpillars_ped_cycle_xyres16_points.py plus train_cfg, the `loss` block
+# (focal alpha / gamma, smooth-L1 sigma and code weights, the classification and localisation weights), the direction-loss weight
+# and the positive / negative class weights, which det_ops.PointPillarsLoss reads (model.loss(points, offsets, example)), and the
+# target assigner's settings: det_ops.assign_targets_batch takes the thresholds (they equal the anchor generators').
+
+class_names = ["Cyclist", "Pedestrian"]
+point_cloud_range = [0, -19.84, -2.5, 47.36, 19.84, 0.5]
+voxel_size = [0.16, 0.16, 3]
+
+model = dict(
+    type="PointPillarsKITTIPoints",
+    num_point_features=4,
+    use_norm=True,
+    voxel_feature_extractor=dict(num_filters=[64], with_distance=False),
+    middle_feature_extractor=None,
+    num_class=2,
+    class_names=class_names,
+    voxel_generator=dict(point_cloud_range=point_cloud_range, voxel_size=voxel_size, max_number_of_points_per_voxel=32,
+                         max_number_of_voxels=40000),
+    rpn=dict(layer_nums=[3, 5, 5], layer_strides=[1, 2, 2], num_filters=[64, 128, 256], upsample_strides=[1, 2, 4],
+             num_upsample_filters=[128, 128, 128], num_input_filters=64),
+    # two generators of two rotations each -> 4 anchors per cell (cyclist 0, cyclist 90, pedestrian 0, pedestrian 90), 293 632 in all
+    anchor_generators=[
+        dict(sizes=[0.6, 1.76, 1.73], strides=[0.16, 0.16, 0.0], offsets=[0.08, -19.76, -1.465], rotations=[0, 1.57],
+             matched_threshold=0.5, unmatched_threshold=0.35),
+        dict(sizes=[0.6, 0.8, 1.73], strides=[0.16, 0.16, 0.0], offsets=[0.08, -19.76, -1.2], rotations=[0, 1.57],
+             matched_threshold=0.5, unmatched_threshold=0.35),
+    ],
+    anchor_area_threshold=1,
+    use_direction_classifier=True,
+    encode_background_as_zeros=True,
+    use_sigmoid_score=True,
+    use_bev=False,
+)
+
+train_cfg = dict(
+    loss=dict(
+        classification_loss=dict(alpha=0.25, gamma=2.0),
+        localization_loss=dict(sigma=3.0, code_weight=[1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0]),
+        classification_weight=1.0,
+        localization_weight=2.0,
+    ),
+    direction_loss_weight=0.2,
+    pos_class_weight=1.0,
+    neg_class_weight=1.0,
+    assigner=dict(matched_threshold=0.5, unmatched_threshold=0.35, sample_positive_fraction=-1, sample_size=512,
+                  region_similarity_calculator="nearest_iou_similarity"),
+)
+
+test_cfg = dict(
+    nms_pre_max_size=900,
+    nms_post_max_size=300,
+    nms_score_threshold=0.09,
+    nms_iou_threshold=0.01,
+    post_center_limit_range=[0, -19.84, -2.5, 47.36, 19.84, 0.5],
+)
+
+data = dict(pseudo_image_hw=(248, 296), pseudo_image_channels=64, feature_map_hw=(248, 296))

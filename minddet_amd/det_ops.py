@@ -16,6 +16,9 @@ read the same (paths relative to /root/reference/minddet/models):
   cp_loss, CenterPointLoss, center_point_loss
                           centerpoint/det3d_ms/models/bbox_heads/center_head.py:208-271 (CenterHead.loss) with
                           centerpoint/det3d_ms/models/losses/centernet_loss.py:22-82 (FastFocalLoss, RegLoss)
+  pp_loss, PointPillarsLoss, point_pillars_loss
+                          pointpillars/src/pointpillars.py:817-872 (PointPillarsWithLossCell.construct behind the network) with
+                          pointpillars/src/core/losses.py:40-191; assign_targets_batch stacks assign_targets per sample
 
 All tensors are torch CUDA tensors; work is enqueued on the current stream; nothing here
 synchronises.  There is no CPU path.
@@ -1426,3 +1429,146 @@ def center_point_loss(head, targets, loss):
     """differentiable form: -> (total [1] f32, parts [T,12], num_pos [T]); the forward runs md_cp_loss_grad once, the backward returns
     grad_output x (d total / d head) in the head's dtype.  parts and num_pos carry no gradient."""
     return _CenterPointLossFn.apply(head, targets, loss)
+
+
+# ----------------------------------------------------------------------------- KITTI PointPillars training loss (csrc/pploss.hip)
+PP_LOSS_STRIP = 64            # MD_PP_LOSS_STRIP: cells per workgroup of the dense pass (the workspace formula)
+PP_LOSS_COUNT_CHUNK = 4096    # MD_PP_LOSS_COUNT_CHUNK: labels per workgroup of the positive count
+
+
+class _PPLossAttrs(ctypes.Structure):
+    _fields_ = [("head", _PPHeadAttrs), ("alpha", ctypes.c_float), ("gamma", ctypes.c_float), ("sigma", ctypes.c_float),
+                ("code_weights", ctypes.c_float * 7), ("cls_weight", ctypes.c_float), ("loc_weight", ctypes.c_float),
+                ("dir_weight", ctypes.c_float), ("pos_cls_weight", ctypes.c_float), ("neg_cls_weight", ctypes.c_float)]
+
+
+def pp_loss_attrs(head_offsets, num_anchors, num_classes, alpha=0.25, gamma=2.0, sigma=3.0, code_weights=(1.0,) * 7, cls_weight=1.0,
+                  loc_weight=2.0, dir_weight=0.2, pos_cls_weight=1.0, neg_cls_weight=1.0):
+    """md_pp_loss_attrs: head_offsets = PPAnchorHead.head_offsets() ({cls, box, dir_cls}: first channels; dir_cls None = no direction
+    loss), alpha None = no alpha factor; the other names are the reference configuration's (classification_loss.alpha / gamma,
+    localization_loss.sigma / code_weight, classification_weight, localization_weight, direction_loss_weight, pos_class_weight,
+    neg_class_weight).  The defaults are the values of both KITTI configurations."""
+    cw = [float(v) for v in code_weights]
+    if len(cw) != 7:
+        raise ValueError(f"pp_loss_attrs: 7 code weights, got {len(cw)}")
+    off_dir = head_offsets.get("dir_cls")
+    at = _PPLossAttrs()
+    at.head = _PPHeadAttrs(int(head_offsets["cls"]), int(head_offsets["box"]), -1 if off_dir is None else int(off_dir), int(num_anchors),
+                           int(num_classes), 0, 1)
+    if alpha is not None and float(alpha) < 0:
+        raise ValueError("pp_loss_attrs: alpha is None or >= 0")
+    at.alpha, at.gamma, at.sigma = -1.0 if alpha is None else float(alpha), float(gamma), float(sigma)
+    for j, v in enumerate(cw):
+        at.code_weights[j] = v
+    at.cls_weight, at.loc_weight, at.dir_weight = float(cls_weight), float(loc_weight), float(dir_weight)
+    at.pos_cls_weight, at.neg_cls_weight = float(pos_cls_weight), float(neg_cls_weight)
+    return at
+
+
+def pp_loss_workspace_bytes(B, H, W, num_anchors):
+    strips = (H * W + PP_LOSS_STRIP - 1) // PP_LOSS_STRIP
+    chunks = (H * W * num_anchors + PP_LOSS_COUNT_CHUNK - 1) // PP_LOSS_COUNT_CHUNK
+    return 40 * B * strips + 4 * B * chunks
+
+
+def pp_loss(head, labels, reg_targets, anchors, at, grad=False, out=None):
+    """PointPillarsWithLossCell.construct behind the network (pointpillars/src/pointpillars.py:817-872 with src/core/losses.py:40-191)
+    on the device (md_pp_loss / md_pp_loss_grad, include/minddet_hip_pploss.h): head [B,H,W,C] bf16 raw outputs in the layout of
+    PPAnchorHead.head_offsets(), labels [B,N] i32 and reg_targets [B,N,7] f32 (assign_targets_batch), anchors [N,7] f32 -> dict with
+    total [1] f32, parts [5] f32 (loc, cls, dir as they enter the total, cls_pos, cls_neg), num_pos [B] f32 and, with grad=True, grad
+    [B,H,W,C] f32 = d total / d head.  Every element of every output is written, so `out` (such a dict from an earlier call) can be
+    reused without clearing."""
+    if head.dtype != torch.bfloat16 or head.dim() != 4:
+        raise ValueError("pp_loss: head has to be [B,H,W,C] bfloat16")
+    head = head.contiguous()
+    dev = head.device
+    B, H, W, _ = head.shape
+    A = int(at.head.num_anchors)
+    n = H * W * A
+    if tuple(labels.shape) != (B, n) or labels.dtype != torch.int32 or tuple(reg_targets.shape) != (B, n, 7):
+        raise ValueError(f"pp_loss: labels has to be int32 [{B}, {n}] and reg_targets [{B}, {n}, 7], got {tuple(labels.shape)} "
+                         f"{labels.dtype} / {tuple(reg_targets.shape)}")
+    want = dict(total=((1,), torch.float32), parts=((5,), torch.float32), num_pos=((B,), torch.float32))
+    if grad:
+        want["grad"] = (tuple(head.shape), torch.float32)
+    if out is None:
+        out = {k: torch.empty(shp, dtype=dt, device=dev) for k, (shp, dt) in want.items()}
+    for k, (shp, dt) in want.items():
+        if tuple(out[k].shape) != shp or out[k].dtype != dt:
+            raise ValueError(f"pp_loss: out[{k!r}] has to be {dt} of shape {shp}")
+    ws = torch.empty((pp_loss_workspace_bytes(B, H, W, A),), dtype=torch.uint8, device=dev)
+    ops = [head, labels.contiguous(), _f32c(reg_targets), _f32c(anchors).reshape(-1, 7), out["parts"], out["num_pos"], out["total"]]
+    if grad:
+        _lib.call("md_pp_loss_grad", ops + [out["grad"], ws], extra=at)
+    else:
+        _lib.call("md_pp_loss", ops + [ws], extra=at)
+    return out
+
+
+class PointPillarsLoss:
+    """The loss of a KITTI PointPillars model: the head's channel layout plus the reference configuration's loss settings (the keys of
+    its `loss` block, direction_loss_weight, pos_class_weight, neg_class_weight).  __call__(head, labels, reg_targets, anchors,
+    grad=False) -> the dict of pp_loss."""
+
+    def __init__(self, head_offsets, num_anchors, num_classes, loss=None, direction_loss_weight=0.2, pos_class_weight=1.0,
+                 neg_class_weight=1.0):
+        loss = dict(loss or {})
+        cls_cfg, loc_cfg = dict(loss.get("classification_loss", {})), dict(loss.get("localization_loss", {}))
+        self.head_offsets, self.num_anchors, self.num_classes = dict(head_offsets), int(num_anchors), int(num_classes)
+        self.alpha, self.gamma = cls_cfg.get("alpha", 0.25), float(cls_cfg.get("gamma", 2.0))
+        self.sigma = float(loc_cfg.get("sigma", 3.0))
+        self.code_weights = [float(v) for v in (loc_cfg.get("code_weight") or [1.0] * 7)]
+        self.cls_weight, self.loc_weight = float(loss.get("classification_weight", 1.0)), float(loss.get("localization_weight", 2.0))
+        self.dir_weight = float(direction_loss_weight)
+        self.pos_cls_weight, self.neg_cls_weight = float(pos_class_weight), float(neg_class_weight)
+        self.at = pp_loss_attrs(self.head_offsets, self.num_anchors, self.num_classes, self.alpha, self.gamma, self.sigma, self.code_weights,
+                                self.cls_weight, self.loc_weight, self.dir_weight, self.pos_cls_weight, self.neg_cls_weight)
+
+    @classmethod
+    def from_net(cls, net, train_cfg=None):
+        """net: a graphs.PointPillarsNet (or the from-points model that wraps one); train_cfg: the config's train_cfg (its "loss" block
+        and the three weights beside it); None = the values of the KITTI configurations"""
+        net = getattr(net, "inner", net)
+        t = dict(train_cfg or {})
+        return cls(net.head_offsets(), net.num_anchors, net.num_class, t.get("loss"), t.get("direction_loss_weight", 0.2),
+                   t.get("pos_class_weight", 1.0), t.get("neg_class_weight", 1.0))
+
+    @classmethod
+    def from_config(cls, cfg, net):
+        return cls.from_net(net, cfg.train_cfg)
+
+    def __call__(self, head, labels, reg_targets, anchors, grad=False, out=None):
+        return pp_loss(head, labels, reg_targets, anchors, self.at, grad=grad, out=out)
+
+
+class _PointPillarsLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, head, labels, reg_targets, anchors, loss):
+        out = pp_loss(head.detach(), labels, reg_targets, anchors, loss.at, grad=True)
+        ctx.save_for_backward(out["grad"])
+        ctx.head_dtype = head.dtype
+        ctx.mark_non_differentiable(out["parts"], out["num_pos"])
+        return out["total"], out["parts"], out["num_pos"]
+
+    @staticmethod
+    def backward(ctx, g_total, g_parts, g_num_pos):
+        (grad,) = ctx.saved_tensors
+        return (g_total.to(torch.float32) * grad).to(ctx.head_dtype), None, None, None, None
+
+
+def point_pillars_loss(head, labels, reg_targets, anchors, loss):
+    """differentiable form: -> (total [1] f32, parts [5], num_pos [B]); the forward runs md_pp_loss_grad once, the backward returns
+    grad_output x (d total / d head) in the head's dtype.  parts and num_pos carry no gradient."""
+    return _PointPillarsLossFn.apply(head, labels, reg_targets, anchors, loss)
+
+
+def assign_targets_batch(anchors, gt_boxes, gt_classes, matched_thr, unmatched_thr, anchors_mask=None):
+    """assign_targets for a batch: gt_boxes / gt_classes are per-sample lists ([G_b,7] / [G_b] or None), anchors_mask [B,N] or None
+    -> (labels [B,N] i32, bbox_targets [B,N,7] f32, bbox_outside_weights [B,N] f32, gt_ids [B,N] i32), the inputs of pp_loss.  One
+    md_assign_targets call per sample (no new kernel), nothing read back."""
+    B = len(gt_boxes)
+    if B < 1 or (gt_classes is not None and len(gt_classes) != B) or (anchors_mask is not None and len(anchors_mask) != B):
+        raise ValueError("assign_targets_batch: one gt_boxes / gt_classes / anchors_mask entry per sample, at least one sample")
+    rows = [assign_targets(anchors, gt_boxes[b], None if gt_classes is None else gt_classes[b], matched_thr, unmatched_thr,
+                           None if anchors_mask is None else anchors_mask[b]) for b in range(B)]
+    return tuple(torch.stack([r[i] for r in rows]) for i in range(4))

@@ -1214,6 +1214,8 @@ class PointPillarsNet(Module):
         self.anchor_area_threshold = float(anchor_area_threshold)
         self.class_names = list(class_names) if class_names is not None else None
         self.test_cfg = dict(test_cfg)
+        self.train_cfg = dict(train_cfg) if train_cfg else None
+        self._loss = None
         off = self.bbox_head.head_offsets()
         self.post = det_ops.PPHeadPost(dict(num_anchors=self.num_anchors, num_classes=self.num_class, off_cls=off["cls"], off_box=off["box"],
                                             off_dir=off["dir_cls"], use_self_train=use_self_train,
@@ -1271,6 +1273,21 @@ class PointPillarsNet(Module):
         if anchors_mask is None:
             return self.forward_split(pseudo_image)
         return self.forward_split((pseudo_image, anchors_mask), prepare=lambda p, m: (p, m))
+
+    def loss_op(self):
+        """det_ops.PointPillarsLoss of this head's layout with the settings of train_cfg (None: the KITTI configurations' values)"""
+        if self._loss is None:
+            self._loss = det_ops.PointPillarsLoss.from_net(self, self.train_cfg)
+        return self._loss
+
+    def loss(self, pseudo_image, example, grad=False):
+        """PointPillarsWithLossCell.construct (pointpillars/src/pointpillars.py:817-872): the neck and the head, then the loss on the head
+        tensor.  example = dict(labels [B,N] i32, reg_targets [B,N,7] f32), the first two outputs of det_ops.assign_targets_batch on
+        self.anchors -> the dict of det_ops.pp_loss (grad=True: with d total / d head, the first gradient of a training step) plus
+        `head`, the tensor the gradient belongs to; the differentiable form is det_ops.point_pillars_loss(head, ..., self.loss_op())."""
+        head = self.bbox_head(self.neck(pseudo_image))
+        out = self.loss_op()(head, example["labels"], example["reg_targets"], self.anchors, grad=grad)
+        return dict(out, head=head)
 
 
 # ----------------------------------------------------------------------------- PointPillars (KITTI) from raw points (csrc/ppreader.hip)
@@ -1376,6 +1393,14 @@ class PointPillarsKITTIPoints(Module):
         return self.inner.forward(canvas, mask)
 
     __call__ = forward
+
+    def loss(self, points, offsets, example, grad=False):
+        """the voxeliser and the pillar encoder of forward() (the anchor mask belongs to the targets, not to the loss), then
+        PointPillarsNet.loss on the canvas (example: labels, reg_targets of the model's anchors)"""
+        voxels, coors, num_points, voxel_num = det_ops.voxelize(points, offsets, self.voxel_size, self.pc_range, self.max_points, self.max_voxels)
+        canvas = det_ops.pp_pillar_encode(voxels, num_points, coors, voxel_num, self.reader.packed, self.grid_hw, self.reader.voxel_size,
+                                          self.reader.offsets)
+        return self.inner.loss(canvas, example, grad=grad)
 
 
 # ----------------------------------------------------------------------------- YOLOv5 (build-authored; parity unpinned)

@@ -19,6 +19,12 @@ read the same (paths relative to /root/reference/minddet/models):
   pp_loss, PointPillarsLoss, point_pillars_loss
                           pointpillars/src/pointpillars.py:817-872 (PointPillarsWithLossCell.construct behind the network) with
                           pointpillars/src/core/losses.py:40-191; assign_targets_batch stacks assign_targets per sample
+  cn_assign_targets, CenterNetTargets
+                          centernet/src/dataset.py:317-384 (the target part of COCOHP.preprocess_fn, for a batch) with
+                          centernet/src/image.py:59-63,94-144
+  cn_loss, CenterNetLoss, center_net_loss
+                          centernet/src/centernet_det.py:177-237 (CenterNetLossCell.construct behind the network) with
+                          centernet/src/utils.py:132-245 (Sigmoid, FocalLoss, RegLoss)
 
 All tensors are torch CUDA tensors; work is enqueued on the current stream; nothing here
 synchronises.  There is no CPU path.
@@ -1572,3 +1578,177 @@ def assign_targets_batch(anchors, gt_boxes, gt_classes, matched_thr, unmatched_t
     rows = [assign_targets(anchors, gt_boxes[b], None if gt_classes is None else gt_classes[b], matched_thr, unmatched_thr,
                            None if anchors_mask is None else anchors_mask[b]) for b in range(B)]
     return tuple(torch.stack([r[i] for r in rows]) for i in range(4))
+
+
+# ----------------------------------------------------------------------------- CenterNet training targets (csrc/cntargets.hip)
+CN_MAX_OBJS = 1024            # MD_CN_MAX_OBJS
+CN_LOSS_STRIP = 64            # MD_CN_LOSS_STRIP: cells per workgroup of the dense pass (the workspace formula)
+CN_LOSS_COUNT_CHUNK = 16384   # MD_CN_LOSS_COUNT_CHUNK: heat-map elements per workgroup of the count pass
+
+
+class _CNTargetsAttrs(ctypes.Structure):
+    _fields_ = [("min_overlap", ctypes.c_float)]
+
+
+def cn_assign_targets(boxes, classes, *, num_classes, feature_map_size, max_objs, min_overlap=0.7, out=None):
+    """The target part of COCOHP.preprocess_fn (centernet/src/dataset.py:343-359) for a batch on the device (md_cn_assign_targets,
+    include/minddet_hip_cn.h): boxes [B,G,4] f32 (x0, y0, x1, y1 in output-map coordinates, after the flip and the affine transform,
+    before the clip), classes [B,G] (1-based category_id; < 1 or > num_classes: a padding row), G <= max_objs -> dict with the
+    reference's keys: hm [B,C,H,W] f32, ind [B,M] i32, reg_mask [B,M] u8, wh [B,M,2] f32, reg [B,M,2] f32.  feature_map_size = (W, H);
+    every element of every output is written by the op, so `out` (such a dict from an earlier call) can be reused without clearing."""
+    at = _CNTargetsAttrs(float(min_overlap))
+    g = _f32c(boxes)
+    dev = g.device
+    cls = classes.to(device=dev, dtype=torch.int32).contiguous()
+    B, G = g.shape[0], g.shape[1]
+    C, M = int(num_classes), int(max_objs)
+    W, H = int(feature_map_size[0]), int(feature_map_size[1])
+    want = dict(hm=((B, C, H, W), torch.float32), ind=((B, M), torch.int32), reg_mask=((B, M), torch.uint8), wh=((B, M, 2), torch.float32),
+                reg=((B, M, 2), torch.float32))
+    if out is None:
+        out = {k: torch.empty(shp, dtype=dt, device=dev) for k, (shp, dt) in want.items()}
+    for k, (shp, dt) in want.items():
+        if tuple(out[k].shape) != shp or out[k].dtype != dt:
+            raise ValueError(f"cn_assign_targets: out[{k!r}] has to be {dt} of shape {shp}")
+    ws = torch.empty((max(B * M, 1) * 16,), dtype=torch.uint8, device=dev)
+    _lib.call("md_cn_assign_targets", [g, cls, out["hm"], out["ind"], out["reg_mask"], out["wh"], out["reg"], ws], extra=at)
+    return out
+
+
+class CenterNetTargets:
+    """The target step of a CenterNet config: num_classes, the output map (input_res // down_ratio), max_objs and min_overlap.
+    __call__(bboxes [B,G,4] original-image boxes, category_id [B,G], trans [B,2,3] float64 `trans_output` matrices or None,
+    flip_width [B] (the image width of a flipped sample, 0 or less: not flipped) or None) -> the dict of cn_assign_targets.  The flip
+    (`width - x[2,0] - 1` in fp32, dataset.py:340) and affine_transform (image.py:59-63: ((t00 x + t01 y) + t02) in float64, rounded to
+    fp32) are elementwise torch ops on the device; rows past max_objs are dropped (dataset.py:274).  trans None: the boxes are
+    output-map boxes already."""
+
+    def __init__(self, num_classes=80, feature_map_size=(128, 128), max_objs=128, min_overlap=0.7):
+        self.num_classes, self.max_objs, self.min_overlap = int(num_classes), int(max_objs), float(min_overlap)
+        self.feature_map_size = (int(feature_map_size[0]), int(feature_map_size[1]))
+
+    @classmethod
+    def from_config(cls, cfg):
+        a = cfg.train_cfg["assigner"]
+        h, w = (int(v) for v in a["input_res"])
+        d = int(a["down_ratio"])
+        return cls(cfg.model["num_classes"], (w // d, h // d), a["max_objs"], a.get("min_overlap", 0.7))
+
+    def __call__(self, bboxes, category_id, trans=None, flip_width=None, out=None):
+        b = _f32c(bboxes)[:, :self.max_objs]
+        cls = category_id[:, :self.max_objs]
+        dev = b.device
+        if flip_width is not None:
+            fw = torch.as_tensor(flip_width, device=dev).to(torch.float32).reshape(-1, 1)
+            flipped = fw > 0
+            x0 = torch.where(flipped, fw - b[..., 2] - 1.0, b[..., 0])
+            x1 = torch.where(flipped, fw - b[..., 0] - 1.0, b[..., 2])
+            b = torch.stack((x0, b[..., 1], x1, b[..., 3]), -1)
+        if trans is not None:
+            t = torch.as_tensor(trans, device=dev).to(torch.float64).reshape(-1, 1, 2, 3)
+            pts = b.to(torch.float64).reshape(b.shape[0], b.shape[1], 2, 1, 2)       # [B,G,corner,1,(x, y)]
+            tt = t.unsqueeze(2)                                                       # [B,1,1,2,3]
+            b = ((tt[..., 0] * pts[..., 0] + tt[..., 1] * pts[..., 1]) + tt[..., 2]).to(torch.float32).reshape(b.shape[0], b.shape[1], 4)
+        return cn_assign_targets(b, cls, num_classes=self.num_classes, feature_map_size=self.feature_map_size, max_objs=self.max_objs,
+                                 min_overlap=self.min_overlap, out=out)
+
+
+# ----------------------------------------------------------------------------- CenterNet training loss (csrc/cnloss.hip)
+class _CNLossAttrs(ctypes.Structure):
+    _fields_ = [("num_classes", ctypes.c_int32), ("off_hm", ctypes.c_int32), ("off_wh", ctypes.c_int32), ("off_reg", ctypes.c_int32),
+                ("hm_weight", ctypes.c_float), ("wh_weight", ctypes.c_float), ("off_weight", ctypes.c_float)]
+
+
+def cn_loss_attrs(num_classes, off_hm=0, off_wh=None, off_reg=None, hm_weight=1.0, wh_weight=0.1, off_weight=1.0, reg_offset=True):
+    """md_cn_loss_attrs: the heads' first channels in the layout of graphs.CenterNet.features (hm at 0, wh behind it, reg behind wh;
+    reg_offset False: no offset head) and the reference's hm_weight / wh_weight / off_weight (default_config.yaml: 1, 0.1, 1)"""
+    nc = int(num_classes)
+    off_wh = int(off_hm) + nc if off_wh is None else int(off_wh)
+    off_reg = (off_wh + 2 if off_reg is None else int(off_reg)) if reg_offset else -1
+    return _CNLossAttrs(nc, int(off_hm), off_wh, off_reg, float(hm_weight), float(wh_weight), float(off_weight))
+
+
+def cn_loss_workspace_bytes(B, C, H, W):
+    strips = (H * W + CN_LOSS_STRIP - 1) // CN_LOSS_STRIP
+    chunks = (B * C * H * W + CN_LOSS_COUNT_CHUNK - 1) // CN_LOSS_COUNT_CHUNK
+    return 8 * B * (4 + 2 * strips) + 4 * chunks
+
+
+def cn_loss(head, targets, at, grad=False, out=None):
+    """CenterNetLossCell.construct behind the network (centernet_det.py:177-237, FocalLoss + two RegLoss) on the device (md_cn_loss /
+    md_cn_loss_grad, include/minddet_hip_cn.h): head [B,H,W,Cp] bf16 raw logits in the layout of graphs.CenterNet.features, targets =
+    the dict of cn_assign_targets (hm, ind, reg_mask, wh, reg) -> dict with total [1] f32, parts [3] f32 (hm_loss, wh_loss, off_loss),
+    num_pos [1] f32 and, with grad=True, grad [B,H,W,Cp] f32 = d total / d head.  Every element of every output is written, so `out`
+    (such a dict from an earlier call) can be reused without clearing.  A slot whose ind is out of range is skipped as if masked."""
+    if head.dtype != torch.bfloat16 or head.dim() != 4:
+        raise ValueError("cn_loss: head has to be [B,H,W,Cp] bfloat16")
+    head = head.contiguous()
+    dev = head.device
+    B, H, W, _ = head.shape
+    want = dict(total=((1,), torch.float32), parts=((3,), torch.float32), num_pos=((1,), torch.float32))
+    if grad:
+        want["grad"] = (tuple(head.shape), torch.float32)
+    if out is None:
+        out = {k: torch.empty(shp, dtype=dt, device=dev) for k, (shp, dt) in want.items()}
+    for k, (shp, dt) in want.items():
+        if tuple(out[k].shape) != shp or out[k].dtype != dt:
+            raise ValueError(f"cn_loss: out[{k!r}] has to be {dt} of shape {shp}")
+    ws = torch.empty((cn_loss_workspace_bytes(B, int(at.num_classes), H, W),), dtype=torch.uint8, device=dev)
+    ops = [head, targets["hm"], targets["ind"], targets["reg_mask"], targets["wh"], targets["reg"], out["parts"], out["num_pos"],
+           out["total"]]
+    if grad:
+        _lib.call("md_cn_loss_grad", ops + [out["grad"], ws], extra=at)
+    else:
+        _lib.call("md_cn_loss", ops + [ws], extra=at)
+    return out
+
+
+class CenterNetLoss:
+    """The loss of a CenterNet head: its channel layout plus the reference's net_config loss settings.  Only the configuration the
+    reference trains is built: FocalLoss on the heat map and L1 RegLoss on wh / reg of one stack; mse_loss, dense_wh, cat_spec_wh,
+    another reg_loss or num_stacks != 1 raise ValueError.  __call__(head, targets, grad=False) -> the dict of cn_loss."""
+
+    def __init__(self, num_classes=80, off_hm=0, hm_weight=1.0, wh_weight=0.1, off_weight=1.0, reg_offset=True, reg_loss="l1",
+                 mse_loss=False, dense_wh=False, cat_spec_wh=False, num_stacks=1):
+        given = dict(mse_loss=mse_loss, dense_wh=dense_wh, cat_spec_wh=cat_spec_wh, reg_loss=reg_loss, num_stacks=num_stacks)
+        built = dict(mse_loss=False, dense_wh=False, cat_spec_wh=False, reg_loss="l1", num_stacks=1)
+        for name, v in given.items():
+            if v != built[name]:
+                raise ValueError(f"CenterNetLoss: {name}={v!r} is not built (only {name}={built[name]!r} is)")
+        self.num_classes, self.reg_offset = int(num_classes), bool(reg_offset)
+        self.hm_weight, self.wh_weight, self.off_weight = float(hm_weight), float(wh_weight), float(off_weight)
+        self.at = cn_loss_attrs(self.num_classes, off_hm, None, None, self.hm_weight, self.wh_weight, self.off_weight, self.reg_offset)
+
+    @classmethod
+    def from_config(cls, cfg, num_classes=None):
+        loss = dict(cfg.train_cfg.get("loss", {}))
+        return cls(cfg.model["num_classes"] if num_classes is None else num_classes, **loss)
+
+    @classmethod
+    def from_model(cls, net, train_cfg=None):
+        """net: a graphs.CenterNet; train_cfg: a config's train_cfg (its "loss" block), None = the reference's default values"""
+        return cls(net.num_classes, **dict((train_cfg or {}).get("loss", {})))
+
+    def __call__(self, head, targets, grad=False, out=None):
+        return cn_loss(head, targets, self.at, grad=grad, out=out)
+
+
+class _CenterNetLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, head, targets, loss):
+        out = cn_loss(head.detach(), targets, loss.at, grad=True)
+        ctx.save_for_backward(out["grad"])
+        ctx.head_dtype = head.dtype
+        ctx.mark_non_differentiable(out["parts"], out["num_pos"])
+        return out["total"], out["parts"], out["num_pos"]
+
+    @staticmethod
+    def backward(ctx, g_total, g_parts, g_num_pos):
+        (grad,) = ctx.saved_tensors
+        return (g_total.to(torch.float32) * grad).to(ctx.head_dtype), None, None
+
+
+def center_net_loss(head, targets, loss):
+    """differentiable form: -> (total [1] f32, parts [3], num_pos [1]); the forward runs md_cn_loss_grad once, the backward returns
+    grad_output x (d total / d head) in the head's dtype.  parts and num_pos carry no gradient."""
+    return _CenterNetLossFn.apply(head, targets, loss)

@@ -730,6 +730,7 @@ class CenterNet(Module):
         self.head2 = ConvModule(init, 3 * hc, self.n_out, 1, bn=False, relu=False, bias=True)
         self.fuse_heads()
         self.decode = det_ops.DetectionDecode(reg_offset=True, K=K)
+        self.train_cfg, self._loss = train_cfg, None
 
     def fuse_heads(self):
         """(Re)build the fused head convs' weights from self.heads (to() calls it: they are packed like any other conv)."""
@@ -772,6 +773,20 @@ class CenterNet(Module):
         return det
 
     __call__ = forward
+
+    def loss_op(self):
+        """det_ops.CenterNetLoss of this head's layout with the settings of train_cfg (None: the reference's default values)"""
+        if self._loss is None:
+            self._loss = det_ops.CenterNetLoss.from_model(self, self.train_cfg)
+        return self._loss
+
+    def loss(self, images, example, grad=False):
+        """CenterNetLossCell.construct (centernet/src/centernet_det.py:206-237): features(), then the loss on the head tensor.
+        example = the dict of det_ops.cn_assign_targets (hm, ind, reg_mask, wh, reg) -> the dict of det_ops.cn_loss (grad=True: with
+        d total / d head, the first gradient of a training step) plus `head`, the tensor the gradient belongs to; the differentiable
+        form is det_ops.center_net_loss(head, example, self.loss_op())."""
+        head = self.features(images)
+        return dict(self.loss_op()(head, example, grad=grad), head=head)
 
 
 # ----------------------------------------------------------------------------- CenterPoint RPN neck

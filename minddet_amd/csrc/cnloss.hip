@@ -15,12 +15,8 @@
 //                          writes the regression elements that sample b's slots touch: of the slots sharing a cell the first sums its
 //                          siblings' signs and stores each element once
 // Arithmetic: every term and every sum in float64, rounded to fp32 once on output (the header says why).
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-
-#include "aot.h"
-#include "device.h"
+// The block sums and their order, the focal terms, the strip staging, the L1 slot pieces and the entry's ownership rule: loss_common.h.
+#include "loss_common.h"
 #include "../../include/minddet_hip_cn.h"
 
 #pragma clang fp contract(off)
@@ -42,34 +38,6 @@ struct CnlParams {
     float hm_weight, wh_weight, off_weight;
 };
 
-// N block sums at once, in a fixed order (256 lanes; red: 4 N doubles); every lane gets the sums
-template <int N> __device__ __forceinline__ void cnl_block_sums(double (&v)[N], double *red) {
-#pragma unroll
-    for (int e = 0; e < N; ++e)
-        for (int off = 32; off > 0; off >>= 1) v[e] += __shfl_down(v[e], off, 64);
-    __syncthreads();   // red may still be read from an earlier call
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int e = 0; e < N; ++e) red[(threadIdx.x >> 6) * N + e] = v[e];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int e = 0; e < N; ++e) v[e] = ((red[e] + red[N + e]) + red[2 * N + e]) + red[3 * N + e];
-}
-// a block sum of integers (256 lanes; red: 4 ints); every lane gets the sum
-__device__ __forceinline__ int cnl_block_count(int v, int *red) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
-
-__device__ __forceinline__ bool cnl_slot_valid(int m, int i, int HW) { return m != 0 && i >= 0 && i < HW; }
-__device__ __forceinline__ int cnl_sign(float pred, float target) { return (pred > target) - (pred < target); }
-// weight sgn / den rounded once; +0 when the signs cancel, whatever the weight's sign
-__device__ __forceinline__ float cnl_reg_grad(float weight, int sgn, double den) { return sgn == 0 ? 0.f : (float)((double)weight * (double)sgn / den); }
-
 __global__ __launch_bounds__(256) void cn_loss_count_kernel(const uint16_t *__restrict__ head, const float *__restrict__ hm,
                                                             const int *__restrict__ ind, const uint8_t *__restrict__ mask,
                                                             const float *__restrict__ wh, const float *__restrict__ reg, CnlParams p,
@@ -90,7 +58,7 @@ __global__ __launch_bounds__(256) void cn_loss_count_kernel(const uint16_t *__re
         } else {
             for (int i = threadIdx.x; i < n; i += 256) cnt += src[i] == 1.f;
         }
-        cnt = cnl_block_count(cnt, ired);
+        cnt = block_count(cnt, ired);
         if (threadIdx.x == 0) counts[blockIdx.x] = cnt;
         return;
     }
@@ -99,14 +67,14 @@ __global__ __launch_bounds__(256) void cn_loss_count_kernel(const uint16_t *__re
     for (int k = threadIdx.x; k < p.M; k += 256) {
         const size_t s = (size_t)b * p.M + k;
         const int i = ind[s];
-        if (!cnl_slot_valid(mask[s], i, p.HW)) continue;
+        if (!slot_valid(mask[s], i, p.HW)) continue;
         const uint16_t *cell = head + ((size_t)b * p.HW + i) * p.Cp;
         acc[0] += 1.0;
         acc[1] += fabs((double)bf2f(cell[p.off_wh]) - (double)wh[s * 2]) + fabs((double)bf2f(cell[p.off_wh + 1]) - (double)wh[s * 2 + 1]);
         if (p.use_off)
             acc[2] += fabs((double)bf2f(cell[p.off_reg]) - (double)reg[s * 2]) + fabs((double)bf2f(cell[p.off_reg + 1]) - (double)reg[s * 2 + 1]);
     }
-    cnl_block_sums<3>(acc, red);
+    block_sums<3>(acc, red);
     if (threadIdx.x == 0) {
         double *dst = rec + (size_t)b * CNL_REC;
         dst[0] = acc[0]; dst[1] = acc[1]; dst[2] = acc[2]; dst[3] = 0.0;
@@ -124,24 +92,14 @@ __global__ __launch_bounds__(256) void cn_loss_dense_kernel(const uint16_t *__re
     uint16_t *sh = (uint16_t *)(smem + CNL_LDS_HEAD);                            // [CNL_STRIP][Cp] bf16
     float *sg = (float *)(smem + CNL_LDS_HEAD + (size_t)CNL_STRIP * p.Cp * 2);   // [CNL_STRIP][Cp] f32 (GRAD)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int b = blockIdx.x / p.strips_per_sample, n0 = (blockIdx.x - b * p.strips_per_sample) * CNL_STRIP;
-    const int cells = min(CNL_STRIP, p.HW - n0), elems = cells * p.Cp;
-    const size_t base = ((size_t)b * p.HW + n0) * p.Cp;
+    const Strip st = strip_of_block(p.strips_per_sample, CNL_STRIP, p.HW, p.Cp);
+    const int b = st.b, n0 = st.n0, cells = st.cells;
 
-    if (vec) {   // Cp a multiple of 8 and both pointers 16-byte aligned: the strip starts on a 16-byte boundary in head and in grad
-        const uint4 *src = (const uint4 *)(head + base);
-        for (int i = threadIdx.x; i < elems / 8; i += 256) ((uint4 *)sh)[i] = src[i];
-        if (GRAD)
-            for (int i = threadIdx.x; i < elems / 4; i += 256) ((float4 *)sg)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    } else {
-        for (int i = threadIdx.x; i < elems; i += 256) sh[i] = head[base + i];
-        if (GRAD)
-            for (int i = threadIdx.x; i < elems; i += 256) sg[i] = 0.f;
-    }
+    stage_strip<GRAD>(sh, sg, head + st.base, st.elems, vec);
     {   // num_pos: a sum of exact integers
         int n = 0;
         for (int i = threadIdx.x; i < p.n_chunks; i += 256) n += counts[i];
-        n = cnl_block_count(n, ired);   // (the barriers inside also publish sh / sg)
+        n = block_count(n, ired);   // (the barriers inside also publish sh / sg)
         if (threadIdx.x == 0) s_n[0] = n > 0 ? (double)n : 1.0;
     }
     __syncthreads();
@@ -154,18 +112,15 @@ __global__ __launch_bounds__(256) void cn_loss_dense_kernel(const uint16_t *__re
             const float t = plane[(size_t)c * p.HW];
             const bool is_pos = t == 1.f, is_neg = t < 1.f;
             if (!is_pos && !is_neg) continue;   // hm > 1 or NaN: in neither sum (the grad strip is already zero)
-            const double s = 1.0 / (1.0 + exp(-(double)bf2f(sh[lane * p.Cp + p.off_hm + c])));
-            const bool open = s > 1e-4 && s < 1.0 - 1e-4;   // the clip passes the gradient
-            const double pr = fmin(fmax(s, 1e-4), 1.0 - 1e-4), om = 1.0 - pr;
+            bool open;
+            const double pr = clipped_p(bf2f(sh[lane * p.Cp + p.off_hm + c]), open);
             double d;
             if (is_pos) {
-                const double lp = log(pr);
-                acc[0] += lp * (om * om);
-                d = (om * om) * (om - 2.0 * pr * lp);
+                acc[0] += pos_term(pr);
+                d = pos_term_grad(pr, open);
             } else {
-                const double q = 1.0 - (double)t, q2 = q * q, g4 = q2 * q2, l1p = log(om);
-                acc[1] += l1p * (pr * pr) * g4;
-                d = g4 * (pr * pr) * (2.0 * om * l1p - pr);
+                acc[1] += neg_term(pr, t);
+                d = neg_term_grad(pr, open, t);
             }
             if (GRAD) {
                 const float g = open ? (float)(scale * d) : 0.f;
@@ -173,19 +128,12 @@ __global__ __launch_bounds__(256) void cn_loss_dense_kernel(const uint16_t *__re
             }
         }
     }
-    cnl_block_sums<2>(acc, red);
+    block_sums<2>(acc, red);
     if (threadIdx.x == 0) {
         part[(size_t)blockIdx.x * 2] = acc[0];
         part[(size_t)blockIdx.x * 2 + 1] = acc[1];
     }
-    if (GRAD) {   // (the block sums' barriers stand between the last write of sg and these reads)
-        if (vec) {
-            float4 *dst = (float4 *)(grad + base);
-            for (int i = threadIdx.x; i < elems / 4; i += 256) dst[i] = ((const float4 *)sg)[i];
-        } else {
-            for (int i = threadIdx.x; i < elems; i += 256) grad[base + i] = sg[i];
-        }
-    }
+    if (GRAD) flush_strip(grad + st.base, sg, st.elems, vec);   // (the block sums' barriers stand between the last write of sg and these reads)
 }
 
 template <bool GRAD>
@@ -201,7 +149,7 @@ __global__ __launch_bounds__(256) void cn_loss_finish_kernel(const uint16_t *__r
     // the batch's valid slots: a sum of exact integers (every workgroup needs it for the regression gradient)
     double nv[1] = {0.0};
     for (int i = threadIdx.x; i < p.B; i += 256) nv[0] += rec[(size_t)i * CNL_REC];
-    cnl_block_sums<1>(nv, red);
+    block_sums<1>(nv, red);
     const double den = 2.0 * nv[0] + 1e-4;
     if (b == 0) {
         double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // num_pos, sum |wh|, sum |off|, pos, neg, -
@@ -214,7 +162,7 @@ __global__ __launch_bounds__(256) void cn_loss_finish_kernel(const uint16_t *__r
             acc[3] += part[(size_t)i * 2];
             acc[4] += part[(size_t)i * 2 + 1];
         }
-        cnl_block_sums<6>(acc, red);
+        block_sums<6>(acc, red);
         if (threadIdx.x == 0) {
             const double n = acc[0] == 0.0 ? 1.0 : acc[0];
             const double hm_loss = -(acc[3] + acc[4]) / n, wh_loss = acc[1] / den, off_loss = p.use_off ? acc[2] / den : 0.0;
@@ -230,7 +178,7 @@ __global__ __launch_bounds__(256) void cn_loss_finish_kernel(const uint16_t *__r
     const size_t row0 = (size_t)b * p.M;
     for (int k = threadIdx.x; k < p.M; k += 256) {
         const int i = ind[row0 + k];
-        s_ind[k] = cnl_slot_valid(mask[row0 + k], i, p.HW) ? i : -1;
+        s_ind[k] = slot_valid(mask[row0 + k], i, p.HW) ? i : -1;
     }
     __syncthreads();
     for (int k = threadIdx.x; k < p.M; k += 256) {
@@ -247,19 +195,19 @@ __global__ __launch_bounds__(256) void cn_loss_finish_kernel(const uint16_t *__r
         for (int k2 = k; k2 < p.M; ++k2) {
             if (s_ind[k2] != i) continue;
             const float *tw = wh + (row0 + k2) * 2;
-            sw0 += cnl_sign(pw0, tw[0]);
-            sw1 += cnl_sign(pw1, tw[1]);
+            sw0 += l1_sign(pw0, tw[0]);
+            sw1 += l1_sign(pw1, tw[1]);
             if (p.use_off) {
                 const float *tr = reg + (row0 + k2) * 2;
-                so0 += cnl_sign(po0, tr[0]);
-                so1 += cnl_sign(po1, tr[1]);
+                so0 += l1_sign(po0, tr[0]);
+                so1 += l1_sign(po1, tr[1]);
             }
         }
-        grad[cell_at + p.off_wh] = cnl_reg_grad(p.wh_weight, sw0, den);
-        grad[cell_at + p.off_wh + 1] = cnl_reg_grad(p.wh_weight, sw1, den);
+        grad[cell_at + p.off_wh] = reg_grad(p.wh_weight, sw0, den);
+        grad[cell_at + p.off_wh + 1] = reg_grad(p.wh_weight, sw1, den);
         if (p.use_off) {
-            grad[cell_at + p.off_reg] = cnl_reg_grad(p.off_weight, so0, den);
-            grad[cell_at + p.off_reg + 1] = cnl_reg_grad(p.off_weight, so1, den);
+            grad[cell_at + p.off_reg] = reg_grad(p.off_weight, so0, den);
+            grad[cell_at + p.off_reg + 1] = reg_grad(p.off_weight, so1, den);
         }
     }
 }
@@ -283,13 +231,9 @@ static int cn_loss_entry(MD_AOT_ARGS, bool with_grad) {
     if (with_grad) a.require(a.same_shape(9, 0));
     a.require(at->num_classes == C && at->off_reg >= -1);
     if (int rc = a.rc()) return rc;
-    // each gradient element has one owner: the heads inside [0, Cp) and apart
     const bool has_reg = at->off_reg != -1;
     const int64_t lo[3] = {at->off_hm, at->off_wh, at->off_reg}, hi[3] = {at->off_hm + C, (int64_t)at->off_wh + 2, (int64_t)at->off_reg + 2};
-    for (int i = 0; i < (has_reg ? 3 : 2); ++i) {
-        a.require(lo[i] >= 0 && hi[i] <= Cp);
-        for (int j = i + 1; j < (has_reg ? 3 : 2); ++j) a.require(hi[i] <= lo[j] || hi[j] <= lo[i]);
-    }
+    heads_disjoint(a, lo, hi, has_reg ? 3 : 2, Cp);
     a.require(isfinite(at->hm_weight) && isfinite(at->wh_weight) && isfinite(at->off_weight));
     if (int rc = a.rc()) return rc;
     const int64_t lim = (int64_t)1 << 30;
@@ -316,19 +260,16 @@ static int cn_loss_entry(MD_AOT_ARGS, bool with_grad) {
     const int *ind = (const int *)params[2];
     const uint8_t *mask = (const uint8_t *)params[3];
     float *grad = with_grad ? (float *)params[9] : nullptr;
-    const int vec = Cp % 8 == 0 && (uintptr_t)head % 16 == 0 && (uintptr_t)grad % 16 == 0, hm_vec = (uintptr_t)hm % 16 == 0;
-    const size_t lds = CNL_LDS_HEAD + (size_t)CNL_STRIP * Cp * (with_grad ? 6 : 2);   // Cp <= 160: at most 96 + 61440 bytes
+    const int vec = strip_vec(Cp, head, grad), hm_vec = (uintptr_t)hm % 16 == 0;
+    const size_t lds = strip_lds_bytes(CNL_LDS_HEAD, CNL_STRIP, Cp, with_grad);   // Cp <= 160: at most 96 + 61440 bytes
     hipLaunchKernelGGL(cn_loss_count_kernel, dim3((unsigned)(n_chunks + B)), dim3(256), 0, s, head, hm, ind, mask, wh, reg, p, hm_vec, counts,
                        rec);
-    if (with_grad) {
-        hipLaunchKernelGGL(cn_loss_dense_kernel<true>, dim3((unsigned)n_strips), dim3(256), lds, s, head, hm, p, vec, counts, part, grad);
-        hipLaunchKernelGGL(cn_loss_finish_kernel<true>, dim3((unsigned)B), dim3(256), 0, s, head, ind, mask, wh, reg, p, counts, rec, part,
-                           (int)n_strips, (float *)params[6], (float *)params[7], (float *)params[8], grad);
-    } else {
-        hipLaunchKernelGGL(cn_loss_dense_kernel<false>, dim3((unsigned)n_strips), dim3(256), lds, s, head, hm, p, vec, counts, part, grad);
-        hipLaunchKernelGGL(cn_loss_finish_kernel<false>, dim3(1), dim3(256), 0, s, head, ind, mask, wh, reg, p, counts, rec, part,
-                           (int)n_strips, (float *)params[6], (float *)params[7], (float *)params[8], grad);
-    }
+    grad_or_not(with_grad, [&](auto g) {   // the forward alone needs workgroup 0 of the finish kernel only
+        constexpr bool GRAD = decltype(g)::value;
+        hipLaunchKernelGGL(cn_loss_dense_kernel<GRAD>, dim3((unsigned)n_strips), dim3(256), lds, s, head, hm, p, vec, counts, part, grad);
+        hipLaunchKernelGGL(cn_loss_finish_kernel<GRAD>, dim3(GRAD ? (unsigned)B : 1u), dim3(256), 0, s, head, ind, mask, wh, reg, p, counts, rec,
+                           part, (int)n_strips, (float *)params[6], (float *)params[7], (float *)params[8], grad);
+    });
     return launched();
 }
 

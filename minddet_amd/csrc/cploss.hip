@@ -13,12 +13,8 @@
 //                          the gradient, workgroup (task, sample) writes the elements that slots touch: of the slots sharing a cell
 //                          (and class) the first sums its siblings in slot order and stores the element once, from the float64 sum
 // Arithmetic: every term and every sum in float64, rounded to fp32 once on output (the header says why).
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-
-#include "aot.h"
-#include "device.h"
+// The block sums and their order, the focal terms, the strip staging and the entry's ownership rule: loss_common.h.
+#include "loss_common.h"
 #include "../../include/minddet_hip_cploss.h"
 
 #pragma clang fp contract(off)
@@ -43,41 +39,7 @@ struct CplParams {
     CplTask task[MD_CP_MAX_TASKS];
 };
 
-// p = clip(sigmoid(x), 1e-4, 1 - 1e-4); open: the clip passes the gradient
-__device__ __forceinline__ double clipped_p(float x, bool &open) {
-    const double s = 1.0 / (1.0 + exp(-(double)x));
-    open = s > 1e-4 && s < 1.0 - 1e-4;
-    return fmin(fmax(s, 1e-4), 1.0 - 1e-4);
-}
-// the negative focal term log(1 - p) p^2 (1 - hm)^4 and its derivative with respect to the logit (0 where the clip is active)
-__device__ __forceinline__ void neg_term(double p, bool open, float hmv, double &loss, double &dloss) {
-    const double q = 1.0 - (double)hmv, q2 = q * q, g4 = q2 * q2;
-    const double l1p = log(1.0 - p);
-    loss = l1p * (p * p) * g4;
-    dloss = open ? g4 * (p * p) * (2.0 * (1.0 - p) * l1p - p) : 0.0;
-}
-// the positive focal term log(p) (1 - p)^2 and its derivative with respect to the logit
-__device__ __forceinline__ void pos_term(double p, bool open, double &loss, double &dloss) {
-    const double lp = log(p), om = 1.0 - p;
-    loss = lp * (om * om);
-    dloss = open ? (om * om) * (om - 2.0 * p * lp) : 0.0;
-}
-__device__ __forceinline__ bool slot_valid(int m, int i, int c, int HW, int nc) { return m != 0 && i >= 0 && i < HW && c >= 0 && c < nc; }
-
-// N block sums at once, in a fixed order (256 lanes; red: 4 N doubles); every lane gets the sums
-template <int N> __device__ __forceinline__ void block_sums(double (&v)[N], double *red) {
-#pragma unroll
-    for (int e = 0; e < N; ++e)
-        for (int off = 32; off > 0; off >>= 1) v[e] += __shfl_down(v[e], off, 64);
-    __syncthreads();   // red may still be read from an earlier call
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int e = 0; e < N; ++e) red[(threadIdx.x >> 6) * N + e] = v[e];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int e = 0; e < N; ++e) v[e] = ((red[e] + red[N + e]) + red[2 * N + e]) + red[3 * N + e];
-}
+__device__ __forceinline__ bool slot_valid(int m, int i, int c, int HW, int nc) { return slot_valid(m, i, HW) && c >= 0 && c < nc; }
 
 __global__ __launch_bounds__(256) void cp_loss_slot_kernel(const uint16_t *__restrict__ head, const float *__restrict__ anno,
                                                            const int *__restrict__ ind, const uint8_t *__restrict__ mask,
@@ -95,10 +57,8 @@ __global__ __launch_bounds__(256) void cp_loss_slot_kernel(const uint16_t *__res
         const uint16_t *cell = head + ((size_t)b * p.HW + i) * p.Cp;
         bool open;
         const double pr = clipped_p(bf2f(cell[tk.off_hm + c]), open);
-        double loss, dloss;
-        pos_term(pr, open, loss, dloss);
         acc[0] += 1.0;
-        acc[1] += loss;
+        acc[1] += pos_term(pr);
         const float *target = anno + (row0 + k) * 10;
 #pragma unroll
         for (int j = 0; j < 10; ++j)
@@ -130,20 +90,10 @@ __global__ __launch_bounds__(256) void cp_loss_dense_kernel(const uint16_t *__re
     uint16_t *sh = (uint16_t *)(smem + CPL_LDS_HEAD);                            // [CPL_STRIP][Cp] bf16
     float *sg = (float *)(smem + CPL_LDS_HEAD + (size_t)CPL_STRIP * p.Cp * 2);   // [CPL_STRIP][Cp] f32 (GRAD)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int b = blockIdx.x / p.strips_per_sample, n0 = (blockIdx.x - b * p.strips_per_sample) * CPL_STRIP;
-    const int cells = min(CPL_STRIP, p.HW - n0), elems = cells * p.Cp;
-    const size_t base = ((size_t)b * p.HW + n0) * p.Cp;
+    const Strip st = strip_of_block(p.strips_per_sample, CPL_STRIP, p.HW, p.Cp);
+    const int b = st.b, n0 = st.n0, cells = st.cells;
 
-    if (vec) {   // Cp a multiple of 8 and both pointers 16-byte aligned: the strip starts on a 16-byte boundary in head and in grad
-        const uint4 *src = (const uint4 *)(head + base);
-        for (int i = threadIdx.x; i < elems / 8; i += 256) ((uint4 *)sh)[i] = src[i];
-        if (GRAD)
-            for (int i = threadIdx.x; i < elems / 4; i += 256) ((float4 *)sg)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    } else {
-        for (int i = threadIdx.x; i < elems; i += 256) sh[i] = head[base + i];
-        if (GRAD)
-            for (int i = threadIdx.x; i < elems; i += 256) sg[i] = 0.f;
-    }
+    stage_strip<GRAD>(sh, sg, head + st.base, st.elems, vec);
     if (threadIdx.x < 32) tacc[threadIdx.x] = 0.0;
     for (int t = wave; t < p.T; t += 4) {
         const double n = wave_num_pos(rec, t, p.B, p.T, lane);
@@ -161,7 +111,9 @@ __global__ __launch_bounds__(256) void cp_loss_dense_kernel(const uint16_t *__re
             if (lane < cells) {
                 bool open;
                 const double pr = clipped_p(bf2f(sh[lane * p.Cp + off_hm + c]), open);
-                neg_term(pr, open, hm[(((size_t)b * p.T + t) * p.C + c) * p.HW + n0 + lane], loss, dloss);
+                const float hmv = hm[(((size_t)b * p.T + t) * p.C + c) * p.HW + n0 + lane];
+                loss = neg_term(pr, hmv);
+                dloss = neg_term_grad(pr, open, hmv);
                 if (GRAD) sg[lane * p.Cp + off_hm + c] = (float)(scale[t] * dloss);
             }
             for (int off = 32; off > 0; off >>= 1) loss += __shfl_down(loss, off, 64);
@@ -173,14 +125,7 @@ __global__ __launch_bounds__(256) void cp_loss_dense_kernel(const uint16_t *__re
         const int t = threadIdx.x;
         neg_part[(size_t)blockIdx.x * p.T + t] = ((tacc[t] + tacc[8 + t]) + tacc[16 + t]) + tacc[24 + t];
     }
-    if (GRAD) {
-        if (vec) {
-            float4 *dst = (float4 *)(grad + base);
-            for (int i = threadIdx.x; i < elems / 4; i += 256) dst[i] = ((const float4 *)sg)[i];
-        } else {
-            for (int i = threadIdx.x; i < elems; i += 256) grad[base + i] = sg[i];
-        }
-    }
+    if (GRAD) flush_strip(grad + st.base, sg, st.elems, vec);
 }
 
 template <bool GRAD>
@@ -276,9 +221,9 @@ __global__ __launch_bounds__(512) void cp_loss_finish_kernel(const uint16_t *__r
         {
             bool open;
             const double pr = clipped_p(bf2f(cell[tk.off_hm + c]), open);
-            double nl, nd, pl, pd, sum = 0.0;
-            neg_term(pr, open, hm[(((size_t)b * p.T + t) * p.C + c) * p.HW + i], nl, nd);
-            pos_term(pr, open, pl, pd);
+            const float hmv = hm[(((size_t)b * p.T + t) * p.C + c) * p.HW + i];
+            const double nd = neg_term_grad(pr, open, hmv), pd = pos_term_grad(pr, open);
+            double sum = 0.0;
             for (int r = 0; r < after_class; ++r) sum += pd;   // the siblings' terms are equal (one p): added one by one, in slot order
             grad[cell_at + tk.off_hm + c] = (float)(scale * (nd + sum));
         }
@@ -298,7 +243,7 @@ __global__ __launch_bounds__(512) void cp_loss_finish_kernel(const uint16_t *__r
                 for (int j = 0; j < 10; ++j) {
                     if (j < tk.ncol) {
                         const float tv = target[tk.tcol[j]];
-                        sgn[j] += (pred[j] > tv) - (pred[j] < tv);
+                        sgn[j] += l1_sign(pred[j], tv);
                     }
                 }
             }
@@ -341,7 +286,6 @@ static int cp_loss_entry(MD_AOT_ARGS, bool with_grad) {
         const int64_t first[6] = {s.off_reg, s.off_height, s.off_dim, s.off_rot, s.off_hm, s.off_vel};
         const int64_t width[6] = {2, 1, 3, 2, s.num_classes, 2};
         for (int h = 0; h < (vel ? 6 : 5); ++h) {
-            a.require(first[h] >= 0 && first[h] + width[h] <= Cp);
             lo[n_range] = first[h];
             hi[n_range++] = first[h] + width[h];
         }
@@ -357,9 +301,7 @@ static int cp_loss_entry(MD_AOT_ARGS, bool with_grad) {
         tk.nc = s.num_classes;
         max_nc = s.num_classes > max_nc ? s.num_classes : max_nc;
     }
-    if (int rc = a.rc()) return rc;
-    for (int i = 0; i < n_range; ++i)
-        for (int j = i + 1; j < n_range; ++j) a.require(hi[i] <= lo[j] || hi[j] <= lo[i]);   // each gradient element has one owner
+    heads_disjoint(a, lo, hi, n_range, Cp);
     a.require(C == max_nc && isfinite(at->weight));
     for (int j = 0; j < 10; ++j) a.require(isfinite(at->code_weights[j]));
     if (int rc = a.rc()) return rc;
@@ -379,18 +321,15 @@ static int cp_loss_entry(MD_AOT_ARGS, bool with_grad) {
     const int *ind = (const int *)params[3], *cat = (const int *)params[5];
     const uint8_t *mask = (const uint8_t *)params[4];
     float *grad = with_grad ? (float *)params[9] : nullptr;
-    const int vec = Cp % 8 == 0 && (uintptr_t)head % 16 == 0 && (uintptr_t)grad % 16 == 0;
-    const size_t lds = CPL_LDS_HEAD + (size_t)CPL_STRIP * Cp * (with_grad ? 6 : 2);
+    const int vec = strip_vec(Cp, head, grad);
+    const size_t lds = strip_lds_bytes(CPL_LDS_HEAD, CPL_STRIP, Cp, with_grad);
     hipLaunchKernelGGL(cp_loss_slot_kernel, dim3((unsigned)T, (unsigned)B), dim3(256), 0, s, head, anno, ind, mask, cat, p, rec);
-    if (with_grad) {
-        hipLaunchKernelGGL(cp_loss_dense_kernel<true>, dim3((unsigned)n_strips), dim3(256), lds, s, head, hm, p, vec, rec, neg_part, grad);
-        hipLaunchKernelGGL(cp_loss_finish_kernel<true>, dim3((unsigned)T, (unsigned)B), dim3(512), 0, s, head, hm, anno, ind, mask, cat, p, rec,
-                           neg_part, (int)n_strips, (float *)params[6], (float *)params[7], (float *)params[8], grad);
-    } else {
-        hipLaunchKernelGGL(cp_loss_dense_kernel<false>, dim3((unsigned)n_strips), dim3(256), lds, s, head, hm, p, vec, rec, neg_part, grad);
-        hipLaunchKernelGGL(cp_loss_finish_kernel<false>, dim3(1, 1), dim3(512), 0, s, head, hm, anno, ind, mask, cat, p, rec, neg_part,
-                           (int)n_strips, (float *)params[6], (float *)params[7], (float *)params[8], grad);
-    }
+    grad_or_not(with_grad, [&](auto g) {   // the forward alone needs workgroup (0, 0) of the finish kernel only
+        constexpr bool GRAD = decltype(g)::value;
+        hipLaunchKernelGGL(cp_loss_dense_kernel<GRAD>, dim3((unsigned)n_strips), dim3(256), lds, s, head, hm, p, vec, rec, neg_part, grad);
+        hipLaunchKernelGGL(cp_loss_finish_kernel<GRAD>, GRAD ? dim3((unsigned)T, (unsigned)B) : dim3(1, 1), dim3(512), 0, s, head, hm, anno, ind,
+                           mask, cat, p, rec, neg_part, (int)n_strips, (float *)params[6], (float *)params[7], (float *)params[8], grad);
+    });
     return launched();
 }
 

@@ -14,12 +14,8 @@
 //                          partials (loc, cls, dir, cls_pos, cls_neg; already divided by n_b) per strip in the workspace
 //   pp_loss_finish_kernel  one workgroup reduces the partials in a fixed order into parts / total and writes num_pos
 // Arithmetic: every term and every sum in float64, rounded to fp32 once on output (the header says why).
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-
-#include "aot.h"
-#include "device.h"
+// The block sums and their order, the strip staging and the entry's ownership rule: loss_common.h.
+#include "loss_common.h"
 #include "../../include/minddet_hip_pploss.h"
 
 #pragma clang fp contract(off)
@@ -39,21 +35,6 @@ struct PplParams {
     float alpha, gamma, sigma, cw[7], cls_weight, loc_weight, dir_weight, pos_cls_weight, neg_cls_weight;
 };
 
-// PPL_Q block sums at once, in a fixed order (256 lanes; red: 4 PPL_Q doubles); every lane gets the sums
-__device__ __forceinline__ void ppl_block_sums(double (&v)[PPL_Q], double *red) {
-#pragma unroll
-    for (int e = 0; e < PPL_Q; ++e)
-        for (int off = 32; off > 0; off >>= 1) v[e] += __shfl_down(v[e], off, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int e = 0; e < PPL_Q; ++e) red[(threadIdx.x >> 6) * PPL_Q + e] = v[e];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int e = 0; e < PPL_Q; ++e) v[e] = ((red[e] + red[PPL_Q + e]) + red[2 * PPL_Q + e]) + red[3 * PPL_Q + e];
-}
-
 // softplus(s) = max(s, 0) + log1p(exp(-|s|)), m = sigmoid(s) and om = 1 - sigmoid(s) = sigmoid(-s), none of them by a subtraction from 1
 __device__ __forceinline__ void softplus_sigmoid(double s, double &sp, double &m, double &om) {
     const double e = exp(-fabs(s)), r = 1.0 / (1.0 + e);
@@ -70,10 +51,8 @@ __global__ __launch_bounds__(256) void pp_loss_count_kernel(const int *__restric
     const int *src = labels + (size_t)b * N + c0;
     int cnt = 0;
     for (int i = threadIdx.x; i < n; i += 256) cnt += src[i] > 0;
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) counts[(size_t)b * chunks_per_sample + blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+    cnt = block_count(cnt, red);
+    if (threadIdx.x == 0) counts[(size_t)b * chunks_per_sample + blockIdx.x] = cnt;
 }
 
 template <bool GRAD>
@@ -88,21 +67,11 @@ __global__ __launch_bounds__(256) void pp_loss_dense_kernel(const uint16_t *__re
     uint16_t *sh = (uint16_t *)(smem + PPL_LDS_HEAD + (size_t)PPL_STRIP * p.A * 4);         // [PPL_STRIP][C] bf16
     float *sg = (float *)(smem + PPL_LDS_HEAD + (size_t)PPL_STRIP * (p.A * 4 + p.C * 2));   // [PPL_STRIP][C] f32 (GRAD)
     const int lane = threadIdx.x & 63;
-    const int b = blockIdx.x / p.strips_per_sample, n0 = (blockIdx.x - b * p.strips_per_sample) * PPL_STRIP;
-    const int cells = min(PPL_STRIP, p.HW - n0), elems = cells * p.C, nanch = cells * p.A;
-    const size_t base = ((size_t)b * p.HW + n0) * p.C;          // of the strip in head and grad
+    const Strip st = strip_of_block(p.strips_per_sample, PPL_STRIP, p.HW, p.C);
+    const int b = st.b, n0 = st.n0, nanch = st.cells * p.A;
     const size_t anchor0 = (size_t)b * p.N + (size_t)n0 * p.A;  // of the strip's first anchor in labels and reg_targets
 
-    if (vec) {   // H W C a multiple of 8 and both pointers 16-byte aligned: every strip starts on a 16-byte boundary in head and in grad
-        const uint4 *src = (const uint4 *)(head + base);
-        for (int i = threadIdx.x; i < elems / 8; i += 256) ((uint4 *)sh)[i] = src[i];
-        if (GRAD)
-            for (int i = threadIdx.x; i < elems / 4; i += 256) ((float4 *)sg)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    } else {
-        for (int i = threadIdx.x; i < elems; i += 256) sh[i] = head[base + i];
-        if (GRAD)
-            for (int i = threadIdx.x; i < elems; i += 256) sg[i] = 0.f;
-    }
+    stage_strip<GRAD>(sh, sg, head + st.base, st.elems, vec);
     for (int i = threadIdx.x; i < nanch; i += 256) s_lab[i] = labels[anchor0 + i];
     if (threadIdx.x < 64) {   // the sample's positives: a sum of exact integers
         int n = 0;
@@ -184,7 +153,7 @@ __global__ __launch_bounds__(256) void pp_loss_dense_kernel(const uint16_t *__re
         }
     }
 
-    ppl_block_sums(acc, red);
+    block_sums<PPL_Q>(acc, red);
     if (threadIdx.x == 0) {
         double *dst = part + (size_t)blockIdx.x * PPL_Q;
         dst[0] = acc[0] / nb;
@@ -193,14 +162,7 @@ __global__ __launch_bounds__(256) void pp_loss_dense_kernel(const uint16_t *__re
         dst[3] = acc[3];
         dst[4] = acc[4];
     }
-    if (GRAD) {   // (the block sums' barriers stand between the last write of sg and these reads)
-        if (vec) {
-            float4 *dst = (float4 *)(grad + base);
-            for (int i = threadIdx.x; i < elems / 4; i += 256) dst[i] = ((const float4 *)sg)[i];
-        } else {
-            for (int i = threadIdx.x; i < elems; i += 256) grad[base + i] = sg[i];
-        }
-    }
+    if (GRAD) flush_strip(grad + st.base, sg, st.elems, vec);   // (the block sums' barriers stand between the last write of sg and these reads)
 }
 
 __global__ __launch_bounds__(256) void pp_loss_finish_kernel(const double *__restrict__ part, const int *__restrict__ counts, PplParams p,
@@ -212,7 +174,7 @@ __global__ __launch_bounds__(256) void pp_loss_finish_kernel(const double *__res
 #pragma unroll
         for (int e = 0; e < PPL_Q; ++e) acc[e] += part[(size_t)i * PPL_Q + e];
     }
-    ppl_block_sums(acc, red);
+    block_sums<PPL_Q>(acc, red);
     if (threadIdx.x == 0) {
         const double batch = (double)p.B;
         const double loc = (double)p.loc_weight * acc[0] / batch, cls = (double)p.cls_weight * acc[1] / batch;
@@ -248,14 +210,11 @@ static int pp_loss_entry(MD_AOT_ARGS, bool with_grad) {
     a.require(h.num_anchors >= 1 && h.num_classes >= 1 && h.score_mode == 0 && h.self_train == 1 && h.off_dir >= -1);
     if (int rc = a.rc()) return rc;
     const int64_t A = h.num_anchors, K = h.num_classes, HW = H * W;
-    // each gradient element has one owner: the heads inside [0, C) and apart (A K <= C, so the products below are small)
+    // (A K <= C, so the products below are small)
     const bool dir = h.off_dir != -1;
     const int64_t lo[3] = {h.off_cls, h.off_box, h.off_dir}, hi[3] = {h.off_cls + A * K, h.off_box + A * 7, h.off_dir + A * 2};
     a.require(A <= C && K <= C);
-    for (int i = 0; i < (dir ? 3 : 2); ++i) {
-        a.require(lo[i] >= 0 && hi[i] <= C);
-        for (int j = i + 1; j < (dir ? 3 : 2); ++j) a.require(hi[i] <= lo[j] || hi[j] <= lo[i]);
-    }
+    heads_disjoint(a, lo, hi, dir ? 3 : 2, C);
     if (int rc = a.rc()) return rc;
     const int64_t lim = (int64_t)1 << 30;
     const bool big = B >= lim || HW >= lim || HW * A >= lim;   // N itself past the limit: the extents below cannot be compared safely
@@ -293,15 +252,13 @@ static int pp_loss_entry(MD_AOT_ARGS, bool with_grad) {
     const int *labels = (const int *)params[1];
     const float *reg = (const float *)params[2], *anchors = (const float *)params[3];
     float *grad = with_grad ? (float *)params[7] : nullptr;
-    const int vec = (HW * C) % 8 == 0 && (uintptr_t)head % 16 == 0 && (uintptr_t)grad % 16 == 0;
-    const size_t lds = PPL_LDS_HEAD + (size_t)PPL_STRIP * (A * 4 + C * (with_grad ? 6 : 2));   // 8 A <= C <= 128: at most 176 + 64 (64 + 768) = 53424 bytes
+    const int vec = strip_vec(HW * C, head, grad);   // (a sample's H W C elements: C itself need not be a multiple of 8)
+    const size_t lds = strip_lds_bytes(PPL_LDS_HEAD, PPL_STRIP, C, with_grad, A * 4);   // 8 A <= C <= 128: at most 176 + 64 (64 + 768) = 53424 bytes
     hipLaunchKernelGGL(pp_loss_count_kernel, dim3((unsigned)cps, (unsigned)B), dim3(256), 0, s, labels, (int)N, (int)cps, counts);
-    if (with_grad)
-        hipLaunchKernelGGL(pp_loss_dense_kernel<true>, dim3((unsigned)n_strips), dim3(256), lds, s, head, labels, reg, anchors, p, vec, counts,
-                           part, grad);
-    else
-        hipLaunchKernelGGL(pp_loss_dense_kernel<false>, dim3((unsigned)n_strips), dim3(256), lds, s, head, labels, reg, anchors, p, vec, counts,
-                           part, grad);
+    grad_or_not(with_grad, [&](auto g) {
+        hipLaunchKernelGGL(pp_loss_dense_kernel<decltype(g)::value>, dim3((unsigned)n_strips), dim3(256), lds, s, head, labels, reg, anchors, p, vec,
+                           counts, part, grad);
+    });
     hipLaunchKernelGGL(pp_loss_finish_kernel, dim3(1), dim3(256), 0, s, part, counts, p, (int)n_strips, (float *)params[4], (float *)params[5],
                        (float *)params[6]);
     return launched();

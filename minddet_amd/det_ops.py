@@ -1253,6 +1253,54 @@ def anchors_mask_batched(coors, voxel_num, grid_size_xy, anchors_bv, voxel_size,
     return (mask, area) if with_area else mask
 
 
+# ----------------------------------------------------------------------------- training operators: outputs, head losses
+def _out_dict(who, want, out, dev):
+    """want: {key: (shape, dtype)} -> `out` checked against it, or a new dict of empty tensors on dev"""
+    if out is None:
+        out = {k: torch.empty(shp, dtype=dt, device=dev) for k, (shp, dt) in want.items()}
+    for k, (shp, dt) in want.items():
+        if tuple(out[k].shape) != shp or out[k].dtype != dt:
+            raise ValueError(f"{who}: out[{k!r}] has to be {dt} of shape {shp}")
+    return out
+
+
+def _bf16_head(who, head, layout):
+    if head.dtype != torch.bfloat16 or head.dim() != 4:
+        raise ValueError(f"{who}: head has to be {layout} bfloat16")
+    return head.contiguous()
+
+
+def _head_loss(who, sym, head, operands, want, ws_bytes, at, grad, out):
+    """One call of a loss over a merged head tensor (the head _bf16_head returned): `sym`(head, *operands, parts, num_pos, total,
+    workspace) or, with grad, `sym`_grad with grad (head's shape, f32) in front of the workspace.  want: (shape, dtype) of parts and
+    num_pos -> the dict of total, parts, num_pos [, grad]."""
+    want = dict(total=((1,), torch.float32), **want)
+    if grad:
+        want["grad"] = (tuple(head.shape), torch.float32)
+    out = _out_dict(who, want, out, head.device)
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=head.device)
+    outs = [out["parts"], out["num_pos"], out["total"]] + ([out["grad"]] if grad else [])
+    _lib.call(sym + "_grad" if grad else sym, [head, *operands, *outs, ws], extra=at)
+    return out
+
+
+class _HeadLossFn(torch.autograd.Function):
+    """call(head) -> the dict of a *_loss with grad=True; the differentiable form of all three"""
+
+    @staticmethod
+    def forward(ctx, head, call):
+        out = call(head.detach())
+        ctx.save_for_backward(out["grad"])
+        ctx.head_dtype = head.dtype
+        ctx.mark_non_differentiable(out["parts"], out["num_pos"])
+        return out["total"], out["parts"], out["num_pos"]
+
+    @staticmethod
+    def backward(ctx, g_total, g_parts, g_num_pos):
+        (grad,) = ctx.saved_tensors
+        return (g_total.to(torch.float32) * grad).to(ctx.head_dtype), None
+
+
 # ----------------------------------------------------------------------------- CenterPoint training targets (csrc/cptargets.hip)
 class _CPTargetsAttrs(ctypes.Structure):
     _fields_ = [("num_tasks", ctypes.c_int32), ("num_classes", ctypes.c_int32 * 8), ("voxel_size", ctypes.c_float * 2),
@@ -1290,11 +1338,7 @@ def cp_assign_targets(gt_boxes, gt_classes, *, tasks, voxel_size, pc_range, out_
     W, H = int(feature_map_size[0]), int(feature_map_size[1])
     want = dict(hm=((B, T, C, H, W), torch.float32), anno_box=((B, T, M, 10), torch.float32), ind=((B, T, M), torch.int32),
                 mask=((B, T, M), torch.uint8), cat=((B, T, M), torch.int32), gt_boxes_and_cls=((B, M, 10), torch.float32))
-    if out is None:
-        out = {k: torch.empty(shp, dtype=dt, device=dev) for k, (shp, dt) in want.items()}
-    for k, (shp, dt) in want.items():
-        if tuple(out[k].shape) != shp or out[k].dtype != dt:
-            raise ValueError(f"cp_assign_targets: out[{k!r}] has to be {dt} of shape {shp}")
+    out = _out_dict("cp_assign_targets", want, out, dev)
     ws = torch.empty((max(B * T * (G + 1), 1) * 16,), dtype=torch.uint8, device=dev)
     _lib.call("md_cp_assign_targets", [g, cls, out["hm"], out["anno_box"], out["ind"], out["mask"], out["cat"], out["gt_boxes_and_cls"], ws],
               extra=at)
@@ -1367,28 +1411,12 @@ def cp_loss(head, targets, at, grad=False, out=None):
     box_loss[10]), num_pos [T] f32 and, with grad=True, grad [B,H,W,Cp] f32 = d total / d head.  Every element of every output is
     written, so `out` (such a dict from an earlier call) can be reused without clearing.  A slot whose ind or cat is out of range is
     skipped as if masked."""
-    if head.dtype != torch.bfloat16 or head.dim() != 4:
-        raise ValueError("cp_loss: head has to be [B,H,W,Cp] bfloat16")
-    head = head.contiguous()
-    dev = head.device
+    head = _bf16_head("cp_loss", head, "[B,H,W,Cp]")
     B, H, W, _ = head.shape
     T = int(at.num_tasks)
-    want = dict(total=((1,), torch.float32), parts=((T, 12), torch.float32), num_pos=((T,), torch.float32))
-    if grad:
-        want["grad"] = (tuple(head.shape), torch.float32)
-    if out is None:
-        out = {k: torch.empty(shp, dtype=dt, device=dev) for k, (shp, dt) in want.items()}
-    for k, (shp, dt) in want.items():
-        if tuple(out[k].shape) != shp or out[k].dtype != dt:
-            raise ValueError(f"cp_loss: out[{k!r}] has to be {dt} of shape {shp}")
-    ws = torch.empty((cp_loss_workspace_bytes(B, T, H, W),), dtype=torch.uint8, device=dev)
-    ops = [head, targets["hm"], targets["anno_box"], targets["ind"], targets["mask"], targets["cat"], out["parts"], out["num_pos"],
-           out["total"]]
-    if grad:
-        _lib.call("md_cp_loss_grad", ops + [out["grad"], ws], extra=at)
-    else:
-        _lib.call("md_cp_loss", ops + [ws], extra=at)
-    return out
+    want = dict(parts=((T, 12), torch.float32), num_pos=((T,), torch.float32))
+    return _head_loss("cp_loss", "md_cp_loss", head, [targets[k] for k in ("hm", "anno_box", "ind", "mask", "cat")], want,
+                      cp_loss_workspace_bytes(B, T, H, W), at, grad, out)
 
 
 class CenterPointLoss:
@@ -1416,25 +1444,10 @@ class CenterPointLoss:
         return cp_loss(head, targets, self.at, grad=grad, out=out)
 
 
-class _CenterPointLossFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, head, targets, loss):
-        out = cp_loss(head.detach(), targets, loss.at, grad=True)
-        ctx.save_for_backward(out["grad"])
-        ctx.head_dtype = head.dtype
-        ctx.mark_non_differentiable(out["parts"], out["num_pos"])
-        return out["total"], out["parts"], out["num_pos"]
-
-    @staticmethod
-    def backward(ctx, g_total, g_parts, g_num_pos):
-        (grad,) = ctx.saved_tensors
-        return (g_total.to(torch.float32) * grad).to(ctx.head_dtype), None, None
-
-
 def center_point_loss(head, targets, loss):
     """differentiable form: -> (total [1] f32, parts [T,12], num_pos [T]); the forward runs md_cp_loss_grad once, the backward returns
     grad_output x (d total / d head) in the head's dtype.  parts and num_pos carry no gradient."""
-    return _CenterPointLossFn.apply(head, targets, loss)
+    return _HeadLossFn.apply(head, lambda h: cp_loss(h, targets, loss.at, grad=True))
 
 
 # ----------------------------------------------------------------------------- KITTI PointPillars training loss (csrc/pploss.hip)
@@ -1484,31 +1497,16 @@ def pp_loss(head, labels, reg_targets, anchors, at, grad=False, out=None):
     total [1] f32, parts [5] f32 (loc, cls, dir as they enter the total, cls_pos, cls_neg), num_pos [B] f32 and, with grad=True, grad
     [B,H,W,C] f32 = d total / d head.  Every element of every output is written, so `out` (such a dict from an earlier call) can be
     reused without clearing."""
-    if head.dtype != torch.bfloat16 or head.dim() != 4:
-        raise ValueError("pp_loss: head has to be [B,H,W,C] bfloat16")
-    head = head.contiguous()
-    dev = head.device
+    head = _bf16_head("pp_loss", head, "[B,H,W,C]")
     B, H, W, _ = head.shape
     A = int(at.head.num_anchors)
     n = H * W * A
     if tuple(labels.shape) != (B, n) or labels.dtype != torch.int32 or tuple(reg_targets.shape) != (B, n, 7):
         raise ValueError(f"pp_loss: labels has to be int32 [{B}, {n}] and reg_targets [{B}, {n}, 7], got {tuple(labels.shape)} "
                          f"{labels.dtype} / {tuple(reg_targets.shape)}")
-    want = dict(total=((1,), torch.float32), parts=((5,), torch.float32), num_pos=((B,), torch.float32))
-    if grad:
-        want["grad"] = (tuple(head.shape), torch.float32)
-    if out is None:
-        out = {k: torch.empty(shp, dtype=dt, device=dev) for k, (shp, dt) in want.items()}
-    for k, (shp, dt) in want.items():
-        if tuple(out[k].shape) != shp or out[k].dtype != dt:
-            raise ValueError(f"pp_loss: out[{k!r}] has to be {dt} of shape {shp}")
-    ws = torch.empty((pp_loss_workspace_bytes(B, H, W, A),), dtype=torch.uint8, device=dev)
-    ops = [head, labels.contiguous(), _f32c(reg_targets), _f32c(anchors).reshape(-1, 7), out["parts"], out["num_pos"], out["total"]]
-    if grad:
-        _lib.call("md_pp_loss_grad", ops + [out["grad"], ws], extra=at)
-    else:
-        _lib.call("md_pp_loss", ops + [ws], extra=at)
-    return out
+    want = dict(parts=((5,), torch.float32), num_pos=((B,), torch.float32))
+    return _head_loss("pp_loss", "md_pp_loss", head, [labels.contiguous(), _f32c(reg_targets), _f32c(anchors).reshape(-1, 7)], want,
+                      pp_loss_workspace_bytes(B, H, W, A), at, grad, out)
 
 
 class PointPillarsLoss:
@@ -1547,25 +1545,10 @@ class PointPillarsLoss:
         return pp_loss(head, labels, reg_targets, anchors, self.at, grad=grad, out=out)
 
 
-class _PointPillarsLossFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, head, labels, reg_targets, anchors, loss):
-        out = pp_loss(head.detach(), labels, reg_targets, anchors, loss.at, grad=True)
-        ctx.save_for_backward(out["grad"])
-        ctx.head_dtype = head.dtype
-        ctx.mark_non_differentiable(out["parts"], out["num_pos"])
-        return out["total"], out["parts"], out["num_pos"]
-
-    @staticmethod
-    def backward(ctx, g_total, g_parts, g_num_pos):
-        (grad,) = ctx.saved_tensors
-        return (g_total.to(torch.float32) * grad).to(ctx.head_dtype), None, None, None, None
-
-
 def point_pillars_loss(head, labels, reg_targets, anchors, loss):
     """differentiable form: -> (total [1] f32, parts [5], num_pos [B]); the forward runs md_pp_loss_grad once, the backward returns
     grad_output x (d total / d head) in the head's dtype.  parts and num_pos carry no gradient."""
-    return _PointPillarsLossFn.apply(head, labels, reg_targets, anchors, loss)
+    return _HeadLossFn.apply(head, lambda h: pp_loss(h, labels, reg_targets, anchors, loss.at, grad=True))
 
 
 def assign_targets_batch(anchors, gt_boxes, gt_classes, matched_thr, unmatched_thr, anchors_mask=None):
@@ -1605,11 +1588,7 @@ def cn_assign_targets(boxes, classes, *, num_classes, feature_map_size, max_objs
     W, H = int(feature_map_size[0]), int(feature_map_size[1])
     want = dict(hm=((B, C, H, W), torch.float32), ind=((B, M), torch.int32), reg_mask=((B, M), torch.uint8), wh=((B, M, 2), torch.float32),
                 reg=((B, M, 2), torch.float32))
-    if out is None:
-        out = {k: torch.empty(shp, dtype=dt, device=dev) for k, (shp, dt) in want.items()}
-    for k, (shp, dt) in want.items():
-        if tuple(out[k].shape) != shp or out[k].dtype != dt:
-            raise ValueError(f"cn_assign_targets: out[{k!r}] has to be {dt} of shape {shp}")
+    out = _out_dict("cn_assign_targets", want, out, dev)
     ws = torch.empty((max(B * M, 1) * 16,), dtype=torch.uint8, device=dev)
     _lib.call("md_cn_assign_targets", [g, cls, out["hm"], out["ind"], out["reg_mask"], out["wh"], out["reg"], ws], extra=at)
     return out
@@ -1680,27 +1659,11 @@ def cn_loss(head, targets, at, grad=False, out=None):
     the dict of cn_assign_targets (hm, ind, reg_mask, wh, reg) -> dict with total [1] f32, parts [3] f32 (hm_loss, wh_loss, off_loss),
     num_pos [1] f32 and, with grad=True, grad [B,H,W,Cp] f32 = d total / d head.  Every element of every output is written, so `out`
     (such a dict from an earlier call) can be reused without clearing.  A slot whose ind is out of range is skipped as if masked."""
-    if head.dtype != torch.bfloat16 or head.dim() != 4:
-        raise ValueError("cn_loss: head has to be [B,H,W,Cp] bfloat16")
-    head = head.contiguous()
-    dev = head.device
+    head = _bf16_head("cn_loss", head, "[B,H,W,Cp]")
     B, H, W, _ = head.shape
-    want = dict(total=((1,), torch.float32), parts=((3,), torch.float32), num_pos=((1,), torch.float32))
-    if grad:
-        want["grad"] = (tuple(head.shape), torch.float32)
-    if out is None:
-        out = {k: torch.empty(shp, dtype=dt, device=dev) for k, (shp, dt) in want.items()}
-    for k, (shp, dt) in want.items():
-        if tuple(out[k].shape) != shp or out[k].dtype != dt:
-            raise ValueError(f"cn_loss: out[{k!r}] has to be {dt} of shape {shp}")
-    ws = torch.empty((cn_loss_workspace_bytes(B, int(at.num_classes), H, W),), dtype=torch.uint8, device=dev)
-    ops = [head, targets["hm"], targets["ind"], targets["reg_mask"], targets["wh"], targets["reg"], out["parts"], out["num_pos"],
-           out["total"]]
-    if grad:
-        _lib.call("md_cn_loss_grad", ops + [out["grad"], ws], extra=at)
-    else:
-        _lib.call("md_cn_loss", ops + [ws], extra=at)
-    return out
+    want = dict(parts=((3,), torch.float32), num_pos=((1,), torch.float32))
+    return _head_loss("cn_loss", "md_cn_loss", head, [targets[k] for k in ("hm", "ind", "reg_mask", "wh", "reg")], want,
+                      cn_loss_workspace_bytes(B, int(at.num_classes), H, W), at, grad, out)
 
 
 class CenterNetLoss:
@@ -1733,22 +1696,7 @@ class CenterNetLoss:
         return cn_loss(head, targets, self.at, grad=grad, out=out)
 
 
-class _CenterNetLossFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, head, targets, loss):
-        out = cn_loss(head.detach(), targets, loss.at, grad=True)
-        ctx.save_for_backward(out["grad"])
-        ctx.head_dtype = head.dtype
-        ctx.mark_non_differentiable(out["parts"], out["num_pos"])
-        return out["total"], out["parts"], out["num_pos"]
-
-    @staticmethod
-    def backward(ctx, g_total, g_parts, g_num_pos):
-        (grad,) = ctx.saved_tensors
-        return (g_total.to(torch.float32) * grad).to(ctx.head_dtype), None, None
-
-
 def center_net_loss(head, targets, loss):
     """differentiable form: -> (total [1] f32, parts [3], num_pos [1]); the forward runs md_cn_loss_grad once, the backward returns
     grad_output x (d total / d head) in the head's dtype.  parts and num_pos carry no gradient."""
-    return _CenterNetLossFn.apply(head, targets, loss)
+    return _HeadLossFn.apply(head, lambda h: cn_loss(h, targets, loss.at, grad=True))

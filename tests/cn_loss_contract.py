@@ -5,7 +5,7 @@ tests/test_cn_loss_cpu.py compares it with a literal torch-float64 transcription
 tests/test_cn_loss_gpu.py holds the device result to it.  The comparison helpers are those of tests/cp_loss_contract.py."""
 import numpy as np
 
-from tests.cp_loss_contract import compare_grad, ulps_apart  # noqa: F401
+from tests.cp_loss_contract import compare_grad, compare_losses, ulps_apart  # noqa: F401
 
 LO, HI = 1e-4, 1 - 1e-4
 
@@ -61,13 +61,3 @@ def loss(head, hm, ind, reg_mask, wh, reg, *, num_classes, off_hm, off_wh, off_r
         out["grad"] = grad.reshape(B, H, W, Cp)
     return out
 
-
-def compare_losses(got, want):
-    """parts / num_pos / total of a result (fp32) against the contract's float64 rounded to fp32 -> the worst distance in ulp"""
-    worst = 0
-    for k in ("parts", "num_pos", "total"):
-        g = np.asarray(got[k], np.float32).reshape(-1)
-        w = np.asarray(want[k], np.float64).astype(np.float32).reshape(-1)
-        assert g.shape == w.shape and np.isfinite(g).all(), k
-        worst = max(worst, int(ulps_apart(g, w).max()))
-    return worst

@@ -2,8 +2,11 @@
 direction terms, the five parts, total, and the analytic gradient of total with respect to every head element.  Inputs are the values
 the operator is given (the bf16 head values widened exactly, the fp32 targets, anchors and attributes); nothing here is rounded.
 tests/test_pp_loss_cpu.py compares it with a literal torch-float64 transcription of the reference's loss under autograd;
-tests/test_pp_loss_gpu.py holds the device result to it.  The comparison helpers both tests use live here too.  No torch."""
+tests/test_pp_loss_gpu.py holds the device result to it.  ulps_apart and compare_losses are those of
+tests/cp_loss_contract.py; compare_grad (its structural zeros are a condition of its own) lives here.  No torch."""
 import numpy as np
+
+from tests.cp_loss_contract import compare_losses, ulps_apart  # noqa: F401
 
 DEFAULTS = dict(alpha=0.25, gamma=2.0, sigma=3.0, code_weights=(1.0,) * 7, cls_weight=1.0, loc_weight=2.0, dir_weight=0.2,
                 pos_cls_weight=1.0, neg_cls_weight=1.0)
@@ -110,25 +113,6 @@ def loss(head, labels, reg_targets, anchors, *, off_cls, off_box, off_dir, num_a
 
 
 # ---------------------------------------------------------------------------------------------------- comparison
-def ulps_apart(a, b):
-    """fp32 arrays -> how many representable values apart (signed values; -0 and +0 coincide)"""
-    def ordered(v):
-        i = np.ascontiguousarray(v, np.float32).view(np.int32).astype(np.int64)
-        return np.where(i < 0, -(i & 0x7FFFFFFF), i)
-    return np.abs(ordered(a) - ordered(b))
-
-
-def compare_losses(got, want):
-    """parts / num_pos / total of a result (fp32) against the contract's float64 rounded to fp32 -> the worst distance in ulp"""
-    worst = 0
-    for k in ("parts", "num_pos", "total"):
-        g = np.asarray(got[k], np.float32).reshape(-1)
-        w = np.asarray(want[k], np.float64).astype(np.float32).reshape(-1)
-        assert g.shape == w.shape and np.isfinite(g).all(), k
-        worst = max(worst, int(ulps_apart(g, w).max()))
-    return worst
-
-
 def compare_grad(got, want):
     """got fp32 [B,H,W,C] against the contract's result -> (elements outside the structural zeros, of those how many differ at all from
     the contract's float64 rounded to fp32, the worst distance in ulp, structural zeros whose bits are not +0.0, NaNs)"""

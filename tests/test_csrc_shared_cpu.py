@@ -1,6 +1,7 @@
 """CPU: the device code the kernels share is stated once.  A text scan of minddet_amd/csrc: the bf16 conversions, the packed ReLU, the
-buffer-descriptor flag word and the vector typedefs live in device.h, the delta-to-box arithmetic in box_codec.h, and no .hip file
-spells any of them again (a new kernel includes the header instead of copying the file before it)."""
+buffer-descriptor flag word and the vector typedefs live in device.h, the delta-to-box arithmetic in box_codec.h, the training losses'
+block sums, focal terms, strip staging and ownership rule in loss_common.h, and no .hip file spells any of them again (a new kernel
+includes the header instead of copying the file before it)."""
 import glob
 import os
 
@@ -18,11 +19,16 @@ ONLY_IN = {
     "0x7fffu +": "device.h",             # software round-to-nearest-even
     "ext_vector_type": "device.h",       # vector typedefs
     "fminf(fmaxf(dw": "box_codec.h",     # delta-to-box decode
+    "__shfl_down(v[e]": "loss_common.h",       # the losses' fixed-order block sums
+    "1.0 - 1e-4": "loss_common.h",             # the clipped sigmoid of the focal terms
+    "(pred > target)": "loss_common.h",        # the sign of an L1 term
+    "elems / 8": "loss_common.h",              # the 16-byte staging of a dense kernel's strip
+    "hi[i] <= lo[j]": "loss_common.h",         # each gradient element has one owner
 }
 
 
 def test_every_translation_unit_was_read():
-    assert len(HIP) >= 15 and {"device.h", "box_codec.h", "aot.h"} <= set(SRC)
+    assert len(HIP) >= 15 and {"device.h", "box_codec.h", "aot.h", "loss_common.h"} <= set(SRC)
 
 
 @pytest.mark.parametrize("text", list(ONLY_IN), ids=[t.strip("( +") for t in ONLY_IN])

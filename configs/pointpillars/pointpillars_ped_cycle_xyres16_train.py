@@ -44,6 +44,12 @@ train_cfg = dict(
     direction_loss_weight=0.2,
     pos_class_weight=1.0,
     neg_class_weight=1.0,
+    # the training branch of prep_pointcloud (det_ops.PointCloudAugment, model.train_example): the reference configuration's values
+    # (groundtruth_localization_noise_std, groundtruth_rotation_uniform_noise, global_rotation_uniform_noise,
+    # global_scaling_uniform_noise, global_random_rotation_range_per_object; global_loc_noise_std is fixed by its dataset builder)
+    augment=dict(gt_loc_noise_std=[0.25, 0.25, 0.25], gt_rotation_noise=[-0.15707963267, 0.15707963267],
+                 global_rotation_noise=[-0.78539816, 0.78539816], global_scaling_noise=[0.95, 1.05], global_loc_noise_std=[0.2, 0.2, 0.2],
+                 global_random_rot_range=[0, 0], num_try=100),
     assigner=dict(matched_threshold=0.5, unmatched_threshold=0.35, sample_positive_fraction=-1, sample_size=512,
                   region_similarity_calculator="nearest_iou_similarity"),
 )

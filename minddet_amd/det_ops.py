@@ -1253,6 +1253,184 @@ def anchors_mask_batched(coors, voxel_num, grid_size_xy, anchors_bv, voxel_size,
     return (mask, area) if with_area else mask
 
 
+# ----------------------------------------------------------------------------- KITTI training augmentation (csrc/pcaug.hip)
+PCAUG_MAX_BOXES, PCAUG_MAX_TRIES = 256, 128     # MD_PCAUG_MAX_BOXES, MD_PCAUG_MAX_TRIES
+
+
+class _PCBoxesAttrs(ctypes.Structure):
+    _fields_ = [("bv_range", ctypes.c_float * 4)]
+
+
+def _i32c(t, dev):
+    return t.to(device=dev, dtype=torch.int32).contiguous()
+
+
+def _f64c(t, dev):
+    return t.to(device=dev, dtype=torch.float64).contiguous()
+
+
+def pc_noise_per_object(gt_boxes, gt_count, valid, loc_noises, rot_noises, grot_noises=None):
+    """noise_per_object without groups (pointpillars/src/core/preprocess.py:560-668) for a batch on the device
+    (md_pc_noise_per_object, include/minddet_hip_pcaug.h): gt_boxes [B,G,7] f32, gt_count [B], valid [B,G], the draws loc_noises
+    [B,G,T,3], rot_noises [B,G,T] and grot_noises [B,G,T] or None (None: noise_per_box, no per-object global rotation) in float64
+    -> (selected [B,G] i32, obj_transform [B,G,4] f64, boxes_out [B,G,7] f32)."""
+    g = _f32c(gt_boxes)
+    if g.dim() != 3 or g.shape[2] != 7:
+        raise ValueError(f"pc_noise_per_object: gt_boxes are [B, G, 7] (boxes wider than 7 are not built), got {tuple(g.shape)}")
+    dev, (B, G) = g.device, g.shape[:2]
+    if G > PCAUG_MAX_BOXES or not 1 <= rot_noises.shape[-1] <= PCAUG_MAX_TRIES:
+        raise ValueError(f"pc_noise_per_object: at most {PCAUG_MAX_BOXES} boxes and 1 .. {PCAUG_MAX_TRIES} tries per sample")
+    selected = torch.empty((B, G), dtype=torch.int32, device=dev)
+    tf = torch.empty((B, G, 4), dtype=torch.float64, device=dev)
+    out = torch.empty((B, G, 7), dtype=torch.float32, device=dev)
+    _lib.call("md_pc_noise_per_object", [g, _i32c(gt_count, dev), valid.to(device=dev, dtype=torch.uint8).contiguous(), _f64c(loc_noises, dev),
+                                         _f64c(rot_noises, dev), None if grot_noises is None else _f64c(grot_noises, dev), selected, tf, out])
+    return selected, tf, out
+
+
+def pc_augment_points_workspace_bytes(N, B, G, R):
+    """bytes of scratch md_pc_augment_points takes (include/minddet_hip_pcaug.h)"""
+    return 128 * B * (G + R) + 64 * B + 4 * (N // 256 + 3)
+
+
+def pc_augment_points(points, offsets, obj_boxes, gt_count, valid, obj_transform, glob, remove_boxes=None, remove_count=None,
+                      remove_from=None, workspace=True):
+    """remove_points_in_boxes + points_transform_ + the point side of the four global steps + a stable compaction
+    (md_pc_augment_points): points [N,4] f32 with offsets [B+1] i32 as voxelize takes them, obj_boxes [B,G,7] f32 (BEFORE the noise),
+    obj_transform [B,G,4] f64 of pc_noise_per_object, glob [B,6] f64 (flip, rotation, scale, tx, ty, tz), optionally remove_boxes
+    [B,R,7] with remove_count [B] and remove_from [B] -> (points_out [N,4] f32, offsets_out [B+1] i32, owner [N] i32).
+    workspace=False leaves the scratch to the library's per-stream pool."""
+    if points.dim() != 2 or points.shape[1] != 4:
+        raise ValueError(f"pc_augment_points: points are [N, 4] (without_reflectivity is not built), got {tuple(points.shape)}")
+    points, g = _f32c(points), _f32c(obj_boxes)
+    dev, N, B, G = points.device, points.shape[0], g.shape[0], g.shape[1]
+    rem = [None, None, None]
+    if remove_boxes is not None:
+        if remove_count is None or remove_from is None:
+            raise ValueError("pc_augment_points: remove_boxes come with remove_count and remove_from")
+        rem = [_f32c(remove_boxes), _i32c(remove_count, dev), _i32c(remove_from, dev)]
+    R = 0 if rem[0] is None else rem[0].shape[1]
+    out = torch.empty((N, 4), dtype=torch.float32, device=dev)
+    offsets_out = torch.empty((B + 1,), dtype=torch.int32, device=dev)
+    owner = torch.empty((N,), dtype=torch.int32, device=dev)
+    ops = [points, _i32c(offsets, dev), g, _i32c(gt_count, dev), valid.to(device=dev, dtype=torch.uint8).contiguous(),
+           _f64c(obj_transform, dev), *rem, _f64c(glob, dev), out, offsets_out, owner]
+    if workspace:
+        ops.append(torch.empty((pc_augment_points_workspace_bytes(N, B, G, R),), dtype=torch.uint8, device=dev))
+    _lib.call("md_pc_augment_points", ops)
+    return out, offsets_out, owner
+
+
+def pc_augment_boxes(boxes, gt_count, valid, classes, glob, bv_range):
+    """the box side of the four global steps, filter_gt_box_outside_range, limit_period and the gt_boxes_mask selection
+    (md_pc_augment_boxes): boxes [B,G,7] f32 (pc_noise_per_object's boxes_out), classes [B,G], glob [B,6] f64, bv_range (x min, y min,
+    x max, y max) -> (gt_boxes [B,G,7] f32 and gt_classes [B,G] i32, the kept rows in front and zeros behind, out_count [B] i32)."""
+    g = _f32c(boxes)
+    if g.dim() != 3 or g.shape[2] != 7:
+        raise ValueError(f"pc_augment_boxes: boxes are [B, G, 7], got {tuple(g.shape)}")
+    dev, (B, G) = g.device, g.shape[:2]
+    at = _PCBoxesAttrs((ctypes.c_float * 4)(*[float(v) for v in bv_range]))
+    out = torch.empty((B, G, 7), dtype=torch.float32, device=dev)
+    cls = torch.empty((B, G), dtype=torch.int32, device=dev)
+    count = torch.empty((B,), dtype=torch.int32, device=dev)
+    _lib.call("md_pc_augment_boxes", [g, _i32c(gt_count, dev), valid.to(device=dev, dtype=torch.uint8).contiguous(), _i32c(classes, dev),
+                                      _f64c(glob, dev), out, cls, count], extra=at)
+    return out, cls, count
+
+
+_PCAUG_REFUSED = ("group_ids", "use_group_id", "reference_detections", "remove_environment", "remove_outside_points", "without_reflectivity",
+                  "bev_only", "shuffle_points")
+
+
+class PointCloudAugment:
+    """The training branch of prep_pointcloud (pointpillars/src/data/preprocess.py:124-170) on the device, built from the reference's
+    keys and defaults (:24-29): gt_rotation_noise, gt_loc_noise_std, global_rotation_noise, global_scaling_noise, global_loc_noise_std,
+    global_random_rot_range, plus num_try (100, :144), flip_probability (0.5, core/preprocess.py:686) and bv_range (x min, y min, x max,
+    y max of the voxel generator's range, :162).  group_ids, reference_detections, remove_environment, remove_outside_points,
+    without_reflectivity, bev_only and shuffle_points are not built: a true value raises ValueError."""
+
+    def __init__(self, bv_range, gt_rotation_noise=(-math.pi / 3, math.pi / 3), gt_loc_noise_std=(1.0, 1.0, 1.0),
+                 global_rotation_noise=(-math.pi / 4, math.pi / 4), global_scaling_noise=(0.95, 1.05), global_loc_noise_std=(0.2, 0.2, 0.2),
+                 global_random_rot_range=(0.78, 2.35), num_try=100, flip_probability=0.5, **options):
+        for k, v in options.items():
+            if k not in _PCAUG_REFUSED:
+                raise ValueError(f"PointCloudAugment: unknown option {k!r}")
+            if v not in (None, False):
+                raise ValueError(f"PointCloudAugment: {k} is not built")
+
+        def pair(v):           # a scalar means [-v, v] (core/preprocess.py:572-575, 673-674)
+            return (-float(v), float(v)) if not isinstance(v, (list, tuple)) else (float(v[0]), float(v[1]))
+
+        def triple(v):
+            return (float(v),) * 3 if not isinstance(v, (list, tuple)) else tuple(float(x) for x in v)
+
+        self.bv_range = tuple(float(v) for v in bv_range)
+        self.gt_rotation_noise, self.gt_loc_noise_std = pair(gt_rotation_noise), triple(gt_loc_noise_std)
+        self.global_rotation_noise, self.global_scaling_noise = pair(global_rotation_noise), pair(global_scaling_noise)
+        self.global_loc_noise_std, self.global_random_rot_range = triple(global_loc_noise_std), pair(global_random_rot_range)
+        self.num_try, self.flip_probability = int(num_try), float(flip_probability)
+        if len(self.bv_range) != 4 or len(self.gt_loc_noise_std) != 3 or len(self.global_loc_noise_std) != 3:
+            raise ValueError("PointCloudAugment: bv_range has 4 values, the noise stds 3")
+        if not 1 <= self.num_try <= PCAUG_MAX_TRIES:
+            raise ValueError(f"PointCloudAugment: num_try in 1 .. {PCAUG_MAX_TRIES}, got {self.num_try}")
+        # enable_grot, core/preprocess.py:576-578
+        self.enable_grot = abs(self.global_random_rot_range[0] - self.global_random_rot_range[1]) >= 1e-3
+
+    @classmethod
+    def from_config(cls, cfg):
+        """cfg.train_cfg["augment"] (the reference's keys) and the voxel generator's range"""
+        r = cfg.model["voxel_generator"]["point_cloud_range"]
+        return cls((r[0], r[1], r[3], r[4]), **dict(cfg.train_cfg["augment"]))
+
+    def draw(self, gt_boxes, gt_count, generator=None):
+        """The random draws of one batch as float64 device tensors, with the reference's distributions: loc [B,G,T,3] normal with
+        gt_loc_noise_std, rot [B,G,T] uniform in gt_rotation_noise, grot [B,G,T] uniform in global_random_rot_range shifted per box by
+        -atan2(x, y) (core/preprocess.py:584-595; None unless enable_grot), glob [B,6] = (flip with flip_probability, rotation uniform in
+        global_rotation_noise, scale uniform in global_scaling_noise, translation normal with global_loc_noise_std x, y and -- as the
+        reference does, :800 -- x again for z).  The draws come from torch's generator (`generator`: a torch.Generator of the boxes'
+        device, None = the default one), NOT from numpy's random stream: the reference's distributions, not its sequence."""
+        g = _f32c(gt_boxes)
+        dev, (B, G), T = g.device, g.shape[:2], self.num_try
+        f64 = dict(dtype=torch.float64, device=dev, generator=generator)
+
+        def uniform(shape, lo, hi):
+            return lo + (hi - lo) * torch.rand(shape, **f64)
+
+        loc = torch.randn((B, G, T, 3), **f64) * torch.tensor(self.gt_loc_noise_std, dtype=torch.float64, device=dev)
+        rot = uniform((B, G, T), *self.gt_rotation_noise)
+        grot = None
+        if self.enable_grot:
+            shift = torch.atan2(g[..., 0].double(), g[..., 1].double())[..., None]
+            grot = uniform((B, G, T), *self.global_random_rot_range) - shift
+        glob = torch.empty((B, 6), dtype=torch.float64, device=dev)
+        glob[:, 0] = (torch.rand((B,), **f64) < self.flip_probability).double()
+        glob[:, 1] = uniform((B,), *self.global_rotation_noise)
+        glob[:, 2] = uniform((B,), *self.global_scaling_noise)
+        std = self.global_loc_noise_std
+        glob[:, 3:6] = torch.randn((B, 3), **f64) * torch.tensor([std[0], std[1], std[0]], dtype=torch.float64, device=dev)
+        return dict(loc=loc, rot=rot, grot=grot, glob=glob)
+
+    def __call__(self, points, offsets, gt_boxes, gt_classes, gt_count, valid=None, sampled=None, draws=None, generator=None):
+        """points [N,4] f32, offsets [B+1] i32, gt_boxes [B,G,7] f32, gt_classes [B,G], gt_count [B]; valid [B,G] (None: every row);
+        sampled = dict(remove_boxes [B,R,7], remove_count [B], remove_from [B]) when the caller put sampled objects' points in front
+        of each sample; draws = the dict of draw() (None: drawn here) -> dict(points, offsets, gt_boxes, gt_classes, gt_count,
+        selected, owner), nothing read back."""
+        g = _f32c(gt_boxes)
+        dev = g.device
+        if valid is None:
+            valid = torch.ones(g.shape[:2], dtype=torch.uint8, device=dev)
+        if draws is None:
+            draws = self.draw(g, gt_count, generator)
+        if (draws.get("grot") is not None) != self.enable_grot:
+            raise ValueError("PointCloudAugment: draws carry grot exactly when global_random_rot_range is an interval")
+        selected, tf, moved = pc_noise_per_object(g, gt_count, valid, draws["loc"], draws["rot"], draws.get("grot"))
+        s = dict(sampled or {})
+        pts, offs, owner = pc_augment_points(points, offsets, g, gt_count, valid, tf, draws["glob"], s.get("remove_boxes"),
+                                             s.get("remove_count"), s.get("remove_from"))
+        boxes, classes, count = pc_augment_boxes(moved, gt_count, valid, gt_classes, draws["glob"], self.bv_range)
+        return dict(points=pts, offsets=offs, gt_boxes=boxes, gt_classes=classes, gt_count=count, selected=selected, owner=owner)
+
+
 # ----------------------------------------------------------------------------- training operators: outputs, head losses
 def _out_dict(who, want, out, dev):
     """want: {key: (shape, dtype)} -> `out` checked against it, or a new dict of empty tensors on dev"""

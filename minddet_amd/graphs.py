@@ -1417,6 +1417,43 @@ class PointPillarsKITTIPoints(Module):
                                           self.reader.offsets)
         return self.inner.loss(canvas, example, grad=grad)
 
+    def augment_op(self):
+        """det_ops.PointCloudAugment with train_cfg["augment"] (None: the reference's defaults) on this model's range"""
+        if getattr(self, "_augment", None) is None:
+            r = self.pc_range
+            self._augment = det_ops.PointCloudAugment((r[0], r[1], r[3], r[4]), **dict((self.inner.train_cfg or {}).get("augment") or {}))
+        return self._augment
+
+    def train_example(self, points, offsets, gt_boxes, gt_classes, gt_count, generator=None, draws=None, valid=None, sampled=None):
+        """Raw points and ground truth -> the `example` of loss(), on the device with nothing read back: the training branch of
+        prep_pointcloud (det_ops.PointCloudAugment: points [N,4] f32, offsets [B+1] i32, gt_boxes [B,G,7] f32, gt_classes [B,G],
+        gt_count [B]; draws = the dict of its draw(), None: drawn with `generator`), the front end on the augmented points, and one
+        det_ops.assign_targets per sample on the fixed-capacity box list: the rows from the sample's count on are replaced by a box
+        far outside every anchor with class 1, the reference's "ground truth nothing overlaps" case, which changes no target.
+        -> dict(labels [B,A] i32, reg_targets [B,A,7] f32, reg_weights [B,A] f32, gt_ids [B,A] i32, anchors_mask [B,A] u8, canvas,
+        augment = the dict of PointCloudAugment)."""
+        a = self.augment_op()(points, offsets, gt_boxes, gt_classes, gt_count, valid=valid, sampled=sampled, draws=draws, generator=generator)
+        canvas, mask, _ = self.front_end(a["points"], a["offsets"])
+        boxes, classes = a["gt_boxes"], a["gt_classes"]
+        dev, (B, G) = boxes.device, boxes.shape[:2]
+        pad = torch.arange(G, device=dev)[None, :] >= a["gt_count"][:, None]
+        far = torch.tensor([1e6, 1e6, 0.0, 1.0, 1.0, 1.0, 0.0], dtype=torch.float32, device=dev)
+        boxes = torch.where(pad[..., None], far, boxes)
+        classes = torch.where(pad, torch.ones_like(classes), classes)
+        if getattr(self, "_thresholds", None) is None:
+            gen = det_ops.generate_anchors(self.inner.generators, (1,) + tuple(self.inner.feature_hw), device=dev)
+            self._thresholds = (gen["matched_thresholds"].reshape(-1).contiguous(), gen["unmatched_thresholds"].reshape(-1).contiguous())
+        mt, ut = self._thresholds
+        rows = [det_ops.assign_targets(self.inner.anchors, boxes[b], classes[b], mt, ut, mask[b]) for b in range(B)]
+        labels, reg_targets, reg_weights, gt_ids = (torch.stack([r[i] for r in rows]) for i in range(4))
+        return dict(labels=labels, reg_targets=reg_targets, reg_weights=reg_weights, gt_ids=gt_ids, anchors_mask=mask, canvas=canvas, augment=a)
+
+    def train_loss(self, points, offsets, gt_boxes, gt_classes, gt_count, generator=None, draws=None, valid=None, sampled=None, grad=False):
+        """train_example, then PointPillarsNet.loss on its canvas: raw points + ground truth -> loss (and, grad=True, d total / d head)
+        as one device chain.  -> the dict of loss() plus `example`."""
+        ex = self.train_example(points, offsets, gt_boxes, gt_classes, gt_count, generator=generator, draws=draws, valid=valid, sampled=sampled)
+        return dict(self.inner.loss(ex["canvas"], ex, grad=grad), example=ex)
+
 
 # ----------------------------------------------------------------------------- YOLOv5 (build-authored; parity unpinned)
 SPPF_FUSED = os.environ.get("MD_SPPF_FUSED", "1") != "0"    # A/B knob: 0 = three md_maxpool2d launches + four concat copies per SPPF block

@@ -53,6 +53,10 @@ train_cfg = dict(
     # CenterHead.loss: the loc-loss weight and one weight per anno_box column (reg 2, height, dim 3, vel 2, rot 2), the reference
     # configuration's values; det_ops.CenterPointLoss.from_config reads them
     loss=dict(weight=0.25, code_weights=[1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 0.2, 0.2, 1.0, 1.0]),
+    # the Preprocess step's training values of the reference configuration; det_ops.CenterPointAugment.from_config reads them
+    augment=dict(global_rot_noise=[-0.3925, 0.3925], global_scale_noise=[0.95, 1.05], global_translate_std=0, min_points_in_gt=-1),
+    # the voxel budget the reference trains with (PillarDetector.loss / train_loss)
+    max_voxel_num=30000,
 )
 
 voxel_size = [0.2, 0.2]

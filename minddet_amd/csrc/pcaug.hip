@@ -22,6 +22,8 @@
 
 #pragma clang fp contract(off)
 
+#include "aug_geom.h"      // rect_corners, covers, collide; find_sample and the compaction's block counts, scan and ranks
+
 namespace md {
 
 static_assert(sizeof(md_pc_boxes_attrs) == 16, "minddet_hip_pcaug.h: attribute struct layout");
@@ -31,54 +33,6 @@ constexpr int PCA_MAX_BOXES = MD_PCAUG_MAX_BOXES, PCA_MAX_TRIES = MD_PCAUG_MAX_T
 constexpr int PCA_REC = 16;      // doubles per box record
 constexpr int PCA_GREC = 8;      // doubles per sample record
 constexpr double PCA_PI = 3.141592653589793, PCA_2PI = 6.283185307179586;
-
-// corners of the (w, l) rectangle rotated by the angle whose cosine / sine are c / s, in the reference's order (box2d_to_corner_jit,
-// box_np_ops.py:340-360: (-,-), (-,+), (+,+), (+,-) halves; row vector times [[c, -s], [s, c]]), about (0, 0)
-__device__ __forceinline__ void rect_corners(double w, double l, double c, double s, double *x, double *y) {
-    const double nx[4] = {-0.5, -0.5, 0.5, 0.5}, ny[4] = {-0.5, 0.5, 0.5, -0.5};
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        const double px = nx[m] * w, py = ny[m] * l;
-        x[m] = px * c + py * s;
-        y[m] = -px * s + py * c;
-    }
-}
-
-// _get_box_overlap_another (:769-785), clockwise: every corner of Q strictly on the inner side of every edge of P
-__device__ __forceinline__ bool covers(const double *px, const double *py, const double *qx, const double *qy) {
-    for (int m = 0; m < 4; ++m)
-        for (int k = 0; k < 4; ++k) {
-            const int k1 = (k + 1) & 3;
-            const double vx = -(px[k] - px[k1]), vy = -(py[k] - py[k1]);
-            double cross = vy * (px[k] - qx[m]);
-            cross -= vx * (py[k] - qy[m]);
-            if (cross >= 0) return false;
-        }
-    return true;
-}
-
-// box_collision_test (:708-746) for one pair, quirk (a) read as the text means it
-__device__ __forceinline__ bool collide(const double *ax, const double *ay, const double *bx, const double *by) {
-    const double aminx = fmin(fmin(ax[0], ax[1]), fmin(ax[2], ax[3])), amaxx = fmax(fmax(ax[0], ax[1]), fmax(ax[2], ax[3]));
-    const double aminy = fmin(fmin(ay[0], ay[1]), fmin(ay[2], ay[3])), amaxy = fmax(fmax(ay[0], ay[1]), fmax(ay[2], ay[3]));
-    const double bminx = fmin(fmin(bx[0], bx[1]), fmin(bx[2], bx[3])), bmaxx = fmax(fmax(bx[0], bx[1]), fmax(bx[2], bx[3]));
-    const double bminy = fmin(fmin(by[0], by[1]), fmin(by[2], by[3])), bmaxy = fmax(fmax(by[0], by[1]), fmax(by[2], by[3]));
-    const double iw = fmin(amaxx, bmaxx) - fmax(aminx, bminx), ih = fmin(amaxy, bmaxy) - fmax(aminy, bminy);
-    if (!(ih > 0 && iw > 0)) return false;
-    for (int k = 0; k < 4; ++k)          // _get_ret (:749-766)
-        for (int m = 0; m < 4; ++m) {
-            const double a0 = ax[k], a1 = ay[k], b0 = ax[(k + 1) & 3], b1 = ay[(k + 1) & 3];
-            const double c0 = bx[m], c1 = by[m], d0 = bx[(m + 1) & 3], d1 = by[(m + 1) & 3];
-            const bool acd = (d1 - a1) * (c0 - a0) > (c1 - a1) * (d0 - a0);
-            const bool bcd = (d1 - b1) * (c0 - b0) > (c1 - b1) * (d0 - b0);
-            if (acd != bcd) {
-                const bool abc = (c1 - a1) * (b0 - a0) > (b1 - a1) * (c0 - a0);
-                const bool abd = (d1 - a1) * (b0 - a0) > (b1 - a1) * (d0 - a0);
-                if (abc != abd) return true;
-            }
-        }
-    return covers(ax, ay, bx, by) || covers(bx, by, ax, ay);
-}
 
 struct NoiseArgs {
     const float *boxes; const int *count; const uint8_t *valid; const double *loc, *rot, *grot;
@@ -247,16 +201,6 @@ __device__ __forceinline__ bool inside_box(const double *r, double x, double y, 
     return fabs(lx) < r[5] && fabs(ly) < r[6] && dz > 0 && dz < r[7];
 }
 
-// the sample of point i, or -1: a binary search of offsets[0 .. B] where it lies (at most 13 reads of a table every workgroup shares)
-__device__ __forceinline__ int find_sample(const int *__restrict__ offsets, int B, int i) {
-    int lo = 0, hi = B + 1;                 // first index whose offset is above i
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (offsets[mid] > i) hi = mid; else lo = mid + 1;
-    }
-    return (lo == 0 || lo == B + 1) ? -1 : lo - 1;
-}
-
 __global__ __launch_bounds__(256) void pc_classify_kernel(PointArgs a) {
     __shared__ int wcnt[4];
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -282,37 +226,12 @@ __global__ __launch_bounds__(256) void pc_classify_kernel(PointArgs a) {
         }
     }
     if (i < a.N) a.owner[i] = own;
-    const unsigned long long keep = __ballot(own != -2);
-    if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6] = __popcll(keep);
-    __syncthreads();
-    if (threadIdx.x == 0) a.bsum[blockIdx.x] = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+    block_keep_count(own != -2, wcnt, a.bsum);
 }
 
 __global__ __launch_bounds__(256) void pc_scan_kernel(PointArgs a) {
     __shared__ int wsum[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int carry = 0;
-    for (int base = 0; base < a.nb; base += 256) {
-        const int k = base + threadIdx.x;
-        const int v = k < a.nb ? a.bsum[k] : 0;
-        int inc = v;
-        for (int d = 1; d < 64; d <<= 1) {
-            const int t = __shfl_up(inc, d, 64);
-            if (lane >= d) inc += t;
-        }
-        __syncthreads();
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        int before = 0, all = 0;
-        for (int w = 0; w < 4; ++w) {
-            if (w < wave) before += wsum[w];
-            all += wsum[w];
-        }
-        if (k < a.nb) a.bsum[k] = carry + before + inc - v;
-        carry += all;
-    }
-    if (threadIdx.x == 0) a.bsum[a.nb] = carry;
-    __syncthreads();
+    scan_block_counts(a.bsum, a.nb, wsum);
     for (int b = threadIdx.x; b <= a.B; b += 256) {
         const int o = min(max(a.offsets[b], 0), a.N), blk = o >> 8;      // blk <= nb
         int v = a.bsum[blk];
@@ -323,18 +242,14 @@ __global__ __launch_bounds__(256) void pc_scan_kernel(PointArgs a) {
 
 __global__ __launch_bounds__(256) void pc_scatter_kernel(PointArgs a) {
     __shared__ int wcnt[4];
-    const int i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = blockIdx.x * 256 + threadIdx.x;
     const int b = find_sample(a.offsets, a.B, i);
     const int own = i < a.N ? a.owner[i] : -2;
     const bool keep = own != -2;
-    const unsigned long long bal = __ballot(keep);
-    if (lane == 0) wcnt[wave] = __popcll(bal);
-    __syncthreads();
+    const int at = block_rank(keep, wcnt, a.bsum);
     const int total = a.bsum[a.nb];
     if (i < a.N && i >= total) a.out[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     if (!keep || b < 0) return;
-    int at = a.bsum[blockIdx.x] + __popcll(bal & ((1ull << lane) - 1ull));
-    for (int w = 0; w < wave; ++w) at += wcnt[w];
     const float4 p = a.pts[i];
     double x = p.x, y = p.y, z = p.z;
     if (own >= 0) {

@@ -1431,6 +1431,222 @@ class PointCloudAugment:
         return dict(points=pts, offsets=offs, gt_boxes=boxes, gt_classes=classes, gt_count=count, selected=selected, owner=owner)
 
 
+# ----------------------------------------------------------------------------- CenterPoint training input (csrc/cpaug.hip)
+CPAUG_MAX_GT, CPAUG_MAX_CAND = 512, 256     # MD_CPAUG_MAX_GT, MD_CPAUG_MAX_CAND
+
+
+class _CPCountAttrs(ctypes.Structure):
+    _fields_ = [("min_points", ctypes.c_int32)]
+
+
+class _CPBoxesAttrs(ctypes.Structure):
+    _fields_ = [("bv_range", ctypes.c_float * 4)]
+
+
+def _u8c(t, dev):
+    return t.to(device=dev, dtype=torch.uint8).contiguous()
+
+
+def _boxes9(who, t):
+    g = _f32c(t)
+    if g.dim() != 3 or g.shape[2] != 9:
+        raise ValueError(f"{who}: boxes are [B, n, 9] (x, y, z, w, l, h, vx, vy, r), got {tuple(g.shape)}")
+    return g
+
+
+def _points5(who, t):
+    if t.dim() != 2 or t.shape[1] != 5:
+        raise ValueError(f"{who}: points are [N, 5], got {tuple(t.shape)}")
+    return _f32c(t)
+
+
+def cp_aug_count_points_workspace_bytes(B, G):
+    """bytes of scratch md_cp_aug_count_points takes (include/minddet_hip_cpaug.h)"""
+    return 96 * B * G
+
+
+def cp_aug_count_points(points, offsets, gt_boxes, gt_count, min_points=-1, workspace=True):
+    """points_count_rbbox + the min_points_in_gt mask (md_cp_aug_count_points, include/minddet_hip_cpaug.h): points [N,5] f32 with
+    offsets [B+1] i32 as voxelize takes them, gt_boxes [B,G,9] f32, gt_count [B] -> (counts [B,G] i32, keep [B,G] u8 = g < gt_count and
+    (min_points <= 0 or counts >= min_points)).  workspace=False leaves the scratch to the library's per-stream pool."""
+    points, g = _points5("cp_aug_count_points", points), _boxes9("cp_aug_count_points", gt_boxes)
+    dev, (B, G) = g.device, g.shape[:2]
+    counts = torch.empty((B, G), dtype=torch.int32, device=dev)
+    keep = torch.empty((B, G), dtype=torch.uint8, device=dev)
+    ops = [points, _i32c(offsets, dev), g, _i32c(gt_count, dev), counts, keep]
+    if workspace:
+        ops.append(torch.empty((max(cp_aug_count_points_workspace_bytes(B, G), 16),), dtype=torch.uint8, device=dev))
+    _lib.call("md_cp_aug_count_points", ops, extra=_CPCountAttrs(int(min_points)))
+    return counts, keep
+
+
+def cp_aug_select_workspace_bytes(B, G, S):
+    """bytes of scratch md_cp_aug_select takes (include/minddet_hip_cpaug.h)"""
+    return 8 * B * S * ((G + S + 63) // 64)
+
+
+def cp_aug_select(gt_boxes, gt_count, keep, cand_boxes, cand_count, cand_group, workspace=True):
+    """the accept step of the ground-truth sampler (md_cp_aug_select): gt_boxes [B,G,9], gt_count [B], keep [B,G] u8 of
+    cp_aug_count_points, cand_boxes [B,S,9] in draw order, cand_count [B], cand_group [B,S] i32 (non-decreasing per sample, one value
+    per sample_class_v2 call) -> accept [B,S] u8.  A sample whose groups decrease accepts nothing."""
+    g, c = _boxes9("cp_aug_select", gt_boxes), _boxes9("cp_aug_select", cand_boxes)
+    dev, (B, G), S = g.device, g.shape[:2], c.shape[1]
+    accept = torch.empty((B, S), dtype=torch.uint8, device=dev)
+    ops = [g, _i32c(gt_count, dev), _u8c(keep, dev), c, _i32c(cand_count, dev), _i32c(cand_group, dev), accept]
+    if workspace:
+        ops.append(torch.empty((max(cp_aug_select_workspace_bytes(B, G, S), 16),), dtype=torch.uint8, device=dev))
+    _lib.call("md_cp_aug_select", ops)
+    return accept
+
+
+def cp_aug_points_workspace_bytes(N, Ns, B):
+    """bytes of scratch md_cp_aug_points takes (include/minddet_hip_cpaug.h)"""
+    return 64 * B + (N + Ns) + 4 * ((N + Ns) // 256 + 3)
+
+
+def cp_aug_points(points, offsets, glob, cand_points=None, cand_offsets=None, cand_boxes=None, accept=None, workspace=True):
+    """the accepted candidates' points (each plus its box centre) in front of every sample's scene points, then the point side of
+    the two flips, the rotation, the scale and the translation (md_cp_aug_points): points [N,5] f32, offsets [B+1] i32, glob [B,7]
+    f64 (flip_a, flip_b, rot, scale, tx, ty, tz); cand_points [Ns,5] f32 in each candidate's frame, cand_offsets [B S + 1] i32,
+    cand_boxes [B,S,9], accept [B,S] u8 -- all four or none -> (points_out [N+Ns,5] f32 with zero rows behind the last kept row,
+    offsets_out [B+1] i32)."""
+    points = _points5("cp_aug_points", points)
+    dev, N, B = points.device, points.shape[0], offsets.numel() - 1
+    cand = [cand_points, cand_offsets, cand_boxes, accept]
+    if any(c is None for c in cand) != all(c is None for c in cand):
+        raise ValueError("cp_aug_points: cand_points, cand_offsets, cand_boxes and accept come together")
+    Ns = 0
+    if cand_points is not None:
+        cand = [_points5("cp_aug_points", cand_points.to(dev)), _i32c(cand_offsets, dev), _boxes9("cp_aug_points", cand_boxes), _u8c(accept, dev)]
+        Ns = cand[0].shape[0]
+    out = torch.empty((N + Ns, 5), dtype=torch.float32, device=dev)
+    offsets_out = torch.empty((B + 1,), dtype=torch.int32, device=dev)
+    ops = [points, _i32c(offsets, dev), *cand, _f64c(glob, dev), out, offsets_out]
+    if workspace:
+        ops.append(torch.empty((cp_aug_points_workspace_bytes(N, Ns, B),), dtype=torch.uint8, device=dev))
+    _lib.call("md_cp_aug_points", ops)
+    return out, offsets_out
+
+
+def cp_aug_boxes(gt_boxes, gt_classes, gt_count, keep, glob, bv_range, cand_boxes=None, cand_classes=None, accept=None):
+    """the class selection, the box side of the two flips, the rotation, the scale (velocities included) and the translation, and
+    filter_gt_box_outside_range (md_cp_aug_boxes): gt_boxes [B,G,9], gt_classes [B,G] (global 1-based class, 0: a name outside
+    class_names), gt_count [B], keep [B,G] u8, glob [B,7] f64, bv_range (x min, y min, x max, y max); cand_boxes [B,S,9], cand_classes
+    [B,S], accept [B,S] u8 -- all three or none -> (boxes_out [B,G+S,9] f32, classes_out [B,G+S] i32: the surviving rows in front,
+    zeros with class 0 behind, out_count [B] i32)."""
+    g = _boxes9("cp_aug_boxes", gt_boxes)
+    dev, (B, G) = g.device, g.shape[:2]
+    cand = [cand_boxes, cand_classes, accept]
+    if any(c is None for c in cand) != all(c is None for c in cand):
+        raise ValueError("cp_aug_boxes: cand_boxes, cand_classes and accept come together")
+    S = 0
+    if cand_boxes is not None:
+        cand = [_boxes9("cp_aug_boxes", cand_boxes), _i32c(cand_classes, dev), _u8c(accept, dev)]
+        S = cand[0].shape[1]
+    at = _CPBoxesAttrs((ctypes.c_float * 4)(*[float(v) for v in bv_range]))
+    out = torch.empty((B, G + S, 9), dtype=torch.float32, device=dev)
+    cls = torch.empty((B, G + S), dtype=torch.int32, device=dev)
+    count = torch.empty((B,), dtype=torch.int32, device=dev)
+    _lib.call("md_cp_aug_boxes", [g, _i32c(gt_classes, dev), _i32c(gt_count, dev), _u8c(keep, dev), *cand, _f64c(glob, dev), out, cls, count],
+              extra=at)
+    return out, cls, count
+
+
+class CenterPointAugment:
+    """The training branch of the reference's Preprocess step and the ground-truth filter of its Voxelization step
+    (centerpoint/det3d_ms/datasets/pipelines/preprocess.py:46-157, 187-193) on the device, built from the reference's keys:
+    global_rot_noise, global_scale_noise, global_translate_std, min_points_in_gt, plus bv_range (x min, y min, x max, y max of the
+    voxel generator's range).  The database draw and the file reads of the ground-truth sampler stay with the caller, who passes the
+    drawn candidates in draw order as `sampled`.
+
+    Not built, a true / non-default value raises ValueError: flip_coor, group sampling (use_group_sampling / group_ids), the sampler's
+    per-object global rotation (global_random_rotation_range_per_object other than [0, 0]), random_crop, and shuffle_points.
+    shuffle_points=True is refused rather than ignored because the voxeliser is order-dependent (the first max_points points of a
+    cell and the first max_voxels cells win), so a shuffle changes the result; and the merged list has a data-dependent length (the
+    accepted candidates' points), so on the device a shuffle is a keyed sort of a list whose length is not known on the host -- work
+    of its own, not a flag of this operator."""
+
+    _REFUSED = ("shuffle_points", "flip_coor", "use_group_sampling", "group_ids", "random_crop", "no_augmentation", "npoints")
+
+    def __init__(self, bv_range, global_rot_noise, global_scale_noise, global_translate_std=0, min_points_in_gt=-1, **options):
+        for k, v in options.items():
+            if k == "global_random_rotation_range_per_object":
+                if v is not None and any(float(x) != 0.0 for x in (v if isinstance(v, (list, tuple)) else [v])):
+                    raise ValueError("CenterPointAugment: the sampler's per-object global rotation is not built")
+                continue
+            if k not in self._REFUSED:
+                raise ValueError(f"CenterPointAugment: unknown option {k!r}")
+            if v not in (None, False, -1):
+                raise ValueError(f"CenterPointAugment: {k} is not built")
+
+        def pair(v):           # a scalar means [-v, v] (core/sampler/preprocess.py:666-667)
+            return (-float(v), float(v)) if not isinstance(v, (list, tuple)) else (float(v[0]), float(v[1]))
+
+        self.bv_range = tuple(float(v) for v in bv_range)
+        if len(self.bv_range) != 4:
+            raise ValueError("CenterPointAugment: bv_range has 4 values")
+        self.global_rot_noise = pair(global_rot_noise)
+        if isinstance(global_scale_noise, (list, tuple)):
+            self.global_scale_noise = (float(global_scale_noise[0]), float(global_scale_noise[1]))
+        else:
+            raise ValueError("CenterPointAugment: global_scale_noise is (min_scale, max_scale)")
+        std = global_translate_std
+        std = [float(std)] * 3 if not isinstance(std, (list, tuple)) else [float(v) for v in std]
+        if len(std) != 3:
+            raise ValueError("CenterPointAugment: global_translate_std is a number or 3 values")
+        self.global_translate_std = tuple(std)
+        self.min_points_in_gt = int(min_points_in_gt)
+
+    @classmethod
+    def from_config(cls, cfg):
+        """cfg.train_cfg["augment"] (the reference's keys) and the voxel generator's range"""
+        r = cfg.model["voxel_generator"]["range"]
+        return cls((r[0], r[1], r[3], r[4]), **dict(cfg.train_cfg["augment"]))
+
+    def draw(self, B, generator=None, device="cuda"):
+        """global [B,7] float64 on the device with the reference's distributions: two Bernoulli(0.5) (random_flip_both), the
+        rotation uniform in global_rot_noise, the scale uniform in global_scale_noise, the translation normal with
+        global_translate_std x, y and -- as the reference does, core/sampler/preprocess.py:825-827 -- x again for z (zeros when every
+        std is 0).  From torch's generator, not numpy's stream: the reference's distributions, not its sequence."""
+        if generator is not None:
+            device = generator.device
+        f64 = dict(dtype=torch.float64, device=device, generator=generator)
+        glob = torch.empty((B, 7), dtype=torch.float64, device=device)
+        glob[:, 0] = (torch.rand((B,), **f64) < 0.5).double()
+        glob[:, 1] = (torch.rand((B,), **f64) < 0.5).double()
+        lo, hi = self.global_rot_noise
+        glob[:, 2] = lo + (hi - lo) * torch.rand((B,), **f64)
+        lo, hi = self.global_scale_noise
+        glob[:, 3] = lo + (hi - lo) * torch.rand((B,), **f64)
+        std = self.global_translate_std
+        glob[:, 4:7] = torch.randn((B, 3), **f64) * torch.tensor([std[0], std[1], std[0]], dtype=torch.float64, device=device)
+        return glob
+
+    def __call__(self, points, offsets, gt_boxes, gt_classes, gt_count, sampled=None, draws=None, generator=None):
+        """points [N,5] f32, offsets [B+1] i32, gt_boxes [B,G,9] f32, gt_classes [B,G] (global 1-based class, 0: a name outside
+        class_names), gt_count [B]; sampled = dict(points [Ns,5], offsets [B S + 1], boxes [B,S,9], classes [B,S], group [B,S],
+        count [B]) or None; draws = global [B,7] f64 of draw() (None: drawn here with `generator`) -> dict(points, offsets, gt_boxes
+        [B,G+S,9], gt_classes [B,G+S], gt_count [B], counts, keep, accept (None without `sampled`), global), nothing read back."""
+        g = _boxes9("CenterPointAugment", gt_boxes)
+        dev, B = g.device, g.shape[0]
+        glob = self.draw(B, generator, dev) if draws is None else _f64c(draws, dev)
+        counts, keep = cp_aug_count_points(points, offsets, g, gt_count, self.min_points_in_gt)
+        s = dict(sampled) if sampled is not None else None
+        accept = None
+        if s is not None:
+            missing = {"points", "offsets", "boxes", "classes", "group", "count"} - set(s)
+            if missing:
+                raise ValueError(f"CenterPointAugment: sampled lacks {sorted(missing)}")
+            accept = cp_aug_select(g, gt_count, keep, s["boxes"], s["count"], s["group"])
+            pts, offs = cp_aug_points(points, offsets, glob, s["points"], s["offsets"], s["boxes"], accept)
+            boxes, classes, count = cp_aug_boxes(g, gt_classes, gt_count, keep, glob, self.bv_range, s["boxes"], s["classes"], accept)
+        else:
+            pts, offs = cp_aug_points(points, offsets, glob)
+            boxes, classes, count = cp_aug_boxes(g, gt_classes, gt_count, keep, glob, self.bv_range)
+        return dict(points=pts, offsets=offs, gt_boxes=boxes, gt_classes=classes, gt_count=count, counts=counts, keep=keep, accept=accept,
+                    **{"global": glob})
+
+
 # ----------------------------------------------------------------------------- training operators: outputs, head losses
 def _out_dict(who, want, out, dev):
     """want: {key: (shape, dtype)} -> `out` checked against it, or a new dict of empty tensors on dev"""

@@ -1112,6 +1112,9 @@ class PillarDetector(Module):
         self.grid_hw = (gy, gx)
         if (self.reader.vx, self.reader.vy) != self.voxel_size[:2] or self.reader.num_filters[-1] != self.backbone.nchannels:
             raise ValueError("PillarDetector: the reader's voxel_size / width do not match the voxel generator / the backbone")
+        self.train_cfg = dict(train_cfg) if train_cfg else None
+        self._voxel_generator = vg
+        self._augment = self._targets = None
 
     def children(self):
         return [self.reader, self.backbone, self.detector]
@@ -1142,6 +1145,56 @@ class PillarDetector(Module):
         return self.detector.forward(canvas)
 
     __call__ = forward
+
+    def _train_cfg(self, key):
+        if not self.train_cfg or key not in self.train_cfg:
+            raise ValueError(f"PillarDetector: train_cfg[{key!r}] is needed for training (see configs/centerpoint/centerpoint_pp_nusc_train.py)")
+        return self.train_cfg[key]
+
+    def augment_op(self):
+        """det_ops.CenterPointAugment with train_cfg["augment"] on this model's range"""
+        if self._augment is None:
+            r = self.pc_range
+            self._augment = det_ops.CenterPointAugment((r[0], r[1], r[3], r[4]), **dict(self._train_cfg("augment")))
+        return self._augment
+
+    def targets_op(self):
+        """det_ops.CenterPointTargets with train_cfg["assigner"] on this model's voxel generator"""
+        if self._targets is None:
+            self._targets = det_ops.CenterPointTargets(self._train_cfg("assigner"), self._voxel_generator)
+        return self._targets
+
+    def _train_canvas(self, points, offsets):
+        # the reference trains with its own voxel budget (30 000 on nuScenes, 60 000 in evaluation)
+        max_voxels = int((self.train_cfg or {}).get("max_voxel_num", self.max_voxels))
+        voxels, coors, num_points, voxel_num = det_ops.voxelize(points, offsets, self.voxel_size, self.pc_range, self.max_points, max_voxels)
+        return self.backbone(self.reader, voxels, coors, num_points, voxel_num, self.grid_hw)
+
+    def loss(self, points, offsets, example, grad=False):
+        """the voxeliser (with train_cfg["max_voxel_num"] where given) and the pillar encoder, then PointPillars.loss on the canvas:
+        example = the dict of det_ops.cp_assign_targets -> the dict of det_ops.cp_loss (grad=True: with d total / d head)"""
+        if points.shape[1] != self.reader.num_input_features:
+            raise ValueError(f"PillarDetector: the reader takes {self.reader.num_input_features} point features, got {points.shape[1]}")
+        return self.detector.loss(self._train_canvas(points, offsets), example, grad=grad)
+
+    def train_example(self, points, offsets, gt_boxes, gt_classes, gt_count, generator=None, draws=None, sampled=None):
+        """Raw points and ground truth -> the `example` of loss(), on the device with nothing read back: the training branch of the
+        reference's Preprocess and the ground-truth filter of its Voxelization (det_ops.CenterPointAugment: points [N,5] f32, offsets
+        [B+1] i32, gt_boxes [B,G,9] f32, gt_classes [B,G] global 1-based class or 0, gt_count [B]; sampled = the drawn database
+        candidates, draws = global [B,7] f64 of its draw(), None: drawn with `generator`), then AssignLabel
+        (det_ops.CenterPointTargets) on the fixed-capacity box list, whose rows behind the sample's count are class 0, i.e. padding.
+        -> the dict of det_ops.cp_assign_targets plus augment = the dict of CenterPointAugment."""
+        a = self.augment_op()(points, offsets, gt_boxes, gt_classes, gt_count, sampled=sampled, draws=draws, generator=generator)
+        tg = self.targets_op()
+        if a["gt_boxes"].shape[1] > tg.max_objs:
+            raise ValueError(f"PillarDetector: G + S = {a['gt_boxes'].shape[1]} rows exceed max_objs = {tg.max_objs}")
+        return dict(tg(a["gt_boxes"], a["gt_classes"]), augment=a)
+
+    def train_loss(self, points, offsets, gt_boxes, gt_classes, gt_count, generator=None, draws=None, sampled=None, grad=False):
+        """train_example, then loss() on the augmented points: raw points + ground truth -> loss (and, grad=True, d total / d head)
+        as one device chain.  -> the dict of loss() plus `example`."""
+        ex = self.train_example(points, offsets, gt_boxes, gt_classes, gt_count, generator=generator, draws=draws, sampled=sampled)
+        return dict(self.loss(ex["augment"]["points"], ex["augment"]["offsets"], ex, grad=grad), example=ex)
 
 
 # ----------------------------------------------------------------------------- PointPillars, anchor-based (KITTI)

@@ -56,7 +56,8 @@ int md_pp_pillar_encode(MD_AOT_ARGS);
  * in : coors[B,MV,4] i32 (b, z, y, x), voxel_num[B] i32 (md_voxelize's outputs), anchors_bv[N,4] f32
  * out: mask[B,N] u8 [, area[B,N] f32 or NULL] [, workspace u8: B * grid_y * grid_x * 4 bytes]
  * extra: md_anchor_mask_attrs (minddet_hip.h), required.
- * Row b equals, bit for bit, what md_anchor_mask gives for coors[b, :clamp(voxel_num[b], 0, MV), 1:]: the voxels are counted per
+ * Row b equals, bit for bit, what md_anchor_mask gives for coors[b, :clamp(voxel_num[b], 0, MV), 1:] (both entries are in
+ * csrc/ppreader.hip and launch one set of kernels, md_anchor_mask with B = 1 and every row counted): the voxels are counted per
  * (y, x) cell -- a voxel whose y or x is outside the grid is not counted, its b and z are not looked at -- then area = the count
  * inside the anchor's cell range from the integral image (integers: exact), mask = area > area_threshold.
  * 2: coors not [B,MV,4], voxel_num not [B], anchors_bv not [N,4], mask / area not [B,N].   4: grid_x or grid_y < 1, B x cells > 2^28,

@@ -1,6 +1,6 @@
 // aug_geom.h -- device code shared by the two training-augmentation sources (pcaug.hip: KITTI PointPillars, cpaug.hip: CenterPoint):
-// the BEV rectangle, the collision predicate of box_collision_test (quirk (a) of include/minddet_hip_pcaug.h) and the pieces of the
-// stable compaction (sample of a row, block counts, the one-workgroup scan, ballot ranks).  Include it after
+// the BEV rectangle, the collision predicate of box_collision_test (quirk (a) of include/minddet_hip_pcaug.h) and the sample of a row (the
+// stable compaction of the rows is workgroup.h's).  Include it after
 // `#pragma clang fp contract(off)`: every expression here is evaluated as written.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -67,52 +67,6 @@ __device__ __forceinline__ int find_sample(const int *__restrict__ offsets, int 
         if (offsets[mid] > i) hi = mid; else lo = mid + 1;
     }
     return (lo == 0 || lo == B + 1) ? -1 : lo - 1;
-}
-
-// The stable compaction, 256 rows per workgroup.  Pass 1: block_keep_count leaves the workgroup's number of kept rows in bsum[block].
-// Pass 2 (one workgroup of 256): scan_block_counts turns bsum[0 .. nb) into its exclusive prefix in place, the total in bsum[nb].
-// Pass 3: block_rank is a kept row's place in the output.  wcnt: 4 ints of LDS; all three hold a barrier, so every lane calls them.
-__device__ __forceinline__ void block_keep_count(bool keep, int *wcnt, int *bsum) {
-    const unsigned long long bal = __ballot(keep);
-    if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6] = __popcll(bal);
-    __syncthreads();
-    if (threadIdx.x == 0) bsum[blockIdx.x] = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
-}
-
-__device__ __forceinline__ void scan_block_counts(int *bsum, int nb, int *wsum) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int carry = 0;
-    for (int base = 0; base < nb; base += 256) {
-        const int k = base + threadIdx.x;
-        const int v = k < nb ? bsum[k] : 0;
-        int inc = v;
-        for (int d = 1; d < 64; d <<= 1) {
-            const int t = __shfl_up(inc, d, 64);
-            if (lane >= d) inc += t;
-        }
-        __syncthreads();
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        int before = 0, all = 0;
-        for (int w = 0; w < 4; ++w) {
-            if (w < wave) before += wsum[w];
-            all += wsum[w];
-        }
-        if (k < nb) bsum[k] = carry + before + inc - v;
-        carry += all;
-    }
-    if (threadIdx.x == 0) bsum[nb] = carry;
-    __syncthreads();
-}
-
-__device__ __forceinline__ int block_rank(bool keep, int *wcnt, const int *bsum) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long bal = __ballot(keep);
-    if (lane == 0) wcnt[wave] = __popcll(bal);
-    __syncthreads();
-    int at = bsum[blockIdx.x] + __popcll(bal & ((1ull << lane) - 1ull));
-    for (int w = 0; w < wave; ++w) at += wcnt[w];
-    return at;
 }
 
 }  // namespace md

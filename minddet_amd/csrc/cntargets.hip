@@ -6,10 +6,8 @@
 //   cn_row_kernel   one lane per (sample, slot): clip, size test, radius, centre; wh / ind / reg / reg_mask written for every slot (zeros
 //                   for a skipped row and for the slots past G) and the draw list (ct_int x, y, radius, class; radius -1 = nothing
 //                   to draw) left in the workspace, one entry per slot
-//   cn_heat_kernel  gather form (cp_heat_kernel's): one workgroup per 64 x 16 tile of one (sample, class) map; the sample's draw list is
-//                   compacted to the entries of the class whose window meets the tile, each lane takes the maximum over them for its
-//                   four consecutive x cells and stores them once, zeros included (16-byte stores where the row pitch allows).  A map
-//                   no object of its class touches costs the list scan per workgroup and the zero fill, nothing per cell.
+//   cn_heat_kernel  heatmap.h's heat_tile on one 64 x 16 tile of one (sample, class) map, the sample's draw list filtered by class.  A
+//                   map no object of its class touches costs the list scan per workgroup and the zero fill, nothing per cell.
 // The fp32 steps in the operation order of the numpy code under NumPy >= 2 scalar promotion (fp contraction off); radius and Gaussian
 // in float64.
 #include <hip/hip_runtime.h>
@@ -21,12 +19,13 @@
 
 #pragma clang fp contract(off)
 
+#include "heatmap.h"
+
 namespace md {
 
 static_assert(sizeof(md_cn_targets_attrs) == 4, "minddet_hip_cn.h: attribute struct layout");
 
 constexpr int CNT_MAX_M = MD_CN_MAX_OBJS;
-constexpr int CNT_TILE_W = 64, CNT_TILE_H = 16;   // 16 lanes x 4 cells wide, 16 rows: one cell quad per lane of a 256-lane workgroup
 
 struct CntParams {
     int B, G, M, C, H, W;
@@ -89,66 +88,9 @@ __global__ __launch_bounds__(256) void cn_row_kernel(const float *__restrict__ b
 }
 
 __global__ __launch_bounds__(256) void cn_heat_kernel(const int4 *__restrict__ draw, CntParams p, int tiles_x, float *__restrict__ hm) {
-    __shared__ int4 obj[CNT_MAX_M];        // the surviving entries: (cx, cy, radius, -)
-    __shared__ double den[CNT_MAX_M];      // 2 s s of each
-    __shared__ int wave_cnt[4];
-    __shared__ int n_obj;
-    const int tile = blockIdx.x, c = blockIdx.y, b = blockIdx.z;
-    const int tx0 = (tile % tiles_x) * CNT_TILE_W, ty0 = (tile / tiles_x) * CNT_TILE_H;
-    const int tx1 = min(tx0 + CNT_TILE_W, p.W) - 1, ty1 = min(ty0 + CNT_TILE_H, p.H) - 1;
-    const int4 *dl = draw + (size_t)b * p.M;
-    const int n = min(p.G, p.M);   // (slots past G hold radius -1)
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) n_obj = 0;
-    __syncthreads();
-    // compaction in list order: ballot inside each wave, the waves' counts through LDS
-    for (int j0 = 0; j0 < n; j0 += 256) {
-        const int j = j0 + threadIdx.x;
-        int4 e = make_int4(0, 0, -1, -1);
-        if (j < n) e = dl[j];
-        // the window [cx - r, cx + r] x [cy - r, cy + r] meets the tile (written so that no sum can overflow)
-        const bool keep = e.z >= 0 && e.w == c && e.z >= tx0 - e.x && e.z >= e.x - tx1 && e.z >= ty0 - e.y && e.z >= e.y - ty1;
-        const unsigned long long bal = __ballot(keep);
-        if (lane == 0) wave_cnt[wave] = __popcll(bal);
-        __syncthreads();
-        int at = n_obj;
-        for (int v = 0; v < wave; ++v) at += wave_cnt[v];
-        at += __popcll(bal & ((1ull << lane) - 1ull));
-        if (keep) {
-            obj[at] = e;
-            const double sigma = (2.0 * (double)e.z + 1.0) / 6.0;   // diameter / 6
-            den[at] = 2.0 * sigma * sigma;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) n_obj += wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
-        __syncthreads();
-    }
-    const int m = n_obj;
-    const int y = ty0 + (threadIdx.x >> 4), x0 = tx0 + (threadIdx.x & 15) * 4;
-    if (y >= p.H || x0 >= p.W) return;
-    float v[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int o = 0; o < m; ++o) {
-        const int4 e = obj[o];
-        const int dy = y - e.y;
-        if (abs(dy) > e.z) continue;
-        const double dy2 = (double)dy * (double)dy, d = den[o];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int dx = x0 + i - e.x;
-            if (abs(dx) <= e.z) {
-                // gaussian2D's cut h < eps * max can never fire: the smallest value, at a corner, is exp(-2 r r / (2 s s)) with
-                // s = (2 r + 1) / 6 > r / 3, which is above exp(-9), far above 2.2e-16
-                const float gval = (float)exp(-((double)dx * (double)dx + dy2) / d);
-                v[i] = fmaxf(v[i], gval);
-            }
-        }
-    }
-    float *dst = hm + (((size_t)b * p.C + c) * p.H + y) * p.W + x0;
-    if (x0 + 3 < p.W && ((uintptr_t)dst & 15) == 0) {
-        *(float4 *)dst = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-        for (int i = 0; i < 4 && x0 + i < p.W; ++i) dst[i] = v[i];
-    }
+    const int c = blockIdx.y, b = blockIdx.z;
+    // (slots past G hold radius -1)
+    heat_tile<CNT_MAX_M>(draw + (size_t)b * p.M, min(p.G, p.M), c, blockIdx.x, tiles_x, p.H, p.W, hm + ((size_t)b * p.C + c) * p.H * p.W);
 }
 
 }  // namespace md
@@ -185,7 +127,7 @@ extern "C" int md_cn_assign_targets(MD_AOT_ARGS) {
     if (M > 0)
         hipLaunchKernelGGL(cn_row_kernel, dim3((unsigned)((B * M + 255) / 256)), dim3(256), 0, s, (const float *)params[0],
                            (const int *)params[1], p, (int *)params[3], (uint8_t *)params[4], (float *)params[5], (float *)params[6], draw);
-    const int tiles_x = (int)((W + CNT_TILE_W - 1) / CNT_TILE_W), tiles_y = (int)((H + CNT_TILE_H - 1) / CNT_TILE_H);
+    const int tiles_x = (int)((W + HEAT_TILE_W - 1) / HEAT_TILE_W), tiles_y = (int)((H + HEAT_TILE_H - 1) / HEAT_TILE_H);
     hipLaunchKernelGGL(cn_heat_kernel, dim3((unsigned)(tiles_x * tiles_y), (unsigned)C, (unsigned)B), dim3(256), 0, s, draw, p, tiles_x,
                        (float *)params[2]);
     return launched();

@@ -36,6 +36,7 @@
 #pragma clang fp contract(off)
 
 #include "aug_geom.h"
+#include "workgroup.h"
 
 namespace md {
 
@@ -254,7 +255,7 @@ __global__ __launch_bounds__(256) void cp_points_flag_kernel(PtsArgs a) {
 // sample record: 0 flip_a, 1 flip_b, 2 cos / 3 sin of the rotation, 4 scale, 5-7 translation
 __global__ __launch_bounds__(256) void cp_points_scan_kernel(PtsArgs a) {
     __shared__ int wsum[4];
-    scan_block_counts(a.bsum, a.nb, wsum);
+    compaction_offsets(a.bsum, a.nb, wsum);
     for (int b = threadIdx.x; b <= a.B; b += 256) {
         const int o = clampi(merged_start(a, b), 0, a.N + a.Ns), blk = o >> 8;      // blk <= nb
         int v = a.bsum[blk];
@@ -364,7 +365,7 @@ __global__ __launch_bounds__(64) void cp_boxes_kernel(BoxArgs a) {
         }
         const unsigned long long bal = __ballot(keep);
         if (keep) {
-            const int at = base + __popcll(bal & ((1ull << lane) - 1ull));
+            const int at = base + lane_rank(bal);
             float *dst = out + (size_t)at * CPA_BOX;
             for (int e = 0; e < CPA_BOX; ++e) dst[e] = o[e];
             out_cls[at] = cls;

@@ -7,9 +7,7 @@
 //   cp_slot_kernel  one workgroup per (sample, task): the sample's rows staged in LDS, membership and slot ranks by counting, every row
 //                   of ind / mask / cat / anno_box and the task's rows of gt_boxes_and_cls written once, and the task's draw list
 //                   (ct_int x, y, radius, class; one entry per slot, radius -1 for a skipped row) left in the workspace
-//   cp_heat_kernel  gather form: one workgroup per 64 x 16 tile of one (sample, task, class) map; the draw list is compacted to the
-//                   entries of the class whose window meets the tile, each lane takes the maximum over them for its four consecutive
-//                   x cells and stores them once, zeros included (16-byte stores where the row pitch allows) -- no memset, no atomics
+//   cp_heat_kernel  heatmap.h's heat_tile on one 64 x 16 tile of one (sample, task, class) map, the task's draw list filtered by class
 // Same float32 operation order as the numpy code under NumPy >= 2 scalar promotion (fp contraction off); the Gaussian in float64.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -20,12 +18,13 @@
 
 #pragma clang fp contract(off)
 
+#include "heatmap.h"
+
 namespace md {
 
 static_assert(sizeof(md_cp_targets_attrs) == 4 + 8 * 4 + 2 * 4 + 2 * 4 + 4 + 4 + 4, "minddet_hip_cptargets.h: attribute struct layout");
 
 constexpr int CPT_MAX_GT = MD_CP_TARGETS_MAX_GT;
-constexpr int CPT_TILE_W = 64, CPT_TILE_H = 16;   // 16 lanes x 4 cells wide, 16 rows: one cell quad per lane of a 256-lane workgroup
 constexpr int CPT_INVALID = 0x7fffffff;
 
 struct CptParams {
@@ -55,15 +54,6 @@ __device__ __forceinline__ float gaussian_radius_f32(float height, float width, 
     return fminf(fminf(r1, r2), r3);
 }
 
-__device__ __forceinline__ int block_sum(int v, int *red) {
-    // 256 lanes: wave totals through LDS (red: 4 ints)
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    __syncthreads();   // red may still be read from an earlier call
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
-
 __global__ __launch_bounds__(256) void cp_slot_kernel(const float *__restrict__ gt_boxes, const int *__restrict__ gt_classes, CptParams p,
                                                       float *__restrict__ anno_box, int *__restrict__ ind, uint8_t *__restrict__ mask,
                                                       int *__restrict__ cat, float *__restrict__ gbc, int4 *__restrict__ draw) {
@@ -84,9 +74,9 @@ __global__ __launch_bounds__(256) void cp_slot_kernel(const float *__restrict__ 
         n_task += valid && c > base && c <= base + nc;
     }
     for (int j = G + threadIdx.x; j < ((G + 3) & ~3); j += 256) cls[j] = CPT_INVALID;   // the counting loop reads four classes at a time
-    n_before = block_sum(n_before, red);
-    n_task = block_sum(n_task, red);
-    n_all = block_sum(n_all, red);   // (the barriers inside also publish box / cls)
+    n_before = block_count(n_before, red);
+    n_task = block_count(n_task, red);
+    n_all = block_count(n_all, red);   // (the barriers inside also publish box / cls)
 
     const size_t row0 = ((size_t)b * p.T + t) * M;
     int4 *dl = draw + ((size_t)b * p.T + t) * (G + 1);
@@ -143,67 +133,10 @@ __global__ __launch_bounds__(256) void cp_slot_kernel(const float *__restrict__ 
 }
 
 __global__ __launch_bounds__(256) void cp_heat_kernel(const int4 *__restrict__ draw, CptParams p, int tiles_x, float *__restrict__ hm) {
-    __shared__ int4 obj[CPT_MAX_GT];        // the surviving entries: (cx, cy, radius, -)
-    __shared__ double den[CPT_MAX_GT];      // 2 s s of each
-    __shared__ int wave_cnt[4];
-    __shared__ int n_obj;
-    const int tile = blockIdx.x, tc = blockIdx.y, b = blockIdx.z;
-    const int t = tc / p.C, c = tc - t * p.C;
-    const int tx0 = (tile % tiles_x) * CPT_TILE_W, ty0 = (tile / tiles_x) * CPT_TILE_H;
-    const int tx1 = min(tx0 + CPT_TILE_W, p.W) - 1, ty1 = min(ty0 + CPT_TILE_H, p.H) - 1;
+    const int tc = blockIdx.y, b = blockIdx.z, t = tc / p.C, c = tc - t * p.C;
     const int4 *dl = draw + ((size_t)b * p.T + t) * (p.G + 1);
     const int n = c < p.num_classes[t] ? min(dl[0].x, p.G) : 0;   // a channel past the task's classes: nothing to scan, zeros are stored
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) n_obj = 0;
-    __syncthreads();
-    // compaction in list order: ballot inside each wave, the waves' counts through LDS
-    for (int j0 = 0; j0 < n; j0 += 256) {
-        const int j = j0 + threadIdx.x;
-        int4 e = make_int4(0, 0, -1, -1);
-        if (j < n) e = dl[1 + j];
-        // the window [cx - r, cx + r] x [cy - r, cy + r] meets the tile (written so that no sum can overflow)
-        const bool keep = e.z >= 0 && e.w == c && e.z >= tx0 - e.x && e.z >= e.x - tx1 && e.z >= ty0 - e.y && e.z >= e.y - ty1;
-        const unsigned long long bal = __ballot(keep);
-        if (lane == 0) wave_cnt[wave] = __popcll(bal);
-        __syncthreads();
-        int at = n_obj;
-        for (int v = 0; v < wave; ++v) at += wave_cnt[v];
-        at += __popcll(bal & ((1ull << lane) - 1ull));
-        if (keep) {
-            obj[at] = e;
-            const double sigma = (2.0 * (double)e.z + 1.0) / 6.0;   // diameter / 6
-            den[at] = 2.0 * sigma * sigma;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) n_obj += wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
-        __syncthreads();
-    }
-    const int m = n_obj;
-    const int y = ty0 + (threadIdx.x >> 4), x0 = tx0 + (threadIdx.x & 15) * 4;
-    if (y >= p.H || x0 >= p.W) return;
-    float v[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int o = 0; o < m; ++o) {
-        const int4 e = obj[o];
-        const int dy = y - e.y;
-        if (abs(dy) > e.z) continue;
-        const double dy2 = (double)dy * (double)dy, d = den[o];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int dx = x0 + i - e.x;
-            if (abs(dx) <= e.z) {
-                // gaussian2D's cut h < eps * max can never fire: the smallest value, at a corner, is exp(-2 r r / (2 s s)) with
-                // s = (2 r + 1) / 6 > r / 3, which is above exp(-9), far above 2.2e-16
-                const float gval = (float)exp(-((double)dx * (double)dx + dy2) / d);
-                v[i] = fmaxf(v[i], gval);
-            }
-        }
-    }
-    float *dst = hm + (((size_t)b * p.T * p.C + tc) * p.H + y) * p.W + x0;
-    if (x0 + 3 < p.W && ((uintptr_t)dst & 15) == 0) {
-        *(float4 *)dst = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-        for (int i = 0; i < 4 && x0 + i < p.W; ++i) dst[i] = v[i];
-    }
+    heat_tile<CPT_MAX_GT>(dl + 1, n, c, blockIdx.x, tiles_x, p.H, p.W, hm + ((size_t)b * p.T * p.C + tc) * p.H * p.W);
 }
 
 }  // namespace md
@@ -255,7 +188,7 @@ extern "C" int md_cp_assign_targets(MD_AOT_ARGS) {
     int4 *draw = (int4 *)ws.ptr;
     hipLaunchKernelGGL(cp_slot_kernel, dim3((unsigned)T, (unsigned)B), dim3(256), 0, s, (const float *)params[0], (const int *)params[1], p,
                        (float *)params[3], (int *)params[4], (uint8_t *)params[5], (int *)params[6], (float *)params[7], draw);
-    const int tiles_x = (int)((W + CPT_TILE_W - 1) / CPT_TILE_W), tiles_y = (int)((H + CPT_TILE_H - 1) / CPT_TILE_H);
+    const int tiles_x = (int)((W + HEAT_TILE_W - 1) / HEAT_TILE_W), tiles_y = (int)((H + HEAT_TILE_H - 1) / HEAT_TILE_H);
     hipLaunchKernelGGL(cp_heat_kernel, dim3((unsigned)(tiles_x * tiles_y), (unsigned)(T * C), (unsigned)B), dim3(256), 0, s, draw, p, tiles_x,
                        (float *)params[2]);
     return launched();

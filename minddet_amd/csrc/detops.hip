@@ -4,8 +4,7 @@
 //   md_anchors_3d_stride   pointpillars/src/core/box_np_ops.py:453-523 (create_anchors_3d_stride)
 //   md_anchors_3d_range    pointpillars/src/core/box_np_ops.py:526-568 (create_anchors_3d_range); both write into the
 //                          concatenated table of several generators (pointpillars/src/core/target_assigner.py:227-249)
-//   md_anchor_mask         pointpillars/src/data/preprocess.py:211-225 +
-//                          pointpillars/src/core/box_np_ops.py:745-776
+//   (md_anchor_mask: ppreader.hip, next to the batched md_pp_anchor_mask whose kernels it shares)
 //   md_second_box_decode   pointpillars/src/core/box_ops.py:47-85 / box_np_ops.py:40-67
 //   md_topk_segmented      ops.TopK(sorted=True) call sites: centernet/src/decode.py:81,96,101;
 //                          centerpoint/.../center_head.py:435; pointpillars/src/pointpillars.py:764
@@ -22,6 +21,7 @@
 
 #include "aot.h"
 #include "device.h"
+#include "workgroup.h"
 
 // every product and sum below rounds on its own; set before box_codec.h, whose delta2bbox_one takes the including unit's mode
 #pragma clang fp contract(off)
@@ -109,57 +109,6 @@ __global__ void anchors_3d_range_kernel(Anchor3dRangeArgs a, float *__restrict__
         o[3] = a.size[sz][0]; o[4] = a.size[sz][1]; o[5] = a.size[sz][2];
         o[6] = a.rot[r];
     }
-}
-
-// anchor mask: dense count map -> integral image -> 4-corner box sums (integer exact)
-__global__ void amask_scatter_kernel(const int *__restrict__ coors, int nv, int nx, int ny, int *__restrict__ dense) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nv) return;
-    const int y = coors[i * 3 + 1], x = coors[i * 3 + 2];
-    if ((unsigned)y < (unsigned)ny && (unsigned)x < (unsigned)nx) atomicAdd(&dense[y * nx + x], 1);
-}
-// cumsum along axis 0 (y) then axis 1 (x): one thread per column / per row (maps are ~500x500)
-__global__ void amask_cumsum_y_kernel(int *__restrict__ dense, int nx, int ny) {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x;
-    if (x >= nx) return;
-    int acc = 0;
-    for (int y = 0; y < ny; ++y) { acc += dense[y * nx + x]; dense[y * nx + x] = acc; }
-}
-__global__ void amask_cumsum_x_kernel(int *__restrict__ dense, int nx, int ny) {
-    // one wave per row, wave-level inclusive scan over 64-wide chunks
-    const int y = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (y >= ny) return;
-    int carry = 0;
-    for (int x0 = 0; x0 < nx; x0 += 64) {
-        const int x = x0 + lane;
-        int v = x < nx ? dense[y * nx + x] : 0;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_up(v, o, 64);
-            if (lane >= o) v += t;
-        }
-        v += carry;
-        if (x < nx) dense[y * nx + x] = v;
-        carry = __shfl(v, 63, 64);
-    }
-}
-__global__ void amask_area_kernel(const int *__restrict__ dense, const float *__restrict__ bv, int n, int nx, int ny,
-                                  float sx, float sy, float ox, float oy, float thr, float *__restrict__ area,
-                                  unsigned char *__restrict__ mask) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float4 b = *reinterpret_cast<const float4 *>(bv + (size_t)i * 4);
-    int c0 = (int)floorf((b.x - ox) / sx), c1 = (int)floorf((b.y - oy) / sy);
-    int c2 = (int)floorf((b.z - ox) / sx), c3 = (int)floorf((b.w - oy) / sy);
-    c0 = max(c0, 0); c1 = max(c1, 0); c2 = min(c2, nx - 1); c3 = min(c3, ny - 1);
-    // numpy negative indices wrap (a box entirely left of / below the grid): mirror that
-    const int C0 = c0, C1 = c1, C2 = c2 < 0 ? c2 + nx : c2, C3 = c3 < 0 ? c3 + ny : c3;
-    const int c0w = min(C0, nx - 1), c1w = min(C1, ny - 1);
-    const int v = dense[C3 * nx + C2] - dense[C3 * nx + c0w] - dense[c1w * nx + C2] + dense[c1w * nx + c0w];
-    const float a = (float)v;
-    area[i] = a;
-    mask[i] = a > thr ? 1 : 0;
 }
 
 // ------------------------------------------------------------------------------------------ codecs
@@ -408,7 +357,7 @@ __device__ void topk_block_select(const float *__restrict__ scores, const int *_
     {
         unsigned c = 0;
         sweep([&](int i, unsigned u) { c += (i < n && u > omin) ? 1u : 0u; });
-        for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+        c = wave_sum_all(c);
         if ((tid & 63) == 0 && c) atomicAdd(&s_count, c);
     }
     __syncthreads();
@@ -483,13 +432,13 @@ __device__ void topk_block_select(const float *__restrict__ scores, const int *_
                 if (ln == leader) base_pos = atomicAdd(&s_count, (unsigned)__popcll(bal));
                 base_pos = __builtin_amdgcn_readlane(base_pos, leader);
                 if (take) {
-                    const unsigned pos = base_pos + (unsigned)__popcll(bal & ((1ull << ln) - 1ull));
+                    const unsigned pos = base_pos + (unsigned)lane_rank(bal);
                     if (pos < (unsigned)TOPK_MAXK) sel[pos] = ((unsigned long long)(~u) << 32) | (unsigned)i;
                 }
             }
             ties += (i < n && u > omin && u == thr && remaining > 0) ? 1u : 0u;
         });
-        for (int o = 32; o > 0; o >>= 1) ties += __shfl_xor(ties, o, 64);
+        ties = wave_sum_all(ties);
         if ((tid & 63) == 0 && ties) atomicAdd(&s_tie_total, ties);
     }
     __syncthreads();
@@ -520,7 +469,7 @@ __device__ void topk_block_select(const float *__restrict__ scores, const int *_
             }
             __syncthreads();
             if (tie) {
-                const unsigned rank = s_wave_base[wv] + (unsigned)__popcll(bal & ((1ull << ln) - 1ull));
+                const unsigned rank = s_wave_base[wv] + (unsigned)lane_rank(bal);
                 if (rank < remaining) sel[(unsigned)kk - remaining + rank] = ((unsigned long long)(~u) << 32) | (unsigned)i;
             }
             const bool done = s_tie_taken >= remaining;   // every thread reads the same value between the two barriers
@@ -663,23 +612,11 @@ __global__ __launch_bounds__(256) void topk_compact_kernel(const float *__restri
         if (i >= c1 || !(u[j] > omin && (u[j] >> 21) >= b1)) u[j] = 0u;  // ford() of a selectable score is never 0
         cnt += u[j] != 0u;
     }
-    unsigned inc = cnt;  // inclusive prefix over the wave, then wave bases through LDS
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-    }
-    __syncthreads();  // part[] is reused
-    if (lane == 63) part[wv] = inc;
-    __syncthreads();
-    unsigned wbase = 0, total = 0;
-    for (int w = 0; w < 4; ++w) {
-        if (w < wv) wbase += part[w];
-        total += part[w];
-    }
+    unsigned total;
+    const unsigned before = block_exclusive_scan<4>(cnt, part, total);   // (its leading barrier: part[] is reused)
     if (tid == 0) part[8] = total ? atomicAdd(&cand_cnt[seg], total) : 0u;
     __syncthreads();
-    unsigned pos = part[8] + wbase + inc - cnt;
+    unsigned pos = part[8] + before;
 #pragma unroll
     for (int j = 0; j < PER; ++j) {
         if (u[j] != 0u) {
@@ -1310,34 +1247,6 @@ extern "C" int md_anchors_3d_range(MD_AOT_ARGS) {
     const int64_t locs = (int64_t)a.D * a.H * a.W;
     if (g.numel(0) != locs * a.slots * 7 || !g.have({0})) return MD_ERR_ARG;
     hipLaunchKernelGGL(anchors_3d_range_kernel, dim3(grid1d((size_t)locs * per)), dim3(256), 0, (hipStream_t)stream, a, (float *)params[0]);
-    return launched();
-}
-
-extern "C" int md_anchor_mask(MD_AOT_ARGS) {
-    // in: coors[V,3] i32 (z,y,x), anchors_bv[N,4] f32 ; out: area[N] f32, mask[N] u8 ; ws: ny*nx i32
-    Args a(MD_ARGS, 4, 5);
-    const md_anchor_mask_attrs *at = a.attrs<md_anchor_mask_attrs>(extra);
-    a.tensor(0, I32, 2); a.tensor(1, F32, 2); a.tensor(2, F32); a.tensor(3, U8);
-    const int64_t nv = a.d(0, 0), n = a.d(1, 0);
-    a.require(nv >= 0 && n >= 0 && a.d(0, 1) == 3 && a.d(1, 1) == 4 && a.numel(2) >= n && a.numel(3) >= n);
-    if (int rc = a.rc()) return rc;
-    const int nx = at->grid_x, ny = at->grid_y;
-    if (nx < 1 || ny < 1 || (int64_t)nx * ny > (1 << 28)) return MD_ERR_SIZE;
-    if ((nv > 0 && !a.have({0})) || (n > 0 && !a.have({1, 2, 3}))) return MD_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    Scratch ws;
-    if (int rc = ws.acquire((size_t)nx * ny * 4, a, 4, s)) return rc;
-    int *dense = (int *)ws.ptr;
-    MD_HIP_TRY(hipMemsetAsync(dense, 0, (size_t)nx * ny * 4, s));
-    if (nv > 0)
-        hipLaunchKernelGGL(amask_scatter_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, s,
-                           (const int *)params[0], (int)nv, nx, ny, dense);
-    hipLaunchKernelGGL(amask_cumsum_y_kernel, dim3((nx + 255) / 256), dim3(256), 0, s, dense, nx, ny);
-    hipLaunchKernelGGL(amask_cumsum_x_kernel, dim3((ny + 3) / 4), dim3(256), 0, s, dense, nx, ny);
-    if (n > 0)
-        hipLaunchKernelGGL(amask_area_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dense,
-                           (const float *)params[1], (int)n, nx, ny, at->voxel_x, at->voxel_y, at->offset_x,
-                           at->offset_y, at->area_threshold, (float *)params[2], (unsigned char *)params[3]);
     return launched();
 }
 

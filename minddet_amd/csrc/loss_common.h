@@ -11,6 +11,7 @@
 
 #include "aot.h"
 #include "device.h"
+#include "workgroup.h"
 
 #pragma clang fp contract(off)
 
@@ -31,14 +32,7 @@ template <int N> __device__ __forceinline__ void block_sums(double (&v)[N], doub
 #pragma unroll
     for (int e = 0; e < N; ++e) v[e] = ((red[e] + red[N + e]) + red[2 * N + e]) + red[3 * N + e];
 }
-// a block sum of integers (256 lanes; red: 4 ints); every lane gets the sum
-__device__ __forceinline__ int block_count(int v, int *red) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
+// (block_count, the block sum of integers: workgroup.h)
 
 // ---------------------------------------------------------------------------------------------------- focal terms (CenterNet form)
 // A term and its derivative are two functions (the logs and squares they both spell are computed once after inlining): a caller that

@@ -26,6 +26,7 @@
 
 #include "aot.h"
 #include "rot_geom.h"
+#include "workgroup.h"
 #include "../../include/minddet_hip_cp.h"
 
 #pragma clang fp contract(off)
@@ -423,7 +424,7 @@ __global__ __launch_bounds__(256) void nms_scan_kernel(const unsigned long long 
                 cand = ~cur;
             }
             if ((kept >> lane) & 1ull) {
-                const int pos = total + __popcll(kept & ((1ull << lane) - 1ull));
+                const int pos = total + lane_rank(kept);
                 keep[pos] = (KeepT)r;
                 if (pos < SCAN_KEEP_CAP) s_keep[pos] = r;
                 if (keepmask) keepmask[r] = 1;

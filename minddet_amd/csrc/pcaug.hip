@@ -22,7 +22,8 @@
 
 #pragma clang fp contract(off)
 
-#include "aug_geom.h"      // rect_corners, covers, collide; find_sample and the compaction's block counts, scan and ranks
+#include "aug_geom.h"      // rect_corners, covers, collide, find_sample
+#include "workgroup.h"     // the compaction's block counts, scan and ranks
 
 namespace md {
 
@@ -231,7 +232,7 @@ __global__ __launch_bounds__(256) void pc_classify_kernel(PointArgs a) {
 
 __global__ __launch_bounds__(256) void pc_scan_kernel(PointArgs a) {
     __shared__ int wsum[4];
-    scan_block_counts(a.bsum, a.nb, wsum);
+    compaction_offsets(a.bsum, a.nb, wsum);
     for (int b = threadIdx.x; b <= a.B; b += 256) {
         const int o = min(max(a.offsets[b], 0), a.N), blk = o >> 8;      // blk <= nb
         int v = a.bsum[blk];
@@ -311,7 +312,7 @@ __global__ __launch_bounds__(64) void pc_boxes_kernel(BoxArgs a) {
         }
         const unsigned long long bal = __ballot(keep);
         if (keep) {
-            const int at = base + __popcll(bal & ((1ull << lane) - 1ull));
+            const int at = base + lane_rank(bal);
             float *dst = a.out + ((size_t)b * G + at) * 7;
             for (int e = 0; e < 7; ++e) dst[e] = o[e];
             a.out_classes[(size_t)b * G + at] = a.classes[(size_t)b * G + g];

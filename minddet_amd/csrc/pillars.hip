@@ -27,6 +27,7 @@
 #include "../../include/minddet_hip_points.h"
 #include "aot.h"
 #include "device.h"
+#include "workgroup.h"
 
 namespace md {
 
@@ -97,24 +98,7 @@ __global__ __launch_bounds__(PV_THREADS) void vox_flag_kernel(VoxArgs a) {
 // ---- exclusive prefix sum of an int array in three launches: block sums, one workgroup over the block sums, the blocks again
 __device__ __forceinline__ int pv_block_exclusive(int v, int *total) {   // exclusive scan of one value per thread over the workgroup
     __shared__ int wsum[PV_THREADS / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += t;
-    }
-    __syncthreads();                    // a second call in one kernel must not overwrite wsum under a reader
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    int base = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < PV_THREADS / 64; ++w) {
-        if (w < wave) base += wsum[w];
-        all += wsum[w];
-    }
-    *total = all;
-    return base + inc - v;
+    return block_exclusive_scan<PV_THREADS / 64>(v, wsum, *total);   // (its leading barrier: a second call must not overwrite wsum under a reader)
 }
 
 __global__ __launch_bounds__(PV_THREADS) void scan_reduce_kernel(const int *val, int n, int *bsum) {
@@ -129,15 +113,8 @@ __global__ __launch_bounds__(PV_THREADS) void scan_reduce_kernel(const int *val,
 }
 
 __global__ __launch_bounds__(PV_THREADS) void scan_top_kernel(int *bsum, int nb) {   // one workgroup; bsum -> its exclusive prefix, in place
-    int carry = 0;
-    for (int base = 0; base < nb; base += PV_THREADS) {
-        const int i = base + threadIdx.x;
-        const int v = i < nb ? bsum[i] : 0;
-        int total;
-        const int ex = pv_block_exclusive(v, &total);
-        if (i < nb) bsum[i] = carry + ex;
-        carry += total;
-    }
+    __shared__ int wsum[PV_THREADS / 64];
+    scan_block_counts<PV_THREADS / 64>(bsum, nb, wsum);
 }
 
 __global__ __launch_bounds__(PV_THREADS) void scan_down_kernel(const int *val, int n, const int *bsum, int *out) {   // out[n + 1]

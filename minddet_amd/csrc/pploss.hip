@@ -76,7 +76,7 @@ __global__ __launch_bounds__(256) void pp_loss_dense_kernel(const uint16_t *__re
     if (threadIdx.x < 64) {   // the sample's positives: a sum of exact integers
         int n = 0;
         for (int i = lane; i < p.chunks_per_sample; i += 64) n += counts[(size_t)b * p.chunks_per_sample + i];
-        for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64);
+        n = wave_sum_all(n);
         if (lane == 0) s_nb[0] = (double)max(n, 1);
     }
     __syncthreads();

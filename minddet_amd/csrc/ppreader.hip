@@ -1,5 +1,5 @@
 // ppreader.hip -- the front end of the anchor-based (KITTI) PointPillars: md_pp_pillar_encode (its PillarFeatureNet + PointPillarsScatter
-// in one launch) and md_pp_anchor_mask (the anchor mask of a whole batch, voxel_num read on the device).  The ABI, the exact semantics
+// in one launch), md_pp_anchor_mask (the anchor mask of a whole batch, voxel_num read on the device) and md_anchor_mask (of one sample).  The ABI, the exact semantics
 // and the reference lines are in include/minddet_hip_ppreader.h.
 //
 // md_pp_pillar_encode: one wave owns one voxel at a time (grid-stride over the B x max_voxels rows, rows >= voxel_num[b] skipped
@@ -21,8 +21,10 @@
 // the MFMA work is 2 x 160 000 instructions of 16 passes, under 10 us over 1024 SIMDs.
 // DESIGN 9 item 9 has the measured figure (98 us at 40 000 live rows per sample: far from that floor, and not bound by the product).
 //
-// md_pp_anchor_mask: md_anchor_mask's four steps (zero, scatter-add, cumsum along y and x, 4-corner box sums), each as one launch over
-// the batch; a sample's rows are cut at voxel_num[b] on the device.  Integer counts: the result is exact whatever the atomics' order.
+// md_pp_anchor_mask, md_anchor_mask (pointpillars/src/data/preprocess.py:211-225 + core/box_np_ops.py:745-776): four steps (zero,
+// scatter-add, cumsum along y and x, 4-corner box sums), each as one launch over the batch; a sample's rows are cut at voxel_num[b] on
+// the device.  md_anchor_mask, the mask of one sample from [V, 3] coordinates, is the same launches with B = 1 and no voxel_num.
+// Integer counts: the result is exact whatever the atomics' order.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -30,6 +32,7 @@
 #include "../../include/minddet_hip_ppreader.h"
 #include "aot.h"
 #include "device.h"
+#include "workgroup.h"
 
 namespace md {
 
@@ -168,25 +171,27 @@ __global__ __launch_bounds__(PR_WAVES * 64) void pp_pillar_encode_kernel(PPEncAr
     }
 }
 
-// ---- anchor mask over the batch: md_anchor_mask's kernels (detops.hip) with a sample index
-__global__ void ppmask_scatter_kernel(const int *__restrict__ coors, const int *__restrict__ voxel_num, int B, int MV, int nx, int ny,
-                                      int *__restrict__ dense) {
+// ---- the anchor mask of B samples (md_anchor_mask: B = 1): dense count map -> integral image -> 4-corner box sums, integer exact
+// coors: B * MV rows of `row` ints with y and x in columns cy and cx; voxel_num: rows of a sample that count, or NULL for all MV
+__global__ void amask_scatter_kernel(const int *__restrict__ coors, int row, int cy, int cx, const int *__restrict__ voxel_num, int B,
+                                     int MV, int nx, int ny, int *__restrict__ dense) {
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < (size_t)B * MV; e += (size_t)gridDim.x * blockDim.x) {
         const int b = (int)(e / MV), i = (int)(e - (size_t)b * MV);
-        if (i >= voxel_num[b]) continue;
-        const int y = coors[e * 4 + 2], x = coors[e * 4 + 3];
+        if (voxel_num && i >= voxel_num[b]) continue;
+        const int y = coors[e * row + cy], x = coors[e * row + cx];
         if ((unsigned)y < (unsigned)ny && (unsigned)x < (unsigned)nx) atomicAdd(&dense[((size_t)b * ny + y) * nx + x], 1);
     }
 }
-__global__ void ppmask_cumsum_y_kernel(int *__restrict__ dense, int B, int nx, int ny) {
+// cumsum along y then along x: one thread per column, one wave per row (maps are ~500 x 500)
+__global__ void amask_cumsum_y_kernel(int *__restrict__ dense, int B, int nx, int ny) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= B * nx) return;
     const int b = t / nx, x = t - b * nx;
-    int *d = dense + (size_t)b * ny * nx;
+    int *d = dense + (size_t)b * ny * nx + x;   // the column, one row further each step
     int acc = 0;
-    for (int y = 0; y < ny; ++y) { acc += d[y * nx + x]; d[y * nx + x] = acc; }
+    for (int y = 0; y < ny; ++y, d += nx) { acc += d[0]; d[0] = acc; }
 }
-__global__ void ppmask_cumsum_x_kernel(int *__restrict__ dense, int B, int nx, int ny) {   // one wave per row of a sample
+__global__ void amask_cumsum_x_kernel(int *__restrict__ dense, int B, int nx, int ny) {   // 64-wide chunks with a carry
     const int row = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (row >= B * ny) return;
@@ -194,20 +199,13 @@ __global__ void ppmask_cumsum_x_kernel(int *__restrict__ dense, int B, int nx, i
     int carry = 0;
     for (int x0 = 0; x0 < nx; x0 += 64) {
         const int x = x0 + lane;
-        int v = x < nx ? d[x] : 0;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_up(v, o, 64);
-            if (lane >= o) v += t;
-        }
-        v += carry;
+        const int v = wave_inclusive_scan(x < nx ? d[x] : 0) + carry;
         if (x < nx) d[x] = v;
         carry = __shfl(v, 63, 64);
     }
 }
-// the arithmetic of amask_area_kernel, expression for expression: the two must agree bit for bit
-__global__ void ppmask_area_kernel(const int *__restrict__ dense, const float *__restrict__ bv, int B, int n, int nx, int ny, float sx,
-                                   float sy, float ox, float oy, float thr, float *__restrict__ area, unsigned char *__restrict__ mask) {
+__global__ void amask_area_kernel(const int *__restrict__ dense, const float *__restrict__ bv, int B, int n, int nx, int ny, float sx,
+                                  float sy, float ox, float oy, float thr, float *__restrict__ area, unsigned char *__restrict__ mask) {
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < (size_t)B * n; e += (size_t)gridDim.x * blockDim.x) {
         const int s = (int)(e / n), i = (int)(e - (size_t)s * n);
         const int *d = dense + (size_t)s * ny * nx;
@@ -223,6 +221,23 @@ __global__ void ppmask_area_kernel(const int *__restrict__ dense, const float *_
         if (area) area[e] = ar;
         mask[e] = ar > thr ? 1 : 0;
     }
+}
+
+// the four steps on `dense` (B ny nx ints).  cap: most workgroups of the two grid-stride launches (md_anchor_mask's grids have no cap)
+static int anchor_mask_launch(hipStream_t s, int *dense, const int *coors, int row, int cy, int cx, const int *voxel_num, int64_t B,
+                              int64_t MV, const float *bv, int64_t n, const md_anchor_mask_attrs *at, float *area, unsigned char *mask,
+                              size_t cap) {
+    const int nx = at->grid_x, ny = at->grid_y;
+    MD_HIP_TRY(hipMemsetAsync(dense, 0, (size_t)B * ny * nx * 4, s));
+    if (MV > 0)
+        hipLaunchKernelGGL(amask_scatter_kernel, dim3(grid1d((size_t)(B * MV), cap)), dim3(256), 0, s, coors, row, cy, cx, voxel_num, (int)B,
+                           (int)MV, nx, ny, dense);
+    hipLaunchKernelGGL(amask_cumsum_y_kernel, dim3((unsigned)((B * nx + 255) / 256)), dim3(256), 0, s, dense, (int)B, nx, ny);
+    hipLaunchKernelGGL(amask_cumsum_x_kernel, dim3((unsigned)((B * ny + 3) / 4)), dim3(256), 0, s, dense, (int)B, nx, ny);
+    if (n > 0)
+        hipLaunchKernelGGL(amask_area_kernel, dim3(grid1d((size_t)(B * n), cap)), dim3(256), 0, s, (const int *)dense, bv, (int)B, (int)n, nx,
+                           ny, at->voxel_x, at->voxel_y, at->offset_x, at->offset_y, at->area_threshold, area, mask);
+    return launched();
 }
 
 static inline bool pr_finite(float x) { return x == x && x - x == 0.f; }
@@ -286,18 +301,25 @@ extern "C" int md_pp_anchor_mask(MD_AOT_ARGS) {
     if ((MV > 0 && !g.have({0})) || !g.have({1}) || (n > 0 && !g.have({2, 3}))) return MD_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     Scratch ws;
-    const size_t cells = (size_t)B * ny * nx;
-    if (int rc = ws.acquire(cells * 4, g, 5, s)) return rc;
-    int *dense = (int *)ws.ptr;
-    MD_HIP_TRY(hipMemsetAsync(dense, 0, cells * 4, s));
-    if (MV > 0)
-        hipLaunchKernelGGL(ppmask_scatter_kernel, dim3(grid1d((size_t)(B * MV))), dim3(256), 0, s, g.ptr<const int>(0), g.ptr<const int>(1),
-                           (int)B, (int)MV, nx, ny, dense);
-    hipLaunchKernelGGL(ppmask_cumsum_y_kernel, dim3((unsigned)((B * nx + 255) / 256)), dim3(256), 0, s, dense, (int)B, nx, ny);
-    hipLaunchKernelGGL(ppmask_cumsum_x_kernel, dim3((unsigned)((B * ny + 3) / 4)), dim3(256), 0, s, dense, (int)B, nx, ny);
-    if (n > 0)
-        hipLaunchKernelGGL(ppmask_area_kernel, dim3(grid1d((size_t)(B * n))), dim3(256), 0, s, (const int *)dense, g.ptr<const float>(2),
-                           (int)B, (int)n, nx, ny, at->voxel_x, at->voxel_y, at->offset_x, at->offset_y, at->area_threshold,
-                           g.given(4) ? g.ptr<float>(4) : nullptr, g.ptr<unsigned char>(3));
-    return launched();
+    if (int rc = ws.acquire((size_t)B * ny * nx * 4, g, 5, s)) return rc;
+    return anchor_mask_launch(s, (int *)ws.ptr, g.ptr<const int>(0), 4, 2, 3, g.ptr<const int>(1), B, MV, g.ptr<const float>(2), n, at,
+                              g.given(4) ? g.ptr<float>(4) : nullptr, g.ptr<unsigned char>(3), 16384);
+}
+
+// The mask of one sample.  in: coors[V,3] i32 (z,y,x), anchors_bv[N,4] f32 ; out: area[N] f32, mask[N] u8 ; ws: ny*nx i32
+extern "C" int md_anchor_mask(MD_AOT_ARGS) {
+    Args a(MD_ARGS, 4, 5);
+    const md_anchor_mask_attrs *at = a.attrs<md_anchor_mask_attrs>(extra);
+    a.tensor(0, I32, 2); a.tensor(1, F32, 2); a.tensor(2, F32); a.tensor(3, U8);
+    const int64_t nv = a.d(0, 0), n = a.d(1, 0);
+    a.require(nv >= 0 && n >= 0 && a.d(0, 1) == 3 && a.d(1, 1) == 4 && a.numel(2) >= n && a.numel(3) >= n);
+    if (int rc = a.rc()) return rc;
+    const int nx = at->grid_x, ny = at->grid_y;
+    if (nx < 1 || ny < 1 || (int64_t)nx * ny > (1 << 28)) return MD_ERR_SIZE;
+    if ((nv > 0 && !a.have({0})) || (n > 0 && !a.have({1, 2, 3}))) return MD_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    Scratch ws;
+    if (int rc = ws.acquire((size_t)nx * ny * 4, a, 4, s)) return rc;
+    return anchor_mask_launch(s, (int *)ws.ptr, (const int *)params[0], 3, 1, 2, nullptr, 1, nv, (const float *)params[1], n, at,
+                              (float *)params[2], (unsigned char *)params[3], ~(size_t)0);
 }

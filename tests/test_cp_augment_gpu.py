@@ -177,11 +177,11 @@ def contract_batch(s, b, min_points, bv):
     return dict(count=cnt, accept=accept, pts=p, boxes=bx)
 
 
-def batch3():
+def batch3(sizes=(0, 300, 2050)):
     """B = 3: an empty sample without ground truth, 300 and 2 050 points (blocks that straddle samples, several blocks per sample);
     G = 6, S = 5; the last sample has no candidates (cand_count 0) though its rows are filled"""
     rng = np.random.default_rng(5)
-    sizes, G, S = [0, 300, 2050], 6, 5
+    G, S = 6, 5
     boxes = np.zeros((3, G, 9), np.float32)
     for b in range(3):
         for g in range(G):
@@ -244,6 +244,16 @@ def test_batch_with_an_empty_sample_and_straddling_blocks():
     assert not got["accept"][2].any() and got["offsets"][3] - got["offsets"][2] == 2050
     assert 0 < got["accept"][1].sum() < 5 and (got["keep"][1] == 0).any() and got["keep"][1].any()
     assert len(got["points"]) == 2350 + len(s["cand_points"]) and got["offsets"][3] < len(got["points"])
+
+
+def test_compaction_with_more_block_counts_than_one_scan_pass():
+    """256 * 256 + 1 scene points and the candidates' in front of them: more than 256 block counts, so the one-workgroup scan of the
+    counts takes a second pass and carries the first's total"""
+    s = batch3(sizes=(0, 300, 256 * 256 + 1 - 300))
+    bv = (-51.2, -51.2, 51.2, 51.2)
+    got = to_np(run_ops(batch_dev(s), bv, 10))
+    assert all(check_batch("batch3 x 257 blocks", s, got, 10, bv))
+    assert len(got["points"]) > 256 * 256 and got["offsets"][3] > 256 * 256 and got["points"][got["offsets"][3] - 1].any()
 
 
 def crowded():

@@ -1,7 +1,9 @@
 """CPU: the device code the kernels share is stated once.  A text scan of minddet_amd/csrc: the bf16 conversions, the packed ReLU, the
 buffer-descriptor flag word and the vector typedefs live in device.h, the delta-to-box arithmetic in box_codec.h, the training losses'
-block sums, focal terms, strip staging and ownership rule in loss_common.h, and no .hip file spells any of them again (a new kernel
-includes the header instead of copying the file before it)."""
+block sums, focal terms, strip staging and ownership rule in loss_common.h, the integer wave and workgroup primitives (scans, ballot
+ranks) in workgroup.h, the gather-form Gaussian heat map in heatmap.h, the anchor mask's kernels (one set for md_anchor_mask and
+md_pp_anchor_mask) in ppreader.hip, and no other file spells any of them again (a new kernel includes the header instead of copying
+the file before it)."""
 import glob
 import os
 
@@ -24,11 +26,17 @@ ONLY_IN = {
     "(pred > target)": "loss_common.h",        # the sign of an L1 term
     "elems / 8": "loss_common.h",              # the 16-byte staging of a dense kernel's strip
     "hi[i] <= lo[j]": "loss_common.h",         # each gradient element has one owner
+    "__shfl_up(": "workgroup.h",               # the 64-lane inclusive scan
+    "(1ull << lane) - 1ull": "workgroup.h",    # a lane's rank in a ballot
+    "exp(-((double)dx": "heatmap.h",           # the float64 Gaussian of a heat map
+    "2.0 * sigma * sigma": "heatmap.h",        # its denominator
+    "d[C3 * nx + C2]": "ppreader.hip",         # the anchor mask's 4-corner box sum
+    "acc += d[": "ppreader.hip",               # its column cumsum
 }
 
 
 def test_every_translation_unit_was_read():
-    assert len(HIP) >= 15 and {"device.h", "box_codec.h", "aot.h", "loss_common.h"} <= set(SRC)
+    assert len(HIP) >= 15 and {"device.h", "box_codec.h", "aot.h", "loss_common.h", "workgroup.h", "heatmap.h"} <= set(SRC)
 
 
 @pytest.mark.parametrize("text", list(ONLY_IN), ids=[t.strip("( +") for t in ONLY_IN])

@@ -171,11 +171,11 @@ def test_crowded_scenes_select_the_contracts_tries():
         assert (sel >= 64).any() and (sel > 0).sum() >= 20 and (sel[:, :33] < 0).sum() >= 20 and (sel[1, 33:] == -1).all()
 
 
-def batch3():
+def batch3(sizes=(0, 300, 2050)):
     """B = 3: an empty sample, 300 and 2 050 points (blocks that straddle samples, several blocks per sample), the empty sample without
     ground truth; G = 6, T = 7, R = 2"""
     rng = np.random.default_rng(5)
-    sizes, G, T, R = [0, 300, 2050], 6, 7, 2
+    G, T, R = 6, 7, 2
     boxes = np.zeros((3, G, 7), np.float32)
     for b in range(3):
         for g in range(G):
@@ -206,8 +206,7 @@ def batch3_inputs(s):
                 remove_boxes=dev(s["rem"]), remove_count=dev(s["rem_count"]), remove_from=dev(s["rem_from"])), offs
 
 
-def test_batch_with_an_empty_sample_and_straddling_blocks():
-    s = batch3()
+def check_batch3(s):
     d, offs = batch3_inputs(s)
     got = to_np(run_ops(d, s["bv"]))
     assert got["offsets"][0] == 0 and (np.diff(got["offsets"]) >= 0).all() and got["offsets"][1] == 0
@@ -227,7 +226,22 @@ def test_batch_with_an_empty_sample_and_straddling_blocks():
         assert same or not pts["decided"].all()
         if b == 0:
             assert (one["selected"] == -1).all() and not one["gt_boxes"].any() and int(one["gt_count"]) == 0 and (one["owner"] < 0).all()
+    return got, offs
+
+
+def test_batch_with_an_empty_sample_and_straddling_blocks():
+    got, offs = check_batch3(batch3())
     assert (got["owner"][offs[1]:offs[2]] >= 0).any() and (got["selected"][1] >= 0).sum() >= 4
+
+
+def test_compaction_with_more_block_counts_than_one_scan_pass():
+    """256 * 256 + 1 points: 257 block counts, so the one-workgroup scan of the counts takes a second pass and carries the first's total"""
+    s = batch3(sizes=(0, 300, 256 * 256 + 1 - 300))
+    got, offs = check_batch3(s)
+    total = int(got["offsets"][3])
+    assert len(got["owner"]) == 256 * 256 + 1 and total > 256 * 128
+    # every kept row's place, whatever the contract left undecided: the fourth column is copied, so it names the row
+    assert np.array_equal(got["points"][:total, 3], np.concatenate(s["points"])[got["owner"] != -2, 3])
 
 
 def test_determinism_and_call_forms():

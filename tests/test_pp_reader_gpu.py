@@ -196,6 +196,43 @@ def test_batched_anchor_mask_equals_md_anchor_mask_per_sample(name):
     assert torch.equal(det_ops.anchors_mask_batched(ct, vt, (W, H), m.anchors_bv, m.voxel_size, m.pc_range, m.anchor_area_threshold), want_mask)
 
 
+def test_batched_anchor_mask_equals_the_numpy_oracle_per_sample():
+    """md_anchor_mask and md_pp_anchor_mask run one set of kernels, so the test above compares the code with itself: here the judge is
+    oracle/np_ops.anchors_mask (pinned to the reference's fixture by tests/test_oracle_golden.py), area and mask exact.  B = 3 on a
+    70 x 5 grid: a row is one full 64-lane chunk and a partial one, so the carry between chunks runs.  The oracle is given what the
+    header says is counted (the first voxel_num[b] rows, those inside the grid).  It raises IndexError for an anchor that lies right of
+    the grid (c0 >= nx), as the reference does; the device clamps that corner to the last column, so the box is empty: area 0."""
+    from oracle import np_ops
+
+    nx, ny, B, MV = 70, 5, 3, 48
+    vs, pcr = np.array([0.5, 0.5, 4.0], np.float32), np.array([0.0, -1.25, -3.0, 35.0, 1.25, 1.0], np.float32)
+    rng = np.random.default_rng(7)
+    coors = np.stack([np.broadcast_to(np.arange(B)[:, None], (B, MV)), np.zeros((B, MV), np.int64), rng.integers(0, ny, (B, MV)),
+                      rng.integers(0, nx, (B, MV))], -1).astype(np.int32)
+    coors[0, 3, 3], coors[2, 5, 2] = nx, -1                                   # outside the grid, among the counted rows: not counted
+    coors[:, :4, 3] = [63, 64, 69, 0]                                         # both sides of the chunk boundary and both ends of a row
+    voxel_num = np.array([MV, 0, 17], np.int32)
+    bv = np.array([[-10.0, -10.0, 100.0, 100.0],                              # covers everything
+                   [-10.0, -1.0, -3.0, 1.0],                                  # entirely left of the grid: c2 < 0 wraps, as numpy's index does
+                   [3.0, -0.75, 20.25, 0.5], [30.0, -1.25, 34.25, 1.0], [31.5, 0.0, 32.5, 0.75], [0.0, -1.25, 34.75, 1.0],
+                   [40.0, -1.0, 50.0, 1.0]], np.float32)                      # entirely right of the grid (last: the oracle does not take it)
+    N = len(bv)
+    want_area, want_mask = np.zeros((B, N), np.float32), np.zeros((B, N), np.uint8)
+    for b in range(B):
+        c = coors[b, :voxel_num[b], 1:]
+        c = c[(c[:, 1] >= 0) & (c[:, 1] < ny) & (c[:, 2] >= 0) & (c[:, 2] < nx)]
+        a, k = np_ops.anchors_mask(c, (nx, ny), bv[:-1], vs, pcr, 1)
+        want_area[b, :-1], want_mask[b, :-1] = a, k
+    assert want_area[0, 0] > 20 and not want_area[1].any() and want_mask[2].any() and len(set(want_area[0])) > 4
+    at = det_ops._AnchorMaskAttrs(nx, ny, float(vs[0]), float(vs[1]), float(pcr[0]), float(pcr[1]), 1)
+    mask, area = Guarded((B, N), torch.uint8), Guarded((B, N), torch.float32)
+    _lib.call("md_pp_anchor_mask", [dev(coors), dev(voxel_num), dev(bv), mask.t, area.t], extra=at)
+    torch.cuda.synchronize()
+    assert mask.guards_intact() and area.guards_intact()
+    print("area", area.t.cpu().numpy().tolist(), "want", want_area.tolist())
+    assert np.array_equal(area.t.cpu().numpy(), want_area) and np.array_equal(mask.t.cpu().numpy(), want_mask)
+
+
 # ------------------------------------------------------------------------------------------------------------------------ the model
 def small_cloud(m, B, n, seed):
     rng = np.random.default_rng(seed)

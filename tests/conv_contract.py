@@ -1,7 +1,8 @@
 """The conv family's contract (include/minddet_hip.h) written out in plain torch: the launch-plan structs and md_conv_plan wrapper, a
-weight packer, and a float64 reference of md_conv2d / md_conv2d_head / md_conv1x1_dual that rounds to bf16 exactly where the header
-says the kernels do.  Shared by tests/test_conv_plan_cpu.py (plans), tests/test_conv_reference_cpu.py (the reference against
-F.conv2d / F.conv_transpose2d composed by hand) and tests/test_conv_production_gpu.py (every production call against the reference).
+weight packer, and a float64 reference of md_conv2d / md_conv2d_head / md_conv1x1_dual / md_conv2d_grouped that rounds to bf16 exactly
+where the header says the kernels do.  Shared by tests/test_conv_plan_cpu.py (plans), tests/test_conv_reference_cpu.py (the reference
+against F.conv2d / F.conv_transpose2d composed by hand), tests/test_conv_production_gpu.py (every production call against the reference),
+tests/neck_checks.py (an RPN neck layer by layer) and tests/test_centerpoint_conv_gpu.py (the grouped op, CenterHead and CenterPoint's neck).
 
 A call's arguments are (op, shapes, attrs): the shapes of its parameters in the op's order (None = NULL) and its attribute record as a
 dict with the field names of md_conv2d_attrs / md_conv1x1_dual_attrs -- the form tests/golden/conv_plans.json stores."""
@@ -304,6 +305,63 @@ def reference_dual(xa, xb, wl, bias, stride_b, relu, exact=True):
         return epilogue(pre, relu)
     absum = dual_sum(xa, xb, wl, stride_b, absolute=True) + bias.double().abs()
     return gaussian_bound(pre, absum, accumulation_c(wl.shape[1] + 1), relu)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# md_conv2d_grouped: G narrow convs on consecutive 64-channel slices of x, each one conv_stage
+# ---------------------------------------------------------------------------------------------------------------------------------
+def grouped_attrs(k, couts, y_offs=None, w_rows=None, relu=0, x_c_off=0):
+    """an md_conv2d_grouped_attrs record as a dict (cout / y_off / w_row as lists of G entries; default: side by side from 0)"""
+    side = [sum(couts[:g]) for g in range(len(couts))]
+    return dict(k=k, relu=int(relu), groups=len(couts), cin_g=64, x_c_off=x_c_off, reserved0=0, cout=list(couts),
+                y_off=list(side if y_offs is None else y_offs), w_row=list(side if w_rows is None else w_rows))
+
+
+def grouped_geometries(x_shape, a, y_shape=None):
+    """md_conv2d_grouped: one Geometry per group -- k x k, stride 1, pad k / 2 on channels [x_c_off + 64 g, + 64) of x, written to
+    channels [y_off[g], + cout[g]) of y (y_shape None: the narrowest y that holds every group)"""
+    n, h, w, _ = x_shape
+    k, G = a["k"], a["groups"]
+    assert a["cin_g"] == 64 and k in (1, 3)
+    if y_shape is None:
+        y_shape = (n, h, w, (max(a["y_off"][g] + a["cout"][g] for g in range(G)) + 7) // 8 * 8)
+    return [Geometry(k, k, 1, k // 2, k // 2, h, w, 1, 0, 0, a["y_off"][g], a["cout"][g], a["x_c_off"] + 64 * g, 64, tuple(y_shape))
+            for g in range(G)]
+
+
+def reference_grouped(x, wls, biases, a, y_shape, exact=True):
+    """md_conv2d_grouped's whole output: wls[g] the logical [cout_g, k, k, 64] weight of group g, biases[g] its [cout_g] bias -> the
+    float64 value of every element the call writes and NaN elsewhere, in y's [N, H, W, Cy] layout (exact-regime data); else (y, bound),
+    the bound NaN where y is.  One conv_stage per group."""
+    y = torch.full(tuple(y_shape), float("nan"), dtype=torch.float64, device=x.device)
+    bound = None if exact else torch.full_like(y, float("nan"))
+    for g, wl, b in zip(grouped_geometries(x.shape, a, y_shape), wls, biases):
+        assert tuple(wl.shape) == (g.cout, g.kh, g.kw, 64) and tuple(b.shape) == (g.cout,)
+        v, e = conv_stage(x, None if exact else 0.0, wl, b, g, a["relu"])
+        out_view(y, g)[...] = v
+        if not exact:
+            out_view(bound, g)[...] = e
+    return y if exact else (y, bound)
+
+
+def pack_grouped(wls, biases, w_rows=None, rows=None, fill=0.0):
+    """the operands of the header: w [R, k*k*64] with w[w_row[g] + c, tap * 64 + ci] = wls[g][c, ky, kx, ci] (tap = ky * k + kx), bias [R]
+    f32 and w_row.  w_rows None: the groups' rows one after the other; rows no group owns hold `fill`.  Keeps the weights' dtype."""
+    couts = [wl.shape[0] for wl in wls]
+    if w_rows is None:
+        w_rows = [sum(couts[:g]) for g in range(len(couts))]
+    R = max(r + c for r, c in zip(w_rows, couts)) if rows is None else rows
+    kk = wls[0].shape[1] * wls[0].shape[2] * 64
+    w = torch.full((R, kk), fill, dtype=wls[0].dtype, device=wls[0].device)
+    bias = torch.full((R,), fill, dtype=torch.float32, device=wls[0].device)
+    for r, wl, b in zip(w_rows, wls, biases):
+        for c in range(wl.shape[0]):
+            for ky in range(wl.shape[1]):
+                for kx in range(wl.shape[2]):
+                    t = ky * wl.shape[2] + kx
+                    w[r + c, t * 64:(t + 1) * 64] = wl[c, ky, kx]
+            bias[r + c] = b[c]
+    return w, bias, list(w_rows)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

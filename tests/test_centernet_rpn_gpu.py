@@ -1,7 +1,8 @@
 """-m gpu: the reference-present graphs -- CenterNet-R18 (neck with Conv2dTranspose 4x4 s2 p1, fused heads,
 sigmoid+clip, max-pool NMS, two-stage top-k, gather decode) and the CenterPoint RPN neck (strided conv /
 Conv2dTranspose k=s deblocks writing a channel-concatenated output) -- against the torch/numpy oracle.
-Conv stacks: bf16 fp tolerance; decode indices: bit-exact from the device head tensors."""
+Conv stacks: bf16 fp tolerance; decode indices: bit-exact from the device head tensors.
+CenterPoint's neck is held launch by launch to the float64 conv contract in tests/test_centerpoint_conv_gpu.py."""
 import numpy as np
 import pytest
 import torch

@@ -5,7 +5,8 @@ kernel, md_conv2d_grouped (csrc/grouped.hip).
 (c) the CenterHead head tensor against the torch oracle (conv_module(quant=True) per branch);
 (d) the known answer of center_head.py:490-491: [4,512,512,64] -> neck [4,128,128,384] -> shared [4,128,128,64];
 (e) the detector end to end at B = 2: decode against np_ops.centerpoint_decode away from the score threshold, then TopK order, NMS keep
-    lists, counts and the merged dets / labels / count bit-exact against the oracle and the merge rule of tools_ms/eval.py:84-111."""
+    lists, counts and the merged dets / labels / count bit-exact against the oracle and the merge rule of tools_ms/eval.py:84-111.
+The grouped op and every CenterHead launch are held to the float64 conv contract in tests/test_centerpoint_conv_gpu.py."""
 import os
 
 import numpy as np

@@ -36,13 +36,14 @@ import torch
 from minddet_amd import _lib, nn_ops
 from tests import conv_contract as cc
 from tests.conftest import has_gpu
+from tests.conv_checks import GUARD, SENTINEL, Data, sentinel_out  # noqa: F401 (GUARD: test_sampling_gpu.py takes it from here)
+from tests.conv_checks import check as _check
+from tests.conv_checks import check_guards as _check_guards
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not has_gpu(), reason="needs MI355X")]
 DEV = "cuda:0"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CALLS = json.load(open(os.path.join(ROOT, "tests", "golden", "conv_plans.json")))["calls"]
-SENTINEL = 0x7FA5          # a bf16 NaN bit pattern (as int16) that no computed value takes
-GUARD = 1 << 16            # sentinel elements on each side of the output tensor
 CHUNK_ELEMS = 1 << 27      # float64 elements per image chunk of the reference (1 GiB per tensor)
 
 
@@ -57,46 +58,11 @@ def _lib_fn(name, restype):
 
 
 def _sentinel_out(shape):
-    """(y, flat): an output tensor of `shape` filled with the sentinel, inside a sentinel buffer GUARD elements longer on each side"""
-    n = 1
-    for s in shape:
-        n *= s
-    flat = torch.full((n + 2 * GUARD,), SENTINEL, dtype=torch.int16, device=DEV)
-    return flat[GUARD:GUARD + n].view(torch.bfloat16).view(shape), flat
+    return sentinel_out(shape, DEV)
 
 
-def _check_guards(flat):
-    assert bool((flat[:GUARD] == SENTINEL).all()) and bool((flat[-GUARD:] == SENTINEL).all()), "write outside the output tensor"
-
-
-class _Data:
-    """the two regimes' value draws (on the device, from one generator per case)"""
-
-    def __init__(self, exact, seed):
-        self.exact = exact
-        self.g = torch.Generator(device=DEV).manual_seed(seed)
-
-    def act(self, shape, hi=2):
-        if self.exact:
-            return torch.randint(-hi, hi + 1, shape, generator=self.g, device=DEV, dtype=torch.int16).to(torch.bfloat16)
-        return torch.randn(shape, generator=self.g, device=DEV).to(torch.bfloat16)
-
-    def weight(self, shape, k, silu=False):
-        """logical weight, bf16 values (exact: {-1, 0, 1} 2^-s; s > 0 only for SiLU layers, to keep the pre-activation near 0)"""
-        if self.exact:
-            s = max(0, round(0.5 * torch.log2(torch.tensor(4.0 * k / 3 / 16)).item())) if silu else 0
-            w = torch.randint(-1, 2, shape, generator=self.g, device=DEV, dtype=torch.int16).float() * 2.0 ** -s
-        else:
-            w = torch.randn(shape, generator=self.g, device=DEV) / k ** 0.5
-        return w.to(torch.bfloat16)
-
-    def bias(self, n, n_pad):
-        b = torch.zeros((n_pad,), dtype=torch.float32, device=DEV)
-        if self.exact:
-            b[:n] = torch.randint(-3, 4, (n,), generator=self.g, device=DEV).float()
-        else:
-            b[:n] = torch.randn((n,), generator=self.g, device=DEV)
-        return b
+def _Data(exact, seed):
+    return Data(exact, seed, DEV)
 
 
 def _call(op, tensors, e, n_launches, kernel_id):
@@ -136,23 +102,6 @@ def _compare(got, pre, abs_sum, relu, res, c, exact):
         idx = tuple(int(v) for v in (ratio > 1).nonzero()[0])
         raise AssertionError(f"{int((ratio > 1).sum())} outputs past the bound; first at {idx}: got {got[idx].item()}, want "
                              f"{y[idx].item()} +- {bnd[idx].item()}")
-    return worst
-
-
-def _check(got, ref, exact):
-    """got against a reference: exact -> float64 bf16 values, bit for bit; else (y, bound) -> worst err / bound"""
-    if exact:
-        want = ref.to(torch.bfloat16).view(torch.int16)
-        bad = got.contiguous().view(torch.int16) != want
-        nbad = int(bad.sum())
-        assert not nbad, f"{nbad} of {bad.numel()} outputs differ; first at {tuple(int(v) for v in bad.nonzero()[0])}"
-        return 0.0
-    y, bnd = ref
-    err = (got.double() - y).abs()
-    assert bool(torch.isfinite(err).all()), "non-finite output"
-    ratio = err / bnd
-    worst = float(ratio.max())
-    assert worst <= 1, f"{int((ratio > 1).sum())} outputs past the bound; first at {tuple(int(v) for v in (ratio > 1).nonzero()[0])}"
     return worst
 
 

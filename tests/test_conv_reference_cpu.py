@@ -250,3 +250,111 @@ def test_gaussian_chain_bound_holds_for_an_fp32_bottleneck():
     y = F.relu(rnd(rnd(f(t2, w3[:, None, None, :]) + b3) + x.repeat(1, 1, 1, 4)))
     want, bound = cc.reference_bottleneck(x, w1, b1, w2, b2, w3, b3, x.repeat(1, 1, 1, 4), exact=False)
     assert ((y - want).abs() <= bound).all()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# md_conv2d_grouped: the reference and the packer of conv_contract, and how much the contract's two regimes see
+# ---------------------------------------------------------------------------------------------------------------------------------
+def torch_grouped(x, wls, biases, k, x_c_off):
+    """float64 F.conv2d(groups=G) on the groups' slices of NHWC x, every group's weight padded to 16 rows -> per group [n, H, W, cout_g]"""
+    G = len(wls)
+    wf, bf = torch.zeros((16 * G, 64, k, k), dtype=torch.float64), torch.zeros((16 * G,), dtype=torch.float64)
+    for g, (wl, b) in enumerate(zip(wls, biases)):
+        wf[16 * g:16 * g + wl.shape[0]] = wl.permute(0, 3, 1, 2)
+        bf[16 * g:16 * g + wl.shape[0]] = b
+    y = nhwc(F.conv2d(nchw(x[..., x_c_off:x_c_off + 64 * G]), wf, bf, padding=k // 2, groups=G))
+    return [y[..., 16 * g:16 * g + wl.shape[0]] for g, wl in enumerate(wls)]
+
+
+@pytest.mark.parametrize("k", [1, 3])
+def test_grouped_reference_against_torch(k):
+    """x_c_off != 0 on a tensor with trailing channels, out-of-order y_off with gaps, every written element and only those"""
+    couts, y_offs, cy = [3, 1, 2, 16, 5], [40, 3, 37, 8, 27], 48
+    x = ints((2, 7, 9, 8 + 320 + 16), 2, 60)
+    wls = [ints((c, k, k, 64), 1, 61 + g) for g, c in enumerate(couts)]
+    biases = [ints((c,), 3, 70 + g) for g, c in enumerate(couts)]
+    for relu in (0, 1):
+        a = cc.grouped_attrs(k, couts, y_offs, relu=relu, x_c_off=8)
+        geos = cc.grouped_geometries(x.shape, a, (2, 7, 9, cy))
+        assert [(g.x_c_off, g.c_off, g.cout, g.cin, g.k) for g in geos] == [(8 + 64 * i, y_offs[i], couts[i], 64, 64 * k * k) for i in range(5)]
+        y = cc.reference_grouped(x, wls, biases, a, (2, 7, 9, cy))
+        written = torch.zeros(cy, dtype=torch.bool)
+        for g, want in enumerate(torch_grouped(x, wls, biases, k, 8)):
+            written[y_offs[g]:y_offs[g] + couts[g]] = True
+            assert torch.equal(y[..., y_offs[g]:y_offs[g] + couts[g]], rnd(F.relu(want) if relu else want)), (relu, g)
+        assert y[..., ~written].isnan().all() and not y[..., written].isnan().any()
+        # the Gaussian-regime form: the same values before the rounding, a bound on exactly the written elements
+        v, bound = cc.reference_grouped(x, wls, biases, a, (2, 7, 9, cy), exact=False)
+        assert torch.equal(v.isnan(), y.isnan()) and torch.equal(bound.isnan(), y.isnan()) and bool((bound[..., written] > 0).all())
+        assert torch.equal(rnd(v[..., written]), y[..., written])
+
+
+def test_grouped_packers_agree():
+    """conv_contract.pack_grouped, written from the header, and nn_ops.pack_conv2d_grouped give one operand for BN-free convs"""
+    from minddet_amd import nn_ops
+
+    for k in (1, 3):
+        couts = [2, 16, 1, 3]
+        wls = [ints((c, k, k, 64), 1, 80 + g) for g, c in enumerate(couts)]
+        biases = [ints((c,), 3, 90 + g) for g, c in enumerate(couts)]
+        w, b, rows = cc.pack_grouped([wl.to(BF) for wl in wls], biases)
+        pk = nn_ops.pack_conv2d_grouped([(wl.permute(0, 3, 1, 2).float(), bb.float(), None) for wl, bb in zip(wls, biases)])
+        assert rows == pk.w_rows == [0, 2, 18, 19] and pk.couts == couts and pk.k == k
+        assert w.dtype == pk.w.dtype == BF and torch.equal(w, pk.w) and b.dtype == pk.bias.dtype and torch.equal(b, pk.bias)
+        # element (row, K) of the header, and rows of one's own choosing
+        assert w[2 + 7, (k * k - 1) * 64 + 5] == wls[1][7, k - 1, k - 1, 5] and w[19 + 2, (k // 2 * k) * 64 + 63] == wls[3][2, k // 2, 0, 63]
+        w2, b2, rows2 = cc.pack_grouped(wls, biases, w_rows=[20, 0, 19, 16], rows=24, fill=7.0)
+        assert rows2 == [20, 0, 19, 16] and torch.equal(w2[0:16], w[2:18].double()) and torch.equal(w2[20:22], w[0:2].double())
+        assert bool((w2[22:] == 7).all()) and bool((b2[22:] == 7).all()) and torch.equal(b2[16:19], b[19:22])
+
+
+def _simulated_kernel(x, wls, biases, a, y_shape, defect=None):
+    """md_conv2d_grouped as a correct kernel computes it -- fp32 F.conv2d per group, bias, ReLU, one rounding to bf16 -- into a
+    NaN-filled y; defect: 'swap' two input channels within every group, 'tap' drop one tap, 'column' zero image column 32 of x"""
+    y = torch.full(y_shape, float("nan"), dtype=BF)
+    k = a["k"]
+    xf = x.float()
+    if defect == "column":
+        xf = xf.clone()
+        xf[:, :, 32] = 0
+    for g, (wl, b) in enumerate(zip(wls, biases)):
+        c0 = a["x_c_off"] + 64 * g
+        xs = xf[..., c0:c0 + 64]
+        w = wl.float()
+        if defect == "swap":
+            xs = xs[..., [0, 1, 2, 3, 4, 9, 6, 7, 8, 5] + list(range(10, 64))]
+        if defect == "tap":
+            w = w.clone()
+            w[:, 0, k - 1] = 0
+        v = nhwc(F.conv2d(nchw(xs), w.permute(0, 3, 1, 2), b.float(), padding=k // 2))
+        y[..., a["y_off"][g]:a["y_off"][g] + a["cout"][g]] = (F.relu(v) if a["relu"] else v).to(BF)
+    return y
+
+
+def test_grouped_contract_passes_a_correct_kernel_and_sees_three_defects():
+    """On the draws the GPU test makes (conv_checks.grouped_operands of the ragged case, on the CPU generator): an fp32 computation with
+    one bf16 rounding is bit-equal to the reference in the exact regime and within the bound everywhere in the Gaussian regime; two
+    swapped input channels, a dropped tap and a zeroed image column at the tile boundary each break both."""
+    from tests.conv_checks import grouped_operands
+
+    for exact in (True, False):
+        x, wls, biases, a, y_shape = grouped_operands("ragged", exact, "cpu")
+        ref = cc.reference_grouped(x, wls, biases, a, y_shape, exact=exact)
+        y, bound = (ref, None) if exact else ref
+        written = ~y.isnan()
+
+        def wrong(defect):
+            """fraction of the written elements that miss the contract"""
+            got = _simulated_kernel(x, wls, biases, a, y_shape, defect).double()
+            assert torch.equal(got.isnan(), ~written)
+            bad = got[written] != y[written] if exact else (got[written] - y[written]).abs() > bound[written]
+            return float(bad.double().mean())
+
+        assert wrong(None) == 0.0, exact
+        for defect, least in (("swap", 0.5), ("tap", 0.5), ("column", 0.02)):
+            f = wrong(defect)
+            print(f"exact={exact} {defect}: {100 * f:.1f} % of the elements miss the contract")
+            assert f >= least, (exact, defect, f)
+        if not exact:
+            got = _simulated_kernel(x, wls, biases, a, y_shape).double()
+            print(f"correct kernel, Gaussian regime: worst err / bound {float(((got[written] - y[written]).abs() / bound[written]).max()):.3f}")

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from tests import conv_contract as cc
+from tests import neck_checks
 from tests import pp_contract as ppc
 from tests.abi_cases_pp import CASES
 from tests.conftest import has_gpu
@@ -283,70 +284,24 @@ def test_tiny_detector_end_to_end():
 
 
 def _logical(m):
-    """(folded weights as the kernel holds them: bf16 values, [cout, kh, kw, cin] float64; fp32 bias) of a ConvModule"""
-    from minddet_amd import nn_ops
-
-    w, b = nn_ops._fold_bn(m.weight, m.bias, m.bn)
-    return w.to(torch.bfloat16).double().permute(0, 2, 3, 1).to(DEV), b.to(DEV)
+    return neck_checks.logical(m, DEV)
 
 
 def _neck_and_head_reference(m, x):
-    """The RPN of pointpillars.py:367-621 and the three 1x1 heads restated layer by layer in float64 on the folded bf16 weights, each
-    layer through conv_contract.conv_stage, in two ways at once:
-    * the chain: the exact value of the whole net and conv_contract's accumulated bound (fp32 accumulation, one bf16 rounding per
-      layer, carried through the following layers' |w|).  Through sixteen randomly initialised layers that worst-case bound grows by
-      the layers' sum |w| each time and ends far above the values; it is asserted because it is the bound that holds, and printed.
-    * layer by layer from the DEVICE's own input of each layer (the module run alone: the launch forward() makes): the bound of one
-      conv on exact inputs, which is what pins each kernel launch.
+    """The RPN of pointpillars.py:367-621 (tests/neck_checks.py: every launch held to conv_contract.conv_stage on the device's own input,
+    and the float64 chain with its accumulated bound.  Through sixteen randomly initialised layers that worst-case bound grows by the
+    layers' sum |w| each time and ends far above the values; it is asserted because it is the bound that holds, and printed) and
+    the three 1x1 heads restated the same way.
     -> (device neck output rebuilt from the single launches, (chain value, chain bound) of the neck, of the head, worst single-layer
     err / bound)"""
-    from minddet_amd import graphs, nn_ops
-
-    worst = 0.0
-
-    def stage(t, e, td, wl, b, geo, relu, yd):
-        nonlocal worst
-        want, bound = cc.conv_stage(td.double(), 0.0, wl, b, geo, relu)             # this launch alone, on the device's input
-        r = float(((yd.double() - want).abs() / bound).max())
-        worst = max(worst, r)
-        assert r <= 1.0, (geo, r)
-        return cc.conv_stage(t, e, wl, b, geo, relu)
-
-    ups, ups_d = [], []
-    t, e, td = x.double(), 0.0, x
-    for i, blk in enumerate(m.neck.blocks):
-        for cm in blk:
-            wl, b = _logical(cm)
-            n, h, w, _ = t.shape
-            yd = cm(td)
-            t, e = stage(t, e, td, wl, b, cc._plain(n, h, w, cm.cin, 3, cm.stride, 1, cm.cout), 1, yd)
-            td = yd
-        d = m.neck.deblocks[i]
-        n, h, w, _ = t.shape
-        ud = d(td)
-        if isinstance(d, graphs.DeconvModule):
-            s = d.stride
-            wf, b = nn_ops._fold_bn(d.weight_t.permute(1, 0, 2, 3), None, d.bn)                     # [cout, cin, k, k]
-            wf = wf.to(torch.bfloat16).double().to(DEV)
-            u = torch.zeros((n, h * s, w * s, d.cout), dtype=torch.float64, device=DEV)
-            ue = torch.zeros_like(u)
-            for py in range(s):
-                for px in range(s):
-                    u[:, py::s, px::s], ue[:, py::s, px::s] = stage(t, e, td, wf[:, :, py, px][:, None, None, :], b.to(DEV),
-                                                                    cc._plain(n, h, w, d.cin, 1, 1, 0, d.cout), 1, ud[:, py::s, px::s])
-        else:
-            wl, b = _logical(d)
-            u, ue = stage(t, e, td, wl, b, cc._plain(n, h, w, d.cin, 1, 1, 0, d.cout), 1, ud)
-        ups.append((u, ue))
-        ups_d.append(ud)
-    feat, fe = torch.cat([u for u, _ in ups], 3), torch.cat([ue for _, ue in ups], 3)
-    feat_d = torch.cat(ups_d, 3)
+    stage = neck_checks.Stages()
+    feat_d, (feat, fe) = neck_checks.neck_reference(m.neck, x, stage)
     heads = []
     for cm in m.bbox_head.children():
         wl, b = _logical(cm)
         n, h, w, c = feat.shape
         heads.append(stage(feat, fe, feat_d, wl, b, cc._plain(n, h, w, c, 1, 1, 0, cm.cout), 0, cm(feat_d)[..., :cm.cout]))
-    return feat_d, (feat, fe), (torch.cat([v for v, _ in heads], 3), torch.cat([b for _, b in heads], 3)), worst
+    return feat_d, (feat, fe), (torch.cat([v for v, _ in heads], 3), torch.cat([b for _, b in heads], 3)), stage.worst
 
 
 def _check_net(tag, m, x, aux):

@@ -13,6 +13,7 @@
 
 #include "aot.h"
 #include "device.h"
+#include "image_sample.h"
 
 namespace md {
 
@@ -34,33 +35,11 @@ __global__ __launch_bounds__(256) void image_preprocess_kernel(PreArgs a, size_t
         float v[3] = {0.f, 0.f, 0.f};
         const bool inside = (unsigned)x < (unsigned)a.Wo && (unsigned)y < (unsigned)a.Ho;
         if (inside) {
-            const float *m = a.mat + (size_t)n * 6;
-            const float sx = m[0] * (float)x + m[1] * (float)y + m[2];
-            const float sy = m[3] * (float)x + m[4] * (float)y + m[5];
-            // a source position outside (-1, Ws) x (-1, Hs) touches no pixel: huge, infinite and NaN positions stop here, before
-            // the conversion to int (undefined for them), and read as the border value
-            if (sx > -1.f && sx < (float)a.Ws && sy > -1.f && sy < (float)a.Hs) {
-                const float xf = floorf(sx), yf = floorf(sy);
-                const int x0 = (int)xf, y0 = (int)yf;
-                const float lx = sx - xf, ly = sy - yf;
-                const uint8_t *base = a.img + (size_t)n * a.Hs * a.Ws * 3;
+            sample_bilinear(a.img + (size_t)n * a.Hs * a.Ws * 3, a.Ws, a.Hs, a.Ws, a.mat + (size_t)n * 6, x, y, v);
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int yy = y0 + (q >> 1), xx = x0 + (q & 1);
-                    const float w = ((q >> 1) ? ly : 1.f - ly) * ((q & 1) ? lx : 1.f - lx);
-                    if ((unsigned)yy < (unsigned)a.Hs && (unsigned)xx < (unsigned)a.Ws) {  // BORDER_CONSTANT, value 0
-                        const uint8_t *p = base + ((size_t)yy * a.Ws + xx) * 3;
-                        v[0] += w * (float)p[0]; v[1] += w * (float)p[1]; v[2] += w * (float)p[2];
-                    }
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < 3; ++c) v[c] = (v[c] * (1.0f / 255.0f) - a.norm[c]) / a.norm[3 + c];
+            for (int c = 0; c < 3; ++c) v[c] = normalised_level(v[c], a.norm, c);
         }
-        uint16_t *dst = a.out + e * a.C;
-        const uint2 lo = make_uint2(pk_bf16(v[0], v[1]), pk_bf16(v[2], 0.f));
-        *reinterpret_cast<uint2 *>(dst) = lo;
-        if (a.C == 8) *reinterpret_cast<uint2 *>(dst + 4) = make_uint2(0u, 0u);
+        store_pixel(a.out + e * a.C, v, a.C);
     }
 }
 

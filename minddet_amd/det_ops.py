@@ -25,6 +25,9 @@ read the same (paths relative to /root/reference/minddet/models):
   cn_loss, CenterNetLoss, center_net_loss
                           centernet/src/centernet_det.py:177-237 (CenterNetLossCell.construct behind the network) with
                           centernet/src/utils.py:132-245 (Sigmoid, FocalLoss, RegLoss)
+  cn_aug_transform, cn_aug_image, CenterNetAugment
+                          centernet/src/dataset.py:278-315 (the training branch of COCOHP.preprocess_fn in front of the targets)
+                          with centernet/src/image.py:25-57,208-253 (get_affine_transform, color_aug)
 
 All tensors are torch CUDA tensors; work is enqueued on the current stream; nothing here
 synchronises.  There is no CPU path.
@@ -2094,3 +2097,190 @@ def center_net_loss(head, targets, loss):
     """differentiable form: -> (total [1] f32, parts [3], num_pos [1]); the forward runs md_cn_loss_grad once, the backward returns
     grad_output x (d total / d head) in the head's dtype.  parts and num_pos carry no gradient."""
     return _HeadLossFn.apply(head, lambda h: cn_loss(h, targets, loss.at, grad=True))
+
+
+# ----------------------------------------------------------------------------- CenterNet training input (csrc/cnaug.hip)
+CNAUG_MAX_BATCH = 65535       # MD_CNAUG_MAX_BATCH
+CNAUG_GREY_CHUNK = 2048       # MD_CNAUG_GREY_CHUNK: output pixels per partial sum of the grey pass (the workspace formula)
+CN_COLOUR_ORDERS = ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0))   # 0 brightness_, 1 contrast_, 2 saturation_
+
+
+class _CNAugTransformAttrs(ctypes.Structure):
+    _fields_ = [("rand_crop", ctypes.c_int32), ("scale", ctypes.c_double), ("shift", ctypes.c_double), ("flip_prop", ctypes.c_double),
+                ("in_h", ctypes.c_int32), ("in_w", ctypes.c_int32), ("down_ratio", ctypes.c_int32)]
+
+
+class _CNAugImageAttrs(ctypes.Structure):
+    _fields_ = [("out_h", ctypes.c_int32), ("out_w", ctypes.c_int32), ("pad_lo", ctypes.c_int32), ("pad_hi", ctypes.c_int32)]
+
+
+def _sizes2(who, sizes, dev):
+    s = _i32c(sizes, dev)
+    if s.dim() != 2 or s.shape[1] != 2:
+        raise ValueError(f"{who}: sizes are [B, 2] (h, w), got {tuple(s.shape)}")
+    return s
+
+
+def cn_aug_transform(sizes, draws, *, rand_crop, scale, shift, flip_prop, input_hw, down_ratio):
+    """The random block of COCOHP.preprocess_fn and its two matrices (md_cn_aug_transform, include/minddet_hip_cnaug.h): sizes [B,2]
+    (h, w) of the source images, draws [B,4] f64 (the values the reference drew, in its order) -> (mat_in [B,6] f32, the matrix
+    nn_ops.image_preprocess / cn_aug_image take, for the stored unflipped image with the flip folded in; trans_out [B,6] f64, the
+    `trans_output` CenterNetTargets takes; flip_width [B] i32, w where the sample is flipped, else 0)."""
+    dev = draws.device
+    s, d = _sizes2("cn_aug_transform", sizes, dev), _f64c(draws, dev)
+    B = s.shape[0]
+    if d.dim() != 2 or d.shape != (B, 4):
+        raise ValueError(f"cn_aug_transform: draws are [B, 4] float64, got {tuple(d.shape)} for B = {B}")
+    at = _CNAugTransformAttrs(int(bool(rand_crop)), float(scale), float(shift), float(flip_prop), int(input_hw[0]), int(input_hw[1]), int(down_ratio))
+    mat_in = torch.empty((B, 6), dtype=torch.float32, device=dev)
+    trans_out = torch.empty((B, 6), dtype=torch.float64, device=dev)
+    flip_width = torch.empty((B,), dtype=torch.int32, device=dev)
+    _lib.call("md_cn_aug_transform", [s, d, mat_in, trans_out, flip_width], extra=at)
+    return mat_in, trans_out, flip_width
+
+
+def cn_aug_image_workspace_bytes(B, out_h, out_w):
+    """bytes of scratch md_cn_aug_image takes with colour augmentation (include/minddet_hip_cnaug.h)"""
+    return 8 * B * ((out_h * out_w + CNAUG_GREY_CHUNK - 1) // CNAUG_GREY_CHUNK + 1)
+
+
+def cn_aug_image(img_u8, sizes, mat_in, mean, std, out_hw, colour=None, stem_layout=True, workspace=True, out=None):
+    """cv2.warpAffine + / 255 + color_aug + (inp - mean) / std + the layout on the device (md_cn_aug_image): img_u8 [B,Hs,Ws,3] uint8
+    BGR samples padded to a common extent, sizes [B,2] (h, w) of each, mat_in [B,6] f32, colour [B,8] f64 (three alphas, three
+    lighting terms, the order index 0..5 of CN_COLOUR_ORDERS, one spare) or None -> the bf16 network input in the layout of
+    nn_ops.image_preprocess (stem_layout: the zero-bordered 4-channel layout, else [B,out_h,out_w,8]).  colour None: the same bits as
+    nn_ops.image_preprocess.  workspace=False leaves the scratch to the library's per-stream pool."""
+    from .nn_ops import STEM_PAD_HI, STEM_PAD_LO
+
+    dev, B = img_u8.device, img_u8.shape[0]
+    ho, wo = (int(v) for v in out_hw)
+    lo, hi, c = (STEM_PAD_LO, STEM_PAD_HI, 4) if stem_layout else (0, 0, 8)
+    shape = (B, ho + lo + hi, wo + lo + hi, c)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.bfloat16, device=dev)
+    elif tuple(out.shape) != shape or out.dtype != torch.bfloat16:
+        raise ValueError(f"cn_aug_image: out is {shape} bfloat16")
+    norm = torch.tensor([float(v) for v in mean] + [float(v) for v in std], dtype=torch.float32, device=dev)
+    ops = [img_u8, _sizes2("cn_aug_image", sizes, dev), _f32c(mat_in), norm, None if colour is None else _f64c(colour, dev), out]
+    if workspace and colour is not None:
+        ops.append(torch.empty((max(cn_aug_image_workspace_bytes(B, ho, wo), 16),), dtype=torch.uint8, device=dev))
+    _lib.call("md_cn_aug_image", ops, extra=_CNAugImageAttrs(ho, wo, lo, hi))
+    return out
+
+
+class CenterNetAugment:
+    """The training branch of COCOHP.preprocess_fn in front of the targets (centernet/src/dataset.py:278-315, color_aug of
+    centernet/src/image.py:208-253) on the device, built from the reference's dataset_config keys: rand_crop, scale, shift, flip_prop,
+    color_aug, eig_val, eig_vec, mean, std, plus input_hw (input_res_train), down_ratio and stem_layout (None: the stem's 4-channel
+    layout where nn_ops.stem_layout_ok(input_hw), else [B,H,W,8]).  color_aug's constants are the reference's
+    (image.py:252-253: the three alphas 1 + U(-0.4, 0.4), the lighting alpha N(0, 0.1)).
+
+    draw() makes the random values with the reference's distributions from torch's generator, NOT from numpy's and Python's random
+    streams: the reference's distributions, not its sequence.
+
+    Not built, a true / non-zero value raises ValueError: a rotation (rot, aug_rot, rotate), keep_res, and a down_ratio that differs
+    between the two axes."""
+
+    _ZERO_ONLY = ("rot", "aug_rot", "rotate", "keep_res")
+
+    def __init__(self, input_hw=(512, 512), down_ratio=4, rand_crop=True, scale=0.4, shift=0.1, flip_prop=0.5, color_aug=True,
+                 eig_val=(0.2141788, 0.01817699, 0.00341571),
+                 eig_vec=((-0.58752847, -0.69563484, 0.41340352), (-0.5832747, 0.00994535, -0.81221408), (-0.56089297, 0.71832671, 0.41158938)),
+                 mean=(0.40789654, 0.44719302, 0.47026115), std=(0.28863828, 0.27408164, 0.27809835), stem_layout=None, **options):
+        for k, v in options.items():
+            if k not in self._ZERO_ONLY:
+                raise ValueError(f"CenterNetAugment: unknown option {k!r}")
+            if v not in (None, False, 0, 0.0):
+                raise ValueError(f"CenterNetAugment: {k} is not built")
+        if isinstance(down_ratio, (list, tuple)):
+            if len(set(int(v) for v in down_ratio)) != 1:
+                raise ValueError("CenterNetAugment: a down_ratio that differs between the axes is not built")
+            down_ratio = down_ratio[0]
+        self.input_hw, self.down_ratio = (int(input_hw[0]), int(input_hw[1])), int(down_ratio)
+        if min(self.input_hw) < self.down_ratio or self.down_ratio < 1:
+            raise ValueError("CenterNetAugment: input_hw >= down_ratio >= 1")
+        if stem_layout is None:            # the one-launch stem's layout wherever the input extent admits it (nn_ops.stem_layout_ok)
+            from .nn_ops import stem_layout_ok
+            stem_layout = stem_layout_ok(*self.input_hw)
+        self.rand_crop, self.color_aug, self.stem_layout = bool(rand_crop), bool(color_aug), bool(stem_layout)
+        self.scale, self.shift, self.flip_prop = float(scale), float(shift), float(flip_prop)
+        if not 0.0 <= self.flip_prop <= 1.0:
+            raise ValueError("CenterNetAugment: flip_prop in [0, 1]")
+        # the reference holds the four arrays in fp32 (default_config.yaml:88-93)
+        self.eig_val = np.asarray(eig_val, np.float32).astype(np.float64)
+        self.eig_vec = np.asarray(eig_vec, np.float32).astype(np.float64)
+        self.mean, self.std = tuple(np.asarray(mean, np.float32).tolist()), tuple(np.asarray(std, np.float32).tolist())
+        if self.eig_val.shape != (3,) or self.eig_vec.shape != (3, 3) or len(self.mean) != 3 or len(self.std) != 3:
+            raise ValueError("CenterNetAugment: eig_val, mean, std have 3 values, eig_vec 3 x 3")
+
+    @classmethod
+    def from_config(cls, cfg):
+        """cfg.train_cfg["augment"] (the reference's keys) on the input of cfg.train_cfg["assigner"] (input_res, down_ratio)"""
+        a = cfg.train_cfg["assigner"]
+        return cls(a["input_res"], a["down_ratio"], **dict(cfg.train_cfg["augment"]))
+
+    @staticmethod
+    def get_border(border, size):
+        """COCOHP._get_border (dataset.py:207-211) as tensor arithmetic: border // i for the first i = 1, 2, 4, ... with
+        size - border // i > border // i"""
+        out, found = torch.zeros_like(size), torch.zeros_like(size, dtype=torch.bool)
+        i = 1
+        while True:
+            b = border // i
+            ok = (size - b > b) & ~found
+            out = torch.where(ok, torch.full_like(size, b), out)
+            found = found | ok
+            if b == 0:
+                return out
+            i *= 2
+
+    def draw(self, sizes, generator=None):
+        """sizes [B,2] (h, w) on the device -> (draws [B,4] f64, colour [B,8] f64 or None without color_aug), the operands of
+        cn_aug_transform / cn_aug_image, with the reference's distributions.  rand_crop: np.random.choice(np.arange(0.6, 1.4, 0.1)) as
+        element i of that array with i uniform in 0..7, np.random.randint(border, size - border) per axis with _get_border(128, size); else three
+        standard normals; the flip's uniform; colour: 1 + U(-0.4, 0.4) three times, eig_vec . (eig_val * N(0, 0.1)^3), the order uniform
+        over the six permutations.  Nothing is read back."""
+        s = sizes if generator is None else sizes.to(generator.device)
+        dev, B = s.device, s.shape[0]
+        f64 = dict(dtype=torch.float64, device=dev, generator=generator)
+        draws = torch.empty((B, 4), dtype=torch.float64, device=dev)
+        if self.rand_crop:
+            table = torch.as_tensor(np.arange(0.6, 1.4, 0.1), device=dev)      # np.arange's own eight values
+            draws[:, 0] = table[torch.floor(torch.rand((B,), **f64) * 8).clamp_(max=7).long()]
+            for col, k in ((1, 1), (2, 0)):             # c[0] along the width, c[1] along the height
+                size = s[:, k].to(torch.int64)
+                lo = self.get_border(128, size)
+                span = (size - 2 * lo).clamp(min=1).to(torch.float64)
+                off = torch.minimum(torch.floor(torch.rand((B,), **f64) * span), span - 1)
+                draws[:, col] = lo.to(torch.float64) + off
+        else:
+            draws[:, :3] = torch.randn((B, 3), **f64)
+        draws[:, 3] = torch.rand((B,), **f64)
+        if not self.color_aug:
+            return draws, None
+        colour = torch.zeros((B, 8), dtype=torch.float64, device=dev)
+        colour[:, :3] = 1.0 + (torch.rand((B, 3), **f64) * 0.8 - 0.4)
+        alpha = torch.randn((B, 3), **f64) * 0.1
+        val = torch.as_tensor(self.eig_val, device=dev)
+        vec = torch.as_tensor(self.eig_vec, device=dev)
+        colour[:, 3:6] = (alpha * val) @ vec.T
+        colour[:, 6] = torch.floor(torch.rand((B,), **f64) * 6).clamp_(max=5)
+        return draws, colour
+
+    def __call__(self, images_u8, sizes, draws=None, colour=None, generator=None):
+        """images_u8 [B,Hs,Ws,3] uint8 BGR on the device (padded to a common extent), sizes [B,2] (h, w); draws / colour: the pair of
+        draw() (None: drawn here with `generator`; color_aug False: no colour is applied) -> (input: the bf16 network input, trans_out
+        [B,6] f64, flip_width [B] i32), nothing read back."""
+        dev = images_u8.device
+        s = _sizes2("CenterNetAugment", sizes, dev)
+        if draws is None:
+            draws, drawn = self.draw(s, generator)
+            colour = drawn if colour is None else colour
+        if not self.color_aug:
+            colour = None
+        elif colour is None:
+            colour = self.draw(s, generator)[1]
+        mat_in, trans_out, flip_width = cn_aug_transform(s, draws.to(dev), rand_crop=self.rand_crop, scale=self.scale, shift=self.shift,
+                                                         flip_prop=self.flip_prop, input_hw=self.input_hw, down_ratio=self.down_ratio)
+        inp = cn_aug_image(images_u8, s, mat_in, self.mean, self.std, self.input_hw, colour=colour, stem_layout=self.stem_layout)
+        return inp, trans_out, flip_width

@@ -730,7 +730,7 @@ class CenterNet(Module):
         self.head2 = ConvModule(init, 3 * hc, self.n_out, 1, bn=False, relu=False, bias=True)
         self.fuse_heads()
         self.decode = det_ops.DetectionDecode(reg_offset=True, K=K)
-        self.train_cfg, self._loss = train_cfg, None
+        self.train_cfg, self._loss, self._augment, self._targets = train_cfg, None, None, None
 
     def fuse_heads(self):
         """(Re)build the fused head convs' weights from self.heads (to() calls it: they are packed like any other conv)."""
@@ -787,6 +787,43 @@ class CenterNet(Module):
         form is det_ops.center_net_loss(head, example, self.loss_op())."""
         head = self.features(images)
         return dict(self.loss_op()(head, example, grad=grad), head=head)
+
+    def _train_cfg(self, key):
+        if not self.train_cfg or key not in self.train_cfg:
+            raise ValueError(f"CenterNet: train_cfg[{key!r}] is needed for training (see configs/centernet/centernet_r18_dcn_train.py)")
+        return self.train_cfg[key]
+
+    def augment_op(self):
+        """det_ops.CenterNetAugment with train_cfg["augment"] on the input of train_cfg["assigner"], in the stem's input layout"""
+        if self._augment is None:
+            a = self._train_cfg("assigner")
+            self._augment = det_ops.CenterNetAugment(a["input_res"], a["down_ratio"], **dict(self._train_cfg("augment")))
+        return self._augment
+
+    def targets_op(self):
+        """det_ops.CenterNetTargets with train_cfg["assigner"] for this model's classes"""
+        if self._targets is None:
+            a = self._train_cfg("assigner")
+            h, w = (int(v) for v in a["input_res"])
+            d = int(a["down_ratio"])
+            self._targets = det_ops.CenterNetTargets(self.num_classes, (w // d, h // d), a["max_objs"], a.get("min_overlap", 0.7))
+        return self._targets
+
+    def train_example(self, images_u8, sizes, bboxes, category_id, generator=None, draws=None, colour=None):
+        """Raw images and ground truth -> (input, example) of loss(), on the device with nothing read back: the training branch of
+        COCOHP.preprocess_fn (det_ops.CenterNetAugment: images_u8 [B,Hs,Ws,3] uint8 BGR padded to a common extent, sizes [B,2] (h, w);
+        draws / colour = the pair of its draw(), None: drawn with `generator`), then the target step (det_ops.CenterNetTargets) on
+        bboxes [B,G,4] original-image boxes and category_id [B,G], fed the augmentation's trans_out and flip_width as device tensors.
+        -> (the bf16 network input, the dict of det_ops.cn_assign_targets plus trans_out and flip_width)."""
+        inp, trans_out, flip_width = self.augment_op()(images_u8, sizes, draws=draws, colour=colour, generator=generator)
+        example = self.targets_op()(bboxes, category_id, trans=trans_out, flip_width=flip_width)
+        return inp, dict(example, trans_out=trans_out, flip_width=flip_width)
+
+    def train_loss(self, images_u8, sizes, bboxes, category_id, generator=None, draws=None, colour=None, grad=False):
+        """train_example, then loss() on the augmented input: raw images + ground truth -> loss (and, grad=True, d total / d head) as
+        one device chain.  -> the dict of loss() plus `example`."""
+        inp, ex = self.train_example(images_u8, sizes, bboxes, category_id, generator=generator, draws=draws, colour=colour)
+        return dict(self.loss(inp, ex, grad=grad), example=ex)
 
 
 # ----------------------------------------------------------------------------- CenterPoint RPN neck

@@ -92,6 +92,15 @@ struct Args {
 #define MD_ARGS nparam, params, ndims, shapes, dtypes
 
 static inline bool fits_i32(long long x) { return x <= 0x7fffffffLL; }
+// an output that shares its address with an input or with another output (operands [0, n_in) are inputs, [n_in, n_all) outputs)
+static inline bool aliased(void **params, int n_in, int n_all) {
+    for (int o = n_in; o < n_all; ++o) {
+        if (!params[o]) continue;
+        for (int k = 0; k < o; ++k)
+            if (params[k] == params[o]) return true;
+    }
+    return false;
+}
 // the one launch epilogue: the launches of the call were accepted by the runtime
 static inline int launched() { return hipGetLastError() == hipSuccess ? MD_OK : MD_ERR_HIP; }
 // grid of a 1-D grid-stride kernel over `total` elements, 256 per workgroup, at most `cap` workgroups

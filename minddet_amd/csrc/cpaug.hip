@@ -379,16 +379,6 @@ __global__ __launch_bounds__(64) void cp_boxes_kernel(BoxArgs a) {
     if (lane == 0) a.out_count[b] = base;
 }
 
-// an output that shares its address with an input or with another output (operands [0, n_in) are inputs, [n_in, n_all) outputs)
-static bool aliased(void **params, int n_in, int n_all) {
-    for (int o = n_in; o < n_all; ++o) {
-        if (!params[o]) continue;
-        for (int k = 0; k < o; ++k)
-            if (params[k] == params[o]) return true;
-    }
-    return false;
-}
-
 }  // namespace md
 
 using namespace md;

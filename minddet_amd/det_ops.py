@@ -1650,6 +1650,224 @@ class CenterPointAugment:
                     **{"global": glob})
 
 
+# ----------------------------------------------------------------------------- CenterPoint multi-sweep input (csrc/cpsweeps.hip)
+CPSWEEPS_MAX_SWEEPS, CPSWEEPS_MAX_BATCH = 32, 256     # MD_CPSWEEPS_MAX_SWEEPS, MD_CPSWEEPS_MAX_BATCH
+SWEEP_REMOVE_CLOSE, SWEEP_TRANSFORM = 1, 2            # the bits of seg_flags
+
+
+class _CPSweepsAttrs(ctypes.Structure):
+    _fields_ = [("radius", ctypes.c_float), ("reserved0", ctypes.c_int32)]
+
+
+def cp_sweeps_merge_workspace_bytes(N, B, S):
+    """bytes of scratch md_cp_sweeps_merge takes (include/minddet_hip_cpsweeps.h)"""
+    return 4 * (N // 256 + B * S + 3)
+
+
+def cp_sweeps_merge(points, seg_range, transforms, time_lag, seg_flags, radius=1.0, workspace=True, out=None):
+    """read_sweep per segment and the concatenation of the nuScenes loader (md_cp_sweeps_merge, include/minddet_hip_cpsweeps.h):
+    points [N,4 or 5] f32, one pool of rows; seg_range [B,S,2] i32 (begin, end) in output order; transforms [B,S,12] f64 (rows 0-2 of
+    the 4x4); time_lag [B,S] f64; seg_flags [B,S] i32 (SWEEP_REMOVE_CLOSE | SWEEP_TRANSFORM) -> (points_out [M,5] f32 with zero rows
+    behind the last kept row, offsets_out [B+1] i32, status [B] i32: bit 0 a range outside [0, N], bit 1 more than N rows in all).
+    out: a [M,5] f32 tensor with M >= N to write into (None: N rows).  workspace=False leaves the scratch to the per-stream pool."""
+    if points.dim() != 2 or points.shape[1] not in (4, 5):
+        raise ValueError(f"cp_sweeps_merge: points are [N, 4] or [N, 5], got {tuple(points.shape)}")
+    points = _f32c(points)
+    dev, N = points.device, points.shape[0]
+    if seg_range.dim() != 3 or seg_range.shape[2] != 2:
+        raise ValueError(f"cp_sweeps_merge: seg_range is [B, S, 2], got {tuple(seg_range.shape)}")
+    B, S = seg_range.shape[:2]
+    for name, t, want in (("transforms", transforms, (B, S, 12)), ("time_lag", time_lag, (B, S)), ("seg_flags", seg_flags, (B, S))):
+        if tuple(t.shape) != want:
+            raise ValueError(f"cp_sweeps_merge: {name} is {list(want)} beside seg_range {[B, S, 2]}, got {tuple(t.shape)}")
+    if out is None:
+        out = torch.empty((N, 5), dtype=torch.float32, device=dev)
+    elif out.dim() != 2 or out.shape[1] != 5 or out.shape[0] < N or out.dtype != torch.float32:
+        raise ValueError(f"cp_sweeps_merge: out is [M, 5] f32 with M >= {N}, got {tuple(out.shape)} {out.dtype}")
+    offsets_out = torch.empty((B + 1,), dtype=torch.int32, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    ops = [points, _i32c(seg_range, dev), _f64c(transforms, dev), _f64c(time_lag, dev), _i32c(seg_flags, dev), out, offsets_out, status]
+    if workspace:
+        ops.append(torch.empty((cp_sweeps_merge_workspace_bytes(N, B, S),), dtype=torch.uint8, device=dev))
+    _lib.call("md_cp_sweeps_merge", ops, extra=_CPSweepsAttrs(float(radius), 0))
+    return out, offsets_out, status
+
+
+def _sweep_order(order):
+    if order not in ("key_first", "oldest_first"):
+        raise ValueError(f"sweeps: order is 'key_first' (the loader) or 'oldest_first' (the deployment demo), got {order!r}")
+    return order
+
+
+class SweepMerger:
+    """The tables of cp_sweeps_merge for the reference's two callers, built on the host (a few numbers per sweep).
+    order="key_first": LoadPointCloudFromFile, nuScenes branch (centerpoint/det3d_ms/datasets/pipelines/loading.py:133-159): the key
+    frame unfiltered and untransformed with time 0, then the nsweeps - 1 past sweeps in the order of the np.random.choice draw, each
+    through remove_close (min_distance) and, unless its transform_matrix is None (the padding sweeps of nusc_common.py:443-450), the
+    4x4.  order="oldest_first": the deployment demo (tools_ms/multi_sweep_inference_ros.py:194-270): the past sweeps oldest first,
+    each transformed, the current frame last; min_distance=None filters nothing, as the demo does.
+    Not built, refused with ValueError: virtual points, random_select, a dataset type other than nuScenes."""
+
+    def __init__(self, nsweeps, min_distance=1.0, order="key_first", **options):
+        for k, v in options.items():
+            if k in ("virtual", "random_select"):
+                if v:
+                    raise ValueError(f"SweepMerger: {k} is not built")
+            elif k in ("dataset", "type"):
+                if v not in (None, "NuScenesDataset"):
+                    raise ValueError(f"SweepMerger: the {v} branch of LoadPointCloudFromFile is not built (nuScenes only)")
+            else:
+                raise ValueError(f"SweepMerger: unknown option {k!r}")
+        self.nsweeps, self.order = int(nsweeps), _sweep_order(order)
+        if not 1 <= self.nsweeps <= CPSWEEPS_MAX_SWEEPS:
+            raise ValueError(f"SweepMerger: nsweeps in [1, {CPSWEEPS_MAX_SWEEPS}], got {nsweeps}")
+        self.min_distance = None if min_distance is None else float(min_distance)
+        if self.min_distance is not None and not (self.min_distance >= 0 and math.isfinite(self.min_distance)):
+            raise ValueError("SweepMerger: min_distance is a finite radius >= 0, or None")
+
+    @classmethod
+    def from_config(cls, cfg):
+        """cfg.data["sweeps"]: nsweeps, min_distance, order (and the options that are refused)"""
+        data = cfg.data if hasattr(cfg, "data") else cfg["data"]
+        if "sweeps" not in data:
+            raise ValueError("SweepMerger: the config has no data['sweeps'] (see configs/centerpoint/centerpoint_pp_nusc_sweeps.py)")
+        return cls(**dict(data["sweeps"]))
+
+    @property
+    def radius(self):
+        return 0.0 if self.min_distance is None else self.min_distance
+
+    def tables(self, lengths, matrices, time_lags, order=None, begins=None):
+        """lengths [B][nsweeps] rows per frame, frame 0 the key (current) frame, then the past sweeps as the info lists them (newest
+        first); matrices [B][nsweeps] 4x4 float64 or None = no transform (frame 0's is not looked at); time_lags [B][nsweeps]
+        (frame 0's is not looked at: its time is 0).  One sample may be given without the outer list.  begins [B][nsweeps]: each
+        frame's first row in the pool (None: the frames lie back to back in the order given).  order, key_first only: None keeps the
+        past sweeps as listed; an object with .choice (np.random, a RandomState, a Generator) draws choice(nsweeps - 1, nsweeps - 1,
+        replace=False) per sample as the loader does; an array [B][nsweeps - 1] is a recorded draw.
+        -> dict(seg_range [B,S,2] i32, transforms [B,S,12] f64, time_lag [B,S] f64, seg_flags [B,S] i32, order [B,S-1] i64), numpy"""
+        if len(lengths) and not hasattr(lengths[0], "__len__"):
+            lengths, matrices, time_lags = [lengths], [matrices], [time_lags]
+            begins = None if begins is None else [begins]
+            if order is not None and not hasattr(order, "choice"):
+                order = [order]
+        B, S = len(lengths), self.nsweeps
+        if len(matrices) != B or len(time_lags) != B or any(len(x) != S for t in (lengths, matrices, time_lags) for x in t):
+            raise ValueError(f"SweepMerger: lengths, matrices and time_lags are [B][{S}]")
+        past = S - 1
+        if order is None:
+            perm = np.tile(np.arange(past, dtype=np.int64), (B, 1))
+        elif hasattr(order, "choice"):
+            if self.order != "key_first":
+                raise ValueError("SweepMerger: the demo's order is not drawn")
+            perm = np.stack([np.asarray(order.choice(past, past, replace=False), np.int64) for _ in range(B)]).reshape(B, past)
+        else:
+            perm = np.asarray(order, np.int64).reshape(B, past)
+            if any(sorted(p.tolist()) != list(range(past)) for p in perm):
+                raise ValueError("SweepMerger: order is a permutation of the past sweeps per sample")
+        if self.order == "oldest_first":
+            if order is not None:
+                raise ValueError("SweepMerger: the demo's order is fixed")
+            perm = perm[:, ::-1]
+        seg = np.zeros((B, S, 2), np.int32)
+        tf = np.tile(np.eye(4)[:3].reshape(12), (B, S, 1))
+        lag = np.zeros((B, S), np.float64)
+        flags = np.zeros((B, S), np.int32)
+        filt = SWEEP_REMOVE_CLOSE if self.min_distance is not None else 0
+        at = 0
+        for b in range(B):
+            start = []
+            for i in range(S):
+                start.append(at if begins is None else int(begins[b][i]))
+                at += int(lengths[b][i])
+            frames = [1 + int(i) for i in perm[b]]
+            frames = [0] + frames if self.order == "key_first" else frames + [0]
+            for s, i in enumerate(frames):
+                seg[b, s] = (start[i], start[i] + int(lengths[b][i]))
+                if i == 0:
+                    continue
+                lag[b, s] = float(time_lags[b][i])
+                flags[b, s] = filt
+                if matrices[b][i] is not None:
+                    m = np.asarray(matrices[b][i], np.float64)
+                    if m.shape != (4, 4):
+                        raise ValueError(f"SweepMerger: a transform is a 4x4, got {m.shape}")
+                    tf[b, s] = m[:3].reshape(12)
+                    flags[b, s] |= SWEEP_TRANSFORM
+        return dict(seg_range=seg, transforms=tf, time_lag=lag, seg_flags=flags, order=perm.copy())
+
+    def __call__(self, points, lengths, matrices, time_lags, order=None, begins=None, out=None):
+        """tables(), four small host-to-device copies, then cp_sweeps_merge on the pool `points` -> (points, offsets, status)"""
+        t = self.tables(lengths, matrices, time_lags, order=order, begins=begins)
+        dev = points.device
+        return cp_sweeps_merge(points, *[torch.from_numpy(t[k]).to(dev) for k in ("seg_range", "transforms", "time_lag", "seg_flags")],
+                               radius=self.radius, out=out)
+
+
+class SweepRing:
+    """The streaming form of the deployment demo (tools_ms/multi_sweep_inference_ros.py:194-270): a ring of the last nsweeps frames in
+    ONE [nsweeps slot_rows, Fin] device buffer.  push() copies the new frame device-to-device into the slot of the frame it evicts and
+    merges the frames held into the newest frame with one cp_sweeps_merge call whose ranges point into the ring: a past frame is never
+    copied again.  The poses arrive on the host (16 numbers per frame): inv(G_newest) @ G_i is composed there in numpy float64.
+    order="oldest_first": the demo's, the current frame last; "key_first": the current frame, then the past frames newest first.
+    min_distance=None filters nothing (the demo); a radius applies remove_close to the past frames."""
+
+    def __init__(self, nsweeps, slot_rows, order="oldest_first", min_distance=None, device="cuda"):
+        self.merger = SweepMerger(nsweeps, min_distance=min_distance, order=order)
+        self.nsweeps, self.slot_rows, self.device = self.merger.nsweeps, int(slot_rows), torch.device(device)
+        if self.slot_rows < 1 or self.nsweeps * self.slot_rows >= 1 << 30:
+            raise ValueError("SweepRing: slot_rows >= 1 and nsweeps slot_rows < 2^30")
+        self.buffer = None
+        self.frames = []        # (slot, rows, global_from_lidar 4x4 float64, stamp), oldest first
+        self.pushed = 0
+
+    def matrices(self):
+        """[len(frames)] 4x4 float64, oldest first: inv(G_newest) @ G_i (the newest frame's is the identity up to rounding)"""
+        inv = np.linalg.inv(self.frames[-1][2])
+        return [inv @ g for _, _, g, _ in self.frames]
+
+    def tables(self):
+        """the four tables of the frames held (B = 1, S = nsweeps; the segments of frames not yet pushed are empty), numpy"""
+        held = self.frames[::-1]                                  # newest first: frame 0 is the current one, as SweepMerger takes them
+        mats = self.matrices()[::-1]
+        pad = self.nsweeps - len(held)
+        lengths = [n for _, n, _, _ in held] + [0] * pad
+        begins = [slot * self.slot_rows for slot, _, _, _ in held] + [0] * pad
+        newest = held[0][3]
+        lags = [float(newest) - float(st) for _, _, _, st in held] + [0.0] * pad
+        return self.merger.tables(lengths, [None] + mats[1:] + [None] * pad, lags, begins=begins)
+
+    def admit(self, rows, global_from_lidar, stamp):
+        """the host side of push(): a frame of `rows` rows takes the slot of the frame it evicts -> the slot"""
+        n = int(rows)
+        if n > self.slot_rows:
+            raise ValueError(f"SweepRing: a frame of {n} rows does not fit a slot of {self.slot_rows}")
+        g = np.asarray(global_from_lidar, np.float64)
+        if g.shape != (4, 4):
+            raise ValueError(f"SweepRing: global_from_lidar is a 4x4, got {g.shape}")
+        slot = self.pushed % self.nsweeps
+        if len(self.frames) == self.nsweeps:
+            self.frames.pop(0)                                    # the oldest frame: its slot is the one overwritten
+        self.frames.append((slot, n, g.copy(), float(stamp)))
+        self.pushed += 1
+        return slot
+
+    def push(self, points, global_from_lidar, stamp):
+        """points [n,4 or 5] f32 on the device, n <= slot_rows; global_from_lidar 4x4 float64 (host); stamp in seconds
+        -> (points [nsweeps slot_rows,5], offsets [2], status [1]) of the merged cloud in this frame, time = stamp - stamp_i"""
+        if points.dim() != 2 or points.shape[1] not in (4, 5):
+            raise ValueError(f"SweepRing: points are [n, 4] or [n, 5], got {tuple(points.shape)}")
+        if self.buffer is not None and points.shape[1] != self.buffer.shape[1]:
+            raise ValueError(f"SweepRing: the ring holds {self.buffer.shape[1]}-wide points, got {points.shape[1]}")
+        n = points.shape[0]
+        slot = self.admit(n, global_from_lidar, stamp)
+        if self.buffer is None:
+            self.buffer = torch.zeros((self.nsweeps * self.slot_rows, points.shape[1]), dtype=torch.float32, device=self.device)
+        self.buffer[slot * self.slot_rows:slot * self.slot_rows + n].copy_(points)
+        t = self.tables()
+        return cp_sweeps_merge(self.buffer, *[torch.from_numpy(t[k]).to(self.device) for k in ("seg_range", "transforms", "time_lag", "seg_flags")],
+                               radius=self.merger.radius)
+
+
 # ----------------------------------------------------------------------------- training operators: outputs, head losses
 def _out_dict(who, want, out, dev):
     """want: {key: (shape, dtype)} -> `out` checked against it, or a new dict of empty tensors on dev"""

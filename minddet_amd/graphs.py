@@ -1134,7 +1134,8 @@ class PillarDetector(Module):
     (md_pillar_encode) -> graphs.PointPillars (neck, bbox_head, post-processing, unchanged).  Everything stays on the device: the
     outputs have fixed capacity and no size is read back."""
 
-    def __init__(self, reader, backbone, neck, bbox_head, voxel_generator, train_cfg=None, test_cfg=None, pretrained=None, seed=7):
+    def __init__(self, reader, backbone, neck, bbox_head, voxel_generator, train_cfg=None, test_cfg=None, pretrained=None, seed=7,
+                 sweeps=None):
         from .registry import build
         self.reader = build(dict(reader, seed=seed + 2) if isinstance(reader, dict) and "seed" not in reader else reader, READERS)
         self.backbone = build_backbone(backbone)
@@ -1152,6 +1153,7 @@ class PillarDetector(Module):
         self.train_cfg = dict(train_cfg) if train_cfg else None
         self._voxel_generator = vg
         self._augment = self._targets = None
+        self._sweeps_cfg, self._sweeps = (dict(sweeps) if sweeps else None), None
 
     def children(self):
         return [self.reader, self.backbone, self.detector]
@@ -1182,6 +1184,27 @@ class PillarDetector(Module):
         return self.detector.forward(canvas)
 
     __call__ = forward
+
+    def sweeps_op(self):
+        """det_ops.SweepMerger with the model's `sweeps` (nsweeps, min_distance, order; configs/centerpoint/centerpoint_pp_nusc_sweeps.py)"""
+        if self._sweeps is None:
+            if not self._sweeps_cfg:
+                raise ValueError("PillarDetector: the model has no `sweeps` (see configs/centerpoint/centerpoint_pp_nusc_sweeps.py)")
+            self._sweeps = det_ops.SweepMerger(**self._sweeps_cfg)
+        return self._sweeps
+
+    def merge_sweeps(self, points, lengths, matrices, time_lags, order=None, begins=None, return_status=False):
+        """The reference loader's multi-sweep step on the device (det_ops.SweepMerger: read_sweep per past sweep and the concatenation):
+        points [N, 4 or 5] f32 = the pool that holds every frame of the B samples; lengths, matrices, time_lags [B][nsweeps] (frame 0
+        the key frame; a matrix None = no transform), order = the loader's draw -> (points [N, 5] f32, offsets [B + 1] i32) as forward
+        and train_example take them (zero rows behind offsets[B]); nothing is read back.  return_status=True: plus status [B] i32."""
+        pts, offsets, status = self.sweeps_op()(points, lengths, matrices, time_lags, order=order, begins=begins)
+        return (pts, offsets, status) if return_status else (pts, offsets)
+
+    def forward_sweeps(self, points, lengths, matrices, time_lags, order=None, begins=None, return_aux=False):
+        """merge_sweeps, then forward on the merged cloud"""
+        pts, offsets = self.merge_sweeps(points, lengths, matrices, time_lags, order=order, begins=begins)
+        return self.forward(pts, offsets, return_aux=return_aux)
 
     def _train_cfg(self, key):
         if not self.train_cfg or key not in self.train_cfg:

@@ -28,6 +28,9 @@ read the same (paths relative to /root/reference/minddet/models):
   cn_aug_transform, cn_aug_image, CenterNetAugment
                           centernet/src/dataset.py:278-315 (the training branch of COCOHP.preprocess_fn in front of the targets)
                           with centernet/src/image.py:25-57,208-253 (get_affine_transform, color_aug)
+  KittiCalibration, crop_hulls, kitti_boxes_to_lidar, kitti_rows
+                          pointpillars/src/core/box_np_ops.py:395-449, 581-636 (remove_outside_points, the frustums, box_camera_to_lidar),
+                          pointpillars/src/data/preprocess.py:59-71, 87 and pointpillars/src/predict.py:204-262, 331-396
 
 All tensors are torch CUDA tensors; work is enqueued on the current stream; nothing here
 synchronises.  There is no CPU path.
@@ -2502,3 +2505,199 @@ class CenterNetAugment:
                                                          flip_prop=self.flip_prop, input_hw=self.input_hw, down_ratio=self.down_ratio)
         inp = cn_aug_image(images_u8, s, mat_in, self.mean, self.std, self.input_hw, colour=colour, stem_layout=self.stem_layout)
         return inp, trans_out, flip_width
+
+
+# ----------------------------------------------------------------------------- KITTI camera-frame ends (csrc/kitti.hip)
+CROP_MAX_HULLS, CROP_MAX_BATCH = 64, 4096                          # MD_CROP_MAX_HULLS, MD_CROP_MAX_BATCH
+KITTI_MAX_DETS, KITTI_MAX_LABELS, KITTI_MAX_BATCH = 512, 4096, 4096     # MD_KITTI_MAX_DETS, MD_KITTI_MAX_LABELS, MD_KITTI_MAX_BATCH
+_KITTI_REFUSED = ("remove_environment", "random_crop", "generate_single_sample_dict", "fp32_calibration")
+
+
+class _KittiRowsAttrs(ctypes.Structure):
+    _fields_ = [("limit_range", ctypes.c_float * 6), ("use_limit", ctypes.c_int32), ("lidar_input", ctypes.c_int32)]
+
+
+def kitti_io_options(**options):
+    """The options of prep_pointcloud / predict.py that the KITTI device chain does not build: a true value raises ValueError.
+    remove_environment (the reference calls it on boxes that are still in the camera frame, data/preprocess.py:79 before :87: a quirk
+    nobody should want restated), random_crop, generate_single_sample_dict (use_self_train=False) and fp32 calibration arithmetic."""
+    for k, v in options.items():
+        if k == "use_self_train":
+            if v is False:
+                raise ValueError("kitti: generate_single_sample_dict (use_self_train=False) is not built")
+        elif k not in _KITTI_REFUSED:
+            raise ValueError(f"kitti: unknown option {k!r}")
+        elif v not in (None, False):
+            raise ValueError(f"kitti: {k} is not built")
+
+
+def _crt_kitti(proj):
+    """projection_matrix_to_crt_kitti (box_np_ops.py:395-408), the same numpy calls"""
+    cr, ct = proj[0:3, 0:3], proj[0:3, 3]
+    rinv, cinv = np.linalg.qr(np.linalg.inv(cr))
+    return np.linalg.inv(cinv), np.linalg.inv(rinv), cinv @ ct
+
+
+def _frustum_corners(bboxes, c, near_clip=0.001, far_clip=100):
+    """get_frustum_v2 (box_np_ops.py:432-449; get_frustum :410-428 is its one-box form): bboxes [n,4] -> [n,8,3] in the camera frame"""
+    fku, fkv, u0v0 = c[0, 0], -c[1, 1], c[0:2, 2]
+    n = bboxes.shape[0]
+    z = np.tile(np.array([near_clip] * 4 + [far_clip] * 4, dtype=c.dtype)[np.newaxis, :, np.newaxis], [n, 1, 1])
+    corners = bboxes[..., [0, 1, 0, 3, 2, 3, 2, 1]].reshape(-1, 4, 2)
+    near = (corners - u0v0) / np.array([fku / near_clip, -fkv / near_clip], dtype=c.dtype)
+    far = (corners - u0v0) / np.array([fku / far_clip, -fkv / far_clip], dtype=c.dtype)
+    return np.concatenate([np.concatenate([near, far], axis=1), z], axis=-1)
+
+
+class KittiCalibration:
+    """The calibration of a batch of KITTI frames and its products, composed on the host in float64 and uploaded once each:
+    rect [B,4,4] (R0_rect), trv2c [B,4,4] (Tr_velo_to_cam), p2 [B,4,4], image_shape [B,2] (h, w).  A single frame may come without the
+    batch axis.  The arrays are widened to float64 -- a stated choice: the reference works in the calibration arrays' dtype (fp32 in its
+    info files); fp32_calibration=True is refused.
+      lidar2cam   rect @ trv2c                           (lidar_to_camera, box_np_ops.py:590-596)
+      cam2lidar   inv(rect @ trv2c)                      (camera_to_lidar multiplies by inv((rect @ trv2c).T) from the right, :581-587)
+      image_frustum()            [B,1,8,3] lidar-frame corners of remove_outside_points (:625-632): projection_matrix_to_crt_kitti,
+                                 get_frustum of [0, 0, w, h], -= t, inv(r) @, camera_to_lidar -- the same numpy calls
+      detection_frustums(bboxes [B,K,4], count)   (hulls [B,K,8,3], count) of the reference_detections lines (data/preprocess.py:59-65)
+    device: where tensor() puts the products ("cpu" keeps everything on the host, for tests without a GPU)."""
+
+    def __init__(self, rect, trv2c, p2, image_shape, device="cuda", **options):
+        kitti_io_options(**options)
+
+        def mats(a, name):
+            a = np.asarray(a.cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float64)
+            a = a[None] if a.ndim == 2 else a
+            if a.ndim != 3 or a.shape[1:] != (4, 4):
+                raise ValueError(f"KittiCalibration: {name} is [B, 4, 4] (KITTI's 3x4 extended by the row 0 0 0 1), got {a.shape}")
+            return np.ascontiguousarray(a)
+
+        self.rect, self.trv2c, self.p2 = mats(rect, "rect"), mats(trv2c, "trv2c"), mats(p2, "p2")
+        shp = np.asarray(image_shape.cpu().numpy() if isinstance(image_shape, torch.Tensor) else image_shape)
+        shp = shp[None] if shp.ndim == 1 else shp
+        self.B = len(self.rect)
+        if shp.shape != (self.B, 2) or len(self.trv2c) != self.B or len(self.p2) != self.B:
+            raise ValueError("KittiCalibration: rect, trv2c and p2 are [B, 4, 4] and image_shape [B, 2] (h, w) for one B")
+        if self.B > KITTI_MAX_BATCH:
+            raise ValueError(f"KittiCalibration: at most {KITTI_MAX_BATCH} frames")
+        self.image_shape = np.ascontiguousarray(shp, dtype=np.int32)
+        self.device = device
+        self.lidar2cam = np.stack([r @ t for r, t in zip(self.rect, self.trv2c)])
+        self.cam2lidar = np.stack([np.linalg.inv(m) for m in self.lidar2cam])
+        self._crt = [_crt_kitti(p) for p in self.p2]
+        self._dev = {}
+
+    def _to_lidar(self, b, frustums):
+        """frustums [n,8,3] in the camera frame of P2 -> the lidar frame, as remove_outside_points and prep_pointcloud do"""
+        _, r, t = self._crt[b]
+        f = frustums - t
+        f = np.einsum("ij, akj->aki", np.linalg.inv(r), f)
+        f = np.concatenate([f, np.ones(list(f.shape[:-1]) + [1])], axis=-1)
+        return (f @ np.linalg.inv((self.rect[b] @ self.trv2c[b]).T))[..., :3]
+
+    def image_frustum_host(self):
+        out = []
+        for b in range(self.B):
+            h, w = self.image_shape[b]
+            out.append(self._to_lidar(b, _frustum_corners(np.array([[0, 0, w, h]], dtype=np.float64), self._crt[b][0])))
+        return np.stack(out) if out else np.zeros((0, 1, 8, 3))
+
+    def detection_frustums_host(self, bboxes, count=None):
+        bboxes = np.asarray(bboxes.cpu().numpy() if isinstance(bboxes, torch.Tensor) else bboxes, dtype=np.float64)
+        if bboxes.ndim != 3 or bboxes.shape[0] != self.B or bboxes.shape[2] != 4:
+            raise ValueError(f"KittiCalibration: reference detections are [B, K, 4] image boxes, got {bboxes.shape}")
+        K = bboxes.shape[1]
+        if K > CROP_MAX_HULLS:
+            raise ValueError(f"KittiCalibration: at most {CROP_MAX_HULLS} reference detections per frame, got {K}")
+        count = np.full(self.B, K, np.int32) if count is None else np.asarray(count.cpu().numpy() if isinstance(count, torch.Tensor) else count, np.int32)
+        hulls = np.stack([self._to_lidar(b, _frustum_corners(bboxes[b], self._crt[b][0])) for b in range(self.B)]) if self.B and K else \
+            np.zeros((self.B, K, 8, 3))
+        return hulls, count
+
+    def tensor(self, name):
+        """lidar2cam, cam2lidar, p2, image_shape, image_frustum, image_count on the device, uploaded at the first use"""
+        if name not in self._dev:
+            host = {"image_frustum": self.image_frustum_host, "image_count": lambda: np.ones(self.B, np.int32)}.get(name, lambda: getattr(self, name))()
+            self._dev[name] = torch.from_numpy(np.ascontiguousarray(host)).to(self.device)
+        return self._dev[name]
+
+    def image_frustum(self):
+        return self.tensor("image_frustum")
+
+    def detection_frustums(self, bboxes, count=None):
+        hulls, count = self.detection_frustums_host(bboxes, count)
+        return torch.from_numpy(np.ascontiguousarray(hulls)).to(self.device), torch.from_numpy(count).to(self.device)
+
+
+def crop_hulls_workspace_bytes(N, B, K):
+    """bytes of scratch md_pc_crop_hulls takes (include/minddet_hip_kitti.h)"""
+    return 192 * B * K + 4 * (N // 256 + 3)
+
+
+def crop_hulls(points, offsets, hulls, hull_count, workspace=True, out=None):
+    """Keep the points inside any of a sample's convex hexahedra (md_pc_crop_hulls, include/minddet_hip_kitti.h): points [N,4] f32 with
+    offsets [B+1] i32, hulls [B,K,8,3] f64 (lidar-frame corners in the reference's corner order), hull_count [B] i32 ->
+    (points_out [N,4] f32 with zero rows behind the last kept row, offsets_out [B+1] i32, keep [N] u8).  out: an [N,4] f32 tensor to
+    write into.  workspace=False leaves the scratch to the per-stream pool."""
+    if points.dim() != 2 or points.shape[1] != 4:
+        raise ValueError(f"crop_hulls: points are [N, 4] (other widths are not built), got {tuple(points.shape)}")
+    points = _f32c(points)
+    dev, N = points.device, points.shape[0]
+    if hulls.dim() != 4 or tuple(hulls.shape[2:]) != (8, 3):
+        raise ValueError(f"crop_hulls: hulls are [B, K, 8, 3], got {tuple(hulls.shape)}")
+    B, K = hulls.shape[:2]
+    if K > CROP_MAX_HULLS or B > CROP_MAX_BATCH:
+        raise ValueError(f"crop_hulls: at most {CROP_MAX_HULLS} hulls per sample and {CROP_MAX_BATCH} samples, got {K} and {B}")
+    if tuple(offsets.shape) != (B + 1,) or tuple(hull_count.shape) != (B,):
+        raise ValueError(f"crop_hulls: offsets are [{B + 1}] and hull_count [{B}] beside hulls {tuple(hulls.shape)}")
+    if out is None:
+        out = torch.empty((N, 4), dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != (N, 4) or out.dtype != torch.float32:
+        raise ValueError(f"crop_hulls: out is [{N}, 4] f32, got {tuple(out.shape)} {out.dtype}")
+    offsets_out = torch.empty((B + 1,), dtype=torch.int32, device=dev)
+    keep = torch.empty((N,), dtype=torch.uint8, device=dev)
+    ops = [points, _i32c(offsets, dev), _f64c(hulls, dev), _i32c(hull_count, dev), out, offsets_out, keep]
+    if workspace:
+        ops.append(torch.empty((crop_hulls_workspace_bytes(N, B, K),), dtype=torch.uint8, device=dev))
+    _lib.call("md_pc_crop_hulls", ops)
+    return out, offsets_out, keep
+
+
+def kitti_boxes_to_lidar(boxes_cam, gt_count, cam2lidar):
+    """box_camera_to_lidar for a batch (md_kitti_boxes_to_lidar): boxes_cam [B,G,7] f32 (x, y, z, l, h, w, r), gt_count [B],
+    cam2lidar [B,4,4] f64 -> boxes_lidar [B,G,7] f32 (x, y, z, w, l, h, r), zero rows from the count on."""
+    g = _f32c(boxes_cam)
+    if g.dim() != 3 or g.shape[2] != 7:
+        raise ValueError(f"kitti_boxes_to_lidar: boxes are [B, G, 7], got {tuple(g.shape)}")
+    dev, (B, G) = g.device, g.shape[:2]
+    if G > KITTI_MAX_LABELS or B > KITTI_MAX_BATCH:
+        raise ValueError(f"kitti_boxes_to_lidar: at most {KITTI_MAX_LABELS} rows per sample and {KITTI_MAX_BATCH} samples")
+    if tuple(cam2lidar.shape) != (B, 4, 4) or tuple(gt_count.shape) != (B,):
+        raise ValueError(f"kitti_boxes_to_lidar: cam2lidar is [{B}, 4, 4] and gt_count [{B}]")
+    out = torch.empty((B, G, 7), dtype=torch.float32, device=dev)
+    _lib.call("md_kitti_boxes_to_lidar", [g, _i32c(gt_count, dev), _f64c(cam2lidar, dev), out])
+    return out
+
+
+def kitti_rows(dets, count, lidar2cam, p2, image_shape, limit_range=None, lidar_input=False):
+    """generate_single_sample_dict_old (without its direction flip) + predict_kitti_to_anno for a batch (md_kitti_rows): dets [B,M,9] f32
+    and count [B] as the KITTI model's forward returns them, lidar2cam / p2 [B,4,4] f64, image_shape [B,2] i32 (h, w); limit_range =
+    post_center_limit_range or None -> (rows [B,M,14] f32: alpha, bbox, dimensions l h w, location, rotation_y, score, label;
+    src [B,M] i32; out_count [B] i32)."""
+    d = _f32c(dets)
+    if d.dim() != 3 or d.shape[2] != 9:
+        raise ValueError(f"kitti_rows: dets are [B, M, 9], got {tuple(d.shape)}")
+    dev, (B, M) = d.device, d.shape[:2]
+    if M > KITTI_MAX_DETS or B > KITTI_MAX_BATCH:
+        raise ValueError(f"kitti_rows: at most {KITTI_MAX_DETS} detections per sample and {KITTI_MAX_BATCH} samples")
+    for name, t, want in (("count", count, (B,)), ("lidar2cam", lidar2cam, (B, 4, 4)), ("p2", p2, (B, 4, 4)), ("image_shape", image_shape, (B, 2))):
+        if tuple(t.shape) != want:
+            raise ValueError(f"kitti_rows: {name} is {list(want)}, got {tuple(t.shape)}")
+    lim = [0.0] * 6 if limit_range is None else [float(v) for v in limit_range]
+    if len(lim) != 6 or any(math.isnan(v) for v in lim):
+        raise ValueError("kitti_rows: limit_range has six values, none a NaN")
+    at = _KittiRowsAttrs((ctypes.c_float * 6)(*lim), int(limit_range is not None), int(bool(lidar_input)))
+    rows = torch.empty((B, M, 14), dtype=torch.float32, device=dev)
+    src = torch.empty((B, M), dtype=torch.int32, device=dev)
+    out_count = torch.empty((B,), dtype=torch.int32, device=dev)
+    _lib.call("md_kitti_rows", [d, _i32c(count, dev), _f64c(lidar2cam, dev), _f64c(p2, dev), _i32c(image_shape, dev), rows, src, out_count], extra=at)
+    return rows, src, out_count

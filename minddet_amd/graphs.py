@@ -1567,6 +1567,46 @@ class PointPillarsKITTIPoints(Module):
         ex = self.train_example(points, offsets, gt_boxes, gt_classes, gt_count, generator=generator, draws=draws, valid=valid, sampled=sampled)
         return dict(self.inner.loss(ex["canvas"], ex, grad=grad), example=ex)
 
+    def _kitti_options(self):
+        """test_cfg's KITTI keys: remove_outside_points (True), lidar_input (False), post_center_limit_range (None); the options that
+        are not built raise (det_ops.kitti_io_options)"""
+        tc = self.test_cfg
+        det_ops.kitti_io_options(**{k: tc[k] for k in ("remove_environment", "random_crop", "use_self_train", "fp32_calibration") if k in tc})
+        return bool(tc.get("remove_outside_points", True)), bool(tc.get("lidar_input", False)), tc.get("post_center_limit_range")
+
+    def prepare_kitti(self, points, offsets, calib, gt_boxes_camera=None, gt_count=None, reference_detections=None):
+        """The camera-frame part of prep_pointcloud (pointpillars/src/data/preprocess.py:59-71, 87) on the device: a raw velodyne scan
+        [N,4] f32 with offsets [B+1] and its det_ops.KittiCalibration -> (points, offsets) cut to the camera's view, ready for forward /
+        train_example, and -- with gt_boxes_camera [B,G,7] f32 (x, y, z, l, h, w, r) and gt_count [B] -- the lidar ground truth
+        [B,G,7] (else None).  Order as the reference's: the frustums of reference_detections (= (bboxes [B,K,4], count [B] or None))
+        first, then the image frustum (test_cfg.remove_outside_points, skipped with lidar_input).  Nothing is read back."""
+        crop_image, lidar_input, _ = self._kitti_options()
+        if points.dim() != 2 or points.shape[1] != 4:
+            raise ValueError(f"PointPillarsKITTIPoints: the KITTI crop takes [N, 4] points, got {tuple(points.shape)}")
+        if reference_detections is not None:
+            bboxes, count = reference_detections if isinstance(reference_detections, (tuple, list)) else (reference_detections, None)
+            points, offsets, _ = det_ops.crop_hulls(points, offsets, *calib.detection_frustums(bboxes, count))
+        if crop_image and not lidar_input:
+            points, offsets, _ = det_ops.crop_hulls(points, offsets, calib.image_frustum(), calib.tensor("image_count"))
+        boxes = None
+        if gt_boxes_camera is not None:
+            if gt_count is None:
+                raise ValueError("PointPillarsKITTIPoints: gt_boxes_camera come with gt_count")
+            boxes = det_ops.kitti_boxes_to_lidar(gt_boxes_camera, gt_count, calib.tensor("cam2lidar"))
+        return points, offsets, boxes
+
+    def forward_kitti(self, points, offsets, calib):
+        """A raw velodyne scan and its calibration -> KITTI result rows, as one device chain: prepare_kitti's crop, forward, and
+        det_ops.kitti_rows with test_cfg.post_center_limit_range and lidar_input (generate_single_sample_dict_old + predict_kitti_to_anno,
+        pointpillars/src/predict.py:204-262, 331-396) -> (rows [B,M,14] f32, src [B,M] i32, out_count [B] i32, dets [B,M,9] f32);
+        kitti_eval.rows_to_annos formats them on the host."""
+        _, lidar_input, limit = self._kitti_options()
+        pts, offs, _ = self.prepare_kitti(points, offsets, calib)
+        dets, count = self.forward(pts, offs)
+        rows, src, out_count = det_ops.kitti_rows(dets, count, calib.tensor("lidar2cam"), calib.tensor("p2"), calib.tensor("image_shape"),
+                                                  limit_range=limit, lidar_input=lidar_input)
+        return rows, src, out_count, dets
+
 
 # ----------------------------------------------------------------------------- YOLOv5 (build-authored; parity unpinned)
 SPPF_FUSED = os.environ.get("MD_SPPF_FUSED", "1") != "0"    # A/B knob: 0 = three md_maxpool2d launches + four concat copies per SPPF block

@@ -22,7 +22,8 @@ mAP table, 41-point precision rows, clean_data flags, get_thresholds -- on 223 s
 kitti_eval_vectors.json, written by tests/golden/gen_kitti_eval.py from pointpillars/src/core/eval_utils.py imported with numba's
 decorators as identities).  The "full" protocol shares that machinery; its BEV / 3D / AOS parts (eval_gpu/eval.py needs
 numba.cuda) are checked against a scalar restatement of the matching rules and hand-computed answers only: parity unpinned there,
-as is any run on real KITTI results.  The lidar -> camera -> image box geometry reproduces the reference's box_ops.py outputs (same
+as is any run on real KITTI results.  `rows_to_annos` formats the rows that det_ops.kitti_rows (md_kitti_rows) wrote on the device -- the same
+filters, clip and alpha for a batch with nothing read back in between -- into the same dicts.  The lidar -> camera -> image box geometry reproduces the reference's box_ops.py outputs (same
 golden file); the annotation writer's filter rules (predict.py needs skimage through kitti_common: not importable) are restated.  Reference quirk: eval_utils.get_split_parts has no guard, fewer than 50 images crash it.
 """
 import numpy as np
@@ -125,6 +126,26 @@ def predictions_to_kitti_annos(predictions, batch_image_shape, class_names, cent
                 rows["score"].append(score)
         anno = {k: np.stack(v) for k, v in rows.items()} if rows["name"] else empty_result_anno()
         anno["image_idx"] = np.array([pred["image_idx"]] * anno["name"].shape[0], dtype=np.int64)
+        annos.append(anno)
+    return annos
+
+
+def rows_to_annos(rows, src, count, dets, class_names, image_idx):
+    """The result rows of det_ops.kitti_rows / PointPillarsKITTIPoints.forward_kitti ([B,M,14]: alpha, bbox, dimensions l h w, location,
+    rotation_y, score, label; src [B,M]; count [B]; device tensors or arrays) -> the annotation dicts predictions_to_kitti_annos returns,
+    one per sample.  Host formatting only: the filters, the clip and alpha were applied on the device; this adds the names,
+    truncated 0, occluded 0 and image_idx.  `dets` (the detections the rows came from) is not read: src says which row each one was."""
+    rows, src, count = (np.asarray(t.cpu().numpy() if hasattr(t, "cpu") else t) for t in (rows, src, count))
+    annos = []
+    for b in range(rows.shape[0]):
+        n = int(count[b])
+        if n == 0:
+            anno = empty_result_anno()
+        else:
+            r = rows[b, :n].astype(np.float64)
+            anno = dict(name=np.array([class_names[int(k)] for k in r[:, 13]]), truncated=np.zeros(n), occluded=np.zeros(n, np.int64),
+                        alpha=r[:, 0], bbox=r[:, 1:5], dimensions=r[:, 5:8], location=r[:, 8:11], rotation_y=r[:, 11], score=r[:, 12])
+        anno["image_idx"] = np.array([image_idx[b]] * n, dtype=np.int64)
         annos.append(anno)
     return annos
 

@@ -318,6 +318,8 @@ int md_bottleneck(MD_AOT_ARGS);
  * md_conv2d launches it replaces (bf16 operands, fp32 accumulation in the same K order, the intermediate and the pre-shortcut value
  * rounded to bf16): bit-identical to them.  With pass_through the next C channels of x are copied to the next C channels of y (the
  * cv2(x) half of the C3 concat buffer travels with the result).  x and y must not overlap: MD_ERR_ARG.
+ * Held to a float64 reference of these rounding points (tests/conv_contract.py reference_c3_pair) by tests/test_c3pair_gpu.py:
+ * test_c3_pair_exact_regime_against_float64, test_c3_pair_gaussian_regime_stage_by_stage and test_c3_pair_gaussian_regime_against_float64.
  * in : x[N,H,W,XC] bf16, w1[C, roundup(C, 64)] bf16, b12[2C] f32 (conv1's biases, then conv2's), w2[C, roundup(9C, 64)] bf16 -- the
  *      weights as md_conv2d packs them (K zero-padded to a multiple of 64):
  *        C = 32 : w1[32, 64],   w2[32, 320],   korder 0: K = tap * 32 + ci;

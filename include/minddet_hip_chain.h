@@ -19,7 +19,9 @@ extern "C" {
  * out: y[N,H,W,512] bf16, t1[N,H,W,128] bf16.   extra: not read.
  *   y  = bf16(relu(bf16(w3 . t2 + b3) + res))      -- the roundings of md_conv2d with a residual and relu = 1
  *   t1 = bf16(relu(w1 . y + b1))                   -- md_conv2d with relu = 1 on the stored (bf16) y
- * Both results are bit-identical to those two md_conv2d calls.  All activations are whole contiguous NHWC tensors: an operand with
+ * Both results are bit-identical to those two md_conv2d calls, and both are held to a float64 reference of these rounding points
+ * (tests/conv_contract.py reference_pw_chain) by tests/test_pw_chain_gpu.py: test_exact_regime_both_outputs_bit_for_bit and
+ * test_gaussian_regime_y_and_t1_within_the_float64_contract.  All activations are whole contiguous NHWC tensors: an operand with
  * another channel count (a channel slice of a wider tensor) is refused.
  * 2: channel counts other than 128 / 512 / 128, weight or bias shapes other than the above, N H W not the same in every activation,
  *    y or t1 overlapping t2, res or each other (the residual of a tile is fetched while earlier tiles are stored: in place is not safe).

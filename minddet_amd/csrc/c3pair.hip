@@ -19,6 +19,9 @@
 // small on purpose: what a tile costs is its chain of exposed latencies (x tile, weights, shortcut values, stores), and only a second /
 // third resident workgroup hides them (r04, tools/c3pair_check.py: a deeper ring with ONE workgroup per CU was no faster than two launches).  K order = md_conv2d's for these layers (1x1: k;
 // 3x3 with korder 1: (ci / 64, tap, ci % 64)), same MFMA shape, same bf16 rounding points: bit-identical to the two launches.
+// Held to float64 by tests/test_c3pair_gpu.py against conv_contract.reference_c3_pair at C = 32, 64 and 128: an exact regime (a draw
+// that keeps both SiLU stages exact; every output the RNE rounding of the float64 chain, either neighbour at the few SiLU midpoints),
+// and a Gaussian regime within the derived bound, stage by stage on the device's own intermediate and end to end.
 //
 // LDS: T (192 rows x 2 C B; b1 | b2 in its unused last rows) | ring = 48 KiB (C = 64: three workgroups per CU) / 80 KiB (C = 128: two).
 #include <hip/hip_runtime.h>

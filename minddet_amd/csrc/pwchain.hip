@@ -14,7 +14,8 @@
 //     place (each 8-byte cell is read and re-written by the same lane) and the image leaves as whole 128-B-line buffer stores;
 //   * the eight wave images together ARE the y tile [32 px][512]: after one workgroup barrier every wave reads all eight as B fragments of
 //     v_mfma_f32_16x16x32_bf16 for its 16 conv1 couts (the chip rounds this shape exactly as the 32x32x16 one the 128x128 kernel uses:
-//     tools/pp_mf_ab.py; tests/test_pw_chain_gpu.py compares the bits).  Two image sets: the next tile's residual lands in the other set
+//     tools/pp_mf_ab.py; test_exact_regime_both_outputs_bit_for_bit of tests/test_pw_chain_gpu.py holds t1 to the float64 result bit for
+//     bit on integer data, independently of md_conv2d).  Two image sets: the next tile's residual lands in the other set
 //     while GEMM 2 reads this one;
 //   * t1 is assembled as a [32 px][128] tile in LDS and leaves as whole 256-B rows one barrier later (under the next tile's GEMM 1).
 // Every global access goes through a buffer descriptor re-based per tile with 64-bit scalar math: rows past M read zeros / drop their
@@ -22,6 +23,8 @@
 // descriptor and its DMAs / stores are still issued, so every wave's vector-memory queue has the same shape in every iteration and the
 // waits are compile-time counts.  No two workgroups touch a common byte, so their placement on the XCDs does not matter.
 // Rounds exactly where the two md_conv2d launches round (conv + bias -> bf16, + residual -> bf16, ReLU; conv1 reads the bf16 y).
+// Held to float64 by tests/test_pw_chain_gpu.py against conv_contract.reference_pw_chain: y and t1 bit for bit in the exact regime, each
+// within one conv's derived bound in the Gaussian regime, at workgroup tile counts of 1 to 5 (below, at and above the look-ahead).
 //
 // LDS: ring 32 KiB | 2 x 8 images 64 KiB | t1 tile 8 KiB | b3 2 KiB = 106 KiB (b1: four registers per lane).
 #include <hip/hip_runtime.h>

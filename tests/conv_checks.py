@@ -1,6 +1,6 @@
-"""Shared by the tests that hold a conv launch to tests/conv_contract.py (test_conv_production_gpu.py, test_centerpoint_conv_gpu.py and,
-for the data draws, test_conv_reference_cpu.py): the two regimes' value draws, the sentinel-filled output with guard zones, and the
-comparison of an output with a reference of conv_contract."""
+"""Shared by the tests that hold a conv launch to tests/conv_contract.py (test_conv_production_gpu.py, test_centerpoint_conv_gpu.py,
+test_c3pair_gpu.py, test_pw_chain_gpu.py and, for the data draws, test_conv_reference_cpu.py): the two regimes' value draws, the
+sentinel-filled output with guard zones, and the comparison of an output with a reference of conv_contract."""
 import torch
 
 SENTINEL = 0x7FA5          # a bf16 NaN bit pattern (as int16) that no computed value takes
@@ -65,6 +65,59 @@ def check(got, ref, exact):
     worst = float(ratio.max())
     assert worst <= 1, f"{int((ratio > 1).sum())} outputs past the bound; first at {tuple(int(v) for v in (ratio > 1).nonzero()[0])}"
     return worst
+
+
+def check_silu(got, pre, res=None):
+    """exact regime of a SiLU layer: got against the float64 pre-activation (+ the residual values) by the either-neighbour rule --
+    every element equals the RNE rounding of the float64 SiLU, or, where that SiLU lies within the kernels' error of a rounding
+    midpoint (`near`), the result of the other bf16 neighbour.  -> the share of `near` elements"""
+    from tests import conv_contract as cc
+
+    t, other, near = cc.silu_rounding(pre)
+    want = cc.epilogue(pre, 2, res, t).to(torch.bfloat16).view(torch.int16)
+    alt = cc.epilogue(pre, 2, res, other).to(torch.bfloat16).view(torch.int16)
+    gi = got.contiguous().view(torch.int16)
+    bad = (gi != want) & ~(near & (gi == alt))
+    nbad = int(bad.sum())
+    assert not nbad, f"{nbad} of {bad.numel()} outputs differ; first at {tuple(int(v) for v in bad.nonzero()[0])}"
+    return float(near.double().mean())
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# md_c3_pair: the draws of test_c3pair_gpu.py (test_conv_reference_cpu.py checks the exact draw's conditions on the same values)
+# ---------------------------------------------------------------------------------------------------------------------------------
+def c3_pair_seed(case, exact):
+    return 4000 + 2 * (len(case[0]) * 7 + case[2]) + int(exact)
+
+
+def c3_pair_operands(case, exact, device):
+    """one regime's draw of a row of test_c3pair_gpu.CASES -> (x, w1l, b1, w2l, b2): x [N, H, W, XC] bf16 with NaN in every channel
+    the call must not read, logical weights w1l [C, C] and w2l [C, 3, 3, C] bf16, biases f32.  Drawn on the CPU generator whatever the
+    device, so the conditions conv_contract.reference_c3_pair asserts can be checked without a GPU on the very values the GPU test uses.
+
+    The exact draw keeps a chain of two SiLU layers exact: x in {-1, 0, 1}; every row of w1 has 6 non-zeros of +-1/2 and b1 is one of
+    0.5, 1.0 .. 3.0, so the stage-1 pre-activation takes 18 values in [-2.5, 6], none of them near a rounding midpoint of SiLU, and t
+    has a smallest quantum of 2^-10; w2 is +-2^-2 (C = 32) or +-2^-3 (C = 64, 128) at density 1/3 and b2 an integer |b2| <= 3: the
+    stage-2 pre-activation has a standard deviation of 3 to 6 and reaches +-20, so SiLU is exercised from its flat tail to its linear
+    branch, and stage 2 needs 18 to 20 of fp32's 24 bits."""
+    name, n, h, w, c, shortcut, passt, xc, xo = case[:9]
+    g = torch.Generator().manual_seed(c3_pair_seed(case, exact))
+    if exact:
+        x = torch.randint(-1, 2, (n, h, w, xc), generator=g).to(torch.bfloat16)
+        cols = torch.rand((c, c), generator=g).argsort(dim=1)[:, :6]
+        w1l = torch.zeros((c, c)).scatter_(1, cols, torch.randint(0, 2, (c, 6), generator=g).float() - 0.5).to(torch.bfloat16)
+        b1 = torch.randint(1, 7, (c,), generator=g).float() * 0.5
+        sign = torch.randint(0, 2, (c, 3, 3, c), generator=g).float() * 2 - 1
+        w2l = (sign * (torch.rand((c, 3, 3, c), generator=g) < 1 / 3) * (0.25 if c == 32 else 0.125)).to(torch.bfloat16)
+        b2 = torch.randint(-3, 4, (c,), generator=g).float()
+    else:
+        d = Data(False, c3_pair_seed(case, exact), "cpu")
+        x, w1l, b1 = d.act((n, h, w, xc)), d.weight((c, c), c), d.bias(c, c)
+        w2l, b2 = d.weight((c, 3, 3, c), 9 * c), d.bias(c, c)
+    read = torch.zeros(xc, dtype=torch.bool)
+    read[xo:xo + (2 * c if passt else c)] = True
+    x[..., ~read] = float("nan")
+    return tuple(v.to(device) for v in (x, w1l, b1, w2l, b2))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

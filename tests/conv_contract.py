@@ -2,7 +2,8 @@
 weight packer, and a float64 reference of md_conv2d / md_conv2d_head / md_conv1x1_dual / md_conv2d_grouped that rounds to bf16 exactly
 where the header says the kernels do.  Shared by tests/test_conv_plan_cpu.py (plans), tests/test_conv_reference_cpu.py (the reference
 against F.conv2d / F.conv_transpose2d composed by hand), tests/test_conv_production_gpu.py (every production call against the reference),
-tests/neck_checks.py (an RPN neck layer by layer) and tests/test_centerpoint_conv_gpu.py (the grouped op, CenterHead and CenterPoint's neck).
+tests/neck_checks.py (an RPN neck layer by layer), tests/test_centerpoint_conv_gpu.py (the grouped op, CenterHead and CenterPoint's neck),
+tests/test_c3pair_gpu.py (md_c3_pair) and tests/test_pw_chain_gpu.py (md_pw_chain).
 
 A call's arguments are (op, shapes, attrs): the shapes of its parameters in the op's order (None = NULL) and its attribute record as a
 dict with the field names of md_conv2d_attrs / md_conv1x1_dual_attrs -- the form tests/golden/conv_plans.json stores."""
@@ -432,3 +433,85 @@ def reference_bottleneck(x, w1l, b1, w2l, b2, w3l, b3, res=None, wdl=None, bd=No
         r = x.double()
     y, e = conv_stage(t2, e2, w3l[:, None, None, :], b3, _plain(n, h, w, 64, 1, 1, 0, 256), 1, r, re)
     return y if exact else (y, e)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# md_c3_pair and md_pw_chain: two convs in one launch, each one conv_stage
+# ---------------------------------------------------------------------------------------------------------------------------------
+NEAR_CAP = 2e-3   # largest share of stage-2 outputs of an exact-regime md_c3_pair draw that may take either bf16 neighbour
+
+
+def grid(v):
+    """the largest power of two (<= 1) that every element of v is an integer multiple of"""
+    v = v.double()
+    for s in range(0, 64):
+        q = v * 2.0 ** s
+        if bool((q == q.round()).all()):
+            return 2.0 ** -s
+    raise AssertionError("values are on no binary grid down to 2^-63")
+
+
+def fp32_exact_bits(abs_sum, unit):
+    """bits an fp32 accumulation needs to hold every partial sum of terms that are multiples of `unit` and sum to at most abs_sum in
+    magnitude: below 24 the sum is exact in any summation order"""
+    return float(torch.log2(abs_sum.max() / unit))
+
+
+def c3_pair_weights(w1l, w2l):
+    """the operands of the header from the logical weights w1l [C, C], w2l [C, 3, 3, C]: w1 [C, roundup(C, 64)] and w2 [C, roundup(9 C, 64)]
+    with K order 0 (tap * C + ci) for C = 32 and 1 ((ci / 64) * 576 + tap * 64 + ci % 64) above; K zero padded"""
+    c = w1l.shape[0]
+    return (pack_weight(w1l[:, None, None, :], 0, (c + 63) // 64 * 64, c), pack_weight(w2l, 0 if c == 32 else 1, (9 * c + 63) // 64 * 64, c))
+
+
+def reference_c3_pair(x, w1l, b1, w2l, b2, x_c_off, shortcut, exact=True):
+    """md_c3_pair on channels [x_c_off, x_c_off + C) of x: t = bf16(silu(conv1x1(x) + b1)), u = bf16(silu(conv3x3/p1(t) + b2)) with the
+    zero padding applied to t, y = bf16(u + x) if shortcut else u.  w1l [C, C], w2l [C, 3, 3, C] logical weights.
+    exact=False -> (y, bound), the chain of two conv_stage calls.
+    exact=True  -> (t, pre2, res): the stage-1 value, the float64 stage-2 pre-activation and the residual values (None without the
+    shortcut); the caller judges SiLU's rounding of pre2 with silu_rounding / epilogue.  The draw has to keep the chain exact, and
+    that is ASSERTED here:
+      (a) no stage-1 pre-activation is `near` in silu_rounding: t is the one bf16 value every correct kernel gives;
+      (b) both stages are exact in fp32 in any summation order: max(sum|t w2| + |b2|) over (the smallest bf16 quantum among the
+          non-zero t times the weights' grid) is below 2^24, and likewise stage 1;
+      (c) at most NEAR_CAP of the stage-2 outputs are `near` (may take either bf16 neighbour);
+      (d) the shortcut add, done in fp32, rounds to the bf16 value the exact sum rounds to, for both admissible u."""
+    n, h, w, _ = x.shape
+    c = w1l.shape[0]
+    assert tuple(w1l.shape) == (c, c) and tuple(w2l.shape) == (c, 3, 3, c)
+    g1 = Geometry(1, 1, 1, 0, 0, h, w, 1, 0, 0, 0, c, x_c_off, c, (n, h, w, c))
+    g2 = _plain(n, h, w, c, 3, 1, 1, c)
+    xs = x[..., x_c_off:x_c_off + c].double()
+    res = xs if shortcut else None
+    w1 = w1l[:, None, None, :]
+    if not exact:
+        t, e_t = conv_stage(x, 0.0, w1, b1, g1, 2)
+        return conv_stage(t, e_t, w2l, b2, g2, 2, res)
+    pre1 = conv_sum(x, w1, g1) + b1.double()
+    u1 = grid(xs) * grid(w1l)
+    assert grid(b1) >= u1 and fp32_exact_bits(conv_sum(x, w1, g1, absolute=True) + b1.double().abs(), u1) < 24, "(b) stage 1"
+    t, _, near1 = silu_rounding(pre1)
+    assert not bool(near1.any()), f"(a) {int(near1.sum())} stage-1 pre-activations are near a rounding midpoint"
+    u2 = float(bf16_quantum(t[t != 0]).min()) * grid(w2l)
+    bits = fp32_exact_bits(conv_sum(t, w2l, g2, absolute=True) + b2.double().abs(), u2)
+    assert grid(b2) >= u2 and bits < 24, f"(b) stage 2 needs {bits:.1f} bits"
+    pre2 = conv_sum(t, w2l, g2) + b2.double()
+    u, other, near = silu_rounding(pre2)
+    share = float(near.double().mean())
+    assert share <= NEAR_CAP, f"(c) either-neighbour share {share:.2e}"
+    if shortcut:
+        for v in (u, other):
+            s = v + res
+            assert torch.equal(bf16_rne(s.float().double()), bf16_rne(s)), "(d) the fp32 shortcut add changes the rounding"
+    return t, pre2, res
+
+
+def reference_pw_chain(t2, res, w3l, b3, w1l, b1, exact=True):
+    """md_pw_chain: y = relu(bf16(bf16(conv3(t2) + b3) + res)), t1 = bf16(relu(conv1(y) + b1)); w3l [512, 128], w1l [128, 512] logical
+    weights.  ReLU only, so the exact regime is exact for both outputs -> (y, t1), or ((y, e_y), (t1, e_t1))"""
+    n, h, w, c = t2.shape
+    cy = w3l.shape[0]
+    assert tuple(w3l.shape) == (cy, c) and tuple(w1l.shape) == (c, cy) and tuple(res.shape) == (n, h, w, cy)
+    y, e_y = conv_stage(t2, None if exact else 0.0, w3l[:, None, None, :], b3, _plain(n, h, w, c, 1, 1, 0, cy), 1, res.double())
+    t1, e_t1 = conv_stage(y, e_y, w1l[:, None, None, :], b1, _plain(n, h, w, cy, 1, 1, 0, c), 1)
+    return (y, t1) if exact else ((y, e_y), (t1, e_t1))

@@ -358,3 +358,260 @@ def test_grouped_contract_passes_a_correct_kernel_and_sees_three_defects():
         if not exact:
             got = _simulated_kernel(x, wls, biases, a, y_shape).double()
             print(f"correct kernel, Gaussian regime: worst err / bound {float(((got[written] - y[written]).abs() / bound[written]).max()):.3f}")
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# md_c3_pair and md_pw_chain: the references of conv_contract, the exact draw's conditions, and what the two regimes see
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _c3_small_cases():
+    from tests.test_c3pair_gpu import SMALL
+
+    return SMALL
+
+
+def _c3_case(name):
+    return next(c for c in _c3_small_cases() if c[0] == name)
+
+
+def _c3_draw(case, exact):
+    from tests.conv_checks import c3_pair_operands
+
+    return c3_pair_operands(case, exact, "cpu")
+
+
+def silu_by_hand(pre):
+    """float64 SiLU through torch.sigmoid, rounded to bf16 once"""
+    return cc.bf16_rne(pre * torch.sigmoid(pre))
+
+
+@pytest.mark.parametrize("name", ["c32_offsets_pass_through", "c32_ragged", "c128_offsets_no_second_half", "c128_ragged", "c64_offsets"])
+def test_c3_pair_reference_against_torch(name):
+    """reference_c3_pair against F.conv2d composed by hand with a rounding at each of the header's rounding points: C = 32 (K order 0)
+    and C = 128 (K order 1), with and without the shortcut, with x_c_off != 0 (NaN in every channel of x outside the slice); and the
+    packed operands element by element against the header's K orders"""
+    name, n, h, w, c, shortcut, passt, xc, xo = _c3_case(name)[:9]
+    x, w1l, b1, w2l, b2 = (v.double() for v in _c3_draw(_c3_case(name), True))
+    assert x[..., :xo].isnan().all() and x[..., xo + (2 * c if passt else c):].isnan().all() and not x[..., xo:xo + c].isnan().any()
+    xs = x[..., xo:xo + c]
+    pre1 = torch_conv(xs, w1l[:, None, None, :]) + b1
+    t_want = silu_by_hand(pre1)
+    pre2_want = torch_conv(t_want, w2l, 1, (1,) * 4) + b2                     # F.conv2d's zero padding pads t
+    for sc in (False, True):
+        t, pre2, res = cc.reference_c3_pair(x, w1l, b1, w2l, b2, xo, sc, exact=True)
+        assert torch.equal(t, t_want) and torch.equal(pre2, pre2_want)        # multiples of 2^-13 below 2^6: exact in float64
+        assert (res is None) if not sc else torch.equal(res, xs)
+        u = silu_by_hand(pre2)
+        assert torch.equal(cc.epilogue(pre2, 2, res), rnd(u + xs) if sc else u)
+        # the Gaussian form: the unrounded float64 chain and a positive bound
+        v, bound = cc.reference_c3_pair(x, w1l, b1, w2l, b2, xo, sc, exact=False)
+        p1 = pre1 * torch.sigmoid(pre1)
+        p2 = torch_conv(p1, w2l, 1, (1,) * 4) + b2
+        assert torch.allclose(v, p2 * torch.sigmoid(p2) + (xs if sc else 0), rtol=1e-12, atol=1e-12) and bool((bound > 0).all())
+    w1, w2 = cc.c3_pair_weights(w1l, w2l)
+    assert tuple(w1.shape) == (c, (c + 63) // 64 * 64) and tuple(w2.shape) == (c, (9 * c + 63) // 64 * 64)
+    assert torch.equal(w1[:, :c], w1l) and not w1[:, c:].any() and not w2[:, 9 * c:].any()
+    for co, i, j, ci in ((0, 0, 0, 0), (c - 1, 2, 2, c - 1), (5, 1, 2, c // 2 + 3), (17, 2, 0, 31), (c // 2, 0, 1, c - 30)):
+        tap = 3 * i + j
+        k = tap * 32 + ci if c == 32 else (ci // 64) * 576 + tap * 64 + ci % 64
+        assert w2[co, k] == w2l[co, i, j, ci]
+
+
+def test_c3_pair_exact_draw_keeps_the_chain_exact_for_every_case():
+    """conditions (a) to (d) of reference_c3_pair (asserted inside it) on the very draws the GPU test uses, every small case: no
+    stage-1 value near a rounding midpoint, both stages exact in fp32, the either-neighbour share of stage 2 at most 2e-3"""
+    for case in _c3_small_cases():
+        x, w1l, b1, w2l, b2 = _c3_draw(case, True)
+        t, pre2, _ = cc.reference_c3_pair(x, w1l, b1, w2l, b2, case[8], case[5], exact=True)
+        g2 = cc._plain(case[1], case[2], case[3], case[4], 3, 1, 1, case[4])
+        unit = float(cc.bf16_quantum(t[t != 0]).min()) * cc.grid(w2l)
+        bits = cc.fp32_exact_bits(cc.conv_sum(t, w2l, g2, absolute=True) + b2.double().abs(), unit)
+        share = float(cc.silu_rounding(pre2)[2].double().mean())
+        print(f"{case[0]}: smallest quantum of t 2^{torch.log2(cc.bf16_quantum(t[t != 0]).min()).item():.0f}, stage 2 needs {bits:.1f} bits, "
+              f"pre2 in [{pre2.min().item():.1f}, {pre2.max().item():.1f}] (std {pre2.std().item():.1f}), either-neighbour share {share:.2e}")
+        assert bits < 24 and share <= cc.NEAR_CAP == 2e-3
+
+
+def test_c3_pair_reference_refuses_a_draw_that_is_not_exact():
+    """the asserted conditions bite: a stage-1 value at a rounding midpoint of SiLU, and stage-2 weights on too fine a grid"""
+    case = _c3_case("c32_one_tile_exact")
+    x, w1l, b1, w2l, b2 = (v.double() for v in _c3_draw(case, True))
+    with pytest.raises(AssertionError, match=r"\(b\)"):
+        cc.reference_c3_pair(x, w1l, b1, w2l * (1 + 2.0 ** -7) * 2.0 ** -12, b2, 0, True)
+    # a bias on the 2^-20 grid whose SiLU lies at the bf16 midpoint 1 + 2^-8 (bisection on v), with w1 scaled to 2^-20 so that
+    # stage 1 stays exact in fp32: wherever a pixel's six inputs are all zero the pre-activation is that bias
+    lo, hi = torch.tensor(1.0, dtype=torch.float64), torch.tensor(2.0, dtype=torch.float64)
+    for _ in range(60):
+        mid = (lo + hi) / 2
+        lo, hi = (mid, hi) if cc.silu64(mid) < 1 + 2.0 ** -8 else (lo, mid)
+    v = torch.round(lo * 2.0 ** 20) * 2.0 ** -20
+    assert bool(cc.silu_rounding(v)[2])
+    with pytest.raises(AssertionError, match=r"\(a\)"):
+        cc.reference_c3_pair(x, w1l * 2.0 ** -19, torch.full_like(b1, float(v)), w2l, b2, 0, True)
+
+
+def test_pw_chain_reference_against_torch():
+    """reference_pw_chain against F.conv2d composed by hand: y = relu(rnd(rnd(conv3 + b3) + res)), t1 = rnd(relu(conv1(y) + b1)), a
+    residual of both signs, biases wide enough that both of y's roundings round"""
+    t2, res = ints((2, 5, 7, 128), 2, 100), ints((2, 5, 7, 512), 8, 101)
+    w3, w1 = ints((512, 128), 1, 102), ints((128, 512), 1, 103)
+    b3, b1 = ints((512,), 400, 104), ints((128,), 3, 105)
+    v = rnd(torch_conv(t2, w3[:, None, None, :]) + b3)
+    y_want = F.relu(rnd(v + res))
+    t1_want = rnd(F.relu(torch_conv(y_want, w1[:, None, None, :]) + b1))
+    y, t1 = cc.reference_pw_chain(t2, res, w3, b3, w1, b1)
+    assert torch.equal(y, y_want) and torch.equal(t1, t1_want)
+    assert bool((res > 0).any()) and bool((res < 0).any()) and 0.2 < float((y == 0).double().mean()) < 0.8
+    assert not torch.equal(y, F.relu(rnd(torch_conv(t2, w3[:, None, None, :]) + b3 + res)))     # the two roundings are seen
+    (yv, ey), (tv, et) = cc.reference_pw_chain(t2, res, w3, b3, w1, b1, exact=False)
+    assert torch.equal(yv, F.relu(torch_conv(t2, w3[:, None, None, :]) + b3 + res)) and bool((ey > 0).all()) and bool((et > 0).all())
+    assert torch.equal(tv, F.relu(torch_conv(yv, w1[:, None, None, :]) + b1))
+
+
+def _f32conv(t, w, p=0):
+    """fp32 F.conv2d of NHWC t (float64 values that fp32 holds) with a [cout, kh, kw, cin] weight, zero padding p -> float64"""
+    return nhwc(F.conv2d(F.pad(nchw(t).float(), (p,) * 4), w.permute(0, 3, 1, 2).float())).double()
+
+
+def test_gaussian_chain_bound_holds_for_an_fp32_c3_pair_and_pw_chain():
+    """the propagated bounds of reference_c3_pair and reference_pw_chain against the chains computed in fp32 with bf16 rounding points"""
+    g = torch.Generator().manual_seed(110)
+    silu32 = lambda v: F.silu(v.float()).double()
+    for c, sc in ((32, True), (128, True), (64, False)):
+        x = torch.randn((1, 6, 7, c + 16), generator=g).to(BF).double()
+        w1, w2 = ((torch.randn(s, generator=g) / k ** 0.5).to(BF).double() for s, k in (((c, c), c), ((c, 3, 3, c), 9 * c)))
+        b1, b2 = torch.randn((c,), generator=g).float(), torch.randn((c,), generator=g).float()
+        xs = x[..., 8:8 + c]
+        t = rnd(silu32(_f32conv(xs, w1[:, None, None, :]) + b1))
+        u = rnd(silu32(_f32conv(t, w2, 1) + b2))
+        y = rnd(u + xs) if sc else u
+        want, bound = cc.reference_c3_pair(x, w1, b1, w2, b2, 8, sc, exact=False)
+        assert ((y - want).abs() <= bound).all(), c
+    t2, res = torch.randn((1, 5, 6, 128), generator=g).to(BF).double(), torch.randn((1, 5, 6, 512), generator=g).to(BF).double()
+    w3, w1 = ((torch.randn(s, generator=g) / s[1] ** 0.5).to(BF).double() for s in ((512, 128), (128, 512)))
+    b3, b1 = torch.randn((512,), generator=g).float(), torch.randn((128,), generator=g).float()
+    y = F.relu(rnd(rnd(_f32conv(t2, w3[:, None, None, :]) + b3) + res))
+    t1 = rnd(F.relu(_f32conv(y, w1[:, None, None, :]) + b1))
+    (yv, ey), (tv, et) = cc.reference_pw_chain(t2, res, w3, b3, w1, b1, exact=False)
+    assert ((y - yv).abs() <= ey).all() and ((t1 - tv).abs() <= et).all()
+
+
+def _unpack_w2(w2, c, korder):
+    """the packed [C, roundup(9 C, 64)] operand read in K order `korder` -> the logical [C, 3, 3, C] weight a kernel multiplies with"""
+    w = w2[:, :9 * c]
+    return w.reshape(c, c // 64, 3, 3, 64).permute(0, 2, 3, 1, 4).reshape(c, 3, 3, c) if korder else w.reshape(c, 3, 3, c)
+
+
+def _simulated_c3_pair(x, w1, b12, w2, xo, shortcut, defect=None):
+    """md_c3_pair as a correct kernel computes it from the header's operands -- fp32 convs, fp32 SiLU, T1 zero outside the image and
+    rounded to bf16, the pre-shortcut value rounded to bf16, the shortcut added in fp32 and rounded again -> bf16 [N, H, W, C].
+    defect: 'halo' T1's pixels outside the image are silu(b1) instead of 0; 'unrounded' the intermediate stays fp32; 'single' the
+    shortcut is added before the rounding (one rounding instead of two); 'korder0' w2 is read in K order 0 whatever the width"""
+    c = w1.shape[0]
+    b1, b2 = b12[:c].float(), b12[c:].float()
+    xs = x[..., xo:xo + c].float()
+    t = F.silu(nhwc(F.conv2d(nchw(xs), w1[:, :c].float()[:, :, None, None])) + b1)
+    t = t if defect == "unrounded" else t.to(BF).float()
+    tp = F.pad(nchw(t), (1,) * 4)
+    if defect == "halo":
+        edge = torch.ones_like(tp[:, :1])
+        edge[:, :, 1:-1, 1:-1] = 0
+        tp = tp + edge * F.silu(b1).to(BF).float()[None, :, None, None]
+    korder = 0 if c == 32 or defect == "korder0" else 1
+    u = F.silu(nhwc(F.conv2d(tp, _unpack_w2(w2, c, korder).float().permute(0, 3, 1, 2))) + b2)
+    if not shortcut:
+        return u.to(BF)
+    return (u + xs).to(BF) if defect == "single" else (u.to(BF).float() + xs).to(BF)
+
+
+def _old_c3_tolerance_passes(got, x, w1l, b1, w2l, b2, xo, shortcut):
+    """the judge of test_c3_pair_equals_two_launches_and_fp32: fp32 torch with bf16-rounded intermediates, |err| <= 2e-2 |y| + 3e-2"""
+    c = w1l.shape[0]
+    xs = x[..., xo:xo + c].float()
+    t = F.silu(_f32conv(xs.double(), w1l[:, None, None, :]).float() + b1).to(BF).float()
+    want = F.silu(_f32conv(t.double(), w2l, 1).float() + b2).to(BF).float()
+    want = want + xs if shortcut else want
+    return bool(((got.float() - want).abs() <= 2e-2 * want.abs() + 3e-2).all())
+
+
+def test_c3_pair_contract_passes_a_correct_kernel_and_sees_four_defects():
+    """On the draws the GPU test makes: the simulated kernel meets the exact regime's either-neighbour rule and the Gaussian bound at
+    C = 32, 64 and 128; T1 not zeroed outside the image, an un-rounded intermediate, the shortcut added before the rounding and
+    (C = 128) K order 0 instead of 1 each fail the exact regime.  The fp32 judge of test_c3_pair_equals_two_launches_and_fp32
+    (|err| <= 2e-2 |y| + 3e-2), evaluated on the Gaussian draw, PASSES the un-rounded intermediate and the single rounding: it is
+    several bf16 ulps wide at outputs of order 1, which is why the contract tests exist."""
+    from tests.conv_checks import check, check_silu
+
+    def exact_fails(case, defect):
+        x, w1l, b1, w2l, b2 = _c3_draw(case, True)
+        _, pre2, res = cc.reference_c3_pair(x, w1l, b1, w2l, b2, case[8], case[5], exact=True)
+        w1, w2 = cc.c3_pair_weights(w1l, w2l)
+        try:
+            check_silu(_simulated_c3_pair(x, w1, torch.cat([b1, b2]), w2, case[8], case[5], defect), pre2, res)
+        except AssertionError as e:
+            return str(e)
+        return None
+
+    def gaussian(case, defect):
+        """(inside the contract's bound, inside the old fp32 tolerance)"""
+        x, w1l, b1, w2l, b2 = _c3_draw(case, False)
+        w1, w2 = cc.c3_pair_weights(w1l, w2l)
+        got = _simulated_c3_pair(x, w1, torch.cat([b1, b2]), w2, case[8], case[5], defect)
+        y, bound = cc.reference_c3_pair(x, w1l, b1, w2l, b2, case[8], case[5], exact=False)
+        return bool(((got.double() - y).abs() <= bound).all()), _old_c3_tolerance_passes(got, x, w1l, b1, w2l, b2, case[8], case[5])
+
+    for name in ("c32_ragged", "c64_offsets", "c128_offsets_no_second_half", "c128_ragged", "c64_smaller_than_a_tile"):
+        assert exact_fails(_c3_case(name), None) is None, name
+        assert gaussian(_c3_case(name), None) == (True, True), name
+    for name, defects in (("c32_ragged", ("halo", "unrounded", "single")), ("c128_offsets_no_second_half", ("halo", "unrounded", "single", "korder0"))):
+        for defect in defects:
+            why = exact_fails(_c3_case(name), defect)
+            in_bound, old_passes = gaussian(_c3_case(name), defect)
+            print(f"{name} {defect}: exact regime: {why}; Gaussian regime: {'inside' if in_bound else 'outside'} the bound; "
+                  f"the fp32 tolerance {'passes' if old_passes else 'fails'} it")
+            assert why is not None, (name, defect)
+            if defect in ("unrounded", "single"):
+                assert old_passes, (name, defect)
+
+
+def _simulated_pw_chain(t2, res, w3, b3, w1, b1, defect=None):
+    """md_pw_chain as a correct kernel computes it: fp32 GEMMs, y = relu(bf16(bf16(conv3 + b3) + res)), t1 = bf16(relu(conv1(y) + b1)).
+    defect: 'fp32_y' conv1 reads the un-rounded fp32 y; 'relu_first' ReLU is applied before the residual add"""
+    v = (t2.float() @ w3.float().t() + b3.float())
+    if defect == "relu_first":
+        y = (F.relu(v.to(BF).float()) + res.float()).to(BF)
+    else:
+        y = F.relu((v.to(BF).float() + res.float()).to(BF))
+    y_in = F.relu(v + res.float()) if defect == "fp32_y" else y.float()
+    return y, F.relu(y_in @ w1.float().t() + b1.float()).to(BF)
+
+
+def test_pw_chain_contract_passes_a_correct_kernel_and_sees_two_defects():
+    """the draw of test_pw_chain_gpu's exact regime (every second channel of b3 wide, so that y's roundings round) and a Gaussian one:
+    the simulated kernel is bit-equal / within the bounds; conv1 on the un-rounded fp32 y and ReLU before the residual add each fail
+    the exact regime"""
+    from tests.conv_checks import Data, check
+
+    d = Data(True, 7001, "cpu")
+    t2, res = d.act((1, 5, 7, 128)), d.act((1, 5, 7, 512), hi=8)
+    w3, w1, b3, b1 = d.weight((512, 128), 128), d.weight((128, 512), 512), d.bias(512, 512), d.bias(128, 128)
+    b3[1::2] = torch.randint(-400, 401, (256,), generator=d.g).float()
+    y_ref, t1_ref = cc.reference_pw_chain(t2, res, w3, b3, w1, b1)
+    y, t1 = _simulated_pw_chain(t2, res, w3, b3, w1, b1)
+    check(y, y_ref, True)
+    check(t1, t1_ref, True)
+    y, t1 = _simulated_pw_chain(t2, res, w3, b3, w1, b1, "fp32_y")
+    check(y, y_ref, True)                                     # y itself is right: only t1 can show this defect
+    with pytest.raises(AssertionError, match="outputs differ"):
+        check(t1, t1_ref, True)
+    y, t1 = _simulated_pw_chain(t2, res, w3, b3, w1, b1, "relu_first")
+    with pytest.raises(AssertionError, match="outputs differ"):
+        check(y, y_ref, True)
+    d = Data(False, 7002, "cpu")
+    t2, res = d.act((1, 5, 7, 128)), d.act((1, 5, 7, 512))
+    w3, w1, b3, b1 = d.weight((512, 128), 128), d.weight((128, 512), 512), d.bias(512, 512), d.bias(128, 128)
+    y, t1 = _simulated_pw_chain(t2, res, w3, b3, w1, b1)
+    ref_y, ref_t1 = cc.reference_pw_chain(t2, res, w3, b3, w1, b1, exact=False)
+    ry, rt = check(y, ref_y, False), check(t1, ref_t1, False)
+    n, h, w, _ = t2.shape
+    r1 = check(t1, cc.conv_stage(y.double(), 0.0, w1[:, None, None, :], b1, cc._plain(n, h, w, 512, 1, 1, 0, 128), 1), False)
+    print(f"correct kernel, Gaussian regime: worst err / bound y {ry:.3f}, t1 {rt:.3f} (chain), {r1:.3f} (on its own y)")

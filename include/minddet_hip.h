@@ -17,7 +17,11 @@
  *     workspace buffer (dtype "uint8") may follow the outputs -- when absent the op uses the
  *     library's scratch pool: ONE buffer per (device, stream), grown on demand and reused by
  *     every later call on that stream (no driver call in the steady state; md_scratch_release
- *     frees it).
+ *     frees it).  How many bytes an op takes has ONE owner: the host function
+ *     int64_t md_<op>_workspace_bytes(int64_t extent, ...) declared under the op.  It makes no
+ *     device or runtime call, returns -1 for a negative extent, and is the number the op itself
+ *     holds a caller's workspace to (a smaller one -> 4).  A caller sizes its buffer by asking it;
+ *     the formulas in the comments are upper bounds for readers who cannot.
  *   - every pointer in params[] is DEVICE memory owned by the caller; outputs are fixed
  *     shape and padded (keep[N] has `num` valid leading entries, the rest 0 --
  *     iou-bev-nms-org.cpp:247-249,274-281).
@@ -150,12 +154,15 @@ typedef struct md_nms_attrs {
  * in : boxes[B,N,4] f32 (or [N,4]), count[B] i32 (valid leading boxes per list, clamped to [0, N]; may be a
  *      NULL pointer = all N), group[B,N] i32 (class / task key: boxes with different keys
  *      never suppress each other; may be a NULL pointer)
- * out: keep_mask[B,N] u8, keep_idx[B,N] i32 (leading num valid, rest 0), num[B] i32
+ * out: keep_mask[B,N] u8, keep_idx[B,N] i32 (leading num valid, rest 0), num[B] i32 ; [workspace u8:
+ *      md_nms_aligned_workspace_bytes(B, N, max_output) bytes; never more than 8 B N ceil(N / 64) + 4 B + 252; a workspace of the
+ *      leading 8 B N ceil(N / 64) bytes (the suppression mask) alone is accepted too and runs the single full pass]
  * extra: md_nms_attrs (required).  With max_output = q > 0 the list is cut right after its q-th kept box.  No dead-area rule: a
  * zero-area box is kept unless a kept box suppresses it, and whether coincident ones do follows from the mode: mode 0 with
  * eps 0 sees 0/0 = NaN and mode 2 sees 0 / 1e-8 = 0 (all kept); mode 1 (+1 pixel), and mode 0 with eps > 0, give such a box a
  * positive area, coincident ones have ovr 1 and only the first is kept.  NaN rule above. */
 int md_nms_aligned(MD_AOT_ARGS);
+int64_t md_nms_aligned_workspace_bytes(int64_t B, int64_t n, int64_t max_output);
 
 typedef struct md_soft_nms_attrs {
     float sigma, Nt, threshold; /* reference call: sigma 0.5 (default), Nt 0.5, threshold 0.001 */
@@ -611,11 +618,13 @@ typedef struct md_topk_attrs {
                             than max_segment is still selected exactly, by the slower global-memory passes */
 } md_topk_attrs;
 /* in scores[T] f32, seg_off[L+1] i32 ; out values[L,k] f32 (padded -FLT_MAX), indices[L,k] i32
- * (relative to the segment, padded 0), count[L] i32 ; optional workspace
- * (L*(2048*4+4) rounded up to 256, + L*8192*8 bytes) for the multi-workgroup path.
+ * (relative to the segment, padded 0), count[L] i32 ; optional workspace u8 of
+ * md_topk_segmented_workspace_bytes(L, k, max_segment) bytes: 0 where a single-workgroup form runs (no workspace is looked
+ * at), else at least L*(2048*4+4) rounded up to 256, + L*8192*8 bytes for the multi-workgroup path.
  * Order: descending, ties to the lower index; -0.0 and +0.0 are one value (a -0.0 is returned as +0.0).
  * NaN scores have no specified order. */
 int md_topk_segmented(MD_AOT_ARGS);
+int64_t md_topk_segmented_workspace_bytes(int64_t L, int64_t k, int64_t max_segment);
 /* Diagnostic: the form the calling thread's last md_topk_segmented call launched -- 0 none (an error or L == 0),
  * 1 one workgroup per segment, 2 LDS-staged, 3 multi-workgroup. */
 int md_topk_last_path(void);

@@ -29,7 +29,8 @@ typedef struct md_cn_targets_attrs {
  *      two affine_transform calls, dataset.py:339-342, before the clip), classes[B,G] i32 (the reference's 1-based category_id; < 1 or
  *      > C: a padding row, skipped), G <= M
  * out: hm[B,C,H,W] f32, ind[B,M] i32, reg_mask[B,M] u8, wh[B,M,2] f32, reg[B,M,2] f32 -- every element written, zeros included ;
- *      [workspace u8, 16-byte aligned: at least 16 B M bytes; without it the library's per-stream scratch pool serves]
+ *      [workspace u8, 16-byte aligned: md_cn_assign_targets_workspace_bytes(B, M) bytes, at least 16 B M; without it the library's
+ *      per-stream scratch pool serves]
  * extra: md_cn_targets_attrs, required.  C, H, W, M from the shapes; H, W >= 1.
  *
  * Per row k (dataset.py:343-359 as written, fp32 unless said otherwise):
@@ -45,6 +46,7 @@ typedef struct md_cn_targets_attrs {
  * 2: G > M, an extent other than documented, H or W < 1, min_overlap outside (0, 1) or not finite, a workspace that is not 16-byte aligned.
  * 4: M > MD_CN_MAX_OBJS, an operand of 2^30 elements or more, B or C > 65535, a workspace smaller than documented. */
 int md_cn_assign_targets(MD_AOT_ARGS);
+int64_t md_cn_assign_targets_workspace_bytes(int64_t B, int64_t M);
 
 typedef struct md_cn_loss_attrs {
     int32_t num_classes;                      /* C */
@@ -58,8 +60,9 @@ typedef struct md_cn_loss_attrs {
  *      outputs of md_cn_assign_targets)
  * out: parts[3] f32 (hm_loss, wh_loss, off_loss), num_pos[1] f32, total[1] f32 ;
  *      md_cn_loss_grad only: grad[B,H,W,Cp] f32 = d total / d head, every element written ;
- *      [workspace u8, 8-byte aligned: at least 8 B (4 + 2 ceil(H W / MD_CN_LOSS_STRIP)) + 4 ceil(B C H W / MD_CN_LOSS_COUNT_CHUNK)
- *      bytes; without it the library's per-stream scratch pool serves]
+ *      [workspace u8, 8-byte aligned: md_cn_loss_workspace_bytes(B, C, H, W) bytes (one function for both entry points), at least
+ *      8 B (4 + 2 ceil(H W / MD_CN_LOSS_STRIP)) + 4 ceil(B C H W / MD_CN_LOSS_COUNT_CHUNK); without it the library's per-stream
+ *      scratch pool serves]
  * extra: md_cn_loss_attrs, required.  B, H, W >= 1.
  *
  * As real-valued math on the given bf16 and fp32 values.  Arithmetic: every per-element term and every sum is evaluated in float64
@@ -85,6 +88,7 @@ typedef struct md_cn_loss_attrs {
  *    documented. */
 int md_cn_loss(MD_AOT_ARGS);      /* forward only */
 int md_cn_loss_grad(MD_AOT_ARGS); /* forward + d total / d head, in the same passes */
+int64_t md_cn_loss_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W);
 
 #ifdef __cplusplus
 }

@@ -81,8 +81,9 @@ typedef struct md_cn_aug_image_attrs {
  *      the index 0..5 of the permutation in lexicographic order with 0 = brightness_, 1 = contrast_, 2 = saturation_:
  *      0 = (b, c, s), 1 = (b, s, c), 2 = (c, b, s), 3 = (c, s, b), 4 = (s, b, c), 5 = (s, c, b).  NULL: no colour augmentation
  * out: y[B, pad_lo + out_h + pad_hi, pad_lo + out_w + pad_hi, C = 4 | 8] bf16, md_image_preprocess's output layout; the border and the
- *      spare channels are exactly +0 ; [workspace u8, 8-byte aligned: 8 B ((out_h out_w + 2047) / 2048 + 1) bytes suffice; without it
- *      the library's per-stream scratch pool serves; not touched when colour is NULL]
+ *      spare channels are exactly +0 ; [workspace u8, 8-byte aligned: md_cn_aug_image_workspace_bytes(B, out_h, out_w) bytes; never more
+ *      than 8 B ((out_h out_w + 2047) / 2048 + 1); without it the library's per-stream scratch pool serves; not touched when colour
+ *      is NULL]
  * extra: md_cn_aug_image_attrs, required.
  * Per output pixel of the image area:
  *   1. v[c] = the fp32 bilinear sample in grey levels, exactly md_image_preprocess's (csrc/image_sample.h)
@@ -99,6 +100,7 @@ typedef struct md_cn_aug_image_attrs {
  * 2: an extent other than documented, C not 4 or 8, a workspace that is not 8-byte aligned, an output that shares its address with an
  * input.  4: an operand of 2^30 elements or more, B > MD_CNAUG_MAX_BATCH, a workspace smaller than documented. */
 int md_cn_aug_image(MD_AOT_ARGS);
+int64_t md_cn_aug_image_workspace_bytes(int64_t B, int64_t out_h, int64_t out_w);
 
 #ifdef __cplusplus
 }

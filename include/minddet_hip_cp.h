@@ -34,8 +34,9 @@ typedef struct md_nms_rotated_attrs {
  * 267-372, iou3d_nms.cpp:102-133) or boxes_iou_nms_gpu (centerpoint/det3d_ms/ops/iou-bev-nms-org.cpp:237-283) per list, in the shape
  * of md_nms_aligned.
  * in : boxes[L,N,7] f32 (x, y, z, dx, dy, dz, heading; or [N,7], L = 1), count[L] i32 or NULL (all N rows of every list valid)
- * out: keep_idx[L,N] i32 (the leading num[l] entries are the kept rows in order, the rest 0), num[L] i32 ; [workspace u8: at least
- *      L N (20 x 4 + ceil(N / 64) x 8) bytes; without it the library's per-stream scratch pool serves]
+ * out: keep_idx[L,N] i32 (the leading num[l] entries are the kept rows in order, the rest 0), num[L] i32 ; [workspace u8:
+ *      md_nms_rotated_workspace_bytes(L, N) bytes, at least L N (20 x 4 + ceil(N / 64) x 8); without it the library's per-stream
+ *      scratch pool serves]
  * extra: md_nms_rotated_attrs, required.
  * Only the first min(count[l], N) rows of list l are read (a count <= 0 keeps nothing).  The per-pair predicate is the one the
  * single-list operators compute, so keep_idx[l, :num[l]] equals NmsGpu / boxes_iou_nms_gpu on boxes[l, :count[l]] bit for bit (cut
@@ -43,6 +44,7 @@ typedef struct md_nms_rotated_attrs {
  * 2: the last extent of boxes != 7, count / keep_idx / num not of L / L N / L elements, mode outside {0, 1}, max_output < 0.
  * 4: N > 65536 or L > 65535, a workspace smaller than documented. */
 int md_nms_rotated(MD_AOT_ARGS);
+int64_t md_nms_rotated_workspace_bytes(int64_t L, int64_t n);
 
 typedef struct md_cp_task_attrs {
     int32_t off_reg, off_height, off_dim, off_rot; /* first channel of the task's reg (2), height (1), dim (3), rot (2) heads */

@@ -52,19 +52,22 @@ typedef struct md_cp_count_attrs {
  * in : points[N,F] f32, F = 5 (the B samples back to back); offsets[B+1] i32 (as md_voxelize takes them); gt_boxes[B,G,9] f32;
  *      gt_count[B] i32 (a count outside [0, G] is clamped)
  * out: counts[B,G] i32 (0 for g >= gt_count[b]); keep[B,G] u8 = g < gt_count[b] and (min_points <= 0 or counts >= min_points) ;
- *      [workspace u8: 96 B G bytes suffice; without it the library's per-stream scratch pool serves]
+ *      [workspace u8: md_cp_aug_count_points_workspace_bytes(B, G) bytes; never more than 96 B G; without it the library's per-stream
+ *      scratch pool serves]
  * extra: md_cp_count_attrs, required.
  * Inside: with (dx, dy, dz) = p - (x, y, z) and (lx, ly) = (dx cos r - dy sin r, dx sin r + dy cos r): |lx| < w / 2, |ly| < l / 2 and
  * |dz| < h / 2, all strict.  A point before offsets[0] or from offsets[B] on belongs to no sample.
  * 2: F != 5, an extent other than documented.  4: N >= 2^30, G > MD_CPAUG_MAX_GT, B > MD_CPAUG_MAX_BATCH, a workspace smaller than
  * documented. */
 int md_cp_aug_count_points(MD_AOT_ARGS);
+int64_t md_cp_aug_count_points_workspace_bytes(int64_t B, int64_t G);
 
 /* The accept step of sample_class_v2 (sample_ops.py:245-291) as sample_all drives it (:127-154), enable_global_rot false.
  * in : gt_boxes[B,G,9] f32, gt_count[B] i32, keep[B,G] u8 (md_cp_aug_count_points'), cand_boxes[B,S,9] f32 (the drawn database boxes
  *      in draw order), cand_count[B] i32 (clamped to [0, S]), cand_group[B,S] i32 (non-decreasing per sample; one value stands for
  *      one sample_class_v2 call)
- * out: accept[B,S] u8 (0 for s >= cand_count[b]) ; [workspace u8: 8 B S ((G + S + 63) / 64) bytes suffice; else the pool]
+ * out: accept[B,S] u8 (0 for s >= cand_count[b]) ; [workspace u8: md_cp_aug_select_workspace_bytes(B, G, S) bytes; never more
+ *      than 8 B S ((G + S + 63) / 64); else the pool]
  * For each group in order: the matrix of box_collision_test over the avoid list (the kept ground-truth rows, then the candidates
  * accepted in earlier groups) followed by the group's candidates, the diagonal cleared; the group's candidates are walked in order: a
  * candidate whose row has a live column is rejected and its row and column are cleared, any other is accepted (quirk (c)).  BEV
@@ -73,20 +76,22 @@ int md_cp_aug_count_points(MD_AOT_ARGS);
  * 2: an extent other than documented.  4: G > MD_CPAUG_MAX_GT, S > MD_CPAUG_MAX_CAND, B > MD_CPAUG_MAX_BATCH, a workspace smaller than
  * documented. */
 int md_cp_aug_select(MD_AOT_ARGS);
+int64_t md_cp_aug_select_workspace_bytes(int64_t B, int64_t G, int64_t S);
 
 /* The point side of sample_all's result (:168-185, without rot_transform), np.concatenate([sampled_points, points]) and the point
  * side of the four global steps, as one stable compaction.
  * in : points[N,F] f32, F = 5; offsets[B+1] i32; cand_points[Ns,F] f32 (every candidate's points in its own frame, as the database file
  *      holds them, candidate after candidate), cand_offsets[B S + 1] i32, cand_boxes[B,S,9] f32, accept[B,S] u8 -- NULL all four or
  *      none (then Ns = 0); global[B,7] f64
- * out: points_out[N+Ns,F] f32, offsets_out[B+1] i32 ; [workspace u8: 64 B + (N + Ns) + 4 ((N + Ns) / 256 + 3) bytes suffice; else
- *      the pool]
+ * out: points_out[N+Ns,F] f32, offsets_out[B+1] i32 ; [workspace u8: md_cp_aug_points_workspace_bytes(N, Ns, B) bytes; never more than
+ *      64 B + (N + Ns) + 4 ((N + Ns) / 256 + 3); else the pool]
  * Per sample the output holds the accepted candidates' points in candidate order, each plus its box centre (x, y, z), then the scene
  * points in their order; then flip_a, flip_b, the rotation, the scale and the translation on columns 0-2.  Columns 3 and up pass
  * through bit for bit.  The samples sit back to back, zero rows behind the last kept row.
  * 2: F != 5, an extent other than documented, candidate operands given in part.  4: N + Ns >= 2^30, S > MD_CPAUG_MAX_CAND,
  * B > MD_CPAUG_MAX_BATCH, a workspace smaller than documented. */
 int md_cp_aug_points(MD_AOT_ARGS);
+int64_t md_cp_aug_points_workspace_bytes(int64_t N, int64_t Ns, int64_t B);
 
 typedef struct md_cp_boxes_attrs {
     float bv_range[4]; /* x min, y min, x max, y max of the training range; finite */

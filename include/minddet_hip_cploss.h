@@ -32,7 +32,8 @@ typedef struct md_cp_loss_attrs {
  *      md_cp_assign_targets; C = the largest num_classes)
  * out: parts[T,12] f32 (per task hm_loss, loc_loss, box_loss[10]), num_pos[T] f32, total[1] f32 ;
  *      md_cp_loss_grad only: grad[B,H,W,Cp] f32 = d total / d head, every element written (zeros and padding channels included) ;
- *      [workspace u8: at least 8 B T (12 + ceil(H W / MD_CP_LOSS_STRIP)) bytes; without it the library's per-stream scratch pool serves]
+ *      [workspace u8: md_cp_loss_workspace_bytes(B, T, H, W) bytes (one function for both entry points), at least
+ *      8 B T (12 + ceil(H W / MD_CP_LOSS_STRIP)); without it the library's per-stream scratch pool serves]
  * extra: md_cp_loss_attrs, required.  B, H, W >= 1.
  *
  * Per task t, as real-valued math on the given bf16 and fp32 values.  Arithmetic: every per-element term and every sum is evaluated
@@ -64,6 +65,7 @@ typedef struct md_cp_loss_attrs {
  *    documented. */
 int md_cp_loss(MD_AOT_ARGS);      /* forward only */
 int md_cp_loss_grad(MD_AOT_ARGS); /* forward + d total / d head, in the same passes */
+int64_t md_cp_loss_workspace_bytes(int64_t B, int64_t T, int64_t H, int64_t W);
 
 #ifdef __cplusplus
 }

@@ -46,7 +46,8 @@ typedef struct md_cp_sweeps_attrs {
  *      transforms[B,S,12] f64: rows 0-2 of the 4x4, row-major; time_lag[B,S] f64;
  *      seg_flags[B,S] i32: bit 0 = apply remove_close, bit 1 = apply the transform; the other bits are reserved, 0, and not read
  * out: points_out[M,5] f32, M >= N; offsets_out[B+1] i32; status[B] i32 ;
- *      [workspace u8: 4 (N / 256 + B S + 3) bytes suffice; without it the library's per-stream scratch pool serves]
+ *      [workspace u8: md_cp_sweeps_merge_workspace_bytes(N, B, S) bytes, never more than the 4 (N / 256 + B S + 3) bytes that
+ *      always suffice; without it the library's per-stream scratch pool serves]
  * extra: md_cp_sweeps_attrs, required.
  * Per sample, per segment in the listed order, per row in row order: with bit 0 the row is dropped if fabsf(x) < radius &&
  * fabsf(y) < radius on the untransformed fp32 values, both strict (a NaN coordinate compares false: the row is kept, as in numpy).
@@ -61,6 +62,7 @@ typedef struct md_cp_sweeps_attrs {
  * the address of an input or of another output.  4: N or M >= 2^30, S > MD_CPSWEEPS_MAX_SWEEPS, B > MD_CPSWEEPS_MAX_BATCH, a
  * workspace smaller than documented. */
 int md_cp_sweeps_merge(MD_AOT_ARGS);
+int64_t md_cp_sweeps_merge_workspace_bytes(int64_t N, int64_t B, int64_t S);
 
 #ifdef __cplusplus
 }

@@ -32,8 +32,8 @@ typedef struct md_cp_targets_attrs {
  * in : gt_boxes[B,G,9] f32 (x, y, z, w, l, h, vx, vy, rot), gt_classes[B,G] i32 (global 1-based class; 0, a negative id or an id past
  *      the last task's classes: a padding row that belongs to no task)
  * out: hm[B,T,C,H,W] f32 (C = the largest num_classes; row = y, column = x), anno_box[B,T,M,10] f32, ind[B,T,M] i32, mask[B,T,M] u8,
- *      cat[B,T,M] i32, gt_boxes_and_cls[B,M,10] f32 ; [workspace u8: at least B T (G + 1) x 16 bytes; without it the library's
- *      per-stream scratch pool serves]
+ *      cat[B,T,M] i32, gt_boxes_and_cls[B,M,10] f32 ; [workspace u8: md_cp_assign_targets_workspace_bytes(B, T, G) bytes, at least
+ *      B T (G + 1) x 16; without it the library's per-stream scratch pool serves]
  * extra: md_cp_targets_attrs, required.  M = max_objs and the feature map H x W are taken from the shapes.
  * Every element of every output is written (zeros included): the caller clears nothing.
  *
@@ -61,6 +61,7 @@ typedef struct md_cp_targets_attrs {
  * 4: G > MD_CP_TARGETS_MAX_GT (the rows of a sample are staged in LDS), an operand of 2^30 elements or more, B or T C > 65535,
  *    a workspace smaller than documented. */
 int md_cp_assign_targets(MD_AOT_ARGS);
+int64_t md_cp_assign_targets_workspace_bytes(int64_t B, int64_t T, int64_t G);
 
 #ifdef __cplusplus
 }

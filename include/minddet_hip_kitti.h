@@ -46,8 +46,8 @@ extern "C" {
  *      near rectangle, then the far one); hull_count[B] i32, clamped to [0, K]
  * out: points_out[N,4] f32 (each sample's kept points in their order, the samples back to back, zero rows behind the last kept point),
  *      offsets_out[B+1] i32, keep[N] u8 indexed like the input (1 kept; 0 dropped, or a point before offsets[0] or from offsets[B] on,
- *      which belongs to no sample) ; [workspace u8: 192 B K + 4 (N / 256 + 3) bytes suffice; without it the library's per-stream
- *      scratch pool serves]
+ *      which belongs to no sample) ; [workspace u8: md_pc_crop_hulls_workspace_bytes(N, B, K) bytes, never more than the
+ *      192 B K + 4 (N / 256 + 3) bytes that always suffice; without it the library's per-stream scratch pool serves]
  * Planes: surface j of a hull takes the corners 0 1 2 3 / 7 6 5 4 / 0 3 7 4 / 1 5 6 2 / 0 4 5 1 / 3 2 6 7; from its first three
  * corners s0, s1, s2 (surface_equ_3d_jit, geometry.py:7-15): n = (s0 - s1) x (s1 - s2), d = -((n0 s0x + n1 s0y) + n2 s0z).
  * A point is outside a hull iff sign = ((px n0 + py n1) + pz n2) + d >= 0 for one of the six surfaces (geometry.py:46-54), so inside
@@ -57,6 +57,7 @@ extern "C" {
  * 2: an extent other than documented, F != 4, an output at the address of an input or of another output.  4: N >= 2^30,
  * K > MD_CROP_MAX_HULLS, B > MD_CROP_MAX_BATCH, a workspace smaller than documented. */
 int md_pc_crop_hulls(MD_AOT_ARGS);
+int64_t md_pc_crop_hulls_workspace_bytes(int64_t N, int64_t B, int64_t K);
 
 /* box_camera_to_lidar (box_np_ops.py:599-613) for a batch of label rows.
  * in : boxes_cam[B,G,7] f32 (x, y, z, l, h, w, r in the rectified camera frame), gt_count[B] i32 (clamped to [0, G]),

@@ -66,8 +66,8 @@ int md_pc_noise_per_object(MD_AOT_ARGS);
  *      global[B,6] f64 = (flip 0 / 1, rotation, scale, tx, ty, tz)
  * out: points_out[N,4] f32 (each sample's kept points in their order, the samples back to back, zero rows behind the last kept point),
  *      offsets_out[B+1] i32, owner[N] i32 indexed like the input (the first VALID box g < gt_count[b] that contains the point: only
- *      that box's transform is applied, :434-441; -1: none; -2: dropped) ; [workspace u8: 128 B (G + R) + 64 B + 4 (N / 256 + 3)
- *      bytes suffice; without it the library's per-stream scratch pool serves]
+ *      that box's transform is applied, :434-441; -1: none; -2: dropped) ; [workspace u8: md_pc_augment_points_workspace_bytes(N, B, G, R) bytes; never
+ *      more than 128 B (G + R) + 64 B + 4 (N / 256 + 3); without it the library's per-stream scratch pool serves]
  * A point of sample b whose index within the sample is >= remove_from[b] and which lies in one of the first remove_count[b] remove
  * boxes is dropped (the points in front are the sampled objects' own, data/preprocess.py:124-127).  A point before offsets[0] or from
  * offsets[B] on belongs to no sample and is dropped.
@@ -79,6 +79,7 @@ int md_pc_noise_per_object(MD_AOT_ARGS);
  * 2: F != 4, an extent other than documented, remove operands given in part.  4: N >= 2^30, G or R > MD_PCAUG_MAX_BOXES,
  * B > MD_PCAUG_MAX_BATCH, a workspace smaller than documented. */
 int md_pc_augment_points(MD_AOT_ARGS);
+int64_t md_pc_augment_points_workspace_bytes(int64_t N, int64_t B, int64_t G, int64_t R);
 
 typedef struct md_pc_boxes_attrs {
     float bv_range[4]; /* x min, y min, x max, y max of the training range; finite */

@@ -22,7 +22,8 @@ typedef struct md_voxelize_attrs {
  * in : points[N,F] f32, F = 4 or 5 (x, y, z first), the B samples back to back; offsets[B+1] i32 (sample b = points
  *      [offsets[b], offsets[b+1]); device memory, non-decreasing, within [0, N])
  * out: voxels[B,max_voxels,max_points,F] f32, coors[B,max_voxels,4] i32 = (b, z, y, x), num_points[B,max_voxels] i32,
- *      voxel_num[B] i32 [, workspace u8: 4 * (2 B gx gy gz + 3 N + 2 B max_voxels + (N + B max_voxels) / 1024) + 4096 bytes suffice].
+ *      voxel_num[B] i32 [, workspace u8: md_voxelize_workspace_bytes(N, B, gx gy gz, max_voxels) bytes; never more than
+ *      4 * (2 B gx gy gz + 3 N + 2 B max_voxels + (N + B max_voxels) / 1024) + 4096].
  * extra: md_voxelize_attrs, required.  The grid is nearbyint((max - min) / voxel_size) cells per axis, computed in fp32 (:24-27).
  * The result equals the reference's sequential loop bit for bit: a point's cell is floor((p - min) / voxel_size) per axis with an
  * fp32 subtract and a correctly rounded fp32 divide; the point is dropped if any axis is outside [0, grid); voxels are numbered in the
@@ -33,6 +34,7 @@ typedef struct md_voxelize_attrs {
  * 2: F not 4 or 5, output shapes that do not match each other or the attributes, voxel_size <= 0, max <= min, a non-finite attribute.
  * 4: N, B x cells or B x max_voxels >= 2^30, B > 4096, max_points > 65536. */
 int md_voxelize(MD_AOT_ARGS);
+int64_t md_voxelize_workspace_bytes(int64_t N, int64_t B, int64_t cells, int64_t max_voxels);
 
 typedef struct md_pillar_encode_attrs {
     float vx, vy;             /* voxel_size x, y (pillar_encoder.py:123-124) */

@@ -37,8 +37,9 @@ typedef struct md_pp_loss_attrs {
  *      f32, anchors[N,7] f32 ; N = H W A, anchor n = (y W + x) A + a
  * out: parts[5] f32 = (loc, cls, dir as they enter the total, cls_pos, cls_neg), num_pos[B] f32, total[1] f32 ;
  *      md_pp_loss_grad only: grad[B,H,W,C] f32 = d total / d head, every element written (zeros and padding channels included) ;
- *      [workspace u8: at least 40 B ceil(H W / MD_PP_LOSS_STRIP) + 4 B ceil(N / MD_PP_LOSS_COUNT_CHUNK) bytes, 8-byte aligned; without
- *      it the library's per-stream scratch pool serves]
+ *      [workspace u8, 8-byte aligned: md_pp_loss_workspace_bytes(B, H, W, A) bytes (one function for both entry points), at least
+ *      40 B ceil(H W / MD_PP_LOSS_STRIP) + 4 B ceil(N / MD_PP_LOSS_COUNT_CHUNK); without it the library's per-stream scratch pool
+ *      serves]
  * extra: md_pp_loss_attrs, required.  B, H, W >= 1.  K = num_classes, A = num_anchors.
  *
  * As real-valued math on the given bf16 and fp32 values.  Arithmetic: every per-element term and every sum is evaluated in float64
@@ -72,6 +73,7 @@ typedef struct md_pp_loss_attrs {
  *    B > 65535, a workspace smaller than documented. */
 int md_pp_loss(MD_AOT_ARGS);      /* forward only */
 int md_pp_loss_grad(MD_AOT_ARGS); /* forward + d total / d head, in the same passes */
+int64_t md_pp_loss_workspace_bytes(int64_t B, int64_t H, int64_t W, int64_t num_anchors);
 
 #ifdef __cplusplus
 }

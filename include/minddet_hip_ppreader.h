@@ -54,7 +54,8 @@ int md_pp_pillar_encode(MD_AOT_ARGS);
 /* The anchor mask of pointpillars/src/data/preprocess.py:211-225 + core/box_np_ops.py:745-776 for a whole batch, with the number of
  * voxels of each sample read on the device.
  * in : coors[B,MV,4] i32 (b, z, y, x), voxel_num[B] i32 (md_voxelize's outputs), anchors_bv[N,4] f32
- * out: mask[B,N] u8 [, area[B,N] f32 or NULL] [, workspace u8: B * grid_y * grid_x * 4 bytes]
+ * out: mask[B,N] u8 [, area[B,N] f32 or NULL] [, workspace u8: md_pp_anchor_mask_workspace_bytes(B, grid_x, grid_y) bytes, at
+ *      least B * grid_y * grid_x * 4]
  * extra: md_anchor_mask_attrs (minddet_hip.h), required.
  * Row b equals, bit for bit, what md_anchor_mask gives for coors[b, :clamp(voxel_num[b], 0, MV), 1:] (both entries are in
  * csrc/ppreader.hip and launch one set of kernels, md_anchor_mask with B = 1 and every row counted): the voxels are counted per
@@ -63,6 +64,7 @@ int md_pp_pillar_encode(MD_AOT_ARGS);
  * 2: coors not [B,MV,4], voxel_num not [B], anchors_bv not [N,4], mask / area not [B,N].   4: grid_x or grid_y < 1, B x cells > 2^28,
  *    B x N or B x MV >= 2^31. */
 int md_pp_anchor_mask(MD_AOT_ARGS);
+int64_t md_pp_anchor_mask_workspace_bytes(int64_t B, int64_t grid_x, int64_t grid_y);
 
 #ifdef __cplusplus
 }

@@ -58,7 +58,28 @@ def exported_symbols():
     names = re.findall(r"^\s*int\s+(\w+)\s*\(MD_AOT_ARGS\)\s*;", txt, flags=re.M)
     names += re.findall(r"^\s*const char \*(\w+)\s*\(void\)\s*;", txt, flags=re.M)
     names += re.findall(r"^\s*int\s+(\w+)\s*\(void\)\s*;", txt, flags=re.M)
+    names += re.findall(r"^\s*int64_t\s+(\w+_workspace_bytes)\s*\((?:int64_t \w+(?:, )?)+\)\s*;", txt, flags=re.M)
     return names
+
+
+def workspace_bytes(op, *dims):
+    """Bytes of scratch entry point `op` takes for the given extents: the library's own answer (<op>_workspace_bytes, declared under
+    the op in its header), never arithmetic on this side."""
+    fn = getattr(lib(), op + "_workspace_bytes")
+    fn.restype = ctypes.c_int64
+    fn.argtypes = [ctypes.c_int64] * len(dims)
+    n = fn(*[int(d) for d in dims])
+    if n < 0:
+        raise MindDetHipError(f"{op}_workspace_bytes{tuple(dims)}: a negative extent")
+    return n
+
+
+def scratch(op, dims, device):
+    """The workspace operand of `op` for the given extents, from torch's caching allocator (never blocks, unlike the library's pool
+    when it grows).  At least 16 bytes: an empty tensor has no address, and the op would take that for an absent workspace."""
+    import torch
+
+    return torch.empty((max(workspace_bytes(op, *dims), 16),), dtype=torch.uint8, device=device)
 
 
 def call(name, tensors, extra=None, stream=None):

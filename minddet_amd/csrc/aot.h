@@ -199,6 +199,15 @@ struct Scratch {
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// Scratch sizes have one owner (include/minddet_hip.h "Conventions"): per op one host function of the extents fills the byte offsets of
+// the workspace's parts and their total; the exported md_<op>_workspace_bytes returns that total (-1 for a negative extent, below) and
+// the entry point acquires and carves with the same values.
+static inline bool any_negative(std::initializer_list<int64_t> extents) {
+    for (int64_t v : extents)
+        if (v < 0) return true;
+    return false;
+}
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device) instead of once per launch: it is a driver call on the
 // launch path of every layer otherwise (r02 ADVICE; the YOLOv5s step is launch-bound) and would also run inside graph capture.
 // Cache keyed by the kernel's host address (lock-free insert; a full table or a device id >= 8 just sets the attribute again).  The

@@ -198,6 +198,13 @@ extern "C" int md_cn_aug_transform(MD_AOT_ARGS) {
     return launched();
 }
 
+// partial sums per sample of the grey pass of md_cn_aug_image: one per CNA_CHUNK output pixels
+static int64_t cn_grey_chunks(int64_t out_h, int64_t out_w) { return (out_h * out_w + CNA_CHUNK - 1) / CNA_CHUNK; }
+// scratch of md_cn_aug_image: part[B][chunks] f64 at 0, then mean[B] f64
+extern "C" int64_t md_cn_aug_image_workspace_bytes(int64_t B, int64_t out_h, int64_t out_w) {
+    return any_negative({B, out_h, out_w}) ? -1 : B * (cn_grey_chunks(out_h, out_w) + 1) * 8;
+}
+
 extern "C" int md_cn_aug_image(MD_AOT_ARGS) {
     // in : img[B,Hs,Ws,3] u8, sizes[B,2] i32, mat_in[B,6] f32, norm[6] f32, colour[B,8] f64 | NULL
     // out: y[B, pad_lo + out_h + pad_hi, pad_lo + out_w + pad_hi, C = 4 | 8] bf16 ; [workspace]
@@ -225,20 +232,21 @@ extern "C" int md_cn_aug_image(MD_AOT_ARGS) {
     hipStream_t s = (hipStream_t)stream;
     ImageArgs a;
     a.Hs = (int)Hs; a.Ws = (int)Ws; a.Ho = at->out_h; a.Wo = at->out_w; a.Hp = (int)Hp; a.Wp = (int)Wp; a.C = (int)C; a.pad_lo = at->pad_lo;
-    a.nblk = (int)(((int64_t)a.Ho * a.Wo + CNA_CHUNK - 1) / CNA_CHUNK);
+    a.nblk = (int)cn_grey_chunks(a.Ho, a.Wo);
     a.img = (const uint8_t *)params[0]; a.sizes = (const int *)params[1]; a.mat = (const float *)params[2]; a.norm = (const float *)params[3];
     a.colour = colour ? (const double *)params[4] : nullptr; a.out = (uint16_t *)params[5];
     a.part = nullptr; a.mean = nullptr;
     const dim3 grid((unsigned)((Hp * Wp + 255) / 256), (unsigned)B);
+    const int64_t need = md_cn_aug_image_workspace_bytes(B, a.Ho, a.Wo);
     Scratch ws;
     if (colour) {
-        if (int rc = ws.acquire((size_t)B * (a.nblk + 1) * 8, g, 6, s)) return rc;
+        if (int rc = ws.acquire((size_t)need, g, 6, s)) return rc;
         a.part = (double *)ws.ptr; a.mean = a.part + (size_t)B * a.nblk;
         hipLaunchKernelGGL(cn_grey_kernel, dim3((unsigned)a.nblk, (unsigned)B), dim3(256), 0, s, a);
         hipLaunchKernelGGL(cn_grey_finish_kernel, dim3((unsigned)B), dim3(256), 0, s, a);
         hipLaunchKernelGGL(cn_image_kernel<true>, grid, dim3(256), 0, s, a);
     } else {
-        if (g.given(6) && g.workspace(6) >= 0 && g.workspace(6) < (int64_t)B * (a.nblk + 1) * 8) return MD_ERR_SIZE;
+        if (g.given(6) && g.workspace(6) >= 0 && g.workspace(6) < need) return MD_ERR_SIZE;   // (no scratch is taken without colour draws)
         hipLaunchKernelGGL(cn_image_kernel<false>, grid, dim3(256), 0, s, a);
     }
     return launched();

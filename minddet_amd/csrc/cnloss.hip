@@ -212,6 +212,19 @@ __global__ __launch_bounds__(256) void cn_loss_finish_kernel(const uint16_t *__r
     }
 }
 
+// scratch of md_cn_loss and md_cn_loss_grad: rec[B][CNL_REC] f64 at 0, part[B sps][2] f64, counts[chunks] i32; sps = the strips of
+// CNL_STRIP cells per sample, chunks = the chunks of CNL_CHUNK heat-map elements of the batch
+struct CnlScratch { int64_t sps, chunks, part, counts, total; };
+static CnlScratch cn_loss_scratch(int64_t B, int64_t C, int64_t H, int64_t W) {
+    CnlScratch w;
+    w.sps = (H * W + CNL_STRIP - 1) / CNL_STRIP;
+    w.chunks = (B * C * H * W + CNL_CHUNK - 1) / CNL_CHUNK;
+    w.part = 8 * CNL_REC * B;
+    w.counts = w.part + 8 * 2 * B * w.sps;
+    w.total = w.counts + 4 * w.chunks;
+    return w;
+}
+
 static int cn_loss_entry(MD_AOT_ARGS, bool with_grad) {
     // in : head[B,H,W,Cp] bf16, hm[B,C,H,W] f32, ind[B,M] i32, reg_mask[B,M] u8, wh[B,M,2] f32, reg[B,M,2] f32
     // out: parts[3] f32, num_pos[1] f32, total[1] f32 [, grad[B,H,W,Cp] f32] ; [workspace]
@@ -239,11 +252,11 @@ static int cn_loss_entry(MD_AOT_ARGS, bool with_grad) {
     const int64_t lim = (int64_t)1 << 30;
     if (M > CNL_MAX_M || Cp > MD_CN_LOSS_MAX_CHANNELS || B > 65535 || a.numel(0) >= lim || a.numel(1) >= lim || B * M * 2 >= lim) return MD_ERR_SIZE;
     if (!a.have({0, 1, 2, 3, 4, 5, 6, 7, 8}) || (with_grad && !a.have({9}))) return MD_ERR_ARG;
-    const int64_t HW = H * W, sps = (HW + CNL_STRIP - 1) / CNL_STRIP, n_strips = B * sps, hm_elems = B * C * HW;
-    const int64_t n_chunks = (hm_elems + CNL_CHUNK - 1) / CNL_CHUNK;
+    const CnlScratch w = cn_loss_scratch(B, C, H, W);
+    const int64_t HW = H * W, sps = w.sps, n_strips = B * sps, hm_elems = B * C * HW, n_chunks = w.chunks;
     hipStream_t s = (hipStream_t)stream;
     Scratch ws;
-    if (int rc = ws.acquire((size_t)(8 * (CNL_REC * B + 2 * n_strips) + 4 * n_chunks), a, WS, s)) return rc;
+    if (int rc = ws.acquire((size_t)w.total, a, WS, s)) return rc;
     if ((uintptr_t)ws.ptr % 8 != 0) return MD_ERR_ARG;
 
     CnlParams p;
@@ -253,8 +266,8 @@ static int cn_loss_entry(MD_AOT_ARGS, bool with_grad) {
     p.use_off = has_reg && at->off_weight > 0.f;
     p.hm_elems = hm_elems;
     p.hm_weight = at->hm_weight; p.wh_weight = at->wh_weight; p.off_weight = at->off_weight;
-    double *rec = (double *)ws.ptr, *part = rec + CNL_REC * B;
-    int *counts = (int *)(part + 2 * n_strips);
+    double *rec = (double *)ws.ptr, *part = (double *)((char *)ws.ptr + w.part);
+    int *counts = (int *)((char *)ws.ptr + w.counts);
     const uint16_t *head = (const uint16_t *)params[0];
     const float *hm = (const float *)params[1], *wh = (const float *)params[4], *reg = (const float *)params[5];
     const int *ind = (const int *)params[2];
@@ -277,5 +290,8 @@ static int cn_loss_entry(MD_AOT_ARGS, bool with_grad) {
 
 using namespace md;
 
+extern "C" int64_t md_cn_loss_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W) {
+    return any_negative({B, C, H, W}) ? -1 : cn_loss_scratch(B, C, H, W).total;
+}
 extern "C" int md_cn_loss(MD_AOT_ARGS) { return cn_loss_entry(nparam, params, ndims, shapes, dtypes, stream, extra, false); }
 extern "C" int md_cn_loss_grad(MD_AOT_ARGS) { return cn_loss_entry(nparam, params, ndims, shapes, dtypes, stream, extra, true); }

@@ -97,6 +97,11 @@ __global__ __launch_bounds__(256) void cn_heat_kernel(const int4 *__restrict__ d
 
 using namespace md;
 
+// scratch of md_cn_assign_targets: draw[B][M] int4
+extern "C" int64_t md_cn_assign_targets_workspace_bytes(int64_t B, int64_t M) {
+    return any_negative({B, M}) ? -1 : B * M * 16;
+}
+
 extern "C" int md_cn_assign_targets(MD_AOT_ARGS) {
     // in : boxes[B,G,4] f32, classes[B,G] i32
     // out: hm[B,C,H,W] f32, ind[B,M] i32, reg_mask[B,M] u8, wh[B,M,2] f32, reg[B,M,2] f32 ; [workspace >= 16 B M bytes]
@@ -118,7 +123,7 @@ extern "C" int md_cn_assign_targets(MD_AOT_ARGS) {
     if (!a.have({0, 1, 2, 3, 4, 5, 6})) return MD_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     Scratch ws;
-    if (int rc = ws.acquire((size_t)(B * M) * 16, a, 7, s)) return rc;
+    if (int rc = ws.acquire((size_t)md_cn_assign_targets_workspace_bytes(B, M), a, 7, s)) return rc;
     if ((uintptr_t)ws.ptr % 16 != 0) return MD_ERR_ARG;
     CntParams p;
     p.B = (int)B; p.G = (int)G; p.M = (int)M; p.C = (int)C; p.H = (int)H; p.W = (int)W;

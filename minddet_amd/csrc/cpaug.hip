@@ -383,6 +383,27 @@ __global__ __launch_bounds__(64) void cp_boxes_kernel(BoxArgs a) {
 
 using namespace md;
 
+// scratch of md_cp_aug_count_points: rec[B G][CPA_REC] f64
+extern "C" int64_t md_cp_aug_count_points_workspace_bytes(int64_t B, int64_t G) {
+    return any_negative({B, G}) ? -1 : B * G * CPA_REC * 8;
+}
+// scratch of md_cp_aug_select: bits[B][S][ceil((G + S) / 64)] u64
+extern "C" int64_t md_cp_aug_select_workspace_bytes(int64_t B, int64_t G, int64_t S) {
+    return any_negative({B, G, S}) ? -1 : B * S * ((G + S + 63) / 64) * 8;
+}
+// scratch of md_cp_aug_points: grec[B][CPA_GREC] f64 at 0, bsum[ceil((N + Ns) / 256) + 1] i32, flag[N + Ns] u8
+struct PtsScratch { int64_t bsum, flag, total; };
+static PtsScratch cp_points_scratch(int64_t N, int64_t Ns, int64_t B) {
+    PtsScratch w;
+    w.bsum = B * CPA_GREC * 8;
+    w.flag = w.bsum + ((N + Ns + 255) / 256 + 1) * 4;
+    w.total = w.flag + N + Ns;
+    return w;
+}
+extern "C" int64_t md_cp_aug_points_workspace_bytes(int64_t N, int64_t Ns, int64_t B) {
+    return any_negative({N, Ns, B}) ? -1 : cp_points_scratch(N, Ns, B).total;
+}
+
 extern "C" int md_cp_aug_count_points(MD_AOT_ARGS) {
     // in : points[N,5] f32, offsets[B+1] i32, gt_boxes[B,G,9] f32, gt_count[B] i32
     // out: counts[B,G] i32, keep[B,G] u8 ; [workspace]
@@ -402,7 +423,7 @@ extern "C" int md_cp_aug_count_points(MD_AOT_ARGS) {
     if (aliased(params, 4, 6)) return MD_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     Scratch ws;
-    if (int rc = ws.acquire((size_t)(B * G) * CPA_REC * 8, a, 6, s)) return rc;
+    if (int rc = ws.acquire((size_t)md_cp_aug_count_points_workspace_bytes(B, G), a, 6, s)) return rc;
     if (B * G == 0) return MD_OK;
     CountArgs k;
     k.pts = (const float *)params[0]; k.offsets = (const int *)params[1]; k.boxes = (const float *)params[2];
@@ -432,7 +453,7 @@ extern "C" int md_cp_aug_select(MD_AOT_ARGS) {
     hipStream_t s = (hipStream_t)stream;
     const int64_t W = (G + S + 63) / 64;
     Scratch ws;
-    if (int rc = ws.acquire((size_t)(B * S * W) * 8, a, 7, s)) return rc;
+    if (int rc = ws.acquire((size_t)md_cp_aug_select_workspace_bytes(B, G, S), a, 7, s)) return rc;
     if (B * S == 0) return MD_OK;
     SelectArgs k;
     k.gt = (const float *)params[0]; k.gcount = (const int *)params[1]; k.keep = (const uint8_t *)params[2];
@@ -471,15 +492,15 @@ extern "C" int md_cp_aug_points(MD_AOT_ARGS) {
     if (aliased(params, 7, 9)) return MD_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     const int64_t rows = N + Ns, nb = (rows + 255) / 256;
-    const size_t grec_bytes = (size_t)B * CPA_GREC * 8, bsum_bytes = (size_t)(nb + 1) * 4;
+    const PtsScratch w = cp_points_scratch(N, Ns, B);
     Scratch ws;
-    if (int rc = ws.acquire(grec_bytes + bsum_bytes + (size_t)rows, a, 9, s)) return rc;
+    if (int rc = ws.acquire((size_t)w.total, a, 9, s)) return rc;
     PtsArgs k;
     k.pts = (const float *)params[0]; k.offsets = (const int *)params[1];
     k.cpts = cand ? (const float *)params[2] : nullptr; k.coffs = cand ? (const int *)params[3] : nullptr;
     k.cboxes = cand ? (const float *)params[4] : nullptr; k.accept = cand ? (const uint8_t *)params[5] : nullptr;
     k.glob = (const double *)params[6]; k.out = (float *)params[7]; k.offsets_out = (int *)params[8];
-    k.grec = (double *)ws.ptr; k.bsum = (int *)((char *)ws.ptr + grec_bytes); k.flag = (uint8_t *)ws.ptr + grec_bytes + bsum_bytes;
+    k.grec = (double *)ws.ptr; k.bsum = (int *)((char *)ws.ptr + w.bsum); k.flag = (uint8_t *)ws.ptr + w.flag;
     k.N = (int)N; k.Ns = (int)Ns; k.B = (int)B; k.S = (int)S; k.nb = (int)nb;
     if (nb > 0) hipLaunchKernelGGL(cp_points_flag_kernel, dim3((unsigned)nb), dim3(256), 0, s, k);
     hipLaunchKernelGGL(cp_points_scan_kernel, dim3(1), dim3(256), 0, s, k);

@@ -254,6 +254,17 @@ __global__ __launch_bounds__(512) void cp_loss_finish_kernel(const uint16_t *__r
     }
 }
 
+// scratch of md_cp_loss and md_cp_loss_grad: rec[B T][CPL_REC] f64 at 0, then neg_part[B T][sps] f64, sps = the strips of CPL_STRIP
+// cells per sample
+struct CplScratch { int64_t sps, neg_part, total; };
+static CplScratch cp_loss_scratch(int64_t B, int64_t T, int64_t H, int64_t W) {
+    CplScratch w;
+    w.sps = (H * W + CPL_STRIP - 1) / CPL_STRIP;
+    w.neg_part = 8 * B * T * CPL_REC;
+    w.total = w.neg_part + 8 * B * T * w.sps;
+    return w;
+}
+
 static int cp_loss_entry(MD_AOT_ARGS, bool with_grad) {
     // in : head[B,H,W,Cp] bf16, hm[B,T,C,H,W] f32, anno_box[B,T,M,10] f32, ind[B,T,M] i32, mask[B,T,M] u8, cat[B,T,M] i32
     // out: parts[T,12] f32, num_pos[T] f32, total[1] f32 [, grad[B,H,W,Cp] f32] ; [workspace]
@@ -308,14 +319,15 @@ static int cp_loss_entry(MD_AOT_ARGS, bool with_grad) {
     const int64_t lim = (int64_t)1 << 30;
     if (M > CPL_MAX_M || Cp > MD_CP_LOSS_MAX_CHANNELS || B > 65535 || a.numel(0) >= lim || a.numel(1) >= lim || a.numel(2) >= lim) return MD_ERR_SIZE;
     if (!a.have({0, 1, 2, 3, 4, 5, 6, 7, 8}) || (with_grad && !a.have({9}))) return MD_ERR_ARG;
-    const int64_t HW = H * W, sps = (HW + CPL_STRIP - 1) / CPL_STRIP, n_strips = B * sps;
+    const CplScratch w = cp_loss_scratch(B, T, H, W);
+    const int64_t HW = H * W, sps = w.sps, n_strips = B * sps;
     hipStream_t s = (hipStream_t)stream;
     Scratch ws;
-    if (int rc = ws.acquire((size_t)(8 * B * T * (CPL_REC + sps)), a, WS, s)) return rc;
+    if (int rc = ws.acquire((size_t)w.total, a, WS, s)) return rc;
     p.B = (int)B; p.T = (int)T; p.C = (int)C; p.HW = (int)HW; p.Cp = (int)Cp; p.M = (int)M; p.strips_per_sample = (int)sps;
     p.weight = at->weight;
     for (int j = 0; j < 10; ++j) p.cw[j] = at->code_weights[j];
-    double *rec = (double *)ws.ptr, *neg_part = rec + B * T * CPL_REC;
+    double *rec = (double *)ws.ptr, *neg_part = (double *)((char *)ws.ptr + w.neg_part);
     const uint16_t *head = (const uint16_t *)params[0];
     const float *hm = (const float *)params[1], *anno = (const float *)params[2];
     const int *ind = (const int *)params[3], *cat = (const int *)params[5];
@@ -337,5 +349,8 @@ static int cp_loss_entry(MD_AOT_ARGS, bool with_grad) {
 
 using namespace md;
 
+extern "C" int64_t md_cp_loss_workspace_bytes(int64_t B, int64_t T, int64_t H, int64_t W) {
+    return any_negative({B, T, H, W}) ? -1 : cp_loss_scratch(B, T, H, W).total;
+}
 extern "C" int md_cp_loss(MD_AOT_ARGS) { return cp_loss_entry(nparam, params, ndims, shapes, dtypes, stream, extra, false); }
 extern "C" int md_cp_loss_grad(MD_AOT_ARGS) { return cp_loss_entry(nparam, params, ndims, shapes, dtypes, stream, extra, true); }

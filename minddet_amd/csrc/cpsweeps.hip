@@ -163,6 +163,16 @@ __global__ __launch_bounds__(256) void cps_scatter_kernel(SweepArgs a) {
 
 using namespace md;
 
+// workgroups of the count and scatter kernels of md_cp_sweeps_merge: one per 256 input rows and one per segment, at least one
+static int64_t cps_blocks(int64_t N, int64_t B, int64_t S) {
+    const int64_t nb = (N + 255) / 256 + B * S;
+    return nb ? nb : 1;
+}
+// scratch of md_cp_sweeps_merge: bsum[blocks + 1] i32
+extern "C" int64_t md_cp_sweeps_merge_workspace_bytes(int64_t N, int64_t B, int64_t S) {
+    return any_negative({N, B, S}) ? -1 : (cps_blocks(N, B, S) + 1) * 4;
+}
+
 extern "C" int md_cp_sweeps_merge(MD_AOT_ARGS) {
     // in : points[N,Fin] f32, seg_range[B,S,2] i32, transforms[B,S,12] f64, time_lag[B,S] f64, seg_flags[B,S] i32
     // out: points_out[M,5] f32, offsets_out[B+1] i32, status[B] i32 ; [workspace]
@@ -185,10 +195,9 @@ extern "C" int md_cp_sweeps_merge(MD_AOT_ARGS) {
     if (M > 0 && !a.have({5})) return MD_ERR_ARG;
     if (aliased(params, 5, 8)) return MD_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    int64_t nb = (N + 255) / 256 + B * S;
-    if (nb == 0) nb = 1;
+    const int64_t nb = cps_blocks(N, B, S);
     Scratch ws;
-    if (int rc = ws.acquire((size_t)(nb + 1) * 4, a, 8, s)) return rc;
+    if (int rc = ws.acquire((size_t)md_cp_sweeps_merge_workspace_bytes(N, B, S), a, 8, s)) return rc;
     SweepArgs k;
     k.pts = (const float *)params[0]; k.range = (const int *)params[1]; k.tf = (const double *)params[2];
     k.lag = (const double *)params[3]; k.flags = (const int *)params[4];

@@ -143,6 +143,11 @@ __global__ __launch_bounds__(256) void cp_heat_kernel(const int4 *__restrict__ d
 
 using namespace md;
 
+// scratch of md_cp_assign_targets: draw[B][T][G + 1] int4
+extern "C" int64_t md_cp_assign_targets_workspace_bytes(int64_t B, int64_t T, int64_t G) {
+    return any_negative({B, T, G}) ? -1 : B * T * (G + 1) * 16;
+}
+
 extern "C" int md_cp_assign_targets(MD_AOT_ARGS) {
     // in : gt_boxes[B,G,9] f32, gt_classes[B,G] i32
     // out: hm[B,T,C,H,W] f32, anno_box[B,T,M,10] f32, ind[B,T,M] i32, mask[B,T,M] u8, cat[B,T,M] i32, gt_boxes_and_cls[B,M,10] f32 ;
@@ -180,7 +185,7 @@ extern "C" int md_cp_assign_targets(MD_AOT_ARGS) {
     if (!a.have({0, 1, 2, 3, 4, 5, 6, 7})) return MD_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     Scratch ws;
-    if (int rc = ws.acquire((size_t)(B * T * (G + 1)) * 16, a, 8, s)) return rc;
+    if (int rc = ws.acquire((size_t)md_cp_assign_targets_workspace_bytes(B, T, G), a, 8, s)) return rc;
     p.G = (int)G; p.M = (int)M; p.T = (int)T; p.C = (int)C; p.H = (int)H; p.W = (int)W;
     p.total_classes = total;
     p.vs_x = at->voxel_size[0]; p.vs_y = at->voxel_size[1]; p.pc_x = at->pc_range[0]; p.pc_y = at->pc_range[1];

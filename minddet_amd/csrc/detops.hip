@@ -1288,6 +1288,23 @@ extern "C" int md_delta2bbox(MD_AOT_ARGS) {
 static thread_local int g_topk_last_path = 0;
 extern "C" int md_topk_last_path(void) { return g_topk_last_path; }
 
+// scratch of md_topk_segmented, taken by the multi-workgroup form alone (total 0: one of the single-workgroup forms runs, L >= 1):
+// ghist[L][TK_BINS] u32 and cand_cnt[L] u32 at 0, padded to 256 bytes, then cand[L][TK_CAP] u64
+struct TopkScratch { int64_t cand, total; };
+static TopkScratch topk_scratch(int64_t L, int64_t k, int64_t max_segment) {
+    TopkScratch w = {0, 0};
+    // (r03: lowering the threshold to one 8192-score chunk -- the 32-image YOLO batches, 25 200 / 8 400 scores per image, run the single-workgroup
+    // form for 110 / 86 us -- measured no gain: three launches + a memset cost what the idle CUs cost)
+    if (max_segment > 4 * TK_CHUNK && k <= TK_CAP / 2 && L <= 65535) {
+        w.cand = (int64_t)align_up((size_t)L * TK_BINS * 4 + (size_t)L * 4, 256);
+        w.total = w.cand + L * TK_CAP * 8;
+    }
+    return w;
+}
+extern "C" int64_t md_topk_segmented_workspace_bytes(int64_t L, int64_t k, int64_t max_segment) {
+    return any_negative({L, k, max_segment}) ? -1 : topk_scratch(L, k, max_segment).total;
+}
+
 extern "C" int md_topk_segmented(MD_AOT_ARGS) {
     // in: scores[T] f32, seg_off[L+1] i32 ; out: values[L,k] f32, indices[L,k] i32, count[L] i32
     g_topk_last_path = 0;
@@ -1302,15 +1319,13 @@ extern "C" int md_topk_segmented(MD_AOT_ARGS) {
     if (L == 0) return MD_OK;
     if (!a.have({0, 1, 2, 3, 4})) return MD_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    // (r03: lowering the threshold to one 8192-score chunk -- the 32-image YOLO batches, 25 200 / 8 400 scores per image, run the single-workgroup
-    // form for 110 / 86 us -- measured no gain: three launches + a memset cost what the idle CUs cost)
-    if (at->max_segment > 4 * TK_CHUNK && at->k <= TK_CAP / 2 && L <= 65535) {
-        const size_t hist_bytes = align_up((size_t)L * TK_BINS * 4 + (size_t)L * 4, 256);
+    const TopkScratch w = topk_scratch(L, at->k, at->max_segment);
+    if (w.total) {
         Scratch ws;
-        if (int rc = ws.acquire(hist_bytes + (size_t)L * TK_CAP * 8, a, 5, s)) return rc;
+        if (int rc = ws.acquire((size_t)w.total, a, 5, s)) return rc;
         unsigned *ghist = (unsigned *)ws.ptr, *cand_cnt = ghist + (size_t)L * TK_BINS;
-        unsigned long long *cand = (unsigned long long *)((char *)ws.ptr + hist_bytes);
-        MD_HIP_TRY(hipMemsetAsync(ws.ptr, 0, hist_bytes, s));
+        unsigned long long *cand = (unsigned long long *)((char *)ws.ptr + w.cand);
+        MD_HIP_TRY(hipMemsetAsync(ws.ptr, 0, (size_t)w.cand, s));
         const unsigned chunks = (unsigned)((at->max_segment + TK_CHUNK - 1) / TK_CHUNK);
         hipLaunchKernelGGL(topk_hist_kernel, dim3(chunks, (unsigned)L), dim3(256), 0, s, (const float *)params[0],
                            (const int *)params[1], at->min_score, ghist);

@@ -207,6 +207,18 @@ __global__ __launch_bounds__(64) void kr_rows_kernel(RowArgs a) {
 
 using namespace md;
 
+// scratch of md_pc_crop_hulls: planes[B K][KC_PLANE] f64 at 0, bsum[ceil(N / 256) + 1] i32
+struct CropScratch { int64_t bsum, total; };
+static CropScratch crop_scratch(int64_t N, int64_t B, int64_t K) {
+    CropScratch w;
+    w.bsum = B * K * KC_PLANE * 8;
+    w.total = w.bsum + ((N + 255) / 256 + 1) * 4;
+    return w;
+}
+extern "C" int64_t md_pc_crop_hulls_workspace_bytes(int64_t N, int64_t B, int64_t K) {
+    return any_negative({N, B, K}) ? -1 : crop_scratch(N, B, K).total;
+}
+
 extern "C" int md_pc_crop_hulls(MD_AOT_ARGS) {
     // in : points[N,4] f32, offsets[B+1] i32, hulls[B,K,8,3] f64, hull_count[B] i32
     // out: points_out[N,4] f32, offsets_out[B+1] i32, keep[N] u8 ; [workspace]
@@ -226,14 +238,14 @@ extern "C" int md_pc_crop_hulls(MD_AOT_ARGS) {
     if (aliased(params, 4, 7)) return MD_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     const int64_t nb = (N + 255) / 256;
-    const size_t plane_bytes = (size_t)(B * K) * KC_PLANE * 8;
+    const CropScratch w = crop_scratch(N, B, K);
     Scratch ws;
-    if (int rc = ws.acquire(plane_bytes + (size_t)(nb + 1) * 4, a, 7, s)) return rc;
+    if (int rc = ws.acquire((size_t)w.total, a, 7, s)) return rc;
     CropArgs k;
     k.pts = (const float4 *)params[0]; k.offsets = (const int *)params[1]; k.hulls = (const double *)params[2];
     k.hull_count = (const int *)params[3];
     k.out = (float4 *)params[4]; k.offsets_out = (int *)params[5]; k.keep = (uint8_t *)params[6];
-    k.planes = (double *)ws.ptr; k.bsum = (int *)((char *)ws.ptr + plane_bytes);
+    k.planes = (double *)ws.ptr; k.bsum = (int *)((char *)ws.ptr + w.bsum);
     k.N = (int)N; k.B = (int)B; k.K = (int)K; k.nb = (int)nb;
     if (B * K > 0) hipLaunchKernelGGL(kc_planes_kernel, dim3((unsigned)((B * K * 6 + 255) / 256)), dim3(256), 0, s, k);
     if (nb > 0) hipLaunchKernelGGL(kc_classify_kernel, dim3((unsigned)nb), dim3(256), 0, s, k);

@@ -659,6 +659,19 @@ extern "C" int NmsNormalGpu(MD_AOT_ARGS) {
     return launched();
 }
 
+// scratch of md_nms_rotated: mask[L][n][ceil(n / 64)] u64 at 0 (the 8-byte words first: the records are a multiple of 4 bytes only),
+// then rec[L][n][ROT_REC] f32
+struct RotatedScratch { int64_t rec, total; };
+static RotatedScratch nms_rotated_scratch(int64_t L, int64_t n) {
+    RotatedScratch w;
+    w.rec = L * n * ((n + TILE - 1) / TILE) * 8;
+    w.total = w.rec + L * n * ROT_REC * 4;
+    return w;
+}
+extern "C" int64_t md_nms_rotated_workspace_bytes(int64_t L, int64_t n) {
+    return any_negative({L, n}) ? -1 : nms_rotated_scratch(L, n).total;
+}
+
 // include/minddet_hip_cp.h.  in: boxes[L,N,7] f32 (or [N,7]), count[L] i32 | NULL ; out: keep_idx[L,N] i32, num[L] i32 ; [workspace].
 // extra: md_nms_rotated_attrs (required)
 extern "C" int md_nms_rotated(MD_AOT_ARGS) {
@@ -678,11 +691,11 @@ extern "C" int md_nms_rotated(MD_AOT_ARGS) {
     if (n == 0) return hipMemsetAsync(params[3], 0, sizeof(int) * L, s) == hipSuccess ? MD_OK : MD_ERR_HIP;
     if (!a.have({0, 2})) return MD_ERR_ARG;
     const int cb = (int)((n + TILE - 1) / TILE);
-    const size_t mask_bytes = (size_t)L * n * cb * 8, rec_bytes = (size_t)L * n * ROT_REC * 4;
+    const RotatedScratch w = nms_rotated_scratch(L, n);
     Scratch ws;
-    if (int rc = ws.acquire(mask_bytes + rec_bytes, a, 4, s)) return rc;
-    unsigned long long *mask = (unsigned long long *)ws.ptr;     // (the 8-byte words first: rec_bytes is a multiple of 4 only)
-    float *rec = (float *)((char *)ws.ptr + mask_bytes);
+    if (int rc = ws.acquire((size_t)w.total, a, 4, s)) return rc;
+    unsigned long long *mask = (unsigned long long *)ws.ptr;
+    float *rec = (float *)((char *)ws.ptr + w.rec);
     const int *count = a.given(1) ? a.ptr<const int>(1) : nullptr;
     hipLaunchKernelGGL(rot_prep_batched_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)L), dim3(256), 0, s,
                        a.ptr<const float>(0), count, (int)n, rec);
@@ -765,6 +778,21 @@ extern "C" int md_rotate_iou_eval(MD_AOT_ARGS) {
     return launched();
 }
 
+// scratch of md_nms_aligned: mask[B][n][ceil(n / 64)] u64 at 0, then -- for the two-level form only, flags < total -- need_full[B] i32.
+// P: the prefix that the first pass of the two-level form decides (below), a multiple of 64
+struct AlignedScratch { int64_t P, flags, total; };
+static AlignedScratch nms_aligned_scratch(int64_t B, int64_t n, int64_t max_output) {
+    const int64_t want = max_output > 128 ? 4 * max_output : 512;
+    AlignedScratch w;
+    w.P = (want + TILE - 1) / TILE * TILE;
+    w.flags = B * n * ((n + TILE - 1) / TILE) * 8;
+    w.total = w.flags + (max_output > 0 && n >= 2 * w.P ? (int64_t)align_up((size_t)B * 4, 256) : 0);
+    return w;
+}
+extern "C" int64_t md_nms_aligned_workspace_bytes(int64_t B, int64_t n, int64_t max_output) {
+    return any_negative({B, n, max_output}) ? -1 : nms_aligned_scratch(B, n, max_output).total;
+}
+
 extern "C" int md_nms_aligned(MD_AOT_ARGS) {
     // in: boxes[B,N,4] f32 (or [N,4]), count[B] i32 | NULL, group[B,N] i32 | NULL ; out: keep_mask[B,N] u8, keep_idx[B,N] i32, num[B] i32 ;
     // [workspace].  extra: md_nms_attrs (required)
@@ -784,30 +812,26 @@ extern "C" int md_nms_aligned(MD_AOT_ARGS) {
     if (n == 0) return hipMemsetAsync(params[5], 0, sizeof(int) * B, s) == hipSuccess ? MD_OK : MD_ERR_HIP;
     if (!a.have({0, 3, 4})) return MD_ERR_ARG;
     const int cb = (int)((n + TILE - 1) / TILE);
-    const size_t mask_bytes = (size_t)B * n * cb * 8;
     // Quota prefix pass.  With an output quota (max_output > 0) the scan stops at the quota-th kept box, and a box is suppressed by
     // higher-ranked kept boxes only: the first P boxes decide among themselves, so when they already yield max_output survivors the
     // P x P corner of the mask is all that was ever needed (YOLO: 4 096 candidates, quota 300 -> 190 tiles instead of 2 080 per
     // image).  Pass 1 = mask corner + scan over the first P boxes; it raises a per-list flag when the quota was NOT filled although
     // the list goes on, and pass 2 (full mask + full scan, gated by that flag on the device: no host synchronisation) redoes those
     // lists from scratch.  Outputs are identical to the single full pass in every case.
-    const int64_t want = (int64_t)4 * at->max_output > 512 ? (int64_t)4 * at->max_output : 512;
-    const int P = (int)((want + TILE - 1) / TILE * TILE);
-    const bool two_level = at->max_output > 0 && n >= 2 * (int64_t)P;
-    const size_t flag_bytes = two_level ? align_up((size_t)B * 4, 256) : 0;
+    const AlignedScratch w = nms_aligned_scratch(B, n, at->max_output);
     Scratch ws;
-    int rc = ws.acquire(mask_bytes + flag_bytes, a, 6, s);
-    bool tl = two_level;
-    if (rc == MD_ERR_SIZE && two_level) {   // a caller workspace sized for the mask only: single full pass
+    int rc = ws.acquire((size_t)w.total, a, 6, s);
+    bool tl = w.flags < w.total;
+    if (rc == MD_ERR_SIZE && tl) {   // a caller workspace sized for the mask only: single full pass
         tl = false;
-        rc = ws.acquire(mask_bytes, a, 6, s);
+        rc = ws.acquire((size_t)w.flags, a, 6, s);
     }
     if (rc) return rc;
     unsigned long long *mask = (unsigned long long *)ws.ptr;
     int *need_full = nullptr;
     if (tl) {
-        need_full = (int *)((char *)ws.ptr + mask_bytes);   // (mask_bytes is a multiple of 8)
-        const int cbp = P / TILE;
+        need_full = (int *)((char *)ws.ptr + w.flags);   // (the mask is a multiple of 8 bytes)
+        const int P = (int)w.P, cbp = P / TILE;          // (P <= n / 2 here)
         hipLaunchKernelGGL(nms_aligned_mask_kernel, dim3(cbp * (cbp + 1) / 2, (unsigned)B), dim3(256), 0, s,
                            (const float *)params[0], (const int *)params[1], (const int *)params[2], (int)n,
                            at->iou_threshold, at->eps, at->mode, mask, cb, cbp, P, (const int *)nullptr);

@@ -358,6 +358,19 @@ extern "C" int md_pc_noise_per_object(MD_AOT_ARGS) {
     return launched();
 }
 
+// scratch of md_pc_augment_points: rec[B (G + R)][PCA_REC] f64 at 0, grec[B][PCA_GREC] f64, bsum[ceil(N / 256) + 1] i32
+struct PointScratch { int64_t grec, bsum, total; };
+static PointScratch pc_points_scratch(int64_t N, int64_t B, int64_t G, int64_t R) {
+    PointScratch w;
+    w.grec = B * (G + R) * PCA_REC * 8;
+    w.bsum = w.grec + B * PCA_GREC * 8;
+    w.total = w.bsum + ((N + 255) / 256 + 1) * 4;
+    return w;
+}
+extern "C" int64_t md_pc_augment_points_workspace_bytes(int64_t N, int64_t B, int64_t G, int64_t R) {
+    return any_negative({N, B, G, R}) ? -1 : pc_points_scratch(N, B, G, R).total;
+}
+
 extern "C" int md_pc_augment_points(MD_AOT_ARGS) {
     // in : points[N,4] f32, offsets[B+1] i32, obj_boxes[B,G,7] f32, gt_count[B] i32, valid[B,G] u8, obj_transform[B,G,4] f64,
     //      remove_boxes[B,R,7] f32 | NULL, remove_count[B] i32 | NULL, remove_from[B] i32 | NULL, global[B,6] f64
@@ -386,9 +399,9 @@ extern "C" int md_pc_augment_points(MD_AOT_ARGS) {
     if (params[10] == params[12] || params[11] == params[12] || params[10] == params[11]) return MD_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     const int64_t nb = (N + 255) / 256;
-    const size_t rec_bytes = (size_t)(B * (G + R)) * PCA_REC * 8, grec_bytes = (size_t)B * PCA_GREC * 8;
+    const PointScratch w = pc_points_scratch(N, B, G, R);
     Scratch ws;
-    if (int rc = ws.acquire(rec_bytes + grec_bytes + (size_t)(nb + 1) * 4, a, 13, s)) return rc;
+    if (int rc = ws.acquire((size_t)w.total, a, 13, s)) return rc;
     PointArgs k;
     k.pts = (const float4 *)params[0]; k.offsets = (const int *)params[1]; k.obj = (const float *)params[2];
     k.count = (const int *)params[3]; k.valid = (const uint8_t *)params[4]; k.tf = (const double *)params[5];
@@ -396,7 +409,7 @@ extern "C" int md_pc_augment_points(MD_AOT_ARGS) {
     k.rem_from = rem ? (const int *)params[8] : nullptr;
     k.glob = (const double *)params[9];
     k.out = (float4 *)params[10]; k.offsets_out = (int *)params[11]; k.owner = (int *)params[12];
-    k.rec = (double *)ws.ptr; k.grec = (double *)((char *)ws.ptr + rec_bytes); k.bsum = (int *)((char *)ws.ptr + rec_bytes + grec_bytes);
+    k.rec = (double *)ws.ptr; k.grec = (double *)((char *)ws.ptr + w.grec); k.bsum = (int *)((char *)ws.ptr + w.bsum);
     k.N = (int)N; k.B = (int)B; k.G = (int)G; k.R = (int)R; k.nb = (int)nb;
     if (B > 0) hipLaunchKernelGGL(pc_record_kernel, dim3((unsigned)((B * (G + R + 1) + 255) / 256)), dim3(256), 0, s, k);
     if (nb > 0) hipLaunchKernelGGL(pc_classify_kernel, dim3((unsigned)nb), dim3(256), 0, s, k);

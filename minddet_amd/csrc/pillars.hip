@@ -343,6 +343,26 @@ static inline bool finite_f(float x) { return x == x && x - x == 0.f; }
 
 using namespace md;
 
+// scratch of md_voxelize for N points and B samples of `cells` cells and MV voxels: eight i32 arrays, each padded to 64 entries.  The
+// offsets count i32 entries, total counts bytes.  first, cvox: [B cells]; cell, flag: [N]; pre: [N + 1]; cnt: [B MV]; start: [B MV + 1];
+// bsum: one entry per scan block of the longer of the two scans, and one more
+struct VoxScratch { int64_t first, cvox, cell, flag, pre, cnt, start, bsum, total; };
+static VoxScratch voxelize_scratch(int64_t N, int64_t B, int64_t cells, int64_t MV) {
+    const int64_t nbN = (N + PV_BLOCK - 1) / PV_BLOCK, nbV = (B * MV + PV_BLOCK - 1) / PV_BLOCK;
+    int64_t ints = 0;
+    auto take = [&](int64_t n) { const int64_t at = ints; ints += (n + 63) / 64 * 64; return at; };
+    VoxScratch w;
+    w.first = take(B * cells); w.cvox = take(B * cells);
+    w.cell = take(N); w.flag = take(N); w.pre = take(N + 1);
+    w.cnt = take(B * MV); w.start = take(B * MV + 1);
+    w.bsum = take((nbN > nbV ? nbN : nbV) + 1);
+    w.total = ints * 4;
+    return w;
+}
+extern "C" int64_t md_voxelize_workspace_bytes(int64_t N, int64_t B, int64_t cells, int64_t max_voxels) {
+    return any_negative({N, B, cells, max_voxels}) ? -1 : voxelize_scratch(N, B, cells, max_voxels).total;
+}
+
 // in : points[N,F] f32, offsets[B+1] i32 ; out: voxels[B,MV,MP,F] f32, coors[B,MV,4] i32, num_points[B,MV] i32, voxel_num[B] i32
 // [, workspace u8].  extra: md_voxelize_attrs (required).  Every check precedes the first device call.
 extern "C" int md_voxelize(MD_AOT_ARGS) {
@@ -376,18 +396,10 @@ extern "C" int md_voxelize(MD_AOT_ARGS) {
 
     const size_t nbN = (size_t)(N + PV_BLOCK - 1) / PV_BLOCK, nbV = (size_t)(B * MV + PV_BLOCK - 1) / PV_BLOCK;
     const size_t n_first = (size_t)(B * G), n_pts = (size_t)N, n_vox = (size_t)(B * MV);
-    size_t ints = 0;
-    const size_t o_first = ints; ints += align_up(n_first, 64);
-    const size_t o_cvox = ints; ints += align_up(n_first, 64);
-    const size_t o_cell = ints; ints += align_up(n_pts, 64);
-    const size_t o_flag = ints; ints += align_up(n_pts, 64);
-    const size_t o_pre = ints; ints += align_up(n_pts + 1, 64);
-    const size_t o_cnt = ints; ints += align_up(n_vox, 64);
-    const size_t o_start = ints; ints += align_up(n_vox + 1, 64);
-    const size_t o_bsum = ints; ints += align_up((nbN > nbV ? nbN : nbV) + 1, 64);
+    const VoxScratch w = voxelize_scratch(N, B, G, MV);
     hipStream_t s = (hipStream_t)stream;
     Scratch sc;
-    if (int rc = sc.acquire(ints * 4, g, 6, s)) return rc;
+    if (int rc = sc.acquire((size_t)w.total, g, 6, s)) return rc;
     int *ws = (int *)sc.ptr;
 
     VoxArgs a;
@@ -396,8 +408,8 @@ extern "C" int md_voxelize(MD_AOT_ARGS) {
     a.N = (int)N; a.F = (int)F; a.B = (int)B; a.MV = (int)MV; a.MP = (int)MP;
     a.gx = grid[0]; a.gy = grid[1]; a.gz = grid[2]; a.G = (int)G;
     for (int k = 0; k < 3; ++k) { a.lo[k] = at->range[k]; a.vs[k] = at->voxel_size[k]; }
-    a.first = ws + o_first; a.cell_vox = ws + o_cvox; a.cell_of = ws + o_cell; a.flag = ws + o_flag; a.pre = ws + o_pre;
-    a.cnt = ws + o_cnt; a.start = ws + o_start; a.bsum = ws + o_bsum;
+    a.first = ws + w.first; a.cell_vox = ws + w.cvox; a.cell_of = ws + w.cell; a.flag = ws + w.flag; a.pre = ws + w.pre;
+    a.cnt = ws + w.cnt; a.start = ws + w.start; a.bsum = ws + w.bsum;
 
     if (n_vox * MP * F) MD_HIP_TRY(hipMemsetAsync(a.voxels, 0, n_vox * MP * F * 4, s));
     if (n_vox) MD_HIP_TRY(hipMemsetAsync(a.coors, 0, n_vox * 16, s));

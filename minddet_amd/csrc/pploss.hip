@@ -193,6 +193,18 @@ __global__ __launch_bounds__(256) void pp_loss_finish_kernel(const double *__res
     }
 }
 
+// scratch of md_pp_loss and md_pp_loss_grad: part[B sps][PPL_Q] f64 at 0, then counts[B][cps] i32; sps = the strips of PPL_STRIP cells,
+// cps = the chunks of PPL_CHUNK labels per sample
+struct PplScratch { int64_t sps, cps, counts, total; };
+static PplScratch pp_loss_scratch(int64_t B, int64_t H, int64_t W, int64_t A) {
+    PplScratch w;
+    w.sps = (H * W + PPL_STRIP - 1) / PPL_STRIP;
+    w.cps = (H * W * A + PPL_CHUNK - 1) / PPL_CHUNK;
+    w.counts = 8 * PPL_Q * B * w.sps;
+    w.total = w.counts + 4 * B * w.cps;
+    return w;
+}
+
 static int pp_loss_entry(MD_AOT_ARGS, bool with_grad) {
     // in : head[B,H,W,C] bf16, labels[B,N] i32, reg_targets[B,N,7] f32, anchors[N,7] f32
     // out: parts[5] f32, num_pos[B] f32, total[1] f32 [, grad[B,H,W,C] f32] ; [workspace]
@@ -231,10 +243,11 @@ static int pp_loss_entry(MD_AOT_ARGS, bool with_grad) {
     if (int rc = a.rc()) return rc;
     if (big || C > MD_PP_LOSS_MAX_CHANNELS || B > 65535 || a.numel(0) >= lim || a.numel(2) >= lim) return MD_ERR_SIZE;
     if (!a.have({0, 1, 2, 3, 4, 5, 6}) || (with_grad && !a.have({7}))) return MD_ERR_ARG;
-    const int64_t sps = (HW + PPL_STRIP - 1) / PPL_STRIP, n_strips = B * sps, cps = (N + PPL_CHUNK - 1) / PPL_CHUNK;
+    const PplScratch w = pp_loss_scratch(B, H, W, A);
+    const int64_t sps = w.sps, n_strips = B * sps, cps = w.cps;
     hipStream_t s = (hipStream_t)stream;
     Scratch ws;
-    if (int rc = ws.acquire((size_t)(8 * PPL_Q * n_strips + 4 * B * cps), a, WS, s)) return rc;
+    if (int rc = ws.acquire((size_t)w.total, a, WS, s)) return rc;
     if ((uintptr_t)ws.ptr % 8 != 0) return MD_ERR_ARG;
 
     PplParams p;
@@ -247,7 +260,7 @@ static int pp_loss_entry(MD_AOT_ARGS, bool with_grad) {
     p.cls_weight = at->cls_weight; p.loc_weight = at->loc_weight; p.dir_weight = at->dir_weight;
     p.pos_cls_weight = at->pos_cls_weight; p.neg_cls_weight = at->neg_cls_weight;
     double *part = (double *)ws.ptr;
-    int *counts = (int *)(part + PPL_Q * n_strips);
+    int *counts = (int *)((char *)ws.ptr + w.counts);
     const uint16_t *head = (const uint16_t *)params[0];
     const int *labels = (const int *)params[1];
     const float *reg = (const float *)params[2], *anchors = (const float *)params[3];
@@ -268,5 +281,8 @@ static int pp_loss_entry(MD_AOT_ARGS, bool with_grad) {
 
 using namespace md;
 
+extern "C" int64_t md_pp_loss_workspace_bytes(int64_t B, int64_t H, int64_t W, int64_t num_anchors) {
+    return any_negative({B, H, W, num_anchors}) ? -1 : pp_loss_scratch(B, H, W, num_anchors).total;
+}
 extern "C" int md_pp_loss(MD_AOT_ARGS) { return pp_loss_entry(nparam, params, ndims, shapes, dtypes, stream, extra, false); }
 extern "C" int md_pp_loss_grad(MD_AOT_ARGS) { return pp_loss_entry(nparam, params, ndims, shapes, dtypes, stream, extra, true); }

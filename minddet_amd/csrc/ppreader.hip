@@ -284,6 +284,11 @@ extern "C" int md_pp_pillar_encode(MD_AOT_ARGS) {
     return launched();
 }
 
+// scratch of md_pp_anchor_mask: one i32 per cell of every sample's grid, [B][grid_y][grid_x]
+extern "C" int64_t md_pp_anchor_mask_workspace_bytes(int64_t B, int64_t grid_x, int64_t grid_y) {
+    return any_negative({B, grid_x, grid_y}) ? -1 : B * grid_y * grid_x * 4;
+}
+
 // in : coors[B,MV,4] i32, voxel_num[B] i32, anchors_bv[N,4] f32 ; out: mask[B,N] u8 [, area[B,N] f32 or NULL] [, workspace u8].
 // extra: md_anchor_mask_attrs (required).
 extern "C" int md_pp_anchor_mask(MD_AOT_ARGS) {
@@ -301,7 +306,7 @@ extern "C" int md_pp_anchor_mask(MD_AOT_ARGS) {
     if ((MV > 0 && !g.have({0})) || !g.have({1}) || (n > 0 && !g.have({2, 3}))) return MD_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     Scratch ws;
-    if (int rc = ws.acquire((size_t)B * ny * nx * 4, g, 5, s)) return rc;
+    if (int rc = ws.acquire((size_t)md_pp_anchor_mask_workspace_bytes(B, nx, ny), g, 5, s)) return rc;
     return anchor_mask_launch(s, (int *)ws.ptr, g.ptr<const int>(0), 4, 2, 3, g.ptr<const int>(1), B, MV, g.ptr<const float>(2), n, at,
                               g.given(4) ? g.ptr<float>(4) : nullptr, g.ptr<unsigned char>(3), 16384);
 }

@@ -211,8 +211,7 @@ def nms_aligned(boxes_sorted, thresh, eps=0.0, mode=NMS_MODE_JIT, count=None, gr
     params = [b, count, group, mask, idx, num]
     if workspace is None and B * n > 0:
         # suppression-mask scratch from torch's caching allocator (never blocks), not from the op's hipMallocAsync fallback
-        cb = (n + 63) // 64
-        workspace = torch.empty((B * n * cb * 8 + (B * 4 + 255) // 256 * 256,), dtype=torch.uint8, device=dev)
+        workspace = _lib.scratch("md_nms_aligned", (B, n, max(int(max_output), 0)), dev)
     if workspace is not None:
         params.append(workspace)
     _lib.call("md_nms_aligned", params, extra=_NmsAttrs(float(thresh), float(eps), int(mode), int(max_output)))
@@ -435,12 +434,12 @@ def topk_segmented(scores, seg_offsets, k, min_score=None, out_cnt=None, max_seg
     cnt = out_cnt if out_cnt is not None else torch.empty((L,), dtype=torch.int32, device=scores.device)
     max_segment = int(scores.numel() if max_segment is None else max_segment)
     params = [scores, seg_offsets, vals, idx, cnt]
-    if max_segment > 4 * 8192 and k <= 4096 and L <= 65535:
+    dims = (L, int(k), max_segment)
+    if min(dims) >= 0 and _lib.workspace_bytes("md_topk_segmented", *dims):
         # the multi-workgroup select takes scratch: hand it a block of torch's caching allocator.  Without it the op falls back to
         # hipMallocAsync / hipFreeAsync, which BLOCKED the host ~7 ms per call on ROCm 7.2 (r03 tools/host_enqueue.py: 49.6 of the
         # 51.9 ms the host spent enqueuing one Faster R-CNN step sat in these seven calls, the device queue running dry behind each)
-        hist = ((L * (2048 * 4 + 4)) + 255) // 256 * 256
-        params.append(torch.empty((hist + L * 8192 * 8,), dtype=torch.uint8, device=scores.device))
+        params.append(_lib.scratch("md_topk_segmented", dims, scores.device))
     _lib.call("md_topk_segmented", params,
               extra=_TopkAttrs(int(k), -FLT_MAX if min_score is None else float(min_score), max_segment))
     return vals, idx, cnt
@@ -713,7 +712,7 @@ def nms_rotated(boxes, thresh, mode, count=None, max_output=0, workspace=None):
     params = [b, count, idx, num]
     if workspace is None and L * n > 0:
         # record + mask scratch from torch's caching allocator (never blocks), as nms_aligned does
-        workspace = torch.empty((L * n * (20 * 4 + (n + 63) // 64 * 8),), dtype=torch.uint8, device=dev)
+        workspace = _lib.scratch("md_nms_rotated", (L, n), dev)
     if workspace is not None:
         params.append(workspace)
     _lib.call("md_nms_rotated", params, extra=_NmsRotatedAttrs(float(thresh), int(mode), int(max_output)))
@@ -1131,9 +1130,7 @@ def voxel_grid(voxel_size, pc_range):
 
 def voxelize_workspace_bytes(N, B, cells, max_voxels):
     """bytes of scratch md_voxelize takes for N points, B samples of `cells` cells (include/minddet_hip_points.h)"""
-    up = lambda n: (n + 63) // 64 * 64
-    nb = (max(N, B * max_voxels) + 1023) // 1024
-    return 4 * (2 * up(B * cells) + 2 * up(N) + up(N + 1) + up(B * max_voxels) + up(B * max_voxels + 1) + up(nb + 1))
+    return _lib.workspace_bytes("md_voxelize", N, B, cells, max_voxels)
 
 
 def voxelize(points, offsets, voxel_size, pc_range, max_points, max_voxels):
@@ -1152,7 +1149,7 @@ def voxelize(points, offsets, voxel_size, pc_range, max_points, max_voxels):
     coors = torch.empty((B, max_voxels, 4), dtype=torch.int32, device=dev)
     num_points = torch.empty((B, max_voxels), dtype=torch.int32, device=dev)
     voxel_num = torch.empty((B,), dtype=torch.int32, device=dev)
-    ws = torch.empty((voxelize_workspace_bytes(N, B, gx * gy * gz, max_voxels),), dtype=torch.uint8, device=dev)
+    ws = _lib.scratch("md_voxelize", (N, B, gx * gy * gz, max_voxels), dev)
     _lib.call("md_voxelize", [points, offsets, voxels, coors, num_points, voxel_num, ws], extra=at)
     return voxels, coors, num_points, voxel_num
 
@@ -1254,7 +1251,7 @@ def anchors_mask_batched(coors, voxel_num, grid_size_xy, anchors_bv, voxel_size,
     B, dev = coors.shape[0], bv.device
     mask = torch.empty((B, bv.shape[0]), dtype=torch.uint8, device=dev)
     area = torch.empty((B, bv.shape[0]), dtype=torch.float32, device=dev) if with_area else None
-    ws = torch.empty((max(B, 1) * at.grid_x * at.grid_y * 4,), dtype=torch.uint8, device=dev)
+    ws = _lib.scratch("md_pp_anchor_mask", (B, at.grid_x, at.grid_y), dev)
     _lib.call("md_pp_anchor_mask", [coors, voxel_num, bv, mask, area, ws], extra=at)
     return (mask, area) if with_area else mask
 
@@ -1296,7 +1293,7 @@ def pc_noise_per_object(gt_boxes, gt_count, valid, loc_noises, rot_noises, grot_
 
 def pc_augment_points_workspace_bytes(N, B, G, R):
     """bytes of scratch md_pc_augment_points takes (include/minddet_hip_pcaug.h)"""
-    return 128 * B * (G + R) + 64 * B + 4 * (N // 256 + 3)
+    return _lib.workspace_bytes("md_pc_augment_points", N, B, G, R)
 
 
 def pc_augment_points(points, offsets, obj_boxes, gt_count, valid, obj_transform, glob, remove_boxes=None, remove_count=None,
@@ -1322,7 +1319,7 @@ def pc_augment_points(points, offsets, obj_boxes, gt_count, valid, obj_transform
     ops = [points, _i32c(offsets, dev), g, _i32c(gt_count, dev), valid.to(device=dev, dtype=torch.uint8).contiguous(),
            _f64c(obj_transform, dev), *rem, _f64c(glob, dev), out, offsets_out, owner]
     if workspace:
-        ops.append(torch.empty((pc_augment_points_workspace_bytes(N, B, G, R),), dtype=torch.uint8, device=dev))
+        ops.append(_lib.scratch("md_pc_augment_points", (N, B, G, R), dev))
     _lib.call("md_pc_augment_points", ops)
     return out, offsets_out, owner
 
@@ -1468,7 +1465,7 @@ def _points5(who, t):
 
 def cp_aug_count_points_workspace_bytes(B, G):
     """bytes of scratch md_cp_aug_count_points takes (include/minddet_hip_cpaug.h)"""
-    return 96 * B * G
+    return _lib.workspace_bytes("md_cp_aug_count_points", B, G)
 
 
 def cp_aug_count_points(points, offsets, gt_boxes, gt_count, min_points=-1, workspace=True):
@@ -1481,14 +1478,14 @@ def cp_aug_count_points(points, offsets, gt_boxes, gt_count, min_points=-1, work
     keep = torch.empty((B, G), dtype=torch.uint8, device=dev)
     ops = [points, _i32c(offsets, dev), g, _i32c(gt_count, dev), counts, keep]
     if workspace:
-        ops.append(torch.empty((max(cp_aug_count_points_workspace_bytes(B, G), 16),), dtype=torch.uint8, device=dev))
+        ops.append(_lib.scratch("md_cp_aug_count_points", (B, G), dev))
     _lib.call("md_cp_aug_count_points", ops, extra=_CPCountAttrs(int(min_points)))
     return counts, keep
 
 
 def cp_aug_select_workspace_bytes(B, G, S):
     """bytes of scratch md_cp_aug_select takes (include/minddet_hip_cpaug.h)"""
-    return 8 * B * S * ((G + S + 63) // 64)
+    return _lib.workspace_bytes("md_cp_aug_select", B, G, S)
 
 
 def cp_aug_select(gt_boxes, gt_count, keep, cand_boxes, cand_count, cand_group, workspace=True):
@@ -1500,14 +1497,14 @@ def cp_aug_select(gt_boxes, gt_count, keep, cand_boxes, cand_count, cand_group, 
     accept = torch.empty((B, S), dtype=torch.uint8, device=dev)
     ops = [g, _i32c(gt_count, dev), _u8c(keep, dev), c, _i32c(cand_count, dev), _i32c(cand_group, dev), accept]
     if workspace:
-        ops.append(torch.empty((max(cp_aug_select_workspace_bytes(B, G, S), 16),), dtype=torch.uint8, device=dev))
+        ops.append(_lib.scratch("md_cp_aug_select", (B, G, S), dev))
     _lib.call("md_cp_aug_select", ops)
     return accept
 
 
 def cp_aug_points_workspace_bytes(N, Ns, B):
     """bytes of scratch md_cp_aug_points takes (include/minddet_hip_cpaug.h)"""
-    return 64 * B + (N + Ns) + 4 * ((N + Ns) // 256 + 3)
+    return _lib.workspace_bytes("md_cp_aug_points", N, Ns, B)
 
 
 def cp_aug_points(points, offsets, glob, cand_points=None, cand_offsets=None, cand_boxes=None, accept=None, workspace=True):
@@ -1529,7 +1526,7 @@ def cp_aug_points(points, offsets, glob, cand_points=None, cand_offsets=None, ca
     offsets_out = torch.empty((B + 1,), dtype=torch.int32, device=dev)
     ops = [points, _i32c(offsets, dev), *cand, _f64c(glob, dev), out, offsets_out]
     if workspace:
-        ops.append(torch.empty((cp_aug_points_workspace_bytes(N, Ns, B),), dtype=torch.uint8, device=dev))
+        ops.append(_lib.scratch("md_cp_aug_points", (N, Ns, B), dev))
     _lib.call("md_cp_aug_points", ops)
     return out, offsets_out
 
@@ -1664,7 +1661,7 @@ class _CPSweepsAttrs(ctypes.Structure):
 
 def cp_sweeps_merge_workspace_bytes(N, B, S):
     """bytes of scratch md_cp_sweeps_merge takes (include/minddet_hip_cpsweeps.h)"""
-    return 4 * (N // 256 + B * S + 3)
+    return _lib.workspace_bytes("md_cp_sweeps_merge", N, B, S)
 
 
 def cp_sweeps_merge(points, seg_range, transforms, time_lag, seg_flags, radius=1.0, workspace=True, out=None):
@@ -1691,7 +1688,7 @@ def cp_sweeps_merge(points, seg_range, transforms, time_lag, seg_flags, radius=1
     status = torch.empty((B,), dtype=torch.int32, device=dev)
     ops = [points, _i32c(seg_range, dev), _f64c(transforms, dev), _f64c(time_lag, dev), _i32c(seg_flags, dev), out, offsets_out, status]
     if workspace:
-        ops.append(torch.empty((cp_sweeps_merge_workspace_bytes(N, B, S),), dtype=torch.uint8, device=dev))
+        ops.append(_lib.scratch("md_cp_sweeps_merge", (N, B, S), dev))
     _lib.call("md_cp_sweeps_merge", ops, extra=_CPSweepsAttrs(float(radius), 0))
     return out, offsets_out, status
 
@@ -1888,15 +1885,15 @@ def _bf16_head(who, head, layout):
     return head.contiguous()
 
 
-def _head_loss(who, sym, head, operands, want, ws_bytes, at, grad, out):
+def _head_loss(who, sym, head, operands, want, ws_dims, at, grad, out):
     """One call of a loss over a merged head tensor (the head _bf16_head returned): `sym`(head, *operands, parts, num_pos, total,
     workspace) or, with grad, `sym`_grad with grad (head's shape, f32) in front of the workspace.  want: (shape, dtype) of parts and
-    num_pos -> the dict of total, parts, num_pos [, grad]."""
+    num_pos; ws_dims: the extents `sym`_workspace_bytes takes -> the dict of total, parts, num_pos [, grad]."""
     want = dict(total=((1,), torch.float32), **want)
     if grad:
         want["grad"] = (tuple(head.shape), torch.float32)
     out = _out_dict(who, want, out, head.device)
-    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=head.device)
+    ws = _lib.scratch(sym, ws_dims, head.device)
     outs = [out["parts"], out["num_pos"], out["total"]] + ([out["grad"]] if grad else [])
     _lib.call(sym + "_grad" if grad else sym, [head, *operands, *outs, ws], extra=at)
     return out
@@ -1957,7 +1954,7 @@ def cp_assign_targets(gt_boxes, gt_classes, *, tasks, voxel_size, pc_range, out_
     want = dict(hm=((B, T, C, H, W), torch.float32), anno_box=((B, T, M, 10), torch.float32), ind=((B, T, M), torch.int32),
                 mask=((B, T, M), torch.uint8), cat=((B, T, M), torch.int32), gt_boxes_and_cls=((B, M, 10), torch.float32))
     out = _out_dict("cp_assign_targets", want, out, dev)
-    ws = torch.empty((max(B * T * (G + 1), 1) * 16,), dtype=torch.uint8, device=dev)
+    ws = _lib.scratch("md_cp_assign_targets", (B, T, G), dev)
     _lib.call("md_cp_assign_targets", [g, cls, out["hm"], out["anno_box"], out["ind"], out["mask"], out["cat"], out["gt_boxes_and_cls"], ws],
               extra=at)
     return out
@@ -1990,9 +1987,6 @@ class CenterPointTargets:
 
 
 # ----------------------------------------------------------------------------- CenterPoint training loss (csrc/cploss.hip)
-CP_LOSS_STRIP = 64      # MD_CP_LOSS_STRIP: cells per workgroup of the dense pass (the workspace formula)
-
-
 class _CPLossAttrs(ctypes.Structure):
     _fields_ = [("num_tasks", ctypes.c_int32), ("task", _CPTaskAttrs * CP_MAX_TASKS), ("weight", ctypes.c_float),
                 ("code_weights", ctypes.c_float * 10)]
@@ -2019,7 +2013,7 @@ def cp_loss_attrs(task_offsets, num_classes, weight, code_weights):
 
 
 def cp_loss_workspace_bytes(B, T, H, W):
-    return 8 * B * T * (12 + (H * W + CP_LOSS_STRIP - 1) // CP_LOSS_STRIP)
+    return _lib.workspace_bytes("md_cp_loss", B, T, H, W)
 
 
 def cp_loss(head, targets, at, grad=False, out=None):
@@ -2034,7 +2028,7 @@ def cp_loss(head, targets, at, grad=False, out=None):
     T = int(at.num_tasks)
     want = dict(parts=((T, 12), torch.float32), num_pos=((T,), torch.float32))
     return _head_loss("cp_loss", "md_cp_loss", head, [targets[k] for k in ("hm", "anno_box", "ind", "mask", "cat")], want,
-                      cp_loss_workspace_bytes(B, T, H, W), at, grad, out)
+                      (B, T, H, W), at, grad, out)
 
 
 class CenterPointLoss:
@@ -2069,10 +2063,6 @@ def center_point_loss(head, targets, loss):
 
 
 # ----------------------------------------------------------------------------- KITTI PointPillars training loss (csrc/pploss.hip)
-PP_LOSS_STRIP = 64            # MD_PP_LOSS_STRIP: cells per workgroup of the dense pass (the workspace formula)
-PP_LOSS_COUNT_CHUNK = 4096    # MD_PP_LOSS_COUNT_CHUNK: labels per workgroup of the positive count
-
-
 class _PPLossAttrs(ctypes.Structure):
     _fields_ = [("head", _PPHeadAttrs), ("alpha", ctypes.c_float), ("gamma", ctypes.c_float), ("sigma", ctypes.c_float),
                 ("code_weights", ctypes.c_float * 7), ("cls_weight", ctypes.c_float), ("loc_weight", ctypes.c_float),
@@ -2103,9 +2093,7 @@ def pp_loss_attrs(head_offsets, num_anchors, num_classes, alpha=0.25, gamma=2.0,
 
 
 def pp_loss_workspace_bytes(B, H, W, num_anchors):
-    strips = (H * W + PP_LOSS_STRIP - 1) // PP_LOSS_STRIP
-    chunks = (H * W * num_anchors + PP_LOSS_COUNT_CHUNK - 1) // PP_LOSS_COUNT_CHUNK
-    return 40 * B * strips + 4 * B * chunks
+    return _lib.workspace_bytes("md_pp_loss", B, H, W, num_anchors)
 
 
 def pp_loss(head, labels, reg_targets, anchors, at, grad=False, out=None):
@@ -2124,7 +2112,7 @@ def pp_loss(head, labels, reg_targets, anchors, at, grad=False, out=None):
                          f"{labels.dtype} / {tuple(reg_targets.shape)}")
     want = dict(parts=((5,), torch.float32), num_pos=((B,), torch.float32))
     return _head_loss("pp_loss", "md_pp_loss", head, [labels.contiguous(), _f32c(reg_targets), _f32c(anchors).reshape(-1, 7)], want,
-                      pp_loss_workspace_bytes(B, H, W, A), at, grad, out)
+                      (B, H, W, A), at, grad, out)
 
 
 class PointPillarsLoss:
@@ -2183,8 +2171,6 @@ def assign_targets_batch(anchors, gt_boxes, gt_classes, matched_thr, unmatched_t
 
 # ----------------------------------------------------------------------------- CenterNet training targets (csrc/cntargets.hip)
 CN_MAX_OBJS = 1024            # MD_CN_MAX_OBJS
-CN_LOSS_STRIP = 64            # MD_CN_LOSS_STRIP: cells per workgroup of the dense pass (the workspace formula)
-CN_LOSS_COUNT_CHUNK = 16384   # MD_CN_LOSS_COUNT_CHUNK: heat-map elements per workgroup of the count pass
 
 
 class _CNTargetsAttrs(ctypes.Structure):
@@ -2207,7 +2193,7 @@ def cn_assign_targets(boxes, classes, *, num_classes, feature_map_size, max_objs
     want = dict(hm=((B, C, H, W), torch.float32), ind=((B, M), torch.int32), reg_mask=((B, M), torch.uint8), wh=((B, M, 2), torch.float32),
                 reg=((B, M, 2), torch.float32))
     out = _out_dict("cn_assign_targets", want, out, dev)
-    ws = torch.empty((max(B * M, 1) * 16,), dtype=torch.uint8, device=dev)
+    ws = _lib.scratch("md_cn_assign_targets", (B, M), dev)
     _lib.call("md_cn_assign_targets", [g, cls, out["hm"], out["ind"], out["reg_mask"], out["wh"], out["reg"], ws], extra=at)
     return out
 
@@ -2266,9 +2252,7 @@ def cn_loss_attrs(num_classes, off_hm=0, off_wh=None, off_reg=None, hm_weight=1.
 
 
 def cn_loss_workspace_bytes(B, C, H, W):
-    strips = (H * W + CN_LOSS_STRIP - 1) // CN_LOSS_STRIP
-    chunks = (B * C * H * W + CN_LOSS_COUNT_CHUNK - 1) // CN_LOSS_COUNT_CHUNK
-    return 8 * B * (4 + 2 * strips) + 4 * chunks
+    return _lib.workspace_bytes("md_cn_loss", B, C, H, W)
 
 
 def cn_loss(head, targets, at, grad=False, out=None):
@@ -2281,7 +2265,7 @@ def cn_loss(head, targets, at, grad=False, out=None):
     B, H, W, _ = head.shape
     want = dict(parts=((3,), torch.float32), num_pos=((1,), torch.float32))
     return _head_loss("cn_loss", "md_cn_loss", head, [targets[k] for k in ("hm", "ind", "reg_mask", "wh", "reg")], want,
-                      cn_loss_workspace_bytes(B, int(at.num_classes), H, W), at, grad, out)
+                      (B, int(at.num_classes), H, W), at, grad, out)
 
 
 class CenterNetLoss:
@@ -2322,7 +2306,6 @@ def center_net_loss(head, targets, loss):
 
 # ----------------------------------------------------------------------------- CenterNet training input (csrc/cnaug.hip)
 CNAUG_MAX_BATCH = 65535       # MD_CNAUG_MAX_BATCH
-CNAUG_GREY_CHUNK = 2048       # MD_CNAUG_GREY_CHUNK: output pixels per partial sum of the grey pass (the workspace formula)
 CN_COLOUR_ORDERS = ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0))   # 0 brightness_, 1 contrast_, 2 saturation_
 
 
@@ -2362,7 +2345,7 @@ def cn_aug_transform(sizes, draws, *, rand_crop, scale, shift, flip_prop, input_
 
 def cn_aug_image_workspace_bytes(B, out_h, out_w):
     """bytes of scratch md_cn_aug_image takes with colour augmentation (include/minddet_hip_cnaug.h)"""
-    return 8 * B * ((out_h * out_w + CNAUG_GREY_CHUNK - 1) // CNAUG_GREY_CHUNK + 1)
+    return _lib.workspace_bytes("md_cn_aug_image", B, out_h, out_w)
 
 
 def cn_aug_image(img_u8, sizes, mat_in, mean, std, out_hw, colour=None, stem_layout=True, workspace=True, out=None):
@@ -2384,7 +2367,7 @@ def cn_aug_image(img_u8, sizes, mat_in, mean, std, out_hw, colour=None, stem_lay
     norm = torch.tensor([float(v) for v in mean] + [float(v) for v in std], dtype=torch.float32, device=dev)
     ops = [img_u8, _sizes2("cn_aug_image", sizes, dev), _f32c(mat_in), norm, None if colour is None else _f64c(colour, dev), out]
     if workspace and colour is not None:
-        ops.append(torch.empty((max(cn_aug_image_workspace_bytes(B, ho, wo), 16),), dtype=torch.uint8, device=dev))
+        ops.append(_lib.scratch("md_cn_aug_image", (B, ho, wo), dev))
     _lib.call("md_cn_aug_image", ops, extra=_CNAugImageAttrs(ho, wo, lo, hi))
     return out
 
@@ -2630,7 +2613,7 @@ class KittiCalibration:
 
 def crop_hulls_workspace_bytes(N, B, K):
     """bytes of scratch md_pc_crop_hulls takes (include/minddet_hip_kitti.h)"""
-    return 192 * B * K + 4 * (N // 256 + 3)
+    return _lib.workspace_bytes("md_pc_crop_hulls", N, B, K)
 
 
 def crop_hulls(points, offsets, hulls, hull_count, workspace=True, out=None):
@@ -2657,7 +2640,7 @@ def crop_hulls(points, offsets, hulls, hull_count, workspace=True, out=None):
     keep = torch.empty((N,), dtype=torch.uint8, device=dev)
     ops = [points, _i32c(offsets, dev), _f64c(hulls, dev), _i32c(hull_count, dev), out, offsets_out, keep]
     if workspace:
-        ops.append(torch.empty((crop_hulls_workspace_bytes(N, B, K),), dtype=torch.uint8, device=dev))
+        ops.append(_lib.scratch("md_pc_crop_hulls", (N, B, K), dev))
     _lib.call("md_pc_crop_hulls", ops)
     return out, offsets_out, keep
 

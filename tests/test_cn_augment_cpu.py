@@ -83,8 +83,10 @@ def test_ctypes_mirrors_and_limits_have_the_headers_layout():
     src = open(os.path.join(ROOT, "minddet_amd", "csrc", "cnaug.hip")).read()
     assert "sizeof(md_cn_aug_transform_attrs) == 48 && sizeof(md_cn_aug_image_attrs) == 16" in src
     defines = {k: int(v) for k, v in re.findall(r"^#define (\w+) (\d+)\b", HDR, flags=re.M)}
-    assert (defines["MD_CNAUG_MAX_BATCH"], defines["MD_CNAUG_GREY_CHUNK"]) == (det_ops.CNAUG_MAX_BATCH, det_ops.CNAUG_GREY_CHUNK) == (65535, 2048)
+    assert (defines["MD_CNAUG_MAX_BATCH"], defines["MD_CNAUG_GREY_CHUNK"]) == (det_ops.CNAUG_MAX_BATCH, 2048) == (65535, 2048)
     assert det_ops.cn_aug_image_workspace_bytes(2, 6, 10) == 32 and det_ops.cn_aug_image_workspace_bytes(16, 512, 512) == 8 * 16 * 129
+    # (the chunk decides: 2048 pixels are one partial sum per sample, one more pixel is two)
+    assert det_ops.cn_aug_image_workspace_bytes(1, 1, 2048) == 16 and det_ops.cn_aug_image_workspace_bytes(1, 1, 2049) == 24
     assert det_ops.CN_COLOUR_ORDERS == cc.ORDERS
 
 

@@ -75,8 +75,10 @@ def test_ctypes_mirrors_have_the_headers_layout():
     src = "".join(open(os.path.join(ROOT, "minddet_amd", "csrc", f)).read() for f in ("cntargets.hip", "cnloss.hip"))
     assert "static_assert(sizeof(md_cn_targets_attrs) == 4" in src and "static_assert(sizeof(md_cn_loss_attrs) == 4 * 4 + 3 * 4" in src
     defines = {k: int(v) for k, v in re.findall(r"^#define (\w+) (\d+)\b", HDR, flags=re.M)}
-    assert (defines["MD_CN_MAX_OBJS"], defines["MD_CN_LOSS_STRIP"], defines["MD_CN_LOSS_COUNT_CHUNK"]) == \
-        (det_ops.CN_MAX_OBJS, det_ops.CN_LOSS_STRIP, det_ops.CN_LOSS_COUNT_CHUNK)
+    assert (defines["MD_CN_MAX_OBJS"], defines["MD_CN_LOSS_STRIP"], defines["MD_CN_LOSS_COUNT_CHUNK"]) == (det_ops.CN_MAX_OBJS, 64, 16384)
+    # (each decides the library's answer: 64 cells are one strip of 16 bytes, 16384 heat-map elements one count of 4)
+    assert [det_ops.cn_loss_workspace_bytes(1, 1, 1, w) for w in (64, 65)] == [8 * (4 + 2) + 4, 8 * (4 + 4) + 4]
+    assert [det_ops.cn_loss_workspace_bytes(1, c, 128, 128) for c in (1, 2)] == [8 * (4 + 512) + 4, 8 * (4 + 512) + 8]
 
 
 @pytest.mark.parametrize("case", TARGET_CASES, ids=[c.id for c in TARGET_CASES])

@@ -57,7 +57,7 @@ def test_ctypes_mirrors_and_limits_have_the_headers_layout():
         assert getattr(det_ops, name) == int(re.search(rf"#define {macro} (\d+)", HDR).group(1))
     assert (det_ops.CPAUG_MAX_GT, det_ops.CPAUG_MAX_CAND) == (512, 256) and "#define MD_CPAUG_MAX_BATCH 4096" in HDR
     assert det_ops.cp_aug_count_points_workspace_bytes(2, 3) == 576 and det_ops.cp_aug_select_workspace_bytes(2, 3, 4) == 64
-    assert det_ops.cp_aug_points_workspace_bytes(300, 40, 2) == 484
+    assert det_ops.cp_aug_points_workspace_bytes(300, 40, 2) == 480 <= 484              # (the library's answer, the header's bound)
 
 
 def test_collision_predicate_is_defined_once():

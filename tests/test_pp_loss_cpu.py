@@ -62,7 +62,10 @@ def test_ctypes_mirrors_have_the_headers_layout():
     for got in (det_ops._PPHeadAttrs, dict(PPLoss._fields_)["head"]):
         assert layout(got) == layout(head), got
     defines = {k: int(v) for k, v in re.findall(r"^#define (\w+) (\d+)\b", HDR, flags=re.M)}
-    assert defines["MD_PP_LOSS_STRIP"] == det_ops.PP_LOSS_STRIP and defines["MD_PP_LOSS_COUNT_CHUNK"] == det_ops.PP_LOSS_COUNT_CHUNK
+    assert defines["MD_PP_LOSS_STRIP"] == 64 and defines["MD_PP_LOSS_COUNT_CHUNK"] == 4096
+    # (each decides the library's answer: 64 cells are one strip of 40 bytes, 4096 labels one count of 4)
+    assert [det_ops.pp_loss_workspace_bytes(1, 1, w, 1) for w in (64, 65)] == [40 + 4, 80 + 4]
+    assert [det_ops.pp_loss_workspace_bytes(1, 64, 64, a) for a in (1, 2)] == [40 * 64 + 4, 40 * 64 + 8]
     assert defines["MD_PP_LOSS_MAX_CHANNELS"] >= 2 * 48                                   # both shipped heads (C = 24, 48) with room to spare
 
 

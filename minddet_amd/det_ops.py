@@ -31,6 +31,9 @@ read the same (paths relative to /root/reference/minddet/models):
   KittiCalibration, crop_hulls, kitti_boxes_to_lidar, kitti_rows
                           pointpillars/src/core/box_np_ops.py:395-449, 581-636 (remove_outside_points, the frustums, box_camera_to_lidar),
                           pointpillars/src/data/preprocess.py:59-71, 87 and pointpillars/src/predict.py:204-262, 331-396
+  kitti_eval_flags, kitti_eval_overlaps, kitti_eval_match, kitti_eval_thresholds, kitti_eval_stats
+                          pointpillars/eval_gpu/eval.py:9-297, 483-599 (clean_data, the three overlaps, compute_statistics,
+                          get_thresholds and the sums of eval_class, for all images at once; minddet_amd/kitti_eval.py drives them)
 
 All tensors are torch CUDA tensors; work is enqueued on the current stream; nothing here
 synchronises.  There is no CPU path.
@@ -2684,3 +2687,137 @@ def kitti_rows(dets, count, lidar2cam, p2, image_shape, limit_range=None, lidar_
     out_count = torch.empty((B,), dtype=torch.int32, device=dev)
     _lib.call("md_kitti_rows", [d, _i32c(count, dev), _f64c(lidar2cam, dev), _f64c(p2, dev), _i32c(image_shape, dev), rows, src, out_count], extra=at)
     return rows, src, out_count
+
+
+# ----------------------------------------------------------------------------- KITTI AP evaluation (csrc/kittieval.hip)
+KEVAL_MAX_DETS, KEVAL_MAX_GTS, KEVAL_MAX_IMAGES = 512, 512, 65536      # MD_KEVAL_MAX_DETS, MD_KEVAL_MAX_GTS, MD_KEVAL_MAX_IMAGES
+KEVAL_MAX_CLASSES, KEVAL_MAX_LEVELS, KEVAL_SAMPLE_PTS = 8, 4, 41       # MD_KEVAL_MAX_CLASSES, MD_KEVAL_MAX_LEVELS, MD_KEVAL_SAMPLE_PTS
+
+
+class _KittiEvalFlagsAttrs(ctypes.Structure):
+    _fields_ = [("abs_gt_height", ctypes.c_int32)]
+
+
+class _KittiEvalOverlapsAttrs(ctypes.Structure):
+    _fields_ = [("metric", ctypes.c_int32)]
+
+
+class _KittiEvalStatsAttrs(ctypes.Structure):
+    _fields_ = [("metric", ctypes.c_int32), ("compute_aos", ctypes.c_int32)]
+
+
+def _i64c(t, dev):
+    return t.to(device=dev, dtype=torch.int64).contiguous()
+
+
+def _keval_shape(who, name, t, want):
+    if tuple(t.shape) != tuple(want):
+        raise ValueError(f"{who}: {name} is {list(want)}, got {tuple(t.shape)}")
+
+
+def _keval_limits(who, I=0, Cn=1, K=1, Gt=0, Dt=0, P=0):
+    if Cn < 1 or K < 1:
+        raise ValueError(f"{who}: at least one class and one overlap level")
+    if I > KEVAL_MAX_IMAGES or Cn > KEVAL_MAX_CLASSES or K > KEVAL_MAX_LEVELS:
+        raise ValueError(f"{who}: at most {KEVAL_MAX_IMAGES} images, {KEVAL_MAX_CLASSES} classes and {KEVAL_MAX_LEVELS} overlap levels, got {I}, {Cn}, {K}")
+    if Gt > KEVAL_MAX_IMAGES * KEVAL_MAX_GTS or Dt > KEVAL_MAX_IMAGES * KEVAL_MAX_DETS or P >= 1 << 31:
+        raise ValueError(f"{who}: at most {KEVAL_MAX_GTS} ground truths and {KEVAL_MAX_DETS} detections per image and fewer than 2^31 pairs")
+
+
+def kitti_eval_flags(gt_box, gt_occ, gt_trunc, gt_valid, dt_box, dt_same, abs_gt_height=False):
+    """clean_data for the three difficulties and the Cn classes of gt_valid / dt_same (md_kitti_eval_flags, include/
+    minddet_hip_kittieval.h): gt_box [Gt,4] f64, gt_occ [Gt] i32, gt_trunc [Gt] f64, gt_valid [Cn,Gt] u8, dt_box [Dt,4] f64,
+    dt_same [Cn,Dt] u8 -> (ign_gt [Cn,3,Gt] u8, ign_dt [Cn,3,Dt] u8, num_valid [Cn,3] i32); the flags as 1 + clean_data's."""
+    who, dev = "kitti_eval_flags", gt_box.device
+    if gt_box.dim() != 2 or gt_box.shape[1] != 4 or dt_box.dim() != 2 or dt_box.shape[1] != 4 or gt_valid.dim() != 2:
+        raise ValueError(f"{who}: gt_box is [Gt, 4], dt_box [Dt, 4] and gt_valid [Cn, Gt]")
+    Gt, Dt, Cn = gt_box.shape[0], dt_box.shape[0], gt_valid.shape[0]
+    for name, t, want in (("gt_occ", gt_occ, (Gt,)), ("gt_trunc", gt_trunc, (Gt,)), ("gt_valid", gt_valid, (Cn, Gt)), ("dt_same", dt_same, (Cn, Dt))):
+        _keval_shape(who, name, t, want)
+    _keval_limits(who, Cn=Cn, Gt=Gt, Dt=Dt)
+    ign_gt = torch.empty((Cn, 3, Gt), dtype=torch.uint8, device=dev)
+    ign_dt = torch.empty((Cn, 3, Dt), dtype=torch.uint8, device=dev)
+    num_valid = torch.empty((Cn, 3), dtype=torch.int32, device=dev)
+    _lib.call("md_kitti_eval_flags", [_f64c(gt_box, dev), _i32c(gt_occ, dev), _f64c(gt_trunc, dev), _u8c(gt_valid, dev), _f64c(dt_box, dev),
+                                      _u8c(dt_same, dev), ign_gt, ign_dt, num_valid], extra=_KittiEvalFlagsAttrs(int(bool(abs_gt_height))))
+    return ign_gt, ign_dt, num_valid
+
+
+def kitti_eval_overlaps(gt_off, dt_off, ov_off, gt, dt, metric, pairs):
+    """calculate_overlaps for all images in one launch (md_kitti_eval_overlaps): offsets [I+1] (ov_off i64), gt / dt the image boxes
+    [.,4] f64 for metric 0, the camera boxes [.,7] f64 for metrics 1 and 2; pairs: the length of the result, at least ov_off[I] (the
+    host knows it from the extents) -> ov [pairs] f64, image i's block ground-truth-major [G_i, D_i] at ov_off[i]."""
+    who, dev = "kitti_eval_overlaps", gt.device
+    if metric not in (0, 1, 2):
+        raise ValueError(f"{who}: metric is 0, 1 or 2, got {metric!r}")
+    W = 4 if metric == 0 else 7
+    if gt.dim() != 2 or gt.shape[1] != W or dt.dim() != 2 or dt.shape[1] != W or gt_off.dim() != 1 or gt_off.shape[0] < 1:
+        raise ValueError(f"{who}: metric {metric} takes gt [Gt, {W}] and dt [Dt, {W}] and offsets [I + 1]")
+    I = gt_off.shape[0] - 1
+    _keval_shape(who, "dt_off", dt_off, (I + 1,))
+    _keval_shape(who, "ov_off", ov_off, (I + 1,))
+    _keval_limits(who, I=I, Gt=gt.shape[0], Dt=dt.shape[0], P=int(pairs))
+    ov = torch.empty((int(pairs),), dtype=torch.float64, device=dev)
+    _lib.call("md_kitti_eval_overlaps", [_i32c(gt_off, dev), _i32c(dt_off, dev), _i64c(ov_off, dev), _f64c(gt, dev), _f64c(dt, dev), ov],
+              extra=_KittiEvalOverlapsAttrs(int(metric)))
+    return ov
+
+
+def _keval_match_operands(who, ov, ign_gt, ign_dt, dt_score, gt_off, dt_off, ov_off, min_overlap):
+    if ov.dim() != 1 or ign_gt.dim() != 3 or ign_dt.dim() != 3 or ign_gt.shape[1] != 3 or min_overlap.dim() != 2 or gt_off.dim() != 1 or gt_off.shape[0] < 1:
+        raise ValueError(f"{who}: ov is [P], ign_gt [Cn, 3, Gt], ign_dt [Cn, 3, Dt], min_overlap [Cn, K] and the offsets [I + 1]")
+    dev, (Cn, _, Gt), Dt, I, K = ov.device, ign_gt.shape, ign_dt.shape[2], gt_off.shape[0] - 1, min_overlap.shape[1]
+    for name, t, want in (("ign_dt", ign_dt, (Cn, 3, Dt)), ("dt_score", dt_score, (Dt,)), ("dt_off", dt_off, (I + 1,)), ("ov_off", ov_off, (I + 1,)),
+                          ("min_overlap", min_overlap, (Cn, K))):
+        _keval_shape(who, name, t, want)
+    _keval_limits(who, I=I, Cn=Cn, K=K, Gt=Gt, Dt=Dt, P=ov.shape[0])
+    ops = [_f64c(ov, dev), _u8c(ign_gt, dev), _u8c(ign_dt, dev), _f64c(dt_score, dev), _i32c(gt_off, dev), _i32c(dt_off, dev), _i64c(ov_off, dev),
+           _f64c(min_overlap, dev)]
+    return ops, dev, I, Cn, K, Gt, Dt
+
+
+def kitti_eval_match(ov, ign_gt, ign_dt, dt_score, gt_off, dt_off, ov_off, min_overlap):
+    """Pass 1 of eval_class for every (class, difficulty, overlap level, image) (md_kitti_eval_match) -> matched [Cn,3,K,Gt] f64: the
+    score of the detection that became a true positive for the ground truth, -inf otherwise."""
+    ops, dev, I, Cn, K, Gt, Dt = _keval_match_operands("kitti_eval_match", ov, ign_gt, ign_dt, dt_score, gt_off, dt_off, ov_off, min_overlap)
+    matched = torch.empty((Cn, 3, K, Gt), dtype=torch.float64, device=dev)
+    _lib.call("md_kitti_eval_match", ops + [matched])
+    return matched
+
+
+def kitti_eval_thresholds(sorted_scores, num_valid):
+    """get_thresholds for every task (md_kitti_eval_thresholds): sorted_scores [Cn,3,K,Gt] f64, the rows of kitti_eval_match's result
+    sorted descending; num_valid [Cn,3] i32 -> (thresholds [Cn,3,K,41] f64, NaN behind nthresh; nthresh [Cn,3,K] i32)."""
+    who, dev = "kitti_eval_thresholds", sorted_scores.device
+    if sorted_scores.dim() != 4 or sorted_scores.shape[1] != 3:
+        raise ValueError(f"{who}: the scores are [Cn, 3, K, Gt], got {tuple(sorted_scores.shape)}")
+    Cn, _, K, Gt = sorted_scores.shape
+    _keval_shape(who, "num_valid", num_valid, (Cn, 3))
+    _keval_limits(who, Cn=Cn, K=K, Gt=Gt)
+    thresholds = torch.empty((Cn, 3, K, KEVAL_SAMPLE_PTS), dtype=torch.float64, device=dev)
+    nthresh = torch.empty((Cn, 3, K), dtype=torch.int32, device=dev)
+    _lib.call("md_kitti_eval_thresholds", [_f64c(sorted_scores, dev), _i32c(num_valid, dev), thresholds, nthresh])
+    return thresholds, nthresh
+
+
+def kitti_eval_stats(ov, ign_gt, ign_dt, dt_score, gt_off, dt_off, ov_off, min_overlap, thresholds, nthresh, gt_box, gt_dc, dt_box, gt_alpha,
+                     dt_alpha, metric, compute_aos=False):
+    """Pass 2 of eval_class for every (task, threshold, image) and the sums over the images (md_kitti_eval_stats) -> (img_counts
+    [Cn,3,K,41,I,3] i32 (tp, fp, fn), img_sim [Cn,3,K,41,I] f64, pr_counts [Cn,3,K,41,3] i32, pr_sim [Cn,3,K,41] f64); rows at or
+    behind nthresh are zero."""
+    who = "kitti_eval_stats"
+    if metric not in (0, 1, 2):
+        raise ValueError(f"{who}: metric is 0, 1 or 2, got {metric!r}")
+    ops, dev, I, Cn, K, Gt, Dt = _keval_match_operands(who, ov, ign_gt, ign_dt, dt_score, gt_off, dt_off, ov_off, min_overlap)
+    N = KEVAL_SAMPLE_PTS
+    for name, t, want in (("thresholds", thresholds, (Cn, 3, K, N)), ("nthresh", nthresh, (Cn, 3, K)), ("gt_box", gt_box, (Gt, 4)), ("gt_dc", gt_dc, (Gt,)),
+                          ("dt_box", dt_box, (Dt, 4)), ("gt_alpha", gt_alpha, (Gt,)), ("dt_alpha", dt_alpha, (Dt,))):
+        _keval_shape(who, name, t, want)
+    img_counts = torch.empty((Cn, 3, K, N, I, 3), dtype=torch.int32, device=dev)
+    img_sim = torch.empty((Cn, 3, K, N, I), dtype=torch.float64, device=dev)
+    pr_counts = torch.empty((Cn, 3, K, N, 3), dtype=torch.int32, device=dev)
+    pr_sim = torch.empty((Cn, 3, K, N), dtype=torch.float64, device=dev)
+    ops += [_f64c(thresholds, dev), _i32c(nthresh, dev), _f64c(gt_box, dev), _u8c(gt_dc, dev), _f64c(dt_box, dev), _f64c(gt_alpha, dev),
+            _f64c(dt_alpha, dev), img_counts, img_sim, pr_counts, pr_sim]
+    _lib.call("md_kitti_eval_stats", ops, extra=_KittiEvalStatsAttrs(int(metric), int(bool(compute_aos))))
+    return img_counts, img_sim, pr_counts, pr_sim

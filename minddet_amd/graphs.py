@@ -1607,6 +1607,17 @@ class PointPillarsKITTIPoints(Module):
                                                   limit_range=limit, lidar_input=lidar_input)
         return rows, src, out_count, dets
 
+    def evaluate_kitti(self, rows, count, gt_annos, class_names, current_classes=(0, 1, 2), protocol="full", difficultys=(0, 1, 2)):
+        """The official KITTI result of forward_kitti's rows (rows [B,M,14], out_count [B]) against the ground-truth annotation dicts of
+        the same B frames, on the device: kitti_eval.PackedEval.with_rows takes the rows as they lie (no host copy), the md_kitti_eval_*
+        operators count, kitti_eval.get_official_eval_result(backend="device") divides and prints.  class_names: the detector's label
+        names (rows[..., 13] indexes them).  -> what get_official_eval_result returns on rows_to_annos of the same rows."""
+        from . import kitti_eval
+
+        table = kitti_eval.CLASS_NAMES_MS if protocol == "ms" else kitti_eval.CLASS_NAMES_FULL
+        packed = kitti_eval.pack_annos(gt_annos, None, table, device=rows.device).with_rows(rows, count, class_names)
+        return kitti_eval.get_official_eval_result(gt_annos, None, list(current_classes), protocol, difficultys, backend="device", packed=packed)
+
 
 # ----------------------------------------------------------------------------- YOLOv5 (build-authored; parity unpinned)
 SPPF_FUSED = os.environ.get("MD_SPPF_FUSED", "1") != "0"    # A/B knob: 0 = three md_maxpool2d launches + four concat copies per SPPF block

@@ -25,6 +25,12 @@ numba.cuda) are checked against a scalar restatement of the matching rules and h
 as is any run on real KITTI results.  `rows_to_annos` formats the rows that det_ops.kitti_rows (md_kitti_rows) wrote on the device -- the same
 filters, clip and alpha for a batch with nothing read back in between -- into the same dicts.  The lidar -> camera -> image box geometry reproduces the reference's box_ops.py outputs (same
 golden file); the annotation writer's filter rules (predict.py needs skimage through kitti_common: not importable) are restated.  Reference quirk: eval_utils.get_split_parts has no guard, fewer than 50 images crash it.
+
+The device path (at the end of this file; include/minddet_hip_kittieval.h): pack_annos lays the annotations of all images out as one flat
+set of tensors (PackedEval; with_rows takes the detection half from md_kitti_rows' device rows), eval_class_device runs clean_data, the
+overlaps, both matching passes, get_thresholds and the sums over the images as the five md_kitti_eval_* operators and ends in the same
+host tail as eval_class; get_official_eval_result(backend="device") selects it.  The host functions above stay as they are: they are the
+default and the judge of the device path (tests/test_kitti_eval_device_gpu.py).
 """
 import numpy as np
 
@@ -355,6 +361,23 @@ def calculate_overlaps(gt_annos, dt_annos, metric, rotate_iou=None):
     return [fn(d, g) for d, g in zip(_boxes_of(dt_annos, metric), _boxes_of(gt_annos, metric))]
 
 
+def _curves_from_counts(pr, precision, recall, aos=None):
+    """The tail of eval_class (eval_gpu/eval.py:577-594) for one (class, difficulty, overlap level): pr [nt,4] (tp, fp, fn, similarity
+    summed over the images, one row per threshold) -> the 41-long zero rows precision / recall / aos filled in place: the divisions,
+    then the right-to-left envelope.  eval_class and eval_class_device both end here."""
+    nt = len(pr)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        recall[:nt] = pr[:, 0] / (pr[:, 0] + pr[:, 2])
+        precision[:nt] = pr[:, 0] / (pr[:, 0] + pr[:, 1])
+        if aos is not None:
+            aos[:nt] = pr[:, 3] / (pr[:, 0] + pr[:, 1])
+    for i in range(nt):      # the envelope runs over the whole 41-long row (zeros past nt), as in :590-594
+        precision[i] = np.max(precision[i:])
+        recall[i] = np.max(recall[i:])
+        if aos is not None:
+            aos[i] = np.max(aos[i:])
+
+
 def eval_class(gt_annos, dt_annos, current_classes, difficultys, metric, min_overlaps, compute_aos=False,
                class_names=CLASS_NAMES_FULL, rotate_iou=None):
     """eval_gpu/eval.py:483-599 -> {"recall", "precision", "orientation"}: [class, difficulty, min_overlap, 41]."""
@@ -390,17 +413,7 @@ def eval_class(gt_annos, dt_annos, current_classes, difficultys, metric, min_ove
                         pr[t, 2] += fn
                         if sim != -1:
                             pr[t, 3] += sim
-                nt = len(thresholds)
-                with np.errstate(divide="ignore", invalid="ignore"):
-                    recall[m, n, k, :nt] = pr[:, 0] / (pr[:, 0] + pr[:, 2])
-                    precision[m, n, k, :nt] = pr[:, 0] / (pr[:, 0] + pr[:, 1])
-                    if compute_aos:
-                        aos[m, n, k, :nt] = pr[:, 3] / (pr[:, 0] + pr[:, 1])
-                for i in range(nt):      # the envelope runs over the whole 41-long row (zeros past nt), as in :590-594
-                    precision[m, n, k, i] = np.max(precision[m, n, k, i:])
-                    recall[m, n, k, i] = np.max(recall[m, n, k, i:])
-                    if compute_aos:
-                        aos[m, n, k, i] = np.max(aos[m, n, k, i:])
+                _curves_from_counts(pr, precision[m, n, k], recall[m, n, k], aos[m, n, k] if compute_aos else None)
     return {"recall": recall, "precision": precision, "orientation": aos}
 
 
@@ -421,10 +434,26 @@ _NAMES_FULL = {0: "Car", 1: "Pedestrian", 2: "Cyclist", 3: "Van", 4: "Person_sit
 _NAMES_MS = {0: "Car", 1: "Pedestrian", 2: "Cyclist", 3: "Van", 4: "Person_sitting", 5: "car", 6: "tractor", 7: "trailer"}
 
 
-def get_official_eval_result(gt_annos, dt_annos, current_classes, protocol="full", difficultys=(0, 1, 2), rotate_iou=None):
+def _wants_aos(dt_annos):
+    """eval_gpu/eval.py:738-744: the first non-empty detection annotation decides"""
+    for anno in dt_annos:
+        if anno["alpha"].shape[0] != 0:
+            return bool(anno["alpha"][0] != -10)
+    return False
+
+
+def get_official_eval_result(gt_annos, dt_annos, current_classes, protocol="full", difficultys=(0, 1, 2), rotate_iou=None, backend="host",
+                             packed=None):
     """protocol "ms": eval_utils.py:645-702 (what pointpillars/eval.py prints: image-bbox AP, 11 points) -> (text, map_bbox
     [class, difficulty, 1]).  protocol "full": eval_gpu/eval.py:697-885 -> (text, dict of the *_R40 entries); AOS is computed
-    when the first non-empty detection annotation carries a real alpha (!= -10), :738-744."""
+    when the first non-empty detection annotation carries a real alpha (!= -10), :738-744.
+    backend "host": eval_class, numpy loops around md_rotate_iou_eval.  backend "device": the annotations are packed once
+    (pack_annos; or `packed`, a PackedEval made earlier, e.g. by PackedEval.with_rows, and then dt_annos is not read) and every metric
+    runs through eval_class_device: the md_kitti_eval_* operators, with the divisions and the envelope on the host as before."""
+    if backend not in ("host", "device"):
+        raise ValueError(f"backend is 'host' or 'device', got {backend!r}")
+    if packed is not None and backend != "device":
+        raise ValueError("a PackedEval is evaluated by backend='device'")
     ms = protocol == "ms"
     names, table = (_NAMES_MS, _MIN_OVERLAPS_MS) if ms else (_NAMES_FULL, _MIN_OVERLAPS_FULL)
     to_class = {v: k for k, v in names.items()}
@@ -433,8 +462,19 @@ def get_official_eval_result(gt_annos, dt_annos, current_classes, protocol="full
     classes = [to_class[c] if isinstance(c, str) else c for c in current_classes]
     min_overlaps = table[:, :, classes]
     cn = CLASS_NAMES_MS if ms else CLASS_NAMES_FULL
+    if backend == "device":
+        if packed is None:
+            packed = pack_annos(gt_annos, dt_annos, cn)
+        elif tuple(packed.class_names) != tuple(cn):
+            raise ValueError(f"the PackedEval was made for the class table {packed.class_names}, protocol {protocol!r} takes {cn}")
+
+        def run(metric, diffs, aos):
+            return eval_class_device(packed, classes, diffs, metric, min_overlaps, aos)
+    else:
+        def run(metric, diffs, aos):
+            return eval_class(gt_annos, dt_annos, classes, diffs, metric, min_overlaps, aos, cn, rotate_iou)
     if ms:
-        ret = eval_class(gt_annos, dt_annos, classes, difficultys, 0, min_overlaps, False, cn)
+        ret = run(0, difficultys, False)
         map_bbox = get_map(ret["precision"])
         text = "        Easy   Mod    Hard\n"
         for j, c in enumerate(classes):
@@ -442,14 +482,10 @@ def get_official_eval_result(gt_annos, dt_annos, current_classes, protocol="full
                 text += f"{names[c]} " + "AP@{:.2f}, {:.2f}, {:.2f}:".format(*min_overlaps[i, :, j]) + "\n"
                 text += f"bbox AP: {map_bbox[j, 0, i]: .2f}, {map_bbox[j, 1, i]: .2f}, {map_bbox[j, 2, i]: .2f}\n"
         return text, map_bbox
-    compute_aos = False
-    for anno in dt_annos:
-        if anno["alpha"].shape[0] != 0:
-            compute_aos = bool(anno["alpha"][0] != -10)
-            break
+    compute_aos = _wants_aos(dt_annos) if packed is None else packed.compute_aos
     res = {}
     for metric, key in ((0, "bbox"), (1, "bev"), (2, "3d")):
-        ret = eval_class(gt_annos, dt_annos, classes, (0, 1, 2), metric, min_overlaps, compute_aos and metric == 0, cn, rotate_iou)
+        ret = run(metric, (0, 1, 2), compute_aos and metric == 0)
         res[key] = (get_map(ret["precision"]), get_map_r40(ret["precision"]))
         if metric == 0 and compute_aos:
             res["aos"] = (get_map(ret["orientation"]), get_map_r40(ret["orientation"]))
@@ -470,3 +506,187 @@ def get_official_eval_result(gt_annos, dt_annos, current_classes, protocol="full
                     for d, dn in enumerate(("easy", "moderate", "hard")):
                         out[f"{names[c]}_{tag}/{dn}_R40"] = float(v[j, d, 0])
     return text, out
+
+
+# ----------------------------------------------------------------------------- the device path (include/minddet_hip_kittieval.h)
+MAX_DETS, MAX_GTS, MAX_IMAGES, MAX_CLASSES, MAX_LEVELS = 512, 512, 65536, 8, 4     # the MD_KEVAL_MAX_* of the header
+
+
+def _valid_codes(names, class_names):
+    """[Cn, n] uint8: 1 + the `valid` of clean_data for class c by index in class_names (2 the class, 1 its neighbour class, 0 other)"""
+    out = np.zeros((len(class_names), len(names)), np.uint8)
+    for c, cur in enumerate(class_names):
+        cur = cur.lower()
+        for i, name in enumerate(names):
+            name = str(name).lower()
+            if name == cur:
+                out[c, i] = 2
+            elif (cur == "pedestrian" and name == "person_sitting") or (cur == "car" and name == "van"):
+                out[c, i] = 1
+    return out
+
+
+class PackedEval:
+    """Annotations of I images as one flat set of tensors, the operands of the md_kitti_eval_* operators (the layout is stated in
+    include/minddet_hip_kittieval.h).  Names stay on the host: they arrive as gt_valid / gt_dc / dt_same codes per class of
+    `class_names`.  Made by pack_annos; with_rows replaces the detection half by device rows.  Host-side facts: I, gt_counts [I],
+    pairs (the length the overlap tensor takes, >= ov_off[I]), compute_aos, abs_gt_height (the "ms" table's rule)."""
+    GT = ("gt_box", "gt_alpha", "gt_occ", "gt_trunc", "gt_dc", "gt_valid", "gt_cam")
+    DT = ("dt_box", "dt_alpha", "dt_score", "dt_same", "dt_cam")
+
+    def __init__(self, class_names, device):
+        self.class_names, self.device = tuple(class_names), device
+        self.abs_gt_height = self.class_names == CLASS_NAMES_MS
+        self.gt_cam = self.dt_cam = self.dt_off = None
+        self.compute_aos = False
+
+    def with_rows(self, rows, count, class_names):
+        """The detection half from the device tensors det_ops.kitti_rows / forward_kitti return: rows [I,M,14] f32 (alpha, bbox,
+        dimensions l h w, location, rotation_y, score, label), count [I]; class_names: the detector's label names.  fp32 widened to
+        float64, label -> class through a small device table, offsets from a device scan of count; nothing is copied to the host.
+        The detection tensors have I M rows, the first dt_off[I] of them are the detections (what pack_annos(rows_to_annos(...)) holds),
+        the rest is zero; the overlap tensor takes sum G_i M elements.  compute_aos is set: the rows carry a real alpha."""
+        import torch
+
+        if rows.dim() != 3 or rows.shape[2] != 14 or rows.shape[0] != self.I or tuple(count.shape) != (self.I,):
+            raise ValueError(f"with_rows: rows are [{self.I}, M, 14] and count [{self.I}], got {tuple(rows.shape)} and {tuple(count.shape)}")
+        B, M = rows.shape[:2]
+        if M > MAX_DETS:
+            raise ValueError(f"with_rows: at most {MAX_DETS} detections per image, got {M}")
+        pairs = int(self.gt_counts.sum()) * M
+        if pairs >= 1 << 31:
+            raise ValueError("with_rows: 2^31 or more overlap pairs")
+        dev = rows.device
+        out = PackedEval(self.class_names, dev)
+        for k in ("I", "gt_counts", "gt_off") + self.GT:
+            setattr(out, k, getattr(self, k))
+        cnt = count.to(torch.int64).clamp(0, M)
+        off = torch.zeros((B + 1,), dtype=torch.int64, device=dev)
+        off[1:] = torch.cumsum(cnt, 0)
+        j = torch.arange(B * M, dtype=torch.int64, device=dev)
+        b = torch.searchsorted(off[1:].contiguous(), j, right=True).clamp(max=max(B - 1, 0))
+        valid = j < off[B]
+        src = torch.where(valid, b * M + (j - off[b]), torch.zeros_like(j)) if B * M else j
+        r = torch.where(valid[:, None], rows.reshape(B * M, 14)[src].to(torch.float64), torch.zeros((), dtype=torch.float64, device=dev))
+        table = torch.from_numpy(np.array([[n.lower() == c.lower() for n in class_names] for c in self.class_names], np.uint8).reshape(
+            len(self.class_names), len(class_names))).to(dev)
+        label = r[:, 13].to(torch.int64).clamp(0, max(len(class_names) - 1, 0))
+        out.dt_off = off.to(torch.int32)
+        out.dt_alpha, out.dt_box, out.dt_score = r[:, 0].contiguous(), r[:, 1:5].contiguous(), r[:, 12].contiguous()
+        out.dt_cam = torch.cat([r[:, 8:11], r[:, 5:8], r[:, 11:12]], 1).contiguous()
+        out.dt_same = (table[:, label] * valid.to(torch.uint8)[None]).contiguous()
+        ov_off = torch.zeros((B + 1,), dtype=torch.int64, device=dev)
+        ov_off[1:] = torch.cumsum(torch.from_numpy(self.gt_counts.astype(np.int64)).to(dev) * cnt, 0)
+        out.ov_off, out.pairs, out.compute_aos = ov_off, pairs, True
+        return out
+
+
+def pack_annos(gt_annos, dt_annos, class_names=CLASS_NAMES_FULL, device="cuda"):
+    """Annotation dicts of I images -> PackedEval.  dt_annos None packs the ground truth alone (for PackedEval.with_rows).
+    Annotations without location / dimensions / rotation_y pack without the *_cam tensors (metrics 1 and 2 then raise ValueError).
+    Beyond the limits of include/minddet_hip_kittieval.h: ValueError."""
+    import torch
+
+    I = len(gt_annos)
+    if dt_annos is not None and len(dt_annos) != I:
+        raise ValueError("gt_annos and dt_annos must pair up image by image")
+    if I > MAX_IMAGES or len(class_names) > MAX_CLASSES or len(class_names) < 1:
+        raise ValueError(f"pack_annos: at most {MAX_IMAGES} images and 1 to {MAX_CLASSES} classes")
+    p = PackedEval(class_names, device)
+    p.I = I
+
+    def put(a, dtype):
+        return torch.from_numpy(np.ascontiguousarray(a, dtype)).to(device)
+
+    def col(annos, key, width=None):
+        parts = [np.asarray(a[key], np.float64).reshape((-1, width) if width else (-1,)) for a in annos]
+        return np.concatenate(parts, 0) if parts else np.zeros((0, width) if width else (0,))
+
+    def cam(annos):
+        if not all(k in a for a in annos for k in ("location", "dimensions", "rotation_y")):
+            return None
+        return np.concatenate([col(annos, "location", 3), col(annos, "dimensions", 3), col(annos, "rotation_y").reshape(-1, 1)], 1)
+
+    def offsets(annos, limit, what):
+        n = np.array([len(a["name"]) for a in annos], np.int64)
+        if len(n) and n.max() > limit:
+            raise ValueError(f"pack_annos: at most {limit} {what} per image, got {int(n.max())}")
+        return n, np.concatenate([[0], np.cumsum(n)])
+
+    g, g_off = offsets(gt_annos, MAX_GTS, "ground truths")
+    names = [str(n) for a in gt_annos for n in a["name"]]
+    p.gt_counts = g
+    p.gt_off = put(g_off, np.int32)
+    p.gt_box, p.gt_alpha, p.gt_trunc = put(col(gt_annos, "bbox", 4), np.float64), put(col(gt_annos, "alpha"), np.float64), put(col(gt_annos, "truncated"), np.float64)
+    p.gt_occ = put(col(gt_annos, "occluded"), np.int32)
+    p.gt_dc = put(np.array([n == "DontCare" for n in names], np.uint8).reshape(-1), np.uint8)
+    p.gt_valid = put(_valid_codes(names, class_names), np.uint8)
+    c = cam(gt_annos)
+    p.gt_cam = None if c is None else put(c, np.float64)
+    if dt_annos is None:
+        return p
+    d, d_off = offsets(dt_annos, MAX_DETS, "detections")
+    ov = np.concatenate([[0], np.cumsum(g * d)])
+    if ov[-1] >= 1 << 31:
+        raise ValueError("pack_annos: 2^31 or more overlap pairs")
+    dnames = [str(n).lower() for a in dt_annos for n in a["name"]]
+    p.dt_off, p.ov_off, p.pairs = put(d_off, np.int32), put(ov, np.int64), int(ov[-1])
+    p.dt_box, p.dt_alpha, p.dt_score = put(col(dt_annos, "bbox", 4), np.float64), put(col(dt_annos, "alpha"), np.float64), put(col(dt_annos, "score"), np.float64)
+    p.dt_same = put(np.array([[n == cn.lower() for n in dnames] for cn in class_names], np.uint8).reshape(len(class_names), len(dnames)), np.uint8)
+    c = cam(dt_annos)
+    p.dt_cam = None if c is None else put(c, np.float64)
+    p.compute_aos = _wants_aos(dt_annos)
+    return p
+
+
+def device_tables(packed, current_classes, metric, min_overlaps, compute_aos=False):
+    """The five md_kitti_eval_* calls on a PackedEval -> dict of device tensors: ign_gt, ign_dt, num_valid, ov, matched, thresholds,
+    nthresh, img_counts, img_sim, pr_counts, pr_sim, each [class of current_classes, 3 difficulties, overlap level, ...].  Nothing is
+    read back here."""
+    import torch
+
+    from . import det_ops
+    if metric not in (0, 1, 2):
+        raise ValueError("unknown metric")
+    if metric != 0 and (packed.gt_cam is None or packed.dt_cam is None):
+        raise ValueError("metrics 1 and 2 take location, dimensions and rotation_y, which these annotations lack")
+    if packed.dt_off is None:
+        raise ValueError("this PackedEval holds ground truth only: pack detections, or use with_rows")
+    cls = [int(c) for c in current_classes]
+    mo = np.asarray(min_overlaps, np.float64)[:, metric, :]                 # [K, class]
+    if mo.shape[1] != len(cls) or not cls or max(cls) >= len(packed.class_names) or min(cls) < 0:
+        raise ValueError("min_overlaps is [K, 3, len(current_classes)] and the classes index the pack's class table")
+    if mo.shape[0] > MAX_LEVELS:
+        raise ValueError(f"at most {MAX_LEVELS} overlap levels")
+    dev = packed.gt_box.device
+    idx = torch.tensor(cls, dtype=torch.int64, device=dev)
+    min_overlap = torch.from_numpy(np.ascontiguousarray(mo.T)).to(dev)
+    t = {}
+    t["ign_gt"], t["ign_dt"], t["num_valid"] = det_ops.kitti_eval_flags(packed.gt_box, packed.gt_occ, packed.gt_trunc, packed.gt_valid[idx],
+                                                                        packed.dt_box, packed.dt_same[idx], packed.abs_gt_height)
+    gt, dt = (packed.gt_box, packed.dt_box) if metric == 0 else (packed.gt_cam, packed.dt_cam)
+    t["ov"] = det_ops.kitti_eval_overlaps(packed.gt_off, packed.dt_off, packed.ov_off, gt, dt, metric, packed.pairs)
+    offs = (packed.gt_off, packed.dt_off, packed.ov_off, min_overlap)
+    t["matched"] = det_ops.kitti_eval_match(t["ov"], t["ign_gt"], t["ign_dt"], packed.dt_score, *offs)
+    ordered = torch.sort(t["matched"], dim=-1, descending=True).values      # plumbing: equal values are interchangeable
+    t["thresholds"], t["nthresh"] = det_ops.kitti_eval_thresholds(ordered, t["num_valid"])
+    t["img_counts"], t["img_sim"], t["pr_counts"], t["pr_sim"] = det_ops.kitti_eval_stats(
+        t["ov"], t["ign_gt"], t["ign_dt"], packed.dt_score, *offs, t["thresholds"], t["nthresh"], packed.gt_box, packed.gt_dc, packed.dt_box,
+        packed.gt_alpha, packed.dt_alpha, metric, compute_aos)
+    return t
+
+
+def eval_class_device(packed, current_classes, difficultys, metric, min_overlaps, compute_aos=False):
+    """eval_class on the device path: the count tables come from device_tables (one read of [class, 3, K, 41] counts at the end), the
+    divisions and the envelope from the helper eval_class ends in.  Same dict, shapes and NaN conventions as eval_class."""
+    t = device_tables(packed, current_classes, metric, min_overlaps, compute_aos)
+    counts, sim, nth = t["pr_counts"].cpu().numpy().astype(np.float64), t["pr_sim"].cpu().numpy(), t["nthresh"].cpu().numpy()
+    shape = [len(current_classes), len(difficultys), counts.shape[2], N_SAMPLE_PTS]
+    precision, recall, aos = np.zeros(shape), np.zeros(shape), np.zeros(shape)
+    for m in range(shape[0]):
+        for n, difficulty in enumerate(difficultys):
+            for k in range(shape[2]):
+                nt = int(nth[m, difficulty, k])
+                pr = np.concatenate([counts[m, difficulty, k, :nt], sim[m, difficulty, k, :nt, None]], 1)
+                _curves_from_counts(pr, precision[m, n, k], recall[m, n, k], aos[m, n, k] if compute_aos else None)
+    return {"recall": recall, "precision": precision, "orientation": aos}

@@ -34,6 +34,9 @@ read the same (paths relative to /root/reference/minddet/models):
   kitti_eval_flags, kitti_eval_overlaps, kitti_eval_match, kitti_eval_thresholds, kitti_eval_stats
                           pointpillars/eval_gpu/eval.py:9-297, 483-599 (clean_data, the three overlaps, compute_statistics,
                           get_thresholds and the sums of eval_class, for all images at once; minddet_amd/kitti_eval.py drives them)
+  coco_eval_rows, coco_eval_match, coco_eval_accumulate
+                          centernet/src/post_process.py:64-89 (to_float, convert_eval_format) and the COCOeval bbox evaluate() /
+                          accumulate() called at centernet/eval.py:181-187; minddet_amd/coco_eval.py drives them
 
 All tensors are torch CUDA tensors; work is enqueued on the current stream; nothing here
 synchronises.  There is no CPU path.
@@ -2821,3 +2824,103 @@ def kitti_eval_stats(ov, ign_gt, ign_dt, dt_score, gt_off, dt_off, ov_off, min_o
             _f64c(dt_alpha, dev), img_counts, img_sim, pr_counts, pr_sim]
     _lib.call("md_kitti_eval_stats", ops, extra=_KittiEvalStatsAttrs(int(metric), int(bool(compute_aos))))
     return img_counts, img_sim, pr_counts, pr_sim
+
+
+# ----------------------------------------------------------------------------- COCO bbox AP evaluation (csrc/cocoeval.hip)
+COCOEVAL_MAX_DETS, COCOEVAL_MAX_GTS, COCOEVAL_MAX_IMAGE_DETS = 100, 256, 512      # MD_COCOEVAL_MAX_DETS, _MAX_GTS, _MAX_IMAGE_DETS
+COCOEVAL_MAX_CELLS, COCOEVAL_MAX_CATS, COCOEVAL_MAX_ROWS = 1 << 24, 128, 1 << 26   # MD_COCOEVAL_MAX_CELLS, _MAX_CATS, _MAX_ROWS
+COCOEVAL_MAX_LABELS, COCOEVAL_MAX_THRS, COCOEVAL_MAX_AREAS = 4096, 16, 8           # MD_COCOEVAL_MAX_LABELS, _MAX_THRS, _MAX_AREAS
+COCOEVAL_MAX_RECS, COCOEVAL_MAX_MAXDETS = 256, 8                                   # MD_COCOEVAL_MAX_RECS, _MAX_MAXDETS
+
+
+class _CocoEvalRowsAttrs(ctypes.Structure):
+    _fields_ = [("first_image", ctypes.c_int32)]
+
+
+def _ceval_limits(who, C=1, Kc=1, Gt=0, Dt=0, T=1, A=1, R=1, M=1):
+    if min(C, Kc, T, A, R, M) < 1:
+        raise ValueError(f"{who}: at least one cell, category, threshold, area range, recall threshold and maxDets value")
+    if C >= COCOEVAL_MAX_CELLS or Kc > COCOEVAL_MAX_CATS or Gt > COCOEVAL_MAX_ROWS or Dt > COCOEVAL_MAX_ROWS:
+        raise ValueError(f"{who}: fewer than {COCOEVAL_MAX_CELLS} cells, at most {COCOEVAL_MAX_CATS} categories and {COCOEVAL_MAX_ROWS} rows, got "
+                         f"{C}, {Kc}, {max(Gt, Dt)}")
+    if T > COCOEVAL_MAX_THRS or A > COCOEVAL_MAX_AREAS or R > COCOEVAL_MAX_RECS or M > COCOEVAL_MAX_MAXDETS or A * T * Dt >= 1 << 31:
+        raise ValueError(f"{who}: at most {COCOEVAL_MAX_THRS} IoU thresholds, {COCOEVAL_MAX_AREAS} area ranges, {COCOEVAL_MAX_RECS} recall thresholds, "
+                         f"{COCOEVAL_MAX_MAXDETS} maxDets values and fewer than 2^31 (area range, threshold, row) entries")
+
+
+def coco_eval_rows(dets, count, label_to_k, first_image, dt_box, dt_area, dt_score, dt_cat, dt_rank, dt_beg, dt_cnt, dt_src):
+    """dets_to_coco + the grouping into (image, category) cells for one batch, nothing read back (md_coco_eval_rows, include/
+    minddet_hip_cocoeval.h): dets [B,max_det,6] f32 (x1, y1, x2, y2, score, label), count [B] i32, label_to_k [L] i32 (-1 drops the row).
+    The eight outputs are the operands of the whole set (Dt = I max_det rows, I Kc cells), written in place for the images
+    first_image .. first_image + B - 1: dt_box [Dt,4] f64, dt_area, dt_score [Dt] f64, dt_cat, dt_rank [Dt] i32, dt_beg, dt_cnt [I Kc]
+    i32, dt_src [Dt] i32."""
+    who = "coco_eval_rows"
+    if dets.dim() != 3 or dets.shape[2] != 6 or dets.shape[1] < 1 or dets.dtype != torch.float32:
+        raise ValueError(f"{who}: dets are [B, max_det, 6] float32, got {tuple(dets.shape)} {dets.dtype}")
+    dev, (B, max_det) = dets.device, dets.shape[:2]
+    if max_det > COCOEVAL_MAX_IMAGE_DETS:
+        raise ValueError(f"{who}: at most {COCOEVAL_MAX_IMAGE_DETS} rows per image, got {max_det}")
+    if label_to_k.dim() != 1 or not 1 <= label_to_k.shape[0] <= COCOEVAL_MAX_LABELS:
+        raise ValueError(f"{who}: label_to_k is [L], 1 <= L <= {COCOEVAL_MAX_LABELS}")
+    _keval_shape(who, "count", count, (B,))
+    if dt_box.dim() != 2 or dt_beg.dim() != 1 or dt_box.shape[0] < 1 or dt_box.shape[0] % max_det or dt_beg.shape[0] < 1:
+        raise ValueError(f"{who}: dt_box is [I max_det, 4] and dt_beg [I Kc]")
+    Dt, C = dt_box.shape[0], dt_beg.shape[0]
+    I = Dt // max_det
+    if C % I:
+        raise ValueError(f"{who}: {C} cells are no multiple of {I} images")
+    outs = (("dt_box", dt_box, (Dt, 4), torch.float64), ("dt_area", dt_area, (Dt,), torch.float64), ("dt_score", dt_score, (Dt,), torch.float64),
+            ("dt_cat", dt_cat, (Dt,), torch.int32), ("dt_rank", dt_rank, (Dt,), torch.int32), ("dt_beg", dt_beg, (C,), torch.int32),
+            ("dt_cnt", dt_cnt, (C,), torch.int32), ("dt_src", dt_src, (Dt,), torch.int32))
+    for name, t, want, dtype in outs:
+        _keval_shape(who, name, t, want)
+        if t.dtype != dtype or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{who}: {name} is a contiguous {dtype} tensor on {dev} (it is written in place)")
+    _ceval_limits(who, C=C, Kc=C // I, Dt=Dt)
+    if first_image < 0 or first_image + B > I:
+        raise ValueError(f"{who}: images {first_image} .. {first_image + B - 1} of {I}")
+    _lib.call("md_coco_eval_rows", [dets.contiguous(), _i32c(count, dev), _i32c(label_to_k, dev)] + [t for _, t, _, _ in outs],
+              extra=_CocoEvalRowsAttrs(int(first_image)))
+
+
+def coco_eval_match(gt_beg, gt_cnt, dt_beg, dt_cnt, gt_box, gt_area, gt_crowd, gt_ignore, dt_box, dt_area, iou_thr, area_rng):
+    """COCOBboxEval._evaluate_img for every (cell, area range) and all thresholds (md_coco_eval_match): the cell tables [I Kc] i32, the
+    ground-truth rows (gt_box [Gt,4], gt_area [Gt] f64, gt_crowd, gt_ignore [Gt] u8), the detection rows (dt_box [Dt,4], dt_area [Dt]
+    f64), iou_thr [T] f64, area_rng [A,2] f64 -> (dtm [A,T,Dt] i32: the packed ground-truth row matched or -1, dt_ig [A,T,Dt] u8,
+    cell_ngt [A, I Kc] i32).  The per-cell counts are device data the kernel clamps; the packer refuses a cell beyond the limits."""
+    who, dev = "coco_eval_match", gt_box.device
+    if gt_beg.dim() != 1 or gt_box.dim() != 2 or gt_box.shape[1] != 4 or dt_box.dim() != 2 or dt_box.shape[1] != 4 or iou_thr.dim() != 1 or area_rng.dim() != 2:
+        raise ValueError(f"{who}: the cell tables are [I Kc], gt_box [Gt, 4], dt_box [Dt, 4], iou_thr [T] and area_rng [A, 2]")
+    C, Gt, Dt, T, A = gt_beg.shape[0], gt_box.shape[0], dt_box.shape[0], iou_thr.shape[0], area_rng.shape[0]
+    for name, t, want in (("gt_cnt", gt_cnt, (C,)), ("dt_beg", dt_beg, (C,)), ("dt_cnt", dt_cnt, (C,)), ("gt_area", gt_area, (Gt,)), ("gt_crowd", gt_crowd, (Gt,)),
+                          ("gt_ignore", gt_ignore, (Gt,)), ("dt_area", dt_area, (Dt,)), ("area_rng", area_rng, (A, 2))):
+        _keval_shape(who, name, t, want)
+    _ceval_limits(who, C=C, Gt=Gt, Dt=Dt, T=T, A=A)
+    dtm = torch.empty((A, T, Dt), dtype=torch.int32, device=dev)
+    dt_ig = torch.empty((A, T, Dt), dtype=torch.uint8, device=dev)
+    cell_ngt = torch.empty((A, C), dtype=torch.int32, device=dev)
+    _lib.call("md_coco_eval_match", [_i32c(gt_beg, dev), _i32c(gt_cnt, dev), _i32c(dt_beg, dev), _i32c(dt_cnt, dev), _f64c(gt_box, dev), _f64c(gt_area, dev),
+                                     _u8c(gt_crowd, dev), _u8c(gt_ignore, dev), _f64c(dt_box, dev), _f64c(dt_area, dev), _f64c(iou_thr, dev),
+                                     _f64c(area_rng, dev), dtm, dt_ig, cell_ngt])
+    return dtm, dt_ig, cell_ngt
+
+
+def coco_eval_accumulate(order, cat_off, dt_rank, dtm, dt_ig, cell_ngt, rec_thr, max_dets):
+    """The body of COCOBboxEval.evaluate() (md_coco_eval_accumulate): order [Dt] i32 (detection rows, category-major, descending score,
+    equal scores in row order), cat_off [Kc+1] i32, dt_rank [Dt] i32, coco_eval_match's three results, rec_thr [R] f64, max_dets [M] i32
+    -> (precision [T,R,Kc,A,M] f64, recall [T,Kc,A,M] f64, n_gt [A,Kc] i32)."""
+    who, dev = "coco_eval_accumulate", dtm.device
+    if order.dim() != 1 or cat_off.dim() != 1 or cat_off.shape[0] < 2 or dtm.dim() != 3 or cell_ngt.dim() != 2 or rec_thr.dim() != 1 or max_dets.dim() != 1:
+        raise ValueError(f"{who}: order is [Dt], cat_off [Kc + 1], dtm [A, T, Dt], cell_ngt [A, I Kc], rec_thr [R] and max_dets [M]")
+    Dt, Kc, (A, T, _), C, R, M = order.shape[0], cat_off.shape[0] - 1, dtm.shape, cell_ngt.shape[1], rec_thr.shape[0], max_dets.shape[0]
+    for name, t, want in (("dt_rank", dt_rank, (Dt,)), ("dtm", dtm, (A, T, Dt)), ("dt_ig", dt_ig, (A, T, Dt)), ("cell_ngt", cell_ngt, (A, C))):
+        _keval_shape(who, name, t, want)
+    if C < 1 or C % Kc:
+        raise ValueError(f"{who}: {C} cells are no multiple of {Kc} categories")
+    _ceval_limits(who, C=C, Kc=Kc, Dt=Dt, T=T, A=A, R=R, M=M)
+    precision = torch.empty((T, R, Kc, A, M), dtype=torch.float64, device=dev)
+    recall = torch.empty((T, Kc, A, M), dtype=torch.float64, device=dev)
+    n_gt = torch.empty((A, Kc), dtype=torch.int32, device=dev)
+    _lib.call("md_coco_eval_accumulate", [_i32c(order, dev), _i32c(cat_off, dev), _i32c(dt_rank, dev), _i32c(dtm, dev), _u8c(dt_ig, dev), _i32c(cell_ngt, dev),
+                                          _f64c(rec_thr, dev), _i32c(max_dets, dev), precision, recall, n_gt])
+    return precision, recall, n_gt

@@ -37,6 +37,10 @@ read the same (paths relative to /root/reference/minddet/models):
   coco_eval_rows, coco_eval_match, coco_eval_accumulate
                           centernet/src/post_process.py:64-89 (to_float, convert_eval_format) and the COCOeval bbox evaluate() /
                           accumulate() called at centernet/eval.py:181-187; minddet_amd/coco_eval.py drives them
+  nusc_rows, nusc_eval_match, nusc_eval_accumulate
+                          centerpoint/det3d_ms/datasets/nuscenes/nusc_common.py:160-201 (_second_det_to_nusc_box,
+                          _lidar_nusc_box_to_global), nuscenes.py:252-293 (the attribute rule) and the devkit's DetectionEval called at
+                          nusc_common.py:659-674; minddet_amd/nusc_eval.py drives them
 
 All tensors are torch CUDA tensors; work is enqueued on the current stream; nothing here
 synchronises.  There is no CPU path.
@@ -2924,3 +2928,116 @@ def coco_eval_accumulate(order, cat_off, dt_rank, dtm, dt_ig, cell_ngt, rec_thr,
     _lib.call("md_coco_eval_accumulate", [_i32c(order, dev), _i32c(cat_off, dev), _i32c(dt_rank, dev), _i32c(dtm, dev), _u8c(dt_ig, dev), _i32c(cell_ngt, dev),
                                           _f64c(rec_thr, dev), _i32c(max_dets, dev), precision, recall, n_gt])
     return precision, recall, n_gt
+
+
+# ----------------------------------------------------------------------------- nuScenes detection evaluation (csrc/nusceval.hip)
+NUSCEVAL_MAX_SAMPLE_DETS, NUSCEVAL_MAX_GTS, NUSCEVAL_MAX_CLASSES, NUSCEVAL_MAX_THRS = 512, 1024, 16, 8      # MD_NUSCEVAL_MAX_SAMPLE_DETS, _MAX_GTS, ...
+NUSCEVAL_MAX_RECS, NUSCEVAL_MAX_CELLS, NUSCEVAL_MAX_ROWS, NUSCEVAL_MAX_LABELS = 256, 1 << 24, 1 << 26, 4096 # MD_NUSCEVAL_MAX_RECS, _MAX_CELLS, ...
+
+
+class _NuscRowsAttrs(ctypes.Structure):
+    _fields_ = [("first_sample", ctypes.c_int32)]
+
+
+class _NuscEvalAttrs(ctypes.Structure):
+    _fields_ = [("tp_index", ctypes.c_int32)]
+
+
+def _neval_limits(who, C=1, Kc=1, Gt=0, Dt=0, D=1, R=1):
+    if min(C, Kc, D, R) < 1:
+        raise ValueError(f"{who}: at least one cell, class, distance threshold and recall point")
+    if C >= NUSCEVAL_MAX_CELLS or Kc > NUSCEVAL_MAX_CLASSES or Gt > NUSCEVAL_MAX_ROWS or Dt > NUSCEVAL_MAX_ROWS:
+        raise ValueError(f"{who}: fewer than {NUSCEVAL_MAX_CELLS} cells, at most {NUSCEVAL_MAX_CLASSES} classes and {NUSCEVAL_MAX_ROWS} rows, got "
+                         f"{C}, {Kc}, {max(Gt, Dt)}")
+    if D > NUSCEVAL_MAX_THRS or R > NUSCEVAL_MAX_RECS:
+        raise ValueError(f"{who}: at most {NUSCEVAL_MAX_THRS} distance thresholds and {NUSCEVAL_MAX_RECS} recall points, got {D} and {R}")
+
+
+def nusc_rows(dets, count, pose, label_to_k, class_range, attr_moving, attr_still, first_sample, dt_xyz, dt_size, dt_quat, dt_vel, dt_yaw, dt_score,
+              dt_cat, dt_attr, dt_rank, dt_src, dt_beg, dt_cnt):
+    """dets_to_nusc, the class-range filter and the grouping into (sample, class) cells for one batch, nothing read back (md_nusc_rows,
+    include/minddet_hip_nusceval.h): dets [B,max_det,11] f32 (md_cp_pack's rows), count [B] i32, pose [B,14] f64 (cs_rotation,
+    cs_translation, ego_rotation, ego_translation), label_to_k [L] i32 (-1 drops the row), class_range [Kc] f64, attr_moving, attr_still
+    [Kc] i32.  The twelve outputs are the operands of the whole set (Dt = I max_det rows, I Kc cells), written in place for the samples
+    first_sample .. first_sample + B - 1: dt_xyz, dt_size [Dt,3], dt_quat [Dt,4], dt_vel [Dt,2], dt_yaw, dt_score [Dt] f64, dt_cat,
+    dt_attr, dt_rank, dt_src [Dt] i32, dt_beg, dt_cnt [I Kc] i32."""
+    who = "nusc_rows"
+    if dets.dim() != 3 or dets.shape[2] != 11 or dets.shape[1] < 1 or dets.dtype != torch.float32:
+        raise ValueError(f"{who}: dets are [B, max_det, 11] float32, got {tuple(dets.shape)} {dets.dtype}")
+    dev, (B, max_det) = dets.device, dets.shape[:2]
+    if max_det > NUSCEVAL_MAX_SAMPLE_DETS:
+        raise ValueError(f"{who}: at most {NUSCEVAL_MAX_SAMPLE_DETS} rows per sample, got {max_det}")
+    if label_to_k.dim() != 1 or not 1 <= label_to_k.shape[0] <= NUSCEVAL_MAX_LABELS:
+        raise ValueError(f"{who}: label_to_k is [L], 1 <= L <= {NUSCEVAL_MAX_LABELS}")
+    if class_range.dim() != 1 or class_range.shape[0] < 1:
+        raise ValueError(f"{who}: class_range is [Kc]")
+    Kc = class_range.shape[0]
+    for name, t, want in (("count", count, (B,)), ("pose", pose, (B, 14)), ("attr_moving", attr_moving, (Kc,)), ("attr_still", attr_still, (Kc,))):
+        _keval_shape(who, name, t, want)
+    if dt_xyz.dim() != 2 or dt_beg.dim() != 1 or dt_xyz.shape[0] < 1 or dt_xyz.shape[0] % max_det or dt_beg.shape[0] != dt_xyz.shape[0] // max_det * Kc:
+        raise ValueError(f"{who}: dt_xyz is [I max_det, 3] and dt_beg [I Kc]")
+    Dt, C = dt_xyz.shape[0], dt_beg.shape[0]
+    I, f64, i32 = Dt // max_det, torch.float64, torch.int32
+    outs = (("dt_xyz", dt_xyz, (Dt, 3), f64), ("dt_size", dt_size, (Dt, 3), f64), ("dt_quat", dt_quat, (Dt, 4), f64), ("dt_vel", dt_vel, (Dt, 2), f64),
+            ("dt_yaw", dt_yaw, (Dt,), f64), ("dt_score", dt_score, (Dt,), f64), ("dt_cat", dt_cat, (Dt,), i32), ("dt_attr", dt_attr, (Dt,), i32),
+            ("dt_rank", dt_rank, (Dt,), i32), ("dt_src", dt_src, (Dt,), i32), ("dt_beg", dt_beg, (C,), i32), ("dt_cnt", dt_cnt, (C,), i32))
+    for name, t, want, dtype in outs:
+        _keval_shape(who, name, t, want)
+        if t.dtype != dtype or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{who}: {name} is a contiguous {dtype} tensor on {dev} (it is written in place)")
+    _neval_limits(who, C=C, Kc=Kc, Dt=Dt)
+    if first_sample < 0 or first_sample + B > I:
+        raise ValueError(f"{who}: samples {first_sample} .. {first_sample + B - 1} of {I}")
+    _lib.call("md_nusc_rows", [dets.contiguous(), _i32c(count, dev), _f64c(pose, dev), _i32c(label_to_k, dev), _f64c(class_range, dev),
+                               _i32c(attr_moving, dev), _i32c(attr_still, dev)] + [t for _, t, _, _ in outs], extra=_NuscRowsAttrs(int(first_sample)))
+
+
+def nusc_eval_match(gt_beg, gt_cnt, dt_beg, dt_cnt, gt_xy, gt_size, gt_yaw, gt_vel, gt_attr, dt_xyz, dt_size, dt_yaw, dt_vel, dt_attr, dist_thr, period,
+                    tp_index):
+    """The greedy centre-distance matching of the devkit's accumulate() for every (sample, class) cell and all thresholds
+    (md_nusc_eval_match): the cell tables [I Kc] i32, the ground-truth rows (gt_xy [Gt,2], gt_size [Gt,3], gt_yaw [Gt], gt_vel [Gt,2] f64,
+    gt_attr [Gt] i32), the detection rows (dt_xyz [Dt,3], dt_size [Dt,3], dt_yaw [Dt], dt_vel [Dt,2] f64, dt_attr [Dt] i32), dist_thr [D]
+    f64, period [Kc] f64, tp_index -> (dtm [D,Dt] i32: the packed ground-truth row matched or -1, err [Dt,5] f64: the five errors of the
+    match at threshold tp_index, cell_ngt [I Kc] i32).  The per-cell counts are device data the kernel clamps; the packer refuses a cell
+    beyond the limits."""
+    who, dev = "nusc_eval_match", gt_xy.device
+    if gt_beg.dim() != 1 or gt_xy.dim() != 2 or gt_xy.shape[1] != 2 or dt_xyz.dim() != 2 or dt_xyz.shape[1] != 3 or dist_thr.dim() != 1 or period.dim() != 1:
+        raise ValueError(f"{who}: the cell tables are [I Kc], gt_xy [Gt, 2], dt_xyz [Dt, 3], dist_thr [D] and period [Kc]")
+    C, Gt, Dt, D, Kc = gt_beg.shape[0], gt_xy.shape[0], dt_xyz.shape[0], dist_thr.shape[0], period.shape[0]
+    for name, t, want in (("gt_cnt", gt_cnt, (C,)), ("dt_beg", dt_beg, (C,)), ("dt_cnt", dt_cnt, (C,)), ("gt_size", gt_size, (Gt, 3)), ("gt_yaw", gt_yaw, (Gt,)),
+                          ("gt_vel", gt_vel, (Gt, 2)), ("gt_attr", gt_attr, (Gt,)), ("dt_size", dt_size, (Dt, 3)), ("dt_yaw", dt_yaw, (Dt,)),
+                          ("dt_vel", dt_vel, (Dt, 2)), ("dt_attr", dt_attr, (Dt,))):
+        _keval_shape(who, name, t, want)
+    _neval_limits(who, C=C, Kc=Kc, Gt=Gt, Dt=Dt, D=D)
+    if C % Kc or not 0 <= tp_index < D:
+        raise ValueError(f"{who}: {C} cells are a multiple of {Kc} classes and tp_index lies in [0, {D}), got {tp_index}")
+    dtm = torch.empty((D, Dt), dtype=torch.int32, device=dev)
+    err = torch.empty((Dt, 5), dtype=torch.float64, device=dev)
+    cell_ngt = torch.empty((C,), dtype=torch.int32, device=dev)
+    _lib.call("md_nusc_eval_match", [_i32c(gt_beg, dev), _i32c(gt_cnt, dev), _i32c(dt_beg, dev), _i32c(dt_cnt, dev), _f64c(gt_xy, dev), _f64c(gt_size, dev),
+                                     _f64c(gt_yaw, dev), _f64c(gt_vel, dev), _i32c(gt_attr, dev), _f64c(dt_xyz, dev), _f64c(dt_size, dev), _f64c(dt_yaw, dev),
+                                     _f64c(dt_vel, dev), _i32c(dt_attr, dev), _f64c(dist_thr, dev), _f64c(period, dev), dtm, err, cell_ngt],
+              extra=_NuscEvalAttrs(int(tp_index)))
+    return dtm, err, cell_ngt
+
+
+def nusc_eval_accumulate(order, cat_off, dt_score, dtm, err, cell_ngt, rec_thr, tp_index):
+    """The curves of the devkit's accumulate() (md_nusc_eval_accumulate): order [Dt] i32 (detection rows, class-major, walking order
+    across the samples), cat_off [Kc+1] i32, dt_score [Dt] f64, nusc_eval_match's three results, rec_thr [R] f64, tp_index ->
+    (precision [Kc,D,R], confidence [Kc,D,R], tp_err [Kc,5,R] f64, n_gt [Kc], n_match [Kc,D] i32, tp_scan [D,Dt] i32, m_conf [Dt],
+    m_cum [5,Dt] f64)."""
+    who, dev = "nusc_eval_accumulate", dtm.device
+    if order.dim() != 1 or cat_off.dim() != 1 or cat_off.shape[0] < 2 or dtm.dim() != 2 or cell_ngt.dim() != 1 or rec_thr.dim() != 1:
+        raise ValueError(f"{who}: order is [Dt], cat_off [Kc + 1], dtm [D, Dt], cell_ngt [I Kc] and rec_thr [R]")
+    Dt, Kc, D, C, R = order.shape[0], cat_off.shape[0] - 1, dtm.shape[0], cell_ngt.shape[0], rec_thr.shape[0]
+    for name, t, want in (("dt_score", dt_score, (Dt,)), ("dtm", dtm, (D, Dt)), ("err", err, (Dt, 5))):
+        _keval_shape(who, name, t, want)
+    if C < 1 or C % Kc or not 0 <= tp_index < D:
+        raise ValueError(f"{who}: {C} cells are a multiple of {Kc} classes and tp_index lies in [0, {D}), got {tp_index}")
+    _neval_limits(who, C=C, Kc=Kc, Dt=Dt, D=D, R=R)
+    f = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)
+    i = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)
+    outs = (f(Kc, D, R), f(Kc, D, R), f(Kc, 5, R), i(Kc), i(Kc, D), i(D, Dt), f(Dt), f(5, Dt))
+    _lib.call("md_nusc_eval_accumulate", [_i32c(order, dev), _i32c(cat_off, dev), _f64c(dt_score, dev), _i32c(dtm, dev), _f64c(err, dev), _i32c(cell_ngt, dev),
+                                          _f64c(rec_thr, dev)] + list(outs), extra=_NuscEvalAttrs(int(tp_index)))
+    return outs

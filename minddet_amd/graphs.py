@@ -1048,6 +1048,19 @@ class PointPillars(Module):
         head, _ = self.bbox_head(self.neck(pseudo_image))
         return self.bbox_head.loss(example, head, grad=grad)
 
+    def evaluate_nusc(self, dets, count, poses, gt_records, ego_translations):
+        """The nuScenes detection result (detection_cvpr_2019) of forward()'s rows (dets [B, max_det, 11], count [B]) for the B samples
+        of ego_translations, on the device: nusc_eval.PackedNusc.add_dets takes the rows as they lie (md_nusc_rows: the global frame,
+        the attribute rule, the class-range filter and the grouping, no host copy), md_nusc_eval_match and md_nusc_eval_accumulate fill
+        the curves, NuscDetectionEval.summarize() reads them.  poses: per sample cs_rotation, cs_translation, ego_rotation,
+        ego_translation (nusc_eval.pose_array); the class names are the config's `tasks` in order.
+        -> what NuscDetectionEval(gt_records, rows_to_results' records, ...).summarize() returns on the same rows."""
+        from . import nusc_eval
+
+        names = [n for task in self.bbox_head.class_names for n in task]
+        packed = nusc_eval.pack_nusc(gt_records, ego_translations, names, device=dets.device).add_dets(dets, count, poses, 0)
+        return nusc_eval.NuscDetectionEval.from_packed(packed).evaluate(backend="device").summarize()
+
 
 def merge_center_tasks(outs, num_classes, max_per_task):
     """The task merge of tools_ms/eval.py:84-111 on the device: per sample and task the first size rows, size = the rows among the first
@@ -1205,6 +1218,11 @@ class PillarDetector(Module):
         """merge_sweeps, then forward on the merged cloud"""
         pts, offsets = self.merge_sweeps(points, lengths, matrices, time_lags, order=order, begins=begins)
         return self.forward(pts, offsets, return_aux=return_aux)
+
+    def evaluate_nusc(self, dets, count, poses, gt_records, ego_translations):
+        """The nuScenes detection result of forward()'s rows on the device, beside PointPillarsKITTIPoints.evaluate_kitti:
+        PointPillars.evaluate_nusc of the inner detector (class names from the config's `tasks`)."""
+        return self.detector.evaluate_nusc(dets, count, poses, gt_records, ego_translations)
 
     def _train_cfg(self, key):
         if not self.train_cfg or key not in self.train_cfg:

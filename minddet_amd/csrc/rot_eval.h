@@ -11,6 +11,15 @@ namespace md {
 constexpr int RIE_LANES = 256;                 // lanes of the calling workgroup = the stride between a lane's polygon slots
 constexpr int RIE_PTS = 24;                    // polygon slots per lane
 constexpr int RIE_LDS_FLOATS = 3 * RIE_PTS * RIE_LANES;
+// The one departure from the reference.  When two edges are collinear (equal yaw, one shared edge line) its four strict orientation tests
+// are decided by rounding, and where they say "crossing" the point is a quotient of two rounding residues: a vertex anywhere in the plane,
+// an intersection of 672 m2 for two cars, an IoU of -34 (tests/rot_eval_contract.py has the figures).  A crossing lies on both segments,
+// so a point is kept only if it is within tol = 2^-16 x the largest coordinate of the four end points of the extent of both segments and of
+// both edge lines (NaN and infinity fail).  A point dropped wrongly would have to be that far off; one kept wrongly adds at most
+// tol x edge length / 2 to the area, 2.6e-3 m2 for a car at 80 m.  Every non-coincident pair of the contract's generators keeps the bits
+// it had without the test; among 112 522 further overlapping jittered pairs 5 changed, each a crossing of edges within 1.4e-3 rad of
+// parallel that had left its segments, and each result moved towards the float64 geometric value (worst error 3.9e-3 -> 1.6e-4).
+constexpr float RIE_CROSS_TOL = 1.52587890625e-05f;   // 2^-16
 
 __device__ __forceinline__ void rie_corners(const float *rb, float *c) {
 #pragma clang fp contract(off)
@@ -60,9 +69,19 @@ __device__ __forceinline__ float rie_pair(const float *r1, const float *r2, int 
                     const float DC0 = D0 - C0, DC1 = D1 - C1;
                     const float ABBA = A0 * B1 - B0 * A1, CDDC = C0 * D1 - D0 * C1;
                     const float DH = BA1 * DC0 - BA0 * DC1;
-                    px[m * RIE_LANES] = (ABBA * DC0 - BA0 * CDDC) / DH;
-                    py[m * RIE_LANES] = (ABBA * DC1 - BA1 * CDDC) / DH;
-                    ++m;
+                    const float X = (ABBA * DC0 - BA0 * CDDC) / DH, Y = (ABBA * DC1 - BA1 * CDDC) / DH;
+                    // the one departure from the reference: the crossing has to lie on both segments (RIE_CROSS_TOL)
+                    const float mag = fmaxf(fmaxf(fmaxf(fabsf(A0), fabsf(A1)), fmaxf(fabsf(B0), fabsf(B1))),
+                                            fmaxf(fmaxf(fabsf(C0), fabsf(C1)), fmaxf(fabsf(D0), fabsf(D1))));
+                    const float tol = RIE_CROSS_TOL * mag;
+                    if (X >= fmaxf(fminf(A0, B0), fminf(C0, D0)) - tol && X <= fminf(fmaxf(A0, B0), fmaxf(C0, D0)) + tol &&
+                        Y >= fmaxf(fminf(A1, B1), fminf(C1, D1)) - tol && Y <= fminf(fmaxf(A1, B1), fmaxf(C1, D1)) + tol &&
+                        fabsf(BA0 * (Y - A1) - BA1 * (X - A0)) <= tol * (fabsf(BA0) + fabsf(BA1)) &&
+                        fabsf(DC0 * (Y - C1) - DC1 * (X - C0)) <= tol * (fabsf(DC0) + fabsf(DC1))) {
+                        px[m * RIE_LANES] = X;
+                        py[m * RIE_LANES] = Y;
+                        ++m;
+                    }
                 }
             }
         }

@@ -26,6 +26,18 @@ as is any run on real KITTI results.  `rows_to_annos` formats the rows that det_
 filters, clip and alpha for a batch with nothing read back in between -- into the same dicts.  The lidar -> camera -> image box geometry reproduces the reference's box_ops.py outputs (same
 golden file); the annotation writer's filter rules (predict.py needs skimage through kitti_common: not importable) are restated.  Reference quirk: eval_utils.get_split_parts has no guard, fewer than 50 images crash it.
 
+Coincident boxes (a property of the reference's rotated overlap, eval_gpu/rotate_iou.py:164-179, kept here): its corner-inside test is a
+non-strict fp32 `>=` and its edge-crossing test a strict `>`, so when corners of one box lie on the edges of the other the roundings
+decide which vertices the intersection polygon gets.  Measured on the fp32 restatement of that arithmetic, 257 car-sized pairs in
+KITTI's range each (tests/rot_eval_contract.py, tests/test_rot_eval_contract_cpu.py): a box against a bit-identical copy of itself
+comes out with an IoU below 0.99 -- mostly 0 or about 1/3 -- for 98.8 % of the pairs at arbitrary yaw and for 74.7 % at yaw in
+{+-1.57, pi}; only at yaw exactly 0 is it 1.  Equal yaw with one shared edge line: 13.6 % below 0.99 of the true IoU.  One thing is not
+kept: for two collinear edges the reference's crossing point is a quotient of two rounding residues (restated literally: intersection
+areas up to 672 m2 for cars, IoU from -34.6 to +30.8, for 36 % of such pairs); csrc/rot_eval.h keeps a crossing only if it lies on
+both segments, which changes no other pair the tests know.  Evaluating a result set against a bit-identical copy of itself is
+therefore not a sanity check this metric supports unless every yaw is 0.  Away from coincidence the kernels are held to a float64
+geometric judge (tests/test_rot_eval_gpu.py).
+
 The device path (at the end of this file; include/minddet_hip_kittieval.h): pack_annos lays the annotations of all images out as one flat
 set of tensors (PackedEval; with_rows takes the detection half from md_kitti_rows' device rows), eval_class_device runs clean_data, the
 overlaps, both matching passes, get_thresholds and the sums over the images as the five md_kitti_eval_* operators and ends in the same

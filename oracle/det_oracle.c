@@ -307,6 +307,7 @@ int orc_circle_nms(const float *d, int64_t n, float thresh, uint8_t *keepmask) {
  * criterion -1: IoU, 0: inter/area1, 1: inter/area2, 2: raw intersection.  The reference runs under numba.cuda
  * (absent here) and ships no fixture: parity unpinned; cross-checked in tests against orc_rot_overlap.
  * --------------------------------------------------------------------------------------------------------- */
+#define RIE_CROSS_TOL 1.52587890625e-05f /* 2^-16, as csrc/rot_eval.h */
 static void rie_corners(const float *rb, float *c) {
     const float a_cos = cosf(rb[4]), a_sin = sinf(rb[4]);
     const float cx[4] = {-rb[2] / 2, -rb[2] / 2, rb[2] / 2, rb[2] / 2};
@@ -337,7 +338,15 @@ static int rie_seg(const float *p1, const float *p2, int i, int j, float *t) {
             const float DH = BA1 * DC0 - BA0 * DC1, Dx = ABBA * DC0 - BA0 * CDDC, Dy = ABBA * DC1 - BA1 * CDDC;
             t[0] = Dx / DH;
             t[1] = Dy / DH;
-            return 1;
+            /* not in the reference (rot_eval.h says why): a crossing lies on both segments; for collinear edges the four tests
+             * above are decided by rounding and Dx / DH is a quotient of rounding residues, anywhere in the plane */
+            const float mag = fmaxf(fmaxf(fmaxf(fabsf(A0), fabsf(A1)), fmaxf(fabsf(B0), fabsf(B1))),
+                                    fmaxf(fmaxf(fabsf(C0), fabsf(C1)), fmaxf(fabsf(D0), fabsf(D1))));
+            const float tol = RIE_CROSS_TOL * mag;
+            return t[0] >= fmaxf(fminf(A0, B0), fminf(C0, D0)) - tol && t[0] <= fminf(fmaxf(A0, B0), fmaxf(C0, D0)) + tol &&
+                   t[1] >= fmaxf(fminf(A1, B1), fminf(C1, D1)) - tol && t[1] <= fminf(fmaxf(A1, B1), fmaxf(C1, D1)) + tol &&
+                   fabsf(BA0 * (t[1] - A1) - BA1 * (t[0] - A0)) <= tol * (fabsf(BA0) + fabsf(BA1)) &&
+                   fabsf(DC0 * (t[1] - C1) - DC1 * (t[0] - C0)) <= tol * (fabsf(DC0) + fabsf(DC1));
         }
     }
     return 0;

@@ -52,6 +52,11 @@ train_cfg = dict(
                  global_random_rot_range=[0, 0], num_try=100),
     assigner=dict(matched_threshold=0.5, unmatched_threshold=0.35, sample_positive_fraction=-1, sample_size=512,
                   region_similarity_calculator="nearest_iou_similarity"),
+    # the optimizer of the reference's train.py (nn.Adam with weight decay, no gradient clip) and its learning-rate schedule
+    # (optim.exponential_decay_lr): the reference configuration's values.  model.head_trainer() reads `optimizer`.
+    optimizer=dict(type="Adam", weight_decay=0.0001),
+    lr=dict(type="exponential_decay_lr", initial_learning_rate=0.0002, decay_rate=0.8, decay_epoch=15, is_stair=True, max_num_epochs=80,
+            batch_size=4),
 )
 
 test_cfg = dict(

@@ -197,6 +197,13 @@ struct Scratch {
     }
 };
 
+// acquire, then the alignment the op's carve of the buffer needs: MD_ERR_ARG for a caller's workspace that does not have it (a pool
+// buffer always does)
+static inline int acquire_aligned(Scratch &ws, size_t bytes, const Args &a, int ws_index, hipStream_t s, size_t align) {
+    if (int rc = ws.acquire(bytes, a, ws_index, s)) return rc;
+    return (uintptr_t)ws.ptr % align != 0 ? MD_ERR_ARG : MD_OK;
+}
+
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // Scratch sizes have one owner (include/minddet_hip.h "Conventions"): per op one host function of the extents fills the byte offsets of

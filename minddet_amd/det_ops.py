@@ -3041,3 +3041,76 @@ def nusc_eval_accumulate(order, cat_off, dt_score, dtm, err, cell_ngt, rec_thr, 
     _lib.call("md_nusc_eval_accumulate", [_i32c(order, dev), _i32c(cat_off, dev), _f64c(dt_score, dev), _i32c(dtm, dev), _f64c(err, dev), _i32c(cell_ngt, dev),
                                           _f64c(rec_thr, dev)] + list(outs), extra=_NuscEvalAttrs(int(tp_index)))
     return outs
+
+
+# ----------------------------------------------------------------------------- the training step behind the losses (csrc/convbwd.hip, optim.hip)
+class _Conv1x1BwdAttrs(ctypes.Structure):
+    """md_conv1x1_bwd_attrs (include/minddet_hip_train.h)"""
+    _fields_ = [("cin", ctypes.c_int32), ("cout", ctypes.c_int32), ("x_c_off", ctypes.c_int32), ("dy_c_off", ctypes.c_int32),
+                ("reserved0", ctypes.c_int32)]
+
+
+class _AdamAttrs(ctypes.Structure):
+    """md_adam_attrs (include/minddet_hip_train.h)"""
+    _fields_ = [(n, ctypes.c_double) for n in ("lr", "beta1", "beta2", "beta1_power", "beta2_power", "eps", "weight_decay", "max_norm",
+                                               "grad_scale", "reserved0")]
+
+
+def conv1x1_bwd_weight_workspace_bytes(P, cin, cout):
+    return _lib.workspace_bytes("md_conv1x1_bwd_weight", P, cin, cout)
+
+
+def conv1x1_bwd_weight(x, dy, pc, x_c_off=0, dy_c_off=0, out=None, with_bias=True, workspace=True):
+    """Weight and bias gradient of the pointwise layer `pc` (nn_ops.PackedConv of a 1x1 conv) on the device (md_conv1x1_bwd_weight):
+    x [N,H,W,Cx] bf16, the layer's input at channels [x_c_off, x_c_off + pc.cin); dy [N,H,W,Cy] f32, d loss / d output at channels
+    [dy_c_off, dy_c_off + pc.cout) (what a *_loss(grad=True) returns) -> (dw f32 of pc.w's shape, db f32 of pc.bias's shape or None),
+    padding rows and columns +0.0.  out = (dw, db): written in place (views of a flat gradient buffer).  workspace=False: the
+    library's scratch pool instead of a torch allocation."""
+    who = "conv1x1_bwd_weight"
+    if pc.kh != 1 or pc.kw != 1 or pc.stride != 1 or pc.pad != 0:
+        raise ValueError(f"{who}: a 1x1 / stride 1 / pad 0 layer, got {pc.kh}x{pc.kw} stride {pc.stride} pad {pc.pad}")
+    if x.dtype != torch.bfloat16 or x.dim() != 4 or dy.dtype != torch.float32 or dy.dim() != 4 or tuple(x.shape[:3]) != tuple(dy.shape[:3]):
+        raise ValueError(f"{who}: x is [N,H,W,Cx] bfloat16 and dy [N,H,W,Cy] float32 over the same pixels, got {tuple(x.shape)} {x.dtype}, "
+                         f"{tuple(dy.shape)} {dy.dtype}")
+    rows, kpad = pc.w.shape
+    if out is None:
+        out = (torch.empty((rows, kpad), dtype=torch.float32, device=x.device),
+               torch.empty((pc.bias.shape[0],), dtype=torch.float32, device=x.device) if with_bias else None)
+    dw, db = out
+    P = x.shape[0] * x.shape[1] * x.shape[2]
+    ws = _lib.scratch("md_conv1x1_bwd_weight", (P, pc.cin, pc.cout), x.device) if workspace else None
+    at = _Conv1x1BwdAttrs(int(pc.cin), int(pc.cout), int(x_c_off), int(dy_c_off), 0)
+    _lib.call("md_conv1x1_bwd_weight", [x.contiguous(), dy.contiguous(), dw, db] + ([ws] if ws is not None else []), extra=at)
+    return dw, db
+
+
+def grad_sumsq_workspace_bytes(n):
+    return _lib.workspace_bytes("md_grad_sumsq", n)
+
+
+def grad_sumsq(grad, out=None, workspace=True):
+    """sum of squares of a flat f32 gradient in float64, in a fixed order (md_grad_sumsq) -> [1] f64"""
+    if grad.dtype != torch.float32 or grad.dim() != 1:
+        raise ValueError(f"grad_sumsq: grad is a flat float32 tensor, got {tuple(grad.shape)} {grad.dtype}")
+    if out is None:
+        out = torch.empty((1,), dtype=torch.float64, device=grad.device)
+    ws = _lib.scratch("md_grad_sumsq", (grad.shape[0],), grad.device) if workspace else None
+    _lib.call("md_grad_sumsq", [grad, out] + ([ws] if ws is not None else []))
+    return out
+
+
+def adam_attrs(lr, beta1, beta2, beta1_power, beta2_power, eps=1e-8, weight_decay=0.0, max_norm=None, grad_scale=1.0):
+    return _AdamAttrs(float(lr), float(beta1), float(beta2), float(beta1_power), float(beta2_power), float(eps), float(weight_decay),
+                      0.0 if max_norm is None else float(max_norm), float(grad_scale), 0.0)
+
+
+def adam_step(grad, param, m, v, *, lr, beta1, beta2, beta1_power, beta2_power, eps=1e-8, weight_decay=0.0, sumsq=None, max_norm=None,
+              grad_scale=1.0, shadow=None):
+    """One Adam.construct of the reference for a flat range, in place (md_adam_step, include/minddet_hip_train.h): grad, param, m, v
+    [n] f32; sumsq [K] f64 with max_norm = the global-norm clip (None: none); beta1_power / beta2_power the running products, this step
+    included; shadow [ns <= n] bf16 receives the new param[:ns]."""
+    if (sumsq is None) != (max_norm is None):
+        raise ValueError("adam_step: sumsq and max_norm come together (the global-norm clip) or not at all")
+    at = adam_attrs(lr, beta1, beta2, beta1_power, beta2_power, eps, weight_decay, max_norm, grad_scale)
+    _lib.call("md_adam_step", [grad, sumsq, param, m, v, shadow], extra=at)
+    return param

@@ -1293,8 +1293,17 @@ class PPAnchorHead(Module):
     def children(self):
         return [m for m in (self.conv_cls, self.conv_box, self.conv_dir_cls) if m is not None]
 
+    _trainer = None     # optim.HeadTrainer of this head (PointPillarsNet.head_trainer): derived from the merged pack, so owned here
+
+    def to(self, device):
+        if self._trainer is not None:
+            self._trainer.sync_modules()    # the ConvModules are the source of truth of a repack: they get the trained master first
+        return super().to(device)
+
     def _derive(self, device):
         self._merged = merged_conv(self.children(), device)
+        if self._trainer is not None:
+            self._trainer.bind()            # the trainer's buffers around the new pack; master, moments and powers kept
 
     def head_offsets(self):
         """first channel of each conv's outputs in the head tensor; dir_cls None without a direction classifier"""
@@ -1434,6 +1443,22 @@ class PointPillarsNet(Module):
         head = self.bbox_head(self.neck(pseudo_image))
         out = self.loss_op()(head, example["labels"], example["reg_targets"], self.anchors, grad=grad)
         return dict(out, head=head)
+
+    def head_trainer(self, optimizer_cfg=None):
+        """optim.HeadTrainer of this model's head (the three 1x1 convs, the neck frozen): train_step(pseudo_image, example, lr, beta1)
+        continues loss(grad=True) through md_conv1x1_bwd_weight, md_grad_sumsq and md_adam_step on the device.  optimizer_cfg: None =
+        train_cfg["optimizer"] (none there: optim.DEFAULT_OPTIMIZER).  One trainer per head: a call without a config returns the
+        existing one, a call with one replaces it (fresh moments).  The model has to be on its device."""
+        from . import optim
+
+        if optimizer_cfg is None and self.bbox_head._trainer is not None:
+            return self.bbox_head._trainer
+        cfg = optimizer_cfg if optimizer_cfg is not None else (self.train_cfg or {}).get("optimizer")
+        if self.bbox_head._trainer is not None:       # the replaced trainer leaves its master in the modules and lets go of the pack
+            self.bbox_head._trainer.sync_modules()
+            self.bbox_head._trainer = None
+            self.bbox_head._derive(self.bbox_head._merged.w.device)
+        return optim.HeadTrainer(self, cfg)
 
 
 # ----------------------------------------------------------------------------- PointPillars (KITTI) from raw points (csrc/ppreader.hip)
@@ -1584,6 +1609,16 @@ class PointPillarsKITTIPoints(Module):
         as one device chain.  -> the dict of loss() plus `example`."""
         ex = self.train_example(points, offsets, gt_boxes, gt_classes, gt_count, generator=generator, draws=draws, valid=valid, sampled=sampled)
         return dict(self.inner.loss(ex["canvas"], ex, grad=grad), example=ex)
+
+    def head_trainer(self, optimizer_cfg=None):
+        """PointPillarsNet.head_trainer of the inner model"""
+        return self.inner.head_trainer(optimizer_cfg)
+
+    def train_step(self, points, offsets, gt_boxes, gt_classes, gt_count, lr, beta1=0.9, generator=None, draws=None, valid=None, sampled=None):
+        """train_example, then HeadTrainer.train_step on its canvas: raw points + ground truth -> one update of the head, as one device
+        chain.  -> the dict of HeadTrainer.train_step plus `example`."""
+        ex = self.train_example(points, offsets, gt_boxes, gt_classes, gt_count, generator=generator, draws=draws, valid=valid, sampled=sampled)
+        return dict(self.head_trainer().train_step(ex["canvas"], ex, lr, beta1), example=ex)
 
     def _kitti_options(self):
         """test_cfg's KITTI keys: remove_outside_points (True), lidar_input (False), post_center_limit_range (None); the options that

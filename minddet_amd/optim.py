@@ -1,0 +1,178 @@
+"""The optimizer side of a training step: the reference's learning-rate schedules on the host (numpy, one array per run) and its Adam
+on the device (det_ops.grad_sumsq + det_ops.adam_step, include/minddet_hip_train.h), plus the trainer of the KITTI head.
+
+  OneCycle               centerpoint/det3d_ms/solver/learning_schedules_fastai.py (OneCycle.get_lr: two cosine phases for the rate and
+                         for beta1)
+  exponential_decay_lr   the schedule pointpillars/train.py:76-93 asks MindSpore for (the function itself is not in the reference)
+  Adam                   centerpoint/det3d_ms/solver/custom_adam.py:590-668 (Adam.construct); max_norm=None is the plain nn.Adam of
+                         pointpillars/train.py
+  HeadTrainer            graphs.PointPillarsNet.head_trainer(): neck -> head -> md_pp_loss_grad -> md_conv1x1_bwd_weight ->
+                         md_grad_sumsq -> md_adam_step on the merged 1x1 heads, the neck frozen
+
+Nothing here reads a device value back."""
+import math
+
+import numpy as np
+import torch
+
+from . import det_ops
+
+
+def _annealing_cos(start, end, pct):
+    return end + (start - end) / 2 * (np.cos(np.pi * pct) + 1)
+
+
+class OneCycle:
+    """The reference's OneCycle(total_step, lr_max, div_factor, pct_start, moms): the rate rises from lr_max / div_factor to lr_max over
+    the first int(pct_start total_step) steps and falls to lr_max / div_factor / 1e4 over the rest, beta1 goes moms[0] -> moms[1] ->
+    moms[0], each phase a half cosine of (step - start) / (end - start).  get_lr() -> (lrs, moms), float32 arrays of total_step values,
+    equal bit for bit to the reference's (tests/golden/one_cycle_vectors.npz)."""
+
+    def __init__(self, total_step, lr_max, div_factor, pct_start, moms=(0.95, 0.85)):
+        self.total_step, self.lr_max, self.div_factor, self.pct_start, self.moms = int(total_step), lr_max, div_factor, pct_start, tuple(moms)
+        low = lr_max / div_factor
+        cut = int(pct_start * self.total_step)
+        if not 0 < cut < self.total_step:
+            raise ValueError(f"OneCycle: the second phase starts inside the run, got step {cut} of {self.total_step}")
+        # (first step, one past the last, value at the phase's start, at its end)
+        self.lr_phases = [(0, cut, low, lr_max), (cut, self.total_step, lr_max, low / 1e4)]
+        self.mom_phases = [(0, cut, self.moms[0], self.moms[1]), (cut, self.total_step, self.moms[1], self.moms[0])]
+
+    @staticmethod
+    def _at(phases, step):
+        start, end, a, b = [ph for ph in phases if step >= ph[0]][-1]
+        return _annealing_cos(a, b, (step - start) / (end - start))
+
+    def step(self, step):
+        return self._at(self.lr_phases, step), self._at(self.mom_phases, step)
+
+    def get_lr(self):
+        vals = [self.step(i) for i in range(self.total_step)]
+        return np.array([v[0] for v in vals]).astype(np.float32), np.array([v[1] for v in vals]).astype(np.float32)
+
+
+def exponential_decay_lr(learning_rate, decay_rate, total_step, step_per_epoch, decay_epoch, is_stair=False):
+    """learning_rate decay_rate^(epoch / decay_epoch) per step, epoch = step // step_per_epoch, the exponent floored when is_stair -> a
+    list of total_step Python floats.  Unpinned: the reference (pointpillars/train.py:76-93) calls MindSpore's function of this name,
+    which is not in its repository; this is that function's documented form, evaluated in float64."""
+    if total_step < 1 or step_per_epoch < 1 or decay_epoch < 1:
+        raise ValueError("exponential_decay_lr: total_step, step_per_epoch and decay_epoch are positive")
+    out = []
+    for i in range(int(total_step)):
+        e = (i // int(step_per_epoch)) / int(decay_epoch)
+        out.append(float(learning_rate) * float(decay_rate) ** (math.floor(e) if is_stair else e))
+    return out
+
+
+class Adam:
+    """The reference's Adam over one flat fp32 range on the device.  `param`, `grad`, `m`, `v` are flat [n] f32 buffers; view(name) is a
+    tensor's slice of any of them (`sizes`: ordered {name: shape}).  step(lr, beta1) advances the two running powers as the reference's
+    fp32 Parameters do (beta1_power *= beta1, beta2_power *= beta2, before the update) and runs md_grad_sumsq (only with max_norm) and
+    md_adam_step once.  max_norm=None: pointpillars/train.py's nn.Adam(weight_decay); max_norm=35 with a per-step beta1 (OneCycle's
+    moms): CenterPoint's.  shadow: a bf16 tensor whose first elements mirror param (the packed weights a conv reads)."""
+
+    def __init__(self, sizes, device, beta2=0.999, eps=1e-8, weight_decay=0.0, max_norm=None, grad_scale=1.0, shadow=None):
+        self.slices, n = {}, 0
+        for name, shape in sizes.items():
+            k = int(np.prod(shape))
+            self.slices[name] = (n, n + k, tuple(shape))
+            n += k
+        self.n = n
+        self.param, self.grad, self.m, self.v = (torch.zeros((n,), dtype=torch.float32, device=device) for _ in range(4))
+        self.sumsq = torch.zeros((1,), dtype=torch.float64, device=device)
+        self.beta2, self.eps, self.weight_decay, self.max_norm, self.grad_scale = float(beta2), float(eps), float(weight_decay), max_norm, float(grad_scale)
+        self.beta1_power, self.beta2_power = np.float32(1.0), np.float32(1.0)
+        self.shadow = shadow
+        self.steps = 0
+
+    def view(self, name, of="param"):
+        lo, hi, shape = self.slices[name]
+        return getattr(self, of)[lo:hi].view(shape)
+
+    def step(self, lr, beta1=0.9):
+        self.beta1_power = np.float32(self.beta1_power * np.float32(beta1))
+        self.beta2_power = np.float32(self.beta2_power * np.float32(self.beta2))
+        clip = self.max_norm is not None
+        if clip:
+            det_ops.grad_sumsq(self.grad, out=self.sumsq)
+        det_ops.adam_step(self.grad, self.param, self.m, self.v, lr=lr, beta1=beta1, beta2=self.beta2, beta1_power=float(self.beta1_power),
+                          beta2_power=float(self.beta2_power), eps=self.eps, weight_decay=self.weight_decay,
+                          sumsq=self.sumsq if clip else None, max_norm=self.max_norm, grad_scale=self.grad_scale,
+                          shadow=None if self.shadow is None else self.shadow.view(-1))
+        self.steps += 1
+
+    def state(self):
+        """the mutable state, cloned (the device buffers and the two powers): load_state(state()) restores this moment"""
+        return dict(param=self.param.clone(), m=self.m.clone(), v=self.v.clone(), beta1_power=self.beta1_power, beta2_power=self.beta2_power,
+                    steps=self.steps)
+
+    def load_state(self, st):
+        for k in ("param", "m", "v"):
+            getattr(self, k).copy_(st[k])
+        self.beta1_power, self.beta2_power, self.steps = np.float32(st["beta1_power"]), np.float32(st["beta2_power"]), int(st["steps"])
+        if self.shadow is not None:
+            ns = self.shadow.numel()
+            self.shadow.view(-1).copy_(self.param[:ns].to(torch.bfloat16))
+
+
+DEFAULT_OPTIMIZER = dict(type="Adam", beta2=0.999, eps=1e-8, weight_decay=1e-4, max_norm=None, grad_scale=1.0)
+
+
+class HeadTrainer:
+    """Trains graphs.PPAnchorHead (conv_cls, conv_box, conv_dir_cls as the one merged 1x1 launch) on the device with the neck frozen.
+    The flat parameter is the merged pack widened to fp32 followed by its bias; the optimizer's shadow is the merged pack's bf16 `w`
+    itself and the pack's bias IS the master's bias slice, so the forward pass behind a step runs on the new weights with no copy.
+    The head owns the trainer (PPAnchorHead._derive): a later to() writes the master back into the three ConvModules, repacks, and
+    binds the trainer to the new pack with its moments and powers kept.
+    optimizer_cfg: train_cfg["optimizer"] (keys of DEFAULT_OPTIMIZER; `type` must be "Adam")."""
+
+    def __init__(self, net, optimizer_cfg=None):
+        cfg = dict(DEFAULT_OPTIMIZER, **dict(optimizer_cfg or {}))
+        if cfg.pop("type") != "Adam":
+            raise ValueError("HeadTrainer: only the reference's Adam is built")
+        unknown = set(cfg) - set(DEFAULT_OPTIMIZER)
+        if unknown:
+            raise ValueError(f"HeadTrainer: optimizer options that are not built: {sorted(unknown)}")
+        self.net, self.head, self.cfg, self.opt = net, net.bbox_head, cfg, None
+        if getattr(self.head, "_merged", None) is None:
+            raise ValueError("HeadTrainer: move the model to its device first (to(device) packs the head)")
+        self.head._trainer = self
+        self.bind()
+
+    def bind(self):
+        """(re)build the flat buffers around the head's current merged pack; the moments, the powers and the fp32 master survive"""
+        pc, old = self.head._merged, self.opt
+        rows, kpad = pc.w.shape
+        dev = pc.w.device
+        opt = Adam(dict(w=(rows, kpad), b=(rows,)), dev, shadow=pc.w, **self.cfg)
+        if old is None:
+            opt.view("w").copy_(pc.w.to(torch.float32))
+            opt.view("b").copy_(pc.bias)
+        else:
+            for k in ("param", "m", "v"):
+                getattr(opt, k).copy_(getattr(old, k).to(dev))
+            opt.beta1_power, opt.beta2_power, opt.steps = old.beta1_power, old.beta2_power, old.steps
+            pc.w.copy_(opt.view("w").to(torch.bfloat16))
+        pc.bias = opt.view("b")          # the bias md_conv2d reads is the fp32 master
+        self.opt = opt
+
+    def train_step(self, pseudo_image, example, lr, beta1=0.9):
+        """One step on a batch: pseudo_image [B,H,W,64] bf16, example = dict(labels, reg_targets) of the model's anchors -> the dict of
+        PointPillarsNet.loss(grad=True) (the loss BEFORE the update) plus `neck`.  Nothing is read back."""
+        net, opt = self.net, self.opt
+        feat = net.neck(pseudo_image)
+        head = self.head(feat)
+        out = net.loss_op()(head, example["labels"], example["reg_targets"], net.anchors, grad=True)
+        det_ops.conv1x1_bwd_weight(feat, out["grad"], self.head._merged, out=(opt.view("w", "grad"), opt.view("b", "grad")))
+        opt.step(lr, beta1)
+        return dict(out, head=head, neck=feat)
+
+    def sync_modules(self):
+        """the fp32 master back into conv_cls / conv_box / conv_dir_cls (weight [cout,cin,1,1], bias [cout]), where weights.py and a
+        repack read it.  A host copy: for export, not for the step."""
+        w, b = self.opt.view("w").detach().cpu(), self.opt.view("b").detach().cpu()
+        row = 0
+        for mod in self.head.children():
+            mod.weight = w[row:row + mod.cout, :mod.cin].reshape(mod.cout, mod.cin, 1, 1).clone()
+            mod.bias = b[row:row + mod.cout].clone()
+            row += mod.cout

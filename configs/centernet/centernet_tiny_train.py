@@ -20,6 +20,10 @@ train_cfg = dict(
                  eig_vec=[[-0.58752847, -0.69563484, 0.41340352], [-0.5832747, 0.00994535, -0.81221408],
                           [-0.56089297, 0.71832671, 0.41158938]],
                  mean=[0.40789654, 0.44719302, 0.47026115], std=[0.28863828, 0.27408164, 0.27809835]),
+    # default_config.yaml:112-132 (train_config: Adam, the MultiDecay schedule); graphs.CenterNet.head_trainer reads `optimizer`,
+    # optim.multi_epochs_decay_lr takes the values of `lr_config`.  The reference's loss_scale_value 1024 is not applied: fp32 gradients.
+    optimizer=dict(type="Adam", eps=1e-7, weight_decay=0.0),
+    lr_config=dict(type="MultiEpochsDecayLR", learning_rate=5e-4, multi_epochs=[90, 120], factor=10, warmup_steps=0, batch_size=16),
 )
 test_cfg = dict(K=20, reg_offset=True)
 

@@ -16,17 +16,29 @@
 //                                are added in order through LDS; wave 0 stores the [16 MT][128] block of the slab to the workspace
 //   conv1x1_wgrad_sum_kernel     per element of dw / db: 8 interleaved chains over the slabs, then the chains in order; padding +0.0
 // The order of every addition is fixed by P alone (the header states the longest chain, L(P)).
+//
+// md_conv_bwd_weight (include/minddet_hip_convbwd.h) is the same two launches for a k x k conv, k = 1 or 3: (tap, channel) is one virtual
+// column axis of k k cin columns, an 8-channel chunk lies inside one tap (cin % 8 == 0), so lane group c owns one tap's chunk and loads
+// its own shifted pixel x[p + d_t] under its own in-image predicate (K = 3 instantiation; K = 1 is the kernel above, unchanged).  The
+// summing launch maps an element of dw to its virtual column (both K orders of a pack) and writes +0.0 outside the layer's blocks.
+//
+// md_conv1x1_bwd_data: dx[p, i] = sum_o dy[p, o] w[o, i], optionally through a ReLU mask.  conv1x1_dgrad_kernel, grid (ceil(P / 256),
+// ceil(cin / 128)): the workgroup keeps the [cout][128] tile of w (bf16) in LDS, each wave takes 16 pixels per step as the MFMA's rows, o
+// as its reduction index (lane (c, q) loads dy[pixel c][4 s + q]: the fast axis of dy, no transpose), eight MFMAs per step and o-quad for
+// the eight channels of lane group c; the lane then holds eight consecutive channels of four pixels and stores them as two 16-byte rows.
 #include <math.h>
 
 #include "aot.h"
 #include "device.h"
-#include "../../include/minddet_hip_train.h"
+#include "../../include/minddet_hip_convbwd.h"
 
 #pragma clang fp contract(off)
 
 namespace md {
 
 static_assert(sizeof(md_conv1x1_bwd_attrs) == 5 * 4, "minddet_hip_train.h: attribute struct layout");
+static_assert(sizeof(md_conv_bwd_attrs) == 24 * 4 && sizeof(md_conv1x1_bwd_data_attrs) == 6 * 4, "minddet_hip_convbwd.h: attribute struct layout");
+static_assert(MD_CONV_BWD_MAX_CIN_K1 == MD_CONV1X1_BWD_MAX_CIN && MD_CONV_BWD_MAX_COUT == MD_CONV1X1_BWD_MAX_COUT, "one kernel, one set of limits");
 
 constexpr int WG_GROUP = 128;   // channels of x per workgroup column: 16 lanes x 8 bf16 = one 16-byte load per lane
 constexpr int WG_RING = 4;      // pixel groups a wave loads ahead of its MFMAs
@@ -36,6 +48,9 @@ struct WgParams {
     int P, S, n_slabs, cin, cout, R;      // R: rows of a partial block = cout rounded up to 16
     int Cx, Cy, x_c_off, dy_c_off, xvec;  // xvec: every 8-channel chunk of x the layer reads is 16-byte aligned
     int rows, kpad, rowsb;                // extents of dw and db (rowsb 0: no db)
+    // md_conv_bwd_weight: KK = taps cin virtual columns (taps = 1: KK = cin), the map's extents, dw's column order and the live blocks
+    int KK, taps, H, W, korder, n_blocks;
+    md_conv_bwd_block blk[MD_CONV_BWD_MAX_BLOCKS];
 };
 
 // x[p][ch .. ch + 7] as four packed words; zero where the lane has no pixel or no channels
@@ -52,7 +67,7 @@ __device__ __forceinline__ u32x4 wg_load_x(const uint16_t *__restrict__ x, size_
     return v;
 }
 
-template <int MT>
+template <int MT, int K>
 __global__ __launch_bounds__(256) void conv1x1_wgrad_kernel(const uint16_t *__restrict__ x, const float *__restrict__ dy, WgParams p,
                                                             float *__restrict__ ws_dw, float *__restrict__ ws_db) {
     __shared__ float s_acc[MT * 8 * 4 * 64];   // one wave's accumulators, [(m 8 + j) 4 + reg][lane]
@@ -61,11 +76,13 @@ __global__ __launch_bounds__(256) void conv1x1_wgrad_kernel(const uint16_t *__re
     const int slab = blockIdx.x, ch = blockIdx.y * WG_GROUP + 8 * c, ob = blockIdx.z * 16 * MT;
     const long long p0 = (long long)slab * p.S;
     const int pend = (int)min((long long)p.P, p0 + p.S);   // one past the slab's last pixel
-    const bool chok = ch < p.cin;                          // (cin % 8 == 0: a chunk is inside the layer or outside it)
+    const int ncol = K == 1 ? p.cin : p.KK;                // columns of a partial block; K = 3: ch is the virtual column tap cin + channel
+    const bool chok = ch < ncol;                           // (cin % 8 == 0: a chunk is inside the layer, and inside one tap, or outside it)
+    const int tap = K == 1 ? 0 : ch / p.cin, ddy = K == 1 ? 0 : tap / K - K / 2, ddx = K == 1 ? 0 : tap % K - K / 2;
     bool rowok[MT];
 #pragma unroll
     for (int m = 0; m < MT; ++m) rowok[m] = ob + 16 * m + c < p.cout;
-    const uint16_t *xs = x + p.x_c_off + ch;
+    const uint16_t *xs = x + p.x_c_off + (ch - tap * p.cin);
     const float *ds = dy + p.dy_c_off + ob + c;
 
     f32x4 acc[MT][8];
@@ -84,7 +101,14 @@ __global__ __launch_bounds__(256) void conv1x1_wgrad_kernel(const uint16_t *__re
     auto load = [&](int s, u32x4 &xv, float (&av)[MT]) {
         const long long pix = p0 + 16LL * s + 4 * wave + q;
         const bool in = pix < pend;
-        xv = wg_load_x(xs, (size_t)pix * p.Cx, in && chok, p.xvec);
+        if constexpr (K == 1) {
+            xv = wg_load_x(xs, (size_t)pix * p.Cx, in && chok, p.xvec);
+        } else {
+            // the tap's pixel p + d_t, zero where it leaves p's own image (row h + ddy, column w + ddx of the same n)
+            const int row = (int)(pix / p.W), w = (int)(pix - (long long)row * p.W) + ddx, h = row % p.H + ddy;
+            const bool inside = (unsigned)h < (unsigned)p.H && (unsigned)w < (unsigned)p.W;
+            xv = wg_load_x(xs, (size_t)(pix + ddy * p.W + ddx) * p.Cx, in && chok && inside, p.xvec);
+        }
 #pragma unroll
         for (int m = 0; m < MT; ++m) av[m] = in && rowok[m] ? ds[(size_t)pix * p.Cy + 16 * m] : 0.f;
     };
@@ -154,7 +178,7 @@ __global__ __launch_bounds__(256) void conv1x1_wgrad_kernel(const uint16_t *__re
             for (int e = 0; e < 4; ++e) {
                 const int o = ob + 16 * m + 4 * q + e;
                 if (o < p.R) {
-                    float *dst = ws_dw + ((size_t)slab * p.R + o) * p.cin + ch;
+                    float *dst = ws_dw + ((size_t)slab * p.R + o) * ncol + ch;
                     *(f32x4 *)dst = (f32x4){acc[m][0][e], acc[m][1][e], acc[m][2][e], acc[m][3][e]};
                     *(f32x4 *)(dst + 4) = (f32x4){acc[m][4][e], acc[m][5][e], acc[m][6][e], acc[m][7][e]};
                 }
@@ -163,6 +187,9 @@ __global__ __launch_bounds__(256) void conv1x1_wgrad_kernel(const uint16_t *__re
 }
 
 // one element of dw (flat index < rows kpad) or db (behind them) per lane & 31; lane >> 5 is the chain
+// G (md_conv_bwd_weight beyond kernel 1 / korder 0 / dense): the element's column is col(t, i) of the header, and an (o, i) outside the
+// blocks has no source: +0.0
+template <bool G>
 __global__ __launch_bounds__(256) void conv1x1_wgrad_sum_kernel(const float *__restrict__ ws_dw, const float *__restrict__ ws_db, WgParams p,
                                                                 float *__restrict__ dw, float *__restrict__ db) {
     __shared__ float red[WG_WAYS][32];
@@ -173,9 +200,28 @@ __global__ __launch_bounds__(256) void conv1x1_wgrad_sum_kernel(const float *__r
     size_t stride = 0;
     if (e < n_dw) {
         const int o = (int)(e / p.kpad), i = (int)(e - (long long)o * p.kpad);
-        if (o < p.cout && i < p.cin) {
-            src = ws_dw + (size_t)o * p.cin + i;
-            stride = (size_t)p.R * p.cin;
+        if constexpr (!G) {
+            if (o < p.cout && i < p.cin) {
+                src = ws_dw + (size_t)o * p.cin + i;
+                stride = (size_t)p.R * p.cin;
+            }
+        } else if (o < p.cout && i < p.KK) {
+            int t, ci;   // column i of dw is tap t, channel ci
+            if (p.korder) {
+                const int g = i / (p.taps * 64), r = i - g * (p.taps * 64);
+                t = r >> 6;
+                ci = g * 64 + (r & 63);
+            } else {
+                t = i / p.cin;
+                ci = i - t * p.cin;
+            }
+            bool live = p.n_blocks == 0;
+            for (int b = 0; b < p.n_blocks; ++b)
+                live = live || (o >= p.blk[b].row0 && o < p.blk[b].row0 + p.blk[b].rows && ci >= p.blk[b].col0 && ci < p.blk[b].col0 + p.blk[b].cols);
+            if (live) {
+                src = ws_dw + (size_t)o * p.KK + t * p.cin + ci;
+                stride = (size_t)p.R * p.KK;
+            }
         }
     } else if (e < total) {
         const int o = (int)(e - n_dw);
@@ -215,11 +261,29 @@ static WgScratch wgrad_scratch(int64_t P, int64_t cin, int64_t cout) {
     return w;
 }
 
-static int conv1x1_bwd_weight_entry(MD_AOT_ARGS) {
+template <int K>
+static void wgrad_launch(int mt, dim3 grid, hipStream_t s, const uint16_t *x, const float *dy, const WgParams &p, float *ws_dw, float *ws_db) {
+    if (mt == 1) hipLaunchKernelGGL((conv1x1_wgrad_kernel<1, K>), grid, dim3(256), 0, s, x, dy, p, ws_dw, ws_db);
+    else if (mt == 2) hipLaunchKernelGGL((conv1x1_wgrad_kernel<2, K>), grid, dim3(256), 0, s, x, dy, p, ws_dw, ws_db);
+    else hipLaunchKernelGGL((conv1x1_wgrad_kernel<4, K>), grid, dim3(256), 0, s, x, dy, p, ws_dw, ws_db);
+}
+
+// md_conv1x1_bwd_weight (kxk false: md_conv1x1_bwd_attrs, a kernel-1, korder-0, dense layer) and md_conv_bwd_weight (md_conv_bwd_attrs)
+static int conv_bwd_weight_entry(MD_AOT_ARGS, bool kxk) {
     // in : x[N,H,W,Cx] bf16, dy[N,H,W,Cy] f32 ; out: dw[rows,kpad] f32, db[rowsb] f32 or NULL ; [workspace]
     const int WS = 4;
     Args a(MD_ARGS, WS, WS + 1);
-    const md_conv1x1_bwd_attrs *at = a.attrs<md_conv1x1_bwd_attrs>(extra);
+    md_conv_bwd_attrs full;
+    memset(&full, 0, sizeof(full));
+    full.kernel = 1;
+    if (kxk) {
+        const md_conv_bwd_attrs *at = a.attrs<md_conv_bwd_attrs>(extra);
+        if (at) full = *at;
+    } else {
+        const md_conv1x1_bwd_attrs *at = a.attrs<md_conv1x1_bwd_attrs>(extra);
+        if (at) { full.cin = at->cin; full.cout = at->cout; full.x_c_off = at->x_c_off; full.dy_c_off = at->dy_c_off; full.reserved0 = at->reserved0; }
+    }
+    const md_conv_bwd_attrs *at = &full;
     a.tensor(0, BF16, 4); a.tensor(1, F32, 4); a.tensor(2, F32, 2); a.optional(3, F32, 1);
     a.optional(WS, U8);
     if (int rc = a.rc()) return rc;
@@ -228,19 +292,25 @@ static int conv1x1_bwd_weight_entry(MD_AOT_ARGS) {
     a.require(N >= 1 && H >= 1 && W >= 1 && Cx >= 1 && Cy >= 1);
     a.require(a.d(1, 0) == N && a.d(1, 1) == H && a.d(1, 2) == W);
     a.require(at->reserved0 == 0 && at->cin >= 1 && at->cout >= 1 && at->x_c_off >= 0 && at->dy_c_off >= 0);
+    a.require((at->kernel == 1 || at->kernel == 3) && (at->korder == 0 || at->korder == 1) && at->n_blocks >= 0 && at->n_blocks <= MD_CONV_BWD_MAX_BLOCKS);
     if (int rc = a.rc()) return rc;
-    const int64_t cin = at->cin, cout = at->cout;
+    const int64_t cin = at->cin, cout = at->cout, taps = at->kernel * at->kernel, KK = taps * cin;
+    for (int b = 0; b < at->n_blocks; ++b) {
+        const md_conv_bwd_block &k = at->blocks[b];
+        a.require(k.row0 >= 0 && k.rows >= 1 && k.col0 >= 0 && k.cols >= 1 && (int64_t)k.row0 + k.rows <= cout && (int64_t)k.col0 + k.cols <= cin);
+    }
     a.require(at->x_c_off + cin <= Cx && at->dy_c_off + cout <= Cy);
-    a.require(a.d(2, 0) >= cout && a.d(2, 1) >= cin && (!with_db || a.d(3, 0) >= cout));
+    a.require(a.d(2, 0) >= cout && a.d(2, 1) >= KK && (!with_db || a.d(3, 0) >= cout));
     a.require(!aliased(params, 2, 4));
     if (int rc = a.rc()) return rc;
     const int64_t lim = (int64_t)1 << 31;
-    if (cin % 8 != 0 || cin > MD_CONV1X1_BWD_MAX_CIN || cout > MD_CONV1X1_BWD_MAX_COUT) return MD_ERR_SIZE;
+    if (cin % 8 != 0 || cin > (at->kernel == 1 ? MD_CONV_BWD_MAX_CIN_K1 : MD_CONV_BWD_MAX_CIN_K3) || cout > MD_CONV_BWD_MAX_COUT) return MD_ERR_SIZE;
+    if (at->korder == 1 && cin % 64 != 0) return MD_ERR_SIZE;
     if (N >= lim || H >= lim || W >= lim || N * H >= lim || N * H * W >= lim) return MD_ERR_SIZE;
     const int64_t P = N * H * W;
     if (a.numel(2) + (with_db ? a.numel(3) : 0) >= lim) return MD_ERR_SIZE;
     if (!a.have({0, 1, 2})) return MD_ERR_ARG;
-    const WgScratch w = wgrad_scratch(P, cin, cout);
+    const WgScratch w = wgrad_scratch(P, KK, cout);
     hipStream_t s = (hipStream_t)stream;
     Scratch ws;
     if (int rc = acquire_aligned(ws, (size_t)w.total, a, WS, s, 16)) return rc;
@@ -251,17 +321,129 @@ static int conv1x1_bwd_weight_entry(MD_AOT_ARGS) {
     p.Cx = (int)Cx; p.Cy = (int)Cy; p.x_c_off = at->x_c_off; p.dy_c_off = at->dy_c_off;
     p.xvec = Cx % 8 == 0 && at->x_c_off % 8 == 0 && (uintptr_t)params[0] % 16 == 0;
     p.rows = (int)a.d(2, 0); p.kpad = (int)a.d(2, 1); p.rowsb = with_db ? (int)a.d(3, 0) : 0;
+    p.KK = (int)KK; p.taps = (int)taps; p.H = (int)H; p.W = (int)W; p.korder = at->korder; p.n_blocks = at->n_blocks;
+    for (int b = 0; b < at->n_blocks; ++b) p.blk[b] = at->blocks[b];
     const uint16_t *x = (const uint16_t *)params[0];
     const float *dy = (const float *)params[1];
     float *ws_dw = (float *)ws.ptr, *ws_db = (float *)((char *)ws.ptr + w.db);
     const int mt = cout <= 16 ? 1 : (cout <= 32 ? 2 : 4);
-    const dim3 grid((unsigned)w.n_slabs, (unsigned)((cin + WG_GROUP - 1) / WG_GROUP), (unsigned)((cout + 16 * mt - 1) / (16 * mt)));
-    if (mt == 1) hipLaunchKernelGGL(conv1x1_wgrad_kernel<1>, grid, dim3(256), 0, s, x, dy, p, ws_dw, ws_db);
-    else if (mt == 2) hipLaunchKernelGGL(conv1x1_wgrad_kernel<2>, grid, dim3(256), 0, s, x, dy, p, ws_dw, ws_db);
-    else hipLaunchKernelGGL(conv1x1_wgrad_kernel<4>, grid, dim3(256), 0, s, x, dy, p, ws_dw, ws_db);
+    const dim3 grid((unsigned)w.n_slabs, (unsigned)((KK + WG_GROUP - 1) / WG_GROUP), (unsigned)((cout + 16 * mt - 1) / (16 * mt)));
+    if (at->kernel == 1) wgrad_launch<1>(mt, grid, s, x, dy, p, ws_dw, ws_db);
+    else wgrad_launch<3>(mt, grid, s, x, dy, p, ws_dw, ws_db);
     const int64_t elems = (int64_t)p.rows * p.kpad + p.rowsb;
-    hipLaunchKernelGGL(conv1x1_wgrad_sum_kernel, dim3((unsigned)((elems + 31) / 32)), dim3(256), 0, s, ws_dw, ws_db, p, (float *)params[2],
-                       with_db ? (float *)params[3] : nullptr);
+    const dim3 sgrid((unsigned)((elems + 31) / 32));
+    float *dw = (float *)params[2], *db = with_db ? (float *)params[3] : nullptr;
+    if (at->kernel == 1 && at->korder == 0 && at->n_blocks == 0) hipLaunchKernelGGL(conv1x1_wgrad_sum_kernel<false>, sgrid, dim3(256), 0, s, ws_dw, ws_db, p, dw, db);
+    else hipLaunchKernelGGL(conv1x1_wgrad_sum_kernel<true>, sgrid, dim3(256), 0, s, ws_dw, ws_db, p, dw, db);
+    return launched();
+}
+
+// ---------------------------------------------------------------------------------------------------- md_conv1x1_bwd_data
+constexpr int DG_PIXELS = 256;   // pixels per workgroup: four steps of 16 per wave behind one fill of the weight tile
+
+struct DgParams {
+    int P, cin, cout, kq;                        // kq: o-quads of the reduction, ceil(cout / 4)
+    int Cy, Cdx, Ca, kpad, dy_c_off, dx_c_off, act_c_off;
+    int wvec, avec, dxvec, has_act;              // 16-byte paths: every chunk of w / act / dx the layer touches is aligned
+};
+
+__global__ __launch_bounds__(256) void conv1x1_dgrad_kernel(const float *__restrict__ dy, const uint16_t *__restrict__ w,
+                                                            const uint16_t *__restrict__ act, DgParams p, float *__restrict__ dx) {
+    extern __shared__ __attribute__((aligned(16))) uint16_t s_w[];   // [4 kq][128]: w[o][128 g + ..], zero past cout and past cin
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, q = lane >> 4;
+    const int g0 = blockIdx.y * WG_GROUP, ch = g0 + 8 * c;
+    const bool chok = ch < p.cin;
+    for (int k = threadIdx.x; k < 4 * p.kq * 16; k += 256) {
+        const int o = k >> 4, cc = g0 + 8 * (k & 15);
+        *(u32x4 *)(s_w + (size_t)k * 8) = wg_load_x(w, (size_t)o * p.kpad + cc, o < p.cout && cc < p.cin, p.wvec);
+    }
+    __syncthreads();
+
+    const float *ds = dy + p.dy_c_off + q;
+    for (int step = 0; step < DG_PIXELS / 64; ++step) {
+        const long long base = (long long)blockIdx.x * DG_PIXELS + 64 * step + 16 * wave;
+        if (base >= p.P) break;
+        const long long pa = base + c;                          // the MFMA row this lane feeds
+        const bool rowok = pa < p.P;
+        const float *dp = ds + (size_t)(rowok ? pa : 0) * p.Cy;
+        f32x4 acc[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int s = 0; s < p.kq; ++s) {
+            const float av = rowok && 4 * s + q < p.cout ? dp[4 * s] : 0.f;
+            const u32x4 wv = *(const u32x4 *)(s_w + ((size_t)(4 * s + q) * 16 + c) * 8);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                acc[2 * k] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, __uint_as_float(wv[k] << 16), acc[2 * k], 0, 0, 0);
+                acc[2 * k + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, __uint_as_float(wv[k] & 0xffff0000u), acc[2 * k + 1], 0, 0, 0);
+            }
+        }
+        // accumulator element e of tile j: pixel base + 4 q + e, channel ch + j: eight consecutive floats per pixel and lane
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const long long pix = base + 4 * q + e;
+            if (!chok || pix >= p.P) continue;
+            float v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = acc[j][e];
+            if (p.has_act) {
+                const u32x4 m = wg_load_x(act, (size_t)pix * p.Ca + p.act_c_off + ch, true, p.avec);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    v[2 * k] = __uint_as_float(m[k] << 16) > 0.f ? v[2 * k] : 0.f;               // (false for -0, a negative, a NaN)
+                    v[2 * k + 1] = __uint_as_float(m[k] & 0xffff0000u) > 0.f ? v[2 * k + 1] : 0.f;
+                }
+            }
+            float *dst = dx + (size_t)pix * p.Cdx + p.dx_c_off + ch;
+            if (p.dxvec) {
+                *(f32x4 *)dst = (f32x4){v[0], v[1], v[2], v[3]};
+                *(f32x4 *)(dst + 4) = (f32x4){v[4], v[5], v[6], v[7]};
+            } else {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) dst[j] = v[j];
+            }
+        }
+    }
+}
+
+static int conv1x1_bwd_data_entry(MD_AOT_ARGS) {
+    // in : dy[N,H,W,Cy] f32, w[rows,kpad] bf16, act[N,H,W,Ca] bf16 or NULL ; out: dx[N,H,W,Cdx] f32
+    Args a(MD_ARGS, 4, 4);
+    const md_conv1x1_bwd_data_attrs *at = a.attrs<md_conv1x1_bwd_data_attrs>(extra);
+    a.tensor(0, F32, 4); a.tensor(1, BF16, 2); a.optional(2, BF16, 4); a.tensor(3, F32, 4);
+    if (int rc = a.rc()) return rc;
+    const int64_t N = a.d(0, 0), H = a.d(0, 1), W = a.d(0, 2), Cy = a.d(0, 3), Cdx = a.d(3, 3);
+    const bool with_act = a.given(2);
+    const int64_t Ca = with_act ? a.d(2, 3) : 0;
+    a.require(N >= 1 && H >= 1 && W >= 1 && Cy >= 1 && Cdx >= 1);
+    a.require(a.d(3, 0) == N && a.d(3, 1) == H && a.d(3, 2) == W);
+    a.require(!with_act || (a.d(2, 0) == N && a.d(2, 1) == H && a.d(2, 2) == W && Ca >= 1));
+    a.require(at->reserved0 == 0 && at->cin >= 1 && at->cout >= 1 && at->dy_c_off >= 0 && at->dx_c_off >= 0 && at->act_c_off >= 0);
+    if (int rc = a.rc()) return rc;
+    const int64_t cin = at->cin, cout = at->cout;
+    a.require(at->dy_c_off + cout <= Cy && at->dx_c_off + cin <= Cdx && (with_act ? at->act_c_off + cin <= Ca : at->act_c_off == 0));
+    a.require(a.d(1, 0) >= cout && a.d(1, 1) >= cin);
+    a.require(!aliased(params, 3, 4));
+    if (int rc = a.rc()) return rc;
+    const int64_t lim = (int64_t)1 << 31;
+    if (cin % 8 != 0 || cin > MD_CONV1X1_BWD_DATA_MAX_CIN || cout > MD_CONV1X1_BWD_DATA_MAX_COUT) return MD_ERR_SIZE;
+    if (N >= lim || H >= lim || W >= lim || N * H >= lim || N * H * W >= lim) return MD_ERR_SIZE;
+    const int64_t P = N * H * W;
+    if (P * Cy >= lim || P * Cdx >= lim || P * Ca >= lim || a.numel(1) >= lim) return MD_ERR_SIZE;
+    if (!a.have({0, 1, 3})) return MD_ERR_ARG;
+
+    DgParams p;
+    memset(&p, 0, sizeof(p));
+    p.P = (int)P; p.cin = (int)cin; p.cout = (int)cout; p.kq = (int)((cout + 3) / 4);
+    p.Cy = (int)Cy; p.Cdx = (int)Cdx; p.Ca = (int)Ca; p.kpad = (int)a.d(1, 1);
+    p.dy_c_off = at->dy_c_off; p.dx_c_off = at->dx_c_off; p.act_c_off = at->act_c_off; p.has_act = with_act;
+    p.wvec = p.kpad % 8 == 0 && (uintptr_t)params[1] % 16 == 0;
+    p.avec = with_act && Ca % 8 == 0 && at->act_c_off % 8 == 0 && (uintptr_t)params[2] % 16 == 0;
+    p.dxvec = Cdx % 4 == 0 && at->dx_c_off % 4 == 0 && (uintptr_t)params[3] % 16 == 0;
+    const dim3 grid((unsigned)((P + DG_PIXELS - 1) / DG_PIXELS), (unsigned)((cin + WG_GROUP - 1) / WG_GROUP));
+    const size_t lds = (size_t)4 * p.kq * WG_GROUP * sizeof(uint16_t);   // at most 256 x 128 x 2 = 64 KiB
+    hipLaunchKernelGGL(conv1x1_dgrad_kernel, grid, dim3(256), lds, (hipStream_t)stream, (const float *)params[0], (const uint16_t *)params[1],
+                       with_act ? (const uint16_t *)params[2] : nullptr, p, (float *)params[3]);
     return launched();
 }
 
@@ -272,4 +454,10 @@ using namespace md;
 extern "C" int64_t md_conv1x1_bwd_weight_workspace_bytes(int64_t P, int64_t cin, int64_t cout) {
     return any_negative({P, cin, cout}) ? -1 : wgrad_scratch(P, cin, cout).total;
 }
-extern "C" int md_conv1x1_bwd_weight(MD_AOT_ARGS) { return conv1x1_bwd_weight_entry(nparam, params, ndims, shapes, dtypes, stream, extra); }
+extern "C" int md_conv1x1_bwd_weight(MD_AOT_ARGS) { return conv_bwd_weight_entry(nparam, params, ndims, shapes, dtypes, stream, extra, false); }
+extern "C" int64_t md_conv_bwd_weight_workspace_bytes(int64_t P, int64_t cin, int64_t cout, int64_t kernel) {
+    return any_negative({P, cin, cout}) || (kernel != 1 && kernel != 3) ? -1 : wgrad_scratch(P, kernel * kernel * cin, cout).total;
+}
+extern "C" int md_conv_bwd_weight(MD_AOT_ARGS) { return conv_bwd_weight_entry(nparam, params, ndims, shapes, dtypes, stream, extra, true); }
+extern "C" int md_conv1x1_bwd_data(MD_AOT_ARGS) { return conv1x1_bwd_data_entry(nparam, params, ndims, shapes, dtypes, stream, extra); }
+

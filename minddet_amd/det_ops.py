@@ -3084,6 +3084,82 @@ def conv1x1_bwd_weight(x, dy, pc, x_c_off=0, dy_c_off=0, out=None, with_bias=Tru
     return dw, db
 
 
+class _ConvBwdBlock(ctypes.Structure):
+    """md_conv_bwd_block (include/minddet_hip_convbwd.h)"""
+    _fields_ = [("row0", ctypes.c_int32), ("rows", ctypes.c_int32), ("col0", ctypes.c_int32), ("cols", ctypes.c_int32)]
+
+
+class _ConvBwdAttrs(ctypes.Structure):
+    """md_conv_bwd_attrs (include/minddet_hip_convbwd.h)"""
+    _fields_ = [("cin", ctypes.c_int32), ("cout", ctypes.c_int32), ("x_c_off", ctypes.c_int32), ("dy_c_off", ctypes.c_int32),
+                ("kernel", ctypes.c_int32), ("korder", ctypes.c_int32), ("n_blocks", ctypes.c_int32), ("blocks", _ConvBwdBlock * 4),
+                ("reserved0", ctypes.c_int32)]
+
+
+class _Conv1x1BwdDataAttrs(ctypes.Structure):
+    """md_conv1x1_bwd_data_attrs (include/minddet_hip_convbwd.h)"""
+    _fields_ = [("cin", ctypes.c_int32), ("cout", ctypes.c_int32), ("dy_c_off", ctypes.c_int32), ("dx_c_off", ctypes.c_int32),
+                ("act_c_off", ctypes.c_int32), ("reserved0", ctypes.c_int32)]
+
+
+def conv_bwd_attrs(cin, cout, x_c_off=0, dy_c_off=0, kernel=1, korder=0, blocks=()):
+    """md_conv_bwd_attrs; blocks: up to four (row0, rows, col0, cols)"""
+    if len(blocks) > 4:
+        raise ValueError(f"conv_bwd_weight: at most 4 blocks, got {len(blocks)}")
+    at = _ConvBwdAttrs(int(cin), int(cout), int(x_c_off), int(dy_c_off), int(kernel), int(korder), len(blocks))
+    for k, b in enumerate(blocks):
+        at.blocks[k] = _ConvBwdBlock(*[int(v) for v in b])
+    return at
+
+
+def conv_bwd_weight_workspace_bytes(P, cin, cout, kernel):
+    return _lib.workspace_bytes("md_conv_bwd_weight", P, cin, cout, kernel)
+
+
+def conv_bwd_weight(x, dy, pc, x_c_off=0, dy_c_off=0, cout=None, blocks=(), out=None, with_bias=True, workspace=True):
+    """Weight and bias gradient of the layer `pc` (nn_ops.PackedConv of a 1x1 or a 3x3 / stride 1 / pad 1 conv) on the device
+    (md_conv_bwd_weight): x [N,H,W,Cx] bf16, the layer's input at channels [x_c_off, x_c_off + pc.cin); dy [N,H,W,Cy] f32, d loss / d
+    output at channels [dy_c_off, dy_c_off + cout) (cout: pc.cout unless given) -> (dw f32 of pc.w's shape and K order, db f32 of
+    pc.bias's shape or None), padding +0.0.  blocks: (row0, rows, col0, cols) ranges of (output, input) channels outside of which dw
+    is +0.0 (a fused block-diagonal layer).  out = (dw, db): written in place.  workspace=False: the library's scratch pool."""
+    who = "conv_bwd_weight"
+    k = pc.kh
+    if pc.kh != pc.kw or k not in (1, 3) or pc.stride != 1 or pc.pad != (k - 1) // 2:
+        raise ValueError(f"{who}: a 1x1 or 3x3 / stride 1 / same-padding layer, got {pc.kh}x{pc.kw} stride {pc.stride} pad {pc.pad}")
+    if x.dtype != torch.bfloat16 or x.dim() != 4 or dy.dtype != torch.float32 or dy.dim() != 4 or tuple(x.shape[:3]) != tuple(dy.shape[:3]):
+        raise ValueError(f"{who}: x is [N,H,W,Cx] bfloat16 and dy [N,H,W,Cy] float32 over the same pixels, got {tuple(x.shape)} {x.dtype}, "
+                         f"{tuple(dy.shape)} {dy.dtype}")
+    rows, kpad = pc.w.shape
+    cout = int(pc.cout if cout is None else cout)
+    if out is None:
+        out = (torch.empty((rows, kpad), dtype=torch.float32, device=x.device),
+               torch.empty((pc.bias.shape[0],), dtype=torch.float32, device=x.device) if with_bias else None)
+    dw, db = out
+    P = x.shape[0] * x.shape[1] * x.shape[2]
+    ws = _lib.scratch("md_conv_bwd_weight", (P, pc.cin, cout, k), x.device) if workspace else None
+    at = conv_bwd_attrs(pc.cin, cout, x_c_off, dy_c_off, k, getattr(pc, "korder", 0) if k > 1 else 0, blocks)
+    _lib.call("md_conv_bwd_weight", [x.contiguous(), dy.contiguous(), dw, db] + ([ws] if ws is not None else []), extra=at)
+    return dw, db
+
+
+def conv1x1_bwd_data(dy, pc, cin=None, cout=None, act=None, dy_c_off=0, dx_c_off=0, act_c_off=0, out=None):
+    """Input gradient of the pointwise layer `pc` (md_conv1x1_bwd_data): dy [N,H,W,Cy] f32 at channels [dy_c_off, dy_c_off + cout), the
+    layer's bf16 pack pc.w as the forward pass read it; act [N,H,W,Ca] bf16 = the layer's input where a ReLU made it (dx is +0.0 where
+    act is not > 0) -> dx [N,H,W,Cdx] f32, written at channels [dx_c_off, dx_c_off + cin) (out: an existing tensor, its other
+    channels are left alone; default a fresh [N,H,W,cin]).  cin / cout default to pc's."""
+    who = "conv1x1_bwd_data"
+    if pc.kh != 1 or pc.kw != 1 or pc.stride != 1 or pc.pad != 0:
+        raise ValueError(f"{who}: a 1x1 / stride 1 / pad 0 layer, got {pc.kh}x{pc.kw} stride {pc.stride} pad {pc.pad}")
+    if dy.dtype != torch.float32 or dy.dim() != 4 or (act is not None and (act.dtype != torch.bfloat16 or tuple(act.shape[:3]) != tuple(dy.shape[:3]))):
+        raise ValueError(f"{who}: dy is [N,H,W,Cy] float32 and act [N,H,W,Ca] bfloat16 over the same pixels")
+    cin, cout = int(pc.cin if cin is None else cin), int(pc.cout if cout is None else cout)
+    if out is None:
+        out = torch.empty(tuple(dy.shape[:3]) + (dx_c_off + cin,), dtype=torch.float32, device=dy.device)
+    at = _Conv1x1BwdDataAttrs(cin, cout, int(dy_c_off), int(dx_c_off), int(act_c_off), 0)
+    _lib.call("md_conv1x1_bwd_data", [dy.contiguous(), pc.w, None if act is None else act.contiguous(), out], extra=at)
+    return out
+
+
 def grad_sumsq_workspace_bytes(n):
     return _lib.workspace_bytes("md_grad_sumsq", n)
 

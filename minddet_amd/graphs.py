@@ -750,9 +750,17 @@ class CenterNet(Module):
     def children(self):
         return [self.backbone] + self.neck + [self.head1, self.head2]
 
+    _trainer = None     # optim.CenterNetHeadTrainer of this model (head_trainer()): derived from the packs of head1 / head2, so owned here
+
     def to(self, device):
+        if self._trainer is not None:
+            self._trainer.sync_modules()    # self.heads is the source of truth of a repack: it gets the trained masters first
         self.fuse_heads()   # head1 / head2 are children whose weights derive from self.heads: refreshed before they are packed
         return super().to(device)
+
+    def _derive(self, device):
+        if self._trainer is not None:
+            self._trainer.bind()            # the trainer's buffers around the new packs; masters, moments and powers kept
 
     def features(self, images):
         x = self.backbone(images)[-1]
@@ -824,6 +832,31 @@ class CenterNet(Module):
         one device chain.  -> the dict of loss() plus `example`."""
         inp, ex = self.train_example(images_u8, sizes, bboxes, category_id, generator=generator, draws=draws, colour=colour)
         return dict(self.loss(inp, ex, grad=grad), example=ex)
+
+    def head_trainer(self, optimizer_cfg=None):
+        """optim.CenterNetHeadTrainer of this model (head1 and head2, the backbone and the neck frozen): train_step(inp, example, lr,
+        beta1) continues loss(grad=True) through md_conv_bwd_weight, md_conv1x1_bwd_data and md_adam_step on the device.
+        optimizer_cfg: None = train_cfg["optimizer"] (none there: optim.CENTERNET_OPTIMIZER).  One trainer per model: a call without a
+        config returns the existing one, a call with one replaces it (fresh moments).  The model has to be on its device."""
+        from . import optim
+
+        if optimizer_cfg is None and self._trainer is not None:
+            return self._trainer
+        cfg = optimizer_cfg if optimizer_cfg is not None else (self.train_cfg or {}).get("optimizer")
+        if self._trainer is not None:       # the replaced trainer leaves its masters in self.heads and lets go of the packs
+            device = self.head1.packed.w.device
+            self._trainer.sync_modules()
+            self._trainer = None
+            self.fuse_heads()
+            for m in (self.head1, self.head2):
+                m.to(device)
+        return optim.CenterNetHeadTrainer(self, cfg)
+
+    def train_step(self, images_u8, sizes, bboxes, category_id, lr, beta1=0.9, generator=None, draws=None, colour=None):
+        """train_example, then one step of head_trainer() on the augmented input: raw images + ground truth -> updated heads as one
+        device chain.  -> the dict of CenterNetHeadTrainer.train_step plus `example`."""
+        inp, ex = self.train_example(images_u8, sizes, bboxes, category_id, generator=generator, draws=draws, colour=colour)
+        return dict(self.head_trainer().train_step(inp, ex, lr, beta1), example=ex)
 
 
 # ----------------------------------------------------------------------------- CenterPoint RPN neck

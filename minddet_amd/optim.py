@@ -1,13 +1,17 @@
 """The optimizer side of a training step: the reference's learning-rate schedules on the host (numpy, one array per run) and its Adam
-on the device (det_ops.grad_sumsq + det_ops.adam_step, include/minddet_hip_train.h), plus the trainer of the KITTI head.
+on the device (det_ops.grad_sumsq + det_ops.adam_step, include/minddet_hip_train.h), plus the trainers of the KITTI head and of
+CenterNet's heads.
 
   OneCycle               centerpoint/det3d_ms/solver/learning_schedules_fastai.py (OneCycle.get_lr: two cosine phases for the rate and
                          for beta1)
   exponential_decay_lr   the schedule pointpillars/train.py:76-93 asks MindSpore for (the function itself is not in the reference)
+  multi_epochs_decay_lr  centernet/src/utils.py:501-538 (MultiEpochsDecayLR, the MultiDecay schedule of centernet/default_config.yaml)
   Adam                   centerpoint/det3d_ms/solver/custom_adam.py:590-668 (Adam.construct); max_norm=None is the plain nn.Adam of
                          pointpillars/train.py
   HeadTrainer            graphs.PointPillarsNet.head_trainer(): neck -> head -> md_pp_loss_grad -> md_conv1x1_bwd_weight ->
                          md_grad_sumsq -> md_adam_step on the merged 1x1 heads, the neck frozen
+  CenterNetHeadTrainer   graphs.CenterNet.head_trainer(): head1 (3x3 + ReLU) -> head2 (block-diagonal 1x1) -> md_cn_loss_grad ->
+                         md_conv_bwd_weight -> md_conv1x1_bwd_data -> md_conv_bwd_weight -> md_adam_step, backbone and neck frozen
 
 Nothing here reads a device value back."""
 import math
@@ -62,6 +66,18 @@ def exponential_decay_lr(learning_rate, decay_rate, total_step, step_per_epoch, 
         e = (i // int(step_per_epoch)) / int(decay_epoch)
         out.append(float(learning_rate) * float(decay_rate) ** (math.floor(e) if is_stair else e))
     return out
+
+
+def multi_epochs_decay_lr(learning_rate, multi_epochs, steps_per_epoch, factor, total_step):
+    """The reference's MultiEpochsDecayLR (centernet/src/utils.py:501-538; CenterNetMultiEpochsDecayLR.construct returns it, its warm-up
+    commented out): learning_rate / factor^k at step i, k = the number of multi_epochs whose first step multi_epochs[j] steps_per_epoch
+    is <= i -> a list of total_step Python floats, evaluated in float64."""
+    if not isinstance(multi_epochs, (list, tuple)):
+        raise TypeError("multi_epochs must be list or tuple.")
+    if total_step < 1 or steps_per_epoch < 1:
+        raise ValueError("multi_epochs_decay_lr: total_step and steps_per_epoch are positive")
+    cuts = [float(e) * int(steps_per_epoch) for e in multi_epochs]
+    return [float(learning_rate) / float(factor) ** sum(c <= i for c in cuts) for i in range(int(total_step))]
 
 
 class Adam:
@@ -176,3 +192,104 @@ class HeadTrainer:
             mod.weight = w[row:row + mod.cout, :mod.cin].reshape(mod.cout, mod.cin, 1, 1).clone()
             mod.bias = b[row:row + mod.cout].clone()
             row += mod.cout
+
+
+CENTERNET_OPTIMIZER = dict(type="Adam", beta2=0.999, eps=1e-7, weight_decay=0.0, max_norm=None, grad_scale=1.0)
+
+
+def pack_columns(pc):
+    """[kh kw, cin] int64: the column of pc.w that holds tap t, input channel i -- the two K orders of nn_ops.pack_conv, col(t, i) of
+    include/minddet_hip_convbwd.h"""
+    taps, cin = pc.kh * pc.kw, pc.cin
+    t, i = torch.meshgrid(torch.arange(taps), torch.arange(cin), indexing="ij")
+    if getattr(pc, "korder", 0) == 1:
+        return (i // 64) * (taps * 64) + t * 64 + i % 64
+    return t * cin + i
+
+
+class CenterNetHeadTrainer:
+    """Trains the heads of graphs.CenterNet (head1: the fused 3x3 conv + ReLU, head2: the block-diagonal 1x1 conv) on the device with
+    the backbone and the neck frozen: head1 -> head2 -> md_cn_loss_grad -> md_conv_bwd_weight (head2, inside its three blocks) ->
+    md_conv1x1_bwd_data (through head1's ReLU) -> md_conv_bwd_weight (head1, 3x3) -> md_adam_step per pack.
+    One Adam per pack (`opts["head1"]`, `opts["head2"]`): the flat parameter is the pack widened to fp32 followed by its bias, the
+    optimizer's shadow is the pack's bf16 `w` itself and the pack's bias IS the master's bias slice, so the forward pass behind a step
+    runs on the new weights with no copy.  The model owns the trainer: a later to() writes the masters back into net.heads (the
+    per-head ConvModules, the source of truth), fuses, repacks, and binds the trainer to the new packs with moments and powers kept.
+    The reference multiplies the loss by loss_scale_value 1024 and divides the gradients by it again; the gradients here are fp32 and no
+    scale is applied (grad_scale 1).  optimizer_cfg: train_cfg["optimizer"] (keys of CENTERNET_OPTIMIZER; `type` must be "Adam";
+    the global-norm clip is not built across two ranges)."""
+
+    def __init__(self, net, optimizer_cfg=None):
+        cfg = dict(CENTERNET_OPTIMIZER, **dict(optimizer_cfg or {}))
+        if cfg.pop("type") != "Adam":
+            raise ValueError("CenterNetHeadTrainer: only the reference's Adam is built")
+        unknown = set(cfg) - set(CENTERNET_OPTIMIZER)
+        if unknown or cfg["max_norm"] is not None:
+            raise ValueError(f"CenterNetHeadTrainer: optimizer options that are not built: {sorted(unknown) or ['max_norm']}")
+        self.net, self.cfg, self.opts = net, cfg, None
+        if net.head1.packed is None or not net.head1.packed.w.is_cuda:
+            raise ValueError("CenterNetHeadTrainer: move the model to its device first (to(device) packs the heads)")
+        net._trainer = self
+        self.bind()
+
+    def blocks(self):
+        """(row0, rows, col0, cols) of hm / wh / reg in head2: the live part of the block-diagonal layer"""
+        out, row, hc = [], 0, self.net.head_conv
+        for k, name in enumerate(("hm", "wh", "reg")):
+            c2 = self.net.heads[name][1]
+            out.append((row, c2.cout, k * hc, hc))
+            row += c2.cout
+        return out
+
+    def bind(self):
+        """(re)build the flat buffers around the model's current packs; the moments, the powers and the fp32 masters survive"""
+        old, opts = self.opts, {}
+        for name in ("head1", "head2"):
+            pc = getattr(self.net, name).packed
+            rows, kpad = pc.w.shape
+            opt = Adam(dict(w=(rows, kpad), b=(rows,)), pc.w.device, shadow=pc.w, **self.cfg)
+            if old is None:
+                opt.view("w").copy_(pc.w.to(torch.float32))
+                opt.view("b").copy_(pc.bias)
+            else:
+                for k in ("param", "m", "v"):
+                    getattr(opt, k).copy_(getattr(old[name], k).to(pc.w.device))
+                opt.beta1_power, opt.beta2_power, opt.steps = old[name].beta1_power, old[name].beta2_power, old[name].steps
+                pc.w.copy_(opt.view("w").to(torch.bfloat16))
+            pc.bias = opt.view("b")          # the bias md_conv2d reads is the fp32 master
+            opts[name] = opt
+        self.opts = opts
+
+    def train_step(self, inp, example, lr, beta1=0.9):
+        """One step on a batch: inp = the network input of CenterNet.train_example, example = its target dict -> the dict of
+        CenterNet.loss(grad=True) (the loss BEFORE the update) plus `x` (the neck's output), `h` (head1's) and `dh`.  Nothing is read
+        back."""
+        net, o1, o2 = self.net, self.opts["head1"], self.opts["head2"]
+        x = net.backbone(inp)[-1]
+        for m in net.neck:
+            x = m(x)
+        h = net.head1(x)
+        head = net.head2(h)
+        out = net.loss_op()(head, example, grad=True)
+        g, pc1, pc2 = out["grad"], net.head1.packed, net.head2.packed
+        det_ops.conv_bwd_weight(h, g, pc2, cout=net.n_out, blocks=self.blocks(), out=(o2.view("w", "grad"), o2.view("b", "grad")))
+        dh = det_ops.conv1x1_bwd_data(g, pc2, cout=net.n_out, act=h)
+        det_ops.conv_bwd_weight(x, dh, pc1, out=(o1.view("w", "grad"), o1.view("b", "grad")))
+        o2.step(lr, beta1)
+        o1.step(lr, beta1)
+        return dict(out, head=head, x=x, h=h, dh=dh)
+
+    def sync_modules(self):
+        """the fp32 masters back into net.heads[name] = (3x3 ConvModule, 1x1 ConvModule) (weight [cout,cin,k,k], bias [cout]), where
+        fuse_heads(), weights.py and a repack read them.  A host copy: for export, not for the step."""
+        net, hc = self.net, self.net.head_conv
+        pc1 = net.head1.packed
+        w1, b1 = self.opts["head1"].view("w").detach().cpu(), self.opts["head1"].view("b").detach().cpu()
+        w2, b2 = self.opts["head2"].view("w").detach().cpu(), self.opts["head2"].view("b").detach().cpu()
+        w1 = w1[:, pack_columns(pc1).reshape(-1)].reshape(w1.shape[0], pc1.kh, pc1.kw, pc1.cin).permute(0, 3, 1, 2)   # [rows, cin, kh, kw]
+        for (row0, rows, col0, cols), name in zip(self.blocks(), ("hm", "wh", "reg")):
+            c1, c2 = net.heads[name]
+            c1.weight = w1[col0:col0 + cols, :c1.cin].clone().contiguous()
+            c1.bias = b1[col0:col0 + cols].clone()
+            c2.weight = w2[row0:row0 + rows, col0:col0 + cols].reshape(rows, cols, 1, 1).clone()
+            c2.bias = b2[row0:row0 + rows].clone()

@@ -1050,11 +1050,12 @@ def yolo_decode(head, boxes, scores, labels, num_classes, num_anchors, stride, a
 
 def assign_targets(anchors, gt_boxes, gt_classes, matched_thr, unmatched_thr, anchors_mask=None):
     """create_target_np (pointpillars/src/core/target_assigner.py:29-166; TargetAssigner.assign :196-224) on the device:
-    -> (labels [A] i32, bbox_targets [A,7] f32, bbox_outside_weights [A] f32, gt_ids [A] i32).  Thresholds: float or [A]."""
+    -> (labels [A] i32, bbox_targets [A,7] f32, bbox_outside_weights [A] f32, gt_ids [A] i32).  Thresholds: float or [A];
+    gt_boxes None or [0,7]: a scene without ground truth."""
     a = _f32c(anchors).reshape(-1, 7)
     dev, A = a.device, a.shape[0]
-    g = _f32c(gt_boxes).reshape(-1, 7)
-    G = g.shape[0]
+    g = None if gt_boxes is None else _f32c(gt_boxes).reshape(-1, 7)
+    G = 0 if g is None else g.shape[0]
     cls = (torch.ones((G,), dtype=torch.int32, device=dev) if gt_classes is None
            else gt_classes.to(device=dev, dtype=torch.int32).contiguous())
 

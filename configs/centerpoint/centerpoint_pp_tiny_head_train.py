@@ -1,16 +1,14 @@
-# CenterPoint on pillars from raw points, test-sized, with the training settings: a PillarDetector on a 64 x 64 grid (0.2 m cells,
-# 12.8 m x 12.8 m), two tasks, a 16 x 16 head, at most 32 objects per sample.  For the training chain raw points + ground truth ->
-# augmented points -> voxels -> canvas -> head -> targets -> loss (PillarDetector.train_loss); the keys are those of
-# centerpoint_pp_nusc_train.py.  centerpoint_pp_tiny_points_train.py restated, with the multi-sweep step of
-# centerpoint_pp_nusc_sweeps.py in front: the key frame and two past sweeps (PillarDetector.merge_sweeps / forward_sweeps).
-
-sweeps = dict(nsweeps=3, min_distance=1.0, order="key_first")
+# CenterPoint on pillars at the pseudo-image level, test-sized, with the training settings: the neck and the head of
+# centerpoint_pp_tiny_points_train.py behind a 64 x 64 pseudo-image (0.2 m cells, 12.8 m x 12.8 m), two tasks (12 SepHead branches), a
+# 16 x 16 head, at most 32 objects per sample.  For the head's training step (graphs.PointPillars.train_step: pseudo-image + targets ->
+# updated head); the keys are those of centerpoint_pp_nusc_train.py.
 
 tasks = [
     dict(num_class=1, class_names=["car"]),
     dict(num_class=2, class_names=["pedestrian", "traffic_cone"]),
 ]
 
+# the grid the pseudo-image stands for (det_ops.CenterPointTargets reads the range and the voxel size; the model takes the canvas itself)
 voxel_generator = dict(
     range=[-6.4, -6.4, -5.0, 6.4, 6.4, 3.0],
     voxel_size=[0.2, 0.2, 8],
@@ -19,10 +17,7 @@ voxel_generator = dict(
 )
 
 model = dict(
-    type="PillarDetector",
-    reader=dict(type="PillarFeatureNet", num_filters=[64, 64], num_input_features=5, with_distance=False, voxel_size=(0.2, 0.2, 8),
-                pc_range=(-6.4, -6.4, -5.0, 6.4, 6.4, 3.0)),
-    backbone=dict(type="PointPillarsScatter", ds_factor=1),
+    type="PointPillars",
     neck=dict(type="RPN", layer_nums=[3, 5, 5], ds_layer_strides=[2, 2, 2], ds_num_filters=[64, 128, 256],
               us_layer_strides=[0.5, 1, 2], us_num_filters=[128, 128, 128], num_input_features=64),
     bbox_head=dict(
@@ -34,8 +29,6 @@ model = dict(
         num_hm_conv=2,
         init_bias=-2.19,
     ),
-    voxel_generator=voxel_generator,
-    sweeps=sweeps,
 )
 
 train_cfg = dict(
@@ -47,9 +40,6 @@ train_cfg = dict(
         min_radius=2,
     ),
     loss=dict(weight=0.25, code_weights=[1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 0.2, 0.2, 1.0, 1.0]),
-    augment=dict(global_rot_noise=[-0.3925, 0.3925], global_scale_noise=[0.95, 1.05], global_translate_std=0.2, min_points_in_gt=2),
-    max_voxel_num=2048,
-    # the training settings of centerpoint_pp_tiny_points_train.py, its optimizer and schedule included
     optimizer=dict(type="Adam", weight_decay=0.01, max_norm=35.0),
     lr_config=dict(type="OneCycle", lr_max=1e-3, moms=[0.95, 0.85], div_factor=10.0, pct_start=0.4),
 )
@@ -65,4 +55,4 @@ test_cfg = dict(
     voxel_size=voxel_size,
 )
 
-data = dict(points_features=5, pseudo_image_hw=(64, 64), pseudo_image_channels=64, sweeps=sweeps)
+data = dict(pseudo_image_hw=(64, 64), pseudo_image_channels=64)

@@ -45,6 +45,10 @@ train_cfg = dict(
     loss=dict(weight=0.25, code_weights=[1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 0.2, 0.2, 1.0, 1.0]),
     augment=dict(global_rot_noise=[-0.3925, 0.3925], global_scale_noise=[0.95, 1.05], global_translate_std=0.2, min_points_in_gt=2),
     max_voxel_num=2048,
+    # the reference's nuScenes schedule: Adam with weight decay 0.01 behind a global-norm clip at 35 (optim.CENTERPOINT_OPTIMIZER), the
+    # OneCycle rate and beta1 (optim.OneCycle); graphs.PillarDetector.head_trainer() reads `optimizer`
+    optimizer=dict(type="Adam", weight_decay=0.01, max_norm=35.0),
+    lr_config=dict(type="OneCycle", lr_max=1e-3, moms=[0.95, 0.85], div_factor=10.0, pct_start=0.4),
 )
 
 voxel_size = [0.2, 0.2]

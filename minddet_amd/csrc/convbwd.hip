@@ -26,11 +26,16 @@
 // ceil(cin / 128)): the workgroup keeps the [cout][128] tile of w (bf16) in LDS, each wave takes 16 pixels per step as the MFMA's rows, o
 // as its reduction index (lane (c, q) loads dy[pixel c][4 s + q]: the fast axis of dy, no transpose), eight MFMAs per step and o-quad for
 // the eight channels of lane group c; the lane then holds eight consecutive channels of four pixels and stores them as two 16-byte rows.
+//
+// md_conv2d_grouped_bwd_weight / _bwd_data (include/minddet_hip_groupedbwd.h) carry the gradient through md_conv2d_grouped (grouped.hip):
+// the weight gradient is wgrad_body<1, K> with the group as blockIdx.z (grouped_wgrad_kernel) and a summing launch that finds an element's
+// group by its row; the data gradient is grouped_dgrad_kernel, the pointwise form with (tap, o) as the reduction index and each lane's own
+// shifted pixel of dy, 64 channels (one group) per 16 lanes.
 #include <math.h>
 
 #include "aot.h"
 #include "device.h"
-#include "../../include/minddet_hip_convbwd.h"
+#include "../../include/minddet_hip_groupedbwd.h"
 
 #pragma clang fp contract(off)
 
@@ -67,13 +72,14 @@ __device__ __forceinline__ u32x4 wg_load_x(const uint16_t *__restrict__ x, size_
     return v;
 }
 
+// the body of the first launch; ob: the first output channel of the workgroup's 16 MT rows
 template <int MT, int K>
-__global__ __launch_bounds__(256) void conv1x1_wgrad_kernel(const uint16_t *__restrict__ x, const float *__restrict__ dy, WgParams p,
-                                                            float *__restrict__ ws_dw, float *__restrict__ ws_db) {
+__device__ __forceinline__ void wgrad_body(const uint16_t *__restrict__ x, const float *__restrict__ dy, const WgParams &p,
+                                           float *__restrict__ ws_dw, float *__restrict__ ws_db, const int ob) {
     __shared__ float s_acc[MT * 8 * 4 * 64];   // one wave's accumulators, [(m 8 + j) 4 + reg][lane]
     __shared__ float s_db[4][MT * 16];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, q = lane >> 4;
-    const int slab = blockIdx.x, ch = blockIdx.y * WG_GROUP + 8 * c, ob = blockIdx.z * 16 * MT;
+    const int slab = blockIdx.x, ch = blockIdx.y * WG_GROUP + 8 * c;
     const long long p0 = (long long)slab * p.S;
     const int pend = (int)min((long long)p.P, p0 + p.S);   // one past the slab's last pixel
     const int ncol = K == 1 ? p.cin : p.KK;                // columns of a partial block; K = 3: ch is the virtual column tap cin + channel
@@ -186,6 +192,44 @@ __global__ __launch_bounds__(256) void conv1x1_wgrad_kernel(const uint16_t *__re
     }
 }
 
+template <int MT, int K>
+__global__ __launch_bounds__(256) void conv1x1_wgrad_kernel(const uint16_t *__restrict__ x, const float *__restrict__ dy, WgParams p,
+                                                            float *__restrict__ ws_dw, float *__restrict__ ws_db) {
+    wgrad_body<MT, K>(x, dy, p, ws_dw, ws_db, blockIdx.z * 16 * MT);
+}
+
+// md_conv2d_grouped_bwd_weight: the same body, blockIdx.z is the group; its channel offsets, its cout and its part of the workspace come
+// from the table (one 16-row tile per group: cout <= 16)
+struct GroupTable {
+    int G, per_dw, per_db;   // floats of one group's dw / db partials in the workspace
+    int cout[MD_GROUPED_MAX_GROUPS], y_off[MD_GROUPED_MAX_GROUPS], w_row[MD_GROUPED_MAX_GROUPS];
+};
+
+template <int K>
+__global__ __launch_bounds__(256) void grouped_wgrad_kernel(const uint16_t *__restrict__ x, const float *__restrict__ dy, WgParams p, GroupTable t,
+                                                            float *__restrict__ ws_dw, float *__restrict__ ws_db) {
+    const int g = blockIdx.z;
+    p.x_c_off += 64 * g;
+    p.dy_c_off = t.y_off[g];
+    p.cout = t.cout[g];
+    wgrad_body<1, K>(x, dy, p, ws_dw + (size_t)g * t.per_dw, ws_db + (size_t)g * t.per_db, 0);
+}
+
+// the sum of one element's slab partials: WG_WAYS interleaved chains over the slabs, then the chains in order
+__device__ __forceinline__ float wgrad_sum_slabs(const float *__restrict__ src, size_t stride, int n_slabs, float (&red)[WG_WAYS][32], int t, int way) {
+    float acc = 0.f;
+    if (src) {
+#pragma unroll 4
+        for (int s = way; s < n_slabs; s += WG_WAYS) acc += src[(size_t)s * stride];
+    }
+    red[way][t] = acc;
+    __syncthreads();
+    float v = red[0][t];
+#pragma unroll
+    for (int k = 1; k < WG_WAYS; ++k) v += red[k][t];
+    return src ? v + 0.f : 0.f;   // (a sum of -0.0 alone leaves +0.0 as well)
+}
+
 // one element of dw (flat index < rows kpad) or db (behind them) per lane & 31; lane >> 5 is the chain
 // G (md_conv_bwd_weight beyond kernel 1 / korder 0 / dense): the element's column is col(t, i) of the header, and an (o, i) outside the
 // blocks has no source: +0.0
@@ -230,18 +274,35 @@ __global__ __launch_bounds__(256) void conv1x1_wgrad_sum_kernel(const float *__r
             stride = (size_t)p.R;
         }
     }
-    float acc = 0.f;
-    if (src) {
-#pragma unroll 4
-        for (int s = way; s < p.n_slabs; s += WG_WAYS) acc += src[(size_t)s * stride];
-    }
-    red[way][t] = acc;
-    __syncthreads();
+    const float v = wgrad_sum_slabs(src, stride, p.n_slabs, red, t, way);
     if (way == 0 && e < total) {
-        float v = red[0][t];
-#pragma unroll
-        for (int k = 1; k < WG_WAYS; ++k) v += red[k][t];
-        v = src ? v + 0.f : 0.f;   // (a sum of -0.0 alone leaves +0.0 as well)
+        if (e < n_dw) dw[e] = v;
+        else db[e - n_dw] = v;
+    }
+}
+
+// md_conv2d_grouped_bwd_weight: an element of dw[R][KK] / db[R] belongs to the group whose rows hold it (none: +0.0)
+__global__ __launch_bounds__(256) void grouped_wgrad_sum_kernel(const float *__restrict__ ws_dw, const float *__restrict__ ws_db, WgParams p, GroupTable tb,
+                                                                float *__restrict__ dw, float *__restrict__ db) {
+    __shared__ float red[WG_WAYS][32];
+    const int t = threadIdx.x & 31, way = threadIdx.x >> 5;
+    const long long n_dw = (long long)p.rows * p.kpad, total = n_dw + p.rowsb;
+    const long long e = (long long)blockIdx.x * 32 + t;
+    const float *src = nullptr;
+    size_t stride = 0;
+    if (e < total) {
+        const bool is_w = e < n_dw;
+        const int o = is_w ? (int)(e / p.kpad) : (int)(e - n_dw), i = is_w ? (int)(e - (long long)o * p.kpad) : 0;
+        for (int g = 0; g < tb.G; ++g) {
+            const int r = o - tb.w_row[g];
+            if (r >= 0 && r < tb.cout[g]) {
+                src = is_w ? ws_dw + (size_t)g * tb.per_dw + (size_t)r * p.KK + i : ws_db + (size_t)g * tb.per_db + r;
+                stride = is_w ? (size_t)p.R * p.KK : (size_t)p.R;
+            }
+        }
+    }
+    const float v = wgrad_sum_slabs(src, stride, p.n_slabs, red, t, way);
+    if (way == 0 && e < total) {
         if (e < n_dw) dw[e] = v;
         else db[e - n_dw] = v;
     }
@@ -447,6 +508,242 @@ static int conv1x1_bwd_data_entry(MD_AOT_ARGS) {
     return launched();
 }
 
+// ---------------------------------------------------------------------------------------------------- md_conv2d_grouped_bwd_*
+// the forward table as both backward operators take it: R rows of the pack, Cy channels of dy, Cs channels of the tensor(s) the groups'
+// 64-channel slices lie in (x; dx and act).  Every check of the table; the caller asks a.rc() behind it.
+static void grouped_table_checks(Args &a, const md_conv2d_grouped_attrs *at, int64_t R, int64_t Cy, int64_t Cs, bool disjoint_rows) {
+    if (!a.require(at->reserved0 == 0 && (at->k == 1 || at->k == 3) && at->relu == 0 && at->cin_g == 64)) return;
+    if (!a.require(at->groups >= 1 && at->groups <= MD_GROUPED_MAX_GROUPS)) return;
+    a.require(at->x_c_off >= 0 && at->x_c_off + (int64_t)at->groups * 64 <= Cs);
+    for (int g = 0; g < at->groups; ++g) {
+        const int64_t co = at->cout[g], yo = at->y_off[g], wr = at->w_row[g];
+        a.require(co >= 1 && co <= 16 && yo >= 0 && yo + co <= Cy && wr >= 0 && wr + co <= R);
+        for (int h = 0; disjoint_rows && h < g; ++h)   // two groups summing into one row of dw
+            a.require(!(wr < (int64_t)at->w_row[h] + at->cout[h] && at->w_row[h] < wr + co));
+    }
+}
+
+// 16-pixel steps of a wave behind one read of a w fragment.  One: the kernel waits on its dy and act loads, so waves per SIMD count
+// (83 VGPRs); four steps (232 VGPRs, two waves per SIMD) took 1.56x the time at the nuScenes shape
+constexpr int GD_STEPS = MD_GROUPED_BWD_TILE / 64;
+
+struct GdParams {
+    int P, H, W, Cy, Cdx, Ca, KW;             // KW = k k 64, a row of the pack
+    int x_c_off, has_act, wvec, avec, dxvec;  // wide paths: every 8-byte piece of w / act and every 16-byte piece of dx is aligned
+    int G;
+    int cout[MD_GROUPED_MAX_GROUPS], y_off[MD_GROUPED_MAX_GROUPS], w_row[MD_GROUPED_MAX_GROUPS];
+};
+
+// grid (ceil(P / MD_GROUPED_BWD_TILE), ceil(G / MD_GROUPED_BWD_WALK)).  Lane (c, q) feeds MFMA row c (pixel c of a step) with
+// dy[pixel - d_t][o = 4 s + q] and column c of MFMA j with w[o][t 64 + 4 c + j]: after the four MFMAs of a step the lane holds channels
+// 4 c .. 4 c + 3 of pixels 4 q .. 4 q + 3 and stores each as one 16-byte row, 256 contiguous bytes per pixel and group.  The taps are
+// unrolled, so a group's nine dy loads per lane are in flight together.
+template <int K>
+__global__ __launch_bounds__(256, 4) void grouped_dgrad_kernel(const float *__restrict__ dy, const uint16_t *__restrict__ w,
+                                                            const uint16_t *__restrict__ act, GdParams p, float *__restrict__ dx) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, q = lane >> 4;
+    const long long base = (long long)blockIdx.x * MD_GROUPED_BWD_TILE + 16 * GD_STEPS * wave;
+    if (base >= p.P) return;   // the whole wave; the kernel has no barrier
+    long long pix[GD_STEPS];   // the pixel of the MFMA row this lane feeds in step u, its row and column in its own image
+    int ph[GD_STEPS], pw[GD_STEPS];
+#pragma unroll
+    for (int u = 0; u < GD_STEPS; ++u) {
+        pix[u] = base + 16 * u + c;
+        const long long pc = pix[u] < p.P ? pix[u] : 0;
+        const int row = (int)(pc / p.W);
+        pw[u] = (int)(pc - (long long)row * p.W);
+        ph[u] = row % p.H;
+    }
+    for (int gi = 0; gi < MD_GROUPED_BWD_WALK; ++gi) {
+        const int g = blockIdx.y * MD_GROUPED_BWD_WALK + gi;
+        if (g >= p.G) break;
+        const int cout = p.cout[g], cq = (cout + 3) >> 2;
+        const float *dg = dy + p.y_off[g];
+        const uint16_t *wg = w + (size_t)p.w_row[g] * p.KW + 4 * c;
+        f32x4 acc[GD_STEPS][4];
+#pragma unroll
+        for (int u = 0; u < GD_STEPS; ++u)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[u][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int t = 0; t < K * K; ++t) {
+            const int ddy = t / K - K / 2, ddx = t % K - K / 2;
+            // the term's pixel q - d_t, inside q's own image or no term
+            bool in[GD_STEPS];
+            size_t off[GD_STEPS];
+#pragma unroll
+            for (int u = 0; u < GD_STEPS; ++u) {
+                in[u] = pix[u] < p.P && (unsigned)(ph[u] - ddy) < (unsigned)p.H && (unsigned)(pw[u] - ddx) < (unsigned)p.W;
+                off[u] = in[u] ? (size_t)(pix[u] - ddy * p.W - ddx) * p.Cy : 0;
+            }
+            for (int s = 0; s < cq; ++s) {
+                const int o = 4 * s + q;
+                const bool live = o < cout;
+                unsigned w01 = 0u, w23 = 0u;   // w[o][t 64 + 4 c .. + 3]; rows past cout are zero
+                if (live) {
+                    const uint16_t *wp = wg + (size_t)o * p.KW + t * 64;
+                    if (p.wvec) {
+                        const u32x2 v = *(const u32x2 *)wp;
+                        w01 = v[0];
+                        w23 = v[1];
+                    } else {
+                        w01 = (unsigned)wp[0] | ((unsigned)wp[1] << 16);
+                        w23 = (unsigned)wp[2] | ((unsigned)wp[3] << 16);
+                    }
+                }
+                const float b0 = __uint_as_float(w01 << 16), b1 = __uint_as_float(w01 & 0xffff0000u);
+                const float b2 = __uint_as_float(w23 << 16), b3 = __uint_as_float(w23 & 0xffff0000u);
+#pragma unroll
+                for (int u = 0; u < GD_STEPS; ++u) {
+                    const float av = in[u] && live ? dg[off[u] + o] : 0.f;
+                    acc[u][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b0, acc[u][0], 0, 0, 0);
+                    acc[u][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b1, acc[u][1], 0, 0, 0);
+                    acc[u][2] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b2, acc[u][2], 0, 0, 0);
+                    acc[u][3] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b3, acc[u][3], 0, 0, 0);
+                }
+            }
+        }
+        // accumulator element e of MFMA j in step u: pixel base + 16 u + 4 q + e, channel 64 g + 4 c + j
+        const int chn = p.x_c_off + 64 * g + 4 * c;
+#pragma unroll
+        for (int u = 0; u < GD_STEPS; ++u)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const long long px = base + 16 * u + 4 * q + e;
+                if (px >= p.P) continue;
+                float v[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) v[j] = acc[u][j][e];
+                if (p.has_act) {
+                    const uint16_t *ap = act + (size_t)px * p.Ca + chn;
+                    unsigned m01, m23;
+                    if (p.avec) {
+                        const u32x2 m = *(const u32x2 *)ap;
+                        m01 = m[0];
+                        m23 = m[1];
+                    } else {
+                        m01 = (unsigned)ap[0] | ((unsigned)ap[1] << 16);
+                        m23 = (unsigned)ap[2] | ((unsigned)ap[3] << 16);
+                    }
+                    v[0] = __uint_as_float(m01 << 16) > 0.f ? v[0] : 0.f;            // (false for -0, a negative, a NaN)
+                    v[1] = __uint_as_float(m01 & 0xffff0000u) > 0.f ? v[1] : 0.f;
+                    v[2] = __uint_as_float(m23 << 16) > 0.f ? v[2] : 0.f;
+                    v[3] = __uint_as_float(m23 & 0xffff0000u) > 0.f ? v[3] : 0.f;
+                }
+                float *dst = dx + (size_t)px * p.Cdx + chn;
+                if (p.dxvec) {
+                    *(f32x4 *)dst = (f32x4){v[0], v[1], v[2], v[3]};
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) dst[j] = v[j];
+                }
+            }
+    }
+}
+
+static int grouped_bwd_data_entry(MD_AOT_ARGS) {
+    // in : dy[N,H,W,Cy] f32, w[R, k k 64] bf16, act[N,H,W,Ca] bf16 or NULL ; out: dx[N,H,W,Cdx] f32
+    Args a(MD_ARGS, 4, 4);
+    const md_conv2d_grouped_attrs *at = a.attrs<md_conv2d_grouped_attrs>(extra);
+    a.tensor(0, F32, 4); a.tensor(1, BF16, 2); a.optional(2, BF16, 4); a.tensor(3, F32, 4);
+    if (int rc = a.rc()) return rc;
+    const int64_t N = a.d(0, 0), H = a.d(0, 1), W = a.d(0, 2), Cy = a.d(0, 3), Cdx = a.d(3, 3), R = a.d(1, 0);
+    const bool with_act = a.given(2);
+    const int64_t Ca = with_act ? a.d(2, 3) : 0;
+    a.require(N >= 1 && H >= 1 && W >= 1 && Cy >= 1 && Cdx >= 1 && R >= 1);
+    a.require(a.d(3, 0) == N && a.d(3, 1) == H && a.d(3, 2) == W);
+    a.require(!with_act || (a.d(2, 0) == N && a.d(2, 1) == H && a.d(2, 2) == W));
+    grouped_table_checks(a, at, R, Cy, with_act && Ca < Cdx ? Ca : Cdx, false);
+    if (int rc = a.rc()) return rc;
+    a.require(a.d(1, 1) == (int64_t)at->k * at->k * 64);
+    a.require(!aliased(params, 3, 4));
+    if (int rc = a.rc()) return rc;
+    const int64_t lim = (int64_t)1 << 31;
+    if (N >= lim || H >= lim || W >= lim || N * H >= lim || N * H * W >= lim) return MD_ERR_SIZE;
+    const int64_t P = N * H * W;
+    if (P * Cy >= lim || P * Cdx >= lim || P * Ca >= lim || a.numel(1) >= lim) return MD_ERR_SIZE;
+    if (!a.have({0, 1, 3})) return MD_ERR_ARG;
+
+    GdParams p;
+    memset(&p, 0, sizeof(p));
+    p.P = (int)P; p.H = (int)H; p.W = (int)W; p.Cy = (int)Cy; p.Cdx = (int)Cdx; p.Ca = (int)Ca; p.KW = at->k * at->k * 64;
+    p.x_c_off = at->x_c_off; p.has_act = with_act; p.G = at->groups;
+    p.wvec = (uintptr_t)params[1] % 8 == 0;
+    p.avec = with_act && Ca % 4 == 0 && at->x_c_off % 4 == 0 && (uintptr_t)params[2] % 8 == 0;
+    p.dxvec = Cdx % 4 == 0 && at->x_c_off % 4 == 0 && (uintptr_t)params[3] % 16 == 0;
+    for (int g = 0; g < at->groups; ++g) { p.cout[g] = at->cout[g]; p.y_off[g] = at->y_off[g]; p.w_row[g] = at->w_row[g]; }
+    const dim3 grid((unsigned)((P + MD_GROUPED_BWD_TILE - 1) / MD_GROUPED_BWD_TILE), (unsigned)((at->groups + MD_GROUPED_BWD_WALK - 1) / MD_GROUPED_BWD_WALK));
+    const float *dy = (const float *)params[0];
+    const uint16_t *w = (const uint16_t *)params[1], *act = with_act ? (const uint16_t *)params[2] : nullptr;
+    if (at->k == 1) hipLaunchKernelGGL(grouped_dgrad_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, dy, w, act, p, (float *)params[3]);
+    else hipLaunchKernelGGL(grouped_dgrad_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, dy, w, act, p, (float *)params[3]);
+    return launched();
+}
+
+// scratch of md_conv2d_grouped_bwd_weight: per group the scratch of md_conv_bwd_weight for one group (cin 64, one 16-row tile), the groups'
+// dw partials back to back at 0, then their db partials
+struct GwScratch { WgScratch one; int64_t per_dw, per_db, db, total; };
+static GwScratch grouped_wgrad_scratch(int64_t P, int64_t groups, int64_t k) {
+    GwScratch s;
+    s.one = wgrad_scratch(P, k * k * 64, 16);
+    s.per_dw = s.one.db / 4;
+    s.per_db = (s.one.total - s.one.db) / 4;
+    s.db = groups * s.one.db;
+    s.total = groups * s.one.total;
+    return s;
+}
+
+static int grouped_bwd_weight_entry(MD_AOT_ARGS) {
+    // in : x[N,H,W,C] bf16, dy[N,H,W,Cy] f32 ; out: dw[R, k k 64] f32, db[R] f32 or NULL ; [workspace]
+    const int WS = 4;
+    Args a(MD_ARGS, WS, WS + 1);
+    const md_conv2d_grouped_attrs *at = a.attrs<md_conv2d_grouped_attrs>(extra);
+    a.tensor(0, BF16, 4); a.tensor(1, F32, 4); a.tensor(2, F32, 2); a.optional(3, F32, 1);
+    a.optional(WS, U8);
+    if (int rc = a.rc()) return rc;
+    const int64_t N = a.d(0, 0), H = a.d(0, 1), W = a.d(0, 2), Cx = a.d(0, 3), Cy = a.d(1, 3), R = a.d(2, 0);
+    const bool with_db = a.given(3);
+    a.require(N >= 1 && H >= 1 && W >= 1 && Cx >= 1 && Cy >= 1 && R >= 1);
+    a.require(a.d(1, 0) == N && a.d(1, 1) == H && a.d(1, 2) == W);
+    grouped_table_checks(a, at, R, Cy, Cx, true);
+    if (int rc = a.rc()) return rc;
+    const int64_t KK = (int64_t)at->k * at->k * 64, G = at->groups;
+    a.require(a.d(2, 1) == KK && (!with_db || a.d(3, 0) == R));
+    a.require(!aliased(params, 2, 4));
+    if (int rc = a.rc()) return rc;
+    const int64_t lim = (int64_t)1 << 31;
+    if (N >= lim || H >= lim || W >= lim || N * H >= lim || N * H * W >= lim) return MD_ERR_SIZE;
+    const int64_t P = N * H * W;
+    if (P * Cx >= lim || P * Cy >= lim || a.numel(2) + (with_db ? a.numel(3) : 0) >= lim) return MD_ERR_SIZE;
+    if (!a.have({0, 1, 2})) return MD_ERR_ARG;
+    const GwScratch w = grouped_wgrad_scratch(P, G, at->k);
+    hipStream_t s = (hipStream_t)stream;
+    Scratch ws;
+    if (int rc = acquire_aligned(ws, (size_t)w.total, a, WS, s, 16)) return rc;
+
+    WgParams p;   // one group's md_conv_bwd_weight call (cin 64, korder 0, dense); the kernel fills in the group's offsets and cout
+    memset(&p, 0, sizeof(p));
+    p.P = (int)P; p.S = (int)w.one.S; p.n_slabs = (int)w.one.n_slabs; p.cin = 64; p.cout = 0; p.R = (int)w.one.R;
+    p.Cx = (int)Cx; p.Cy = (int)Cy; p.x_c_off = at->x_c_off; p.dy_c_off = 0;
+    p.xvec = Cx % 8 == 0 && at->x_c_off % 8 == 0 && (uintptr_t)params[0] % 16 == 0;
+    p.rows = (int)R; p.kpad = (int)KK; p.rowsb = with_db ? (int)R : 0;
+    p.KK = (int)KK; p.taps = at->k * at->k; p.H = (int)H; p.W = (int)W;
+    GroupTable t;
+    memset(&t, 0, sizeof(t));
+    t.G = (int)G; t.per_dw = (int)w.per_dw; t.per_db = (int)w.per_db;
+    for (int g = 0; g < G; ++g) { t.cout[g] = at->cout[g]; t.y_off[g] = at->y_off[g]; t.w_row[g] = at->w_row[g]; }
+    const uint16_t *x = (const uint16_t *)params[0];
+    const float *dy = (const float *)params[1];
+    float *ws_dw = (float *)ws.ptr, *ws_db = (float *)((char *)ws.ptr + w.db);
+    const dim3 grid((unsigned)w.one.n_slabs, (unsigned)((KK + WG_GROUP - 1) / WG_GROUP), (unsigned)G);
+    if (at->k == 1) hipLaunchKernelGGL(grouped_wgrad_kernel<1>, grid, dim3(256), 0, s, x, dy, p, t, ws_dw, ws_db);
+    else hipLaunchKernelGGL(grouped_wgrad_kernel<3>, grid, dim3(256), 0, s, x, dy, p, t, ws_dw, ws_db);
+    const int64_t elems = (int64_t)p.rows * p.kpad + p.rowsb;
+    float *dw = (float *)params[2], *db = with_db ? (float *)params[3] : nullptr;
+    hipLaunchKernelGGL(grouped_wgrad_sum_kernel, dim3((unsigned)((elems + 31) / 32)), dim3(256), 0, s, ws_dw, ws_db, p, t, dw, db);
+    return launched();
+}
+
 }  // namespace md
 
 using namespace md;
@@ -460,4 +757,9 @@ extern "C" int64_t md_conv_bwd_weight_workspace_bytes(int64_t P, int64_t cin, in
 }
 extern "C" int md_conv_bwd_weight(MD_AOT_ARGS) { return conv_bwd_weight_entry(nparam, params, ndims, shapes, dtypes, stream, extra, true); }
 extern "C" int md_conv1x1_bwd_data(MD_AOT_ARGS) { return conv1x1_bwd_data_entry(nparam, params, ndims, shapes, dtypes, stream, extra); }
+extern "C" int md_conv2d_grouped_bwd_data(MD_AOT_ARGS) { return grouped_bwd_data_entry(nparam, params, ndims, shapes, dtypes, stream, extra); }
+extern "C" int64_t md_conv2d_grouped_bwd_weight_workspace_bytes(int64_t P, int64_t groups, int64_t k) {
+    return any_negative({P, groups}) || (k != 1 && k != 3) ? -1 : grouped_wgrad_scratch(P, groups, k).total;
+}
+extern "C" int md_conv2d_grouped_bwd_weight(MD_AOT_ARGS) { return grouped_bwd_weight_entry(nparam, params, ndims, shapes, dtypes, stream, extra); }
 

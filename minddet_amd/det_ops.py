@@ -3161,6 +3161,57 @@ def conv1x1_bwd_data(dy, pc, cin=None, cout=None, act=None, dy_c_off=0, dx_c_off
     return out
 
 
+def _grouped_bwd_check(who, pk, t, name, x_c_off):
+    """the refusals both grouped gradients share: pk a nn_ops.PackedGrouped without a ReLU, t [N,H,W,C] holding every group's slice"""
+    if getattr(pk, "relu", 0):
+        raise ValueError(f"{who}: the gradient of a grouped conv with a ReLU behind it is not built")
+    if x_c_off < 0 or x_c_off + 64 * pk.groups > t.shape[3]:
+        raise ValueError(f"{who}: {pk.groups} groups of 64 channels from channel {x_c_off} do not fit {name} {tuple(t.shape)}")
+
+
+def conv2d_grouped_bwd_data(dy, pk, act=None, x_c_off=0, out=None):
+    """Input gradient of nn_ops.conv2d_grouped(x, pk, y, x_c_off) (md_conv2d_grouped_bwd_data, include/minddet_hip_groupedbwd.h): dy
+    [N,H,W,Cy] f32 = d loss / d y in y's layout (pk.y_offs), the grouped pack pk.w as the forward pass read it; act [N,H,W,Ca] bf16 =
+    the forward pass's x where a ReLU made it (dx is +0.0 where act is not > 0) -> dx [N,H,W,Cdx] f32, group g written at channels
+    [x_c_off + 64 g, + 64) (out: an existing tensor, its other channels are left alone; default a fresh [N,H,W,x_c_off + 64 groups])."""
+    who = "conv2d_grouped_bwd_data"
+    if dy.dtype != torch.float32 or dy.dim() != 4 or (act is not None and (act.dtype != torch.bfloat16 or act.dim() != 4 or
+                                                                          tuple(act.shape[:3]) != tuple(dy.shape[:3]))):
+        raise ValueError(f"{who}: dy is [N,H,W,Cy] float32 and act [N,H,W,Ca] bfloat16 over the same pixels")
+    if out is None:
+        out = torch.empty(tuple(dy.shape[:3]) + (x_c_off + 64 * pk.groups,), dtype=torch.float32, device=dy.device)
+    if out.dtype != torch.float32 or out.dim() != 4 or tuple(out.shape[:3]) != tuple(dy.shape[:3]):
+        raise ValueError(f"{who}: out is [N,H,W,Cdx] float32 over dy's pixels, got {tuple(out.shape)} {out.dtype}")
+    for t, name in ((out, "out"),) + (((act, "act"),) if act is not None else ()):
+        _grouped_bwd_check(who, pk, t, name, x_c_off)
+    _lib.call("md_conv2d_grouped_bwd_data", [dy.contiguous(), pk.w, None if act is None else act.contiguous(), out], extra=pk.attrs(x_c_off))
+    return out
+
+
+def conv2d_grouped_bwd_weight_workspace_bytes(P, groups, k):
+    return _lib.workspace_bytes("md_conv2d_grouped_bwd_weight", P, groups, k)
+
+
+def conv2d_grouped_bwd_weight(x, dy, pk, x_c_off=0, out=None, with_bias=True, workspace=True):
+    """Weight and bias gradient of every group of nn_ops.conv2d_grouped(x, pk, y, x_c_off) in one pair of launches
+    (md_conv2d_grouped_bwd_weight): x [N,H,W,C] bf16, dy [N,H,W,Cy] f32 = d loss / d y -> (dw f32 of pk.w's shape and layout, db f32 of
+    pk.bias's shape or None); group g's rows are what conv_bwd_weight returns for that group alone, bit for bit.  out = (dw, db): written
+    in place (views of a flat gradient buffer).  workspace=False: the library's scratch pool instead of a torch allocation."""
+    who = "conv2d_grouped_bwd_weight"
+    if x.dtype != torch.bfloat16 or x.dim() != 4 or dy.dtype != torch.float32 or dy.dim() != 4 or tuple(x.shape[:3]) != tuple(dy.shape[:3]):
+        raise ValueError(f"{who}: x is [N,H,W,C] bfloat16 and dy [N,H,W,Cy] float32 over the same pixels, got {tuple(x.shape)} {x.dtype}, "
+                         f"{tuple(dy.shape)} {dy.dtype}")
+    _grouped_bwd_check(who, pk, x, "x", x_c_off)
+    if out is None:
+        out = (torch.empty(tuple(pk.w.shape), dtype=torch.float32, device=x.device),
+               torch.empty((pk.w.shape[0],), dtype=torch.float32, device=x.device) if with_bias else None)
+    dw, db = out
+    P = x.shape[0] * x.shape[1] * x.shape[2]
+    ws = _lib.scratch("md_conv2d_grouped_bwd_weight", (P, pk.groups, pk.k), x.device) if workspace else None
+    _lib.call("md_conv2d_grouped_bwd_weight", [x.contiguous(), dy.contiguous(), dw, db] + ([ws] if ws is not None else []), extra=pk.attrs(x_c_off))
+    return dw, db
+
+
 def grad_sumsq_workspace_bytes(n):
     return _lib.workspace_bytes("md_grad_sumsq", n)
 

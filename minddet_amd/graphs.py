@@ -984,11 +984,37 @@ class CenterHead(Module):
         run merged (_derive); branches() lists both."""
         return [self.shared_conv] + [c2 for _, _, _, c2 in self.branches()]
 
+    _trainer = None     # optim.CenterPointHeadTrainer of this head (head_trainer()): derived from the two packs of _derive, so owned here
+
+    def to(self, device):
+        if self._trainer is not None:
+            self._trainer.sync_modules()    # the per-branch ConvModules are the source of truth of a repack: they get the trained masters first
+        return super().to(device)
+
     def _derive(self, device):
         br = self.branches()
         self._first = merged_conv([c1 for _, _, c1, _ in br], device)
         self._second = nn_ops.pack_conv2d_grouped([(c2.weight, c2.bias, None) for _, _, _, c2 in br],
                                                   y_offs=[self.offsets[t][h] for t, h, _, _ in br]).to(device)
+        if self._trainer is not None:
+            self._trainer.bind()            # the trainer's buffers around the new packs; masters, moments and powers kept
+
+    def head_trainer(self, optimizer_cfg=None):
+        """optim.CenterPointHeadTrainer of this head (every SepHead branch, first and last convs; the shared conv frozen):
+        train_step(feat, example, lr, beta1) continues loss(grad=True) through md_conv2d_grouped_bwd_weight, md_conv2d_grouped_bwd_data,
+        md_conv_bwd_weight, md_grad_sumsq and md_adam_step on the device.  optimizer_cfg: None = optim.CENTERPOINT_OPTIMIZER.  One
+        trainer per head: a call without a config returns the existing one, a call with one replaces it (fresh moments).  The head has to
+        be on its device."""
+        from . import optim
+
+        if optimizer_cfg is None and self._trainer is not None:
+            return self._trainer
+        if self._trainer is not None:       # the replaced trainer leaves its masters in the modules and lets go of the packs
+            device = self._first.w.device
+            self._trainer.sync_modules()
+            self._trainer = None
+            self._derive(device)
+        return optim.CenterPointHeadTrainer(self, optimizer_cfg)
 
     def task_offsets(self, grouped=None):
         """per task {head: first channel} in the head tensor __call__ returns (grouped None: the SEPHEAD_GROUPED setting)"""
@@ -1003,18 +1029,26 @@ class CenterHead(Module):
     def __call__(self, x, grouped=None):
         """x [B, H, W, in_channels] bf16 -> (head, shared): the head tensor (layout: task_offsets()) and the shared conv's output
         [B, H, W, 64] (construct's (ret_dicts, x), center_head.py:193-200)."""
+        if grouped if grouped is not None else SEPHEAD_GROUPED:
+            return self.forward_mid(x)[:2]
         sh = self.shared_conv(x)
         mid = nn_ops.conv2d(sh, self._first)                                    # [B, H, W, 64 x branches]
         B, H, W, _ = sh.shape
-        if grouped if grouped is not None else SEPHEAD_GROUPED:
-            head = torch.empty((B, H, W, (self.head_channels + 7) // 8 * 8), dtype=torch.bfloat16, device=x.device)
-            nn_ops.conv2d_grouped(mid, self._second, head)
-        else:
-            br = self.branches()
-            head = torch.empty((B, H, W, 8 * len(br)), dtype=torch.bfloat16, device=x.device)
-            for i, (_, _, _, c2) in enumerate(br):
-                nn_ops.conv2d(mid, c2.packed, out=head, c_off=8 * i, x_c_off=64 * i)
+        br = self.branches()
+        head = torch.empty((B, H, W, 8 * len(br)), dtype=torch.bfloat16, device=x.device)
+        for i, (_, _, _, c2) in enumerate(br):
+            nn_ops.conv2d(mid, c2.packed, out=head, c_off=8 * i, x_c_off=64 * i)
         return head, sh
+
+    def forward_mid(self, x):
+        """the three launches of the fast form -> (head, shared, mid): mid [B, H, W, 64 x branches] bf16 is the merged first convs'
+        output, the tensor the grouped conv reads (a training step differentiates through it)"""
+        sh = self.shared_conv(x)
+        mid = nn_ops.conv2d(sh, self._first)                                    # [B, H, W, 64 x branches]
+        B, H, W, _ = sh.shape
+        head = torch.empty((B, H, W, (self.head_channels + 7) // 8 * 8), dtype=torch.bfloat16, device=x.device)
+        nn_ops.conv2d_grouped(mid, self._second, head)
+        return head, sh, mid
 
     def loss(self, example, head, grad=False):
         """center_head.py:208-271 on the head tensor of __call__ (raw logits in the layout of task_offsets(); the per-branch A/B layout
@@ -1046,6 +1080,7 @@ class PointPillars(Module):
         self.neck = build_neck(dict(neck, seed=seed) if isinstance(neck, dict) and "seed" not in neck else neck)
         self.bbox_head = build_head(dict(bbox_head, seed=seed + 1) if isinstance(bbox_head, dict) and "seed" not in bbox_head else bbox_head)
         self.test_cfg = test_cfg
+        self.train_cfg = dict(train_cfg) if train_cfg else None
         self.max_per_task = int(test_cfg["nms"]["nms_post_max_size"])
         self.cp_post = CP_POST if cp_post is None else bool(cp_post)
         self._post_batched = None
@@ -1080,6 +1115,20 @@ class PointPillars(Module):
         det_ops.cp_loss (grad=True: with d total / d head, the first gradient of a training step)"""
         head, _ = self.bbox_head(self.neck(pseudo_image))
         return self.bbox_head.loss(example, head, grad=grad)
+
+    def head_trainer(self, optimizer_cfg=None):
+        """CenterHead.head_trainer of the model's head; optimizer_cfg: None = train_cfg["optimizer"] (none there:
+        optim.CENTERPOINT_OPTIMIZER)"""
+        if optimizer_cfg is None and self.bbox_head._trainer is None:
+            optimizer_cfg = (self.train_cfg or {}).get("optimizer") or {}
+        return self.bbox_head.head_trainer(optimizer_cfg)
+
+    def train_step(self, pseudo_image, example, lr, beta1=0.9):
+        """One training step of the head on a batch (the neck frozen): pseudo_image [B, H, W, 64] bf16, example = the dict of
+        det_ops.cp_assign_targets -> the dict of loss(grad=True) (the loss BEFORE the update) plus `neck`, `head`, `shared`, `mid` and
+        `dmid` (optim.CenterPointHeadTrainer.train_step).  Nothing is read back."""
+        feat = self.neck(pseudo_image)
+        return dict(self.head_trainer().train_step(feat, example, lr, beta1), neck=feat)
 
     def evaluate_nusc(self, dets, count, poses, gt_records, ego_translations):
         """The nuScenes detection result (detection_cvpr_2019) of forward()'s rows (dets [B, max_det, 11], count [B]) for the B samples
@@ -1306,6 +1355,20 @@ class PillarDetector(Module):
         as one device chain.  -> the dict of loss() plus `example`."""
         ex = self.train_example(points, offsets, gt_boxes, gt_classes, gt_count, generator=generator, draws=draws, sampled=sampled)
         return dict(self.loss(ex["augment"]["points"], ex["augment"]["offsets"], ex, grad=grad), example=ex)
+
+    def head_trainer(self, optimizer_cfg=None):
+        """PointPillars.head_trainer of the inner detector (optimizer_cfg None: this model's train_cfg["optimizer"])"""
+        if optimizer_cfg is None and self.bbox_head._trainer is None:
+            optimizer_cfg = (self.train_cfg or {}).get("optimizer") or {}
+        return self.detector.head_trainer(optimizer_cfg)
+
+    def train_step(self, points, offsets, gt_boxes, gt_classes, gt_count, lr, beta1=0.9, generator=None, draws=None, sampled=None):
+        """train_example, then one step of head_trainer() on the augmented points: raw points + ground truth -> updated head as one
+        device chain (reader, backbone, neck and shared conv frozen).  -> the dict of PointPillars.train_step plus `example`."""
+        ex = self.train_example(points, offsets, gt_boxes, gt_classes, gt_count, generator=generator, draws=draws, sampled=sampled)
+        self.head_trainer()
+        canvas = self._train_canvas(ex["augment"]["points"], ex["augment"]["offsets"])
+        return dict(self.detector.train_step(canvas, ex, lr, beta1), example=ex)
 
 
 # ----------------------------------------------------------------------------- PointPillars, anchor-based (KITTI)

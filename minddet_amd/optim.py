@@ -1,6 +1,6 @@
 """The optimizer side of a training step: the reference's learning-rate schedules on the host (numpy, one array per run) and its Adam
-on the device (det_ops.grad_sumsq + det_ops.adam_step, include/minddet_hip_train.h), plus the trainers of the KITTI head and of
-CenterNet's heads.
+on the device (det_ops.grad_sumsq + det_ops.adam_step, include/minddet_hip_train.h), plus the trainers of the KITTI head, of
+CenterNet's heads and of CenterPoint's head.
 
   OneCycle               centerpoint/det3d_ms/solver/learning_schedules_fastai.py (OneCycle.get_lr: two cosine phases for the rate and
                          for beta1)
@@ -12,6 +12,9 @@ CenterNet's heads.
                          md_grad_sumsq -> md_adam_step on the merged 1x1 heads, the neck frozen
   CenterNetHeadTrainer   graphs.CenterNet.head_trainer(): head1 (3x3 + ReLU) -> head2 (block-diagonal 1x1) -> md_cn_loss_grad ->
                          md_conv_bwd_weight -> md_conv1x1_bwd_data -> md_conv_bwd_weight -> md_adam_step, backbone and neck frozen
+  CenterPointHeadTrainer graphs.CenterHead.head_trainer(): merged first convs (3x3 + ReLU) -> md_conv2d_grouped -> md_cp_loss_grad ->
+                         md_conv2d_grouped_bwd_weight -> md_conv2d_grouped_bwd_data -> md_conv_bwd_weight (chunked) -> md_grad_sumsq ->
+                         md_adam_step over one flat range (the global-norm clip), neck and shared conv frozen
 
 Nothing here reads a device value back."""
 import math
@@ -293,3 +296,101 @@ class CenterNetHeadTrainer:
             c1.bias = b1[col0:col0 + cols].clone()
             c2.weight = w2[row0:row0 + rows, col0:col0 + cols].reshape(rows, cols, 1, 1).clone()
             c2.bias = b2[row0:row0 + rows].clone()
+
+
+CENTERPOINT_OPTIMIZER = dict(type="Adam", beta2=0.999, eps=1e-8, weight_decay=0.01, max_norm=35.0, grad_scale=1.0)
+
+
+def identity_bn(bn):
+    """A frozen eval-mode BatchNorm (gamma, beta, mean, var, eps) re-expressed so that nn_ops._fold_bn leaves the conv in front of it
+    as it is: mean, var and eps stay, gamma = sqrt(var + eps) in the fold's own fp32 expression (its scale is then exactly 1.0) and
+    beta = mean (its shift exactly 0).  What a trainer writes back beside a master that already holds the folded weights."""
+    _, _, mean, var, eps = bn
+    return torch.sqrt(torch.as_tensor(var).to(torch.float32) + eps), mean, mean, var, eps
+
+
+class CenterPointHeadTrainer:
+    """Trains every SepHead branch of graphs.CenterHead (the merged first 3x3 convs + ReLU and the grouped last 3x3 convs) on the device
+    with the neck and the shared conv frozen: shared conv -> merged first conv (`mid`) -> md_conv2d_grouped (`head`) -> md_cp_loss_grad
+    -> md_conv2d_grouped_bwd_weight (mid, g) -> md_conv2d_grouped_bwd_data (g through mid's ReLU: `dmid`) -> md_conv_bwd_weight (shared,
+    dmid) in chunks of at most FIRST_CHUNK output channels, each writing its rows of the flat gradient -> md_grad_sumsq -> md_adam_step.
+    ONE Adam over ONE flat range [w_first | w_second | b_first | b_second], so the reference's global-norm clip (max_norm 35) covers both
+    packs; its shadow is one bf16 buffer the two packs' `w` are views of, and the packs' biases ARE the master's slices, so the forward
+    pass behind a step runs on the new weights with no copy.  The first convs' BatchNorm is frozen: the trained parameters are the folded
+    pack (weight x scale, shift), the statistics never move (the reference trains with batch statistics; not built).  The head owns the
+    trainer (CenterHead._derive): a later to() writes the masters back into the per-branch ConvModules (sync_modules), repacks, and binds
+    the trainer to the new packs with masters, moments and powers kept.
+    optimizer_cfg: train_cfg["optimizer"] (keys of CENTERPOINT_OPTIMIZER; `type` must be "Adam")."""
+    FIRST_CHUNK = 256       # MD_CONV_BWD_MAX_COUT
+
+    def __init__(self, head, optimizer_cfg=None):
+        cfg = dict(CENTERPOINT_OPTIMIZER, **dict(optimizer_cfg or {}))
+        if cfg.pop("type") != "Adam":
+            raise ValueError("CenterPointHeadTrainer: only the reference's Adam is built")
+        unknown = set(cfg) - set(CENTERPOINT_OPTIMIZER)
+        if unknown:
+            raise ValueError(f"CenterPointHeadTrainer: optimizer options that are not built: {sorted(unknown)}")
+        self.head, self.cfg, self.opt = head, cfg, None
+        if getattr(head, "_first", None) is None or not head._first.w.is_cuda:
+            raise ValueError("CenterPointHeadTrainer: move the model to its device first (to(device) packs the head)")
+        head._trainer = self
+        self.bind()
+
+    def bind(self):
+        """(re)build the flat buffers around the head's current packs; the moments, the powers and the fp32 masters survive"""
+        pc1, pk2, old = self.head._first, self.head._second, self.opt
+        dev = pc1.w.device
+        n1, n2 = pc1.w.numel(), pk2.w.numel()
+        shadow = torch.empty((n1 + n2,), dtype=torch.bfloat16, device=dev)
+        sizes = dict(w1=tuple(pc1.w.shape), w2=tuple(pk2.w.shape), b1=tuple(pc1.bias.shape), b2=tuple(pk2.bias.shape))
+        opt = Adam(sizes, dev, shadow=shadow, **self.cfg)
+        if old is None:
+            opt.view("w1").copy_(pc1.w.to(torch.float32))
+            opt.view("w2").copy_(pk2.w.to(torch.float32))
+            opt.view("b1").copy_(pc1.bias)
+            opt.view("b2").copy_(pk2.bias)
+        else:
+            for k in ("param", "m", "v"):
+                getattr(opt, k).copy_(getattr(old, k).to(dev))
+            opt.beta1_power, opt.beta2_power, opt.steps = old.beta1_power, old.beta2_power, old.steps
+        shadow.copy_(opt.param[:n1 + n2].to(torch.bfloat16))
+        pc1.w, pk2.w = shadow[:n1].view(pc1.w.shape), shadow[n1:].view(pk2.w.shape)      # the weights the convs read are the shadow
+        pc1.bias, pk2.bias = opt.view("b1"), opt.view("b2")                              # and their biases the fp32 master
+        self.opt = opt
+
+    def train_step(self, feat, example, lr, beta1=0.9):
+        """One step on a batch: feat [B,H,W,in_channels] bf16 = the neck's output, example = the dict of det_ops.cp_assign_targets ->
+        the dict of CenterHead.loss(grad=True) (the loss BEFORE the update) plus `head`, `shared`, `mid` and `dmid`.  Nothing is read
+        back."""
+        head, opt = self.head, self.opt
+        pc1, pk2 = head._first, head._second
+        head_t, sh, mid = head.forward_mid(feat)
+        out = head.loss(example, head_t, grad=True)
+        g = out["grad"]
+        det_ops.conv2d_grouped_bwd_weight(mid, g, pk2, out=(opt.view("w2", "grad"), opt.view("b2", "grad")))
+        dmid = det_ops.conv2d_grouped_bwd_data(g, pk2, act=mid)
+        gw, gb = opt.view("w1", "grad"), opt.view("b1", "grad")
+        rows = gw.shape[0]
+        for r0 in range(0, pc1.cout, self.FIRST_CHUNK):
+            n = min(self.FIRST_CHUNK, pc1.cout - r0)
+            r1 = rows if r0 + n == pc1.cout else r0 + n       # the last chunk writes the pack's padding rows (+0.0) as well
+            det_ops.conv_bwd_weight(sh, dmid, pc1, dy_c_off=r0, cout=n, out=(gw[r0:r1], gb[r0:r1]))
+        opt.step(lr, beta1)
+        return dict(out, head=head_t, shared=sh, mid=mid, dmid=dmid)
+
+    def sync_modules(self):
+        """the fp32 masters back into head.tasks[t][name] = (c1, c2) (weight [cout,64,3,3], bias [cout]), where weights.py and a repack
+        read them; c1's BatchNorm becomes identity_bn of its frozen statistics, so nn_ops._fold_bn returns the master bit for bit.  A
+        host copy: for export, not for the step."""
+        pc1, pk2 = self.head._first, self.head._second
+        w1, b1 = self.opt.view("w1").detach().cpu(), self.opt.view("b1").detach().cpu()
+        w2, b2 = self.opt.view("w2").detach().cpu(), self.opt.view("b2").detach().cpu()
+        w1 = w1[:, pack_columns(pc1).reshape(-1)].reshape(w1.shape[0], pc1.kh, pc1.kw, pc1.cin).permute(0, 3, 1, 2)   # [rows, cin, kh, kw]
+        k = pk2.k
+        for i, (_, _, c1, c2) in enumerate(self.head.branches()):
+            c1.weight = w1[64 * i:64 * i + 64, :c1.cin].clone().contiguous()
+            c1.bias = b1[64 * i:64 * i + 64].clone()
+            c1.bn = identity_bn(c1.bn)
+            r0, c = pk2.w_rows[i], pk2.couts[i]
+            c2.weight = w2[r0:r0 + c].reshape(c, k, k, 64).permute(0, 3, 1, 2).clone().contiguous()
+            c2.bias = b2[r0:r0 + c].clone()

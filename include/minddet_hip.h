@@ -438,7 +438,11 @@ int md_mask_select(MD_AOT_ARGS);
 /* Mask R-CNN: paste each detection's S x S mask into the image (the standard last step of the mask branch, BASELINE configs[4]):
  * bilinear resampling of the mask probabilities onto the pixel centres of the detection's box (grid_sample align_corners=False, zero
  * padding: mmdet _do_paste_mask / torchvision paste_masks_in_image), then mask >= threshold.  Absent from the reference (README bullet):
- * parity unpinned; oracle/np_ops.py::paste_masks restates the kernel's fp32 operation sequence, the comparison is bit-exact.
+ * parity unpinned; oracle/np_ops.py::paste_masks restates the kernel's fp32 operation sequence, the comparison is bit-exact; the float64
+ * statement of this definition, with the band fp32 may differ in, is tests/paste_contract.py).
+ * Outside the mask's support (sample position ix <= -1 or ix >= S, same for y) a pixel is 0 WHATEVER the threshold: this departs from
+ * the literal grid_sample sentence only for threshold <= 0, where zero padding would turn the whole image on.  A NaN threshold, a NaN
+ * interpolated value or a NaN / infinite sample position gives 0.
  * in masks[R,S,S] f32, dets[R,6] f32 (x1,y1,x2,y2,score,label; slots with score 0 or an empty box give an all-zero mask) ;
  * out bits != 0: words[R, img_h, ceil(img_w / 32)] i32 (bit j of word k of a row = pixel 32 k + j), else mask[R, img_h, img_w] u8 (0 / 1).
  * One HBM-write-bound launch: img_h * img_w / 8 bytes per detection (bit form). */

@@ -19,9 +19,10 @@
  *     every later call on that stream (no driver call in the steady state; md_scratch_release
  *     frees it).  How many bytes an op takes has ONE owner: the host function
  *     int64_t md_<op>_workspace_bytes(int64_t extent, ...) declared under the op.  It makes no
- *     device or runtime call, returns -1 for a negative extent, and is the number the op itself
- *     holds a caller's workspace to (a smaller one -> 4).  A caller sizes its buffer by asking it;
- *     the formulas in the comments are upper bounds for readers who cannot.
+ *     device or runtime call, returns -1 for a negative extent and for a byte count that does not
+ *     fit int64_t, and is the number the op itself holds a caller's workspace to (a smaller
+ *     one -> 4).  A caller sizes its buffer by asking it; the formulas in the comments are upper
+ *     bounds for readers who cannot.
  *   - every pointer in params[] is DEVICE memory owned by the caller; outputs are fixed
  *     shape and padded (keep[N] has `num` valid leading entries, the rest 0 --
  *     iou-bev-nms-org.cpp:247-249,274-281).
@@ -42,7 +43,11 @@
  *       ndims == NULL, shapes == NULL, shapes[i] == NULL, a rank or extent other than the op documents, a dtypes[i] other than
  *       documented; then the op's own attribute checks;
  *       then -> 4, the size limits the op documents; a call with defects of both kinds returns 2 or 4, 2 where the defect is one
- *       of the descriptor checks above.
+ *       of the descriptor checks above.  Two size limits hold for every op: no extent of an operand other than the workspace may
+ *       exceed 2^31 - 1 (the kernels index with int), and an extent product that does not fit int64_t -- an operand's element
+ *       count, or any product an op tests -- counts as over every size limit: 4, or 2 where a descriptor defect is also present.
+ *       A negative extent is a descriptor defect (2).  The size tests are made in checked arithmetic (md::mul in csrc/aot.h):
+ *       no extent a caller can pass makes them wrap.
  *     dtypes may be NULL and so may any dtypes[i]: an undescribed dtype passes.  An operand documented "or NULL" / "may be NULL"
  *     is optional: with params[i] == NULL nothing else about it is looked at.  The five reference-ABI ops below also accept
  *     shapes[i] == NULL for thresh and for their outputs (shapes a caller does not describe are not checked).  With work to

@@ -18,6 +18,48 @@
 
 namespace md {
 
+// The one checked product of the size tests: the product of the factors, INT64_MAX when it does not fit int64_t -- a value that fails
+// every limit test (include/minddet_hip.h "Conventions": an extent product that does not fit counts as over every size limit).  The
+// entry points test products of caller extents through this, never through a raw `*`, which would be undefined where it wraps.
+static inline int64_t mul(std::initializer_list<int64_t> factors) {
+    int64_t n = 1;
+    for (int64_t f : factors)
+        if (__builtin_mul_overflow(n, f, &n)) return INT64_MAX;
+    return n;
+}
+// a + b for non-negative terms, INT64_MAX when it does not fit (and INT64_MAX stays INT64_MAX)
+static inline int64_t add(int64_t a, int64_t b) {
+    int64_t n;
+    return __builtin_add_overflow(a, b, &n) ? INT64_MAX : n;
+}
+// Sz: a non-negative count for the scratch layouts (below: "Scratch sizes have one owner").  It is 128 bits wide and sticks at INF
+// (2^126) through every operator, so a layout function written in plain arithmetic on Sz extents cannot wrap, and an element count
+// above int64_t that a later division brings back (4 ceil(B C H W / chunk)) still gives the exact byte count.  The conversions out are
+// explicit; the one to int64_t answers INT64_MAX for a count that does not fit -- the value that fails every limit test, and that
+// ws_answer() below turns into the -1 of md_<op>_workspace_bytes.  A layout function computes in Sz locals and converts each part once,
+// where it fills its struct.
+struct Sz {
+    __int128 v;
+    static constexpr __int128 INF = (__int128)1 << 126;
+    Sz(int64_t x = 0) : v(x < 0 ? INF : (__int128)x) { }
+    static Sz wide(__int128 x) { Sz s; s.v = x < 0 || x >= INF ? INF : x; return s; }
+    bool fits() const { return v <= (__int128)INT64_MAX; }
+    explicit operator int64_t() const { return fits() ? (int64_t)v : INT64_MAX; }
+    explicit operator bool() const { return v != 0; }
+    friend Sz operator*(Sz a, Sz b) {
+        __int128 r;
+        return a.v == INF || b.v == INF || __builtin_mul_overflow(a.v, b.v, &r) ? wide(INF) : wide(r);
+    }
+    friend Sz operator+(Sz a, Sz b) { return wide(a.v + b.v); }                                  // (both <= 2^126: no wrap)
+    friend Sz operator-(Sz a, Sz b) { return a.v == INF || b.v == INF ? wide(INF) : wide(a.v - b.v); }
+    friend Sz operator/(Sz a, Sz b) { return a.v == INF || b.v == INF || b.v == 0 ? wide(INF) : wide(a.v / b.v); }
+    friend bool operator<(Sz a, Sz b) { return a.v < b.v; }
+    friend bool operator>(Sz a, Sz b) { return a.v > b.v; }
+    friend bool operator<=(Sz a, Sz b) { return a.v <= b.v; }
+    friend bool operator>=(Sz a, Sz b) { return a.v >= b.v; }
+    friend bool operator==(Sz a, Sz b) { return a.v == b.v; }
+};
+
 // Args: the one argument-check layer of every AOT entry point (the rule is stated once, in include/minddet_hip.h "Conventions").
 // A view over (nparam, params, ndims, shapes, dtypes) that is built, filled with the op's operands and asked for rc() BEFORE the
 // entry point makes any device or runtime call.  The first failure latches its code; every accessor is safe whatever the caller passed:
@@ -28,13 +70,16 @@ struct Args {
     int nparam; void **params; int *ndims; int64_t **shapes; const char **dtypes;
     int err = MD_OK;
     unsigned ok = 0;      // bit i: operand i is described (ndims[i], shapes[i]) and was accepted
+    bool oversize = false;   // an accepted operand other than a workspace has an extent above INT32_MAX (the kernels index with int)
+                             // or an element count that does not fit int64_t
 
     // nparam in [lo, hi] (hi - lo trailing operands, e.g. the workspace, may be left out) and a params array
     Args(int np, void **p, int *nd, int64_t **sh, const char **dt, int lo, int hi) : nparam(np), params(p), ndims(nd), shapes(sh), dtypes(dt) {
         if (np < lo || np > hi) err = MD_ERR_NPARAM;
         else if (!p) err = MD_ERR_ARG;
     }
-    int rc() const { return err; }
+    // the descriptor checks come first (1, 2); an extent no op can take is the first of the size limits (4)
+    int rc() const { return err ? err : oversize ? MD_ERR_SIZE : MD_OK; }
     bool require(bool cond, int code = MD_ERR_ARG) {
         if (!cond && !err) err = code;
         return cond;
@@ -43,11 +88,17 @@ struct Args {
     template <typename T> const T *attrs(const void *extra) { require(extra != nullptr); return (const T *)extra; }
     // required operand i: described, of rank in [rank, rank_hi] (ANY = not looked at), of dtype `dt` where the caller names one
     // (dtypes == NULL or dtypes[i] == NULL passes, dt == nullptr = not looked at)
-    bool tensor(int i, const char *dt, int rank = ANY, int rank_hi = ANY) {
+    // No extent may be negative (2).  capped: no extent may exceed INT32_MAX either (rc() then answers 4 once the descriptors pass).
+    bool tensor(int i, const char *dt, int rank = ANY, int rank_hi = ANY, bool capped = true) {
         if (err) return false;
         if (i < 0 || i >= nparam || i >= 32 || !ndims || !shapes || !shapes[i] || ndims[i] < 0) return require(false);
         if (rank != ANY && (ndims[i] < rank || ndims[i] > (rank_hi == ANY ? rank : rank_hi))) return require(false);
         if (dt && dtypes && dtypes[i] && strcmp(dtypes[i], dt) != 0) return require(false);
+        for (int k = 0; k < ndims[i]; ++k) {
+            if (shapes[i][k] < 0) return require(false);
+            if (capped && shapes[i][k] > INT32_MAX) oversize = true;
+        }
+        if (capped && prod(i) == INT64_MAX) oversize = true;    // an element count that does not fit int64_t
         ok |= 1u << i;
         return true;
     }
@@ -59,6 +110,8 @@ struct Args {
     }
     // operand whose pointer may be NULL (or that lies past nparam): then nothing else is looked at
     bool optional(int i, const char *dt, int rank = ANY, int rank_hi = ANY) { return !given(i) || tensor(i, dt, rank, rank_hi); }
+    // the optional trailing workspace: bytes of any rank, and no cap on an extent (a workspace larger than the op takes is legal)
+    bool scratch(int i) { return !given(i) || tensor(i, U8, ANY, ANY, false); }
     bool given(int i) const { return !err && i >= 0 && i < nparam && params[i] != nullptr; }
     int rank(int i) const { return i >= 0 && i < 32 && (ok >> i & 1) ? ndims[i] : -1; }
     // extent k of operand i; k < 0 counts from the last
@@ -70,9 +123,11 @@ struct Args {
     int64_t numel(int i) const { return rank(i) < 0 ? -1 : prod(i); }
     // bytes of the caller's workspace operand, -1 when it is absent (the scratch pool then serves) or not described
     int64_t workspace(int i) const { return i < nparam && params[i] && ndims && shapes && shapes[i] ? prod(i) : -1; }
+    // element count, INT64_MAX when it does not fit int64_t (as md::mul): never wrapped, so never small by accident
     int64_t prod(int i) const {
         int64_t n = 1;
-        for (int k = 0; k < ndims[i]; ++k) n *= shapes[i][k];
+        for (int k = 0; k < ndims[i]; ++k)
+            if (__builtin_mul_overflow(n, shapes[i][k], &n)) return INT64_MAX;
         return n;
     }
     // operands i, j agree in rank and every extent
@@ -92,6 +147,11 @@ struct Args {
 #define MD_ARGS nparam, params, ndims, shapes, dtypes
 
 static inline bool fits_i32(long long x) { return x <= 0x7fffffffLL; }
+// byte ranges [a, a + an) and [b, b + bn) share a byte (an, bn >= 0, INT64_MAX from md::mul included: unsigned, so nothing wraps into UB)
+static inline bool ranges_overlap(const void *a, int64_t an, const void *b, int64_t bn) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb + (uintptr_t)bn && pb < pa + (uintptr_t)an;
+}
 // an output that shares its address with an input or with another output (operands [0, n_in) are inputs, [n_in, n_all) outputs)
 static inline bool aliased(void **params, int n_in, int n_all) {
     for (int o = n_in; o < n_all; ++o) {
@@ -205,10 +265,13 @@ static inline int acquire_aligned(Scratch &ws, size_t bytes, const Args &a, int 
 }
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+static inline Sz align_up(Sz x, int64_t a) { return (x + (a - 1)) / a * a; }
 
 // Scratch sizes have one owner (include/minddet_hip.h "Conventions"): per op one host function of the extents fills the byte offsets of
 // the workspace's parts and their total; the exported md_<op>_workspace_bytes returns that total (-1 for a negative extent, below) and
 // the entry point acquires and carves with the same values.
+// what md_<op>_workspace_bytes answers for a checked total: -1 for a byte count that does not fit int64_t
+static inline int64_t ws_answer(int64_t total) { return total == INT64_MAX || total < 0 ? -1 : total; }
 static inline bool any_negative(std::initializer_list<int64_t> extents) {
     for (int64_t v : extents)
         if (v < 0) return true;

@@ -530,10 +530,10 @@ extern "C" int md_bottleneck(MD_AOT_ARGS) {
         g.tensor(7, BF16, 2); g.tensor(8, F32);
         g.require(!g.given(6) && g.given(8) && Cin == 64 && g.d(7, 0) == 256 && g.d(7, 1) == 64 && g.numel(8) >= 256);
     } else if (g.given(6)) {
-        g.require(g.numel(6) == N * H * W * 256);
+        g.require(g.numel(6) == mul({N, H, W, 256}));
     } else g.require(Cin == 256);
     if (int rc = g.rc()) return rc;
-    if (N * H * W == 0) return MD_OK;
+    if (mul({N, H, W}) == 0) return MD_OK;
     if (!g.have({0, 1, 2, 3, 4, 5, 9})) return MD_ERR_ARG;
     if (H > 32000 || W > 32000) return MD_ERR_SIZE;
     const long long x_img = H * W * Cin * 2;

@@ -513,22 +513,25 @@ extern "C" int md_c3_pair(MD_AOT_ARGS) {
     g.tensor(0, BF16, 4); g.tensor(1, BF16, 2); g.tensor(2, F32); g.tensor(3, BF16, 2); g.tensor(4, BF16, 4);
     const int64_t N = g.d(0, 0), H = g.d(0, 1), W = g.d(0, 2), XC = g.d(0, 3), YC = g.d(4, 3);
     const int64_t C = g.d(1, 0);
-    const int64_t k1 = (C + 63) / 64 * 64, k2 = (9 * C + 63) / 64 * 64;   // md_conv2d pads the packed K to a multiple of 64
-    g.require((C == 32 || C == 64 || C == 128) && g.d(1, 1) == k1 && g.d(3, 0) == C && g.d(3, 1) == k2 && g.numel(2) == 2 * C);
+    const bool c_ok = C == 32 || C == 64 || C == 128;
+    // md_conv2d pads the packed K to a multiple of 64
+    const int64_t k1 = c_ok ? (C + 63) / 64 * 64 : -1, k2 = c_ok ? (9 * C + 63) / 64 * 64 : -1;
+    g.require(c_ok && g.d(1, 1) == k1 && g.d(3, 0) == C && g.d(3, 1) == k2 && g.numel(2) == 2 * C);
     g.require(g.d(4, 0) == N && g.d(4, 1) == H && g.d(4, 2) == W);
     if (int rc = g.rc()) return rc;
     const int64_t span = at->pass_through ? 2 * C : C;
     if (at->x_c_off < 0 || at->y_c_off < 0 || at->x_c_off % 8 || at->y_c_off % 8 || XC % 8 || YC % 8 || at->x_c_off + span > XC || at->y_c_off + span > YC)
         return MD_ERR_ARG;
-    if (N * H * W == 0) return MD_OK;
+    if (mul({N, H, W}) == 0) return MD_OK;
     if (!g.have({0, 1, 2, 3, 4})) return MD_ERR_ARG;
     {   // x and y must not overlap (see above)
         const char *xb = (const char *)params[0], *yb = (const char *)params[4];
-        const long long xn = N * H * W * XC * 2, yn = N * H * W * YC * 2;
-        if (xb < yb + yn && yb < xb + xn) return MD_ERR_ARG;
+        const long long xn = mul({N, H, W, XC, 2}), yn = mul({N, H, W, YC, 2});
+        if (ranges_overlap(xb, xn, yb, yn)) return MD_ERR_ARG;
     }
     if (H > 32000 || W > 32000) return MD_ERR_SIZE;
-    if (N * H * W * XC * 2 >= 0x7fff0000LL || N * H * W * YC * 2 >= 0x7fff0000LL) return MD_ERR_SIZE;   // 32-bit buffer offsets into x and y
+    // 32-bit buffer offsets into x and y
+    if (mul({N, H, W, XC, 2}) >= 0x7fff0000LL || mul({N, H, W, YC, 2}) >= 0x7fff0000LL) return MD_ERR_SIZE;
     C3PairArgs a;
     a.x = (const uint16_t *)params[0]; a.w1 = (const uint16_t *)params[1]; a.b12 = (const float *)params[2];
     a.w2 = (const uint16_t *)params[3]; a.y = (uint16_t *)params[4];
@@ -539,7 +542,7 @@ extern "C" int md_c3_pair(MD_AOT_ARGS) {
     if (!fits_i32(n_tiles * 8)) return MD_ERR_SIZE;
     a.n_tiles = (int)n_tiles;
     a.pt_per_xcd = (a.n_tiles + 7) / 8;
-    a.x_bytes = (unsigned)(N * H * W * XC * 2);
+    a.x_bytes = (unsigned)(N * H * W * XC * 2);     // (both below 2 GiB - 64 KiB: the size test above)
     a.y_bytes = (unsigned)(N * H * W * YC * 2);
     a.w1_ld = (int)k1; a.w2_ld = (int)k2;
     a.dbg = nullptr;

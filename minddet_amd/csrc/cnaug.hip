@@ -199,10 +199,10 @@ extern "C" int md_cn_aug_transform(MD_AOT_ARGS) {
 }
 
 // partial sums per sample of the grey pass of md_cn_aug_image: one per CNA_CHUNK output pixels
-static int64_t cn_grey_chunks(int64_t out_h, int64_t out_w) { return (out_h * out_w + CNA_CHUNK - 1) / CNA_CHUNK; }
+static Sz cn_grey_chunks(Sz out_h, Sz out_w) { return (out_h * out_w + (CNA_CHUNK - 1)) / CNA_CHUNK; }
 // scratch of md_cn_aug_image: part[B][chunks] f64 at 0, then mean[B] f64
 extern "C" int64_t md_cn_aug_image_workspace_bytes(int64_t B, int64_t out_h, int64_t out_w) {
-    return any_negative({B, out_h, out_w}) ? -1 : B * (cn_grey_chunks(out_h, out_w) + 1) * 8;
+    return any_negative({B, out_h, out_w}) ? -1 : ws_answer((int64_t)(Sz(B) * (cn_grey_chunks(out_h, out_w) + 1) * 8));
 }
 
 extern "C" int md_cn_aug_image(MD_AOT_ARGS) {
@@ -211,7 +211,7 @@ extern "C" int md_cn_aug_image(MD_AOT_ARGS) {
     Args g(MD_ARGS, 6, 7);
     const md_cn_aug_image_attrs *at = g.attrs<md_cn_aug_image_attrs>(extra);
     g.tensor(0, U8, 4); g.tensor(1, I32, 2); g.tensor(2, F32, 2); g.tensor(3, F32); g.optional(4, CNA_F64, 2); g.tensor(5, BF16, 4);
-    g.optional(6, U8);
+    g.scratch(6);
     if (int rc = g.rc()) return rc;
     const bool colour = g.given(4);
     const int64_t B = g.d(0, 0), Hs = g.d(0, 1), Ws = g.d(0, 2), Hp = g.d(5, 1), Wp = g.d(5, 2), C = g.d(5, 3);
@@ -232,7 +232,7 @@ extern "C" int md_cn_aug_image(MD_AOT_ARGS) {
     hipStream_t s = (hipStream_t)stream;
     ImageArgs a;
     a.Hs = (int)Hs; a.Ws = (int)Ws; a.Ho = at->out_h; a.Wo = at->out_w; a.Hp = (int)Hp; a.Wp = (int)Wp; a.C = (int)C; a.pad_lo = at->pad_lo;
-    a.nblk = (int)cn_grey_chunks(a.Ho, a.Wo);
+    a.nblk = (int)(int64_t)cn_grey_chunks(a.Ho, a.Wo);
     a.img = (const uint8_t *)params[0]; a.sizes = (const int *)params[1]; a.mat = (const float *)params[2]; a.norm = (const float *)params[3];
     a.colour = colour ? (const double *)params[4] : nullptr; a.out = (uint16_t *)params[5];
     a.part = nullptr; a.mean = nullptr;

@@ -215,14 +215,10 @@ __global__ __launch_bounds__(256) void cn_loss_finish_kernel(const uint16_t *__r
 // scratch of md_cn_loss and md_cn_loss_grad: rec[B][CNL_REC] f64 at 0, part[B sps][2] f64, counts[chunks] i32; sps = the strips of
 // CNL_STRIP cells per sample, chunks = the chunks of CNL_CHUNK heat-map elements of the batch
 struct CnlScratch { int64_t sps, chunks, part, counts, total; };
-static CnlScratch cn_loss_scratch(int64_t B, int64_t C, int64_t H, int64_t W) {
-    CnlScratch w;
-    w.sps = (H * W + CNL_STRIP - 1) / CNL_STRIP;
-    w.chunks = (B * C * H * W + CNL_CHUNK - 1) / CNL_CHUNK;
-    w.part = 8 * CNL_REC * B;
-    w.counts = w.part + 8 * 2 * B * w.sps;
-    w.total = w.counts + 4 * w.chunks;
-    return w;
+static CnlScratch cn_loss_scratch(Sz B, Sz C, Sz H, Sz W) {
+    const Sz sps = (H * W + (CNL_STRIP - 1)) / CNL_STRIP, chunks = (B * C * H * W + (CNL_CHUNK - 1)) / CNL_CHUNK;
+    const Sz part = 8 * CNL_REC * B, counts = part + 8 * 2 * B * sps, total = counts + 4 * chunks;
+    return {(int64_t)sps, (int64_t)chunks, (int64_t)part, (int64_t)counts, (int64_t)total};
 }
 
 static int cn_loss_entry(MD_AOT_ARGS, bool with_grad) {
@@ -234,7 +230,7 @@ static int cn_loss_entry(MD_AOT_ARGS, bool with_grad) {
     a.tensor(0, BF16, 4); a.tensor(1, F32, 4); a.tensor(2, I32, 2); a.tensor(3, U8, 2); a.tensor(4, F32, 3); a.tensor(5, F32, 3);
     a.tensor(6, F32, 1); a.tensor(7, F32, 1); a.tensor(8, F32, 1);
     if (with_grad) a.tensor(9, F32, 4);
-    a.optional(WS, U8);
+    a.scratch(WS);
     if (int rc = a.rc()) return rc;
     const int64_t B = a.d(0, 0), H = a.d(0, 1), W = a.d(0, 2), Cp = a.d(0, 3), C = a.d(1, 1), M = a.d(2, 1);
     a.require(B >= 1 && H >= 1 && W >= 1 && Cp >= 1 && C >= 1 && M >= 0);
@@ -250,7 +246,9 @@ static int cn_loss_entry(MD_AOT_ARGS, bool with_grad) {
     a.require(isfinite(at->hm_weight) && isfinite(at->wh_weight) && isfinite(at->off_weight));
     if (int rc = a.rc()) return rc;
     const int64_t lim = (int64_t)1 << 30;
-    if (M > CNL_MAX_M || Cp > MD_CN_LOSS_MAX_CHANNELS || B > 65535 || a.numel(0) >= lim || a.numel(1) >= lim || B * M * 2 >= lim) return MD_ERR_SIZE;
+    if (M > CNL_MAX_M || Cp > MD_CN_LOSS_MAX_CHANNELS || B > 65535 || a.numel(0) >= lim || a.numel(1) >= lim ||
+        mul({B, M, 2}) >= lim)
+        return MD_ERR_SIZE;
     if (!a.have({0, 1, 2, 3, 4, 5, 6, 7, 8}) || (with_grad && !a.have({9}))) return MD_ERR_ARG;
     const CnlScratch w = cn_loss_scratch(B, C, H, W);
     const int64_t HW = H * W, sps = w.sps, n_strips = B * sps, hm_elems = B * C * HW, n_chunks = w.chunks;
@@ -291,7 +289,7 @@ static int cn_loss_entry(MD_AOT_ARGS, bool with_grad) {
 using namespace md;
 
 extern "C" int64_t md_cn_loss_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W) {
-    return any_negative({B, C, H, W}) ? -1 : cn_loss_scratch(B, C, H, W).total;
+    return any_negative({B, C, H, W}) ? -1 : ws_answer(cn_loss_scratch(B, C, H, W).total);
 }
 extern "C" int md_cn_loss(MD_AOT_ARGS) { return cn_loss_entry(nparam, params, ndims, shapes, dtypes, stream, extra, false); }
 extern "C" int md_cn_loss_grad(MD_AOT_ARGS) { return cn_loss_entry(nparam, params, ndims, shapes, dtypes, stream, extra, true); }

@@ -99,7 +99,7 @@ using namespace md;
 
 // scratch of md_cn_assign_targets: draw[B][M] int4
 extern "C" int64_t md_cn_assign_targets_workspace_bytes(int64_t B, int64_t M) {
-    return any_negative({B, M}) ? -1 : B * M * 16;
+    return any_negative({B, M}) ? -1 : ws_answer((int64_t)(Sz(B) * M * 16));
 }
 
 extern "C" int md_cn_assign_targets(MD_AOT_ARGS) {
@@ -108,7 +108,7 @@ extern "C" int md_cn_assign_targets(MD_AOT_ARGS) {
     Args a(MD_ARGS, 7, 8);
     const md_cn_targets_attrs *at = a.attrs<md_cn_targets_attrs>(extra);
     a.tensor(0, F32, 3); a.tensor(1, I32, 2); a.tensor(2, F32, 4); a.tensor(3, I32, 2); a.tensor(4, U8, 2); a.tensor(5, F32, 3);
-    a.tensor(6, F32, 3); a.optional(7, U8);
+    a.tensor(6, F32, 3); a.scratch(7);
     if (int rc = a.rc()) return rc;
     const int64_t B = a.d(0, 0), G = a.d(0, 1), C = a.d(2, 1), H = a.d(2, 2), W = a.d(2, 3), M = a.d(3, 1);
     a.require(B >= 0 && G >= 0 && M >= 0 && C >= 1 && H >= 1 && W >= 1 && a.d(0, 2) == 4 && a.d(1, 0) == B && a.d(1, 1) == G);
@@ -118,7 +118,7 @@ extern "C" int md_cn_assign_targets(MD_AOT_ARGS) {
     a.require(at->min_overlap > 0.f && at->min_overlap < 1.f);   // (false for a NaN)
     if (int rc = a.rc()) return rc;
     const int64_t lim = (int64_t)1 << 30;
-    if (M > CNT_MAX_M || B * G * 4 >= lim || a.numel(2) >= lim || B * M * 2 >= lim || B > 65535 || C > 65535) return MD_ERR_SIZE;
+    if (M > CNT_MAX_M || mul({B, G, 4}) >= lim || a.numel(2) >= lim || mul({B, M, 2}) >= lim || B > 65535 || C > 65535) return MD_ERR_SIZE;
     if (B == 0) return MD_OK;
     if (!a.have({0, 1, 2, 3, 4, 5, 6})) return MD_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;

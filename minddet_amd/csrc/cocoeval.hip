@@ -302,7 +302,7 @@ __global__ __launch_bounds__(256) void ce_accum_kernel(AccumArgs a) {
 static bool ce_too_large(int64_t C, int64_t Kc, int64_t Gt, int64_t Dt, int64_t T, int64_t A, int64_t R, int64_t M) {
     return C >= MD_COCOEVAL_MAX_CELLS || Kc > MD_COCOEVAL_MAX_CATS || Gt > MD_COCOEVAL_MAX_ROWS || Dt > MD_COCOEVAL_MAX_ROWS ||
            T > MD_COCOEVAL_MAX_THRS || A > MD_COCOEVAL_MAX_AREAS || R > MD_COCOEVAL_MAX_RECS || M > MD_COCOEVAL_MAX_MAXDETS ||
-           A * T * Dt >= ((int64_t)1 << 31);
+           mul({A, T, Dt}) >= ((int64_t)1 << 31);
 }
 
 }  // namespace md

@@ -1923,9 +1923,9 @@ static int validate_conv2d(int nparam, void **params, int *ndims, int64_t **shap
     // The LDS-DMA kernels address the activation tensor with 32-bit byte offsets.  A batch whose input (or output /
     // residual, which the kernels address with 64-bit math but the same image split applies to) exceeds 2 GiB is run
     // as consecutive image chunks on the same stream: every tensor of the call is sliced along N.
-    const long long n_img = g.d(0, 0), x_img = g.d(0, 1) * g.d(0, 2) * g.d(0, 3) * 2;
+    const long long n_img = g.d(0, 0), x_img = mul({g.d(0, 1), g.d(0, 2), g.d(0, 3), 2});
     c.per = n_img;
-    if (n_img > 1 && x_img > 0 && x_img < c.tn.chunk_limit && n_img * x_img >= c.tn.chunk_limit && g.d(4, 0) == n_img &&
+    if (n_img > 1 && x_img > 0 && x_img < c.tn.chunk_limit && mul({n_img, x_img}) >= c.tn.chunk_limit && g.d(4, 0) == n_img &&
         (!params[3] || g.d(3, 0) == n_img)) {
         const long long per_max = c.tn.chunk_limit / x_img;          // images a chunk may hold (>= 1)
         const long long n_chunks = (n_img + per_max - 1) / per_max;
@@ -1976,7 +1976,9 @@ static int validate_conv2d(int nparam, void **params, int *ndims, int64_t **shap
         if ((a.Ho - 1) * a.os + a.oy >= a.Hf || (a.Wo - 1) * a.os + a.ox >= a.Wf || a.c_off + a.Cout > a.Ctot) return MD_ERR_ARG;
     }
     if (a.Cin % 8 || a.Cout % 8 || a.Ctot % 8 || g.d(4, 0) != a.N) return MD_ERR_ARG;
-    a.Kreal = a.kh * a.kw * a.Cin;
+    const int64_t kreal = mul({a.kh, a.kw, a.Cin});
+    if (!fits_i32(kreal)) return MD_ERR_ARG;    // (above Kpad, an int: the test below)
+    a.Kreal = (int)kreal;
     a.Kpad = (int)g.d(1, 1);
     const int ctile = md_conv2d_cout_tile(a.Cout);
     const int cout_pad = (a.Cout + ctile - 1) / ctile * ctile;
@@ -1997,7 +1999,7 @@ static int validate_conv2d(int nparam, void **params, int *ndims, int64_t **shap
     if (c.empty) return MD_OK;
     if (!g.have({0, 4})) return MD_ERR_ARG;
     // (per chunk: the first chunk is the largest)
-    if (!fits_i32(c.per * a.Ho * a.Wo) || !fits_i32(c.per * a.H * a.W * 2) || a.H > 32000 || a.W > 32000) return MD_ERR_SIZE;
+    if (!fits_i32(mul({c.per, a.Ho, a.Wo})) || !fits_i32(mul({c.per, a.H, a.W, 2})) || a.H > 32000 || a.W > 32000) return MD_ERR_SIZE;
     a.cpt = a.Cin / 8;
     a.pointwise = a.kh == 1 && a.kw == 1 && a.stride == 1 && a.pad_top == 0 && a.pad_left == 0 && a.H == a.Ho && a.W == a.Wo;
     c.x_img = (long long)a.H * a.W * a.Xs; c.y_img = (long long)a.Hf * a.Wf * a.Ctot; c.w_bytes = (long long)cout_pad * a.Kpad * 2;
@@ -2021,9 +2023,9 @@ static int validate_dual(int nparam, void **params, int *ndims, int64_t **shapes
         return MD_ERR_ARG;
     const int64_t cout_pad = (Cout + 127) / 128 * 128;
     if (g.d(2, 0) != cout_pad || g.d(2, 1) != Ca + Cb || g.numel(3) != cout_pad) return MD_ERR_ARG;
-    if (params[4] && g.numel(4) != N * Ho * Wo * Cout) return MD_ERR_ARG;
+    if (params[4] && g.numel(4) != mul({N, Ho, Wo, Cout})) return MD_ERR_ARG;
     c = ConvCall{};
-    c.empty = N * Ho * Wo == 0;
+    c.empty = mul({N, Ho, Wo}) == 0;
     if (c.empty) return MD_OK;
     if (!g.have({0, 1, 5})) return MD_ERR_ARG;
     if (Hb > 32000 || Wb > 32000) return MD_ERR_SIZE;
@@ -2060,7 +2062,7 @@ static int validate_head(int nparam, void **params, int *ndims, int64_t **shapes
     if (int rc = g.rc()) return rc;
     if (at->adv || at->relu != 1 || at->res_upsample) return MD_ERR_ARG;
     const int64_t N = g.d(5, 0), Ho = g.d(5, 1), Wo = g.d(5, 2);
-    c[0] = ConvCall{}; c[0].empty = N * Ho * Wo == 0;
+    c[0] = ConvCall{}; c[0].empty = mul({N, Ho, Wo}) == 0;
     if (c[0].empty) return MD_OK;
     if (!g.have({0, 5})) return MD_ERR_ARG;
     int64_t sy[4] = {N, Ho, Wo, 256}, snull[1] = {0}, sw2[2] = {g.d(3, 0), 256}, sb2[1] = {g.d(3, 0)};

@@ -310,16 +310,12 @@ __global__ __launch_bounds__(256) void grouped_wgrad_sum_kernel(const float *__r
 
 // scratch of md_conv1x1_bwd_weight: dw partials [n_slabs][R][cin] f32 at 0, then db partials [n_slabs][R] f32
 struct WgScratch { int64_t S, n_slabs, R, db, total; };
-static WgScratch wgrad_scratch(int64_t P, int64_t cin, int64_t cout) {
-    WgScratch w;
-    const int64_t per = (P + MD_CONV1X1_BWD_MAX_SLABS - 1) / MD_CONV1X1_BWD_MAX_SLABS;
-    w.S = (per + 15) / 16 * 16;
-    if (w.S < MD_CONV1X1_BWD_SLAB_MIN) w.S = MD_CONV1X1_BWD_SLAB_MIN;
-    w.n_slabs = (P + w.S - 1) / w.S;
-    w.R = (cout + 15) / 16 * 16;
-    w.db = 4 * w.n_slabs * w.R * cin;
-    w.total = w.db + 4 * w.n_slabs * w.R;
-    return w;
+static WgScratch wgrad_scratch(Sz P, Sz cin, Sz cout) {
+    const Sz per = (P + (MD_CONV1X1_BWD_MAX_SLABS - 1)) / MD_CONV1X1_BWD_MAX_SLABS;
+    Sz S = (per + 15) / 16 * 16;
+    if (S < MD_CONV1X1_BWD_SLAB_MIN) S = MD_CONV1X1_BWD_SLAB_MIN;
+    const Sz n_slabs = (P + S - 1) / S, R = (cout + 15) / 16 * 16, db = 4 * n_slabs * R * cin, total = db + 4 * n_slabs * R;
+    return {(int64_t)S, (int64_t)n_slabs, (int64_t)R, (int64_t)db, (int64_t)total};
 }
 
 template <int K>
@@ -346,7 +342,7 @@ static int conv_bwd_weight_entry(MD_AOT_ARGS, bool kxk) {
     }
     const md_conv_bwd_attrs *at = &full;
     a.tensor(0, BF16, 4); a.tensor(1, F32, 4); a.tensor(2, F32, 2); a.optional(3, F32, 1);
-    a.optional(WS, U8);
+    a.scratch(WS);
     if (int rc = a.rc()) return rc;
     const int64_t N = a.d(0, 0), H = a.d(0, 1), W = a.d(0, 2), Cx = a.d(0, 3), Cy = a.d(1, 3);
     const bool with_db = a.given(3);
@@ -367,9 +363,9 @@ static int conv_bwd_weight_entry(MD_AOT_ARGS, bool kxk) {
     const int64_t lim = (int64_t)1 << 31;
     if (cin % 8 != 0 || cin > (at->kernel == 1 ? MD_CONV_BWD_MAX_CIN_K1 : MD_CONV_BWD_MAX_CIN_K3) || cout > MD_CONV_BWD_MAX_COUT) return MD_ERR_SIZE;
     if (at->korder == 1 && cin % 64 != 0) return MD_ERR_SIZE;
-    if (N >= lim || H >= lim || W >= lim || N * H >= lim || N * H * W >= lim) return MD_ERR_SIZE;
-    const int64_t P = N * H * W;
-    if (a.numel(2) + (with_db ? a.numel(3) : 0) >= lim) return MD_ERR_SIZE;
+    if (N >= lim || H >= lim || W >= lim || mul({N, H}) >= lim || mul({N, H, W}) >= lim) return MD_ERR_SIZE;
+    const int64_t P = mul({N, H, W});
+    if (add(a.numel(2), with_db ? a.numel(3) : 0) >= lim) return MD_ERR_SIZE;
     if (!a.have({0, 1, 2})) return MD_ERR_ARG;
     const WgScratch w = wgrad_scratch(P, KK, cout);
     hipStream_t s = (hipStream_t)stream;
@@ -488,9 +484,9 @@ static int conv1x1_bwd_data_entry(MD_AOT_ARGS) {
     if (int rc = a.rc()) return rc;
     const int64_t lim = (int64_t)1 << 31;
     if (cin % 8 != 0 || cin > MD_CONV1X1_BWD_DATA_MAX_CIN || cout > MD_CONV1X1_BWD_DATA_MAX_COUT) return MD_ERR_SIZE;
-    if (N >= lim || H >= lim || W >= lim || N * H >= lim || N * H * W >= lim) return MD_ERR_SIZE;
-    const int64_t P = N * H * W;
-    if (P * Cy >= lim || P * Cdx >= lim || P * Ca >= lim || a.numel(1) >= lim) return MD_ERR_SIZE;
+    if (N >= lim || H >= lim || W >= lim || mul({N, H}) >= lim || mul({N, H, W}) >= lim) return MD_ERR_SIZE;
+    const int64_t P = mul({N, H, W});
+    if (mul({P, Cy}) >= lim || mul({P, Cdx}) >= lim || mul({P, Ca}) >= lim || a.numel(1) >= lim) return MD_ERR_SIZE;
     if (!a.have({0, 1, 3})) return MD_ERR_ARG;
 
     DgParams p;
@@ -659,9 +655,9 @@ static int grouped_bwd_data_entry(MD_AOT_ARGS) {
     a.require(!aliased(params, 3, 4));
     if (int rc = a.rc()) return rc;
     const int64_t lim = (int64_t)1 << 31;
-    if (N >= lim || H >= lim || W >= lim || N * H >= lim || N * H * W >= lim) return MD_ERR_SIZE;
-    const int64_t P = N * H * W;
-    if (P * Cy >= lim || P * Cdx >= lim || P * Ca >= lim || a.numel(1) >= lim) return MD_ERR_SIZE;
+    if (N >= lim || H >= lim || W >= lim || mul({N, H}) >= lim || mul({N, H, W}) >= lim) return MD_ERR_SIZE;
+    const int64_t P = mul({N, H, W});
+    if (mul({P, Cy}) >= lim || mul({P, Cdx}) >= lim || mul({P, Ca}) >= lim || a.numel(1) >= lim) return MD_ERR_SIZE;
     if (!a.have({0, 1, 3})) return MD_ERR_ARG;
 
     GdParams p;
@@ -683,13 +679,14 @@ static int grouped_bwd_data_entry(MD_AOT_ARGS) {
 // scratch of md_conv2d_grouped_bwd_weight: per group the scratch of md_conv_bwd_weight for one group (cin 64, one 16-row tile), the groups'
 // dw partials back to back at 0, then their db partials
 struct GwScratch { WgScratch one; int64_t per_dw, per_db, db, total; };
-static GwScratch grouped_wgrad_scratch(int64_t P, int64_t groups, int64_t k) {
+static GwScratch grouped_wgrad_scratch(Sz P, Sz groups, Sz k) {
     GwScratch s;
     s.one = wgrad_scratch(P, k * k * 64, 16);
-    s.per_dw = s.one.db / 4;
-    s.per_db = (s.one.total - s.one.db) / 4;
-    s.db = groups * s.one.db;
-    s.total = groups * s.one.total;
+    const Sz db = s.one.db, total = s.one.total;      // (INT64_MAX where the one-group layout does not fit: it stays so below)
+    s.per_dw = (int64_t)(db / 4);
+    s.per_db = (int64_t)((total - db) / 4);
+    s.db = (int64_t)(groups * db);
+    s.total = (int64_t)(groups * total);
     return s;
 }
 
@@ -699,7 +696,7 @@ static int grouped_bwd_weight_entry(MD_AOT_ARGS) {
     Args a(MD_ARGS, WS, WS + 1);
     const md_conv2d_grouped_attrs *at = a.attrs<md_conv2d_grouped_attrs>(extra);
     a.tensor(0, BF16, 4); a.tensor(1, F32, 4); a.tensor(2, F32, 2); a.optional(3, F32, 1);
-    a.optional(WS, U8);
+    a.scratch(WS);
     if (int rc = a.rc()) return rc;
     const int64_t N = a.d(0, 0), H = a.d(0, 1), W = a.d(0, 2), Cx = a.d(0, 3), Cy = a.d(1, 3), R = a.d(2, 0);
     const bool with_db = a.given(3);
@@ -712,9 +709,9 @@ static int grouped_bwd_weight_entry(MD_AOT_ARGS) {
     a.require(!aliased(params, 2, 4));
     if (int rc = a.rc()) return rc;
     const int64_t lim = (int64_t)1 << 31;
-    if (N >= lim || H >= lim || W >= lim || N * H >= lim || N * H * W >= lim) return MD_ERR_SIZE;
-    const int64_t P = N * H * W;
-    if (P * Cx >= lim || P * Cy >= lim || a.numel(2) + (with_db ? a.numel(3) : 0) >= lim) return MD_ERR_SIZE;
+    if (N >= lim || H >= lim || W >= lim || mul({N, H}) >= lim || mul({N, H, W}) >= lim) return MD_ERR_SIZE;
+    const int64_t P = mul({N, H, W});
+    if (mul({P, Cx}) >= lim || mul({P, Cy}) >= lim || add(a.numel(2), with_db ? a.numel(3) : 0) >= lim) return MD_ERR_SIZE;
     if (!a.have({0, 1, 2})) return MD_ERR_ARG;
     const GwScratch w = grouped_wgrad_scratch(P, G, at->k);
     hipStream_t s = (hipStream_t)stream;
@@ -749,17 +746,18 @@ static int grouped_bwd_weight_entry(MD_AOT_ARGS) {
 using namespace md;
 
 extern "C" int64_t md_conv1x1_bwd_weight_workspace_bytes(int64_t P, int64_t cin, int64_t cout) {
-    return any_negative({P, cin, cout}) ? -1 : wgrad_scratch(P, cin, cout).total;
+    return any_negative({P, cin, cout}) ? -1 : ws_answer(wgrad_scratch(P, cin, cout).total);
 }
 extern "C" int md_conv1x1_bwd_weight(MD_AOT_ARGS) { return conv_bwd_weight_entry(nparam, params, ndims, shapes, dtypes, stream, extra, false); }
 extern "C" int64_t md_conv_bwd_weight_workspace_bytes(int64_t P, int64_t cin, int64_t cout, int64_t kernel) {
-    return any_negative({P, cin, cout}) || (kernel != 1 && kernel != 3) ? -1 : wgrad_scratch(P, kernel * kernel * cin, cout).total;
+    if (any_negative({P, cin, cout}) || (kernel != 1 && kernel != 3)) return -1;
+    return ws_answer(wgrad_scratch(P, Sz(kernel * kernel) * cin, cout).total);
 }
 extern "C" int md_conv_bwd_weight(MD_AOT_ARGS) { return conv_bwd_weight_entry(nparam, params, ndims, shapes, dtypes, stream, extra, true); }
 extern "C" int md_conv1x1_bwd_data(MD_AOT_ARGS) { return conv1x1_bwd_data_entry(nparam, params, ndims, shapes, dtypes, stream, extra); }
 extern "C" int md_conv2d_grouped_bwd_data(MD_AOT_ARGS) { return grouped_bwd_data_entry(nparam, params, ndims, shapes, dtypes, stream, extra); }
 extern "C" int64_t md_conv2d_grouped_bwd_weight_workspace_bytes(int64_t P, int64_t groups, int64_t k) {
-    return any_negative({P, groups}) || (k != 1 && k != 3) ? -1 : grouped_wgrad_scratch(P, groups, k).total;
+    return any_negative({P, groups}) || (k != 1 && k != 3) ? -1 : ws_answer(grouped_wgrad_scratch(P, groups, k).total);
 }
 extern "C" int md_conv2d_grouped_bwd_weight(MD_AOT_ARGS) { return grouped_bwd_weight_entry(nparam, params, ndims, shapes, dtypes, stream, extra); }
 

@@ -385,23 +385,20 @@ using namespace md;
 
 // scratch of md_cp_aug_count_points: rec[B G][CPA_REC] f64
 extern "C" int64_t md_cp_aug_count_points_workspace_bytes(int64_t B, int64_t G) {
-    return any_negative({B, G}) ? -1 : B * G * CPA_REC * 8;
+    return any_negative({B, G}) ? -1 : ws_answer((int64_t)(Sz(B) * G * CPA_REC * 8));
 }
 // scratch of md_cp_aug_select: bits[B][S][ceil((G + S) / 64)] u64
 extern "C" int64_t md_cp_aug_select_workspace_bytes(int64_t B, int64_t G, int64_t S) {
-    return any_negative({B, G, S}) ? -1 : B * S * ((G + S + 63) / 64) * 8;
+    return any_negative({B, G, S}) ? -1 : ws_answer((int64_t)(Sz(B) * S * ((Sz(G) + S + 63) / 64) * 8));
 }
 // scratch of md_cp_aug_points: grec[B][CPA_GREC] f64 at 0, bsum[ceil((N + Ns) / 256) + 1] i32, flag[N + Ns] u8
 struct PtsScratch { int64_t bsum, flag, total; };
-static PtsScratch cp_points_scratch(int64_t N, int64_t Ns, int64_t B) {
-    PtsScratch w;
-    w.bsum = B * CPA_GREC * 8;
-    w.flag = w.bsum + ((N + Ns + 255) / 256 + 1) * 4;
-    w.total = w.flag + N + Ns;
-    return w;
+static PtsScratch cp_points_scratch(Sz N, Sz Ns, Sz B) {
+    const Sz bsum = B * CPA_GREC * 8, flag = bsum + ((N + Ns + 255) / 256 + 1) * 4, total = flag + N + Ns;
+    return {(int64_t)bsum, (int64_t)flag, (int64_t)total};
 }
 extern "C" int64_t md_cp_aug_points_workspace_bytes(int64_t N, int64_t Ns, int64_t B) {
-    return any_negative({N, Ns, B}) ? -1 : cp_points_scratch(N, Ns, B).total;
+    return any_negative({N, Ns, B}) ? -1 : ws_answer(cp_points_scratch(N, Ns, B).total);
 }
 
 extern "C" int md_cp_aug_count_points(MD_AOT_ARGS) {
@@ -410,7 +407,7 @@ extern "C" int md_cp_aug_count_points(MD_AOT_ARGS) {
     Args a(MD_ARGS, 6, 7);
     const md_cp_count_attrs *at = a.attrs<md_cp_count_attrs>(extra);
     a.tensor(0, F32, 2); a.tensor(1, I32, 1); a.tensor(2, F32, 3); a.tensor(3, I32, 1); a.tensor(4, I32, 2); a.tensor(5, U8, 2);
-    a.optional(6, U8);
+    a.scratch(6);
     if (int rc = a.rc()) return rc;
     const int64_t N = a.d(0, 0), B = a.d(1, 0) - 1, G = a.d(2, 1);
     a.require(N >= 0 && B >= 0 && G >= 0 && a.d(0, 1) == CPA_F && a.d(2, 0) == B && a.d(2, 2) == CPA_BOX && a.d(3, 0) == B);
@@ -441,7 +438,7 @@ extern "C" int md_cp_aug_select(MD_AOT_ARGS) {
     // out: accept[B,S] u8 ; [workspace]
     Args a(MD_ARGS, 7, 8);
     a.tensor(0, F32, 3); a.tensor(1, I32, 1); a.tensor(2, U8, 2); a.tensor(3, F32, 3); a.tensor(4, I32, 1); a.tensor(5, I32, 2);
-    a.tensor(6, U8, 2); a.optional(7, U8);
+    a.tensor(6, U8, 2); a.scratch(7);
     if (int rc = a.rc()) return rc;
     const int64_t B = a.d(0, 0), G = a.d(0, 1), S = a.d(3, 1);
     a.require(B >= 0 && G >= 0 && S >= 0 && a.d(0, 2) == CPA_BOX && a.d(1, 0) == B && a.d(2, 0) == B && a.d(2, 1) == G);
@@ -471,7 +468,7 @@ extern "C" int md_cp_aug_points(MD_AOT_ARGS) {
     // out: points_out[N+Ns,5] f32, offsets_out[B+1] i32 ; [workspace]
     Args a(MD_ARGS, 9, 10);
     a.tensor(0, F32, 2); a.tensor(1, I32, 1); a.optional(2, F32, 2); a.optional(3, I32, 1); a.optional(4, F32, 3); a.optional(5, U8, 2);
-    a.tensor(6, F64, 2); a.tensor(7, F32, 2); a.tensor(8, I32, 1); a.optional(9, U8);
+    a.tensor(6, F64, 2); a.tensor(7, F32, 2); a.tensor(8, I32, 1); a.scratch(9);
     if (int rc = a.rc()) return rc;
     const int64_t N = a.d(0, 0), B = a.d(1, 0) - 1;
     const bool cand = a.given(2);

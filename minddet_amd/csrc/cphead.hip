@@ -192,7 +192,7 @@ extern "C" int md_cp_scores(MD_AOT_ARGS) {
     if (int rc = cp_head_of(at, H, W, C, h)) return rc;
     const int64_t n = H * W, T = h.T;
     if (g.d(1, 0) != B || g.d(1, 1) != T || g.d(1, 2) != n) return MD_ERR_ARG;
-    if (C > 480 || !fits_i32(B * T * n) || !fits_i32(B * n * C)) return MD_ERR_SIZE;
+    if (C > 480 || !fits_i32(mul({B, T, n})) || !fits_i32(mul({B, n, C}))) return MD_ERR_SIZE;
     if (B * n == 0) return MD_OK;
     if (!g.have({0, 1})) return MD_ERR_ARG;
     const uint16_t *head = g.ptr<const uint16_t>(0);
@@ -220,7 +220,7 @@ extern "C" int md_cp_decode_selected(MD_AOT_ARGS) {
     if (g.d(3, 0) != B || g.d(3, 1) != T || g.d(3, 2) != k || g.d(3, 3) != 9 || g.d(4, 0) != B || g.d(4, 1) != T || g.d(4, 2) != k ||
         g.d(4, 3) != 7 || g.d(5, 0) != B || g.d(5, 1) != T || g.d(5, 2) != k)
         return MD_ERR_ARG;
-    if (!fits_i32(B * T * k * 9) || !fits_i32(B * H * W * C)) return MD_ERR_SIZE;
+    if (!fits_i32(mul({B, T, k, 9})) || !fits_i32(mul({B, H, W, C}))) return MD_ERR_SIZE;
     if (B * k == 0) return MD_OK;
     if (!g.have({0, 1, 2, 3, 4, 5})) return MD_ERR_ARG;
     hipLaunchKernelGGL(cp_decode_selected_kernel, dim3((unsigned)((B * T * k + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
@@ -245,7 +245,7 @@ extern "C" int md_cp_pack(MD_AOT_ARGS) {
     for (int i = 4; i <= 5; ++i)
         if (g.d(i, 0) != B || g.d(i, 1) != T) return MD_ERR_ARG;
     if (g.d(6, 0) != B || g.d(6, 1) != T * m || g.d(6, 2) != 11 || g.d(7, 0) != B) return MD_ERR_ARG;
-    if (T * m > 65536 || !fits_i32(B * T * k * 9) || !fits_i32(B * T * m * 11)) return MD_ERR_SIZE;
+    if (mul({T, m}) > 65536 || !fits_i32(mul({B, T, k, 9})) || !fits_i32(mul({B, T, m, 11}))) return MD_ERR_SIZE;
     if (B == 0) return MD_OK;
     if (!g.have({6, 7}) || (k > 0 && !g.have({0, 1, 2, 3})) || !g.have({4, 5})) return MD_ERR_ARG;
     CpPackArgs a;

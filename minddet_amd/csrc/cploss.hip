@@ -257,12 +257,9 @@ __global__ __launch_bounds__(512) void cp_loss_finish_kernel(const uint16_t *__r
 // scratch of md_cp_loss and md_cp_loss_grad: rec[B T][CPL_REC] f64 at 0, then neg_part[B T][sps] f64, sps = the strips of CPL_STRIP
 // cells per sample
 struct CplScratch { int64_t sps, neg_part, total; };
-static CplScratch cp_loss_scratch(int64_t B, int64_t T, int64_t H, int64_t W) {
-    CplScratch w;
-    w.sps = (H * W + CPL_STRIP - 1) / CPL_STRIP;
-    w.neg_part = 8 * B * T * CPL_REC;
-    w.total = w.neg_part + 8 * B * T * w.sps;
-    return w;
+static CplScratch cp_loss_scratch(Sz B, Sz T, Sz H, Sz W) {
+    const Sz sps = (H * W + (CPL_STRIP - 1)) / CPL_STRIP, neg_part = 8 * B * T * CPL_REC, total = neg_part + 8 * B * T * sps;
+    return {(int64_t)sps, (int64_t)neg_part, (int64_t)total};
 }
 
 static int cp_loss_entry(MD_AOT_ARGS, bool with_grad) {
@@ -274,7 +271,7 @@ static int cp_loss_entry(MD_AOT_ARGS, bool with_grad) {
     a.tensor(0, BF16, 4); a.tensor(1, F32, 5); a.tensor(2, F32, 4); a.tensor(3, I32, 3); a.tensor(4, U8, 3); a.tensor(5, I32, 3);
     a.tensor(6, F32, 2); a.tensor(7, F32, 1); a.tensor(8, F32, 1);
     if (with_grad) a.tensor(9, F32, 4);
-    a.optional(WS, U8);
+    a.scratch(WS);
     if (int rc = a.rc()) return rc;
     const int64_t B = a.d(0, 0), H = a.d(0, 1), W = a.d(0, 2), Cp = a.d(0, 3), T = a.d(1, 1), C = a.d(1, 2), M = a.d(2, 2);
     a.require(B >= 1 && H >= 1 && W >= 1 && Cp >= 1 && M >= 0);
@@ -350,7 +347,7 @@ static int cp_loss_entry(MD_AOT_ARGS, bool with_grad) {
 using namespace md;
 
 extern "C" int64_t md_cp_loss_workspace_bytes(int64_t B, int64_t T, int64_t H, int64_t W) {
-    return any_negative({B, T, H, W}) ? -1 : cp_loss_scratch(B, T, H, W).total;
+    return any_negative({B, T, H, W}) ? -1 : ws_answer(cp_loss_scratch(B, T, H, W).total);
 }
 extern "C" int md_cp_loss(MD_AOT_ARGS) { return cp_loss_entry(nparam, params, ndims, shapes, dtypes, stream, extra, false); }
 extern "C" int md_cp_loss_grad(MD_AOT_ARGS) { return cp_loss_entry(nparam, params, ndims, shapes, dtypes, stream, extra, true); }

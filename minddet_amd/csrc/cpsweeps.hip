@@ -164,13 +164,13 @@ __global__ __launch_bounds__(256) void cps_scatter_kernel(SweepArgs a) {
 using namespace md;
 
 // workgroups of the count and scatter kernels of md_cp_sweeps_merge: one per 256 input rows and one per segment, at least one
-static int64_t cps_blocks(int64_t N, int64_t B, int64_t S) {
-    const int64_t nb = (N + 255) / 256 + B * S;
-    return nb ? nb : 1;
+static Sz cps_blocks(Sz N, Sz B, Sz S) {
+    const Sz nb = (N + 255) / 256 + B * S;
+    return nb ? nb : Sz(1);
 }
 // scratch of md_cp_sweeps_merge: bsum[blocks + 1] i32
 extern "C" int64_t md_cp_sweeps_merge_workspace_bytes(int64_t N, int64_t B, int64_t S) {
-    return any_negative({N, B, S}) ? -1 : (cps_blocks(N, B, S) + 1) * 4;
+    return any_negative({N, B, S}) ? -1 : ws_answer((int64_t)((cps_blocks(N, B, S) + 1) * 4));
 }
 
 extern "C" int md_cp_sweeps_merge(MD_AOT_ARGS) {
@@ -179,7 +179,7 @@ extern "C" int md_cp_sweeps_merge(MD_AOT_ARGS) {
     Args a(MD_ARGS, 8, 9);
     const md_cp_sweeps_attrs *at = a.attrs<md_cp_sweeps_attrs>(extra);
     a.tensor(0, F32, 2); a.tensor(1, I32, 3); a.tensor(2, "float64", 3); a.tensor(3, "float64", 2); a.tensor(4, I32, 2);
-    a.tensor(5, F32, 2); a.tensor(6, I32, 1); a.tensor(7, I32, 1); a.optional(8, U8);
+    a.tensor(5, F32, 2); a.tensor(6, I32, 1); a.tensor(7, I32, 1); a.scratch(8);
     if (int rc = a.rc()) return rc;
     const int64_t N = a.d(0, 0), Fin = a.d(0, 1), B = a.d(1, 0), S = a.d(1, 1), M = a.d(5, 0);
     a.require(N >= 0 && (Fin == 4 || Fin == 5) && B >= 0 && S >= 0 && a.d(1, 2) == 2);
@@ -195,7 +195,7 @@ extern "C" int md_cp_sweeps_merge(MD_AOT_ARGS) {
     if (M > 0 && !a.have({5})) return MD_ERR_ARG;
     if (aliased(params, 5, 8)) return MD_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    const int64_t nb = cps_blocks(N, B, S);
+    const int64_t nb = (int64_t)cps_blocks(N, B, S);
     Scratch ws;
     if (int rc = ws.acquire((size_t)md_cp_sweeps_merge_workspace_bytes(N, B, S), a, 8, s)) return rc;
     SweepArgs k;

@@ -145,7 +145,7 @@ using namespace md;
 
 // scratch of md_cp_assign_targets: draw[B][T][G + 1] int4
 extern "C" int64_t md_cp_assign_targets_workspace_bytes(int64_t B, int64_t T, int64_t G) {
-    return any_negative({B, T, G}) ? -1 : B * T * (G + 1) * 16;
+    return any_negative({B, T, G}) ? -1 : ws_answer((int64_t)(Sz(B) * T * (Sz(G) + 1) * 16));
 }
 
 extern "C" int md_cp_assign_targets(MD_AOT_ARGS) {
@@ -155,7 +155,7 @@ extern "C" int md_cp_assign_targets(MD_AOT_ARGS) {
     Args a(MD_ARGS, 8, 9);
     const md_cp_targets_attrs *at = a.attrs<md_cp_targets_attrs>(extra);
     a.tensor(0, F32, 3); a.tensor(1, I32, 2); a.tensor(2, F32, 5); a.tensor(3, F32, 4); a.tensor(4, I32, 3); a.tensor(5, U8, 3);
-    a.tensor(6, I32, 3); a.tensor(7, F32, 3); a.optional(8, U8);
+    a.tensor(6, I32, 3); a.tensor(7, F32, 3); a.scratch(8);
     if (int rc = a.rc()) return rc;
     const int64_t B = a.d(0, 0), G = a.d(0, 1), T = a.d(2, 1), C = a.d(2, 2), H = a.d(2, 3), W = a.d(2, 4), M = a.d(3, 2);
     a.require(B >= 0 && G >= 0 && M >= 0 && H >= 1 && W >= 1 && a.d(0, 2) == 9 && a.d(1, 0) == B && a.d(1, 1) == G);
@@ -179,7 +179,8 @@ extern "C" int md_cp_assign_targets(MD_AOT_ARGS) {
     a.require(at->gaussian_overlap > 0.f && at->gaussian_overlap < 1.f);   // (false for a NaN)
     if (int rc = a.rc()) return rc;
     const int64_t lim = (int64_t)1 << 30;
-    if (G > CPT_MAX_GT || B * G * 9 >= lim || a.numel(2) >= lim || a.numel(3) >= lim || a.numel(7) >= lim || B > 65535 || T * C > 65535)
+    if (G > CPT_MAX_GT || mul({B, G, 9}) >= lim || a.numel(2) >= lim || a.numel(3) >= lim || a.numel(7) >= lim || B > 65535 ||
+        mul({T, C}) > 65535)
         return MD_ERR_SIZE;
     if (B == 0) return MD_OK;
     if (!a.have({0, 1, 2, 3, 4, 5, 6, 7})) return MD_ERR_ARG;

@@ -1291,7 +1291,7 @@ extern "C" int md_topk_last_path(void) { return g_topk_last_path; }
 // scratch of md_topk_segmented, taken by the multi-workgroup form alone (total 0: one of the single-workgroup forms runs, L >= 1):
 // ghist[L][TK_BINS] u32 and cand_cnt[L] u32 at 0, padded to 256 bytes, then cand[L][TK_CAP] u64
 struct TopkScratch { int64_t cand, total; };
-static TopkScratch topk_scratch(int64_t L, int64_t k, int64_t max_segment) {
+static TopkScratch topk_scratch(int64_t L, int64_t k, int64_t max_segment) {     // (L <= 65535 where anything is taken: no product can wrap)
     TopkScratch w = {0, 0};
     // (r03: lowering the threshold to one 8192-score chunk -- the 32-image YOLO batches, 25 200 / 8 400 scores per image, run the single-workgroup
     // form for 110 / 86 us -- measured no gain: three launches + a memset cost what the idle CUs cost)
@@ -1315,7 +1315,7 @@ extern "C" int md_topk_segmented(MD_AOT_ARGS) {
     if (int rc = a.rc()) return rc;
     if (L < 0 || at->k < 1) return MD_ERR_ARG;
     if (at->k > TOPK_MAXK) return MD_ERR_SIZE;
-    if (a.numel(2) != L * at->k || a.numel(3) != L * at->k || a.numel(4) != L) return MD_ERR_ARG;
+    if (a.numel(2) != mul({L, at->k}) || a.numel(3) != mul({L, at->k}) || a.numel(4) != L) return MD_ERR_ARG;
     if (L == 0) return MD_OK;
     if (!a.have({0, 1, 2, 3, 4})) return MD_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
@@ -1381,10 +1381,11 @@ extern "C" int md_roi_align(MD_AOT_ARGS) {
         else if (g.d(1 + l, 3) != a.C || g.d(1 + l, 0) != a.N) return MD_ERR_ARG;
     }
     if (a.C % 8) return MD_ERR_ARG;
-    if (g.numel(1 + L) != R * a.P * a.P * a.C) return MD_ERR_ARG;
+    if (g.numel(1 + L) != mul({R, a.P, a.P, a.C})) return MD_ERR_ARG;
     if (R == 0) return MD_OK;
     for (int i = 0; i < 2 + L; ++i)
         if (!g.have({i})) return MD_ERR_ARG;
+    if (mul({R, a.P, a.P, a.C}) == INT64_MAX) return MD_ERR_SIZE;
     const size_t total = (size_t)R * a.P * a.P * (a.C / 8);
     if (a.C % 32 == 0)
         hipLaunchKernelGGL(roi_align_c32_kernel, dim3(grid1d(total / 4)), dim3(256), 0, (hipStream_t)stream, a,
@@ -1401,6 +1402,7 @@ extern "C" int md_heat_nms(MD_AOT_ARGS) {
     a.tensor(0, F32, 4); a.tensor(1, F32);
     a.require(a.numel(1) == a.numel(0));
     if (int rc = a.rc()) return rc;
+    if (a.numel(0) == INT64_MAX) return MD_ERR_SIZE;
     const size_t planes = (size_t)a.d(0, 0) * a.d(0, 1);
     const int H = (int)a.d(0, 2), W = (int)a.d(0, 3);
     if (planes * H * W == 0) return MD_OK;
@@ -1421,8 +1423,8 @@ extern "C" int md_heat_peaks(MD_AOT_ARGS) {
     a.H = (int)g.d(0, 1); a.W = (int)g.d(0, 2); a.Cp = (int)g.d(0, 3);
     a.c0 = at->c0; a.nc = at->num_classes; a.lo = at->lo; a.hi = at->hi;
     if (a.Cp % 8 || a.c0 < 0 || a.c0 % 8 || a.nc < 1 || a.c0 + (a.nc + 7) / 8 * 8 > a.Cp) return MD_ERR_ARG;
-    if (g.numel(1) != B * a.nc * a.H * a.W || (g.given(2) && g.numel(2) != B * a.nc * a.H * a.W)) return MD_ERR_ARG;
-    if (B * a.H * a.W == 0) return MD_OK;
+    if (g.numel(1) != mul({B, a.nc, a.H, a.W}) || (g.given(2) && g.numel(2) != mul({B, a.nc, a.H, a.W}))) return MD_ERR_ARG;
+    if (mul({B, a.H, a.W}) == 0) return MD_OK;
     if (!g.have({0, 1})) return MD_ERR_ARG;
     const long long tiles = (long long)((a.H + PK_TH - 1) / PK_TH) * ((a.W + PK_TW - 1) / PK_TW);
     if (!fits_i32(tiles) || B > 65535 || (a.nc + PK_C - 1) / PK_C > 65535) return MD_ERR_SIZE;
@@ -1437,15 +1439,16 @@ extern "C" int md_centernet_assemble(MD_AOT_ARGS) {
     Args a(MD_ARGS, 8, 8);
     a.tensor(0, F32, 2); a.tensor(1, I32); a.tensor(2, I32, 3); a.tensor(3, F32, 4); a.optional(4, F32);
     a.tensor(5, F32); a.tensor(6, I32); a.tensor(7, I32);
+    const int64_t total = a.numel(0);      // B K
+    a.require(a.d(2, 2) == a.d(0, 1) && a.d(2, 0) == a.d(0, 0) && a.d(3, 0) == a.d(0, 0) && a.d(3, 1) == 2 && a.numel(5) == mul({total, 6}));
+    a.require(a.numel(1) >= total && a.numel(6) >= total && a.numel(7) >= total && (!a.given(4) || a.numel(4) >= a.numel(3)));
+    if (int rc = a.rc()) return rc;
+    if (total == 0) return MD_OK;
+    if (!a.have({0, 1, 2, 3, 5, 6, 7})) return MD_ERR_ARG;
+    if (!fits_i32(total + 255) || !fits_i32(mul({a.d(2, 1), a.d(0, 1)}))) return MD_ERR_SIZE;      // the kernel counts items and C K in int
     const int B = (int)a.d(0, 0), K = (int)a.d(0, 1), C = (int)a.d(2, 1);
     const int H = (int)a.d(3, 2), W = (int)a.d(3, 3);
-    a.require(a.d(2, 2) == K && a.d(2, 0) == B && a.d(3, 0) == B && a.d(3, 1) == 2 && a.numel(5) == (int64_t)B * K * 6);
-    a.require(a.numel(1) >= (int64_t)B * K && a.numel(6) >= (int64_t)B * K && a.numel(7) >= (int64_t)B * K &&
-              (!a.given(4) || a.numel(4) >= a.numel(3)));
-    if (int rc = a.rc()) return rc;
-    if (B * K == 0) return MD_OK;
-    if (!a.have({0, 1, 2, 3, 5, 6, 7})) return MD_ERR_ARG;
-    hipLaunchKernelGGL(centernet_assemble_kernel, dim3((B * K + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(centernet_assemble_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        (const float *)params[0], (const int *)params[1], (const int *)params[2], (const float *)params[3],
                        (const float *)params[4], B, C, K, H, W, (float *)params[5], (int *)params[6], (int *)params[7]);
     return launched();
@@ -1468,8 +1471,8 @@ extern "C" int md_centerpoint_decode(MD_AOT_ARGS) {
     a.g.score_thr = at->score_threshold; a.g.osf = at->out_size_factor; a.g.vx = at->voxel_size[0]; a.g.vy = at->voxel_size[1];
     a.g.px = at->pc_range[0]; a.g.py = at->pc_range[1];
     for (int i = 0; i < 3; ++i) { a.g.rmin[i] = at->post_center_range[i]; a.g.rmax[i] = at->post_center_range[3 + i]; }
-    const int64_t total = (int64_t)B * a.H * a.W;
-    if (g.numel(1) != total || g.numel(2) != total || g.numel(3) != total * 9 || g.numel(4) != total * 7) return MD_ERR_ARG;
+    const int64_t total = mul({B, a.H, a.W});
+    if (g.numel(1) != total || g.numel(2) != total || g.numel(3) != mul({total, 9}) || g.numel(4) != mul({total, 7})) return MD_ERR_ARG;
     if (total == 0) return MD_OK;
     if (!fits_i32(total)) return MD_ERR_SIZE;
     if (!g.have({0, 1, 2, 3, 4})) return MD_ERR_ARG;
@@ -1492,10 +1495,10 @@ extern "C" int md_yolo_decode(MD_AOT_ARGS) {
     a.off = at->out_offset; a.total = at->out_total;
     if (a.A < 1 || a.A > 3 || a.nc < 1 || a.A * (5 + a.nc) > a.Cp) return MD_ERR_ARG;
     for (int i = 0; i < a.A; ++i) { a.aw[i] = at->anchors[2 * i]; a.ah[i] = at->anchors[2 * i + 1]; }
-    const int64_t per = (int64_t)a.H * a.W * a.A;
+    const int64_t per = mul({a.H, a.W, a.A});
     if (a.off < 0 || a.off + per > a.total) return MD_ERR_ARG;
-    if (g.numel(1) != (int64_t)B * a.total * 4 || g.numel(2) != (int64_t)B * a.total || g.numel(3) != (int64_t)B * a.total) return MD_ERR_ARG;
-    if (B * per == 0) return MD_OK;
+    if (g.numel(1) != mul({B, a.total, 4}) || g.numel(2) != (int64_t)B * a.total || g.numel(3) != (int64_t)B * a.total) return MD_ERR_ARG;
+    if (mul({B, per}) == 0) return MD_OK;
     if (a.Cp % 8 || !g.have({0, 1, 2, 3})) return MD_ERR_ARG;
     // cells per 256-thread workgroup: A threads per cell, rows of Cp/2 + 1 dwords in at most 60 KiB of LDS
     int cells = 256 / a.A;
@@ -1515,8 +1518,8 @@ extern "C" int md_standup_boxes(MD_AOT_ARGS) {
     Args a(MD_ARGS, 2, 2);
     a.tensor(0, F32, 2); a.tensor(1, F32);
     const int64_t n = a.d(0, 0);
-    const int S = (int)a.d(0, 1);
-    a.require((S == 5 || S == 7) && a.numel(1) == n * 4);
+    const int64_t S = a.d(0, 1);
+    a.require((S == 5 || S == 7) && a.numel(1) == mul({n, 4}));
     if (int rc = a.rc()) return rc;
     if (n == 0) return MD_OK;
     if (!fits_i32(n)) return MD_ERR_SIZE;
@@ -1534,12 +1537,14 @@ extern "C" int md_gather_rows(MD_AOT_ARGS) {
     // in: src[B,n,W] f32, idx[B,k] i32, cnt[B] i32 or NULL ; out: out[B,k,W] f32
     Args a(MD_ARGS, 4, 4);
     a.tensor(0, F32, 3); a.tensor(1, I32, 2); a.optional(2, I32); a.tensor(3, F32);
-    const int B = (int)a.d(0, 0), n = (int)a.d(0, 1), W = (int)a.d(0, 2), k = (int)a.d(1, 1);
-    a.require(a.d(1, 0) == B && a.numel(3) == (int64_t)B * k * W && (!a.given(2) || a.numel(2) >= B));
+    const int64_t total = mul({a.d(0, 0), a.d(1, 1), a.d(0, 2)});
+    a.require(a.d(1, 0) == a.d(0, 0) && a.numel(3) == total && (!a.given(2) || a.numel(2) >= a.d(0, 0)));
     if (int rc = a.rc()) return rc;
-    if ((int64_t)B * k * W == 0) return MD_OK;
+    if (total == 0) return MD_OK;
     if (!a.have({0, 1, 3})) return MD_ERR_ARG;
-    hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)(((int64_t)B * k * W + 255) / 256)), dim3(256), 0,
+    if (!fits_i32((total + 255) / 256)) return MD_ERR_SIZE;     // the grid; every extent fits int (rc() above)
+    const int B = (int)a.d(0, 0), n = (int)a.d(0, 1), W = (int)a.d(0, 2), k = (int)a.d(1, 1);
+    hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
                        (hipStream_t)stream, (const float *)params[0], (const int *)params[1], (const int *)params[2], B, n, k,
                        W, (float *)params[3]);
     return launched();
@@ -1571,11 +1576,11 @@ extern "C" int md_yolov8_decode(MD_AOT_ARGS) {
     const int B = (int)g.d(0, 0);
     a.H = (int)g.d(0, 1); a.W = (int)g.d(0, 2); a.Cp = (int)g.d(0, 3);
     a.nc = at->num_classes; a.R = at->reg_max; a.stride = at->stride; a.thr = at->conf_thres; a.off = at->out_offset; a.total = at->out_total;
-    const int per = a.H * a.W;
+    const int64_t per = (int64_t)a.H * a.W;
     if (a.nc < 1 || a.R < 1 || a.R > 64 || 4 * a.R + a.nc > a.Cp || a.off < 0 || a.off + per > a.total) return MD_ERR_ARG;
-    if (g.numel(1) != (int64_t)B * a.total * 4 || g.numel(2) != (int64_t)B * a.total || g.numel(3) != (int64_t)B * a.total) return MD_ERR_ARG;
-    if ((int64_t)B * per == 0) return MD_OK;
-    if (!fits_i32((int64_t)B * per)) return MD_ERR_SIZE;
+    if (g.numel(1) != mul({B, a.total, 4}) || g.numel(2) != (int64_t)B * a.total || g.numel(3) != (int64_t)B * a.total) return MD_ERR_ARG;
+    if (mul({B, per}) == 0) return MD_OK;
+    if (!fits_i32(mul({B, per}))) return MD_ERR_SIZE;
     if (a.Cp % 8 || !g.have({0, 1, 2, 3})) return MD_ERR_ARG;
     int cells = 128;                                  // one thread per cell; rows of Cp/2 + 1 dwords in at most 60 KiB of LDS
     const int rowb = (a.Cp / 2 + 1) * 4;

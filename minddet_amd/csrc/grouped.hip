@@ -170,12 +170,12 @@ extern "C" int md_conv2d_grouped(MD_AOT_ARGS) {
         for (int h = 0; h < g; ++h)   // two groups writing one channel would race
             if (yo < at->y_off[h] + at->cout[h] && at->y_off[h] < yo + co) return MD_ERR_ARG;
     }
-    if (N * H * W == 0) return MD_OK;
+    if (mul({N, H, W}) == 0) return MD_OK;
     if (!g.have({0, 1, 2, 3})) return MD_ERR_ARG;
     {   // y must not overlap x (a workgroup's halo pixels are other workgroups' outputs)
         const char *xb = (const char *)params[0], *yb = (const char *)params[3];
-        const long long xn = N * H * W * C * 2, yn = N * H * W * Cy * 2;
-        if (xb < yb + yn && yb < xb + xn) return MD_ERR_ARG;
+        const long long xn = mul({N, H, W, C, 2}), yn = mul({N, H, W, Cy, 2});
+        if (ranges_overlap(xb, xn, yb, yn)) return MD_ERR_ARG;
     }
     if (H > 32000 || W > 32000 || C > 65536 || Cy > 65536) return MD_ERR_SIZE;
     GroupedArgs a;

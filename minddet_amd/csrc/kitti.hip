@@ -209,14 +209,12 @@ using namespace md;
 
 // scratch of md_pc_crop_hulls: planes[B K][KC_PLANE] f64 at 0, bsum[ceil(N / 256) + 1] i32
 struct CropScratch { int64_t bsum, total; };
-static CropScratch crop_scratch(int64_t N, int64_t B, int64_t K) {
-    CropScratch w;
-    w.bsum = B * K * KC_PLANE * 8;
-    w.total = w.bsum + ((N + 255) / 256 + 1) * 4;
-    return w;
+static CropScratch crop_scratch(Sz N, Sz B, Sz K) {
+    const Sz bsum = B * K * KC_PLANE * 8, total = bsum + ((N + 255) / 256 + 1) * 4;
+    return {(int64_t)bsum, (int64_t)total};
 }
 extern "C" int64_t md_pc_crop_hulls_workspace_bytes(int64_t N, int64_t B, int64_t K) {
-    return any_negative({N, B, K}) ? -1 : crop_scratch(N, B, K).total;
+    return any_negative({N, B, K}) ? -1 : ws_answer(crop_scratch(N, B, K).total);
 }
 
 extern "C" int md_pc_crop_hulls(MD_AOT_ARGS) {
@@ -224,7 +222,7 @@ extern "C" int md_pc_crop_hulls(MD_AOT_ARGS) {
     // out: points_out[N,4] f32, offsets_out[B+1] i32, keep[N] u8 ; [workspace]
     Args a(MD_ARGS, 7, 8);
     a.tensor(0, F32, 2); a.tensor(1, I32, 1); a.tensor(2, F64, 4); a.tensor(3, I32, 1);
-    a.tensor(4, F32, 2); a.tensor(5, I32, 1); a.tensor(6, U8, 1); a.optional(7, U8);
+    a.tensor(4, F32, 2); a.tensor(5, I32, 1); a.tensor(6, U8, 1); a.scratch(7);
     if (int rc = a.rc()) return rc;
     const int64_t N = a.d(0, 0), B = a.d(1, 0) - 1, K = a.d(2, 1);
     a.require(N >= 0 && B >= 0 && K >= 0 && a.d(0, 1) == 4 && a.d(2, 0) == B && a.d(2, 2) == 8 && a.d(2, 3) == 3 && a.d(3, 0) == B);

@@ -576,14 +576,12 @@ extern "C" int NmsNormalGpu(MD_AOT_ARGS) {
 // scratch of md_nms_rotated: mask[L][n][ceil(n / 64)] u64 at 0 (the 8-byte words first: the records are a multiple of 4 bytes only),
 // then rec[L][n][ROT_REC] f32
 struct RotatedScratch { int64_t rec, total; };
-static RotatedScratch nms_rotated_scratch(int64_t L, int64_t n) {
-    RotatedScratch w;
-    w.rec = L * n * ((n + TILE - 1) / TILE) * 8;
-    w.total = w.rec + L * n * ROT_REC * 4;
-    return w;
+static RotatedScratch nms_rotated_scratch(Sz L, Sz n) {
+    const Sz rec = L * n * ((n + TILE - 1) / TILE) * 8, total = rec + L * n * ROT_REC * 4;
+    return {(int64_t)rec, (int64_t)total};
 }
 extern "C" int64_t md_nms_rotated_workspace_bytes(int64_t L, int64_t n) {
-    return any_negative({L, n}) ? -1 : nms_rotated_scratch(L, n).total;
+    return any_negative({L, n}) ? -1 : ws_answer(nms_rotated_scratch(L, n).total);
 }
 
 // include/minddet_hip_cp.h.  in: boxes[L,N,7] f32 (or [N,7]), count[L] i32 | NULL ; out: keep_idx[L,N] i32, num[L] i32 ; [workspace].
@@ -596,7 +594,7 @@ extern "C" int md_nms_rotated(MD_AOT_ARGS) {
     const int64_t L = a.rank(0) == 3 ? a.d(0, 0) : 1, n = a.d(0, -2);
     a.require(a.d(0, -1) == 7 && L >= 0 && n >= 0);
     a.require(n <= (1 << 16) && L <= 65535, MD_ERR_SIZE);
-    a.require((!a.given(1) || a.numel(1) == L) && a.numel(2) == L * n && a.numel(3) == L);
+    a.require((!a.given(1) || a.numel(1) == L) && a.numel(2) == mul({L, n}) && a.numel(3) == L);
     if (int rc = a.rc()) return rc;
     if (at->mode < 0 || at->mode > 1 || at->max_output < 0) return MD_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
@@ -659,7 +657,7 @@ static Args pair_matrix_args(int nparam, void **params, int *ndims, int64_t **sh
     Args a(MD_ARGS, 3, 3);
     a.tensor(0, F32, 2); a.tensor(1, F32, 2); a.tensor(2, F32);
     n = a.d(0, 0); k = a.d(1, 0);
-    a.require(n >= 0 && k >= 0 && a.d(0, 1) == width && a.d(1, 1) == width && a.numel(2) >= n * k);
+    a.require(n >= 0 && k >= 0 && a.d(0, 1) == width && a.d(1, 1) == width && a.numel(2) >= mul({n, k}));
     return a;
 }
 
@@ -671,6 +669,7 @@ extern "C" int md_iou_aligned(MD_AOT_ARGS) {
     if (n == 0 || k == 0) return MD_OK;
     if (!a.have({0, 1, 2})) return MD_ERR_ARG;
     const float eps = extra ? ((const md_iou_attrs *)extra)->eps : 0.f;
+    if (!fits_i32((mul({n, k}) - 1) / 256 + 1)) return MD_ERR_SIZE;      // one thread per pair: the grid
     const size_t total = (size_t)n * k;
     hipLaunchKernelGGL(iou_aligned_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        a.ptr<const float>(0), (int)n, a.ptr<const float>(1), (int)k, eps, a.ptr<float>(2));
@@ -686,6 +685,7 @@ extern "C" int md_rotate_iou_eval(MD_AOT_ARGS) {
     if (n > (1 << 24) || k > (1 << 24)) return MD_ERR_SIZE;
     if (!a.have({0, 1, 2})) return MD_ERR_ARG;
     const int criterion = extra ? ((const md_rotate_iou_attrs *)extra)->criterion : -1;
+    if (!fits_i32((mul({n, k}) - 1) / 256 + 1)) return MD_ERR_SIZE;      // one thread per pair: the grid
     const size_t total = (size_t)n * k;
     hipLaunchKernelGGL(rotate_iou_eval_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        a.ptr<const float>(0), (int)n, a.ptr<const float>(1), (int)k, criterion, a.ptr<float>(2));
@@ -695,16 +695,14 @@ extern "C" int md_rotate_iou_eval(MD_AOT_ARGS) {
 // scratch of md_nms_aligned: mask[B][n][ceil(n / 64)] u64 at 0, then -- for the two-level form only, flags < total -- need_full[B] i32.
 // P: the prefix that the first pass of the two-level form decides (below), a multiple of 64
 struct AlignedScratch { int64_t P, flags, total; };
-static AlignedScratch nms_aligned_scratch(int64_t B, int64_t n, int64_t max_output) {
-    const int64_t want = max_output > 128 ? 4 * max_output : 512;
-    AlignedScratch w;
-    w.P = (want + TILE - 1) / TILE * TILE;
-    w.flags = B * n * ((n + TILE - 1) / TILE) * 8;
-    w.total = w.flags + (max_output > 0 && n >= 2 * w.P ? (int64_t)align_up((size_t)B * 4, 256) : 0);
-    return w;
+static AlignedScratch nms_aligned_scratch(Sz B, Sz n, Sz max_output) {
+    const Sz want = max_output > 128 ? 4 * max_output : Sz(512);
+    const Sz P = (want + TILE - 1) / TILE * TILE, flags = B * n * ((n + TILE - 1) / TILE) * 8;
+    const Sz total = flags + (max_output > 0 && n >= 2 * P ? align_up(B * 4, 256) : Sz(0));
+    return {(int64_t)P, (int64_t)flags, (int64_t)total};
 }
 extern "C" int64_t md_nms_aligned_workspace_bytes(int64_t B, int64_t n, int64_t max_output) {
-    return any_negative({B, n, max_output}) ? -1 : nms_aligned_scratch(B, n, max_output).total;
+    return any_negative({B, n, max_output}) ? -1 : ws_answer(nms_aligned_scratch(B, n, max_output).total);
 }
 
 extern "C" int md_nms_aligned(MD_AOT_ARGS) {
@@ -769,7 +767,7 @@ extern "C" int md_soft_nms(MD_AOT_ARGS) {
     const md_soft_nms_attrs *at = a.attrs<md_soft_nms_attrs>(extra);
     a.tensor(0, F32, 2, 3); a.tensor(1, F32); a.optional(2, I32); a.tensor(3, F32); a.tensor(4, I32); a.tensor(5, I32);
     const int64_t L = a.rank(0) == 3 ? a.d(0, 0) : 1, n = a.d(0, -2);
-    a.require(a.d(0, -1) == 4 && a.numel(1) == L * n && a.numel(3) == L * n && a.numel(4) == L * n && a.numel(5) == L &&
+    a.require(a.d(0, -1) == 4 && a.numel(1) == mul({L, n}) && a.numel(3) == mul({L, n}) && a.numel(4) == mul({L, n}) && a.numel(5) == L &&
               (!a.given(2) || a.numel(2) >= L));
     a.require(n <= 1024, MD_ERR_SIZE);
     if (int rc = a.rc()) return rc;

@@ -102,7 +102,7 @@ __global__ __launch_bounds__(256) void adam_step_kernel(const float *__restrict_
 }
 
 static int64_t grad_sumsq_blocks(int64_t n) {
-    const int64_t chunks = (n + GS_CHUNK - 1) / GS_CHUNK;
+    const int64_t chunks = n / GS_CHUNK + (n % GS_CHUNK != 0);
     return chunks < 1 ? 1 : (chunks > GS_MAX_BLOCKS ? GS_MAX_BLOCKS : chunks);
 }
 
@@ -111,7 +111,7 @@ static int grad_sumsq_entry(MD_AOT_ARGS) {
     const int WS = 2;
     Args a(MD_ARGS, WS, WS + 1);
     a.tensor(0, F32, 1); a.tensor(1, "float64", 1);
-    a.optional(WS, U8);
+    a.scratch(WS);
     if (int rc = a.rc()) return rc;
     const int64_t n = a.d(0, 0);
     a.require(n >= 1 && a.d(1, 0) == 1);

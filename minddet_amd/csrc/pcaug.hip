@@ -360,15 +360,12 @@ extern "C" int md_pc_noise_per_object(MD_AOT_ARGS) {
 
 // scratch of md_pc_augment_points: rec[B (G + R)][PCA_REC] f64 at 0, grec[B][PCA_GREC] f64, bsum[ceil(N / 256) + 1] i32
 struct PointScratch { int64_t grec, bsum, total; };
-static PointScratch pc_points_scratch(int64_t N, int64_t B, int64_t G, int64_t R) {
-    PointScratch w;
-    w.grec = B * (G + R) * PCA_REC * 8;
-    w.bsum = w.grec + B * PCA_GREC * 8;
-    w.total = w.bsum + ((N + 255) / 256 + 1) * 4;
-    return w;
+static PointScratch pc_points_scratch(Sz N, Sz B, Sz G, Sz R) {
+    const Sz grec = B * (G + R) * PCA_REC * 8, bsum = grec + B * PCA_GREC * 8, total = bsum + ((N + 255) / 256 + 1) * 4;
+    return {(int64_t)grec, (int64_t)bsum, (int64_t)total};
 }
 extern "C" int64_t md_pc_augment_points_workspace_bytes(int64_t N, int64_t B, int64_t G, int64_t R) {
-    return any_negative({N, B, G, R}) ? -1 : pc_points_scratch(N, B, G, R).total;
+    return any_negative({N, B, G, R}) ? -1 : ws_answer(pc_points_scratch(N, B, G, R).total);
 }
 
 extern "C" int md_pc_augment_points(MD_AOT_ARGS) {
@@ -378,7 +375,7 @@ extern "C" int md_pc_augment_points(MD_AOT_ARGS) {
     Args a(MD_ARGS, 13, 14);
     a.tensor(0, F32, 2); a.tensor(1, I32, 1); a.tensor(2, F32, 3); a.tensor(3, I32, 1); a.tensor(4, U8, 2); a.tensor(5, F64, 3);
     a.optional(6, F32, 3); a.optional(7, I32, 1); a.optional(8, I32, 1); a.tensor(9, F64, 2);
-    a.tensor(10, F32, 2); a.tensor(11, I32, 1); a.tensor(12, I32, 1); a.optional(13, U8);
+    a.tensor(10, F32, 2); a.tensor(11, I32, 1); a.tensor(12, I32, 1); a.scratch(13);
     if (int rc = a.rc()) return rc;
     const int64_t N = a.d(0, 0), B = a.d(1, 0) - 1, G = a.d(2, 1);
     const bool rem = a.given(6);

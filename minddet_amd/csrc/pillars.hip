@@ -347,20 +347,20 @@ using namespace md;
 // offsets count i32 entries, total counts bytes.  first, cvox: [B cells]; cell, flag: [N]; pre: [N + 1]; cnt: [B MV]; start: [B MV + 1];
 // bsum: one entry per scan block of the longer of the two scans, and one more
 struct VoxScratch { int64_t first, cvox, cell, flag, pre, cnt, start, bsum, total; };
-static VoxScratch voxelize_scratch(int64_t N, int64_t B, int64_t cells, int64_t MV) {
-    const int64_t nbN = (N + PV_BLOCK - 1) / PV_BLOCK, nbV = (B * MV + PV_BLOCK - 1) / PV_BLOCK;
-    int64_t ints = 0;
-    auto take = [&](int64_t n) { const int64_t at = ints; ints += (n + 63) / 64 * 64; return at; };
+static VoxScratch voxelize_scratch(Sz N, Sz B, Sz cells, Sz MV) {
+    const Sz nbN = (N + (PV_BLOCK - 1)) / PV_BLOCK, nbV = (B * MV + (PV_BLOCK - 1)) / PV_BLOCK;
+    Sz ints = 0;
+    auto take = [&](Sz n) { const Sz at = ints; ints = ints + (n + 63) / 64 * 64; return (int64_t)at; };
     VoxScratch w;
     w.first = take(B * cells); w.cvox = take(B * cells);
     w.cell = take(N); w.flag = take(N); w.pre = take(N + 1);
     w.cnt = take(B * MV); w.start = take(B * MV + 1);
     w.bsum = take((nbN > nbV ? nbN : nbV) + 1);
-    w.total = ints * 4;
+    w.total = (int64_t)(ints * 4);
     return w;
 }
 extern "C" int64_t md_voxelize_workspace_bytes(int64_t N, int64_t B, int64_t cells, int64_t max_voxels) {
-    return any_negative({N, B, cells, max_voxels}) ? -1 : voxelize_scratch(N, B, cells, max_voxels).total;
+    return any_negative({N, B, cells, max_voxels}) ? -1 : ws_answer(voxelize_scratch(N, B, cells, max_voxels).total);
 }
 
 // in : points[N,F] f32, offsets[B+1] i32 ; out: voxels[B,MV,MP,F] f32, coors[B,MV,4] i32, num_points[B,MV] i32, voxel_num[B] i32
@@ -369,7 +369,7 @@ extern "C" int md_voxelize(MD_AOT_ARGS) {
     Args g(MD_ARGS, 6, 7);
     const md_voxelize_attrs *at = g.attrs<md_voxelize_attrs>(extra);
     g.tensor(0, F32, 2); g.tensor(1, I32, 1); g.tensor(2, F32, 4); g.tensor(3, I32, 3); g.tensor(4, I32, 2); g.tensor(5, I32, 1);
-    g.optional(6, U8);
+    g.scratch(6);
     if (int rc = g.rc()) return rc;
     const int64_t N = g.d(0, 0), F = g.d(0, 1), B = g.d(1, 0) - 1;
     const int64_t MV = g.d(2, 1), MP = g.d(2, 2);
@@ -389,7 +389,7 @@ extern "C" int md_voxelize(MD_AOT_ARGS) {
         grid[k] = (int)r;
     }
     const long long G = (long long)grid[0] * grid[1] * grid[2];
-    if (N >= (1 << 30) || G * (B > 0 ? B : 1) >= (1 << 30) || B * MV >= (1 << 30) || B > 4096) return MD_ERR_SIZE;
+    if (N >= (1 << 30) || mul({G, B > 0 ? B : 1}) >= (1 << 30) || mul({B, MV}) >= (1 << 30) || B > 4096) return MD_ERR_SIZE;
     if (MP > 65536) return MD_ERR_SIZE;
     if (B == 0) return MD_OK;
     if (!g.have({0, 1, 2, 3, 4, 5})) return MD_ERR_ARG;
@@ -456,7 +456,8 @@ extern "C" int md_pillar_encode(MD_AOT_ARGS) {
     if (two && (g.d(6, 0) != 64 || g.d(6, 1) != 64 || g.d(7, 0) != 64)) return MD_ERR_ARG;
     if (g.d(8, 0) != B || g.d(8, 3) != 64 || H < 0 || W < 0 || B < 0 || MV < 0 || MP < 0) return MD_ERR_ARG;
     if (MP > PE_MAX_POINTS) return MD_ERR_SIZE;
-    if (B * MV >= (1 << 30) || !fits_i32(B * MV * MP * F / 4) || H > 65536 || W > 65536 || !fits_i32(B * H * W / 4)) return MD_ERR_SIZE;
+    if (mul({B, MV}) >= (1 << 30) || !fits_i32(mul({B, MV, MP, F}) / 4) || H > 65536 || W > 65536 || !fits_i32(mul({B, H, W}) / 4))
+        return MD_ERR_SIZE;
     if (B * H * W == 0) return MD_OK;
     if (!g.have({0, 1, 2, 3, 4, 5, 8})) return MD_ERR_ARG;
     EncArgs a;

@@ -214,6 +214,7 @@ extern "C" int md_maxpool2d(MD_AOT_ARGS) {
     if (C % 8 || a.d(1, 3) != C || a.d(1, 0) != N || at->k < 1 || at->stride < 1 || at->pad < 0) return MD_ERR_ARG;
     if (Ho != (H + 2 * at->pad - at->k) / at->stride + 1 || Wo != (W + 2 * at->pad - at->k) / at->stride + 1)
         return MD_ERR_ARG;
+    if (a.numel(0) == INT64_MAX || a.numel(1) == INT64_MAX) return MD_ERR_SIZE;
     const size_t total = (size_t)N * Ho * Wo * (C / 8);
     if (total == 0) return MD_OK;
     if (!a.have({0, 1})) return MD_ERR_ARG;
@@ -241,11 +242,11 @@ extern "C" int md_sppf_pool(MD_AOT_ARGS) {
     const long long N = a.d(0, 0), H = a.d(0, 1), W = a.d(0, 2), Ctot = a.d(0, 3);
     const int C = at->channels, k = at->k;
     if (C < 8 || C % 8 || Ctot % 8 || Ctot < 4LL * C || k < 1 || k % 2 == 0) return MD_ERR_ARG;
-    if (N * H * W == 0) return MD_OK;
+    if (mul({N, H, W}) == 0) return MD_OK;
     if (!a.have({0})) return MD_ERR_ARG;
     if (H > 4096 || W > 4096) return MD_ERR_SIZE;
     const int cc = md_sppf_pool_groups((int)H, (int)W, C);
-    if (cc == 0 || !fits_i32(N * (C / 8 / cc))) return MD_ERR_SIZE;
+    if (cc == 0 || !fits_i32(mul({N, C / 8 / cc}))) return MD_ERR_SIZE;
     const int lds = (int)(H * W * cc * 64);
     if (ensure_dyn_lds((const void *)sppf_pool_kernel, lds) != MD_OK) return MD_ERR_HIP;
     hipLaunchKernelGGL(sppf_pool_kernel, dim3((unsigned)(N * (C / 8 / cc))), dim3(256), lds, (hipStream_t)stream, (uint16_t *)params[0], (int)H, (int)W, C,
@@ -257,10 +258,12 @@ extern "C" int md_sppf_pool(MD_AOT_ARGS) {
 extern "C" int md_upsample_add(MD_AOT_ARGS) {
     Args a(MD_ARGS, 3, 3);
     a.tensor(0, BF16, 4); a.tensor(1, BF16, 4); a.tensor(2, BF16, 4);
+    a.require(a.d(0, 3) % 8 == 0 && a.d(1, 0) == a.d(0, 0) && a.d(1, 3) == a.d(0, 3) && a.d(1, 1) >= 1 && a.d(1, 2) >= 1);
+    a.require(a.same_shape(2, 0));
+    if (int rc = a.rc()) return rc;
     const int N = (int)a.d(0, 0), H = (int)a.d(0, 1), W = (int)a.d(0, 2), C = (int)a.d(0, 3);
     const int Ht = (int)a.d(1, 1), Wt = (int)a.d(1, 2);
-    a.require(C % 8 == 0 && a.d(1, 0) == N && a.d(1, 3) == C && Ht >= 1 && Wt >= 1 && a.same_shape(2, 0));
-    if (int rc = a.rc()) return rc;
+    if (a.numel(0) == INT64_MAX || a.numel(1) == INT64_MAX) return MD_ERR_SIZE;
     const size_t total = (size_t)N * H * W * (C / 8);
     if (total == 0) return MD_OK;
     if (!a.have({0, 1, 2})) return MD_ERR_ARG;
@@ -301,6 +304,7 @@ static int slice_write_impl(MD_AOT_ARGS, int up) {
     if (a.d(1, 0) != N || H != Hs * up || W != Ws * up || C < 8 || C % 8 || Cs % 8 || Ctot % 8 || at->c0 % 8 || at->c0 < 0 || sc0 % 8 || sc0 < 0 ||
         at->width != C || at->c0 + C > Ctot || sc0 + C > Cs)
         return MD_ERR_ARG;
+    if (a.numel(0) == INT64_MAX || a.numel(1) == INT64_MAX) return MD_ERR_SIZE;
     const size_t total = (size_t)N * H * W * (C / 8);
     if (total == 0) return MD_OK;
     if (!a.have({0, 1})) return MD_ERR_ARG;

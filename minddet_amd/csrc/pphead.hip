@@ -128,7 +128,7 @@ extern "C" int md_pp_scores(MD_AOT_ARGS) {
     const int64_t N = H * W * A;
     if (g.d(2, 0) != B || g.d(2, 1) != N || g.d(3, 0) != B || g.d(3, 1) != N) return MD_ERR_ARG;
     if (g.given(1) && (g.d(1, 0) != B || g.d(1, 1) != N)) return MD_ERR_ARG;
-    if (!fits_i32(N) || !fits_i32(B * N) || !fits_i32(B * H * W * C)) return MD_ERR_SIZE;
+    if (!fits_i32(N) || !fits_i32(mul({B, N})) || !fits_i32(mul({B, H, W, C}))) return MD_ERR_SIZE;
     if (B * N == 0) return MD_OK;
     if (!g.have({0, 2, 3})) return MD_ERR_ARG;
     PPScoreArgs a;
@@ -164,7 +164,7 @@ extern "C" int md_pp_decode_selected(MD_AOT_ARGS) {
         g.d(8, 1) != k)
         return MD_ERR_ARG;
     if (g.given(9) && (g.d(9, 0) != B || g.d(9, 1) != k || g.d(9, 2) != 7)) return MD_ERR_ARG;
-    if (!fits_i32(N * 7) || !fits_i32(B * N) || !fits_i32(B * k * 9) || !fits_i32(B * H * W * C)) return MD_ERR_SIZE;
+    if (!fits_i32(mul({N, 7})) || !fits_i32(mul({B, N})) || !fits_i32(mul({B, k, 9})) || !fits_i32(mul({B, H, W, C}))) return MD_ERR_SIZE;
     if (B * k == 0) return MD_OK;
     if (!g.have({0, 1, 2, 3, 4, 5, 6, 7, 8})) return MD_ERR_ARG;
     PPDecodeArgs a;

@@ -196,13 +196,10 @@ __global__ __launch_bounds__(256) void pp_loss_finish_kernel(const double *__res
 // scratch of md_pp_loss and md_pp_loss_grad: part[B sps][PPL_Q] f64 at 0, then counts[B][cps] i32; sps = the strips of PPL_STRIP cells,
 // cps = the chunks of PPL_CHUNK labels per sample
 struct PplScratch { int64_t sps, cps, counts, total; };
-static PplScratch pp_loss_scratch(int64_t B, int64_t H, int64_t W, int64_t A) {
-    PplScratch w;
-    w.sps = (H * W + PPL_STRIP - 1) / PPL_STRIP;
-    w.cps = (H * W * A + PPL_CHUNK - 1) / PPL_CHUNK;
-    w.counts = 8 * PPL_Q * B * w.sps;
-    w.total = w.counts + 4 * B * w.cps;
-    return w;
+static PplScratch pp_loss_scratch(Sz B, Sz H, Sz W, Sz A) {
+    const Sz sps = (H * W + (PPL_STRIP - 1)) / PPL_STRIP, cps = (H * W * A + (PPL_CHUNK - 1)) / PPL_CHUNK;
+    const Sz counts = 8 * PPL_Q * B * sps, total = counts + 4 * B * cps;
+    return {(int64_t)sps, (int64_t)cps, (int64_t)counts, (int64_t)total};
 }
 
 static int pp_loss_entry(MD_AOT_ARGS, bool with_grad) {
@@ -214,7 +211,7 @@ static int pp_loss_entry(MD_AOT_ARGS, bool with_grad) {
     a.tensor(0, BF16, 4); a.tensor(1, I32, 2); a.tensor(2, F32, 3); a.tensor(3, F32, 2);
     a.tensor(4, F32, 1); a.tensor(5, F32, 1); a.tensor(6, F32, 1);
     if (with_grad) a.tensor(7, F32, 4);
-    a.optional(WS, U8);
+    a.scratch(WS);
     if (int rc = a.rc()) return rc;
     const int64_t B = a.d(0, 0), H = a.d(0, 1), W = a.d(0, 2), C = a.d(0, 3);
     const md_pp_head_attrs &h = at->head;
@@ -229,7 +226,7 @@ static int pp_loss_entry(MD_AOT_ARGS, bool with_grad) {
     heads_disjoint(a, lo, hi, dir ? 3 : 2, C);
     if (int rc = a.rc()) return rc;
     const int64_t lim = (int64_t)1 << 30;
-    const bool big = B >= lim || HW >= lim || HW * A >= lim;   // N itself past the limit: the extents below cannot be compared safely
+    const bool big = B >= lim || HW >= lim || mul({HW, A}) >= lim;   // N itself past the limit: the extents below cannot be compared safely
     const int64_t N = big ? 0 : HW * A;
     if (!big) {
         a.require(a.d(1, 0) == B && a.d(1, 1) == N && a.d(2, 0) == B && a.d(2, 1) == N && a.d(2, 2) == 7 && a.d(3, 0) == N && a.d(3, 1) == 7);
@@ -282,7 +279,7 @@ static int pp_loss_entry(MD_AOT_ARGS, bool with_grad) {
 using namespace md;
 
 extern "C" int64_t md_pp_loss_workspace_bytes(int64_t B, int64_t H, int64_t W, int64_t num_anchors) {
-    return any_negative({B, H, W, num_anchors}) ? -1 : pp_loss_scratch(B, H, W, num_anchors).total;
+    return any_negative({B, H, W, num_anchors}) ? -1 : ws_answer(pp_loss_scratch(B, H, W, num_anchors).total);
 }
 extern "C" int md_pp_loss(MD_AOT_ARGS) { return pp_loss_entry(nparam, params, ndims, shapes, dtypes, stream, extra, false); }
 extern "C" int md_pp_loss_grad(MD_AOT_ARGS) { return pp_loss_entry(nparam, params, ndims, shapes, dtypes, stream, extra, true); }

@@ -266,7 +266,8 @@ extern "C" int md_pp_pillar_encode(MD_AOT_ARGS) {
     if (g.d(4, 0) != 64 || g.d(5, 0) != 64 || g.d(6, 0) != 64) return MD_ERR_ARG;
     if (g.d(7, 0) != B || g.d(7, 3) != 64 || H < 0 || W < 0 || B < 0 || MV < 0 || MP < 0) return MD_ERR_ARG;
     if (MP > 32) return MD_ERR_SIZE;
-    if (B * MV >= (1 << 30) || !fits_i32(B * MV * MP) || H > 65536 || W > 65536 || !fits_i32(B * H * W / 4)) return MD_ERR_SIZE;
+    if (mul({B, MV}) >= (1 << 30) || !fits_i32(mul({B, MV, MP})) || H > 65536 || W > 65536 || !fits_i32(mul({B, H, W}) / 4))
+        return MD_ERR_SIZE;
     if (B * H * W == 0) return MD_OK;
     if (!g.have({0, 1, 2, 3, 4, 5, 6, 7})) return MD_ERR_ARG;
     PPEncArgs a;
@@ -286,7 +287,7 @@ extern "C" int md_pp_pillar_encode(MD_AOT_ARGS) {
 
 // scratch of md_pp_anchor_mask: one i32 per cell of every sample's grid, [B][grid_y][grid_x]
 extern "C" int64_t md_pp_anchor_mask_workspace_bytes(int64_t B, int64_t grid_x, int64_t grid_y) {
-    return any_negative({B, grid_x, grid_y}) ? -1 : B * grid_y * grid_x * 4;
+    return any_negative({B, grid_x, grid_y}) ? -1 : ws_answer((int64_t)(Sz(B) * grid_y * grid_x * 4));
 }
 
 // in : coors[B,MV,4] i32, voxel_num[B] i32, anchors_bv[N,4] f32 ; out: mask[B,N] u8 [, area[B,N] f32 or NULL] [, workspace u8].
@@ -300,8 +301,8 @@ extern "C" int md_pp_anchor_mask(MD_AOT_ARGS) {
     if (B < 0 || MV < 0 || n < 0 || g.d(0, 2) != 4 || g.d(1, 0) != B || g.d(2, 1) != 4 || g.d(3, 0) != B || g.d(3, 1) != n) return MD_ERR_ARG;
     if (g.given(4) && (g.d(4, 0) != B || g.d(4, 1) != n)) return MD_ERR_ARG;
     const int nx = at->grid_x, ny = at->grid_y;
-    if (nx < 1 || ny < 1 || (int64_t)nx * ny * (B > 0 ? B : 1) > (1 << 28)) return MD_ERR_SIZE;
-    if (!fits_i32(B * n) || !fits_i32(B * MV)) return MD_ERR_SIZE;
+    if (nx < 1 || ny < 1 || mul({nx, ny, B > 0 ? B : 1}) > (1 << 28)) return MD_ERR_SIZE;
+    if (!fits_i32(mul({B, n})) || !fits_i32(mul({B, MV}))) return MD_ERR_SIZE;
     if (B == 0) return MD_OK;
     if ((MV > 0 && !g.have({0})) || !g.have({1}) || (n > 0 && !g.have({2, 3}))) return MD_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;

@@ -301,10 +301,10 @@ extern "C" int md_pw_chain(MD_AOT_ARGS) {
     for (int i : {1, 6, 7}) g.require(g.d(i, 0) == N && g.d(i, 1) == H && g.d(i, 2) == W);
     g.require(N >= 0 && H >= 0 && W >= 0);
     if (int rc = g.rc()) return rc;
-    if (N * H * W == 0) return MD_OK;
+    if (mul({N, H, W}) == 0) return MD_OK;
     if (!g.have({0, 1, 2, 3, 4, 5, 6, 7})) return MD_ERR_ARG;
-    if (!fits_i32(N) || !fits_i32(H) || !fits_i32(W) || !fits_i32(N * H) || !fits_i32(N * H * W)) return MD_ERR_SIZE;
-    const long long M = N * H * W;
+    if (!fits_i32(N) || !fits_i32(H) || !fits_i32(W) || !fits_i32(mul({N, H})) || !fits_i32(mul({N, H, W}))) return MD_ERR_SIZE;
+    const long long M = mul({N, H, W});
     // the outputs overlap neither an input nor each other
     const long long nb[8] = {M * 256, M * 1024, 0, 0, 0, 0, M * 1024, M * 256};
     for (int o : {6, 7})

@@ -202,13 +202,13 @@ extern "C" int md_stem_pool(MD_AOT_ARGS) {
     if (g.d(3, 0) != a.N || g.d(3, 1) != a.Hq || g.d(3, 2) != a.Wq) return MD_ERR_ARG;
     if (a.N == 0) return MD_OK;
     if (!g.have({0, 3})) return MD_ERR_ARG;
-    const long long x_bytes = (long long)a.N * a.Hp * a.Wp * 8;
+    const long long x_bytes = mul({a.N, a.Hp, a.Wp, 8});
     if (x_bytes >= 0x7fff0000LL) return MD_ERR_SIZE;
     a.x = (const uint16_t *)params[0]; a.w = (const uint16_t *)params[1]; a.bias = (const float *)params[2];
     a.y = (uint16_t *)params[3];
     a.x_bytes = (unsigned)x_bytes;
     a.tiles_x = a.Wq / ST_TPW; a.tiles_y = a.Hq / ST_TPH;
-    const long long n_tiles = (long long)a.N * a.tiles_x * a.tiles_y;
+    const long long n_tiles = mul({a.N, a.tiles_x, a.tiles_y});
     if (!fits_i32(n_tiles)) return MD_ERR_SIZE;
     a.n_tiles = (int)n_tiles;
     if (ensure_dyn_lds((const void *)stem_pool_kernel, ST_LDS) != MD_OK) return MD_ERR_HIP;

@@ -141,10 +141,9 @@ static int launch_stem_conv(StemConvArgs &a, hipStream_t s) {
     constexpr int PR = 2 * SC_TH + KH - 2;
     constexpr int PATCH_ALLOC = ((PR * SC_ROWB / 16 + 63) / 64) * 1024;
     const int lds = PATCH_ALLOC + SC_TH * SC_TW * (COUT * 2 + 16);
-    auto k = stem_conv_kernel<KH, COUT>;
-    if (lds > 64 * 1024 && ensure_dyn_lds((const void *)k, lds) != MD_OK) return MD_ERR_HIP;
+    if (lds > 64 * 1024 && ensure_dyn_lds((const void *)stem_conv_kernel<KH, COUT>, lds) != MD_OK) return MD_ERR_HIP;
     const int grid = a.n_tiles < 256 * 3 ? a.n_tiles : 256 * 3;   // persistent: up to three workgroups per CU
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(256), lds, s, a);
+    hipLaunchKernelGGL((stem_conv_kernel<KH, COUT>), dim3((unsigned)grid), dim3(256), lds, s, a);
     return launched();
 }
 
@@ -172,14 +171,14 @@ extern "C" int md_stem_conv(MD_AOT_ARGS) {
     if (g.d(3, 0) != a.N || g.d(3, 1) != a.Ho || g.d(3, 2) != a.Wo) return MD_ERR_ARG;
     if (a.N == 0) return MD_OK;
     if (!g.have({0, 3})) return MD_ERR_ARG;
-    const long long x_bytes = (long long)a.N * a.Hp * a.Wp * 8;
+    const long long x_bytes = mul({a.N, a.Hp, a.Wp, 8});
     if (x_bytes >= 0x7fff0000LL) return MD_ERR_SIZE;
     a.x = (const uint16_t *)params[0]; a.w = (const uint16_t *)params[1]; a.bias = (const float *)params[2];
     a.y = (uint16_t *)params[3];
     a.x_bytes = (unsigned)x_bytes;
     a.act = at->act;
     a.tiles_x = a.Wo / SC_TW; a.tiles_y = a.Ho / SC_TH;
-    const long long n_tiles = (long long)a.N * a.tiles_x * a.tiles_y;
+    const long long n_tiles = mul({a.N, a.tiles_x, a.tiles_y});
     if (!fits_i32(n_tiles)) return MD_ERR_SIZE;
     a.n_tiles = (int)n_tiles;
     hipStream_t s = (hipStream_t)stream;

@@ -132,7 +132,7 @@ extern "C" int md_assign_targets(MD_AOT_ARGS) {
     const int64_t A = a.d(0, 0), G = a.given(1) ? a.d(1, 0) : 0;
     if (G > 0) { a.tensor(1, F32, 2); a.tensor(2, I32); }
     a.require(A >= 0 && G >= 0 && a.d(0, 1) == 7 && (G == 0 || a.d(1, 1) == 7));
-    a.require(a.numel(3) == A && a.numel(4) == A && a.numel(6) == A && a.numel(7) == A * 7 && a.numel(8) == A && a.numel(9) == A &&
+    a.require(a.numel(3) == A && a.numel(4) == A && a.numel(6) == A && a.numel(7) == mul({A, 7}) && a.numel(8) == A && a.numel(9) == A &&
               (G == 0 || a.numel(2) == G) && (!a.given(5) || a.numel(5) == A));
     if (int rc = a.rc()) return rc;
     if (A == 0) return MD_OK;

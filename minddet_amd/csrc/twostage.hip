@@ -187,15 +187,17 @@ extern "C" int md_rpn_decode(MD_AOT_ARGS) {
     const md_rpn_decode_attrs *at = a.attrs<md_rpn_decode_attrs>(extra);
     a.tensor(0, BF16, 4); a.tensor(1, F32); a.tensor(2, I32, 2); a.tensor(3, I32); a.tensor(4, F32); a.tensor(5, F32);
     if (int rc = a.rc()) return rc;
-    const int B = (int)a.d(0, 0), HW = (int)(a.d(0, 1) * a.d(0, 2)), Cp = (int)a.d(0, 3);
-    const int k = (int)a.d(2, 1), A = at->num_anchors;
-    if (a.d(2, 0) != B || A < 1 || 5 * A > Cp || a.numel(1) != (int64_t)HW * A * 4) return MD_ERR_ARG;
-    if (a.numel(4) != (int64_t)B * k * 4 || a.numel(5) != (int64_t)B * k || a.numel(3) < B) return MD_ERR_ARG;
-    if (B * k == 0) return MD_OK;
+    const int64_t hw = mul({a.d(0, 1), a.d(0, 2)}), Cp64 = a.d(0, 3), total = mul({a.d(0, 0), a.d(2, 1)});     // total: B k
+    const int A = at->num_anchors;
+    if (a.d(2, 0) != a.d(0, 0) || A < 1 || 5 * (int64_t)A > Cp64 || a.numel(1) != mul({hw, A, 4})) return MD_ERR_ARG;
+    if (a.numel(4) != mul({total, 4}) || a.numel(5) != total || a.numel(3) < a.d(0, 0)) return MD_ERR_ARG;
+    if (total == 0) return MD_OK;
     if (!a.have({0, 1, 2, 3, 4, 5})) return MD_ERR_ARG;
+    if (!fits_i32(add(total, 255)) || !fits_i32(mul({hw, A}))) return MD_ERR_SIZE;      // the kernel counts items and anchors in int
+    const int B = (int)a.d(0, 0), HW = (int)hw, Cp = (int)Cp64, k = (int)a.d(2, 1);
     DecodeP p;
     fill_decode(p, at->decode);
-    hipLaunchKernelGGL(rpn_decode_kernel, dim3((B * k + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(rpn_decode_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        (const uint16_t *)params[0], (const float *)params[1], (const int *)params[2], (const int *)params[3],
                        B, k, HW, A, Cp, p, (float *)params[4], (float *)params[5]);
     return launched();
@@ -205,11 +207,12 @@ extern "C" int md_rpn_merge(MD_AOT_ARGS) {
     // in: boxes[L,B,k,4] f32, scores[L,B,k] f32, keep[L,B,k] u8 ; out: mboxes[B,L*k,4] f32, mscores[B,L*k] f32
     Args a(MD_ARGS, 5, 5);
     a.tensor(0, F32); a.tensor(1, F32, 3); a.tensor(2, U8); a.tensor(3, F32); a.tensor(4, F32);
-    const int L = (int)a.d(1, 0), B = (int)a.d(1, 1), k = (int)a.d(1, 2);
-    const int64_t tot = (int64_t)L * B * k;
-    a.require(a.numel(0) == tot * 4 && a.numel(2) == tot && a.numel(3) == tot * 4 && a.numel(4) == tot);
+    const int64_t tot = a.numel(1);
+    a.require(a.numel(0) == mul({tot, 4}) && a.numel(2) == tot && a.numel(3) == mul({tot, 4}) && a.numel(4) == tot);
     if (int rc = a.rc()) return rc;
     if (tot == 0) return MD_OK;
+    if (!md::fits_i32((tot + 255) / 256)) return MD_ERR_SIZE;      // the grid; every extent fits int (rc() above)
+    const int L = (int)a.d(1, 0), B = (int)a.d(1, 1), k = (int)a.d(1, 2);
     if (!a.have({0, 1, 2, 3, 4})) return MD_ERR_ARG;
     hipLaunchKernelGGL(rpn_merge_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        (const float *)params[0], (const float *)params[1], (const unsigned char *)params[2], L, B, k,
@@ -221,13 +224,16 @@ extern "C" int md_make_rois(MD_AOT_ARGS) {
     // in: mboxes[B,P,4] f32, topv[B,post] f32, topi[B,post] i32, cnt[B] i32 ; out: rois[B*post,5] f32, scores[B*post] f32
     Args a(MD_ARGS, 6, 6);
     a.tensor(0, F32, 3); a.tensor(1, F32, 2); a.tensor(2, I32); a.tensor(3, I32); a.tensor(4, F32); a.tensor(5, F32);
-    const int B = (int)a.d(0, 0), per = (int)a.d(0, 1), post = (int)a.d(1, 1);
-    a.require(a.d(1, 0) == B && a.numel(4) == (int64_t)B * post * 5 && a.numel(5) == (int64_t)B * post);
-    a.require(a.numel(0) >= (int64_t)B * per * 4 && a.numel(2) >= (int64_t)B * post && a.numel(3) >= B);
+    const int64_t total = a.numel(1);      // B post
+    a.require(a.d(1, 0) == a.d(0, 0) && a.numel(4) == mul({total, 5}) && a.numel(5) == total);
+    a.require(a.numel(2) >= total && a.numel(3) >= a.d(0, 0));
+    a.require(mul({a.d(0, 0), a.d(0, 1)}) == 0 || a.d(0, 2) >= 4);      // numel(0) >= B P 4, of a rank-3 operand
     if (int rc = a.rc()) return rc;
-    if (B * post == 0) return MD_OK;
+    if (total == 0) return MD_OK;
     if (!a.have({0, 1, 2, 3, 4, 5})) return MD_ERR_ARG;
-    hipLaunchKernelGGL(make_rois_kernel, dim3((B * post + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+    if (!fits_i32(total + 255)) return MD_ERR_SIZE;      // the kernel counts its items in int
+    const int B = (int)a.d(0, 0), per = (int)a.d(0, 1), post = (int)a.d(1, 1);
+    hipLaunchKernelGGL(make_rois_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        (const float *)params[0], (const float *)params[1], (const int *)params[2], (const int *)params[3],
                        B, post, per, (float *)params[4], (float *)params[5]);
     return launched();
@@ -257,14 +263,16 @@ extern "C" int md_rcnn_decode_selected(MD_AOT_ARGS) {
     const md_rcnn_attrs *at = a.attrs<md_rcnn_attrs>(extra);
     a.tensor(0, BF16, 2); a.tensor(1, F32); a.tensor(2, I32, 2); a.tensor(3, I32); a.tensor(4, F32); a.tensor(5, I32);
     if (int rc = a.rc()) return rc;
-    const int R = (int)a.d(0, 0), Cp = (int)a.d(0, 1), B = (int)a.d(2, 0), npre = (int)a.d(2, 1);
-    if (B < 1 || R % B || at->reg_offset + 4 * at->num_classes > Cp) return MD_ERR_ARG;
-    if (a.numel(4) != (int64_t)B * npre * 4 || a.numel(5) != (int64_t)B * npre || a.numel(1) < (int64_t)R * 5 || a.numel(3) < B) return MD_ERR_ARG;
-    if (B * npre == 0) return MD_OK;
+    const int R = (int)a.d(0, 0), Cp = (int)a.d(0, 1), B = (int)a.d(2, 0), npre = (int)a.d(2, 1);      // (rc() above: each fits int)
+    const int64_t total = a.numel(2);      // B npre
+    if (B < 1 || R % B || at->reg_offset + 4 * (int64_t)at->num_classes > Cp) return MD_ERR_ARG;
+    if (a.numel(4) != mul({total, 4}) || a.numel(5) != total || a.numel(1) < (int64_t)R * 5 || a.numel(3) < B) return MD_ERR_ARG;
+    if (total == 0) return MD_OK;
     if (!a.have({0, 1, 2, 3, 4, 5})) return MD_ERR_ARG;
+    if (!fits_i32(total + 255)) return MD_ERR_SIZE;      // the kernel counts its items in int
     DecodeP p;
     fill_decode(p, at->decode);
-    hipLaunchKernelGGL(rcnn_decode_selected_kernel, dim3((B * npre + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(rcnn_decode_selected_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        (const uint16_t *)params[0], (const float *)params[1], (const int *)params[2], (const int *)params[3],
                        B, npre, R / B, at->num_classes, Cp, at->reg_offset, p, (float *)params[4], (int *)params[5]);
     return launched();
@@ -277,20 +285,21 @@ extern "C" int md_pack_detections(MD_AOT_ARGS) {
     a.require(nparam != 8, MD_ERR_NPARAM);
     const int o = nparam == 9 ? 6 : 5;   // index of dets
     a.tensor(0, F32); a.tensor(1, F32, 2); a.tensor(2, I32); a.tensor(3, I32); a.tensor(4, I32); a.tensor(o, F32, 3); a.tensor(o + 1, I32);
-    const int B = (int)a.d(1, 0), npre = (int)a.d(1, 1), max_det = (int)a.d(o, 1);
-    a.require(a.d(o, 0) == B && a.d(o, 2) == 6);
-    a.require(a.numel(0) >= (int64_t)B * npre * 4 && a.numel(2) >= (int64_t)B * npre && a.numel(3) >= (int64_t)B * npre && a.numel(4) >= B &&
-              a.numel(o + 1) >= B);
+    a.require(a.d(o, 0) == a.d(1, 0) && a.d(o, 2) == 6);
+    a.require(a.numel(0) >= md::mul({a.numel(1), 4}) && a.numel(2) >= a.numel(1) && a.numel(3) >= a.numel(1) && a.numel(4) >= a.d(1, 0) &&
+              a.numel(o + 1) >= a.d(1, 0));
     if (nparam == 9) {
         a.tensor(5, I32); a.tensor(8, I32);
-        a.require(a.numel(5) == B && a.numel(8) == B);
-        if (B > 0) a.have({5, 8});
+        a.require(a.numel(5) == a.d(1, 0) && a.numel(8) == a.d(1, 0));
+        if (a.d(1, 0) > 0) a.have({5, 8});
     }
     if (int rc = a.rc()) return rc;
+    const int B = (int)a.d(1, 0), npre = (int)a.d(1, 1), max_det = (int)a.d(o, 1);
     const int *sel_cnt = nparam == 9 ? a.ptr<const int>(5) : nullptr;
     int *status = nparam == 9 ? a.ptr<int>(8) : nullptr;
-    if (B * max_det == 0) return MD_OK;
+    if (md::mul({B, max_det}) == 0) return MD_OK;
     if (!a.have({0, 1, 2, 3, 4, o, o + 1})) return MD_ERR_ARG;
+    if (!md::fits_i32(md::mul({B, max_det}) + 255)) return MD_ERR_SIZE;     // the grid arithmetic below is int
     hipLaunchKernelGGL(pack_dets_kernel, dim3((B * max_det + 255) / 256), dim3(256), 0, (hipStream_t)stream,
                        (const float *)params[0], (const float *)params[1], (const int *)params[2], (const int *)params[3],
                        (const int *)params[4], B, npre, max_det, (float *)params[o], (int *)params[o + 1], sel_cnt, status);
@@ -327,8 +336,9 @@ extern "C" int md_mask_select(MD_AOT_ARGS) {
     if (int rc = a.rc()) return rc;
     const int64_t R = a.d(0, 0), S = a.d(0, 1), C = a.d(0, 3);
     const int nc = *num_classes;
-    if (a.d(0, 2) != S || nc < 1 || nc > C || a.numel(1) != R * 6 || a.numel(2) != R * S * S) return MD_ERR_ARG;
-    if (R * S * S == 0) return MD_OK;
+    if (a.d(0, 2) != S || nc < 1 || nc > C || a.numel(1) != md::mul({R, 6}) || a.numel(2) != md::mul({R, S, S})) return MD_ERR_ARG;
+    if (md::mul({R, S, S}) == 0) return MD_OK;
+    if (!md::fits_i32(S * S)) return MD_ERR_SIZE;      // the kernel takes S * S as an int
     if (!a.have({0, 1, 2})) return MD_ERR_ARG;
     const size_t total = (size_t)R * S * S;
     const size_t nb = (total + 255) / 256;

@@ -9,118 +9,13 @@ import pytest
 
 from minddet_amd import _lib
 from tests.abi_cases import CASES
-
-ITEM = {"float32": 4, "bfloat16": 2, "int32": 4, "int64": 8, "uint8": 1}
-WRONG_DTYPE = b"float64"    # no operand of any op is float64
+from tests.abi_derive import ITEM, WRONG_DTYPE, Call, _numel, mutations, rank_defects  # noqa: F401 (other tests import them from here)
 
 
 def aot_symbols():
     hdr = open(_lib.LIB_PATH.replace("minddet_amd/" + _lib.LIB_PATH.split("/")[-1], "include/minddet_hip.h")).read()
     aot = set(re.findall(r"^\s*int\s+(\w+)\s*\(MD_AOT_ARGS\)\s*;", hdr, flags=re.M))
     return [n for n in _lib.exported_symbols() if n in aot]
-
-
-class Call:
-    """the C arrays of one call; every field can be replaced before `run`"""
-
-    def __init__(self, case):
-        self.case = case
-        ops = case.operands
-        self.n = len(ops)
-        self.shapes = [list(t.shape) for t in ops]
-        self.dtypes = [None if t.null else t.dtype.encode() for t in ops]
-        self.null_ptr = [t.null for t in ops]
-        self.null_shape = [False] * self.n
-        self.params_null = self.ndims_null = self.shapes_null = self.dtypes_null = self.extra_null = False
-
-    def run(self, lib):
-        n = self.n
-        # one host block per operand, disjoint and as large as the tensor (md_c3_pair / md_conv2d_grouped compare address ranges)
-        sizes = [max(64, ITEM[t.dtype] * max(1, _numel(t.shape)) + 64) for t in self.case.operands] + [64] * (n - len(self.case.operands))
-        arena = (C.c_char * sum(sizes))()
-        base, off = C.addressof(arena), 0
-        params = (C.c_void_p * n)()
-        ndims = (C.c_int * n)()
-        shapes = (C.POINTER(C.c_int64) * n)()
-        dtypes = (C.c_char_p * n)()
-        keep = []
-        for i in range(n):
-            described = i < len(self.shapes)
-            null = described and self.null_ptr[i]
-            params[i] = None if null else base + off
-            off += sizes[i]
-            shp = ([] if self.case.operands[i].null else self.shapes[i]) if described else [64]
-            ndims[i] = len(shp)
-            buf = (C.c_int64 * max(len(shp), 1))(*shp)
-            keep.append(buf)
-            shapes[i] = None if (described and self.null_shape[i]) else C.cast(buf, C.POINTER(C.c_int64))
-            dtypes[i] = self.dtypes[i] if described else b"uint8"
-        extra = None if (self.case.extra is None or self.extra_null) else C.byref(self.case.extra)
-        return getattr(lib, self.case.sym)(n, None if self.params_null else params, None if self.ndims_null else ndims,
-                                           None if self.shapes_null else shapes, None if self.dtypes_null else dtypes, None, extra)
-
-
-def _numel(shape):
-    n = 1
-    for d in shape:
-        n *= d
-    return n
-
-
-def rank_defects(t):
-    """the shapes a rank +- 1 defect of operand t gives, per abi_cases' `rank` kinds"""
-    if t.kind == "loose" or t.rank == "free":
-        return []
-    out = [("rank-1", list(t.shape[:-1]))]
-    if t.rank == "exact":
-        out.append(("rank+1", list(t.shape) + [2]))
-    return out
-
-
-def mutations(case):
-    """-> [(kind, operand index or None, Call, expected rc)]"""
-    out = []
-    lo, hi = min(case.nparam), max(case.nparam)
-    for n in sorted({lo - 1, hi + 1} | {k for k in range(lo, hi) if k not in case.nparam}):
-        c = Call(case)
-        c.n = n
-        if n < len(case.operands):
-            c.shapes, c.dtypes, c.null_ptr, c.null_shape = c.shapes[:n], c.dtypes[:n], c.null_ptr[:n], c.null_shape[:n]
-        out.append(("nparam", None, c, 1))
-    for field in ("params_null", "ndims_null", "shapes_null"):
-        c = Call(case)
-        setattr(c, field, True)
-        out.append((field, None, c, 2))
-    if case.extra_required:
-        c = Call(case)
-        c.extra_null = True
-        out.append(("extra_null", None, c, 2))
-    first_rank = True
-    for i, t in enumerate(case.operands):
-        if t.null:
-            continue            # an optional operand the valid row leaves out: nothing about it is looked at
-        if t.kind == "req":
-            c = Call(case)
-            c.null_shape[i] = True
-            out.append(("shape_null", i, c, 2))
-        if t.kind != "opt":
-            c = Call(case)
-            c.null_ptr[i] = True
-            out.append(("ptr_null", i, c, 2))
-        c = Call(case)
-        c.dtypes[i] = WRONG_DTYPE
-        out.append(("dtype", i, c, 2))
-        for kind, shp in rank_defects(t):
-            c = Call(case)
-            c.shapes[i] = shp
-            out.append((kind, i, c, 2))
-            if first_rank:      # an undescribed dtype passes: the same rank defect with dtypes == NULL is still refused by the rank
-                first_rank = False
-                c = Call(case)
-                c.shapes[i] = shp
-                c.dtypes_null = True
-                out.append(("rank_without_dtypes", i, c, 2))
-    return out
 
 
 def test_table_has_a_row_for_every_declared_symbol():

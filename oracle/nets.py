@@ -316,22 +316,6 @@ def mask_head_forward(mh, feats, dets, quant=False):
     return out.reshape(B, D, 2 * mh.P, 2 * mh.P)
 
 
-def centernet_features(model, x, quant=False):
-    """centernet/src/centernet_det.py:162-174 with the UNFUSED heads (three 3x3 + three 1x1 convs)."""
-    f = resnet_forward(model.backbone, x, quant)[-1]
-    for m in model.neck:
-        if hasattr(m, "weight_t"):
-            f = deconv_module(m, f, quant)
-        elif hasattr(m, "offset_weight"):
-            f = deform_conv_module(m, f, quant)
-        else:
-            f = conv_module(m, f, quant=quant)
-    out = {}
-    for name, (c1, c2) in model.heads.items():
-        out[name] = conv_module(c2, conv_module(c1, f, quant=quant), quant=quant)
-    return out
-
-
 def rpn_neck_forward(neck, x, quant=False):
     ups = []
     for i, blk in enumerate(neck.blocks):

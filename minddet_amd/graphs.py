@@ -119,8 +119,16 @@ class Module:
     without any is a leaf and packs its own parameters in `_derive`.  `to(device)` is the one place packs are made: it packs the
     children, then `_derive(device)` builds every pack that is derived from theirs (fused blocks, merged convs, stem forms) into plain
     attributes -- so the call that repacks a conv also rebuilds what was made from it -- empties the device constants and advances
-    the process-wide pack generation SplitForward keys its priming pass on."""
+    the process-wide pack generation SplitForward keys its priming pass on.
+    A module whose packs are trained holds their trainer (an optim head trainer; `_head_trainer` makes, returns and replaces it) as
+    `_trainer`, because the trainer's buffers are derived from those packs too: to() first has it write its fp32 masters back into
+    the modules (sync_modules(): they are the source of truth of a repack), then lets `_refresh()` rebuild the children's weights
+    that derive from other modules, packs the children, `_derive`s, and last binds the trainer to the new packs (bind(): masters,
+    moments and powers kept).  A direct `_derive` call binds nothing.
+    `_lazy(name, build)` keeps an operator that is built on first use (a loss, an augmentation) on the instance; to() leaves those."""
     generation = 0
+    _trainer = None
+    TRAIN_CFG_HINT = ""      # where a training config of this class is found: the end of _train_cfg's message
 
     def children(self):
         return []
@@ -133,12 +141,20 @@ class Module:
     conv_modules = modules
 
     def to(self, device):
+        if self._trainer is not None:
+            self._trainer.sync_modules()
+        self._refresh()
         for c in self.children():
             c.to(device)
         self._derive(device)
+        if self._trainer is not None:
+            self._trainer.bind()
         self._consts = {}
         Module.generation += 1
         return self
+
+    def _refresh(self):
+        pass
 
     def _derive(self, device):
         pass
@@ -148,6 +164,30 @@ class Module:
         if key not in self._consts:
             self._consts[key] = build()
         return self._consts[key]
+
+    def _lazy(self, name, build):
+        ops = self.__dict__.setdefault("_ops", {})
+        if name not in ops:
+            ops[name] = build()
+        return ops[name]
+
+    def _train_cfg(self, key):
+        if not self.train_cfg or key not in self.train_cfg:
+            raise ValueError(f"{type(self).__name__}: train_cfg[{key!r}] is needed for training (see {self.TRAIN_CFG_HINT})")
+        return self.train_cfg[key]
+
+    def _head_trainer(self, cls, model, optimizer_cfg, fallback, rederive):
+        """The one trainer of this module's packs, cls(model, config): without an optimizer_cfg the existing one, or the first, made
+        with `fallback`; with one a new trainer (fresh moments) in place of the existing one, which first leaves its masters in the
+        modules and lets go of the packs (it keeps its own buffers and step count), `rederive()` then rebuilding this module's packs
+        from the modules on their device."""
+        if optimizer_cfg is None and self._trainer is not None:
+            return self._trainer
+        if self._trainer is not None:
+            self._trainer.sync_modules()
+            self._trainer = None
+            rederive()
+        return cls(model, optimizer_cfg if optimizer_cfg is not None else fallback)
 
 
 def _segments(B, n, device):
@@ -730,7 +770,7 @@ class CenterNet(Module):
         self.head2 = ConvModule(init, 3 * hc, self.n_out, 1, bn=False, relu=False, bias=True)
         self.fuse_heads()
         self.decode = det_ops.DetectionDecode(reg_offset=True, K=K)
-        self.train_cfg, self._loss, self._augment, self._targets = train_cfg, None, None, None
+        self.train_cfg = train_cfg
 
     def fuse_heads(self):
         """(Re)build the fused head convs' weights from self.heads (to() calls it: they are packed like any other conv)."""
@@ -750,17 +790,10 @@ class CenterNet(Module):
     def children(self):
         return [self.backbone] + self.neck + [self.head1, self.head2]
 
-    _trainer = None     # optim.CenterNetHeadTrainer of this model (head_trainer()): derived from the packs of head1 / head2, so owned here
+    TRAIN_CFG_HINT = "configs/centernet/centernet_r18_dcn_train.py"
 
-    def to(self, device):
-        if self._trainer is not None:
-            self._trainer.sync_modules()    # self.heads is the source of truth of a repack: it gets the trained masters first
-        self.fuse_heads()   # head1 / head2 are children whose weights derive from self.heads: refreshed before they are packed
-        return super().to(device)
-
-    def _derive(self, device):
-        if self._trainer is not None:
-            self._trainer.bind()            # the trainer's buffers around the new packs; masters, moments and powers kept
+    def _refresh(self):
+        self.fuse_heads()   # head1 / head2 are children whose weights derive from self.heads (which a trainer has just written)
 
     def features(self, images):
         x = self.backbone(images)[-1]
@@ -784,9 +817,7 @@ class CenterNet(Module):
 
     def loss_op(self):
         """det_ops.CenterNetLoss of this head's layout with the settings of train_cfg (None: the reference's default values)"""
-        if self._loss is None:
-            self._loss = det_ops.CenterNetLoss.from_model(self, self.train_cfg)
-        return self._loss
+        return self._lazy("loss", lambda: det_ops.CenterNetLoss.from_model(self, self.train_cfg))
 
     def loss(self, images, example, grad=False):
         """CenterNetLossCell.construct (centernet/src/centernet_det.py:206-237): features(), then the loss on the head tensor.
@@ -796,26 +827,21 @@ class CenterNet(Module):
         head = self.features(images)
         return dict(self.loss_op()(head, example, grad=grad), head=head)
 
-    def _train_cfg(self, key):
-        if not self.train_cfg or key not in self.train_cfg:
-            raise ValueError(f"CenterNet: train_cfg[{key!r}] is needed for training (see configs/centernet/centernet_r18_dcn_train.py)")
-        return self.train_cfg[key]
-
     def augment_op(self):
         """det_ops.CenterNetAugment with train_cfg["augment"] on the input of train_cfg["assigner"], in the stem's input layout"""
-        if self._augment is None:
+        def build():
             a = self._train_cfg("assigner")
-            self._augment = det_ops.CenterNetAugment(a["input_res"], a["down_ratio"], **dict(self._train_cfg("augment")))
-        return self._augment
+            return det_ops.CenterNetAugment(a["input_res"], a["down_ratio"], **dict(self._train_cfg("augment")))
+        return self._lazy("augment", build)
 
     def targets_op(self):
         """det_ops.CenterNetTargets with train_cfg["assigner"] for this model's classes"""
-        if self._targets is None:
+        def build():
             a = self._train_cfg("assigner")
             h, w = (int(v) for v in a["input_res"])
             d = int(a["down_ratio"])
-            self._targets = det_ops.CenterNetTargets(self.num_classes, (w // d, h // d), a["max_objs"], a.get("min_overlap", 0.7))
-        return self._targets
+            return det_ops.CenterNetTargets(self.num_classes, (w // d, h // d), a["max_objs"], a.get("min_overlap", 0.7))
+        return self._lazy("targets", build)
 
     def train_example(self, images_u8, sizes, bboxes, category_id, generator=None, draws=None, colour=None):
         """Raw images and ground truth -> (input, example) of loss(), on the device with nothing read back: the training branch of
@@ -840,17 +866,12 @@ class CenterNet(Module):
         config returns the existing one, a call with one replaces it (fresh moments).  The model has to be on its device."""
         from . import optim
 
-        if optimizer_cfg is None and self._trainer is not None:
-            return self._trainer
-        cfg = optimizer_cfg if optimizer_cfg is not None else (self.train_cfg or {}).get("optimizer")
-        if self._trainer is not None:       # the replaced trainer leaves its masters in self.heads and lets go of the packs
+        def rederive():
             device = self.head1.packed.w.device
-            self._trainer.sync_modules()
-            self._trainer = None
             self.fuse_heads()
             for m in (self.head1, self.head2):
                 m.to(device)
-        return optim.CenterNetHeadTrainer(self, cfg)
+        return self._head_trainer(optim.CenterNetHeadTrainer, self, optimizer_cfg, (self.train_cfg or {}).get("optimizer"), rederive)
 
     def train_step(self, images_u8, sizes, bboxes, category_id, lr, beta1=0.9, generator=None, draws=None, colour=None):
         """train_example, then one step of head_trainer() on the augmented input: raw images + ground truth -> updated heads as one
@@ -948,7 +969,6 @@ class CenterHead(Module):
         # the loss settings of center_head.py:124-125: the loc-loss weight and one weight per anno_box column (default: all 1)
         self.weight = float(weight)
         self.code_weights = [float(v) for v in code_weights] if code_weights else [1.0] * (10 if "vel" in common_heads else 8)
-        self._loss = None
         self.shared_conv = ConvModule(init, self.in_channels, self.share, 3, 1, 1, bn=True, relu=True, bias=True)
         self.tasks = []
         for nc in self.num_classes:
@@ -984,37 +1004,23 @@ class CenterHead(Module):
         run merged (_derive); branches() lists both."""
         return [self.shared_conv] + [c2 for _, _, _, c2 in self.branches()]
 
-    _trainer = None     # optim.CenterPointHeadTrainer of this head (head_trainer()): derived from the two packs of _derive, so owned here
-
-    def to(self, device):
-        if self._trainer is not None:
-            self._trainer.sync_modules()    # the per-branch ConvModules are the source of truth of a repack: they get the trained masters first
-        return super().to(device)
+    _first = _second = None     # the merged first convs and the grouped last convs (_derive): what optim.CenterPointHeadTrainer trains
 
     def _derive(self, device):
         br = self.branches()
         self._first = merged_conv([c1 for _, _, c1, _ in br], device)
         self._second = nn_ops.pack_conv2d_grouped([(c2.weight, c2.bias, None) for _, _, _, c2 in br],
                                                   y_offs=[self.offsets[t][h] for t, h, _, _ in br]).to(device)
-        if self._trainer is not None:
-            self._trainer.bind()            # the trainer's buffers around the new packs; masters, moments and powers kept
 
-    def head_trainer(self, optimizer_cfg=None):
+    def head_trainer(self, optimizer_cfg=None, fallback=None):
         """optim.CenterPointHeadTrainer of this head (every SepHead branch, first and last convs; the shared conv frozen):
         train_step(feat, example, lr, beta1) continues loss(grad=True) through md_conv2d_grouped_bwd_weight, md_conv2d_grouped_bwd_data,
-        md_conv_bwd_weight, md_grad_sumsq and md_adam_step on the device.  optimizer_cfg: None = optim.CENTERPOINT_OPTIMIZER.  One
-        trainer per head: a call without a config returns the existing one, a call with one replaces it (fresh moments).  The head has to
-        be on its device."""
+        md_conv_bwd_weight, md_grad_sumsq and md_adam_step on the device.  optimizer_cfg: None = `fallback`, the config of the
+        detector around the head, which has no train_cfg of its own (None: optim.CENTERPOINT_OPTIMIZER).  One trainer per head: a call
+        without an optimizer_cfg returns the existing one, a call with one replaces it (fresh moments).  The head has to be on its device."""
         from . import optim
 
-        if optimizer_cfg is None and self._trainer is not None:
-            return self._trainer
-        if self._trainer is not None:       # the replaced trainer leaves its masters in the modules and lets go of the packs
-            device = self._first.w.device
-            self._trainer.sync_modules()
-            self._trainer = None
-            self._derive(device)
-        return optim.CenterPointHeadTrainer(self, optimizer_cfg)
+        return self._head_trainer(optim.CenterPointHeadTrainer, self, optimizer_cfg, fallback, lambda: self._derive(self._first.w.device))
 
     def task_offsets(self, grouped=None):
         """per task {head: first channel} in the head tensor __call__ returns (grouped None: the SEPHEAD_GROUPED setting)"""
@@ -1058,9 +1064,7 @@ class CenterHead(Module):
         return self.loss_op()(head, example, grad=grad)
 
     def loss_op(self):
-        if self._loss is None:
-            self._loss = det_ops.CenterPointLoss.from_head(self)
-        return self._loss
+        return self._lazy("loss", lambda: det_ops.CenterPointLoss.from_head(self))
 
 
 @DETECTORS.register_module
@@ -1083,15 +1087,13 @@ class PointPillars(Module):
         self.train_cfg = dict(train_cfg) if train_cfg else None
         self.max_per_task = int(test_cfg["nms"]["nms_post_max_size"])
         self.cp_post = CP_POST if cp_post is None else bool(cp_post)
-        self._post_batched = None
 
     def children(self):
         return [self.neck, self.bbox_head]
 
     def post_batched(self):
-        if self._post_batched is None:
-            self._post_batched = det_ops.CenterHeadPostBatched(self.bbox_head.task_offsets(), self.bbox_head.num_classes, self.test_cfg)
-        return self._post_batched
+        return self._lazy("post_batched", lambda: det_ops.CenterHeadPostBatched(self.bbox_head.task_offsets(), self.bbox_head.num_classes,
+                                                                               self.test_cfg))
 
     def forward(self, pseudo_image, return_aux=False):
         """pseudo_image [B, H, W, 64] bf16 -> (dets [B, tasks x nms_post_max_size, 11] f32, count [B] i32): per row the 9 box values
@@ -1119,9 +1121,7 @@ class PointPillars(Module):
     def head_trainer(self, optimizer_cfg=None):
         """CenterHead.head_trainer of the model's head; optimizer_cfg: None = train_cfg["optimizer"] (none there:
         optim.CENTERPOINT_OPTIMIZER)"""
-        if optimizer_cfg is None and self.bbox_head._trainer is None:
-            optimizer_cfg = (self.train_cfg or {}).get("optimizer") or {}
-        return self.bbox_head.head_trainer(optimizer_cfg)
+        return self.bbox_head.head_trainer(optimizer_cfg, fallback=(self.train_cfg or {}).get("optimizer"))
 
     def train_step(self, pseudo_image, example, lr, beta1=0.9):
         """One training step of the head on a batch (the neck frozen): pseudo_image [B, H, W, 64] bf16, example = the dict of
@@ -1247,8 +1247,7 @@ class PillarDetector(Module):
             raise ValueError("PillarDetector: the reader's voxel_size / width do not match the voxel generator / the backbone")
         self.train_cfg = dict(train_cfg) if train_cfg else None
         self._voxel_generator = vg
-        self._augment = self._targets = None
-        self._sweeps_cfg, self._sweeps = (dict(sweeps) if sweeps else None), None
+        self._sweeps_cfg = dict(sweeps) if sweeps else None
 
     def children(self):
         return [self.reader, self.backbone, self.detector]
@@ -1282,11 +1281,9 @@ class PillarDetector(Module):
 
     def sweeps_op(self):
         """det_ops.SweepMerger with the model's `sweeps` (nsweeps, min_distance, order; configs/centerpoint/centerpoint_pp_nusc_sweeps.py)"""
-        if self._sweeps is None:
-            if not self._sweeps_cfg:
-                raise ValueError("PillarDetector: the model has no `sweeps` (see configs/centerpoint/centerpoint_pp_nusc_sweeps.py)")
-            self._sweeps = det_ops.SweepMerger(**self._sweeps_cfg)
-        return self._sweeps
+        if not self._sweeps_cfg:
+            raise ValueError("PillarDetector: the model has no `sweeps` (see configs/centerpoint/centerpoint_pp_nusc_sweeps.py)")
+        return self._lazy("sweeps", lambda: det_ops.SweepMerger(**self._sweeps_cfg))
 
     def merge_sweeps(self, points, lengths, matrices, time_lags, order=None, begins=None, return_status=False):
         """The reference loader's multi-sweep step on the device (det_ops.SweepMerger: read_sweep per past sweep and the concatenation):
@@ -1306,23 +1303,16 @@ class PillarDetector(Module):
         PointPillars.evaluate_nusc of the inner detector (class names from the config's `tasks`)."""
         return self.detector.evaluate_nusc(dets, count, poses, gt_records, ego_translations)
 
-    def _train_cfg(self, key):
-        if not self.train_cfg or key not in self.train_cfg:
-            raise ValueError(f"PillarDetector: train_cfg[{key!r}] is needed for training (see configs/centerpoint/centerpoint_pp_nusc_train.py)")
-        return self.train_cfg[key]
+    TRAIN_CFG_HINT = "configs/centerpoint/centerpoint_pp_nusc_train.py"
 
     def augment_op(self):
         """det_ops.CenterPointAugment with train_cfg["augment"] on this model's range"""
-        if self._augment is None:
-            r = self.pc_range
-            self._augment = det_ops.CenterPointAugment((r[0], r[1], r[3], r[4]), **dict(self._train_cfg("augment")))
-        return self._augment
+        r = self.pc_range
+        return self._lazy("augment", lambda: det_ops.CenterPointAugment((r[0], r[1], r[3], r[4]), **dict(self._train_cfg("augment"))))
 
     def targets_op(self):
         """det_ops.CenterPointTargets with train_cfg["assigner"] on this model's voxel generator"""
-        if self._targets is None:
-            self._targets = det_ops.CenterPointTargets(self._train_cfg("assigner"), self._voxel_generator)
-        return self._targets
+        return self._lazy("targets", lambda: det_ops.CenterPointTargets(self._train_cfg("assigner"), self._voxel_generator))
 
     def _train_canvas(self, points, offsets):
         # the reference trains with its own voxel budget (30 000 on nuScenes, 60 000 in evaluation)
@@ -1357,9 +1347,7 @@ class PillarDetector(Module):
         return dict(self.loss(ex["augment"]["points"], ex["augment"]["offsets"], ex, grad=grad), example=ex)
 
     def head_trainer(self, optimizer_cfg=None):
-        """PointPillars.head_trainer of the inner detector (optimizer_cfg None: this model's train_cfg["optimizer"])"""
-        if optimizer_cfg is None and self.bbox_head._trainer is None:
-            optimizer_cfg = (self.train_cfg or {}).get("optimizer") or {}
+        """PointPillars.head_trainer of the inner detector (optimizer_cfg None: train_cfg["optimizer"], which the detector got too)"""
         return self.detector.head_trainer(optimizer_cfg)
 
     def train_step(self, points, offsets, gt_boxes, gt_classes, gt_count, lr, beta1=0.9, generator=None, draws=None, sampled=None):
@@ -1389,17 +1377,10 @@ class PPAnchorHead(Module):
     def children(self):
         return [m for m in (self.conv_cls, self.conv_box, self.conv_dir_cls) if m is not None]
 
-    _trainer = None     # optim.HeadTrainer of this head (PointPillarsNet.head_trainer): derived from the merged pack, so owned here
-
-    def to(self, device):
-        if self._trainer is not None:
-            self._trainer.sync_modules()    # the ConvModules are the source of truth of a repack: they get the trained master first
-        return super().to(device)
+    _merged = None      # the three convs as one pack (_derive): what optim.HeadTrainer (PointPillarsNet.head_trainer) trains
 
     def _derive(self, device):
         self._merged = merged_conv(self.children(), device)
-        if self._trainer is not None:
-            self._trainer.bind()            # the trainer's buffers around the new pack; master, moments and powers kept
 
     def head_offsets(self):
         """first channel of each conv's outputs in the head tensor; dir_cls None without a direction classifier"""
@@ -1466,7 +1447,6 @@ class PointPillarsNet(Module):
         self.class_names = list(class_names) if class_names is not None else None
         self.test_cfg = dict(test_cfg)
         self.train_cfg = dict(train_cfg) if train_cfg else None
-        self._loss = None
         off = self.bbox_head.head_offsets()
         self.post = det_ops.PPHeadPost(dict(num_anchors=self.num_anchors, num_classes=self.num_class, off_cls=off["cls"], off_box=off["box"],
                                             off_dir=off["dir_cls"], use_self_train=use_self_train,
@@ -1527,9 +1507,7 @@ class PointPillarsNet(Module):
 
     def loss_op(self):
         """det_ops.PointPillarsLoss of this head's layout with the settings of train_cfg (None: the KITTI configurations' values)"""
-        if self._loss is None:
-            self._loss = det_ops.PointPillarsLoss.from_net(self, self.train_cfg)
-        return self._loss
+        return self._lazy("loss", lambda: det_ops.PointPillarsLoss.from_net(self, self.train_cfg))
 
     def loss(self, pseudo_image, example, grad=False):
         """PointPillarsWithLossCell.construct (pointpillars/src/pointpillars.py:817-872): the neck and the head, then the loss on the head
@@ -1547,14 +1525,9 @@ class PointPillarsNet(Module):
         existing one, a call with one replaces it (fresh moments).  The model has to be on its device."""
         from . import optim
 
-        if optimizer_cfg is None and self.bbox_head._trainer is not None:
-            return self.bbox_head._trainer
-        cfg = optimizer_cfg if optimizer_cfg is not None else (self.train_cfg or {}).get("optimizer")
-        if self.bbox_head._trainer is not None:       # the replaced trainer leaves its master in the modules and lets go of the pack
-            self.bbox_head._trainer.sync_modules()
-            self.bbox_head._trainer = None
-            self.bbox_head._derive(self.bbox_head._merged.w.device)
-        return optim.HeadTrainer(self, cfg)
+        head = self.bbox_head
+        return head._head_trainer(optim.HeadTrainer, self, optimizer_cfg, (self.train_cfg or {}).get("optimizer"),
+                                  lambda: head._derive(head._merged.w.device))
 
 
 # ----------------------------------------------------------------------------- PointPillars (KITTI) from raw points (csrc/ppreader.hip)
@@ -1671,10 +1644,9 @@ class PointPillarsKITTIPoints(Module):
 
     def augment_op(self):
         """det_ops.PointCloudAugment with train_cfg["augment"] (None: the reference's defaults) on this model's range"""
-        if getattr(self, "_augment", None) is None:
-            r = self.pc_range
-            self._augment = det_ops.PointCloudAugment((r[0], r[1], r[3], r[4]), **dict((self.inner.train_cfg or {}).get("augment") or {}))
-        return self._augment
+        r = self.pc_range
+        return self._lazy("augment", lambda: det_ops.PointCloudAugment((r[0], r[1], r[3], r[4]),
+                                                                       **dict((self.inner.train_cfg or {}).get("augment") or {})))
 
     def train_example(self, points, offsets, gt_boxes, gt_classes, gt_count, generator=None, draws=None, valid=None, sampled=None):
         """Raw points and ground truth -> the `example` of loss(), on the device with nothing read back: the training branch of
@@ -1692,10 +1664,10 @@ class PointPillarsKITTIPoints(Module):
         far = torch.tensor([1e6, 1e6, 0.0, 1.0, 1.0, 1.0, 0.0], dtype=torch.float32, device=dev)
         boxes = torch.where(pad[..., None], far, boxes)
         classes = torch.where(pad, torch.ones_like(classes), classes)
-        if getattr(self, "_thresholds", None) is None:
+        def thresholds():
             gen = det_ops.generate_anchors(self.inner.generators, (1,) + tuple(self.inner.feature_hw), device=dev)
-            self._thresholds = (gen["matched_thresholds"].reshape(-1).contiguous(), gen["unmatched_thresholds"].reshape(-1).contiguous())
-        mt, ut = self._thresholds
+            return gen["matched_thresholds"].reshape(-1).contiguous(), gen["unmatched_thresholds"].reshape(-1).contiguous()
+        mt, ut = self._lazy("thresholds", thresholds)
         rows = [det_ops.assign_targets(self.inner.anchors, boxes[b], classes[b], mt, ut, mask[b]) for b in range(B)]
         labels, reg_targets, reg_weights, gt_ids = (torch.stack([r[i] for r in rows]) for i in range(4))
         return dict(labels=labels, reg_targets=reg_targets, reg_weights=reg_weights, gt_ids=gt_ids, anchors_mask=mask, canvas=canvas, augment=a)

@@ -127,53 +127,124 @@ class Adam:
 
     def load_state(self, st):
         for k in ("param", "m", "v"):
-            getattr(self, k).copy_(st[k])
+            getattr(self, k).copy_(st[k])           # (from any device)
         self.beta1_power, self.beta2_power, self.steps = np.float32(st["beta1_power"]), np.float32(st["beta2_power"]), int(st["steps"])
+        self.refresh_shadow()
+
+    def adopt(self, old):
+        """the mutable state of another Adam over the same layout, on any device (a trainer's rebind): load_state without the clone"""
+        self.load_state(vars(old))
+
+    def refresh_shadow(self):
+        """the fp32 master rounded into the bf16 shadow"""
         if self.shadow is not None:
-            ns = self.shadow.numel()
-            self.shadow.view(-1).copy_(self.param[:ns].to(torch.bfloat16))
+            self.shadow.view(-1).copy_(self.param[:self.shadow.numel()].to(torch.bfloat16))
+
+
+def pack_columns(pc):
+    """[kh kw, cin] int64: the column of pc.w that holds tap t, input channel i -- the two K orders of nn_ops.pack_conv, col(t, i) of
+    include/minddet_hip_convbwd.h"""
+    taps, cin = pc.kh * pc.kw, pc.cin
+    t, i = torch.meshgrid(torch.arange(taps), torch.arange(cin), indexing="ij")
+    if getattr(pc, "korder", 0) == 1:
+        return (i // 64) * (taps * 64) + t * 64 + i % 64
+    return t * cin + i
+
+
+def bind_range(packs, cfg, old=None):
+    """One Adam (options cfg) around the packs of a range, packs = [(pack, its weight's slice name, its bias's), ...]: the flat fp32
+    master is [every pack's w ... | every pack's bias ...] (weights first: the shadow mirrors param[:shadow.numel()]), the shadow one
+    fresh bf16 buffer.  old None: the master is the packs widened to fp32; else the master, moments, powers and step count of `old`
+    (an Adam of the same layout, on any device) carried over.  Then the packs read the optimizer's memory: every `w` becomes a view
+    of the shadow, every `bias` the master's slice, so the forward pass behind a step runs on the new weights with no copy."""
+    dev = packs[0][0].w.device
+    sizes = {wn: tuple(pc.w.shape) for pc, wn, _ in packs}
+    sizes.update({bn: tuple(pc.bias.shape) for pc, _, bn in packs})
+    shadow = torch.empty((sum(pc.w.numel() for pc, _, _ in packs),), dtype=torch.bfloat16, device=dev)
+    opt = Adam(sizes, dev, shadow=shadow, **cfg)
+    if old is None:
+        for pc, wn, bn in packs:
+            opt.view(wn).copy_(pc.w.to(torch.float32))
+            opt.view(bn).copy_(pc.bias)
+        opt.refresh_shadow()
+    else:
+        opt.adopt(old)
+    for pc, wn, bn in packs:
+        lo, hi, shape = opt.slices[wn]
+        pc.w, pc.bias = shadow[lo:hi].view(shape), opt.view(bn)
+    return opt
+
+
+class _HeadTrainerBase:
+    """What the head trainers share, everything that is not a model's arithmetic: the optimizer config, the registration with the
+    module that owns the packs, the binding of one Adam per range (bind_range) and the host copy of a master.  A subclass names its
+    DEFAULTS (the keys an optimizer_cfg may set, `type` must be "Adam") and the keys it REFUSES unless None, and gives
+      _attach(model)  keeps what train_step reads of the constructor's first argument -> the owner: the graphs.Module whose to()
+                      makes the packs and which holds the trainer as `_trainer` (Module.to: sync_modules() before a repack,
+                      bind() after it; Module._head_trainer replaces the trainer)
+      ranges()        ordered {range name: [(pack, weight slice name, bias slice name), ...]} of the owner's CURRENT packs
+      train_step, and the loops of sync_modules that write the masters into the model's own modules."""
+    DEFAULTS, REFUSES = None, ()
+
+    @classmethod
+    def check_config(cls, optimizer_cfg):
+        """optimizer_cfg over the DEFAULTS -> Adam's options (no `type`); ValueError for what is not built"""
+        cfg = dict(cls.DEFAULTS, **dict(optimizer_cfg or {}))
+        if cfg.pop("type") != "Adam":
+            raise ValueError(f"{cls.__name__}: only the reference's Adam is built")
+        bad = sorted(set(cfg) - set(cls.DEFAULTS)) + [k for k in cls.REFUSES if cfg.get(k) is not None]
+        if bad:
+            raise ValueError(f"{cls.__name__}: optimizer options that are not built: {bad}")
+        return cfg
+
+    def __init__(self, model, optimizer_cfg=None):
+        self.cfg, self.opts = self.check_config(optimizer_cfg), None       # (raises before the model is touched)
+        owner = self._attach(model)
+        if any(pc is None or not pc.w.is_cuda for packs in self.ranges().values() for pc, _, _ in packs):
+            raise ValueError(f"{type(self).__name__}: move the model to its device first (to(device) makes the packs)")
+        owner._trainer = self
+        self.bind()
+
+    @property
+    def opt(self):
+        """the Adam of a trainer with one range"""
+        (opt,) = self.opts.values()
+        return opt
+
+    def bind(self):
+        """(re)build the flat buffers around the owner's current packs; the fp32 masters, the moments, the powers and the step counts
+        survive"""
+        old = self.opts or {}
+        self.opts = {name: bind_range(packs, self.cfg, old.get(name)) for name, packs in self.ranges().items()}
+
+    @staticmethod
+    def _host(opt, wname, bname, pc=None):
+        """(w, b) of a slice pair on the host; with a nn_ops.pack_conv pack that is not 1x1, w as [rows, cin, kh, kw] (through the
+        pack's column map), else as it lies"""
+        w, b = opt.view(wname).detach().cpu(), opt.view(bname).detach().cpu()
+        if pc is not None and pc.kh * pc.kw > 1:
+            w = w[:, pack_columns(pc).reshape(-1)].reshape(w.shape[0], pc.kh, pc.kw, pc.cin).permute(0, 3, 1, 2)
+        return w, b
 
 
 DEFAULT_OPTIMIZER = dict(type="Adam", beta2=0.999, eps=1e-8, weight_decay=1e-4, max_norm=None, grad_scale=1.0)
 
 
-class HeadTrainer:
+class HeadTrainer(_HeadTrainerBase):
     """Trains graphs.PPAnchorHead (conv_cls, conv_box, conv_dir_cls as the one merged 1x1 launch) on the device with the neck frozen.
-    The flat parameter is the merged pack widened to fp32 followed by its bias; the optimizer's shadow is the merged pack's bf16 `w`
-    itself and the pack's bias IS the master's bias slice, so the forward pass behind a step runs on the new weights with no copy.
-    The head owns the trainer (PPAnchorHead._derive): a later to() writes the master back into the three ConvModules, repacks, and
-    binds the trainer to the new pack with its moments and powers kept.
+    The flat parameter (`opt`) is the merged pack widened to fp32 followed by its bias; the merged pack's bf16 `w` is the optimizer's
+    shadow and the pack's bias IS the master's bias slice, so the forward pass behind a step runs on the new weights with no copy.
+    The head owns the trainer (Module.to): a later to() writes the master back into the three ConvModules, repacks, and binds the
+    trainer to the new pack with its moments and powers kept.
     optimizer_cfg: train_cfg["optimizer"] (keys of DEFAULT_OPTIMIZER; `type` must be "Adam")."""
+    DEFAULTS = DEFAULT_OPTIMIZER
 
-    def __init__(self, net, optimizer_cfg=None):
-        cfg = dict(DEFAULT_OPTIMIZER, **dict(optimizer_cfg or {}))
-        if cfg.pop("type") != "Adam":
-            raise ValueError("HeadTrainer: only the reference's Adam is built")
-        unknown = set(cfg) - set(DEFAULT_OPTIMIZER)
-        if unknown:
-            raise ValueError(f"HeadTrainer: optimizer options that are not built: {sorted(unknown)}")
-        self.net, self.head, self.cfg, self.opt = net, net.bbox_head, cfg, None
-        if getattr(self.head, "_merged", None) is None:
-            raise ValueError("HeadTrainer: move the model to its device first (to(device) packs the head)")
-        self.head._trainer = self
-        self.bind()
+    def _attach(self, net):
+        self.net, self.head = net, net.bbox_head
+        return self.head
 
-    def bind(self):
-        """(re)build the flat buffers around the head's current merged pack; the moments, the powers and the fp32 master survive"""
-        pc, old = self.head._merged, self.opt
-        rows, kpad = pc.w.shape
-        dev = pc.w.device
-        opt = Adam(dict(w=(rows, kpad), b=(rows,)), dev, shadow=pc.w, **self.cfg)
-        if old is None:
-            opt.view("w").copy_(pc.w.to(torch.float32))
-            opt.view("b").copy_(pc.bias)
-        else:
-            for k in ("param", "m", "v"):
-                getattr(opt, k).copy_(getattr(old, k).to(dev))
-            opt.beta1_power, opt.beta2_power, opt.steps = old.beta1_power, old.beta2_power, old.steps
-            pc.w.copy_(opt.view("w").to(torch.bfloat16))
-        pc.bias = opt.view("b")          # the bias md_conv2d reads is the fp32 master
-        self.opt = opt
+    def ranges(self):
+        return dict(head=[(self.head._merged, "w", "b")])
 
     def train_step(self, pseudo_image, example, lr, beta1=0.9):
         """One step on a batch: pseudo_image [B,H,W,64] bf16, example = dict(labels, reg_targets) of the model's anchors -> the dict of
@@ -189,7 +260,7 @@ class HeadTrainer:
     def sync_modules(self):
         """the fp32 master back into conv_cls / conv_box / conv_dir_cls (weight [cout,cin,1,1], bias [cout]), where weights.py and a
         repack read it.  A host copy: for export, not for the step."""
-        w, b = self.opt.view("w").detach().cpu(), self.opt.view("b").detach().cpu()
+        w, b = self._host(self.opt, "w", "b")
         row = 0
         for mod in self.head.children():
             mod.weight = w[row:row + mod.cout, :mod.cin].reshape(mod.cout, mod.cin, 1, 1).clone()
@@ -200,40 +271,26 @@ class HeadTrainer:
 CENTERNET_OPTIMIZER = dict(type="Adam", beta2=0.999, eps=1e-7, weight_decay=0.0, max_norm=None, grad_scale=1.0)
 
 
-def pack_columns(pc):
-    """[kh kw, cin] int64: the column of pc.w that holds tap t, input channel i -- the two K orders of nn_ops.pack_conv, col(t, i) of
-    include/minddet_hip_convbwd.h"""
-    taps, cin = pc.kh * pc.kw, pc.cin
-    t, i = torch.meshgrid(torch.arange(taps), torch.arange(cin), indexing="ij")
-    if getattr(pc, "korder", 0) == 1:
-        return (i // 64) * (taps * 64) + t * 64 + i % 64
-    return t * cin + i
-
-
-class CenterNetHeadTrainer:
+class CenterNetHeadTrainer(_HeadTrainerBase):
     """Trains the heads of graphs.CenterNet (head1: the fused 3x3 conv + ReLU, head2: the block-diagonal 1x1 conv) on the device with
     the backbone and the neck frozen: head1 -> head2 -> md_cn_loss_grad -> md_conv_bwd_weight (head2, inside its three blocks) ->
     md_conv1x1_bwd_data (through head1's ReLU) -> md_conv_bwd_weight (head1, 3x3) -> md_adam_step per pack.
     One Adam per pack (`opts["head1"]`, `opts["head2"]`): the flat parameter is the pack widened to fp32 followed by its bias, the
-    optimizer's shadow is the pack's bf16 `w` itself and the pack's bias IS the master's bias slice, so the forward pass behind a step
-    runs on the new weights with no copy.  The model owns the trainer: a later to() writes the masters back into net.heads (the
-    per-head ConvModules, the source of truth), fuses, repacks, and binds the trainer to the new packs with moments and powers kept.
+    pack's bf16 `w` is the optimizer's shadow and the pack's bias IS the master's bias slice, so the forward pass behind a step
+    runs on the new weights with no copy.  The model owns the trainer (Module.to): a later to() writes the masters back into
+    net.heads (the per-head ConvModules, the source of truth), fuses, repacks, and binds the trainer to the new packs with moments and
+    powers kept.
     The reference multiplies the loss by loss_scale_value 1024 and divides the gradients by it again; the gradients here are fp32 and no
     scale is applied (grad_scale 1).  optimizer_cfg: train_cfg["optimizer"] (keys of CENTERNET_OPTIMIZER; `type` must be "Adam";
     the global-norm clip is not built across two ranges)."""
+    DEFAULTS, REFUSES = CENTERNET_OPTIMIZER, ("max_norm",)
 
-    def __init__(self, net, optimizer_cfg=None):
-        cfg = dict(CENTERNET_OPTIMIZER, **dict(optimizer_cfg or {}))
-        if cfg.pop("type") != "Adam":
-            raise ValueError("CenterNetHeadTrainer: only the reference's Adam is built")
-        unknown = set(cfg) - set(CENTERNET_OPTIMIZER)
-        if unknown or cfg["max_norm"] is not None:
-            raise ValueError(f"CenterNetHeadTrainer: optimizer options that are not built: {sorted(unknown) or ['max_norm']}")
-        self.net, self.cfg, self.opts = net, cfg, None
-        if net.head1.packed is None or not net.head1.packed.w.is_cuda:
-            raise ValueError("CenterNetHeadTrainer: move the model to its device first (to(device) packs the heads)")
-        net._trainer = self
-        self.bind()
+    def _attach(self, net):
+        self.net = net
+        return net
+
+    def ranges(self):
+        return {name: [(getattr(self.net, name).packed, "w", "b")] for name in ("head1", "head2")}
 
     def blocks(self):
         """(row0, rows, col0, cols) of hm / wh / reg in head2: the live part of the block-diagonal layer"""
@@ -243,25 +300,6 @@ class CenterNetHeadTrainer:
             out.append((row, c2.cout, k * hc, hc))
             row += c2.cout
         return out
-
-    def bind(self):
-        """(re)build the flat buffers around the model's current packs; the moments, the powers and the fp32 masters survive"""
-        old, opts = self.opts, {}
-        for name in ("head1", "head2"):
-            pc = getattr(self.net, name).packed
-            rows, kpad = pc.w.shape
-            opt = Adam(dict(w=(rows, kpad), b=(rows,)), pc.w.device, shadow=pc.w, **self.cfg)
-            if old is None:
-                opt.view("w").copy_(pc.w.to(torch.float32))
-                opt.view("b").copy_(pc.bias)
-            else:
-                for k in ("param", "m", "v"):
-                    getattr(opt, k).copy_(getattr(old[name], k).to(pc.w.device))
-                opt.beta1_power, opt.beta2_power, opt.steps = old[name].beta1_power, old[name].beta2_power, old[name].steps
-                pc.w.copy_(opt.view("w").to(torch.bfloat16))
-            pc.bias = opt.view("b")          # the bias md_conv2d reads is the fp32 master
-            opts[name] = opt
-        self.opts = opts
 
     def train_step(self, inp, example, lr, beta1=0.9):
         """One step on a batch: inp = the network input of CenterNet.train_example, example = its target dict -> the dict of
@@ -285,11 +323,9 @@ class CenterNetHeadTrainer:
     def sync_modules(self):
         """the fp32 masters back into net.heads[name] = (3x3 ConvModule, 1x1 ConvModule) (weight [cout,cin,k,k], bias [cout]), where
         fuse_heads(), weights.py and a repack read them.  A host copy: for export, not for the step."""
-        net, hc = self.net, self.net.head_conv
-        pc1 = net.head1.packed
-        w1, b1 = self.opts["head1"].view("w").detach().cpu(), self.opts["head1"].view("b").detach().cpu()
-        w2, b2 = self.opts["head2"].view("w").detach().cpu(), self.opts["head2"].view("b").detach().cpu()
-        w1 = w1[:, pack_columns(pc1).reshape(-1)].reshape(w1.shape[0], pc1.kh, pc1.kw, pc1.cin).permute(0, 3, 1, 2)   # [rows, cin, kh, kw]
+        net = self.net
+        w1, b1 = self._host(self.opts["head1"], "w", "b", net.head1.packed)
+        w2, b2 = self._host(self.opts["head2"], "w", "b", net.head2.packed)
         for (row0, rows, col0, cols), name in zip(self.blocks(), ("hm", "wh", "reg")):
             c1, c2 = net.heads[name]
             c1.weight = w1[col0:col0 + cols, :c1.cin].clone().contiguous()
@@ -309,7 +345,7 @@ def identity_bn(bn):
     return torch.sqrt(torch.as_tensor(var).to(torch.float32) + eps), mean, mean, var, eps
 
 
-class CenterPointHeadTrainer:
+class CenterPointHeadTrainer(_HeadTrainerBase):
     """Trains every SepHead branch of graphs.CenterHead (the merged first 3x3 convs + ReLU and the grouped last 3x3 convs) on the device
     with the neck and the shared conv frozen: shared conv -> merged first conv (`mid`) -> md_conv2d_grouped (`head`) -> md_cp_loss_grad
     -> md_conv2d_grouped_bwd_weight (mid, g) -> md_conv2d_grouped_bwd_data (g through mid's ReLU: `dmid`) -> md_conv_bwd_weight (shared,
@@ -318,45 +354,18 @@ class CenterPointHeadTrainer:
     packs; its shadow is one bf16 buffer the two packs' `w` are views of, and the packs' biases ARE the master's slices, so the forward
     pass behind a step runs on the new weights with no copy.  The first convs' BatchNorm is frozen: the trained parameters are the folded
     pack (weight x scale, shift), the statistics never move (the reference trains with batch statistics; not built).  The head owns the
-    trainer (CenterHead._derive): a later to() writes the masters back into the per-branch ConvModules (sync_modules), repacks, and binds
+    trainer (Module.to): a later to() writes the masters back into the per-branch ConvModules (sync_modules), repacks, and binds
     the trainer to the new packs with masters, moments and powers kept.
     optimizer_cfg: train_cfg["optimizer"] (keys of CENTERPOINT_OPTIMIZER; `type` must be "Adam")."""
+    DEFAULTS = CENTERPOINT_OPTIMIZER
     FIRST_CHUNK = 256       # MD_CONV_BWD_MAX_COUT
 
-    def __init__(self, head, optimizer_cfg=None):
-        cfg = dict(CENTERPOINT_OPTIMIZER, **dict(optimizer_cfg or {}))
-        if cfg.pop("type") != "Adam":
-            raise ValueError("CenterPointHeadTrainer: only the reference's Adam is built")
-        unknown = set(cfg) - set(CENTERPOINT_OPTIMIZER)
-        if unknown:
-            raise ValueError(f"CenterPointHeadTrainer: optimizer options that are not built: {sorted(unknown)}")
-        self.head, self.cfg, self.opt = head, cfg, None
-        if getattr(head, "_first", None) is None or not head._first.w.is_cuda:
-            raise ValueError("CenterPointHeadTrainer: move the model to its device first (to(device) packs the head)")
-        head._trainer = self
-        self.bind()
+    def _attach(self, head):
+        self.head = head
+        return head
 
-    def bind(self):
-        """(re)build the flat buffers around the head's current packs; the moments, the powers and the fp32 masters survive"""
-        pc1, pk2, old = self.head._first, self.head._second, self.opt
-        dev = pc1.w.device
-        n1, n2 = pc1.w.numel(), pk2.w.numel()
-        shadow = torch.empty((n1 + n2,), dtype=torch.bfloat16, device=dev)
-        sizes = dict(w1=tuple(pc1.w.shape), w2=tuple(pk2.w.shape), b1=tuple(pc1.bias.shape), b2=tuple(pk2.bias.shape))
-        opt = Adam(sizes, dev, shadow=shadow, **self.cfg)
-        if old is None:
-            opt.view("w1").copy_(pc1.w.to(torch.float32))
-            opt.view("w2").copy_(pk2.w.to(torch.float32))
-            opt.view("b1").copy_(pc1.bias)
-            opt.view("b2").copy_(pk2.bias)
-        else:
-            for k in ("param", "m", "v"):
-                getattr(opt, k).copy_(getattr(old, k).to(dev))
-            opt.beta1_power, opt.beta2_power, opt.steps = old.beta1_power, old.beta2_power, old.steps
-        shadow.copy_(opt.param[:n1 + n2].to(torch.bfloat16))
-        pc1.w, pk2.w = shadow[:n1].view(pc1.w.shape), shadow[n1:].view(pk2.w.shape)      # the weights the convs read are the shadow
-        pc1.bias, pk2.bias = opt.view("b1"), opt.view("b2")                              # and their biases the fp32 master
-        self.opt = opt
+    def ranges(self):
+        return dict(head=[(self.head._first, "w1", "b1"), (self.head._second, "w2", "b2")])
 
     def train_step(self, feat, example, lr, beta1=0.9):
         """One step on a batch: feat [B,H,W,in_channels] bf16 = the neck's output, example = the dict of det_ops.cp_assign_targets ->
@@ -382,10 +391,9 @@ class CenterPointHeadTrainer:
         """the fp32 masters back into head.tasks[t][name] = (c1, c2) (weight [cout,64,3,3], bias [cout]), where weights.py and a repack
         read them; c1's BatchNorm becomes identity_bn of its frozen statistics, so nn_ops._fold_bn returns the master bit for bit.  A
         host copy: for export, not for the step."""
-        pc1, pk2 = self.head._first, self.head._second
-        w1, b1 = self.opt.view("w1").detach().cpu(), self.opt.view("b1").detach().cpu()
-        w2, b2 = self.opt.view("w2").detach().cpu(), self.opt.view("b2").detach().cpu()
-        w1 = w1[:, pack_columns(pc1).reshape(-1)].reshape(w1.shape[0], pc1.kh, pc1.kw, pc1.cin).permute(0, 3, 1, 2)   # [rows, cin, kh, kw]
+        pk2 = self.head._second
+        w1, b1 = self._host(self.opt, "w1", "b1", self.head._first)
+        w2, b2 = self._host(self.opt, "w2", "b2")
         k = pk2.k
         for i, (_, _, c1, c2) in enumerate(self.head.branches()):
             c1.weight = w1[64 * i:64 * i + 64, :c1.cin].clone().contiguous()

@@ -1,7 +1,8 @@
 """One valid small call per MD_AOT_ARGS entry point of libminddet_hip.so, written from include/minddet_hip.h: operand shapes, dtypes,
-the attribute struct, and which operands are optional.  tests/test_abi_checks_cpu.py derives single-defect calls from each row (no GPU:
-the argument checks complete before any device call); tests/test_abi_accept_gpu.py makes each row once with zero-filled tensors and
-expects rc 0, which is what proves the derived calls carry ONE defect.  Zero indices, counts and offsets are in range for every row.
+the attribute struct, and which operands are optional.  tests/test_abi_checks_cpu.py derives single-defect calls from each row (tests/abi_derive.py,
+as each feature's CPU test file does from its tests/abi_cases_*.py table; no GPU: the argument checks complete before any device call);
+tests/test_abi_accept_gpu.py makes each row once with zero-filled tensors and expects rc 0, which is what proves the derived calls
+carry ONE defect.  Zero indices, counts and offsets are in range for every row.
 
 Operand kinds
   req    required: described (ndims[i], shapes[i]), dtype as documented, data pointer non-NULL when the call has work

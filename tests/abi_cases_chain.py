@@ -1,6 +1,6 @@
 """One valid small call per MD_AOT_ARGS entry point of include/minddet_hip_chain.h, in the form of tests/abi_cases.py (operand kinds and
-rank flags are explained there).  tests/test_pw_chain_cpu.py derives the single-defect calls with the machinery of
-tests/test_abi_checks_cpu.py; tests/test_pw_chain_gpu.py makes the row once on the GPU and expects rc 0."""
+rank flags are explained there).  The feature's CPU test file hands each row to the single-defect test of tests/abi_derive.py, and
+tests/test_abi_accept_gpu.py makes each row once on the GPU and expects rc 0."""
 from tests.abi_cases import B16, F, Case, T
 
 

@@ -1,6 +1,6 @@
 """One valid small call of md_cp_loss and md_cp_loss_grad (include/minddet_hip_cploss.h) per optional-operand form, in the form of
-tests/abi_cases.py (operand kinds and rank flags are explained there).  tests/test_cp_loss_cpu.py derives the single-defect calls with
-the machinery of tests/test_abi_checks_cpu.py; tests/test_cp_loss_gpu.py makes each row once on the GPU and expects rc 0."""
+tests/abi_cases.py (operand kinds and rank flags are explained there).  The feature's CPU test file hands each row to the single-defect
+test of tests/abi_derive.py, and tests/test_abi_accept_gpu.py makes each row once on the GPU and expects rc 0."""
 from tests.abi_cases import B16, F, I, U8, Case, S, T, f32, i32
 
 CPTask = S(*[(n, i32) for n in ("off_reg", "off_height", "off_dim", "off_rot", "off_vel", "off_hm", "num_classes", "class_base")])

@@ -1,6 +1,6 @@
 """One valid small call of md_cp_assign_targets (include/minddet_hip_cptargets.h) per optional-operand form, in the form of
-tests/abi_cases.py (operand kinds and rank flags are explained there).  tests/test_cp_targets_cpu.py derives the single-defect calls
-with the machinery of tests/test_abi_checks_cpu.py; tests/test_cp_targets_gpu.py makes each row once on the GPU and expects rc 0."""
+tests/abi_cases.py (operand kinds and rank flags are explained there).  The feature's CPU test file hands each row to the single-defect
+test of tests/abi_derive.py, and tests/test_abi_accept_gpu.py makes each row once on the GPU and expects rc 0."""
 from tests.abi_cases import F, I, U8, Case, S, T, f32, i32   # noqa: F401
 
 CPTargets = S(("num_tasks", i32), ("num_classes", i32 * 8), ("voxel_size", f32 * 2), ("pc_range", f32 * 2), ("out_size_factor", i32),

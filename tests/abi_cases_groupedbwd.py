@@ -1,7 +1,7 @@
 """One valid small call of md_conv2d_grouped_bwd_data and md_conv2d_grouped_bwd_weight (include/minddet_hip_groupedbwd.h) per
-optional-operand form, in the form of tests/abi_cases.py (operand kinds and rank flags are explained there).
-tests/test_groupedbwd_ops_cpu.py derives the single-defect calls with the machinery of tests/test_abi_checks_cpu.py;
-tests/test_groupedbwd_gpu.py makes each row once on the GPU and expects rc 0."""
+optional-operand form, in the form of tests/abi_cases.py (operand kinds and rank flags are explained there).  The feature's CPU test file
+hands each row to the single-defect test of tests/abi_derive.py, and tests/test_abi_accept_gpu.py makes each row once on the GPU and
+expects rc 0."""
 import ctypes as C
 
 from tests.abi_cases import B16, F, U8, Case, Grouped, T

@@ -1,7 +1,7 @@
-"""One valid small call of include/minddet_hip_kittieval.h per call form, in the form of tests/abi_cases.py (operand kinds and rank
-flags are explained there).  tests/test_kitti_eval_device_cpu.py derives the single-defect calls with the machinery of
-tests/test_abi_checks_cpu.py (float64 rows: tests/pcaug_cases.py); tests/test_kitti_eval_device_gpu.py makes each row once on the GPU
-and expects rc 0.  The extents: I = 2 images, Gt = 5, Dt = 6, Cn = 2, K = 2, P = 16 pairs."""
+"""One valid small call of include/minddet_hip_kittieval.h per call form, in the form of tests/abi_cases.py (operand kinds and rank flags
+are explained there).  The feature's CPU test file hands each row to the single-defect test of tests/abi_derive.py, and
+tests/test_abi_accept_gpu.py makes each row once on the GPU and expects rc 0.  The extents: I = 2 images, Gt = 5, Dt = 6, Cn = 2, K = 2, P
+= 16 pairs."""
 from tests.abi_cases import I64, U8, Case, I, S, T, i32
 
 F64 = "float64"

@@ -1,7 +1,6 @@
-"""One valid small call of md_conv1x1_bwd_weight, md_grad_sumsq and md_adam_step (include/minddet_hip_train.h) per optional-operand
-form, in the form of tests/abi_cases.py (operand kinds and rank flags are explained there).  tests/test_train_ops_cpu.py derives the
-single-defect calls with the machinery of tests/test_abi_checks_cpu.py (float64 rows: tests/pcaug_cases.py); tests/test_conv_bwd_gpu.py
-and tests/test_optim_gpu.py make each row once on the GPU and expect rc 0."""
+"""One valid small call of md_conv1x1_bwd_weight, md_grad_sumsq and md_adam_step (include/minddet_hip_train.h) per optional-operand form,
+in the form of tests/abi_cases.py (operand kinds and rank flags are explained there).  The feature's CPU test file hands each row to the
+single-defect test of tests/abi_derive.py, and tests/test_abi_accept_gpu.py makes each row once on the GPU and expects rc 0."""
 from tests.abi_cases import B16, F, U8, Case, S, T, f64, i32
 
 F64 = "float64"

@@ -1,10 +1,20 @@
-"""Calls derived from the rows of the tests/abi_cases*.py tables, for the tests that make them: the single-defect calls that
-tests/test_abi_checks_cpu.py makes in-process (Call, mutations), and the same calls written as lines of a case file for the host replay
-program of tests/host/ (tests/test_host_replay_cpu.py), together with that test's hostile extents."""
+"""The call side of the ABI tests, stated once.  From the rows of the tests/abi_cases*.py tables: the single-defect calls (Call,
+mutations) and the test that makes them in-process (refuse_single_defects, with the kinds each table's rows must give rise to);
+the edit kit with which a feature's own test states its semantic
+refusals (lib_handle, edited, rc, raw and the edit constructors attr, item, shape, both); and the same calls written as lines of a
+case file for the host replay program of tests/host/ (tests/test_host_replay_cpu.py), together with that test's hostile extents.
+tests/abi_header.py is the header side."""
+import copy
 import ctypes as C
+import functools
+import os
 
-ITEM = {"float32": 4, "bfloat16": 2, "int32": 4, "int64": 8, "uint8": 1}
-WRONG_DTYPE = b"float64"    # no operand of any op is float64
+ITEM = {"float32": 4, "float64": 8, "bfloat16": 2, "int32": 4, "int64": 8, "uint8": 1}
+
+
+def wrong_dtype(t):
+    """a dtype operand t does not have: float64, and float32 for a float64 operand"""
+    return b"float32" if t.dtype == "float64" else b"float64"
 
 
 class Call:
@@ -95,7 +105,7 @@ def mutations(case):
             c.null_ptr[i] = True
             out.append(("ptr_null", i, c, 2))
         c = Call(case)
-        c.dtypes[i] = WRONG_DTYPE
+        c.dtypes[i] = wrong_dtype(t)
         out.append(("dtype", i, c, 2))
         for kind, shp in rank_defects(t):
             c = Call(case)
@@ -110,8 +120,116 @@ def mutations(case):
     return out
 
 
+# table -> the defects every one of its rows must give rise to, whatever its operands are (the main table has rows without a rank defect).
+# A new table gets its line here and a parametrised test over its rows that calls refuse_single_defects; tests/test_abi_checks_cpu.py
+# fails for a table that lacks either
+_EVERY = frozenset({"nparam", "params_null", "ndims_null", "shapes_null", "shape_null", "ptr_null", "dtype", "rank-1", "rank+1"})
+KINDS = {"abi_cases": frozenset()}
+KINDS.update({"abi_cases_" + t: _EVERY for t in ("chain", "cocoeval", "cpaug", "kitti", "kittieval", "pcaug")})
+KINDS.update({"abi_cases_" + t: _EVERY | {"extra_null"}
+              for t in ("cn", "cnaug", "cp", "cploss", "cpsweeps", "cptargets", "nusceval", "points", "pp", "pploss", "ppreader")})
+KINDS.update({"abi_cases_" + t: _EVERY | {"rank_without_dtypes", "extra_null"} for t in ("convbwd", "groupedbwd")})
+KINDS["abi_cases_train"] = _EVERY | {"rank_without_dtypes"}      # (its rows without an attribute struct have no extra_null)
+
+
+def refuse_single_defects(table, case):
+    """the single-defect test of one row of `table`: every derived call, made in-process with dummy host pointers (a refused call never
+    dereferences a tensor pointer), returns its documented code, and the kinds of KINDS[table] are all among them.  (This module is
+    not assertion-rewritten by pytest: every assert carries its own message.)"""
+    lib = lib_handle()
+    muts = mutations(case)
+    kinds = {k for k, _, _, _ in muts}
+    assert KINDS[table] <= kinds, (case.id, sorted(KINDS[table] - kinds))
+    assert ("extra_null" in kinds) == case.extra_required, case.id
+    if table == "abi_cases_train":
+        assert case.extra_required == (case.extra is not None), case.id
+    bad = []
+    for kind, i, call, expected in muts:
+        got = call.run(lib)          # the process surviving every one of these is part of the assertion
+        if got != expected:
+            bad.append((kind, i, got, expected))
+    assert not bad, f"{case.id}: (defect, operand, rc, expected) {bad}"
+
+
+# ----- the edit kit: a feature's semantic refusals are edits of a valid row, made in-process
+@functools.lru_cache(maxsize=None)
+def lib_handle():
+    """the library as a plain ctypes handle, built first if it is missing"""
+    from minddet_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        _lib.build()
+    return C.CDLL(_lib.LIB_PATH)
+
+
+def edited(case, edit):
+    """a Call of `case` after edit(copy of the case): the copy has its own attribute struct and operand list"""
+    c = copy.copy(case)
+    if case.extra is not None:
+        c.extra = type(case.extra).from_buffer_copy(case.extra)
+    c.operands = list(case.operands)
+    edit(c)
+    return Call(c)
+
+
+def rc(case, edit):
+    return edited(case, edit).run(lib_handle())
+
+
+def raw(case, edit=None, same=(), shift=None):
+    """the case's call after edit(copy) on dummy addresses 4 KiB apart and 4 KiB aligned (a refused call never dereferences a tensor
+    pointer, so the extents may describe more memory than exists); same = [(o, k)]: operand o gets the address of operand k;
+    shift = (o, bytes): operand o's address is moved by so many bytes -> rc"""
+    call = edited(case, edit or (lambda c: None))
+    ops, n = call.case.operands, call.n
+    arena = (C.c_char * (4096 * (n + 2)))()
+    base = (C.addressof(arena) + 4095) // 4096 * 4096
+    addr = {i: base + 4096 * i for i in range(n)}
+    for o, k in same:
+        addr[o] = addr[k]
+    if shift:
+        addr[shift[0]] += shift[1]
+    params, ndims = (C.c_void_p * n)(), (C.c_int * n)()
+    shapes, dtypes = (C.POINTER(C.c_int64) * n)(), (C.c_char_p * n)()
+    keep = []
+    for i in range(n):
+        params[i] = None if ops[i].null else addr[i]
+        shp = [] if ops[i].null else list(ops[i].shape)
+        ndims[i] = len(shp)
+        keep.append((C.c_int64 * max(len(shp), 1))(*shp))
+        shapes[i] = C.cast(keep[-1], C.POINTER(C.c_int64))
+        dtypes[i] = None if ops[i].null else ops[i].dtype.encode()
+    extra = None if call.case.extra is None else C.byref(call.case.extra)
+    return getattr(lib_handle(), call.case.sym)(n, params, ndims, shapes, dtypes, None, extra)
+
+
+def attr(name, v):
+    return lambda c: setattr(c.extra, name, v)
+
+
+def item(name, index, v):
+    """element `index` of the array attribute `name`"""
+    def edit(c):
+        getattr(c.extra, name)[index] = v
+    return edit
+
+
+def shape(i, shp, dtype=None):
+    """operand i with another shape (and dtype, where one is given); its kind, rank and why stay"""
+    def edit(c):
+        t = copy.copy(c.operands[i])
+        t.shape, t.dtype = tuple(shp), dtype or t.dtype
+        c.operands[i] = t
+    return edit
+
+
+def both(*edits):
+    def edit(c):
+        for e in edits:
+            e(c)
+    return edit
+
+
 # ----- the same calls as lines of a case file for tests/host/replay (the format is described at the top of tests/host/replay.cpp)
-ITEM64 = dict(ITEM, float64=8)
 # the hostile substitutions: a call that carries one is refused (1, 2 or 4, never 0)
 HOSTILE = (-1, -2 ** 63, 2 ** 31, 2 ** 32, 2 ** 62, 2 ** 63 - 1)
 WRAP_PAIRS = ((2 ** 32, 2 ** 32), (2 ** 31, 2 ** 33), (2 ** 33, 2 ** 31))      # products that wrap int64 to 0
@@ -128,7 +246,6 @@ def all_rows():
     """[(table, Case)] of every tests/abi_cases*.py table, in file order"""
     import glob
     import importlib
-    import os
     here = os.path.dirname(os.path.abspath(__file__))
     rows = []
     for path in sorted(glob.glob(os.path.join(here, "abi_cases*.py"))):
@@ -151,7 +268,7 @@ def call_line(ident, call, stream=0):
     """one CALL line: what Call.run hands the entry point, with the data pointers as offsets into the replay's arena (one block per
     operand, disjoint, as large as the VALID row's tensor: md_c3_pair / md_conv2d_grouped compare address ranges)"""
     ops, n = call.case.operands, call.n
-    sizes = [max(64, ITEM64[t.dtype] * max(1, _numel(t.shape)) + 64) for t in ops] + [64] * (n - len(ops))
+    sizes = [max(64, ITEM[t.dtype] * max(1, _numel(t.shape)) + 64) for t in ops] + [64] * (n - len(ops))
     sizes = [(s + 255) // 256 * 256 for s in sizes]
     words = ["CALL", ident.replace(" ", "_"), call.case.sym, str(stream), str(n),
              str(call.params_null * 1 + call.ndims_null * 2 + call.shapes_null * 4 + call.dtypes_null * 8),

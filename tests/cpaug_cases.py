@@ -1,6 +1,5 @@
 """What tests/test_cp_augment_cpu.py, tests/test_cp_augment_gpu.py and tools share about the CenterPoint training input: the fixture
-(tests/golden/cp_augment_vectors.npz) by case and the contract (tests/cpaug_contract.py) evaluated on it.  The single-defect calls for
-rows with float64 operands are those of tests/pcaug_cases.py (mutations64, edited)."""
+(tests/golden/cp_augment_vectors.npz) by case and the contract (tests/cpaug_contract.py) evaluated on it."""
 import functools
 import os
 

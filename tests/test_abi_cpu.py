@@ -5,9 +5,9 @@ import ctypes
 import os
 import re
 
-import pytest
 
 from minddet_amd import _lib
+from tests import abi_header as ah
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -62,7 +62,7 @@ def test_no_process_wide_tuning_setters_and_reserved0_is_checked():
     (md_conv_tune), the library exports no setter, and md_conv2d_attrs.reserved0 != 0 is MD_ERR_ARG (checked before any device call,
     so this runs without a GPU)."""
     lib = ctypes.CDLL(_lib.LIB_PATH)
-    hdr = open(os.path.join(ROOT, "include", "minddet_hip.h")).read()
+    hdr = ah.header("minddet_hip.h")
     assert "md_conv2d_set_" not in hdr
     for n in ("md_conv2d_set_chunk_limit", "md_conv2d_set_stream_rounds", "md_conv2d_set_stream_tune", "md_conv2d_set_pers_min_k",
               "md_conv2d_set_dual_pp_min_k"):
@@ -70,10 +70,9 @@ def test_no_process_wide_tuning_setters_and_reserved0_is_checked():
     from minddet_amd import nn_ops
 
     # the ctypes mirror has the header's field list (23 int32 + 6 int32 of md_conv_tune)
-    m = re.search(r"typedef struct md_conv2d_attrs \{(.*?)\} md_conv2d_attrs;", hdr, flags=re.S)
-    body = re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)
-    n_i32 = sum(len(d.split(",")) for d in re.findall(r"int32_t\s+([^;]+);", body))
-    assert n_i32 == 23 and "md_conv_tune tune;" in body
+    body = ah.statements("md_conv2d_attrs", hdr)
+    n_i32 = sum(len(s.split(",")) for s in body if re.match(r"int32_t\s", s))
+    assert n_i32 == 23 and "md_conv_tune tune" in body
     assert ctypes.sizeof(nn_ops._ConvAttrs) == 4 * (23 + 6) and ctypes.sizeof(nn_ops.ConvTune) == 24
     assert ctypes.sizeof(nn_ops._DualAttrs) == 4 * (2 + 6)
     # reserved0 != 0 -> rc 2; dummy host pointers are never dereferenced on this path

@@ -1,5 +1,5 @@
-"""CPU: the CenterNet training input without a GPU -- the ABI of include/minddet_hip_cnaug.h (the functions exported, the single-defect
-calls and the semantic refusals answered before any device call, the ctypes mirrors laid out as the header says), the contract
+"""CPU: the CenterNet training input without a GPU -- the ABI of include/minddet_hip_cnaug.h (the functions exported,
+the semantic refusals answered before any device call, the ctypes mirrors laid out as the header says), the contract
 tests/cnaug_contract.py against the reference's own values (tests/golden/cn_augment_vectors.npz, written by
 tests/golden/gen_cn_augment.py from COCOHP.preprocess_fn and color_aug; tests/golden/cn_target_vectors.npz for the targets behind the
 matrix), the sensitivity of the output to the order of the grey sum, det_ops.CenterNetAugment built from the train configs and its
@@ -7,7 +7,6 @@ refusals."""
 import ctypes as C
 import functools
 import os
-import re
 
 import numpy as np
 import pytest
@@ -16,13 +15,14 @@ import torch
 from minddet_amd import _lib, det_ops
 from tests import cn_targets_contract as ct
 from tests import cnaug_contract as cc
-from tests.abi_cases import B16, F, I, T
+from tests import abi_header as ah
+from tests.abi_cases import B16, I
 from tests.abi_cases_cnaug import CASES, F64, CNImage, CNTransform
-from tests.pcaug_cases import edited, mutations64
+from tests.abi_derive import attr, both, edited, lib_handle, rc, refuse_single_defects, shape
 from tests.test_cn_targets_cpu import fixture_case as targets_case
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = open(os.path.join(ROOT, "include", "minddet_hip_cnaug.h")).read()
+HDR = ah.header("minddet_hip_cnaug.h")
 GOLD = os.path.join(ROOT, "tests", "golden", "cn_augment_vectors.npz")
 SYMS = ["md_cn_aug_transform", "md_cn_aug_image"]
 U8 = "uint8"
@@ -48,20 +48,13 @@ def contract_transform(f, i):
     return cc.transform(f["size"][i:i + 1], f["draws"][i:i + 1], **attrs_of(f, i))
 
 
-def _lib_handle():
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    return C.CDLL(_lib.LIB_PATH)
-
-
 def test_header_declares_the_symbols_and_the_library_exports_them():
-    pat = r"^\s*int\s+(\w+)\s*\(MD_AOT_ARGS\)\s*;"     # the expression of _lib.exported_symbols
-    assert re.findall(pat, HDR, flags=re.M) == SYMS and '#include "minddet_hip.h"' in HDR
+    assert ah.aot_symbols(HDR) == SYMS and '#include "minddet_hip.h"' in HDR
     for cite in ("dataset.py:278-315", "image.py:208-253", "image.py:229", "image.py:29-30", "DESIGN 9 item 5"):
         assert cite in HDR, cite
     assert "minddet_hip_cnaug.h" in open(os.path.join(ROOT, "minddet_amd", "csrc", "Makefile")).read()
     assert {c.sym for c in CASES} == set(SYMS) and len({c.id for c in CASES}) == len(CASES)
-    lib = _lib_handle()
+    lib = lib_handle()
     for s in SYMS:
         assert getattr(lib, s)(0, None, None, None, None, None, None) == 1      # wrong parameter count, before anything else
     assert not set(SYMS) & set(_lib.exported_symbols())                          # declared in the new header only
@@ -71,9 +64,7 @@ def test_ctypes_mirrors_and_limits_have_the_headers_layout():
     want = {"md_cn_aug_transform_attrs": ["int32_t rand_crop", "double scale, shift", "double flip_prop", "int32_t in_h, in_w", "int32_t down_ratio"],
             "md_cn_aug_image_attrs": ["int32_t out_h, out_w, pad_lo, pad_hi"]}
     for name, fields in want.items():
-        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), HDR, flags=re.S).group(1)
-        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-        assert [s.strip() for s in body.split(";") if s.strip()] == fields
+        assert ah.statements(name, HDR) == fields
     for got in (det_ops._CNAugTransformAttrs, CNTransform):       # int32, pad, three doubles, three int32, pad
         assert C.sizeof(got) == 48
         assert [(n, getattr(got, n).offset) for n, _ in got._fields_] == [("rand_crop", 0), ("scale", 8), ("shift", 16), ("flip_prop", 24),
@@ -82,7 +73,7 @@ def test_ctypes_mirrors_and_limits_have_the_headers_layout():
         assert C.sizeof(got) == 16 and [n for n, _ in got._fields_] == ["out_h", "out_w", "pad_lo", "pad_hi"]
     src = open(os.path.join(ROOT, "minddet_amd", "csrc", "cnaug.hip")).read()
     assert "sizeof(md_cn_aug_transform_attrs) == 48 && sizeof(md_cn_aug_image_attrs) == 16" in src
-    defines = {k: int(v) for k, v in re.findall(r"^#define (\w+) (\d+)\b", HDR, flags=re.M)}
+    defines = ah.defines(HDR)
     assert (defines["MD_CNAUG_MAX_BATCH"], defines["MD_CNAUG_GREY_CHUNK"]) == (det_ops.CNAUG_MAX_BATCH, 2048) == (65535, 2048)
     assert det_ops.cn_aug_image_workspace_bytes(2, 6, 10) == 32 and det_ops.cn_aug_image_workspace_bytes(16, 512, 512) == 8 * 16 * 129
     # (the chunk decides: 2048 pixels are one partial sum per sample, one more pixel is two)
@@ -101,73 +92,45 @@ def test_sampler_is_stated_once_and_shared():
 
 @pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])
 def test_single_defect_calls_are_refused_without_a_device(case):
-    lib = _lib_handle()
-    muts = mutations64(case)
-    kinds = {k for k, _, _, _ in muts}
-    assert {"nparam", "params_null", "ndims_null", "shapes_null", "extra_null", "shape_null", "ptr_null", "dtype", "rank-1", "rank+1"} <= kinds
-    bad = [(kind, i, rc, want) for kind, i, call, want in muts for rc in [call.run(lib)] if rc != want]
-    assert not bad, f"{case.id}: (defect, operand, rc, expected) {bad}"
-
-
-def _rc(case, edit):
-    return edited(case, edit).run(_lib_handle())
-
-
-def _shape(i, shp, dtype=F):
-    def edit(c):
-        c.operands[i] = T(shp, dtype, c.operands[i].kind, c.operands[i].rank, why=c.operands[i].why)
-    return edit
-
-
-def _both(*edits):
-    def edit(c):
-        for e in edits:
-            e(c)
-    return edit
-
-
-def _attr(name, v):
-    def edit(c):
-        setattr(c.extra, name, v)
-    return edit
+    refuse_single_defects("abi_cases_cnaug", case)
 
 
 def test_semantic_refusals_return_the_documented_codes():
     nan, inf = float("nan"), float("inf")
     tr, tr_plain, img_ws, img_pool, img_plain = CASES
-    for i, e in enumerate([_shape(0, (2, 3), I), _shape(0, (3, 2), I), _shape(1, (3, 4), F64), _shape(1, (2, 5), F64), _shape(2, (2, 5)), _shape(2, (3, 6)),
-                           _shape(3, (2, 5), F64), _shape(3, (3, 6), F64), _shape(4, (3,), I)]):
-        assert _rc(tr, e) == ARG, i
+    for i, e in enumerate([shape(0, (2, 3), I), shape(0, (3, 2), I), shape(1, (3, 4), F64), shape(1, (2, 5), F64), shape(2, (2, 5)), shape(2, (3, 6)),
+                           shape(3, (2, 5), F64), shape(3, (3, 6), F64), shape(4, (3,), I)]):
+        assert rc(tr, e) == ARG, i
     for name, v in (("scale", nan), ("scale", inf), ("shift", nan), ("shift", -inf), ("flip_prop", nan), ("flip_prop", -0.01), ("flip_prop", 1.01),
                     ("down_ratio", 0), ("down_ratio", -4), ("in_h", 0), ("in_w", 0), ("in_h", 3)):          # (in_h below down_ratio: an empty map)
-        assert _rc(tr_plain, _attr(name, v)) == ARG, (name, v)
-    big = _both(_shape(0, (65536, 2), I), _shape(1, (65536, 4), F64), _shape(2, (65536, 6)), _shape(3, (65536, 6), F64), _shape(4, (65536,), I))
-    assert _rc(tr, big) == SIZE
+        assert rc(tr_plain, attr(name, v)) == ARG, (name, v)
+    big = both(shape(0, (65536, 2), I), shape(1, (65536, 4), F64), shape(2, (65536, 6)), shape(3, (65536, 6), F64), shape(4, (65536,), I))
+    assert rc(tr, big) == SIZE
 
-    for i, e in enumerate([_shape(0, (2, 8, 12, 4), U8), _shape(0, (3, 8, 12, 3), U8), _shape(1, (3, 2), I), _shape(1, (2, 3), I), _shape(2, (2, 5)), _shape(2, (3, 6)),
-                           _shape(3, (5,)), _shape(3, (7,)), _shape(4, (2, 7), F64), _shape(4, (3, 8), F64), _shape(5, (2, 6, 10, 3), B16),
-                           _shape(5, (2, 6, 10, 16), B16), _shape(5, (2, 7, 10, 8), B16), _shape(5, (2, 6, 11, 8), B16), _shape(5, (3, 6, 10, 8), B16),
-                           _attr("out_h", 0), _attr("out_w", -1), _attr("pad_lo", -1), _attr("pad_hi", 1)]):
-        assert _rc(img_ws, e) == ARG, i
-    assert _rc(img_plain, _shape(5, (2, 6, 10, 5), B16)) == ARG
-    assert _rc(img_ws, _shape(6, (31,), U8)) == SIZE and _rc(img_plain, _shape(5, (2, 22, 26, 4), B16)) == ARG      # (the stem pads need the attrs)
+    for i, e in enumerate([shape(0, (2, 8, 12, 4), U8), shape(0, (3, 8, 12, 3), U8), shape(1, (3, 2), I), shape(1, (2, 3), I), shape(2, (2, 5)), shape(2, (3, 6)),
+                           shape(3, (5,)), shape(3, (7,)), shape(4, (2, 7), F64), shape(4, (3, 8), F64), shape(5, (2, 6, 10, 3), B16),
+                           shape(5, (2, 6, 10, 16), B16), shape(5, (2, 7, 10, 8), B16), shape(5, (2, 6, 11, 8), B16), shape(5, (3, 6, 10, 8), B16),
+                           attr("out_h", 0), attr("out_w", -1), attr("pad_lo", -1), attr("pad_hi", 1)]):
+        assert rc(img_ws, e) == ARG, i
+    assert rc(img_plain, shape(5, (2, 6, 10, 5), B16)) == ARG
+    assert rc(img_ws, shape(6, (31,), U8)) == SIZE and rc(img_plain, shape(5, (2, 22, 26, 4), B16)) == ARG      # (the stem pads need the attrs)
     call = edited(img_pool, lambda c: None)               # (the shapes alone say B = 65536: the host blocks stay small, nothing is touched)
     for i, t in enumerate(call.case.operands):
         if i != 3:
             call.shapes[i] = [65536] + list(t.shape[1:])
-    assert call.run(_lib_handle()) == SIZE
+    assert call.run(lib_handle()) == SIZE
     call = edited(img_plain, lambda c: None)              # a source of 2^30 elements
     call.shapes[0] = [2, 16384, 16384, 3]
-    assert call.run(_lib_handle()) == SIZE
-    call = edited(img_plain, _attr("out_h", 1 << 14))     # an output of 2^30 elements
+    assert call.run(lib_handle()) == SIZE
+    call = edited(img_plain, attr("out_h", 1 << 14))     # an output of 2^30 elements
     call.case.extra.out_w = 1 << 13
     call.shapes[5] = [2, 1 << 14, 1 << 13, 8]
-    assert call.run(_lib_handle()) == SIZE
+    assert call.run(lib_handle()) == SIZE
 
 
 def _raw_call(case, patch):
     """the case's call with one host block per operand; patch(params) edits the pointer array"""
-    lib = _lib_handle()
+    lib = lib_handle()
     ops = case.operands
     n = len(ops)
     bufs = [(C.c_char * 65536)() for _ in range(n)]

@@ -1,4 +1,4 @@
-"""CPU: the CenterNet training loss without a GPU -- the ABI of include/minddet_hip_cn.h (the single-defect calls and the semantic
+"""CPU: the CenterNet training loss without a GPU -- the ABI of include/minddet_hip_cn.h (the semantic
 refusals answered before any device call), the contract tests/cn_loss_contract.py against a literal torch-float64 transcription of the
 reference's Sigmoid / FocalLoss / RegLoss / CenterNetLossCell under autograd on the committed reference targets
 (tests/golden/cn_target_vectors.npz), and the refusals of det_ops.CenterNetLoss."""
@@ -8,22 +8,17 @@ import torch
 
 from minddet_amd import det_ops
 from tests import cn_loss_contract as cl
-from tests.abi_cases import B16, F, I, U8
+from tests.abi_cases import B16, I, U8
 from tests.abi_cases_cn import LOSS_CASES
-from tests.test_abi_checks_cpu import mutations
-from tests.test_cn_targets_cpu import _lib_handle, attr, both, fixture_case, rc_of, shape
+from tests.abi_derive import attr, both, rc, refuse_single_defects, shape
+from tests.test_cn_targets_cpu import fixture_case
 
 WEIGHTS = dict(hm_weight=1.0, wh_weight=float(np.float32(0.1)), off_weight=1.0)      # the values an fp32 attribute struct carries
 
 
 @pytest.mark.parametrize("case", LOSS_CASES, ids=[c.id for c in LOSS_CASES])
 def test_single_defect_calls_are_refused_without_a_device(case):
-    lib = _lib_handle()
-    muts = mutations(case)
-    kinds = {k for k, _, _, _ in muts}
-    assert {"nparam", "params_null", "ndims_null", "shapes_null", "extra_null", "shape_null", "ptr_null", "dtype", "rank-1", "rank+1"} <= kinds
-    bad = [(kind, i, rc, want) for kind, i, call, want in muts for rc in [call.run(lib)] if rc != want]
-    assert not bad, f"{case.id}: (defect, operand, rc, expected) {bad}"
+    refuse_single_defects("abi_cases_cn", case)
 
 
 @pytest.mark.parametrize("case", [LOSS_CASES[0], LOSS_CASES[3]], ids=[LOSS_CASES[0].id, LOSS_CASES[3].id])
@@ -44,18 +39,18 @@ def test_semantic_refusals_return_the_documented_codes(case):
     if grad:
         edits += [shape(9, (1, 8, 12, 16)), shape(9, (1, 12, 8, 8)), shape(9, (2, 8, 12, 8))]
     for i, e in enumerate(edits):
-        assert rc_of(case, e) == ARG, i
-    assert rc_of(case, attr("off_reg", -1)) is not None                                       # (no offset head: accepted, checked on the GPU)
+        assert rc(case, e) == ARG, i
+    assert rc(case, attr("off_reg", -1)) is not None                                       # (no offset head: accepted, checked on the GPU)
     big = 1100                                                                                # M above the LDS bound
     grow = both(shape(2, (1, big), I), shape(3, (1, big), U8), shape(4, (1, big, 2)), shape(5, (1, big, 2)))
-    assert rc_of(case, grow) == SIZE
+    assert rc(case, grow) == SIZE
     wide = both(shape(0, (1, 8, 12, 168), B16), *([shape(9, (1, 8, 12, 168))] if grad else []))   # Cp above the LDS bound
-    assert rc_of(case, wide) == SIZE
+    assert rc(case, wide) == SIZE
     huge = both(shape(0, (1, 1 << 14, 1 << 13, 8), B16), shape(1, (1, 3, 1 << 14, 1 << 13)),      # operands of 2^30 elements and more
                 *([shape(9, (1, 1 << 14, 1 << 13, 8))] if grad else []))
-    assert rc_of(case, huge) == SIZE
+    assert rc(case, huge) == SIZE
     if "[workspace]" in case.id:
-        assert rc_of(case, shape(len(case.operands) - 1, (67,), U8)) == SIZE                  # one byte short
+        assert rc(case, shape(len(case.operands) - 1, (67,), U8)) == SIZE                  # one byte short
 
 
 # ---------------------------------------------------------------------------------------------------- the reference, transcribed

@@ -1,31 +1,24 @@
-"""CPU: the CenterNet training targets without a GPU -- the ABI of include/minddet_hip_cn.h (the function exported, the single-defect
-calls and the semantic refusals answered before any device call, the ctypes mirrors laid out as the header says), the contract
+"""CPU: the CenterNet training targets without a GPU -- the ABI of include/minddet_hip_cn.h (the function exported,
+the semantic refusals answered before any device call, the ctypes mirrors laid out as the header says), the contract
 tests/cn_targets_contract.py against the reference's own outputs (tests/golden/cn_target_vectors.npz, written by
 tests/golden/gen_cn_targets.py from COCOHP.preprocess_fn), the flip and affine transform in front of it, and the configs."""
-import copy
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
 
-from minddet_amd import _lib, det_ops
+from minddet_amd import det_ops
 from tests import cn_targets_contract as ct
-from tests.abi_cases import F, I, T, U8
+from tests import abi_header as ah
+from tests.abi_cases import I, U8
 from tests.abi_cases_cn import CASES, TARGET_CASES, CNLoss, CNTargets
-from tests.test_abi_checks_cpu import Call, mutations
+from tests.abi_derive import attr, both, lib_handle, rc, refuse_single_defects, shape
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = open(os.path.join(ROOT, "include", "minddet_hip_cn.h")).read()
+HDR = ah.header("minddet_hip_cn.h")
 GOLD = os.path.join(ROOT, "tests", "golden", "cn_target_vectors.npz")
 NAMES = ("small", "tiles", "plants")
-
-
-def _lib_handle():
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    return C.CDLL(_lib.LIB_PATH)
 
 
 def fixture_case(name):
@@ -38,29 +31,12 @@ def fixture_case(name):
     return inputs, kw, {k: z[name + "_" + k] for k in ct.KEYS}
 
 
-def struct_of(text, name):
-    """the ctypes mirror of `typedef struct name { ... } name;` in the header"""
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), text, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = []
-    for stmt in filter(None, (s.strip() for s in body.split(";"))):
-        ty, decl = stmt.split(None, 1)
-        for d in decl.split(","):
-            fields.append((d.strip(), {"int32_t": C.c_int32, "float": C.c_float}[ty]))
-    return type(name, (C.Structure,), {"_fields_": fields})
-
-
-def layout(s):
-    return [(n, getattr(s, n).offset, getattr(s, n).size) for n, _ in s._fields_]
-
-
 def test_header_declares_the_three_symbols_and_the_library_exports_them():
-    pat = r"^\s*int\s+(\w+)\s*\(MD_AOT_ARGS\)\s*;"     # the expression of _lib.exported_symbols
-    assert re.findall(pat, HDR, flags=re.M) == ["md_cn_assign_targets", "md_cn_loss", "md_cn_loss_grad"] and '#include "minddet_hip.h"' in HDR
+    assert ah.aot_symbols(HDR) == ["md_cn_assign_targets", "md_cn_loss", "md_cn_loss_grad"] and '#include "minddet_hip.h"' in HDR
     assert "dataset.py:317-384" in HDR and "image.py:94-144" in HDR and "centernet_det.py:177-237" in HDR and "utils.py:48-245" in HDR
     assert "minddet_hip_cn.h" in open(os.path.join(ROOT, "minddet_amd", "csrc", "Makefile")).read()
     assert {c.sym for c in CASES} == {"md_cn_assign_targets", "md_cn_loss", "md_cn_loss_grad"} and len({c.id for c in CASES}) == len(CASES)
-    lib = _lib_handle()
+    lib = lib_handle()
     for sym in ("md_cn_assign_targets", "md_cn_loss", "md_cn_loss_grad"):
         assert getattr(lib, sym)(0, None, None, None, None, None, None) == 1             # wrong parameter count, before anything else
 
@@ -68,13 +44,13 @@ def test_header_declares_the_three_symbols_and_the_library_exports_them():
 def test_ctypes_mirrors_have_the_headers_layout():
     for name, mirrors, size in (("md_cn_targets_attrs", (det_ops._CNTargetsAttrs, CNTargets), 4),
                                 ("md_cn_loss_attrs", (det_ops._CNLossAttrs, CNLoss), 28)):
-        want = struct_of(HDR, name)
+        want = ah.struct_of(name, HDR)
         assert C.sizeof(want) == size
         for got in mirrors:
-            assert C.sizeof(got) == size and layout(got) == layout(want), got
+            assert C.sizeof(got) == size and ah.layout(got) == ah.layout(want), got
     src = "".join(open(os.path.join(ROOT, "minddet_amd", "csrc", f)).read() for f in ("cntargets.hip", "cnloss.hip"))
     assert "static_assert(sizeof(md_cn_targets_attrs) == 4" in src and "static_assert(sizeof(md_cn_loss_attrs) == 4 * 4 + 3 * 4" in src
-    defines = {k: int(v) for k, v in re.findall(r"^#define (\w+) (\d+)\b", HDR, flags=re.M)}
+    defines = ah.defines(HDR)
     assert (defines["MD_CN_MAX_OBJS"], defines["MD_CN_LOSS_STRIP"], defines["MD_CN_LOSS_COUNT_CHUNK"]) == (det_ops.CN_MAX_OBJS, 64, 16384)
     # (each decides the library's answer: 64 cells are one strip of 16 bytes, 16384 heat-map elements one count of 4)
     assert [det_ops.cn_loss_workspace_bytes(1, 1, 1, w) for w in (64, 65)] == [8 * (4 + 2) + 4, 8 * (4 + 4) + 4]
@@ -83,37 +59,7 @@ def test_ctypes_mirrors_have_the_headers_layout():
 
 @pytest.mark.parametrize("case", TARGET_CASES, ids=[c.id for c in TARGET_CASES])
 def test_single_defect_calls_are_refused_without_a_device(case):
-    lib = _lib_handle()
-    muts = mutations(case)
-    kinds = {k for k, _, _, _ in muts}
-    assert {"nparam", "params_null", "ndims_null", "shapes_null", "extra_null", "shape_null", "ptr_null", "dtype", "rank-1", "rank+1"} <= kinds
-    bad = [(kind, i, rc, want) for kind, i, call, want in muts for rc in [call.run(lib)] if rc != want]
-    assert not bad, f"{case.id}: (defect, operand, rc, expected) {bad}"
-
-
-def rc_of(case, edit):
-    c = copy.copy(case)
-    c.extra = type(case.extra).from_buffer_copy(case.extra)
-    c.operands = list(case.operands)
-    edit(c)
-    return Call(c).run(_lib_handle())
-
-
-def shape(i, shp, dtype=F):
-    def edit(c):
-        c.operands[i] = T(shp, dtype)
-    return edit
-
-
-def both(*edits):
-    def edit(c):
-        for e in edits:
-            e(c)
-    return edit
-
-
-def attr(name, value):
-    return lambda c: setattr(c.extra, name, value)
+    refuse_single_defects("abi_cases_cn", case)
 
 
 def test_semantic_refusals_return_the_documented_codes():
@@ -128,15 +74,15 @@ def test_semantic_refusals_return_the_documented_codes():
         shape(6, (1, 4, 1)),
     ]
     for i, e in enumerate(edits):
-        assert rc_of(case, e) == ARG, i
+        assert rc(case, e) == ARG, i
     big = 1100                                                                            # M above the LDS bound
     grow = both(shape(3, (1, big), I), shape(4, (1, big), U8), shape(5, (1, big, 2)), shape(6, (1, big, 2)))
-    assert rc_of(case, grow) == SIZE
-    assert rc_of(case, shape(2, (1, 70000, 8, 12))) == SIZE                               # C above the grid bound
-    assert rc_of(case, shape(2, (1, 3, 1 << 15, 1 << 14))) == SIZE                        # an operand of 2^30 elements and more
-    assert rc_of(TARGET_CASES[1], shape(7, (63,), U8)) == SIZE                            # one byte short of 16 B M
+    assert rc(case, grow) == SIZE
+    assert rc(case, shape(2, (1, 70000, 8, 12))) == SIZE                               # C above the grid bound
+    assert rc(case, shape(2, (1, 3, 1 << 15, 1 << 14))) == SIZE                        # an operand of 2^30 elements and more
+    assert rc(TARGET_CASES[1], shape(7, (63,), U8)) == SIZE                            # one byte short of 16 B M
     for ok in (1e-9, 0.999, float(np.float32(1.0) - np.float32(2.0) ** -24)):             # every fp32 value inside (0, 1) passes the checks
-        assert rc_of(case, both(attr("min_overlap", ok), shape(2, (1, 70000, 8, 12)))) == SIZE
+        assert rc(case, both(attr("min_overlap", ok), shape(2, (1, 70000, 8, 12)))) == SIZE
 
 
 @pytest.mark.parametrize("name", NAMES)

@@ -1,5 +1,5 @@
 """CPU: the COCO bbox AP operators without a GPU -- the ABI of include/minddet_hip_cocoeval.h (the three functions exported, header and
-Makefile wired, the single-defect calls, every documented rc 2 / rc 4 and aliasing answered before any device call, the ctypes mirrors
+Makefile wired, every documented rc 2 / rc 4 and aliasing answered before any device call, the ctypes mirrors
 and limits laid out as the header says), the Python layer's refusals, coco_eval.pack_coco against what COCOBboxEval groups, the contract
 (tests/coco_eval_contract.py) against COCOBboxEval.evaluate() bit for bit, the to_float recipe against Python's formatting, and the six
 planted defects, each of which must change the contract's tables on the test set."""
@@ -15,12 +15,11 @@ import torch
 from minddet_amd import _lib, det_ops
 from minddet_amd import coco_eval as ce
 from tests import coco_eval_contract as cc
-from tests.abi_cases import T
-from tests.abi_cases_cocoeval import CASES, CELLS, DT, GT, KC, MAX_DET, NA, NI, NL, NM, NR, NT, RowsAttrs
-from tests.pcaug_cases import edited, mutations64
+from tests import abi_header as ah
+from tests.abi_cases_cocoeval import CASES, CELLS, DT, GT, KC, MAX_DET, NA, NI, NM, NR, NT, RowsAttrs
+from tests.abi_derive import attr, edited, lib_handle, rc, refuse_single_defects, shape
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR_PATH = os.path.join(ROOT, "include", "minddet_hip_cocoeval.h")
 SYMS = ["md_coco_eval_rows", "md_coco_eval_match", "md_coco_eval_accumulate"]
 ARG, SIZE = 2, 4
 BY_ID = {c.id: c for c in CASES}
@@ -28,15 +27,9 @@ EV = ce.COCOBboxEval
 AREA = np.array(list(EV.AREA_RNG.values()), np.float64)
 
 
-def _lib_handle():
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    return C.CDLL(_lib.LIB_PATH)
-
-
 def test_header_declares_the_symbols_and_the_library_exports_them():
-    hdr = open(HDR_PATH).read()
-    assert re.findall(r"^\s*int\s+(\w+)\s*\(MD_AOT_ARGS\)\s*;", hdr, flags=re.M) == SYMS and "_workspace_bytes" not in hdr
+    hdr = ah.header("minddet_hip_cocoeval.h")
+    assert ah.aot_symbols(hdr) == SYMS and "_workspace_bytes" not in hdr
     for cite in ("post_process.py:64-89", "centernet/eval.py:181-187", "fma(v, 100, -p)", "the highest row on equal IoU"):
         assert cite in hdr, cite
     mk = open(os.path.join(ROOT, "minddet_amd", "csrc", "Makefile")).read()
@@ -45,7 +38,7 @@ def test_header_declares_the_symbols_and_the_library_exports_them():
     assert src.index("#pragma clang fp contract(off)") < src.index('#include "aot.h"') and ".acquire(" not in src and not re.search(r"atomic\w*\(", src)
     assert '#include "workgroup.h"' in src and "hipMemset" not in src
     assert {c.sym for c in CASES} == set(SYMS) and len({c.id for c in CASES}) == len(CASES)
-    lib = _lib_handle()
+    lib = lib_handle()
     for sym in SYMS:
         assert getattr(lib, sym)(0, None, None, None, None, None, None) == 1      # wrong parameter count, before anything else
         assert sym not in _lib.exported_symbols()                                  # declared in the new header only
@@ -55,12 +48,11 @@ def test_header_declares_the_symbols_and_the_library_exports_them():
 
 
 def test_ctypes_mirrors_and_limits_have_the_headers_layout():
-    hdr = open(HDR_PATH).read()
-    body = re.search(r"typedef struct md_coco_eval_rows_attrs \{(.*?)\} md_coco_eval_rows_attrs;", hdr, flags=re.S).group(1)
-    assert [s.strip() for s in re.sub(r"/\*.*?\*/", "", body, flags=re.S).split(";") if s.strip()] == ["int32_t first_image"]
+    hdr = ah.header("minddet_hip_cocoeval.h")
+    assert ah.statements("md_coco_eval_rows_attrs", hdr) == ["int32_t first_image"]
     for got in (det_ops._CocoEvalRowsAttrs, RowsAttrs):
         assert C.sizeof(got) == 4 and got.first_image.offset == 0
-    macros = {k: int(v) for k, v in re.findall(r"#define MD_COCOEVAL_(\w+) (\d+)", hdr)}
+    macros = {k[len("MD_COCOEVAL_"):]: v for k, v in ah.defines(hdr).items() if k.startswith("MD_COCOEVAL_")}
     assert set(macros) == {"MAX_DETS", "MAX_GTS", "MAX_IMAGE_DETS", "MAX_CELLS", "MAX_CATS", "MAX_ROWS", "MAX_LABELS", "MAX_THRS", "MAX_AREAS", "MAX_RECS",
                            "MAX_MAXDETS"}
     for name, v in macros.items():
@@ -72,29 +64,7 @@ def test_ctypes_mirrors_and_limits_have_the_headers_layout():
 
 @pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])
 def test_single_defect_calls_are_refused_without_a_device(case):
-    lib = _lib_handle()
-    muts = mutations64(case)
-    kinds = {k for k, _, _, _ in muts}
-    want = {"nparam", "params_null", "ndims_null", "shapes_null", "shape_null", "ptr_null", "dtype", "rank-1", "rank+1"}
-    assert want | ({"extra_null"} if case.extra_required else set()) <= kinds
-    bad = [(kind, i, rc, want) for kind, i, call, want in muts for rc in [call.run(lib)] if rc != want]
-    assert not bad, f"{case.id}: (defect, operand, rc, expected) {bad}"
-
-
-def _rc(case, edit):
-    return edited(case, edit).run(_lib_handle())
-
-
-def _shape(i, shp):
-    def edit(c):
-        c.operands[i] = T(shp, c.operands[i].dtype, c.operands[i].kind, c.operands[i].rank, why=c.operands[i].why)
-    return edit
-
-
-def _attr(field, v):
-    def edit(c):
-        setattr(c.extra, field, v)
-    return edit
+    refuse_single_defects("abi_cases_cocoeval", case)
 
 
 def _described(case, shapes):
@@ -103,27 +73,27 @@ def _described(case, shapes):
     call = edited(case, lambda c: None)
     for i, shp in shapes.items():
         call.shapes[i] = list(shp)
-    return call.run(_lib_handle())
+    return call.run(lib_handle())
 
 
 def test_semantic_refusals_return_the_documented_codes():
     rows, match, accum = BY_ID["md_coco_eval_rows[whole set]"], BY_ID["md_coco_eval_match"], BY_ID["md_coco_eval_accumulate"]
     # every extent that disagrees: rc 2
-    for i, e in enumerate([_shape(0, (NI, MAX_DET, 5)), _shape(0, (NI, 3, 6)), _shape(1, (NI + 1,)), _shape(3, (DT, 3)), _shape(3, (DT + 1, 4)), _shape(4, (DT - 1,)),
-                           _shape(5, (DT + 1,)), _shape(6, (DT - 1,)), _shape(7, (DT + 1,)), _shape(8, (CELLS + 1,)), _shape(9, (CELLS - 1,)), _shape(10, (DT + 1,)),
-                           _shape(0, (NI + 1, MAX_DET, 6)), _attr("first_image", -1), _attr("first_image", 1), _attr("first_image", NI)]):
-        assert _rc(rows, e) == ARG, i
+    for i, e in enumerate([shape(0, (NI, MAX_DET, 5)), shape(0, (NI, 3, 6)), shape(1, (NI + 1,)), shape(3, (DT, 3)), shape(3, (DT + 1, 4)), shape(4, (DT - 1,)),
+                           shape(5, (DT + 1,)), shape(6, (DT - 1,)), shape(7, (DT + 1,)), shape(8, (CELLS + 1,)), shape(9, (CELLS - 1,)), shape(10, (DT + 1,)),
+                           shape(0, (NI + 1, MAX_DET, 6)), attr("first_image", -1), attr("first_image", 1), attr("first_image", NI)]):
+        assert rc(rows, e) == ARG, i
     assert _described(rows, {8: (CELLS + 1,), 9: (CELLS + 1,)}) == ARG             # seven cells over two images
-    for i, e in enumerate([_shape(1, (CELLS + 1,)), _shape(2, (CELLS - 1,)), _shape(3, (CELLS + 1,)), _shape(4, (GT, 5)), _shape(5, (GT + 1,)), _shape(6, (GT - 1,)),
-                           _shape(7, (GT + 1,)), _shape(8, (DT, 5)), _shape(9, (DT + 1,)), _shape(11, (NA, 3)), _shape(11, (NA + 1, 2)), _shape(10, (NT + 1,)),
-                           _shape(12, (NA, NT, DT + 1)), _shape(13, (NA, NT + 1, DT)), _shape(13, (NA + 1, NT, DT)), _shape(14, (NA, CELLS + 1)),
-                           _shape(14, (NA + 1, CELLS))]):
-        assert _rc(match, e) == ARG, i
-    for i, e in enumerate([_shape(0, (DT + 1,)), _shape(2, (DT - 1,)), _shape(1, (KC + 2,)), _shape(1, (1,)), _shape(4, (NA, NT, DT + 1)), _shape(4, (NA, NT + 1, DT)),
-                           _shape(5, (NA + 1, CELLS)), _shape(5, (NA, CELLS + 1)), _shape(6, (NR + 1,)), _shape(7, (NM + 1,)), _shape(8, (NT, NR, KC, NA, NM + 1)),
-                           _shape(8, (NT, NR, KC + 1, NA, NM)), _shape(9, (NT, KC, NA + 1, NM)), _shape(9, (NT + 1, KC, NA, NM)), _shape(10, (NA, KC + 1)),
-                           _shape(10, (NA + 1, KC))]):
-        assert _rc(accum, e) == ARG, i
+    for i, e in enumerate([shape(1, (CELLS + 1,)), shape(2, (CELLS - 1,)), shape(3, (CELLS + 1,)), shape(4, (GT, 5)), shape(5, (GT + 1,)), shape(6, (GT - 1,)),
+                           shape(7, (GT + 1,)), shape(8, (DT, 5)), shape(9, (DT + 1,)), shape(11, (NA, 3)), shape(11, (NA + 1, 2)), shape(10, (NT + 1,)),
+                           shape(12, (NA, NT, DT + 1)), shape(13, (NA, NT + 1, DT)), shape(13, (NA + 1, NT, DT)), shape(14, (NA, CELLS + 1)),
+                           shape(14, (NA + 1, CELLS))]):
+        assert rc(match, e) == ARG, i
+    for i, e in enumerate([shape(0, (DT + 1,)), shape(2, (DT - 1,)), shape(1, (KC + 2,)), shape(1, (1,)), shape(4, (NA, NT, DT + 1)), shape(4, (NA, NT + 1, DT)),
+                           shape(5, (NA + 1, CELLS)), shape(5, (NA, CELLS + 1)), shape(6, (NR + 1,)), shape(7, (NM + 1,)), shape(8, (NT, NR, KC, NA, NM + 1)),
+                           shape(8, (NT, NR, KC + 1, NA, NM)), shape(9, (NT, KC, NA + 1, NM)), shape(9, (NT + 1, KC, NA, NM)), shape(10, (NA, KC + 1)),
+                           shape(10, (NA + 1, KC))]):
+        assert rc(accum, e) == ARG, i
     # every documented limit: rc 4 (the descriptions alone say so)
     D = det_ops
     md1 = D.COCOEVAL_MAX_IMAGE_DETS + 1
@@ -159,7 +129,7 @@ def test_semantic_refusals_return_the_documented_codes():
 
 def test_aliased_outputs_are_refused():
     """an output at the address of an input or of another output: rc 2 before any device call"""
-    lib = _lib_handle()
+    lib = lib_handle()
     for cid, pairs in (("md_coco_eval_rows[whole set]", ((3, 0), (6, 1), (7, 6), (9, 8), (10, 2), (5, 4))),
                        ("md_coco_eval_match", ((12, 0), (13, 6), (13, 12), (14, 3), (14, 12))),
                        ("md_coco_eval_accumulate", ((8, 6), (9, 8), (10, 5), (10, 1)))):

@@ -1,5 +1,5 @@
 """CPU: the conv-backward operators without a GPU -- the ABI of include/minddet_hip_convbwd.h (the two operators and the workspace function
-exported, the single-defect calls and the semantic refusals answered before any device call, the ctypes mirrors laid out as the header
+exported, the semantic refusals answered before any device call, the ctypes mirrors laid out as the header
 says), the judges of tests/convbwd_contract.py against torch-CPU float64 autograd of F.conv2d (weight, bias and input gradients for
 k = 1 and 3 over several images: the contract is pinned independently of a hand derivation), the column-order map against
 nn_ops.pack_conv, optim.multi_epochs_decay_lr by hand-computed values and the two CenterNet train configs' optimizer blocks."""
@@ -13,21 +13,15 @@ import torch
 
 from minddet_amd import _lib, det_ops, nn_ops, optim
 from tests import convbwd_contract as cc, train_contract as tc
-from tests.abi_cases import B16, F, T, U8
+from tests import abi_header as ah
+from tests.abi_cases import B16, U8
 from tests.abi_cases_convbwd import CASES, Block, Conv1x1BwdData, ConvBwd, workspace_bytes
-from tests.pcaug_cases import edited, mutations64
-from tests.test_cp_loss_cpu import _struct_of
+from tests.abi_derive import attr, both, edited, lib_handle, raw, rc, refuse_single_defects, shape
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = open(os.path.join(ROOT, "include", "minddet_hip_convbwd.h")).read()
+HDR = ah.header("minddet_hip_convbwd.h")
 OPS = ["md_conv_bwd_weight", "md_conv1x1_bwd_data"]
 ARG, SIZE = 2, 4
-
-
-def _lib_handle():
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    return C.CDLL(_lib.LIB_PATH)
 
 
 def _case(tag, sym):
@@ -35,8 +29,7 @@ def _case(tag, sym):
 
 
 def test_header_declares_the_operators_and_the_library_exports_them():
-    pat = r"^\s*int\s+(\w+)\s*\(MD_AOT_ARGS\)\s*;"
-    assert re.findall(pat, HDR, flags=re.M) == OPS and '#include "minddet_hip_train.h"' in HDR
+    assert ah.aot_symbols(HDR) == OPS and '#include "minddet_hip_train.h"' in HDR
     ws = re.findall(r"^extern int64_t (\w+_workspace_bytes)\((?:int64_t \w+(?:, )?)+\);", HDR, flags=re.M)
     assert ws == ["md_conv_bwd_weight_workspace_bytes"] and not re.search(r"^int64_t ", HDR, flags=re.M)
     assert re.search(r"^int md_conv_bwd_weight\(MD_AOT_ARGS\);\nextern int64_t md_conv_bwd_weight_workspace_bytes\(", HDR, flags=re.M)
@@ -44,7 +37,7 @@ def test_header_declares_the_operators_and_the_library_exports_them():
     src = open(os.path.join(ROOT, "minddet_amd", "csrc", "convbwd.hip")).read()
     assert "acquire_aligned(" in src and ".acquire(" not in src and not re.search(r"atomic\w*\(", src)
     assert {c.sym for c in CASES} == set(OPS) and len({c.id for c in CASES}) == len(CASES)
-    lib = _lib_handle()
+    lib = lib_handle()
     for sym in OPS:
         assert getattr(lib, sym)(0, None, None, None, None, None, None) == 1             # wrong parameter count, before anything else
     assert hasattr(lib, ws[0])
@@ -57,7 +50,7 @@ def test_header_declares_the_operators_and_the_library_exports_them():
 
 
 def test_workspace_function_follows_the_headers_formula():
-    defines = {k: int(v) for k, v in re.findall(r"^#define (\w+) (\d+)\b", HDR, flags=re.M)}
+    defines = ah.defines(HDR)
     assert (defines["MD_CONV_BWD_MAX_CIN_K1"], defines["MD_CONV_BWD_MAX_CIN_K3"], defines["MD_CONV_BWD_MAX_COUT"], defines["MD_CONV_BWD_MAX_BLOCKS"]) == \
         (1024, 256, 256, 4)
     assert (defines["MD_CONV1X1_BWD_DATA_MAX_CIN"], defines["MD_CONV1X1_BWD_DATA_MAX_COUT"]) == (1024, 256)
@@ -70,7 +63,7 @@ def test_workspace_function_follows_the_headers_formula():
             assert det_ops.conv_bwd_weight_workspace_bytes(P, cin, cout, k) == 4 * n * R * (k * k * cin + 1), (P, cin, cout, k)
         assert det_ops.conv_bwd_weight_workspace_bytes(P, cin, cout, 1) == det_ops.conv1x1_bwd_weight_workspace_bytes(P, cin, cout)
     assert workspace_bytes(3) == det_ops.conv_bwd_weight_workspace_bytes(15, 8, 3, 3)
-    f = _lib_handle().md_conv_bwd_weight_workspace_bytes
+    f = lib_handle().md_conv_bwd_weight_workspace_bytes
     f.restype, f.argtypes = C.c_int64, [C.c_int64] * 4
     assert f(8, 8, 8, 3) > 0 and all(f(*[-1 if j == k else 8 for j in range(3)], 3) == -1 for k in range(3))     # a negative extent answers -1
     assert f(8, 8, 8, 2) == -1 and f(8, 8, 8, -1) == -1                                                        # so does a kernel the op does not have
@@ -79,17 +72,14 @@ def test_workspace_function_follows_the_headers_formula():
 
 
 def test_ctypes_mirrors_have_the_headers_layout():
-    block = _struct_of(HDR, "md_conv_bwd_block", {})
-    conv = _struct_of(HDR, "md_conv_bwd_attrs", {"md_conv_bwd_block": block})
-    data = _struct_of(HDR, "md_conv1x1_bwd_data_attrs", {})
+    block = ah.struct_of("md_conv_bwd_block", HDR)
+    conv = ah.struct_of("md_conv_bwd_attrs", HDR, known={"md_conv_bwd_block": block})
+    data = ah.struct_of("md_conv1x1_bwd_data_attrs", HDR)
     assert C.sizeof(block) == 16 and C.sizeof(conv) == 24 * 4 and C.sizeof(data) == 6 * 4
-
-    def layout(s):
-        return [(n, getattr(s, n).offset, getattr(s, n).size) for n, _ in s._fields_]
 
     for got, want in ((det_ops._ConvBwdBlock, block), (Block, block), (det_ops._ConvBwdAttrs, conv), (ConvBwd, conv),
                       (det_ops._Conv1x1BwdDataAttrs, data), (Conv1x1BwdData, data)):
-        assert C.sizeof(got) == C.sizeof(want) and layout(got) == layout(want), got
+        assert ah.same_layout(got, want), got
     at = det_ops.conv_bwd_attrs(64, 9, 4, 3, kernel=3, korder=1, blocks=[(0, 5, 0, 8), (5, 2, 8, 8)])
     assert [getattr(at, n) for n in ("cin", "cout", "x_c_off", "dy_c_off", "kernel", "korder", "n_blocks", "reserved0")] == [64, 9, 4, 3, 3, 1, 2, 0]
     assert [(b.row0, b.rows, b.col0, b.cols) for b in at.blocks] == [(0, 5, 0, 8), (5, 2, 8, 8), (0, 0, 0, 0), (0, 0, 0, 0)]
@@ -99,43 +89,7 @@ def test_ctypes_mirrors_have_the_headers_layout():
 
 @pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])
 def test_single_defect_calls_are_refused_without_a_device(case):
-    lib = _lib_handle()
-    muts = mutations64(case)
-    kinds = {k for k, _, _, _ in muts}
-    want = {"nparam", "params_null", "ndims_null", "shapes_null", "shape_null", "ptr_null", "dtype", "rank-1", "rank+1", "rank_without_dtypes", "extra_null"}
-    assert want <= kinds
-    bad = [(kind, i, rc, want) for kind, i, call, want in muts for rc in [call.run(lib)] if rc != want]
-    assert not bad, f"{case.id}: (defect, operand, rc, expected) {bad}"
-
-
-def _rc(case, edit):
-    return edited(case, edit).run(_lib_handle())
-
-
-def _raw(case, edit=None, same=()):
-    """the case's call after edit(copy) on dummy addresses 4 KiB apart (a refused call never dereferences a tensor pointer, so the
-    extents may describe more memory than exists); same = [(o, k)]: operand o gets the address of operand k -> rc"""
-    call = edited(case, edit or (lambda c: None))
-    ops, n = call.case.operands, call.n
-    arena = (C.c_char * (4096 * (n + 1)))()
-    addr = {i: C.addressof(arena) + 4096 * i for i in range(n)}
-    for o, k in same:
-        addr[o] = addr[k]
-    params, ndims = (C.c_void_p * n)(), (C.c_int * n)()
-    shapes, dtypes = (C.POINTER(C.c_int64) * n)(), (C.c_char_p * n)()
-    keep = []
-    for i in range(n):
-        params[i] = None if ops[i].null else addr[i]
-        shp = [] if ops[i].null else list(ops[i].shape)
-        ndims[i] = len(shp)
-        keep.append((C.c_int64 * max(len(shp), 1))(*shp))
-        shapes[i] = C.cast(keep[-1], C.POINTER(C.c_int64))
-        dtypes[i] = None if ops[i].null else ops[i].dtype.encode()
-    return getattr(_lib_handle(), call.case.sym)(n, params, ndims, shapes, dtypes, None, C.byref(call.case.extra))
-
-
-def _attr(name, value):
-    return lambda c: setattr(c.extra, name, value)
+    refuse_single_defects("abi_cases_convbwd", case)
 
 
 def _block(k, *vals):
@@ -144,56 +98,43 @@ def _block(k, *vals):
     return edit
 
 
-def _shape(i, shp, dtype=F):
-    def edit(c):
-        c.operands[i] = T(shp, dtype, c.operands[i].kind)
-    return edit
-
-
-def _both(*edits):
-    def edit(c):
-        for e in edits:
-            e(c)
-    return edit
-
-
 @pytest.mark.parametrize("tag", ["[pool, k3]", "[workspace, k3]", "[workspace, k1]", "[pool, k3, one block]"])
 def test_wgrad_semantic_refusals_return_the_documented_codes(tag):
     case = _case(tag, "md_conv_bwd_weight")
     k = case.extra.kernel
     edits = [
-        _attr("reserved0", 1), _attr("reserved0", -1), _attr("cin", 0), _attr("cin", -8), _attr("cout", 0), _attr("cout", -1),
-        _attr("x_c_off", -8), _attr("dy_c_off", -1),
-        _attr("x_c_off", 16), _attr("cin", 24), _attr("dy_c_off", 6), _attr("cout", 7),            # a channel range outside x / dy
-        _attr("kernel", 0), _attr("kernel", 2), _attr("kernel", 5), _attr("kernel", -3), _attr("korder", 2), _attr("korder", -1),
-        _attr("n_blocks", -1), _attr("n_blocks", 5),
-        _shape(0, (0, 3, 5, 16), B16), _shape(0, (1, 0, 5, 16), B16), _shape(1, (1, 3, 0, 8)),     # no pixel
-        _shape(1, (1, 3, 4, 8)), _shape(1, (2, 3, 5, 8)), _shape(0, (1, 5, 3, 16), B16),           # x and dy over different pixels
-        _shape(2, (2, 128)), _shape(2, (32, k * k * 8 - 1)), _shape(3, (2,)),                      # dw / db smaller than the layer
+        attr("reserved0", 1), attr("reserved0", -1), attr("cin", 0), attr("cin", -8), attr("cout", 0), attr("cout", -1),
+        attr("x_c_off", -8), attr("dy_c_off", -1),
+        attr("x_c_off", 16), attr("cin", 24), attr("dy_c_off", 6), attr("cout", 7),            # a channel range outside x / dy
+        attr("kernel", 0), attr("kernel", 2), attr("kernel", 5), attr("kernel", -3), attr("korder", 2), attr("korder", -1),
+        attr("n_blocks", -1), attr("n_blocks", 5),
+        shape(0, (0, 3, 5, 16), B16), shape(0, (1, 0, 5, 16), B16), shape(1, (1, 3, 0, 8)),     # no pixel
+        shape(1, (1, 3, 4, 8)), shape(1, (2, 3, 5, 8)), shape(0, (1, 5, 3, 16), B16),           # x and dy over different pixels
+        shape(2, (2, 128)), shape(2, (32, k * k * 8 - 1)), shape(3, (2,)),                      # dw / db smaller than the layer
     ]
     # a block outside [0, cout) x [0, cin), or empty
     for vals in ((0, 4, 0, 8), (2, 2, 0, 8), (-1, 2, 0, 8), (0, 3, 1, 8), (0, 3, -1, 4), (0, 0, 0, 8), (0, 3, 0, 0), (3, 1, 0, 8), (0, 1, 8, 1)):
-        edits.append(_both(_attr("n_blocks", 1), _block(0, *vals)))
-    edits.append(_both(_attr("n_blocks", 2), _block(0, 0, 3, 0, 8), _block(1, 0, 4, 0, 8)))         # the second one
+        edits.append(both(attr("n_blocks", 1), _block(0, *vals)))
+    edits.append(both(attr("n_blocks", 2), _block(0, 0, 3, 0, 8), _block(1, 0, 4, 0, 8)))         # the second one
     for i, e in enumerate(edits):
-        assert _rc(case, e) == ARG, i
+        assert rc(case, e) == ARG, i
     for o, kk in ((2, 0), (2, 1), (3, 0), (3, 1), (3, 2)):                                         # an output at another operand's address
-        assert _raw(case, same=[(o, kk)]) == ARG, (o, kk)
+        assert raw(case, same=[(o, kk)]) == ARG, (o, kk)
     # the stated limits: each edit keeps every extent consistent, so the limit alone refuses it
-    wide_x = _both(_shape(0, (1, 3, 5, 24), B16), _attr("x_c_off", 0), _shape(2, (32, 128)))
-    assert _rc(case, _both(wide_x, _attr("cin", 12))) == SIZE                                      # cin % 8
-    many = _both(_shape(1, (1, 3, 5, 264)), _shape(2, (264, 128)), _shape(3, (264,)), _attr("dy_c_off", 0))
-    assert _rc(case, _both(many, _attr("cout", 257))) == SIZE
+    wide_x = both(shape(0, (1, 3, 5, 24), B16), attr("x_c_off", 0), shape(2, (32, 128)))
+    assert rc(case, both(wide_x, attr("cin", 12))) == SIZE                                      # cin % 8
+    many = both(shape(1, (1, 3, 5, 264)), shape(2, (264, 128)), shape(3, (264,)), attr("dy_c_off", 0))
+    assert rc(case, both(many, attr("cout", 257))) == SIZE
     lim = 1024 if k == 1 else 256
-    wide = _both(_shape(0, (1, 3, 5, lim + 16), B16), _shape(2, (32, k * k * (lim + 8))), _attr("x_c_off", 0))
-    assert _rc(case, _both(wide, _attr("cin", lim + 8))) == SIZE
-    assert _rc(case, _attr("korder", 1)) == SIZE                                                   # korder 1 with cin 8
-    huge = _both(_shape(0, (2 ** 16, 2 ** 15, 1, 16), B16), _shape(1, (2 ** 16, 2 ** 15, 1, 8)))   # P = 2^31
-    assert _raw(case, huge) == SIZE
-    assert _raw(case, _shape(0, (2 ** 16, 2 ** 15, 1, 16), B16)) == ARG                            # (dy no longer matches)
-    assert _raw(case, _shape(2, (2 ** 16, 2 ** 15))) == SIZE                                       # dw of 2^31 elements
+    wide = both(shape(0, (1, 3, 5, lim + 16), B16), shape(2, (32, k * k * (lim + 8))), attr("x_c_off", 0))
+    assert rc(case, both(wide, attr("cin", lim + 8))) == SIZE
+    assert rc(case, attr("korder", 1)) == SIZE                                                   # korder 1 with cin 8
+    huge = both(shape(0, (2 ** 16, 2 ** 15, 1, 16), B16), shape(1, (2 ** 16, 2 ** 15, 1, 8)))   # P = 2^31
+    assert raw(case, huge) == SIZE
+    assert raw(case, shape(0, (2 ** 16, 2 ** 15, 1, 16), B16)) == ARG                            # (dy no longer matches)
+    assert raw(case, shape(2, (2 ** 16, 2 ** 15))) == SIZE                                       # dw of 2^31 elements
     if "workspace" in tag:
-        assert _rc(case, _shape(4, (workspace_bytes(k) - 1,), U8)) == SIZE                         # one byte short
+        assert rc(case, shape(4, (workspace_bytes(k) - 1,), U8)) == SIZE                         # one byte short
 
 
 def test_a_misaligned_workspace_is_refused():
@@ -210,7 +151,7 @@ def test_a_misaligned_workspace_is_refused():
         params[i] = base + 4096 * i + (8 if i == 4 else 0)                                         # the workspace 8 bytes off a 16-byte boundary
         keep.append((C.c_int64 * len(op.shape))(*op.shape))
         ndims[i], shapes[i], dtypes[i] = len(op.shape), C.cast(keep[-1], C.POINTER(C.c_int64)), op.dtype.encode()
-    assert _lib_handle().md_conv_bwd_weight(n, params, ndims, shapes, dtypes, None, C.byref(case.extra)) == ARG
+    assert lib_handle().md_conv_bwd_weight(n, params, ndims, shapes, dtypes, None, C.byref(case.extra)) == ARG
 
 
 @pytest.mark.parametrize("tag", ["[act]", "[no act]"])
@@ -218,26 +159,26 @@ def test_dgrad_semantic_refusals_return_the_documented_codes(tag):
     case = _case(tag, "md_conv1x1_bwd_data")
     act = tag == "[act]"
     edits = [
-        _attr("reserved0", 1), _attr("cin", 0), _attr("cin", -8), _attr("cout", 0), _attr("cout", -1), _attr("dy_c_off", -1), _attr("dx_c_off", -4),
-        _attr("act_c_off", -1),
-        _attr("dy_c_off", 6), _attr("cout", 7), _attr("dx_c_off", 5), _attr("cin", 16),            # a channel range outside dy / dx
-        _shape(0, (0, 3, 5, 8)), _shape(0, (1, 3, 0, 8)), _shape(3, (1, 3, 4, 12)), _shape(3, (2, 3, 5, 12)),
-        _shape(1, (2, 64), B16), _shape(1, (32, 7), B16),                                          # w smaller than the layer
+        attr("reserved0", 1), attr("cin", 0), attr("cin", -8), attr("cout", 0), attr("cout", -1), attr("dy_c_off", -1), attr("dx_c_off", -4),
+        attr("act_c_off", -1),
+        attr("dy_c_off", 6), attr("cout", 7), attr("dx_c_off", 5), attr("cin", 16),            # a channel range outside dy / dx
+        shape(0, (0, 3, 5, 8)), shape(0, (1, 3, 0, 8)), shape(3, (1, 3, 4, 12)), shape(3, (2, 3, 5, 12)),
+        shape(1, (2, 64), B16), shape(1, (32, 7), B16),                                          # w smaller than the layer
     ]
-    edits += [_attr("act_c_off", 5), _shape(2, (1, 3, 4, 12), B16), _shape(2, (1, 3, 5, 11), B16)] if act else [_attr("act_c_off", 4)]
+    edits += [attr("act_c_off", 5), shape(2, (1, 3, 4, 12), B16), shape(2, (1, 3, 5, 11), B16)] if act else [attr("act_c_off", 4)]
     for i, e in enumerate(edits):
-        assert _rc(case, e) == ARG, i
+        assert rc(case, e) == ARG, i
     for k in (0, 1) + ((2,) if act else ()):                                                       # dx at another operand's address
-        assert _raw(case, same=[(3, k)]) == ARG, k
-    grow = lambda cin: _both(_shape(1, (32, cin + 8), B16), _shape(3, (1, 3, 5, cin + 8)), _shape(2, (1, 3, 5, cin + 8), B16) if act else (lambda c: None),
-                             _attr("dx_c_off", 0), _attr("act_c_off", 0))
-    assert _rc(case, _both(grow(16), _attr("cin", 12))) == SIZE
-    assert _rc(case, _both(grow(1040), _attr("cin", 1032))) == SIZE
-    assert _rc(case, _both(_shape(0, (1, 3, 5, 264)), _shape(1, (264, 64), B16), _attr("dy_c_off", 0), _attr("cout", 257))) == SIZE
-    huge = _both(_shape(0, (2 ** 16, 2 ** 15, 1, 8)), _shape(3, (2 ** 16, 2 ** 15, 1, 12)), _shape(2, (2 ** 16, 2 ** 15, 1, 12), B16) if act else (lambda c: None))
-    assert _raw(case, huge) == SIZE
-    big = _both(_shape(0, (2 ** 14, 2 ** 14, 1, 8)), _shape(3, (2 ** 14, 2 ** 14, 1, 12)), _shape(2, (2 ** 14, 2 ** 14, 1, 12), B16) if act else (lambda c: None))
-    assert _raw(case, big) == SIZE                                                                 # P = 2^28, dy of 2^31 elements
+        assert raw(case, same=[(3, k)]) == ARG, k
+    grow = lambda cin: both(shape(1, (32, cin + 8), B16), shape(3, (1, 3, 5, cin + 8)), shape(2, (1, 3, 5, cin + 8), B16) if act else (lambda c: None),
+                             attr("dx_c_off", 0), attr("act_c_off", 0))
+    assert rc(case, both(grow(16), attr("cin", 12))) == SIZE
+    assert rc(case, both(grow(1040), attr("cin", 1032))) == SIZE
+    assert rc(case, both(shape(0, (1, 3, 5, 264)), shape(1, (264, 64), B16), attr("dy_c_off", 0), attr("cout", 257))) == SIZE
+    huge = both(shape(0, (2 ** 16, 2 ** 15, 1, 8)), shape(3, (2 ** 16, 2 ** 15, 1, 12)), shape(2, (2 ** 16, 2 ** 15, 1, 12), B16) if act else (lambda c: None))
+    assert raw(case, huge) == SIZE
+    big = both(shape(0, (2 ** 14, 2 ** 14, 1, 8)), shape(3, (2 ** 14, 2 ** 14, 1, 12)), shape(2, (2 ** 14, 2 ** 14, 1, 12), B16) if act else (lambda c: None))
+    assert raw(case, big) == SIZE                                                                 # P = 2^28, dy of 2^31 elements
 
 
 # ---------------------------------------------------------------------------------------------------- the judges against autograd

@@ -1,5 +1,5 @@
-"""CPU: the CenterPoint training input without a GPU -- the ABI of include/minddet_hip_cpaug.h (the functions exported, the
-single-defect calls and the semantic refusals answered before any device call, the ctypes mirrors laid out as the header says), the
+"""CPU: the CenterPoint training input without a GPU -- the ABI of include/minddet_hip_cpaug.h (the functions exported,
+the semantic refusals answered before any device call, the ctypes mirrors laid out as the header says), the
 contract tests/cpaug_contract.py against the reference's own outputs (tests/golden/cp_augment_vectors.npz, written by
 tests/golden/gen_cp_augment.py from points_count_rbbox, sample_all, the four global steps and filter_gt_box_outside_range),
 det_ops.CenterPointAugment built from the train config and its refusals, and the one definition of the collision predicate."""
@@ -14,31 +14,25 @@ import torch
 
 from minddet_amd import _lib, det_ops
 from tests import cpaug_contract as cc
-from tests.abi_cases import F, I, T
+from tests import abi_header as ah
+from tests.abi_cases import I, T
 from tests.abi_cases_cpaug import CASES, F64, CPBoxes, CPCount
+from tests.abi_derive import both, edited, item, lib_handle, rc, refuse_single_defects, shape
 from tests.cpaug_cases import GOLD, NAMES, contract_case, fixture_case, has_candidates
-from tests.pcaug_cases import edited, mutations64
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = open(os.path.join(ROOT, "include", "minddet_hip_cpaug.h")).read()
+HDR = ah.header("minddet_hip_cpaug.h")
 SYMS = ["md_cp_aug_count_points", "md_cp_aug_select", "md_cp_aug_points", "md_cp_aug_boxes"]
 U8 = "uint8"
 
 
-def _lib_handle():
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    return C.CDLL(_lib.LIB_PATH)
-
-
 def test_header_declares_the_symbols_and_the_library_exports_them():
-    pat = r"^\s*int\s+(\w+)\s*\(MD_AOT_ARGS\)\s*;"     # the expression of _lib.exported_symbols
-    assert re.findall(pat, HDR, flags=re.M) == SYMS and '#include "minddet_hip_points.h"' in HDR
+    assert ah.aot_symbols(HDR) == SYMS and '#include "minddet_hip_points.h"' in HDR
     for cite in ("preprocess.py:46-157, 187-193", "sample_ops.py:127-154, 245-291", "box_np_ops.py:9-14", ":102-116", ":825-827"):
         assert cite in HDR, cite
     assert "minddet_hip_cpaug.h" in open(os.path.join(ROOT, "minddet_amd", "csrc", "Makefile")).read()
     assert {c.sym for c in CASES} == set(SYMS) and len({c.id for c in CASES}) == len(CASES)
-    lib = _lib_handle()
+    lib = lib_handle()
     for s in SYMS:
         assert getattr(lib, s)(0, None, None, None, None, None, None) == 1      # wrong parameter count, before anything else
     assert not set(SYMS) & set(_lib.exported_symbols())                          # declared in the new header only
@@ -46,15 +40,13 @@ def test_header_declares_the_symbols_and_the_library_exports_them():
 
 def test_ctypes_mirrors_and_limits_have_the_headers_layout():
     for name, want in (("md_cp_count_attrs", ["int32_t min_points"]), ("md_cp_boxes_attrs", ["float bv_range[4]"])):
-        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), HDR, flags=re.S).group(1)
-        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-        assert [s.strip() for s in body.split(";") if s.strip()] == want
+        assert ah.statements(name, HDR) == want
     for got in (det_ops._CPBoxesAttrs, CPBoxes):
         assert C.sizeof(got) == 16 and got.bv_range.offset == 0 and got.bv_range.size == 16
     for got in (det_ops._CPCountAttrs, CPCount):
         assert C.sizeof(got) == 4 and got.min_points.offset == 0
     for name, macro in (("CPAUG_MAX_GT", "MD_CPAUG_MAX_GT"), ("CPAUG_MAX_CAND", "MD_CPAUG_MAX_CAND")):
-        assert getattr(det_ops, name) == int(re.search(rf"#define {macro} (\d+)", HDR).group(1))
+        assert getattr(det_ops, name) == ah.defines(HDR)[macro]
     assert (det_ops.CPAUG_MAX_GT, det_ops.CPAUG_MAX_CAND) == (512, 256) and "#define MD_CPAUG_MAX_BATCH 4096" in HDR
     assert det_ops.cp_aug_count_points_workspace_bytes(2, 3) == 576 and det_ops.cp_aug_select_workspace_bytes(2, 3, 4) == 64
     assert det_ops.cp_aug_points_workspace_bytes(300, 40, 2) == 480 <= 484              # (the library's answer, the header's bound)
@@ -73,30 +65,7 @@ def test_collision_predicate_is_defined_once():
 
 @pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])
 def test_single_defect_calls_are_refused_without_a_device(case):
-    lib = _lib_handle()
-    muts = mutations64(case)
-    kinds = {k for k, _, _, _ in muts}
-    assert {"nparam", "params_null", "ndims_null", "shapes_null", "shape_null", "ptr_null", "dtype", "rank-1", "rank+1"} <= kinds
-    assert ("extra_null" in kinds) == case.extra_required
-    bad = [(kind, i, rc, want) for kind, i, call, want in muts for rc in [call.run(lib)] if rc != want]
-    assert not bad, f"{case.id}: (defect, operand, rc, expected) {bad}"
-
-
-def _rc(case, edit):
-    return edited(case, edit).run(_lib_handle())
-
-
-def _shape(i, shp, dtype=F):
-    def edit(c):
-        c.operands[i] = T(shp, dtype, c.operands[i].kind, c.operands[i].rank, why=c.operands[i].why)
-    return edit
-
-
-def _both(*edits):
-    def edit(c):
-        for e in edits:
-            e(c)
-    return edit
+    refuse_single_defects("abi_cases_cpaug", case)
 
 
 def _null(i):
@@ -109,57 +78,55 @@ def _null(i):
 def test_semantic_refusals_return_the_documented_codes():
     ARG, SIZE = 2, 4
     count_ws, count, select_ws, select, points_ws, points, boxes, boxes_plain = CASES
-    for i, e in enumerate([_shape(0, (300, 4)), _shape(0, (300, 6)), _shape(1, (4,), I), _shape(2, (2, 3, 7)), _shape(2, (3, 3, 9)), _shape(3, (3,), I),
-                           _shape(4, (2, 4), I), _shape(5, (2, 4), U8), _shape(5, (3, 3), U8)]):
-        assert _rc(count, e) == ARG, i
-    grow = _both(_shape(2, (2, 513, 9)), _shape(4, (2, 513), I), _shape(5, (2, 513), U8))
-    assert _rc(count, grow) == SIZE
+    for i, e in enumerate([shape(0, (300, 4)), shape(0, (300, 6)), shape(1, (4,), I), shape(2, (2, 3, 7)), shape(2, (3, 3, 9)), shape(3, (3,), I),
+                           shape(4, (2, 4), I), shape(5, (2, 4), U8), shape(5, (3, 3), U8)]):
+        assert rc(count, e) == ARG, i
+    grow = both(shape(2, (2, 513, 9)), shape(4, (2, 513), I), shape(5, (2, 513), U8))
+    assert rc(count, grow) == SIZE
     call = edited(count, lambda c: None)                  # (the shapes alone say 2^30 points: the host blocks stay small, nothing is touched)
     call.shapes[0] = [1 << 30, 5]
-    assert call.run(_lib_handle()) == SIZE
-    assert _rc(count_ws, _shape(6, (575,), U8)) == SIZE
+    assert call.run(lib_handle()) == SIZE
+    assert rc(count_ws, shape(6, (575,), U8)) == SIZE
 
-    for i, e in enumerate([_shape(0, (2, 3, 7)), _shape(1, (3,), I), _shape(2, (2, 4), U8), _shape(3, (2, 4, 7)), _shape(3, (3, 4, 9)), _shape(4, (3,), I),
-                           _shape(5, (2, 5), I), _shape(6, (2, 5), U8)]):
-        assert _rc(select, e) == ARG, i
-    assert _rc(select, _both(_shape(0, (2, 513, 9)), _shape(2, (2, 513), U8))) == SIZE
-    assert _rc(select, _both(_shape(3, (2, 257, 9)), _shape(5, (2, 257), I), _shape(6, (2, 257), U8))) == SIZE
-    assert _rc(select_ws, _shape(7, (63,), U8)) == SIZE
+    for i, e in enumerate([shape(0, (2, 3, 7)), shape(1, (3,), I), shape(2, (2, 4), U8), shape(3, (2, 4, 7)), shape(3, (3, 4, 9)), shape(4, (3,), I),
+                           shape(5, (2, 5), I), shape(6, (2, 5), U8)]):
+        assert rc(select, e) == ARG, i
+    assert rc(select, both(shape(0, (2, 513, 9)), shape(2, (2, 513), U8))) == SIZE
+    assert rc(select, both(shape(3, (2, 257, 9)), shape(5, (2, 257), I), shape(6, (2, 257), U8))) == SIZE
+    assert rc(select_ws, shape(7, (63,), U8)) == SIZE
 
-    for i, e in enumerate([_both(_shape(0, (300, 4)), _shape(7, (340, 4))), _shape(1, (4,), I), _shape(2, (40, 4)), _shape(3, (8,), I), _shape(3, (10,), I),
-                           _shape(4, (2, 4, 7)), _shape(4, (3, 4, 9)), _shape(5, (2, 5), U8), _shape(6, (2, 6), F64), _shape(6, (3, 7), F64),
-                           _shape(7, (300, 5)), _shape(7, (340, 4)), _shape(8, (2,), I)]):
-        assert _rc(points_ws, e) == ARG, i
+    for i, e in enumerate([both(shape(0, (300, 4)), shape(7, (340, 4))), shape(1, (4,), I), shape(2, (40, 4)), shape(3, (8,), I), shape(3, (10,), I),
+                           shape(4, (2, 4, 7)), shape(4, (3, 4, 9)), shape(5, (2, 5), U8), shape(6, (2, 6), F64), shape(6, (3, 7), F64),
+                           shape(7, (300, 5)), shape(7, (340, 4)), shape(8, (2,), I)]):
+        assert rc(points_ws, e) == ARG, i
     for i in (2, 3, 4, 5):                                # candidate operands given in part
-        assert _rc(points_ws, _null(i)) == ARG, i
-    assert _rc(points, _shape(7, (340, 5))) == ARG        # no candidates: N rows
+        assert rc(points_ws, _null(i)) == ARG, i
+    assert rc(points, shape(7, (340, 5))) == ARG        # no candidates: N rows
     call = edited(points, lambda c: None)
     call.shapes[0], call.shapes[7] = [1 << 30, 5], [1 << 30, 5]
-    assert call.run(_lib_handle()) == SIZE
-    assert _rc(points_ws, _both(_shape(3, (2 * 257 + 1,), I), _shape(4, (2, 257, 9)), _shape(5, (2, 257), U8))) == SIZE
-    assert _rc(points_ws, _shape(9, (479,), U8)) == SIZE                                       # 480 bytes are used
+    assert call.run(lib_handle()) == SIZE
+    assert rc(points_ws, both(shape(3, (2 * 257 + 1,), I), shape(4, (2, 257, 9)), shape(5, (2, 257), U8))) == SIZE
+    assert rc(points_ws, shape(9, (479,), U8)) == SIZE                                       # 480 bytes are used
 
     nan, inf = float("nan"), float("inf")
-    for i, e in enumerate([_shape(0, (2, 3, 7)), _shape(1, (2, 4), I), _shape(2, (3,), I), _shape(3, (2, 4), U8), _shape(4, (2, 4, 7)), _shape(5, (2, 5), I),
-                           _shape(6, (2, 5), U8), _shape(7, (2, 6), F64), _shape(8, (2, 6, 9)), _shape(8, (2, 7, 7)), _shape(9, (2, 6), I),
-                           _shape(10, (3,), I)]):
-        assert _rc(boxes, e) == ARG, i
+    for i, e in enumerate([shape(0, (2, 3, 7)), shape(1, (2, 4), I), shape(2, (3,), I), shape(3, (2, 4), U8), shape(4, (2, 4, 7)), shape(5, (2, 5), I),
+                           shape(6, (2, 5), U8), shape(7, (2, 6), F64), shape(8, (2, 6, 9)), shape(8, (2, 7, 7)), shape(9, (2, 6), I),
+                           shape(10, (3,), I)]):
+        assert rc(boxes, e) == ARG, i
     for i in (4, 5, 6):
-        assert _rc(boxes, _null(i)) == ARG, i
-    assert _rc(boxes_plain, _shape(8, (2, 7, 9))) == ARG
+        assert rc(boxes, _null(i)) == ARG, i
+    assert rc(boxes_plain, shape(8, (2, 7, 9))) == ARG
     for k, v in ((0, nan), (1, inf), (2, -inf), (3, nan)):
-        def attr(c, k=k, v=v):
-            c.extra.bv_range[k] = v
-        assert _rc(boxes, attr) == ARG, (k, v)
-    grow = _both(_shape(0, (2, 513, 9)), _shape(1, (2, 513), I), _shape(3, (2, 513), U8), _shape(8, (2, 517, 9)), _shape(9, (2, 517), I))
-    assert _rc(boxes, grow) == SIZE
-    grow = _both(_shape(4, (2, 257, 9)), _shape(5, (2, 257), I), _shape(6, (2, 257), U8), _shape(8, (2, 260, 9)), _shape(9, (2, 260), I))
-    assert _rc(boxes, grow) == SIZE
+        assert rc(boxes, item("bv_range", k, v)) == ARG, (k, v)
+    grow = both(shape(0, (2, 513, 9)), shape(1, (2, 513), I), shape(3, (2, 513), U8), shape(8, (2, 517, 9)), shape(9, (2, 517), I))
+    assert rc(boxes, grow) == SIZE
+    grow = both(shape(4, (2, 257, 9)), shape(5, (2, 257), I), shape(6, (2, 257), U8), shape(8, (2, 260, 9)), shape(9, (2, 260), I))
+    assert rc(boxes, grow) == SIZE
 
 
 def test_aliased_outputs_are_refused():
     """an output at the address of an input or of another output: rc 2 before any device call"""
-    lib = _lib_handle()
+    lib = lib_handle()
     for case, pairs in ((CASES[1], [(4, 3), (5, 4)]), (CASES[3], [(6, 2)]), (CASES[4], [(7, 0), (7, 2), (8, 1)]), (CASES[6], [(8, 0), (9, 1), (10, 2), (10, 9)])):
         for out, other in pairs:
             call = edited(case, lambda c: None)

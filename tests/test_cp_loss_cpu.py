@@ -1,93 +1,53 @@
-"""CPU: the CenterPoint training loss without a GPU -- the ABI of include/minddet_hip_cploss.h (the two functions exported, the
-single-defect calls and the semantic refusals answered before any device call, the ctypes mirrors laid out as the header says), the
+"""CPU: the CenterPoint training loss without a GPU -- the ABI of include/minddet_hip_cploss.h (the two functions exported,
+the semantic refusals answered before any device call, the ctypes mirrors laid out as the header says), the
 contract tests/cp_loss_contract.py against a literal torch-float64 transcription of the reference's FastFocalLoss / RegLoss /
 CenterHead.loss under autograd on the committed reference targets (tests/golden/cp_target_vectors.npz), and the config."""
-import copy
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
-from minddet_amd import _lib, det_ops
+from minddet_amd import det_ops
 from tests import cp_loss_contract as cl
-from tests.abi_cases import B16, F, I, T, U8
+from tests import abi_header as ah
+from tests.abi_cases import B16, I, U8
 from tests.abi_cases_cploss import CASES, CPLoss
-from tests.test_abi_checks_cpu import Call, mutations
+from tests.abi_derive import attr, both, item, lib_handle, rc, refuse_single_defects, shape
 from tests.test_cp_targets_cpu import fixture_case
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = open(os.path.join(ROOT, "include", "minddet_hip_cploss.h")).read()
-HDR_CP = open(os.path.join(ROOT, "include", "minddet_hip_cp.h")).read()
+HDR = ah.header("minddet_hip_cploss.h")
+HDR_CP = ah.header("minddet_hip_cp.h")
 WEIGHT = float(np.float32(0.25))
 CODE_WEIGHTS = [float(np.float32(v)) for v in (1, 1, 1, 1, 1, 1, 0.2, 0.2, 1, 1)]     # the values an fp32 attribute struct carries
 
 
-def _lib_handle():
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    return C.CDLL(_lib.LIB_PATH)
-
-
 def test_header_declares_the_two_symbols_and_the_library_exports_them():
-    pat = r"^\s*int\s+(\w+)\s*\(MD_AOT_ARGS\)\s*;"     # the expression of _lib.exported_symbols
-    assert re.findall(pat, HDR, flags=re.M) == ["md_cp_loss", "md_cp_loss_grad"] and '#include "minddet_hip_cp.h"' in HDR
+    assert ah.aot_symbols(HDR) == ["md_cp_loss", "md_cp_loss_grad"] and '#include "minddet_hip_cp.h"' in HDR
     assert "center_head.py:208-271" in HDR and "centernet_loss.py:22-82" in HDR
     assert "minddet_hip_cploss.h" in open(os.path.join(ROOT, "minddet_amd", "csrc", "Makefile")).read()
     assert {c.sym for c in CASES} == {"md_cp_loss", "md_cp_loss_grad"} and len({c.id for c in CASES}) == len(CASES)
-    lib = _lib_handle()
+    lib = lib_handle()
     for sym in ("md_cp_loss", "md_cp_loss_grad"):
         assert getattr(lib, sym)(0, None, None, None, None, None, None) == 1             # wrong parameter count, before anything else
 
 
-def _struct_of(text, name, known):
-    """the ctypes mirror of `typedef struct name { ... } name;` in a header (array extents may be #define names)"""
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), text, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    defines = {k: int(v) for k, v in re.findall(r"^#define (\w+) (\d+)\b", HDR + HDR_CP, flags=re.M)}
-    fields = []
-    for stmt in filter(None, (s.strip() for s in body.split(";"))):
-        ty, decl = stmt.split(None, 1)
-        base = dict(known, int32_t=C.c_int32, float=C.c_float)[ty]
-        for d in decl.split(","):
-            m = re.fullmatch(r"(\w+)\s*(?:\[(\w+)\])?", d.strip())
-            n = m.group(2)
-            fields.append((m.group(1), base if n is None else base * (int(n) if n.isdigit() else defines[n])))
-    return type(name, (C.Structure,), {"_fields_": fields})
-
-
 def test_ctypes_mirrors_have_the_headers_layout():
-    task = _struct_of(HDR_CP, "md_cp_task_attrs", {})
-    want = _struct_of(HDR, "md_cp_loss_attrs", {"md_cp_task_attrs": task})
+    task = ah.struct_of("md_cp_task_attrs", HDR_CP)
+    want = ah.struct_of("md_cp_loss_attrs", HDR, HDR_CP, known={"md_cp_task_attrs": task})
     assert C.sizeof(task) == 8 * 4 and C.sizeof(want) == 4 + 8 * 32 + 4 + 40
 
-    def layout(s):
-        return [(n, getattr(s, n).offset, getattr(s, n).size) for n, _ in s._fields_]
-
     for got in (det_ops._CPLossAttrs, CPLoss):
-        assert C.sizeof(got) == C.sizeof(want) and layout(got) == layout(want), got
+        assert ah.same_layout(got, want), got
     for got in (det_ops._CPTaskAttrs, dict(CPLoss._fields_)["task"]._type_):
-        assert layout(got) == layout(task), got
+        assert ah.layout(got) == ah.layout(task), got
 
 
 @pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])
 def test_single_defect_calls_are_refused_without_a_device(case):
-    lib = _lib_handle()
-    muts = mutations(case)
-    kinds = {k for k, _, _, _ in muts}
-    assert {"nparam", "params_null", "ndims_null", "shapes_null", "extra_null", "shape_null", "ptr_null", "dtype", "rank-1", "rank+1"} <= kinds
-    bad = [(kind, i, rc, want) for kind, i, call, want in muts for rc in [call.run(lib)] if rc != want]
-    assert not bad, f"{case.id}: (defect, operand, rc, expected) {bad}"
-
-
-def _rc(case, edit):
-    c = copy.copy(case)
-    c.extra = type(case.extra).from_buffer_copy(case.extra)
-    c.operands = list(case.operands)
-    edit(c)
-    return Call(c).run(_lib_handle())
+    refuse_single_defects("abi_cases_cploss", case)
 
 
 @pytest.mark.parametrize("case", [CASES[0], CASES[3]], ids=[CASES[0].id, CASES[3].id])
@@ -95,27 +55,8 @@ def test_semantic_refusals_return_the_documented_codes(case):
     ARG, SIZE = 2, 4
     grad = case.sym == "md_cp_loss_grad"
 
-    def attr(name, value):
-        return lambda c: setattr(c.extra, name, value)
-
     def task(t, name, value):
         return lambda c: setattr(c.extra.task[t], name, value)
-
-    def cw(j, value):
-        def edit(c):
-            c.extra.code_weights[j] = value
-        return edit
-
-    def shape(i, shp, dtype=F):
-        def edit(c):
-            c.operands[i] = T(shp, dtype)
-        return edit
-
-    def both(*edits):
-        def edit(c):
-            for e in edits:
-                e(c)
-        return edit
 
     nan, inf = float("nan"), float("inf")
     edits = [
@@ -124,7 +65,7 @@ def test_semantic_refusals_return_the_documented_codes(case):
         task(0, "off_reg", -1), task(1, "off_hm", 23), task(1, "off_dim", 22), task(0, "off_vel", -2), task(1, "off_rot", 24),
         task(1, "off_height", 24),                                                            # a head outside [0, Cp)
         task(1, "off_reg", 9), task(0, "off_hm", 9),                                          # two heads on one channel
-        attr("weight", nan), attr("weight", inf), cw(0, nan), cw(9, -inf),
+        attr("weight", nan), attr("weight", inf), item("code_weights", 0, nan), item("code_weights", 9, -inf),
         shape(0, (0, 8, 12, 24), B16),                                                        # an empty batch
         shape(0, (2, 8, 12, 24), B16), shape(1, (1, 2, 2, 8, 11)), shape(1, (1, 2, 2, 9, 12)), shape(1, (1, 2, 1, 8, 12)),
         shape(1, (1, 3, 2, 8, 12)), shape(2, (1, 2, 4, 9)), shape(2, (1, 2, 5, 10)), shape(2, (2, 2, 4, 10)), shape(3, (1, 2, 5), I),
@@ -133,14 +74,14 @@ def test_semantic_refusals_return_the_documented_codes(case):
     if grad:
         edits += [shape(9, (1, 8, 12, 16)), shape(9, (1, 12, 8, 24)), shape(9, (2, 8, 12, 24))]
     for i, e in enumerate(edits):
-        assert _rc(case, e) == ARG, i
+        assert rc(case, e) == ARG, i
     big = 1100                                                                                # M above the LDS bound
     grow = both(shape(2, (1, 2, big, 10)), shape(3, (1, 2, big), I), shape(4, (1, 2, big), U8), shape(5, (1, 2, big), I))
-    assert _rc(case, grow) == SIZE
+    assert rc(case, grow) == SIZE
     wide = both(shape(0, (1, 8, 12, 168), B16), *([shape(9, (1, 8, 12, 168))] if grad else []))   # Cp above the LDS bound
-    assert _rc(case, wide) == SIZE
+    assert rc(case, wide) == SIZE
     if "[workspace]" in case.id:
-        assert _rc(case, shape(len(case.operands) - 1, (223,), U8)) == SIZE                   # one byte short of 8 B T (12 + strips)
+        assert rc(case, shape(len(case.operands) - 1, (223,), U8)) == SIZE                   # one byte short of 8 B T (12 + strips)
 
 
 # ---------------------------------------------------------------------------------------------------- the reference, transcribed

@@ -7,7 +7,7 @@ differing at all (the cap and its reason are those of tests/test_cp_targets_gpu.
 ulp of float64 round to different fp32 neighbours on about 2^-27 of the values; an fp32 evaluation would differ on a large share);
 md_cp_loss bit-identical to md_cp_loss_grad in parts / num_pos / total.  Then: the shape without vel, the column order pinned by
 perturbing one head channel at a time, equal results across calls, streams and the scratch-pool form with garbage-filled outputs,
-autograd through det_ops.center_point_loss, the production shape, and the ABI rows accepted."""
+autograd through det_ops.center_point_loss, and the production shape."""
 import functools
 import os
 
@@ -16,7 +16,6 @@ import pytest
 import torch
 
 from tests import cp_loss_contract as cl
-from tests.abi_cases_cploss import CASES
 from tests.conftest import has_gpu
 from tests.test_cp_loss_cpu import CODE_WEIGHTS, WEIGHT, bf16_logits, head_layout
 from tests.test_cp_targets_cpu import fixture_case
@@ -271,15 +270,3 @@ def test_production_shape_equals_the_contract():
     assert head.shape == (B, H, W, 72) and (H, W) == (128, 128) and want["num_pos"].min() > 100
     check("nusc b4", got, want)
     assert np.array_equal(bits(to_np(head_mod.loss(targets, head))["total"]), bits(got["total"]))
-
-
-def test_every_abi_row_is_accepted():
-    from minddet_amd import _lib
-
-    dt = {"float32": torch.float32, "bfloat16": torch.bfloat16, "int32": torch.int32, "int64": torch.int64, "uint8": torch.uint8}
-    keep = []
-    for c in CASES:
-        tensors = [None if t.null else torch.zeros(t.shape, dtype=dt[t.dtype], device=DEV) for t in c.operands]
-        keep.append(tensors)
-        assert _lib.call(c.sym, tensors, extra=c.extra) == 0, c.id
-    torch.cuda.synchronize()

@@ -1,11 +1,10 @@
-"""CPU: the CenterPoint multi-sweep input without a GPU -- the ABI of include/minddet_hip_cpsweeps.h (the function exported, the
-single-defect calls and the semantic refusals answered before any device call, the ctypes mirror laid out as the header says), the
+"""CPU: the CenterPoint multi-sweep input without a GPU -- the ABI of include/minddet_hip_cpsweeps.h (the function exported,
+the semantic refusals answered before any device call, the ctypes mirror laid out as the header says), the
 contract tests/cp_sweeps_contract.py against the reference's own outputs (tests/golden/cp_sweeps_vectors.npz, written by
 tests/golden/gen_cp_sweeps.py from LoadPointCloudFromFile and read_sweep), det_ops.SweepMerger's tables against the recorded draw,
 det_ops.SweepRing's host matrices, the two configs and the refused options."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
@@ -13,49 +12,40 @@ import torch
 
 from minddet_amd import _lib, det_ops
 from tests import cp_sweeps_contract as sc
-from tests.abi_cases import F, I, T
+from tests import abi_header as ah
+from tests.abi_cases import I
 from tests.abi_cases_cpsweeps import CASES, F64, CPSweeps
+from tests.abi_derive import attr, both, edited, lib_handle, rc, refuse_single_defects, shape
 from tests.cp_sweeps_cases import GOLD, NAMES, case_tables, contract_case, fixture_case, pose, radius, reference_cloud
-from tests.pcaug_cases import edited, mutations64
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR_PATH = os.path.join(ROOT, "include", "minddet_hip_cpsweeps.h")
 SYM = "md_cp_sweeps_merge"
 U8 = "uint8"
 
 
 def _hdr():
-    return open(HDR_PATH).read()
-
-
-def _lib_handle():
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    return C.CDLL(_lib.LIB_PATH)
+    return ah.header("minddet_hip_cpsweeps.h")
 
 
 def test_header_declares_the_symbol_and_the_library_exports_it():
     hdr = _hdr()
-    pat = r"^\s*int\s+(\w+)\s*\(MD_AOT_ARGS\)\s*;"     # the expression of _lib.exported_symbols
-    assert re.findall(pat, hdr, flags=re.M) == [SYM] and '#include "minddet_hip_points.h"' in hdr
+    assert ah.aot_symbols(hdr) == [SYM] and '#include "minddet_hip_points.h"' in hdr
     for cite in ("loading.py:56-80, 133-159", "multi_sweep_inference_ros.py:194-270", "nusc_common.py:443-450", "shuffle_points", "Waymo", "virtual",
                  "quaternions"):
         assert cite in hdr, cite
     assert "minddet_hip_cpsweeps.h" in open(os.path.join(ROOT, "minddet_amd", "csrc", "Makefile")).read()
     assert {c.sym for c in CASES} == {SYM} and len({c.id for c in CASES}) == len(CASES)
-    assert getattr(_lib_handle(), SYM)(0, None, None, None, None, None, None) == 1      # wrong parameter count, before anything else
+    assert getattr(lib_handle(), SYM)(0, None, None, None, None, None, None) == 1      # wrong parameter count, before anything else
     assert SYM not in _lib.exported_symbols()                                            # declared in the new header only
 
 
 def test_ctypes_mirror_limits_and_workspace_have_the_headers_layout():
     hdr = _hdr()
-    body = re.search(r"typedef struct md_cp_sweeps_attrs \{(.*?)\} md_cp_sweeps_attrs;", hdr, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    assert [s.strip() for s in body.split(";") if s.strip()] == ["float radius", "int32_t reserved0"]
+    assert ah.statements("md_cp_sweeps_attrs", hdr) == ["float radius", "int32_t reserved0"]
     for got in (det_ops._CPSweepsAttrs, CPSweeps):
         assert C.sizeof(got) == 8 and got.radius.offset == 0 and got.radius.size == 4 and got.reserved0.offset == 4 and got.reserved0.size == 4
     for name, macro in (("CPSWEEPS_MAX_SWEEPS", "MD_CPSWEEPS_MAX_SWEEPS"), ("CPSWEEPS_MAX_BATCH", "MD_CPSWEEPS_MAX_BATCH")):
-        assert getattr(det_ops, name) == int(re.search(rf"#define {macro} (\d+)", hdr).group(1))
+        assert getattr(det_ops, name) == ah.defines(hdr)[macro]
     assert det_ops.CPSWEEPS_MAX_SWEEPS >= 16 and det_ops.CPSWEEPS_MAX_BATCH >= 256
     assert (det_ops.SWEEP_REMOVE_CLOSE, det_ops.SWEEP_TRANSFORM) == (sc.REMOVE_CLOSE, sc.TRANSFORM) == (1, 2)
     assert "4 (N / 256 + B S + 3) bytes" in hdr
@@ -64,63 +54,36 @@ def test_ctypes_mirror_limits_and_workspace_have_the_headers_layout():
 
 @pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])
 def test_single_defect_calls_are_refused_without_a_device(case):
-    lib = _lib_handle()
-    muts = mutations64(case)
-    kinds = {k for k, _, _, _ in muts}
-    assert {"nparam", "params_null", "ndims_null", "shapes_null", "shape_null", "ptr_null", "dtype", "rank-1", "rank+1", "extra_null"} <= kinds
-    bad = [(kind, i, rc, want) for kind, i, call, want in muts for rc in [call.run(lib)] if rc != want]
-    assert not bad, f"{case.id}: (defect, operand, rc, expected) {bad}"
-
-
-def _rc(case, edit):
-    return edited(case, edit).run(_lib_handle())
-
-
-def _shape(i, shp, dtype=F):
-    def edit(c):
-        c.operands[i] = T(shp, dtype, c.operands[i].kind, c.operands[i].rank, why=c.operands[i].why)
-    return edit
-
-
-def _both(*edits):
-    def edit(c):
-        for e in edits:
-            e(c)
-    return edit
+    refuse_single_defects("abi_cases_cpsweeps", case)
 
 
 def test_semantic_refusals_return_the_documented_codes():
     ARG, SIZE = 2, 4
     ws, pool = CASES
-    for i, e in enumerate([_shape(0, (300, 3)), _shape(0, (300, 6)), _shape(1, (2, 3, 3), I), _shape(1, (3, 3, 2), I), _shape(1, (2, 4, 2), I),
-                           _shape(2, (2, 3, 9), F64), _shape(2, (2, 4, 12), F64), _shape(3, (2, 4), F64), _shape(3, (3, 3), F64), _shape(4, (2, 4), I),
-                           _shape(5, (299, 5)), _shape(5, (300, 4)), _shape(5, (300, 6)), _shape(6, (2,), I), _shape(6, (4,), I), _shape(7, (3,), I)]):
-        assert _rc(ws, e) == ARG, i
-    assert _rc(pool, _shape(5, (299, 5))) == ARG              # M < N
+    for i, e in enumerate([shape(0, (300, 3)), shape(0, (300, 6)), shape(1, (2, 3, 3), I), shape(1, (3, 3, 2), I), shape(1, (2, 4, 2), I),
+                           shape(2, (2, 3, 9), F64), shape(2, (2, 4, 12), F64), shape(3, (2, 4), F64), shape(3, (3, 3), F64), shape(4, (2, 4), I),
+                           shape(5, (299, 5)), shape(5, (300, 4)), shape(5, (300, 6)), shape(6, (2,), I), shape(6, (4,), I), shape(7, (3,), I)]):
+        assert rc(ws, e) == ARG, i
+    assert rc(pool, shape(5, (299, 5))) == ARG              # M < N
     nan, inf = float("nan"), float("inf")
     for v in (nan, inf, -inf, -1.0, -1e-30):
-        def attr(c, v=v):
-            c.extra.radius = v
-        assert _rc(ws, attr) == ARG, v
-
-    def reserved(c):
-        c.extra.reserved0 = 1
-    assert _rc(ws, reserved) == ARG
+        assert rc(ws, attr("radius", v)) == ARG, v
+    assert rc(ws, attr("reserved0", 1)) == ARG
     S1, B1 = det_ops.CPSWEEPS_MAX_SWEEPS + 1, det_ops.CPSWEEPS_MAX_BATCH + 1
-    grow_s = _both(_shape(1, (2, S1, 2), I), _shape(2, (2, S1, 12), F64), _shape(3, (2, S1), F64), _shape(4, (2, S1), I))
-    assert _rc(pool, grow_s) == SIZE
-    grow_b = _both(_shape(1, (B1, 3, 2), I), _shape(2, (B1, 3, 12), F64), _shape(3, (B1, 3), F64), _shape(4, (B1, 3), I), _shape(6, (B1 + 1,), I),
-                   _shape(7, (B1,), I))
-    assert _rc(pool, grow_b) == SIZE
+    grow_s = both(shape(1, (2, S1, 2), I), shape(2, (2, S1, 12), F64), shape(3, (2, S1), F64), shape(4, (2, S1), I))
+    assert rc(pool, grow_s) == SIZE
+    grow_b = both(shape(1, (B1, 3, 2), I), shape(2, (B1, 3, 12), F64), shape(3, (B1, 3), F64), shape(4, (B1, 3), I), shape(6, (B1 + 1,), I),
+                   shape(7, (B1,), I))
+    assert rc(pool, grow_b) == SIZE
     call = edited(pool, lambda c: None)                       # (the shapes alone say 2^30 points: the host blocks stay small, nothing is touched)
     call.shapes[0], call.shapes[5] = [1 << 30, 4], [1 << 30, 5]
-    assert call.run(_lib_handle()) == SIZE
-    assert _rc(ws, _shape(8, (35,), U8)) == SIZE              # 36 bytes are used
+    assert call.run(lib_handle()) == SIZE
+    assert rc(ws, shape(8, (35,), U8)) == SIZE              # 36 bytes are used
 
 
 def test_aliased_outputs_are_refused():
     """an output at the address of an input or of another output: rc 2 before any device call"""
-    lib = _lib_handle()
+    lib = lib_handle()
     case = CASES[0]
     for out, other in ((5, 0), (6, 1), (7, 4), (7, 6), (6, 5)):
         call = edited(case, lambda c: None)

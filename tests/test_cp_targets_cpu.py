@@ -1,31 +1,24 @@
-"""CPU: the CenterPoint training targets without a GPU -- the ABI of include/minddet_hip_cptargets.h (the function exported, the
-single-defect calls and the semantic refusals answered before any device call, the ctypes mirrors laid out as the header says), the
+"""CPU: the CenterPoint training targets without a GPU -- the ABI of include/minddet_hip_cptargets.h (the function exported,
+the semantic refusals answered before any device call, the ctypes mirrors laid out as the header says), the
 contract tests/cp_targets_contract.py against the reference's own outputs (tests/golden/cp_target_vectors.npz, written by
 tests/golden/gen_cp_targets.py from AssignLabel), the accuracy condition of the GPU test met by the reference itself, and the config."""
-import copy
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
 
-from minddet_amd import _lib, det_ops
+from minddet_amd import det_ops
 from tests import cp_targets_contract as ct
-from tests.abi_cases import F, I, T
+from tests import abi_header as ah
+from tests.abi_cases import I
 from tests.abi_cases_cptargets import CASES, CPTargets
-from tests.test_abi_checks_cpu import Call, mutations
+from tests.abi_derive import attr, both, item, lib_handle, rc, refuse_single_defects, shape
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = open(os.path.join(ROOT, "include", "minddet_hip_cptargets.h")).read()
+HDR = ah.header("minddet_hip_cptargets.h")
 GOLD = os.path.join(ROOT, "tests", "golden", "cp_target_vectors.npz")
 NAMES = ("small", "tiles", "plants")
-
-
-def _lib_handle():
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    return C.CDLL(_lib.LIB_PATH)
 
 
 def fixture_case(name):
@@ -39,82 +32,37 @@ def fixture_case(name):
 
 
 def test_header_declares_the_symbol_and_the_library_exports_it():
-    pat = r"^\s*int\s+(\w+)\s*\(MD_AOT_ARGS\)\s*;"     # the expression of _lib.exported_symbols
-    assert re.findall(pat, HDR, flags=re.M) == ["md_cp_assign_targets"] and '#include "minddet_hip.h"' in HDR
+    assert ah.aot_symbols(HDR) == ["md_cp_assign_targets"] and '#include "minddet_hip.h"' in HDR
     assert "preprocess.py:285-521" in HDR and "center_utils.py:16-" in HDR
     assert "minddet_hip_cptargets.h" in open(os.path.join(ROOT, "minddet_amd", "csrc", "Makefile")).read()
     assert {c.sym for c in CASES} == {"md_cp_assign_targets"} and len({c.id for c in CASES}) == len(CASES)
-    lib = _lib_handle()
+    lib = lib_handle()
     assert lib.md_cp_assign_targets(0, None, None, None, None, None, None) == 1      # wrong parameter count, before anything else
 
 
 def test_ctypes_mirrors_have_the_headers_layout():
-    body = re.search(r"typedef struct md_cp_targets_attrs \{(.*?)\} md_cp_targets_attrs;", HDR, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = []
-    for stmt in filter(None, (s.strip() for s in body.split(";"))):
-        ty, decl = stmt.split(None, 1)
-        m = re.fullmatch(r"(\w+)\s*(?:\[(\d+)\])?", decl.strip())
-        base = {"int32_t": C.c_int32, "float": C.c_float}[ty]
-        fields.append((m.group(1), base if m.group(2) is None else base * int(m.group(2))))
-    want = type("Want", (C.Structure,), {"_fields_": fields})
+    want = ah.struct_of("md_cp_targets_attrs", HDR)
     assert C.sizeof(want) == 16 * 4
-
-    def layout(s):
-        return [(n, getattr(s, n).offset, getattr(s, n).size) for n, _ in s._fields_]
-
     for got in (det_ops._CPTargetsAttrs, CPTargets):
-        assert C.sizeof(got) == C.sizeof(want) and layout(got) == layout(want), got
+        assert ah.same_layout(got, want), got
 
 
 @pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])
 def test_single_defect_calls_are_refused_without_a_device(case):
-    lib = _lib_handle()
-    muts = mutations(case)
-    kinds = {k for k, _, _, _ in muts}
-    assert {"nparam", "params_null", "ndims_null", "shapes_null", "extra_null", "shape_null", "ptr_null", "dtype", "rank-1", "rank+1"} <= kinds
-    bad = [(kind, i, rc, want) for kind, i, call, want in muts for rc in [call.run(lib)] if rc != want]
-    assert not bad, f"{case.id}: (defect, operand, rc, expected) {bad}"
-
-
-def _rc(case, edit):
-    c = copy.copy(case)
-    c.extra = type(case.extra).from_buffer_copy(case.extra)
-    c.operands = list(case.operands)
-    edit(c)
-    return Call(c).run(_lib_handle())
+    refuse_single_defects("abi_cases_cptargets", case)
 
 
 def test_semantic_refusals_return_the_documented_codes():
     ARG, SIZE = 2, 4
     case = CASES[0]
 
-    def attr(name, value):
-        return lambda c: setattr(c.extra, name, value)
-
-    def elem(name, i, value):
-        def edit(c):
-            getattr(c.extra, name)[i] = value
-        return edit
-
-    def shape(i, shp, dtype=F):
-        def edit(c):
-            c.operands[i] = T(shp, dtype)
-        return edit
-
-    def both(*edits):
-        def edit(c):
-            for e in edits:
-                e(c)
-        return edit
-
     nan, inf = float("nan"), float("inf")
     edits = [
         both(shape(0, (1, 5, 9)), shape(1, (1, 5), I)),                                   # G > M: the reference's assertion
-        elem("num_classes", 1, 3), elem("num_classes", 1, 1), elem("num_classes", 0, 0),  # C != max(num_classes), a task without classes
+        item("num_classes", 1, 3), item("num_classes", 1, 1), item("num_classes", 0, 0),  # C != max(num_classes), a task without classes
         attr("num_tasks", 0), attr("num_tasks", 9), attr("num_tasks", 1), attr("num_tasks", 3),
-        elem("voxel_size", 0, nan), elem("voxel_size", 1, 0.0), elem("voxel_size", 0, -0.2), elem("voxel_size", 1, inf),
-        elem("pc_range", 0, nan), elem("pc_range", 1, inf), attr("out_size_factor", 0), attr("out_size_factor", -4),
+        item("voxel_size", 0, nan), item("voxel_size", 1, 0.0), item("voxel_size", 0, -0.2), item("voxel_size", 1, inf),
+        item("pc_range", 0, nan), item("pc_range", 1, inf), attr("out_size_factor", 0), attr("out_size_factor", -4),
         attr("gaussian_overlap", nan), attr("gaussian_overlap", 0.0), attr("gaussian_overlap", 1.0), attr("gaussian_overlap", -0.1),
         attr("min_radius", -1),
         shape(0, (1, 3, 8)), shape(0, (2, 3, 9)), shape(1, (1, 4), I), shape(2, (1, 3, 2, 8, 12)), shape(2, (1, 2, 1, 8, 12)),
@@ -122,11 +70,11 @@ def test_semantic_refusals_return_the_documented_codes():
         shape(6, (2, 2, 4), I), shape(7, (1, 5, 10)), shape(7, (1, 4, 9)),
     ]
     for i, e in enumerate(edits):
-        assert _rc(case, e) == ARG, i
+        assert rc(case, e) == ARG, i
     big = 1100                                                                            # G above the LDS bound (M as large: not rc 2)
     grow = both(shape(0, (1, big, 9)), shape(1, (1, big), I), shape(3, (1, 2, big, 10)), shape(4, (1, 2, big), I), shape(5, (1, 2, big), "uint8"),
                 shape(6, (1, 2, big), I), shape(7, (1, big, 10)))
-    assert _rc(case, grow) == SIZE
+    assert rc(case, grow) == SIZE
 
 
 @pytest.mark.parametrize("name", NAMES)

@@ -1,5 +1,5 @@
 """CPU: the grouped conv-backward operators without a GPU -- the ABI of include/minddet_hip_groupedbwd.h (the two operators and the
-workspace function exported, the single-defect calls and the semantic refusals answered before any device call), the judges of
+workspace function exported, the semantic refusals answered before any device call), the judges of
 tests/groupedbwd_contract.py against torch-CPU float64 autograd of F.conv2d(..., groups=G) with the per-group weights embedded in a
 grouped conv of equal widths (k = 1 and 3, three images, couts 1 / 2 / 3), the mask rule, the channels no group covers, the frozen
 BatchNorm that optim.CenterPointHeadTrainer.sync_modules writes back (nn_ops._fold_bn returns the master bit for bit) and the optimizer
@@ -14,20 +14,15 @@ import torch
 
 from minddet_amd import _lib, det_ops, nn_ops, optim
 from tests import groupedbwd_contract as gc, train_contract as tc
-from tests.abi_cases import B16, F, U8, Grouped, T
+from tests import abi_header as ah
+from tests.abi_cases import B16, U8, Grouped
 from tests.abi_cases_groupedbwd import CASES, workspace_bytes
-from tests.pcaug_cases import edited, mutations64
+from tests.abi_derive import attr, both, item, lib_handle, raw, rc, refuse_single_defects, shape
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = open(os.path.join(ROOT, "include", "minddet_hip_groupedbwd.h")).read()
+HDR = ah.header("minddet_hip_groupedbwd.h")
 OPS = ["md_conv2d_grouped_bwd_data", "md_conv2d_grouped_bwd_weight"]
 ARG, SIZE = 2, 4
-
-
-def _lib_handle():
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    return C.CDLL(_lib.LIB_PATH)
 
 
 def _case(tag, sym):
@@ -35,8 +30,7 @@ def _case(tag, sym):
 
 
 def test_header_declares_the_operators_and_the_library_exports_them():
-    pat = r"^\s*int\s+(\w+)\s*\(MD_AOT_ARGS\)\s*;"
-    assert re.findall(pat, HDR, flags=re.M) == OPS and '#include "minddet_hip_convbwd.h"' in HDR
+    assert ah.aot_symbols(HDR) == OPS and '#include "minddet_hip_convbwd.h"' in HDR
     ws = re.findall(r"^extern int64_t (\w+_workspace_bytes)\((?:int64_t \w+(?:, )?)+\);", HDR, flags=re.M)
     assert ws == ["md_conv2d_grouped_bwd_weight_workspace_bytes"] and not re.search(r"^int64_t ", HDR, flags=re.M)
     assert re.search(r"^int md_conv2d_grouped_bwd_weight\(MD_AOT_ARGS\);\nextern int64_t md_conv2d_grouped_bwd_weight_workspace_bytes\(", HDR, flags=re.M)
@@ -44,7 +38,7 @@ def test_header_declares_the_operators_and_the_library_exports_them():
     assert '#include "../../include/minddet_hip_groupedbwd.h"' in src
     assert "acquire_aligned(" in src and ".acquire(" not in src and not re.search(r"atomic\w*\(", src)
     assert {c.sym for c in CASES} == set(OPS) and len({c.id for c in CASES}) == len(CASES)
-    lib = _lib_handle()
+    lib = lib_handle()
     for sym in OPS:
         assert getattr(lib, sym)(0, None, None, None, None, None, None) == 1             # wrong parameter count, before anything else
     assert hasattr(lib, ws[0])
@@ -53,17 +47,14 @@ def test_header_declares_the_operators_and_the_library_exports_them():
     assert {c.tag for c in CASES if c.sym == OPS[1]} == {f"[{w}, k{k}{d}]" for w in ("pool", "workspace") for k in (1, 3) for d in ("", ", no db")}
     for text in ("Ld(k, cout) = k k cout", "|dx - exact| <= Ld 2^-24 sum_{t, o} |dy w|", "bit for bit", "relu must be 0"):
         assert text in HDR, text
-    defines = {k: int(v) for k, v in re.findall(r"^#define (\w+) (\d+)\b", HDR, flags=re.M)}
+    defines = ah.defines(HDR)
     assert defines == dict(MD_GROUPED_BWD_TILE=64, MD_GROUPED_BWD_WALK=4)
 
 
 def test_the_attribute_table_is_the_forward_calls():
-    def layout(s):
-        return [(n, getattr(s, n).offset, getattr(s, n).size) for n, _ in s._fields_]
-
-    assert C.sizeof(nn_ops._GroupedAttrs) == C.sizeof(Grouped) == (6 + 3 * 64) * 4 and layout(nn_ops._GroupedAttrs) == layout(Grouped)
-    main = open(os.path.join(ROOT, "include", "minddet_hip.h")).read()
-    body = re.search(r"typedef struct md_conv2d_grouped_attrs \{(.*?)\} md_conv2d_grouped_attrs;", main, flags=re.S).group(1)
+    assert C.sizeof(nn_ops._GroupedAttrs) == C.sizeof(Grouped) == (6 + 3 * 64) * 4 and ah.layout(nn_ops._GroupedAttrs) == ah.layout(Grouped)
+    main = ah.header("minddet_hip.h")
+    body = "; ".join(ah.statements("md_conv2d_grouped_attrs", main))
     assert re.findall(r"int32_t (\w+)", body) == [n for n, _ in Grouped._fields_] and "#define MD_GROUPED_MAX_GROUPS 64" in main
 
 
@@ -79,7 +70,7 @@ def test_workspace_function_follows_the_headers_rule():
             for G in (1, 3, 36, 64):
                 assert det_ops.conv2d_grouped_bwd_weight_workspace_bytes(P, G, k) == G * one, (P, G, k)
     assert workspace_bytes(3) == det_ops.conv2d_grouped_bwd_weight_workspace_bytes(15, 2, 3)
-    f = _lib_handle().md_conv2d_grouped_bwd_weight_workspace_bytes
+    f = lib_handle().md_conv2d_grouped_bwd_weight_workspace_bytes
     f.restype, f.argtypes = C.c_int64, [C.c_int64] * 3
     assert f(8, 8, 3) > 0 and f(-1, 8, 3) == -1 and f(8, -1, 3) == -1
     assert all(f(8, 8, k) == -1 for k in (-1, 0, 2, 5))
@@ -90,77 +81,19 @@ def test_workspace_function_follows_the_headers_rule():
     assert body.splitlines() == ['    return _lib.workspace_bytes("md_conv2d_grouped_bwd_weight", P, groups, k)']
 
 
-@pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])
-def test_single_defect_calls_are_refused_without_a_device(case):
-    lib = _lib_handle()
-    muts = mutations64(case)
-    kinds = {k for k, _, _, _ in muts}
-    want = {"nparam", "params_null", "ndims_null", "shapes_null", "shape_null", "ptr_null", "dtype", "rank-1", "rank+1", "rank_without_dtypes", "extra_null"}
-    assert want <= kinds
-    bad = [(kind, i, rc, want) for kind, i, call, want in muts for rc in [call.run(lib)] if rc != want]
-    assert not bad, f"{case.id}: (defect, operand, rc, expected) {bad}"
-
-
-def _rc(case, edit):
-    return edited(case, edit).run(_lib_handle())
-
-
-def _raw(case, edit=None, same=(), shift=None):
-    """the case's call after edit(copy) on dummy addresses 4 KiB apart (a refused call never dereferences a tensor pointer, so the
-    extents may describe more memory than exists); same = [(o, k)]: operand o gets the address of operand k; shift = (o, bytes) -> rc"""
-    call = edited(case, edit or (lambda c: None))
-    ops, n = call.case.operands, call.n
-    arena = (C.c_char * (4096 * (n + 2)))()
-    base = (C.addressof(arena) + 4095) // 4096 * 4096
-    addr = {i: base + 4096 * i for i in range(n)}
-    for o, k in same:
-        addr[o] = addr[k]
-    if shift:
-        addr[shift[0]] += shift[1]
-    params, ndims = (C.c_void_p * n)(), (C.c_int * n)()
-    shapes, dtypes = (C.POINTER(C.c_int64) * n)(), (C.c_char_p * n)()
-    keep = []
-    for i in range(n):
-        params[i] = None if ops[i].null else addr[i]
-        shp = [] if ops[i].null else list(ops[i].shape)
-        ndims[i] = len(shp)
-        keep.append((C.c_int64 * max(len(shp), 1))(*shp))
-        shapes[i] = C.cast(keep[-1], C.POINTER(C.c_int64))
-        dtypes[i] = None if ops[i].null else ops[i].dtype.encode()
-    return getattr(_lib_handle(), call.case.sym)(n, params, ndims, shapes, dtypes, None, C.byref(call.case.extra))
-
-
-def _attr(name, value):
-    return lambda c: setattr(c.extra, name, value)
-
-
-def _item(name, g, value):
-    def edit(c):
-        getattr(c.extra, name)[g] = value
-    return edit
-
-
-def _shape(i, shp, dtype=F):
-    def edit(c):
-        c.operands[i] = T(shp, dtype, c.operands[i].kind)
-    return edit
-
-
-def _both(*edits):
-    def edit(c):
-        for e in edits:
-            e(c)
-    return edit
-
-
 # the refusals of the table, the same for both operators (rows: 6, dy channels: 8, the sliced tensor: 144 channels, x_c_off 8, 2 groups)
 TABLE_EDITS = [
-    _attr("reserved0", 1), _attr("reserved0", -1), _attr("k", 0), _attr("k", 2), _attr("k", 5), _attr("k", -3), _attr("relu", 1), _attr("relu", -1),
-    _attr("cin_g", 32), _attr("cin_g", 0), _attr("groups", 0), _attr("groups", -1), _attr("groups", 65), _attr("groups", 3),
-    _attr("x_c_off", -8), _attr("x_c_off", 17), _attr("x_c_off", 24),
-    _item("cout", 0, 0), _item("cout", 1, 17), _item("cout", 1, -1), _item("y_off", 0, -1), _item("y_off", 0, 8), _item("y_off", 1, 6),
-    _item("w_row", 0, -1), _item("w_row", 1, 4), _item("w_row", 0, 6),
+    attr("reserved0", 1), attr("reserved0", -1), attr("k", 0), attr("k", 2), attr("k", 5), attr("k", -3), attr("relu", 1), attr("relu", -1),
+    attr("cin_g", 32), attr("cin_g", 0), attr("groups", 0), attr("groups", -1), attr("groups", 65), attr("groups", 3),
+    attr("x_c_off", -8), attr("x_c_off", 17), attr("x_c_off", 24),
+    item("cout", 0, 0), item("cout", 1, 17), item("cout", 1, -1), item("y_off", 0, -1), item("y_off", 0, 8), item("y_off", 1, 6),
+    item("w_row", 0, -1), item("w_row", 1, 4), item("w_row", 0, 6),
 ]
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])
+def test_single_defect_calls_are_refused_without_a_device(case):
+    refuse_single_defects("abi_cases_groupedbwd", case)
 
 
 @pytest.mark.parametrize("tag", ["[k3, act]", "[k3, no act]", "[k1, act]"])
@@ -168,20 +101,20 @@ def test_dgrad_semantic_refusals_return_the_documented_codes(tag):
     case = _case(tag, OPS[0])
     k, act = case.extra.k, "no act" not in tag
     edits = TABLE_EDITS + [
-        _shape(0, (0, 3, 5, 8)), _shape(0, (1, 3, 0, 8)), _shape(3, (1, 3, 4, 144)), _shape(3, (2, 3, 5, 144)), _shape(3, (1, 3, 5, 135)),
-        _shape(1, (6, k * k * 64 + 64), B16), _shape(1, (6, 64 if k == 3 else 576), B16), _shape(1, (4, k * k * 64), B16),
+        shape(0, (0, 3, 5, 8)), shape(0, (1, 3, 0, 8)), shape(3, (1, 3, 4, 144)), shape(3, (2, 3, 5, 144)), shape(3, (1, 3, 5, 135)),
+        shape(1, (6, k * k * 64 + 64), B16), shape(1, (6, 64 if k == 3 else 576), B16), shape(1, (4, k * k * 64), B16),
     ]
-    edits += [_shape(2, (1, 3, 4, 144), B16), _shape(2, (1, 3, 5, 135), B16)] if act else []
+    edits += [shape(2, (1, 3, 4, 144), B16), shape(2, (1, 3, 5, 135), B16)] if act else []
     for i, e in enumerate(edits):
-        assert _rc(case, e) == ARG, i
+        assert rc(case, e) == ARG, i
     for o in (0, 1) + ((2,) if act else ()):                                                       # dx at another operand's address
-        assert _raw(case, same=[(3, o)]) == ARG, o
-    also = (lambda shp: _shape(2, shp[:3] + (144,), B16)) if act else (lambda shp: (lambda c: None))
+        assert raw(case, same=[(3, o)]) == ARG, o
+    also = (lambda shp: shape(2, shp[:3] + (144,), B16)) if act else (lambda shp: (lambda c: None))
     huge = (2 ** 16, 2 ** 15, 1)                                                                   # P = 2^31
-    assert _raw(case, _both(_shape(0, huge + (8,)), _shape(3, huge + (144,)), also(huge))) == SIZE
+    assert raw(case, both(shape(0, huge + (8,)), shape(3, huge + (144,)), also(huge))) == SIZE
     big = (2 ** 14, 2 ** 10, 1)                                                                    # P = 2^24: dx of 2^31 elements and more
-    assert _raw(case, _both(_shape(0, big + (8,)), _shape(3, big + (144,)), also(big))) == SIZE
-    assert _raw(case, _shape(0, huge + (8,))) == ARG                                               # (dx no longer matches)
+    assert raw(case, both(shape(0, big + (8,)), shape(3, big + (144,)), also(big))) == SIZE
+    assert raw(case, shape(0, huge + (8,))) == ARG                                               # (dx no longer matches)
 
 
 @pytest.mark.parametrize("tag", ["[pool, k3]", "[workspace, k3]", "[workspace, k1]", "[pool, k3, no db]"])
@@ -189,23 +122,23 @@ def test_wgrad_semantic_refusals_return_the_documented_codes(tag):
     case = _case(tag, OPS[1])
     k = case.extra.k
     edits = TABLE_EDITS + [
-        _item("w_row", 1, 0), _both(_item("w_row", 0, 3), _item("cout", 0, 2)),                    # two groups that share a row of w
-        _shape(0, (0, 3, 5, 144), B16), _shape(1, (1, 3, 0, 8)), _shape(1, (1, 3, 4, 8)), _shape(1, (2, 3, 5, 8)), _shape(0, (1, 3, 5, 135), B16),
-        _shape(2, (6, k * k * 64 + 64)), _shape(2, (6, 64 if k == 3 else 576)), _shape(2, (4, k * k * 64)),
+        item("w_row", 1, 0), both(item("w_row", 0, 3), item("cout", 0, 2)),                    # two groups that share a row of w
+        shape(0, (0, 3, 5, 144), B16), shape(1, (1, 3, 0, 8)), shape(1, (1, 3, 4, 8)), shape(1, (2, 3, 5, 8)), shape(0, (1, 3, 5, 135), B16),
+        shape(2, (6, k * k * 64 + 64)), shape(2, (6, 64 if k == 3 else 576)), shape(2, (4, k * k * 64)),
     ]
-    edits += [_shape(3, (5,)), _shape(3, (8,))] if "no db" not in tag else []
+    edits += [shape(3, (5,)), shape(3, (8,))] if "no db" not in tag else []
     for i, e in enumerate(edits):
-        assert _rc(case, e) == ARG, i
+        assert rc(case, e) == ARG, i
     for o, kk in ((2, 0), (2, 1)) + (((3, 0), (3, 1), (3, 2)) if "no db" not in tag else ()):      # an output at another operand's address
-        assert _raw(case, same=[(o, kk)]) == ARG, (o, kk)
+        assert raw(case, same=[(o, kk)]) == ARG, (o, kk)
     huge = (2 ** 16, 2 ** 15, 1)
-    assert _raw(case, _both(_shape(0, huge + (144,), B16), _shape(1, huge + (8,)))) == SIZE        # P = 2^31
+    assert raw(case, both(shape(0, huge + (144,), B16), shape(1, huge + (8,)))) == SIZE        # P = 2^31
     big = (2 ** 14, 2 ** 10, 1)
-    assert _raw(case, _both(_shape(0, big + (144,), B16), _shape(1, big + (8,)))) == SIZE          # P = 2^24: x of 2^31 elements and more
-    assert _raw(case, _shape(0, huge + (144,), B16)) == ARG                                        # (dy no longer matches)
+    assert raw(case, both(shape(0, big + (144,), B16), shape(1, big + (8,)))) == SIZE          # P = 2^24: x of 2^31 elements and more
+    assert raw(case, shape(0, huge + (144,), B16)) == ARG                                        # (dy no longer matches)
     if "workspace" in tag:
-        assert _rc(case, _shape(4, (workspace_bytes(k) - 1,), U8)) == SIZE                         # one byte short
-        assert _raw(case, shift=(4, 8)) == ARG                                                     # 8 bytes off a 16-byte boundary
+        assert rc(case, shape(4, (workspace_bytes(k) - 1,), U8)) == SIZE                         # one byte short
+        assert raw(case, shift=(4, 8)) == ARG                                                     # 8 bytes off a 16-byte boundary
 
 
 # ---------------------------------------------------------------------------------------------------- the judges against autograd

@@ -4,9 +4,9 @@ any device or runtime call; size limits return 4).
 
 tests/host/Makefile compiles minddet_amd/csrc/*.hip with ASan + UBSan on the host side and links them with a replay program and a
 stand-in for the HIP runtime that keeps a ledger of every runtime call (no real runtime is linked: the program cannot open a device).
-This module writes the calls -- every valid row of every tests/abi_cases*.py table, every single-defect call of
-tests/test_abi_checks_cpu.py, and every row with hostile extents substituted -- into a case file, replays it once, and holds the
-return codes and the ledger to the header's rules.  Nothing built with a sanitizer is loaded into python."""
+This module writes the calls -- every valid row of every tests/abi_cases*.py table, every single-defect call tests/abi_derive.py
+derives from them (the calls tests/test_abi_checks_cpu.py makes in-process), and every row with hostile extents substituted -- into a
+case file, replays it once, and holds the return codes and the ledger to the header's rules.  Nothing built with a sanitizer is loaded into python."""
 import copy
 import functools
 import os
@@ -17,7 +17,6 @@ import subprocess
 from minddet_amd import _lib
 from tests import abi_derive as ad
 from tests.abi_cases import F, U8, T
-from tests.pcaug_cases import Call64, mutations64
 from tests.test_workspace_cpu import BOUNDS, COVERED, DIMS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -102,13 +101,13 @@ def with_workspace(case, nbytes):
     ops = list(case.operands[:at])
     ops += [T((1,), F, "opt", null=True) for _ in range(at - len(ops))]
     c.operands = ops + [T((nbytes,), U8, "opt", "free")]
-    return Call64(c)
+    return ad.Call(c)
 
 
 def without_workspace(case):
     c = copy.copy(case)
     c.operands = list(case.operands[:ad.workspace_index(case)])
-    return Call64(c)
+    return ad.Call(c)
 
 
 def ws_dims(case, shapes=None):
@@ -147,7 +146,7 @@ def written():
         ws = ad.workspace_index(case)
         valid_dims = ws_dims(case) if case.sym in WS_OP else None
         # every valid row: as written; without its workspace (the pool); with a workspace of exactly the library's answer; one byte short
-        add(f"valid/{base}/row", ad.call_line(f"valid/{base}/row", Call64(case)), kind="valid", case=case)
+        add(f"valid/{base}/row", ad.call_line(f"valid/{base}/row", ad.Call(case)), kind="valid", case=case)
         if ws is not None:
             add(f"valid/{base}/pool", ad.call_line(f"valid/{base}/pool", without_workspace(case)), kind="valid", case=case)
         if valid_dims is not None:
@@ -157,20 +156,16 @@ def written():
             if need > 16:       # (Scratch::acquire holds an answer of 0 to 16 bytes, tests/test_workspace_cpu.py)
                 add(f"short/{base}", ad.call_line(f"short/{base}", with_workspace(case, need - 1)), kind="short")
         if case.id in EMPTY_BATCH:
-            call = ad.substituted(case, {EMPTY_BATCH[case.id]: 0})
-            ec = Call64.__new__(Call64)
-            ec.__dict__.update(call.__dict__)
+            ec = ad.substituted(case, {EMPTY_BATCH[case.id]: 0})
             ec.null_ptr = [null or 0 in shape for null, shape in zip(ec.null_ptr, ec.shapes)]
             add(f"empty/{base}", ad.call_line(f"empty/{base}", ec), kind="empty")
-        for k, (kind, i, call, want) in enumerate(mutations64(case)):
+        for k, (kind, i, call, want) in enumerate(ad.mutations(case)):
             add(f"defect/{base}/{k}:{kind}/{i}", ad.call_line(f"defect/{base}/{k}:{kind}/{i}", call), kind="defect", want=want)
         for label, table_, probe in ad.hostile_tables(case):
             call = ad.substituted(case, table_)
-            hc = Call64.__new__(Call64)
-            hc.__dict__.update(call.__dict__)
             # a probe (tests/abi_derive.py: every extent below the cap of Args::tensor, by membership in the PROBE sets) reaches the op's
             # own arithmetic, and a huge call may be legal; every other substitution is hostile and must be refused
-            add(f"hostile/{base}/{label}", ad.call_line(f"hostile/{base}/{label}", hc), kind="probe" if probe else "hostile")
+            add(f"hostile/{base}/{label}", ad.call_line(f"hostile/{base}/{label}", call), kind="probe" if probe else "hostile")
             if valid_dims is not None:
                 dims = ws_dims(case, call.shapes)
                 if dims != valid_dims and fits(dims):
@@ -339,8 +334,8 @@ def _events(words, name):
 
 def test_the_scratch_pool_keeps_one_buffer_per_stream_and_frees_what_it_took():
     row = _pool_row()
-    small = Call64(row)                                      # 16 B M = 64 bytes of scratch
-    large = Call64(row)                                      # B = 1024, M = 128: 2 MiB
+    small = ad.Call(row)                                      # 16 B M = 64 bytes of scratch
+    large = ad.Call(row)                                      # B = 1024, M = 128: 2 MiB
     large.shapes = [[1024, 3, 4], [1024, 3], [1024, 3, 8, 12], [1024, 128], [1024, 128], [1024, 128, 2], [1024, 128, 2]]
     need_large = _lib.workspace_bytes("md_cn_assign_targets", 1024, 128)
     assert need_large == 2 << 20

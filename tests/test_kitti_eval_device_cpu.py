@@ -1,5 +1,5 @@
 """CPU: the KITTI AP evaluation operators without a GPU -- the ABI of include/minddet_hip_kittieval.h (the five functions exported, header
-and Makefile wired, the single-defect calls, every documented rc 2 / rc 4 and aliasing answered before any device call, the ctypes
+and Makefile wired, every documented rc 2 / rc 4 and aliasing answered before any device call, the ctypes
 mirrors and limits laid out as the header says), kitti_eval.pack_annos' codes against what clean_data derives from the names, the
 Python layer's refusals, and eval_class after its tail moved into the helper eval_class_device shares."""
 import ctypes as C
@@ -13,21 +13,14 @@ import torch
 
 from minddet_amd import _lib, det_ops
 from minddet_amd import kitti_eval as ke
-from tests.abi_cases import T
+from tests import abi_header as ah
 from tests.abi_cases_kittieval import CASES, CN, DT, GT, K, NI, PTS, FlagsAttrs, OverlapsAttrs, StatsAttrs
-from tests.pcaug_cases import edited, mutations64
+from tests.abi_derive import attr, edited, lib_handle, rc, refuse_single_defects, shape
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR_PATH = os.path.join(ROOT, "include", "minddet_hip_kittieval.h")
 SYMS = ["md_kitti_eval_flags", "md_kitti_eval_overlaps", "md_kitti_eval_match", "md_kitti_eval_thresholds", "md_kitti_eval_stats"]
 ARG, SIZE = 2, 4
 BY_ID = {c.id: c for c in CASES}
-
-
-def _lib_handle():
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    return C.CDLL(_lib.LIB_PATH)
 
 
 def _golden():
@@ -39,8 +32,8 @@ def _np_anno(a):
 
 
 def test_header_declares_the_symbols_and_the_library_exports_them():
-    hdr = open(HDR_PATH).read()
-    assert re.findall(r"^\s*int\s+(\w+)\s*\(MD_AOT_ARGS\)\s*;", hdr, flags=re.M) == SYMS and "_workspace_bytes" not in hdr
+    hdr = ah.header("minddet_hip_kittieval.h")
+    assert ah.aot_symbols(hdr) == SYMS and "_workspace_bytes" not in hdr
     for cite in ("eval_gpu/eval.py:9-27", "eval_utils.py:36-115", "rotate_iou.py:167-302", "ground-truth-major"):
         assert cite in hdr, cite
     mk = open(os.path.join(ROOT, "minddet_amd", "csrc", "Makefile")).read()
@@ -48,7 +41,7 @@ def test_header_declares_the_symbols_and_the_library_exports_them():
     src = open(os.path.join(ROOT, "minddet_amd", "csrc", "kittieval.hip")).read()
     assert src.index("#pragma clang fp contract(off)") < src.index('#include "aot.h"') and ".acquire(" not in src and not re.search(r"atomic\w*\(", src)
     assert {c.sym for c in CASES} == set(SYMS) and len({c.id for c in CASES}) == len(CASES)
-    lib = _lib_handle()
+    lib = lib_handle()
     for sym in SYMS:
         assert getattr(lib, sym)(0, None, None, None, None, None, None) == 1      # wrong parameter count, before anything else
         assert sym not in _lib.exported_symbols()                                  # declared in the new header only
@@ -61,11 +54,10 @@ def test_header_declares_the_symbols_and_the_library_exports_them():
 
 
 def test_ctypes_mirrors_and_limits_have_the_headers_layout():
-    hdr = open(HDR_PATH).read()
+    hdr = ah.header("minddet_hip_kittieval.h")
 
     def fields(name):
-        body = re.search(rf"typedef struct {name} \{{(.*?)\}} {name};", hdr, flags=re.S).group(1)
-        return [s.strip() for s in re.sub(r"/\*.*?\*/", "", body, flags=re.S).split(";") if s.strip()]
+        return ah.statements(name, hdr)
 
     assert fields("md_kitti_eval_flags_attrs") == ["int32_t abs_gt_height"]
     assert fields("md_kitti_eval_overlaps_attrs") == ["int32_t metric"]
@@ -79,35 +71,13 @@ def test_ctypes_mirrors_and_limits_have_the_headers_layout():
     for name, macro, ke_name in (("KEVAL_MAX_DETS", "MD_KEVAL_MAX_DETS", "MAX_DETS"), ("KEVAL_MAX_GTS", "MD_KEVAL_MAX_GTS", "MAX_GTS"),
                                  ("KEVAL_MAX_IMAGES", "MD_KEVAL_MAX_IMAGES", "MAX_IMAGES"), ("KEVAL_MAX_CLASSES", "MD_KEVAL_MAX_CLASSES", "MAX_CLASSES"),
                                  ("KEVAL_MAX_LEVELS", "MD_KEVAL_MAX_LEVELS", "MAX_LEVELS"), ("KEVAL_SAMPLE_PTS", "MD_KEVAL_SAMPLE_PTS", "N_SAMPLE_PTS")):
-        assert getattr(det_ops, name) == getattr(ke, ke_name) == int(re.search(rf"#define {macro} (\d+)", hdr).group(1))
+        assert getattr(det_ops, name) == getattr(ke, ke_name) == ah.defines(hdr)[macro]
     assert det_ops.KEVAL_MAX_DETS == det_ops.KITTI_MAX_DETS == 512 and det_ops.KEVAL_SAMPLE_PTS == PTS == 41
 
 
 @pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])
 def test_single_defect_calls_are_refused_without_a_device(case):
-    lib = _lib_handle()
-    muts = mutations64(case)
-    kinds = {k for k, _, _, _ in muts}
-    want = {"nparam", "params_null", "ndims_null", "shapes_null", "shape_null", "ptr_null", "dtype", "rank-1", "rank+1"}
-    assert want | ({"extra_null"} if case.extra_required else set()) <= kinds
-    bad = [(kind, i, rc, want) for kind, i, call, want in muts for rc in [call.run(lib)] if rc != want]
-    assert not bad, f"{case.id}: (defect, operand, rc, expected) {bad}"
-
-
-def _rc(case, edit):
-    return edited(case, edit).run(_lib_handle())
-
-
-def _shape(i, shp):
-    def edit(c):
-        c.operands[i] = T(shp, c.operands[i].dtype, c.operands[i].kind, c.operands[i].rank, why=c.operands[i].why)
-    return edit
-
-
-def _attr(field, v):
-    def edit(c):
-        setattr(c.extra, field, v)
-    return edit
+    refuse_single_defects("abi_cases_kittieval", case)
 
 
 def _described(case, shapes):
@@ -116,34 +86,34 @@ def _described(case, shapes):
     call = edited(case, lambda c: None)
     for i, shp in shapes.items():
         call.shapes[i] = list(shp)
-    return call.run(_lib_handle())
+    return call.run(lib_handle())
 
 
 def test_semantic_refusals_return_the_documented_codes():
     flags, ov0, ov1 = BY_ID["md_kitti_eval_flags[full]"], BY_ID["md_kitti_eval_overlaps[metric 0]"], BY_ID["md_kitti_eval_overlaps[metric 1]"]
     match, thr, stats = BY_ID["md_kitti_eval_match"], BY_ID["md_kitti_eval_thresholds"], BY_ID["md_kitti_eval_stats[metric 0, aos 1]"]
     # every extent that disagrees: rc 2
-    for i, e in enumerate([_shape(0, (GT, 3)), _shape(0, (GT + 1, 4)), _shape(1, (GT - 1,)), _shape(2, (GT + 1,)), _shape(3, (CN, GT + 1)), _shape(4, (DT, 5)),
-                           _shape(5, (CN + 1, DT)), _shape(5, (CN, DT - 1)), _shape(6, (CN, 2, GT)), _shape(6, (CN, 3, GT + 1)), _shape(7, (CN + 1, 3, DT)),
-                           _shape(7, (CN, 3, DT + 1)), _shape(8, (CN, 2)), _shape(8, (CN + 1, 3)), _attr("abs_gt_height", 2), _attr("abs_gt_height", -1)]):
-        assert _rc(flags, e) == ARG, i
-    for i, e in enumerate([_shape(1, (NI,)), _shape(2, (NI + 2,)), _shape(3, (GT, 7)), _shape(4, (DT, 7)), _shape(3, (GT, 5)), _attr("metric", 3), _attr("metric", -1)]):
-        assert _rc(ov0, e) == ARG, i
-    for i, e in enumerate([_shape(3, (GT, 4)), _shape(4, (DT, 4)), _shape(4, (DT, 5))]):
-        assert _rc(ov1, e) == ARG, i
-    common = [_shape(1, (CN, 2, GT)), _shape(2, (CN + 1, 3, DT)), _shape(2, (CN, 2, DT)), _shape(3, (DT + 1,)), _shape(5, (NI,)), _shape(6, (NI + 2,)),
-              _shape(7, (CN + 1, K))]
-    for i, e in enumerate(common + [_shape(8, (CN, 3, K, GT + 1)), _shape(8, (CN, 3, K + 1, GT)), _shape(8, (CN, 2, K, GT)), _shape(8, (CN + 1, 3, K, GT))]):
-        assert _rc(match, e) == ARG, i
-    for i, e in enumerate([_shape(0, (CN, 2, K, GT)), _shape(1, (CN, 2)), _shape(1, (CN + 1, 3)), _shape(2, (CN, 3, K, PTS - 1)), _shape(2, (CN, 3, K + 1, PTS)),
-                           _shape(3, (CN, 3, K + 1)), _shape(3, (CN + 1, 3, K))]):
-        assert _rc(thr, e) == ARG, i
-    for i, e in enumerate(common + [_shape(8, (CN, 3, K, PTS + 1)), _shape(9, (CN, 3, K + 1)), _shape(10, (GT, 5)), _shape(10, (GT + 1, 4)), _shape(11, (GT + 1,)),
-                                    _shape(12, (DT - 1, 4)), _shape(13, (GT + 1,)), _shape(14, (DT + 1,)), _shape(15, (CN, 3, K, PTS, NI, 2)),
-                                    _shape(15, (CN, 3, K, PTS, NI + 1, 3)), _shape(16, (CN, 3, K, PTS, NI + 1)), _shape(17, (CN, 3, K, PTS, 4)),
-                                    _shape(17, (CN, 3, K + 1, PTS, 3)), _shape(18, (CN, 3, K, PTS - 1)), _attr("metric", 3), _attr("metric", -1),
-                                    _attr("compute_aos", 2), _attr("compute_aos", -1)]):
-        assert _rc(stats, e) == ARG, i
+    for i, e in enumerate([shape(0, (GT, 3)), shape(0, (GT + 1, 4)), shape(1, (GT - 1,)), shape(2, (GT + 1,)), shape(3, (CN, GT + 1)), shape(4, (DT, 5)),
+                           shape(5, (CN + 1, DT)), shape(5, (CN, DT - 1)), shape(6, (CN, 2, GT)), shape(6, (CN, 3, GT + 1)), shape(7, (CN + 1, 3, DT)),
+                           shape(7, (CN, 3, DT + 1)), shape(8, (CN, 2)), shape(8, (CN + 1, 3)), attr("abs_gt_height", 2), attr("abs_gt_height", -1)]):
+        assert rc(flags, e) == ARG, i
+    for i, e in enumerate([shape(1, (NI,)), shape(2, (NI + 2,)), shape(3, (GT, 7)), shape(4, (DT, 7)), shape(3, (GT, 5)), attr("metric", 3), attr("metric", -1)]):
+        assert rc(ov0, e) == ARG, i
+    for i, e in enumerate([shape(3, (GT, 4)), shape(4, (DT, 4)), shape(4, (DT, 5))]):
+        assert rc(ov1, e) == ARG, i
+    common = [shape(1, (CN, 2, GT)), shape(2, (CN + 1, 3, DT)), shape(2, (CN, 2, DT)), shape(3, (DT + 1,)), shape(5, (NI,)), shape(6, (NI + 2,)),
+              shape(7, (CN + 1, K))]
+    for i, e in enumerate(common + [shape(8, (CN, 3, K, GT + 1)), shape(8, (CN, 3, K + 1, GT)), shape(8, (CN, 2, K, GT)), shape(8, (CN + 1, 3, K, GT))]):
+        assert rc(match, e) == ARG, i
+    for i, e in enumerate([shape(0, (CN, 2, K, GT)), shape(1, (CN, 2)), shape(1, (CN + 1, 3)), shape(2, (CN, 3, K, PTS - 1)), shape(2, (CN, 3, K + 1, PTS)),
+                           shape(3, (CN, 3, K + 1)), shape(3, (CN + 1, 3, K))]):
+        assert rc(thr, e) == ARG, i
+    for i, e in enumerate(common + [shape(8, (CN, 3, K, PTS + 1)), shape(9, (CN, 3, K + 1)), shape(10, (GT, 5)), shape(10, (GT + 1, 4)), shape(11, (GT + 1,)),
+                                    shape(12, (DT - 1, 4)), shape(13, (GT + 1,)), shape(14, (DT + 1,)), shape(15, (CN, 3, K, PTS, NI, 2)),
+                                    shape(15, (CN, 3, K, PTS, NI + 1, 3)), shape(16, (CN, 3, K, PTS, NI + 1)), shape(17, (CN, 3, K, PTS, 4)),
+                                    shape(17, (CN, 3, K + 1, PTS, 3)), shape(18, (CN, 3, K, PTS - 1)), attr("metric", 3), attr("metric", -1),
+                                    attr("compute_aos", 2), attr("compute_aos", -1)]):
+        assert rc(stats, e) == ARG, i
     # every documented limit: rc 4 (the descriptions alone say so)
     C1, K1, I1 = det_ops.KEVAL_MAX_CLASSES + 1, det_ops.KEVAL_MAX_LEVELS + 1, det_ops.KEVAL_MAX_IMAGES + 1
     G1, D1 = det_ops.KEVAL_MAX_IMAGES * det_ops.KEVAL_MAX_GTS + 1, det_ops.KEVAL_MAX_IMAGES * det_ops.KEVAL_MAX_DETS + 1
@@ -168,7 +138,7 @@ def test_semantic_refusals_return_the_documented_codes():
 
 def test_aliased_outputs_are_refused():
     """an output at the address of an input or of another output: rc 2 before any device call"""
-    lib = _lib_handle()
+    lib = lib_handle()
     for cid, pairs in (("md_kitti_eval_flags[full]", ((6, 3), (7, 5), (7, 6), (8, 1))), ("md_kitti_eval_overlaps[metric 0]", ((5, 3), (5, 4))),
                        ("md_kitti_eval_match", ((8, 0), (8, 3))), ("md_kitti_eval_thresholds", ((2, 0), (3, 1), (3, 2))),
                        ("md_kitti_eval_stats[metric 0, aos 1]", ((15, 9), (16, 0), (17, 15), (18, 16), (18, 8)))):

@@ -1,11 +1,10 @@
 """CPU: the KITTI camera-frame ends without a GPU -- the ABI of include/minddet_hip_kitti.h (the three functions exported, header and
-Makefile wired, the single-defect calls and every documented rc 2 / rc 4 answered before any device call, the ctypes mirror laid out
+Makefile wired, every documented rc 2 / rc 4 answered before any device call, the ctypes mirror laid out
 as the header says), det_ops.KittiCalibration's frustums and the contract tests/kitti_io_contract.py against the reference's own
 outputs (tests/golden/kitti_io_vectors.npz, written by tests/golden/gen_kitti_io.py), the contract's rows against
 minddet_amd/kitti_eval.py's host path within the derived bound, rows_to_annos, the two configs and the refused options."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
@@ -13,57 +12,48 @@ import torch
 
 from minddet_amd import _lib, det_ops, kitti_eval
 from tests import kitti_io_contract as kc
-from tests.abi_cases import F, I, T
+from tests import abi_header as ah
+from tests.abi_cases import I
 from tests.abi_cases_kitti import CASES, F64, KittiRows   # noqa: F401
+from tests.abi_derive import attr, both, edited, item, lib_handle, rc, refuse_single_defects, shape
 from tests.kitti_io_cases import CAR_RANGE, GOLD, boxes_as_hulls, calibration, detections, fixture
-from tests.pcaug_cases import edited, mutations64
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR_PATH = os.path.join(ROOT, "include", "minddet_hip_kitti.h")
 SYMS = ["md_pc_crop_hulls", "md_kitti_boxes_to_lidar", "md_kitti_rows"]
 U8 = "uint8"
 ARG, SIZE = 2, 4
 
 
 def _hdr():
-    return open(HDR_PATH).read()
-
-
-def _lib_handle():
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    return C.CDLL(_lib.LIB_PATH)
+    return ah.header("minddet_hip_kitti.h")
 
 
 def test_header_declares_the_symbols_and_the_library_exports_them():
     hdr = _hdr()
-    pat = r"^\s*int\s+(\w+)\s*\(MD_AOT_ARGS\)\s*;"     # the expression of _lib.exported_symbols
-    assert re.findall(pat, hdr, flags=re.M) == SYMS and '#include "minddet_hip_points.h"' in hdr
+    assert ah.aot_symbols(hdr) == SYMS and '#include "minddet_hip_points.h"' in hdr
     for cite in ("box_np_ops.py:625-636", "preprocess.py:59-67", "box_np_ops.py:599-613", "predict.py:204-262, 331-396", "geometry.py:46-54",
                  "remove_environment", "random_crop", "generate_single_sample_dict", "fp32-calibration"):
         assert cite in hdr, cite
     mk = open(os.path.join(ROOT, "minddet_amd", "csrc", "Makefile")).read()
     assert "minddet_hip_kitti.h" in mk and os.path.exists(os.path.join(ROOT, "minddet_amd", "csrc", "kitti.hip"))
     assert {c.sym for c in CASES} == set(SYMS) and len({c.id for c in CASES}) == len(CASES)
-    lib = _lib_handle()
+    lib = lib_handle()
     for sym in SYMS:
         assert getattr(lib, sym)(0, None, None, None, None, None, None) == 1      # wrong parameter count, before anything else
         assert sym not in _lib.exported_symbols()                                  # declared in the new header only
-    old = open(os.path.join(ROOT, "include", "minddet_hip_pcaug.h")).read()       # its note stays true of those ops
+    old = ah.header("minddet_hip_pcaug.h")       # its note stays true of those ops
     assert "reference_detections, remove_environment, remove_outside_points" in old
 
 
 def test_ctypes_mirror_limits_and_workspace_have_the_headers_layout():
     hdr = _hdr()
-    body = re.search(r"typedef struct md_kitti_rows_attrs \{(.*?)\} md_kitti_rows_attrs;", hdr, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    assert [s.strip() for s in body.split(";") if s.strip()] == ["float limit_range[6]", "int32_t use_limit", "int32_t lidar_input"]
+    assert ah.statements("md_kitti_rows_attrs", hdr) == ["float limit_range[6]", "int32_t use_limit", "int32_t lidar_input"]
     for got in (det_ops._KittiRowsAttrs, KittiRows):
         assert C.sizeof(got) == 32 and got.limit_range.offset == 0 and got.limit_range.size == 24
         assert got.use_limit.offset == 24 and got.lidar_input.offset == 28 and got.lidar_input.size == 4
     for name, macro in (("CROP_MAX_HULLS", "MD_CROP_MAX_HULLS"), ("CROP_MAX_BATCH", "MD_CROP_MAX_BATCH"), ("KITTI_MAX_DETS", "MD_KITTI_MAX_DETS"),
                         ("KITTI_MAX_LABELS", "MD_KITTI_MAX_LABELS"), ("KITTI_MAX_BATCH", "MD_KITTI_MAX_BATCH")):
-        assert getattr(det_ops, name) == int(re.search(rf"#define {macro} (\d+)", hdr).group(1))
+        assert getattr(det_ops, name) == ah.defines(hdr)[macro]
     assert det_ops.CROP_MAX_HULLS == kc.MAX_HULLS == 64 and det_ops.KITTI_MAX_DETS == kc.MAX_DETS == 512
     assert "192 B K + 4 (N / 256 + 3) bytes" in hdr
     assert det_ops.crop_hulls_workspace_bytes(300, 2, 3) == 1164 <= 1168 and det_ops.crop_hulls_workspace_bytes(480000, 4, 1) == 8272 <= 768 + 4 * 1878
@@ -71,75 +61,47 @@ def test_ctypes_mirror_limits_and_workspace_have_the_headers_layout():
 
 @pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])
 def test_single_defect_calls_are_refused_without_a_device(case):
-    lib = _lib_handle()
-    muts = mutations64(case)
-    kinds = {k for k, _, _, _ in muts}
-    want = {"nparam", "params_null", "ndims_null", "shapes_null", "shape_null", "ptr_null", "dtype", "rank-1", "rank+1"}
-    assert want | ({"extra_null"} if case.extra_required else set()) <= kinds
-    bad = [(kind, i, rc, want) for kind, i, call, want in muts for rc in [call.run(lib)] if rc != want]
-    assert not bad, f"{case.id}: (defect, operand, rc, expected) {bad}"
-
-
-def _rc(case, edit):
-    return edited(case, edit).run(_lib_handle())
-
-
-def _shape(i, shp, dtype=F):
-    def edit(c):
-        c.operands[i] = T(shp, dtype, c.operands[i].kind, c.operands[i].rank, why=c.operands[i].why)
-    return edit
-
-
-def _both(*edits):
-    def edit(c):
-        for e in edits:
-            e(c)
-    return edit
+    refuse_single_defects("abi_cases_kitti", case)
 
 
 def test_semantic_refusals_return_the_documented_codes():
     ws, pool, lidar, rows, _ = CASES
     # md_pc_crop_hulls: F != 4, every extent that disagrees
-    for i, e in enumerate([_shape(0, (300, 3)), _shape(0, (300, 5)), _shape(1, (2,), I), _shape(1, (4,), I), _shape(2, (3, 3, 8, 3), F64),
-                           _shape(2, (2, 3, 7, 3), F64), _shape(2, (2, 3, 8, 4), F64), _shape(3, (3,), I), _shape(4, (299, 4)), _shape(4, (300, 3)),
-                           _shape(5, (2,), I), _shape(6, (299,), U8), _shape(6, (301,), U8)]):
-        assert _rc(ws, e) == ARG, i
+    for i, e in enumerate([shape(0, (300, 3)), shape(0, (300, 5)), shape(1, (2,), I), shape(1, (4,), I), shape(2, (3, 3, 8, 3), F64),
+                           shape(2, (2, 3, 7, 3), F64), shape(2, (2, 3, 8, 4), F64), shape(3, (3,), I), shape(4, (299, 4)), shape(4, (300, 3)),
+                           shape(5, (2,), I), shape(6, (299,), U8), shape(6, (301,), U8)]):
+        assert rc(ws, e) == ARG, i
     K1, B1 = det_ops.CROP_MAX_HULLS + 1, det_ops.CROP_MAX_BATCH + 1
-    assert _rc(pool, _shape(2, (2, K1, 8, 3), F64)) == SIZE
-    assert _rc(pool, _both(_shape(1, (B1 + 1,), I), _shape(2, (B1, 1, 8, 3), F64), _shape(3, (B1,), I), _shape(5, (B1 + 1,), I))) == SIZE
+    assert rc(pool, shape(2, (2, K1, 8, 3), F64)) == SIZE
+    assert rc(pool, both(shape(1, (B1 + 1,), I), shape(2, (B1, 1, 8, 3), F64), shape(3, (B1,), I), shape(5, (B1 + 1,), I))) == SIZE
     call = edited(pool, lambda c: None)                       # (the shapes alone say 2^30 points: the host blocks stay small, nothing is touched)
     call.shapes[0], call.shapes[4], call.shapes[6] = [1 << 30, 4], [1 << 30, 4], [1 << 30]
-    assert call.run(_lib_handle()) == SIZE
-    assert _rc(ws, _shape(7, (1159,), U8)) == SIZE            # 1160 bytes are used
+    assert call.run(lib_handle()) == SIZE
+    assert rc(ws, shape(7, (1159,), U8)) == SIZE            # 1160 bytes are used
     # md_kitti_boxes_to_lidar
-    for i, e in enumerate([_shape(0, (2, 5, 6)), _shape(0, (2, 5, 8)), _shape(1, (3,), I), _shape(2, (2, 3, 4), F64), _shape(2, (2, 4, 3), F64),
-                           _shape(2, (3, 4, 4), F64), _shape(3, (2, 4, 7)), _shape(3, (2, 5, 6))]):
-        assert _rc(lidar, e) == ARG, i
+    for i, e in enumerate([shape(0, (2, 5, 6)), shape(0, (2, 5, 8)), shape(1, (3,), I), shape(2, (2, 3, 4), F64), shape(2, (2, 4, 3), F64),
+                           shape(2, (3, 4, 4), F64), shape(3, (2, 4, 7)), shape(3, (2, 5, 6))]):
+        assert rc(lidar, e) == ARG, i
     G1, B2 = det_ops.KITTI_MAX_LABELS + 1, det_ops.KITTI_MAX_BATCH + 1
-    assert _rc(lidar, _both(_shape(0, (2, G1, 7)), _shape(3, (2, G1, 7)))) == SIZE
-    assert _rc(lidar, _both(_shape(0, (B2, 1, 7)), _shape(1, (B2,), I), _shape(2, (B2, 4, 4), F64), _shape(3, (B2, 1, 7)))) == SIZE
+    assert rc(lidar, both(shape(0, (2, G1, 7)), shape(3, (2, G1, 7)))) == SIZE
+    assert rc(lidar, both(shape(0, (B2, 1, 7)), shape(1, (B2,), I), shape(2, (B2, 4, 4), F64), shape(3, (B2, 1, 7)))) == SIZE
     # md_kitti_rows
-    for i, e in enumerate([_shape(0, (2, 5, 8)), _shape(0, (2, 5, 10)), _shape(1, (3,), I), _shape(2, (2, 3, 4), F64), _shape(3, (2, 4, 3), F64),
-                           _shape(3, (3, 4, 4), F64), _shape(4, (2, 3), I), _shape(4, (3, 2), I), _shape(5, (2, 5, 13)), _shape(5, (2, 4, 14)),
-                           _shape(6, (2, 4), I), _shape(6, (3, 5), I), _shape(7, (3,), I)]):
-        assert _rc(rows, e) == ARG, i
+    for i, e in enumerate([shape(0, (2, 5, 8)), shape(0, (2, 5, 10)), shape(1, (3,), I), shape(2, (2, 3, 4), F64), shape(3, (2, 4, 3), F64),
+                           shape(3, (3, 4, 4), F64), shape(4, (2, 3), I), shape(4, (3, 2), I), shape(5, (2, 5, 13)), shape(5, (2, 4, 14)),
+                           shape(6, (2, 4), I), shape(6, (3, 5), I), shape(7, (3,), I)]):
+        assert rc(rows, e) == ARG, i
     for field, v in (("use_limit", 2), ("use_limit", -1), ("lidar_input", 2), ("lidar_input", -1)):
-        def attr(c, field=field, v=v):
-            setattr(c.extra, field, v)
-        assert _rc(rows, attr) == ARG, (field, v)
-
-    def nan_limit(c):
-        c.extra.limit_range[4] = float("nan")
-    assert _rc(rows, nan_limit) == ARG
+        assert rc(rows, attr(field, v)) == ARG, (field, v)
+    assert rc(rows, item("limit_range", 4, float("nan"))) == ARG
     M1 = det_ops.KITTI_MAX_DETS + 1
-    assert _rc(rows, _both(_shape(0, (2, M1, 9)), _shape(5, (2, M1, 14)), _shape(6, (2, M1), I))) == SIZE
-    assert _rc(rows, _both(_shape(0, (B2, 1, 9)), _shape(1, (B2,), I), _shape(2, (B2, 4, 4), F64), _shape(3, (B2, 4, 4), F64), _shape(4, (B2, 2), I),
-                           _shape(5, (B2, 1, 14)), _shape(6, (B2, 1), I), _shape(7, (B2,), I))) == SIZE
+    assert rc(rows, both(shape(0, (2, M1, 9)), shape(5, (2, M1, 14)), shape(6, (2, M1), I))) == SIZE
+    assert rc(rows, both(shape(0, (B2, 1, 9)), shape(1, (B2,), I), shape(2, (B2, 4, 4), F64), shape(3, (B2, 4, 4), F64), shape(4, (B2, 2), I),
+                           shape(5, (B2, 1, 14)), shape(6, (B2, 1), I), shape(7, (B2,), I))) == SIZE
 
 
 def test_aliased_outputs_are_refused():
     """an output at the address of an input or of another output: rc 2 before any device call"""
-    lib = _lib_handle()
+    lib = lib_handle()
     for case, pairs in ((CASES[0], ((4, 0), (5, 1), (6, 5), (5, 3), (6, 4))), (CASES[2], ((3, 0),)), (CASES[3], ((5, 0), (6, 4), (7, 1), (7, 6), (6, 5)))):
         for out, other in pairs:
             call = edited(case, lambda c: None)

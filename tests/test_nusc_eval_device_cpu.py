@@ -1,5 +1,5 @@
 """CPU: the nuScenes evaluation operators without a GPU -- the ABI of include/minddet_hip_nusceval.h (the three functions exported, header
-and Makefile wired, the single-defect calls, every documented rc 2 / rc 4 and aliasing answered before any device call, the ctypes mirrors
+and Makefile wired, every documented rc 2 / rc 4 and aliasing answered before any device call, the ctypes mirrors
 and limits laid out as the header says), the Python layer's refusals, the contract (tests/nusc_eval_contract.py) against
 NuscDetectionEval.evaluate() bit for bit on the test set, the rows contract against dets_to_nusc and pack_nusc, the element rule of
 interp against np.interp, the eight planted defects, each of which must change the contract's tables, and summarize() on a hand-computed
@@ -13,30 +13,23 @@ import numpy as np
 import pytest
 import torch
 
-from minddet_amd import _lib, det_ops
+from minddet_amd import det_ops
 from minddet_amd import nusc_eval as ne
 from tests import nusc_eval_contract as nc
-from tests.abi_cases import T
-from tests.abi_cases_nusceval import CASES, CELLS, DT, GT, KC, MAX_DET, ND, NI, NL, NR, EvalAttrs, RowsAttrs
-from tests.pcaug_cases import edited, mutations64
+from tests import abi_header as ah
+from tests.abi_cases_nusceval import CASES, CELLS, DT, GT, KC, MAX_DET, ND, NI, NR, EvalAttrs, RowsAttrs
+from tests.abi_derive import attr, edited, lib_handle, rc, refuse_single_defects, shape
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR_PATH = os.path.join(ROOT, "include", "minddet_hip_nusceval.h")
 SYMS = ["md_nusc_rows", "md_nusc_eval_match", "md_nusc_eval_accumulate"]
 ARG, SIZE = 2, 4
 BY_ID = {c.id: c for c in CASES}
 REC = np.linspace(0, 1, 101)
 
 
-def _lib_handle():
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    return C.CDLL(_lib.LIB_PATH)
-
-
 def test_header_declares_the_symbols_and_the_library_exports_them():
-    hdr = open(HDR_PATH).read()
-    assert re.findall(r"^\s*int\s+(\w+)\s*\(MD_AOT_ARGS\)\s*;", hdr, flags=re.M) == SYMS and "_workspace_bytes" not in hdr
+    hdr = ah.header("minddet_hip_nusceval.h")
+    assert ah.aot_symbols(hdr) == SYMS and "_workspace_bytes" not in hdr
     for cite in ("nusc_common.py:160-201", "nuscenes.py:252-293", "nusc_common.py:659-674", "the lowest row on equal distance", "np.cumsum's bits"):
         assert cite in hdr, cite
     mk = open(os.path.join(ROOT, "minddet_amd", "csrc", "Makefile")).read()
@@ -45,7 +38,7 @@ def test_header_declares_the_symbols_and_the_library_exports_them():
     assert src.index("#pragma clang fp contract(off)") < src.index('#include "aot.h"') and ".acquire(" not in src and not re.search(r"atomic\w*\(", src)
     assert '#include "workgroup.h"' in src and "hipMemset" not in src
     assert {c.sym for c in CASES} == set(SYMS) and len({c.id for c in CASES}) == len(CASES)
-    lib = _lib_handle()
+    lib = lib_handle()
     for sym in SYMS:
         assert getattr(lib, sym)(0, None, None, None, None, None, None) == 1      # wrong parameter count, before anything else
     for other in os.listdir(os.path.join(ROOT, "include")):
@@ -54,14 +47,13 @@ def test_header_declares_the_symbols_and_the_library_exports_them():
 
 
 def test_ctypes_mirrors_and_limits_have_the_headers_layout():
-    hdr = open(HDR_PATH).read()
+    hdr = ah.header("minddet_hip_nusceval.h")
     for struct, field, mirrors in (("md_nusc_rows_attrs", "first_sample", (det_ops._NuscRowsAttrs, RowsAttrs)),
                                    ("md_nusc_eval_attrs", "tp_index", (det_ops._NuscEvalAttrs, EvalAttrs))):
-        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), hdr, flags=re.S).group(1)
-        assert [s.strip() for s in re.sub(r"/\*.*?\*/", "", body, flags=re.S).split(";") if s.strip()] == ["int32_t " + field]
+        assert ah.statements(struct, hdr) == ["int32_t " + field]
         for got in mirrors:
             assert C.sizeof(got) == 4 and getattr(got, field).offset == 0
-    macros = {k: int(v) for k, v in re.findall(r"#define MD_NUSCEVAL_(\w+) (\d+)", hdr)}
+    macros = {k[len("MD_NUSCEVAL_"):]: v for k, v in ah.defines(hdr).items() if k.startswith("MD_NUSCEVAL_")}
     assert set(macros) == {"MAX_SAMPLE_DETS", "MAX_GTS", "MAX_CLASSES", "MAX_THRS", "MAX_RECS", "MAX_CELLS", "MAX_ROWS", "MAX_LABELS"}
     for name, v in macros.items():
         assert getattr(det_ops, "NUSCEVAL_" + name) == v, name
@@ -74,29 +66,7 @@ def test_ctypes_mirrors_and_limits_have_the_headers_layout():
 
 @pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])
 def test_single_defect_calls_are_refused_without_a_device(case):
-    lib = _lib_handle()
-    muts = mutations64(case)
-    kinds = {k for k, _, _, _ in muts}
-    want = {"nparam", "params_null", "ndims_null", "shapes_null", "shape_null", "ptr_null", "dtype", "rank-1", "rank+1", "extra_null"}
-    assert want <= kinds
-    bad = [(kind, i, rc, want) for kind, i, call, want in muts for rc in [call.run(lib)] if rc != want]
-    assert not bad, f"{case.id}: (defect, operand, rc, expected) {bad}"
-
-
-def _rc(case, edit):
-    return edited(case, edit).run(_lib_handle())
-
-
-def _shape(i, shp):
-    def edit(c):
-        c.operands[i] = T(shp, c.operands[i].dtype, c.operands[i].kind, c.operands[i].rank, why=c.operands[i].why)
-    return edit
-
-
-def _attr(field, v):
-    def edit(c):
-        setattr(c.extra, field, v)
-    return edit
+    refuse_single_defects("abi_cases_nusceval", case)
 
 
 def _described(case, shapes):
@@ -105,29 +75,29 @@ def _described(case, shapes):
     call = edited(case, lambda c: None)
     for i, shp in shapes.items():
         call.shapes[i] = list(shp)
-    return call.run(_lib_handle())
+    return call.run(lib_handle())
 
 
 def test_semantic_refusals_return_the_documented_codes():
     rows, match, accum = BY_ID["md_nusc_rows[whole set]"], BY_ID["md_nusc_eval_match"], BY_ID["md_nusc_eval_accumulate"]
     # every extent that disagrees: rc 2
-    for i, e in enumerate([_shape(0, (NI, MAX_DET, 10)), _shape(0, (NI, 3, 11)), _shape(1, (NI + 1,)), _shape(2, (NI, 13)), _shape(2, (NI + 1, 14)),
-                           _shape(5, (KC + 1,)), _shape(6, (KC - 1,)), _shape(7, (DT, 4)), _shape(8, (DT + 1, 3)), _shape(9, (DT, 3)), _shape(10, (DT, 3)),
-                           _shape(11, (DT + 1,)), _shape(12, (DT - 1,)), _shape(13, (DT + 1,)), _shape(14, (DT - 1,)), _shape(15, (DT + 1,)),
-                           _shape(16, (DT - 1,)), _shape(17, (CELLS + 1,)), _shape(18, (CELLS - 1,)), _shape(0, (NI + 1, MAX_DET, 11)),
-                           _attr("first_sample", -1), _attr("first_sample", 1), _attr("first_sample", NI)]):
-        assert _rc(rows, e) == ARG, i
+    for i, e in enumerate([shape(0, (NI, MAX_DET, 10)), shape(0, (NI, 3, 11)), shape(1, (NI + 1,)), shape(2, (NI, 13)), shape(2, (NI + 1, 14)),
+                           shape(5, (KC + 1,)), shape(6, (KC - 1,)), shape(7, (DT, 4)), shape(8, (DT + 1, 3)), shape(9, (DT, 3)), shape(10, (DT, 3)),
+                           shape(11, (DT + 1,)), shape(12, (DT - 1,)), shape(13, (DT + 1,)), shape(14, (DT - 1,)), shape(15, (DT + 1,)),
+                           shape(16, (DT - 1,)), shape(17, (CELLS + 1,)), shape(18, (CELLS - 1,)), shape(0, (NI + 1, MAX_DET, 11)),
+                           attr("first_sample", -1), attr("first_sample", 1), attr("first_sample", NI)]):
+        assert rc(rows, e) == ARG, i
     assert _described(rows, {17: (CELLS + 3,), 18: (CELLS + 3,)}) == ARG            # nine cells over two samples of three classes
-    for i, e in enumerate([_shape(1, (CELLS + 1,)), _shape(2, (CELLS - 1,)), _shape(3, (CELLS + 1,)), _shape(4, (GT, 3)), _shape(5, (GT, 2)), _shape(5, (GT + 1, 3)),
-                           _shape(6, (GT - 1,)), _shape(7, (GT, 3)), _shape(8, (GT + 1,)), _shape(9, (DT, 2)), _shape(10, (DT + 1, 3)), _shape(11, (DT - 1,)),
-                           _shape(12, (DT, 3)), _shape(13, (DT + 1,)), _shape(16, (ND, DT + 1)), _shape(16, (ND + 1, DT)), _shape(17, (DT, 4)),
-                           _shape(17, (DT + 1, 5)), _shape(18, (CELLS + 1,)), _shape(15, (KC + 1,)), _attr("tp_index", -1), _attr("tp_index", ND)]):
-        assert _rc(match, e) == ARG, i
-    for i, e in enumerate([_shape(0, (DT + 1,)), _shape(2, (DT - 1,)), _shape(1, (KC + 2,)), _shape(1, (1,)), _shape(3, (ND, DT + 1)), _shape(4, (DT, 4)),
-                           _shape(4, (DT + 1, 5)), _shape(5, (CELLS + 1,)), _shape(7, (KC, ND, NR + 1)), _shape(8, (KC, ND + 1, NR)), _shape(8, (KC + 1, ND, NR)),
-                           _shape(9, (KC, 4, NR)), _shape(10, (KC + 1,)), _shape(11, (KC, ND + 1)), _shape(12, (ND, DT + 1)), _shape(12, (ND + 1, DT)),
-                           _shape(13, (DT + 1,)), _shape(14, (4, DT)), _shape(14, (5, DT + 1)), _attr("tp_index", -1), _attr("tp_index", ND)]):
-        assert _rc(accum, e) == ARG, i
+    for i, e in enumerate([shape(1, (CELLS + 1,)), shape(2, (CELLS - 1,)), shape(3, (CELLS + 1,)), shape(4, (GT, 3)), shape(5, (GT, 2)), shape(5, (GT + 1, 3)),
+                           shape(6, (GT - 1,)), shape(7, (GT, 3)), shape(8, (GT + 1,)), shape(9, (DT, 2)), shape(10, (DT + 1, 3)), shape(11, (DT - 1,)),
+                           shape(12, (DT, 3)), shape(13, (DT + 1,)), shape(16, (ND, DT + 1)), shape(16, (ND + 1, DT)), shape(17, (DT, 4)),
+                           shape(17, (DT + 1, 5)), shape(18, (CELLS + 1,)), shape(15, (KC + 1,)), attr("tp_index", -1), attr("tp_index", ND)]):
+        assert rc(match, e) == ARG, i
+    for i, e in enumerate([shape(0, (DT + 1,)), shape(2, (DT - 1,)), shape(1, (KC + 2,)), shape(1, (1,)), shape(3, (ND, DT + 1)), shape(4, (DT, 4)),
+                           shape(4, (DT + 1, 5)), shape(5, (CELLS + 1,)), shape(7, (KC, ND, NR + 1)), shape(8, (KC, ND + 1, NR)), shape(8, (KC + 1, ND, NR)),
+                           shape(9, (KC, 4, NR)), shape(10, (KC + 1,)), shape(11, (KC, ND + 1)), shape(12, (ND, DT + 1)), shape(12, (ND + 1, DT)),
+                           shape(13, (DT + 1,)), shape(14, (4, DT)), shape(14, (5, DT + 1)), attr("tp_index", -1), attr("tp_index", ND)]):
+        assert rc(accum, e) == ARG, i
     # every documented limit: rc 4 (the descriptions alone say so)
     D = det_ops
     md1 = D.NUSCEVAL_MAX_SAMPLE_DETS + 1
@@ -161,7 +131,7 @@ def test_semantic_refusals_return_the_documented_codes():
 
 def test_aliased_outputs_are_refused():
     """an output at the address of an input or of another output: rc 2 before any device call"""
-    lib = _lib_handle()
+    lib = lib_handle()
     for cid, pairs in (("md_nusc_rows[whole set]", ((7, 0), (13, 1), (8, 7), (18, 17), (16, 3), (12, 11), (9, 2))),
                        ("md_nusc_eval_match", ((16, 0), (17, 4), (17, 16), (18, 3), (18, 16))),
                        ("md_nusc_eval_accumulate", ((7, 6), (8, 7), (10, 5), (12, 3), (14, 13), (13, 2)))):

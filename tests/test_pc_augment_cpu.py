@@ -1,11 +1,10 @@
-"""CPU: the KITTI training augmentation without a GPU -- the ABI of include/minddet_hip_pcaug.h (the functions exported, the
-single-defect calls and the semantic refusals answered before any device call, the ctypes mirrors laid out as the header says), the
+"""CPU: the KITTI training augmentation without a GPU -- the ABI of include/minddet_hip_pcaug.h (the functions exported,
+the semantic refusals answered before any device call, the ctypes mirrors laid out as the header says), the
 contract tests/pcaug_contract.py against the reference's own outputs (tests/golden/pc_augment_vectors.npz, written by
 tests/golden/gen_pc_augment.py from noise_per_object, remove_points_in_boxes, the four global steps and
 filter_gt_box_outside_range), and det_ops.PointCloudAugment built from both train configs."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
@@ -13,117 +12,85 @@ import torch
 
 from minddet_amd import _lib, det_ops
 from tests import pcaug_contract as pc
-from tests.abi_cases import F, I, T
+from tests import abi_header as ah
+from tests.abi_cases import I, T
 from tests.abi_cases_pcaug import CASES, F64, PCBoxes
-from tests.pcaug_cases import GOLD, NAMES, contract_case, edited, fixture_case, mutations64, reference_owner
+from tests.abi_derive import both, edited, item, lib_handle, rc, refuse_single_defects, shape
+from tests.pcaug_cases import GOLD, NAMES, contract_case, fixture_case, reference_owner
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = open(os.path.join(ROOT, "include", "minddet_hip_pcaug.h")).read()
+HDR = ah.header("minddet_hip_pcaug.h")
 SYMS = ["md_pc_noise_per_object", "md_pc_augment_points", "md_pc_augment_boxes"]
 UNDECIDED_CAP = 2e-3      # of the pairs within 1 m of a face (the reference's points_in_rbbox against a float64 judge on 24 boxes x 6 000 points: 2.7e-4)
 
 
-def _lib_handle():
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    return C.CDLL(_lib.LIB_PATH)
-
-
 def test_header_declares_the_symbols_and_the_library_exports_them():
-    pat = r"^\s*int\s+(\w+)\s*\(MD_AOT_ARGS\)\s*;"     # the expression of _lib.exported_symbols
-    assert re.findall(pat, HDR, flags=re.M) == SYMS and '#include "minddet_hip_points.h"' in HDR
+    assert ah.aot_symbols(HDR) == SYMS and '#include "minddet_hip_points.h"' in HDR
     for cite in ("preprocess.py:124-170", ":560-668", ":423-441", ":138-152", "geometry.py:18-55", "box_np_ops.py:390-392"):
         assert cite in HDR, cite
     for quirk in ("(a)", "(b)", "(c)", "(d)", "(e)"):
         assert quirk in HDR
     assert "minddet_hip_pcaug.h" in open(os.path.join(ROOT, "minddet_amd", "csrc", "Makefile")).read()
     assert {c.sym for c in CASES} == set(SYMS) and len({c.id for c in CASES}) == len(CASES)
-    lib = _lib_handle()
+    lib = lib_handle()
     for s in SYMS:
         assert getattr(lib, s)(0, None, None, None, None, None, None) == 1      # wrong parameter count, before anything else
     assert not set(SYMS) & set(_lib.exported_symbols())                          # declared in the new header only
 
 
 def test_ctypes_mirrors_have_the_headers_layout():
-    body = re.search(r"typedef struct md_pc_boxes_attrs \{(.*?)\} md_pc_boxes_attrs;", HDR, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    assert [s.strip() for s in body.split(";") if s.strip()] == ["float bv_range[4]"]
+    assert ah.statements("md_pc_boxes_attrs", HDR) == ["float bv_range[4]"]
     for got in (det_ops._PCBoxesAttrs, PCBoxes):
         assert C.sizeof(got) == 16 and got.bv_range.offset == 0 and got.bv_range.size == 16
     for name, macro in (("PCAUG_MAX_BOXES", "MD_PCAUG_MAX_BOXES"), ("PCAUG_MAX_TRIES", "MD_PCAUG_MAX_TRIES")):
-        assert getattr(det_ops, name) == int(re.search(rf"#define {macro} (\d+)", HDR).group(1))
+        assert getattr(det_ops, name) == ah.defines(HDR)[macro]
 
 
 @pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])
 def test_single_defect_calls_are_refused_without_a_device(case):
-    lib = _lib_handle()
-    muts = mutations64(case)
-    kinds = {k for k, _, _, _ in muts}
-    assert {"nparam", "params_null", "ndims_null", "shapes_null", "shape_null", "ptr_null", "dtype", "rank-1", "rank+1"} <= kinds
-    assert ("extra_null" in kinds) == case.extra_required
-    bad = [(kind, i, rc, want) for kind, i, call, want in muts for rc in [call.run(lib)] if rc != want]
-    assert not bad, f"{case.id}: (defect, operand, rc, expected) {bad}"
-
-
-def _rc(case, edit):
-    return edited(case, edit).run(_lib_handle())
-
-
-def _shape(i, shp, dtype=F):
-    def edit(c):
-        c.operands[i] = T(shp, dtype, c.operands[i].kind, c.operands[i].rank, why=c.operands[i].why)
-    return edit
-
-
-def _both(*edits):
-    def edit(c):
-        for e in edits:
-            e(c)
-    return edit
+    refuse_single_defects("abi_cases_pcaug", case)
 
 
 def test_semantic_refusals_return_the_documented_codes():
     ARG, SIZE = 2, 4
     noise, noise_null, points, points_ws, boxes = CASES
-    for i, e in enumerate([_shape(0, (2, 3, 8)), _shape(0, (2, 3, 9)), _shape(1, (3,), I), _shape(2, (2, 4), "uint8"), _shape(3, (2, 3, 4, 2), F64),
-                           _shape(4, (2, 3, 5), F64), _shape(5, (2, 3, 5), F64), _shape(6, (2, 4), I), _shape(7, (2, 3, 3), F64), _shape(8, (2, 4, 7)),
-                           _both(_shape(3, (2, 3, 0, 3), F64), _shape(4, (2, 3, 0), F64), _shape(5, (2, 3, 0), F64))]):     # T < 1
-        assert _rc(noise, e) == ARG, i
-    assert _rc(noise_null, _shape(0, (2, 3, 8))) == ARG
+    for i, e in enumerate([shape(0, (2, 3, 8)), shape(0, (2, 3, 9)), shape(1, (3,), I), shape(2, (2, 4), "uint8"), shape(3, (2, 3, 4, 2), F64),
+                           shape(4, (2, 3, 5), F64), shape(5, (2, 3, 5), F64), shape(6, (2, 4), I), shape(7, (2, 3, 3), F64), shape(8, (2, 4, 7)),
+                           both(shape(3, (2, 3, 0, 3), F64), shape(4, (2, 3, 0), F64), shape(5, (2, 3, 0), F64))]):     # T < 1
+        assert rc(noise, e) == ARG, i
+    assert rc(noise_null, shape(0, (2, 3, 8))) == ARG
 
     def grow_noise(G, Tn, B=2):
-        return _both(_shape(0, (B, G, 7)), _shape(1, (B,), I), _shape(2, (B, G), "uint8"), _shape(3, (B, G, Tn, 3), F64), _shape(4, (B, G, Tn), F64),
-                     _shape(5, (B, G, Tn), F64), _shape(6, (B, G), I), _shape(7, (B, G, 4), F64), _shape(8, (B, G, 7)))
+        return both(shape(0, (B, G, 7)), shape(1, (B,), I), shape(2, (B, G), "uint8"), shape(3, (B, G, Tn, 3), F64), shape(4, (B, G, Tn), F64),
+                     shape(5, (B, G, Tn), F64), shape(6, (B, G), I), shape(7, (B, G, 4), F64), shape(8, (B, G, 7)))
 
-    assert _rc(noise, grow_noise(257, 4)) == SIZE and _rc(noise, grow_noise(3, 129)) == SIZE and _rc(noise, grow_noise(1, 1, 4097)) == SIZE
+    assert rc(noise, grow_noise(257, 4)) == SIZE and rc(noise, grow_noise(3, 129)) == SIZE and rc(noise, grow_noise(1, 1, 4097)) == SIZE
 
-    for i, e in enumerate([_both(_shape(0, (300, 5)), _shape(10, (300, 5))), _shape(0, (300, 3)), _shape(1, (4,), I), _shape(2, (2, 3, 8)),
-                           _shape(3, (3,), I), _shape(4, (2, 2), "uint8"), _shape(5, (2, 3, 3), F64), _shape(6, (2, 2, 8)), _shape(6, (3, 2, 7)),
-                           _shape(7, (3,), I), _shape(8, (1,), I), _shape(9, (2, 5), F64), _shape(9, (3, 6), F64), _shape(10, (299, 4)),
-                           _shape(11, (2,), I), _shape(12, (301,), I)]):
-        assert _rc(points, e) == ARG, i
+    for i, e in enumerate([both(shape(0, (300, 5)), shape(10, (300, 5))), shape(0, (300, 3)), shape(1, (4,), I), shape(2, (2, 3, 8)),
+                           shape(3, (3,), I), shape(4, (2, 2), "uint8"), shape(5, (2, 3, 3), F64), shape(6, (2, 2, 8)), shape(6, (3, 2, 7)),
+                           shape(7, (3,), I), shape(8, (1,), I), shape(9, (2, 5), F64), shape(9, (3, 6), F64), shape(10, (299, 4)),
+                           shape(11, (2,), I), shape(12, (301,), I)]):
+        assert rc(points, e) == ARG, i
 
     def part(c):                                          # remove operands given in part
         t = c.operands[7]
         c.operands[7] = T(t.shape, t.dtype, "opt", null=True)
-    assert _rc(points, part) == ARG
+    assert rc(points, part) == ARG
     big = 1 << 30
     call = edited(points, lambda c: None)                             # (the shapes alone say 2^30 points: the host blocks stay small, nothing is touched)
     call.shapes[0], call.shapes[10], call.shapes[12] = [big, 4], [big, 4], [big]
-    assert call.run(_lib_handle()) == SIZE
-    assert _rc(points, _shape(6, (2, 257, 7))) == SIZE
-    assert _rc(points_ws, _shape(13, (900,), "uint8")) == SIZE                                  # R = 0 here: 908 bytes are used
+    assert call.run(lib_handle()) == SIZE
+    assert rc(points, shape(6, (2, 257, 7))) == SIZE
+    assert rc(points_ws, shape(13, (900,), "uint8")) == SIZE                                  # R = 0 here: 908 bytes are used
 
     nan, inf = float("nan"), float("inf")
-    for i, e in enumerate([_shape(0, (2, 3, 8)), _shape(1, (3,), I), _shape(2, (2, 4), "uint8"), _shape(3, (2, 4), I), _shape(4, (2, 7), F64),
-                           _shape(5, (2, 4, 7)), _shape(6, (3, 3), I), _shape(7, (3,), I)]):
-        assert _rc(boxes, e) == ARG, i
+    for i, e in enumerate([shape(0, (2, 3, 8)), shape(1, (3,), I), shape(2, (2, 4), "uint8"), shape(3, (2, 4), I), shape(4, (2, 7), F64),
+                           shape(5, (2, 4, 7)), shape(6, (3, 3), I), shape(7, (3,), I)]):
+        assert rc(boxes, e) == ARG, i
     for k, v in ((0, nan), (1, inf), (2, -inf), (3, nan)):
-        def attr(c, k=k, v=v):
-            c.extra.bv_range[k] = v
-        assert _rc(boxes, attr) == ARG, (k, v)
-    grow = _both(_shape(0, (2, 257, 7)), _shape(2, (2, 257), "uint8"), _shape(3, (2, 257), I), _shape(5, (2, 257, 7)), _shape(6, (2, 257), I))
-    assert _rc(boxes, grow) == SIZE
+        assert rc(boxes, item("bv_range", k, v)) == ARG, (k, v)
+    grow = both(shape(0, (2, 257, 7)), shape(2, (2, 257), "uint8"), shape(3, (2, 257), I), shape(5, (2, 257, 7)), shape(6, (2, 257), I))
+    assert rc(boxes, grow) == SIZE
 
 
 def test_fixture_carries_what_the_cases_promise():

@@ -4,7 +4,6 @@ config, the reader's weight import / export, the argument checks of the two entr
 of csrc/pillars.hip."""
 import ctypes as C
 import os
-import re
 import shutil
 import sys
 
@@ -14,8 +13,9 @@ import torch
 
 from minddet_amd import _lib, det_ops, graphs, weights
 from tests import pillar_contract as pc
+from tests import abi_header as ah
 from tests.abi_cases_points import CASES
-from tests.test_abi_checks_cpu import Call, mutations
+from tests.abi_derive import attr, item, rc, refuse_single_defects, shape
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden", "pillar_vectors.npz")
@@ -239,11 +239,10 @@ def test_reader_weights_round_trip(naming):
 
 # -------------------------------------------------------------------------------------------------------------------- ABI and ISA
 def test_points_header_declares_the_two_symbols_and_the_main_header_none_of_them():
-    pts = open(os.path.join(ROOT, "include", "minddet_hip_points.h")).read()
-    main = open(os.path.join(ROOT, "include", "minddet_hip.h")).read()
-    pat = r"^\s*int\s+(\w+)\s*\(MD_AOT_ARGS\)\s*;"
-    assert re.findall(pat, pts, flags=re.M) == ["md_voxelize", "md_pillar_encode"] and '#include "minddet_hip.h"' in pts
-    assert not {"md_voxelize", "md_pillar_encode"} & set(re.findall(pat, main, flags=re.M))
+    pts = ah.header("minddet_hip_points.h")
+    main = ah.header("minddet_hip.h")
+    assert ah.aot_symbols(pts) == ["md_voxelize", "md_pillar_encode"] and '#include "minddet_hip.h"' in pts
+    assert not {"md_voxelize", "md_pillar_encode"} & set(ah.aot_symbols(main))
     assert {c.sym for c in CASES} == {"md_voxelize", "md_pillar_encode"} and len({c.id for c in CASES}) == len(CASES)
     assert C.sizeof(det_ops._VoxelizeAttrs) == 4 * 11 and C.sizeof(det_ops._PillarEncodeAttrs) == 4 * 6
     assert "minddet_hip_points.h" in open(os.path.join(ROOT, "minddet_amd", "csrc", "Makefile")).read()
@@ -251,24 +250,7 @@ def test_points_header_declares_the_two_symbols_and_the_main_header_none_of_them
 
 @pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])
 def test_single_defect_calls_are_refused_without_a_device(case):
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    lib = C.CDLL(_lib.LIB_PATH)
-    muts = mutations(case)
-    kinds = {k for k, _, _, _ in muts}
-    assert {"nparam", "params_null", "ndims_null", "shapes_null", "extra_null", "shape_null", "ptr_null", "dtype", "rank-1", "rank+1"} <= kinds
-    bad = [(kind, i, rc, want) for kind, i, call, want in muts for rc in [call.run(lib)] if rc != want]
-    assert not bad, f"{case.id}: (defect, operand, rc, expected) {bad}"
-
-
-def _rc(case, edit):
-    """the valid row with its attribute struct (a copy) or one shape edited: refused before any device call"""
-    import copy
-    c = copy.copy(case)
-    c.extra = type(case.extra).from_buffer_copy(case.extra)
-    c.operands = list(case.operands)
-    edit(c)
-    return Call(c).run(C.CDLL(_lib.LIB_PATH))
+    refuse_single_defects("abi_cases_points", case)
 
 
 def test_attribute_and_shape_checks():
@@ -278,36 +260,23 @@ def test_attribute_and_shape_checks():
     vox, two, one = CASES
     ARG, SIZE = 2, 4
 
-    def attr(name, value, idx=None):
-        def edit(c):
-            if idx is None:
-                setattr(c.extra, name, value)
-            else:
-                getattr(c.extra, name)[idx] = value
-        return edit
-
-    def shape(i, shp, dtype=F):
-        def edit(c):
-            c.operands[i] = T(shp, dtype)
-        return edit
-
-    for e in (attr("max_points", 5), attr("max_voxels", 7), attr("voxel_size", 0.0, 0), attr("voxel_size", -0.2, 1),
-              attr("voxel_size", float("nan"), 2), attr("range", 2.0, 0), attr("range", float("inf"), 5), shape(0, (16, 3)), shape(0, (16, 6)),
+    for e in (attr("max_points", 5), attr("max_voxels", 7), item("voxel_size", 0, 0.0), item("voxel_size", 1, -0.2),
+              item("voxel_size", 2, float("nan")), item("range", 0, 2.0), item("range", 5, float("inf")), shape(0, (16, 3)), shape(0, (16, 6)),
               shape(2, (3, 8, 4, 5)), shape(2, (2, 8, 4, 4)), shape(3, (2, 8, 3), "int32"), shape(4, (2, 9), "int32"), shape(5, (3,), "int32")):
-        assert _rc(vox, e) == ARG
-    assert _rc(vox, attr("voxel_size", 1e-7, 0)) in (ARG, SIZE)                 # 32 million cells per row
+        assert rc(vox, e) == ARG
+    assert rc(vox, item("voxel_size", 0, 1e-7)) in (ARG, SIZE)                 # 32 million cells per row
     for case in (two, one):
         for e in (attr("with_distance", 1), attr("virtual_points", 1), attr("vx", float("nan")), shape(0, (2, 8, 4, 6)), shape(1, (2, 7), "int32"),
                   shape(2, (2, 8, 3), "int32"), shape(3, (1,), "int32"), shape(4, (48, 10)), shape(4, (case.operands[4].shape[0], 9)),
                   shape(5, (16,)), shape(8, (2, 16, 16, 32), "bfloat16"), shape(8, (3, 16, 16, 64), "bfloat16")):
-            assert _rc(case, e) == ARG, case.id
-        assert _rc(case, shape(0, (2, 8, 65, 5))) == SIZE                       # more rows than the kernel's slab
-    assert _rc(two, shape(6, (64, 32))) == ARG and _rc(two, shape(7, (32,))) == ARG
-    assert _rc(two, shape(4, (64, 10))) == ARG and _rc(one, shape(4, (32, 10))) == ARG      # the first layer's width follows the layer count
+            assert rc(case, e) == ARG, case.id
+        assert rc(case, shape(0, (2, 8, 65, 5))) == SIZE                       # more rows than the kernel's slab
+    assert rc(two, shape(6, (64, 32))) == ARG and rc(two, shape(7, (32,))) == ARG
+    assert rc(two, shape(4, (64, 10))) == ARG and rc(one, shape(4, (32, 10))) == ARG      # the first layer's width follows the layer count
 
     def only_w2(c):
         c.operands[7] = T((64,), F, "opt", null=True)
-    assert _rc(two, only_w2) == ARG
+    assert rc(two, only_w2) == ARG
 
 
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc") or shutil.which("c++filt") is None, reason="needs hipcc + c++filt")

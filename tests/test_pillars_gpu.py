@@ -12,7 +12,6 @@ import torch
 
 from minddet_amd import _lib, det_ops, graphs
 from tests import pillar_contract as pc
-from tests.abi_cases_points import CASES
 from tests.test_pillars_cpu import CFG, GOLD, OUT, fixture_case, random_pfn, random_voxels
 
 pytestmark = pytest.mark.gpu
@@ -225,12 +224,3 @@ def test_detector_from_points_equals_the_detector_on_its_pseudo_image():
         assert ((d[b, :c[b], 10] >= 0) & (d[b, :c[b], 10] < sum(m.bbox_head.num_classes))).all()
     with pytest.raises(ValueError):
         m.forward(points[:, :4].contiguous(), offsets)
-
-
-@pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])
-def test_valid_rows_are_accepted(case):
-    """the rows tests/test_pillars_cpu.py derives its single-defect calls from are valid calls: rc 0 with zero-filled tensors"""
-    dt = {"float32": torch.float32, "bfloat16": torch.bfloat16, "int32": torch.int32, "uint8": torch.uint8}
-    tensors = [None if t.null else torch.zeros(t.shape, dtype=dt[t.dtype], device=DEV) for t in case.operands]
-    assert _lib.call(case.sym, tensors, extra=case.extra) == 0
-    torch.cuda.synchronize()

@@ -1,7 +1,6 @@
 """CPU: the anchor-based PointPillars without a GPU -- the ABI of include/minddet_hip_pp.h (header, symbols, struct size, argument
 checks before any device call), the three configs, the documented refusals, the block1 eps quirk, the float64 contract of
 tests/pp_contract.py against the reference-generated vectors and its either-outcome cap, and the weight round trip."""
-import copy
 import ctypes as C
 import os
 import re
@@ -12,9 +11,10 @@ import torch
 
 from minddet_amd import _lib, det_ops, graphs, weights
 from tests import pp_contract as ppc
-from tests.abi_cases import F, I, T
+from tests import abi_header as ah
+from tests.abi_cases import I
 from tests.abi_cases_pp import CASES
-from tests.test_abi_checks_cpu import Call, mutations
+from tests.abi_derive import attr, rc, refuse_single_defects, shape
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CFG = {n: os.path.join(ROOT, "configs", "pointpillars", f"pointpillars_{n}.py") for n in ("car_xyres16", "ped_cycle_xyres16", "tiny")}
@@ -29,16 +29,15 @@ def _detector(name, seed=7, **over):
 
 # ------------------------------------------------------------------------------------------------------------------------------ ABI
 def test_pp_header_declares_the_two_symbols_and_the_main_header_neither():
-    pp = open(os.path.join(ROOT, "include", "minddet_hip_pp.h")).read()
-    main = open(os.path.join(ROOT, "include", "minddet_hip.h")).read()
-    pat = r"^\s*int\s+(\w+)\s*\(MD_AOT_ARGS\)\s*;"
-    assert re.findall(pat, pp, flags=re.M) == ["md_pp_scores", "md_pp_decode_selected"] and '#include "minddet_hip.h"' in pp
-    assert not {"md_pp_scores", "md_pp_decode_selected"} & set(re.findall(pat, main, flags=re.M))
+    pp = ah.header("minddet_hip_pp.h")
+    main = ah.header("minddet_hip.h")
+    assert ah.aot_symbols(pp) == ["md_pp_scores", "md_pp_decode_selected"] and '#include "minddet_hip.h"' in pp
+    assert not {"md_pp_scores", "md_pp_decode_selected"} & set(ah.aot_symbols(main))
     assert {c.sym for c in CASES} == {"md_pp_scores", "md_pp_decode_selected"} and len({c.id for c in CASES}) == len(CASES)
-    m = re.search(r"typedef struct md_pp_head_attrs \{(.*?)\} md_pp_head_attrs;", pp, flags=re.S)
-    n_i32 = len(re.findall(r"int32_t\s+\w+;", re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)))
+    fields = [re.fullmatch(r"int32_t\s+(\w+)", s).group(1) for s in ah.statements("md_pp_head_attrs", pp)]
+    n_i32 = len(fields)
     assert n_i32 == 7 and C.sizeof(det_ops._PPHeadAttrs) == 4 * n_i32 == C.sizeof(CASES[0].extra)
-    assert [f for f, _ in det_ops._PPHeadAttrs._fields_] == re.findall(r"int32_t\s+(\w+);", re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S))
+    assert [f for f, _ in det_ops._PPHeadAttrs._fields_] == fields
     assert "minddet_hip_pp.h" in open(os.path.join(ROOT, "minddet_amd", "csrc", "Makefile")).read()
     if not os.path.exists(_lib.LIB_PATH):
         _lib.build()
@@ -56,22 +55,7 @@ def test_decode_and_standup_arithmetic_is_shared_by_both_translation_units():
 
 @pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])
 def test_single_defect_calls_are_refused_without_a_device(case):
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    lib = C.CDLL(_lib.LIB_PATH)
-    muts = mutations(case)
-    kinds = {k for k, _, _, _ in muts}
-    assert {"nparam", "params_null", "ndims_null", "shapes_null", "extra_null", "shape_null", "ptr_null", "dtype", "rank-1", "rank+1"} <= kinds
-    bad = [(kind, i, rc, want) for kind, i, call, want in muts for rc in [call.run(lib)] if rc != want]
-    assert not bad, f"{case.id}: (defect, operand, rc, expected) {bad}"
-
-
-def _rc(case, edit):
-    c = copy.copy(case)
-    c.extra = type(case.extra).from_buffer_copy(case.extra)
-    c.operands = list(case.operands)
-    edit(c)
-    return Call(c).run(C.CDLL(_lib.LIB_PATH))
+    refuse_single_defects("abi_cases_pp", case)
 
 
 def test_semantic_refusals_return_2():
@@ -80,25 +64,17 @@ def test_semantic_refusals_return_2():
     sc, _, dec, dec9 = CASES
     ARG = 2
 
-    def attr(name, value):
-        return lambda c: setattr(c.extra, name, value)
-
-    def shape(i, shp, dtype=F):
-        def edit(c):
-            c.operands[i] = T(shp, dtype)
-        return edit
-
     for e in (attr("num_classes", 0), attr("num_classes", -1), attr("num_anchors", 0), attr("off_cls", -1), attr("off_cls", 21),
               attr("num_classes", 13), attr("score_mode", 1), shape(2, (1, 11)), shape(3, (1, 13), I), shape(2, (2, 12)),
               shape(1, (1, 11), "uint8")):
-        assert _rc(sc, e) == ARG
+        assert rc(sc, e) == ARG
     for case in (dec, dec9):
         for e in (attr("self_train", 0), attr("num_anchors", 0), attr("off_box", -1), attr("off_box", 11), attr("off_dir", 21),
                   attr("off_dir", -2), shape(1, (11, 7)), shape(1, (13, 7)), shape(1, (12, 6)), shape(2, (1, 4), I), shape(2, (2, 5), I),
                   shape(3, (2,), I), shape(4, (1, 6)), shape(5, (1, 11), I), shape(6, (1, 4, 9)), shape(6, (1, 5, 8)), shape(7, (1, 6, 4)),
                   shape(8, (1, 4), I)):
-            assert _rc(case, e) == ARG, case.id
-    assert _rc(dec, shape(9, (1, 4, 7))) == ARG and _rc(dec, shape(9, (1, 5, 9))) == ARG
+            assert rc(case, e) == ARG, case.id
+    assert rc(dec, shape(9, (1, 4, 7))) == ARG and rc(dec, shape(9, (1, 5, 9))) == ARG
 
 
 # -------------------------------------------------------------------------------------------------------------------------- the model

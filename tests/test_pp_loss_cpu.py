@@ -1,5 +1,5 @@
-"""CPU: the KITTI PointPillars training loss without a GPU -- the ABI of include/minddet_hip_pploss.h (the two functions exported, the
-single-defect calls and the semantic refusals answered before any device call, the ctypes mirrors laid out as the header says), the
+"""CPU: the KITTI PointPillars training loss without a GPU -- the ABI of include/minddet_hip_pploss.h (the two functions exported,
+the semantic refusals answered before any device call, the ctypes mirrors laid out as the header says), the
 contract tests/pp_loss_contract.py against a literal torch-float64 transcription of the reference's losses.py and
 pointpillars.py:19-127, 817-872 under autograd on the reference's own assigner outputs (tests/golden/target_vectors.npz), and the
 train configs.
@@ -7,61 +7,49 @@ train configs.
 Criteria of the comparison, fixed beforehand: losses to 1e-12 relative; the structural zeros of the gradient exact on both sides; every
 other gradient element, rounded to fp32, differs in at most 1 in 10^4, by 1 ulp.  Measured: 0 differing of the 4 710 / 13 662 / 163
 cls elements and 0 of the box / dir elements, relative loss differences <= 4e-16."""
-import copy
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F_
 
-from minddet_amd import _lib, det_ops
+from minddet_amd import det_ops
 from tests import pp_loss_contract as pl
-from tests.abi_cases import B16, F, I, T, U8
+from tests import abi_header as ah
+from tests.abi_cases import B16, I, U8
 from tests.abi_cases_pploss import CASES, PPLoss
-from tests.test_abi_checks_cpu import Call, mutations
-from tests.test_cp_loss_cpu import _struct_of
+from tests.abi_derive import attr, both, item, lib_handle, rc, refuse_single_defects, shape
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = open(os.path.join(ROOT, "include", "minddet_hip_pploss.h")).read()
-HDR_PP = open(os.path.join(ROOT, "include", "minddet_hip_pp.h")).read()
+HDR = ah.header("minddet_hip_pploss.h")
+HDR_PP = ah.header("minddet_hip_pp.h")
 G = np.load(os.path.join(ROOT, "tests", "golden", "target_vectors.npz"))
 # fixture -> (H, W, A, K): N = H W A
 FIXTURE_SHAPES = dict(car=(54, 62, 2, 1), pedcyc=(40, 60, 4, 2), nogt=(10, 12, 2, 1))
 
 
-def _lib_handle():
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    return C.CDLL(_lib.LIB_PATH)
-
-
 def test_header_declares_the_two_symbols_and_the_library_exports_them():
-    pat = r"^\s*int\s+(\w+)\s*\(MD_AOT_ARGS\)\s*;"     # the expression of _lib.exported_symbols
-    assert re.findall(pat, HDR, flags=re.M) == ["md_pp_loss", "md_pp_loss_grad"] and '#include "minddet_hip_pp.h"' in HDR
+    assert ah.aot_symbols(HDR) == ["md_pp_loss", "md_pp_loss_grad"] and '#include "minddet_hip_pp.h"' in HDR
     assert "pointpillars.py:817-872" in HDR and "losses.py:40-191" in HDR
     assert "minddet_hip_pploss.h" in open(os.path.join(ROOT, "minddet_amd", "csrc", "Makefile")).read()
     assert {c.sym for c in CASES} == {"md_pp_loss", "md_pp_loss_grad"} and len({c.id for c in CASES}) == len(CASES)
-    lib = _lib_handle()
+    lib = lib_handle()
     for sym in ("md_pp_loss", "md_pp_loss_grad"):
         assert getattr(lib, sym)(0, None, None, None, None, None, None) == 1             # wrong parameter count, before anything else
 
 
 def test_ctypes_mirrors_have_the_headers_layout():
-    head = _struct_of(HDR_PP, "md_pp_head_attrs", {})
-    want = _struct_of(HDR, "md_pp_loss_attrs", {"md_pp_head_attrs": head})
+    head = ah.struct_of("md_pp_head_attrs", HDR_PP)
+    want = ah.struct_of("md_pp_loss_attrs", HDR, known={"md_pp_head_attrs": head})
     assert C.sizeof(head) == 7 * 4 and C.sizeof(want) == 28 + 12 + 28 + 12 + 8
 
-    def layout(s):
-        return [(n, getattr(s, n).offset, getattr(s, n).size) for n, _ in s._fields_]
-
     for got in (det_ops._PPLossAttrs, PPLoss):
-        assert C.sizeof(got) == C.sizeof(want) and layout(got) == layout(want), got
+        assert ah.same_layout(got, want), got
     for got in (det_ops._PPHeadAttrs, dict(PPLoss._fields_)["head"]):
-        assert layout(got) == layout(head), got
-    defines = {k: int(v) for k, v in re.findall(r"^#define (\w+) (\d+)\b", HDR, flags=re.M)}
+        assert ah.layout(got) == ah.layout(head), got
+    defines = ah.defines(HDR)
     assert defines["MD_PP_LOSS_STRIP"] == 64 and defines["MD_PP_LOSS_COUNT_CHUNK"] == 4096
     # (each decides the library's answer: 64 cells are one strip of 40 bytes, 4096 labels one count of 4)
     assert [det_ops.pp_loss_workspace_bytes(1, 1, w, 1) for w in (64, 65)] == [40 + 4, 80 + 4]
@@ -71,20 +59,7 @@ def test_ctypes_mirrors_have_the_headers_layout():
 
 @pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])
 def test_single_defect_calls_are_refused_without_a_device(case):
-    lib = _lib_handle()
-    muts = mutations(case)
-    kinds = {k for k, _, _, _ in muts}
-    assert {"nparam", "params_null", "ndims_null", "shapes_null", "extra_null", "shape_null", "ptr_null", "dtype", "rank-1", "rank+1"} <= kinds
-    bad = [(kind, i, rc, want) for kind, i, call, want in muts for rc in [call.run(lib)] if rc != want]
-    assert not bad, f"{case.id}: (defect, operand, rc, expected) {bad}"
-
-
-def _rc(case, edit):
-    c = copy.copy(case)
-    c.extra = type(case.extra).from_buffer_copy(case.extra)
-    c.operands = list(case.operands)
-    edit(c)
-    return Call(c).run(_lib_handle())
+    refuse_single_defects("abi_cases_pploss", case)
 
 
 @pytest.mark.parametrize("case", [CASES[0], CASES[3]], ids=[CASES[0].id, CASES[3].id])
@@ -92,27 +67,8 @@ def test_semantic_refusals_return_the_documented_codes(case):
     ARG, SIZE = 2, 4
     grad = case.sym == "md_pp_loss_grad"
 
-    def attr(name, value):
-        return lambda c: setattr(c.extra, name, value)
-
     def head(name, value):
         return lambda c: setattr(c.extra.head, name, value)
-
-    def cw(j, value):
-        def edit(c):
-            c.extra.code_weights[j] = value
-        return edit
-
-    def shape(i, shp, dtype=F):
-        def edit(c):
-            c.operands[i] = T(shp, dtype)
-        return edit
-
-    def both(*edits):
-        def edit(c):
-            for e in edits:
-                e(c)
-        return edit
 
     nan, inf = float("nan"), float("inf")
     edits = [
@@ -125,7 +81,7 @@ def test_semantic_refusals_return_the_documented_codes(case):
         attr("pos_cls_weight", -1.0), attr("neg_cls_weight", -1.0),
         attr("alpha", nan), attr("alpha", -inf), attr("gamma", inf), attr("gamma", nan), attr("sigma", inf), attr("sigma", nan),
         attr("cls_weight", nan), attr("loc_weight", inf), attr("dir_weight", -inf), attr("pos_cls_weight", inf), attr("neg_cls_weight", nan),
-        cw(0, nan), cw(6, -inf),
+        item("code_weights", 0, nan), item("code_weights", 6, -inf),
         shape(0, (0, 8, 12, 24), B16),                                                        # an empty batch
         shape(0, (1, 0, 12, 24), B16), shape(0, (1, 8, 0, 24), B16),
         shape(0, (2, 8, 12, 24), B16), shape(0, (1, 8, 11, 24), B16), shape(1, (1, 191), I), shape(1, (2, 192), I), shape(2, (1, 192, 6)),
@@ -135,14 +91,14 @@ def test_semantic_refusals_return_the_documented_codes(case):
     if grad:
         edits += [shape(7, (1, 8, 12, 16)), shape(7, (1, 12, 8, 24)), shape(7, (2, 8, 12, 24))]
     for i, e in enumerate(edits):
-        assert _rc(case, e) == ARG, i
+        assert rc(case, e) == ARG, i
     wide = both(shape(0, (1, 8, 12, 136), B16), *([shape(7, (1, 8, 12, 136))] if grad else []))   # C above the LDS bound
-    assert _rc(case, wide) == SIZE
+    assert rc(case, wide) == SIZE
     many = both(shape(0, (65536, 1, 1, 24), B16), shape(1, (65536, 2), I), shape(2, (65536, 2, 7)), shape(3, (2, 7)), shape(5, (65536,)),
                 *([shape(7, (65536, 1, 1, 24))] if grad else []))                                 # B above the grid bound
-    assert _rc(case, many) == SIZE
+    assert rc(case, many) == SIZE
     if "[workspace]" in case.id:
-        assert _rc(case, shape(len(case.operands) - 1, (83,), U8)) == SIZE                    # one byte short of 40 B strips + 4 B chunks
+        assert rc(case, shape(len(case.operands) - 1, (83,), U8)) == SIZE                    # one byte short of 40 B strips + 4 B chunks
 
 
 # ---------------------------------------------------------------------------------------------------- the reference, transcribed

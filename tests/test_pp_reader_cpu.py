@@ -2,7 +2,6 @@
 argument checks before any device call), the interval contract of tests/pp_reader_contract.py against an independent per-voxel loop
 and against six devices the header excludes, the three `_points` configs, the unchanged old configs and refusals, and the weight
 round trip."""
-import copy
 import ctypes as C
 import os
 import re
@@ -13,10 +12,11 @@ import torch
 
 from minddet_amd import _lib, det_ops, graphs, weights
 from tests import pp_reader_contract as prc
-from tests.abi_cases import F, I, T
+from tests import abi_header as ah
+from tests.abi_cases import I
 from tests.abi_cases_ppreader import CASES
+from tests.abi_derive import attr, rc, refuse_single_defects, shape
 from tests.pillar_contract import bf16_round
-from tests.test_abi_checks_cpu import Call, mutations
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("car_xyres16", "ped_cycle_xyres16", "tiny")
@@ -36,16 +36,13 @@ def _detector(name, seed=7, **over):
 
 # ------------------------------------------------------------------------------------------------------------------------------ ABI
 def test_ppreader_header_declares_the_two_symbols_and_no_other_header_does():
-    inc = lambda n: open(os.path.join(ROOT, "include", n)).read()
-    hdr = inc("minddet_hip_ppreader.h")
-    pat = r"^\s*int\s+(\w+)\s*\(MD_AOT_ARGS\)\s*;"
-    assert re.findall(pat, hdr, flags=re.M) == SYMS and '#include "minddet_hip.h"' in hdr
+    hdr = ah.header("minddet_hip_ppreader.h")
+    assert ah.aot_symbols(hdr) == SYMS and '#include "minddet_hip.h"' in hdr
     for other in ("minddet_hip.h", "minddet_hip_points.h", "minddet_hip_pp.h", "minddet_hip_chain.h"):
-        assert not set(SYMS) & set(re.findall(pat, inc(other), flags=re.M)), other
+        assert not set(SYMS) & set(ah.aot_symbols(ah.header(other))), other
     assert {c.sym for c in CASES} == set(SYMS) and len({c.id for c in CASES}) == len(CASES)
-    m = re.search(r"typedef struct md_pp_pillar_encode_attrs \{(.*?)\} md_pp_pillar_encode_attrs;", hdr, flags=re.S)
-    body = re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)
-    names = [n.strip() for decl in re.findall(r"(?:float|int32_t)\s+([^;]+);", body) for n in decl.split(",")]
+    body = ah.statements("md_pp_pillar_encode_attrs", hdr)
+    names = [n.strip() for s in body for n in re.fullmatch(r"(?:float|int32_t)\s+(.+)", s).group(1).split(",")]
     assert names == [f for f, _ in det_ops._PPPillarEncodeAttrs._fields_]
     assert C.sizeof(det_ops._PPPillarEncodeAttrs) == 4 * 8 == C.sizeof(CASES[0].extra)
     assert C.sizeof(det_ops._AnchorMaskAttrs) == 4 * 7 == C.sizeof(CASES[2].extra)
@@ -59,22 +56,7 @@ def test_ppreader_header_declares_the_two_symbols_and_no_other_header_does():
 
 @pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])
 def test_single_defect_calls_are_refused_without_a_device(case):
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    lib = C.CDLL(_lib.LIB_PATH)
-    muts = mutations(case)
-    kinds = {k for k, _, _, _ in muts}
-    assert {"nparam", "params_null", "ndims_null", "shapes_null", "extra_null", "shape_null", "ptr_null", "dtype", "rank-1", "rank+1"} <= kinds
-    bad = [(kind, i, rc, want) for kind, i, call, want in muts for rc in [call.run(lib)] if rc != want]
-    assert not bad, f"{case.id}: (defect, operand, rc, expected) {bad}"
-
-
-def _rc(case, edit):
-    c = copy.copy(case)
-    c.extra = type(case.extra).from_buffer_copy(case.extra)
-    c.operands = list(case.operands)
-    edit(c)
-    return Call(c).run(C.CDLL(_lib.LIB_PATH))
+    refuse_single_defects("abi_cases_ppreader", case)
 
 
 def test_documented_refusals():
@@ -83,29 +65,21 @@ def test_documented_refusals():
     k10, k11, area, plain = CASES
     ARG, SIZE = 2, 4
 
-    def attr(name, value):
-        return lambda c: setattr(c.extra, name, value)
-
-    def shape(i, shp, dtype=F):
-        def edit(c):
-            c.operands[i] = T(shp, dtype)
-        return edit
-
     for case in (k10, k11):
         for e in (attr("reserved0", 1), attr("with_distance", 1 - case.extra.with_distance), attr("with_distance", 2), attr("vx", 0.0),
                   attr("vy", -0.16), attr("vz", float("nan")), attr("vx", float("inf")), attr("x_offset", float("nan")),
                   attr("z_offset", float("inf")), shape(0, (2, 8, 6, 5)), shape(0, (2, 8, 6, 3)), shape(0, (3, 8, 6, 4)), shape(1, (2, 7), I),
                   shape(2, (2, 8, 3), I), shape(3, (1,), I), shape(4, (64, 9)), shape(4, (64, 12)), shape(4, (32, 10 + case.extra.with_distance)),
                   shape(5, (32,)), shape(6, (63,)), shape(7, (2, 16, 16, 32), "bfloat16"), shape(7, (3, 16, 16, 64), "bfloat16")):
-            assert _rc(case, e) == ARG, case.id
-        assert _rc(case, shape(0, (2, 8, 33, 4))) == SIZE                          # more rows than the 32 of the MFMA tile
-        assert _rc(case, shape(7, (2, 70000, 16, 64), "bfloat16")) == SIZE
+            assert rc(case, e) == ARG, case.id
+        assert rc(case, shape(0, (2, 8, 33, 4))) == SIZE                          # more rows than the 32 of the MFMA tile
+        assert rc(case, shape(7, (2, 70000, 16, 64), "bfloat16")) == SIZE
     for case in (area, plain):
         for e in (shape(0, (2, 8, 3), I), shape(0, (3, 8, 4), I), shape(1, (3,), I), shape(2, (5, 5)), shape(3, (2, 6), "uint8"),
                   shape(3, (1, 5), "uint8")):
-            assert _rc(case, e) == ARG, case.id
-        assert _rc(case, attr("grid_x", 0)) == SIZE and _rc(case, attr("grid_y", -3)) == SIZE and _rc(case, attr("grid_x", 1 << 30)) == SIZE
-    assert _rc(area, shape(4, (2, 6))) == ARG and _rc(area, shape(4, (3, 5))) == ARG
+            assert rc(case, e) == ARG, case.id
+        assert rc(case, attr("grid_x", 0)) == SIZE and rc(case, attr("grid_y", -3)) == SIZE and rc(case, attr("grid_x", 1 << 30)) == SIZE
+    assert rc(area, shape(4, (2, 6))) == ARG and rc(area, shape(4, (3, 5))) == ARG
 
 
 # ----------------------------------------------------------------------------------------------------------------------- the contract

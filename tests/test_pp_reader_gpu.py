@@ -10,7 +10,6 @@ import torch
 
 from minddet_amd import _lib, det_ops, graphs
 from tests import pp_reader_contract as prc
-from tests.abi_cases_ppreader import CASES
 from tests.test_pillars_gpu import Guarded
 from tests.test_pp_reader_cpu import CAP, CFG, _detector
 
@@ -61,16 +60,6 @@ def check_encode(bits, lo, hi, live, coors, what):
     empty[cb[b, v], cy[b, v], cx[b, v]] = False
     assert not bits[empty].any(), f"{what}: a cell without a pillar is not zero"
     return either
-
-
-# ------------------------------------------------------------------------------------------------------------------------------ ABI
-@pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])
-def test_valid_rows_are_accepted(case):
-    """the rows tests/test_pp_reader_cpu.py derives its single-defect calls from are valid calls: rc 0 with zero-filled tensors"""
-    dt = {"float32": torch.float32, "bfloat16": torch.bfloat16, "int32": torch.int32, "uint8": torch.uint8}
-    tensors = [None if t.null else torch.zeros(t.shape, dtype=dt[t.dtype], device=DEV) for t in case.operands]
-    assert _lib.call(case.sym, tensors, extra=case.extra) == 0
-    torch.cuda.synchronize()
 
 
 # ------------------------------------------------------------------------------------------------------------------- pillar encoder

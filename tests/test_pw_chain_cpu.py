@@ -1,69 +1,43 @@
 """CPU: the ABI of include/minddet_hip_chain.h without a GPU -- header, symbol, Makefile, the argument checks of md_pw_chain before any
-device call (single-defect calls through host pointers, the machinery of tests/test_abi_checks_cpu.py), its documented refusals, and the
-packs graphs.ResNet makes for it."""
-import copy
+device call (the single-defect calls and its documented refusals, made with the kit of tests/abi_derive.py), and the packs
+graphs.ResNet makes for it."""
 import ctypes as C
 import os
-import re
 
 import pytest
 
-from minddet_amd import _lib, graphs, nn_ops
-from tests.abi_cases import B16, T
+from minddet_amd import graphs, nn_ops
+from tests import abi_header as ah
 from tests.abi_cases_chain import CASES
-from tests.test_abi_checks_cpu import ITEM, Call, mutations
+from tests.abi_derive import ITEM, Call, lib_handle, rc, refuse_single_defects, shape
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ARG = 2
 
 
-def _lib_c():
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    return C.CDLL(_lib.LIB_PATH)
-
-
 def test_chain_header_declares_the_symbol_and_the_main_header_does_not():
-    ch = open(os.path.join(ROOT, "include", "minddet_hip_chain.h")).read()
-    main = open(os.path.join(ROOT, "include", "minddet_hip.h")).read()
-    pat = r"^\s*int\s+(\w+)\s*\(MD_AOT_ARGS\)\s*;"
-    assert re.findall(pat, ch, flags=re.M) == ["md_pw_chain"] and '#include "minddet_hip.h"' in ch
-    assert "md_pw_chain" not in re.findall(pat, main, flags=re.M)
+    ch = ah.header("minddet_hip_chain.h")
+    main = ah.header("minddet_hip.h")
+    assert ah.aot_symbols(ch) == ["md_pw_chain"] and '#include "minddet_hip.h"' in ch
+    assert "md_pw_chain" not in ah.aot_symbols(main)
     assert {c.sym for c in CASES} == {"md_pw_chain"}
     assert "minddet_hip_chain.h" in open(os.path.join(ROOT, "minddet_amd", "csrc", "Makefile")).read()
-    assert hasattr(_lib_c(), "md_pw_chain")
+    assert hasattr(lib_handle(), "md_pw_chain")
 
 
 @pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])
 def test_single_defect_calls_are_refused_without_a_device(case):
-    lib = _lib_c()
-    muts = mutations(case)
-    kinds = {k for k, _, _, _ in muts}
-    assert {"nparam", "params_null", "ndims_null", "shapes_null", "shape_null", "ptr_null", "dtype", "rank-1", "rank+1"} <= kinds
-    bad = [(kind, i, rc, want) for kind, i, call, want in muts for rc in [call.run(lib)] if rc != want]
-    assert not bad, f"{case.id}: (defect, operand, rc, expected) {bad}"
-
-
-def _rc(edit):
-    c = copy.copy(CASES[0])
-    c.operands = list(c.operands)
-    edit(c)
-    return Call(c).run(_lib_c())
+    refuse_single_defects("abi_cases_chain", case)
 
 
 def test_other_channel_counts_and_shapes_return_2():
-    def shape(i, shp, dtype=B16):
-        def edit(c):
-            c.operands[i] = T(shp, dtype)
-        return edit
-
     for e in (shape(0, (1, 3, 5, 64)), shape(0, (1, 3, 5, 256)),        # t2: other mid channels, a channel slice of a wider tensor
               shape(1, (1, 3, 5, 256)), shape(1, (1, 3, 5, 1024)),      # res
               shape(6, (1, 3, 5, 1024)), shape(7, (1, 3, 5, 256)),      # outputs wider than the layer (a channel-concat buffer)
               shape(2, (512, 192)), shape(2, (256, 128)), shape(4, (128, 576)), shape(4, (64, 512)),
               shape(3, (256,), "float32"), shape(5, (64,), "float32"),
               shape(1, (1, 3, 4, 512)), shape(6, (2, 3, 5, 512)), shape(7, (1, 5, 3, 128))):
-        assert _rc(e) == ARG
+        assert rc(CASES[0], e) == ARG
 
 
 class _Aliased(Call):
@@ -93,7 +67,7 @@ class _Aliased(Call):
 
 
 def test_outputs_overlapping_an_input_or_each_other_return_2():
-    lib = _lib_c()
+    lib = lib_handle()
     case = CASES[0]
     res_bytes, t2_bytes = 15 * 512 * 2, 15 * 128 * 2
     # y in place on the residual, y one pixel into it, y ending inside it; t1 in place on t2; y on t2; t1 on res; t1 inside y

@@ -1,5 +1,5 @@
 """CPU: the training-step operators without a GPU -- the ABI of include/minddet_hip_train.h (the three operators and the workspace
-functions exported, the single-defect calls and the semantic refusals answered before any device call, the ctypes mirrors laid out as
+functions exported, the semantic refusals answered before any device call, the ctypes mirrors laid out as
 the header says), the contract tests/train_contract.py against a literal torch-float64 transcription of the reference's dense Adam
 update with its global-norm clip (custom_adam.py:188-222, 590-600), optim.OneCycle against the reference's vectors bit for bit, and the
 exclusion check that gives tests/test_conv_bwd_gpu.py its teeth: on the sixteen-bit inputs the exact result is an fp32 number and a dy
@@ -16,20 +16,14 @@ import torch
 
 from minddet_amd import _lib, det_ops, optim
 from tests import train_cases, train_contract as tc
-from tests.abi_cases import B16, F, T, U8
+from tests import abi_header as ah
+from tests.abi_cases import B16, U8
 from tests.abi_cases_train import CASES, F64, AdamAttrs, Conv1x1Bwd
-from tests.pcaug_cases import edited, mutations64
-from tests.test_cp_loss_cpu import _struct_of
+from tests.abi_derive import attr, both, lib_handle, raw, rc, refuse_single_defects, shape
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = open(os.path.join(ROOT, "include", "minddet_hip_train.h")).read()
+HDR = ah.header("minddet_hip_train.h")
 OPS = ["md_conv1x1_bwd_weight", "md_grad_sumsq", "md_adam_step"]
-
-
-def _lib_handle():
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    return C.CDLL(_lib.LIB_PATH)
 
 
 def _case(tag_part, sym):
@@ -37,15 +31,14 @@ def _case(tag_part, sym):
 
 
 def test_header_declares_the_operators_and_the_library_exports_them():
-    pat = r"^\s*int\s+(\w+)\s*\(MD_AOT_ARGS\)\s*;"     # the expression of _lib.exported_symbols
-    assert re.findall(pat, HDR, flags=re.M) == OPS and '#include "minddet_hip.h"' in HDR
+    assert ah.aot_symbols(HDR) == OPS and '#include "minddet_hip.h"' in HDR
     ws = re.findall(r"^extern int64_t (\w+_workspace_bytes)\((?:int64_t \w+(?:, )?)+\);", HDR, flags=re.M)
     assert ws == ["md_conv1x1_bwd_weight_workspace_bytes", "md_grad_sumsq_workspace_bytes"]
     for fn in ws:                                      # each directly under its operator
         assert re.search(rf"^int {fn[:-len('_workspace_bytes')]}\(MD_AOT_ARGS\);\nextern int64_t {fn}\(", HDR, flags=re.M), fn
     assert "custom_adam.py:590-668" in HDR and "minddet_hip_train.h" in open(os.path.join(ROOT, "minddet_amd", "csrc", "Makefile")).read()
     assert {c.sym for c in CASES} == set(OPS) and len({c.id for c in CASES}) == len(CASES)
-    lib = _lib_handle()
+    lib = lib_handle()
     for sym in OPS:
         assert getattr(lib, sym)(0, None, None, None, None, None, None) == 1             # wrong parameter count, before anything else
     for sym in ws:
@@ -56,7 +49,7 @@ def test_header_declares_the_operators_and_the_library_exports_them():
 
 
 def test_workspace_functions_follow_the_headers_formulas():
-    defines = {k: int(v) for k, v in re.findall(r"^#define (\w+) (\d+)\b", HDR, flags=re.M)}
+    defines = ah.defines(HDR)
     assert (defines["MD_CONV1X1_BWD_SLAB_MIN"], defines["MD_CONV1X1_BWD_MAX_SLABS"], defines["MD_CONV1X1_BWD_SUM_WAYS"]) == \
         (tc.SLAB_MIN, tc.MAX_SLABS, tc.SUM_WAYS)
     assert (defines["MD_CONV1X1_BWD_MAX_CIN"], defines["MD_CONV1X1_BWD_MAX_COUT"]) == (1024, 256)
@@ -70,7 +63,7 @@ def test_workspace_functions_follow_the_headers_formulas():
     assert "L(P) = S / 4 + 3 + ceil(n / 8) + 7" in HDR
     assert [det_ops.grad_sumsq_workspace_bytes(n) for n in (1, 4096, 4097, 4096 * 1024 + 1)] == [8, 8, 16, 8 * 1024]
     assert defines["MD_GRAD_SUMSQ_CHUNK"] == 4096 and defines["MD_GRAD_SUMSQ_MAX_BLOCKS"] == 1024
-    lib = _lib_handle()
+    lib = lib_handle()
     for fn, n in (("md_conv1x1_bwd_weight_workspace_bytes", 3), ("md_grad_sumsq_workspace_bytes", 1)):      # a negative extent answers -1
         f = getattr(lib, fn)
         f.restype, f.argtypes = C.c_int64, [C.c_int64] * n
@@ -82,74 +75,21 @@ def test_workspace_functions_follow_the_headers_formulas():
 
 
 def test_ctypes_mirrors_have_the_headers_layout():
-    conv = _struct_of(HDR, "md_conv1x1_bwd_attrs", {})
-    adam = _struct_of(HDR, "md_adam_attrs", {"double": C.c_double})
+    conv = ah.struct_of("md_conv1x1_bwd_attrs", HDR)
+    adam = ah.struct_of("md_adam_attrs", HDR)
     assert C.sizeof(conv) == 5 * 4 and C.sizeof(adam) == 10 * 8
 
-    def layout(s):
-        return [(n, getattr(s, n).offset, getattr(s, n).size) for n, _ in s._fields_]
-
     for got in (det_ops._Conv1x1BwdAttrs, Conv1x1Bwd):
-        assert C.sizeof(got) == C.sizeof(conv) and layout(got) == layout(conv), got
+        assert ah.same_layout(got, conv), got
     for got in (det_ops._AdamAttrs, AdamAttrs):
-        assert C.sizeof(got) == C.sizeof(adam) and layout(got) == layout(adam), got
+        assert ah.same_layout(got, adam), got
     at = det_ops.adam_attrs(1e-3, 0.9, 0.999, 0.81, 0.998, eps=1e-8, weight_decay=1e-4, max_norm=35.0, grad_scale=0.5)
     assert [getattr(at, n) for n, _ in at._fields_] == [1e-3, 0.9, 0.999, 0.81, 0.998, 1e-8, 1e-4, 35.0, 0.5, 0.0]
 
 
 @pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])
 def test_single_defect_calls_are_refused_without_a_device(case):
-    lib = _lib_handle()
-    muts = mutations64(case)
-    kinds = {k for k, _, _, _ in muts}
-    want = {"nparam", "params_null", "ndims_null", "shapes_null", "shape_null", "ptr_null", "dtype", "rank-1", "rank+1", "rank_without_dtypes"}
-    assert want | ({"extra_null"} if case.extra is not None else set()) <= kinds
-    bad = [(kind, i, rc, want) for kind, i, call, want in muts for rc in [call.run(lib)] if rc != want]
-    assert not bad, f"{case.id}: (defect, operand, rc, expected) {bad}"
-
-
-def _rc(case, edit):
-    return edited(case, edit).run(_lib_handle())
-
-
-def _raw(case, edit=None, same=()):
-    """the case's call after edit(copy) on dummy addresses 4 KiB apart (a refused call never dereferences a tensor pointer, so the
-    extents may describe more memory than exists); same = [(o, k)]: operand o gets the address of operand k -> rc"""
-    call = edited(case, edit or (lambda c: None))
-    ops, n = call.case.operands, call.n
-    arena = (C.c_char * (4096 * (n + 1)))()
-    addr = {i: C.addressof(arena) + 4096 * i for i in range(n)}
-    for o, k in same:
-        addr[o] = addr[k]
-    params, ndims = (C.c_void_p * n)(), (C.c_int * n)()
-    shapes, dtypes = (C.POINTER(C.c_int64) * n)(), (C.c_char_p * n)()
-    keep = []
-    for i in range(n):
-        params[i] = None if ops[i].null else addr[i]
-        shp = [] if ops[i].null else list(ops[i].shape)
-        ndims[i] = len(shp)
-        keep.append((C.c_int64 * max(len(shp), 1))(*shp))
-        shapes[i] = C.cast(keep[-1], C.POINTER(C.c_int64))
-        dtypes[i] = None if ops[i].null else ops[i].dtype.encode()
-    extra = None if call.case.extra is None else C.byref(call.case.extra)
-    return getattr(_lib_handle(), call.case.sym)(n, params, ndims, shapes, dtypes, None, extra)
-
-
-def _attr(name, value):
-    return lambda c: setattr(c.extra, name, value)
-
-
-def _shape(i, shp, dtype=F):
-    def edit(c):
-        c.operands[i] = T(shp, dtype, c.operands[i].kind)
-    return edit
-
-
-def _both(*edits):
-    def edit(c):
-        for e in edits:
-            e(c)
-    return edit
+    refuse_single_defects("abi_cases_train", case)
 
 
 @pytest.mark.parametrize("tag", ["[pool]", "[workspace]"])
@@ -157,29 +97,29 @@ def test_conv_bwd_semantic_refusals_return_the_documented_codes(tag):
     ARG, SIZE = 2, 4
     case = _case(tag, "md_conv1x1_bwd_weight")
     edits = [
-        _attr("reserved0", 1), _attr("reserved0", -1), _attr("cin", 0), _attr("cin", -8), _attr("cout", 0), _attr("cout", -1),
-        _attr("x_c_off", -8), _attr("dy_c_off", -1),
-        _attr("x_c_off", 16), _attr("cin", 24), _attr("dy_c_off", 6), _attr("cout", 7),            # a channel range outside x / dy
-        _shape(0, (0, 3, 5, 16), B16), _shape(0, (1, 0, 5, 16), B16), _shape(1, (1, 3, 0, 8)),     # no pixel
-        _shape(1, (1, 3, 4, 8)), _shape(1, (2, 3, 5, 8)), _shape(0, (1, 5, 3, 16), B16),           # x and dy over different pixels
-        _shape(2, (2, 64)), _shape(2, (32, 7)), _shape(3, (2,)),                                   # dw / db smaller than the layer
+        attr("reserved0", 1), attr("reserved0", -1), attr("cin", 0), attr("cin", -8), attr("cout", 0), attr("cout", -1),
+        attr("x_c_off", -8), attr("dy_c_off", -1),
+        attr("x_c_off", 16), attr("cin", 24), attr("dy_c_off", 6), attr("cout", 7),            # a channel range outside x / dy
+        shape(0, (0, 3, 5, 16), B16), shape(0, (1, 0, 5, 16), B16), shape(1, (1, 3, 0, 8)),     # no pixel
+        shape(1, (1, 3, 4, 8)), shape(1, (2, 3, 5, 8)), shape(0, (1, 5, 3, 16), B16),           # x and dy over different pixels
+        shape(2, (2, 64)), shape(2, (32, 7)), shape(3, (2,)),                                   # dw / db smaller than the layer
     ]
     for i, e in enumerate(edits):
-        assert _rc(case, e) == ARG, i
+        assert rc(case, e) == ARG, i
     for o, k in ((2, 0), (2, 1), (3, 0), (3, 1), (3, 2)):                                          # an output at another operand's address
-        assert _raw(case, same=[(o, k)]) == ARG, (o, k)
+        assert raw(case, same=[(o, k)]) == ARG, (o, k)
     # the stated limits: each edit keeps every extent consistent, so the limit alone refuses it
-    wide_x = _both(_shape(0, (1, 3, 5, 24), B16), _attr("x_c_off", 0))
-    assert _rc(case, _both(wide_x, _attr("cin", 12))) == SIZE
-    many = _both(_shape(1, (1, 3, 5, 264)), _shape(2, (264, 64)), _shape(3, (264,)), _attr("dy_c_off", 0))
-    assert _rc(case, _both(many, _attr("cout", 257))) == SIZE
-    wide = _both(_shape(0, (1, 3, 5, 1040), B16), _shape(2, (32, 1088)), _attr("x_c_off", 0))
-    assert _rc(case, _both(wide, _attr("cin", 1032))) == SIZE
-    huge = _both(_shape(0, (2 ** 16, 2 ** 15, 1, 16), B16), _shape(1, (2 ** 16, 2 ** 15, 1, 8)))   # P = 2^31
-    assert _raw(case, huge) == SIZE
-    assert _raw(case, _shape(0, (2 ** 16, 2 ** 15, 1, 16), B16)) == ARG                            # (dy no longer matches)
+    wide_x = both(shape(0, (1, 3, 5, 24), B16), attr("x_c_off", 0))
+    assert rc(case, both(wide_x, attr("cin", 12))) == SIZE
+    many = both(shape(1, (1, 3, 5, 264)), shape(2, (264, 64)), shape(3, (264,)), attr("dy_c_off", 0))
+    assert rc(case, both(many, attr("cout", 257))) == SIZE
+    wide = both(shape(0, (1, 3, 5, 1040), B16), shape(2, (32, 1088)), attr("x_c_off", 0))
+    assert rc(case, both(wide, attr("cin", 1032))) == SIZE
+    huge = both(shape(0, (2 ** 16, 2 ** 15, 1, 16), B16), shape(1, (2 ** 16, 2 ** 15, 1, 8)))   # P = 2^31
+    assert raw(case, huge) == SIZE
+    assert raw(case, shape(0, (2 ** 16, 2 ** 15, 1, 16), B16)) == ARG                            # (dy no longer matches)
     if tag == "[workspace]":
-        assert _rc(case, _shape(4, (575,), U8)) == SIZE                                            # one byte short of 4 x 16 x 9
+        assert rc(case, shape(4, (575,), U8)) == SIZE                                            # one byte short of 4 x 16 x 9
 
 
 @pytest.mark.parametrize("tag", ["[sumsq, shadow]", "[no sumsq, no shadow]"])
@@ -189,34 +129,34 @@ def test_adam_semantic_refusals_return_the_documented_codes(tag):
     clip, shadow = not case.operands[1].null, not case.operands[5].null
     nan, inf = float("nan"), float("inf")
     edits = [
-        _attr("reserved0", 1.0), _attr("reserved0", -1e-300), _attr("lr", -1e-3), _attr("lr", nan), _attr("lr", inf), _attr("beta1", 1.0),
-        _attr("beta1", -0.1), _attr("beta2", 1.0), _attr("beta2", nan), _attr("beta1_power", 1.0), _attr("beta2_power", 1.0),
-        _attr("beta1_power", -0.5), _attr("eps", -1e-8), _attr("eps", nan), _attr("weight_decay", inf), _attr("grad_scale", -1.0),
-        _attr("grad_scale", nan), _attr("max_norm", nan),
-        _shape(0, (0,)), _shape(0, (99,)), _shape(2, (101,)), _shape(3, (99,)), _shape(4, (1,)),
+        attr("reserved0", 1.0), attr("reserved0", -1e-300), attr("lr", -1e-3), attr("lr", nan), attr("lr", inf), attr("beta1", 1.0),
+        attr("beta1", -0.1), attr("beta2", 1.0), attr("beta2", nan), attr("beta1_power", 1.0), attr("beta2_power", 1.0),
+        attr("beta1_power", -0.5), attr("eps", -1e-8), attr("eps", nan), attr("weight_decay", inf), attr("grad_scale", -1.0),
+        attr("grad_scale", nan), attr("max_norm", nan),
+        shape(0, (0,)), shape(0, (99,)), shape(2, (101,)), shape(3, (99,)), shape(4, (1,)),
     ]
     if clip:
-        edits += [_attr("max_norm", 0.0), _attr("max_norm", -35.0), _shape(1, (0,), F64)]
+        edits += [attr("max_norm", 0.0), attr("max_norm", -35.0), shape(1, (0,), F64)]
     if shadow:
-        edits += [_shape(5, (101,), B16)]                                                          # ns > n
+        edits += [shape(5, (101,), B16)]                                                          # ns > n
     for i, e in enumerate(edits):
-        assert _rc(case, e) == ARG, i
+        assert rc(case, e) == ARG, i
     if clip:
-        assert _rc(case, _shape(1, (1025,), F64)) == SIZE
-    assert _raw(case, _both(*[_shape(i, (2 ** 31,)) for i in (0, 2, 3, 4)])) == SIZE
+        assert rc(case, shape(1, (1025,), F64)) == SIZE
+    assert raw(case, both(*[shape(i, (2 ** 31,)) for i in (0, 2, 3, 4)])) == SIZE
     pairs = [(2, 0), (3, 0), (4, 0), (3, 2), (4, 2), (4, 3)] + ([(5, 0), (5, 2)] if shadow else []) + ([(2, 1)] if clip else [])
     for o, k in pairs:                                                                             # grad may alias no output, nor two outputs each other
-        assert _raw(case, same=[(o, k)]) == ARG, (o, k)
+        assert raw(case, same=[(o, k)]) == ARG, (o, k)
 
 
 def test_grad_sumsq_semantic_refusals_return_the_documented_codes():
     ARG, SIZE = 2, 4
     for tag in ("[pool]", "[workspace]"):
         case = _case(tag, "md_grad_sumsq")
-        for i, e in enumerate([_shape(0, (0,)), _shape(1, (2,), F64), _shape(1, (0,), F64)]):
-            assert _rc(case, e) == ARG, i
-        assert _raw(case, _shape(0, (2 ** 31,))) == SIZE
-    assert _rc(_case("[workspace]", "md_grad_sumsq"), _shape(2, (7,), U8)) == SIZE
+        for i, e in enumerate([shape(0, (0,)), shape(1, (2,), F64), shape(1, (0,), F64)]):
+            assert rc(case, e) == ARG, i
+        assert raw(case, shape(0, (2 ** 31,))) == SIZE
+    assert rc(_case("[workspace]", "md_grad_sumsq"), shape(2, (7,), U8)) == SIZE
 
 
 # ---------------------------------------------------------------------------------------------------- the reference, transcribed

@@ -1,7 +1,7 @@
 """Scratch sizes have one owner (include/minddet_hip.h "Conventions"): every op that takes a workspace exports a host function
 md_<op>_workspace_bytes, holds a caller's workspace to exactly that number, and Python asks it instead of mirroring a formula.  Without
 a GPU: the functions are pure host code, and a call refused for its workspace never touches a tensor pointer (the dummy-pointer calls of
-tests/test_abi_checks_cpu.py)."""
+tests/abi_derive.py)."""
 import copy
 import ctypes as C
 import glob
@@ -15,11 +15,12 @@ from minddet_amd import _lib, det_ops
 from tests import (abi_cases, abi_cases_cn, abi_cases_cnaug, abi_cases_cp, abi_cases_cpaug, abi_cases_cploss, abi_cases_cpsweeps,
                    abi_cases_cptargets, abi_cases_kitti, abi_cases_pcaug, abi_cases_points, abi_cases_pploss, abi_cases_ppreader)
 from tests.abi_cases import F, U8, T
-from tests.pcaug_cases import Call64
+from tests.abi_derive import Call
+from tests.abi_header import defines
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADERS = {os.path.basename(p): open(p).read() for p in sorted(glob.glob(os.path.join(ROOT, "include", "*.h")))}
-DEFINES = {k: int(v) for txt in HEADERS.values() for k, v in re.findall(r"^#define (MD_\w+) (\d+)\b", txt, flags=re.M)}
+DEFINES = defines(*HEADERS.values())
 DECLARED = {name: args.count("int64_t") for txt in HEADERS.values()
             for name, args in re.findall(r"^int64_t (md_\w+)_workspace_bytes\(([^)]*)\);", txt, flags=re.M)}
 
@@ -234,7 +235,7 @@ def _with_workspace(case, nbytes):
     ops = list(case.operands[:at])
     ops += [T((1,), F, "opt", null=True) for _ in range(at - len(ops))]
     c.operands, c.nparam = ops + [T((nbytes,), U8, "opt", "free")], case.nparam
-    return Call64(c)
+    return Call(c)
 
 
 def _need(case):
